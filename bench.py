@@ -11,9 +11,19 @@ halo in front), so the job scores N*F frames per step.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the stream it runs on) and `cpu_baseline` (the CPU oracle = scalar port of the
-libvmaf float extractors, timed on a bounded sample of the same frames; N=1 only).
+Prints ONE JSON line on rank 0: `value` (frames/s over the timed steps), `ms_per_step` and the pooled score.
+A plain run does only that: set up, warm up, time `--steps` steps, write `--dump-outputs`, print.
+
+--full adds everything else the benchmark measures: `roofline` (dominant kernel, HIP-event timed on the
+stream it runs on), per-kernel times from one extra untimed pass, `cpu_baseline` (the CPU oracle = scalar
+port of the libvmaf float extractors, timed on a bounded sample of the same frames; N=1 only), the other
+BASELINE workloads, the end-to-end and bookend legs and the libvmaf side-by-side.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0: the whole job) as float64
+.npy files: features.npy [frames, 20] (record slots 0..19: VIF / ADM numerator and denominator per scale,
+motion, SSIM Y U V), sse.npy [frames, 3] (PSNR SSE Y U V; zero when the workload has no PSNR), vmaf.npy
+[frames] and pooled.npy [min, max, mean, harmonic_mean].  The clip is seeded: the same arguments give the
+same inputs on every run.
 """
 from __future__ import annotations
 
@@ -61,7 +71,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-frames", type=int, default=0, help="0: sized for ~12 s of CPU work")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: min(16, host cores) -- the 1-GPU share of the box")
-    ap.add_argument("--no-events", action="store_true", help="skip per-kernel HIP-event timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline + per-kernel times, CPU baseline, other "
+                         "workloads, end-to-end and bookend legs, libvmaf side-by-side")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records and scores to DIR/*.npy (float64)")
+    ap.add_argument("--no-events", action="store_true", help="with --full: skip per-kernel HIP-event timing")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="finish every clip (collect, score, pool) before the next one is queued (A/B partner of the default)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -77,6 +92,9 @@ def main():
                          "default f32 path")
     ap.add_argument("--stages", action="store_true", help="flushed stage markers on stderr (also PQA_BENCH_STAGES=1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    events = args.full and not args.no_events
     global _STAGES
     _STAGES = _STAGES or args.stages
 
@@ -206,7 +224,7 @@ def main():
     for i in range(args.warmup):
         step()
         _stage(f"warm-up step {i + 1}/{args.warmup} done")
-    if not args.no_events:
+    if events:
         eng.profile_enable([0])       # HIP events around the dominant kernel only (vif_stat_s0) while timing
     barrier()
     t0 = time.perf_counter()
@@ -226,10 +244,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     _stage("timed region closed")
-    prof = eng.profile_read() if not args.no_events else {}
+    timed = dict(result)              # the last timed step's outputs (the breakdown pass below overwrites `result`)
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, timed)
+        _stage(f"outputs written to {args.dump_outputs}")
+    prof = eng.profile_read() if events else {}
     _stage("kernel events read")
     breakdown = {}
-    if not args.no_events:
+    if events:
         eng.profile_enable(True)      # one extra, untimed pass with every kernel timed, for the breakdown
         step()
         breakdown = eng.profile_read()
@@ -261,9 +283,9 @@ def main():
                        "frames_per_gpu": F, "frames_total": total, "batch": args.batch, "frames_per_launch": per_launch,
                        "clips_pipelined": not args.no_pipeline,
                        "parallelism": f"frame-shard x{world}, 1-frame motion halo, all-gather of records + of scores"},
-            "pooled_vmaf_mean": round(result["pooled"]["mean"], 6),
+            "pooled_vmaf_mean": round(timed["pooled"]["mean"], 6),
         }
-        k = prof.get("vif_stat_s0")
+        k = prof.get("vif_stat_s0")   # events were only recorded with --full
         if k and k["launches"]:
             avg_ms = k["ms"] / k["launches"]
             frames_per_launch = k["frames"] / k["launches"]
@@ -353,31 +375,47 @@ def main():
                                        "traffic_source": ca.get("traffic_source"),
                                        "timed": "breakdown pass (one stream, every kernel event-timed), not the timed region"}
 
-        if world == 1 and not args.no_cpu_baseline and not args.fixed_point:  # the CPU leg times the float restatement
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.fixed_point:  # the CPU leg times the float restatement
             threads = args.cpu_threads or min(16, os.cpu_count() or 1)
             n_sample = args.cpu_sample_frames or max(2, min(F, threads * max(1, int(12.0 / (w * h * 2.0e-7)))))
             out["cpu_baseline"] = _cpu_baseline(ref_t, dis_t, halo, bpc, w, h, n_sample, threads,
-                                                result["records"], model, prefix)
-        if world == 1 and args.workload == "2160p" and not args.fixed_point and not args.no_other_configs:
+                                                timed["records"], model, prefix)
+        if args.full and world == 1 and args.workload == "2160p" and not args.fixed_point and not args.no_other_configs:
             out["other_configs"] = _other_configs(args)
-        if world == 1 and args.workload == "2160p" and not args.fixed_point and not args.no_e2e:
+        if args.full and world == 1 and args.workload == "2160p" and not args.fixed_point and not args.no_e2e:
             out["e2e"] = _e2e_leg()
             out["bookend"] = _bookend_leg()
-        probe = probe_libvmaf()
-        if probe["ffmpeg_has_libvmaf"] and world == 1 and not args.no_cpu_baseline:
-            n_lv = min(F, 60 if w * h > 1920 * 1080 else 150)
-            out["libvmaf_side_by_side"] = {"probe": probe, **_libvmaf_leg(probe, ref_t, dis_t, halo, bpc, w, h, model_name,
-                                                                           result["vmaf"], n_lv)}
-        else:
-            out["libvmaf_side_by_side"] = {"probe": probe,
-                                           "result": "not run: no ffmpeg with the libvmaf filter on this box (probed PATH and "
-                                                     "`ffmpeg -filters`; a `vmaf` CLI alone is reported but not driven); "
-                                                     "cpu_baseline.kind = port, parity against libvmaf stays unpinned"
-                                                     if not probe["ffmpeg_has_libvmaf"] else "not run (N > 1 or --no-cpu-baseline)"}
+        if args.full:
+            probe = probe_libvmaf()
+            if probe["ffmpeg_has_libvmaf"] and world == 1 and not args.no_cpu_baseline:
+                n_lv = min(F, 60 if w * h > 1920 * 1080 else 150)
+                out["libvmaf_side_by_side"] = {"probe": probe, **_libvmaf_leg(probe, ref_t, dis_t, halo, bpc, w, h, model_name,
+                                                                               timed["vmaf"], n_lv)}
+            else:
+                out["libvmaf_side_by_side"] = {"probe": probe,
+                                               "result": "not run: no ffmpeg with the libvmaf filter on this host (probed PATH and "
+                                                         "`ffmpeg -filters`; a `vmaf` CLI alone is reported but not driven); "
+                                                         "cpu_baseline.kind = port, parity against libvmaf stays unpinned"
+                                                         if not probe["ffmpeg_has_libvmaf"] else "not run (N > 1 or --no-cpu-baseline)"}
         print(json.dumps(out), flush=True)
     eng.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def _dump_outputs(d: str, res: dict):
+    """--dump-outputs: the records, per-frame scores and pooled score of one step as float64 .npy files (module docstring);
+    192 B per frame, so a whole clip stays far below 64 MB."""
+    from pqa2_amd import _native as N
+    from pqa2_amd.engine import sse_from_records
+    os.makedirs(d, exist_ok=True)
+    rec = res["records"]
+    arrays = {"features": rec[:, :N.REC_SSE],
+              "sse": sse_from_records(rec).astype(np.float64),   # u64 bit patterns in the record; exact in f64 below 2**53
+              "vmaf": res["vmaf"],
+              "pooled": [res["pooled"][k] for k in ("min", "max", "mean", "harmonic_mean")]}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _other_configs(args):
@@ -388,7 +426,7 @@ def _other_configs(args):
     res = {}
     for wl in ("1080p", "2160p10"):
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(max(3, args.steps)),
-               "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-other-configs", "--no-e2e"]
+               "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-e2e"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             d = json.loads(r.stdout.strip().splitlines()[-1])

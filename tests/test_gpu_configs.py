@@ -375,6 +375,37 @@ def test_bench_ranks_sharing_the_gpu_score_the_clip_like_one_rank():
         assert d["pooled_vmaf_mean"] == lines[1]["pooled_vmaf_mean"], (ranks, d["pooled_vmaf_mean"], lines[1]["pooled_vmaf_mean"])
 
 
+def test_bench_plain_line_full_legs_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline alone (no roofline, per-kernel or CPU legs); --full adds the roofline and
+    per-kernel times; --dump-outputs writes the last timed step's records and scores, the same in both runs (seeded clip)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    common = ["--steps", "3", "--warmup", "1", "--workload", "1080p", "--frames", "40", "--batch", "20"]
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--dump-outputs", str(tmp_path / tag)] + common + extra
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[tag] = json.loads(r.stdout.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["steps"] == 3 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 40 * 1e3 / d["ms_per_step"]) <= 1e-2 * d["value"]   # ms rounded to 1 us
+    assert not {"roofline", "kernel_ms_per_frame", "cpu_baseline", "libvmaf_side_by_side"} & set(plain)
+    assert "roofline" in full and "kernel_ms_per_frame" in full and "libvmaf_side_by_side" in full
+    shapes = {"features": (40, 20), "sse": (40, 3), "vmaf": (40,), "pooled": (4,)}
+    for name, shape in shapes.items():
+        a, b = (np.load(tmp_path / tag / f"{name}.npy") for tag in ("plain", "full"))
+        assert a.dtype == np.float64 and a.shape == shape, (name, a.dtype, a.shape)
+        np.testing.assert_array_equal(a, b, err_msg=name)
+    vmaf = np.load(tmp_path / "plain" / "vmaf.npy")
+    assert np.all(np.isfinite(vmaf)) and round(float(vmaf.mean()), 6) == plain["pooled_vmaf_mean"]
+
+
 @pytest.mark.skipif(_n_gpus() < 2, reason="needs two GPUs: arms itself on a multi-GPU box (the 1-GPU lease skips it)")
 def test_bench_two_gpus_on_rccl_prints_a_line():
     """bench.py --gpus 2 exactly as the driver launches it (torch.distributed.run, one rank per GPU, RCCL): one JSON line

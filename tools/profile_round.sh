@@ -24,7 +24,7 @@ T="timeout -k 10 ${PQA_PROF_TIMEOUT:-75}"
 # 96 frames = one launch at 2160p (automatic batch 97), two of 48 at 2160p10 (frames per launch is then exact); three passes of
 # the clip (1 warm-up + 2 steps), short, so a profiler stall costs little
 FRAMES=96
-B="$R/bench.py --workload $WL --steps 2 --warmup 1 --frames $FRAMES --no-cpu-baseline --no-other-configs --no-e2e"
+B="$R/bench.py --full --workload $WL --steps 2 --warmup 1 --frames $FRAMES --no-cpu-baseline --no-other-configs --no-e2e"
 $T rocprofv3 --kernel-trace --stats --output-format csv -d "$RAW/stats" -- python3 $B > "$OUT/${TAG}_bench_${WL}_under_rocprof.json" 2> "$RAW/stats.err" || failed stats
 keep stats
 say "stats pass done"
