@@ -54,7 +54,16 @@ enum {
   PQA_FEAT_PSNR = 1u << 3,   /* FFmpeg psnr filter: per-plane SSE   (:1027-1034)                  */
   PQA_FEAT_SSIM = 1u << 4,   /* FFmpeg ssim filter: per-plane SSIM  (:1057-1064)                  */
   PQA_FEAT_VMAF = PQA_FEAT_VIF | PQA_FEAT_ADM | PQA_FEAT_MOTION,
-  PQA_FEAT_ALL = PQA_FEAT_VMAF | PQA_FEAT_PSNR | PQA_FEAT_SSIM
+  PQA_FEAT_ALL = PQA_FEAT_VMAF | PQA_FEAT_PSNR | PQA_FEAT_SSIM,  /* stays 31: the features of the 24-double record */
+  /* libvmaf's SSIM family (`feature=name=float_ssim` / `float_ms_ssim`, the filter's ssim=1 / ms_ssim=1): luma only, f32,
+   * results in the EXTENSION record (PQA_EXT_*, pqa_collect_ext), never in the 24-double record.  Both run on the frames
+   * that get VIF / ADM (n_subsample); the extension slots of the other frames hold NaN.  Geometry limits: float_ssim needs
+   * the decimated plane (ceil(w / f) x ceil(h / f), f = max(1, round(min(w, h) / 256))) to be >= 11 in both directions,
+   * float_ms_ssim needs its 5th scale (ceil-halved four times) >= 11, i.e. w, h >= 161; pqa_create returns PQA_EINVAL
+   * naming the feature otherwise (float_ssim fits every size pqa_create accepts, w, h >= 16).  Definition and its unpinned items: DESIGN.md sections 1 and 5. */
+  PQA_FEAT_FLOAT_SSIM = 1u << 5,
+  PQA_FEAT_MS_SSIM = 1u << 6,
+  PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -68,6 +77,20 @@ enum {
   PQA_REC_SSE = 20,     /* [3] FFmpeg psnr SSE Y, U, V: uint64 bit-cast into the slot (exact)   */
   PQA_REC_RESERVED = 23,
   PQA_RECORD_DOUBLES = 24
+};
+
+/* One EXTENSION record = PQA_EXT_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and wrap) when
+ * the context runs PQA_FEAT_FLOAT_SSIM or PQA_FEAT_MS_SSIM.  Slots of a feature the context does not run, and of frames
+ * that get no spatial features (n_subsample), are NaN; so are the reserved slots. */
+enum {
+  PQA_EXT_FLOAT_SSIM = 0,     /*     float_ssim: mean of l*c*s over the (decimated) map                */
+  PQA_EXT_FLOAT_SSIM_LCS = 1, /* [3] its means of l, c, s                                               */
+  PQA_EXT_MS_SSIM = 4,        /*     float_ms_ssim = l4^0.1333 * prod_j c_j^w_j * s_j^w_j (in double)    */
+  PQA_EXT_MS_SSIM_L = 5,      /* [5] mean of l per scale 0..4                                           */
+  PQA_EXT_MS_SSIM_C = 10,     /* [5] mean of c per scale                                                */
+  PQA_EXT_MS_SSIM_S = 15,     /* [5] mean of s per scale                                                */
+  PQA_EXT_RESERVED = 20,      /* [4]                                                                    */
+  PQA_EXT_DOUBLES = 24
 };
 
 typedef struct pqa_config {
@@ -120,6 +143,7 @@ typedef struct pqa_ctx pqa_ctx;
 /* Library / record introspection. */
 PQA_API const char* pqa_version(void);
 PQA_API int pqa_record_doubles(void);
+PQA_API int pqa_ext_doubles(void);
 
 /* Fill cfg with defaults (8-bit 4:2:0, PQA_FEAT_VMAF, gain limits 100). */
 PQA_API void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height);
@@ -209,6 +233,12 @@ PQA_API int pqa_flush(pqa_ctx* ctx);
  * slot becomes free for frame index + k * result_capacity.  Replaces reading the libvmaf JSON log / stats files. */
 PQA_API int pqa_collect(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records);
 
+/* pqa_collect with the extension records: exactly its contract (the same waits, the same PQA_ESTATE rules; the frames are
+ * marked collected), and in addition ext[count][PQA_EXT_DOUBLES] receives the extension rows of the same frames.  ext may
+ * be NULL.  A context that runs neither PQA_FEAT_FLOAT_SSIM nor PQA_FEAT_MS_SSIM returns all-NaN rows.
+ * pqa_collect(c, f, n, r) is pqa_collect_ext(c, f, n, r, NULL). */
+PQA_API int pqa_collect_ext(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext);
+
 /* Wait for all submitted work without collecting. */
 PQA_API int pqa_sync(pqa_ctx* ctx);
 
@@ -250,10 +280,11 @@ PQA_API int pqa_set_luma_gray(pqa_ctx* ctx, uint32_t mode);
 /* Measurement hooks (bench.py): HIP-event timing of individual kernels on the context's stream.
  * kernel ids: 0..3 vif_stat scale s (each also produces the next scale's planes), 4..6 reserved,
  * 7..10 adm scale s,
- * 11 motion, 12 sse, 13 ssim, 14 finalize.
+ * 11 motion, 12 sse, 13 ssim, 14 finalize, 15 ms_ssim (all five scales, their decimations and the extension epilogue),
+ * 16 float_ssim.
  * pqa_profile_enable(ctx, 0) stops, (ctx, 1) times every kernel, (ctx, mask << 1) only the kernels whose bit
  * is set in mask (event records between kernels are not free: ~10 % of a step when every kernel is timed). */
-enum { PQA_PROF_KERNELS = 15 };
+enum { PQA_PROF_KERNELS = 17 };
 PQA_API int pqa_profile_enable(pqa_ctx* ctx, int on);
 PQA_API int pqa_profile_read(pqa_ctx* ctx, int kernel_id, double* total_ms, uint64_t* launches, uint64_t* frames);
 PQA_API const char* pqa_profile_kernel_name(int kernel_id);

@@ -13,18 +13,23 @@ LIB_PATH = os.environ.get("PQA_LIB_PATH") or os.path.join(_HERE, "csrc", "libpqa
 PQA_OK, PQA_EINVAL, PQA_EDEVICE, PQA_ENOMEM, PQA_ECANCELLED, PQA_ESTATE = 0, -1, -2, -3, -4, -5
 FEAT_VIF, FEAT_ADM, FEAT_MOTION, FEAT_PSNR, FEAT_SSIM = 1, 2, 4, 8, 16
 FEAT_VMAF = FEAT_VIF | FEAT_ADM | FEAT_MOTION
-FEAT_ALL = FEAT_VMAF | FEAT_PSNR | FEAT_SSIM
+FEAT_ALL = FEAT_VMAF | FEAT_PSNR | FEAT_SSIM   # stays 31: the features of the 24-double record
+FEAT_FLOAT_SSIM, FEAT_MS_SSIM = 32, 64          # libvmaf float_ssim / float_ms_ssim: results in the extension record
+FEAT_KNOWN = FEAT_ALL | FEAT_FLOAT_SSIM | FEAT_MS_SSIM
 VIF_BORDER_FLOAT, VIF_BORDER_INTEGER = 0, 1  # pqa_config.vif_border (include/pqa_vmaf.h)
 FIXED_VIF, FIXED_MOTION, FIXED_ADM, FIXED_ALL = 1, 2, 4, 7   # pqa_config.fixed_point mask
 REC_VIF_NUM, REC_VIF_DEN, REC_ADM_NUM, REC_ADM_DEN, REC_MOTION, REC_SSIM, REC_SSE = 0, 4, 8, 12, 16, 17, 20
 RECORD_DOUBLES = 24
-PROF_KERNELS = 15
+# extension record (pqa_collect_ext): float_ssim, its l/c/s means, float_ms_ssim, per-scale l/c/s means; NaN where not run
+EXT_FLOAT_SSIM, EXT_FLOAT_SSIM_LCS, EXT_MS_SSIM, EXT_MS_SSIM_L, EXT_MS_SSIM_C, EXT_MS_SSIM_S, EXT_RESERVED = 0, 1, 4, 5, 10, 15, 20
+EXT_DOUBLES = 24
+PROF_KERNELS = 17
 GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 
 # every symbol include/pqa_vmaf.h declares
 EXPORTS = [
-    "pqa_version", "pqa_record_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
-    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_flush", "pqa_collect", "pqa_sync",
+    "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
+    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_sync",
     "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape",
@@ -119,6 +124,8 @@ def load():
     lib.pqa_set_motion_halo.argtypes = [vp, vp, i64]
     lib.pqa_flush.argtypes = [vp]
     lib.pqa_collect.argtypes = [vp, i64, i32, vp]
+    lib.pqa_collect_ext.argtypes = [vp, i64, i32, vp, vp]
+    lib.pqa_ext_doubles.restype = C.c_int
     lib.pqa_sync.argtypes = [vp]
     lib.pqa_cancel.argtypes = [vp]
     lib.pqa_luma_stats_device.argtypes = [vp, vp, i64, i64, i32, C.c_uint32, vp]
@@ -134,5 +141,6 @@ def load():
     lib.pqa_profile_kernel_name.argtypes = [C.c_int]
     lib.pqa_profile_kernel_name.restype = C.c_char_p
     assert lib.pqa_record_doubles() == RECORD_DOUBLES
+    assert lib.pqa_ext_doubles() == EXT_DOUBLES
     _lib = lib
     return lib

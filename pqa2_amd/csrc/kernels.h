@@ -197,4 +197,36 @@ struct FinalizeArgs {
 };
 hipError_t launch_finalize(hipStream_t stream, const FinalizeArgs& args);
 
+// ---- SSIM family: libvmaf float_ssim / float_ms_ssim (ssim_family.hip) ---------------------------------------------------
+constexpr int kSsfTileW = 64, kSsfTileH = 32;   // output tile of the map kernel
+constexpr int kMsScales = 5;
+// tiles of the (w - 10) x (h - 10) SSIM map of a w x h plane (0: the map is empty)
+int ssf_tiles(int w, int h);
+// float_ssim's decimation factor: max(1, round(min(w, h) / 256))
+int ssf_decimation(int w, int h);
+// One SSIM map (11 x 11 Gaussian, valid region).  box > 1: the map is formed on the box-decimated planes
+// (ceil(src_w / box) x ceil(src_h / box), float_ssim); box == 1: on the planes themselves (u8 / u16 samples are scaled by
+// inv_scale, f32 planes are taken as they are).  partials: [n_frames][ssf_tiles][4] doubles {sum l, sum c, sum s, sum l*c*s}.
+// down_ref / down_dis (base non-null; box == 1 and u8 / u16 planes only): the same launch also writes the next MS-SSIM scale,
+// as launch_ssf_down would, bit for bit.
+hipError_t launch_ssf_map(hipStream_t stream, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames, int src_w, int src_h,
+                          int box, float inv_scale, double* partials, MutPlaneRun down_ref = MutPlaneRun{nullptr, 0, 0},
+                          MutPlaneRun down_dis = MutPlaneRun{nullptr, 0, 0});
+// 9/7 low-pass and 2:1 decimation of a w x h plane pair into ceil(w/2) x ceil(h/2) f32 planes (next MS-SSIM scale).
+hipError_t launch_ssf_down(hipStream_t stream, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames, int w, int h,
+                           float inv_scale, MutPlaneRun out_ref, MutPlaneRun out_dis);
+// Per-frame epilogue into the extension ring (PQA_EXT_* layout): tile sums in a fixed order, means, the MS-SSIM product in
+// double.  A null fs_part / ms_part[0] leaves that feature's slots NaN.
+struct SsfFinalizeArgs {
+  int n_frames;
+  double* ext;                 // [capacity][ext_stride] ring
+  int ext_stride;
+  int slot_base, slot_step, capacity;   // ring row of batch frame f = (slot_base + f * slot_step) % capacity
+  const double* fs_part;   int fs_tiles;   double fs_norm;      // 1 / map pixels
+  const double* ms_part[kMsScales];   int ms_tiles[kMsScales];   double ms_norm[kMsScales];
+};
+hipError_t launch_ssf_finalize(hipStream_t stream, const SsfFinalizeArgs& args);
+// NaN into n_rows consecutive ring rows starting at slot_base (frames that get no spatial features, fresh rings)
+hipError_t launch_ext_fill_nan(hipStream_t stream, double* ext, int slot_base, int n_rows, int capacity, int stride);
+
 }  // namespace pqa

@@ -120,6 +120,14 @@ struct pqa_ctx {
   int ssim_tiles_n[3] = {};
   double ssim_norm[3] = {};
   double* records = nullptr;
+  // SSIM family (PQA_FEAT_FLOAT_SSIM / PQA_FEAT_MS_SSIM; ssim_family.hip): nothing is allocated unless one of the bits is set
+  double* ext = nullptr;             // [capacity][PQA_EXT_DOUBLES] ring beside `records`
+  Level ms_lv[kMsScales];            // MS-SSIM scales 1..4: f32 planes for ssf_sb frames
+  double* ms_part[kMsScales] = {};   // [ssf_sb][tiles][4] per scale
+  int ms_tiles[kMsScales] = {};
+  double* fs_part = nullptr;         // float_ssim: [ssf_sb][tiles][4]
+  int fs_tiles = 0, fs_box = 1;
+  int ssf_sb = 0;                    // frames per pass through the pyramid (bounds its memory at 2160p)
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -207,7 +215,7 @@ int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static const char* kProfNames[PQA_PROF_KERNELS] = {
     "vif_stat_s0", "vif_stat_s1", "vif_stat_s2", "vif_stat_s3", "reserved4", "reserved5",
     "reserved6", "adm_scale_s0", "adm_scale_s1", "adm_scale_s2", "adm_scale_s3", "motion", "sse",
-    "ssim", "finalize"};
+    "ssim", "finalize", "ms_ssim", "float_ssim"};
 
 struct ProfScope {
   pqa_ctx* c;
@@ -509,6 +517,60 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
       const PlaneRun b{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
       HIPCHK(c, launch_ssim(st_misc, c->elem, a, b, n, c->pw[p], c->ph[p], (1 << c->cfg.bit_depth) - 1, c->ssim_part[p],
                             sse_t[p] ? c->sse_tile_part[p] : nullptr));
+    }
+  }
+
+  if ((feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM))) {
+    // the SSIM family on the frames that get spatial features, ssf_sb at a time (the MS-SSIM pyramid is sized for that many);
+    // the extension rows of the other frames are NaN
+    if (k > 1) HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext, (int)(first % c->capacity), n, c->capacity, PQA_EXT_DOUBLES));
+    const bool fs = feat & PQA_FEAT_FLOAT_SSIM, ms = feat & PQA_FEAT_MS_SSIM;
+    for (int s0 = 0; s0 < sp_n; s0 += c->ssf_sb) {
+      const int m = sp_n - s0 < c->ssf_sb ? sp_n - s0 : c->ssf_sb;
+      const PlaneRun r0{(const uint8_t*)rYs.base + (int64_t)s0 * rYs.frame_pitch * es, rYs.row_pitch, rYs.frame_pitch};
+      const PlaneRun d0{(const uint8_t*)dYs.base + (int64_t)s0 * dYs.frame_pitch * es, dYs.row_pitch, dYs.frame_pitch};
+      SsfFinalizeArgs sa{};
+      sa.n_frames = m;
+      sa.ext = c->ext;
+      sa.ext_stride = PQA_EXT_DOUBLES;
+      sa.slot_base = (int)((first + e0 + (int64_t)s0 * k) % c->capacity);
+      sa.slot_step = k;
+      sa.capacity = c->capacity;
+      if (fs) {
+        sa.fs_part = c->fs_part; sa.fs_tiles = c->fs_tiles;
+        const int dw = (w + c->fs_box - 1) / c->fs_box, dh = (h + c->fs_box - 1) / c->fs_box;
+        sa.fs_norm = 1.0 / ((double)(dw - 10) * (dh - 10));
+        ProfScope ps(c, 16, m, st_misc);
+        HIPCHK(c, launch_ssf_map(st_misc, c->elem, r0, d0, m, w, h, c->fs_box, c->inv_scale, c->fs_part));
+        if (!ms) HIPCHK(c, launch_ssf_finalize(st_misc, sa));
+      }
+      if (ms) {
+        ProfScope ps(c, 15, m, st_misc);
+        PlaneRun cr = r0, cd = d0;
+        Elem ce = c->elem;
+        for (int j = 0; j < kMsScales; ++j) {
+          const Level& L = c->ms_lv[j];
+          sa.ms_part[j] = c->ms_part[j]; sa.ms_tiles[j] = c->ms_tiles[j];
+          sa.ms_norm[j] = 1.0 / ((double)(L.w - 10) * (L.h - 10));
+          if (j == 0) {   // scale 0 writes scale 1's planes in the same launch (the caller's pair is read once)
+            const Level& N = c->ms_lv[1];
+            HIPCHK(c, launch_ssf_map(st_misc, ce, cr, cd, m, L.w, L.h, 1, c->inv_scale, c->ms_part[0],
+                                     MutPlaneRun{N.ref, N.pitch, N.frame_pitch}, MutPlaneRun{N.dis, N.pitch, N.frame_pitch}));
+          } else {
+            HIPCHK(c, launch_ssf_map(st_misc, ce, cr, cd, m, L.w, L.h, 1, c->inv_scale, c->ms_part[j]));
+          }
+          if (j + 1 < kMsScales) {
+            const Level& N = c->ms_lv[j + 1];
+            if (j > 0)
+              HIPCHK(c, launch_ssf_down(st_misc, ce, cr, cd, m, L.w, L.h, c->inv_scale, MutPlaneRun{N.ref, N.pitch, N.frame_pitch},
+                                        MutPlaneRun{N.dis, N.pitch, N.frame_pitch}));
+            cr = PlaneRun{N.ref, N.pitch, N.frame_pitch};
+            cd = PlaneRun{N.dis, N.pitch, N.frame_pitch};
+            ce = ELEM_F32;
+          }
+        }
+        HIPCHK(c, launch_ssf_finalize(st_misc, sa));
+      }
     }
   }
 
@@ -823,6 +885,7 @@ extern "C" {
 
 const char* pqa_version(void) { return "pqa_vmaf 0.2.0 (gfx950; libvmaf-float VIF/ADM/motion, FFmpeg psnr/ssim; VIF scale 0 on the f16 matrix cores)"; }
 int pqa_record_doubles(void) { return PQA_RECORD_DOUBLES; }
+int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
 
 void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
   if (!cfg) return;
@@ -850,8 +913,21 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     return fail(nullptr, PQA_EINVAL, "unsupported bit depth %u (8, 10, 12)", cfg->bit_depth);
   if (cfg->n_planes != 1 && cfg->n_planes != 3) return fail(nullptr, PQA_EINVAL, "n_planes must be 1 or 3");
   if (cfg->chroma_hshift > 2 || cfg->chroma_vshift > 2) return fail(nullptr, PQA_EINVAL, "bad chroma shift");
-  if ((cfg->features & ~(uint32_t)PQA_FEAT_ALL) || cfg->features == 0)
+  if ((cfg->features & ~(uint32_t)PQA_FEAT_KNOWN) || cfg->features == 0)
     return fail(nullptr, PQA_EINVAL, "bad feature mask 0x%x", cfg->features);
+  if (cfg->features & PQA_FEAT_FLOAT_SSIM) {   // the decimated plane must hold one 11 x 11 window
+    const int f = ssf_decimation((int)cfg->width, (int)cfg->height);
+    if (ssf_tiles(((int)cfg->width + f - 1) / f, ((int)cfg->height + f - 1) / f) == 0)
+      return fail(nullptr, PQA_EINVAL, "frame %ux%u too small for float_ssim (decimated by %d it must be >= 11x11)", cfg->width,
+                  cfg->height, f);
+  }
+  if (cfg->features & PQA_FEAT_MS_SSIM) {      // the 5th scale must hold one 11 x 11 window
+    int sw = (int)cfg->width, sh = (int)cfg->height;
+    for (int j = 1; j < kMsScales; ++j) { sw = (sw + 1) / 2; sh = (sh + 1) / 2; }
+    if (ssf_tiles(sw, sh) == 0)
+      return fail(nullptr, PQA_EINVAL, "frame %ux%u too small for float_ms_ssim (5th scale %dx%d, needs >= 11x11: w, h >= 161)",
+                  cfg->width, cfg->height, sw, sh);
+  }
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
   int ndev = 0;
@@ -1021,6 +1097,42 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     CREATE_HIP(hipMemsetAsync(c->adm_fx_acc, 0, (size_t)c->capacity * 24 * sizeof(long long), c->stream));
   }
   CREATE_TRY(dev_alloc(c, &c->records, (size_t)c->capacity * PQA_RECORD_DOUBLES));
+  if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM)) {
+    // MS-SSIM scales 1..4 hold ~5.3 bytes per luma sample and frame (22 MB per 2160p frame): the pyramid is walked ssf_sb
+    // frames at a time, at most 320 MiB of planes
+    size_t per_frame = 0;
+    int sw = w, sh = h;
+    for (int j = 0; j < kMsScales; ++j) {
+      Level& L = c->ms_lv[j];
+      L.w = sw; L.h = sh;
+      if (j > 0) { L.pitch = round_up(sw, 16); L.frame_pitch = L.pitch * sh; per_frame += (size_t)L.frame_pitch * 2 * sizeof(float); }
+      c->ms_tiles[j] = ssf_tiles(sw, sh);
+      sw = (sw + 1) / 2; sh = (sh + 1) / 2;
+    }
+    c->ssf_sb = B;
+    if ((cfg->features & PQA_FEAT_MS_SSIM) && per_frame) {
+      const int64_t sb = (int64_t)(320ll << 20) / (int64_t)per_frame;
+      c->ssf_sb = (int)(sb < 1 ? 1 : sb < B ? sb : B);
+    }
+    const int SB = c->ssf_sb;
+    if (cfg->features & PQA_FEAT_MS_SSIM) {
+      for (int j = 0; j < kMsScales; ++j) {
+        Level& L = c->ms_lv[j];
+        if (j > 0) {
+          CREATE_TRY(dev_alloc(c, &L.ref, (size_t)L.frame_pitch * SB));
+          CREATE_TRY(dev_alloc(c, &L.dis, (size_t)L.frame_pitch * SB));
+        }
+        CREATE_TRY(dev_alloc(c, &c->ms_part[j], (size_t)c->ms_tiles[j] * 4 * SB));
+      }
+    }
+    if (cfg->features & PQA_FEAT_FLOAT_SSIM) {
+      c->fs_box = ssf_decimation(w, h);
+      c->fs_tiles = ssf_tiles((w + c->fs_box - 1) / c->fs_box, (h + c->fs_box - 1) / c->fs_box);
+      CREATE_TRY(dev_alloc(c, &c->fs_part, (size_t)c->fs_tiles * 4 * SB));
+    }
+    CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
+    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext, 0, c->capacity, c->capacity, PQA_EXT_DOUBLES));
+  }
   CREATE_HIP(hipMemsetAsync(c->records, 0, (size_t)c->capacity * PQA_RECORD_DOUBLES * sizeof(double), c->stream));
   CREATE_HIP(hipStreamSynchronize(c->stream));
 #undef CREATE_TRY
@@ -1308,6 +1420,10 @@ int pqa_sync(pqa_ctx* c) {
 }
 
 int pqa_collect(pqa_ctx* c, int64_t first_index, int32_t count, double* records) {
+  return pqa_collect_ext(c, first_index, count, records, nullptr);
+}
+
+int pqa_collect_ext(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext) {
   if (!c) return PQA_EINVAL;
   if (count < 0 || first_index < 0 || (count > 0 && !records)) return fail(c, PQA_EINVAL, "bad argument");
   if (count > c->capacity) return fail(c, PQA_ESTATE, "count %d exceeds result_capacity %d", count, c->capacity);
@@ -1353,6 +1469,12 @@ int pqa_collect(pqa_ctx* c, int64_t first_index, int32_t count, double* records)
           double* rec = records + (size_t)(done + f) * PQA_RECORD_DOUBLES;
           adm_fixed_epilogue(c->adm_fx[s], &acc[(size_t)f * 24 + s * 6], &rec[PQA_REC_ADM_NUM + s], &rec[PQA_REC_ADM_DEN + s]);
         }
+    }
+    if (ext && c->ext) {   // the extension ring has the record ring's slots
+      HIPCHK(c, hipMemcpy(ext + (size_t)done * PQA_EXT_DOUBLES, c->ext + (size_t)row * PQA_EXT_DOUBLES,
+                          (size_t)n * PQA_EXT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (ext) {      // a context without the SSIM family: nothing it runs has a slot there
+      std::fill(ext + (size_t)done * PQA_EXT_DOUBLES, ext + (size_t)(done + n) * PQA_EXT_DOUBLES, __builtin_nan(""));
     }
     done += n;
     row = 0;

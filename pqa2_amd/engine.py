@@ -234,6 +234,14 @@ class FeatureEngine:
         self._check(self.lib.pqa_collect(self._ctx, first_index, count, out.ctypes.data))
         return out
 
+    def collect_ext(self, first_index: int, count: int):
+        """(records [count, 24], ext [count, EXT_DOUBLES]): collect() plus the extension rows of the same frames
+        (pqa_collect_ext; float_ssim / float_ms_ssim slots, NaN where the context does not run them)."""
+        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
+        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
+        self._check(self.lib.pqa_collect_ext(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data))
+        return out, ext
+
     def flush(self):
         self._check(self.lib.pqa_flush(self._ctx))
 

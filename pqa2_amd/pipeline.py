@@ -28,10 +28,11 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 psnr: bool = True, ssim: bool = True, n_subsample: int = 1, device: int = 0,
                 rank: int = 0, world_size: int = 1, gather_device=None, max_batch: int = 0,
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
-                fixed_point: int = 0) -> ScoreResult | None:
+                fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
-    `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h)."""
+    `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
+    `float_ssim` / `ms_ssim`: libvmaf's float_ssim / float_ms_ssim features as extra metric columns (extension record)."""
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -48,6 +49,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     side = (psnr or ssim)
     n_planes = 1 if (ri.mono or not side) else 3
     feats = N.FEAT_VMAF | (N.FEAT_PSNR if psnr else 0) | (N.FEAT_SSIM if ssim else 0)
+    want_ext = bool(float_ssim or ms_ssim)
+    if want_ext:
+        feats |= (N.FEAT_FLOAT_SSIM if float_ssim else 0) | (N.FEAT_MS_SSIM if ms_ssim else 0)
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -88,22 +92,30 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             i += m
             if progress is not None:
                 progress(i - a, b - a)
-        local = eng.collect(a, b - a) if b > a else np.zeros((0, N.RECORD_DOUBLES))
+        if want_ext:
+            local, local_ext = eng.collect_ext(a, b - a) if b > a else (np.zeros((0, N.RECORD_DOUBLES)),
+                                                                          np.zeros((0, N.EXT_DOUBLES)))
+        else:
+            local = eng.collect(a, b - a) if b > a else np.zeros((0, N.RECORD_DOUBLES))
     except BaseException:
         eng.close()
         raise
     (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
+    ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     if rank != 0:
         return None
     elapsed = time.perf_counter() - t_start
+    extra = {"ext": ext, "float_ssim": bool(float_ssim), "ms_ssim": bool(ms_ssim)} if want_ext else {}
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
-                          fps=n / elapsed if elapsed > 0 else 0.0)
+                          fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
 
 def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim: bool, n_subsample: int = 1,
-                   n_planes: int = 1, fps: float = 0.0) -> ScoreResult:
-    """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines."""
+                   n_planes: int = 1, fps: float = 0.0, ext: np.ndarray | None = None, float_ssim: bool = False,
+                   ms_ssim: bool = False) -> ScoreResult:
+    """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
+    the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim columns."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -121,6 +133,13 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         sv = rec[:, N.REC_SSIM:N.REC_SSIM + n_planes]
         ssim_lines = report.ssim_stats_lines(sv, plane_sizes)
         metrics["ssim"] = report.ssim_all(sv, plane_sizes)
+    if float_ssim or ms_ssim:
+        if ext is None or ext.shape != (n, N.EXT_DOUBLES):
+            raise ValueError("float_ssim / ms_ssim need the extension records of every frame")
+        if float_ssim:
+            metrics["float_ssim"] = ext[:, N.EXT_FLOAT_SSIM].copy()
+        if ms_ssim:
+            metrics["float_ms_ssim"] = ext[:, N.EXT_MS_SSIM].copy()
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:

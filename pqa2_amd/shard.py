@@ -28,19 +28,20 @@ def all_bounds(n_frames: int, world_size: int):
 
 
 def gather_records(local: np.ndarray, n_frames: int, world_size: int, rank: int, device=None,
-                   force_collective: bool = False):
-    """All-gather the per-rank record tiles into the full [n_frames, 24] array (on every rank).
+                   force_collective: bool = False, width: int = RECORD_DOUBLES):
+    """All-gather the per-rank record tiles into the full [n_frames, width] array (on every rank).  width: 24 for the
+    feature records, EXT_DOUBLES for the extension records (pqa_collect_ext) -- the same transport.
 
     One collective: equal-sized tiles of ceil(n/world) rows (short ranks pad with zeros).  float64
     payload carries the uint64 SSE slots bit-exactly (no arithmetic touches them).
     `force_collective`: run the collective even at world_size 1 (a one-rank process group) -- how the RCCL leg is
     exercised on a one-GPU box."""
     if world_size == 1 and not force_collective:
-        return np.asarray(local, np.float64).reshape(-1, RECORD_DOUBLES)
+        return np.asarray(local, np.float64).reshape(-1, width)
     import torch
     import torch.distributed as dist
     rows = -(-n_frames // world_size)
-    tile = np.zeros((rows, RECORD_DOUBLES), np.float64)
+    tile = np.zeros((rows, width), np.float64)
     a, b = shard_bounds(n_frames, world_size, rank)
     assert local.shape[0] == b - a
     tile[: b - a] = local
@@ -48,9 +49,9 @@ def gather_records(local: np.ndarray, n_frames: int, world_size: int, rank: int,
     t = torch.from_numpy(tile.view(np.int64))
     if device is not None:
         t = t.to(device)
-    out = torch.empty((world_size * rows, RECORD_DOUBLES), dtype=torch.int64, device=t.device)
+    out = torch.empty((world_size * rows, width), dtype=torch.int64, device=t.device)
     dist.all_gather_into_tensor(out, t)
-    full = out.cpu().numpy().view(np.float64).reshape(world_size, rows, RECORD_DOUBLES)
+    full = out.cpu().numpy().view(np.float64).reshape(world_size, rows, width)
     parts = []
     for r in range(world_size):
         ra, rb = shard_bounds(n_frames, world_size, r)

@@ -147,6 +147,8 @@ class VMAFAnalyzer(QObject):
         self.child_backend = "nccl"           # collective backend of the child job: nccl (= RCCL) | gloo
         self.child_share_device = False       # True: every rank of the child job uses device 0 (one-GPU rehearsal)
         self.fixed_point = 0                  # PQA_FIXED_* mask (1 VIF, 2 motion): libvmaf's integer arithmetic, slower
+        self.float_ssim_enabled = False       # libvmaf float_ssim (feature=name=float_ssim / ssim=1) per frame and pooled
+        self.ms_ssim_enabled = False          # libvmaf float_ms_ssim (feature=name=float_ms_ssim / ms_ssim=1)
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -164,6 +166,8 @@ class VMAFAnalyzer(QObject):
             self.enable_temporal_features = s.get("enable_temporal_features", False)
             self.psnr_enabled = s.get("psnr_enabled", True)
             self.ssim_enabled = s.get("ssim_enabled", True)
+            self.float_ssim_enabled = bool(s.get("float_ssim_enabled", False))
+            self.ms_ssim_enabled = bool(s.get("ms_ssim_enabled", False))
             logger.info(f"VMAF options set from manager: threads={self.threads}, "
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
@@ -180,13 +184,16 @@ class VMAFAnalyzer(QObject):
         logger.info(f"Set test name to: {test_name}")
 
     def set_advanced_options(self, pool_method="mean", enable_motion_score=False, enable_temporal_features=False,
-                             feature_subsample=1, psnr_enabled=True, ssim_enabled=True):
+                             feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
+                             ms_ssim_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
         self.feature_subsample = feature_subsample
         self.psnr_enabled = psnr_enabled
         self.ssim_enabled = ssim_enabled
+        self.float_ssim_enabled = bool(float_ssim_enabled)
+        self.ms_ssim_enabled = bool(ms_ssim_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -342,7 +349,7 @@ class VMAFAnalyzer(QObject):
             res = score_files(ref, dis, model, psnr=bool(psnr_path), ssim=bool(ssim_path),
                               n_subsample=max(1, int(self.feature_subsample or 1)), device=self.device,
                               max_batch=self.max_batch, engine_factory=self._engine_factory,
-                              fixed_point=self.fixed_point,
+                              fixed_point=self.fixed_point, **self._ssim_family_kwargs(),
                               progress=lambda d, t: self._emit_progress(d, total_frames or t, state),
                               cancelled=lambda: self._terminate_requested)
         except N.PqaCancelled:
@@ -367,6 +374,11 @@ class VMAFAnalyzer(QObject):
                 f.write("\n".join(res["ssim_lines"]) + "\n")
         return True
 
+    def _ssim_family_kwargs(self):
+        """score_files keywords of the SSIM family: only the enabled ones (the default call is the one it always was)."""
+        return {**({"float_ssim": True} if self.float_ssim_enabled else {}),
+                **({"ms_ssim": True} if self.ms_ssim_enabled else {})}
+
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
         reference drives its ffmpeg child (stderr `frame=` lines, terminate -> kill, return code)."""
@@ -380,6 +392,10 @@ class VMAFAnalyzer(QObject):
                "--n-subsample", str(max(1, int(self.feature_subsample or 1))), "--batch", str(self.max_batch)]
         if self.fixed_point:
             cmd += ["--fixed-point", str(int(self.fixed_point))]
+        if self.float_ssim_enabled:
+            cmd += ["--float-ssim"]
+        if self.ms_ssim_enabled:
+            cmd += ["--ms-ssim"]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -473,6 +489,10 @@ class VMAFAnalyzer(QObject):
                 "width": width,
                 "height": height,
             }
+            pooled = vmaf_data.get("pooled_metrics", {})
+            for enabled, key in ((self.float_ssim_enabled, "float_ssim"), (self.ms_ssim_enabled, "float_ms_ssim")):
+                if enabled:
+                    results[key] = pooled[key]["mean"] if key in pooled else None
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)

@@ -57,6 +57,56 @@ FAMILIES = ["vif_scale0", "vif_scale1", "vif_scale2", "vif_scale3", "adm2", "adm
             "adm_scale3", "motion", "motion2"]
 
 
+# the SSIM family (libvmaf float_ssim / float_ms_ssim; tests/ssim_family_ref.py states the definition) -> VERIFY items
+SSIM_IMPLICATES = {
+    "float_ssim": ["f = max(1, round(min(w,h)/256)), box window [x - f//2, x - f//2 + f), sample offset 0, ceil size and "
+                   "half-sample symmetric border of iqa's _iqa_decimate (tests/ssim_family_ref.py box_decimate [VERIFY])",
+                   "11x11 Gaussian sigma 1.5 over the valid region; literal (rounded) taps in libvmaf? (gaussian_taps [VERIFY])",
+                   "s / 2^(bpc-8) sample conversion (to_float [VERIFY]); sqrt(max(sx2,0)*max(sy2,0)) clamp (lcs_maps [VERIFY])"],
+    "float_ms_ssim": ["9/7 low-pass taps, half-sample symmetric border, keep samples 0,2,4,... -> ceil(n/2) "
+                      "(lpf97_decimate [VERIFY])",
+                      "separate means of c and s per scale rather than the mean of c*s (ms_combine [VERIFY])",
+                      "weights 0.0448/0.2856/0.3001/0.2363/0.1333, l only at the 5th scale (MS_WEIGHTS [VERIFY])",
+                      "as float_ssim: Gaussian taps, sample conversion, clamp"],
+}
+
+
+def ssim_family_columns(ref_path, dis_path, want_fs, want_ms, use_gpu, n):
+    """{tag: {key: per-frame column}} of float_ssim / float_ms_ssim (+ the l/c/s means under libvmaf's enable_lcs names)
+    from the restatement and, with use_gpu, from the HIP kernels (pqa_collect_ext)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ssim_family_ref as SR
+    from pqa2_amd.yuvio import open_video
+    rr, dr = open_video(ref_path), open_video(dis_path)
+    info = rr.info
+    refs = [rr.frame(i)[0] for i in range(n)]
+    diss = [dr.frame(i)[0] for i in range(n)]
+
+    def cols(ext):
+        c = {}
+        if want_fs:
+            c["float_ssim"] = ext[:, 0]
+            for j, k in enumerate("lcs"):
+                c[f"float_ssim_{k}"] = ext[:, 1 + j]
+        if want_ms:
+            c["float_ms_ssim"] = ext[:, 4]
+            for j, k in enumerate("lcs"):
+                for s in range(5):
+                    c[f"float_ms_ssim_{k}_scale{s}"] = ext[:, 5 + 5 * j + s]
+        return c
+    out = {"f64 restatement (tests/ssim_family_ref.py)":
+           cols(np.stack([SR.ext_record(refs[i], diss[i], info.bit_depth, want_fs, want_ms) for i in range(n)]))}
+    if use_gpu:
+        from pqa2_amd import _native as N
+        from pqa2_amd.engine import FeatureEngine
+        feats = (N.FEAT_FLOAT_SSIM if want_fs else 0) | (N.FEAT_MS_SSIM if want_ms else 0)
+        with FeatureEngine(info.width, info.height, bit_depth=info.bit_depth, features=feats) as eng:
+            for i in range(n):
+                eng.submit(i, [refs[i]], [diss[i]])
+            out["HIP kernels (csrc/ssim_family.hip)"] = cols(eng.collect_ext(0, n)[1])
+    return out
+
+
 def load_log(path):
     with open(path) as f:
         d = json.load(f)
@@ -149,6 +199,21 @@ def main(argv=None) -> int:
                     if ("integer:" in line) and not integer_keys:
                         continue
                     print(f"{'':28s}   -> check: {line}")
+    want_fs, want_ms = "float_ssim" in log, "float_ms_ssim" in log
+    if want_fs or want_ms:
+        for tag, cols in ssim_family_columns(a.reference, a.distorted, want_fs, want_ms, a.gpu, n).items():
+            print(f"\n== SSIM family: {tag} ==")
+            for key in sorted(k for k in cols if k in log):
+                d = np.abs(cols[key][frame_nums] - log[key])
+                j = int(np.nanargmax(d)) if d.size else 0
+                ok = bool(np.nanmax(d) <= a.tol) if d.size else True
+                print(f"{key:28s} {np.nanmax(d) if d.size else 0.0:22.3e} {frame_nums[j] if d.size else 0:9d}   "
+                      f"{a.tol:.0e}   {'ok' if ok else 'MISMATCH'}")
+                if not ok:
+                    bad = True
+                    fam = "float_ms_ssim" if key.startswith("float_ms_ssim") else "float_ssim"
+                    for line in SSIM_IMPLICATES[fam]:
+                        print(f"{'':28s}   -> check: {line}")
     missing = [prefix + f for f in FAMILIES if prefix + f not in log]
     if missing:
         print(f"\nnot in the log (not compared): {', '.join(missing)}")
