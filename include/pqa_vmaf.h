@@ -63,7 +63,13 @@ enum {
    * naming the feature otherwise (float_ssim fits every size pqa_create accepts, w, h >= 16).  Definition and its unpinned items: DESIGN.md sections 1 and 5. */
   PQA_FEAT_FLOAT_SSIM = 1u << 5,
   PQA_FEAT_MS_SSIM = 1u << 6,
-  PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM  /* what pqa_create accepts */
+  /* bit 7 stays unassigned (tests use it as the unknown bit pqa_create rejects) */
+  /* libvmaf's ciede (`feature=name=ciede`, log key ciede2000): CIEDE2000 colour difference of every luma pixel, chroma
+   * upsampled by replication, results in extension slots PQA_EXT_CIEDE2000 / PQA_EXT_CIEDE_MEAN_DE on the frames that get
+   * VIF / ADM (n_subsample).  Needs n_planes = 3 (PQA_EINVAL naming ciede2000 otherwise); any chroma subsampling.
+   * Definition and its unpinned items: DESIGN.md sections 1 and 5. */
+  PQA_FEAT_CIEDE = 1u << 8,
+  PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -80,8 +86,8 @@ enum {
 };
 
 /* One EXTENSION record = PQA_EXT_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and wrap) when
- * the context runs PQA_FEAT_FLOAT_SSIM or PQA_FEAT_MS_SSIM.  Slots of a feature the context does not run, and of frames
- * that get no spatial features (n_subsample), are NaN; so are the reserved slots. */
+ * the context runs PQA_FEAT_FLOAT_SSIM, PQA_FEAT_MS_SSIM or PQA_FEAT_CIEDE.  Slots of a feature the context does not run,
+ * and of frames that get no spatial features (n_subsample), are NaN; so are the unused slots 22..23. */
 enum {
   PQA_EXT_FLOAT_SSIM = 0,     /*     float_ssim: mean of l*c*s over the (decimated) map                */
   PQA_EXT_FLOAT_SSIM_LCS = 1, /* [3] its means of l, c, s                                               */
@@ -89,7 +95,9 @@ enum {
   PQA_EXT_MS_SSIM_L = 5,      /* [5] mean of l per scale 0..4                                           */
   PQA_EXT_MS_SSIM_C = 10,     /* [5] mean of c per scale                                                */
   PQA_EXT_MS_SSIM_S = 15,     /* [5] mean of s per scale                                                */
-  PQA_EXT_RESERVED = 20,      /* [4]                                                                    */
+  PQA_EXT_RESERVED = 20,      /*     first slot after the SSIM family                                   */
+  PQA_EXT_CIEDE2000 = 20,     /*     ciede2000 = 45 - 20 log10(mean dE00), in double (+inf at mean 0)     */
+  PQA_EXT_CIEDE_MEAN_DE = 21, /*     the frame's mean CIEDE2000 dE00 over its luma pixels                  */
   PQA_EXT_DOUBLES = 24
 };
 
@@ -235,7 +243,7 @@ PQA_API int pqa_collect(pqa_ctx* ctx, int64_t first_index, int32_t count, double
 
 /* pqa_collect with the extension records: exactly its contract (the same waits, the same PQA_ESTATE rules; the frames are
  * marked collected), and in addition ext[count][PQA_EXT_DOUBLES] receives the extension rows of the same frames.  ext may
- * be NULL.  A context that runs neither PQA_FEAT_FLOAT_SSIM nor PQA_FEAT_MS_SSIM returns all-NaN rows.
+ * be NULL.  A context that runs none of PQA_FEAT_FLOAT_SSIM, PQA_FEAT_MS_SSIM, PQA_FEAT_CIEDE returns all-NaN rows.
  * pqa_collect(c, f, n, r) is pqa_collect_ext(c, f, n, r, NULL). */
 PQA_API int pqa_collect_ext(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext);
 
@@ -278,7 +286,8 @@ enum { PQA_GRAY_LUMA = 0, PQA_GRAY_BT601_FULL = 1 };
 PQA_API int pqa_set_luma_gray(pqa_ctx* ctx, uint32_t mode);
 
 /* Measurement hooks (bench.py): HIP-event timing of individual kernels on the context's stream.
- * kernel ids: 0..3 vif_stat scale s (each also produces the next scale's planes), 4..6 reserved,
+ * kernel ids: 0..3 vif_stat scale s (each also produces the next scale's planes), 4 ciede2000 (its kernel and epilogue),
+ * 5..6 reserved,
  * 7..10 adm scale s,
  * 11 motion, 12 sse, 13 ssim, 14 finalize, 15 ms_ssim (all five scales, their decimations and the extension epilogue),
  * 16 float_ssim.
@@ -299,6 +308,11 @@ PQA_API int pqa_debug_vif_march_table(uint16_t* out, int32_t capacity_halfwords)
  * first-pass MFMAs per block, second-pass MFMAs per block}.  A wave = one stripe x one segment; a segment repeats one block
  * of the first pass.  bench.py prices `roofline.mfma` with it instead of mirroring the rule. */
 PQA_API int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* out6);
+
+/* Test hook (needs a device): the CIEDE2000 device function of the PQA_FEAT_CIEDE kernel on n Lab pairs
+ * lab_pairs[n][6] = {L1, a1, b1, L2, a2, b2}: the inputs are converted to f32, de_out[n] receives the f32 results widened.
+ * PQA_EDEVICE without a device (text in pqa_last_error(NULL)), PQA_EINVAL on a null pointer or n < 0. */
+PQA_API int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out);
 
 #ifdef __cplusplus
 }

@@ -229,4 +229,27 @@ hipError_t launch_ssf_finalize(hipStream_t stream, const SsfFinalizeArgs& args);
 // NaN into n_rows consecutive ring rows starting at slot_base (frames that get no spatial features, fresh rings)
 hipError_t launch_ext_fill_nan(hipStream_t stream, double* ext, int slot_base, int n_rows, int capacity, int stride);
 
+// ---- CIEDE2000: libvmaf ciede (ciede.hip) ------------------------------------------------------------------------------
+constexpr int kCiedeTileW = 64, kCiedeTileH = 4;    // chroma samples per workgroup tile: a chroma row per wave
+// tiles of a cw x ch chroma plane (one double partial each)
+int ciede_tiles(int cw, int ch);
+// Sum of the CIEDE2000 differences of every luma pixel of w x h frames (planes Y, U, V of u8 / u16 samples at bit_depth;
+// chroma ceil(w / 2^hshift) x ceil(h / 2^vshift), upsampled by replication).  partials: [n_frames][ciede_tiles] doubles.
+hipError_t launch_ciede(hipStream_t stream, Elem elem, const PlaneRun ref[3], const PlaneRun dis[3], int n_frames, int w,
+                        int h, int hshift, int vshift, int bit_depth, double* partials);
+// Per-frame epilogue: fixed-order sum of the partials, mean (x norm = 1 / (w h)) and 45 - 20 log10(mean) in double, into
+// slots PQA_EXT_CIEDE_MEAN_DE / PQA_EXT_CIEDE2000 of the extension ring; the other slots of the row are left alone.
+struct CiedeFinalizeArgs {
+  int n_frames;
+  double* ext;
+  int ext_stride;
+  int slot_base, slot_step, capacity;   // ring row of batch frame f = (slot_base + f * slot_step) % capacity
+  const double* partials;
+  int n_tiles;
+  double norm;
+};
+hipError_t launch_ciede_finalize(hipStream_t stream, const CiedeFinalizeArgs& args);
+// The kernel's CIEDE2000 device function on n Lab pairs [n][6] (f32, device pointers) -> de_out[n] (pqa_debug_ciede2000).
+hipError_t launch_ciede_debug(hipStream_t stream, const float* lab_pairs, int n, float* de_out);
+
 }  // namespace pqa

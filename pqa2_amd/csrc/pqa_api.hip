@@ -128,6 +128,9 @@ struct pqa_ctx {
   double* fs_part = nullptr;         // float_ssim: [ssf_sb][tiles][4]
   int fs_tiles = 0, fs_box = 1;
   int ssf_sb = 0;                    // frames per pass through the pyramid (bounds its memory at 2160p)
+  // CIEDE2000 (PQA_FEAT_CIEDE; ciede.hip): nothing is allocated unless the bit is set
+  double* ciede_part = nullptr;      // [B][ciede_tiles]
+  int ciede_tiles_n = 0;
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -213,7 +216,7 @@ int dev_alloc(pqa_ctx* c, T** out, size_t count) {
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 static const char* kProfNames[PQA_PROF_KERNELS] = {
-    "vif_stat_s0", "vif_stat_s1", "vif_stat_s2", "vif_stat_s3", "reserved4", "reserved5",
+    "vif_stat_s0", "vif_stat_s1", "vif_stat_s2", "vif_stat_s3", "ciede2000", "reserved5",
     "reserved6", "adm_scale_s0", "adm_scale_s1", "adm_scale_s2", "adm_scale_s3", "motion", "sse",
     "ssim", "finalize", "ms_ssim", "float_ssim"};
 
@@ -520,10 +523,11 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
     }
   }
 
+  // extension features run on the frames that get spatial features; the extension rows of the other frames are NaN
+  if (k > 1 && (feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE)))
+    HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext, (int)(first % c->capacity), n, c->capacity, PQA_EXT_DOUBLES));
   if ((feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM))) {
-    // the SSIM family on the frames that get spatial features, ssf_sb at a time (the MS-SSIM pyramid is sized for that many);
-    // the extension rows of the other frames are NaN
-    if (k > 1) HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext, (int)(first % c->capacity), n, c->capacity, PQA_EXT_DOUBLES));
+    // the SSIM family, ssf_sb frames at a time (the MS-SSIM pyramid is sized for that many)
     const bool fs = feat & PQA_FEAT_FLOAT_SSIM, ms = feat & PQA_FEAT_MS_SSIM;
     for (int s0 = 0; s0 < sp_n; s0 += c->ssf_sb) {
       const int m = sp_n - s0 < c->ssf_sb ? sp_n - s0 : c->ssf_sb;
@@ -572,6 +576,30 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
         HIPCHK(c, launch_ssf_finalize(st_misc, sa));
       }
     }
+  }
+  if ((feat & PQA_FEAT_CIEDE) && sp_n > 0) {
+    // CIEDE2000 on Y, U, V of the frames that get spatial features; the epilogue writes slots 20 / 21 of their rows only
+    PlaneRun r3[3], d3[3];
+    for (int p = 0; p < 3; ++p) {
+      const PlaneRun rp{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
+      const PlaneRun dp{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
+      r3[p] = k > 1 ? sub(rp) : rp;
+      d3[p] = k > 1 ? sub(dp) : dp;
+    }
+    CiedeFinalizeArgs ca{};
+    ca.n_frames = sp_n;
+    ca.ext = c->ext;
+    ca.ext_stride = PQA_EXT_DOUBLES;
+    ca.slot_base = (int)((first + e0) % c->capacity);
+    ca.slot_step = k;
+    ca.capacity = c->capacity;
+    ca.partials = c->ciede_part;
+    ca.n_tiles = c->ciede_tiles_n;
+    ca.norm = 1.0 / ((double)w * h);
+    ProfScope ps(c, 4, sp_n, st_misc);
+    HIPCHK(c, launch_ciede(st_misc, c->elem, r3, d3, sp_n, w, h, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift,
+                           (int)c->cfg.bit_depth, c->ciede_part));
+    HIPCHK(c, launch_ciede_finalize(st_misc, ca));
   }
 
   if (multi) {  // join
@@ -928,6 +956,8 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
       return fail(nullptr, PQA_EINVAL, "frame %ux%u too small for float_ms_ssim (5th scale %dx%d, needs >= 11x11: w, h >= 161)",
                   cfg->width, cfg->height, sw, sh);
   }
+  if ((cfg->features & PQA_FEAT_CIEDE) && cfg->n_planes != 3)
+    return fail(nullptr, PQA_EINVAL, "ciede2000 needs the chroma planes: n_planes must be 3 (got %u)", cfg->n_planes);
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
   int ndev = 0;
@@ -1130,6 +1160,12 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
       c->fs_tiles = ssf_tiles((w + c->fs_box - 1) / c->fs_box, (h + c->fs_box - 1) / c->fs_box);
       CREATE_TRY(dev_alloc(c, &c->fs_part, (size_t)c->fs_tiles * 4 * SB));
     }
+  }
+  if (cfg->features & PQA_FEAT_CIEDE) {
+    c->ciede_tiles_n = ciede_tiles(c->pw[1], c->ph[1]);
+    CREATE_TRY(dev_alloc(c, &c->ciede_part, (size_t)c->ciede_tiles_n * B));
+  }
+  if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE)) {
     CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext, 0, c->capacity, c->capacity, PQA_EXT_DOUBLES));
   }
@@ -1648,6 +1684,28 @@ int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* out6) {
   int shape[6];
   vif_march_shape((int)width, (int)height, shape);
   for (int i = 0; i < 6; ++i) out6[i] = shape[i];
+  return PQA_OK;
+}
+
+int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out) {
+  if (n < 0 || (n > 0 && (!lab_pairs || !de_out))) return fail(nullptr, PQA_EINVAL, "bad argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
+  if (n == 0) return PQA_OK;
+  std::vector<float> in((size_t)n * 6), out((size_t)n);
+  for (size_t i = 0; i < in.size(); ++i) in[i] = (float)lab_pairs[i];
+  float* d_in = nullptr;
+  float* d_out = nullptr;
+  hipError_t e = hipMalloc(&d_in, in.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_out, out.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_in, in.data(), in.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_ciede_debug(nullptr, d_in, n, d_out);
+  if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, out.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (d_in) hipFree(d_in);
+  if (d_out) hipFree(d_out);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_ciede2000: %s", hipGetErrorString(e));
+  for (int32_t i = 0; i < n; ++i) de_out[i] = (double)out[i];
   return PQA_OK;
 }
 

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(kBlock) void ssf_finalize_kernel(const SsfFinalizeA
   }
   e[4] = ms;
   for (int j = 0; j < kMsScales; ++j) { e[5 + j] = lm[j]; e[10 + j] = cm[j]; e[15 + j] = sm[j]; }
-  for (int q = 20; q < a.ext_stride; ++q) e[q] = nan;
+  // slots 20.. belong to other features (CIEDE2000): left as they are (NaN from the ring fill where nothing writes them)
 }
 
 __global__ __launch_bounds__(64) void ext_nan_kernel(double* ext, int slot_base, int capacity, int stride) {

@@ -28,11 +28,13 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 psnr: bool = True, ssim: bool = True, n_subsample: int = 1, device: int = 0,
                 rank: int = 0, world_size: int = 1, gather_device=None, max_batch: int = 0,
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
-                fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False) -> ScoreResult | None:
+                fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
+                ciede: bool = False) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
-    `float_ssim` / `ms_ssim`: libvmaf's float_ssim / float_ms_ssim features as extra metric columns (extension record)."""
+    `float_ssim` / `ms_ssim`: libvmaf's float_ssim / float_ms_ssim features as extra metric columns (extension record).
+    `ciede`: libvmaf's ciede feature as the extra column ciede2000 (needs the chroma planes: a monochrome clip is an error)."""
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -45,13 +47,15 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
+    if ciede and ri.mono:
+        raise ValueError("ciede2000 needs the chroma planes, but the clips are monochrome")
     mdl = M.load_model(model)
-    side = (psnr or ssim)
+    side = (psnr or ssim or ciede)
     n_planes = 1 if (ri.mono or not side) else 3
     feats = N.FEAT_VMAF | (N.FEAT_PSNR if psnr else 0) | (N.FEAT_SSIM if ssim else 0)
-    want_ext = bool(float_ssim or ms_ssim)
+    want_ext = bool(float_ssim or ms_ssim or ciede)
     if want_ext:
-        feats |= (N.FEAT_FLOAT_SSIM if float_ssim else 0) | (N.FEAT_MS_SSIM if ms_ssim else 0)
+        feats |= (N.FEAT_FLOAT_SSIM if float_ssim else 0) | (N.FEAT_MS_SSIM if ms_ssim else 0) | (N.FEAT_CIEDE if ciede else 0)
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -107,15 +111,18 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         return None
     elapsed = time.perf_counter() - t_start
     extra = {"ext": ext, "float_ssim": bool(float_ssim), "ms_ssim": bool(ms_ssim)} if want_ext else {}
+    if ciede:
+        extra["ciede"] = True
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                           fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
 
 def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim: bool, n_subsample: int = 1,
                    n_planes: int = 1, fps: float = 0.0, ext: np.ndarray | None = None, float_ssim: bool = False,
-                   ms_ssim: bool = False) -> ScoreResult:
+                   ms_ssim: bool = False, ciede: bool = False) -> ScoreResult:
     """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
-    the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim columns."""
+    / `ciede` the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim /
+    ciede2000 columns."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -133,13 +140,15 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         sv = rec[:, N.REC_SSIM:N.REC_SSIM + n_planes]
         ssim_lines = report.ssim_stats_lines(sv, plane_sizes)
         metrics["ssim"] = report.ssim_all(sv, plane_sizes)
-    if float_ssim or ms_ssim:
+    if float_ssim or ms_ssim or ciede:
         if ext is None or ext.shape != (n, N.EXT_DOUBLES):
-            raise ValueError("float_ssim / ms_ssim need the extension records of every frame")
+            raise ValueError("float_ssim / ms_ssim / ciede2000 need the extension records of every frame")
         if float_ssim:
             metrics["float_ssim"] = ext[:, N.EXT_FLOAT_SSIM].copy()
         if ms_ssim:
             metrics["float_ms_ssim"] = ext[:, N.EXT_MS_SSIM].copy()
+        if ciede:
+            metrics["ciede2000"] = ext[:, N.EXT_CIEDE2000].copy()
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:

@@ -65,6 +65,7 @@ def main(argv=None) -> int:
                     help="PQA_FIXED_* mask (1 VIF, 2 motion): extractors run in libvmaf's fixed-point arithmetic")
     ap.add_argument("--float-ssim", action="store_true", help="add libvmaf's float_ssim feature (per frame and pooled)")
     ap.add_argument("--ms-ssim", action="store_true", help="add libvmaf's float_ms_ssim feature (per frame and pooled)")
+    ap.add_argument("--ciede", action="store_true", help="add libvmaf's ciede feature, key ciede2000 (per frame and pooled)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -100,7 +101,8 @@ def main(argv=None) -> int:
         res = score_files(a.reference, a.distorted, a.model, psnr=bool(a.psnr_log), ssim=bool(a.ssim_log),
                           n_subsample=a.n_subsample, device=local_rank, rank=rank, world_size=world,
                           gather_device=gather_device, max_batch=a.batch, progress=progress, fixed_point=a.fixed_point,
-                          **({"float_ssim": True} if a.float_ssim else {}), **({"ms_ssim": True} if a.ms_ssim else {}))
+                          **({"float_ssim": True} if a.float_ssim else {}), **({"ms_ssim": True} if a.ms_ssim else {}),
+                          **({"ciede": True} if a.ciede else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
         return 1

@@ -149,6 +149,7 @@ class VMAFAnalyzer(QObject):
         self.fixed_point = 0                  # PQA_FIXED_* mask (1 VIF, 2 motion): libvmaf's integer arithmetic, slower
         self.float_ssim_enabled = False       # libvmaf float_ssim (feature=name=float_ssim / ssim=1) per frame and pooled
         self.ms_ssim_enabled = False          # libvmaf float_ms_ssim (feature=name=float_ms_ssim / ms_ssim=1)
+        self.ciede_enabled = False            # libvmaf ciede (feature=name=ciede, key ciede2000) per frame and pooled
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -168,6 +169,7 @@ class VMAFAnalyzer(QObject):
             self.ssim_enabled = s.get("ssim_enabled", True)
             self.float_ssim_enabled = bool(s.get("float_ssim_enabled", False))
             self.ms_ssim_enabled = bool(s.get("ms_ssim_enabled", False))
+            self.ciede_enabled = bool(s.get("ciede_enabled", False))
             logger.info(f"VMAF options set from manager: threads={self.threads}, "
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
@@ -185,7 +187,7 @@ class VMAFAnalyzer(QObject):
 
     def set_advanced_options(self, pool_method="mean", enable_motion_score=False, enable_temporal_features=False,
                              feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
-                             ms_ssim_enabled=False):
+                             ms_ssim_enabled=False, ciede_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -194,6 +196,7 @@ class VMAFAnalyzer(QObject):
         self.ssim_enabled = ssim_enabled
         self.float_ssim_enabled = bool(float_ssim_enabled)
         self.ms_ssim_enabled = bool(ms_ssim_enabled)
+        self.ciede_enabled = bool(ciede_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -375,9 +378,11 @@ class VMAFAnalyzer(QObject):
         return True
 
     def _ssim_family_kwargs(self):
-        """score_files keywords of the SSIM family: only the enabled ones (the default call is the one it always was)."""
+        """score_files keywords of the extension features (SSIM family, ciede): only the enabled ones (the default call is
+        the one it always was)."""
         return {**({"float_ssim": True} if self.float_ssim_enabled else {}),
-                **({"ms_ssim": True} if self.ms_ssim_enabled else {})}
+                **({"ms_ssim": True} if self.ms_ssim_enabled else {}),
+                **({"ciede": True} if self.ciede_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -396,6 +401,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--float-ssim"]
         if self.ms_ssim_enabled:
             cmd += ["--ms-ssim"]
+        if self.ciede_enabled:
+            cmd += ["--ciede"]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -490,7 +497,8 @@ class VMAFAnalyzer(QObject):
                 "height": height,
             }
             pooled = vmaf_data.get("pooled_metrics", {})
-            for enabled, key in ((self.float_ssim_enabled, "float_ssim"), (self.ms_ssim_enabled, "float_ms_ssim")):
+            for enabled, key in ((self.float_ssim_enabled, "float_ssim"), (self.ms_ssim_enabled, "float_ms_ssim"),
+                                 (self.ciede_enabled, "ciede2000")):
                 if enabled:
                     results[key] = pooled[key]["mean"] if key in pooled else None
             self.analysis_progress.emit(100)

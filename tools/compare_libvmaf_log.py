@@ -106,6 +106,43 @@ def ssim_family_columns(ref_path, dis_path, want_fs, want_ms, use_gpu, n):
             out["HIP kernels (csrc/ssim_family.hip)"] = cols(eng.collect_ext(0, n)[1])
     return out
 
+# libvmaf ciede (log key ciede2000; tests/ciede_ref.py states the definition, every constant in its CONST table) -> VERIFY items
+SSIM_IMPLICATES["ciede2000"] = [
+    "chroma upsampled to luma size by replication (tests/ciede_ref.py upsample [VERIFY])",
+    "Y = y/(255 s), U = u/(255 s) - 0.5 with s = 2^(bpc-8): chroma centred at 0.5 or at 128/255 (CONST chroma_offset [VERIFY])",
+    "BT.709 analog Y'UV matrix R = Y + 1.28033 V, G = Y - 0.21482 U - 0.38059 V, B = Y + 2.12798 U, no clamp (CONST [VERIFY])",
+    "sRGB transfer c > 0.04045 ? ((c + 0.055) / 1.055)^2.4 : c / 12.92, x 100",
+    "4-digit D65 sRGB -> XYZ matrix vs the 7-digit one (CONST xyz [VERIFY])",
+    "Lab white (95.047, 100, 108.883), f(t) = t > 0.008856 ? cbrt(t) : 7.787 t + 16/116",
+    "dE00 with kL = kC = kH = 1, Sharma's hue-mean rule, h' = 0 where a' = b = 0",
+    "score 45 - 20 log10(mean dE00), and what libvmaf writes at mean 0 (here +inf) [VERIFY]",
+]
+
+
+def ciede_columns(ref_path, dis_path, use_gpu, n):
+    """{tag: {"ciede2000": per-frame column}} from the f64 restatement and, with use_gpu, from the HIP kernel."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ciede_ref as CR
+    from pqa2_amd.yuvio import open_video
+    rr, dr = open_video(ref_path), open_video(dis_path)
+    info = rr.info
+    if info.mono:
+        raise SystemExit("ciede2000 in the log but the clips are monochrome")
+    refs = [rr.frame(i) for i in range(n)]
+    diss = [dr.frame(i) for i in range(n)]
+    out = {"f64 restatement (tests/ciede_ref.py)":
+           {"ciede2000": np.array([CR.frame_slots(refs[i], diss[i], info.bit_depth, info.hshift, info.vshift)[0]
+                                   for i in range(n)])}}
+    if use_gpu:
+        from pqa2_amd import _native as N
+        from pqa2_amd.engine import FeatureEngine
+        with FeatureEngine(info.width, info.height, bit_depth=info.bit_depth, n_planes=3, chroma_shift=(info.hshift, info.vshift),
+                           features=N.FEAT_CIEDE) as eng:
+            for i in range(n):
+                eng.submit(i, refs[i], diss[i])
+            out["HIP kernel (csrc/ciede.hip)"] = {"ciede2000": eng.collect_ext(0, n)[1][:, N.EXT_CIEDE2000]}
+    return out
+
 
 def load_log(path):
     with open(path) as f:
@@ -214,6 +251,19 @@ def main(argv=None) -> int:
                     fam = "float_ms_ssim" if key.startswith("float_ms_ssim") else "float_ssim"
                     for line in SSIM_IMPLICATES[fam]:
                         print(f"{'':28s}   -> check: {line}")
+    if "ciede2000" in log:
+        for tag, cols in ciede_columns(a.reference, a.distorted, a.gpu, n).items():
+            print(f"\n== ciede2000: {tag} ==")
+            d = np.abs(cols["ciede2000"][frame_nums] - log["ciede2000"])
+            d = np.where(np.isinf(cols["ciede2000"][frame_nums]) & (cols["ciede2000"][frame_nums] == log["ciede2000"]), 0.0, d)
+            j = int(np.nanargmax(d)) if d.size else 0
+            ok = bool(np.nanmax(d) <= a.tol) if d.size else True
+            print(f"{'ciede2000':28s} {np.nanmax(d) if d.size else 0.0:22.3e} {frame_nums[j] if d.size else 0:9d}   "
+                  f"{a.tol:.0e}   {'ok' if ok else 'MISMATCH'}")
+            if not ok:
+                bad = True
+                for line in SSIM_IMPLICATES["ciede2000"]:
+                    print(f"{'':28s}   -> check: {line}")
     missing = [prefix + f for f in FAMILIES if prefix + f not in log]
     if missing:
         print(f"\nnot in the log (not compared): {', '.join(missing)}")
