@@ -69,7 +69,16 @@ enum {
    * VIF / ADM (n_subsample).  Needs n_planes = 3 (PQA_EINVAL naming ciede2000 otherwise); any chroma subsampling.
    * Definition and its unpinned items: DESIGN.md sections 1 and 5. */
   PQA_FEAT_CIEDE = 1u << 8,
-  PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE  /* what pqa_create accepts */
+  /* libvmaf's cambi banding index (`feature=name=cambi`): CAMBI of the distorted luma in extension slot PQA_EXT_CAMBI;
+   * with PQA_FEAT_CAMBI_FULL_REF also CAMBI of the reference luma in PQA_EXT_CAMBI_SOURCE (cambi_full_reference =
+   * max(cambi - cambi_source, 0) is formed by the caller).  Frames that get VIF / ADM only (n_subsample).  Luma only, any
+   * n_planes, bit depth 8 or 10 (PQA_EINVAL naming cambi at 12 bit); FULL_REF without PQA_FEAT_CAMBI is PQA_EINVAL.
+   * Every frame size pqa_create accepts is defined (the window grows with w + h).  Definition and its unpinned items:
+   * DESIGN.md sections 1 and 5; its host-built tables: pqa_debug_cambi_params. */
+  PQA_FEAT_CAMBI = 1u << 9,
+  PQA_FEAT_CAMBI_FULL_REF = 1u << 10,
+  PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI |
+                   PQA_FEAT_CAMBI_FULL_REF  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -86,8 +95,8 @@ enum {
 };
 
 /* One EXTENSION record = PQA_EXT_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and wrap) when
- * the context runs PQA_FEAT_FLOAT_SSIM, PQA_FEAT_MS_SSIM or PQA_FEAT_CIEDE.  Slots of a feature the context does not run,
- * and of frames that get no spatial features (n_subsample), are NaN; so are the unused slots 22..23. */
+ * the context runs PQA_FEAT_FLOAT_SSIM, PQA_FEAT_MS_SSIM, PQA_FEAT_CIEDE or PQA_FEAT_CAMBI.  Slots of a feature the context
+ * does not run, and of frames that get no spatial features (n_subsample), are NaN. */
 enum {
   PQA_EXT_FLOAT_SSIM = 0,     /*     float_ssim: mean of l*c*s over the (decimated) map                */
   PQA_EXT_FLOAT_SSIM_LCS = 1, /* [3] its means of l, c, s                                               */
@@ -98,6 +107,8 @@ enum {
   PQA_EXT_RESERVED = 20,      /*     first slot after the SSIM family                                   */
   PQA_EXT_CIEDE2000 = 20,     /*     ciede2000 = 45 - 20 log10(mean dE00), in double (+inf at mean 0)     */
   PQA_EXT_CIEDE_MEAN_DE = 21, /*     the frame's mean CIEDE2000 dE00 over its luma pixels                  */
+  PQA_EXT_CAMBI = 22,         /*     cambi of the distorted luma                                        */
+  PQA_EXT_CAMBI_SOURCE = 23,  /*     cambi of the reference luma (PQA_FEAT_CAMBI_FULL_REF; NaN without)   */
   PQA_EXT_DOUBLES = 24
 };
 
@@ -243,7 +254,8 @@ PQA_API int pqa_collect(pqa_ctx* ctx, int64_t first_index, int32_t count, double
 
 /* pqa_collect with the extension records: exactly its contract (the same waits, the same PQA_ESTATE rules; the frames are
  * marked collected), and in addition ext[count][PQA_EXT_DOUBLES] receives the extension rows of the same frames.  ext may
- * be NULL.  A context that runs none of PQA_FEAT_FLOAT_SSIM, PQA_FEAT_MS_SSIM, PQA_FEAT_CIEDE returns all-NaN rows.
+ * be NULL.  A context that runs none of PQA_FEAT_FLOAT_SSIM, PQA_FEAT_MS_SSIM, PQA_FEAT_CIEDE, PQA_FEAT_CAMBI returns
+ * all-NaN rows.
  * pqa_collect(c, f, n, r) is pqa_collect_ext(c, f, n, r, NULL). */
 PQA_API int pqa_collect_ext(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext);
 
@@ -313,6 +325,20 @@ PQA_API int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* 
  * lab_pairs[n][6] = {L1, a1, b1, L2, a2, b2}: the inputs are converted to f32, de_out[n] receives the f32 results widened.
  * PQA_EDEVICE without a device (text in pqa_last_error(NULL)), PQA_EINVAL on a null pointer or n < 0. */
 PQA_API int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out);
+
+/* Test hook (no device needed): the host-built tables the PQA_FEAT_CAMBI kernels use at w x h and bit_depth (8 or 10):
+ * out[PQA_CAMBI_PARAM_INTS] = {adjusted window size, r, pixels_in_window, mask threshold, tvi_for_diff[1..4],
+ * contrast weights[4], (w_s, h_s) of scales 0..4}.  PQA_EINVAL on a null pointer, cap < PQA_CAMBI_PARAM_INTS, a size
+ * pqa_create rejects or another bit depth. */
+enum { PQA_CAMBI_PARAM_INTS = 22 };
+PQA_API int pqa_debug_cambi_params(uint32_t w, uint32_t h, uint32_t bit_depth, int32_t* out, int32_t cap);
+
+/* Test hook (needs a device): the PQA_FEAT_CAMBI kernels on one w x h luma plane in host memory (u8 at bit_depth 8, u16 at
+ * 10; rows row_pitch_bytes apart).  cmap[cap] receives the c-values of scales 0..4, each w_s x h_s row-major, one after
+ * another (sum of w_s h_s floats; PQA_EINVAL when cap is smaller); *score (nullable) the frame's cambi.  PQA_EINVAL on a
+ * null pointer or a size / depth pqa_create rejects for cambi, PQA_EDEVICE without a device. */
+PQA_API int pqa_debug_cambi_cmap(const void* luma, int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth,
+                                 float* cmap, int64_t cap, double* score);
 
 #ifdef __cplusplus
 }

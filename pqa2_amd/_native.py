@@ -16,7 +16,8 @@ FEAT_VMAF = FEAT_VIF | FEAT_ADM | FEAT_MOTION
 FEAT_ALL = FEAT_VMAF | FEAT_PSNR | FEAT_SSIM   # stays 31: the features of the 24-double record
 FEAT_FLOAT_SSIM, FEAT_MS_SSIM = 32, 64          # libvmaf float_ssim / float_ms_ssim: results in the extension record
 FEAT_CIEDE = 256                                # libvmaf ciede (ciede2000): results in the extension record (bit 7 unassigned)
-FEAT_KNOWN = FEAT_ALL | FEAT_FLOAT_SSIM | FEAT_MS_SSIM | FEAT_CIEDE
+FEAT_CAMBI, FEAT_CAMBI_FULL_REF = 512, 1024          # libvmaf cambi of the distorted (and reference) luma: extension record
+FEAT_KNOWN = FEAT_ALL | FEAT_FLOAT_SSIM | FEAT_MS_SSIM | FEAT_CIEDE | FEAT_CAMBI | FEAT_CAMBI_FULL_REF
 VIF_BORDER_FLOAT, VIF_BORDER_INTEGER = 0, 1  # pqa_config.vif_border (include/pqa_vmaf.h)
 FIXED_VIF, FIXED_MOTION, FIXED_ADM, FIXED_ALL = 1, 2, 4, 7   # pqa_config.fixed_point mask
 REC_VIF_NUM, REC_VIF_DEN, REC_ADM_NUM, REC_ADM_DEN, REC_MOTION, REC_SSIM, REC_SSE = 0, 4, 8, 12, 16, 17, 20
@@ -24,6 +25,8 @@ RECORD_DOUBLES = 24
 # extension record (pqa_collect_ext): float_ssim, its l/c/s means, float_ms_ssim, per-scale l/c/s means; NaN where not run
 EXT_FLOAT_SSIM, EXT_FLOAT_SSIM_LCS, EXT_MS_SSIM, EXT_MS_SSIM_L, EXT_MS_SSIM_C, EXT_MS_SSIM_S, EXT_RESERVED = 0, 1, 4, 5, 10, 15, 20
 EXT_CIEDE2000, EXT_CIEDE_MEAN_DE = 20, 21   # ciede2000 = 45 - 20 log10(mean dE00), and the mean itself
+EXT_CAMBI, EXT_CAMBI_SOURCE = 22, 23         # cambi of the distorted luma, and of the reference luma (FULL_REF; NaN without)
+CAMBI_PARAM_INTS = 22                        # pqa_debug_cambi_params
 EXT_DOUBLES = 24
 PROF_KERNELS = 17
 GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
@@ -35,7 +38,7 @@ EXPORTS = [
     "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape",
-    "pqa_debug_ciede2000",
+    "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap",
 ]
 
 
@@ -142,6 +145,8 @@ def load():
     lib.pqa_debug_vif_march_table.argtypes = [vp, i32]
     lib.pqa_debug_vif_march_shape.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(i32 * 6)]
     lib.pqa_debug_ciede2000.argtypes = [vp, i32, vp]
+    lib.pqa_debug_cambi_params.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, i32]
+    lib.pqa_debug_cambi_cmap.argtypes = [vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int64, vp]
     lib.pqa_profile_kernel_name.argtypes = [C.c_int]
     lib.pqa_profile_kernel_name.restype = C.c_char_p
     assert lib.pqa_record_doubles() == RECORD_DOUBLES

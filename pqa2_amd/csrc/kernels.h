@@ -252,4 +252,36 @@ hipError_t launch_ciede_finalize(hipStream_t stream, const CiedeFinalizeArgs& ar
 // The kernel's CIEDE2000 device function on n Lab pairs [n][6] (f32, device pointers) -> de_out[n] (pqa_debug_ciede2000).
 hipError_t launch_ciede_debug(hipStream_t stream, const float* lab_pairs, int n, float* de_out);
 
+// ---- CAMBI: libvmaf cambi banding index (cambi.hip) --------------------------------------------------------------------
+constexpr int kCambiScales = 5, kCambiDiffs = 4;
+constexpr int kCambiParamInts = 22;   // pqa_debug_cambi_params: ws, r, piw, T, tvi[4], weights[4], (w_s, h_s)[5]
+// The host-built tables of a w x h frame (definition: tests/cambi_ref.py CONST).
+struct CambiParams {
+  int ws, r, piw, mask_t;
+  int tvi[kCambiDiffs];        // tvi_for_diff[d], d = 1..4
+  int weights[kCambiDiffs];    // contrast weights
+  int sw[kCambiScales], sh[kCambiScales];
+  int64_t off[kCambiScales + 1];     // scale s's samples start at off[s] of a frame's [off[5]] work planes
+  int chunk[kCambiScales + 1];       // pooling chunks of scale s: [chunk[s], chunk[s + 1])
+  int topk[kCambiScales];            // k = clamp((int)(0.6 N), 1, N)
+};
+CambiParams cambi_params(int w, int h);
+// Once per context before launch_cambi: lets the c-value kernel of this size and bit depth have its LDS (> 64 KiB at 10 bit).
+hipError_t cambi_prepare(const CambiParams& prm, int bit_depth);
+// Work planes of cambi_sb frames, allocated by the context when PQA_FEAT_CAMBI is set.
+struct CambiWork {
+  uint16_t* plane;    // [sb][off[5]]  10-bit samples per scale (mode-filtered at s > 0)
+  uint8_t* mask;      // [sb][off[5]]
+  float* cmap;        // [sb][off[5]]  c-values
+  uint32_t* hist;     // [sb][5][2048] radix-select histograms
+  int32_t* sel;       // [sb][5][4]    radix-select state
+  double* partials;   // [sb][chunk[5]]
+};
+// CAMBI of the luma of n_frames frames (u8 / u16 samples at bit_depth 8 or 10) into slot `slot` of the extension ring
+// rows (slot_base + f * slot_step) % capacity; the other slots of the rows are left alone.  n_frames <= the sb of `wk`.
+// wk.cmap then holds each frame's c-values of scales 0..4 at offsets prm.off[s] (pqa_debug_cambi_cmap reads them).
+hipError_t launch_cambi(hipStream_t stream, Elem elem, PlaneRun luma, int n_frames, int w, int h, int bit_depth,
+                        const CambiParams& prm, const CambiWork& wk, double* ext, int ext_stride, int slot, int slot_base,
+                        int slot_step, int capacity);
+
 }  // namespace pqa

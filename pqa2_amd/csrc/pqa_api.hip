@@ -131,6 +131,10 @@ struct pqa_ctx {
   // CIEDE2000 (PQA_FEAT_CIEDE; ciede.hip): nothing is allocated unless the bit is set
   double* ciede_part = nullptr;      // [B][ciede_tiles]
   int ciede_tiles_n = 0;
+  // CAMBI (PQA_FEAT_CAMBI; cambi.hip): nothing is allocated unless the bit is set
+  CambiParams cambi_prm{};
+  CambiWork cambi_wk{};
+  int cambi_sb = 0;                  // frames per pass (bounds the work planes at 2160p)
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -524,7 +528,7 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
   }
 
   // extension features run on the frames that get spatial features; the extension rows of the other frames are NaN
-  if (k > 1 && (feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE)))
+  if (k > 1 && (feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)))
     HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext, (int)(first % c->capacity), n, c->capacity, PQA_EXT_DOUBLES));
   if ((feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM))) {
     // the SSIM family, ssf_sb frames at a time (the MS-SSIM pyramid is sized for that many)
@@ -600,6 +604,22 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
     HIPCHK(c, launch_ciede(st_misc, c->elem, r3, d3, sp_n, w, h, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift,
                            (int)c->cfg.bit_depth, c->ciede_part));
     HIPCHK(c, launch_ciede_finalize(st_misc, ca));
+  }
+  if ((feat & PQA_FEAT_CAMBI) && sp_n > 0) {
+    // CAMBI of the distorted (and, FULL_REF, the reference) luma, cambi_sb frames at a time; slots 22 / 23 of their rows
+    const bool full = feat & PQA_FEAT_CAMBI_FULL_REF;
+    for (int s0 = 0; s0 < sp_n; s0 += c->cambi_sb) {
+      const int m = sp_n - s0 < c->cambi_sb ? sp_n - s0 : c->cambi_sb;
+      const int slot_base = (int)((first + e0 + (int64_t)s0 * k) % c->capacity);
+      const PlaneRun d0{(const uint8_t*)dYs.base + (int64_t)s0 * dYs.frame_pitch * es, dYs.row_pitch, dYs.frame_pitch};
+      HIPCHK(c, launch_cambi(st_misc, c->elem, d0, m, w, h, (int)c->cfg.bit_depth, c->cambi_prm, c->cambi_wk, c->ext,
+                             PQA_EXT_DOUBLES, PQA_EXT_CAMBI, slot_base, k, c->capacity));
+      if (full) {
+        const PlaneRun r0{(const uint8_t*)rYs.base + (int64_t)s0 * rYs.frame_pitch * es, rYs.row_pitch, rYs.frame_pitch};
+        HIPCHK(c, launch_cambi(st_misc, c->elem, r0, m, w, h, (int)c->cfg.bit_depth, c->cambi_prm, c->cambi_wk, c->ext,
+                               PQA_EXT_DOUBLES, PQA_EXT_CAMBI_SOURCE, slot_base, k, c->capacity));
+      }
+    }
   }
 
   if (multi) {  // join
@@ -958,6 +978,10 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
   }
   if ((cfg->features & PQA_FEAT_CIEDE) && cfg->n_planes != 3)
     return fail(nullptr, PQA_EINVAL, "ciede2000 needs the chroma planes: n_planes must be 3 (got %u)", cfg->n_planes);
+  if ((cfg->features & PQA_FEAT_CAMBI_FULL_REF) && !(cfg->features & PQA_FEAT_CAMBI))
+    return fail(nullptr, PQA_EINVAL, "cambi full reference (PQA_FEAT_CAMBI_FULL_REF) needs PQA_FEAT_CAMBI");
+  if ((cfg->features & PQA_FEAT_CAMBI) && cfg->bit_depth != 8 && cfg->bit_depth != 10)
+    return fail(nullptr, PQA_EINVAL, "cambi supports bit depth 8 or 10 (got %u)", cfg->bit_depth);
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
   int ndev = 0;
@@ -1165,7 +1189,23 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->ciede_tiles_n = ciede_tiles(c->pw[1], c->ph[1]);
     CREATE_TRY(dev_alloc(c, &c->ciede_part, (size_t)c->ciede_tiles_n * B));
   }
-  if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE)) {
+  if (cfg->features & PQA_FEAT_CAMBI) {
+    // work planes: 7 bytes per sample of the five scales (~77 MB per 2160p frame), at most ~512 MiB per pass
+    c->cambi_prm = cambi_params(w, h);
+    const CambiParams& cp = c->cambi_prm;
+    CREATE_HIP(cambi_prepare(cp, (int)cfg->bit_depth));
+    const int64_t per_frame = cp.off[kCambiScales] * 7 + (int64_t)cp.chunk[kCambiScales] * 8;
+    const int64_t sb = (int64_t)(512ll << 20) / per_frame;
+    c->cambi_sb = (int)(sb < 1 ? 1 : sb < B ? sb : B);
+    const size_t SB = (size_t)c->cambi_sb;
+    CREATE_TRY(dev_alloc(c, &c->cambi_wk.plane, (size_t)cp.off[kCambiScales] * SB));
+    CREATE_TRY(dev_alloc(c, &c->cambi_wk.mask, (size_t)cp.off[kCambiScales] * SB));
+    CREATE_TRY(dev_alloc(c, &c->cambi_wk.cmap, (size_t)cp.off[kCambiScales] * SB));
+    CREATE_TRY(dev_alloc(c, &c->cambi_wk.hist, (size_t)kCambiScales * 2048 * SB));
+    CREATE_TRY(dev_alloc(c, &c->cambi_wk.sel, (size_t)kCambiScales * 4 * SB));
+    CREATE_TRY(dev_alloc(c, &c->cambi_wk.partials, (size_t)cp.chunk[kCambiScales] * SB));
+  }
+  if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)) {
     CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext, 0, c->capacity, c->capacity, PQA_EXT_DOUBLES));
   }
@@ -1706,6 +1746,65 @@ int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out) {
   if (d_out) hipFree(d_out);
   if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_ciede2000: %s", hipGetErrorString(e));
   for (int32_t i = 0; i < n; ++i) de_out[i] = (double)out[i];
+  return PQA_OK;
+}
+
+int pqa_debug_cambi_params(uint32_t w, uint32_t h, uint32_t bit_depth, int32_t* out, int32_t cap) {
+  if (!out || cap < PQA_CAMBI_PARAM_INTS) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: null or short output");
+  if (w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: unsupported %ux%u at %u bit", w, h, bit_depth);
+  static_assert(kCambiParamInts == PQA_CAMBI_PARAM_INTS, "pqa_debug_cambi_params layout");
+  const CambiParams p = cambi_params((int)w, (int)h);
+  int i = 0;
+  out[i++] = p.ws; out[i++] = p.r; out[i++] = p.piw; out[i++] = p.mask_t;
+  for (int d = 0; d < kCambiDiffs; ++d) out[i++] = p.tvi[d];
+  for (int d = 0; d < kCambiDiffs; ++d) out[i++] = p.weights[d];
+  for (int s = 0; s < kCambiScales; ++s) { out[i++] = p.sw[s]; out[i++] = p.sh[s]; }
+  return PQA_OK;
+}
+
+int pqa_debug_cambi_cmap(const void* luma, int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth, float* cmap,
+                         int64_t cap, double* score) {
+  if (!luma || !cmap || w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: bad argument");
+  const int es = bit_depth > 8 ? 2 : 1;
+  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: bad row pitch %lld", (long long)row_pitch_bytes);
+  const CambiParams p = cambi_params((int)w, (int)h);
+  const int64_t total = p.off[kCambiScales];
+  if (cap < total) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: cmap holds %lld floats, needs %lld", (long long)cap,
+                               (long long)total);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
+  void* src = nullptr;
+  double* ext = nullptr;
+  CambiWork wk{};
+  const size_t plane_bytes = (size_t)w * h * es;
+  hipError_t e = cambi_prepare(p, (int)bit_depth);
+  if (e == hipSuccess) e = hipMalloc(&src, plane_bytes);
+  if (e == hipSuccess) e = hipMalloc(&ext, PQA_EXT_DOUBLES * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&wk.plane, (size_t)total * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc(&wk.mask, (size_t)total);
+  if (e == hipSuccess) e = hipMalloc(&wk.cmap, (size_t)total * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&wk.hist, (size_t)kCambiScales * 2048 * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&wk.sel, (size_t)kCambiScales * 4 * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&wk.partials, (size_t)p.chunk[kCambiScales] * sizeof(double));
+  if (e == hipSuccess)
+    e = hipMemcpy2D(src, (size_t)w * es, luma, (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const PlaneRun run{src, (int64_t)w, (int64_t)w * h};
+    e = launch_cambi(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, run, 1, (int)w, (int)h, (int)bit_depth, p, wk, ext, PQA_EXT_DOUBLES,
+                     PQA_EXT_CAMBI, 0, 1, 1);
+  }
+  if (e == hipSuccess) e = hipMemcpy(cmap, wk.cmap, (size_t)total * sizeof(float), hipMemcpyDeviceToHost);
+  double ext_row[PQA_EXT_DOUBLES];
+  if (e == hipSuccess) e = hipMemcpy(ext_row, ext, sizeof ext_row, hipMemcpyDeviceToHost);
+  for (void* q : {src, (void*)ext, (void*)wk.plane, (void*)wk.mask, (void*)wk.cmap, (void*)wk.hist, (void*)wk.sel,
+                  (void*)wk.partials})
+    if (q) hipFree(q);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_cambi_cmap: %s", hipGetErrorString(e));
+  if (score) *score = ext_row[PQA_EXT_CAMBI];
   return PQA_OK;
 }
 

@@ -29,12 +29,14 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 rank: int = 0, world_size: int = 1, gather_device=None, max_batch: int = 0,
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
                 fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
-                ciede: bool = False) -> ScoreResult | None:
+                ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
     `float_ssim` / `ms_ssim`: libvmaf's float_ssim / float_ms_ssim features as extra metric columns (extension record).
-    `ciede`: libvmaf's ciede feature as the extra column ciede2000 (needs the chroma planes: a monochrome clip is an error)."""
+    `ciede`: libvmaf's ciede feature as the extra column ciede2000 (needs the chroma planes: a monochrome clip is an error).
+    `cambi`: libvmaf's cambi banding index of the distorted luma as the extra column cambi (8- and 10-bit clips);
+    `cambi_full_ref` adds cambi_source (the reference's) and cambi_full_reference = max(cambi - cambi_source, 0)."""
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -47,15 +49,18 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
+    if cambi_full_ref and not cambi:
+        raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
         raise ValueError("ciede2000 needs the chroma planes, but the clips are monochrome")
     mdl = M.load_model(model)
     side = (psnr or ssim or ciede)
     n_planes = 1 if (ri.mono or not side) else 3
     feats = N.FEAT_VMAF | (N.FEAT_PSNR if psnr else 0) | (N.FEAT_SSIM if ssim else 0)
-    want_ext = bool(float_ssim or ms_ssim or ciede)
+    want_ext = bool(float_ssim or ms_ssim or ciede or cambi)
     if want_ext:
         feats |= (N.FEAT_FLOAT_SSIM if float_ssim else 0) | (N.FEAT_MS_SSIM if ms_ssim else 0) | (N.FEAT_CIEDE if ciede else 0)
+        feats |= (N.FEAT_CAMBI if cambi else 0) | (N.FEAT_CAMBI_FULL_REF if cambi_full_ref else 0)
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -113,16 +118,21 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     extra = {"ext": ext, "float_ssim": bool(float_ssim), "ms_ssim": bool(ms_ssim)} if want_ext else {}
     if ciede:
         extra["ciede"] = True
+    if cambi:
+        extra["cambi"] = True
+    if cambi_full_ref:
+        extra["cambi_full_ref"] = True
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                           fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
 
 def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim: bool, n_subsample: int = 1,
                    n_planes: int = 1, fps: float = 0.0, ext: np.ndarray | None = None, float_ssim: bool = False,
-                   ms_ssim: bool = False, ciede: bool = False) -> ScoreResult:
+                   ms_ssim: bool = False, ciede: bool = False, cambi: bool = False,
+                   cambi_full_ref: bool = False) -> ScoreResult:
     """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
     / `ciede` the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim /
-    ciede2000 columns."""
+    ciede2000 columns, with `cambi` / `cambi_full_ref` libvmaf's cambi, cambi_source and cambi_full_reference."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -140,15 +150,23 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         sv = rec[:, N.REC_SSIM:N.REC_SSIM + n_planes]
         ssim_lines = report.ssim_stats_lines(sv, plane_sizes)
         metrics["ssim"] = report.ssim_all(sv, plane_sizes)
-    if float_ssim or ms_ssim or ciede:
+    if float_ssim or ms_ssim or ciede or cambi:
         if ext is None or ext.shape != (n, N.EXT_DOUBLES):
-            raise ValueError("float_ssim / ms_ssim / ciede2000 need the extension records of every frame")
+            raise ValueError("float_ssim / ms_ssim / ciede2000 / cambi need the extension records of every frame")
         if float_ssim:
             metrics["float_ssim"] = ext[:, N.EXT_FLOAT_SSIM].copy()
         if ms_ssim:
             metrics["float_ms_ssim"] = ext[:, N.EXT_MS_SSIM].copy()
         if ciede:
             metrics["ciede2000"] = ext[:, N.EXT_CIEDE2000].copy()
+        if cambi:
+            metrics["cambi"] = ext[:, N.EXT_CAMBI].copy()
+            if cambi_full_ref:
+                src = ext[:, N.EXT_CAMBI_SOURCE].copy()
+                metrics["cambi_source"] = src
+                with np.errstate(invalid="ignore"):
+                    metrics["cambi_full_reference"] = np.where(np.isnan(metrics["cambi"]) | np.isnan(src), np.nan,
+                                                               np.maximum(metrics["cambi"] - src, 0.0))
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:

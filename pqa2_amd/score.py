@@ -66,6 +66,9 @@ def main(argv=None) -> int:
     ap.add_argument("--float-ssim", action="store_true", help="add libvmaf's float_ssim feature (per frame and pooled)")
     ap.add_argument("--ms-ssim", action="store_true", help="add libvmaf's float_ms_ssim feature (per frame and pooled)")
     ap.add_argument("--ciede", action="store_true", help="add libvmaf's ciede feature, key ciede2000 (per frame and pooled)")
+    ap.add_argument("--cambi", action="store_true", help="add libvmaf's cambi banding index of the distorted luma")
+    ap.add_argument("--cambi-full-ref", action="store_true",
+                    help="with --cambi: also cambi_source and cambi_full_reference (per frame and pooled)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -102,7 +105,8 @@ def main(argv=None) -> int:
                           n_subsample=a.n_subsample, device=local_rank, rank=rank, world_size=world,
                           gather_device=gather_device, max_batch=a.batch, progress=progress, fixed_point=a.fixed_point,
                           **({"float_ssim": True} if a.float_ssim else {}), **({"ms_ssim": True} if a.ms_ssim else {}),
-                          **({"ciede": True} if a.ciede else {}))
+                          **({"ciede": True} if a.ciede else {}), **({"cambi": True} if a.cambi else {}),
+                          **({"cambi_full_ref": True} if a.cambi_full_ref else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
         return 1

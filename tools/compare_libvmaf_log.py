@@ -144,6 +144,49 @@ def ciede_columns(ref_path, dis_path, use_gpu, n):
     return out
 
 
+# libvmaf cambi (log keys cambi, cambi_source, cambi_full_reference; tests/cambi_ref.py, every constant in CONST) -> VERIFY
+CAMBI_KEYS = ("cambi", "cambi_source", "cambi_full_reference")
+SSIM_IMPLICATES["cambi"] = [
+    "8-bit samples x 4 with no 2x2 anti-dithering average (tests/cambi_ref.py preprocess [VERIFY])",
+    "spatial mask: 7x7 sum of D > 24, T fixed rather than resolution-dependent (CONST mask_threshold [VERIFY])",
+    "window ws = ((65 (W + H)) // 375) >> 4, r = ws >> 1 (CONST ws_* [VERIFY rounding])",
+    "mode filter: min of three distinct values, rows 0 / h-1 keep their decimated samples (mode3 [VERIFY])",
+    "TVI: BT.1886 EOTF Lw = 300, Lb = 0.01, Weber threshold 0.019 (CONST eotf_*, tvi_threshold [VERIFY])",
+    "contrast weights {1, 2, 3, 4} (CONST contrast_weights [VERIFY])",
+    "top-k pooling k = clamp(int(0.6 N), 1, N), unmasked zeros included (CONST topk [VERIFY truncation])",
+    "cambi_full_reference = max(cambi - cambi_source, 0) (full_reference [VERIFY])",
+]
+
+
+def cambi_columns(ref_path, dis_path, use_gpu, n):
+    """{tag: {key: per-frame column}} of the three cambi keys from the restatement and, with use_gpu, the HIP kernels."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cambi_ref as KR
+    from pqa2_amd.yuvio import open_video
+    rr, dr = open_video(ref_path), open_video(dis_path)
+    info = rr.info
+    if info.bit_depth not in KR.CONST["bit_depths"]:
+        raise SystemExit(f"cambi in the log but the clips are {info.bit_depth}-bit (cambi is defined at 8 and 10 bit here)")
+    refs = [rr.frame(i)[0] for i in range(n)]
+    diss = [dr.frame(i)[0] for i in range(n)]
+
+    def cols(dis, src):
+        return {"cambi": dis, "cambi_source": src,
+                "cambi_full_reference": np.array([KR.full_reference(a, b) for a, b in zip(dis, src)])}
+    out = {"restatement (tests/cambi_ref.py)": cols(np.array([KR.cambi(d, info.bit_depth) for d in diss]),
+                                                    np.array([KR.cambi(r, info.bit_depth) for r in refs]))}
+    if use_gpu:
+        from pqa2_amd import _native as N
+        from pqa2_amd.engine import FeatureEngine
+        with FeatureEngine(info.width, info.height, bit_depth=info.bit_depth,
+                           features=N.FEAT_CAMBI | N.FEAT_CAMBI_FULL_REF) as eng:
+            for i in range(n):
+                eng.submit(i, [refs[i]], [diss[i]])
+            ext = eng.collect_ext(0, n)[1]
+        out["HIP kernels (csrc/cambi.hip)"] = cols(ext[:, N.EXT_CAMBI], ext[:, N.EXT_CAMBI_SOURCE])
+    return out
+
+
 def load_log(path):
     with open(path) as f:
         d = json.load(f)
@@ -264,6 +307,19 @@ def main(argv=None) -> int:
                 bad = True
                 for line in SSIM_IMPLICATES["ciede2000"]:
                     print(f"{'':28s}   -> check: {line}")
+    if any(k in log for k in CAMBI_KEYS):
+        for tag, cols in cambi_columns(a.reference, a.distorted, a.gpu, n).items():
+            print(f"\n== cambi: {tag} ==")
+            for key in (k for k in CAMBI_KEYS if k in log):
+                d = np.abs(cols[key][frame_nums] - log[key])
+                j = int(np.nanargmax(d)) if d.size else 0
+                ok = bool(np.nanmax(d) <= a.tol) if d.size else True
+                print(f"{key:28s} {np.nanmax(d) if d.size else 0.0:22.3e} {frame_nums[j] if d.size else 0:9d}   "
+                      f"{a.tol:.0e}   {'ok' if ok else 'MISMATCH'}")
+                if not ok:
+                    bad = True
+                    for line in SSIM_IMPLICATES["cambi"]:
+                        print(f"{'':28s}   -> check: {line}")
     missing = [prefix + f for f in FAMILIES if prefix + f not in log]
     if missing:
         print(f"\nnot in the log (not compared): {', '.join(missing)}")
