@@ -77,8 +77,14 @@ enum {
    * DESIGN.md sections 1 and 5; its host-built tables: pqa_debug_cambi_params. */
   PQA_FEAT_CAMBI = 1u << 9,
   PQA_FEAT_CAMBI_FULL_REF = 1u << 10,
+  /* libvmaf's psnr_hvs (`feature=name=psnr_hvs`): per plane, 8x8 blocks at a step of 7, Daala's integer DCT, contrast
+   * masking and CSF weighting; psnr_hvs_y / _cb / _cr, psnr_hvs and the three plane MSEs in the SECOND extension record
+   * (PQA_EXT2_*, pqa_collect_ext2) on the frames that get VIF / ADM (n_subsample).  Needs n_planes = 3 (PQA_EINVAL naming
+   * psnr_hvs otherwise) and every plane >= 8 x 8; any chroma subsampling, 8, 10 and 12 bit.  Definition and its unpinned
+   * items: DESIGN.md sections 1 and 5; its tables: pqa_debug_psnr_hvs_tables. */
+  PQA_FEAT_PSNR_HVS = 1u << 11,
   PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI |
-                   PQA_FEAT_CAMBI_FULL_REF  /* what pqa_create accepts */
+                   PQA_FEAT_CAMBI_FULL_REF | PQA_FEAT_PSNR_HVS  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -110,6 +116,19 @@ enum {
   PQA_EXT_CAMBI = 22,         /*     cambi of the distorted luma                                        */
   PQA_EXT_CAMBI_SOURCE = 23,  /*     cambi of the reference luma (PQA_FEAT_CAMBI_FULL_REF; NaN without)   */
   PQA_EXT_DOUBLES = 24
+};
+
+/* The SECOND extension record = PQA_EXT2_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and
+ * wrap) when the context runs PQA_FEAT_PSNR_HVS; read with pqa_collect_ext2.  Frames that get no spatial features
+ * (n_subsample) hold NaN, and so does the reserved slot. */
+enum {
+  PQA_EXT2_PSNR_HVS_Y = 0,    /*     psnr_hvs_y = 10 log10(max^2 / mse_Y), max = 2^bpc - 1 (+inf at mse 0)   */
+  PQA_EXT2_PSNR_HVS_CB = 1,   /*     psnr_hvs_cb                                                        */
+  PQA_EXT2_PSNR_HVS_CR = 2,   /*     psnr_hvs_cr                                                        */
+  PQA_EXT2_PSNR_HVS = 3,      /*     psnr_hvs = 10 log10(max^2 / (0.8 mse_Y + 0.1 (mse_Cb + mse_Cr)))     */
+  PQA_EXT2_PSNR_HVS_MSE = 4,  /* [3] mse_Y, mse_Cb, mse_Cr                                               */
+  PQA_EXT2_RESERVED = 7,
+  PQA_EXT2_DOUBLES = 8
 };
 
 typedef struct pqa_config {
@@ -163,6 +182,7 @@ typedef struct pqa_ctx pqa_ctx;
 PQA_API const char* pqa_version(void);
 PQA_API int pqa_record_doubles(void);
 PQA_API int pqa_ext_doubles(void);
+PQA_API int pqa_ext2_doubles(void);
 
 /* Fill cfg with defaults (8-bit 4:2:0, PQA_FEAT_VMAF, gain limits 100). */
 PQA_API void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height);
@@ -259,6 +279,11 @@ PQA_API int pqa_collect(pqa_ctx* ctx, int64_t first_index, int32_t count, double
  * pqa_collect(c, f, n, r) is pqa_collect_ext(c, f, n, r, NULL). */
 PQA_API int pqa_collect_ext(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext);
 
+/* pqa_collect_ext with the second extension record as well: exactly its contract, and in addition
+ * ext2[count][PQA_EXT2_DOUBLES] receives the ext2 rows of the same frames.  ext and ext2 may be NULL.  A context without
+ * PQA_FEAT_PSNR_HVS returns all-NaN ext2 rows. */
+PQA_API int pqa_collect_ext2(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2);
+
 /* Wait for all submitted work without collecting. */
 PQA_API int pqa_sync(pqa_ctx* ctx);
 
@@ -339,6 +364,23 @@ PQA_API int pqa_debug_cambi_params(uint32_t w, uint32_t h, uint32_t bit_depth, i
  * null pointer or a size / depth pqa_create rejects for cambi, PQA_EDEVICE without a device. */
 PQA_API int pqa_debug_cambi_cmap(const void* luma, int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth,
                                  float* cmap, int64_t cap, double* score);
+
+/* Test hook (no device needed): the PQA_FEAT_PSNR_HVS kernel's od_bin_fdct8x8 (its own host / device function) on n
+ * row-major 8 x 8 int32 blocks in[n][64] -> out[n][64] (row i = vertical frequency i).  PQA_EINVAL on a null pointer or
+ * n < 0. */
+PQA_API int pqa_debug_psnr_hvs_dct8x8(const int32_t* in, int32_t* out, int32_t n);
+
+/* Test hook (no device needed): out[PQA_PSNR_HVS_TABLE_FLOATS] = the CSF tables of Y, Cb, Cr ([3][8][8] f32), then the
+ * mask tables M = (0.3885746225901003 CSF)^2 ([3][8][8]).  PQA_EINVAL on a null pointer or a smaller cap. */
+enum { PQA_PSNR_HVS_TABLE_FLOATS = 384 };
+PQA_API int pqa_debug_psnr_hvs_tables(float* out, int32_t cap);
+
+/* Test hook (needs a device): the PQA_FEAT_PSNR_HVS kernel on one w x h plane pair in host memory (u8 at bit_depth 8, u16
+ * above; rows row_pitch_bytes apart) with the tables of plane_kind (0 = Y, 1 = Cb, 2 = Cr).  block_err receives the
+ * per-block error sums, [(h - 1) / 7][(w - 1) / 7] f32 row-major; *mse (nullable) the plane's mse.  PQA_EINVAL on a null
+ * pointer, a plane under 8 x 8, a bad depth, pitch or kind, PQA_EDEVICE without a device. */
+PQA_API int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
+                                     uint32_t bit_depth, uint32_t plane_kind, float* block_err, double* mse);
 
 #ifdef __cplusplus
 }

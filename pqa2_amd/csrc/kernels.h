@@ -284,4 +284,36 @@ hipError_t launch_cambi(hipStream_t stream, Elem elem, PlaneRun luma, int n_fram
                         const CambiParams& prm, const CambiWork& wk, double* ext, int ext_stride, int slot, int slot_base,
                         int slot_step, int capacity);
 
+// ---- PSNR-HVS: libvmaf psnr_hvs (psnr_hvs.hip) ----------------------------------------------------------------------------
+constexpr int kPhvTileRows = 4;       // block rows per workgroup (32 blocks side by side, eight lanes each)
+constexpr int kPhvTableFloats = 384;  // pqa_debug_psnr_hvs_tables: CSF[3][64], M[3][64]
+// Blocks and workgroups of the three planes: plane p owns workgroups [tile0[p], tile0[p + 1]).
+struct PsnrHvsGeometry {
+  int nbx[3], nby[3], tiles_x[3], tile0[4];
+};
+void psnr_hvs_geometry(const int pw[3], const int ph[3], PsnrHvsGeometry* g);
+// The CSF tables (f32) and the mask tables M = (0.3885746225901003 * CSF)^2 as libvmaf stores them: out[kPhvTableFloats].
+void psnr_hvs_tables(float* out);
+// The kernel's od_bin_fdct8x8 (its own __host__ __device__ function) on n row-major 8 x 8 int32 blocks, on the host.
+void psnr_hvs_fdct8x8_host(const int32_t* in, int32_t* out, int n);
+// Once per process before launch_psnr_hvs: uploads the tables to constant memory.
+hipError_t psnr_hvs_prepare();
+// Block error sums of the Y, Cb, Cr planes of n_frames frames (u8 / u16 samples) -> partials [n_frames][geo.tile0[3]]
+// doubles.  block_err (nullable, debug): frame 0's per-block sums of plane dbg_plane, [nby][nbx] f32.
+hipError_t launch_psnr_hvs(hipStream_t stream, Elem elem, const PlaneRun ref[3], const PlaneRun dis[3], int n_frames,
+                           const PsnrHvsGeometry& geo, double* partials, float* block_err = nullptr, int dbg_plane = 0);
+// Per-frame epilogue: fixed-order sums per plane, mse_p = sum / (64 blocks_p), 10 log10(peak^2 / mse) (+inf at 0) and the
+// 0.8 / 0.1 / 0.1 combination, into slots PQA_EXT2_PSNR_HVS_* of the ext2 ring; slot PQA_EXT2_RESERVED is left alone.
+struct PsnrHvsFinalizeArgs {
+  int n_frames;
+  double* ext2;
+  int ext_stride;
+  int slot_base, slot_step, capacity;   // ring row of batch frame f = (slot_base + f * slot_step) % capacity
+  const double* partials;
+  int tile0[4];
+  int blocks[3];
+  double peak;                          // 2^bpc - 1
+};
+hipError_t launch_psnr_hvs_finalize(hipStream_t stream, const PsnrHvsFinalizeArgs& args);
+
 }  // namespace pqa

@@ -135,6 +135,10 @@ struct pqa_ctx {
   CambiParams cambi_prm{};
   CambiWork cambi_wk{};
   int cambi_sb = 0;                  // frames per pass (bounds the work planes at 2160p)
+  // PSNR-HVS (PQA_FEAT_PSNR_HVS; psnr_hvs.hip): nothing is allocated unless the bit is set
+  double* ext2 = nullptr;            // [capacity][PQA_EXT2_DOUBLES] ring beside `records`
+  PsnrHvsGeometry phv_geo{};
+  double* phv_part = nullptr;        // [B][phv_geo.tile0[3]]
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -621,6 +625,33 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
       }
     }
   }
+  if (feat & PQA_FEAT_PSNR_HVS) {
+    // PSNR-HVS on Y, Cb, Cr of the frames that get spatial features, into slots 0..6 of their ext2 rows
+    if (k > 1)
+      HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext2, (int)(first % c->capacity), n, c->capacity, PQA_EXT2_DOUBLES));
+    if (sp_n > 0) {
+      PlaneRun r3[3], d3[3];
+      for (int p = 0; p < 3; ++p) {
+        const PlaneRun rp{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
+        const PlaneRun dp{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
+        r3[p] = k > 1 ? sub(rp) : rp;
+        d3[p] = k > 1 ? sub(dp) : dp;
+      }
+      PsnrHvsFinalizeArgs pa{};
+      pa.n_frames = sp_n;
+      pa.ext2 = c->ext2;
+      pa.ext_stride = PQA_EXT2_DOUBLES;
+      pa.slot_base = (int)((first + e0) % c->capacity);
+      pa.slot_step = k;
+      pa.capacity = c->capacity;
+      pa.partials = c->phv_part;
+      for (int p = 0; p < 4; ++p) pa.tile0[p] = c->phv_geo.tile0[p];
+      for (int p = 0; p < 3; ++p) pa.blocks[p] = c->phv_geo.nbx[p] * c->phv_geo.nby[p];
+      pa.peak = (double)((1 << c->cfg.bit_depth) - 1);
+      HIPCHK(c, launch_psnr_hvs(st_misc, c->elem, r3, d3, sp_n, c->phv_geo, c->phv_part));
+      HIPCHK(c, launch_psnr_hvs_finalize(st_misc, pa));
+    }
+  }
 
   if (multi) {  // join
     HIPCHK(c, hipEventRecord(c->join_ev[0], st_adm));
@@ -934,6 +965,7 @@ extern "C" {
 const char* pqa_version(void) { return "pqa_vmaf 0.2.0 (gfx950; libvmaf-float VIF/ADM/motion, FFmpeg psnr/ssim; VIF scale 0 on the f16 matrix cores)"; }
 int pqa_record_doubles(void) { return PQA_RECORD_DOUBLES; }
 int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
+int pqa_ext2_doubles(void) { return PQA_EXT2_DOUBLES; }
 
 void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
   if (!cfg) return;
@@ -982,6 +1014,13 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     return fail(nullptr, PQA_EINVAL, "cambi full reference (PQA_FEAT_CAMBI_FULL_REF) needs PQA_FEAT_CAMBI");
   if ((cfg->features & PQA_FEAT_CAMBI) && cfg->bit_depth != 8 && cfg->bit_depth != 10)
     return fail(nullptr, PQA_EINVAL, "cambi supports bit depth 8 or 10 (got %u)", cfg->bit_depth);
+  if ((cfg->features & PQA_FEAT_PSNR_HVS) && cfg->n_planes != 3)
+    return fail(nullptr, PQA_EINVAL, "psnr_hvs needs the chroma planes: n_planes must be 3 (got %u)", cfg->n_planes);
+  if ((cfg->features & PQA_FEAT_PSNR_HVS) &&
+      (((cfg->width + (1u << cfg->chroma_hshift) - 1) >> cfg->chroma_hshift) < 8 ||
+       ((cfg->height + (1u << cfg->chroma_vshift) - 1) >> cfg->chroma_vshift) < 8))
+    return fail(nullptr, PQA_EINVAL, "psnr_hvs needs every plane >= 8x8 (frame %ux%u, chroma shifts %u, %u)", cfg->width,
+                cfg->height, cfg->chroma_hshift, cfg->chroma_vshift);
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
   int ndev = 0;
@@ -1204,6 +1243,13 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     CREATE_TRY(dev_alloc(c, &c->cambi_wk.hist, (size_t)kCambiScales * 2048 * SB));
     CREATE_TRY(dev_alloc(c, &c->cambi_wk.sel, (size_t)kCambiScales * 4 * SB));
     CREATE_TRY(dev_alloc(c, &c->cambi_wk.partials, (size_t)cp.chunk[kCambiScales] * SB));
+  }
+  if (cfg->features & PQA_FEAT_PSNR_HVS) {
+    CREATE_HIP(psnr_hvs_prepare());
+    psnr_hvs_geometry(c->pw, c->ph, &c->phv_geo);
+    CREATE_TRY(dev_alloc(c, &c->phv_part, (size_t)c->phv_geo.tile0[3] * B));
+    CREATE_TRY(dev_alloc(c, &c->ext2, (size_t)c->capacity * PQA_EXT2_DOUBLES));
+    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext2, 0, c->capacity, c->capacity, PQA_EXT2_DOUBLES));
   }
   if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)) {
     CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
@@ -1496,10 +1542,14 @@ int pqa_sync(pqa_ctx* c) {
 }
 
 int pqa_collect(pqa_ctx* c, int64_t first_index, int32_t count, double* records) {
-  return pqa_collect_ext(c, first_index, count, records, nullptr);
+  return pqa_collect_ext2(c, first_index, count, records, nullptr, nullptr);
 }
 
 int pqa_collect_ext(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext) {
+  return pqa_collect_ext2(c, first_index, count, records, ext, nullptr);
+}
+
+int pqa_collect_ext2(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2) {
   if (!c) return PQA_EINVAL;
   if (count < 0 || first_index < 0 || (count > 0 && !records)) return fail(c, PQA_EINVAL, "bad argument");
   if (count > c->capacity) return fail(c, PQA_ESTATE, "count %d exceeds result_capacity %d", count, c->capacity);
@@ -1551,6 +1601,12 @@ int pqa_collect_ext(pqa_ctx* c, int64_t first_index, int32_t count, double* reco
                           (size_t)n * PQA_EXT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
     } else if (ext) {      // a context without the SSIM family: nothing it runs has a slot there
       std::fill(ext + (size_t)done * PQA_EXT_DOUBLES, ext + (size_t)(done + n) * PQA_EXT_DOUBLES, __builtin_nan(""));
+    }
+    if (ext2 && c->ext2) {  // so has the second one
+      HIPCHK(c, hipMemcpy(ext2 + (size_t)done * PQA_EXT2_DOUBLES, c->ext2 + (size_t)row * PQA_EXT2_DOUBLES,
+                          (size_t)n * PQA_EXT2_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (ext2) {
+      std::fill(ext2 + (size_t)done * PQA_EXT2_DOUBLES, ext2 + (size_t)(done + n) * PQA_EXT2_DOUBLES, __builtin_nan(""));
     }
     done += n;
     row = 0;
@@ -1805,6 +1861,80 @@ int pqa_debug_cambi_cmap(const void* luma, int64_t row_pitch_bytes, uint32_t w, 
     if (q) hipFree(q);
   if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_cambi_cmap: %s", hipGetErrorString(e));
   if (score) *score = ext_row[PQA_EXT_CAMBI];
+  return PQA_OK;
+}
+
+int pqa_debug_psnr_hvs_dct8x8(const int32_t* in, int32_t* out, int32_t n) {
+  if (!in || !out || n < 0) return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_dct8x8: bad argument");
+  psnr_hvs_fdct8x8_host(in, out, n);
+  return PQA_OK;
+}
+
+int pqa_debug_psnr_hvs_tables(float* out, int32_t cap) {
+  static_assert(kPhvTableFloats == PQA_PSNR_HVS_TABLE_FLOATS, "pqa_debug_psnr_hvs_tables layout");
+  if (!out || cap < PQA_PSNR_HVS_TABLE_FLOATS)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_tables: null or short output");
+  psnr_hvs_tables(out);
+  return PQA_OK;
+}
+
+int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
+                             uint32_t bit_depth, uint32_t plane_kind, float* block_err, double* mse) {
+  if (!ref || !dis || !block_err || w < 8 || h < 8 || w > 16384 || h > 16384 || plane_kind > 2 ||
+      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_plane: bad argument");
+  const int es = bit_depth > 8 ? 2 : 1;
+  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_plane: bad row pitch %lld", (long long)row_pitch_bytes);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
+  // the plane pair stands in for all three planes; plane_kind picks whose tables and block sums are read back
+  const int pw[3] = {(int)w, (int)w, (int)w}, ph[3] = {(int)h, (int)h, (int)h};
+  PsnrHvsGeometry geo{};
+  psnr_hvs_geometry(pw, ph, &geo);
+  const int nb = geo.nbx[0] * geo.nby[0];
+  void *src = nullptr, *dst = nullptr;
+  double *part = nullptr, *ext2 = nullptr;
+  float* err = nullptr;
+  const size_t plane_bytes = (size_t)w * h * es;
+  hipError_t e = psnr_hvs_prepare();
+  if (e == hipSuccess) e = hipMalloc(&src, plane_bytes);
+  if (e == hipSuccess) e = hipMalloc(&dst, plane_bytes);
+  if (e == hipSuccess) e = hipMalloc(&part, (size_t)geo.tile0[3] * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&ext2, PQA_EXT2_DOUBLES * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&err, (size_t)nb * sizeof(float));
+  if (e == hipSuccess)
+    e = hipMemcpy2D(src, (size_t)w * es, ref, (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy2D(dst, (size_t)w * es, dis, (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    PlaneRun r3[3], d3[3];
+    for (int p = 0; p < 3; ++p) {
+      r3[p] = PlaneRun{src, (int64_t)w, (int64_t)w * h};
+      d3[p] = PlaneRun{dst, (int64_t)w, (int64_t)w * h};
+    }
+    e = launch_psnr_hvs(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, r3, d3, 1, geo, part, err, (int)plane_kind);
+  }
+  if (e == hipSuccess) {
+    PsnrHvsFinalizeArgs pa{};
+    pa.n_frames = 1;
+    pa.ext2 = ext2;
+    pa.ext_stride = PQA_EXT2_DOUBLES;
+    pa.slot_base = 0; pa.slot_step = 1; pa.capacity = 1;
+    pa.partials = part;
+    for (int p = 0; p < 4; ++p) pa.tile0[p] = geo.tile0[p];
+    for (int p = 0; p < 3; ++p) pa.blocks[p] = nb;
+    pa.peak = (double)((1 << bit_depth) - 1);
+    e = launch_psnr_hvs_finalize(nullptr, pa);
+  }
+  if (e == hipSuccess) e = hipMemcpy(block_err, err, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost);
+  double row[PQA_EXT2_DOUBLES];
+  if (e == hipSuccess) e = hipMemcpy(row, ext2, sizeof row, hipMemcpyDeviceToHost);
+  for (void* q : {src, dst, (void*)part, (void*)ext2, (void*)err})
+    if (q) hipFree(q);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_psnr_hvs_plane: %s", hipGetErrorString(e));
+  if (mse) *mse = row[PQA_EXT2_PSNR_HVS_MSE + plane_kind];
   return PQA_OK;
 }
 

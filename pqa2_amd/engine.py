@@ -242,6 +242,16 @@ class FeatureEngine:
         self._check(self.lib.pqa_collect_ext(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data))
         return out, ext
 
+    def collect_ext2(self, first_index: int, count: int):
+        """(records [count, 24], ext [count, EXT_DOUBLES], ext2 [count, EXT2_DOUBLES]): collect_ext() plus the second
+        extension rows of the same frames (pqa_collect_ext2; psnr_hvs slots, NaN where the context does not run it)."""
+        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
+        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
+        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
+        self._check(self.lib.pqa_collect_ext2(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
+                                              ext2.ctypes.data))
+        return out, ext, ext2
+
     def flush(self):
         self._check(self.lib.pqa_flush(self._ctx))
 

@@ -29,14 +29,17 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 rank: int = 0, world_size: int = 1, gather_device=None, max_batch: int = 0,
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
                 fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
-                ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False) -> ScoreResult | None:
+                ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False,
+                psnr_hvs: bool = False) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
     `float_ssim` / `ms_ssim`: libvmaf's float_ssim / float_ms_ssim features as extra metric columns (extension record).
     `ciede`: libvmaf's ciede feature as the extra column ciede2000 (needs the chroma planes: a monochrome clip is an error).
     `cambi`: libvmaf's cambi banding index of the distorted luma as the extra column cambi (8- and 10-bit clips);
-    `cambi_full_ref` adds cambi_source (the reference's) and cambi_full_reference = max(cambi - cambi_source, 0)."""
+    `cambi_full_ref` adds cambi_source (the reference's) and cambi_full_reference = max(cambi - cambi_source, 0).
+    `psnr_hvs`: libvmaf's psnr_hvs feature as the extra columns psnr_hvs_y / _cb / _cr and psnr_hvs (second extension
+    record; needs the chroma planes: a monochrome clip is an error)."""
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -53,14 +56,18 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
         raise ValueError("ciede2000 needs the chroma planes, but the clips are monochrome")
+    if psnr_hvs and ri.mono:
+        raise ValueError("psnr_hvs needs the chroma planes, but the clips are monochrome")
     mdl = M.load_model(model)
-    side = (psnr or ssim or ciede)
+    side = (psnr or ssim or ciede or psnr_hvs)
     n_planes = 1 if (ri.mono or not side) else 3
     feats = N.FEAT_VMAF | (N.FEAT_PSNR if psnr else 0) | (N.FEAT_SSIM if ssim else 0)
     want_ext = bool(float_ssim or ms_ssim or ciede or cambi)
     if want_ext:
         feats |= (N.FEAT_FLOAT_SSIM if float_ssim else 0) | (N.FEAT_MS_SSIM if ms_ssim else 0) | (N.FEAT_CIEDE if ciede else 0)
         feats |= (N.FEAT_CAMBI if cambi else 0) | (N.FEAT_CAMBI_FULL_REF if cambi_full_ref else 0)
+    if psnr_hvs:
+        feats |= N.FEAT_PSNR_HVS
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -101,7 +108,11 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             i += m
             if progress is not None:
                 progress(i - a, b - a)
-        if want_ext:
+        local_ext = local_ext2 = None
+        if psnr_hvs:   # the second extension record is read only when psnr_hvs is on: default calls stay as they were
+            local, local_ext, local_ext2 = eng.collect_ext2(a, b - a) if b > a else (
+                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)))
+        elif want_ext:
             local, local_ext = eng.collect_ext(a, b - a) if b > a else (np.zeros((0, N.RECORD_DOUBLES)),
                                                                           np.zeros((0, N.EXT_DOUBLES)))
         else:
@@ -112,6 +123,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
+    ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
     if rank != 0:
         return None
     elapsed = time.perf_counter() - t_start
@@ -122,6 +134,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         extra["cambi"] = True
     if cambi_full_ref:
         extra["cambi_full_ref"] = True
+    if psnr_hvs:
+        extra.update(ext2=ext2, psnr_hvs=True)
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                           fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
@@ -129,10 +143,12 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
 def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim: bool, n_subsample: int = 1,
                    n_planes: int = 1, fps: float = 0.0, ext: np.ndarray | None = None, float_ssim: bool = False,
                    ms_ssim: bool = False, ciede: bool = False, cambi: bool = False,
-                   cambi_full_ref: bool = False) -> ScoreResult:
+                   cambi_full_ref: bool = False, ext2: np.ndarray | None = None, psnr_hvs: bool = False) -> ScoreResult:
     """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
     / `ciede` the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim /
-    ciede2000 columns, with `cambi` / `cambi_full_ref` libvmaf's cambi, cambi_source and cambi_full_reference."""
+    ciede2000 columns, with `cambi` / `cambi_full_ref` libvmaf's cambi, cambi_source and cambi_full_reference.  With
+    `psnr_hvs` the second extension records `ext2` ([n, EXT2_DOUBLES], pqa_collect_ext2) add psnr_hvs_y / _cb / _cr and
+    psnr_hvs."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -167,6 +183,12 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
                 with np.errstate(invalid="ignore"):
                     metrics["cambi_full_reference"] = np.where(np.isnan(metrics["cambi"]) | np.isnan(src), np.nan,
                                                                np.maximum(metrics["cambi"] - src, 0.0))
+    if psnr_hvs:
+        if ext2 is None or ext2.shape != (n, N.EXT2_DOUBLES):
+            raise ValueError("psnr_hvs needs the second extension records of every frame")
+        for key, slot in (("psnr_hvs_y", N.EXT2_PSNR_HVS_Y), ("psnr_hvs_cb", N.EXT2_PSNR_HVS_CB),
+                          ("psnr_hvs_cr", N.EXT2_PSNR_HVS_CR), ("psnr_hvs", N.EXT2_PSNR_HVS)):
+            metrics[key] = ext2[:, slot].copy()
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:

@@ -69,6 +69,8 @@ def main(argv=None) -> int:
     ap.add_argument("--cambi", action="store_true", help="add libvmaf's cambi banding index of the distorted luma")
     ap.add_argument("--cambi-full-ref", action="store_true",
                     help="with --cambi: also cambi_source and cambi_full_reference (per frame and pooled)")
+    ap.add_argument("--psnr-hvs", action="store_true",
+                    help="add libvmaf's psnr_hvs feature: psnr_hvs_y / _cb / _cr and psnr_hvs (per frame and pooled)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -106,7 +108,8 @@ def main(argv=None) -> int:
                           gather_device=gather_device, max_batch=a.batch, progress=progress, fixed_point=a.fixed_point,
                           **({"float_ssim": True} if a.float_ssim else {}), **({"ms_ssim": True} if a.ms_ssim else {}),
                           **({"ciede": True} if a.ciede else {}), **({"cambi": True} if a.cambi else {}),
-                          **({"cambi_full_ref": True} if a.cambi_full_ref else {}))
+                          **({"cambi_full_ref": True} if a.cambi_full_ref else {}),
+                          **({"psnr_hvs": True} if a.psnr_hvs else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
         return 1

@@ -152,6 +152,7 @@ class VMAFAnalyzer(QObject):
         self.ciede_enabled = False            # libvmaf ciede (feature=name=ciede, key ciede2000) per frame and pooled
         self.cambi_enabled = False            # libvmaf cambi banding index (feature=name=cambi) of the distorted luma
         self.cambi_full_ref_enabled = False   # with cambi: cambi_source and cambi_full_reference (full-reference mode)
+        self.psnr_hvs_enabled = False         # libvmaf psnr_hvs (feature=name=psnr_hvs): psnr_hvs_y / _cb / _cr, psnr_hvs
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -174,6 +175,7 @@ class VMAFAnalyzer(QObject):
             self.ciede_enabled = bool(s.get("ciede_enabled", False))
             self.cambi_enabled = bool(s.get("cambi_enabled", False))
             self.cambi_full_ref_enabled = bool(s.get("cambi_full_ref_enabled", False))
+            self.psnr_hvs_enabled = bool(s.get("psnr_hvs_enabled", False))
             logger.info(f"VMAF options set from manager: threads={self.threads}, "
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
@@ -192,7 +194,7 @@ class VMAFAnalyzer(QObject):
     def set_advanced_options(self, pool_method="mean", enable_motion_score=False, enable_temporal_features=False,
                              feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
                              ms_ssim_enabled=False, ciede_enabled=False, cambi_enabled=False,
-                             cambi_full_ref_enabled=False):
+                             cambi_full_ref_enabled=False, psnr_hvs_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -204,6 +206,7 @@ class VMAFAnalyzer(QObject):
         self.ciede_enabled = bool(ciede_enabled)
         self.cambi_enabled = bool(cambi_enabled)
         self.cambi_full_ref_enabled = bool(cambi_full_ref_enabled)
+        self.psnr_hvs_enabled = bool(psnr_hvs_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -385,13 +388,14 @@ class VMAFAnalyzer(QObject):
         return True
 
     def _ssim_family_kwargs(self):
-        """score_files keywords of the extension features (SSIM family, ciede, cambi): only the enabled ones (the default
-        call is the one it always was).  cambi_full_ref counts only together with cambi."""
+        """score_files keywords of the extension features (SSIM family, ciede, cambi, psnr_hvs): only the enabled ones (the
+        default call is the one it always was).  cambi_full_ref counts only together with cambi."""
         return {**({"float_ssim": True} if self.float_ssim_enabled else {}),
                 **({"ms_ssim": True} if self.ms_ssim_enabled else {}),
                 **({"ciede": True} if self.ciede_enabled else {}),
                 **({"cambi": True} if self.cambi_enabled else {}),
-                **({"cambi_full_ref": True} if self.cambi_enabled and self.cambi_full_ref_enabled else {})}
+                **({"cambi_full_ref": True} if self.cambi_enabled and self.cambi_full_ref_enabled else {}),
+                **({"psnr_hvs": True} if self.psnr_hvs_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -414,6 +418,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--ciede"]
         if self.cambi_enabled:
             cmd += ["--cambi"] + (["--cambi-full-ref"] if self.cambi_full_ref_enabled else [])
+        if self.psnr_hvs_enabled:
+            cmd += ["--psnr-hvs"]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -511,7 +517,9 @@ class VMAFAnalyzer(QObject):
             for enabled, key in ((self.float_ssim_enabled, "float_ssim"), (self.ms_ssim_enabled, "float_ms_ssim"),
                                  (self.ciede_enabled, "ciede2000"), (self.cambi_enabled, "cambi"),
                                  (self.cambi_enabled and self.cambi_full_ref_enabled, "cambi_source"),
-                                 (self.cambi_enabled and self.cambi_full_ref_enabled, "cambi_full_reference")):
+                                 (self.cambi_enabled and self.cambi_full_ref_enabled, "cambi_full_reference"),
+                                 (self.psnr_hvs_enabled, "psnr_hvs_y"), (self.psnr_hvs_enabled, "psnr_hvs_cb"),
+                                 (self.psnr_hvs_enabled, "psnr_hvs_cr"), (self.psnr_hvs_enabled, "psnr_hvs")):
                 if enabled:
                     results[key] = pooled[key]["mean"] if key in pooled else None
             self.analysis_progress.emit(100)

@@ -187,6 +187,44 @@ def cambi_columns(ref_path, dis_path, use_gpu, n):
     return out
 
 
+# libvmaf psnr_hvs (log keys psnr_hvs_y / _cb / _cr, psnr_hvs; tests/psnr_hvs_ref.py, every constant in CONST) -> VERIFY
+PSNR_HVS_KEYS = ("psnr_hvs_y", "psnr_hvs_cb", "psnr_hvs_cr", "psnr_hvs")
+SSIM_IMPLICATES["psnr_hvs"] = [
+    "samples as raw codes with max = 2^bpc - 1, or libvmaf's float copy scaled to 8 bit and truncated to int16 at "
+    "10 / 12 bit (tests/psnr_hvs_ref.py blocks_of, db [VERIFY])",
+    "od_bin_fdct8 lifting constants and the rounding of OD_DCT_RSHIFT (CONST lifts, _rshift [VERIFY])",
+    "coef^2 of the mask formed in int or in float (exact either way below 2^31 here; f32 rounding above 2^24) [VERIFY]",
+    "the 4:2:0 chroma CSF tables used for 4:2:2 and 4:4:4 too (CONST csf_cb420 / csf_cr420 [VERIFY])",
+    "psnr_hvs from 0.8 mse_Y + 0.1 (mse_Cb + mse_Cr) before the dB step (CONST weights [VERIFY])",
+    "the value written at mse 0 (here +inf, as psnr's inf) [VERIFY]",
+]
+
+
+def psnr_hvs_columns(ref_path, dis_path, use_gpu, n):
+    """{tag: {key: per-frame column}} of the four psnr_hvs keys from the restatement and, with use_gpu, the HIP kernel."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import psnr_hvs_ref as HR
+    from pqa2_amd.yuvio import open_video
+    rr, dr = open_video(ref_path), open_video(dis_path)
+    info = rr.info
+    if info.mono:
+        raise SystemExit("psnr_hvs in the log but the clips are monochrome (psnr_hvs needs the chroma planes)")
+    frames = [(rr.frame(i), dr.frame(i)) for i in range(n)]
+    res = [HR.psnr_hvs(r, d, info.bit_depth) for r, d in frames]
+    out = {"restatement (tests/psnr_hvs_ref.py)": {k: np.array([x[k] for x in res]) for k in PSNR_HVS_KEYS}}
+    if use_gpu:
+        from pqa2_amd import _native as N
+        from pqa2_amd.engine import FeatureEngine
+        with FeatureEngine(info.width, info.height, bit_depth=info.bit_depth, n_planes=3,
+                           chroma_shift=(info.hshift, info.vshift), features=N.FEAT_PSNR_HVS) as eng:
+            for i, (r, d) in enumerate(frames):
+                eng.submit(i, r, d)
+            ext2 = eng.collect_ext2(0, n)[2]
+        out["HIP kernel (csrc/psnr_hvs.hip)"] = {k: ext2[:, s] for k, s in zip(
+            PSNR_HVS_KEYS, (N.EXT2_PSNR_HVS_Y, N.EXT2_PSNR_HVS_CB, N.EXT2_PSNR_HVS_CR, N.EXT2_PSNR_HVS))}
+    return out
+
+
 def load_log(path):
     with open(path) as f:
         d = json.load(f)
@@ -319,6 +357,20 @@ def main(argv=None) -> int:
                 if not ok:
                     bad = True
                     for line in SSIM_IMPLICATES["cambi"]:
+                        print(f"{'':28s}   -> check: {line}")
+    if any(k in log for k in PSNR_HVS_KEYS):
+        for tag, cols in psnr_hvs_columns(a.reference, a.distorted, a.gpu, n).items():
+            print(f"\n== psnr_hvs: {tag} ==")
+            for key in (k for k in PSNR_HVS_KEYS if k in log):
+                d = np.abs(cols[key][frame_nums] - log[key])
+                d = np.where(np.isinf(cols[key][frame_nums]) & (cols[key][frame_nums] == log[key]), 0.0, d)
+                j = int(np.nanargmax(d)) if d.size else 0
+                ok = bool(np.nanmax(d) <= a.tol) if d.size else True
+                print(f"{key:28s} {np.nanmax(d) if d.size else 0.0:22.3e} {frame_nums[j] if d.size else 0:9d}   "
+                      f"{a.tol:.0e}   {'ok' if ok else 'MISMATCH'}")
+                if not ok:
+                    bad = True
+                    for line in SSIM_IMPLICATES["psnr_hvs"]:
                         print(f"{'':28s}   -> check: {line}")
     missing = [prefix + f for f in FAMILIES if prefix + f not in log]
     if missing:
