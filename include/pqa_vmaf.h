@@ -83,8 +83,19 @@ enum {
    * psnr_hvs otherwise) and every plane >= 8 x 8; any chroma subsampling, 8, 10 and 12 bit.  Definition and its unpinned
    * items: DESIGN.md sections 1 and 5; its tables: pqa_debug_psnr_hvs_tables. */
   PQA_FEAT_PSNR_HVS = 1u << 11,
+  /* FFmpeg's xpsnr filter (libavfilter/vf_xpsnr.c, FFmpeg >= 7.0): PSNR with per-block weights from the reference's
+   * spatial and temporal activity; XPSNR y / u / v and the three WSSE values in the THIRD extension record (PQA_EXT3_*,
+   * pqa_collect_ext3) on EVERY frame, like psnr / ssim, whatever n_subsample is.  The temporal term reads the previous one
+   * (first order) or two (PQA_FEAT_XPSNR_HFR: second order, for integer frame rates >= 32) reference frames of the chain:
+   * the frames before it in the batch, the pair the context keeps from its previous batch, or the history armed with
+   * pqa_set_ref_history; zero planes at a chain start.  n_planes 1 or 3, any chroma subsampling, 8, 10 and 12 bit.
+   * PQA_EINVAL naming xpsnr for an odd width or height when w * h > 2048 * 1152 (2 x 2 activity), and for
+   * PQA_FEAT_XPSNR_HFR without PQA_FEAT_XPSNR.  Definition and its unpinned items: DESIGN.md sections 1 and 5; its block
+   * sums: pqa_debug_xpsnr_blocks. */
+  PQA_FEAT_XPSNR = 1u << 12,
+  PQA_FEAT_XPSNR_HFR = 1u << 13,
   PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI |
-                   PQA_FEAT_CAMBI_FULL_REF | PQA_FEAT_PSNR_HVS  /* what pqa_create accepts */
+                   PQA_FEAT_CAMBI_FULL_REF | PQA_FEAT_PSNR_HVS | PQA_FEAT_XPSNR | PQA_FEAT_XPSNR_HFR  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -129,6 +140,18 @@ enum {
   PQA_EXT2_PSNR_HVS_MSE = 4,  /* [3] mse_Y, mse_Cb, mse_Cr                                               */
   PQA_EXT2_RESERVED = 7,
   PQA_EXT2_DOUBLES = 8
+};
+
+/* The THIRD extension record = PQA_EXT3_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and
+ * wrap) when the context runs PQA_FEAT_XPSNR; read with pqa_collect_ext3.  Every submitted frame gets its row; slots of
+ * planes the context does not have (n_planes 1) and the reserved slots hold NaN. */
+enum {
+  PQA_EXT3_XPSNR_Y = 0,     /*     XPSNR y = 10 log10(w h (2^bpc - 1)^2 / WSSE_Y) (+inf at WSSE 0)          */
+  PQA_EXT3_XPSNR_U = 1,     /*     XPSNR u (chroma plane size)                                            */
+  PQA_EXT3_XPSNR_V = 2,     /*     XPSNR v                                                                */
+  PQA_EXT3_WSSE = 3,        /* [3] WSSE Y, U, V: integers, exact as doubles                                 */
+  PQA_EXT3_RESERVED = 6,    /* [2]                                                                        */
+  PQA_EXT3_DOUBLES = 8
 };
 
 typedef struct pqa_config {
@@ -183,6 +206,7 @@ PQA_API const char* pqa_version(void);
 PQA_API int pqa_record_doubles(void);
 PQA_API int pqa_ext_doubles(void);
 PQA_API int pqa_ext2_doubles(void);
+PQA_API int pqa_ext3_doubles(void);
 
 /* Fill cfg with defaults (8-bit 4:2:0, PQA_FEAT_VMAF, gain limits 100). */
 PQA_API void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height);
@@ -259,8 +283,16 @@ typedef struct pqa_surface_clip {
 PQA_API int pqa_submit_surfaces(pqa_ctx* ctx, int64_t first_index, int32_t n_frames, const pqa_surface_clip* ref,
                                 const pqa_surface_clip* dis, const pqa_surface_clip* prev_ref);
 
-/* Host-memory variant of the halo for the pqa_submit path. */
+/* Host-memory variant of the halo for the pqa_submit path.  pqa_set_motion_halo(c, p, s) is
+ * pqa_set_ref_history(c, &p, 1, s); p == NULL restarts the chain (n_prev = 0). */
 PQA_API int pqa_set_motion_halo(pqa_ctx* ctx, const void* prev_ref_luma_host, int64_t row_stride);
+
+/* The reference history in front of the next submitted frame (call it before that frame, e.g. frames a-1 and a-2 of a
+ * frame-sharded rank that starts at a): prev_luma_host[0] is the luma of reference frame first-1, prev_luma_host[1] that
+ * of first-2 (rows row_stride bytes apart), n_prev of them (0, 1 or 2; a missing one is a zero plane, as at a chain
+ * start).  It arms motion's halo from prev_luma_host[0] exactly as pqa_set_motion_halo does, and PQA_FEAT_XPSNR's
+ * temporal history from both; n_prev = 0 restarts the chain.  PQA_EINVAL on n_prev outside 0..2 or a null plane. */
+PQA_API int pqa_set_ref_history(pqa_ctx* ctx, const void* const* prev_luma_host, int32_t n_prev, int64_t row_stride);
 
 /* Launch whatever pqa_submit has pending (partial batch). */
 PQA_API int pqa_flush(pqa_ctx* ctx);
@@ -284,6 +316,11 @@ PQA_API int pqa_collect_ext(pqa_ctx* ctx, int64_t first_index, int32_t count, do
  * PQA_FEAT_PSNR_HVS returns all-NaN ext2 rows. */
 PQA_API int pqa_collect_ext2(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2);
 
+/* pqa_collect_ext2 with the third extension record as well: ext3[count][PQA_EXT3_DOUBLES] receives the ext3 rows of the
+ * same frames.  ext, ext2 and ext3 may be NULL.  A context without PQA_FEAT_XPSNR returns all-NaN ext3 rows. */
+PQA_API int pqa_collect_ext3(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
+                             double* ext3);
+
 /* Wait for all submitted work without collecting. */
 PQA_API int pqa_sync(pqa_ctx* ctx);
 
@@ -291,7 +328,7 @@ PQA_API int pqa_sync(pqa_ctx* ctx);
  * PQA_ECANCELLED.  Mirrors VMAFAnalyzer.terminate_analysis (app/vmaf_analyzer.py:139-151). */
 PQA_API int pqa_cancel(pqa_ctx* ctx);
 
-/* Clear the cancel flag and the motion continuity state (start of a new clip). */
+/* Clear the cancel flag and the motion / xpsnr continuity state (start of a new clip). */
 PQA_API int pqa_reset(pqa_ctx* ctx);
 
 /* Text of the most recent failure on this context (ctx == NULL: last pqa_create failure). */
@@ -381,6 +418,15 @@ PQA_API int pqa_debug_psnr_hvs_tables(float* out, int32_t cap);
  * pointer, a plane under 8 x 8, a bad depth, pitch or kind, PQA_EDEVICE without a device. */
 PQA_API int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
                                      uint32_t bit_depth, uint32_t plane_kind, float* block_err, double* mse);
+
+/* Test hook (needs a device): the PQA_FEAT_XPSNR kernels on one w x h luma plane (u8 at bit_depth 8, u16 above; rows
+ * row_pitch_bytes apart) with ref_m1 / ref_m2 (nullable: zero planes) as the reference frames one and two before it and
+ * hfr selecting the second-order temporal term.  out receives [blocks][3] = {sse, sa, ta} per luma block in raster
+ * order, blocks = ceil(w / b) * ceil(h / b) (one block covering the plane when b < 4, with sa = ta = 0); *wsse (nullable)
+ * the plane's WSSE.  PQA_EINVAL on a null pointer, a bad size, depth or pitch, PQA_EDEVICE without a device. */
+PQA_API int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const void* ref_m2, const void* dis,
+                                   int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth, int32_t hfr,
+                                   uint64_t* out, double* wsse);
 
 #ifdef __cplusplus
 }

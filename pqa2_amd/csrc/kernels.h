@@ -316,4 +316,36 @@ struct PsnrHvsFinalizeArgs {
 };
 hipError_t launch_psnr_hvs_finalize(hipStream_t stream, const PsnrHvsFinalizeArgs& args);
 
+// ---- XPSNR: FFmpeg's xpsnr filter (xpsnr.hip) --------------------------------------------------------------------------
+constexpr int kXpStrip = 16;          // block rows per LDS strip (even: 2 x 2 groups never straddle two strips)
+constexpr int kXpLdsCols = 732;       // the widest block (b = 728 at 16384 x 16384) plus the 2-column halo on each side
+constexpr int kXpBlockVals = 5;       // per block: luma sse, sa, ta, then the SSE of chroma block k of U and V
+constexpr unsigned long long kXpGamma = 2;   // XPSNR_GAMMA: the temporal term's weight
+// The frame's block grids (vf_xpsnr.c get_wsse).  plain (b < 4): one block per plane and WSSE = SSE.
+struct XpsnrGeometry {
+  int W, H, Wc, Hc, n_planes, bit_depth;
+  int b, bv, smooth, plain;
+  int bsx, bsy, w_blk, h_blk, n_blk;      // luma blocks (bsx = bsy = b unless plain)
+  int cbx, cby, cw_blk, ch_blk, nc_blk;   // chroma blocks: (b * Wc) / W x (b * Hc) / H
+  double A;                               // sqrt(16 * 2^(2d - 9) / sqrt(max(1e-5, W H / (3840 * 2160))))
+};
+void xpsnr_geometry(int w, int h, int wc, int hc, int n_planes, int bit_depth, XpsnrGeometry* g);
+// Exact block sums of n_frames frames (u8 / u16 samples): out[n_frames][geo.n_blk][kXpBlockVals].  Frame f's predecessors
+// are frames f - 1 and f - 2 of the run; h1 / h2 (nullptr: zero planes; row pitches in elements) stand for frames -1 and -2.
+hipError_t launch_xpsnr_blocks(hipStream_t stream, Elem elem, const PlaneRun ref[3], const PlaneRun dis[3], int n_frames,
+                               const void* h1, int64_t h1_pitch, const void* h2, int64_t h2_pitch, bool hfr,
+                               const XpsnrGeometry& geo, unsigned long long* out);
+// Per frame: weights (into wbuf [n_frames][geo.n_blk]), smoothing, WSSE and dB into slots 0..5 of ring row
+// (slot_base + f) % capacity of ext3; the reserved slots are left alone.
+struct XpFinalizeArgs {
+  int n_frames;
+  const unsigned long long* blk;
+  double* wbuf;
+  double* ext3;
+  int ext_stride, slot_base, capacity;
+  XpsnrGeometry g;
+};
+hipError_t launch_xpsnr_finalize(hipStream_t stream, const XpFinalizeArgs& args);
+
 }  // namespace pqa
+

@@ -139,6 +139,17 @@ struct pqa_ctx {
   double* ext2 = nullptr;            // [capacity][PQA_EXT2_DOUBLES] ring beside `records`
   PsnrHvsGeometry phv_geo{};
   double* phv_part = nullptr;        // [B][phv_geo.tile0[3]]
+  // XPSNR (PQA_FEAT_XPSNR; xpsnr.hip): nothing is allocated unless the bit is set
+  double* ext3 = nullptr;            // [capacity][PQA_EXT3_DOUBLES] ring beside `records`
+  XpsnrGeometry xp_geo{};
+  unsigned long long* xp_blk = nullptr;   // [B][xp_geo.n_blk][kXpBlockVals]
+  double* xp_w = nullptr;                 // [B][xp_geo.n_blk] weights
+  uint8_t* xp_hist[2] = {nullptr, nullptr};   // reference luma planes the chain keeps (the last two of the last batch)
+  int64_t xp_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
+  int64_t xp_hist_pitch = 0;                  // bytes
+  uint8_t* xp_prev = nullptr;        // pqa_submit_surfaces: its shifted prev_ref (allocated on first use)
+  int64_t xp_last = -1;              // last frame of the previous batch (the chain continues at xp_last + 1)
+  int xp_armed = -1;                 // pqa_set_ref_history: planes armed in xp_hist[0..n) for the next batch (-1: none)
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -652,6 +663,49 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
       HIPCHK(c, launch_psnr_hvs_finalize(st_misc, pa));
     }
   }
+  // XPSNR on every frame: its predecessors come from the batch, the caller's halo, the kept pair or the armed history
+  int xp_h1 = -1;   // xp_hist slot that held frame first-1 (-1: the caller's plane or none)
+  if (feat & PQA_FEAT_XPSNR) {
+    if (c->xp_armed >= 0) {
+      c->xp_hist_idx[0] = c->xp_armed >= 1 ? first - 1 : -1;
+      c->xp_hist_idx[1] = c->xp_armed >= 2 ? first - 2 : -1;
+      c->xp_armed = -1;
+    } else if (c->xp_last != first - 1) {   // a chain start: zero planes
+      c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
+    }
+    const auto held = [&](int64_t idx) {   // -1 marks an empty slot: frames before 0 are never held
+      return idx < 0 ? -1 : c->xp_hist_idx[0] == idx ? 0 : c->xp_hist_idx[1] == idx ? 1 : -1;
+    };
+    xp_h1 = held(first - 1);
+    const int j2 = held(first - 2);
+    const void* h1 = nullptr;
+    int64_t hp1 = 0;
+    if (prev) {
+      if (prev_pitch_bytes % es) return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
+      h1 = prev; hp1 = prev_pitch_bytes / es;
+    } else if (xp_h1 >= 0) {
+      h1 = c->xp_hist[xp_h1]; hp1 = c->xp_hist_pitch / es;
+    }
+    const void* h2 = j2 >= 0 ? c->xp_hist[j2] : nullptr;
+    const int64_t hp2 = j2 >= 0 ? c->xp_hist_pitch / es : 0;
+    PlaneRun r3[3], d3[3];
+    for (int p = 0; p < c->n_planes; ++p) {
+      r3[p] = PlaneRun{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
+      d3[p] = PlaneRun{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
+    }
+    XpFinalizeArgs xa{};
+    xa.n_frames = n;
+    xa.blk = c->xp_blk;
+    xa.wbuf = c->xp_w;
+    xa.ext3 = c->ext3;
+    xa.ext_stride = PQA_EXT3_DOUBLES;
+    xa.slot_base = (int)(first % c->capacity);
+    xa.capacity = c->capacity;
+    xa.g = c->xp_geo;
+    HIPCHK(c, launch_xpsnr_blocks(st_misc, c->elem, r3, d3, n, h1, hp1, h2, hp2, (feat & PQA_FEAT_XPSNR_HFR) != 0,
+                                  c->xp_geo, c->xp_blk));
+    HIPCHK(c, launch_xpsnr_finalize(st_misc, xa));
+  }
 
   if (multi) {  // join
     HIPCHK(c, hipEventRecord(c->join_ev[0], st_adm));
@@ -725,6 +779,29 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
     c->have_last = true;
     c->halo_armed = false;
     c->last_index = first + n - 1;
+  }
+  if (feat & PQA_FEAT_XPSNR) {
+    // keep the chain's last two reference luma planes (behind the join: this batch's kernels have read the old ones)
+    const size_t row_bytes = (size_t)w * es;
+    const auto keep = [&](int slot, const void* src, int64_t pitch, int64_t idx) -> hipError_t {
+      c->xp_hist_idx[slot] = idx;
+      return hipMemcpy2DAsync(c->xp_hist[slot], c->xp_hist_pitch, src, pitch, row_bytes, h, hipMemcpyDeviceToDevice, st);
+    };
+    const auto frame = [&](int f) { return (const uint8_t*)ref->plane[0] + (int64_t)f * ref->frame_pitch[0]; };
+    if (n >= 2) {
+      HIPCHK(c, keep(0, frame(n - 2), ref->row_pitch[0], first + n - 2));
+      HIPCHK(c, keep(1, frame(n - 1), ref->row_pitch[0], first + n - 1));
+    } else if (n == 1) {
+      int older = xp_h1;   // frame first-1 stays where it is, or comes from the caller's plane
+      if (older < 0 && prev) {
+        older = 0;
+        HIPCHK(c, keep(0, prev, prev_pitch_bytes, first - 1));
+      }
+      const int slot = older == 0 ? 1 : 0;
+      if (older < 0) c->xp_hist_idx[1] = -1;
+      HIPCHK(c, keep(slot, frame(0), ref->row_pitch[0], first));
+    }
+    c->xp_last = first + n - 1;
   }
   return PQA_OK;
 }
@@ -966,6 +1043,7 @@ const char* pqa_version(void) { return "pqa_vmaf 0.2.0 (gfx950; libvmaf-float VI
 int pqa_record_doubles(void) { return PQA_RECORD_DOUBLES; }
 int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
 int pqa_ext2_doubles(void) { return PQA_EXT2_DOUBLES; }
+int pqa_ext3_doubles(void) { return PQA_EXT3_DOUBLES; }
 
 void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
   if (!cfg) return;
@@ -1021,6 +1099,20 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
        ((cfg->height + (1u << cfg->chroma_vshift) - 1) >> cfg->chroma_vshift) < 8))
     return fail(nullptr, PQA_EINVAL, "psnr_hvs needs every plane >= 8x8 (frame %ux%u, chroma shifts %u, %u)", cfg->width,
                 cfg->height, cfg->chroma_hshift, cfg->chroma_vshift);
+  if ((cfg->features & PQA_FEAT_XPSNR_HFR) && !(cfg->features & PQA_FEAT_XPSNR))
+    return fail(nullptr, PQA_EINVAL, "xpsnr second-order term (PQA_FEAT_XPSNR_HFR) needs PQA_FEAT_XPSNR");
+  if (cfg->features & PQA_FEAT_XPSNR) {
+    XpsnrGeometry g{};
+    xpsnr_geometry((int)cfg->width, (int)cfg->height, (int)((cfg->width + (1u << cfg->chroma_hshift) - 1) >> cfg->chroma_hshift),
+                   (int)((cfg->height + (1u << cfg->chroma_vshift) - 1) >> cfg->chroma_vshift), (int)cfg->n_planes,
+                   (int)cfg->bit_depth, &g);
+    if (g.bv == 2 && ((cfg->width | cfg->height) & 1))
+      return fail(nullptr, PQA_EINVAL, "xpsnr needs an even width and height above 2048x1152 (its 2x2 activity; got %ux%u)",
+                  cfg->width, cfg->height);
+    if (g.nc_blk > g.n_blk || (cfg->n_planes == 3 && g.nc_blk == 0) || g.bsx + 4 > kXpLdsCols)
+      return fail(nullptr, PQA_EINVAL, "xpsnr: unsupported block grid for %ux%u (chroma shifts %u, %u)", cfg->width,
+                  cfg->height, cfg->chroma_hshift, cfg->chroma_vshift);
+  }
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
   int ndev = 0;
@@ -1251,6 +1343,15 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     CREATE_TRY(dev_alloc(c, &c->ext2, (size_t)c->capacity * PQA_EXT2_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext2, 0, c->capacity, c->capacity, PQA_EXT2_DOUBLES));
   }
+  if (cfg->features & PQA_FEAT_XPSNR) {
+    xpsnr_geometry(c->pw[0], c->ph[0], c->pw[1], c->ph[1], c->n_planes, (int)cfg->bit_depth, &c->xp_geo);
+    CREATE_TRY(dev_alloc(c, &c->xp_blk, (size_t)c->xp_geo.n_blk * kXpBlockVals * B));
+    CREATE_TRY(dev_alloc(c, &c->xp_w, (size_t)c->xp_geo.n_blk * B));
+    c->xp_hist_pitch = round_up((int64_t)w * c->esize, 64);
+    for (int j = 0; j < 2; ++j) CREATE_TRY(dev_alloc(c, &c->xp_hist[j], (size_t)c->xp_hist_pitch * h));
+    CREATE_TRY(dev_alloc(c, &c->ext3, (size_t)c->capacity * PQA_EXT3_DOUBLES));
+    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext3, 0, c->capacity, c->capacity, PQA_EXT3_DOUBLES));
+  }
   if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)) {
     CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext, 0, c->capacity, c->capacity, PQA_EXT_DOUBLES));
@@ -1410,6 +1511,14 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
       c->halo_armed = true;
     }
   }
+  if (prev_ref && (c->cfg.features & PQA_FEAT_XPSNR) && shift_luma) {   // xpsnr's frame first-1, shifted down likewise
+    if (!c->xp_prev) {
+      HIPCHK(c, hipMalloc((void**)&c->xp_prev, (size_t)c->xp_hist_pitch * c->ph[0]));
+      c->allocs.push_back(c->xp_prev);
+    }
+    HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->xp_prev, c->xp_hist_pitch, 0,
+                                    c->pw[0], c->ph[0], shift, 1));
+  }
   const int n_launch = (n_frames + c->B - 1) / c->B;   // equal launches, as in pqa_submit_device
   const int per = n_launch ? (n_frames + n_launch - 1) / n_launch : 0;
   for (int done = 0; done < n_frames;) {
@@ -1446,6 +1555,9 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     const void* prev = nullptr;
     int64_t prev_pitch = 0;
     if (done == 0 && prev_ref && !shift_luma) { prev = prev_ref->luma; prev_pitch = prev_ref->luma_row_pitch; }
+    if (done == 0 && prev_ref && shift_luma && (c->cfg.features & PQA_FEAT_XPSNR)) {   // the same frame as the armed halo
+      prev = c->xp_prev; prev_pitch = c->xp_hist_pitch;
+    }
     rc = process_batch(c, first_index + done, n, &r, &d, prev, prev_pitch);
     if (rc != PQA_OK) return rc;
     done += n;
@@ -1504,22 +1616,51 @@ int pqa_submit_fd_run(pqa_ctx* c, int64_t first_index, int32_t n_frames, int ref
   return submit_run(c, first_index, n_frames, src, step);
 }
 
-int pqa_set_motion_halo(pqa_ctx* c, const void* prev_ref_luma_host, int64_t row_stride) {
-  if (!c) return PQA_EINVAL;
-  if (!(c->cfg.features & PQA_FEAT_MOTION)) return PQA_OK;
+namespace {
+// pqa_set_motion_halo / pqa_set_ref_history: motion's halo from prev[0], xpsnr's history from prev[0..n_prev)
+int set_history(pqa_ctx* c, const void* const* prev, int n_prev, int64_t row_stride) {
+  const bool mot = c->cfg.features & PQA_FEAT_MOTION, xp = c->cfg.features & PQA_FEAT_XPSNR;
+  if (!mot && !xp) return PQA_OK;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = flush_pending(c);
   if (rc != PQA_OK) return rc;
-  if (!prev_ref_luma_host) {
+  if (n_prev == 0) {   // a chain start
     c->halo_armed = false;
     c->have_last = false;
+    c->xp_armed = -1;
+    c->xp_last = -1;
+    c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
     return PQA_OK;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy2D(c->last_luma, c->last_luma_pitch, prev_ref_luma_host, row_stride, (size_t)c->pw[0] * c->esize,
-                        c->ph[0], hipMemcpyHostToDevice));
-  c->halo_armed = true;
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  if (mot) {
+    HIPCHK(c, hipMemcpy2D(c->last_luma, c->last_luma_pitch, prev[0], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
+    c->halo_armed = true;
+  }
+  if (xp) {
+    for (int j = 0; j < n_prev; ++j)
+      HIPCHK(c, hipMemcpy2D(c->xp_hist[j], c->xp_hist_pitch, prev[j], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
+    c->xp_armed = n_prev;
+  }
   return PQA_OK;
+}
+}  // namespace
+
+int pqa_set_motion_halo(pqa_ctx* c, const void* prev_ref_luma_host, int64_t row_stride) {
+  if (!c) return PQA_EINVAL;
+  return set_history(c, &prev_ref_luma_host, prev_ref_luma_host ? 1 : 0, row_stride);
+}
+
+int pqa_set_ref_history(pqa_ctx* c, const void* const* prev_luma_host, int32_t n_prev, int64_t row_stride) {
+  if (!c) return PQA_EINVAL;
+  if (n_prev < 0 || n_prev > 2 || (n_prev > 0 && !prev_luma_host))
+    return fail(c, PQA_EINVAL, "pqa_set_ref_history: bad argument (n_prev %d)", n_prev);
+  for (int j = 0; j < n_prev; ++j)
+    if (!prev_luma_host[j]) return fail(c, PQA_EINVAL, "pqa_set_ref_history: plane %d is null", j);
+  if (n_prev > 0 && row_stride < (int64_t)c->pw[0] * c->esize)
+    return fail(c, PQA_EINVAL, "pqa_set_ref_history: row stride %lld smaller than a row", (long long)row_stride);
+  return set_history(c, prev_luma_host, n_prev, row_stride);
 }
 
 int pqa_flush(pqa_ctx* c) {
@@ -1542,14 +1683,19 @@ int pqa_sync(pqa_ctx* c) {
 }
 
 int pqa_collect(pqa_ctx* c, int64_t first_index, int32_t count, double* records) {
-  return pqa_collect_ext2(c, first_index, count, records, nullptr, nullptr);
+  return pqa_collect_ext3(c, first_index, count, records, nullptr, nullptr, nullptr);
 }
 
 int pqa_collect_ext(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext) {
-  return pqa_collect_ext2(c, first_index, count, records, ext, nullptr);
+  return pqa_collect_ext3(c, first_index, count, records, ext, nullptr, nullptr);
 }
 
 int pqa_collect_ext2(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2) {
+  return pqa_collect_ext3(c, first_index, count, records, ext, ext2, nullptr);
+}
+
+int pqa_collect_ext3(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
+                     double* ext3) {
   if (!c) return PQA_EINVAL;
   if (count < 0 || first_index < 0 || (count > 0 && !records)) return fail(c, PQA_EINVAL, "bad argument");
   if (count > c->capacity) return fail(c, PQA_ESTATE, "count %d exceeds result_capacity %d", count, c->capacity);
@@ -1607,6 +1753,12 @@ int pqa_collect_ext2(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
                           (size_t)n * PQA_EXT2_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
     } else if (ext2) {
       std::fill(ext2 + (size_t)done * PQA_EXT2_DOUBLES, ext2 + (size_t)(done + n) * PQA_EXT2_DOUBLES, __builtin_nan(""));
+    }
+    if (ext3 && c->ext3) {  // and the third
+      HIPCHK(c, hipMemcpy(ext3 + (size_t)done * PQA_EXT3_DOUBLES, c->ext3 + (size_t)row * PQA_EXT3_DOUBLES,
+                          (size_t)n * PQA_EXT3_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (ext3) {
+      std::fill(ext3 + (size_t)done * PQA_EXT3_DOUBLES, ext3 + (size_t)(done + n) * PQA_EXT3_DOUBLES, __builtin_nan(""));
     }
     done += n;
     row = 0;
@@ -1744,6 +1896,9 @@ int pqa_reset(pqa_ctx* c) {
   c->have_last = false;
   c->halo_armed = false;
   c->last_index = -1;
+  c->xp_armed = -1;
+  c->xp_last = -1;
+  c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
   c->err.clear();
   return PQA_OK;
 }
@@ -1935,6 +2090,68 @@ int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t row_pitch
     if (q) hipFree(q);
   if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_psnr_hvs_plane: %s", hipGetErrorString(e));
   if (mse) *mse = row[PQA_EXT2_PSNR_HVS_MSE + plane_kind];
+  return PQA_OK;
+}
+
+int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const void* ref_m2, const void* dis, int64_t row_pitch_bytes,
+                           uint32_t w, uint32_t h, uint32_t bit_depth, int32_t hfr, uint64_t* out, double* wsse) {
+  if (!ref || !dis || !out || w < 16 || h < 16 || w > 16384 || h > 16384 ||
+      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: bad argument");
+  const int es = bit_depth > 8 ? 2 : 1;
+  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: bad row pitch %lld", (long long)row_pitch_bytes);
+  XpsnrGeometry geo{};
+  xpsnr_geometry((int)w, (int)h, (int)w, (int)h, 1, (int)bit_depth, &geo);
+  if (geo.bv == 2 && ((w | h) & 1)) return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: odd size above 2048x1152");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
+  const size_t plane_bytes = (size_t)w * h * es;
+  const void* host[4] = {ref, ref_m1, ref_m2, dis};
+  void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  unsigned long long* blk = nullptr;
+  double *wb = nullptr, *ext3 = nullptr;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+    if (!host[i]) continue;
+    e = hipMalloc(&dev[i], plane_bytes);
+    if (e == hipSuccess)
+      e = hipMemcpy2D(dev[i], (size_t)w * es, host[i], (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMalloc((void**)&blk, (size_t)geo.n_blk * kXpBlockVals * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&wb, (size_t)geo.n_blk * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&ext3, PQA_EXT3_DOUBLES * sizeof(double));
+  if (e == hipSuccess) {
+    PlaneRun r3[3] = {{dev[0], (int64_t)w, (int64_t)w * h}}, d3[3] = {{dev[3], (int64_t)w, (int64_t)w * h}};
+    e = launch_xpsnr_blocks(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, r3, d3, 1, dev[1], dev[1] ? (int64_t)w : 0, dev[2],
+                            dev[2] ? (int64_t)w : 0, hfr != 0, geo, blk);
+  }
+  if (e == hipSuccess) {
+    XpFinalizeArgs xa{};
+    xa.n_frames = 1;
+    xa.blk = blk;
+    xa.wbuf = wb;
+    xa.ext3 = ext3;
+    xa.ext_stride = PQA_EXT3_DOUBLES;
+    xa.slot_base = 0;
+    xa.capacity = 1;
+    xa.g = geo;
+    e = launch_xpsnr_finalize(nullptr, xa);
+  }
+  std::vector<unsigned long long> hb;
+  double row[PQA_EXT3_DOUBLES];
+  if (e == hipSuccess) {
+    hb.resize((size_t)geo.n_blk * kXpBlockVals);
+    e = hipMemcpy(hb.data(), blk, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  }
+  if (e == hipSuccess) e = hipMemcpy(row, ext3, sizeof row, hipMemcpyDeviceToHost);
+  for (void* q : {dev[0], dev[1], dev[2], dev[3], (void*)blk, (void*)wb, (void*)ext3})
+    if (q) hipFree(q);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_xpsnr_blocks: %s", hipGetErrorString(e));
+  for (int k = 0; k < geo.n_blk; ++k)
+    for (int i = 0; i < 3; ++i) out[k * 3 + i] = hb[(size_t)k * kXpBlockVals + i];
+  if (wsse) *wsse = row[PQA_EXT3_WSSE];
   return PQA_OK;
 }
 

@@ -159,6 +159,17 @@ class FeatureEngine:
         a = np.ascontiguousarray(prev_ref_luma, dtype=self.dtype)
         self._check(self.lib.pqa_set_motion_halo(self._ctx, a.ctypes.data, a.strides[0]))
 
+    def set_ref_history(self, prev_ref_lumas):
+        """The reference luma planes in front of the next submitted frame: [frame first-1, frame first-2] (at most two;
+        an empty list restarts the chain).  Arms motion's halo from the first and xpsnr's temporal history from both
+        (pqa_set_ref_history)."""
+        planes = [np.ascontiguousarray(p, dtype=self.dtype) for p in prev_ref_lumas]
+        if len(planes) > 2:
+            raise ValueError("set_ref_history takes at most two planes")
+        ptrs = (C.c_void_p * 2)(*([p.ctypes.data for p in planes] + [None] * (2 - len(planes))))
+        stride = planes[0].strides[0] if planes else 0
+        self._check(self.lib.pqa_set_ref_history(self._ctx, ptrs, len(planes), stride))
+
     # -- device-resident path ------------------------------------------------------------------
     def submit_resident(self, first_index: int, n_frames: int, ref_ptrs, dis_ptrs, row_pitch, frame_pitch,
                         prev_ref_luma_ptr: int = 0, prev_row_pitch: int = 0):
@@ -251,6 +262,17 @@ class FeatureEngine:
         self._check(self.lib.pqa_collect_ext2(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
                                               ext2.ctypes.data))
         return out, ext, ext2
+
+    def collect_ext3(self, first_index: int, count: int):
+        """(records, ext, ext2, ext3 [count, EXT3_DOUBLES]): collect_ext2() plus the third extension rows of the same
+        frames (pqa_collect_ext3; xpsnr slots, NaN where the context does not run it)."""
+        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
+        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
+        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
+        ext3 = np.zeros((count, N.EXT3_DOUBLES), np.float64)
+        self._check(self.lib.pqa_collect_ext3(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
+                                              ext2.ctypes.data, ext3.ctypes.data))
+        return out, ext, ext2, ext3
 
     def flush(self):
         self._check(self.lib.pqa_flush(self._ctx))

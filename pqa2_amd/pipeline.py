@@ -30,7 +30,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
                 fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
                 ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False,
-                psnr_hvs: bool = False) -> ScoreResult | None:
+                psnr_hvs: bool = False, xpsnr: bool = False) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -39,7 +39,10 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     `cambi`: libvmaf's cambi banding index of the distorted luma as the extra column cambi (8- and 10-bit clips);
     `cambi_full_ref` adds cambi_source (the reference's) and cambi_full_reference = max(cambi - cambi_source, 0).
     `psnr_hvs`: libvmaf's psnr_hvs feature as the extra columns psnr_hvs_y / _cb / _cr and psnr_hvs (second extension
-    record; needs the chroma planes: a monochrome clip is an error)."""
+    record; needs the chroma planes: a monochrome clip is an error).
+    `xpsnr`: FFmpeg's xpsnr filter on every frame as the extra columns xpsnr_y / _u / _v (third extension record; a
+    monochrome clip gives xpsnr_y only), its stats-file lines and summary; the second-order temporal term when the clip's
+    integer frame rate (fps_num // fps_den) is 32 or more."""
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -59,7 +62,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     if psnr_hvs and ri.mono:
         raise ValueError("psnr_hvs needs the chroma planes, but the clips are monochrome")
     mdl = M.load_model(model)
-    side = (psnr or ssim or ciede or psnr_hvs)
+    side = (psnr or ssim or ciede or psnr_hvs or xpsnr)
     n_planes = 1 if (ri.mono or not side) else 3
     feats = N.FEAT_VMAF | (N.FEAT_PSNR if psnr else 0) | (N.FEAT_SSIM if ssim else 0)
     want_ext = bool(float_ssim or ms_ssim or ciede or cambi)
@@ -68,6 +71,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         feats |= (N.FEAT_CAMBI if cambi else 0) | (N.FEAT_CAMBI_FULL_REF if cambi_full_ref else 0)
     if psnr_hvs:
         feats |= N.FEAT_PSNR_HVS
+    if xpsnr:
+        feats |= N.FEAT_XPSNR | (N.FEAT_XPSNR_HFR if xpsnr_hfr(ri) else 0)
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -78,7 +83,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                vif_enhn_gain_limit=mdl.vif_enhn_gain_limit, adm_enhn_gain_limit=mdl.adm_enhn_gain_limit,
                vif_border=mdl.vif_border, **({"fixed_point": int(fixed_point)} if fixed_point else {}))
     try:
-        if a > 0:
+        if a > 0 and xpsnr:   # xpsnr's temporal term reads two frames back: frames a-1 and a-2 (motion's halo is a-1)
+            eng.set_ref_history([ref_rd.frame(a - 1)[0]] + ([ref_rd.frame(a - 2)[0]] if a >= 2 else []))
+        elif a > 0:
             eng.set_motion_halo(ref_rd.frame(a - 1)[0])   # one-frame halo in front of this rank's chunk
         # both clips are files of packed planes (.y4m): the library reads them straight into its pinned staging (pqa_submit_fd:
         # one copy, no page faults) instead of copying frames out of the readers' mappings
@@ -108,8 +115,12 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             i += m
             if progress is not None:
                 progress(i - a, b - a)
-        local_ext = local_ext2 = None
-        if psnr_hvs:   # the second extension record is read only when psnr_hvs is on: default calls stay as they were
+        local_ext = local_ext2 = local_ext3 = None
+        if xpsnr:      # the third extension record is read only when xpsnr is on
+            local, local_ext, local_ext2, local_ext3 = eng.collect_ext3(a, b - a) if b > a else (
+                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
+                np.zeros((0, N.EXT3_DOUBLES)))
+        elif psnr_hvs:   # the second extension record is read only when psnr_hvs is on: default calls stay as they were
             local, local_ext, local_ext2 = eng.collect_ext2(a, b - a) if b > a else (
                 np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)))
         elif want_ext:
@@ -124,6 +135,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
+    ext3 = shard.gather_records(local_ext3, n, world_size, rank, gather_device, width=N.EXT3_DOUBLES) if xpsnr else None
     if rank != 0:
         return None
     elapsed = time.perf_counter() - t_start
@@ -136,6 +148,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         extra["cambi_full_ref"] = True
     if psnr_hvs:
         extra.update(ext2=ext2, psnr_hvs=True)
+    if xpsnr:
+        extra.update(ext3=ext3, xpsnr=True)
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                           fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
@@ -143,12 +157,14 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
 def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim: bool, n_subsample: int = 1,
                    n_planes: int = 1, fps: float = 0.0, ext: np.ndarray | None = None, float_ssim: bool = False,
                    ms_ssim: bool = False, ciede: bool = False, cambi: bool = False,
-                   cambi_full_ref: bool = False, ext2: np.ndarray | None = None, psnr_hvs: bool = False) -> ScoreResult:
+                   cambi_full_ref: bool = False, ext2: np.ndarray | None = None, psnr_hvs: bool = False,
+                   ext3: np.ndarray | None = None, xpsnr: bool = False) -> ScoreResult:
     """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
     / `ciede` the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim /
     ciede2000 columns, with `cambi` / `cambi_full_ref` libvmaf's cambi, cambi_source and cambi_full_reference.  With
     `psnr_hvs` the second extension records `ext2` ([n, EXT2_DOUBLES], pqa_collect_ext2) add psnr_hvs_y / _cb / _cr and
-    psnr_hvs."""
+    psnr_hvs.  With `xpsnr` the third extension records `ext3` ([n, EXT3_DOUBLES], pqa_collect_ext3) add xpsnr_y / _u /
+    _v, FFmpeg's stats-file lines (xpsnr_lines) and its summary (xpsnr_summary, report.xpsnr_summary) of every frame."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -189,6 +205,16 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         for key, slot in (("psnr_hvs_y", N.EXT2_PSNR_HVS_Y), ("psnr_hvs_cb", N.EXT2_PSNR_HVS_CB),
                           ("psnr_hvs_cr", N.EXT2_PSNR_HVS_CR), ("psnr_hvs", N.EXT2_PSNR_HVS)):
             metrics[key] = ext2[:, slot].copy()
+    xpsnr_lines = xpsnr_summary = None
+    if xpsnr:
+        if ext3 is None or ext3.shape != (n, N.EXT3_DOUBLES):
+            raise ValueError("xpsnr needs the third extension records of every frame")
+        for p, key in enumerate(("xpsnr_y", "xpsnr_u", "xpsnr_v")[:n_planes]):
+            metrics[key] = ext3[:, N.EXT3_XPSNR_Y + p].copy()
+        db = ext3[:, N.EXT3_XPSNR_Y:N.EXT3_XPSNR_Y + n_planes]
+        wsse = ext3[:, N.EXT3_WSSE:N.EXT3_WSSE + n_planes]
+        xpsnr_lines = report.xpsnr_stats_lines(db)
+        xpsnr_summary = report.xpsnr_summary(wsse, db, plane_sizes, info.bit_depth)
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:
@@ -196,4 +222,10 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         scored = {k: np.asarray(v)[keep] for k, v in scored.items()}
         idx = idx[keep]
     return ScoreResult(metrics=scored, frame_indices=idx, records=rec, info=info, fps=fps,
-                       psnr_lines=psnr_lines, ssim_lines=ssim_lines, model_name=mdl.name)
+                       psnr_lines=psnr_lines, ssim_lines=ssim_lines, model_name=mdl.name,
+                       **({"xpsnr_lines": xpsnr_lines, "xpsnr_summary": xpsnr_summary} if xpsnr else {}))
+
+
+def xpsnr_hfr(info) -> bool:
+    """FFmpeg's xpsnr switches to its second-order temporal term at an integer frame rate (num / den truncated) >= 32."""
+    return bool(info.fps_den) and info.fps_num // info.fps_den >= 32

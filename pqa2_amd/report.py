@@ -23,6 +23,65 @@ def _f6(x: float) -> str:
     return f"{x:.6f}"
 
 
+def xpsnr_stats_lines(db: np.ndarray) -> list[str]:
+    """FFmpeg xpsnr `stats_file` lines: `n: %4d` (1-based) then `  XPSNR %c: %3.4f` for y, u, v (as many as db's columns,
+    [n, planes] per-frame dB; +inf prints as inf)."""
+    lines = []
+    for i, row in enumerate(np.asarray(db, dtype=np.float64).reshape(len(db), -1)):
+        s = f"n: {i + 1:4d}"
+        for c, v in zip("yuv", row):
+            s += f"  XPSNR {c}: {_f4(v)}"
+        lines.append(s)
+    return lines
+
+
+def _f4(x: float) -> str:
+    x = float(x)
+    if math.isnan(x):
+        return "nan"
+    if math.isinf(x):
+        return "inf" if x > 0 else "-inf"
+    return f"{x:3.4f}"
+
+
+def xpsnr_summary(wsse: np.ndarray, db: np.ndarray, plane_sizes, bit_depth: int) -> dict:
+    """FFmpeg xpsnr's clip aggregate per plane: the square-mean-root 10 log10(w h max^2 / (sum sqrt(WSSE) / N)^2) when
+    sum sqrt(WSSE) >= N, else the arithmetic mean of the per-frame dB values; {"y", "u", "v" (present planes), "min"}."""
+    wsse = np.asarray(wsse, dtype=np.float64).reshape(len(wsse), -1)
+    db = np.asarray(db, dtype=np.float64).reshape(len(db), -1)
+    n = wsse.shape[0]
+    peak2 = float(((1 << bit_depth) - 1) ** 2)
+    out = {}
+    for p in range(wsse.shape[1]):
+        w, h = plane_sizes[p]
+        s = 0.0
+        for x in wsse[:, p]:          # a running sum in frame order, as the filter keeps it
+            s += math.sqrt(float(x))
+        if n == 0:
+            v = math.inf
+        elif s >= n:
+            avg = s / n
+            v = 10.0 * math.log10(float(w * h * int(peak2)) / (avg * avg))
+        else:
+            t = 0.0
+            for x in db[:, p]:
+                t += float(x)
+            v = t / n
+        out["yuv"[p]] = v
+    out["min"] = min(out.values()) if out else math.nan
+    return out
+
+
+def xpsnr_log_keys(summary: dict | None) -> dict:
+    """Top-level keys of the JSON log that carry FFmpeg's xpsnr summary (xpsnr_y / _u / _v and their minimum, xpsnr); none
+    without one, and none for a value that is not finite."""
+    if not summary:
+        return {}
+    out = {f"xpsnr_{c}": float(summary[c]) for c in "yuv" if c in summary}
+    out["xpsnr"] = float(summary["min"])
+    return {k: v for k, v in out.items() if math.isfinite(v)}   # +inf (identical clips) has no JSON spelling: left out
+
+
 def build_vmaf_log(metrics: dict, fps: float, frame_indices=None, extra_top: dict | None = None) -> dict:
     """dict with libvmaf's JSON schema: version, fps, frames[{frameNum, metrics}], pooled_metrics,
     aggregate_metrics.  Values are rounded to 6 decimals like libvmaf's %.6f writer."""

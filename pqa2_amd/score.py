@@ -71,6 +71,9 @@ def main(argv=None) -> int:
                     help="with --cambi: also cambi_source and cambi_full_reference (per frame and pooled)")
     ap.add_argument("--psnr-hvs", action="store_true",
                     help="add libvmaf's psnr_hvs feature: psnr_hvs_y / _cb / _cr and psnr_hvs (per frame and pooled)")
+    ap.add_argument("--xpsnr", action="store_true",
+                    help="add FFmpeg's xpsnr: xpsnr_y / _u / _v per frame and FFmpeg's summary in the JSON's top level")
+    ap.add_argument("--xpsnr-log", default=None, help="FFmpeg xpsnr stats_file output path (implies --xpsnr)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -109,7 +112,8 @@ def main(argv=None) -> int:
                           **({"float_ssim": True} if a.float_ssim else {}), **({"ms_ssim": True} if a.ms_ssim else {}),
                           **({"ciede": True} if a.ciede else {}), **({"cambi": True} if a.cambi else {}),
                           **({"cambi_full_ref": True} if a.cambi_full_ref else {}),
-                          **({"psnr_hvs": True} if a.psnr_hvs else {}))
+                          **({"psnr_hvs": True} if a.psnr_hvs else {}),
+                          **({"xpsnr": True} if (a.xpsnr or a.xpsnr_log) else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
         return 1
@@ -119,8 +123,12 @@ def main(argv=None) -> int:
             if dist.is_initialized():
                 dist.destroy_process_group()
     if rank == 0:
-        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"], {"model": res["model_name"]})
+        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
+                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary"))})
         report.write_vmaf_json(a.json, log)
+        if a.xpsnr_log and res.get("xpsnr_lines") is not None:
+            with open(a.xpsnr_log, "w") as f:
+                f.write("\n".join(res["xpsnr_lines"]) + "\n")
         if a.psnr_log and res["psnr_lines"] is not None:
             with open(a.psnr_log, "w") as f:
                 f.write("\n".join(res["psnr_lines"]) + "\n")

@@ -153,6 +153,8 @@ class VMAFAnalyzer(QObject):
         self.cambi_enabled = False            # libvmaf cambi banding index (feature=name=cambi) of the distorted luma
         self.cambi_full_ref_enabled = False   # with cambi: cambi_source and cambi_full_reference (full-reference mode)
         self.psnr_hvs_enabled = False         # libvmaf psnr_hvs (feature=name=psnr_hvs): psnr_hvs_y / _cb / _cr, psnr_hvs
+        self.xpsnr_enabled = False            # FFmpeg xpsnr: <test>_<ts>_xpsnr.txt stats file, xpsnr_y / _u / _v, xpsnr
+        self._xpsnr_path = None               # where this analysis writes the xpsnr stats file (set per analysis)
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -176,6 +178,7 @@ class VMAFAnalyzer(QObject):
             self.cambi_enabled = bool(s.get("cambi_enabled", False))
             self.cambi_full_ref_enabled = bool(s.get("cambi_full_ref_enabled", False))
             self.psnr_hvs_enabled = bool(s.get("psnr_hvs_enabled", False))
+            self.xpsnr_enabled = bool(s.get("xpsnr_enabled", False))
             logger.info(f"VMAF options set from manager: threads={self.threads}, "
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
@@ -194,7 +197,7 @@ class VMAFAnalyzer(QObject):
     def set_advanced_options(self, pool_method="mean", enable_motion_score=False, enable_temporal_features=False,
                              feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
                              ms_ssim_enabled=False, ciede_enabled=False, cambi_enabled=False,
-                             cambi_full_ref_enabled=False, psnr_hvs_enabled=False):
+                             cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -207,6 +210,7 @@ class VMAFAnalyzer(QObject):
         self.cambi_enabled = bool(cambi_enabled)
         self.cambi_full_ref_enabled = bool(cambi_full_ref_enabled)
         self.psnr_hvs_enabled = bool(psnr_hvs_enabled)
+        self.xpsnr_enabled = bool(xpsnr_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -305,6 +309,8 @@ class VMAFAnalyzer(QObject):
                 json_path = os.path.join(test_dir, f"{test_name}_{timestamp}_vmaf.json")
                 psnr_path = os.path.join(test_dir, f"{test_name}_{timestamp}_psnr.txt")
                 ssim_path = os.path.join(test_dir, f"{test_name}_{timestamp}_ssim.txt")
+                self._xpsnr_path = (os.path.join(test_dir, f"{test_name}_{timestamp}_xpsnr.txt")
+                                    if self.xpsnr_enabled else None)
 
                 self.get_video_metadata(reference_path)
                 dist_meta = self.get_video_metadata(distorted_path)
@@ -375,8 +381,12 @@ class VMAFAnalyzer(QObject):
             self._fail("VMAF analysis was terminated by user")
             return False
         self.last_fps = res["fps"]
-        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"], {"model": res["model_name"]})
+        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
+                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary"))})
         report.write_vmaf_json(json_path, log)
+        if self.xpsnr_enabled and self._xpsnr_path and res.get("xpsnr_lines") is not None:
+            with open(self._xpsnr_path, "w") as f:
+                f.write("\n".join(res["xpsnr_lines"]) + "\n")
         if psnr_path and res["psnr_lines"] is not None:
             self.status_update.emit("Running PSNR analysis...")
             with open(psnr_path, "w") as f:
@@ -395,7 +405,8 @@ class VMAFAnalyzer(QObject):
                 **({"ciede": True} if self.ciede_enabled else {}),
                 **({"cambi": True} if self.cambi_enabled else {}),
                 **({"cambi_full_ref": True} if self.cambi_enabled and self.cambi_full_ref_enabled else {}),
-                **({"psnr_hvs": True} if self.psnr_hvs_enabled else {})}
+                **({"psnr_hvs": True} if self.psnr_hvs_enabled else {}),
+                **({"xpsnr": True} if self.xpsnr_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -420,6 +431,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--cambi"] + (["--cambi-full-ref"] if self.cambi_full_ref_enabled else [])
         if self.psnr_hvs_enabled:
             cmd += ["--psnr-hvs"]
+        if self.xpsnr_enabled:
+            cmd += ["--xpsnr"] + (["--xpsnr-log", self._xpsnr_path] if self._xpsnr_path else [])
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -522,6 +535,10 @@ class VMAFAnalyzer(QObject):
                                  (self.psnr_hvs_enabled, "psnr_hvs_cr"), (self.psnr_hvs_enabled, "psnr_hvs")):
                 if enabled:
                     results[key] = pooled[key]["mean"] if key in pooled else None
+            if self.xpsnr_enabled:   # FFmpeg's clip summary (square-mean-root), from the log's top level
+                for key in ("xpsnr_y", "xpsnr_u", "xpsnr_v", "xpsnr"):
+                    results[key] = vmaf_data.get(key)
+                results["xpsnr_log"] = self._xpsnr_path
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)

@@ -8,7 +8,13 @@ Give this tool those stats files and the two clips:
     python tools/compare_ffmpeg_stats.py --psnr psnr.txt --ssim ssim.txt ref.y4m dist.y4m [--gpu]
 It regenerates both files from the CPU restatement (oracle/vmaf_oracle.c: exact integer SSE, x264-style SSIM) -- and with
 --gpu from the HIP kernels -- and diffs them line by line: PSNR lines must be IDENTICAL text (they are printed from exact
-integers with %.2f), SSIM fields may differ in the last printed digit (%f of a float ratio).  Exit code 0 / 1."""
+integers with %.2f), SSIM fields may differ in the last printed digit (%f of a float ratio).  Exit code 0 / 1.
+
+--xpsnr xpsnr.txt compares FFmpeg's xpsnr stats file the same way, against tests/xpsnr_ref.py (and with --gpu the HIP
+kernels, csrc/xpsnr.hip); the fields may differ by one unit of the printed %.4f.  FFmpeg treats its FIRST input as the
+original whose activity weights the blocks, so the pin command puts the reference first:
+    ffmpeg -i ref.y4m -i dist.y4m -lavfi "xpsnr=stats_file=xpsnr.txt" -f null -
+On a mismatch it names the unpinned items of DESIGN.md section 1."""
 from __future__ import annotations
 
 import argparse
@@ -55,6 +61,43 @@ def our_lines(ref_path, dis_path, use_gpu):
     return out
 
 
+XPSNR_VERIFY = (
+    "the zero history at the chain start (frame 0, and frame 1 in second order) versus 'previous := current'",
+    "integer frame rate = num / den truncated, second order from 32",
+    "the minimum-smoothing rule (frames <= 640 x 480)",
+    "A's constant 16 and the 2d - 9 exponent",
+    "the 2 x 2 high-pass ring coefficients (above 2048 x 1152)",
+    "the early return of small edge blocks (weight 1, no history update)",
+    "which input FFmpeg treats as the original (the first: put the reference first)",
+    "the stats-line format (n: %4d, 1-based; XPSNR %c: %3.4f)",
+)
+
+
+def xpsnr_lines(ref_path, dis_path, use_gpu):
+    from pqa2_amd import report
+    from pqa2_amd.pipeline import xpsnr_hfr
+    from pqa2_amd.yuvio import open_video
+    from tests import xpsnr_ref as R
+    rd, dd = open_video(ref_path), open_video(dis_path)
+    info = rd.info
+    n = min(len(rd), len(dd))
+    planes = 1 if info.mono else 3
+    hfr = xpsnr_hfr(info)
+    _, db = R.clip([rd.frame(i)[:planes] for i in range(n)], [dd.frame(i)[:planes] for i in range(n)], info.bit_depth, hfr)
+    out = {"restatement (tests/xpsnr_ref.py)": report.xpsnr_stats_lines(db)}
+    if use_gpu:
+        from pqa2_amd import _native as N
+        from pqa2_amd.engine import FeatureEngine
+        feats = N.FEAT_XPSNR | (N.FEAT_XPSNR_HFR if hfr else 0)
+        with FeatureEngine(info.width, info.height, bit_depth=info.bit_depth, n_planes=planes,
+                           chroma_shift=(info.hshift, info.vshift), features=feats) as eng:
+            for i in range(n):
+                eng.submit(i, rd.frame(i)[:planes], dd.frame(i)[:planes])
+            ext3 = eng.collect_ext3(0, n)[3]
+        out["HIP kernels (csrc/xpsnr.hip)"] = report.xpsnr_stats_lines(ext3[:, :planes])
+    return out
+
+
 def numbers(line):
     return [float(x) if x not in ("inf", "-inf", "nan") else float(x) for x in re.findall(r"[:(]\s*(-?inf|nan|-?\d+\.?\d*(?:e[-+]?\d+)?)", line)]
 
@@ -65,13 +108,35 @@ def main(argv=None) -> int:
     ap.add_argument("distorted")
     ap.add_argument("--psnr")
     ap.add_argument("--ssim")
+    ap.add_argument("--xpsnr", help="FFmpeg xpsnr stats_file (reference given to FFmpeg as its first input)")
     ap.add_argument("--gpu", action="store_true")
     ap.add_argument("--ssim-tol", type=float, default=2e-6, help="largest allowed difference of a printed SSIM field")
     a = ap.parse_args(argv)
-    if not a.psnr and not a.ssim:
-        ap.error("give --psnr and / or --ssim")
+    if not a.psnr and not a.ssim and not a.xpsnr:
+        ap.error("give --psnr, --ssim and / or --xpsnr")
     bad = False
-    for tag, (pl, sl) in our_lines(a.reference, a.distorted, a.gpu).items():
+    if a.xpsnr:
+        theirs = [l.rstrip("\n") for l in open(a.xpsnr) if l.strip()]
+        for tag, xl in xpsnr_lines(a.reference, a.distorted, a.gpu).items():
+            print(f"== {tag} ==")
+            ok = len(theirs) == len(xl)
+            first = None
+            for i, (x, y) in enumerate(zip(theirs, xl)):
+                nx, ny = numbers(x), numbers(y)
+                same = len(nx) == len(ny) and all(u == v or (np.isfinite(u) and np.isfinite(v) and abs(u - v) <= 1.5e-4)
+                                                  for u, v in zip(nx, ny))
+                if not same:
+                    ok = False
+                    first = first if first is not None else i
+            print(f"xpsnr stats_file: {len(theirs)} lines, {'ok' if ok else 'MISMATCH'}")
+            if not ok:
+                bad = True
+                if first is not None:
+                    print(f"   first difference at line {first + 1}:\n      ffmpeg: {theirs[first]}\n      ours  : {xl[first]}")
+                print("   -> check the unpinned items (DESIGN.md section 1):")
+                for item in XPSNR_VERIFY:
+                    print(f"      - {item}")
+    for tag, (pl, sl) in (our_lines(a.reference, a.distorted, a.gpu).items() if (a.psnr or a.ssim) else ()):
         print(f"== {tag} ==")
         if a.psnr:
             theirs = [l.rstrip("\n") for l in open(a.psnr) if l.strip()]

@@ -16,6 +16,9 @@ for clip in c64x48_8 c352x288_8 c200x120_10; do
   "$FF" -hide_banner -loglevel error -i "$dis" -i "$ref" -lavfi "psnr=stats_file=$T/$clip.psnr.txt" -f null -
   "$FF" -hide_banner -loglevel error -i "$dis" -i "$ref" -lavfi "ssim=stats_file=$T/$clip.ssim.txt" -f null -
   python3 "$R/tools/compare_ffmpeg_stats.py" --psnr "$T/$clip.psnr.txt" --ssim "$T/$clip.ssim.txt" "$ref" "$dis" "$@" || rc=1
+  # xpsnr (FFmpeg >= 7.0): its FIRST input is the original whose activity weights the blocks, so the reference goes first
+  "$FF" -hide_banner -loglevel error -i "$ref" -i "$dis" -lavfi "xpsnr=stats_file=$T/$clip.xpsnr.txt" -f null -
+  python3 "$R/tools/compare_ffmpeg_stats.py" --xpsnr "$T/$clip.xpsnr.txt" "$ref" "$dis" "$@" || rc=1
 done
 echo "outputs kept in $T"
 exit $rc
