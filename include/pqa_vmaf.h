@@ -94,8 +94,21 @@ enum {
    * sums: pqa_debug_xpsnr_blocks. */
   PQA_FEAT_XPSNR = 1u << 12,
   PQA_FEAT_XPSNR_HFR = 1u << 13,
+  /* FFmpeg's siti filter (libavfilter/vf_siti.c): ITU-T P.910 spatial (SI: standard deviation of the 3 x 3 Sobel
+   * magnitude over the interior pixels) and temporal (TI: standard deviation of the frame difference) information of the
+   * distorted and of the reference luma, in the FOURTH extension record (PQA_EXT4_*, pqa_collect_ext4) on EVERY frame,
+   * whatever n_subsample is.  Limited-range samples are mapped to full range first; PQA_FEAT_SITI_REF_FULL /
+   * PQA_FEAT_SITI_DIS_FULL say that clip's samples are full range already.  TI reads the previous frame of each clip:
+   * the frame before it in the batch, the plane the context keeps from its previous batch, the caller's halo (reference)
+   * or the history armed with pqa_set_ref_history / pqa_set_dis_history; TI = 0 at a chain start.  8 and 10 bit only
+   * (PQA_EINVAL naming siti for 12 bit, and for a range bit without PQA_FEAT_SITI); any n_planes and chroma subsampling
+   * (luma only).  Definition and its unpinned items: DESIGN.md sections 1 and 5; its gradient map: pqa_debug_siti_plane. */
+  PQA_FEAT_SITI = 1u << 14,
+  PQA_FEAT_SITI_REF_FULL = 1u << 15,
+  PQA_FEAT_SITI_DIS_FULL = 1u << 16,
   PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI |
-                   PQA_FEAT_CAMBI_FULL_REF | PQA_FEAT_PSNR_HVS | PQA_FEAT_XPSNR | PQA_FEAT_XPSNR_HFR  /* what pqa_create accepts */
+                   PQA_FEAT_CAMBI_FULL_REF | PQA_FEAT_PSNR_HVS | PQA_FEAT_XPSNR | PQA_FEAT_XPSNR_HFR | PQA_FEAT_SITI |
+                   PQA_FEAT_SITI_REF_FULL | PQA_FEAT_SITI_DIS_FULL  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -154,6 +167,18 @@ enum {
   PQA_EXT3_DOUBLES = 8
 };
 
+/* The FOURTH extension record = PQA_EXT4_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and
+ * wrap) when the context runs PQA_FEAT_SITI; read with pqa_collect_ext4.  Every submitted frame gets its row; the
+ * reserved slots hold NaN. */
+enum {
+  PQA_EXT4_SI = 0,          /* SI of the distorted luma                                                    */
+  PQA_EXT4_TI = 1,          /* TI of the distorted luma (0 at a chain start and on a repeated frame)       */
+  PQA_EXT4_SI_SOURCE = 2,   /* SI of the reference luma                                                    */
+  PQA_EXT4_TI_SOURCE = 3,   /* TI of the reference luma                                                    */
+  PQA_EXT4_RESERVED = 4,    /* [4]                                                                         */
+  PQA_EXT4_DOUBLES = 8
+};
+
 typedef struct pqa_config {
   uint32_t struct_size;        /* sizeof(pqa_config), for ABI growth                              */
   int32_t device;              /* HIP device ordinal                                              */
@@ -207,6 +232,7 @@ PQA_API int pqa_record_doubles(void);
 PQA_API int pqa_ext_doubles(void);
 PQA_API int pqa_ext2_doubles(void);
 PQA_API int pqa_ext3_doubles(void);
+PQA_API int pqa_ext4_doubles(void);
 
 /* Fill cfg with defaults (8-bit 4:2:0, PQA_FEAT_VMAF, gain limits 100). */
 PQA_API void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height);
@@ -294,6 +320,12 @@ PQA_API int pqa_set_motion_halo(pqa_ctx* ctx, const void* prev_ref_luma_host, in
  * temporal history from both; n_prev = 0 restarts the chain.  PQA_EINVAL on n_prev outside 0..2 or a null plane. */
 PQA_API int pqa_set_ref_history(pqa_ctx* ctx, const void* const* prev_luma_host, int32_t n_prev, int64_t row_stride);
 
+/* The distorted clip's luma in front of the next submitted frame (frame a-1 of a frame-sharded rank that starts at a; rows
+ * row_stride bytes apart): PQA_FEAT_SITI's TI of the distorted clip continues from it.  NULL restarts the distorted chain
+ * (TI 0 on the next frame).  The reference side arrives through pqa_set_motion_halo / pqa_set_ref_history.  A no-op
+ * without PQA_FEAT_SITI. */
+PQA_API int pqa_set_dis_history(pqa_ctx* ctx, const void* prev_dis_luma_host, int64_t row_stride);
+
 /* Launch whatever pqa_submit has pending (partial batch). */
 PQA_API int pqa_flush(pqa_ctx* ctx);
 
@@ -321,6 +353,11 @@ PQA_API int pqa_collect_ext2(pqa_ctx* ctx, int64_t first_index, int32_t count, d
 PQA_API int pqa_collect_ext3(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
                              double* ext3);
 
+/* pqa_collect_ext3 with the fourth extension record as well: ext4[count][PQA_EXT4_DOUBLES] receives the ext4 rows of the
+ * same frames.  ext, ext2, ext3 and ext4 may be NULL.  A context without PQA_FEAT_SITI returns all-NaN ext4 rows. */
+PQA_API int pqa_collect_ext4(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
+                             double* ext3, double* ext4);
+
 /* Wait for all submitted work without collecting. */
 PQA_API int pqa_sync(pqa_ctx* ctx);
 
@@ -328,7 +365,7 @@ PQA_API int pqa_sync(pqa_ctx* ctx);
  * PQA_ECANCELLED.  Mirrors VMAFAnalyzer.terminate_analysis (app/vmaf_analyzer.py:139-151). */
 PQA_API int pqa_cancel(pqa_ctx* ctx);
 
-/* Clear the cancel flag and the motion / xpsnr continuity state (start of a new clip). */
+/* Clear the cancel flag and the motion / xpsnr / siti continuity state (start of a new clip). */
 PQA_API int pqa_reset(pqa_ctx* ctx);
 
 /* Text of the most recent failure on this context (ctx == NULL: last pqa_create failure). */
@@ -427,6 +464,13 @@ PQA_API int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t r
 PQA_API int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const void* ref_m2, const void* dis,
                                    int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth, int32_t hfr,
                                    uint64_t* out, double* wsse);
+
+/* Test hook (needs a device): the PQA_FEAT_SITI kernels on one w x h luma plane cur (u8 at bit_depth 8, u16 at 10; rows
+ * row_pitch_bytes apart) with prev (nullable: a chain start) as the frame before it; full_range != 0: no range
+ * conversion.  gmap (nullable) receives the (w - 2) x (h - 2) gradient map in raster order, si_ti[0] / si_ti[1] the SI
+ * and TI.  w, h >= 3.  PQA_EINVAL on a null pointer, a bad size, depth or pitch, PQA_EDEVICE without a device. */
+PQA_API int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
+                                 uint32_t bit_depth, int32_t full_range, float* gmap, double* si_ti);
 
 #ifdef __cplusplus
 }

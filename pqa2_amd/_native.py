@@ -19,8 +19,9 @@ FEAT_CIEDE = 256                                # libvmaf ciede (ciede2000): res
 FEAT_CAMBI, FEAT_CAMBI_FULL_REF = 512, 1024          # libvmaf cambi of the distorted (and reference) luma: extension record
 FEAT_PSNR_HVS = 2048                            # libvmaf psnr_hvs: results in the second extension record (pqa_collect_ext2)
 FEAT_XPSNR, FEAT_XPSNR_HFR = 4096, 8192              # FFmpeg xpsnr (second-order temporal term): third extension record
+FEAT_SITI, FEAT_SITI_REF_FULL, FEAT_SITI_DIS_FULL = 16384, 32768, 65536   # FFmpeg siti (full-range clips): fourth ext. record
 FEAT_KNOWN = (FEAT_ALL | FEAT_FLOAT_SSIM | FEAT_MS_SSIM | FEAT_CIEDE | FEAT_CAMBI | FEAT_CAMBI_FULL_REF | FEAT_PSNR_HVS
-              | FEAT_XPSNR | FEAT_XPSNR_HFR)
+              | FEAT_XPSNR | FEAT_XPSNR_HFR | FEAT_SITI | FEAT_SITI_REF_FULL | FEAT_SITI_DIS_FULL)
 VIF_BORDER_FLOAT, VIF_BORDER_INTEGER = 0, 1  # pqa_config.vif_border (include/pqa_vmaf.h)
 FIXED_VIF, FIXED_MOTION, FIXED_ADM, FIXED_ALL = 1, 2, 4, 7   # pqa_config.fixed_point mask
 REC_VIF_NUM, REC_VIF_DEN, REC_ADM_NUM, REC_ADM_DEN, REC_MOTION, REC_SSIM, REC_SSE = 0, 4, 8, 12, 16, 17, 20
@@ -37,19 +38,22 @@ EXT2_DOUBLES = 8
 # third extension record (pqa_collect_ext3): XPSNR y / u / v, the three WSSE values; NaN where not run / no such plane
 EXT3_XPSNR_Y, EXT3_XPSNR_U, EXT3_XPSNR_V, EXT3_WSSE, EXT3_RESERVED = 0, 1, 2, 3, 6
 EXT3_DOUBLES = 8
+# fourth extension record (pqa_collect_ext4): SI / TI of the distorted, then of the reference luma; NaN where not run
+EXT4_SI, EXT4_TI, EXT4_SI_SOURCE, EXT4_TI_SOURCE, EXT4_RESERVED = 0, 1, 2, 3, 4
+EXT4_DOUBLES = 8
 PSNR_HVS_TABLE_FLOATS = 384                  # pqa_debug_psnr_hvs_tables: CSF[3][8][8], then M[3][8][8]
 PROF_KERNELS = 17
 GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 
 # every symbol include/pqa_vmaf.h declares
 EXPORTS = [
-    "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
-    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_sync",
+    "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
+    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_sync",
     "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape",
     "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
-    "pqa_debug_psnr_hvs_tables", "pqa_debug_psnr_hvs_plane", "pqa_debug_xpsnr_blocks",
+    "pqa_debug_psnr_hvs_tables", "pqa_debug_psnr_hvs_plane", "pqa_debug_xpsnr_blocks", "pqa_debug_siti_plane",
 ]
 
 
@@ -148,6 +152,9 @@ def load():
     lib.pqa_collect_ext3.argtypes = [vp, i64, i32, vp, vp, vp, vp]
     lib.pqa_ext3_doubles.restype = C.c_int
     lib.pqa_set_ref_history.argtypes = [vp, vp, i32, i64]
+    lib.pqa_collect_ext4.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
+    lib.pqa_ext4_doubles.restype = C.c_int
+    lib.pqa_set_dis_history.argtypes = [vp, vp, i64]
     lib.pqa_sync.argtypes = [vp]
     lib.pqa_cancel.argtypes = [vp]
     lib.pqa_luma_stats_device.argtypes = [vp, vp, i64, i64, i32, C.c_uint32, vp]
@@ -167,11 +174,13 @@ def load():
     lib.pqa_debug_psnr_hvs_tables.argtypes = [vp, i32]
     lib.pqa_debug_psnr_hvs_plane.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     lib.pqa_debug_xpsnr_blocks.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, i32, vp, vp]
+    lib.pqa_debug_siti_plane.argtypes = [vp, vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, i32, vp, vp]
     lib.pqa_profile_kernel_name.argtypes = [C.c_int]
     lib.pqa_profile_kernel_name.restype = C.c_char_p
     assert lib.pqa_record_doubles() == RECORD_DOUBLES
     assert lib.pqa_ext_doubles() == EXT_DOUBLES
     assert lib.pqa_ext2_doubles() == EXT2_DOUBLES
     assert lib.pqa_ext3_doubles() == EXT3_DOUBLES
+    assert lib.pqa_ext4_doubles() == EXT4_DOUBLES
     _lib = lib
     return lib

@@ -347,5 +347,18 @@ struct XpFinalizeArgs {
 };
 hipError_t launch_xpsnr_finalize(hipStream_t stream, const XpFinalizeArgs& args);
 
+// ---- SI / TI: FFmpeg's siti filter (siti.hip) ----------------------------------------------------------------------------
+constexpr int kSitiSegRows = 128;     // rows per wave segment (bounds the int32 sum of m^2 per lane: 128 * 1023^2 < 2^31)
+// wave partials per frame and clip of a w x h luma plane (4 doubles each)
+int siti_partials(int w, int h);
+// SI and TI of n_frames frames of n_clips clips (clip 0: distorted, clip 1: reference; u8 / u16 luma, 8 or 10 bit):
+// frame f's predecessor is frame f - 1 of the run; prev0[z] (nullptr: a chain start, TI 0; row pitch in elements) stands
+// for frame -1 of clip z.  full[z]: clip z is full range (no conversion).  partials: [n_frames][2][siti_partials(w, h)][4].
+// SI / TI of clip z go to slots 2z / 2z + 1 of ring row (slot_base + f) % capacity of ext4; the other slots are left alone.
+// gmap (nullable, test hook): the (w - 2) x (h - 2) gradient map of frame 0 of clip 0.
+hipError_t launch_siti(hipStream_t stream, Elem elem, const PlaneRun clip[2], const void* const prev0[2],
+                       const int64_t prev0_pitch[2], const bool full[2], int n_clips, int n_frames, int w, int h,
+                       double* partials, double* ext4, int ext_stride, int slot_base, int capacity, float* gmap);
+
 }  // namespace pqa
 

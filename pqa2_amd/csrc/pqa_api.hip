@@ -150,6 +150,13 @@ struct pqa_ctx {
   uint8_t* xp_prev = nullptr;        // pqa_submit_surfaces: its shifted prev_ref (allocated on first use)
   int64_t xp_last = -1;              // last frame of the previous batch (the chain continues at xp_last + 1)
   int xp_armed = -1;                 // pqa_set_ref_history: planes armed in xp_hist[0..n) for the next batch (-1: none)
+  // SI / TI (PQA_FEAT_SITI; siti.hip): nothing is allocated unless the bit is set
+  double* ext4 = nullptr;            // [capacity][PQA_EXT4_DOUBLES] ring beside `records`
+  double* st_part = nullptr;         // [B][2][siti_partials][4]
+  uint8_t* st_hist[2] = {nullptr, nullptr};   // the last luma plane of each clip's chain (0: distorted, 1: reference)
+  int64_t st_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
+  int64_t st_hist_pitch = 0;                  // bytes
+  bool st_armed[2] = {false, false};          // pqa_set_dis_history / the reference history armed st_hist[z] as frame first-1
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -706,6 +713,31 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
                                   c->xp_geo, c->xp_blk));
     HIPCHK(c, launch_xpsnr_finalize(st_misc, xa));
   }
+  if (feat & PQA_FEAT_SITI) {
+    // SI / TI of both clips on every frame; frame first-1 of each clip: the caller's halo (reference), the kept or the
+    // armed plane; none at a chain start
+    const void* sp0[2] = {nullptr, nullptr};
+    int64_t spp[2] = {0, 0};
+    for (int z = 0; z < 2; ++z) {
+      if (c->st_armed[z]) {
+        c->st_hist_idx[z] = first - 1;
+        c->st_armed[z] = false;
+      }
+      if (c->st_hist_idx[z] >= 0 && c->st_hist_idx[z] == first - 1) {
+        sp0[z] = c->st_hist[z];
+        spp[z] = c->st_hist_pitch / es;
+      }
+    }
+    if (prev) {
+      if (prev_pitch_bytes % es) return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
+      sp0[1] = prev;
+      spp[1] = prev_pitch_bytes / es;
+    }
+    const PlaneRun sc[2] = {dY, rY};
+    const bool sfull[2] = {(feat & PQA_FEAT_SITI_DIS_FULL) != 0, (feat & PQA_FEAT_SITI_REF_FULL) != 0};
+    HIPCHK(c, launch_siti(st_misc, c->elem, sc, sp0, spp, sfull, 2, n, w, h, c->st_part, c->ext4, PQA_EXT4_DOUBLES,
+                          (int)(first % c->capacity), c->capacity, nullptr));
+  }
 
   if (multi) {  // join
     HIPCHK(c, hipEventRecord(c->join_ev[0], st_adm));
@@ -802,6 +834,16 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
       HIPCHK(c, keep(slot, frame(0), ref->row_pitch[0], first));
     }
     c->xp_last = first + n - 1;
+  }
+  if (feat & PQA_FEAT_SITI) {
+    // keep each clip's last luma plane (behind the join: this batch's kernels have read the old ones)
+    const pqa_device_clip* side[2] = {dis, ref};
+    for (int z = 0; z < 2; ++z) {
+      const uint8_t* src = (const uint8_t*)side[z]->plane[0] + (int64_t)(n - 1) * side[z]->frame_pitch[0];
+      HIPCHK(c, hipMemcpy2DAsync(c->st_hist[z], c->st_hist_pitch, src, side[z]->row_pitch[0], (size_t)w * es, h,
+                                 hipMemcpyDeviceToDevice, st));
+      c->st_hist_idx[z] = first + n - 1;
+    }
   }
   return PQA_OK;
 }
@@ -1044,6 +1086,7 @@ int pqa_record_doubles(void) { return PQA_RECORD_DOUBLES; }
 int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
 int pqa_ext2_doubles(void) { return PQA_EXT2_DOUBLES; }
 int pqa_ext3_doubles(void) { return PQA_EXT3_DOUBLES; }
+int pqa_ext4_doubles(void) { return PQA_EXT4_DOUBLES; }
 
 void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
   if (!cfg) return;
@@ -1113,6 +1156,10 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
       return fail(nullptr, PQA_EINVAL, "xpsnr: unsupported block grid for %ux%u (chroma shifts %u, %u)", cfg->width,
                   cfg->height, cfg->chroma_hshift, cfg->chroma_vshift);
   }
+  if ((cfg->features & (PQA_FEAT_SITI_REF_FULL | PQA_FEAT_SITI_DIS_FULL)) && !(cfg->features & PQA_FEAT_SITI))
+    return fail(nullptr, PQA_EINVAL, "siti range bits (PQA_FEAT_SITI_REF_FULL / _DIS_FULL) need PQA_FEAT_SITI");
+  if ((cfg->features & PQA_FEAT_SITI) && cfg->bit_depth != 8 && cfg->bit_depth != 10)
+    return fail(nullptr, PQA_EINVAL, "siti supports bit depth 8 or 10 (got %u)", cfg->bit_depth);
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
   int ndev = 0;
@@ -1352,6 +1399,13 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     CREATE_TRY(dev_alloc(c, &c->ext3, (size_t)c->capacity * PQA_EXT3_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext3, 0, c->capacity, c->capacity, PQA_EXT3_DOUBLES));
   }
+  if (cfg->features & PQA_FEAT_SITI) {
+    CREATE_TRY(dev_alloc(c, &c->st_part, (size_t)siti_partials(w, h) * 2 * 4 * B));
+    c->st_hist_pitch = round_up((int64_t)w * c->esize, 64);
+    for (int z = 0; z < 2; ++z) CREATE_TRY(dev_alloc(c, &c->st_hist[z], (size_t)c->st_hist_pitch * h));
+    CREATE_TRY(dev_alloc(c, &c->ext4, (size_t)c->capacity * PQA_EXT4_DOUBLES));
+    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext4, 0, c->capacity, c->capacity, PQA_EXT4_DOUBLES));
+  }
   if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)) {
     CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext, 0, c->capacity, c->capacity, PQA_EXT_DOUBLES));
@@ -1511,12 +1565,15 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
       c->halo_armed = true;
     }
   }
-  if (prev_ref && (c->cfg.features & PQA_FEAT_XPSNR) && shift_luma) {   // xpsnr's frame first-1, shifted down likewise
+  // xpsnr's and siti's reference frame first-1, shifted down likewise
+  const bool shift_prev = prev_ref && (c->cfg.features & (PQA_FEAT_XPSNR | PQA_FEAT_SITI)) && shift_luma;
+  const int64_t shift_prev_pitch = round_up((int64_t)c->pw[0] * c->esize, 64);
+  if (shift_prev) {
     if (!c->xp_prev) {
-      HIPCHK(c, hipMalloc((void**)&c->xp_prev, (size_t)c->xp_hist_pitch * c->ph[0]));
+      HIPCHK(c, hipMalloc((void**)&c->xp_prev, (size_t)shift_prev_pitch * c->ph[0]));
       c->allocs.push_back(c->xp_prev);
     }
-    HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->xp_prev, c->xp_hist_pitch, 0,
+    HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->xp_prev, shift_prev_pitch, 0,
                                     c->pw[0], c->ph[0], shift, 1));
   }
   const int n_launch = (n_frames + c->B - 1) / c->B;   // equal launches, as in pqa_submit_device
@@ -1555,8 +1612,8 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     const void* prev = nullptr;
     int64_t prev_pitch = 0;
     if (done == 0 && prev_ref && !shift_luma) { prev = prev_ref->luma; prev_pitch = prev_ref->luma_row_pitch; }
-    if (done == 0 && prev_ref && shift_luma && (c->cfg.features & PQA_FEAT_XPSNR)) {   // the same frame as the armed halo
-      prev = c->xp_prev; prev_pitch = c->xp_hist_pitch;
+    if (done == 0 && shift_prev) {   // the same frame as the armed halo
+      prev = c->xp_prev; prev_pitch = shift_prev_pitch;
     }
     rc = process_batch(c, first_index + done, n, &r, &d, prev, prev_pitch);
     if (rc != PQA_OK) return rc;
@@ -1620,7 +1677,8 @@ namespace {
 // pqa_set_motion_halo / pqa_set_ref_history: motion's halo from prev[0], xpsnr's history from prev[0..n_prev)
 int set_history(pqa_ctx* c, const void* const* prev, int n_prev, int64_t row_stride) {
   const bool mot = c->cfg.features & PQA_FEAT_MOTION, xp = c->cfg.features & PQA_FEAT_XPSNR;
-  if (!mot && !xp) return PQA_OK;
+  const bool si = c->cfg.features & PQA_FEAT_SITI;
+  if (!mot && !xp && !si) return PQA_OK;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = flush_pending(c);
   if (rc != PQA_OK) return rc;
@@ -1630,6 +1688,8 @@ int set_history(pqa_ctx* c, const void* const* prev, int n_prev, int64_t row_str
     c->xp_armed = -1;
     c->xp_last = -1;
     c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
+    c->st_armed[1] = false;
+    c->st_hist_idx[1] = -1;
     return PQA_OK;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1642,6 +1702,10 @@ int set_history(pqa_ctx* c, const void* const* prev, int n_prev, int64_t row_str
     for (int j = 0; j < n_prev; ++j)
       HIPCHK(c, hipMemcpy2D(c->xp_hist[j], c->xp_hist_pitch, prev[j], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
     c->xp_armed = n_prev;
+  }
+  if (si) {
+    HIPCHK(c, hipMemcpy2D(c->st_hist[1], c->st_hist_pitch, prev[0], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
+    c->st_armed[1] = true;
   }
   return PQA_OK;
 }
@@ -1661,6 +1725,26 @@ int pqa_set_ref_history(pqa_ctx* c, const void* const* prev_luma_host, int32_t n
   if (n_prev > 0 && row_stride < (int64_t)c->pw[0] * c->esize)
     return fail(c, PQA_EINVAL, "pqa_set_ref_history: row stride %lld smaller than a row", (long long)row_stride);
   return set_history(c, prev_luma_host, n_prev, row_stride);
+}
+
+int pqa_set_dis_history(pqa_ctx* c, const void* prev_dis_luma_host, int64_t row_stride) {
+  if (!c) return PQA_EINVAL;
+  if (!(c->cfg.features & PQA_FEAT_SITI)) return PQA_OK;
+  if (prev_dis_luma_host && row_stride < (int64_t)c->pw[0] * c->esize)
+    return fail(c, PQA_EINVAL, "pqa_set_dis_history: row stride %lld smaller than a row", (long long)row_stride);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = flush_pending(c);
+  if (rc != PQA_OK) return rc;
+  if (!prev_dis_luma_host) {   // a chain start of the distorted clip
+    c->st_armed[0] = false;
+    c->st_hist_idx[0] = -1;
+    return PQA_OK;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy2D(c->st_hist[0], c->st_hist_pitch, prev_dis_luma_host, row_stride, (size_t)c->pw[0] * c->esize,
+                        c->ph[0], hipMemcpyHostToDevice));
+  c->st_armed[0] = true;
+  return PQA_OK;
 }
 
 int pqa_flush(pqa_ctx* c) {
@@ -1683,19 +1767,24 @@ int pqa_sync(pqa_ctx* c) {
 }
 
 int pqa_collect(pqa_ctx* c, int64_t first_index, int32_t count, double* records) {
-  return pqa_collect_ext3(c, first_index, count, records, nullptr, nullptr, nullptr);
+  return pqa_collect_ext4(c, first_index, count, records, nullptr, nullptr, nullptr, nullptr);
 }
 
 int pqa_collect_ext(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext) {
-  return pqa_collect_ext3(c, first_index, count, records, ext, nullptr, nullptr);
+  return pqa_collect_ext4(c, first_index, count, records, ext, nullptr, nullptr, nullptr);
 }
 
 int pqa_collect_ext2(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2) {
-  return pqa_collect_ext3(c, first_index, count, records, ext, ext2, nullptr);
+  return pqa_collect_ext4(c, first_index, count, records, ext, ext2, nullptr, nullptr);
 }
 
 int pqa_collect_ext3(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
                      double* ext3) {
+  return pqa_collect_ext4(c, first_index, count, records, ext, ext2, ext3, nullptr);
+}
+
+int pqa_collect_ext4(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
+                     double* ext3, double* ext4) {
   if (!c) return PQA_EINVAL;
   if (count < 0 || first_index < 0 || (count > 0 && !records)) return fail(c, PQA_EINVAL, "bad argument");
   if (count > c->capacity) return fail(c, PQA_ESTATE, "count %d exceeds result_capacity %d", count, c->capacity);
@@ -1759,6 +1848,12 @@ int pqa_collect_ext3(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
                           (size_t)n * PQA_EXT3_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
     } else if (ext3) {
       std::fill(ext3 + (size_t)done * PQA_EXT3_DOUBLES, ext3 + (size_t)(done + n) * PQA_EXT3_DOUBLES, __builtin_nan(""));
+    }
+    if (ext4 && c->ext4) {  // and the fourth
+      HIPCHK(c, hipMemcpy(ext4 + (size_t)done * PQA_EXT4_DOUBLES, c->ext4 + (size_t)row * PQA_EXT4_DOUBLES,
+                          (size_t)n * PQA_EXT4_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (ext4) {
+      std::fill(ext4 + (size_t)done * PQA_EXT4_DOUBLES, ext4 + (size_t)(done + n) * PQA_EXT4_DOUBLES, __builtin_nan(""));
     }
     done += n;
     row = 0;
@@ -1899,6 +1994,8 @@ int pqa_reset(pqa_ctx* c) {
   c->xp_armed = -1;
   c->xp_last = -1;
   c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
+  c->st_armed[0] = c->st_armed[1] = false;
+  c->st_hist_idx[0] = c->st_hist_idx[1] = -1;
   c->err.clear();
   return PQA_OK;
 }
@@ -2152,6 +2249,50 @@ int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const void* ref_
   for (int k = 0; k < geo.n_blk; ++k)
     for (int i = 0; i < 3; ++i) out[k * 3 + i] = hb[(size_t)k * kXpBlockVals + i];
   if (wsse) *wsse = row[PQA_EXT3_WSSE];
+  return PQA_OK;
+}
+
+int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
+                         uint32_t bit_depth, int32_t full_range, float* gmap, double* si_ti) {
+  if (!cur || !si_ti || w < 3 || h < 3 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_siti_plane: bad argument");
+  const int es = bit_depth > 8 ? 2 : 1;
+  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_siti_plane: bad row pitch %lld", (long long)row_pitch_bytes);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
+  const size_t plane_bytes = (size_t)w * h * es, map_floats = (size_t)(w - 2) * (h - 2);
+  const void* host[2] = {cur, prev};
+  void* dev[2] = {nullptr, nullptr};
+  double *part = nullptr, *ext4 = nullptr;
+  float* dmap = nullptr;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+    if (!host[i]) continue;
+    e = hipMalloc(&dev[i], plane_bytes);
+    if (e == hipSuccess)
+      e = hipMemcpy2D(dev[i], (size_t)w * es, host[i], (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMalloc((void**)&part, (size_t)siti_partials((int)w, (int)h) * 2 * 4 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&ext4, PQA_EXT4_DOUBLES * sizeof(double));
+  if (e == hipSuccess && gmap) e = hipMalloc((void**)&dmap, map_floats * sizeof(float));
+  if (e == hipSuccess) {
+    const PlaneRun clip[2] = {{dev[0], (int64_t)w, (int64_t)w * h}, {dev[0], (int64_t)w, (int64_t)w * h}};
+    const void* p0[2] = {dev[1], nullptr};
+    const int64_t pp[2] = {dev[1] ? (int64_t)w : 0, 0};
+    const bool full[2] = {full_range != 0, false};
+    e = launch_siti(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, clip, p0, pp, full, 1, 1, (int)w, (int)h, part, ext4,
+                    PQA_EXT4_DOUBLES, 0, 1, dmap);
+  }
+  double row[PQA_EXT4_DOUBLES];
+  if (e == hipSuccess) e = hipMemcpy(row, ext4, sizeof row, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && gmap) e = hipMemcpy(gmap, dmap, map_floats * sizeof(float), hipMemcpyDeviceToHost);
+  for (void* q : {dev[0], dev[1], (void*)part, (void*)ext4, (void*)dmap})
+    if (q) hipFree(q);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_siti_plane: %s", hipGetErrorString(e));
+  si_ti[0] = row[PQA_EXT4_SI];
+  si_ti[1] = row[PQA_EXT4_TI];
   return PQA_OK;
 }
 

@@ -170,6 +170,15 @@ class FeatureEngine:
         stride = planes[0].strides[0] if planes else 0
         self._check(self.lib.pqa_set_ref_history(self._ctx, ptrs, len(planes), stride))
 
+    def set_dis_history(self, prev_dis_luma: np.ndarray | None):
+        """The distorted luma plane in front of the next submitted frame (frame first-1), from which siti's TI of the
+        distorted clip continues; None restarts that chain (pqa_set_dis_history)."""
+        if prev_dis_luma is None:
+            self._check(self.lib.pqa_set_dis_history(self._ctx, None, 0))
+            return
+        a = np.ascontiguousarray(prev_dis_luma, dtype=self.dtype)
+        self._check(self.lib.pqa_set_dis_history(self._ctx, a.ctypes.data, a.strides[0]))
+
     # -- device-resident path ------------------------------------------------------------------
     def submit_resident(self, first_index: int, n_frames: int, ref_ptrs, dis_ptrs, row_pitch, frame_pitch,
                         prev_ref_luma_ptr: int = 0, prev_row_pitch: int = 0):
@@ -273,6 +282,18 @@ class FeatureEngine:
         self._check(self.lib.pqa_collect_ext3(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
                                               ext2.ctypes.data, ext3.ctypes.data))
         return out, ext, ext2, ext3
+
+    def collect_ext4(self, first_index: int, count: int):
+        """(records, ext, ext2, ext3, ext4 [count, EXT4_DOUBLES]): collect_ext3() plus the fourth extension rows of the
+        same frames (pqa_collect_ext4; siti slots, NaN where the context does not run it)."""
+        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
+        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
+        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
+        ext3 = np.zeros((count, N.EXT3_DOUBLES), np.float64)
+        ext4 = np.zeros((count, N.EXT4_DOUBLES), np.float64)
+        self._check(self.lib.pqa_collect_ext4(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
+                                              ext2.ctypes.data, ext3.ctypes.data, ext4.ctypes.data))
+        return out, ext, ext2, ext3, ext4
 
     def flush(self):
         self._check(self.lib.pqa_flush(self._ctx))

@@ -30,7 +30,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
                 fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
                 ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False,
-                psnr_hvs: bool = False, xpsnr: bool = False) -> ScoreResult | None:
+                psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -42,7 +42,10 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     record; needs the chroma planes: a monochrome clip is an error).
     `xpsnr`: FFmpeg's xpsnr filter on every frame as the extra columns xpsnr_y / _u / _v (third extension record; a
     monochrome clip gives xpsnr_y only), its stats-file lines and summary; the second-order temporal term when the clip's
-    integer frame rate (fps_num // fps_den) is 32 or more."""
+    integer frame rate (fps_num // fps_den) is 32 or more.
+    `siti`: FFmpeg's siti filter (ITU-T P.910 SI / TI) of the distorted and of the reference luma on every frame as the
+    extra columns siti_si / siti_ti / siti_si_source / siti_ti_source (fourth extension record); a clip whose Y4M header
+    says XCOLORRANGE=FULL is taken as full range, any other as limited range."""
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -73,6 +76,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         feats |= N.FEAT_PSNR_HVS
     if xpsnr:
         feats |= N.FEAT_XPSNR | (N.FEAT_XPSNR_HFR if xpsnr_hfr(ri) else 0)
+    if siti:
+        feats |= N.FEAT_SITI | (N.FEAT_SITI_REF_FULL if ri.color_range == "full" else 0)
+        feats |= N.FEAT_SITI_DIS_FULL if di.color_range == "full" else 0
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -87,6 +93,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             eng.set_ref_history([ref_rd.frame(a - 1)[0]] + ([ref_rd.frame(a - 2)[0]] if a >= 2 else []))
         elif a > 0:
             eng.set_motion_halo(ref_rd.frame(a - 1)[0])   # one-frame halo in front of this rank's chunk
+        if a > 0 and siti:    # siti's TI of the distorted clip continues from its frame a-1 (the reference's: the halo)
+            eng.set_dis_history(dis_rd.frame(a - 1)[0])
         # both clips are files of packed planes (.y4m): the library reads them straight into its pinned staging (pqa_submit_fd:
         # one copy, no page faults) instead of copying frames out of the readers' mappings
         by_fd = all(hasattr(r, "fileno") and hasattr(r, "plane_offsets") for r in (ref_rd, dis_rd)) and hasattr(eng, "submit_file")
@@ -115,8 +123,12 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             i += m
             if progress is not None:
                 progress(i - a, b - a)
-        local_ext = local_ext2 = local_ext3 = None
-        if xpsnr:      # the third extension record is read only when xpsnr is on
+        local_ext = local_ext2 = local_ext3 = local_ext4 = None
+        if siti:       # the fourth extension record is read only when siti is on
+            local, local_ext, local_ext2, local_ext3, local_ext4 = eng.collect_ext4(a, b - a) if b > a else (
+                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
+                np.zeros((0, N.EXT3_DOUBLES)), np.zeros((0, N.EXT4_DOUBLES)))
+        elif xpsnr:    # the third extension record is read only when xpsnr is on
             local, local_ext, local_ext2, local_ext3 = eng.collect_ext3(a, b - a) if b > a else (
                 np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
                 np.zeros((0, N.EXT3_DOUBLES)))
@@ -136,6 +148,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
     ext3 = shard.gather_records(local_ext3, n, world_size, rank, gather_device, width=N.EXT3_DOUBLES) if xpsnr else None
+    ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
     if rank != 0:
         return None
     elapsed = time.perf_counter() - t_start
@@ -150,6 +163,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         extra.update(ext2=ext2, psnr_hvs=True)
     if xpsnr:
         extra.update(ext3=ext3, xpsnr=True)
+    if siti:
+        extra.update(ext4=ext4, siti=True)
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                           fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
@@ -158,13 +173,16 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
                    n_planes: int = 1, fps: float = 0.0, ext: np.ndarray | None = None, float_ssim: bool = False,
                    ms_ssim: bool = False, ciede: bool = False, cambi: bool = False,
                    cambi_full_ref: bool = False, ext2: np.ndarray | None = None, psnr_hvs: bool = False,
-                   ext3: np.ndarray | None = None, xpsnr: bool = False) -> ScoreResult:
+                   ext3: np.ndarray | None = None, xpsnr: bool = False, ext4: np.ndarray | None = None,
+                   siti: bool = False) -> ScoreResult:
     """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
     / `ciede` the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim /
     ciede2000 columns, with `cambi` / `cambi_full_ref` libvmaf's cambi, cambi_source and cambi_full_reference.  With
     `psnr_hvs` the second extension records `ext2` ([n, EXT2_DOUBLES], pqa_collect_ext2) add psnr_hvs_y / _cb / _cr and
     psnr_hvs.  With `xpsnr` the third extension records `ext3` ([n, EXT3_DOUBLES], pqa_collect_ext3) add xpsnr_y / _u /
-    _v, FFmpeg's stats-file lines (xpsnr_lines) and its summary (xpsnr_summary, report.xpsnr_summary) of every frame."""
+    _v, FFmpeg's stats-file lines (xpsnr_lines) and its summary (xpsnr_summary, report.xpsnr_summary) of every frame.
+    With `siti` the fourth extension records `ext4` ([n, EXT4_DOUBLES], pqa_collect_ext4) add siti_si / siti_ti of the
+    distorted and siti_si_source / siti_ti_source of the reference luma."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -215,6 +233,11 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         wsse = ext3[:, N.EXT3_WSSE:N.EXT3_WSSE + n_planes]
         xpsnr_lines = report.xpsnr_stats_lines(db)
         xpsnr_summary = report.xpsnr_summary(wsse, db, plane_sizes, info.bit_depth)
+    if siti:
+        if ext4 is None or ext4.shape != (n, N.EXT4_DOUBLES):
+            raise ValueError("siti needs the fourth extension records of every frame")
+        for key, slot in SITI_KEYS:
+            metrics[key] = ext4[:, slot].copy()
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:
@@ -224,6 +247,10 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
     return ScoreResult(metrics=scored, frame_indices=idx, records=rec, info=info, fps=fps,
                        psnr_lines=psnr_lines, ssim_lines=ssim_lines, model_name=mdl.name,
                        **({"xpsnr_lines": xpsnr_lines, "xpsnr_summary": xpsnr_summary} if xpsnr else {}))
+
+
+SITI_KEYS = (("siti_si", N.EXT4_SI), ("siti_ti", N.EXT4_TI), ("siti_si_source", N.EXT4_SI_SOURCE),
+             ("siti_ti_source", N.EXT4_TI_SOURCE))
 
 
 def xpsnr_hfr(info) -> bool:

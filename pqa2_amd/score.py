@@ -74,6 +74,9 @@ def main(argv=None) -> int:
     ap.add_argument("--xpsnr", action="store_true",
                     help="add FFmpeg's xpsnr: xpsnr_y / _u / _v per frame and FFmpeg's summary in the JSON's top level")
     ap.add_argument("--xpsnr-log", default=None, help="FFmpeg xpsnr stats_file output path (implies --xpsnr)")
+    ap.add_argument("--siti", action="store_true",
+                    help="add FFmpeg's siti (ITU-T P.910 SI / TI) of both clips: siti_si / _ti (distorted) and "
+                         "siti_si_source / _ti_source (reference), per frame and pooled")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -113,7 +116,8 @@ def main(argv=None) -> int:
                           **({"ciede": True} if a.ciede else {}), **({"cambi": True} if a.cambi else {}),
                           **({"cambi_full_ref": True} if a.cambi_full_ref else {}),
                           **({"psnr_hvs": True} if a.psnr_hvs else {}),
-                          **({"xpsnr": True} if (a.xpsnr or a.xpsnr_log) else {}))
+                          **({"xpsnr": True} if (a.xpsnr or a.xpsnr_log) else {}),
+                          **({"siti": True} if a.siti else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
         return 1

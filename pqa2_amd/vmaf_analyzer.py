@@ -155,6 +155,7 @@ class VMAFAnalyzer(QObject):
         self.psnr_hvs_enabled = False         # libvmaf psnr_hvs (feature=name=psnr_hvs): psnr_hvs_y / _cb / _cr, psnr_hvs
         self.xpsnr_enabled = False            # FFmpeg xpsnr: <test>_<ts>_xpsnr.txt stats file, xpsnr_y / _u / _v, xpsnr
         self._xpsnr_path = None               # where this analysis writes the xpsnr stats file (set per analysis)
+        self.siti_enabled = False             # FFmpeg siti (ITU-T P.910 SI / TI) of both clips, per frame and pooled
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -179,6 +180,7 @@ class VMAFAnalyzer(QObject):
             self.cambi_full_ref_enabled = bool(s.get("cambi_full_ref_enabled", False))
             self.psnr_hvs_enabled = bool(s.get("psnr_hvs_enabled", False))
             self.xpsnr_enabled = bool(s.get("xpsnr_enabled", False))
+            self.siti_enabled = bool(s.get("siti_enabled", False))
             logger.info(f"VMAF options set from manager: threads={self.threads}, "
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
@@ -197,7 +199,8 @@ class VMAFAnalyzer(QObject):
     def set_advanced_options(self, pool_method="mean", enable_motion_score=False, enable_temporal_features=False,
                              feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
                              ms_ssim_enabled=False, ciede_enabled=False, cambi_enabled=False,
-                             cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False):
+                             cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False,
+                             siti_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -211,6 +214,7 @@ class VMAFAnalyzer(QObject):
         self.cambi_full_ref_enabled = bool(cambi_full_ref_enabled)
         self.psnr_hvs_enabled = bool(psnr_hvs_enabled)
         self.xpsnr_enabled = bool(xpsnr_enabled)
+        self.siti_enabled = bool(siti_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -406,7 +410,8 @@ class VMAFAnalyzer(QObject):
                 **({"cambi": True} if self.cambi_enabled else {}),
                 **({"cambi_full_ref": True} if self.cambi_enabled and self.cambi_full_ref_enabled else {}),
                 **({"psnr_hvs": True} if self.psnr_hvs_enabled else {}),
-                **({"xpsnr": True} if self.xpsnr_enabled else {})}
+                **({"xpsnr": True} if self.xpsnr_enabled else {}),
+                **({"siti": True} if self.siti_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -433,6 +438,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--psnr-hvs"]
         if self.xpsnr_enabled:
             cmd += ["--xpsnr"] + (["--xpsnr-log", self._xpsnr_path] if self._xpsnr_path else [])
+        if self.siti_enabled:
+            cmd += ["--siti"]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -539,6 +546,11 @@ class VMAFAnalyzer(QObject):
                 for key in ("xpsnr_y", "xpsnr_u", "xpsnr_v", "xpsnr"):
                     results[key] = vmaf_data.get(key)
                 results["xpsnr_log"] = self._xpsnr_path
+            if self.siti_enabled:   # pooled means of both clips, and the distorted clip's maxima (FFmpeg's summary)
+                for key in ("siti_si", "siti_ti", "siti_si_source", "siti_ti_source"):
+                    results[key] = pooled[key]["mean"] if key in pooled else None
+                for key in ("siti_si", "siti_ti"):
+                    results[key + "_max"] = pooled[key]["max"] if key in pooled else None
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
