@@ -106,9 +106,18 @@ enum {
   PQA_FEAT_SITI = 1u << 14,
   PQA_FEAT_SITI_REF_FULL = 1u << 15,
   PQA_FEAT_SITI_DIS_FULL = 1u << 16,
+  /* Capture integrity of the DISTORTED clip: the per-frame quantities FFmpeg's freezedetect, blackdetect and scdet filters
+   * reduce a frame to (libavfilter/vf_freezedetect.c, vf_blackdetect.c, vf_scdet.c), in the FIFTH extension record
+   * (PQA_EXT5_*, pqa_collect_ext5) on EVERY frame, whatever n_subsample is: the exact sum of absolute differences of
+   * every plane against the previous distorted frame, and the number of luma samples <= the black threshold
+   * (pqa_set_black_threshold).  The previous frame is the frame before it in the batch, the planes the context keeps from
+   * its previous batch, or the history armed with pqa_set_dis_history_planes; no SAD (NaN) at a chain start.  8, 10 and
+   * 12 bit, n_planes 1 or 3, any chroma subsampling.  freezedetect's anchored differences: pqa_frame_sad.  The filters'
+   * host state machines: pqa2_amd/integrity.py; definition and its unpinned items: DESIGN.md sections 1 and 5. */
+  PQA_FEAT_INTEGRITY = 1u << 17,
   PQA_FEAT_KNOWN = PQA_FEAT_ALL | PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI |
                    PQA_FEAT_CAMBI_FULL_REF | PQA_FEAT_PSNR_HVS | PQA_FEAT_XPSNR | PQA_FEAT_XPSNR_HFR | PQA_FEAT_SITI |
-                   PQA_FEAT_SITI_REF_FULL | PQA_FEAT_SITI_DIS_FULL  /* what pqa_create accepts */
+                   PQA_FEAT_SITI_REF_FULL | PQA_FEAT_SITI_DIS_FULL | PQA_FEAT_INTEGRITY  /* what pqa_create accepts */
 };
 
 /* One record = PQA_RECORD_DOUBLES 8-byte slots per frame. */
@@ -179,6 +188,16 @@ enum {
   PQA_EXT4_DOUBLES = 8
 };
 
+/* The FIFTH extension record = PQA_EXT5_DOUBLES slots per frame, kept beside the record ring (same slots, capacity and
+ * wrap) when the context runs PQA_FEAT_INTEGRITY; read with pqa_collect_ext5.  Every submitted frame gets its row; the
+ * values are integers, exact as doubles; the reserved slots hold NaN. */
+enum {
+  PQA_EXT5_SAD_PREV = 0,    /* [3] sum |dis_i - dis_{i-1}| of Y, U, V; NaN at a chain start / where there is no plane */
+  PQA_EXT5_BLACK_COUNT = 3, /* luma samples of dis_i with value <= the black threshold                              */
+  PQA_EXT5_RESERVED = 4,    /* [4]                                                                                   */
+  PQA_EXT5_DOUBLES = 8
+};
+
 typedef struct pqa_config {
   uint32_t struct_size;        /* sizeof(pqa_config), for ABI growth                              */
   int32_t device;              /* HIP device ordinal                                              */
@@ -233,6 +252,7 @@ PQA_API int pqa_ext_doubles(void);
 PQA_API int pqa_ext2_doubles(void);
 PQA_API int pqa_ext3_doubles(void);
 PQA_API int pqa_ext4_doubles(void);
+PQA_API int pqa_ext5_doubles(void);
 
 /* Fill cfg with defaults (8-bit 4:2:0, PQA_FEAT_VMAF, gain limits 100). */
 PQA_API void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height);
@@ -326,6 +346,30 @@ PQA_API int pqa_set_ref_history(pqa_ctx* ctx, const void* const* prev_luma_host,
  * without PQA_FEAT_SITI. */
 PQA_API int pqa_set_dis_history(pqa_ctx* ctx, const void* prev_dis_luma_host, int64_t row_stride);
 
+/* The distorted clip's frame in front of the next submitted frame with ALL its planes (frame a-1 of a frame-sharded rank
+ * that starts at a; planes[p] has rows strides[p] bytes apart, p < n_planes): PQA_FEAT_INTEGRITY's differences continue
+ * from it.  It also arms what pqa_set_dis_history arms (from planes[0]).  planes == NULL restarts both chains.  A no-op
+ * without PQA_FEAT_INTEGRITY and PQA_FEAT_SITI. */
+PQA_API int pqa_set_dis_history_planes(pqa_ctx* ctx, const void* const planes[3], const int64_t strides[3]);
+
+/* The integer sample value at or below which a luma sample counts as black (PQA_EXT5_BLACK_COUNT).  Default: FFmpeg
+ * blackdetect's pixel_black_th = 0.10 on a limited-range clip, trunc(16 f + 0.10 * 219 f), f = 2^(bit_depth - 8): 37 /
+ * 151 / 606 at 8 / 10 / 12 bit.  Legal before the first submit and after pqa_reset (PQA_ESTATE otherwise); PQA_EINVAL
+ * above the largest sample value.  pqa_reset keeps the value. */
+PQA_API int pqa_set_black_threshold(pqa_ctx* ctx, uint32_t threshold);
+
+/* freezedetect's anchored differences, synchronously: out[f * 3 + p] = sum |frame_f[p] - anchor[p]| over plane p, exact,
+ * for n_frames frames in HOST memory against one anchor frame (frames[f * 3 + p]: plane p of frame f, rows strides[p] bytes
+ * apart; anchor_planes[p] rows anchor_strides[p] bytes apart; p < n_planes, out is 0 for the other planes).  n_frames
+ * need not fit max_batch.  Needs PQA_FEAT_INTEGRITY (PQA_ESTATE otherwise).  Independent of the scoring chain. */
+PQA_API int pqa_frame_sad(pqa_ctx* ctx, const void* const anchor_planes[3], const int64_t anchor_strides[3],
+                          const void* const* frames, const int64_t strides[3], int32_t n_frames, uint64_t* out);
+
+/* The same for a clip in DEVICE memory (frames: n_frames frames, pitches in bytes) against an anchor frame in device
+ * memory (anchor_planes[p] rows anchor_row_pitch[p] bytes apart). */
+PQA_API int pqa_frame_sad_device(pqa_ctx* ctx, const void* const anchor_planes[3], const int64_t anchor_row_pitch[3],
+                                 const pqa_device_clip* frames, int32_t n_frames, uint64_t* out);
+
 /* Launch whatever pqa_submit has pending (partial batch). */
 PQA_API int pqa_flush(pqa_ctx* ctx);
 
@@ -358,6 +402,11 @@ PQA_API int pqa_collect_ext3(pqa_ctx* ctx, int64_t first_index, int32_t count, d
 PQA_API int pqa_collect_ext4(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
                              double* ext3, double* ext4);
 
+/* pqa_collect_ext4 with the fifth extension record as well: ext5[count][PQA_EXT5_DOUBLES] receives the ext5 rows of the
+ * same frames.  ext .. ext5 may be NULL.  A context without PQA_FEAT_INTEGRITY returns all-NaN ext5 rows. */
+PQA_API int pqa_collect_ext5(pqa_ctx* ctx, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
+                             double* ext3, double* ext4, double* ext5);
+
 /* Wait for all submitted work without collecting. */
 PQA_API int pqa_sync(pqa_ctx* ctx);
 
@@ -365,7 +414,7 @@ PQA_API int pqa_sync(pqa_ctx* ctx);
  * PQA_ECANCELLED.  Mirrors VMAFAnalyzer.terminate_analysis (app/vmaf_analyzer.py:139-151). */
 PQA_API int pqa_cancel(pqa_ctx* ctx);
 
-/* Clear the cancel flag and the motion / xpsnr / siti continuity state (start of a new clip). */
+/* Clear the cancel flag and the motion / xpsnr / siti / integrity continuity state (start of a new clip). */
 PQA_API int pqa_reset(pqa_ctx* ctx);
 
 /* Text of the most recent failure on this context (ctx == NULL: last pqa_create failure). */

@@ -20,8 +20,10 @@ FEAT_CAMBI, FEAT_CAMBI_FULL_REF = 512, 1024          # libvmaf cambi of the dist
 FEAT_PSNR_HVS = 2048                            # libvmaf psnr_hvs: results in the second extension record (pqa_collect_ext2)
 FEAT_XPSNR, FEAT_XPSNR_HFR = 4096, 8192              # FFmpeg xpsnr (second-order temporal term): third extension record
 FEAT_SITI, FEAT_SITI_REF_FULL, FEAT_SITI_DIS_FULL = 16384, 32768, 65536   # FFmpeg siti (full-range clips): fourth ext. record
+FEAT_INTEGRITY = 131072                         # FFmpeg freezedetect / blackdetect / scdet reductions: fifth extension record
 FEAT_KNOWN = (FEAT_ALL | FEAT_FLOAT_SSIM | FEAT_MS_SSIM | FEAT_CIEDE | FEAT_CAMBI | FEAT_CAMBI_FULL_REF | FEAT_PSNR_HVS
-              | FEAT_XPSNR | FEAT_XPSNR_HFR | FEAT_SITI | FEAT_SITI_REF_FULL | FEAT_SITI_DIS_FULL)
+              | FEAT_XPSNR | FEAT_XPSNR_HFR | FEAT_SITI | FEAT_SITI_REF_FULL | FEAT_SITI_DIS_FULL
+              | FEAT_INTEGRITY)
 VIF_BORDER_FLOAT, VIF_BORDER_INTEGER = 0, 1  # pqa_config.vif_border (include/pqa_vmaf.h)
 FIXED_VIF, FIXED_MOTION, FIXED_ADM, FIXED_ALL = 1, 2, 4, 7   # pqa_config.fixed_point mask
 REC_VIF_NUM, REC_VIF_DEN, REC_ADM_NUM, REC_ADM_DEN, REC_MOTION, REC_SSIM, REC_SSE = 0, 4, 8, 12, 16, 17, 20
@@ -41,14 +43,18 @@ EXT3_DOUBLES = 8
 # fourth extension record (pqa_collect_ext4): SI / TI of the distorted, then of the reference luma; NaN where not run
 EXT4_SI, EXT4_TI, EXT4_SI_SOURCE, EXT4_TI_SOURCE, EXT4_RESERVED = 0, 1, 2, 3, 4
 EXT4_DOUBLES = 8
+# fifth extension record (pqa_collect_ext5): exact SAD of Y / U / V against the previous distorted frame (NaN at a chain
+# start / no such plane), the number of luma samples <= the black threshold
+EXT5_SAD_PREV, EXT5_BLACK_COUNT, EXT5_RESERVED = 0, 3, 4
+EXT5_DOUBLES = 8
 PSNR_HVS_TABLE_FLOATS = 384                  # pqa_debug_psnr_hvs_tables: CSF[3][8][8], then M[3][8][8]
 PROF_KERNELS = 17
 GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 
 # every symbol include/pqa_vmaf.h declares
 EXPORTS = [
-    "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
-    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_sync",
+    "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
+    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
     "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape",
@@ -155,6 +161,12 @@ def load():
     lib.pqa_collect_ext4.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
     lib.pqa_ext4_doubles.restype = C.c_int
     lib.pqa_set_dis_history.argtypes = [vp, vp, i64]
+    lib.pqa_collect_ext5.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
+    lib.pqa_ext5_doubles.restype = C.c_int
+    lib.pqa_set_dis_history_planes.argtypes = [vp, C.POINTER(vp * 3), C.POINTER(i64 * 3)]
+    lib.pqa_set_black_threshold.argtypes = [vp, C.c_uint32]
+    lib.pqa_frame_sad.argtypes = [vp, C.POINTER(vp * 3), C.POINTER(i64 * 3), C.POINTER(vp), C.POINTER(i64 * 3), i32, vp]
+    lib.pqa_frame_sad_device.argtypes = [vp, C.POINTER(vp * 3), C.POINTER(i64 * 3), C.POINTER(PqaDeviceClip), i32, vp]
     lib.pqa_sync.argtypes = [vp]
     lib.pqa_cancel.argtypes = [vp]
     lib.pqa_luma_stats_device.argtypes = [vp, vp, i64, i64, i32, C.c_uint32, vp]
@@ -182,5 +194,6 @@ def load():
     assert lib.pqa_ext2_doubles() == EXT2_DOUBLES
     assert lib.pqa_ext3_doubles() == EXT3_DOUBLES
     assert lib.pqa_ext4_doubles() == EXT4_DOUBLES
+    assert lib.pqa_ext5_doubles() == EXT5_DOUBLES
     _lib = lib
     return lib

@@ -360,5 +360,18 @@ hipError_t launch_siti(hipStream_t stream, Elem elem, const PlaneRun clip[2], co
                        const int64_t prev0_pitch[2], const bool full[2], int n_clips, int n_frames, int w, int h,
                        double* partials, double* ext4, int ext_stride, int slot_base, int capacity, float* gmap);
 
+// ---- capture integrity: what FFmpeg's freezedetect / blackdetect / scdet reduce a frame to (integrity.hip) --------------
+constexpr int kIntegrityBlocks = 128;   // workgroups per frame and plane (512 waves, a wave per row at a time)
+// Exact per-plane SAD of n_frames frames of n_planes planes (pw x ph samples each, u8 / u16) and the number of luma samples
+// <= black_threshold.  anchor false: frame f against frame f - 1 of the run, frame 0 against prev0 (all nullptr: a chain
+// start, no SAD for frame 0; row pitches in elements); anchor true: every frame against prev0.
+// partials: [n_frames][3][kIntegrityBlocks][2] uint64.  ext5 (nullable): ring row (slot_base + f) % capacity gets the SADs in
+// slots 0..2 (NaN at a chain start and for planes >= n_planes), the black count in slot 3 and NaN in slots 4..ext_stride-1.
+// out (nullable): [n_frames][3] uint64 SADs.
+hipError_t launch_integrity(hipStream_t stream, Elem elem, const PlaneRun cur[3], const void* const prev0[3],
+                            const int64_t prev0_pitch[3], const int pw[3], const int ph[3], int n_planes, int n_frames,
+                            bool anchor, unsigned black_threshold, unsigned long long* partials, double* ext5,
+                            int ext_stride, int slot_base, int capacity, unsigned long long* out);
+
 }  // namespace pqa
 

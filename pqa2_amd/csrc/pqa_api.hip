@@ -157,6 +157,20 @@ struct pqa_ctx {
   int64_t st_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
   int64_t st_hist_pitch = 0;                  // bytes
   bool st_armed[2] = {false, false};          // pqa_set_dis_history / the reference history armed st_hist[z] as frame first-1
+  // capture integrity (PQA_FEAT_INTEGRITY; integrity.hip): nothing is allocated unless the bit is set
+  double* ext5 = nullptr;            // [capacity][PQA_EXT5_DOUBLES] ring beside `records`
+  unsigned long long* ig_part = nullptr;      // [B][3][kIntegrityBlocks][2]
+  uint8_t* ig_hist[3] = {nullptr, nullptr, nullptr};   // the planes of the last distorted frame of the chain
+  int64_t ig_hist_pitch[3] = {0, 0, 0};       // bytes
+  int64_t ig_hist_idx = -1;                   // its frame index (-1: empty)
+  bool ig_armed = false;                      // pqa_set_dis_history_planes armed ig_hist as frame first-1
+  uint32_t black_thr = 0;                     // pqa_set_black_threshold
+  bool started = false;                       // a batch was launched since pqa_create / pqa_reset
+  // pqa_frame_sad / pqa_frame_sad_device (allocated on first use)
+  uint8_t* ig_anchor[3] = {nullptr, nullptr, nullptr};  // the anchor frame's planes (pitches: ig_hist_pitch)
+  uint8_t* ig_stage = nullptr;                // FB frames of host planes (slot layout: ig_stage_off, ig_stage_bytes)
+  size_t ig_stage_off[3] = {0, 0, 0}, ig_stage_bytes = 0;
+  unsigned long long* ig_out = nullptr;       // [B][3] results of one launch
   unsigned long long* luma_part = nullptr;
   unsigned long long* luma_out = nullptr;
   // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
@@ -329,6 +343,7 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
     const int rc = check_slots_free(c, first, n);
     if (rc != PQA_OK) return rc;
   }
+  c->started = true;
   const PlaneRun rY{ref->plane[0], ref->row_pitch[0] / es, ref->frame_pitch[0] / es};
   const PlaneRun dY{dis->plane[0], dis->row_pitch[0] / es, dis->frame_pitch[0] / es};
   const int w = c->pw[0], h = c->ph[0];
@@ -738,6 +753,27 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
     HIPCHK(c, launch_siti(st_misc, c->elem, sc, sp0, spp, sfull, 2, n, w, h, c->st_part, c->ext4, PQA_EXT4_DOUBLES,
                           (int)(first % c->capacity), c->capacity, nullptr));
   }
+  if (feat & PQA_FEAT_INTEGRITY) {
+    // SAD of every plane of the distorted frames against their predecessors, and the black count; frame first-1: the kept
+    // or the armed planes, none at a chain start
+    if (c->ig_armed) {
+      c->ig_hist_idx = first - 1;
+      c->ig_armed = false;
+    }
+    const bool have = c->ig_hist_idx >= 0 && c->ig_hist_idx == first - 1;
+    PlaneRun cur[3] = {};
+    const void* ip0[3] = {nullptr, nullptr, nullptr};
+    int64_t ipp[3] = {0, 0, 0};
+    for (int p = 0; p < c->n_planes; ++p) {
+      cur[p] = PlaneRun{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
+      if (have) {
+        ip0[p] = c->ig_hist[p];
+        ipp[p] = c->ig_hist_pitch[p] / es;
+      }
+    }
+    HIPCHK(c, launch_integrity(st_misc, c->elem, cur, ip0, ipp, c->pw, c->ph, c->n_planes, n, false, c->black_thr,
+                               c->ig_part, c->ext5, PQA_EXT5_DOUBLES, (int)(first % c->capacity), c->capacity, nullptr));
+  }
 
   if (multi) {  // join
     HIPCHK(c, hipEventRecord(c->join_ev[0], st_adm));
@@ -844,6 +880,15 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
                                  hipMemcpyDeviceToDevice, st));
       c->st_hist_idx[z] = first + n - 1;
     }
+  }
+  if (feat & PQA_FEAT_INTEGRITY) {
+    // keep every plane of the last distorted frame (behind the join: this batch's kernel has read the old ones)
+    for (int p = 0; p < c->n_planes; ++p) {
+      const uint8_t* src = (const uint8_t*)dis->plane[p] + (int64_t)(n - 1) * dis->frame_pitch[p];
+      HIPCHK(c, hipMemcpy2DAsync(c->ig_hist[p], c->ig_hist_pitch[p], src, dis->row_pitch[p], (size_t)c->pw[p] * es, c->ph[p],
+                                 hipMemcpyDeviceToDevice, st));
+    }
+    c->ig_hist_idx = first + n - 1;
   }
   return PQA_OK;
 }
@@ -1087,6 +1132,7 @@ int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
 int pqa_ext2_doubles(void) { return PQA_EXT2_DOUBLES; }
 int pqa_ext3_doubles(void) { return PQA_EXT3_DOUBLES; }
 int pqa_ext4_doubles(void) { return PQA_EXT4_DOUBLES; }
+int pqa_ext5_doubles(void) { return PQA_EXT5_DOUBLES; }
 
 void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
   if (!cfg) return;
@@ -1405,6 +1451,19 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     for (int z = 0; z < 2; ++z) CREATE_TRY(dev_alloc(c, &c->st_hist[z], (size_t)c->st_hist_pitch * h));
     CREATE_TRY(dev_alloc(c, &c->ext4, (size_t)c->capacity * PQA_EXT4_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext4, 0, c->capacity, c->capacity, PQA_EXT4_DOUBLES));
+  }
+  {  // blackdetect's default pixel_black_th = 0.10 on a limited-range clip: 37 / 151 / 606
+    const double f = (double)(1 << (cfg->bit_depth - 8));
+    c->black_thr = (uint32_t)(16.0 * f + 0.10 * 219.0 * f);
+  }
+  if (cfg->features & PQA_FEAT_INTEGRITY) {
+    CREATE_TRY(dev_alloc(c, &c->ig_part, (size_t)B * 3 * kIntegrityBlocks * 2));
+    for (int p = 0; p < c->n_planes; ++p) {
+      c->ig_hist_pitch[p] = round_up((int64_t)c->pw[p] * c->esize, 64);
+      CREATE_TRY(dev_alloc(c, &c->ig_hist[p], (size_t)c->ig_hist_pitch[p] * c->ph[p]));
+    }
+    CREATE_TRY(dev_alloc(c, &c->ext5, (size_t)c->capacity * PQA_EXT5_DOUBLES));
+    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext5, 0, c->capacity, c->capacity, PQA_EXT5_DOUBLES));
   }
   if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)) {
     CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
@@ -1747,6 +1806,156 @@ int pqa_set_dis_history(pqa_ctx* c, const void* prev_dis_luma_host, int64_t row_
   return PQA_OK;
 }
 
+int pqa_set_dis_history_planes(pqa_ctx* c, const void* const planes[3], const int64_t strides[3]) {
+  if (!c) return PQA_EINVAL;
+  const bool ig = c->cfg.features & PQA_FEAT_INTEGRITY, si = c->cfg.features & PQA_FEAT_SITI;
+  if (!ig && !si) return PQA_OK;
+  if (planes) {
+    if (!strides) return fail(c, PQA_EINVAL, "pqa_set_dis_history_planes: null strides");
+    for (int p = 0; p < (ig ? c->n_planes : 1); ++p) {
+      if (!planes[p]) return fail(c, PQA_EINVAL, "pqa_set_dis_history_planes: plane %d is null", p);
+      if (strides[p] < (int64_t)c->pw[p] * c->esize)
+        return fail(c, PQA_EINVAL, "pqa_set_dis_history_planes: plane %d stride %lld smaller than a row", p, (long long)strides[p]);
+    }
+  }
+  if (si) {   // what pqa_set_dis_history arms
+    const int rc = pqa_set_dis_history(c, planes ? planes[0] : nullptr, planes ? strides[0] : 0);
+    if (rc != PQA_OK) return rc;
+  }
+  if (!ig) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = flush_pending(c);
+  if (rc != PQA_OK) return rc;
+  if (!planes) {   // a chain start
+    c->ig_armed = false;
+    c->ig_hist_idx = -1;
+    return PQA_OK;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int p = 0; p < c->n_planes; ++p)
+    HIPCHK(c, hipMemcpy2D(c->ig_hist[p], c->ig_hist_pitch[p], planes[p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
+                          hipMemcpyHostToDevice));
+  c->ig_armed = true;
+  return PQA_OK;
+}
+
+int pqa_set_black_threshold(pqa_ctx* c, uint32_t threshold) {
+  if (!c) return PQA_EINVAL;
+  if (threshold >= (1u << c->cfg.bit_depth))
+    return fail(c, PQA_EINVAL, "black threshold %u above the largest %u-bit sample", threshold, c->cfg.bit_depth);
+  if (c->started || c->pending > 0)
+    return fail(c, PQA_ESTATE, "pqa_set_black_threshold: legal before the first submit and after pqa_reset only");
+  c->black_thr = threshold;
+  return PQA_OK;
+}
+
+namespace {
+// the launches of pqa_frame_sad[_device]: n frames (at most B) of a device clip against the anchor planes, results to out
+int frame_sad_launch(pqa_ctx* c, const void* const anchor[3], const int64_t anchor_pitch_bytes[3], const pqa_device_clip* f,
+                     int n, uint64_t* out) {
+  const int es = c->esize;
+  PlaneRun cur[3] = {};
+  int64_t app[3] = {0, 0, 0};
+  for (int p = 0; p < c->n_planes; ++p) {
+    cur[p] = PlaneRun{f->plane[p], f->row_pitch[p] / es, f->frame_pitch[p] / es};
+    app[p] = anchor_pitch_bytes[p] / es;
+  }
+  if (!c->ig_out) {
+    const int rc = dev_alloc(c, &c->ig_out, (size_t)c->B * 3);
+    if (rc != PQA_OK) return rc;
+  }
+  HIPCHK(c, launch_integrity(c->stream, c->elem, cur, anchor, app, c->pw, c->ph, c->n_planes, n, true, c->black_thr, c->ig_part,
+                             nullptr, 0, 0, 1, c->ig_out));
+  HIPCHK(c, hipMemcpyAsync(out, c->ig_out, (size_t)n * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PQA_OK;
+}
+}  // namespace
+
+int pqa_frame_sad_device(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_row_pitch[3],
+                         const pqa_device_clip* frames, int32_t n_frames, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!anchor_planes || !anchor_row_pitch || !frames || n_frames < 0 || (n_frames > 0 && !out))
+    return fail(c, PQA_EINVAL, "bad argument");
+  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return fail(c, PQA_ESTATE, "pqa_frame_sad_device needs PQA_FEAT_INTEGRITY");
+  for (int p = 0; p < c->n_planes; ++p) {
+    if (!anchor_planes[p] || !frames->plane[p]) return fail(c, PQA_EINVAL, "plane %d pointer is null", p);
+    const int64_t row_bytes = (int64_t)c->pw[p] * c->esize;
+    if (anchor_row_pitch[p] % c->esize || frames->row_pitch[p] % c->esize || frames->frame_pitch[p] % c->esize)
+      return fail(c, PQA_EINVAL, "plane %d pitch is not a multiple of the sample size", p);
+    if (anchor_row_pitch[p] < row_bytes || frames->row_pitch[p] < row_bytes)
+      return fail(c, PQA_EINVAL, "plane %d pitch smaller than a row", p);
+  }
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int done = 0; done < n_frames;) {
+    const int n = n_frames - done < c->B ? n_frames - done : c->B;
+    pqa_device_clip f = *frames;
+    for (int p = 0; p < c->n_planes; ++p) f.plane[p] = (const uint8_t*)frames->plane[p] + (int64_t)done * frames->frame_pitch[p];
+    const int rc = frame_sad_launch(c, anchor_planes, anchor_row_pitch, &f, n, out + (size_t)done * 3);
+    if (rc != PQA_OK) return rc;
+    done += n;
+  }
+  return PQA_OK;
+}
+
+int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_strides[3], const void* const* frames,
+                  const int64_t strides[3], int32_t n_frames, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!anchor_planes || !anchor_strides || n_frames < 0 || (n_frames > 0 && (!frames || !strides || !out)))
+    return fail(c, PQA_EINVAL, "bad argument");
+  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return fail(c, PQA_ESTATE, "pqa_frame_sad needs PQA_FEAT_INTEGRITY");
+  for (int p = 0; p < c->n_planes; ++p) {
+    const int64_t row_bytes = (int64_t)c->pw[p] * c->esize;
+    if (!anchor_planes[p]) return fail(c, PQA_EINVAL, "anchor plane %d pointer is null", p);
+    if (anchor_strides[p] < row_bytes || (n_frames > 0 && strides[p] < row_bytes))
+      return fail(c, PQA_EINVAL, "plane %d stride smaller than a row", p);
+    for (int f = 0; f < n_frames; ++f)   // before anything is queued
+      if (!frames[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "frame %d plane %d pointer is null", f, p);
+  }
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int FB = c->B < 8 ? c->B : 8;   // frames per upload and launch
+  if (!c->ig_stage) {   // lazily: a healthy clip never asks for an anchored difference
+    size_t off = 0;
+    for (int p = 0; p < c->n_planes; ++p) {
+      c->ig_stage_off[p] = off;
+      off += (size_t)round_up(c->ig_hist_pitch[p] * c->ph[p], 256);
+    }
+    c->ig_stage_bytes = off;
+    for (int p = 0; p < c->n_planes; ++p) {
+      const int rc = dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist_pitch[p] * c->ph[p]);
+      if (rc != PQA_OK) return rc;
+    }
+    const int rc = dev_alloc(c, &c->ig_stage, off * (size_t)FB);
+    if (rc != PQA_OK) return rc;
+  }
+  // plain synchronous copies from the caller's (pageable) planes: this call is rare and short, it is not pipelined
+  for (int p = 0; p < c->n_planes; ++p)
+    HIPCHK(c, hipMemcpy2D(c->ig_anchor[p], c->ig_hist_pitch[p], anchor_planes[p], anchor_strides[p], (size_t)c->pw[p] * c->esize,
+                          c->ph[p], hipMemcpyHostToDevice));
+  const void* anchor[3] = {c->ig_anchor[0], c->ig_anchor[1], c->ig_anchor[2]};
+  for (int done = 0; done < n_frames;) {
+    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+    const int n = n_frames - done < FB ? n_frames - done : FB;
+    pqa_device_clip f{};
+    for (int p = 0; p < c->n_planes; ++p) {
+      for (int k = 0; k < n; ++k)
+        HIPCHK(c, hipMemcpy2D(c->ig_stage + (size_t)k * c->ig_stage_bytes + c->ig_stage_off[p], c->ig_hist_pitch[p],
+                              frames[(size_t)(done + k) * 3 + p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
+                              hipMemcpyHostToDevice));
+      f.plane[p] = c->ig_stage + c->ig_stage_off[p];
+      f.row_pitch[p] = c->ig_hist_pitch[p];
+      f.frame_pitch[p] = (int64_t)c->ig_stage_bytes;
+    }
+    const int rc = frame_sad_launch(c, anchor, c->ig_hist_pitch, &f, n, out + (size_t)done * 3);
+    if (rc != PQA_OK) return rc;
+    done += n;
+  }
+  return PQA_OK;
+}
+
 int pqa_flush(pqa_ctx* c) {
   if (!c) return PQA_EINVAL;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
@@ -1767,24 +1976,29 @@ int pqa_sync(pqa_ctx* c) {
 }
 
 int pqa_collect(pqa_ctx* c, int64_t first_index, int32_t count, double* records) {
-  return pqa_collect_ext4(c, first_index, count, records, nullptr, nullptr, nullptr, nullptr);
+  return pqa_collect_ext5(c, first_index, count, records, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int pqa_collect_ext(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext) {
-  return pqa_collect_ext4(c, first_index, count, records, ext, nullptr, nullptr, nullptr);
+  return pqa_collect_ext5(c, first_index, count, records, ext, nullptr, nullptr, nullptr, nullptr);
 }
 
 int pqa_collect_ext2(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2) {
-  return pqa_collect_ext4(c, first_index, count, records, ext, ext2, nullptr, nullptr);
+  return pqa_collect_ext5(c, first_index, count, records, ext, ext2, nullptr, nullptr, nullptr);
 }
 
 int pqa_collect_ext3(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
                      double* ext3) {
-  return pqa_collect_ext4(c, first_index, count, records, ext, ext2, ext3, nullptr);
+  return pqa_collect_ext5(c, first_index, count, records, ext, ext2, ext3, nullptr, nullptr);
 }
 
 int pqa_collect_ext4(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
                      double* ext3, double* ext4) {
+  return pqa_collect_ext5(c, first_index, count, records, ext, ext2, ext3, ext4, nullptr);
+}
+
+int pqa_collect_ext5(pqa_ctx* c, int64_t first_index, int32_t count, double* records, double* ext, double* ext2,
+                     double* ext3, double* ext4, double* ext5) {
   if (!c) return PQA_EINVAL;
   if (count < 0 || first_index < 0 || (count > 0 && !records)) return fail(c, PQA_EINVAL, "bad argument");
   if (count > c->capacity) return fail(c, PQA_ESTATE, "count %d exceeds result_capacity %d", count, c->capacity);
@@ -1854,6 +2068,12 @@ int pqa_collect_ext4(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
                           (size_t)n * PQA_EXT4_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
     } else if (ext4) {
       std::fill(ext4 + (size_t)done * PQA_EXT4_DOUBLES, ext4 + (size_t)(done + n) * PQA_EXT4_DOUBLES, __builtin_nan(""));
+    }
+    if (ext5 && c->ext5) {  // and the fifth
+      HIPCHK(c, hipMemcpy(ext5 + (size_t)done * PQA_EXT5_DOUBLES, c->ext5 + (size_t)row * PQA_EXT5_DOUBLES,
+                          (size_t)n * PQA_EXT5_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (ext5) {
+      std::fill(ext5 + (size_t)done * PQA_EXT5_DOUBLES, ext5 + (size_t)(done + n) * PQA_EXT5_DOUBLES, __builtin_nan(""));
     }
     done += n;
     row = 0;
@@ -1996,6 +2216,9 @@ int pqa_reset(pqa_ctx* c) {
   c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
   c->st_armed[0] = c->st_armed[1] = false;
   c->st_hist_idx[0] = c->st_hist_idx[1] = -1;
+  c->ig_armed = false;
+  c->ig_hist_idx = -1;
+  c->started = false;
   c->err.clear();
   return PQA_OK;
 }

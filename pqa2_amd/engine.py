@@ -179,6 +179,63 @@ class FeatureEngine:
         a = np.ascontiguousarray(prev_dis_luma, dtype=self.dtype)
         self._check(self.lib.pqa_set_dis_history(self._ctx, a.ctypes.data, a.strides[0]))
 
+    def _planes(self, planes):
+        """(keep-alive arrays, pointer triple, stride triple) of the first n_planes planes of a frame."""
+        P, S = C.c_void_p * 3, C.c_int64 * 3
+        pp, ss, keep = P(), S(), []
+        for p in range(self.n_planes):
+            a = np.asarray(planes[p])
+            if a.dtype != self.dtype or a.strides[1] != a.itemsize:
+                a = np.ascontiguousarray(a, dtype=self.dtype)
+            keep.append(a)
+            pp[p], ss[p] = a.ctypes.data, a.strides[0]
+        return keep, pp, ss
+
+    def set_dis_history_planes(self, prev_dis_planes):
+        """Every plane of the distorted frame in front of the next submitted frame (frame first-1): the integrity
+        feature's differences continue from it, and so does siti's TI of the distorted clip; None restarts both chains
+        (pqa_set_dis_history_planes)."""
+        if prev_dis_planes is None:
+            self._check(self.lib.pqa_set_dis_history_planes(self._ctx, None, None))
+            return
+        keep, pp, ss = self._planes(prev_dis_planes)
+        self._check(self.lib.pqa_set_dis_history_planes(self._ctx, C.byref(pp), C.byref(ss)))
+
+    def set_black_threshold(self, threshold: int):
+        """The integer sample value at or below which a luma sample counts as black (pqa_set_black_threshold); legal
+        before the first submit and after reset()."""
+        self._check(self.lib.pqa_set_black_threshold(self._ctx, int(threshold)))
+
+    def frame_sad(self, anchor_planes, frames) -> np.ndarray:
+        """[n, 3] uint64: the exact SAD of every plane of each frame in `frames` (sequences of Y[,U,V] numpy planes in
+        host memory) against the anchor frame's (pqa_frame_sad; synchronous, 0 for planes the engine does not have)."""
+        n = len(frames)
+        out = np.zeros((n, 3), np.uint64)
+        if n == 0:
+            return out
+        keep, ap, as_ = self._planes(anchor_planes)
+        ptrs = (C.c_void_p * (3 * n))()
+        strides = None
+        for f, planes in enumerate(frames):   # packed planes: one common row stride per plane
+            k, pp, strides = self._planes([np.ascontiguousarray(planes[p], dtype=self.dtype) for p in range(self.n_planes)])
+            keep += k
+            for p in range(self.n_planes):
+                ptrs[3 * f + p] = pp[p]
+        self._check(self.lib.pqa_frame_sad(self._ctx, C.byref(ap), C.byref(as_), ptrs, C.byref(strides), n, out.ctypes.data))
+        return out
+
+    def frame_sad_resident(self, anchor_ptrs, anchor_row_pitch, frame_ptrs, row_pitch, frame_pitch, n_frames: int) -> np.ndarray:
+        """[n, 3] uint64 like frame_sad() for a clip in HBM (frame_ptrs: device addresses of frame 0's planes) against an
+        anchor frame in HBM; pitches in bytes per plane (pqa_frame_sad_device)."""
+        out = np.zeros((n_frames, 3), np.uint64)
+        P, S = C.c_void_p * 3, C.c_int64 * 3
+        ap, as_, d = P(), S(), N.PqaDeviceClip()
+        for p in range(self.n_planes):
+            ap[p], as_[p] = anchor_ptrs[p], anchor_row_pitch[p]
+            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = frame_ptrs[p], row_pitch[p], frame_pitch[p]
+        self._check(self.lib.pqa_frame_sad_device(self._ctx, C.byref(ap), C.byref(as_), C.byref(d), n_frames, out.ctypes.data))
+        return out
+
     # -- device-resident path ------------------------------------------------------------------
     def submit_resident(self, first_index: int, n_frames: int, ref_ptrs, dis_ptrs, row_pitch, frame_pitch,
                         prev_ref_luma_ptr: int = 0, prev_row_pitch: int = 0):
@@ -294,6 +351,19 @@ class FeatureEngine:
         self._check(self.lib.pqa_collect_ext4(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
                                               ext2.ctypes.data, ext3.ctypes.data, ext4.ctypes.data))
         return out, ext, ext2, ext3, ext4
+
+    def collect_ext5(self, first_index: int, count: int):
+        """(records, ext, ext2, ext3, ext4, ext5 [count, EXT5_DOUBLES]): collect_ext4() plus the fifth extension rows of
+        the same frames (pqa_collect_ext5; integrity slots, NaN where the context does not run it)."""
+        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
+        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
+        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
+        ext3 = np.zeros((count, N.EXT3_DOUBLES), np.float64)
+        ext4 = np.zeros((count, N.EXT4_DOUBLES), np.float64)
+        ext5 = np.zeros((count, N.EXT5_DOUBLES), np.float64)
+        self._check(self.lib.pqa_collect_ext5(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
+                                              ext2.ctypes.data, ext3.ctypes.data, ext4.ctypes.data, ext5.ctypes.data))
+        return out, ext, ext2, ext3, ext4, ext5
 
     def flush(self):
         self._check(self.lib.pqa_flush(self._ctx))

@@ -30,7 +30,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 progress=None, cancelled=None, engine_factory=None, raw_kwargs=None,
                 fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
                 ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False,
-                psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False) -> ScoreResult | None:
+                psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False,
+                integrity: bool = False, integrity_options=None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -45,7 +46,12 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     integer frame rate (fps_num // fps_den) is 32 or more.
     `siti`: FFmpeg's siti filter (ITU-T P.910 SI / TI) of the distorted and of the reference luma on every frame as the
     extra columns siti_si / siti_ti / siti_si_source / siti_ti_source (fourth extension record); a clip whose Y4M header
-    says XCOLORRANGE=FULL is taken as full range, any other as limited range."""
+    says XCOLORRANGE=FULL is taken as full range, any other as limited range.
+    `integrity`: FFmpeg's freezedetect, blackdetect and scdet on the DISTORTED clip (fifth extension record; every plane of
+    a colour clip): the extra columns scd_mafd / scd_score / black_ratio / freeze_mafd and, under the result's `integrity`
+    key, the event lists freezes / blacks / scene_changes (integrity.py); `integrity_options`: FFmpeg's option names
+    (integrity.DEFAULTS).  The black threshold follows the distorted clip's range (XCOLORRANGE=FULL: full range)."""
+    from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
@@ -65,7 +71,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     if psnr_hvs and ri.mono:
         raise ValueError("psnr_hvs needs the chroma planes, but the clips are monochrome")
     mdl = M.load_model(model)
-    side = (psnr or ssim or ciede or psnr_hvs or xpsnr)
+    side = (psnr or ssim or ciede or psnr_hvs or xpsnr or integrity)
     n_planes = 1 if (ri.mono or not side) else 3
     feats = N.FEAT_VMAF | (N.FEAT_PSNR if psnr else 0) | (N.FEAT_SSIM if ssim else 0)
     want_ext = bool(float_ssim or ms_ssim or ciede or cambi)
@@ -79,6 +85,10 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     if siti:
         feats |= N.FEAT_SITI | (N.FEAT_SITI_REF_FULL if ri.color_range == "full" else 0)
         feats |= N.FEAT_SITI_DIS_FULL if di.color_range == "full" else 0
+    if integrity:
+        feats |= N.FEAT_INTEGRITY
+        ig_opts = IG.options(integrity_options)
+        ig_thr = IG.black_threshold(di.bit_depth, di.color_range == "full", ig_opts["pixel_black_th"])
     a, b = shard.shard_bounds(n, world_size, rank)
     t_start = time.perf_counter()
 
@@ -93,7 +103,11 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             eng.set_ref_history([ref_rd.frame(a - 1)[0]] + ([ref_rd.frame(a - 2)[0]] if a >= 2 else []))
         elif a > 0:
             eng.set_motion_halo(ref_rd.frame(a - 1)[0])   # one-frame halo in front of this rank's chunk
-        if a > 0 and siti:    # siti's TI of the distorted clip continues from its frame a-1 (the reference's: the halo)
+        if integrity:
+            eng.set_black_threshold(ig_thr)
+        if a > 0 and integrity:   # the differences continue from every plane of the distorted frame a-1 (siti's TI too)
+            eng.set_dis_history_planes(dis_rd.frame(a - 1)[:n_planes])
+        elif a > 0 and siti:    # siti's TI of the distorted clip continues from its frame a-1 (the reference's: the halo)
             eng.set_dis_history(dis_rd.frame(a - 1)[0])
         # both clips are files of packed planes (.y4m): the library reads them straight into its pinned staging (pqa_submit_fd:
         # one copy, no page faults) instead of copying frames out of the readers' mappings
@@ -123,8 +137,12 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             i += m
             if progress is not None:
                 progress(i - a, b - a)
-        local_ext = local_ext2 = local_ext3 = local_ext4 = None
-        if siti:       # the fourth extension record is read only when siti is on
+        local_ext = local_ext2 = local_ext3 = local_ext4 = local_ext5 = None
+        if integrity:  # the fifth extension record is read only when integrity is on
+            local, local_ext, local_ext2, local_ext3, local_ext4, local_ext5 = eng.collect_ext5(a, b - a) if b > a else (
+                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
+                np.zeros((0, N.EXT3_DOUBLES)), np.zeros((0, N.EXT4_DOUBLES)), np.zeros((0, N.EXT5_DOUBLES)))
+        elif siti:       # the fourth extension record is read only when siti is on
             local, local_ext, local_ext2, local_ext3, local_ext4 = eng.collect_ext4(a, b - a) if b > a else (
                 np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
                 np.zeros((0, N.EXT3_DOUBLES)), np.zeros((0, N.EXT4_DOUBLES)))
@@ -149,8 +167,36 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
     ext3 = shard.gather_records(local_ext3, n, world_size, rank, gather_device, width=N.EXT3_DOUBLES) if xpsnr else None
     ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
+    ext5 = shard.gather_records(local_ext5, n, world_size, rank, gather_device, width=N.EXT5_DOUBLES) if integrity else None
     if rank != 0:
         return None
+    ig_result = None
+    if integrity:
+        # the state machines run here on the gathered rows of the whole clip (a freeze or a scene score that crosses a shard
+        # boundary needs nothing else: every shard was armed with its frame a-1); freezedetect's anchored SADs, asked for
+        # inside a still run only, come from the distorted file through a context of its own, made on first use
+        plane_sizes = [(di.width, di.height)] + ([(di.chroma_w, di.chroma_h)] * 2 if n_planes == 3 else [])
+        sad_eng, cache = [], {}
+
+        def anchored_sad(anchor, i):
+            if (anchor, i) not in cache:
+                if not sad_eng:
+                    sad_eng.append(make(di.width, di.height, bit_depth=di.bit_depth, n_planes=n_planes,
+                                        chroma_shift=(di.hshift, di.vshift), features=N.FEAT_INTEGRITY, device=device,
+                                        max_batch=8, result_capacity=16))
+                cache.clear()
+                hi = min(n, i + 8)    # a still run asks for consecutive frames against one anchor: fetch a few at once
+                got = sad_eng[0].frame_sad(dis_rd.frame(anchor)[:n_planes], [dis_rd.frame(j)[:n_planes] for j in range(i, hi)])
+                for j in range(i, hi):
+                    cache[(anchor, j)] = got[j - i, :n_planes].astype(np.float64)
+            return cache[(anchor, i)]
+        try:
+            ig_result = IG.analyze(ext5[:, N.EXT5_SAD_PREV:N.EXT5_SAD_PREV + n_planes], ext5[:, N.EXT5_BLACK_COUNT],
+                                   width=di.width, height=di.height, plane_sizes=plane_sizes, bit_depth=di.bit_depth,
+                                   fps_num=di.fps_num, fps_den=di.fps_den, opts=ig_opts, anchored_sad=anchored_sad)
+        finally:
+            for e in sad_eng:
+                e.close()
     elapsed = time.perf_counter() - t_start
     extra = {"ext": ext, "float_ssim": bool(float_ssim), "ms_ssim": bool(ms_ssim)} if want_ext else {}
     if ciede:
@@ -165,6 +211,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         extra.update(ext3=ext3, xpsnr=True)
     if siti:
         extra.update(ext4=ext4, siti=True)
+    if integrity:
+        extra.update(integrity=ig_result)
     return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                           fps=n / elapsed if elapsed > 0 else 0.0, **extra)
 
@@ -174,7 +222,7 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
                    ms_ssim: bool = False, ciede: bool = False, cambi: bool = False,
                    cambi_full_ref: bool = False, ext2: np.ndarray | None = None, psnr_hvs: bool = False,
                    ext3: np.ndarray | None = None, xpsnr: bool = False, ext4: np.ndarray | None = None,
-                   siti: bool = False) -> ScoreResult:
+                   siti: bool = False, integrity: dict | None = None) -> ScoreResult:
     """Host epilogue: records -> libvmaf-named metric columns (+ vmaf), stats-file lines.  With `float_ssim` / `ms_ssim`
     / `ciede` the extension records `ext` ([n, EXT_DOUBLES], pqa_collect_ext) add libvmaf's float_ssim / float_ms_ssim /
     ciede2000 columns, with `cambi` / `cambi_full_ref` libvmaf's cambi, cambi_source and cambi_full_reference.  With
@@ -182,7 +230,9 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
     psnr_hvs.  With `xpsnr` the third extension records `ext3` ([n, EXT3_DOUBLES], pqa_collect_ext3) add xpsnr_y / _u /
     _v, FFmpeg's stats-file lines (xpsnr_lines) and its summary (xpsnr_summary, report.xpsnr_summary) of every frame.
     With `siti` the fourth extension records `ext4` ([n, EXT4_DOUBLES], pqa_collect_ext4) add siti_si / siti_ti of the
-    distorted and siti_si_source / siti_ti_source of the reference luma."""
+    distorted and siti_si_source / siti_ti_source of the reference luma.  With `integrity` (the dict integrity.analyze
+    returns for the clip) its four columns are added and the event lists, the anchors and FFmpeg's log lines go into the
+    result (keys integrity, freeze_anchor, integrity_lines)."""
     n = rec.shape[0]
     prefix = "integer_" if mdl.is_integer else ""
     metrics = M.metrics_from_records(rec, info.width, info.height, prefix)
@@ -238,6 +288,12 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
             raise ValueError("siti needs the fourth extension records of every frame")
         for key, slot in SITI_KEYS:
             metrics[key] = ext4[:, slot].copy()
+    if integrity is not None:
+        from . import integrity as IG
+        for key, col in integrity["columns"].items():
+            if np.shape(col) != (n,):
+                raise ValueError("integrity needs the columns of every frame")
+            metrics[key] = np.asarray(col, np.float64).copy()
     scored = M.score_frames(mdl, metrics)
     idx = np.arange(n)
     if n_subsample > 1:
@@ -246,7 +302,9 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         idx = idx[keep]
     return ScoreResult(metrics=scored, frame_indices=idx, records=rec, info=info, fps=fps,
                        psnr_lines=psnr_lines, ssim_lines=ssim_lines, model_name=mdl.name,
-                       **({"xpsnr_lines": xpsnr_lines, "xpsnr_summary": xpsnr_summary} if xpsnr else {}))
+                       **({"xpsnr_lines": xpsnr_lines, "xpsnr_summary": xpsnr_summary} if xpsnr else {}),
+                       **({"integrity": IG.events_json(integrity), "freeze_anchor": np.asarray(integrity["freeze_anchor"]),
+                           "integrity_lines": IG.log_lines(integrity)} if integrity is not None else {}))
 
 
 SITI_KEYS = (("siti_si", N.EXT4_SI), ("siti_ti", N.EXT4_TI), ("siti_si_source", N.EXT4_SI_SOURCE),

@@ -82,6 +82,12 @@ def xpsnr_log_keys(summary: dict | None) -> dict:
     return {k: v for k, v in out.items() if math.isfinite(v)}   # +inf (identical clips) has no JSON spelling: left out
 
 
+def integrity_log_keys(events: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the capture-integrity event lists (freezes / blacks / scene_changes,
+    pipeline.score_files(integrity=True)); none without them."""
+    return {"integrity": events} if events is not None else {}
+
+
 def build_vmaf_log(metrics: dict, fps: float, frame_indices=None, extra_top: dict | None = None) -> dict:
     """dict with libvmaf's JSON schema: version, fps, frames[{frameNum, metrics}], pooled_metrics,
     aggregate_metrics.  Values are rounded to 6 decimals like libvmaf's %.6f writer."""
@@ -109,6 +115,10 @@ def write_vmaf_json(path: str, log: dict) -> None:
         f.write(f'  "version": "{log["version"]}",\n')
         for k, v in log.items():
             if k in ("version", "fps", "frames", "pooled_metrics", "aggregate_metrics"):
+                continue
+            if isinstance(v, (dict, list)):      # structured extras (the integrity event lists): plain JSON
+                import json
+                f.write(f'  "{k}": {json.dumps(v)},\n')
                 continue
             f.write(f'  "{k}": "{v}",\n' if isinstance(v, str) else f'  "{k}": {num(v)},\n')
         f.write(f'  "fps": {log["fps"]:.2f},\n')

@@ -52,6 +52,7 @@ def _die_with_parent(expected: int, getppid=os.getppid, kill=os.kill) -> None:
 def main(argv=None) -> int:
     parent = _expected_parent()    # before anything slow: imports, argument parsing
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only on this pool's driver: RCCL needs it (before torch loads)
+    from .integrity import DEFAULTS as IG_OPTIONS
     ap = argparse.ArgumentParser(prog="pqa2_amd.score")
     ap.add_argument("reference")
     ap.add_argument("distorted")
@@ -77,6 +78,12 @@ def main(argv=None) -> int:
     ap.add_argument("--siti", action="store_true",
                     help="add FFmpeg's siti (ITU-T P.910 SI / TI) of both clips: siti_si / _ti (distorted) and "
                          "siti_si_source / _ti_source (reference), per frame and pooled")
+    ap.add_argument("--integrity", action="store_true",
+                    help="add FFmpeg's freezedetect / blackdetect / scdet on the distorted clip: scd_mafd, scd_score, "
+                         "black_ratio, freeze_mafd per frame and the event lists under the JSON's top-level integrity key")
+    ap.add_argument("--integrity-log", default=None, help="event log in FFmpeg's wording, one line per event (implies --integrity)")
+    for name in IG_OPTIONS:   # FFmpeg's option names and defaults (integrity.DEFAULTS); each implies --integrity
+        ap.add_argument("--" + name.replace("_", "-"), type=float, default=None, help=f"integrity option {name}")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -108,6 +115,8 @@ def main(argv=None) -> int:
             last[0] = now
             print(f"frame= {done * world} fps=0 q=0.0 size=N/A", file=sys.stderr, flush=True)
 
+    ig_opts = {k: getattr(a, k) for k in IG_OPTIONS if getattr(a, k) is not None}
+    want_ig = bool(a.integrity or a.integrity_log or ig_opts)
     try:
         res = score_files(a.reference, a.distorted, a.model, psnr=bool(a.psnr_log), ssim=bool(a.ssim_log),
                           n_subsample=a.n_subsample, device=local_rank, rank=rank, world_size=world,
@@ -117,7 +126,8 @@ def main(argv=None) -> int:
                           **({"cambi_full_ref": True} if a.cambi_full_ref else {}),
                           **({"psnr_hvs": True} if a.psnr_hvs else {}),
                           **({"xpsnr": True} if (a.xpsnr or a.xpsnr_log) else {}),
-                          **({"siti": True} if a.siti else {}))
+                          **({"siti": True} if a.siti else {}),
+                          **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
         return 1
@@ -128,8 +138,12 @@ def main(argv=None) -> int:
                 dist.destroy_process_group()
     if rank == 0:
         log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
-                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary"))})
+                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
+                                     **report.integrity_log_keys(res.get("integrity"))})
         report.write_vmaf_json(a.json, log)
+        if a.integrity_log and res.get("integrity_lines") is not None:
+            with open(a.integrity_log, "w") as f:
+                f.write("".join(line + "\n" for line in res["integrity_lines"]))
         if a.xpsnr_log and res.get("xpsnr_lines") is not None:
             with open(a.xpsnr_log, "w") as f:
                 f.write("\n".join(res["xpsnr_lines"]) + "\n")

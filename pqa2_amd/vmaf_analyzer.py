@@ -156,6 +156,9 @@ class VMAFAnalyzer(QObject):
         self.xpsnr_enabled = False            # FFmpeg xpsnr: <test>_<ts>_xpsnr.txt stats file, xpsnr_y / _u / _v, xpsnr
         self._xpsnr_path = None               # where this analysis writes the xpsnr stats file (set per analysis)
         self.siti_enabled = False             # FFmpeg siti (ITU-T P.910 SI / TI) of both clips, per frame and pooled
+        self.integrity_enabled = False        # FFmpeg freezedetect / blackdetect / scdet on the distorted clip: event lists,
+        self.integrity_options = {}           # <test>_<ts>_integrity.txt; FFmpeg's option names (integrity.DEFAULTS)
+        self._integrity_path = None           # where this analysis writes the event log (set per analysis)
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -181,6 +184,8 @@ class VMAFAnalyzer(QObject):
             self.psnr_hvs_enabled = bool(s.get("psnr_hvs_enabled", False))
             self.xpsnr_enabled = bool(s.get("xpsnr_enabled", False))
             self.siti_enabled = bool(s.get("siti_enabled", False))
+            self.integrity_enabled = bool(s.get("integrity_enabled", False))
+            self.integrity_options = dict(s.get("integrity_options", {}) or {})
             logger.info(f"VMAF options set from manager: threads={self.threads}, "
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
@@ -200,7 +205,7 @@ class VMAFAnalyzer(QObject):
                              feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
                              ms_ssim_enabled=False, ciede_enabled=False, cambi_enabled=False,
                              cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False,
-                             siti_enabled=False):
+                             siti_enabled=False, integrity_enabled=False, integrity_options=None):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -215,6 +220,8 @@ class VMAFAnalyzer(QObject):
         self.psnr_hvs_enabled = bool(psnr_hvs_enabled)
         self.xpsnr_enabled = bool(xpsnr_enabled)
         self.siti_enabled = bool(siti_enabled)
+        self.integrity_enabled = bool(integrity_enabled)
+        self.integrity_options = dict(integrity_options or {})
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -315,6 +322,8 @@ class VMAFAnalyzer(QObject):
                 ssim_path = os.path.join(test_dir, f"{test_name}_{timestamp}_ssim.txt")
                 self._xpsnr_path = (os.path.join(test_dir, f"{test_name}_{timestamp}_xpsnr.txt")
                                     if self.xpsnr_enabled else None)
+                self._integrity_path = (os.path.join(test_dir, f"{test_name}_{timestamp}_integrity.txt")
+                                        if self.integrity_enabled else None)
 
                 self.get_video_metadata(reference_path)
                 dist_meta = self.get_video_metadata(distorted_path)
@@ -386,8 +395,12 @@ class VMAFAnalyzer(QObject):
             return False
         self.last_fps = res["fps"]
         log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
-                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary"))})
+                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
+                                     **report.integrity_log_keys(res.get("integrity"))})
         report.write_vmaf_json(json_path, log)
+        if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
+            with open(self._integrity_path, "w") as f:
+                f.write("".join(line + "\n" for line in res["integrity_lines"]))
         if self.xpsnr_enabled and self._xpsnr_path and res.get("xpsnr_lines") is not None:
             with open(self._xpsnr_path, "w") as f:
                 f.write("\n".join(res["xpsnr_lines"]) + "\n")
@@ -411,7 +424,8 @@ class VMAFAnalyzer(QObject):
                 **({"cambi_full_ref": True} if self.cambi_enabled and self.cambi_full_ref_enabled else {}),
                 **({"psnr_hvs": True} if self.psnr_hvs_enabled else {}),
                 **({"xpsnr": True} if self.xpsnr_enabled else {}),
-                **({"siti": True} if self.siti_enabled else {})}
+                **({"siti": True} if self.siti_enabled else {}),
+                **({"integrity": True, "integrity_options": dict(self.integrity_options)} if self.integrity_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -440,6 +454,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--xpsnr"] + (["--xpsnr-log", self._xpsnr_path] if self._xpsnr_path else [])
         if self.siti_enabled:
             cmd += ["--siti"]
+        if self.integrity_enabled:
+            cmd += ["--integrity"] + (["--integrity-log", self._integrity_path] if self._integrity_path else [])
+            for k, v in self.integrity_options.items():
+                cmd += ["--" + k.replace("_", "-"), str(v)]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -551,6 +569,9 @@ class VMAFAnalyzer(QObject):
                     results[key] = pooled[key]["mean"] if key in pooled else None
                 for key in ("siti_si", "siti_ti"):
                     results[key + "_max"] = pooled[key]["max"] if key in pooled else None
+            if self.integrity_enabled:   # the event lists, from the log's top level
+                results["integrity"] = vmaf_data.get("integrity")
+                results["integrity_log"] = self._integrity_path
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
