@@ -1,4 +1,5 @@
-"""CPU restatement of libvmaf's float_ssim and float_ms_ssim features (numpy, float64).  Test infrastructure next to
+"""CPU restatement of libvmaf's float_ssim and float_ms_ssim features (numpy, float64; dtype=np.float32 restates the
+kernels' arithmetic, see "f32 mode" below).  Test infrastructure next to
 ab_vs_oracle.py: the GPU kernels (pqa2_amd/csrc/ssim_family.hip) are checked against it, and
 tools/compare_libvmaf_log.py compares it with a real libvmaf log.
 
@@ -26,6 +27,14 @@ marked [VERIFY] is unpinned against libvmaf and listed in DESIGN.md section 1):
   float_ms_ssim (a zero mean gives 0).  That is the defined outcome, on the device as here (ms_combine).
 - Minimum sizes: every map non-empty -- ceil-halved 5th scale >= 11 in both directions (w, h >= 161) for MS-SSIM, the
   decimated plane >= 11 for float_ssim.  [VERIFY: libvmaf's own limit]
+
+f32 mode (dtype=np.float32 on lcs_maps, lpf97_decimate, float_ssim, ms_ssim, ext_record; the default float64 path is
+untouched, bit for bit -- tests/test_ssim_localized_ref.py holds it against a frozen copy): every filter and every map
+value stays in f32, and the moments are formed on x - o with o the plane's background value (its median: on a flat frame
+with a small patch that is the flat level, on any frame a value inside the sample range).  That is the kernels'
+per-thread-offset formulation: variance and covariance do not change, and a flat window gives exactly zero moments.  Means
+are accumulated in f64 in both modes.  The f32 mode is no second definition: it measures how far honest f32 arithmetic is
+from f64 (the f32 oracle of tests/fuzz_parity.py's rule).
 """
 from __future__ import annotations
 
@@ -58,7 +67,16 @@ def gaussian_window() -> np.ndarray:
     return np.outer(g, g)
 
 
-def to_float(plane: np.ndarray, bpc: int) -> np.ndarray:
+def _is_f32(dtype) -> bool:
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"dtype must be float32 or float64, not {dt}")
+    return dt == np.dtype(np.float32)
+
+
+def to_float(plane: np.ndarray, bpc: int, dtype=np.float64) -> np.ndarray:
+    if _is_f32(dtype):
+        return np.asarray(plane, np.float32) / np.float32(1 << (bpc - 8))   # exact: integers over a power of two
     return np.asarray(plane, np.float64) / float(1 << (bpc - 8))
 
 
@@ -89,7 +107,7 @@ def filter_valid_2d(img: np.ndarray, win: np.ndarray) -> np.ndarray:
     """Valid-region 2-D correlation through sliding_window_view (row blocks keep the view's working set small)."""
     kh, kw = win.shape
     oh, ow = img.shape[0] - kh + 1, img.shape[1] - kw + 1
-    out = np.empty((oh, ow))
+    out = np.empty((oh, ow), img.dtype)
     step = max(1, (1 << 22) // max(1, ow * kh * kw))
     for y0 in range(0, oh, step):
         y1 = min(oh, y0 + step)
@@ -123,24 +141,59 @@ def box_decimate(img: np.ndarray, f: int) -> np.ndarray:
     xs = _sym_index(w, -a, w - a + f)
     pad = img[np.ix_(ys, xs)]
     ow, oh = -(-w // f), -(-h // f)
-    acc = np.zeros((oh, ow))
+    acc = np.zeros((oh, ow), img.dtype)
     for dy in range(f):
         for dx in range(f):
             acc += pad[dy:dy + oh * f:f, dx:dx + ow * f:f]
-    return acc / (f * f)
+    return acc / img.dtype.type(f * f)      # f32 planes stay f32 (the sums are integers over a power of two: exact)
 
 
-def lpf97_decimate(img: np.ndarray) -> np.ndarray:
+def lpf97_decimate(img: np.ndarray, dtype=np.float64) -> np.ndarray:
+    taps = LPF97
+    if _is_f32(dtype):
+        img, taps = np.asarray(img, np.float32), LPF97.astype(np.float32)
     h, w = img.shape
     pad = img[np.ix_(_sym_index(h, -4, h + 4), _sym_index(w, -4, w + 4))]
-    hz = sum(LPF97[k] * pad[:, k:k + w] for k in range(9))
-    full = sum(LPF97[k] * hz[k:k + h, :] for k in range(9))
+    hz = sum(taps[k] * pad[:, k:k + w] for k in range(9))
+    full = sum(taps[k] * hz[k:k + h, :] for k in range(9))
     return full[::2, ::2]
 
 
 # ---- SSIM maps --------------------------------------------------------------------------------------------------
-def lcs_maps(x: np.ndarray, y: np.ndarray, separable: bool = False):
+def _lcs_maps_f32(x: np.ndarray, y: np.ndarray, separable: bool):
+    """lcs_maps in f32 throughout, moments about the planes' background values (the kernels' per-thread offsets)."""
+    f = np.float32
+    x, y = np.asarray(x, f), np.asarray(y, f)
+    ox, oy = f(np.median(x)), f(np.median(y))
+    if separable:
+        g = gaussian_taps().astype(f)
+        flt = lambda a: filter_valid_sep(a, g)  # noqa: E731
+    else:
+        win = gaussian_window().astype(f)
+        flt = lambda a: filter_valid_2d(a, win)  # noqa: E731
+    dx, dy = x - ox, y - oy
+    mu, mv = flt(dx), flt(dy)
+    sxx = flt(dx * dx) - mu * mu
+    syy = flt(dy * dy) - mv * mv
+    sxy = flt(dx * dy) - mu * mv
+    mx, my = mu + ox, mv + oy
+    sxsy = np.sqrt(np.maximum(sxx, f(0)) * np.maximum(syy, f(0)))
+    l = (f(2) * (mx * my) + f(C1)) / ((mx * mx + my * my) + f(C1))
+    c = (f(2) * sxsy + f(C2)) / ((sxx + syy) + f(C2))
+    s = (sxy + f(C3)) / (sxsy + f(C3))
+    assert l.dtype == c.dtype == s.dtype == f
+    return l, c, s
+
+
+def _mean(a: np.ndarray) -> float:
+    """Mean accumulated in f64 whatever the map's type."""
+    return float(a.mean()) if a.dtype == np.float64 else float(a.mean(dtype=np.float64))
+
+
+def lcs_maps(x: np.ndarray, y: np.ndarray, separable: bool = False, dtype=np.float64):
     """l, c, s maps over the valid region of two float planes."""
+    if _is_f32(dtype):
+        return _lcs_maps_f32(x, y, separable)
     if separable:
         g = gaussian_taps()
         flt = lambda a: filter_valid_sep(a, g)  # noqa: E731
@@ -175,39 +228,39 @@ def ms_combine(lm, cm, sm) -> float:
     return v * _cpow(lm[MS_SCALES - 1], MS_ALPHA[MS_SCALES - 1])
 
 
-def float_ssim(ref: np.ndarray, dis: np.ndarray, bpc: int = 8, separable: bool = False) -> dict:
+def float_ssim(ref: np.ndarray, dis: np.ndarray, bpc: int = 8, separable: bool = False, dtype=np.float64) -> dict:
     h, w = ref.shape
     if not float_ssim_fits(w, h):
         raise ValueError(f"{w}x{h} is too small for float_ssim")
     f = decimation_factor(w, h)
-    x, y = box_decimate(to_float(ref, bpc), f), box_decimate(to_float(dis, bpc), f)
-    l, c, s = lcs_maps(x, y, separable)
-    return {"float_ssim": float(np.mean(l * c * s)), "l": float(l.mean()), "c": float(c.mean()), "s": float(s.mean())}
+    x, y = box_decimate(to_float(ref, bpc, dtype), f), box_decimate(to_float(dis, bpc, dtype), f)
+    l, c, s = lcs_maps(x, y, separable, dtype)
+    return {"float_ssim": _mean(l * c * s), "l": _mean(l), "c": _mean(c), "s": _mean(s)}
 
 
-def ms_ssim(ref: np.ndarray, dis: np.ndarray, bpc: int = 8, separable: bool = False) -> dict:
+def ms_ssim(ref: np.ndarray, dis: np.ndarray, bpc: int = 8, separable: bool = False, dtype=np.float64) -> dict:
     h, w = ref.shape
     if not ms_ssim_fits(w, h):
         raise ValueError(f"{w}x{h} is too small for float_ms_ssim")
-    x, y = to_float(ref, bpc), to_float(dis, bpc)
+    x, y = to_float(ref, bpc, dtype), to_float(dis, bpc, dtype)
     lm, cm, sm = [], [], []
     for j in range(MS_SCALES):
-        l, c, s = lcs_maps(x, y, separable)
-        lm.append(float(l.mean())); cm.append(float(c.mean())); sm.append(float(s.mean()))
+        l, c, s = lcs_maps(x, y, separable, dtype)
+        lm.append(_mean(l)); cm.append(_mean(c)); sm.append(_mean(s))
         if j + 1 < MS_SCALES:
-            x, y = lpf97_decimate(x), lpf97_decimate(y)
+            x, y = lpf97_decimate(x, dtype), lpf97_decimate(y, dtype)
     return {"float_ms_ssim": ms_combine(lm, cm, sm), "l": lm, "c": cm, "s": sm}
 
 
 def ext_record(ref: np.ndarray, dis: np.ndarray, bpc: int = 8, want_float_ssim: bool = True,
-               want_ms_ssim: bool = True, separable: bool = True) -> np.ndarray:
+               want_ms_ssim: bool = True, separable: bool = True, dtype=np.float64) -> np.ndarray:
     """The 24-double extension record the library returns for this pair (PQA_EXT_* layout; NaN where not run)."""
     e = np.full(24, np.nan)
     if want_float_ssim:
-        fs = float_ssim(ref, dis, bpc, separable)
+        fs = float_ssim(ref, dis, bpc, separable, dtype)
         e[0:4] = [fs["float_ssim"], fs["l"], fs["c"], fs["s"]]
     if want_ms_ssim:
-        ms = ms_ssim(ref, dis, bpc, separable)
+        ms = ms_ssim(ref, dis, bpc, separable, dtype)
         e[4] = ms["float_ms_ssim"]
         e[5:10], e[10:15], e[15:20] = ms["l"], ms["c"], ms["s"]
     return e
