@@ -436,6 +436,31 @@ PQA_API int pqa_luma_stats_device(pqa_ctx* ctx, const void* luma, int64_t row_pi
 PQA_API int pqa_luma_stats(pqa_ctx* ctx, const void* const* luma_frames, int64_t row_stride, int32_t n_frames,
                            uint32_t threshold, uint64_t* out);
 
+/* Temporal alignment: the banded cross-frame SSE of two clips, synchronously.
+ *     D[i][c] = sum over luma pixels of (ref_i - dis_{i+k})^2,  k = k_lo + c,  0 <= i < n_ref,  0 <= c <= k_hi - k_lo
+ *     D[i][c] = UINT64_MAX where i + k is outside [0, n_dis)
+ * Exact uint64 sums; k > 0 means the capture is late (captured frame i + k shows reference frame i).  out (host) is
+ * [n_ref][k_hi - k_lo + 1].  Any context: its width, height and bit depth (8, 10, 12) are used, no feature bit is needed,
+ * device buffers are allocated on first use.  Independent of the scoring chain: a call between two pqa_submit calls changes
+ * no record.  PQA_EINVAL on a null pointer, a negative frame count, k_lo > k_hi, a span above 129 or |k| > 64 (checked
+ * before any device call); n_ref == 0 succeeds and writes nothing.  8-bit clips run on the i8 matrix cores, deeper ones (and
+ * 8-bit ones with PQA_XSSE_MFMA=0 in the environment at pqa_create) on plain integer VALU code: the same integers.
+ * pqa2_amd/align.py turns D into an offset and a frame map; definition, tiling and overflow rule: DESIGN.md section 5.
+ *
+ * pqa_cross_sse_device: both clips in device memory (frame f at luma + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+PQA_API int pqa_cross_sse_device(pqa_ctx* ctx, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch,
+                                 int32_t n_ref, const void* dis_luma, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                 int32_t n_dis, int32_t k_lo, int32_t k_hi, uint64_t* out);
+
+/* The same for frames in HOST memory: ref_frames[i] / dis_frames[j] point at luma planes (rows *_row_stride bytes apart; the
+ * frames need not be contiguous, as for pqa_luma_stats).  Frames go through the pinned staging of pqa_luma_stats, and the
+ * band is walked one 32-frame reference tile at a time over a device window of 31 + span captured frames, so every frame
+ * is uploaded once, whatever the span. */
+PQA_API int pqa_cross_sse(pqa_ctx* ctx, const void* const* ref_frames, int64_t ref_row_stride, int32_t n_ref,
+                          const void* const* dis_frames, int64_t dis_row_stride, int32_t n_dis, int32_t k_lo, int32_t k_hi,
+                          uint64_t* out);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to

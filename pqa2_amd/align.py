@@ -1,0 +1,214 @@
+"""Temporal alignment on the host: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
+constant frame offset and a per-frame map with repeated and dropped frames.
+
+    D[i][c] = sum over luma pixels of (ref_i - dis_{i+k})^2,  k = k_lo + c;  UINT64_MAX where i + k is no captured frame
+
+Sign convention: k > 0 means the capture is late -- captured frame i + k shows reference frame i.  Everything here is
+Python-int / int64 arithmetic on exact integers, so a result does not depend on the machine, the rank or the run.
+
+This replaces the reference's hand-tuned `frame_offset` spin box (app/bookend_alignment.py) and the "SSIM" / "Combined"
+alignment methods its options tab offers and nothing implements."""
+from __future__ import annotations
+
+import numpy as np
+
+SENTINEL = (1 << 64) - 1
+# What one repeated or dropped frame costs in frame_map, as a mean squared error at 8 bit (scaled by 4^(bit_depth - 8)):
+# leaving the straight path must pay for itself by more than an MSE of 25 (a PSNR of about 34 dB) on one frame.  A real
+# repeat or drop saves the whole difference between two different pictures on EVERY later frame, orders of magnitude more
+# on moving content; noise between two captures of the same picture stays well below.  An option value, not a constant of
+# the method.
+DEFAULT_PENALTY_MSE = 25.0
+
+
+def _key(k: int):
+    """the tie order of offsets: the smaller |k| first, then the negative one"""
+    return (abs(k), k)
+
+
+def _band(D, k_lo):
+    D = np.asarray(D)
+    if D.ndim != 2 or D.shape[1] < 1:
+        raise ValueError("D must be [n_ref, span]")
+    span = D.shape[1]
+    if k_lo is None:
+        if span % 2 == 0:
+            raise ValueError("k_lo is needed for a band with an even number of offsets")
+        k_lo = -(span // 2)
+    return D, int(k_lo), span
+
+
+def best_offset(D, n_pixels: int, min_overlap: int | None = None, *, k_lo: int | None = None, n_dis: int | None = None):
+    """(k, mse_at_k, confidence) of the constant offset with the smallest mean of D over its valid rows.
+
+    D is [n_ref, span] (k_lo defaults to the symmetric band -(span // 2)).  Only offsets with at least `min_overlap` valid
+    rows compete; the default is half of the shorter clip (n_dis defaults to the number of captured frames D can see).
+    Ties go to the smaller |k|, then to the negative k.  The means are compared as exact fractions.  `confidence` is the
+    second-smallest mean divided by the smallest (inf at a smallest of 0, or when one offset qualifies and it is 0; 1.0
+    when one offset qualifies and it is not).  ValueError when no offset qualifies."""
+    D, k_lo, span = _band(D, k_lo)
+    n_ref = D.shape[0]
+    valid = D != np.uint64(SENTINEL)
+    if n_dis is None:   # the captured frames the band shows to exist
+        rows, cols = np.nonzero(valid)
+        n_dis = int((rows + cols).max()) + k_lo + 1 if len(rows) else 0
+    if min_overlap is None:
+        min_overlap = max(1, min(n_ref, n_dis) // 2)
+    cands = []
+    for c in range(span):
+        rows = np.flatnonzero(valid[:, c])
+        if len(rows) < max(1, int(min_overlap)):
+            continue
+        total = sum(int(v) for v in D[rows, c])
+        cands.append((total, len(rows), k_lo + c))
+    if not cands:
+        raise ValueError(f"no offset in {k_lo} ... {k_lo + span - 1} has {min_overlap} overlapping frames")
+
+    def less(a, b):   # mean a < mean b, exactly; ties by the offset's key
+        la, lb = a[0] * b[1], b[0] * a[1]
+        return la < lb or (la == lb and _key(a[2]) < _key(b[2]))
+    best = cands[0]
+    for cnd in cands[1:]:
+        if less(cnd, best):
+            best = cnd
+    rest = [cnd for cnd in cands if cnd is not best]
+    mse = best[0] / (best[1] * float(n_pixels))
+    if best[0] == 0:
+        conf = float("inf")
+    elif not rest:
+        conf = 1.0
+    else:
+        second = rest[0]
+        for cnd in rest[1:]:
+            if less(cnd, second):
+                second = cnd
+        conf = (second[0] * best[1]) / (second[1] * best[0])
+    return best[2], mse, conf
+
+
+def default_penalty(n_pixels: int, bit_depth: int = 8, penalty_mse: float | None = None) -> int:
+    """the integer cost of one repeated or dropped frame: penalty_mse * n_pixels, rounded once"""
+    if penalty_mse is None:
+        penalty_mse = DEFAULT_PENALTY_MSE * 4.0 ** (int(bit_depth) - 8)
+    return int(round(float(penalty_mse) * int(n_pixels)))
+
+
+def frame_map(D, n_dis: int, penalty_mse: float | None = None, n_pixels: int = 1, *, k_lo: int | None = None,
+              bit_depth: int = 8, first: int = 0, last: int | None = None):
+    """The cheapest path of offsets k_j over the captured frames j = first ... last - 1 (default: all n_dis of them).
+
+    State k_j costs D[j - k_j][k_j - k_lo] (the reference frame j - k_j must exist).  Steps: k_j = k_{j-1} (both clips
+    advance, free), k_j = k_{j-1} + 1 (the capture repeats a frame: the reference index stays), k_j = k_{j-1} - d (d
+    reference frames were dropped); a step costs P = round(penalty_mse * n_pixels) per repeated or dropped frame.
+    `penalty_mse` defaults to DEFAULT_PENALTY_MSE * 4^(bit_depth - 8).  All sums are Python ints.
+
+    Tie rule: among paths of equal total cost the one whose offsets, read from the LAST captured frame backwards, come
+    first in the order (smaller |k|, then negative k) wins.
+
+    Returns (ref_index, repeated, dropped): ref_index[j - first] is the reference frame captured frame j shows, `repeated`
+    the captured frame numbers that repeat their predecessor, `dropped` the reference frame numbers no captured frame
+    shows because the path jumped over them.  ValueError when a captured frame has no valid state."""
+    D, k_lo, span = _band(D, k_lo)
+    n_ref = D.shape[0]
+    last = int(n_dis) if last is None else int(last)
+    first = int(first)
+    if not (0 <= first <= last <= n_dis):
+        raise ValueError("bad captured frame range")
+    P = default_penalty(n_pixels, bit_depth, penalty_mse)
+    ks = list(range(k_lo, k_lo + span))
+
+    def cost(j, k):
+        i = j - k
+        if i < 0 or i >= n_ref:
+            return None
+        v = int(D[i, k - k_lo])
+        return None if v == SENTINEL else v
+    V, back = [], []   # V[t][s]: cheapest path to state s at frame first + t (None: unreachable)
+    for t, j in enumerate(range(first, last)):
+        row, brow = [None] * span, [None] * span
+        for s, k in enumerate(ks):
+            cj = cost(j, k)
+            if cj is None:
+                continue
+            if t == 0:
+                row[s] = cj
+                continue
+            best = None
+            for sp, kp in enumerate(ks):
+                vp = V[t - 1][sp]
+                if vp is None:
+                    continue
+                if k == kp:
+                    step = 0
+                elif k == kp + 1:
+                    step = P
+                elif k < kp:
+                    step = (kp - k) * P
+                else:
+                    continue
+                cand = (vp + step, _key(kp), sp)
+                if best is None or cand[:2] < best[:2]:
+                    best = cand
+            if best is not None:
+                row[s] = best[0] + cj
+                brow[s] = best[2]
+        if all(v is None for v in row):
+            raise ValueError(f"captured frame {j} has no valid state in the band {k_lo} ... {k_lo + span - 1}")
+        V.append(row)
+        back.append(brow)
+    if not V:
+        return [], [], []
+    s = min((s for s in range(span) if V[-1][s] is not None), key=lambda s: (V[-1][s], _key(ks[s])))
+    path = [0] * len(V)
+    for t in range(len(V) - 1, -1, -1):
+        path[t] = ks[s]
+        if t > 0:
+            s = back[t][s]
+    ref_index = [first + t - k for t, k in enumerate(path)]
+    repeated, dropped = [], []
+    for t in range(1, len(path)):
+        if path[t] == path[t - 1] + 1:
+            repeated.append(first + t)
+        elif path[t] < path[t - 1]:
+            dropped.extend(range(ref_index[t - 1] + 1, ref_index[t]))
+    return ref_index, repeated, dropped
+
+
+def path_cost(D, ks_path, n_pixels: int = 1, penalty_mse: float | None = None, *, k_lo: int | None = None,
+              bit_depth: int = 8, first: int = 0):
+    """The total cost frame_map assigns to the offsets `ks_path` of captured frames first ..., or None when the path is not
+    legal (a state without a reference frame, a step that is not allowed).  What frame_map minimises, stated once more."""
+    D, k_lo, span = _band(D, k_lo)
+    P = default_penalty(n_pixels, bit_depth, penalty_mse)
+    total = 0
+    for t, k in enumerate(ks_path):
+        i = first + t - k
+        if not (k_lo <= k < k_lo + span) or i < 0 or i >= D.shape[0] or int(D[i, k - k_lo]) == SENTINEL:
+            return None
+        total += int(D[i, k - k_lo])
+        if t > 0:
+            kp = ks_path[t - 1]
+            if k == kp + 1:
+                total += P
+            elif k < kp:
+                total += (kp - k) * P
+            elif k != kp:
+                return None
+    return total
+
+
+def align(D, n_ref: int, n_dis: int, n_pixels: int, *, k_lo: int, fps: float = 0.0, bit_depth: int = 8,
+          penalty_mse: float | None = None, min_overlap: int | None = None) -> dict:
+    """best_offset and frame_map of one matrix as the `alignment` object of a result: {offset_frames, offset_seconds, mse,
+    confidence, repeated, dropped, searched}.  The frame map runs over the captured frames that have a reference frame
+    under the offset found, widened by nothing: frames in front of the reference's first picture are the offset itself."""
+    D, k_lo, span = _band(D, k_lo)
+    k, mse, conf = best_offset(D, n_pixels, min_overlap, k_lo=k_lo, n_dis=n_dis)
+    j0, j1 = max(0, k), min(n_dis, D.shape[0] + k)
+    try:
+        _, repeated, dropped = frame_map(D, n_dis, penalty_mse, n_pixels, k_lo=k_lo, bit_depth=bit_depth, first=j0, last=j1)
+    except ValueError:
+        repeated, dropped = [], []
+    return {"offset_frames": int(k), "offset_seconds": (k / fps if fps else 0.0), "mse": float(mse),
+            "confidence": float(conf), "repeated": [int(j) for j in repeated], "dropped": [int(i) for i in dropped],
+            "searched": [int(k_lo), int(k_lo + span - 1)]}

@@ -373,5 +373,30 @@ hipError_t launch_integrity(hipStream_t stream, Elem elem, const PlaneRun cur[3]
                             bool anchor, unsigned black_threshold, unsigned long long* partials, double* ext5,
                             int ext_stride, int slot_base, int capacity, unsigned long long* out);
 
+// ---- temporal alignment: banded cross-frame SSE (cross_sse.hip) ----------------------------------------------------------
+// D[i][c] = sum over luma pixels of (ref_i - dis_{i + k_lo + c})^2, exact uint64; UINT64_MAX where i + k_lo + c is outside
+// [0, dis.n).  Frame f of a clip lives at base + (f % ring) * frame_pitch (a clip that lies whole in memory: ring >= n).
+struct XsseClip {
+  const void* base;
+  int64_t row_pitch, frame_pitch;   // elements
+  int ring;                         // frames the buffer holds
+  int64_t n;                        // frames of the clip
+};
+constexpr int kXsseSegsPerWave = 64;   // 128-pixel row segments per wave: 8192 pixels in an i32 accumulator (limit 131071)
+constexpr int kXsseNormBlocks = 16;    // workgroups per frame of the sum of centred squares
+constexpr int kXsseValuBlocks = 64;    // row groups per (frame, offset) of the VALU path
+int xsse_dis_tiles(int span);          // captured 32-frame tiles one reference tile meets
+int xsse_blocks(int w, int h);         // workgroups per tile pair of the MFMA path
+size_t xsse_part_bytes(bool mfma, int w, int h, int span, int n_tiles);   // workspace of one launch over n_tiles reference tiles
+// 8-bit only: norm_part[(first + f) * kXsseNormBlocks + b], f < count = partial sums of (x - 128)^2 of frames first ...
+hipError_t launch_xsse_norms(hipStream_t stream, const XsseClip& clip, int64_t first, int count, int w, int h,
+                             unsigned long long* norm_part);
+// Rows 32 tile0 ... 32 (tile0 + n_tiles) - 1 (those below ref.n) of out[ref.n][span].  mfma: 8-bit samples on
+// v_mfma_i32_32x32x32_i8, needs the norm partials of every frame it touches (indexed by clip frame number); otherwise plain
+// VALU integers (u8 / u16), norm_ref / norm_dis unused.  Both write the same integers.
+hipError_t launch_cross_sse(hipStream_t stream, Elem elem, bool mfma, const XsseClip& ref, const XsseClip& dis, int w, int h,
+                            int k_lo, int span, int tile0, int n_tiles, void* part, const unsigned long long* norm_ref,
+                            const unsigned long long* norm_dis, unsigned long long* out);
+
 }  // namespace pqa
 

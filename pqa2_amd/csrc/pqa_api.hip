@@ -181,6 +181,10 @@ struct pqa_ctx {
   int LB = 0;
   bool luma_ready = false;
   uint32_t luma_gray = PQA_GRAY_LUMA;
+  // temporal alignment (pqa_cross_sse / pqa_cross_sse_device; cross_sse.hip): grow-only buffers, allocated on first use
+  bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
+  void* xs_buf[6] = {};              // XS_* below
+  size_t xs_cap[6] = {};             // their sizes in bytes
   // motion continuity
   uint8_t* last_luma = nullptr;
   int64_t last_luma_pitch = 0;  // bytes
@@ -1272,6 +1276,8 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->adm_mode = (am && am[0] == '0') ? ADM_TILED : (ap && ap[0] == '0') ? ADM_MARCH : ADM_AUTO;
     const char* mm = getenv("PQA_MOTION_MARCH");  // 0: the LDS-tiled motion kernel (test partner of the march kernel)
     c->motion_mode = (mm && mm[0] == '0') ? MOTION_TILED : MOTION_AUTO;
+    const char* xm = getenv("PQA_XSSE_MFMA");  // 0: the plain-VALU cross-SSE kernel for 8-bit clips too (test partner of the MFMA kernel)
+    c->xsse_mfma = !(xm && xm[0] == '0');
   }
   for (int i = 0; i < 2; ++i) {
     CREATE_HIP(hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
@@ -1518,6 +1524,8 @@ void pqa_destroy(pqa_ctx* c) {
     if (c->luma_dev[i]) hipFree(c->luma_dev[i]);
     if (c->luma_copied[i]) hipEventDestroy(c->luma_copied[i]);
   }
+  for (void* b : c->xs_buf)
+    if (b) hipFree(b);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   for (int i = 0; i < 2; ++i) {
     if (c->aux[i]) hipStreamDestroy(c->aux[i]);
@@ -2109,17 +2117,11 @@ int pqa_luma_stats_device(pqa_ctx* c, const void* luma, int64_t row_pitch, int64
   return PQA_OK;
 }
 
-int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_stride, int32_t n_frames, uint32_t threshold,
-                   uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (n_frames < 0 || (n_frames > 0 && (!luma_frames || !out))) return fail(c, PQA_EINVAL, "bad argument");
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  if (n_frames > 0 && (size_t)row_stride < row_bytes) return fail(c, PQA_EINVAL, "stride smaller than a row");
-  for (int f = 0; f < n_frames; ++f)   // before anything is queued
-    if (!luma_frames[f]) return fail(c, PQA_EINVAL, "frame %d pointer is null", f);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
+namespace {
+// the two pinned + two device halves of LB luma planes that pqa_luma_stats and pqa_cross_sse pack host frames into
+int luma_staging_ensure(pqa_ctx* c) {
   const int h = c->ph[0];
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
   if (!c->luma_ready) {  // lazily: most contexts never detect bookends
     c->luma_pitch = round_up((int64_t)row_bytes, 64);
     c->LB = c->B < 8 ? c->B : 8;
@@ -2141,6 +2143,25 @@ int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_strid
       return fail(c, e == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "luma staging allocation failed: %s", hipGetErrorString(e));
     }
     c->luma_ready = true;
+  }
+  return PQA_OK;
+}
+}  // namespace
+
+int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_stride, int32_t n_frames, uint32_t threshold,
+                   uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (n_frames < 0 || (n_frames > 0 && (!luma_frames || !out))) return fail(c, PQA_EINVAL, "bad argument");
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  if (n_frames > 0 && (size_t)row_stride < row_bytes) return fail(c, PQA_EINVAL, "stride smaller than a row");
+  for (int f = 0; f < n_frames; ++f)   // before anything is queued
+    if (!luma_frames[f]) return fail(c, PQA_EINVAL, "frame %d pointer is null", f);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int h = c->ph[0];
+  {
+    const int rc = luma_staging_ensure(c);
+    if (rc != PQA_OK) return rc;
   }
   const size_t frame_bytes = (size_t)c->luma_pitch * h;
   const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
@@ -2184,6 +2205,168 @@ int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_strid
     done += group;
   }
   return rc;
+}
+
+namespace {
+enum { XS_PART = 0, XS_NORM_REF, XS_NORM_DIS, XS_OUT, XS_REF, XS_DIS };
+
+// a grow-only device buffer of the cross-SSE calls
+int xs_reserve(pqa_ctx* c, int which, size_t bytes) {
+  if (bytes == 0) bytes = 1;
+  if (c->xs_cap[which] >= bytes) return PQA_OK;
+  if (c->xs_buf[which]) {
+    HIPCHK(c, hipFree(c->xs_buf[which]));
+    c->xs_buf[which] = nullptr;
+    c->xs_cap[which] = 0;
+  }
+  HIPCHK(c, hipMalloc(&c->xs_buf[which], bytes));
+  c->xs_cap[which] = bytes;
+  return PQA_OK;
+}
+
+// the argument rules the two entries share; no device call
+int xs_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_ref, int32_t n_dis, int32_t k_lo, int32_t k_hi,
+             const uint64_t* out) {
+  if (!ref || !dis) return fail(c, PQA_EINVAL, "cross_sse: null clip pointer");
+  if (n_ref < 0 || n_dis < 0) return fail(c, PQA_EINVAL, "cross_sse: negative frame count");
+  if (k_lo > k_hi) return fail(c, PQA_EINVAL, "cross_sse: k_lo %d > k_hi %d", k_lo, k_hi);
+  if (k_lo < -64 || k_hi > 64) return fail(c, PQA_EINVAL, "cross_sse: offsets %d ... %d outside -64 ... 64", k_lo, k_hi);
+  if ((int64_t)k_hi - k_lo + 1 > 129) return fail(c, PQA_EINVAL, "cross_sse: span above 129");
+  if (!out) return fail(c, PQA_EINVAL, "cross_sse: null output pointer");
+  if (!c) return PQA_EINVAL;
+  return PQA_OK;
+}
+
+constexpr int kXsTilesPerLaunch = 8;   // reference tiles (of 32 frames) per launch of the device-resident entry
+
+int xs_prepare(pqa_ctx* c, bool mfma, int span, int n_tiles, int32_t n_ref, int32_t n_dis) {
+  int rc = xs_reserve(c, XS_PART, xsse_part_bytes(mfma, c->pw[0], c->ph[0], span, n_tiles));
+  if (rc == PQA_OK) rc = xs_reserve(c, XS_OUT, (size_t)n_ref * span * sizeof(uint64_t));
+  if (rc == PQA_OK && mfma) rc = xs_reserve(c, XS_NORM_REF, (size_t)n_ref * kXsseNormBlocks * sizeof(uint64_t));
+  if (rc == PQA_OK && mfma) rc = xs_reserve(c, XS_NORM_DIS, (size_t)n_dis * kXsseNormBlocks * sizeof(uint64_t));
+  return rc;
+}
+}  // namespace
+
+int pqa_cross_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, int32_t n_ref,
+                         const void* dis_luma, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_dis, int32_t k_lo,
+                         int32_t k_hi, uint64_t* out) {
+  const int chk = xs_check(c, ref_luma, dis_luma, n_ref, n_dis, k_lo, k_hi, out);
+  if (chk != PQA_OK) return chk;
+  const int es = c->esize;
+  const int64_t row_bytes = (int64_t)c->pw[0] * es;
+  if (ref_row_pitch % es || ref_frame_pitch % es || dis_row_pitch % es || dis_frame_pitch % es)
+    return fail(c, PQA_EINVAL, "cross_sse: pitch is not a multiple of the sample size");
+  if (ref_row_pitch < row_bytes || dis_row_pitch < row_bytes) return fail(c, PQA_EINVAL, "cross_sse: pitch smaller than a row");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_ref == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int span = k_hi - k_lo + 1;
+  const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
+  const int n_tiles = (n_ref + 31) / 32;
+  const int per_launch = n_tiles < kXsTilesPerLaunch ? n_tiles : kXsTilesPerLaunch;
+  const int rc = xs_prepare(c, mfma, span, per_launch, n_ref, n_dis);
+  if (rc != PQA_OK) return rc;
+  const XsseClip ref{ref_luma, ref_row_pitch / es, ref_frame_pitch / es, INT32_MAX, n_ref};
+  const XsseClip dis{dis_luma, dis_row_pitch / es, dis_frame_pitch / es, INT32_MAX, n_dis};
+  auto* nr = (unsigned long long*)c->xs_buf[XS_NORM_REF];
+  auto* nd = (unsigned long long*)c->xs_buf[XS_NORM_DIS];
+  if (mfma) {
+    HIPCHK(c, launch_xsse_norms(c->stream, ref, 0, n_ref, c->pw[0], c->ph[0], nr));
+    HIPCHK(c, launch_xsse_norms(c->stream, dis, 0, n_dis, c->pw[0], c->ph[0], nd));
+  }
+  for (int t0 = 0; t0 < n_tiles; t0 += per_launch) {
+    const int nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
+    HIPCHK(c, launch_cross_sse(c->stream, c->elem, mfma, ref, dis, c->pw[0], c->ph[0], k_lo, span, t0, nt, c->xs_buf[XS_PART], nr,
+                               nd, (unsigned long long*)c->xs_buf[XS_OUT]));
+  }
+  HIPCHK(c, hipMemcpyAsync(out, c->xs_buf[XS_OUT], (size_t)n_ref * span * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PQA_OK;
+}
+
+int pqa_cross_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, int32_t n_ref,
+                  const void* const* dis_frames, int64_t dis_row_stride, int32_t n_dis, int32_t k_lo, int32_t k_hi,
+                  uint64_t* out) {
+  const int chk = xs_check(c, ref_frames, dis_frames, n_ref, n_dis, k_lo, k_hi, out);
+  if (chk != PQA_OK) return chk;
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  if ((n_ref > 0 && (size_t)ref_row_stride < row_bytes) || (n_dis > 0 && (size_t)dis_row_stride < row_bytes))
+    return fail(c, PQA_EINVAL, "cross_sse: stride smaller than a row");
+  for (int f = 0; f < n_ref; ++f)   // before anything is queued
+    if (!ref_frames[f]) return fail(c, PQA_EINVAL, "cross_sse: reference frame %d pointer is null", f);
+  for (int f = 0; f < n_dis; ++f)
+    if (!dis_frames[f]) return fail(c, PQA_EINVAL, "cross_sse: captured frame %d pointer is null", f);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_ref == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = luma_staging_ensure(c);
+  if (rc != PQA_OK) return rc;
+  const int span = k_hi - k_lo + 1, h = c->ph[0], es = c->esize;
+  const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
+  rc = xs_prepare(c, mfma, span, 1, n_ref, n_dis);
+  const size_t frame_bytes = (size_t)c->luma_pitch * h;
+  const int dis_ring = 31 + span;   // the captured frames one reference tile meets
+  if (rc == PQA_OK) rc = xs_reserve(c, XS_REF, frame_bytes * 32);
+  if (rc == PQA_OK) rc = xs_reserve(c, XS_DIS, frame_bytes * dis_ring);
+  if (rc != PQA_OK) return rc;
+  const XsseClip ref{c->xs_buf[XS_REF], c->luma_pitch / es, (int64_t)(frame_bytes / es), 32, n_ref};
+  const XsseClip dis{c->xs_buf[XS_DIS], c->luma_pitch / es, (int64_t)(frame_bytes / es), dis_ring, n_dis};
+  auto* nr = (unsigned long long*)c->xs_buf[XS_NORM_REF];
+  auto* nd = (unsigned long long*)c->xs_buf[XS_NORM_DIS];
+  // Every frame crosses PCIe once: reference tile b replaces tile b - 1 in its 32 slots, and the captured window only ever
+  // moves forward, so a tile uploads the captured frames between the previous window's end and its own.  Frames travel in
+  // chunks of LB through the two pinned halves, as in pqa_luma_stats; the stream orders a tile's uploads before its kernels
+  // and those before the next tile's uploads into the same slots.
+  int chunk = 0;
+  auto upload = [&](const void* const* frames, int64_t stride, const XsseClip& clip, int64_t first, int64_t last,
+                    unsigned long long* norms) -> hipError_t {   // frames first ... last - 1 into their ring slots
+    for (int64_t f0 = first; f0 < last; ++chunk) {
+      if (c->cancelled.load()) return hipErrorUnknown;
+      const int n = (int)(last - f0 < c->LB ? last - f0 : c->LB);
+      const int hf = chunk & 1;
+      hipError_t e = chunk >= 2 ? hipEventSynchronize(c->luma_copied[hf]) : hipSuccess;
+      for (int f = 0; f < n && e == hipSuccess; ++f) {
+        uint8_t* pin = c->luma_pinned[hf] + (size_t)f * frame_bytes;
+        copy_plane_rows(pin, c->luma_pitch, (const uint8_t*)frames[f0 + f], stride, row_bytes, h);
+        e = hipMemcpyAsync((uint8_t*)clip.base + (size_t)((f0 + f) % clip.ring) * frame_bytes, pin, frame_bytes,
+                           hipMemcpyHostToDevice, c->stream);
+      }
+      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
+      if (e != hipSuccess) return e;
+      if (mfma) {   // the frames of a chunk lie in consecutive slots unless the ring wraps inside it: one launch per frame run
+        for (int f = 0; f < n && e == hipSuccess; ++f) e = launch_xsse_norms(c->stream, clip, f0 + f, 1, c->pw[0], h, norms);
+        if (e != hipSuccess) return e;
+      }
+      f0 += n;
+    }
+    return hipSuccess;
+  };
+  hipError_t e = hipSuccess;
+  int64_t dis_done = 0;   // captured frames below it have been uploaded (or skipped: no reference tile meets them)
+  const int n_tiles = (n_ref + 31) / 32;
+  for (int t = 0; t < n_tiles && e == hipSuccess; ++t) {
+    const int64_t r0 = (int64_t)t * 32, r1 = r0 + 32 < n_ref ? r0 + 32 : n_ref;
+    int64_t d0 = r0 + k_lo, d1 = r0 + 31 + k_hi + 1;
+    d0 = d0 < dis_done ? dis_done : d0;
+    d1 = d1 > n_dis ? n_dis : d1;
+    e = upload(ref_frames, ref_row_stride, ref, r0, r1, nr);
+    if (e == hipSuccess && d0 < d1) {
+      e = upload(dis_frames, dis_row_stride, dis, d0, d1, nd);
+      dis_done = d1;
+    }
+    if (e == hipSuccess)
+      e = launch_cross_sse(c->stream, c->elem, mfma, ref, dis, c->pw[0], h, k_lo, span, t, 1, c->xs_buf[XS_PART], nr, nd,
+                           (unsigned long long*)c->xs_buf[XS_OUT]);
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(out, c->xs_buf[XS_OUT], (size_t)n_ref * span * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+  // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
+  const hipError_t es2 = hipStreamSynchronize(c->stream);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "cross_sse failed: %s", hipGetErrorString(e));
+  if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
+  return PQA_OK;
 }
 
 int pqa_set_luma_gray(pqa_ctx* c, uint32_t mode) {

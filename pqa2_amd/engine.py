@@ -305,6 +305,41 @@ class FeatureEngine:
         self._check(self.lib.pqa_luma_stats(self._ctx, ptrs, stride, n, int(threshold), out.ctypes.data))
         return out
 
+    # -- temporal alignment ------------------------------------------------------------------
+    def _luma_list(self, frames, what: str):
+        """(arrays kept alive, ctypes pointer array, common row stride) of luma planes in host memory"""
+        arrs = [np.asarray(f) for f in frames]
+        strides = {a.strides[0] for a in arrs if a.ndim == 2}
+        if any(a.ndim != 2 or a.dtype != self.dtype or a.strides[1] != a.itemsize for a in arrs) or len(strides) > 1:
+            arrs = [np.ascontiguousarray(a, dtype=self.dtype) for a in arrs]
+        ptrs = (C.c_void_p * max(len(arrs), 1))()
+        for i, a in enumerate(arrs):
+            if a.shape != (self.height, self.width):
+                raise ValueError(f"{what} frame {i} is {a.shape}, engine is {(self.height, self.width)}")
+            ptrs[i] = a.ctypes.data
+        return arrs, ptrs, (arrs[0].strides[0] if arrs else self.width * np.dtype(self.dtype).itemsize)
+
+    def cross_sse(self, ref_lumas, dis_lumas, k_lo: int, k_hi: int) -> np.ndarray:
+        """[n_ref, k_hi - k_lo + 1] uint64: D[i][c] = sum (ref_i - dis_{i + k_lo + c})^2 over the luma plane, exact;
+        UINT64_MAX where i + k_lo + c is no captured frame (pqa_cross_sse).  Luma planes in HOST memory (lists of 2-D
+        arrays); every frame is uploaded once.  align.best_offset / align.frame_map read the result."""
+        n_ref, n_dis = len(ref_lumas), len(dis_lumas)
+        out = np.zeros((n_ref, max(int(k_hi) - int(k_lo) + 1, 1)), np.uint64)
+        keep_r, rp, rs = self._luma_list(ref_lumas, "reference")
+        keep_d, dp, ds = self._luma_list(dis_lumas, "captured")
+        self._check(self.lib.pqa_cross_sse(self._ctx, rp, rs, n_ref, dp, ds, n_dis, int(k_lo), int(k_hi), out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def cross_sse_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, n_ref: int, dis_ptr: int,
+                           dis_row_pitch: int, dis_frame_pitch: int, n_dis: int, k_lo: int, k_hi: int) -> np.ndarray:
+        """The same for two clips in HBM (device pointers, pitches in bytes; pqa_cross_sse_device)."""
+        out = np.zeros((n_ref, max(int(k_hi) - int(k_lo) + 1, 1)), np.uint64)
+        self._check(self.lib.pqa_cross_sse_device(self._ctx, ref_ptr, ref_row_pitch, ref_frame_pitch, n_ref, dis_ptr,
+                                                  dis_row_pitch, dis_frame_pitch, n_dis, int(k_lo), int(k_hi),
+                                                  out.ctypes.data))
+        return out
+
     # -- results -----------------------------------------------------------------------------
     def collect(self, first_index: int, count: int) -> np.ndarray:
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)

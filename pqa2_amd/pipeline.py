@@ -31,7 +31,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 fixed_point: int = 0, float_ssim: bool = False, ms_ssim: bool = False,
                 ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False,
                 psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False,
-                integrity: bool = False, integrity_options=None) -> ScoreResult | None:
+                integrity: bool = False, integrity_options=None, align: int = 0,
+                align_frames: int | None = None, align_penalty_mse: float | None = None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -50,7 +51,15 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     `integrity`: FFmpeg's freezedetect, blackdetect and scdet on the DISTORTED clip (fifth extension record; every plane of
     a colour clip): the extra columns scd_mafd / scd_score / black_ratio / freeze_mafd and, under the result's `integrity`
     key, the event lists freezes / blacks / scene_changes (integrity.py); `integrity_options`: FFmpeg's option names
-    (integrity.DEFAULTS).  The black threshold follows the distorted clip's range (XCOLORRANGE=FULL: full range)."""
+    (integrity.DEFAULTS).  The black threshold follows the distorted clip's range (XCOLORRANGE=FULL: full range).
+    `align` = K > 0: before scoring, the banded cross-frame SSE of the two lumas over the offsets -K ... K (pqa_cross_sse) is
+    reduced to the constant frame offset k that pairs the clips (align.best_offset), and reference frame i is scored
+    against captured frame i + k over the range where both exist; output frame 0 is the first scored pair.  `align_frames`
+    = A limits the search to the first A reference and A + K captured frames (default: both clips whole).  The result's
+    `alignment` key holds {offset_frames, offset_seconds, mse, confidence, repeated, dropped, searched} -- repeated /
+    dropped from align.frame_map (`align_penalty_mse`: its step cost) are reported, not compensated.  Every rank of a
+    sharded run computes the same exact integers from the same frames, so the ranks agree without a collective.
+    `align` = 0: no search, the clips are paired as they are."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -61,6 +70,14 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         raise ValueError(f"reference is {ri.width}x{ri.height} but distorted is {di.width}x{di.height}")
     if ri.bit_depth != di.bit_depth or (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono):
         raise ValueError("reference and distorted clips differ in pixel format")
+    alignment = None
+    if align:
+        if align < 0 or align > 64:
+            raise ValueError("align must be 0 ... 64 frames")
+        alignment = _find_alignment(ref_rd, dis_rd, int(align), align_frames, align_penalty_mse, device,
+                                    engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+        k = alignment["offset_frames"]
+        ref_rd, dis_rd = _ShiftedReader(ref_rd, max(0, -k)), _ShiftedReader(dis_rd, max(0, k))
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
@@ -213,8 +230,58 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         extra.update(ext4=ext4, siti=True)
     if integrity:
         extra.update(integrity=ig_result)
-    return finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
-                          fps=n / elapsed if elapsed > 0 else 0.0, **extra)
+    res = finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
+                         fps=n / elapsed if elapsed > 0 else 0.0, **extra)
+    if alignment is not None:
+        res["alignment"] = alignment
+    return res
+
+
+class _ShiftedReader:
+    """A clip from its frame `start` on: what score_files reads once the alignment offset is known."""
+
+    def __init__(self, reader, start: int):
+        self._rd, self._start = reader, int(start)
+        self.info = reader.info
+        for name in ("fileno", "plane_offsets", "run_stride"):   # the file-descriptor submit path, where the reader has it
+            if hasattr(reader, name):
+                setattr(self, name, getattr(self, "_" + name))
+
+    def __len__(self):
+        return max(0, len(self._rd) - self._start)
+
+    def frame(self, i: int):
+        return self._rd.frame(i + self._start)
+
+    def _fileno(self):
+        return self._rd.fileno()
+
+    def _plane_offsets(self, i: int):
+        return self._rd.plane_offsets(i + self._start)
+
+    def _run_stride(self, i: int, n: int):
+        return self._rd.run_stride(i + self._start, n)
+
+
+def _find_alignment(ref_rd, dis_rd, K: int, align_frames, penalty_mse, device, make) -> dict:
+    """the `alignment` object of two opened clips: cross-SSE of their lumas over -K ... K on a small context of its own"""
+    from . import align as AL
+    ri = ref_rd.info
+    n_ref, n_dis = len(ref_rd), len(dis_rd)
+    if align_frames is not None:
+        if align_frames < 1:
+            raise ValueError("align_frames must be positive")
+        n_ref, n_dis = min(n_ref, int(align_frames)), min(n_dis, int(align_frames) + K)
+    if n_ref <= 0 or n_dis <= 0:
+        raise ValueError("no frames to align")
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
+               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+    try:
+        D = eng.cross_sse([ref_rd.frame(i)[0] for i in range(n_ref)], [dis_rd.frame(j)[0] for j in range(n_dis)], -K, K)
+    finally:
+        eng.close()
+    return AL.align(D, n_ref, n_dis, ri.width * ri.height, k_lo=-K, fps=ri.fps, bit_depth=ri.bit_depth,
+                    penalty_mse=penalty_mse)
 
 
 def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim: bool, n_subsample: int = 1,

@@ -88,6 +88,27 @@ def integrity_log_keys(events: dict | None) -> dict:
     return {"integrity": events} if events is not None else {}
 
 
+def alignment_log_keys(alignment: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the temporal alignment (pipeline.score_files(align=K)); none without it.
+    An infinite confidence (an exact match) is written as null: JSON has no infinity."""
+    if not alignment:
+        return {}
+    conf = alignment.get("confidence")
+    return {"alignment": {**alignment, "confidence": conf if conf is not None and np.isfinite(conf) else None}}
+
+
+def alignment_summary_line(alignment: dict) -> str:
+    """One line for a summary or a status bar: the offset found, its error and what the frame map saw."""
+    k = int(alignment["offset_frames"])
+    lo, hi = alignment.get("searched", [None, None])
+    conf = alignment.get("confidence")
+    conf_s = "exact match" if conf is None or not np.isfinite(conf) else f"confidence {conf:.1f}x"
+    where = "capture late" if k > 0 else "capture early" if k < 0 else "in step"
+    return (f"Alignment: offset {k:+d} frames ({alignment.get('offset_seconds', 0.0):+.3f} s, {where}), MSE "
+            f"{alignment.get('mse', 0.0):.2f}, {conf_s}, {len(alignment.get('repeated', []))} repeated / "
+            f"{len(alignment.get('dropped', []))} dropped frames, searched {lo} ... {hi}")
+
+
 def build_vmaf_log(metrics: dict, fps: float, frame_indices=None, extra_top: dict | None = None) -> dict:
     """dict with libvmaf's JSON schema: version, fps, frames[{frameNum, metrics}], pooled_metrics,
     aggregate_metrics.  Values are rounded to 6 decimals like libvmaf's %.6f writer."""

@@ -84,6 +84,11 @@ def main(argv=None) -> int:
     ap.add_argument("--integrity-log", default=None, help="event log in FFmpeg's wording, one line per event (implies --integrity)")
     for name in IG_OPTIONS:   # FFmpeg's option names and defaults (integrity.DEFAULTS); each implies --integrity
         ap.add_argument("--" + name.replace("_", "-"), type=float, default=None, help=f"integrity option {name}")
+    ap.add_argument("--align", type=int, default=0, metavar="K",
+                    help="search the frame offset that pairs the clips over -K ... K (banded cross-frame SSE) and score "
+                         "the aligned range; the JSON gets a top-level alignment object")
+    ap.add_argument("--align-frames", type=int, default=None, metavar="N",
+                    help="with --align: search the first N reference frames only (default: the whole clips)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -127,6 +132,7 @@ def main(argv=None) -> int:
                           **({"psnr_hvs": True} if a.psnr_hvs else {}),
                           **({"xpsnr": True} if (a.xpsnr or a.xpsnr_log) else {}),
                           **({"siti": True} if a.siti else {}),
+                          **({"align": a.align, "align_frames": a.align_frames} if a.align else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
@@ -139,7 +145,8 @@ def main(argv=None) -> int:
     if rank == 0:
         log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
                                     {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
-                                     **report.integrity_log_keys(res.get("integrity"))})
+                                     **report.integrity_log_keys(res.get("integrity")),
+                                     **report.alignment_log_keys(res.get("alignment"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -153,6 +160,8 @@ def main(argv=None) -> int:
         if a.ssim_log and res["ssim_lines"] is not None:
             with open(a.ssim_log, "w") as f:
                 f.write("\n".join(res["ssim_lines"]) + "\n")
+        if res.get("alignment"):
+            print(report.alignment_summary_line(res["alignment"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

@@ -159,6 +159,8 @@ class VMAFAnalyzer(QObject):
         self.integrity_enabled = False        # FFmpeg freezedetect / blackdetect / scdet on the distorted clip: event lists,
         self.integrity_options = {}           # <test>_<ts>_integrity.txt; FFmpeg's option names (integrity.DEFAULTS)
         self._integrity_path = None           # where this analysis writes the event log (set per analysis)
+        self.align_enabled = False            # temporal alignment before scoring: search the frame offset over
+        self.align_max_offset = 8             # -align_max_offset ... align_max_offset frames (pipeline.score_files(align=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -190,6 +192,15 @@ class VMAFAnalyzer(QObject):
                         f"feature_subsample={self.feature_subsample}, pool={self.pool_method}")
         except Exception as e:
             logger.error(f"Error setting VMAF options from manager: {e}")
+        for section in ("bookend", "analysis"):   # the alignment switches live beside the bookend settings; `analysis` overrides
+            try:
+                s = options_manager.get_setting(section) or {}
+            except Exception:
+                continue
+            if "align_enabled" in s:
+                self.align_enabled = bool(s["align_enabled"])
+            if "align_max_offset" in s:
+                self.align_max_offset = max(1, min(64, int(s["align_max_offset"])))
 
     set_options_manager = set_options_from_manager
 
@@ -205,7 +216,8 @@ class VMAFAnalyzer(QObject):
                              feature_subsample=1, psnr_enabled=True, ssim_enabled=True, float_ssim_enabled=False,
                              ms_ssim_enabled=False, ciede_enabled=False, cambi_enabled=False,
                              cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False,
-                             siti_enabled=False, integrity_enabled=False, integrity_options=None):
+                             siti_enabled=False, integrity_enabled=False, integrity_options=None,
+                             align_enabled=False, align_max_offset=8):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -222,6 +234,8 @@ class VMAFAnalyzer(QObject):
         self.siti_enabled = bool(siti_enabled)
         self.integrity_enabled = bool(integrity_enabled)
         self.integrity_options = dict(integrity_options or {})
+        self.align_enabled = bool(align_enabled)
+        self.align_max_offset = max(1, min(64, int(align_max_offset)))
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -396,7 +410,8 @@ class VMAFAnalyzer(QObject):
         self.last_fps = res["fps"]
         log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
                                     {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
-                                     **report.integrity_log_keys(res.get("integrity"))})
+                                     **report.integrity_log_keys(res.get("integrity")),
+                                     **report.alignment_log_keys(res.get("alignment"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -425,7 +440,8 @@ class VMAFAnalyzer(QObject):
                 **({"psnr_hvs": True} if self.psnr_hvs_enabled else {}),
                 **({"xpsnr": True} if self.xpsnr_enabled else {}),
                 **({"siti": True} if self.siti_enabled else {}),
-                **({"integrity": True, "integrity_options": dict(self.integrity_options)} if self.integrity_enabled else {})}
+                **({"integrity": True, "integrity_options": dict(self.integrity_options)} if self.integrity_enabled else {}),
+                **({"align": int(self.align_max_offset)} if self.align_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -458,6 +474,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--integrity"] + (["--integrity-log", self._integrity_path] if self._integrity_path else [])
             for k, v in self.integrity_options.items():
                 cmd += ["--" + k.replace("_", "-"), str(v)]
+        if self.align_enabled:
+            cmd += ["--align", str(int(self.align_max_offset))]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -572,6 +590,11 @@ class VMAFAnalyzer(QObject):
             if self.integrity_enabled:   # the event lists, from the log's top level
                 results["integrity"] = vmaf_data.get("integrity")
                 results["integrity_log"] = self._integrity_path
+            if self.align_enabled:   # the offset the clips were paired with, from the log's top level
+                results["alignment"] = vmaf_data.get("alignment")
+                if results["alignment"]:
+                    from . import report
+                    self.status_update.emit(report.alignment_summary_line(results["alignment"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
