@@ -461,6 +461,30 @@ PQA_API int pqa_cross_sse(pqa_ctx* ctx, const void* const* ref_frames, int64_t r
                           const void* const* dis_frames, int64_t dis_row_stride, int32_t n_dis, int32_t k_lo, int32_t k_hi,
                           uint64_t* out);
 
+/* Spatial alignment: the shifted-window luma SSE of n_frames frame pairs, synchronously.  For a search radius R = radius,
+ * 0 <= R <= 16, on frames with W > 2R and H > 2R:
+ *     S[f][j][i] = sum_{y=R}^{H-R-1} sum_{x=R}^{W-R-1} (ref_f[y][x] - dis_f[y + dy][x + dx])^2,  dy = j - R,  dx = i - R
+ * Exact uint64 sums; the summed reference window is the same for every shift, so all entries count (W - 2R)(H - 2R) pixels.
+ * dx > 0 means the captured picture is displaced to the right, dy > 0 down.  out (host) is [n_frames][2R + 1][2R + 1]; frame
+ * f pairs reference frame f with captured frame f.  Any context: its width, height and bit depth (8, 10, 12) are used, no
+ * feature bit is needed, device buffers are allocated on first use, grow only and are freed with the context.  Independent
+ * of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL on a null pointer, a negative
+ * frame count, a radius outside 0 ... 16 or a frame not larger than 2R in either direction (checked before any device call);
+ * n_frames == 0 succeeds and writes nothing.  pqa2_amd/align.py (best_shift) turns S into a shift; definition, tiling and
+ * overflow rule: DESIGN.md section 5.
+ *
+ * pqa_shift_sse_device: both clips in device memory (frame f at luma + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+PQA_API int pqa_shift_sse_device(pqa_ctx* ctx, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch,
+                                 const void* dis_luma, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames,
+                                 int32_t radius, uint64_t* out);
+
+/* The same for frames in HOST memory: ref_frames[f] / dis_frames[f] point at luma planes (rows *_row_stride bytes apart; the
+ * frames need not be contiguous, as for pqa_luma_stats).  Frames go through the pinned staging of pqa_luma_stats in chunks
+ * of 8 pairs. */
+PQA_API int pqa_shift_sse(pqa_ctx* ctx, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
+                          int64_t dis_row_stride, int32_t n_frames, int32_t radius, uint64_t* out);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to

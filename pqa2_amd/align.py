@@ -1,4 +1,5 @@
-"""Temporal alignment on the host: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
+"""Temporal and spatial alignment on the host.  Spatial (best_shift, at the end of this file): from the shifted-window luma
+SSE (FeatureEngine.shift_sse, pqa_shift_sse) to the whole-pixel displacement of the captured picture.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
 constant frame offset and a per-frame map with repeated and dropped frames.
 
     D[i][c] = sum over luma pixels of (ref_i - dis_{i+k})^2,  k = k_lo + c;  UINT64_MAX where i + k is no captured frame
@@ -212,3 +213,61 @@ def align(D, n_ref: int, n_dis: int, n_pixels: int, *, k_lo: int, fps: float = 0
     return {"offset_frames": int(k), "offset_seconds": (k / fps if fps else 0.0), "mse": float(mse),
             "confidence": float(conf), "repeated": [int(j) for j in repeated], "dropped": [int(i) for i in dropped],
             "searched": [int(k_lo), int(k_lo + span - 1)]}
+
+
+# ---- spatial alignment -----------------------------------------------------------------------------------------------------
+def _shift_key(p: int, dx: int, dy: int):
+    """the tie order of shifts: the smaller error, then the shorter shift, then the smaller |dy|, then dy, then dx"""
+    return (p, dx * dx + dy * dy, abs(dy), dy, dx)
+
+
+def _argmin_shift(P, R: int):
+    return min(((dx, dy) for dy in range(-R, R + 1) for dx in range(-R, R + 1)),
+               key=lambda s: _shift_key(P[s[1] + R][s[0] + R], s[0], s[1]))
+
+
+def _parabola(lo: int, mid: int, hi: int):
+    """vertex of the parabola through (-1, lo), (0, mid), (1, hi), relative to 0; None when it has no minimum"""
+    den = lo - 2 * mid + hi
+    return (lo - hi) / (2.0 * den) if den > 0 else None
+
+
+def best_shift(S, radius: int, n_pixels: int = 1) -> dict:
+    """The whole-pixel displacement (dx, dy) of the captured picture from S[n_frames][2R + 1][2R + 1] (pqa_shift_sse):
+    S[f][j][i] is the squared error of frame pair f with the capture read at (x + i - R, y + j - R), so dx > 0 means the
+    captured picture sits to the right of the reference's, dy > 0 below it.
+
+    The frames are pooled, P = sum over f of S[f] in Python ints, and the minimum is taken with the tie key (P, dx^2 + dy^2,
+    |dy|, dy, dx).  Returns {dx, dy, mse, confidence, agreement, at_edge, subpixel_dx, subpixel_dy, searched}:
+    mse = P / (n_frames * n_pixels), n_pixels = (W - 2R)(H - 2R), the pixels one entry of S sums;
+    confidence = (the smallest P outside the 3 x 3 neighbourhood of the minimum) / (P at the minimum): inf when the minimum
+    is 0 and that one is not, 1.0 when both are 0 or the search has no entry outside the neighbourhood;
+    agreement = the share of the frames whose own minimum under the same key is (dx, dy);
+    at_edge = |dx| == R or |dy| == R: a minimum on the border of the search is not a minimum;
+    subpixel_dx / subpixel_dy = the vertex of the three-point parabola through P along each axis, relative to the minimum
+    (-0.5 ... 0.5; informational: a steady +-0.5 hints at scaling, which a shift does not correct), None when at_edge or
+    when the three points have no minimum;  searched = R."""
+    S = np.asarray(S)
+    R = int(radius)
+    if R < 0 or S.ndim != 3 or S.shape[0] < 1 or S.shape[1:] != (2 * R + 1, 2 * R + 1):
+        raise ValueError("S must be [n_frames >= 1, 2R + 1, 2R + 1]")
+    n = S.shape[0]
+    frames = [[[int(v) for v in row] for row in S[f]] for f in range(n)]
+    P = [[sum(frames[f][j][i] for f in range(n)) for i in range(2 * R + 1)] for j in range(2 * R + 1)]
+    dx, dy = _argmin_shift(P, R)
+    best = P[dy + R][dx + R]
+    outside = [P[j][i] for j in range(2 * R + 1) for i in range(2 * R + 1) if abs(j - R - dy) > 1 or abs(i - R - dx) > 1]
+    if not outside:
+        conf = 1.0
+    elif best == 0:
+        conf = float("inf") if min(outside) > 0 else 1.0
+    else:
+        conf = min(outside) / best
+    at_edge = abs(dx) == R or abs(dy) == R
+    sub_x = sub_y = None
+    if not at_edge:
+        sub_x = _parabola(P[dy + R][dx + R - 1], best, P[dy + R][dx + R + 1])
+        sub_y = _parabola(P[dy + R - 1][dx + R], best, P[dy + R + 1][dx + R])
+    return {"dx": int(dx), "dy": int(dy), "mse": best / (float(n) * float(n_pixels)), "confidence": float(conf),
+            "agreement": sum(1 for f in range(n) if _argmin_shift(frames[f], R) == (dx, dy)) / float(n),
+            "at_edge": bool(at_edge), "subpixel_dx": sub_x, "subpixel_dy": sub_y, "searched": R}

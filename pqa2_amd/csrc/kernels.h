@@ -398,5 +398,17 @@ hipError_t launch_cross_sse(hipStream_t stream, Elem elem, bool mfma, const Xsse
                             int k_lo, int span, int tile0, int n_tiles, void* part, const unsigned long long* norm_ref,
                             const unsigned long long* norm_dis, unsigned long long* out);
 
+// ---- spatial alignment: shifted-window luma SSE (shift_sse.hip) ----------------------------------------------------------
+// out[f][j][i] = sum over the window R <= x < w - R, R <= y < h - R of (ref_f[y][x] - dis_f[y + j - R][x + i - R])^2, exact
+// uint64, for n_frames pairs (frame f at base + f * frame_pitch, pitches in elements).  part / rowsq: workspaces of
+// shift_part_bytes / shift_rowsq_bytes for the same (elem, w, h, R, n_frames).
+constexpr int kShiftMaxRadius = 16;
+constexpr int kShiftChunk = 8;   // frame pairs per launch of the two entries
+size_t shift_part_bytes(Elem elem, int w, int h, int R, int n_frames);
+size_t shift_rowsq_bytes(int h, int R, int n_frames);
+hipError_t launch_shift_sse(hipStream_t stream, Elem elem, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
+                            const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int n_frames, int w, int h, int R,
+                            void* part, unsigned long long* rowsq, unsigned long long* out);
+
 }  // namespace pqa
 

@@ -183,8 +183,8 @@ struct pqa_ctx {
   uint32_t luma_gray = PQA_GRAY_LUMA;
   // temporal alignment (pqa_cross_sse / pqa_cross_sse_device; cross_sse.hip): grow-only buffers, allocated on first use
   bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
-  void* xs_buf[6] = {};              // XS_* below
-  size_t xs_cap[6] = {};             // their sizes in bytes
+  void* xs_buf[9] = {};              // XS_* below (the last three: pqa_shift_sse / pqa_shift_sse_device; shift_sse.hip)
+  size_t xs_cap[9] = {};             // their sizes in bytes
   // motion continuity
   uint8_t* last_luma = nullptr;
   int64_t last_luma_pitch = 0;  // bytes
@@ -2208,7 +2208,7 @@ int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_strid
 }
 
 namespace {
-enum { XS_PART = 0, XS_NORM_REF, XS_NORM_DIS, XS_OUT, XS_REF, XS_DIS };
+enum { XS_PART = 0, XS_NORM_REF, XS_NORM_DIS, XS_OUT, XS_REF, XS_DIS, XS_SH_PART, XS_SH_ROWSQ, XS_SH_OUT };
 
 // a grow-only device buffer of the cross-SSE calls
 int xs_reserve(pqa_ctx* c, int which, size_t bytes) {
@@ -2365,6 +2365,108 @@ int pqa_cross_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_str
   const hipError_t es2 = hipStreamSynchronize(c->stream);
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (e != hipSuccess) return fail(c, PQA_EDEVICE, "cross_sse failed: %s", hipGetErrorString(e));
+  if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
+  return PQA_OK;
+}
+
+namespace {
+// the argument rules the two spatial entries share; no device call
+int sh_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int32_t radius, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "shift_sse: negative frame count");
+  if (radius < 0 || radius > kShiftMaxRadius) return fail(c, PQA_EINVAL, "shift_sse: radius %d outside 0 ... %d", radius, kShiftMaxRadius);
+  if (c->pw[0] <= 2 * radius || c->ph[0] <= 2 * radius)
+    return fail(c, PQA_EINVAL, "shift_sse: a %dx%d frame is not larger than twice the radius %d", c->pw[0], c->ph[0], radius);
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "shift_sse: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "shift_sse: null output pointer");
+  return PQA_OK;
+}
+
+int sh_prepare(pqa_ctx* c, int radius, int32_t n_frames) {
+  const int chunk = n_frames < kShiftChunk ? n_frames : kShiftChunk;
+  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  int rc = xs_reserve(c, XS_SH_PART, shift_part_bytes(c->elem, c->pw[0], c->ph[0], radius, chunk));
+  if (rc == PQA_OK) rc = xs_reserve(c, XS_SH_ROWSQ, shift_rowsq_bytes(c->ph[0], radius, chunk));
+  if (rc == PQA_OK) rc = xs_reserve(c, XS_SH_OUT, (size_t)n_frames * n * sizeof(uint64_t));
+  return rc;
+}
+}  // namespace
+
+int pqa_shift_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis_luma,
+                         int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t radius, uint64_t* out) {
+  const int chk = sh_check(c, ref_luma, dis_luma, n_frames, radius, out);
+  if (chk != PQA_OK) return chk;
+  if (n_frames == 0) return PQA_OK;
+  const int es = c->esize;
+  const int64_t row_bytes = (int64_t)c->pw[0] * es;
+  if (ref_row_pitch % es || ref_frame_pitch % es || dis_row_pitch % es || dis_frame_pitch % es)
+    return fail(c, PQA_EINVAL, "shift_sse: pitch is not a multiple of the sample size");
+  if (ref_row_pitch < row_bytes || dis_row_pitch < row_bytes) return fail(c, PQA_EINVAL, "shift_sse: pitch smaller than a row");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = sh_prepare(c, radius, n_frames);
+  if (rc != PQA_OK) return rc;
+  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  auto* dev_out = (unsigned long long*)c->xs_buf[XS_SH_OUT];
+  for (int f0 = 0; f0 < n_frames; f0 += kShiftChunk) {
+    const int m = n_frames - f0 < kShiftChunk ? n_frames - f0 : kShiftChunk;
+    HIPCHK(c, launch_shift_sse(c->stream, c->elem, (const uint8_t*)ref_luma + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
+                               ref_frame_pitch / es, (const uint8_t*)dis_luma + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
+                               dis_frame_pitch / es, m, c->pw[0], c->ph[0], radius, c->xs_buf[XS_SH_PART],
+                               (unsigned long long*)c->xs_buf[XS_SH_ROWSQ], dev_out + (size_t)f0 * n));
+  }
+  HIPCHK(c, hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PQA_OK;
+}
+
+int pqa_shift_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
+                  int64_t dis_row_stride, int32_t n_frames, int32_t radius, uint64_t* out) {
+  const int chk = sh_check(c, ref_frames, dis_frames, n_frames, radius, out);
+  if (chk != PQA_OK) return chk;
+  if (n_frames == 0) return PQA_OK;
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  if ((size_t)ref_row_stride < row_bytes || (size_t)dis_row_stride < row_bytes)
+    return fail(c, PQA_EINVAL, "shift_sse: stride smaller than a row");
+  for (int f = 0; f < n_frames; ++f)   // before anything is queued
+    if (!ref_frames[f] || !dis_frames[f]) return fail(c, PQA_EINVAL, "shift_sse: frame %d pointer is null", f);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = luma_staging_ensure(c);
+  if (rc == PQA_OK) rc = sh_prepare(c, radius, n_frames);   // LB <= kShiftChunk: the workspaces of a full chunk hold every chunk here
+  if (rc != PQA_OK) return rc;
+  const int h = c->ph[0], es = c->esize;
+  const size_t frame_bytes = (size_t)c->luma_pitch * h, n = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  auto* dev_out = (unsigned long long*)c->xs_buf[XS_SH_OUT];
+  // A chunk of LB (<= 8) pairs: the reference frames go through pinned / device half 0, the captured ones through half 1.
+  // The stream orders a chunk's kernels before the next chunk's uploads into the same device halves; a pinned half is
+  // repacked once the copy out of it has finished.
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += c->LB) {
+    if (c->cancelled.load()) break;
+    const int m = n_frames - f0 < c->LB ? n_frames - f0 : c->LB;
+    for (int hf = 0; hf < 2 && e == hipSuccess; ++hf) {
+      const void* const* frames = hf ? dis_frames : ref_frames;
+      const int64_t stride = hf ? dis_row_stride : ref_row_stride;
+      if (f0 > 0) e = hipEventSynchronize(c->luma_copied[hf]);
+      if (e != hipSuccess) break;
+      for (int f = 0; f < m; ++f)
+        copy_plane_rows(c->luma_pinned[hf] + (size_t)f * frame_bytes, c->luma_pitch, (const uint8_t*)frames[f0 + f], stride,
+                        row_bytes, h);
+      e = hipMemcpyAsync(c->luma_dev[hf], c->luma_pinned[hf], (size_t)m * frame_bytes, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
+    }
+    if (e == hipSuccess)
+      e = launch_shift_sse(c->stream, c->elem, c->luma_dev[0], c->luma_pitch / es, (int64_t)(frame_bytes / es), c->luma_dev[1],
+                           c->luma_pitch / es, (int64_t)(frame_bytes / es), m, c->pw[0], h, radius, c->xs_buf[XS_SH_PART],
+                           (unsigned long long*)c->xs_buf[XS_SH_ROWSQ], dev_out + (size_t)f0 * n);
+  }
+  if (e == hipSuccess && !c->cancelled.load())
+    e = hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+  // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
+  const hipError_t es2 = hipStreamSynchronize(c->stream);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "shift_sse failed: %s", hipGetErrorString(e));
   if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
   return PQA_OK;
 }

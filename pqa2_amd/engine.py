@@ -340,6 +340,32 @@ class FeatureEngine:
                                                   out.ctypes.data))
         return out
 
+    # -- spatial alignment -------------------------------------------------------------------
+    def shift_sse(self, ref_frames, dis_frames, radius: int) -> np.ndarray:
+        """[n, 2R + 1, 2R + 1] uint64: S[f][j][i] = sum over the window R <= x < W - R, R <= y < H - R of
+        (ref_f[y][x] - dis_f[y + j - R][x + i - R])^2, exact (pqa_shift_sse).  Luma planes in HOST memory (two lists of 2-D
+        arrays of equal length).  align.best_shift reads the result."""
+        n, R = len(ref_frames), int(radius)
+        if len(dis_frames) != n:
+            raise ValueError("shift_sse needs as many captured as reference frames")
+        side = 2 * R + 1 if 0 <= R <= 16 else 1
+        out = np.zeros((n, side, side), np.uint64)
+        keep_r, rp, rs = self._luma_list(ref_frames, "reference")
+        keep_d, dp, ds = self._luma_list(dis_frames, "captured")
+        self._check(self.lib.pqa_shift_sse(self._ctx, rp, rs, dp, ds, n, R, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def shift_sse_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                           dis_frame_pitch: int, n_frames: int, radius: int) -> np.ndarray:
+        """The same for two clips in HBM (device pointers, pitches in bytes; pqa_shift_sse_device)."""
+        R = int(radius)
+        side = 2 * R + 1 if 0 <= R <= 16 else 1
+        out = np.zeros((max(int(n_frames), 0), side, side), np.uint64)
+        self._check(self.lib.pqa_shift_sse_device(self._ctx, ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch,
+                                                  dis_frame_pitch, int(n_frames), R, out.ctypes.data))
+        return out
+
     # -- results -----------------------------------------------------------------------------
     def collect(self, first_index: int, count: int) -> np.ndarray:
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)

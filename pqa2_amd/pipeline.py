@@ -32,7 +32,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 ciede: bool = False, cambi: bool = False, cambi_full_ref: bool = False,
                 psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False,
                 integrity: bool = False, integrity_options=None, align: int = 0,
-                align_frames: int | None = None, align_penalty_mse: float | None = None) -> ScoreResult | None:
+                align_frames: int | None = None, align_penalty_mse: float | None = None, spatial_align: int = 0,
+                spatial_frames: int = 8) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -59,7 +60,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     `alignment` key holds {offset_frames, offset_seconds, mse, confidence, repeated, dropped, searched} -- repeated /
     dropped from align.frame_map (`align_penalty_mse`: its step cost) are reported, not compensated.  Every rank of a
     sharded run computes the same exact integers from the same frames, so the ranks agree without a collective.
-    `align` = 0: no search, the clips are paired as they are."""
+    `align` = 0: no search, the clips are paired as they are.
+    `spatial_align` = R > 0 (at most 16): before scoring (after the temporal search, on the pairs it found), the shifted-window
+    luma SSE of `spatial_frames` pairs spread evenly over the common range (pqa_shift_sse) is reduced to the whole-pixel
+    displacement (dx, dy) of the captured picture (align.best_shift).  `alignment["spatial"]` holds {dx, dy, mse, confidence,
+    agreement, at_edge, subpixel_dx, subpixel_dy, searched, frames, applied, chroma_exact}; `applied` = not at_edge and
+    (dx, dy) != (0, 0).  When applied, both clips are cropped to the common window and scored at (W - |dx|) x (H - |dy|):
+    the reference from (max(0, -dx), max(0, -dy)), the capture from that origin moved by (dx, dy), chroma planes from
+    `origin >> shift` of each clip.  `chroma_exact` is false when dx or dy is no multiple of the chroma subsampling: chroma
+    is then paired half a chroma sample off.  Scaling and sub-pixel displacement are not corrected.
+    `spatial_align` = 0: no search, pixel (x, y) meets pixel (x, y)."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -78,6 +88,19 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                                     engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
         k = alignment["offset_frames"]
         ref_rd, dis_rd = _ShiftedReader(ref_rd, max(0, -k)), _ShiftedReader(dis_rd, max(0, k))
+    if spatial_align:
+        if spatial_align < 0 or spatial_align > 16:
+            raise ValueError("spatial_align must be 0 ... 16 pixels")
+        if spatial_frames is None or spatial_frames < 1:
+            raise ValueError("spatial_frames must be positive")
+        if ri.width <= 2 * spatial_align or ri.height <= 2 * spatial_align:
+            raise ValueError(f"spatial_align {spatial_align} needs a frame larger than {2 * spatial_align} pixels each way")
+        spatial = _find_shift(ref_rd, dis_rd, int(spatial_align), int(spatial_frames), device,
+                              engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+        alignment = dict(alignment or {}, spatial=spatial)
+        if spatial["applied"]:
+            ref_rd, dis_rd = crop_readers(ref_rd, dis_rd, spatial["dx"], spatial["dy"])
+            ri, di = ref_rd.info, dis_rd.info
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
@@ -261,6 +284,70 @@ class _ShiftedReader:
 
     def _run_stride(self, i: int, n: int):
         return self._rd.run_stride(i + self._start, n)
+
+
+class _CroppedReader:
+    """A clip cut to the window of `width` x `height` luma pixels at (x0, y0): what score_files reads once the spatial shift
+    is known.  Frames are strided views of the wrapped reader's planes (nothing is copied); chroma planes are cut at
+    (x0 >> hshift, y0 >> vshift) to the chroma size of the window.  No file-descriptor path: rows of a window do not lie
+    packed in the file, so the frames go down through FeatureEngine.submit."""
+
+    def __init__(self, reader, x0: int, y0: int, width: int, height: int):
+        import dataclasses
+        src = reader.info
+        if x0 < 0 or y0 < 0 or width < 1 or height < 1 or x0 + width > src.width or y0 + height > src.height:
+            raise ValueError("crop window outside the frame")
+        self._rd, self._x0, self._y0 = reader, int(x0), int(y0)
+        self.info = dataclasses.replace(src, width=int(width), height=int(height))
+
+    def __len__(self):
+        return len(self._rd)
+
+    def windows(self):
+        """[(y0, x0, h, w)] of every plane, in samples of that plane"""
+        i = self.info
+        out = [(self._y0, self._x0, i.height, i.width)]
+        if not i.mono:
+            out += [(self._y0 >> i.vshift, self._x0 >> i.hshift, i.chroma_h, i.chroma_w)] * 2
+        return out
+
+    def frame(self, i: int):
+        planes = self._rd.frame(i)
+        return [p[y:y + h, x:x + w] for p, (y, x, h, w) in zip(planes, self.windows())]
+
+
+def crop_readers(ref_rd, dis_rd, dx: int, dy: int):
+    """both clips cut to their common window under the displacement (dx, dy) of the captured picture: reference pixel (x, y)
+    meets captured pixel (x + dx, y + dy)"""
+    w, h = ref_rd.info.width - abs(dx), ref_rd.info.height - abs(dy)
+    x0, y0 = max(0, -dx), max(0, -dy)
+    return _CroppedReader(ref_rd, x0, y0, w, h), _CroppedReader(dis_rd, x0 + dx, y0 + dy, w, h)
+
+
+def spatial_sample(n: int, count: int):
+    """`count` frame numbers spread evenly over 0 ... n - 1 (the middles of `count` equal parts; fewer when n < count)"""
+    return sorted({(2 * t + 1) * n // (2 * count) for t in range(count)}) if n > 0 else []
+
+
+def _find_shift(ref_rd, dis_rd, R: int, n_frames: int, device, make) -> dict:
+    """the `spatial` object of two opened (and temporally paired) clips: shifted-window SSE of a few luma pairs over
+    -R ... R in both directions on a small context of its own"""
+    from . import align as AL
+    ri = ref_rd.info
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError("no frames to align")
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
+               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+    try:
+        S = eng.shift_sse([ref_rd.frame(i)[0] for i in idx], [dis_rd.frame(i)[0] for i in idx], R)
+    finally:
+        eng.close()
+    sp = AL.best_shift(S, R, (ri.width - 2 * R) * (ri.height - 2 * R))
+    sp["frames"] = len(idx)
+    sp["applied"] = bool(not sp["at_edge"] and (sp["dx"], sp["dy"]) != (0, 0))
+    sp["chroma_exact"] = bool(ri.mono or (sp["dx"] % (1 << ri.hshift) == 0 and sp["dy"] % (1 << ri.vshift) == 0))
+    return sp
 
 
 def _find_alignment(ref_rd, dis_rd, K: int, align_frames, penalty_mse, device, make) -> dict:

@@ -93,8 +93,13 @@ def alignment_log_keys(alignment: dict | None) -> dict:
     An infinite confidence (an exact match) is written as null: JSON has no infinity."""
     if not alignment:
         return {}
-    conf = alignment.get("confidence")
-    return {"alignment": {**alignment, "confidence": conf if conf is not None and np.isfinite(conf) else None}}
+    def finite(obj):
+        conf = obj.get("confidence")
+        return {**obj, "confidence": conf if conf is not None and np.isfinite(conf) else None}
+    out = finite(alignment) if "confidence" in alignment else dict(alignment)
+    if alignment.get("spatial"):
+        out["spatial"] = finite(alignment["spatial"])
+    return {"alignment": out}
 
 
 def alignment_summary_line(alignment: dict) -> str:
@@ -107,6 +112,21 @@ def alignment_summary_line(alignment: dict) -> str:
     return (f"Alignment: offset {k:+d} frames ({alignment.get('offset_seconds', 0.0):+.3f} s, {where}), MSE "
             f"{alignment.get('mse', 0.0):.2f}, {conf_s}, {len(alignment.get('repeated', []))} repeated / "
             f"{len(alignment.get('dropped', []))} dropped frames, searched {lo} ... {hi}")
+
+
+def spatial_summary_line(spatial: dict) -> str:
+    """One line for a summary or a status bar: the displacement found, its error and whether the clips were cropped."""
+    conf = spatial.get("confidence")
+    conf_s = "exact match" if conf is None or not np.isfinite(conf) else f"confidence {conf:.1f}x"
+    if spatial.get("applied"):
+        what = "cropped to the common window" + ("" if spatial.get("chroma_exact", True) else ", chroma half a sample off")
+    elif spatial.get("at_edge"):
+        what = "minimum on the border of the search: not applied"
+    else:
+        what = "in place"
+    return (f"Spatial alignment: capture displaced by ({int(spatial['dx']):+d}, {int(spatial['dy']):+d}) px, MSE "
+            f"{spatial.get('mse', 0.0):.2f}, {conf_s}, agreement {100.0 * spatial.get('agreement', 0.0):.0f} % of "
+            f"{spatial.get('frames', 0)} frames, searched +-{spatial.get('searched')} px, {what}")
 
 
 def build_vmaf_log(metrics: dict, fps: float, frame_indices=None, extra_top: dict | None = None) -> dict:

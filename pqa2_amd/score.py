@@ -89,6 +89,12 @@ def main(argv=None) -> int:
                          "the aligned range; the JSON gets a top-level alignment object")
     ap.add_argument("--align-frames", type=int, default=None, metavar="N",
                     help="with --align: search the first N reference frames only (default: the whole clips)")
+    ap.add_argument("--spatial-align", type=int, default=0, metavar="R",
+                    help="search the whole-pixel displacement of the captured picture over -R ... R in x and y (R <= 16, "
+                         "shifted-window luma SSE) and score both clips cropped to the common window; the JSON's "
+                         "alignment object gets a spatial entry")
+    ap.add_argument("--spatial-frames", type=int, default=8, metavar="N",
+                    help="with --spatial-align: search N frame pairs spread evenly over the clips (default 8)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -133,6 +139,7 @@ def main(argv=None) -> int:
                           **({"xpsnr": True} if (a.xpsnr or a.xpsnr_log) else {}),
                           **({"siti": True} if a.siti else {}),
                           **({"align": a.align, "align_frames": a.align_frames} if a.align else {}),
+                          **({"spatial_align": a.spatial_align, "spatial_frames": a.spatial_frames} if a.spatial_align else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
@@ -160,8 +167,10 @@ def main(argv=None) -> int:
         if a.ssim_log and res["ssim_lines"] is not None:
             with open(a.ssim_log, "w") as f:
                 f.write("\n".join(res["ssim_lines"]) + "\n")
-        if res.get("alignment"):
+        if res.get("alignment") and "offset_frames" in res["alignment"]:
             print(report.alignment_summary_line(res["alignment"]), file=sys.stderr, flush=True)
+        if res.get("alignment") and res["alignment"].get("spatial"):
+            print(report.spatial_summary_line(res["alignment"]["spatial"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

@@ -161,6 +161,8 @@ class VMAFAnalyzer(QObject):
         self._integrity_path = None           # where this analysis writes the event log (set per analysis)
         self.align_enabled = False            # temporal alignment before scoring: search the frame offset over
         self.align_max_offset = 8             # -align_max_offset ... align_max_offset frames (pipeline.score_files(align=))
+        self.spatial_align_enabled = False    # spatial alignment before scoring: search the capture's displacement over
+        self.spatial_align_radius = 8         # -radius ... radius pixels in x and y (pipeline.score_files(spatial_align=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -201,6 +203,10 @@ class VMAFAnalyzer(QObject):
                 self.align_enabled = bool(s["align_enabled"])
             if "align_max_offset" in s:
                 self.align_max_offset = max(1, min(64, int(s["align_max_offset"])))
+            if "spatial_align_enabled" in s:
+                self.spatial_align_enabled = bool(s["spatial_align_enabled"])
+            if "spatial_align_radius" in s:
+                self.spatial_align_radius = max(1, min(16, int(s["spatial_align_radius"])))
 
     set_options_manager = set_options_from_manager
 
@@ -217,7 +223,8 @@ class VMAFAnalyzer(QObject):
                              ms_ssim_enabled=False, ciede_enabled=False, cambi_enabled=False,
                              cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False,
                              siti_enabled=False, integrity_enabled=False, integrity_options=None,
-                             align_enabled=False, align_max_offset=8):
+                             align_enabled=False, align_max_offset=8, spatial_align_enabled=False,
+                             spatial_align_radius=8):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -236,6 +243,8 @@ class VMAFAnalyzer(QObject):
         self.integrity_options = dict(integrity_options or {})
         self.align_enabled = bool(align_enabled)
         self.align_max_offset = max(1, min(64, int(align_max_offset)))
+        self.spatial_align_enabled = bool(spatial_align_enabled)
+        self.spatial_align_radius = max(1, min(16, int(spatial_align_radius)))
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -441,7 +450,8 @@ class VMAFAnalyzer(QObject):
                 **({"xpsnr": True} if self.xpsnr_enabled else {}),
                 **({"siti": True} if self.siti_enabled else {}),
                 **({"integrity": True, "integrity_options": dict(self.integrity_options)} if self.integrity_enabled else {}),
-                **({"align": int(self.align_max_offset)} if self.align_enabled else {})}
+                **({"align": int(self.align_max_offset)} if self.align_enabled else {}),
+                **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -476,6 +486,8 @@ class VMAFAnalyzer(QObject):
                 cmd += ["--" + k.replace("_", "-"), str(v)]
         if self.align_enabled:
             cmd += ["--align", str(int(self.align_max_offset))]
+        if self.spatial_align_enabled:
+            cmd += ["--spatial-align", str(int(self.spatial_align_radius))]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -590,11 +602,13 @@ class VMAFAnalyzer(QObject):
             if self.integrity_enabled:   # the event lists, from the log's top level
                 results["integrity"] = vmaf_data.get("integrity")
                 results["integrity_log"] = self._integrity_path
-            if self.align_enabled:   # the offset the clips were paired with, from the log's top level
+            if self.align_enabled or self.spatial_align_enabled:   # how the clips were paired, from the log's top level
+                from . import report
                 results["alignment"] = vmaf_data.get("alignment")
-                if results["alignment"]:
-                    from . import report
+                if results["alignment"] and "offset_frames" in results["alignment"]:
                     self.status_update.emit(report.alignment_summary_line(results["alignment"]))
+                if results["alignment"] and results["alignment"].get("spatial"):
+                    self.status_update.emit(report.spatial_summary_line(results["alignment"]["spatial"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
