@@ -485,6 +485,33 @@ PQA_API int pqa_shift_sse_device(pqa_ctx* ctx, const void* ref_luma, int64_t ref
 PQA_API int pqa_shift_sse(pqa_ctx* ctx, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
                           int64_t dis_row_stride, int32_t n_frames, int32_t radius, uint64_t* out);
 
+/* Level alignment: the per-level transfer table of n_frames frame pairs of one plane, synchronously.  With L =
+ * pqa_level_bins(ctx) = 2^bit_depth and v = 0 ... L - 1:
+ *     T[f][v][0] = number of pixels of pair f with ref == v
+ *     T[f][v][1] = sum of dis over those pixels          T[f][v][2] = sum of dis^2 over those pixels
+ * Exact uint64.  A reference sample above L - 1 (a 16-bit container can hold one) is counted in bin L - 1; its captured
+ * partner enters the sums as it is.  out (host) is [n_frames][L][3].  plane 0 / 1 / 2 selects the context's luma or chroma
+ * plane size (chroma from chroma_shift).  Any context, no feature bit; the device table is allocated on first use, grows only
+ * and is freed with the context.  Independent of the scoring chain: a call between two pqa_submit calls changes no record.
+ * PQA_EINVAL on a null pointer, a negative frame count, plane < 0 or plane >= n_planes (checked before any device call);
+ * n_frames == 0 succeeds and writes nothing.  pqa2_amd/align.py (best_levels, level_lut) turns T into a gain / offset and
+ * a correction table; kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_level_stats_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+PQA_API int pqa_level_stats_device(pqa_ctx* ctx, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
+                                   const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames,
+                                   int32_t plane, uint64_t* out);
+
+/* The same for frames in HOST memory: ref_frames[f] / dis_frames[f] point at planes of the selected size (rows *_row_stride
+ * bytes apart; the frames need not be contiguous).  Frames go through the pinned staging of pqa_luma_stats in chunks of 8
+ * pairs. */
+PQA_API int pqa_level_stats(pqa_ctx* ctx, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
+                            int64_t dis_row_stride, int32_t n_frames, int32_t plane, uint64_t* out);
+
+/* L, the number of levels of the table above: 2^bit_depth of the context. */
+PQA_API int pqa_level_bins(const pqa_ctx* ctx);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to

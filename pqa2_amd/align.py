@@ -1,5 +1,7 @@
-"""Temporal and spatial alignment on the host.  Spatial (best_shift, at the end of this file): from the shifted-window luma
-SSE (FeatureEngine.shift_sse, pqa_shift_sse) to the whole-pixel displacement of the captured picture.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
+"""Temporal, spatial and level alignment on the host.  Spatial (best_shift, below the temporal part): from the shifted-window luma
+SSE (FeatureEngine.shift_sse, pqa_shift_sse) to the whole-pixel displacement of the captured picture.  Levels (best_levels,
+level_lut, at the end of this file): from the per-level transfer table (FeatureEngine.level_stats, pqa_level_stats) to the gain
+and offset of the captured samples, the named range conversion they amount to and the table that undoes it.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
 constant frame offset and a per-frame map with repeated and dropped frames.
 
     D[i][c] = sum over luma pixels of (ref_i - dis_{i+k})^2,  k = k_lo + c;  UINT64_MAX where i + k is no captured frame
@@ -10,6 +12,8 @@ Python-int / int64 arithmetic on exact integers, so a result does not depend on 
 This replaces the reference's hand-tuned `frame_offset` spin box (app/bookend_alignment.py) and the "SSIM" / "Combined"
 alignment methods its options tab offers and nothing implements."""
 from __future__ import annotations
+
+from fractions import Fraction
 
 import numpy as np
 
@@ -271,3 +275,124 @@ def best_shift(S, radius: int, n_pixels: int = 1) -> dict:
     return {"dx": int(dx), "dy": int(dy), "mse": best / (float(n) * float(n_pixels)), "confidence": float(conf),
             "agreement": sum(1 for f in range(n) if _argmin_shift(frames[f], R) == (dx, dy)) / float(n),
             "at_edge": bool(at_edge), "subpixel_dx": sub_x, "subpixel_dy": sub_y, "searched": R}
+
+
+# ---- level alignment -------------------------------------------------------------------------------------------------------
+LEVEL_MAPS = ("identity", "limited_to_full", "full_to_limited")
+
+
+def named_level_map(name: str, bit_depth: int, chroma: bool = False):
+    """(a, b) of the fixed map dis = a * ref + b, as Fractions, s = 2^(bit_depth - 8):
+    identity a = 1, b = 0;  limited_to_full luma a = 255/219, b = -16 s * 255/219, chroma a = 255/224 about 128 s;
+    full_to_limited luma a = 219/255, b = 16 s, chroma a = 224/255 about 128 s."""
+    s = 1 << (int(bit_depth) - 8)
+    if name == "identity":
+        return Fraction(1), Fraction(0)
+    if name not in LEVEL_MAPS:
+        raise ValueError(f"unknown level map {name!r}")
+    if chroma:
+        a = Fraction(255, 224) if name == "limited_to_full" else Fraction(224, 255)
+        return a, 128 * s * (1 - a)
+    if name == "limited_to_full":
+        return Fraction(255, 219), Fraction(-16 * s * 255, 219)
+    return Fraction(219, 255), Fraction(16 * s)
+
+
+def _fit(levels, T0, T1):
+    """least-squares (a, b) of dis = a * ref + b over `levels` from the counts and sums; None when no slope can be formed"""
+    n = sum(T0[v] for v in levels)
+    sr = sum(v * T0[v] for v in levels)
+    sd = sum(T1[v] for v in levels)
+    srr = sum(v * v * T0[v] for v in levels)
+    srd = sum(v * T1[v] for v in levels)
+    den = n * srr - sr * sr
+    if n == 0 or den == 0:
+        return None
+    a = Fraction(n * srd - sr * sd, den)
+    return a, (Fraction(sd) - a * sr) / n
+
+
+def _map_sse(a, b, top, T0, T1, T2):
+    """sum over the pixels of (dis - clamp(a * ref + b, 0, top))^2, exact: what is left when the capture chain applied the
+    map and clipped to its range"""
+    sse = Fraction(0)
+    for v, c in enumerate(T0):
+        if c:
+            p = min(max(a * v + b, 0), top)
+            sse += T2[v] - 2 * p * T1[v] + p * p * c
+    return sse
+
+
+def best_levels(T, bit_depth: int, *, chroma: bool = False, min_improvement: float = 2.0, snap: float = 1.25) -> dict:
+    """The level mapping of a captured plane from T[n_frames][L][3] (pqa_level_stats; L = 2^bit_depth): T[f][v] = (count, sum
+    of dis, sum of dis^2) over the pixels whose reference sample is v.  The frames are pooled; everything below is Python
+    ints and Fractions, converted to float only in the result.  top = L - 1.
+
+    gain, offset: the least-squares a, b of dis = a * ref + b from the joint moments, refitted once over only those populated
+    reference levels whose predicted captured value a * v + b lies in [1, top - 1], so that clipping at 0 or top does not
+    bias the fit (the first fit is kept when fewer than two such levels remain).  levels_used = the levels of the final fit.
+    The MSE of a map (a, b) is taken against clamp(a * v + b, 0, top).  mse_identity; mse_affine (the fitted map);
+    mse_curve = sum_v (T2 - T1^2 / T0) / N, the residual about the conditional mean: the floor any per-level correction
+    could reach.  named = {identity, limited_to_full, full_to_limited: MSE under named_level_map()}.
+    kind = the named map with the smallest MSE (ties: the order above), or "affine" when that MSE exceeds snap * mse_affine.
+    mismatch = mse_identity > min_improvement * (MSE of the chosen map).  map_gain / map_offset = the chosen map's a, b (the
+    named map's own values, or the fitted ones): what correction_lut() undoes.
+    degenerate = fewer than two reference levels are populated: no fit is made, gain = 1, offset = 0, kind = "identity",
+    mismatch false.  frames = n_frames."""
+    T = np.asarray(T)
+    L = 1 << int(bit_depth)
+    if T.ndim != 3 or T.shape[0] < 1 or T.shape[1:] != (L, 3):
+        raise ValueError("T must be [n_frames >= 1, 2^bit_depth, 3]")
+    top = L - 1
+    T0, T1, T2 = ([sum(int(x) for x in T[:, v, k]) for v in range(L)] for k in range(3))
+    n_pix = sum(T0)
+    if n_pix == 0:
+        raise ValueError("T counts no pixel")
+    populated = [v for v in range(L) if T0[v]]
+
+    def mse(a, b):
+        return _map_sse(a, b, top, T0, T1, T2) / n_pix
+    named = {k: mse(*named_level_map(k, bit_depth, chroma)) for k in LEVEL_MAPS}
+    curve = sum(Fraction(T2[v]) - Fraction(T1[v] * T1[v], T0[v]) for v in populated) / n_pix
+    fit = _fit(populated, T0, T1) if len(populated) >= 2 else None
+    degenerate = fit is None
+    used = populated
+    if degenerate:
+        a, b = Fraction(1), Fraction(0)
+    else:
+        a, b = fit
+        inside = [v for v in populated if 1 <= a * v + b <= top - 1]
+        refit = _fit(inside, T0, T1) if len(inside) >= 2 else None
+        if refit is not None:
+            (a, b), used = refit, inside
+    mse_affine = mse(a, b)
+    kind = "identity" if degenerate else min(LEVEL_MAPS, key=lambda k: named[k])     # min keeps the first of equals
+    chosen = named[kind]
+    if not degenerate and chosen > Fraction(snap) * mse_affine:
+        kind, chosen = "affine", mse_affine
+    ma, mb = (a, b) if kind == "affine" else named_level_map(kind, bit_depth, chroma)
+    return {"gain": float(a), "offset": float(b), "kind": kind,
+            "mismatch": bool(not degenerate and named["identity"] > Fraction(min_improvement) * chosen),
+            "mse_identity": float(named["identity"]), "mse_affine": float(mse_affine), "mse_curve": float(curve),
+            "named": {k: float(x) for k, x in named.items()}, "map_gain": float(ma), "map_offset": float(mb),
+            "levels_used": len(used), "frames": int(T.shape[0]), "degenerate": bool(degenerate)}
+
+
+def level_lut(gain, offset, bit_depth: int) -> np.ndarray:
+    """The inverse of dis = gain * ref + offset as an integer table over the captured levels:
+    lut[d] = clamp(floor((d - offset) / gain + 1/2), 0, top), top = 2^bit_depth - 1, computed in Fractions (a float argument
+    is taken at its exact binary value; pass named_level_map()'s Fractions for a named map).  uint8 at 8 bit, else uint16."""
+    a, b = Fraction(gain), Fraction(offset)
+    if a <= 0:
+        raise ValueError("level_lut needs a positive gain")
+    top = (1 << int(bit_depth)) - 1
+    half = Fraction(1, 2)
+    lut = [min(max(((d - b) / a + half).__floor__(), 0), top) for d in range(top + 1)]
+    return np.asarray(lut, np.uint8 if bit_depth <= 8 else np.uint16)
+
+
+def correction_lut(levels: dict, bit_depth: int, chroma: bool = False) -> np.ndarray:
+    """level_lut() of the map a best_levels() result chose: a named kind with its exact a and b, "affine" with the fit"""
+    if levels["kind"] in LEVEL_MAPS:
+        return level_lut(*named_level_map(levels["kind"], bit_depth, chroma), bit_depth)
+    return level_lut(levels["gain"], levels["offset"], bit_depth)

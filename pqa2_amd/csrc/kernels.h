@@ -410,5 +410,15 @@ hipError_t launch_shift_sse(hipStream_t stream, Elem elem, const void* ref, int6
                             const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int n_frames, int w, int h, int R,
                             void* part, unsigned long long* rowsq, unsigned long long* out);
 
+// ---- level alignment: per-level transfer table (level_stats.hip) ---------------------------------------------------------
+// out[f][v][0 / 1 / 2] = count / sum of dis / sum of dis^2 over the pixels of frame pair f whose reference sample is v (above
+// L - 1: bin L - 1), L = 2^bit_depth, exact uint64, for n_frames pairs of one w x h plane (frame f at base + f * frame_pitch,
+// pitches in elements).  out: device memory of level_out_bytes(bit_depth, n_frames), zeroed by the launch.
+constexpr int kLevelChunk = 8;   // frame pairs per launch of the two entries
+size_t level_out_bytes(int bit_depth, int n_frames);
+hipError_t launch_level_stats(hipStream_t stream, Elem elem, int bit_depth, const void* ref, int64_t ref_row_pitch,
+                              int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                              int n_frames, int w, int h, unsigned long long* out);
+
 }  // namespace pqa
 

@@ -183,8 +183,9 @@ struct pqa_ctx {
   uint32_t luma_gray = PQA_GRAY_LUMA;
   // temporal alignment (pqa_cross_sse / pqa_cross_sse_device; cross_sse.hip): grow-only buffers, allocated on first use
   bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
-  void* xs_buf[9] = {};              // XS_* below (the last three: pqa_shift_sse / pqa_shift_sse_device; shift_sse.hip)
-  size_t xs_cap[9] = {};             // their sizes in bytes
+  void* xs_buf[10] = {};             // XS_* below (XS_SH_*: pqa_shift_sse / pqa_shift_sse_device, shift_sse.hip; XS_LV_OUT: pqa_level_stats /
+                                     // pqa_level_stats_device, level_stats.hip)
+  size_t xs_cap[10] = {};            // their sizes in bytes
   // motion continuity
   uint8_t* last_luma = nullptr;
   int64_t last_luma_pitch = 0;  // bytes
@@ -2208,7 +2209,7 @@ int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_strid
 }
 
 namespace {
-enum { XS_PART = 0, XS_NORM_REF, XS_NORM_DIS, XS_OUT, XS_REF, XS_DIS, XS_SH_PART, XS_SH_ROWSQ, XS_SH_OUT };
+enum { XS_PART = 0, XS_NORM_REF, XS_NORM_DIS, XS_OUT, XS_REF, XS_DIS, XS_SH_PART, XS_SH_ROWSQ, XS_SH_OUT, XS_LV_OUT };
 
 // a grow-only device buffer of the cross-SSE calls
 int xs_reserve(pqa_ctx* c, int which, size_t bytes) {
@@ -2467,6 +2468,97 @@ int pqa_shift_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_str
   const hipError_t es2 = hipStreamSynchronize(c->stream);
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (e != hipSuccess) return fail(c, PQA_EDEVICE, "shift_sse failed: %s", hipGetErrorString(e));
+  if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
+  return PQA_OK;
+}
+
+namespace {
+// the argument rules the two level entries share; no device call
+int lv_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int32_t plane, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "level_stats: negative frame count");
+  if (plane < 0 || plane >= c->n_planes) return fail(c, PQA_EINVAL, "level_stats: plane %d of a context with %d", plane, c->n_planes);
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "level_stats: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "level_stats: null output pointer");
+  return PQA_OK;
+}
+}  // namespace
+
+int pqa_level_bins(const pqa_ctx* c) { return c ? 1 << c->cfg.bit_depth : PQA_EINVAL; }
+
+int pqa_level_stats_device(pqa_ctx* c, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
+                           int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t plane, uint64_t* out) {
+  const int chk = lv_check(c, ref, dis, n_frames, plane, out);
+  if (chk != PQA_OK) return chk;
+  if (n_frames == 0) return PQA_OK;
+  const int es = c->esize, bpc = (int)c->cfg.bit_depth;
+  const int64_t row_bytes = (int64_t)c->pw[plane] * es;
+  if (ref_row_pitch % es || ref_frame_pitch % es || dis_row_pitch % es || dis_frame_pitch % es)
+    return fail(c, PQA_EINVAL, "level_stats: pitch is not a multiple of the sample size");
+  if (ref_row_pitch < row_bytes || dis_row_pitch < row_bytes) return fail(c, PQA_EINVAL, "level_stats: pitch smaller than a row");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = xs_reserve(c, XS_LV_OUT, level_out_bytes(bpc, n_frames));
+  if (rc != PQA_OK) return rc;
+  const size_t n = (size_t)3 << bpc;
+  auto* dev_out = (unsigned long long*)c->xs_buf[XS_LV_OUT];
+  for (int f0 = 0; f0 < n_frames; f0 += kLevelChunk) {
+    const int m = n_frames - f0 < kLevelChunk ? n_frames - f0 : kLevelChunk;
+    HIPCHK(c, launch_level_stats(c->stream, c->elem, bpc, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
+                                 ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
+                                 dis_frame_pitch / es, m, c->pw[plane], c->ph[plane], dev_out + (size_t)f0 * n));
+  }
+  HIPCHK(c, hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PQA_OK;
+}
+
+int pqa_level_stats(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
+                    int64_t dis_row_stride, int32_t n_frames, int32_t plane, uint64_t* out) {
+  const int chk = lv_check(c, ref_frames, dis_frames, n_frames, plane, out);
+  if (chk != PQA_OK) return chk;
+  if (n_frames == 0) return PQA_OK;
+  const size_t row_bytes = (size_t)c->pw[plane] * c->esize;
+  if (ref_row_stride < 0 || dis_row_stride < 0 || (size_t)ref_row_stride < row_bytes || (size_t)dis_row_stride < row_bytes)
+    return fail(c, PQA_EINVAL, "level_stats: stride smaller than a row");
+  for (int f = 0; f < n_frames; ++f)   // before anything is queued
+    if (!ref_frames[f] || !dis_frames[f]) return fail(c, PQA_EINVAL, "level_stats: frame %d pointer is null", f);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int bpc = (int)c->cfg.bit_depth;
+  int rc = luma_staging_ensure(c);
+  if (rc == PQA_OK) rc = xs_reserve(c, XS_LV_OUT, level_out_bytes(bpc, n_frames));
+  if (rc != PQA_OK) return rc;
+  // a chroma plane is no larger than the luma plane, so it travels through the luma staging with the luma pitches
+  const int w = c->pw[plane], h = c->ph[plane], es = c->esize;
+  const size_t frame_bytes = (size_t)c->luma_pitch * c->ph[0], n = (size_t)3 << bpc;
+  auto* dev_out = (unsigned long long*)c->xs_buf[XS_LV_OUT];
+  // chunks of LB (<= kLevelChunk) pairs, staged as in pqa_shift_sse: reference frames through half 0, captured ones through half 1
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += c->LB) {
+    if (c->cancelled.load()) break;
+    const int m = n_frames - f0 < c->LB ? n_frames - f0 : c->LB;
+    for (int hf = 0; hf < 2 && e == hipSuccess; ++hf) {
+      const void* const* frames = hf ? dis_frames : ref_frames;
+      const int64_t stride = hf ? dis_row_stride : ref_row_stride;
+      if (f0 > 0) e = hipEventSynchronize(c->luma_copied[hf]);
+      if (e != hipSuccess) break;
+      for (int f = 0; f < m; ++f)
+        copy_plane_rows(c->luma_pinned[hf] + (size_t)f * frame_bytes, c->luma_pitch, (const uint8_t*)frames[f0 + f], stride,
+                        row_bytes, h);
+      e = hipMemcpyAsync(c->luma_dev[hf], c->luma_pinned[hf], (size_t)m * frame_bytes, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
+    }
+    if (e == hipSuccess)
+      e = launch_level_stats(c->stream, c->elem, bpc, c->luma_dev[0], c->luma_pitch / es, (int64_t)(frame_bytes / es),
+                             c->luma_dev[1], c->luma_pitch / es, (int64_t)(frame_bytes / es), m, w, h, dev_out + (size_t)f0 * n);
+  }
+  if (e == hipSuccess && !c->cancelled.load())
+    e = hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+  // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
+  const hipError_t es2 = hipStreamSynchronize(c->stream);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "level_stats failed: %s", hipGetErrorString(e));
   if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
   return PQA_OK;
 }

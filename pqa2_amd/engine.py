@@ -57,6 +57,7 @@ class FeatureEngine:
         cfg.bit_depth = bit_depth
         cfg.n_planes = n_planes
         cfg.chroma_hshift, cfg.chroma_vshift = chroma_shift
+        self.chroma_shift = (int(chroma_shift[0]), int(chroma_shift[1]))
         cfg.features = features
         cfg.max_batch = max_batch
         cfg.result_capacity = result_capacity
@@ -306,18 +307,19 @@ class FeatureEngine:
         return out
 
     # -- temporal alignment ------------------------------------------------------------------
-    def _luma_list(self, frames, what: str):
-        """(arrays kept alive, ctypes pointer array, common row stride) of luma planes in host memory"""
+    def _luma_list(self, frames, what: str, shape=None):
+        """(arrays kept alive, ctypes pointer array, common row stride) of luma planes (or planes of `shape`) in host memory"""
+        shape = shape or (self.height, self.width)
         arrs = [np.asarray(f) for f in frames]
         strides = {a.strides[0] for a in arrs if a.ndim == 2}
         if any(a.ndim != 2 or a.dtype != self.dtype or a.strides[1] != a.itemsize for a in arrs) or len(strides) > 1:
             arrs = [np.ascontiguousarray(a, dtype=self.dtype) for a in arrs]
         ptrs = (C.c_void_p * max(len(arrs), 1))()
         for i, a in enumerate(arrs):
-            if a.shape != (self.height, self.width):
-                raise ValueError(f"{what} frame {i} is {a.shape}, engine is {(self.height, self.width)}")
+            if a.shape != shape:
+                raise ValueError(f"{what} frame {i} is {a.shape}, engine is {shape}")
             ptrs[i] = a.ctypes.data
-        return arrs, ptrs, (arrs[0].strides[0] if arrs else self.width * np.dtype(self.dtype).itemsize)
+        return arrs, ptrs, (arrs[0].strides[0] if arrs else shape[1] * np.dtype(self.dtype).itemsize)
 
     def cross_sse(self, ref_lumas, dis_lumas, k_lo: int, k_hi: int) -> np.ndarray:
         """[n_ref, k_hi - k_lo + 1] uint64: D[i][c] = sum (ref_i - dis_{i + k_lo + c})^2 over the luma plane, exact;
@@ -364,6 +366,37 @@ class FeatureEngine:
         out = np.zeros((max(int(n_frames), 0), side, side), np.uint64)
         self._check(self.lib.pqa_shift_sse_device(self._ctx, ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch,
                                                   dis_frame_pitch, int(n_frames), R, out.ctypes.data))
+        return out
+
+    # -- level alignment ---------------------------------------------------------------------
+    def plane_shape(self, plane: int):
+        """(height, width) of plane 0 / 1 / 2 of this context in samples (chroma from chroma_shift, rounded up)"""
+        if plane == 0:
+            return (self.height, self.width)
+        hs, vs = self.chroma_shift
+        return ((self.height + (1 << vs) - 1) >> vs, (self.width + (1 << hs) - 1) >> hs)
+
+    def level_stats(self, ref_frames, dis_frames, plane: int = 0) -> np.ndarray:
+        """[n, L, 3] uint64, L = 2^bit_depth: T[f][v] = (count, sum of dis, sum of dis^2) over the pixels of pair f whose
+        reference sample is v, exact (pqa_level_stats).  Planes in HOST memory (two lists of 2-D arrays of equal length,
+        each of the size of `plane` of this context).  align.best_levels reads the result."""
+        n, plane = len(ref_frames), int(plane)
+        if len(dis_frames) != n:
+            raise N.PqaError(N.PQA_EINVAL, "level_stats needs as many captured as reference frames")
+        out = np.zeros((n, 1 << self.bit_depth, 3), np.uint64)
+        shape = self.plane_shape(plane) if 0 <= plane < self.n_planes else None   # a bad plane is the library's to refuse
+        keep_r, rp, rs = self._luma_list(ref_frames if shape else [], "reference", shape)
+        keep_d, dp, ds = self._luma_list(dis_frames if shape else [], "captured", shape)
+        self._check(self.lib.pqa_level_stats(self._ctx, rp, rs, dp, ds, n, plane, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def level_stats_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                             dis_frame_pitch: int, n_frames: int, plane: int = 0) -> np.ndarray:
+        """The same for two clips in HBM (device pointers, pitches in bytes; pqa_level_stats_device)."""
+        out = np.zeros((max(int(n_frames), 0), 1 << self.bit_depth, 3), np.uint64)
+        self._check(self.lib.pqa_level_stats_device(self._ctx, ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch,
+                                                    dis_frame_pitch, int(n_frames), int(plane), out.ctypes.data))
         return out
 
     # -- results -----------------------------------------------------------------------------

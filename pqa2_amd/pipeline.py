@@ -33,7 +33,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False,
                 integrity: bool = False, integrity_options=None, align: int = 0,
                 align_frames: int | None = None, align_penalty_mse: float | None = None, spatial_align: int = 0,
-                spatial_frames: int = 8) -> ScoreResult | None:
+                spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -69,7 +69,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     the reference from (max(0, -dx), max(0, -dy)), the capture from that origin moved by (dx, dy), chroma planes from
     `origin >> shift` of each clip.  `chroma_exact` is false when dx or dy is no multiple of the chroma subsampling: chroma
     is then paired half a chroma sample off.  Scaling and sub-pixel displacement are not corrected.
-    `spatial_align` = 0: no search, pixel (x, y) meets pixel (x, y)."""
+    `spatial_align` = 0: no search, pixel (x, y) meets pixel (x, y).
+    `level_align` = "report" or "apply": before scoring (after the temporal and spatial steps, on the pairs and the window
+    they produced), the per-level transfer table of `level_frames` pairs spread evenly over the common range
+    (pqa_level_stats) is reduced, for every plane the clips have, to the gain and offset of the captured samples and the
+    named range conversion they amount to (align.best_levels).  `alignment["levels"]` holds the luma result {gain, offset,
+    kind, mismatch, mse_identity, mse_affine, mse_curve, named, map_gain, map_offset, levels_used, frames, degenerate,
+    applied} and the same for every plane under `planes` ("y", "u", "v").  "report" changes nothing else: the records are
+    those of a run without the option.  "apply" maps every captured plane whose `mismatch` is true through the integer table
+    that undoes its chosen map (align.correction_lut, numpy.take on the host) before it is scored; `applied` says so per
+    plane.  `level_align` = None: no measurement."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -101,6 +110,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         if spatial["applied"]:
             ref_rd, dis_rd = crop_readers(ref_rd, dis_rd, spatial["dx"], spatial["dy"])
             ri, di = ref_rd.info, dis_rd.info
+    if level_align is not None:
+        if level_align not in ("report", "apply"):
+            raise ValueError('level_align must be None, "report" or "apply"')
+        if level_frames is None or level_frames < 1:
+            raise ValueError("level_frames must be positive")
+        levels, luts = _find_levels(ref_rd, dis_rd, int(level_frames), level_align == "apply", device,
+                                    engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+        alignment = dict(alignment or {}, levels=levels)
+        if any(lut is not None for lut in luts):
+            dis_rd = _LevelledReader(dis_rd, luts)
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
@@ -322,6 +341,49 @@ def crop_readers(ref_rd, dis_rd, dx: int, dy: int):
     w, h = ref_rd.info.width - abs(dx), ref_rd.info.height - abs(dy)
     x0, y0 = max(0, -dx), max(0, -dy)
     return _CroppedReader(ref_rd, x0, y0, w, h), _CroppedReader(dis_rd, x0 + dx, y0 + dy, w, h)
+
+
+class _LevelledReader:
+    """A captured clip with its sample levels mapped back onto the reference's: plane p of every frame goes through the
+    integer table luts[p] (numpy.take; None: the plane is passed on as it is).  What score_files reads under
+    level_align="apply".  No file-descriptor path: the mapped samples exist in host arrays only, so the frames go down
+    through FeatureEngine.submit."""
+
+    def __init__(self, reader, luts):
+        self._rd, self._luts = reader, list(luts)
+        self.info = reader.info
+
+    def __len__(self):
+        return len(self._rd)
+
+    def frame(self, i: int):
+        planes = self._rd.frame(i)
+        return [p if k >= len(self._luts) or self._luts[k] is None else np.take(self._luts[k], p) for k, p in enumerate(planes)]
+
+
+def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make):
+    """(the `levels` object, [a correction table or None per plane]) of two opened, paired clips: the per-level transfer
+    table of a few pairs of every plane on a small context of its own"""
+    from . import align as AL
+    ri = ref_rd.info
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError("no frames to align")
+    n_planes = 1 if ri.mono else 3
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=n_planes, chroma_shift=(ri.hshift, ri.vshift),
+               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+    try:
+        refs, caps = [ref_rd.frame(i) for i in idx], [dis_rd.frame(i) for i in idx]
+        tables = [eng.level_stats([f[p] for f in refs], [f[p] for f in caps], p) for p in range(n_planes)]
+    finally:
+        eng.close()
+    planes, luts = {}, []
+    for p, T in enumerate(tables):
+        lv = AL.best_levels(T, ri.bit_depth, chroma=p > 0)
+        lv["applied"] = bool(apply and lv["mismatch"])
+        luts.append(AL.correction_lut(lv, ri.bit_depth, chroma=p > 0) if lv["applied"] else None)
+        planes["yuv"[p]] = lv
+    return dict(planes["y"], planes=planes), luts
 
 
 def spatial_sample(n: int, count: int):

@@ -99,6 +99,11 @@ def alignment_log_keys(alignment: dict | None) -> dict:
     out = finite(alignment) if "confidence" in alignment else dict(alignment)
     if alignment.get("spatial"):
         out["spatial"] = finite(alignment["spatial"])
+    if alignment.get("levels"):   # no confidence there; any float that is not finite becomes null, per-plane results included
+        def finite_all(obj):
+            return {k: finite_all(v) if isinstance(v, dict) else (None if isinstance(v, float) and not np.isfinite(v) else v)
+                    for k, v in obj.items()}
+        out["levels"] = finite_all(alignment["levels"])
     return {"alignment": out}
 
 
@@ -127,6 +132,24 @@ def spatial_summary_line(spatial: dict) -> str:
     return (f"Spatial alignment: capture displaced by ({int(spatial['dx']):+d}, {int(spatial['dy']):+d}) px, MSE "
             f"{spatial.get('mse', 0.0):.2f}, {conf_s}, agreement {100.0 * spatial.get('agreement', 0.0):.0f} % of "
             f"{spatial.get('frames', 0)} frames, searched +-{spatial.get('searched')} px, {what}")
+
+
+def levels_summary_line(levels: dict) -> str:
+    """One line for a summary or a status bar: the level mapping found for luma, its error and whether it was undone."""
+    if levels.get("degenerate"):
+        return f"Level alignment: flat reference in {levels.get('frames', 0)} frames: no mapping measured"
+    kind = levels.get("kind", "identity")
+    what = {"identity": "levels in place", "limited_to_full": "capture expanded from limited to full range",
+            "full_to_limited": "capture compressed from full to limited range"}.get(kind, "capture levels scaled and offset")
+    planes = levels.get("planes") or {"y": levels}
+    done = [k for k in planes if planes[k].get("applied")]
+    if done:
+        tail = "corrected on " + ", ".join(k.upper() for k in done)
+    else:
+        tail = "not corrected" if levels.get("mismatch") else "nothing to correct"
+    return (f"Level alignment: {what} (gain {levels.get('gain', 1.0):.4f}, offset {levels.get('offset', 0.0):+.2f}), MSE "
+            f"{levels.get('mse_identity', 0.0):.2f} as captured, {levels.get('mse_affine', 0.0):.2f} after the fit, "
+            f"{levels.get('frames', 0)} frames, {tail}")
 
 
 def build_vmaf_log(metrics: dict, fps: float, frame_indices=None, extra_top: dict | None = None) -> dict:

@@ -95,6 +95,13 @@ def main(argv=None) -> int:
                          "alignment object gets a spatial entry")
     ap.add_argument("--spatial-frames", type=int, default=8, metavar="N",
                     help="with --spatial-align: search N frame pairs spread evenly over the clips (default 8)")
+    ap.add_argument("--level-align", action="store_true",
+                    help="measure the level mapping of the capture (gain, offset, limited / full range conversion) from the "
+                         "per-level transfer table of a few frame pairs; the JSON's alignment object gets a levels entry")
+    ap.add_argument("--level-correct", action="store_true",
+                    help="--level-align, and undo a mapping found on every plane that has one before scoring")
+    ap.add_argument("--level-frames", type=int, default=8, metavar="N",
+                    help="with --level-align / --level-correct: measure N frame pairs spread evenly over the clips (default 8)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -140,6 +147,8 @@ def main(argv=None) -> int:
                           **({"siti": True} if a.siti else {}),
                           **({"align": a.align, "align_frames": a.align_frames} if a.align else {}),
                           **({"spatial_align": a.spatial_align, "spatial_frames": a.spatial_frames} if a.spatial_align else {}),
+                          **({"level_align": "apply" if a.level_correct else "report", "level_frames": a.level_frames}
+                             if (a.level_align or a.level_correct) else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
@@ -171,6 +180,8 @@ def main(argv=None) -> int:
             print(report.alignment_summary_line(res["alignment"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("spatial"):
             print(report.spatial_summary_line(res["alignment"]["spatial"]), file=sys.stderr, flush=True)
+        if res.get("alignment") and res["alignment"].get("levels"):
+            print(report.levels_summary_line(res["alignment"]["levels"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

@@ -163,6 +163,8 @@ class VMAFAnalyzer(QObject):
         self.align_max_offset = 8             # -align_max_offset ... align_max_offset frames (pipeline.score_files(align=))
         self.spatial_align_enabled = False    # spatial alignment before scoring: search the capture's displacement over
         self.spatial_align_radius = 8         # -radius ... radius pixels in x and y (pipeline.score_files(spatial_align=))
+        self.level_align_enabled = False      # level alignment before scoring: measure the capture's gain / offset / range
+        self.level_correct_enabled = False    # ... and undo it (implies the measurement; pipeline.score_files(level_align=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -207,6 +209,10 @@ class VMAFAnalyzer(QObject):
                 self.spatial_align_enabled = bool(s["spatial_align_enabled"])
             if "spatial_align_radius" in s:
                 self.spatial_align_radius = max(1, min(16, int(s["spatial_align_radius"])))
+            if "level_align_enabled" in s:
+                self.level_align_enabled = bool(s["level_align_enabled"])
+            if "level_correct_enabled" in s:
+                self.level_correct_enabled = bool(s["level_correct_enabled"])
 
     set_options_manager = set_options_from_manager
 
@@ -224,7 +230,7 @@ class VMAFAnalyzer(QObject):
                              cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False,
                              siti_enabled=False, integrity_enabled=False, integrity_options=None,
                              align_enabled=False, align_max_offset=8, spatial_align_enabled=False,
-                             spatial_align_radius=8):
+                             spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -245,6 +251,8 @@ class VMAFAnalyzer(QObject):
         self.align_max_offset = max(1, min(64, int(align_max_offset)))
         self.spatial_align_enabled = bool(spatial_align_enabled)
         self.spatial_align_radius = max(1, min(16, int(spatial_align_radius)))
+        self.level_align_enabled = bool(level_align_enabled)
+        self.level_correct_enabled = bool(level_correct_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -451,7 +459,9 @@ class VMAFAnalyzer(QObject):
                 **({"siti": True} if self.siti_enabled else {}),
                 **({"integrity": True, "integrity_options": dict(self.integrity_options)} if self.integrity_enabled else {}),
                 **({"align": int(self.align_max_offset)} if self.align_enabled else {}),
-                **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {})}
+                **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {}),
+                **({"level_align": "apply" if self.level_correct_enabled else "report"}
+                   if (self.level_align_enabled or self.level_correct_enabled) else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -488,6 +498,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--align", str(int(self.align_max_offset))]
         if self.spatial_align_enabled:
             cmd += ["--spatial-align", str(int(self.spatial_align_radius))]
+        if self.level_correct_enabled:
+            cmd += ["--level-correct"]
+        elif self.level_align_enabled:
+            cmd += ["--level-align"]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -602,13 +616,16 @@ class VMAFAnalyzer(QObject):
             if self.integrity_enabled:   # the event lists, from the log's top level
                 results["integrity"] = vmaf_data.get("integrity")
                 results["integrity_log"] = self._integrity_path
-            if self.align_enabled or self.spatial_align_enabled:   # how the clips were paired, from the log's top level
+            if (self.align_enabled or self.spatial_align_enabled or self.level_align_enabled
+                    or self.level_correct_enabled):   # how the clips were paired, from the log's top level
                 from . import report
                 results["alignment"] = vmaf_data.get("alignment")
                 if results["alignment"] and "offset_frames" in results["alignment"]:
                     self.status_update.emit(report.alignment_summary_line(results["alignment"]))
                 if results["alignment"] and results["alignment"].get("spatial"):
                     self.status_update.emit(report.spatial_summary_line(results["alignment"]["spatial"]))
+                if results["alignment"] and results["alignment"].get("levels"):
+                    self.status_update.emit(report.levels_summary_line(results["alignment"]["levels"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
