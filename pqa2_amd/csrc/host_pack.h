@@ -1,6 +1,6 @@
 // Host side of the staging path, free of any device call: packing frames -- from memory planes or straight out of files -- into
 // (pinned) staging slots with a small persistent thread pool.  Header-only and plain C++17 so that a CPU harness can drive it
-// under ThreadSanitizer / AddressSanitizer (tests/host_harness.cpp, pytest -m "not gpu"); pqa_api.hip includes it as is.
+// under ThreadSanitizer / AddressSanitizer (tests/host_harness.cpp, pytest -m "not gpu"); pqa_ctx.h includes it as is.
 #pragma once
 #include <atomic>
 #include <cerrno>

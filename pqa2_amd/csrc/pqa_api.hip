@@ -1,58 +1,34 @@
-// C ABI of libpqa_vmaf.so: context, workspaces, batching, host staging, profiling hooks.
+// C ABI of libpqa_vmaf.so: context lifetime, workspaces, batching, the submit paths and their host staging, collect,
+// profiling hooks.  The one-shot analyses beside the scoring chain: pqa_side.hip; the pqa_debug_* entries: pqa_debug.hip.
 // Declarations and the reference interfaces each entry point replaces: include/pqa_vmaf.h.
-#include "../../include/pqa_vmaf.h"
+#include "pqa_ctx.h"
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <memory>
 #include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include <cerrno>
-#include <unistd.h>
-
-#include "host_pack.h"
-#include "host_ring.h"
 #include "ingest.h"
-#include "kernels.h"
 
 using namespace pqa;
 using pqa::host::PackPool;
 using pqa::host::PackTask;
 using pqa::host::run_pack_task;
 
+static thread_local std::string g_create_error;   // pqa_last_error(NULL): what pqa_create and the pqa_debug_* entries report
+
+int pqa::fail(pqa_ctx* c, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (c) c->err = buf; else g_create_error = buf;
+  return code;
+}
+
 namespace {
-
-thread_local std::string g_create_error;
-
-struct Level {
-  int w = 0, h = 0;
-  int64_t pitch = 0, frame_pitch = 0;  // elements (float)
-  float* ref = nullptr;
-  float* dis = nullptr;
-};
-
-struct Half {
-  uint8_t* pinned = nullptr;
-  uint8_t* dev = nullptr;
-  hipEvent_t copied = nullptr, computed = nullptr;
-  bool copied_pending = false, computed_pending = false;
-};
-
-struct ProfEv {
-  hipEvent_t a, b;
-  int id, frames;
-};
-
-constexpr int kBatchEvents = 64;  // ring of per-batch completion events
-constexpr int kLumaOutFrames = 2048;  // luma statistics kept on the device between host copies
 
 // Staging buffers of the host path outlive their context: pinning 2 x 200 MB (2160p 4:2:0, 8 frames) and releasing it again
 // costs ~55 ms per context -- more than scoring a 48-frame 2160p clip -- and the reference's caller makes a fresh analyzer
@@ -81,184 +57,6 @@ void staging_release(StagingSet& s) {   // caller holds the lock or owns s; the 
   s.bytes = 0;
   s.device = -1;
 }
-
-}  // namespace
-
-struct pqa_ctx {
-  pqa_config cfg{};
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr, copy_stream = nullptr;
-  hipStream_t aux[2] = {nullptr, nullptr};  // ADM and motion/PSNR/SSIM chains run beside the VIF chain
-  hipEvent_t fork_ev = nullptr, join_ev[2] = {nullptr, nullptr};
-  Elem elem = ELEM_U8;
-  int esize = 1;
-  float inv_scale = 1.0f;
-  int pw[3] = {0, 0, 0}, ph[3] = {0, 0, 0};
-  int n_planes = 1;
-  int B = 8, HB = 8, capacity = 16384, k_sub = 1;  // B: frames per launch; HB: frames per host-staging half
-  Level vif_lv[4], adm_lv[4];
-  double* vif_part[4] = {};
-  long long* vif_fx_part[4] = {};  // fixed-point VIF: int64 partials instead of (num, den) doubles
-  uint16_t* vif_lut = nullptr;     // integer_vif.c's log2 table, entries 32768..65535
-  bool vif_fixed = false, motion_fixed = false, adm_fixed = false;
-  long long* adm_fx_part[4] = {};   // fixed-point ADM: per-row int64 partials
-  long long* adm_fx_acc = nullptr;  // [capacity][4][6] ring of accumulators, finished on the host in pqa_collect
-  int32_t* adm_div_lut = nullptr;
-  AdmFxScale adm_fx[4] = {};
-  unsigned long long* motion_fx_part = nullptr;
-  int vif_tiles[4] = {};
-  int vif_part_cap0 = 0;   // partial pairs per frame the scale-0 buffer holds (tiled kernels or the march kernel)
-  double* adm_part[4] = {};
-  int adm_tiles[4] = {};
-  float adm_area[4] = {};
-  double* motion_part = nullptr;
-  int motion_tiles_n = 0;
-  unsigned long long* sse_part[3] = {};
-  unsigned long long* sse_part_b[3] = {};
-  unsigned long long* sse_tile_part[3] = {};
-  double* ssim_part[3] = {};
-  int ssim_tiles_n[3] = {};
-  double ssim_norm[3] = {};
-  double* records = nullptr;
-  // SSIM family (PQA_FEAT_FLOAT_SSIM / PQA_FEAT_MS_SSIM; ssim_family.hip): nothing is allocated unless one of the bits is set
-  double* ext = nullptr;             // [capacity][PQA_EXT_DOUBLES] ring beside `records`
-  Level ms_lv[kMsScales];            // MS-SSIM scales 1..4: f32 planes for ssf_sb frames
-  double* ms_part[kMsScales] = {};   // [ssf_sb][tiles][4] per scale
-  int ms_tiles[kMsScales] = {};
-  double* fs_part = nullptr;         // float_ssim: [ssf_sb][tiles][4]
-  int fs_tiles = 0, fs_box = 1;
-  int ssf_sb = 0;                    // frames per pass through the pyramid (bounds its memory at 2160p)
-  // CIEDE2000 (PQA_FEAT_CIEDE; ciede.hip): nothing is allocated unless the bit is set
-  double* ciede_part = nullptr;      // [B][ciede_tiles]
-  int ciede_tiles_n = 0;
-  // CAMBI (PQA_FEAT_CAMBI; cambi.hip): nothing is allocated unless the bit is set
-  CambiParams cambi_prm{};
-  CambiWork cambi_wk{};
-  int cambi_sb = 0;                  // frames per pass (bounds the work planes at 2160p)
-  // PSNR-HVS (PQA_FEAT_PSNR_HVS; psnr_hvs.hip): nothing is allocated unless the bit is set
-  double* ext2 = nullptr;            // [capacity][PQA_EXT2_DOUBLES] ring beside `records`
-  PsnrHvsGeometry phv_geo{};
-  double* phv_part = nullptr;        // [B][phv_geo.tile0[3]]
-  // XPSNR (PQA_FEAT_XPSNR; xpsnr.hip): nothing is allocated unless the bit is set
-  double* ext3 = nullptr;            // [capacity][PQA_EXT3_DOUBLES] ring beside `records`
-  XpsnrGeometry xp_geo{};
-  unsigned long long* xp_blk = nullptr;   // [B][xp_geo.n_blk][kXpBlockVals]
-  double* xp_w = nullptr;                 // [B][xp_geo.n_blk] weights
-  uint8_t* xp_hist[2] = {nullptr, nullptr};   // reference luma planes the chain keeps (the last two of the last batch)
-  int64_t xp_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
-  int64_t xp_hist_pitch = 0;                  // bytes
-  uint8_t* xp_prev = nullptr;        // pqa_submit_surfaces: its shifted prev_ref (allocated on first use)
-  int64_t xp_last = -1;              // last frame of the previous batch (the chain continues at xp_last + 1)
-  int xp_armed = -1;                 // pqa_set_ref_history: planes armed in xp_hist[0..n) for the next batch (-1: none)
-  // SI / TI (PQA_FEAT_SITI; siti.hip): nothing is allocated unless the bit is set
-  double* ext4 = nullptr;            // [capacity][PQA_EXT4_DOUBLES] ring beside `records`
-  double* st_part = nullptr;         // [B][2][siti_partials][4]
-  uint8_t* st_hist[2] = {nullptr, nullptr};   // the last luma plane of each clip's chain (0: distorted, 1: reference)
-  int64_t st_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
-  int64_t st_hist_pitch = 0;                  // bytes
-  bool st_armed[2] = {false, false};          // pqa_set_dis_history / the reference history armed st_hist[z] as frame first-1
-  // capture integrity (PQA_FEAT_INTEGRITY; integrity.hip): nothing is allocated unless the bit is set
-  double* ext5 = nullptr;            // [capacity][PQA_EXT5_DOUBLES] ring beside `records`
-  unsigned long long* ig_part = nullptr;      // [B][3][kIntegrityBlocks][2]
-  uint8_t* ig_hist[3] = {nullptr, nullptr, nullptr};   // the planes of the last distorted frame of the chain
-  int64_t ig_hist_pitch[3] = {0, 0, 0};       // bytes
-  int64_t ig_hist_idx = -1;                   // its frame index (-1: empty)
-  bool ig_armed = false;                      // pqa_set_dis_history_planes armed ig_hist as frame first-1
-  uint32_t black_thr = 0;                     // pqa_set_black_threshold
-  bool started = false;                       // a batch was launched since pqa_create / pqa_reset
-  // pqa_frame_sad / pqa_frame_sad_device (allocated on first use)
-  uint8_t* ig_anchor[3] = {nullptr, nullptr, nullptr};  // the anchor frame's planes (pitches: ig_hist_pitch)
-  uint8_t* ig_stage = nullptr;                // FB frames of host planes (slot layout: ig_stage_off, ig_stage_bytes)
-  size_t ig_stage_off[3] = {0, 0, 0}, ig_stage_bytes = 0;
-  unsigned long long* ig_out = nullptr;       // [B][3] results of one launch
-  unsigned long long* luma_part = nullptr;
-  unsigned long long* luma_out = nullptr;
-  // host-frame luma statistics (pqa_luma_stats): two pinned + two device halves of LB luma planes
-  uint8_t* luma_pinned[2] = {nullptr, nullptr};
-  uint8_t* luma_dev[2] = {nullptr, nullptr};
-  hipEvent_t luma_copied[2] = {nullptr, nullptr};
-  int64_t luma_pitch = 0;
-  int LB = 0;
-  bool luma_ready = false;
-  uint32_t luma_gray = PQA_GRAY_LUMA;
-  // temporal alignment (pqa_cross_sse / pqa_cross_sse_device; cross_sse.hip): grow-only buffers, allocated on first use
-  bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
-  void* xs_buf[10] = {};             // XS_* below (XS_SH_*: pqa_shift_sse / pqa_shift_sse_device, shift_sse.hip; XS_LV_OUT: pqa_level_stats /
-                                     // pqa_level_stats_device, level_stats.hip)
-  size_t xs_cap[10] = {};            // their sizes in bytes
-  // motion continuity
-  uint8_t* last_luma = nullptr;
-  int64_t last_luma_pitch = 0;  // bytes
-  int64_t last_index = -1;
-  bool have_last = false, halo_armed = false;
-  // host staging (pqa_submit path)
-  Half half[2];
-  int cur_half = 0, pending = 0;
-  int64_t pending_first = 0;
-  size_t slot_bytes = 0;
-  size_t plane_off[2][3] = {};
-  int64_t slot_row_pitch[3] = {};
-  bool staging_ready = false;
-  std::thread pin_thread;            // pins the second staging half while the first one fills (ensure_staging)
-  hipError_t pin_err = hipSuccess;   // its result; read after joining it (staging_half_ready)
-  uint8_t* surf_dev = nullptr;   // pqa_submit_surfaces: B slots of unpacked planes (device only, allocated on first use)
-  std::unique_ptr<PackPool> pack_pool;
-  bool pack_pool_tried = false;
-  std::vector<PackTask> pack_tasks;
-  // record-ring bookkeeping (host side): which frame a slot holds, whether it was collected, and the batch that
-  // writes it.  Lets pqa_collect wait for ITS batch only and makes the PQA_ESTATE promises of the header real.
-  host::RecordRing ring;             // host_ring.h
-  hipEvent_t batch_ev[kBatchEvents] = {};
-  uint64_t batch_ev_seq[kBatchEvents] = {};  // sequence number last recorded into each event
-  uint64_t batch_seq = 0;            // batches launched so far (the next batch gets batch_seq + 1)
-  uint64_t done_seq = 0;             // every batch <= done_seq is known to be complete
-  std::atomic<int> cancelled{0};
-  std::string err;
-  std::vector<void*> allocs;
-  // profiling
-  int multi_stream = 0;              // 0 one stream; 1 three streams from the start of a batch; 2 three streams behind VIF scale 0
-  int vif_s0_mode = VIF_S0_AUTO;   // PQA_VIF_MFMA, read once in pqa_create
-  int adm_mode = ADM_AUTO;         // PQA_ADM_MARCH, read once in pqa_create
-  int motion_mode = MOTION_AUTO;   // PQA_MOTION_MARCH, read once in pqa_create
-  bool trace = false;   // PQA_TRACE=1: synchronise after every launch and name it on stderr (localises a stall)
-  bool prof = false;
-  uint32_t prof_mask = 0xffffffffu;
-  std::vector<ProfEv> evs;
-  double prof_ms[PQA_PROF_KERNELS] = {};
-  uint64_t prof_n[PQA_PROF_KERNELS] = {}, prof_frames[PQA_PROF_KERNELS] = {};
-};
-
-namespace {
-
-int fail(pqa_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf; else g_create_error = buf;
-  return code;
-}
-
-#define HIPCHK(c, expr)                                                                          \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      return fail((c), e_ == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "%s failed: %s", #expr, \
-                  hipGetErrorString(e_));                                                        \
-  } while (0)
-
-template <typename T>
-int dev_alloc(pqa_ctx* c, T** out, size_t count) {
-  void* p = nullptr;
-  if (count == 0) count = 1;
-  HIPCHK(c, hipMalloc(&p, count * sizeof(T)));
-  c->allocs.push_back(p);
-  *out = (T*)p;
-  return PQA_OK;
-}
-
-int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 static const char* kProfNames[PQA_PROF_KERNELS] = {
     "vif_stat_s0", "vif_stat_s1", "vif_stat_s2", "vif_stat_s3", "ciede2000", "reserved5",
@@ -992,14 +790,6 @@ int flush_pending(pqa_ctx* c) {
   return PQA_OK;
 }
 
-void copy_plane_rows(uint8_t* dst, int64_t dst_pitch, const uint8_t* src, int64_t src_pitch, size_t row_bytes, int h) {
-  if (dst_pitch == src_pitch) {
-    memcpy(dst, src, (size_t)dst_pitch * (h - 1) + row_bytes);
-    return;
-  }
-  for (int y = 0; y < h; ++y) memcpy(dst + (int64_t)y * dst_pitch, src + (int64_t)y * src_pitch, row_bytes);
-}
-
 // One frame pair from memory planes or from files into the pinned staging slot, its upload queued on the copy stream.
 struct PlaneSrc {
   const uint8_t* ptr;   // memory source (fd < 0): rows `stride` bytes apart
@@ -1521,11 +1311,12 @@ void pqa_destroy(pqa_ctx* c) {
     if (H.computed) hipEventDestroy(H.computed);
   }
   for (int i = 0; i < 2; ++i) {
-    if (c->luma_pinned[i]) hipHostFree(c->luma_pinned[i]);
-    if (c->luma_dev[i]) hipFree(c->luma_dev[i]);
-    if (c->luma_copied[i]) hipEventDestroy(c->luma_copied[i]);
+    Half& L = c->luma_half[i];
+    if (L.pinned) hipHostFree(L.pinned);
+    if (L.dev) hipFree(L.dev);
+    if (L.copied) hipEventDestroy(L.copied);
   }
-  for (void* b : c->xs_buf)
+  for (void* b : c->side_buf)
     if (b) hipFree(b);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   for (int i = 0; i < 2; ++i) {
@@ -1858,113 +1649,6 @@ int pqa_set_black_threshold(pqa_ctx* c, uint32_t threshold) {
   return PQA_OK;
 }
 
-namespace {
-// the launches of pqa_frame_sad[_device]: n frames (at most B) of a device clip against the anchor planes, results to out
-int frame_sad_launch(pqa_ctx* c, const void* const anchor[3], const int64_t anchor_pitch_bytes[3], const pqa_device_clip* f,
-                     int n, uint64_t* out) {
-  const int es = c->esize;
-  PlaneRun cur[3] = {};
-  int64_t app[3] = {0, 0, 0};
-  for (int p = 0; p < c->n_planes; ++p) {
-    cur[p] = PlaneRun{f->plane[p], f->row_pitch[p] / es, f->frame_pitch[p] / es};
-    app[p] = anchor_pitch_bytes[p] / es;
-  }
-  if (!c->ig_out) {
-    const int rc = dev_alloc(c, &c->ig_out, (size_t)c->B * 3);
-    if (rc != PQA_OK) return rc;
-  }
-  HIPCHK(c, launch_integrity(c->stream, c->elem, cur, anchor, app, c->pw, c->ph, c->n_planes, n, true, c->black_thr, c->ig_part,
-                             nullptr, 0, 0, 1, c->ig_out));
-  HIPCHK(c, hipMemcpyAsync(out, c->ig_out, (size_t)n * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return PQA_OK;
-}
-}  // namespace
-
-int pqa_frame_sad_device(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_row_pitch[3],
-                         const pqa_device_clip* frames, int32_t n_frames, uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!anchor_planes || !anchor_row_pitch || !frames || n_frames < 0 || (n_frames > 0 && !out))
-    return fail(c, PQA_EINVAL, "bad argument");
-  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return fail(c, PQA_ESTATE, "pqa_frame_sad_device needs PQA_FEAT_INTEGRITY");
-  for (int p = 0; p < c->n_planes; ++p) {
-    if (!anchor_planes[p] || !frames->plane[p]) return fail(c, PQA_EINVAL, "plane %d pointer is null", p);
-    const int64_t row_bytes = (int64_t)c->pw[p] * c->esize;
-    if (anchor_row_pitch[p] % c->esize || frames->row_pitch[p] % c->esize || frames->frame_pitch[p] % c->esize)
-      return fail(c, PQA_EINVAL, "plane %d pitch is not a multiple of the sample size", p);
-    if (anchor_row_pitch[p] < row_bytes || frames->row_pitch[p] < row_bytes)
-      return fail(c, PQA_EINVAL, "plane %d pitch smaller than a row", p);
-  }
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  for (int done = 0; done < n_frames;) {
-    const int n = n_frames - done < c->B ? n_frames - done : c->B;
-    pqa_device_clip f = *frames;
-    for (int p = 0; p < c->n_planes; ++p) f.plane[p] = (const uint8_t*)frames->plane[p] + (int64_t)done * frames->frame_pitch[p];
-    const int rc = frame_sad_launch(c, anchor_planes, anchor_row_pitch, &f, n, out + (size_t)done * 3);
-    if (rc != PQA_OK) return rc;
-    done += n;
-  }
-  return PQA_OK;
-}
-
-int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_strides[3], const void* const* frames,
-                  const int64_t strides[3], int32_t n_frames, uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!anchor_planes || !anchor_strides || n_frames < 0 || (n_frames > 0 && (!frames || !strides || !out)))
-    return fail(c, PQA_EINVAL, "bad argument");
-  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return fail(c, PQA_ESTATE, "pqa_frame_sad needs PQA_FEAT_INTEGRITY");
-  for (int p = 0; p < c->n_planes; ++p) {
-    const int64_t row_bytes = (int64_t)c->pw[p] * c->esize;
-    if (!anchor_planes[p]) return fail(c, PQA_EINVAL, "anchor plane %d pointer is null", p);
-    if (anchor_strides[p] < row_bytes || (n_frames > 0 && strides[p] < row_bytes))
-      return fail(c, PQA_EINVAL, "plane %d stride smaller than a row", p);
-    for (int f = 0; f < n_frames; ++f)   // before anything is queued
-      if (!frames[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "frame %d plane %d pointer is null", f, p);
-  }
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int FB = c->B < 8 ? c->B : 8;   // frames per upload and launch
-  if (!c->ig_stage) {   // lazily: a healthy clip never asks for an anchored difference
-    size_t off = 0;
-    for (int p = 0; p < c->n_planes; ++p) {
-      c->ig_stage_off[p] = off;
-      off += (size_t)round_up(c->ig_hist_pitch[p] * c->ph[p], 256);
-    }
-    c->ig_stage_bytes = off;
-    for (int p = 0; p < c->n_planes; ++p) {
-      const int rc = dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist_pitch[p] * c->ph[p]);
-      if (rc != PQA_OK) return rc;
-    }
-    const int rc = dev_alloc(c, &c->ig_stage, off * (size_t)FB);
-    if (rc != PQA_OK) return rc;
-  }
-  // plain synchronous copies from the caller's (pageable) planes: this call is rare and short, it is not pipelined
-  for (int p = 0; p < c->n_planes; ++p)
-    HIPCHK(c, hipMemcpy2D(c->ig_anchor[p], c->ig_hist_pitch[p], anchor_planes[p], anchor_strides[p], (size_t)c->pw[p] * c->esize,
-                          c->ph[p], hipMemcpyHostToDevice));
-  const void* anchor[3] = {c->ig_anchor[0], c->ig_anchor[1], c->ig_anchor[2]};
-  for (int done = 0; done < n_frames;) {
-    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-    const int n = n_frames - done < FB ? n_frames - done : FB;
-    pqa_device_clip f{};
-    for (int p = 0; p < c->n_planes; ++p) {
-      for (int k = 0; k < n; ++k)
-        HIPCHK(c, hipMemcpy2D(c->ig_stage + (size_t)k * c->ig_stage_bytes + c->ig_stage_off[p], c->ig_hist_pitch[p],
-                              frames[(size_t)(done + k) * 3 + p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
-                              hipMemcpyHostToDevice));
-      f.plane[p] = c->ig_stage + c->ig_stage_off[p];
-      f.row_pitch[p] = c->ig_hist_pitch[p];
-      f.frame_pitch[p] = (int64_t)c->ig_stage_bytes;
-    }
-    const int rc = frame_sad_launch(c, anchor, c->ig_hist_pitch, &f, n, out + (size_t)done * 3);
-    if (rc != PQA_OK) return rc;
-    done += n;
-  }
-  return PQA_OK;
-}
-
 int pqa_flush(pqa_ctx* c) {
   if (!c) return PQA_EINVAL;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
@@ -2031,6 +1715,9 @@ int pqa_collect_ext5(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   const size_t rec_bytes = PQA_RECORD_DOUBLES * sizeof(double);
+  const struct ExtRing { double* out; const double* dev; int doubles; } rings[5] = {
+      {ext, c->ext, PQA_EXT_DOUBLES},    {ext2, c->ext2, PQA_EXT2_DOUBLES}, {ext3, c->ext3, PQA_EXT3_DOUBLES},
+      {ext4, c->ext4, PQA_EXT4_DOUBLES}, {ext5, c->ext5, PQA_EXT5_DOUBLES}};
   int64_t row = first_index % c->capacity;
   int done = 0;
   while (done < count) {
@@ -2054,519 +1741,18 @@ int pqa_collect_ext5(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
           adm_fixed_epilogue(c->adm_fx[s], &acc[(size_t)f * 24 + s * 6], &rec[PQA_REC_ADM_NUM + s], &rec[PQA_REC_ADM_DEN + s]);
         }
     }
-    if (ext && c->ext) {   // the extension ring has the record ring's slots
-      HIPCHK(c, hipMemcpy(ext + (size_t)done * PQA_EXT_DOUBLES, c->ext + (size_t)row * PQA_EXT_DOUBLES,
-                          (size_t)n * PQA_EXT_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (ext) {      // a context without the SSIM family: nothing it runs has a slot there
-      std::fill(ext + (size_t)done * PQA_EXT_DOUBLES, ext + (size_t)(done + n) * PQA_EXT_DOUBLES, __builtin_nan(""));
-    }
-    if (ext2 && c->ext2) {  // so has the second one
-      HIPCHK(c, hipMemcpy(ext2 + (size_t)done * PQA_EXT2_DOUBLES, c->ext2 + (size_t)row * PQA_EXT2_DOUBLES,
-                          (size_t)n * PQA_EXT2_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (ext2) {
-      std::fill(ext2 + (size_t)done * PQA_EXT2_DOUBLES, ext2 + (size_t)(done + n) * PQA_EXT2_DOUBLES, __builtin_nan(""));
-    }
-    if (ext3 && c->ext3) {  // and the third
-      HIPCHK(c, hipMemcpy(ext3 + (size_t)done * PQA_EXT3_DOUBLES, c->ext3 + (size_t)row * PQA_EXT3_DOUBLES,
-                          (size_t)n * PQA_EXT3_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (ext3) {
-      std::fill(ext3 + (size_t)done * PQA_EXT3_DOUBLES, ext3 + (size_t)(done + n) * PQA_EXT3_DOUBLES, __builtin_nan(""));
-    }
-    if (ext4 && c->ext4) {  // and the fourth
-      HIPCHK(c, hipMemcpy(ext4 + (size_t)done * PQA_EXT4_DOUBLES, c->ext4 + (size_t)row * PQA_EXT4_DOUBLES,
-                          (size_t)n * PQA_EXT4_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (ext4) {
-      std::fill(ext4 + (size_t)done * PQA_EXT4_DOUBLES, ext4 + (size_t)(done + n) * PQA_EXT4_DOUBLES, __builtin_nan(""));
-    }
-    if (ext5 && c->ext5) {  // and the fifth
-      HIPCHK(c, hipMemcpy(ext5 + (size_t)done * PQA_EXT5_DOUBLES, c->ext5 + (size_t)row * PQA_EXT5_DOUBLES,
-                          (size_t)n * PQA_EXT5_DOUBLES * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (ext5) {
-      std::fill(ext5 + (size_t)done * PQA_EXT5_DOUBLES, ext5 + (size_t)(done + n) * PQA_EXT5_DOUBLES, __builtin_nan(""));
+    for (const ExtRing& x : rings) {   // an extension ring has the record ring's slots
+      if (!x.out) continue;
+      double* dst = x.out + (size_t)done * x.doubles;
+      if (x.dev)
+        HIPCHK(c, hipMemcpy(dst, x.dev + (size_t)row * x.doubles, (size_t)n * x.doubles * sizeof(double), hipMemcpyDeviceToHost));
+      else   // a context without the features of this ring: nothing it runs has a slot there
+        std::fill(dst, dst + (size_t)n * x.doubles, __builtin_nan(""));
     }
     done += n;
     row = 0;
   }
   c->ring.mark_collected(first_index, count);
-  return PQA_OK;
-}
-
-int pqa_luma_stats_device(pqa_ctx* c, const void* luma, int64_t row_pitch, int64_t frame_pitch, int32_t n_frames,
-                          uint32_t threshold, uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!luma || n_frames < 0 || (n_frames > 0 && !out)) return fail(c, PQA_EINVAL, "bad argument");
-  if (row_pitch % c->esize || frame_pitch % c->esize) return fail(c, PQA_EINVAL, "pitch is not a multiple of the sample size");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  // launches of up to B frames each write their results side by side into luma_out (kLumaOutFrames frames); the host
-  // copy and the sync happen once per kLumaOutFrames frames, not once per launch
-  for (int done = 0; done < n_frames;) {
-    const int group = n_frames - done < kLumaOutFrames ? n_frames - done : kLumaOutFrames;
-    for (int g0 = 0; g0 < group;) {
-      const int n = group - g0 < c->B ? group - g0 : c->B;
-      const PlaneRun run{(const uint8_t*)luma + (int64_t)(done + g0) * frame_pitch, row_pitch / c->esize, frame_pitch / c->esize};
-      HIPCHK(c, launch_luma_stats(c->stream, c->elem, run, n, c->pw[0], c->ph[0], threshold,
-                                  c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0, c->luma_part,
-                                  c->luma_out + (size_t)g0 * 3));
-      g0 += n;
-    }
-    HIPCHK(c, hipMemcpyAsync(out + (size_t)done * 3, c->luma_out, (size_t)group * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    done += group;
-  }
-  return PQA_OK;
-}
-
-namespace {
-// the two pinned + two device halves of LB luma planes that pqa_luma_stats and pqa_cross_sse pack host frames into
-int luma_staging_ensure(pqa_ctx* c) {
-  const int h = c->ph[0];
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  if (!c->luma_ready) {  // lazily: most contexts never detect bookends
-    c->luma_pitch = round_up((int64_t)row_bytes, 64);
-    c->LB = c->B < 8 ? c->B : 8;
-    const size_t half = (size_t)c->luma_pitch * h * c->LB;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-      if (!c->luma_pinned[i]) e = hipHostMalloc((void**)&c->luma_pinned[i], half, hipHostMallocDefault);
-      if (e == hipSuccess && !c->luma_dev[i]) e = hipMalloc((void**)&c->luma_dev[i], half);
-      if (e == hipSuccess && !c->luma_copied[i]) e = hipEventCreateWithFlags(&c->luma_copied[i], hipEventDisableTiming);
-    }
-    if (e != hipSuccess) {   // all six or none: a half-made set must not make every later call fail on a null handle
-      for (int i = 0; i < 2; ++i) {
-        if (c->luma_pinned[i]) hipHostFree(c->luma_pinned[i]);
-        if (c->luma_dev[i]) hipFree(c->luma_dev[i]);
-        if (c->luma_copied[i]) hipEventDestroy(c->luma_copied[i]);
-        c->luma_pinned[i] = c->luma_dev[i] = nullptr;
-        c->luma_copied[i] = nullptr;
-      }
-      return fail(c, e == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "luma staging allocation failed: %s", hipGetErrorString(e));
-    }
-    c->luma_ready = true;
-  }
-  return PQA_OK;
-}
-}  // namespace
-
-int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_stride, int32_t n_frames, uint32_t threshold,
-                   uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (n_frames < 0 || (n_frames > 0 && (!luma_frames || !out))) return fail(c, PQA_EINVAL, "bad argument");
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  if (n_frames > 0 && (size_t)row_stride < row_bytes) return fail(c, PQA_EINVAL, "stride smaller than a row");
-  for (int f = 0; f < n_frames; ++f)   // before anything is queued
-    if (!luma_frames[f]) return fail(c, PQA_EINVAL, "frame %d pointer is null", f);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int h = c->ph[0];
-  {
-    const int rc = luma_staging_ensure(c);
-    if (rc != PQA_OK) return rc;
-  }
-  const size_t frame_bytes = (size_t)c->luma_pitch * h;
-  const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
-  // Chunks of LB frames alternate between two pinned / device halves; every chunk's kernel writes its results next to the
-  // previous ones in luma_out, and the host gets them in ONE copy + sync per kLumaOutFrames frames: no device-to-host copy
-  // sits between the chunks (into the caller's pageable `out` it would block the host until the kernel in front of it is
-  // done, and the next chunk could not be packed under that kernel).
-  int rc = PQA_OK;
-  int chunk = 0;
-  for (int done = 0; done < n_frames && rc == PQA_OK;) {
-    const int group = n_frames - done < kLumaOutFrames ? n_frames - done : kLumaOutFrames;
-    for (int g0 = 0; g0 < group && rc == PQA_OK; ++chunk) {
-      if (c->cancelled.load()) { rc = fail(c, PQA_ECANCELLED, "cancelled"); break; }
-      const int n = group - g0 < c->LB ? group - g0 : c->LB;
-      const int hf = chunk & 1;
-      hipError_t e = hipSuccess;
-      if (chunk >= 2) e = hipEventSynchronize(c->luma_copied[hf]);   // the upload two chunks ago has left this pinned half
-      if (e == hipSuccess) {
-        for (int f = 0; f < n; ++f)
-          copy_plane_rows(c->luma_pinned[hf] + (size_t)f * frame_bytes, c->luma_pitch, (const uint8_t*)luma_frames[done + g0 + f],
-                          row_stride, row_bytes, h);
-        e = hipMemcpyAsync(c->luma_dev[hf], c->luma_pinned[hf], (size_t)n * frame_bytes, hipMemcpyHostToDevice, c->stream);
-      }
-      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
-      if (e == hipSuccess) {
-        const PlaneRun run{c->luma_dev[hf], c->luma_pitch / c->esize, (int64_t)(frame_bytes / c->esize)};
-        e = launch_luma_stats(c->stream, c->elem, run, n, c->pw[0], h, threshold, gray_bpc, c->luma_part,
-                              c->luma_out + (size_t)g0 * 3);
-      }
-      if (e != hipSuccess) { rc = fail(c, PQA_EDEVICE, "luma statistics chunk failed: %s", hipGetErrorString(e)); break; }
-      g0 += n;
-    }
-    if (rc == PQA_OK) {
-      const hipError_t e = hipMemcpyAsync(out + (size_t)done * 3, c->luma_out, (size_t)group * 3 * sizeof(uint64_t),
-                                          hipMemcpyDeviceToHost, c->stream);
-      if (e != hipSuccess) rc = fail(c, PQA_EDEVICE, "luma statistics copy failed: %s", hipGetErrorString(e));
-    }
-    // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (es != hipSuccess && rc == PQA_OK) rc = fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
-    done += group;
-  }
-  return rc;
-}
-
-namespace {
-enum { XS_PART = 0, XS_NORM_REF, XS_NORM_DIS, XS_OUT, XS_REF, XS_DIS, XS_SH_PART, XS_SH_ROWSQ, XS_SH_OUT, XS_LV_OUT };
-
-// a grow-only device buffer of the cross-SSE calls
-int xs_reserve(pqa_ctx* c, int which, size_t bytes) {
-  if (bytes == 0) bytes = 1;
-  if (c->xs_cap[which] >= bytes) return PQA_OK;
-  if (c->xs_buf[which]) {
-    HIPCHK(c, hipFree(c->xs_buf[which]));
-    c->xs_buf[which] = nullptr;
-    c->xs_cap[which] = 0;
-  }
-  HIPCHK(c, hipMalloc(&c->xs_buf[which], bytes));
-  c->xs_cap[which] = bytes;
-  return PQA_OK;
-}
-
-// the argument rules the two entries share; no device call
-int xs_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_ref, int32_t n_dis, int32_t k_lo, int32_t k_hi,
-             const uint64_t* out) {
-  if (!ref || !dis) return fail(c, PQA_EINVAL, "cross_sse: null clip pointer");
-  if (n_ref < 0 || n_dis < 0) return fail(c, PQA_EINVAL, "cross_sse: negative frame count");
-  if (k_lo > k_hi) return fail(c, PQA_EINVAL, "cross_sse: k_lo %d > k_hi %d", k_lo, k_hi);
-  if (k_lo < -64 || k_hi > 64) return fail(c, PQA_EINVAL, "cross_sse: offsets %d ... %d outside -64 ... 64", k_lo, k_hi);
-  if ((int64_t)k_hi - k_lo + 1 > 129) return fail(c, PQA_EINVAL, "cross_sse: span above 129");
-  if (!out) return fail(c, PQA_EINVAL, "cross_sse: null output pointer");
-  if (!c) return PQA_EINVAL;
-  return PQA_OK;
-}
-
-constexpr int kXsTilesPerLaunch = 8;   // reference tiles (of 32 frames) per launch of the device-resident entry
-
-int xs_prepare(pqa_ctx* c, bool mfma, int span, int n_tiles, int32_t n_ref, int32_t n_dis) {
-  int rc = xs_reserve(c, XS_PART, xsse_part_bytes(mfma, c->pw[0], c->ph[0], span, n_tiles));
-  if (rc == PQA_OK) rc = xs_reserve(c, XS_OUT, (size_t)n_ref * span * sizeof(uint64_t));
-  if (rc == PQA_OK && mfma) rc = xs_reserve(c, XS_NORM_REF, (size_t)n_ref * kXsseNormBlocks * sizeof(uint64_t));
-  if (rc == PQA_OK && mfma) rc = xs_reserve(c, XS_NORM_DIS, (size_t)n_dis * kXsseNormBlocks * sizeof(uint64_t));
-  return rc;
-}
-}  // namespace
-
-int pqa_cross_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, int32_t n_ref,
-                         const void* dis_luma, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_dis, int32_t k_lo,
-                         int32_t k_hi, uint64_t* out) {
-  const int chk = xs_check(c, ref_luma, dis_luma, n_ref, n_dis, k_lo, k_hi, out);
-  if (chk != PQA_OK) return chk;
-  const int es = c->esize;
-  const int64_t row_bytes = (int64_t)c->pw[0] * es;
-  if (ref_row_pitch % es || ref_frame_pitch % es || dis_row_pitch % es || dis_frame_pitch % es)
-    return fail(c, PQA_EINVAL, "cross_sse: pitch is not a multiple of the sample size");
-  if (ref_row_pitch < row_bytes || dis_row_pitch < row_bytes) return fail(c, PQA_EINVAL, "cross_sse: pitch smaller than a row");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_ref == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int span = k_hi - k_lo + 1;
-  const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
-  const int n_tiles = (n_ref + 31) / 32;
-  const int per_launch = n_tiles < kXsTilesPerLaunch ? n_tiles : kXsTilesPerLaunch;
-  const int rc = xs_prepare(c, mfma, span, per_launch, n_ref, n_dis);
-  if (rc != PQA_OK) return rc;
-  const XsseClip ref{ref_luma, ref_row_pitch / es, ref_frame_pitch / es, INT32_MAX, n_ref};
-  const XsseClip dis{dis_luma, dis_row_pitch / es, dis_frame_pitch / es, INT32_MAX, n_dis};
-  auto* nr = (unsigned long long*)c->xs_buf[XS_NORM_REF];
-  auto* nd = (unsigned long long*)c->xs_buf[XS_NORM_DIS];
-  if (mfma) {
-    HIPCHK(c, launch_xsse_norms(c->stream, ref, 0, n_ref, c->pw[0], c->ph[0], nr));
-    HIPCHK(c, launch_xsse_norms(c->stream, dis, 0, n_dis, c->pw[0], c->ph[0], nd));
-  }
-  for (int t0 = 0; t0 < n_tiles; t0 += per_launch) {
-    const int nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
-    HIPCHK(c, launch_cross_sse(c->stream, c->elem, mfma, ref, dis, c->pw[0], c->ph[0], k_lo, span, t0, nt, c->xs_buf[XS_PART], nr,
-                               nd, (unsigned long long*)c->xs_buf[XS_OUT]));
-  }
-  HIPCHK(c, hipMemcpyAsync(out, c->xs_buf[XS_OUT], (size_t)n_ref * span * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return PQA_OK;
-}
-
-int pqa_cross_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, int32_t n_ref,
-                  const void* const* dis_frames, int64_t dis_row_stride, int32_t n_dis, int32_t k_lo, int32_t k_hi,
-                  uint64_t* out) {
-  const int chk = xs_check(c, ref_frames, dis_frames, n_ref, n_dis, k_lo, k_hi, out);
-  if (chk != PQA_OK) return chk;
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  if ((n_ref > 0 && (size_t)ref_row_stride < row_bytes) || (n_dis > 0 && (size_t)dis_row_stride < row_bytes))
-    return fail(c, PQA_EINVAL, "cross_sse: stride smaller than a row");
-  for (int f = 0; f < n_ref; ++f)   // before anything is queued
-    if (!ref_frames[f]) return fail(c, PQA_EINVAL, "cross_sse: reference frame %d pointer is null", f);
-  for (int f = 0; f < n_dis; ++f)
-    if (!dis_frames[f]) return fail(c, PQA_EINVAL, "cross_sse: captured frame %d pointer is null", f);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_ref == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = luma_staging_ensure(c);
-  if (rc != PQA_OK) return rc;
-  const int span = k_hi - k_lo + 1, h = c->ph[0], es = c->esize;
-  const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
-  rc = xs_prepare(c, mfma, span, 1, n_ref, n_dis);
-  const size_t frame_bytes = (size_t)c->luma_pitch * h;
-  const int dis_ring = 31 + span;   // the captured frames one reference tile meets
-  if (rc == PQA_OK) rc = xs_reserve(c, XS_REF, frame_bytes * 32);
-  if (rc == PQA_OK) rc = xs_reserve(c, XS_DIS, frame_bytes * dis_ring);
-  if (rc != PQA_OK) return rc;
-  const XsseClip ref{c->xs_buf[XS_REF], c->luma_pitch / es, (int64_t)(frame_bytes / es), 32, n_ref};
-  const XsseClip dis{c->xs_buf[XS_DIS], c->luma_pitch / es, (int64_t)(frame_bytes / es), dis_ring, n_dis};
-  auto* nr = (unsigned long long*)c->xs_buf[XS_NORM_REF];
-  auto* nd = (unsigned long long*)c->xs_buf[XS_NORM_DIS];
-  // Every frame crosses PCIe once: reference tile b replaces tile b - 1 in its 32 slots, and the captured window only ever
-  // moves forward, so a tile uploads the captured frames between the previous window's end and its own.  Frames travel in
-  // chunks of LB through the two pinned halves, as in pqa_luma_stats; the stream orders a tile's uploads before its kernels
-  // and those before the next tile's uploads into the same slots.
-  int chunk = 0;
-  auto upload = [&](const void* const* frames, int64_t stride, const XsseClip& clip, int64_t first, int64_t last,
-                    unsigned long long* norms) -> hipError_t {   // frames first ... last - 1 into their ring slots
-    for (int64_t f0 = first; f0 < last; ++chunk) {
-      if (c->cancelled.load()) return hipErrorUnknown;
-      const int n = (int)(last - f0 < c->LB ? last - f0 : c->LB);
-      const int hf = chunk & 1;
-      hipError_t e = chunk >= 2 ? hipEventSynchronize(c->luma_copied[hf]) : hipSuccess;
-      for (int f = 0; f < n && e == hipSuccess; ++f) {
-        uint8_t* pin = c->luma_pinned[hf] + (size_t)f * frame_bytes;
-        copy_plane_rows(pin, c->luma_pitch, (const uint8_t*)frames[f0 + f], stride, row_bytes, h);
-        e = hipMemcpyAsync((uint8_t*)clip.base + (size_t)((f0 + f) % clip.ring) * frame_bytes, pin, frame_bytes,
-                           hipMemcpyHostToDevice, c->stream);
-      }
-      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
-      if (e != hipSuccess) return e;
-      if (mfma) {   // the frames of a chunk lie in consecutive slots unless the ring wraps inside it: one launch per frame run
-        for (int f = 0; f < n && e == hipSuccess; ++f) e = launch_xsse_norms(c->stream, clip, f0 + f, 1, c->pw[0], h, norms);
-        if (e != hipSuccess) return e;
-      }
-      f0 += n;
-    }
-    return hipSuccess;
-  };
-  hipError_t e = hipSuccess;
-  int64_t dis_done = 0;   // captured frames below it have been uploaded (or skipped: no reference tile meets them)
-  const int n_tiles = (n_ref + 31) / 32;
-  for (int t = 0; t < n_tiles && e == hipSuccess; ++t) {
-    const int64_t r0 = (int64_t)t * 32, r1 = r0 + 32 < n_ref ? r0 + 32 : n_ref;
-    int64_t d0 = r0 + k_lo, d1 = r0 + 31 + k_hi + 1;
-    d0 = d0 < dis_done ? dis_done : d0;
-    d1 = d1 > n_dis ? n_dis : d1;
-    e = upload(ref_frames, ref_row_stride, ref, r0, r1, nr);
-    if (e == hipSuccess && d0 < d1) {
-      e = upload(dis_frames, dis_row_stride, dis, d0, d1, nd);
-      dis_done = d1;
-    }
-    if (e == hipSuccess)
-      e = launch_cross_sse(c->stream, c->elem, mfma, ref, dis, c->pw[0], h, k_lo, span, t, 1, c->xs_buf[XS_PART], nr, nd,
-                           (unsigned long long*)c->xs_buf[XS_OUT]);
-  }
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(out, c->xs_buf[XS_OUT], (size_t)n_ref * span * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
-  // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
-  const hipError_t es2 = hipStreamSynchronize(c->stream);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "cross_sse failed: %s", hipGetErrorString(e));
-  if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
-  return PQA_OK;
-}
-
-namespace {
-// the argument rules the two spatial entries share; no device call
-int sh_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int32_t radius, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "shift_sse: negative frame count");
-  if (radius < 0 || radius > kShiftMaxRadius) return fail(c, PQA_EINVAL, "shift_sse: radius %d outside 0 ... %d", radius, kShiftMaxRadius);
-  if (c->pw[0] <= 2 * radius || c->ph[0] <= 2 * radius)
-    return fail(c, PQA_EINVAL, "shift_sse: a %dx%d frame is not larger than twice the radius %d", c->pw[0], c->ph[0], radius);
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "shift_sse: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "shift_sse: null output pointer");
-  return PQA_OK;
-}
-
-int sh_prepare(pqa_ctx* c, int radius, int32_t n_frames) {
-  const int chunk = n_frames < kShiftChunk ? n_frames : kShiftChunk;
-  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
-  int rc = xs_reserve(c, XS_SH_PART, shift_part_bytes(c->elem, c->pw[0], c->ph[0], radius, chunk));
-  if (rc == PQA_OK) rc = xs_reserve(c, XS_SH_ROWSQ, shift_rowsq_bytes(c->ph[0], radius, chunk));
-  if (rc == PQA_OK) rc = xs_reserve(c, XS_SH_OUT, (size_t)n_frames * n * sizeof(uint64_t));
-  return rc;
-}
-}  // namespace
-
-int pqa_shift_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis_luma,
-                         int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t radius, uint64_t* out) {
-  const int chk = sh_check(c, ref_luma, dis_luma, n_frames, radius, out);
-  if (chk != PQA_OK) return chk;
-  if (n_frames == 0) return PQA_OK;
-  const int es = c->esize;
-  const int64_t row_bytes = (int64_t)c->pw[0] * es;
-  if (ref_row_pitch % es || ref_frame_pitch % es || dis_row_pitch % es || dis_frame_pitch % es)
-    return fail(c, PQA_EINVAL, "shift_sse: pitch is not a multiple of the sample size");
-  if (ref_row_pitch < row_bytes || dis_row_pitch < row_bytes) return fail(c, PQA_EINVAL, "shift_sse: pitch smaller than a row");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int rc = sh_prepare(c, radius, n_frames);
-  if (rc != PQA_OK) return rc;
-  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
-  auto* dev_out = (unsigned long long*)c->xs_buf[XS_SH_OUT];
-  for (int f0 = 0; f0 < n_frames; f0 += kShiftChunk) {
-    const int m = n_frames - f0 < kShiftChunk ? n_frames - f0 : kShiftChunk;
-    HIPCHK(c, launch_shift_sse(c->stream, c->elem, (const uint8_t*)ref_luma + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
-                               ref_frame_pitch / es, (const uint8_t*)dis_luma + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
-                               dis_frame_pitch / es, m, c->pw[0], c->ph[0], radius, c->xs_buf[XS_SH_PART],
-                               (unsigned long long*)c->xs_buf[XS_SH_ROWSQ], dev_out + (size_t)f0 * n));
-  }
-  HIPCHK(c, hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return PQA_OK;
-}
-
-int pqa_shift_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
-                  int64_t dis_row_stride, int32_t n_frames, int32_t radius, uint64_t* out) {
-  const int chk = sh_check(c, ref_frames, dis_frames, n_frames, radius, out);
-  if (chk != PQA_OK) return chk;
-  if (n_frames == 0) return PQA_OK;
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  if ((size_t)ref_row_stride < row_bytes || (size_t)dis_row_stride < row_bytes)
-    return fail(c, PQA_EINVAL, "shift_sse: stride smaller than a row");
-  for (int f = 0; f < n_frames; ++f)   // before anything is queued
-    if (!ref_frames[f] || !dis_frames[f]) return fail(c, PQA_EINVAL, "shift_sse: frame %d pointer is null", f);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = luma_staging_ensure(c);
-  if (rc == PQA_OK) rc = sh_prepare(c, radius, n_frames);   // LB <= kShiftChunk: the workspaces of a full chunk hold every chunk here
-  if (rc != PQA_OK) return rc;
-  const int h = c->ph[0], es = c->esize;
-  const size_t frame_bytes = (size_t)c->luma_pitch * h, n = (size_t)(2 * radius + 1) * (2 * radius + 1);
-  auto* dev_out = (unsigned long long*)c->xs_buf[XS_SH_OUT];
-  // A chunk of LB (<= 8) pairs: the reference frames go through pinned / device half 0, the captured ones through half 1.
-  // The stream orders a chunk's kernels before the next chunk's uploads into the same device halves; a pinned half is
-  // repacked once the copy out of it has finished.
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += c->LB) {
-    if (c->cancelled.load()) break;
-    const int m = n_frames - f0 < c->LB ? n_frames - f0 : c->LB;
-    for (int hf = 0; hf < 2 && e == hipSuccess; ++hf) {
-      const void* const* frames = hf ? dis_frames : ref_frames;
-      const int64_t stride = hf ? dis_row_stride : ref_row_stride;
-      if (f0 > 0) e = hipEventSynchronize(c->luma_copied[hf]);
-      if (e != hipSuccess) break;
-      for (int f = 0; f < m; ++f)
-        copy_plane_rows(c->luma_pinned[hf] + (size_t)f * frame_bytes, c->luma_pitch, (const uint8_t*)frames[f0 + f], stride,
-                        row_bytes, h);
-      e = hipMemcpyAsync(c->luma_dev[hf], c->luma_pinned[hf], (size_t)m * frame_bytes, hipMemcpyHostToDevice, c->stream);
-      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
-    }
-    if (e == hipSuccess)
-      e = launch_shift_sse(c->stream, c->elem, c->luma_dev[0], c->luma_pitch / es, (int64_t)(frame_bytes / es), c->luma_dev[1],
-                           c->luma_pitch / es, (int64_t)(frame_bytes / es), m, c->pw[0], h, radius, c->xs_buf[XS_SH_PART],
-                           (unsigned long long*)c->xs_buf[XS_SH_ROWSQ], dev_out + (size_t)f0 * n);
-  }
-  if (e == hipSuccess && !c->cancelled.load())
-    e = hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
-  // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
-  const hipError_t es2 = hipStreamSynchronize(c->stream);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "shift_sse failed: %s", hipGetErrorString(e));
-  if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
-  return PQA_OK;
-}
-
-namespace {
-// the argument rules the two level entries share; no device call
-int lv_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int32_t plane, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "level_stats: negative frame count");
-  if (plane < 0 || plane >= c->n_planes) return fail(c, PQA_EINVAL, "level_stats: plane %d of a context with %d", plane, c->n_planes);
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "level_stats: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "level_stats: null output pointer");
-  return PQA_OK;
-}
-}  // namespace
-
-int pqa_level_bins(const pqa_ctx* c) { return c ? 1 << c->cfg.bit_depth : PQA_EINVAL; }
-
-int pqa_level_stats_device(pqa_ctx* c, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
-                           int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t plane, uint64_t* out) {
-  const int chk = lv_check(c, ref, dis, n_frames, plane, out);
-  if (chk != PQA_OK) return chk;
-  if (n_frames == 0) return PQA_OK;
-  const int es = c->esize, bpc = (int)c->cfg.bit_depth;
-  const int64_t row_bytes = (int64_t)c->pw[plane] * es;
-  if (ref_row_pitch % es || ref_frame_pitch % es || dis_row_pitch % es || dis_frame_pitch % es)
-    return fail(c, PQA_EINVAL, "level_stats: pitch is not a multiple of the sample size");
-  if (ref_row_pitch < row_bytes || dis_row_pitch < row_bytes) return fail(c, PQA_EINVAL, "level_stats: pitch smaller than a row");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int rc = xs_reserve(c, XS_LV_OUT, level_out_bytes(bpc, n_frames));
-  if (rc != PQA_OK) return rc;
-  const size_t n = (size_t)3 << bpc;
-  auto* dev_out = (unsigned long long*)c->xs_buf[XS_LV_OUT];
-  for (int f0 = 0; f0 < n_frames; f0 += kLevelChunk) {
-    const int m = n_frames - f0 < kLevelChunk ? n_frames - f0 : kLevelChunk;
-    HIPCHK(c, launch_level_stats(c->stream, c->elem, bpc, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
-                                 ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
-                                 dis_frame_pitch / es, m, c->pw[plane], c->ph[plane], dev_out + (size_t)f0 * n));
-  }
-  HIPCHK(c, hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return PQA_OK;
-}
-
-int pqa_level_stats(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
-                    int64_t dis_row_stride, int32_t n_frames, int32_t plane, uint64_t* out) {
-  const int chk = lv_check(c, ref_frames, dis_frames, n_frames, plane, out);
-  if (chk != PQA_OK) return chk;
-  if (n_frames == 0) return PQA_OK;
-  const size_t row_bytes = (size_t)c->pw[plane] * c->esize;
-  if (ref_row_stride < 0 || dis_row_stride < 0 || (size_t)ref_row_stride < row_bytes || (size_t)dis_row_stride < row_bytes)
-    return fail(c, PQA_EINVAL, "level_stats: stride smaller than a row");
-  for (int f = 0; f < n_frames; ++f)   // before anything is queued
-    if (!ref_frames[f] || !dis_frames[f]) return fail(c, PQA_EINVAL, "level_stats: frame %d pointer is null", f);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int bpc = (int)c->cfg.bit_depth;
-  int rc = luma_staging_ensure(c);
-  if (rc == PQA_OK) rc = xs_reserve(c, XS_LV_OUT, level_out_bytes(bpc, n_frames));
-  if (rc != PQA_OK) return rc;
-  // a chroma plane is no larger than the luma plane, so it travels through the luma staging with the luma pitches
-  const int w = c->pw[plane], h = c->ph[plane], es = c->esize;
-  const size_t frame_bytes = (size_t)c->luma_pitch * c->ph[0], n = (size_t)3 << bpc;
-  auto* dev_out = (unsigned long long*)c->xs_buf[XS_LV_OUT];
-  // chunks of LB (<= kLevelChunk) pairs, staged as in pqa_shift_sse: reference frames through half 0, captured ones through half 1
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += c->LB) {
-    if (c->cancelled.load()) break;
-    const int m = n_frames - f0 < c->LB ? n_frames - f0 : c->LB;
-    for (int hf = 0; hf < 2 && e == hipSuccess; ++hf) {
-      const void* const* frames = hf ? dis_frames : ref_frames;
-      const int64_t stride = hf ? dis_row_stride : ref_row_stride;
-      if (f0 > 0) e = hipEventSynchronize(c->luma_copied[hf]);
-      if (e != hipSuccess) break;
-      for (int f = 0; f < m; ++f)
-        copy_plane_rows(c->luma_pinned[hf] + (size_t)f * frame_bytes, c->luma_pitch, (const uint8_t*)frames[f0 + f], stride,
-                        row_bytes, h);
-      e = hipMemcpyAsync(c->luma_dev[hf], c->luma_pinned[hf], (size_t)m * frame_bytes, hipMemcpyHostToDevice, c->stream);
-      if (e == hipSuccess) e = hipEventRecord(c->luma_copied[hf], c->stream);
-    }
-    if (e == hipSuccess)
-      e = launch_level_stats(c->stream, c->elem, bpc, c->luma_dev[0], c->luma_pitch / es, (int64_t)(frame_bytes / es),
-                             c->luma_dev[1], c->luma_pitch / es, (int64_t)(frame_bytes / es), m, w, h, dev_out + (size_t)f0 * n);
-  }
-  if (e == hipSuccess && !c->cancelled.load())
-    e = hipMemcpyAsync(out, dev_out, (size_t)n_frames * n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
-  // always: nothing queued on the stream may still point at the pinned halves or at `out` when this call returns
-  const hipError_t es2 = hipStreamSynchronize(c->stream);
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "level_stats failed: %s", hipGetErrorString(e));
-  if (es2 != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es2));
-  return PQA_OK;
-}
-
-int pqa_set_luma_gray(pqa_ctx* c, uint32_t mode) {
-  if (!c) return PQA_EINVAL;
-  if (mode != PQA_GRAY_LUMA && mode != PQA_GRAY_BT601_FULL) return fail(c, PQA_EINVAL, "bad gray mode %u", mode);
-  c->luma_gray = mode;
   return PQA_OK;
 }
 
@@ -2623,276 +1809,6 @@ int pqa_profile_read(pqa_ctx* c, int kernel_id, double* total_ms, uint64_t* laun
   if (total_ms) *total_ms = c->prof_ms[kernel_id];
   if (launches) *launches = c->prof_n[kernel_id];
   if (frames) *frames = c->prof_frames[kernel_id];
-  return PQA_OK;
-}
-
-int pqa_debug_vif_march_table(uint16_t* out, int32_t capacity_halfwords) { return vif_march_table(out, capacity_halfwords); }
-int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* out6) {
-  if (!out6 || width == 0 || height == 0 || width > 65536 || height > 65536) return PQA_EINVAL;
-  int shape[6];
-  vif_march_shape((int)width, (int)height, shape);
-  for (int i = 0; i < 6; ++i) out6[i] = shape[i];
-  return PQA_OK;
-}
-
-int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out) {
-  if (n < 0 || (n > 0 && (!lab_pairs || !de_out))) return fail(nullptr, PQA_EINVAL, "bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
-  if (n == 0) return PQA_OK;
-  std::vector<float> in((size_t)n * 6), out((size_t)n);
-  for (size_t i = 0; i < in.size(); ++i) in[i] = (float)lab_pairs[i];
-  float* d_in = nullptr;
-  float* d_out = nullptr;
-  hipError_t e = hipMalloc(&d_in, in.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_out, out.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d_in, in.data(), in.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_ciede_debug(nullptr, d_in, n, d_out);
-  if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, out.size() * sizeof(float), hipMemcpyDeviceToHost);
-  if (d_in) hipFree(d_in);
-  if (d_out) hipFree(d_out);
-  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_ciede2000: %s", hipGetErrorString(e));
-  for (int32_t i = 0; i < n; ++i) de_out[i] = (double)out[i];
-  return PQA_OK;
-}
-
-int pqa_debug_cambi_params(uint32_t w, uint32_t h, uint32_t bit_depth, int32_t* out, int32_t cap) {
-  if (!out || cap < PQA_CAMBI_PARAM_INTS) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: null or short output");
-  if (w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: unsupported %ux%u at %u bit", w, h, bit_depth);
-  static_assert(kCambiParamInts == PQA_CAMBI_PARAM_INTS, "pqa_debug_cambi_params layout");
-  const CambiParams p = cambi_params((int)w, (int)h);
-  int i = 0;
-  out[i++] = p.ws; out[i++] = p.r; out[i++] = p.piw; out[i++] = p.mask_t;
-  for (int d = 0; d < kCambiDiffs; ++d) out[i++] = p.tvi[d];
-  for (int d = 0; d < kCambiDiffs; ++d) out[i++] = p.weights[d];
-  for (int s = 0; s < kCambiScales; ++s) { out[i++] = p.sw[s]; out[i++] = p.sh[s]; }
-  return PQA_OK;
-}
-
-int pqa_debug_cambi_cmap(const void* luma, int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth, float* cmap,
-                         int64_t cap, double* score) {
-  if (!luma || !cmap || w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: bad argument");
-  const int es = bit_depth > 8 ? 2 : 1;
-  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: bad row pitch %lld", (long long)row_pitch_bytes);
-  const CambiParams p = cambi_params((int)w, (int)h);
-  const int64_t total = p.off[kCambiScales];
-  if (cap < total) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: cmap holds %lld floats, needs %lld", (long long)cap,
-                               (long long)total);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
-  void* src = nullptr;
-  double* ext = nullptr;
-  CambiWork wk{};
-  const size_t plane_bytes = (size_t)w * h * es;
-  hipError_t e = cambi_prepare(p, (int)bit_depth);
-  if (e == hipSuccess) e = hipMalloc(&src, plane_bytes);
-  if (e == hipSuccess) e = hipMalloc(&ext, PQA_EXT_DOUBLES * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&wk.plane, (size_t)total * sizeof(uint16_t));
-  if (e == hipSuccess) e = hipMalloc(&wk.mask, (size_t)total);
-  if (e == hipSuccess) e = hipMalloc(&wk.cmap, (size_t)total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&wk.hist, (size_t)kCambiScales * 2048 * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&wk.sel, (size_t)kCambiScales * 4 * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&wk.partials, (size_t)p.chunk[kCambiScales] * sizeof(double));
-  if (e == hipSuccess)
-    e = hipMemcpy2D(src, (size_t)w * es, luma, (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    const PlaneRun run{src, (int64_t)w, (int64_t)w * h};
-    e = launch_cambi(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, run, 1, (int)w, (int)h, (int)bit_depth, p, wk, ext, PQA_EXT_DOUBLES,
-                     PQA_EXT_CAMBI, 0, 1, 1);
-  }
-  if (e == hipSuccess) e = hipMemcpy(cmap, wk.cmap, (size_t)total * sizeof(float), hipMemcpyDeviceToHost);
-  double ext_row[PQA_EXT_DOUBLES];
-  if (e == hipSuccess) e = hipMemcpy(ext_row, ext, sizeof ext_row, hipMemcpyDeviceToHost);
-  for (void* q : {src, (void*)ext, (void*)wk.plane, (void*)wk.mask, (void*)wk.cmap, (void*)wk.hist, (void*)wk.sel,
-                  (void*)wk.partials})
-    if (q) hipFree(q);
-  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_cambi_cmap: %s", hipGetErrorString(e));
-  if (score) *score = ext_row[PQA_EXT_CAMBI];
-  return PQA_OK;
-}
-
-int pqa_debug_psnr_hvs_dct8x8(const int32_t* in, int32_t* out, int32_t n) {
-  if (!in || !out || n < 0) return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_dct8x8: bad argument");
-  psnr_hvs_fdct8x8_host(in, out, n);
-  return PQA_OK;
-}
-
-int pqa_debug_psnr_hvs_tables(float* out, int32_t cap) {
-  static_assert(kPhvTableFloats == PQA_PSNR_HVS_TABLE_FLOATS, "pqa_debug_psnr_hvs_tables layout");
-  if (!out || cap < PQA_PSNR_HVS_TABLE_FLOATS)
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_tables: null or short output");
-  psnr_hvs_tables(out);
-  return PQA_OK;
-}
-
-int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
-                             uint32_t bit_depth, uint32_t plane_kind, float* block_err, double* mse) {
-  if (!ref || !dis || !block_err || w < 8 || h < 8 || w > 16384 || h > 16384 || plane_kind > 2 ||
-      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_plane: bad argument");
-  const int es = bit_depth > 8 ? 2 : 1;
-  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_plane: bad row pitch %lld", (long long)row_pitch_bytes);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
-  // the plane pair stands in for all three planes; plane_kind picks whose tables and block sums are read back
-  const int pw[3] = {(int)w, (int)w, (int)w}, ph[3] = {(int)h, (int)h, (int)h};
-  PsnrHvsGeometry geo{};
-  psnr_hvs_geometry(pw, ph, &geo);
-  const int nb = geo.nbx[0] * geo.nby[0];
-  void *src = nullptr, *dst = nullptr;
-  double *part = nullptr, *ext2 = nullptr;
-  float* err = nullptr;
-  const size_t plane_bytes = (size_t)w * h * es;
-  hipError_t e = psnr_hvs_prepare();
-  if (e == hipSuccess) e = hipMalloc(&src, plane_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dst, plane_bytes);
-  if (e == hipSuccess) e = hipMalloc(&part, (size_t)geo.tile0[3] * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&ext2, PQA_EXT2_DOUBLES * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&err, (size_t)nb * sizeof(float));
-  if (e == hipSuccess)
-    e = hipMemcpy2D(src, (size_t)w * es, ref, (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy2D(dst, (size_t)w * es, dis, (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    PlaneRun r3[3], d3[3];
-    for (int p = 0; p < 3; ++p) {
-      r3[p] = PlaneRun{src, (int64_t)w, (int64_t)w * h};
-      d3[p] = PlaneRun{dst, (int64_t)w, (int64_t)w * h};
-    }
-    e = launch_psnr_hvs(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, r3, d3, 1, geo, part, err, (int)plane_kind);
-  }
-  if (e == hipSuccess) {
-    PsnrHvsFinalizeArgs pa{};
-    pa.n_frames = 1;
-    pa.ext2 = ext2;
-    pa.ext_stride = PQA_EXT2_DOUBLES;
-    pa.slot_base = 0; pa.slot_step = 1; pa.capacity = 1;
-    pa.partials = part;
-    for (int p = 0; p < 4; ++p) pa.tile0[p] = geo.tile0[p];
-    for (int p = 0; p < 3; ++p) pa.blocks[p] = nb;
-    pa.peak = (double)((1 << bit_depth) - 1);
-    e = launch_psnr_hvs_finalize(nullptr, pa);
-  }
-  if (e == hipSuccess) e = hipMemcpy(block_err, err, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost);
-  double row[PQA_EXT2_DOUBLES];
-  if (e == hipSuccess) e = hipMemcpy(row, ext2, sizeof row, hipMemcpyDeviceToHost);
-  for (void* q : {src, dst, (void*)part, (void*)ext2, (void*)err})
-    if (q) hipFree(q);
-  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_psnr_hvs_plane: %s", hipGetErrorString(e));
-  if (mse) *mse = row[PQA_EXT2_PSNR_HVS_MSE + plane_kind];
-  return PQA_OK;
-}
-
-int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const void* ref_m2, const void* dis, int64_t row_pitch_bytes,
-                           uint32_t w, uint32_t h, uint32_t bit_depth, int32_t hfr, uint64_t* out, double* wsse) {
-  if (!ref || !dis || !out || w < 16 || h < 16 || w > 16384 || h > 16384 ||
-      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: bad argument");
-  const int es = bit_depth > 8 ? 2 : 1;
-  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: bad row pitch %lld", (long long)row_pitch_bytes);
-  XpsnrGeometry geo{};
-  xpsnr_geometry((int)w, (int)h, (int)w, (int)h, 1, (int)bit_depth, &geo);
-  if (geo.bv == 2 && ((w | h) & 1)) return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: odd size above 2048x1152");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
-  const size_t plane_bytes = (size_t)w * h * es;
-  const void* host[4] = {ref, ref_m1, ref_m2, dis};
-  void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-  unsigned long long* blk = nullptr;
-  double *wb = nullptr, *ext3 = nullptr;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 4 && e == hipSuccess; ++i) {
-    if (!host[i]) continue;
-    e = hipMalloc(&dev[i], plane_bytes);
-    if (e == hipSuccess)
-      e = hipMemcpy2D(dev[i], (size_t)w * es, host[i], (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc((void**)&blk, (size_t)geo.n_blk * kXpBlockVals * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&wb, (size_t)geo.n_blk * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&ext3, PQA_EXT3_DOUBLES * sizeof(double));
-  if (e == hipSuccess) {
-    PlaneRun r3[3] = {{dev[0], (int64_t)w, (int64_t)w * h}}, d3[3] = {{dev[3], (int64_t)w, (int64_t)w * h}};
-    e = launch_xpsnr_blocks(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, r3, d3, 1, dev[1], dev[1] ? (int64_t)w : 0, dev[2],
-                            dev[2] ? (int64_t)w : 0, hfr != 0, geo, blk);
-  }
-  if (e == hipSuccess) {
-    XpFinalizeArgs xa{};
-    xa.n_frames = 1;
-    xa.blk = blk;
-    xa.wbuf = wb;
-    xa.ext3 = ext3;
-    xa.ext_stride = PQA_EXT3_DOUBLES;
-    xa.slot_base = 0;
-    xa.capacity = 1;
-    xa.g = geo;
-    e = launch_xpsnr_finalize(nullptr, xa);
-  }
-  std::vector<unsigned long long> hb;
-  double row[PQA_EXT3_DOUBLES];
-  if (e == hipSuccess) {
-    hb.resize((size_t)geo.n_blk * kXpBlockVals);
-    e = hipMemcpy(hb.data(), blk, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  }
-  if (e == hipSuccess) e = hipMemcpy(row, ext3, sizeof row, hipMemcpyDeviceToHost);
-  for (void* q : {dev[0], dev[1], dev[2], dev[3], (void*)blk, (void*)wb, (void*)ext3})
-    if (q) hipFree(q);
-  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_xpsnr_blocks: %s", hipGetErrorString(e));
-  for (int k = 0; k < geo.n_blk; ++k)
-    for (int i = 0; i < 3; ++i) out[k * 3 + i] = hb[(size_t)k * kXpBlockVals + i];
-  if (wsse) *wsse = row[PQA_EXT3_WSSE];
-  return PQA_OK;
-}
-
-int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
-                         uint32_t bit_depth, int32_t full_range, float* gmap, double* si_ti) {
-  if (!cur || !si_ti || w < 3 || h < 3 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_siti_plane: bad argument");
-  const int es = bit_depth > 8 ? 2 : 1;
-  if (row_pitch_bytes < (int64_t)w * es || row_pitch_bytes % es)
-    return fail(nullptr, PQA_EINVAL, "pqa_debug_siti_plane: bad row pitch %lld", (long long)row_pitch_bytes);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
-  const size_t plane_bytes = (size_t)w * h * es, map_floats = (size_t)(w - 2) * (h - 2);
-  const void* host[2] = {cur, prev};
-  void* dev[2] = {nullptr, nullptr};
-  double *part = nullptr, *ext4 = nullptr;
-  float* dmap = nullptr;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-    if (!host[i]) continue;
-    e = hipMalloc(&dev[i], plane_bytes);
-    if (e == hipSuccess)
-      e = hipMemcpy2D(dev[i], (size_t)w * es, host[i], (size_t)row_pitch_bytes, (size_t)w * es, h, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc((void**)&part, (size_t)siti_partials((int)w, (int)h) * 2 * 4 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&ext4, PQA_EXT4_DOUBLES * sizeof(double));
-  if (e == hipSuccess && gmap) e = hipMalloc((void**)&dmap, map_floats * sizeof(float));
-  if (e == hipSuccess) {
-    const PlaneRun clip[2] = {{dev[0], (int64_t)w, (int64_t)w * h}, {dev[0], (int64_t)w, (int64_t)w * h}};
-    const void* p0[2] = {dev[1], nullptr};
-    const int64_t pp[2] = {dev[1] ? (int64_t)w : 0, 0};
-    const bool full[2] = {full_range != 0, false};
-    e = launch_siti(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, clip, p0, pp, full, 1, 1, (int)w, (int)h, part, ext4,
-                    PQA_EXT4_DOUBLES, 0, 1, dmap);
-  }
-  double row[PQA_EXT4_DOUBLES];
-  if (e == hipSuccess) e = hipMemcpy(row, ext4, sizeof row, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && gmap) e = hipMemcpy(gmap, dmap, map_floats * sizeof(float), hipMemcpyDeviceToHost);
-  for (void* q : {dev[0], dev[1], (void*)part, (void*)ext4, (void*)dmap})
-    if (q) hipFree(q);
-  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_siti_plane: %s", hipGetErrorString(e));
-  si_ti[0] = row[PQA_EXT4_SI];
-  si_ti[1] = row[PQA_EXT4_TI];
   return PQA_OK;
 }
 

@@ -1,0 +1,227 @@
+// The context behind the C ABI and what its three host units share: pqa_api.hip (context lifetime, the submit paths, collect,
+// profiling), pqa_side.hip (the one-shot analyses that leave the scoring chain alone) and pqa_debug.hip (the pqa_debug_*
+// entries).  Private to the library: callers see include/pqa_vmaf.h only.
+#pragma once
+#include "../../include/pqa_vmaf.h"
+
+#include <atomic>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "host_pack.h"
+#include "host_ring.h"
+#include "kernels.h"
+
+namespace pqa {
+
+struct Level {
+  int w = 0, h = 0;
+  int64_t pitch = 0, frame_pitch = 0;  // elements (float)
+  float* ref = nullptr;
+  float* dis = nullptr;
+};
+
+struct Half {
+  uint8_t* pinned = nullptr;
+  uint8_t* dev = nullptr;
+  hipEvent_t copied = nullptr, computed = nullptr;
+  bool copied_pending = false, computed_pending = false;
+};
+
+struct ProfEv {
+  hipEvent_t a, b;
+  int id, frames;
+};
+
+constexpr int kBatchEvents = 64;  // ring of per-batch completion events
+constexpr int kLumaOutFrames = 2048;  // luma statistics kept on the device between host copies
+
+// The grow-only device buffers of the side analyses, pqa_ctx::side_buf below (side_reserve, pqa_side.hip).
+enum SideBuf {
+  SIDE_XSSE_PART = 0, SIDE_XSSE_NORM_REF, SIDE_XSSE_NORM_DIS, SIDE_XSSE_OUT,   // pqa_cross_sse[_device], cross_sse.hip
+  SIDE_XSSE_REF, SIDE_XSSE_DIS,                                                // pqa_cross_sse: its two rings of uploaded frames
+  SIDE_SHIFT_PART, SIDE_SHIFT_ROWSQ, SIDE_SHIFT_OUT,                           // pqa_shift_sse[_device], shift_sse.hip
+  SIDE_LEVEL_OUT,                                                              // pqa_level_stats[_device], level_stats.hip
+  kSideBufs
+};
+
+}  // namespace pqa
+
+struct pqa_ctx {
+  pqa_config cfg{};
+  int device = 0;
+  hipStream_t own_stream = nullptr, stream = nullptr, copy_stream = nullptr;
+  hipStream_t aux[2] = {nullptr, nullptr};  // ADM and motion/PSNR/SSIM chains run beside the VIF chain
+  hipEvent_t fork_ev = nullptr, join_ev[2] = {nullptr, nullptr};
+  pqa::Elem elem = pqa::ELEM_U8;
+  int esize = 1;
+  float inv_scale = 1.0f;
+  int pw[3] = {0, 0, 0}, ph[3] = {0, 0, 0};
+  int n_planes = 1;
+  int B = 8, HB = 8, capacity = 16384, k_sub = 1;  // B: frames per launch; HB: frames per host-staging half
+  pqa::Level vif_lv[4], adm_lv[4];
+  double* vif_part[4] = {};
+  long long* vif_fx_part[4] = {};  // fixed-point VIF: int64 partials instead of (num, den) doubles
+  uint16_t* vif_lut = nullptr;     // integer_vif.c's log2 table, entries 32768..65535
+  bool vif_fixed = false, motion_fixed = false, adm_fixed = false;
+  long long* adm_fx_part[4] = {};   // fixed-point ADM: per-row int64 partials
+  long long* adm_fx_acc = nullptr;  // [capacity][4][6] ring of accumulators, finished on the host in pqa_collect
+  int32_t* adm_div_lut = nullptr;
+  pqa::AdmFxScale adm_fx[4] = {};
+  unsigned long long* motion_fx_part = nullptr;
+  int vif_tiles[4] = {};
+  int vif_part_cap0 = 0;   // partial pairs per frame the scale-0 buffer holds (tiled kernels or the march kernel)
+  double* adm_part[4] = {};
+  int adm_tiles[4] = {};
+  float adm_area[4] = {};
+  double* motion_part = nullptr;
+  int motion_tiles_n = 0;
+  unsigned long long* sse_part[3] = {};
+  unsigned long long* sse_part_b[3] = {};
+  unsigned long long* sse_tile_part[3] = {};
+  double* ssim_part[3] = {};
+  int ssim_tiles_n[3] = {};
+  double ssim_norm[3] = {};
+  double* records = nullptr;
+  // SSIM family (PQA_FEAT_FLOAT_SSIM / PQA_FEAT_MS_SSIM; ssim_family.hip): nothing is allocated unless one of the bits is set
+  double* ext = nullptr;             // [capacity][PQA_EXT_DOUBLES] ring beside `records`
+  pqa::Level ms_lv[pqa::kMsScales];            // MS-SSIM scales 1..4: f32 planes for ssf_sb frames
+  double* ms_part[pqa::kMsScales] = {};   // [ssf_sb][tiles][4] per scale
+  int ms_tiles[pqa::kMsScales] = {};
+  double* fs_part = nullptr;         // float_ssim: [ssf_sb][tiles][4]
+  int fs_tiles = 0, fs_box = 1;
+  int ssf_sb = 0;                    // frames per pass through the pyramid (bounds its memory at 2160p)
+  // CIEDE2000 (PQA_FEAT_CIEDE; ciede.hip): nothing is allocated unless the bit is set
+  double* ciede_part = nullptr;      // [B][ciede_tiles]
+  int ciede_tiles_n = 0;
+  // CAMBI (PQA_FEAT_CAMBI; cambi.hip): nothing is allocated unless the bit is set
+  pqa::CambiParams cambi_prm{};
+  pqa::CambiWork cambi_wk{};
+  int cambi_sb = 0;                  // frames per pass (bounds the work planes at 2160p)
+  // PSNR-HVS (PQA_FEAT_PSNR_HVS; psnr_hvs.hip): nothing is allocated unless the bit is set
+  double* ext2 = nullptr;            // [capacity][PQA_EXT2_DOUBLES] ring beside `records`
+  pqa::PsnrHvsGeometry phv_geo{};
+  double* phv_part = nullptr;        // [B][phv_geo.tile0[3]]
+  // XPSNR (PQA_FEAT_XPSNR; xpsnr.hip): nothing is allocated unless the bit is set
+  double* ext3 = nullptr;            // [capacity][PQA_EXT3_DOUBLES] ring beside `records`
+  pqa::XpsnrGeometry xp_geo{};
+  unsigned long long* xp_blk = nullptr;   // [B][xp_geo.n_blk][kXpBlockVals]
+  double* xp_w = nullptr;                 // [B][xp_geo.n_blk] weights
+  uint8_t* xp_hist[2] = {nullptr, nullptr};   // reference luma planes the chain keeps (the last two of the last batch)
+  int64_t xp_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
+  int64_t xp_hist_pitch = 0;                  // bytes
+  uint8_t* xp_prev = nullptr;        // pqa_submit_surfaces: its shifted prev_ref (allocated on first use)
+  int64_t xp_last = -1;              // last frame of the previous batch (the chain continues at xp_last + 1)
+  int xp_armed = -1;                 // pqa_set_ref_history: planes armed in xp_hist[0..n) for the next batch (-1: none)
+  // SI / TI (PQA_FEAT_SITI; siti.hip): nothing is allocated unless the bit is set
+  double* ext4 = nullptr;            // [capacity][PQA_EXT4_DOUBLES] ring beside `records`
+  double* st_part = nullptr;         // [B][2][siti_partials][4]
+  uint8_t* st_hist[2] = {nullptr, nullptr};   // the last luma plane of each clip's chain (0: distorted, 1: reference)
+  int64_t st_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
+  int64_t st_hist_pitch = 0;                  // bytes
+  bool st_armed[2] = {false, false};          // pqa_set_dis_history / the reference history armed st_hist[z] as frame first-1
+  // capture integrity (PQA_FEAT_INTEGRITY; integrity.hip): nothing is allocated unless the bit is set
+  double* ext5 = nullptr;            // [capacity][PQA_EXT5_DOUBLES] ring beside `records`
+  unsigned long long* ig_part = nullptr;      // [B][3][kIntegrityBlocks][2]
+  uint8_t* ig_hist[3] = {nullptr, nullptr, nullptr};   // the planes of the last distorted frame of the chain
+  int64_t ig_hist_pitch[3] = {0, 0, 0};       // bytes
+  int64_t ig_hist_idx = -1;                   // its frame index (-1: empty)
+  bool ig_armed = false;                      // pqa_set_dis_history_planes armed ig_hist as frame first-1
+  uint32_t black_thr = 0;                     // pqa_set_black_threshold
+  bool started = false;                       // a batch was launched since pqa_create / pqa_reset
+  // pqa_frame_sad / pqa_frame_sad_device (allocated on first use)
+  uint8_t* ig_anchor[3] = {nullptr, nullptr, nullptr};  // the anchor frame's planes (pitches: ig_hist_pitch)
+  uint8_t* ig_stage = nullptr;                // FB frames of host planes (slot layout: ig_stage_off, ig_stage_bytes)
+  size_t ig_stage_off[3] = {0, 0, 0}, ig_stage_bytes = 0;
+  unsigned long long* ig_out = nullptr;       // [B][3] results of one launch
+  unsigned long long* luma_part = nullptr;
+  unsigned long long* luma_out = nullptr;
+  // host frames of the side analyses (pqa_luma_stats, pqa_cross_sse, pqa_shift_sse, pqa_level_stats): two pinned + two device
+  // halves of LB luma planes (luma_staging_ensure; `computed` is not used here: one stream orders uploads and kernels)
+  pqa::Half luma_half[2];
+  int64_t luma_pitch = 0;
+  int LB = 0;
+  bool luma_ready = false;
+  uint32_t luma_gray = PQA_GRAY_LUMA;
+  bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
+  void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use
+  size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes
+  // motion continuity
+  uint8_t* last_luma = nullptr;
+  int64_t last_luma_pitch = 0;  // bytes
+  int64_t last_index = -1;
+  bool have_last = false, halo_armed = false;
+  // host staging (pqa_submit path)
+  pqa::Half half[2];
+  int cur_half = 0, pending = 0;
+  int64_t pending_first = 0;
+  size_t slot_bytes = 0;
+  size_t plane_off[2][3] = {};
+  int64_t slot_row_pitch[3] = {};
+  bool staging_ready = false;
+  std::thread pin_thread;            // pins the second staging half while the first one fills (ensure_staging)
+  hipError_t pin_err = hipSuccess;   // its result; read after joining it (staging_half_ready)
+  uint8_t* surf_dev = nullptr;   // pqa_submit_surfaces: B slots of unpacked planes (device only, allocated on first use)
+  std::unique_ptr<pqa::host::PackPool> pack_pool;
+  bool pack_pool_tried = false;
+  std::vector<pqa::host::PackTask> pack_tasks;
+  // record-ring bookkeeping (host side): which frame a slot holds, whether it was collected, and the batch that
+  // writes it.  Lets pqa_collect wait for ITS batch only and makes the PQA_ESTATE promises of the header real.
+  pqa::host::RecordRing ring;             // host_ring.h
+  hipEvent_t batch_ev[pqa::kBatchEvents] = {};
+  uint64_t batch_ev_seq[pqa::kBatchEvents] = {};  // sequence number last recorded into each event
+  uint64_t batch_seq = 0;            // batches launched so far (the next batch gets batch_seq + 1)
+  uint64_t done_seq = 0;             // every batch <= done_seq is known to be complete
+  std::atomic<int> cancelled{0};
+  std::string err;
+  std::vector<void*> allocs;
+  // profiling
+  int multi_stream = 0;              // 0 one stream; 1 three streams from the start of a batch; 2 three streams behind VIF scale 0
+  int vif_s0_mode = pqa::VIF_S0_AUTO;   // PQA_VIF_MFMA, read once in pqa_create
+  int adm_mode = pqa::ADM_AUTO;         // PQA_ADM_MARCH, read once in pqa_create
+  int motion_mode = pqa::MOTION_AUTO;   // PQA_MOTION_MARCH, read once in pqa_create
+  bool trace = false;   // PQA_TRACE=1: synchronise after every launch and name it on stderr (localises a stall)
+  bool prof = false;
+  uint32_t prof_mask = 0xffffffffu;
+  std::vector<pqa::ProfEv> evs;
+  double prof_ms[PQA_PROF_KERNELS] = {};
+  uint64_t prof_n[PQA_PROF_KERNELS] = {}, prof_frames[PQA_PROF_KERNELS] = {};
+};
+
+namespace pqa {
+
+// sets pqa_last_error (of the context, or of the calling thread when c is null) and returns code; defined in pqa_api.hip
+int fail(pqa_ctx* c, int code, const char* fmt, ...);
+
+#define HIPCHK(c, expr)                                                                          \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess)                                                                        \
+      return pqa::fail((c), e_ == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "%s failed: %s", #expr, \
+                  hipGetErrorString(e_));                                                        \
+  } while (0)
+
+template <typename T>
+int dev_alloc(pqa_ctx* c, T** out, size_t count) {
+  void* p = nullptr;
+  if (count == 0) count = 1;
+  HIPCHK(c, hipMalloc(&p, count * sizeof(T)));
+  c->allocs.push_back(p);
+  *out = (T*)p;
+  return PQA_OK;
+}
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+inline void copy_plane_rows(uint8_t* dst, int64_t dst_pitch, const uint8_t* src, int64_t src_pitch, size_t row_bytes, int h) {
+  if (dst_pitch == src_pitch) {
+    memcpy(dst, src, (size_t)dst_pitch * (h - 1) + row_bytes);
+    return;
+  }
+  for (int y = 0; y < h; ++y) memcpy(dst + (int64_t)y * dst_pitch, src + (int64_t)y * src_pitch, row_bytes);
+}
+
+}  // namespace pqa

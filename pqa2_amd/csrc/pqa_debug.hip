@@ -1,0 +1,277 @@
+// The pqa_debug_* entries of the C ABI: single kernels and host tables exposed to the tests, on the default stream with
+// scratch memory of their own (no context).  Declarations: include/pqa_vmaf.h.
+#include "pqa_ctx.h"
+
+using namespace pqa;
+
+namespace {
+
+int need_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
+  return PQA_OK;
+}
+
+// the sample size of a plane at bit_depth into *es; its rows are whole samples and at least w of them apart
+int plane_pitch_rule(const char* who, uint32_t bit_depth, uint32_t w, int64_t row_pitch_bytes, int* es) {
+  *es = bit_depth > 8 ? 2 : 1;
+  if (row_pitch_bytes < (int64_t)w * *es || row_pitch_bytes % *es)
+    return fail(nullptr, PQA_EINVAL, "%s: bad row pitch %lld", who, (long long)row_pitch_bytes);
+  return PQA_OK;
+}
+
+// The device allocations of one call, freed on every return path.  `err` is the first failure: once it is set, nothing
+// more is allocated or copied, so a call makes its buffers in a row and looks at err once.
+struct Scratch {
+  void* held[12];
+  int n = 0;
+  hipError_t err = hipSuccess;
+  ~Scratch() { for (int i = 0; i < n; ++i) hipFree(held[i]); }
+  template <typename T>
+  T* get(size_t count) {
+    void* p = nullptr;
+    if (err == hipSuccess) err = n < 12 ? hipMalloc(&p, count * sizeof(T)) : hipErrorOutOfMemory;
+    if (p) held[n++] = p;
+    return (T*)p;
+  }
+  // a packed copy of a host plane (null stays null)
+  void* plane(const void* host, int64_t row_pitch_bytes, size_t row_bytes, uint32_t h) {
+    if (!host) return nullptr;
+    void* p = get<uint8_t>(row_bytes * h);
+    if (err == hipSuccess) err = hipMemcpy2D(p, row_bytes, host, (size_t)row_pitch_bytes, row_bytes, h, hipMemcpyHostToDevice);
+    return p;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int pqa_debug_vif_march_table(uint16_t* out, int32_t capacity_halfwords) { return vif_march_table(out, capacity_halfwords); }
+int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* out6) {
+  if (!out6 || width == 0 || height == 0 || width > 65536 || height > 65536) return PQA_EINVAL;
+  int shape[6];
+  vif_march_shape((int)width, (int)height, shape);
+  for (int i = 0; i < 6; ++i) out6[i] = shape[i];
+  return PQA_OK;
+}
+
+int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out) {
+  if (n < 0 || (n > 0 && (!lab_pairs || !de_out))) return fail(nullptr, PQA_EINVAL, "bad argument");
+  const int rc = need_device();
+  if (rc != PQA_OK) return rc;
+  if (n == 0) return PQA_OK;
+  std::vector<float> in((size_t)n * 6), out((size_t)n);
+  for (size_t i = 0; i < in.size(); ++i) in[i] = (float)lab_pairs[i];
+  Scratch s;
+  float* d_in = s.get<float>(in.size());
+  float* d_out = s.get<float>(out.size());
+  hipError_t e = s.err;
+  if (e == hipSuccess) e = hipMemcpy(d_in, in.data(), in.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_ciede_debug(nullptr, d_in, n, d_out);
+  if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, out.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_ciede2000: %s", hipGetErrorString(e));
+  for (int32_t i = 0; i < n; ++i) de_out[i] = (double)out[i];
+  return PQA_OK;
+}
+
+int pqa_debug_cambi_params(uint32_t w, uint32_t h, uint32_t bit_depth, int32_t* out, int32_t cap) {
+  if (!out || cap < PQA_CAMBI_PARAM_INTS) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: null or short output");
+  if (w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: unsupported %ux%u at %u bit", w, h, bit_depth);
+  static_assert(kCambiParamInts == PQA_CAMBI_PARAM_INTS, "pqa_debug_cambi_params layout");
+  const CambiParams p = cambi_params((int)w, (int)h);
+  int i = 0;
+  out[i++] = p.ws; out[i++] = p.r; out[i++] = p.piw; out[i++] = p.mask_t;
+  for (int d = 0; d < kCambiDiffs; ++d) out[i++] = p.tvi[d];
+  for (int d = 0; d < kCambiDiffs; ++d) out[i++] = p.weights[d];
+  for (int s = 0; s < kCambiScales; ++s) { out[i++] = p.sw[s]; out[i++] = p.sh[s]; }
+  return PQA_OK;
+}
+
+int pqa_debug_cambi_cmap(const void* luma, int64_t row_pitch_bytes, uint32_t w, uint32_t h, uint32_t bit_depth, float* cmap,
+                         int64_t cap, double* score) {
+  if (!luma || !cmap || w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: bad argument");
+  int es = 1;
+  int rc = plane_pitch_rule("pqa_debug_cambi_cmap", bit_depth, w, row_pitch_bytes, &es);
+  if (rc != PQA_OK) return rc;
+  const CambiParams p = cambi_params((int)w, (int)h);
+  const int64_t total = p.off[kCambiScales];
+  if (cap < total) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_cmap: cmap holds %lld floats, needs %lld", (long long)cap,
+                               (long long)total);
+  if ((rc = need_device()) != PQA_OK) return rc;
+  Scratch s;
+  s.err = cambi_prepare(p, (int)bit_depth);
+  void* src = s.plane(luma, row_pitch_bytes, (size_t)w * es, h);
+  double* ext = s.get<double>(PQA_EXT_DOUBLES);
+  CambiWork wk{};
+  wk.plane = s.get<uint16_t>((size_t)total);
+  wk.mask = s.get<uint8_t>((size_t)total);
+  wk.cmap = s.get<float>((size_t)total);
+  wk.hist = s.get<uint32_t>((size_t)kCambiScales * 2048);
+  wk.sel = s.get<int32_t>((size_t)kCambiScales * 4);
+  wk.partials = s.get<double>((size_t)p.chunk[kCambiScales]);
+  hipError_t e = s.err;
+  if (e == hipSuccess) {
+    const PlaneRun run{src, (int64_t)w, (int64_t)w * h};
+    e = launch_cambi(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, run, 1, (int)w, (int)h, (int)bit_depth, p, wk, ext, PQA_EXT_DOUBLES,
+                     PQA_EXT_CAMBI, 0, 1, 1);
+  }
+  if (e == hipSuccess) e = hipMemcpy(cmap, wk.cmap, (size_t)total * sizeof(float), hipMemcpyDeviceToHost);
+  double ext_row[PQA_EXT_DOUBLES];
+  if (e == hipSuccess) e = hipMemcpy(ext_row, ext, sizeof ext_row, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_cambi_cmap: %s", hipGetErrorString(e));
+  if (score) *score = ext_row[PQA_EXT_CAMBI];
+  return PQA_OK;
+}
+
+int pqa_debug_psnr_hvs_dct8x8(const int32_t* in, int32_t* out, int32_t n) {
+  if (!in || !out || n < 0) return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_dct8x8: bad argument");
+  psnr_hvs_fdct8x8_host(in, out, n);
+  return PQA_OK;
+}
+
+int pqa_debug_psnr_hvs_tables(float* out, int32_t cap) {
+  static_assert(kPhvTableFloats == PQA_PSNR_HVS_TABLE_FLOATS, "pqa_debug_psnr_hvs_tables layout");
+  if (!out || cap < PQA_PSNR_HVS_TABLE_FLOATS)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_tables: null or short output");
+  psnr_hvs_tables(out);
+  return PQA_OK;
+}
+
+int pqa_debug_psnr_hvs_plane(const void* ref, const void* dis, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
+                             uint32_t bit_depth, uint32_t plane_kind, float* block_err, double* mse) {
+  if (!ref || !dis || !block_err || w < 8 || h < 8 || w > 16384 || h > 16384 || plane_kind > 2 ||
+      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_psnr_hvs_plane: bad argument");
+  int es = 1;
+  int rc = plane_pitch_rule("pqa_debug_psnr_hvs_plane", bit_depth, w, row_pitch_bytes, &es);
+  if (rc == PQA_OK) rc = need_device();
+  if (rc != PQA_OK) return rc;
+  // the plane pair stands in for all three planes; plane_kind picks whose tables and block sums are read back
+  const int pw[3] = {(int)w, (int)w, (int)w}, ph[3] = {(int)h, (int)h, (int)h};
+  PsnrHvsGeometry geo{};
+  psnr_hvs_geometry(pw, ph, &geo);
+  const int nb = geo.nbx[0] * geo.nby[0];
+  Scratch s;
+  s.err = psnr_hvs_prepare();
+  void* src = s.plane(ref, row_pitch_bytes, (size_t)w * es, h);
+  void* dst = s.plane(dis, row_pitch_bytes, (size_t)w * es, h);
+  double* part = s.get<double>((size_t)geo.tile0[3]);
+  double* ext2 = s.get<double>(PQA_EXT2_DOUBLES);
+  float* err = s.get<float>((size_t)nb);
+  hipError_t e = s.err;
+  if (e == hipSuccess) {
+    PlaneRun r3[3], d3[3];
+    for (int p = 0; p < 3; ++p) {
+      r3[p] = PlaneRun{src, (int64_t)w, (int64_t)w * h};
+      d3[p] = PlaneRun{dst, (int64_t)w, (int64_t)w * h};
+    }
+    e = launch_psnr_hvs(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, r3, d3, 1, geo, part, err, (int)plane_kind);
+  }
+  if (e == hipSuccess) {
+    PsnrHvsFinalizeArgs pa{};
+    pa.n_frames = 1;
+    pa.ext2 = ext2;
+    pa.ext_stride = PQA_EXT2_DOUBLES;
+    pa.slot_base = 0; pa.slot_step = 1; pa.capacity = 1;
+    pa.partials = part;
+    for (int p = 0; p < 4; ++p) pa.tile0[p] = geo.tile0[p];
+    for (int p = 0; p < 3; ++p) pa.blocks[p] = nb;
+    pa.peak = (double)((1 << bit_depth) - 1);
+    e = launch_psnr_hvs_finalize(nullptr, pa);
+  }
+  if (e == hipSuccess) e = hipMemcpy(block_err, err, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost);
+  double row[PQA_EXT2_DOUBLES];
+  if (e == hipSuccess) e = hipMemcpy(row, ext2, sizeof row, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_psnr_hvs_plane: %s", hipGetErrorString(e));
+  if (mse) *mse = row[PQA_EXT2_PSNR_HVS_MSE + plane_kind];
+  return PQA_OK;
+}
+
+int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const void* ref_m2, const void* dis, int64_t row_pitch_bytes,
+                           uint32_t w, uint32_t h, uint32_t bit_depth, int32_t hfr, uint64_t* out, double* wsse) {
+  if (!ref || !dis || !out || w < 16 || h < 16 || w > 16384 || h > 16384 ||
+      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: bad argument");
+  int es = 1;
+  int rc = plane_pitch_rule("pqa_debug_xpsnr_blocks", bit_depth, w, row_pitch_bytes, &es);
+  if (rc != PQA_OK) return rc;
+  XpsnrGeometry geo{};
+  xpsnr_geometry((int)w, (int)h, (int)w, (int)h, 1, (int)bit_depth, &geo);
+  if (geo.bv == 2 && ((w | h) & 1)) return fail(nullptr, PQA_EINVAL, "pqa_debug_xpsnr_blocks: odd size above 2048x1152");
+  if ((rc = need_device()) != PQA_OK) return rc;
+  Scratch s;
+  const void* host[4] = {ref, ref_m1, ref_m2, dis};
+  void* dev[4];
+  for (int i = 0; i < 4; ++i) dev[i] = s.plane(host[i], row_pitch_bytes, (size_t)w * es, h);
+  auto* blk = s.get<unsigned long long>((size_t)geo.n_blk * kXpBlockVals);
+  double* wb = s.get<double>((size_t)geo.n_blk);
+  double* ext3 = s.get<double>(PQA_EXT3_DOUBLES);
+  hipError_t e = s.err;
+  if (e == hipSuccess) {
+    PlaneRun r3[3] = {{dev[0], (int64_t)w, (int64_t)w * h}}, d3[3] = {{dev[3], (int64_t)w, (int64_t)w * h}};
+    e = launch_xpsnr_blocks(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, r3, d3, 1, dev[1], dev[1] ? (int64_t)w : 0, dev[2],
+                            dev[2] ? (int64_t)w : 0, hfr != 0, geo, blk);
+  }
+  if (e == hipSuccess) {
+    XpFinalizeArgs xa{};
+    xa.n_frames = 1;
+    xa.blk = blk;
+    xa.wbuf = wb;
+    xa.ext3 = ext3;
+    xa.ext_stride = PQA_EXT3_DOUBLES;
+    xa.slot_base = 0;
+    xa.capacity = 1;
+    xa.g = geo;
+    e = launch_xpsnr_finalize(nullptr, xa);
+  }
+  std::vector<unsigned long long> hb;
+  double row[PQA_EXT3_DOUBLES];
+  if (e == hipSuccess) {
+    hb.resize((size_t)geo.n_blk * kXpBlockVals);
+    e = hipMemcpy(hb.data(), blk, hb.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  }
+  if (e == hipSuccess) e = hipMemcpy(row, ext3, sizeof row, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_xpsnr_blocks: %s", hipGetErrorString(e));
+  for (int k = 0; k < geo.n_blk; ++k)
+    for (int i = 0; i < 3; ++i) out[k * 3 + i] = hb[(size_t)k * kXpBlockVals + i];
+  if (wsse) *wsse = row[PQA_EXT3_WSSE];
+  return PQA_OK;
+}
+
+int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
+                         uint32_t bit_depth, int32_t full_range, float* gmap, double* si_ti) {
+  if (!cur || !si_ti || w < 3 || h < 3 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_siti_plane: bad argument");
+  int es = 1;
+  int rc = plane_pitch_rule("pqa_debug_siti_plane", bit_depth, w, row_pitch_bytes, &es);
+  if (rc == PQA_OK) rc = need_device();
+  if (rc != PQA_OK) return rc;
+  const size_t map_floats = (size_t)(w - 2) * (h - 2);
+  Scratch s;
+  void* dev[2] = {s.plane(cur, row_pitch_bytes, (size_t)w * es, h), s.plane(prev, row_pitch_bytes, (size_t)w * es, h)};
+  double* part = s.get<double>((size_t)siti_partials((int)w, (int)h) * 2 * 4);
+  double* ext4 = s.get<double>(PQA_EXT4_DOUBLES);
+  float* dmap = gmap ? s.get<float>(map_floats) : nullptr;
+  hipError_t e = s.err;
+  if (e == hipSuccess) {
+    const PlaneRun clip[2] = {{dev[0], (int64_t)w, (int64_t)w * h}, {dev[0], (int64_t)w, (int64_t)w * h}};
+    const void* p0[2] = {dev[1], nullptr};
+    const int64_t pp[2] = {dev[1] ? (int64_t)w : 0, 0};
+    const bool full[2] = {full_range != 0, false};
+    e = launch_siti(nullptr, es == 1 ? ELEM_U8 : ELEM_U16, clip, p0, pp, full, 1, 1, (int)w, (int)h, part, ext4,
+                    PQA_EXT4_DOUBLES, 0, 1, dmap);
+  }
+  double row[PQA_EXT4_DOUBLES];
+  if (e == hipSuccess) e = hipMemcpy(row, ext4, sizeof row, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && gmap) e = hipMemcpy(gmap, dmap, map_floats * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_siti_plane: %s", hipGetErrorString(e));
+  si_ti[0] = row[PQA_EXT4_SI];
+  si_ti[1] = row[PQA_EXT4_TI];
+  return PQA_OK;
+}
+
+}  // extern "C"

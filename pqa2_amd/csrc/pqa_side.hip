@@ -1,0 +1,578 @@
+// The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
+// temporal / spatial / level alignment.  Each has an entry for a clip in HBM and one for frames in host memory; the host
+// entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
+// Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
+#include "pqa_ctx.h"
+
+#include <climits>
+#include <cstdio>
+
+using namespace pqa;
+
+namespace {
+
+int chunk_len(int total, int done, int cap) { return total - done < cap ? total - done : cap; }
+
+// ---- argument rules; no device call ----------------------------------------------------------------------------------
+// `who` opens the message ("cross_sse: ", "plane 1 ", "").
+
+// A clip in HBM: both pitches are whole samples, and rows lie at least min_row bytes apart.
+int check_device_clip(pqa_ctx* c, const char* who, int64_t row_pitch, int64_t frame_pitch, int64_t min_row) {
+  if (row_pitch % c->esize || frame_pitch % c->esize) return fail(c, PQA_EINVAL, "%spitch is not a multiple of the sample size", who);
+  if (row_pitch < min_row) return fail(c, PQA_EINVAL, "%spitch smaller than a row", who);
+  return PQA_OK;
+}
+
+// A list of n host frames, `step` pointers from one to the next (`kind`: "reference ", "captured ", ""): rows `stride` bytes
+// apart hold a row, no pointer is null.  The entries disagree on a negative stride -- pqa_level_stats and pqa_frame_sad
+// refuse it, the others let it pass the unsigned comparison -- and each keeps its answer: refuse_negative.
+int check_host_frames(pqa_ctx* c, const char* who, const char* kind, const void* const* frames, int step, int n, int64_t stride,
+                      size_t row_bytes, bool refuse_negative) {
+  if (n > 0 && ((refuse_negative && stride < 0) || (size_t)stride < row_bytes))
+    return fail(c, PQA_EINVAL, "%sstride smaller than a row", who);
+  for (int f = 0; f < n; ++f)   // before anything is queued
+    if (!frames[(size_t)f * step]) return fail(c, PQA_EINVAL, "%s%sframe %d pointer is null", who, kind, f);
+  return PQA_OK;
+}
+
+// ---- host frames onto the stream ---------------------------------------------------------------------------------------
+// the two pinned + two device halves of LB luma planes that the host entries pack their frames into
+int luma_staging_ensure(pqa_ctx* c) {
+  if (c->luma_ready) return PQA_OK;   // lazily: most contexts never detect bookends
+  c->luma_pitch = round_up((int64_t)c->pw[0] * c->esize, 64);
+  c->LB = c->B < 8 ? c->B : 8;
+  const size_t half = (size_t)c->luma_pitch * c->ph[0] * c->LB;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+    Half& H = c->luma_half[i];
+    if (!H.pinned) e = hipHostMalloc((void**)&H.pinned, half, hipHostMallocDefault);
+    if (e == hipSuccess && !H.dev) e = hipMalloc((void**)&H.dev, half);
+    if (e == hipSuccess && !H.copied) e = hipEventCreateWithFlags(&H.copied, hipEventDisableTiming);
+  }
+  if (e != hipSuccess) {   // all six or none: a half-made set must not make every later call fail on a null handle
+    for (Half& H : c->luma_half) {
+      if (H.pinned) hipHostFree(H.pinned);
+      if (H.dev) hipFree(H.dev);
+      if (H.copied) hipEventDestroy(H.copied);
+      H = Half{};
+    }
+    return fail(c, e == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "luma staging allocation failed: %s", hipGetErrorString(e));
+  }
+  c->luma_ready = true;
+  return PQA_OK;
+}
+
+// n planes of row_bytes x h from frames[0 .. n) (rows `stride` bytes apart) through pinned half hf onto the stream: waits
+// until the upload that last used the half has left it, packs, queues the upload, records the half's event.  The planes
+// land in device half hf, one after the other -- or, with ring_base, frame k in slot (first + k) % ring_slots of that ring,
+// each uploaded as soon as it is packed (a ring may wrap inside a chunk).  A plane smaller than the luma plane travels
+// with the luma pitches.
+hipError_t stage_frames(pqa_ctx* c, int hf, const void* const* frames, int64_t stride, int n, size_t row_bytes, int h,
+                        uint8_t* ring_base = nullptr, int ring_slots = 1, int64_t first = 0) {
+  Half& H = c->luma_half[hf];
+  const size_t frame_bytes = (size_t)c->luma_pitch * c->ph[0];
+  hipError_t e = hipSuccess;
+  if (H.copied_pending) {
+    e = hipEventSynchronize(H.copied);
+    H.copied_pending = false;
+  }
+  for (int f = 0; f < n && e == hipSuccess; ++f) {
+    uint8_t* pin = H.pinned + (size_t)f * frame_bytes;
+    copy_plane_rows(pin, c->luma_pitch, (const uint8_t*)frames[f], stride, row_bytes, h);
+    if (ring_base)
+      e = hipMemcpyAsync(ring_base + (size_t)((first + f) % ring_slots) * frame_bytes, pin, frame_bytes, hipMemcpyHostToDevice,
+                         c->stream);
+  }
+  if (e == hipSuccess && !ring_base) e = hipMemcpyAsync(H.dev, H.pinned, (size_t)n * frame_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(H.copied, c->stream);
+  H.copied_pending = e == hipSuccess;
+  return e;
+}
+
+// The end of every entry, after its launches (e: the first error among them): the results go to the caller unless
+// something failed or the call was cancelled, and the stream is ALWAYS synchronised -- nothing queued on it may still point
+// at the pinned halves or at `out` when the call returns.
+int side_finish(pqa_ctx* c, const char* what, hipError_t e, void* out, const void* dev_out, size_t bytes) {
+  if (e == hipSuccess && !c->cancelled.load()) e = hipMemcpyAsync(out, dev_out, bytes, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  c->luma_half[0].copied_pending = c->luma_half[1].copied_pending = false;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (e != hipSuccess) return fail(c, PQA_EDEVICE, "%s failed: %s", what, hipGetErrorString(e));
+  if (es != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
+  return PQA_OK;
+}
+
+// a grow-only device buffer of the side analyses
+int side_reserve(pqa_ctx* c, SideBuf which, size_t bytes) {
+  if (bytes == 0) bytes = 1;
+  if (c->side_cap[which] >= bytes) return PQA_OK;
+  if (c->side_buf[which]) {
+    HIPCHK(c, hipFree(c->side_buf[which]));
+    c->side_buf[which] = nullptr;
+    c->side_cap[which] = 0;
+  }
+  HIPCHK(c, hipMalloc(&c->side_buf[which], bytes));
+  c->side_cap[which] = bytes;
+  return PQA_OK;
+}
+
+// the launch of pqa_frame_sad[_device]: n frames (at most B) of a device clip against the anchor planes, results to out
+int frame_sad_launch(pqa_ctx* c, const void* const anchor[3], const int64_t anchor_pitch_bytes[3], const pqa_device_clip* f,
+                     int n, uint64_t* out) {
+  const int es = c->esize;
+  PlaneRun cur[3] = {};
+  int64_t app[3] = {0, 0, 0};
+  for (int p = 0; p < c->n_planes; ++p) {
+    cur[p] = PlaneRun{f->plane[p], f->row_pitch[p] / es, f->frame_pitch[p] / es};
+    app[p] = anchor_pitch_bytes[p] / es;
+  }
+  if (!c->ig_out) {
+    const int rc = dev_alloc(c, &c->ig_out, (size_t)c->B * 3);
+    if (rc != PQA_OK) return rc;
+  }
+  const hipError_t e = launch_integrity(c->stream, c->elem, cur, anchor, app, c->pw, c->ph, c->n_planes, n, true, c->black_thr,
+                                        c->ig_part, nullptr, 0, 0, 1, c->ig_out);
+  return side_finish(c, "frame_sad", e, out, c->ig_out, (size_t)n * 3 * sizeof(uint64_t));
+}
+
+// ---- temporal alignment (cross_sse.hip): argument rules (no device call) and workspaces ------------------------------
+int xs_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_ref, int32_t n_dis, int32_t k_lo, int32_t k_hi,
+             const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!ref || !dis) return fail(c, PQA_EINVAL, "cross_sse: null clip pointer");
+  if (n_ref < 0 || n_dis < 0) return fail(c, PQA_EINVAL, "cross_sse: negative frame count");
+  if (k_lo > k_hi) return fail(c, PQA_EINVAL, "cross_sse: k_lo %d > k_hi %d", k_lo, k_hi);
+  if (k_lo < -64 || k_hi > 64) return fail(c, PQA_EINVAL, "cross_sse: offsets %d ... %d outside -64 ... 64", k_lo, k_hi);
+  if ((int64_t)k_hi - k_lo + 1 > 129) return fail(c, PQA_EINVAL, "cross_sse: span above 129");
+  if (!out) return fail(c, PQA_EINVAL, "cross_sse: null output pointer");
+  return PQA_OK;
+}
+
+constexpr int kXsTilesPerLaunch = 8;   // reference tiles (of 32 frames) per launch of the device-resident entry
+
+int xs_prepare(pqa_ctx* c, bool mfma, int span, int n_tiles, int32_t n_ref, int32_t n_dis) {
+  int rc = side_reserve(c, SIDE_XSSE_PART, xsse_part_bytes(mfma, c->pw[0], c->ph[0], span, n_tiles));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_XSSE_OUT, (size_t)n_ref * span * sizeof(uint64_t));
+  if (rc == PQA_OK && mfma) rc = side_reserve(c, SIDE_XSSE_NORM_REF, (size_t)n_ref * kXsseNormBlocks * sizeof(uint64_t));
+  if (rc == PQA_OK && mfma) rc = side_reserve(c, SIDE_XSSE_NORM_DIS, (size_t)n_dis * kXsseNormBlocks * sizeof(uint64_t));
+  return rc;
+}
+
+// ---- spatial alignment (shift_sse.hip): argument rules and workspaces ------------------------------------------------
+int sh_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int32_t radius, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "shift_sse: negative frame count");
+  if (radius < 0 || radius > kShiftMaxRadius) return fail(c, PQA_EINVAL, "shift_sse: radius %d outside 0 ... %d", radius, kShiftMaxRadius);
+  if (c->pw[0] <= 2 * radius || c->ph[0] <= 2 * radius)
+    return fail(c, PQA_EINVAL, "shift_sse: a %dx%d frame is not larger than twice the radius %d", c->pw[0], c->ph[0], radius);
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "shift_sse: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "shift_sse: null output pointer");
+  return PQA_OK;
+}
+
+int sh_prepare(pqa_ctx* c, int radius, int32_t n_frames) {
+  const int chunk = n_frames < kShiftChunk ? n_frames : kShiftChunk;
+  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  int rc = side_reserve(c, SIDE_SHIFT_PART, shift_part_bytes(c->elem, c->pw[0], c->ph[0], radius, chunk));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_SHIFT_ROWSQ, shift_rowsq_bytes(c->ph[0], radius, chunk));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_SHIFT_OUT, (size_t)n_frames * n * sizeof(uint64_t));
+  return rc;
+}
+
+// ---- level alignment (level_stats.hip): argument rules ---------------------------------------------------------------
+int lv_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int32_t plane, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "level_stats: negative frame count");
+  if (plane < 0 || plane >= c->n_planes) return fail(c, PQA_EINVAL, "level_stats: plane %d of a context with %d", plane, c->n_planes);
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "level_stats: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "level_stats: null output pointer");
+  return PQA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pqa_frame_sad_device(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_row_pitch[3],
+                         const pqa_device_clip* frames, int32_t n_frames, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!anchor_planes || !anchor_row_pitch || !frames || n_frames < 0 || (n_frames > 0 && !out))
+    return fail(c, PQA_EINVAL, "bad argument");
+  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return fail(c, PQA_ESTATE, "pqa_frame_sad_device needs PQA_FEAT_INTEGRITY");
+  for (int p = 0; p < c->n_planes; ++p) {
+    if (!anchor_planes[p] || !frames->plane[p]) return fail(c, PQA_EINVAL, "plane %d pointer is null", p);
+    char who[16];
+    snprintf(who, sizeof who, "plane %d ", p);
+    const int64_t row_bytes = (int64_t)c->pw[p] * c->esize;
+    int rc = check_device_clip(c, who, anchor_row_pitch[p], 0, row_bytes);
+    if (rc == PQA_OK) rc = check_device_clip(c, who, frames->row_pitch[p], frames->frame_pitch[p], row_bytes);
+    if (rc != PQA_OK) return rc;
+  }
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int done = 0; done < n_frames;) {
+    const int n = chunk_len(n_frames, done, c->B);
+    pqa_device_clip f = *frames;
+    for (int p = 0; p < c->n_planes; ++p) f.plane[p] = (const uint8_t*)frames->plane[p] + (int64_t)done * frames->frame_pitch[p];
+    const int rc = frame_sad_launch(c, anchor_planes, anchor_row_pitch, &f, n, out + (size_t)done * 3);
+    if (rc != PQA_OK) return rc;
+    done += n;
+  }
+  return PQA_OK;
+}
+
+int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_strides[3], const void* const* frames,
+                  const int64_t strides[3], int32_t n_frames, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!anchor_planes || !anchor_strides || n_frames < 0 || (n_frames > 0 && (!frames || !strides || !out)))
+    return fail(c, PQA_EINVAL, "bad argument");
+  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return fail(c, PQA_ESTATE, "pqa_frame_sad needs PQA_FEAT_INTEGRITY");
+  for (int p = 0; p < c->n_planes; ++p) {
+    const int64_t row_bytes = (int64_t)c->pw[p] * c->esize;
+    if (!anchor_planes[p]) return fail(c, PQA_EINVAL, "anchor plane %d pointer is null", p);
+    if (anchor_strides[p] < row_bytes) return fail(c, PQA_EINVAL, "plane %d stride smaller than a row", p);
+    if (n_frames == 0) continue;
+    char who[16];
+    snprintf(who, sizeof who, "plane %d ", p);
+    const int rc = check_host_frames(c, who, "", frames + p, 3, n_frames, strides[p], (size_t)row_bytes, true);
+    if (rc != PQA_OK) return rc;
+  }
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int FB = c->B < 8 ? c->B : 8;   // frames per upload and launch
+  if (!c->ig_stage) {   // lazily: a healthy clip never asks for an anchored difference
+    size_t off = 0;
+    for (int p = 0; p < c->n_planes; ++p) {
+      c->ig_stage_off[p] = off;
+      off += (size_t)round_up(c->ig_hist_pitch[p] * c->ph[p], 256);
+    }
+    c->ig_stage_bytes = off;
+    for (int p = 0; p < c->n_planes; ++p) {
+      const int rc = dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist_pitch[p] * c->ph[p]);
+      if (rc != PQA_OK) return rc;
+    }
+    const int rc = dev_alloc(c, &c->ig_stage, off * (size_t)FB);
+    if (rc != PQA_OK) return rc;
+  }
+  // plain synchronous copies from the caller's (pageable) planes: this call is rare and short, it is not pipelined
+  for (int p = 0; p < c->n_planes; ++p)
+    HIPCHK(c, hipMemcpy2D(c->ig_anchor[p], c->ig_hist_pitch[p], anchor_planes[p], anchor_strides[p], (size_t)c->pw[p] * c->esize,
+                          c->ph[p], hipMemcpyHostToDevice));
+  const void* anchor[3] = {c->ig_anchor[0], c->ig_anchor[1], c->ig_anchor[2]};
+  for (int done = 0; done < n_frames;) {
+    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+    const int n = chunk_len(n_frames, done, FB);
+    pqa_device_clip f{};
+    for (int p = 0; p < c->n_planes; ++p) {
+      for (int k = 0; k < n; ++k)
+        HIPCHK(c, hipMemcpy2D(c->ig_stage + (size_t)k * c->ig_stage_bytes + c->ig_stage_off[p], c->ig_hist_pitch[p],
+                              frames[(size_t)(done + k) * 3 + p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
+                              hipMemcpyHostToDevice));
+      f.plane[p] = c->ig_stage + c->ig_stage_off[p];
+      f.row_pitch[p] = c->ig_hist_pitch[p];
+      f.frame_pitch[p] = (int64_t)c->ig_stage_bytes;
+    }
+    const int rc = frame_sad_launch(c, anchor, c->ig_hist_pitch, &f, n, out + (size_t)done * 3);
+    if (rc != PQA_OK) return rc;
+    done += n;
+  }
+  return PQA_OK;
+}
+
+// ---- luma statistics ---------------------------------------------------------------------------------------------------
+// Launches write their results side by side into luma_out (kLumaOutFrames frames); the host copy and the sync happen once
+// per kLumaOutFrames frames, not once per launch.
+
+int pqa_set_luma_gray(pqa_ctx* c, uint32_t mode) {
+  if (!c) return PQA_EINVAL;
+  if (mode != PQA_GRAY_LUMA && mode != PQA_GRAY_BT601_FULL) return fail(c, PQA_EINVAL, "bad gray mode %u", mode);
+  c->luma_gray = mode;
+  return PQA_OK;
+}
+
+int pqa_luma_stats_device(pqa_ctx* c, const void* luma, int64_t row_pitch, int64_t frame_pitch, int32_t n_frames,
+                          uint32_t threshold, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!luma || n_frames < 0 || (n_frames > 0 && !out)) return fail(c, PQA_EINVAL, "bad argument");
+  const int chk = check_device_clip(c, "", row_pitch, frame_pitch, INT64_MIN);   // this entry has no rule on the row pitch
+  if (chk != PQA_OK) return chk;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
+  for (int done = 0; done < n_frames;) {
+    const int group = chunk_len(n_frames, done, kLumaOutFrames);
+    hipError_t e = hipSuccess;
+    for (int g0 = 0; g0 < group && e == hipSuccess;) {
+      const int n = chunk_len(group, g0, c->B);
+      const PlaneRun run{(const uint8_t*)luma + (int64_t)(done + g0) * frame_pitch, row_pitch / c->esize, frame_pitch / c->esize};
+      e = launch_luma_stats(c->stream, c->elem, run, n, c->pw[0], c->ph[0], threshold, gray_bpc, c->luma_part,
+                            c->luma_out + (size_t)g0 * 3);
+      g0 += n;
+    }
+    const int rc = side_finish(c, "luma statistics chunk", e, out + (size_t)done * 3, c->luma_out, (size_t)group * 3 * sizeof(uint64_t));
+    if (rc != PQA_OK) return rc;
+    done += group;
+  }
+  return PQA_OK;
+}
+
+int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_stride, int32_t n_frames, uint32_t threshold,
+                   uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (n_frames < 0 || (n_frames > 0 && (!luma_frames || !out))) return fail(c, PQA_EINVAL, "bad argument");
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  int rc = check_host_frames(c, "", "", luma_frames, 1, n_frames, row_stride, row_bytes, false);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = luma_staging_ensure(c);
+  if (rc != PQA_OK) return rc;
+  const int h = c->ph[0];
+  const size_t frame_bytes = (size_t)c->luma_pitch * h;
+  const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
+  // Chunks of LB frames alternate between the two halves; every chunk's kernel writes its results next to the previous
+  // ones in luma_out: no device-to-host copy sits between the chunks (into the caller's pageable `out` it would block the
+  // host until the kernel in front of it is done, and the next chunk could not be packed under that kernel).
+  int hf = 0;
+  for (int done = 0; done < n_frames;) {
+    const int group = chunk_len(n_frames, done, kLumaOutFrames);
+    hipError_t e = hipSuccess;
+    for (int g0 = 0; g0 < group && e == hipSuccess && !c->cancelled.load(); hf ^= 1) {
+      const int n = chunk_len(group, g0, c->LB);
+      e = stage_frames(c, hf, luma_frames + done + g0, row_stride, n, row_bytes, h);
+      if (e == hipSuccess) {
+        const PlaneRun run{c->luma_half[hf].dev, c->luma_pitch / c->esize, (int64_t)(frame_bytes / c->esize)};
+        e = launch_luma_stats(c->stream, c->elem, run, n, c->pw[0], h, threshold, gray_bpc, c->luma_part,
+                              c->luma_out + (size_t)g0 * 3);
+      }
+      g0 += n;
+    }
+    rc = side_finish(c, "luma statistics chunk", e, out + (size_t)done * 3, c->luma_out, (size_t)group * 3 * sizeof(uint64_t));
+    if (rc != PQA_OK) return rc;
+    done += group;
+  }
+  return PQA_OK;
+}
+
+// ---- temporal alignment (cross_sse.hip) --------------------------------------------------------------------------------
+
+int pqa_cross_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, int32_t n_ref,
+                         const void* dis_luma, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_dis, int32_t k_lo,
+                         int32_t k_hi, uint64_t* out) {
+  int rc = xs_check(c, ref_luma, dis_luma, n_ref, n_dis, k_lo, k_hi, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize;
+  const int64_t row_bytes = (int64_t)c->pw[0] * es;
+  rc = check_device_clip(c, "cross_sse: ", ref_row_pitch, ref_frame_pitch, row_bytes);
+  if (rc == PQA_OK) rc = check_device_clip(c, "cross_sse: ", dis_row_pitch, dis_frame_pitch, row_bytes);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_ref == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int span = k_hi - k_lo + 1;
+  const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
+  const int n_tiles = (n_ref + 31) / 32;
+  const int per_launch = n_tiles < kXsTilesPerLaunch ? n_tiles : kXsTilesPerLaunch;
+  rc = xs_prepare(c, mfma, span, per_launch, n_ref, n_dis);
+  if (rc != PQA_OK) return rc;
+  const XsseClip ref{ref_luma, ref_row_pitch / es, ref_frame_pitch / es, INT32_MAX, n_ref};
+  const XsseClip dis{dis_luma, dis_row_pitch / es, dis_frame_pitch / es, INT32_MAX, n_dis};
+  auto* nr = (unsigned long long*)c->side_buf[SIDE_XSSE_NORM_REF];
+  auto* nd = (unsigned long long*)c->side_buf[SIDE_XSSE_NORM_DIS];
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_XSSE_OUT];
+  hipError_t e = hipSuccess;
+  if (mfma) {
+    e = launch_xsse_norms(c->stream, ref, 0, n_ref, c->pw[0], c->ph[0], nr);
+    if (e == hipSuccess) e = launch_xsse_norms(c->stream, dis, 0, n_dis, c->pw[0], c->ph[0], nd);
+  }
+  for (int t0 = 0; t0 < n_tiles && e == hipSuccess; t0 += per_launch)
+    e = launch_cross_sse(c->stream, c->elem, mfma, ref, dis, c->pw[0], c->ph[0], k_lo, span, t0, chunk_len(n_tiles, t0, per_launch),
+                         c->side_buf[SIDE_XSSE_PART], nr, nd, dev_out);
+  return side_finish(c, "cross_sse", e, out, dev_out, (size_t)n_ref * span * sizeof(uint64_t));
+}
+
+int pqa_cross_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, int32_t n_ref,
+                  const void* const* dis_frames, int64_t dis_row_stride, int32_t n_dis, int32_t k_lo, int32_t k_hi,
+                  uint64_t* out) {
+  int rc = xs_check(c, ref_frames, dis_frames, n_ref, n_dis, k_lo, k_hi, out);
+  if (rc != PQA_OK) return rc;
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  rc = check_host_frames(c, "cross_sse: ", "reference ", ref_frames, 1, n_ref, ref_row_stride, row_bytes, false);
+  if (rc == PQA_OK) rc = check_host_frames(c, "cross_sse: ", "captured ", dis_frames, 1, n_dis, dis_row_stride, row_bytes, false);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_ref == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = luma_staging_ensure(c);
+  if (rc != PQA_OK) return rc;
+  const int span = k_hi - k_lo + 1, h = c->ph[0], es = c->esize;
+  const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
+  rc = xs_prepare(c, mfma, span, 1, n_ref, n_dis);
+  const size_t frame_bytes = (size_t)c->luma_pitch * h;
+  const int dis_ring = 31 + span;   // the captured frames one reference tile meets
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_XSSE_REF, frame_bytes * 32);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_XSSE_DIS, frame_bytes * dis_ring);
+  if (rc != PQA_OK) return rc;
+  const XsseClip ref{c->side_buf[SIDE_XSSE_REF], c->luma_pitch / es, (int64_t)(frame_bytes / es), 32, n_ref};
+  const XsseClip dis{c->side_buf[SIDE_XSSE_DIS], c->luma_pitch / es, (int64_t)(frame_bytes / es), dis_ring, n_dis};
+  auto* nr = (unsigned long long*)c->side_buf[SIDE_XSSE_NORM_REF];
+  auto* nd = (unsigned long long*)c->side_buf[SIDE_XSSE_NORM_DIS];
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_XSSE_OUT];
+  // Every frame crosses PCIe once: reference tile b replaces tile b - 1 in its 32 slots, and the captured window only ever
+  // moves forward, so a tile uploads the captured frames between the previous window's end and its own.  Frames travel in
+  // chunks of LB that alternate between the two pinned halves, as in pqa_luma_stats; the stream orders a tile's uploads
+  // before its kernels and those before the next tile's uploads into the same slots.
+  hipError_t e = hipSuccess;
+  int hf = 0;
+  const auto live = [&] { return e == hipSuccess && !c->cancelled.load(); };
+  const auto upload = [&](const void* const* frames, int64_t stride, const XsseClip& clip, int64_t first, int64_t last,
+                          unsigned long long* norms) {   // frames first ... last - 1 into their ring slots
+    for (int64_t f0 = first; f0 < last && live(); hf ^= 1) {
+      const int n = (int)(last - f0 < c->LB ? last - f0 : c->LB);
+      e = stage_frames(c, hf, frames + f0, stride, n, row_bytes, h, (uint8_t*)clip.base, clip.ring, f0);
+      // the frames of a chunk lie in consecutive slots unless the ring wraps inside it: one norm launch per frame
+      for (int f = 0; mfma && f < n && e == hipSuccess; ++f) e = launch_xsse_norms(c->stream, clip, f0 + f, 1, c->pw[0], h, norms);
+      f0 += n;
+    }
+  };
+  int64_t dis_done = 0;   // captured frames below it have been uploaded (or skipped: no reference tile meets them)
+  const int n_tiles = (n_ref + 31) / 32;
+  for (int t = 0; t < n_tiles && live(); ++t) {
+    const int64_t r0 = (int64_t)t * 32, r1 = r0 + 32 < n_ref ? r0 + 32 : n_ref;
+    int64_t d0 = r0 + k_lo, d1 = r0 + 31 + k_hi + 1;
+    d0 = d0 < dis_done ? dis_done : d0;
+    d1 = d1 > n_dis ? n_dis : d1;
+    upload(ref_frames, ref_row_stride, ref, r0, r1, nr);
+    if (d0 < d1) {
+      upload(dis_frames, dis_row_stride, dis, d0, d1, nd);
+      dis_done = d1;
+    }
+    if (live())
+      e = launch_cross_sse(c->stream, c->elem, mfma, ref, dis, c->pw[0], h, k_lo, span, t, 1, c->side_buf[SIDE_XSSE_PART], nr, nd,
+                           dev_out);
+  }
+  return side_finish(c, "cross_sse", e, out, dev_out, (size_t)n_ref * span * sizeof(uint64_t));
+}
+
+// ---- spatial alignment (shift_sse.hip) ---------------------------------------------------------------------------------
+
+int pqa_shift_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis_luma,
+                         int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t radius, uint64_t* out) {
+  int rc = sh_check(c, ref_luma, dis_luma, n_frames, radius, out);
+  if (rc != PQA_OK) return rc;
+  if (n_frames == 0) return PQA_OK;
+  const int es = c->esize;
+  const int64_t row_bytes = (int64_t)c->pw[0] * es;
+  rc = check_device_clip(c, "shift_sse: ", ref_row_pitch, ref_frame_pitch, row_bytes);
+  if (rc == PQA_OK) rc = check_device_clip(c, "shift_sse: ", dis_row_pitch, dis_frame_pitch, row_bytes);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = sh_prepare(c, radius, n_frames);
+  if (rc != PQA_OK) return rc;
+  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_SHIFT_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kShiftChunk)
+    e = launch_shift_sse(c->stream, c->elem, (const uint8_t*)ref_luma + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
+                         ref_frame_pitch / es, (const uint8_t*)dis_luma + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
+                         dis_frame_pitch / es, chunk_len(n_frames, f0, kShiftChunk), c->pw[0], c->ph[0], radius,
+                         c->side_buf[SIDE_SHIFT_PART], (unsigned long long*)c->side_buf[SIDE_SHIFT_ROWSQ], dev_out + (size_t)f0 * n);
+  return side_finish(c, "shift_sse", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+}
+
+int pqa_shift_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
+                  int64_t dis_row_stride, int32_t n_frames, int32_t radius, uint64_t* out) {
+  int rc = sh_check(c, ref_frames, dis_frames, n_frames, radius, out);
+  if (rc != PQA_OK) return rc;
+  if (n_frames == 0) return PQA_OK;
+  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
+  rc = check_host_frames(c, "shift_sse: ", "", ref_frames, 1, n_frames, ref_row_stride, row_bytes, false);
+  if (rc == PQA_OK) rc = check_host_frames(c, "shift_sse: ", "", dis_frames, 1, n_frames, dis_row_stride, row_bytes, false);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = luma_staging_ensure(c);
+  if (rc == PQA_OK) rc = sh_prepare(c, radius, n_frames);   // LB <= kShiftChunk: the workspaces of a full chunk hold every chunk here
+  if (rc != PQA_OK) return rc;
+  const int h = c->ph[0], es = c->esize;
+  const size_t frame_bytes = (size_t)c->luma_pitch * h, n = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_SHIFT_OUT];
+  hipError_t e = hipSuccess;
+  // Chunks of LB (<= 8) pairs: the reference frames go through pinned / device half 0, the captured ones through half 1.
+  // The stream orders a chunk's kernel before the next chunk's uploads into the same device halves.
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += c->LB) {
+    const int m = chunk_len(n_frames, f0, c->LB);
+    e = stage_frames(c, 0, ref_frames + f0, ref_row_stride, m, row_bytes, h);
+    if (e == hipSuccess) e = stage_frames(c, 1, dis_frames + f0, dis_row_stride, m, row_bytes, h);
+    if (e == hipSuccess)
+      e = launch_shift_sse(c->stream, c->elem, c->luma_half[0].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es),
+                           c->luma_half[1].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es), m, c->pw[0], h, radius,
+                           c->side_buf[SIDE_SHIFT_PART], (unsigned long long*)c->side_buf[SIDE_SHIFT_ROWSQ], dev_out + (size_t)f0 * n);
+  }
+  return side_finish(c, "shift_sse", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+}
+
+// ---- level alignment (level_stats.hip) ---------------------------------------------------------------------------------
+
+int pqa_level_bins(const pqa_ctx* c) { return c ? 1 << c->cfg.bit_depth : PQA_EINVAL; }
+
+int pqa_level_stats_device(pqa_ctx* c, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
+                           int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t plane, uint64_t* out) {
+  int rc = lv_check(c, ref, dis, n_frames, plane, out);
+  if (rc != PQA_OK) return rc;
+  if (n_frames == 0) return PQA_OK;
+  const int es = c->esize, bpc = (int)c->cfg.bit_depth;
+  const int64_t row_bytes = (int64_t)c->pw[plane] * es;
+  rc = check_device_clip(c, "level_stats: ", ref_row_pitch, ref_frame_pitch, row_bytes);
+  if (rc == PQA_OK) rc = check_device_clip(c, "level_stats: ", dis_row_pitch, dis_frame_pitch, row_bytes);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = side_reserve(c, SIDE_LEVEL_OUT, level_out_bytes(bpc, n_frames));
+  if (rc != PQA_OK) return rc;
+  const size_t n = (size_t)3 << bpc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_LEVEL_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kLevelChunk)
+    e = launch_level_stats(c->stream, c->elem, bpc, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
+                           ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
+                           dis_frame_pitch / es, chunk_len(n_frames, f0, kLevelChunk), c->pw[plane], c->ph[plane],
+                           dev_out + (size_t)f0 * n);
+  return side_finish(c, "level_stats", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+}
+
+int pqa_level_stats(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
+                    int64_t dis_row_stride, int32_t n_frames, int32_t plane, uint64_t* out) {
+  int rc = lv_check(c, ref_frames, dis_frames, n_frames, plane, out);
+  if (rc != PQA_OK) return rc;
+  if (n_frames == 0) return PQA_OK;
+  const size_t row_bytes = (size_t)c->pw[plane] * c->esize;
+  rc = check_host_frames(c, "level_stats: ", "", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "level_stats: ", "", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int bpc = (int)c->cfg.bit_depth;
+  rc = luma_staging_ensure(c);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_LEVEL_OUT, level_out_bytes(bpc, n_frames));
+  if (rc != PQA_OK) return rc;
+  // a chroma plane is no larger than the luma plane, so it travels through the luma staging with the luma pitches
+  const int w = c->pw[plane], h = c->ph[plane], es = c->esize;
+  const size_t frame_bytes = (size_t)c->luma_pitch * c->ph[0], n = (size_t)3 << bpc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_LEVEL_OUT];
+  hipError_t e = hipSuccess;
+  // chunks of LB (<= kLevelChunk) pairs, staged as in pqa_shift_sse: reference frames through half 0, captured ones through half 1
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += c->LB) {
+    const int m = chunk_len(n_frames, f0, c->LB);
+    e = stage_frames(c, 0, ref_frames + f0, ref_row_stride, m, row_bytes, h);
+    if (e == hipSuccess) e = stage_frames(c, 1, dis_frames + f0, dis_row_stride, m, row_bytes, h);
+    if (e == hipSuccess)
+      e = launch_level_stats(c->stream, c->elem, bpc, c->luma_half[0].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es),
+                             c->luma_half[1].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es), m, w, h, dev_out + (size_t)f0 * n);
+  }
+  return side_finish(c, "level_stats", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+}
+
+}  // extern "C"

@@ -1,0 +1,244 @@
+"""The host-frame staging that pqa_luma_stats, pqa_cross_sse, pqa_shift_sse and pqa_level_stats share (csrc/pqa_side.hip),
+on the MI355X, past its second chunk: a context with max_batch = 2 stages LB = 2 frames per pinned half, so 7 frames make
+four chunks, the last one partial -- a pinned half reused before its upload has left it, or a wrong slot behind a ring
+wrap, changes the integers.  Every result is compared with the numpy restatements as integers; refused calls leave the
+context usable."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import align_ref as AR
+from tests import level_ref as LR
+from tests import spatial_align_ref as SR
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+W, H, N = 48, 32, 7
+
+
+def _engine(w=W, h=H, bpc=8, **kw):
+    from pqa2_amd import _native as Nt
+    from pqa2_amd.engine import FeatureEngine
+    return FeatureEngine(w, h, bit_depth=bpc, n_planes=kw.pop("n_planes", 1), features=Nt.FEAT_PSNR, max_batch=2, **kw)
+
+
+def _padded(frames, pad=5, lead=1):
+    """the same frames as views into one buffer: rows `pad` samples longer than a row, base `lead` samples in"""
+    h, w = frames[0].shape
+    buf = np.zeros((len(frames), h, w + pad), frames[0].dtype)
+    buf[:, :, lead:lead + w] = np.stack(frames)
+    return buf, [buf[i, :, lead:lead + w] for i in range(len(frames))]
+
+
+def _on_device(buf, lead):
+    """(tensor kept alive, device address of frame 0's first sample, row pitch, frame pitch) of a [n, h, pitch] buffer"""
+    import torch
+    t = torch.from_numpy(buf.view(np.uint8).reshape(-1)).cuda()
+    torch.cuda.synchronize()
+    return t, t.data_ptr() + lead * buf.dtype.itemsize, buf.strides[1], buf.strides[0]
+
+
+def _distinct(a):
+    return len({a[f].tobytes() for f in range(len(a))}) == len(a)
+
+
+# ---- spatial and level alignment: the reference through half 0, the capture through half 1 ----------------------------
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_shift_sse_four_chunks(bpc):
+    ref, dis = SR.random_pair(70 + bpc, N, W, H, bpc)
+    want = SR.shift_sse(ref, dis, 2)
+    assert _distinct(want)
+    rbuf, rv = _padded(ref)
+    dbuf, dv = _padded(dis)
+    with _engine(bpc=bpc) as eng:
+        assert np.array_equal(eng.shift_sse(ref, dis, 2), want)
+        assert np.array_equal(eng.shift_sse(rv, dv, 2), want)
+        tr, rp, rrow, rframe = _on_device(rbuf, 1)
+        td, dp, drow, dframe = _on_device(dbuf, 1)
+        assert np.array_equal(eng.shift_sse_resident(rp, rrow, rframe, dp, drow, dframe, N, 2), want)
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_level_stats_four_chunks(bpc):
+    ref, dis = LR.random_pair(70 + bpc, N, W, H, bpc)
+    want = LR.level_stats(ref, dis, bpc)
+    assert _distinct(want)
+    rbuf, rv = _padded(ref)
+    dbuf, dv = _padded(dis)
+    with _engine(bpc=bpc) as eng:
+        assert np.array_equal(eng.level_stats(ref, dis), want)
+        assert np.array_equal(eng.level_stats(rv, dv), want)
+        tr, rp, rrow, rframe = _on_device(rbuf, 1)
+        td, dp, drow, dframe = _on_device(dbuf, 1)
+        assert np.array_equal(eng.level_stats_resident(rp, rrow, rframe, dp, drow, dframe, N), want)
+
+
+def test_level_stats_chroma_plane_four_chunks():
+    """plane 1 of a 4:2:0 context: 24 x 16 samples that travel through the staging with the luma pitches"""
+    ref, dis = LR.random_pair(81, N, W // 2, H // 2)
+    want = LR.level_stats(ref, dis, 8)
+    assert _distinct(want)
+    rbuf, rv = _padded(ref, pad=3)
+    dbuf, dv = _padded(dis, pad=3)
+    with _engine(n_planes=3, chroma_shift=(1, 1)) as eng:
+        assert eng.plane_shape(1) == (H // 2, W // 2)
+        assert np.array_equal(eng.level_stats(ref, dis, 1), want)
+        assert np.array_equal(eng.level_stats(rv, dv, 1), want)
+        tr, rp, rrow, rframe = _on_device(rbuf, 1)
+        td, dp, drow, dframe = _on_device(dbuf, 1)
+        assert np.array_equal(eng.level_stats_resident(rp, rrow, rframe, dp, drow, dframe, N, 1), want)
+
+
+# ---- luma statistics: chunks alternate between the halves -------------------------------------------------------------
+def _luma_sums(frames, thr, gray):
+    from tests.test_bookend import _cv2_style_gray
+    c = np.stack([_cv2_style_gray(f, 8) if gray else f for f in frames]).astype(np.int64)
+    return np.stack([c.sum((1, 2)), (c * c).sum((1, 2)), (c > thr).sum((1, 2))], 1).astype(np.uint64)
+
+
+@pytest.mark.parametrize("gray", [False, True])
+def test_luma_stats_four_chunks(gray):
+    from pqa2_amd import _native as Nt
+    frames = SR.random_pair(90, N, W, H)[0]
+    want = _luma_sums(frames, 120, gray)
+    assert _distinct(want)
+    _, views = _padded(frames)
+    with _engine() as eng:
+        eng.set_luma_gray(Nt.GRAY_BT601_FULL if gray else Nt.GRAY_LUMA)
+        assert np.array_equal(eng.luma_stats(frames, 120), want)
+        assert np.array_equal(eng.luma_stats(views, 120), want)
+
+
+def test_luma_stats_second_result_group():
+    """more than the 2 048 frames whose results the device keeps between two host copies: the second group's offset in
+    `out`, and the chunk parity that carries on across the group boundary.  Five distinct 16 x 16 arrays, over and over."""
+    n = 2048 + 5
+    base = SR.random_pair(91, 5, 16, 16)[0]
+    order = [(3 * i + i // 5) % 5 for i in range(n)]
+    sums = _luma_sums(base, 100, False)
+    want = sums[order]
+    assert _distinct(sums) and all(order[i] != order[i + 1] for i in range(n - 1))   # a result one frame off would show
+    with _engine(16, 16) as eng:
+        assert np.array_equal(eng.luma_stats([base[k] for k in order], 100), want)
+
+
+# ---- temporal alignment: one ring slot per frame, and the ring wraps ---------------------------------------------------
+K_LO, K_HI, N_REF, N_DIS = -3, 5, 40, 45    # two reference tiles, the second partial; a captured ring of 31 + 9 = 40 slots
+
+
+def _cross_clip(bpc):
+    ref, _ = SR.random_pair(100 + bpc, N_REF, W, H, bpc)
+    dis, _ = SR.random_pair(200 + bpc, N_DIS, W, H, bpc)
+    return ref, dis
+
+
+def _cross_both_entries(bpc):
+    """(host entry, resident entry) of the clip: with LB = 2 a chunk of two captured frames straddles the wrap 39 -> 0"""
+    ref, dis = _cross_clip(bpc)
+    rbuf, _ = _padded(ref, pad=0, lead=0)
+    dbuf, _ = _padded(dis, pad=0, lead=0)
+    with _engine(bpc=bpc) as eng:
+        host = eng.cross_sse(ref, dis, K_LO, K_HI)
+        tr, rp, rrow, rframe = _on_device(rbuf, 0)
+        td, dp, drow, dframe = _on_device(dbuf, 0)
+        return host, eng.cross_sse_resident(rp, rrow, rframe, N_REF, dp, drow, dframe, N_DIS, K_LO, K_HI)
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_cross_sse_ring_wrap(bpc):
+    ref, dis = _cross_clip(bpc)
+    want = AR.cross_sse(ref, dis, K_LO, K_HI)
+    assert _distinct(want) and int(want[0, 0]) == int(AR.SENTINEL)
+    host, resident = _cross_both_entries(bpc)
+    assert np.array_equal(host, want) and np.array_equal(resident, want)
+
+
+_CHILD = """
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+from tests.test_gpu_side_staging import _cross_both_entries
+host, resident = _cross_both_entries(8)
+np.savez(sys.argv[2], host=host, resident=resident)
+"""
+
+
+def test_cross_sse_ring_wrap_on_the_valu_path(tmp_path):
+    """the same at 8 bit with PQA_XSSE_MFMA=0 (read at pqa_create): the host entry then skips its per-frame norm launches"""
+    script, res = tmp_path / "child.py", tmp_path / "valu.npz"
+    script.write_text(_CHILD)
+    r = subprocess.run([sys.executable, str(script), ROOT, str(res)], env=dict(os.environ, PQA_XSSE_MFMA="0"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    ref, dis = _cross_clip(8)
+    want = AR.cross_sse(ref, dis, K_LO, K_HI)
+    got = np.load(res)
+    assert np.array_equal(got["host"], want) and np.array_equal(got["resident"], want)
+
+
+# ---- refused calls leave the context usable --------------------------------------------------------------------------
+def _ptrs(frames, hole=None):
+    a = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+    if hole is not None:
+        a[hole] = None
+    return a
+
+
+@pytest.mark.parametrize("entry", ["luma_stats", "cross_sse", "shift_sse", "level_stats"])
+def test_refused_calls_leave_the_context_usable(entry):
+    """a null frame pointer in the middle of the list and a stride one byte short: PQA_EINVAL before anything is queued
+    (`out` keeps its fill), and the next valid call returns the right numbers"""
+    from pqa2_amd import _native as Nt
+    ref, dis = SR.random_pair(110, N, W, H)
+    out = np.full(N * 3 * 256, 0xA5A5A5A5A5A5A5A5, np.uint64)    # the largest result of the four: level_stats
+    with _engine() as eng:
+        lib, ctx, o = eng.lib, eng._ctx, out.ctypes.data
+        calls = {
+            "luma_stats": lambda r, rs, d, ds: lib.pqa_luma_stats(ctx, r, rs, N, 120, o),
+            "cross_sse": lambda r, rs, d, ds: lib.pqa_cross_sse(ctx, r, rs, N, d, ds, N, -1, 1, o),
+            "shift_sse": lambda r, rs, d, ds: lib.pqa_shift_sse(ctx, r, rs, d, ds, N, 2, o),
+            "level_stats": lambda r, rs, d, ds: lib.pqa_level_stats(ctx, r, rs, d, ds, N, 0, o),
+        }
+        call = calls[entry]
+        bad = [(_ptrs(ref, hole=3), W, _ptrs(dis), W), (_ptrs(ref), W - 1, _ptrs(dis), W)]
+        if entry != "luma_stats":    # the captured list has the same rules
+            bad += [(_ptrs(ref), W, _ptrs(dis, hole=N - 2), W), (_ptrs(ref), W, _ptrs(dis), W - 1)]
+        for args in bad:
+            assert call(*args) == Nt.PQA_EINVAL
+            assert lib.pqa_last_error(ctx)
+            assert (out == 0xA5A5A5A5A5A5A5A5).all()
+        assert call(_ptrs(ref), W, _ptrs(dis), W) == Nt.PQA_OK    # the raw call itself works
+        want = {"luma_stats": lambda: _luma_sums(ref, 120, False), "cross_sse": lambda: AR.cross_sse(ref, dis, -1, 1),
+                "shift_sse": lambda: SR.shift_sse(ref, dis, 2), "level_stats": lambda: LR.level_stats(ref, dis, 8)}[entry]()
+        assert np.array_equal(out[:want.size].reshape(want.shape), want)
+        got = {"luma_stats": lambda: eng.luma_stats(ref, 120), "cross_sse": lambda: eng.cross_sse(ref, dis, -1, 1),
+               "shift_sse": lambda: eng.shift_sse(ref, dis, 2), "level_stats": lambda: eng.level_stats(ref, dis)}[entry]()
+        assert np.array_equal(got, want)
+
+
+def test_cross_sse_argument_rules_speak():
+    """each rule of the two temporal entries names itself in pqa_last_error (with a null context none of them is reached:
+    tests/test_align.py::test_argument_rules_need_no_device)"""
+    from pqa2_amd import _native as Nt
+    buf = np.zeros((4, 16, 16), np.uint8)
+    ptrs = _ptrs(list(buf))
+    out = np.zeros(1024, np.uint64)
+    with _engine(16, 16) as eng:
+        lib, ctx, p, o = eng.lib, eng._ctx, buf.ctypes.data, out.ctypes.data
+
+        def dev(ref=p, n_ref=2, dis=p, n_dis=2, k_lo=-1, k_hi=1, o=o):
+            return lib.pqa_cross_sse_device(ctx, ref, 16, 256, n_ref, dis, 16, 256, n_dis, k_lo, k_hi, o)
+
+        def host(ref=ptrs, n_ref=2, dis=ptrs, n_dis=2, k_lo=-1, k_hi=1, o=o):
+            return lib.pqa_cross_sse(ctx, ref, 16, n_ref, dis, 16, n_dis, k_lo, k_hi, o)
+        for call in (dev, host):
+            for kw, word in ((dict(ref=None), b"null"), (dict(dis=None), b"null"), (dict(o=None), b"null"),
+                             (dict(n_ref=-1), b"negative"), (dict(n_dis=-1), b"negative"), (dict(k_lo=2, k_hi=1), b"k_lo"),
+                             (dict(k_lo=-65, k_hi=0), b"outside"), (dict(k_lo=0, k_hi=65), b"outside"),
+                             (dict(k_lo=-100, k_hi=100), b"outside")):
+                assert call(**kw) == Nt.PQA_EINVAL, kw
+                assert word in lib.pqa_last_error(ctx) and lib.pqa_last_error(ctx).startswith(b"cross_sse: "), kw
+        assert host() == Nt.PQA_OK and out[:6].tolist() == [2 ** 64 - 1, 0, 0, 0, 0, 2 ** 64 - 1]
