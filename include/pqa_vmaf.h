@@ -512,6 +512,46 @@ PQA_API int pqa_level_stats(pqa_ctx* ctx, const void* const* ref_frames, int64_t
 /* L, the number of levels of the table above: 2^bit_depth of the context. */
 PQA_API int pqa_level_bins(const pqa_ctx* ctx);
 
+/* Resampling: n_frames planes of src_width x src_height samples become planes of dst_width x dst_height, synchronously, with
+ * one separable polyphase filter in exact integers -- what scoring a clip against a reference of another size needs first.
+ * Samples are u8 in an 8-bit context, otherwise little-endian u16 of the context's bit depth b (a sample above 2^b - 1 is
+ * read as 2^b - 1).  The plane sizes are those of the spec, independent of the context's width and height (each 1 ... 8192):
+ * a chroma plane is resampled as a plane of its own size.  The source window (x0, y0, w, h), in source samples as signed
+ * Q16 integers, is what the destination plane shows: a whole-plane resize is (0, 0, src_width, src_height); a sub-pixel
+ * shift is dst = src size, (w, h) = the size, (x0, y0) = the shift.  Per axis (n_src -> n_dst, window x0, ext), in double:
+ *     step = ext / n_dst, stretch = max(1, step), S = s * stretch, centre of destination sample i: c = x0 + (i + 0.5) step - 0.5,
+ *     taps j = ceil(c - S) ... floor(c + S) with the weights k((j - c) / stretch), normalised to sum 1,
+ *     q = floor(w * 16384 + 0.5), the remainder 16384 - sum q added to the largest q (the first of equals),
+ *     every tap folded onto clamp(j, 0, n_src - 1) (edge replication).
+ * k and s: PQA_RESAMPLE_BILINEAR max(0, 1 - |t|), 1; PQA_RESAMPLE_BICUBIC Keys' cubic with a = -0.6, 2;
+ * PQA_RESAMPLE_LANCZOS3 sinc(t) sinc(t / 3), 3.  The horizontal pass runs first: acc = sum q_h * src (int32),
+ * mid = (acc + 2^(b-1)) >> b (signed, not clamped), acc2 = sum q_v * mid, out = clamp((acc2 + 2^(27-b)) >> (28 - b), 0, 2^b - 1);
+ * all shifts arithmetic.  Identity returns the source; a whole-sample window returns the edge-replicated crop; a constant
+ * plane stays constant.  Coefficient quantisation and the intermediate rounding are this library's own, not swscale's.
+ * Any context, no feature bit; tables and buffers are made on first use, grow only, are kept for the last four (filter,
+ * geometry, window) and freed with the context.  Independent of the scoring chain: a call between two pqa_submit calls
+ * changes no record.  PQA_EINVAL, before any device call, on a null pointer, a bad struct_size or filter, a size outside
+ * 1 ... 8192, a non-positive window, a row pitch shorter than a row (or, in device memory, no multiple of the sample size),
+ * a negative frame count, or a destination sample that needs more than 32 taps (Lanczos beyond 5.3x down, bicubic beyond
+ * 8x down).  n_frames == 0 succeeds and writes nothing.  Bytes between the end of a destination row and the next row are
+ * never written.  Kernel, tiling and overflow bounds: DESIGN.md section 5.
+ *
+ * pqa_resample: frames in HOST memory (src_frames[f] / dst_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 through pinned buffers of this entry's own.
+ * pqa_resample_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device; the resampled planes can go straight into pqa_submit_device. */
+enum { PQA_RESAMPLE_BILINEAR = 0, PQA_RESAMPLE_BICUBIC = 1, PQA_RESAMPLE_LANCZOS3 = 2 };
+typedef struct pqa_resample_spec {
+  uint32_t struct_size, filter;
+  uint32_t src_width, src_height, dst_width, dst_height; /* of THIS plane, 1 ... 8192 */
+  int64_t x0_q16, y0_q16, w_q16, h_q16;                  /* source window; w, h > 0 */
+} pqa_resample_spec;
+PQA_API int pqa_resample(pqa_ctx* ctx, const pqa_resample_spec* spec, const void* const* src_frames, int64_t src_row_stride,
+                         void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames);
+PQA_API int pqa_resample_device(pqa_ctx* ctx, const pqa_resample_spec* spec, const void* src, int64_t src_row_pitch,
+                                int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
+                                int32_t n_frames);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to
@@ -596,6 +636,14 @@ PQA_API int pqa_debug_xpsnr_blocks(const void* ref, const void* ref_m1, const vo
  * and TI.  w, h >= 3.  PQA_EINVAL on a null pointer, a bad size, depth or pitch, PQA_EDEVICE without a device. */
 PQA_API int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_pitch_bytes, uint32_t w, uint32_t h,
                                  uint32_t bit_depth, int32_t full_range, float* gmap, double* si_ti);
+
+/* Test hook (no device needed): one axis of the pqa_resample tables.  Destination sample i of n_dst reads the source samples
+ * first[i] ... first[i] + *taps - 1 of n_src with the coefficients coeff[i * cap_taps + 0 ... *taps) (scale 2^14, a row sums
+ * to 16384; zero from the row's last tap to cap_taps); x0_q16 / ext_q16: the source window of this axis.  *taps: the longest
+ * row (at most 32; rows are cut to their non-zero span).  PQA_EINVAL on a null pointer, a bad filter, a size outside
+ * 1 ... 8192, a non-positive window, a row of more than 32 taps, or cap_taps < *taps (*taps is set then). */
+PQA_API int pqa_debug_resample_table(uint32_t filter, int32_t n_src, int32_t n_dst, int64_t x0_q16, int64_t ext_q16,
+                                     int32_t* first, int16_t* coeff, int32_t cap_taps, int32_t* taps);
 
 #ifdef __cplusplus
 }

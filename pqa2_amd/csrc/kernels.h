@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace pqa {
 
 enum Elem : int { ELEM_U8 = 0, ELEM_U16 = 1, ELEM_F32 = 2 };
@@ -419,6 +421,35 @@ size_t level_out_bytes(int bit_depth, int n_frames);
 hipError_t launch_level_stats(hipStream_t stream, Elem elem, int bit_depth, const void* ref, int64_t ref_row_pitch,
                               int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                               int n_frames, int w, int h, unsigned long long* out);
+
+// ---- exact-integer polyphase resampler (resample.hip) ---------------------------------------------------------------------
+// One axis of the filter: destination sample i reads the source samples first[i] ... first[i] + taps - 1 with the int16
+// coefficients coeff[i][0 .. taps) (scale 2^14, a row sums to 16384, zero-padded; edge replication folded in).  Built on the
+// host in double; resample_table returns 0, or -1 when the arguments are out of range, a row needs
+// more than kRsMaxTaps taps or its sum of |q| reaches 32768.  filter: PQA_RESAMPLE_*; x0_q16 / ext_q16: the source window.
+constexpr int kRsMaxTaps = 32;
+constexpr int kRsChunk = 8;   // frames per launch of the two entries
+struct ResampleTable {
+  std::vector<int32_t> first;
+  std::vector<int16_t> coeff;   // [n_dst][taps]
+  int taps = 0;
+};
+int resample_table(int filter, int n_src, int n_dst, int64_t x0_q16, int64_t ext_q16, ResampleTable* out);
+// What the kernel reads for a pair of tables: `words` is uploaded as it is (first / coefficient pairs of both axes, the
+// source footprint of every tile column and tile row); the rest sizes the launch.
+struct ResamplePlan {
+  std::vector<int32_t> words;
+  size_t off_first_h = 0, off_coef_h = 0, off_first_v = 0, off_coef_v = 0, off_tile_h = 0, off_tile_v = 0;   // in words
+  int wpad = 0, ph = 0, pv = 0, th = 0, mid_rows = 0, sw = 0;
+  size_t lds_bytes = 0;
+};
+void resample_plan(const ResampleTable& th, const ResampleTable& tv, int dst_w, int dst_h, ResamplePlan* plan);
+// n_frames planes of src_w x src_h -> dst_w x dst_h (frame f at base + f * frame_pitch, pitches in elements; samples of
+// `bits` bits).  dev_words: plan.words in device memory.  Reads no source sample outside the plane, writes no byte outside
+// the dst_w samples of a destination row.
+hipError_t launch_resample(hipStream_t stream, Elem elem, int bits, const ResamplePlan& plan, const int* dev_words, const void* src,
+                           int64_t src_row_pitch, int64_t src_frame_pitch, int src_w, int src_h, void* dst, int64_t dst_row_pitch,
+                           int64_t dst_frame_pitch, int dst_w, int dst_h, int n_frames);
 
 }  // namespace pqa
 

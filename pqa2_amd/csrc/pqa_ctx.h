@@ -45,7 +45,17 @@ enum SideBuf {
   SIDE_XSSE_REF, SIDE_XSSE_DIS,                                                // pqa_cross_sse: its two rings of uploaded frames
   SIDE_SHIFT_PART, SIDE_SHIFT_ROWSQ, SIDE_SHIFT_OUT,                           // pqa_shift_sse[_device], shift_sse.hip
   SIDE_LEVEL_OUT,                                                              // pqa_level_stats[_device], level_stats.hip
+  SIDE_RS_TABLE0, SIDE_RS_TABLE1, SIDE_RS_TABLE2, SIDE_RS_TABLE3,              // pqa_resample[_device], resample.hip: cached tables
+  SIDE_RS_SRC, SIDE_RS_DST,                                                    // pqa_resample: a chunk of uploaded / resampled planes
   kSideBufs
+};
+
+// A resampling the context has the device tables of (side_buf[SIDE_RS_TABLE0 + slot]): what pqa_resample was asked for last.
+constexpr int kRsCached = 4;
+struct RsCached {
+  bool valid = false;
+  pqa_resample_spec spec{};
+  ResamplePlan plan;   // `words` is emptied once it is uploaded
 };
 
 }  // namespace pqa
@@ -147,6 +157,10 @@ struct pqa_ctx {
   bool luma_ready = false;
   uint32_t luma_gray = PQA_GRAY_LUMA;
   bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
+  pqa::RsCached rs_cache[pqa::kRsCached];   // pqa_resample[_device]: the tables of the last few (filter, geometry, window)
+  int rs_next = 0;                          // the slot the next new table replaces
+  uint8_t* rs_pin[2] = {nullptr, nullptr};  // pqa_resample: grow-only pinned chunks of source / resampled planes (any plane size)
+  size_t rs_pin_cap[2] = {0, 0};
   void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use
   size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes
   // motion continuity

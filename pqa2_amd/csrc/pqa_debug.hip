@@ -274,4 +274,21 @@ int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_pitch_by
   return PQA_OK;
 }
 
+int pqa_debug_resample_table(uint32_t filter, int32_t n_src, int32_t n_dst, int64_t x0_q16, int64_t ext_q16, int32_t* first,
+                             int16_t* coeff, int32_t cap_taps, int32_t* taps) {
+  if (!first || !coeff || !taps || filter > PQA_RESAMPLE_LANCZOS3 || n_src < 1 || n_src > 8192 || n_dst < 1 || n_dst > 8192 ||
+      ext_q16 <= 0 || cap_taps < 1)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_resample_table: bad argument");
+  ResampleTable t;
+  if (resample_table((int)filter, n_src, n_dst, x0_q16, ext_q16, &t) != 0)
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_resample_table: a destination sample needs more than %d taps", kRsMaxTaps);
+  *taps = t.taps;
+  if (cap_taps < t.taps) return fail(nullptr, PQA_EINVAL, "pqa_debug_resample_table: coeff holds %d taps a row, needs %d", cap_taps, t.taps);
+  for (int i = 0; i < n_dst; ++i) {
+    first[i] = t.first[i];
+    for (int k = 0; k < cap_taps; ++k) coeff[(size_t)i * cap_taps + k] = k < t.taps ? t.coeff[(size_t)i * t.taps + k] : 0;
+  }
+  return PQA_OK;
+}
+
 }  // extern "C"

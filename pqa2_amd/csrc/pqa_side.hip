@@ -1,5 +1,5 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment.  Each has an entry for a clip in HBM and one for frames in host memory; the host
+// temporal / spatial / level alignment, the resampler.  Each has an entry for a clip in HBM and one for frames in host memory; the host
 // entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
@@ -93,7 +93,7 @@ hipError_t stage_frames(pqa_ctx* c, int hf, const void* const* frames, int64_t s
 // something failed or the call was cancelled, and the stream is ALWAYS synchronised -- nothing queued on it may still point
 // at the pinned halves or at `out` when the call returns.
 int side_finish(pqa_ctx* c, const char* what, hipError_t e, void* out, const void* dev_out, size_t bytes) {
-  if (e == hipSuccess && !c->cancelled.load()) e = hipMemcpyAsync(out, dev_out, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && !c->cancelled.load() && bytes) e = hipMemcpyAsync(out, dev_out, bytes, hipMemcpyDeviceToHost, c->stream);
   const hipError_t es = hipStreamSynchronize(c->stream);
   c->luma_half[0].copied_pending = c->luma_half[1].copied_pending = false;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
@@ -186,6 +186,60 @@ int lv_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int
   if (plane < 0 || plane >= c->n_planes) return fail(c, PQA_EINVAL, "level_stats: plane %d of a context with %d", plane, c->n_planes);
   if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "level_stats: null clip pointer");
   if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "level_stats: null output pointer");
+  return PQA_OK;
+}
+
+
+// ---- resampler (resample.hip): argument rules (no device call), tables, pinned chunks ---------------------------------
+int rs_check(pqa_ctx* c, const pqa_resample_spec* sp) {
+  if (!c) return PQA_EINVAL;
+  if (!sp) return fail(c, PQA_EINVAL, "resample: null spec");
+  if (sp->struct_size != sizeof(pqa_resample_spec)) return fail(c, PQA_EINVAL, "resample: bad struct_size %u", sp->struct_size);
+  if (sp->filter > PQA_RESAMPLE_LANCZOS3) return fail(c, PQA_EINVAL, "resample: bad filter %u", sp->filter);
+  for (uint32_t v : {sp->src_width, sp->src_height, sp->dst_width, sp->dst_height})
+    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "resample: plane size %u outside 1 ... 8192", v);
+  if (sp->w_q16 <= 0 || sp->h_q16 <= 0) return fail(c, PQA_EINVAL, "resample: the source window is not positive");
+  return PQA_OK;
+}
+
+// the cached device tables of a spec (built and uploaded when the context has not seen it): *slot
+int rs_tables(pqa_ctx* c, const pqa_resample_spec* sp, int* slot) {
+  for (int i = 0; i < kRsCached; ++i)
+    if (c->rs_cache[i].valid && !memcmp(&c->rs_cache[i].spec, sp, sizeof *sp)) {
+      *slot = i;
+      return PQA_OK;
+    }
+  ResampleTable th, tv;
+  if (resample_table((int)sp->filter, (int)sp->src_width, (int)sp->dst_width, sp->x0_q16, sp->w_q16, &th) != 0 ||
+      resample_table((int)sp->filter, (int)sp->src_height, (int)sp->dst_height, sp->y0_q16, sp->h_q16, &tv) != 0)
+    return fail(c, PQA_EINVAL, "resample: a destination sample needs more than %d taps", kRsMaxTaps);
+  const int i = c->rs_next;
+  RsCached& e = c->rs_cache[i];
+  e.valid = false;
+  resample_plan(th, tv, (int)sp->dst_width, (int)sp->dst_height, &e.plan);
+  HIPCHK(c, hipSetDevice(c->device));
+  const SideBuf buf = (SideBuf)(SIDE_RS_TABLE0 + i);
+  const size_t bytes = e.plan.words.size() * sizeof(int32_t);
+  const int rc = side_reserve(c, buf, bytes);
+  if (rc != PQA_OK) return rc;
+  HIPCHK(c, hipMemcpy(c->side_buf[buf], e.plan.words.data(), bytes, hipMemcpyHostToDevice));   // nothing of this call is queued yet
+  std::vector<int32_t>().swap(e.plan.words);
+  e.spec = *sp;
+  e.valid = true;
+  c->rs_next = (i + 1) % kRsCached;
+  *slot = i;
+  return PQA_OK;
+}
+
+int rs_pin_reserve(pqa_ctx* c, int which, size_t bytes) {
+  if (c->rs_pin_cap[which] >= bytes) return PQA_OK;
+  if (c->rs_pin[which]) {
+    HIPCHK(c, hipHostFree(c->rs_pin[which]));
+    c->rs_pin[which] = nullptr;
+    c->rs_pin_cap[which] = 0;
+  }
+  HIPCHK(c, hipHostMalloc((void**)&c->rs_pin[which], bytes, hipHostMallocDefault));
+  c->rs_pin_cap[which] = bytes;
   return PQA_OK;
 }
 
@@ -573,6 +627,79 @@ int pqa_level_stats(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_s
                              c->luma_half[1].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es), m, w, h, dev_out + (size_t)f0 * n);
   }
   return side_finish(c, "level_stats", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+}
+
+// ---- resampler (resample.hip) ------------------------------------------------------------------------------------------
+
+int pqa_resample_device(pqa_ctx* c, const pqa_resample_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
+                        void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
+  int rc = rs_check(c, spec);
+  if (rc != PQA_OK) return rc;
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "resample: negative frame count");
+  if (n_frames > 0 && (!src || !dst)) return fail(c, PQA_EINVAL, "resample: null plane pointer");
+  const int es = c->esize;
+  rc = check_device_clip(c, "resample: source ", src_row_pitch, src_frame_pitch, (int64_t)spec->src_width * es);
+  if (rc == PQA_OK) rc = check_device_clip(c, "resample: destination ", dst_row_pitch, dst_frame_pitch, (int64_t)spec->dst_width * es);
+  if (rc != PQA_OK) return rc;
+  int slot = 0;
+  rc = rs_tables(c, spec, &slot);   // more than 32 taps: refused before any device call
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kRsChunk)
+    e = launch_resample(c->stream, c->elem, (int)c->cfg.bit_depth, c->rs_cache[slot].plan, (const int*)c->side_buf[SIDE_RS_TABLE0 + slot],
+                        (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch / es, src_frame_pitch / es,
+                        (int)spec->src_width, (int)spec->src_height, (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch / es,
+                        dst_frame_pitch / es, (int)spec->dst_width, (int)spec->dst_height, chunk_len(n_frames, f0, kRsChunk));
+  return side_finish(c, "resample", e, nullptr, nullptr, 0);
+}
+
+int pqa_resample(pqa_ctx* c, const pqa_resample_spec* spec, const void* const* src_frames, int64_t src_row_stride,
+                 void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames) {
+  int rc = rs_check(c, spec);
+  if (rc != PQA_OK) return rc;
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "resample: negative frame count");
+  if (n_frames > 0 && (!src_frames || !dst_frames)) return fail(c, PQA_EINVAL, "resample: null frame list");
+  const int es = c->esize;
+  const int sw = (int)spec->src_width, sh = (int)spec->src_height, dw = (int)spec->dst_width, dh = (int)spec->dst_height;
+  const size_t src_row = (size_t)sw * es, dst_row = (size_t)dw * es;
+  rc = check_host_frames(c, "resample: ", "source ", src_frames, 1, n_frames, src_row_stride, src_row, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "resample: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, dst_row, true);
+  if (rc != PQA_OK) return rc;
+  int slot = 0;
+  rc = rs_tables(c, spec, &slot);   // more than 32 taps: refused before any device call
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // A source plane may be larger than the context's: the chunks of kRsChunk planes travel through pinned buffers and device
+  // buffers of this entry's own, all grow-only.  Rows are packed 16 bytes apart at least, so the kernel loads and stores
+  // four samples at a time.  A chunk is uploaded, resampled, downloaded and copied out before the next one starts.
+  const int64_t sp = round_up((int64_t)src_row, 16), dp = round_up((int64_t)dst_row, 16);
+  const size_t sf = (size_t)sp * sh, df = (size_t)dp * dh;
+  const int chunk = n_frames < kRsChunk ? n_frames : kRsChunk;
+  rc = rs_pin_reserve(c, 0, sf * chunk);
+  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, df * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RS_SRC, sf * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RS_DST, df * chunk);
+  if (rc != PQA_OK) return rc;
+  for (int f0 = 0; f0 < n_frames; f0 += kRsChunk) {
+    const int n = chunk_len(n_frames, f0, kRsChunk);
+    for (int f = 0; f < n; ++f) copy_plane_rows(c->rs_pin[0] + (size_t)f * sf, sp, (const uint8_t*)src_frames[f0 + f], src_row_stride, src_row, sh);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_RS_SRC], c->rs_pin[0], sf * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_resample(c->stream, c->elem, (int)c->cfg.bit_depth, c->rs_cache[slot].plan, (const int*)c->side_buf[SIDE_RS_TABLE0 + slot],
+                          c->side_buf[SIDE_RS_SRC], sp / es, (int64_t)(sf / es), sw, sh, c->side_buf[SIDE_RS_DST], dp / es,
+                          (int64_t)(df / es), dw, dh, n);
+    rc = side_finish(c, "resample", e, c->rs_pin[1], c->side_buf[SIDE_RS_DST], df * n);
+    if (rc != PQA_OK) return rc;
+    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
+      for (int y = 0; y < dh; ++y)
+        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->rs_pin[1] + (size_t)f * df + (size_t)y * dp, dst_row);
+  }
+  return PQA_OK;
 }
 
 }  // extern "C"

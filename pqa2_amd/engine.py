@@ -399,6 +399,50 @@ class FeatureEngine:
                                                     dis_frame_pitch, int(n_frames), int(plane), out.ctypes.data))
         return out
 
+    # -- resampling --------------------------------------------------------------------------
+    def _resample_spec(self, src_shape, dst_shape, filter, window):
+        """the pqa_resample_spec of planes src_shape -> dst_shape ((height, width) each); window = (x0, y0, w, h) in source
+        samples, rounded to Q16 (None: the whole plane)"""
+        if filter not in N.RESAMPLE_FILTERS:
+            raise ValueError(f"resample filter must be one of {sorted(N.RESAMPLE_FILTERS)}, not {filter!r}")
+        x0, y0, ww, wh = window if window is not None else (0, 0, src_shape[1], src_shape[0])
+        sp = N.PqaResampleSpec()
+        sp.struct_size, sp.filter = C.sizeof(N.PqaResampleSpec), N.RESAMPLE_FILTERS[filter]
+        sp.src_width, sp.src_height, sp.dst_width, sp.dst_height = (max(0, int(v)) for v in (src_shape[1], src_shape[0], dst_shape[1], dst_shape[0]))
+        sp.x0_q16, sp.y0_q16, sp.w_q16, sp.h_q16 = (int(round(v * 65536)) for v in (x0, y0, ww, wh))
+        return sp
+
+    def resample(self, frames, dst_shape, filter: str = "bicubic", window=None):
+        """A list of 2-D arrays of dst_shape = (height, width): every plane of `frames` (2-D arrays of one size, which need
+        not be this context's) resized with the exact-integer polyphase filter "bilinear", "bicubic" or "lanczos"
+        (pqa_resample; definition: include/pqa_vmaf.h).  window = (x0, y0, w, h) in source samples is what the result
+        shows (default: the whole plane); a fractional (x0, y0) with dst_shape = the source's is a sub-pixel shift.  Planes
+        in HOST memory; samples of this context's bit depth."""
+        arrs = [np.asarray(f) for f in frames]
+        if any(a.ndim != 2 or a.dtype != self.dtype or a.strides[1] != a.itemsize or a.strides[0] < 0 or a.strides[0] != arrs[0].strides[0]
+               for a in arrs):
+            arrs = [np.ascontiguousarray(a, dtype=self.dtype) for a in arrs]
+        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
+            raise ValueError("resample needs 2-D planes of one size")
+        src_shape = arrs[0].shape if arrs else (int(dst_shape[0]), int(dst_shape[1]))
+        sp = self._resample_spec(src_shape, dst_shape, filter, window)
+        out = [np.empty((sp.dst_height, sp.dst_width), self.dtype) for _ in arrs]
+        sptr, dptr = (C.c_void_p * max(len(arrs), 1))(), (C.c_void_p * max(len(arrs), 1))()
+        for i, (a, o) in enumerate(zip(arrs, out)):
+            sptr[i], dptr[i] = a.ctypes.data, o.ctypes.data
+        itemsize = np.dtype(self.dtype).itemsize
+        self._check(self.lib.pqa_resample(self._ctx, C.byref(sp), sptr, arrs[0].strides[0] if arrs else src_shape[1] * itemsize,
+                                          dptr, sp.dst_width * itemsize, len(arrs)))
+        return out
+
+    def resample_resident(self, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, src_shape, dst_ptr: int,
+                          dst_row_pitch: int, dst_frame_pitch: int, dst_shape, n_frames: int, filter: str = "bicubic", window=None):
+        """The same for planes in HBM (device pointers, pitches in bytes; pqa_resample_device): n_frames planes of src_shape
+        at src_ptr become planes of dst_shape at dst_ptr.  Nothing crosses PCIe; the result can go into submit_resident."""
+        sp = self._resample_spec(src_shape, dst_shape, filter, window)
+        self._check(self.lib.pqa_resample_device(self._ctx, C.byref(sp), src_ptr, src_row_pitch, src_frame_pitch, dst_ptr,
+                                                 dst_row_pitch, dst_frame_pitch, int(n_frames)))
+
     # -- results -----------------------------------------------------------------------------
     def collect(self, first_index: int, count: int) -> np.ndarray:
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)

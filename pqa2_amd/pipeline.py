@@ -33,7 +33,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False,
                 integrity: bool = False, integrity_options=None, align: int = 0,
                 align_frames: int | None = None, align_penalty_mse: float | None = None, spatial_align: int = 0,
-                spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8) -> ScoreResult | None:
+                spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8,
+                resize: str | None = None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -68,7 +69,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     (dx, dy) != (0, 0).  When applied, both clips are cropped to the common window and scored at (W - |dx|) x (H - |dy|):
     the reference from (max(0, -dx), max(0, -dy)), the capture from that origin moved by (dx, dy), chroma planes from
     `origin >> shift` of each clip.  `chroma_exact` is false when dx or dy is no multiple of the chroma subsampling: chroma
-    is then paired half a chroma sample off.  Scaling and sub-pixel displacement are not corrected.
+    is then paired half a chroma sample off.  A scale factor inside the frame and a sub-pixel displacement are not corrected
+    (a clip of another frame size: `resize`).
     `spatial_align` = 0: no search, pixel (x, y) meets pixel (x, y).
     `level_align` = "report" or "apply": before scoring (after the temporal and spatial steps, on the pairs and the window
     they produced), the per-level transfer table of `level_frames` pairs spread evenly over the common range
@@ -85,10 +87,20 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ref_rd = open_video(reference_path, **raw_kwargs)
     dis_rd = open_video(distorted_path, **raw_kwargs)
     ri, di = ref_rd.info, dis_rd.info
-    if (ri.width, ri.height) != (di.width, di.height):
+    if resize is not None and resize not in N.RESAMPLE_FILTERS:
+        raise ValueError(f"resize must be None or one of {sorted(N.RESAMPLE_FILTERS)}")
+    if resize is None and (ri.width, ri.height) != (di.width, di.height):
         raise ValueError(f"reference is {ri.width}x{ri.height} but distorted is {di.width}x{di.height}")
     if ri.bit_depth != di.bit_depth or (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono):
         raise ValueError("reference and distorted clips differ in pixel format")
+    resized = resampler = None
+    if resize is not None:
+        resized = {"filter": resize, "from": [di.width, di.height], "to": [ri.width, ri.height],
+                   "applied": (ri.width, ri.height) != (di.width, di.height)}
+        if resized["applied"]:
+            dis_rd = resampler = _ResampledReader(dis_rd, ri, resize, device,
+                                                  engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+            di = dis_rd.info
     alignment = None
     if align:
         if align < 0 or align > 64:
@@ -228,6 +240,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
     ext5 = shard.gather_records(local_ext5, n, world_size, rank, gather_device, width=N.EXT5_DOUBLES) if integrity else None
     if rank != 0:
+        if resampler is not None:
+            resampler.close()
         return None
     ig_result = None
     if integrity:
@@ -276,7 +290,45 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                          fps=n / elapsed if elapsed > 0 else 0.0, **extra)
     if alignment is not None:
         res["alignment"] = alignment
+    if resized is not None:
+        res["resize"] = resized
+    if resampler is not None:   # on an error its context goes with the reader
+        resampler.close()
     return res
+
+
+class _ResampledReader:
+    """A captured clip resampled to the reference's frame size: what score_files reads under resize=.  Every plane is resized
+    to the reference's plane of the same kind (FeatureEngine.resample) on a small context of its own, as _find_shift makes
+    one; frames are fetched in runs of eight, so that a run is one upload, one launch and one download per plane kind, and the
+    last run is kept.  `info` carries the reference's width and height.  No file-descriptor path: the resampled samples exist
+    in host arrays only, so the frames go down through FeatureEngine.submit.  close() frees the context (as does dropping the
+    reader)."""
+    RUN = 8
+
+    def __init__(self, reader, ref_info, filter: str, device, make):
+        import dataclasses
+        src = reader.info
+        self._rd, self._filter = reader, filter
+        self.info = dataclasses.replace(src, width=ref_info.width, height=ref_info.height)
+        self._shapes = [(self.info.height, self.info.width)] + ([(self.info.chroma_h, self.info.chroma_w)] * 2 if not src.mono else [])
+        self._eng = make(ref_info.width, ref_info.height, bit_depth=src.bit_depth, n_planes=1, chroma_shift=(src.hshift, src.vshift),
+                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd)
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
+            planes = [self._eng.resample([f[p] for f in frames], shape, self._filter) for p, shape in enumerate(self._shapes)]
+            self._first, self._run = first, [[planes[p][k] for p in range(len(self._shapes))] for k in range(len(frames))]
+        return self._run[i - self._first]
 
 
 class _ShiftedReader:

@@ -102,6 +102,9 @@ def main(argv=None) -> int:
                     help="--level-align, and undo a mapping found on every plane that has one before scoring")
     ap.add_argument("--level-frames", type=int, default=8, metavar="N",
                     help="with --level-align / --level-correct: measure N frame pairs spread evenly over the clips (default 8)")
+    ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
+                    help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
+                         "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -149,6 +152,7 @@ def main(argv=None) -> int:
                           **({"spatial_align": a.spatial_align, "spatial_frames": a.spatial_frames} if a.spatial_align else {}),
                           **({"level_align": "apply" if a.level_correct else "report", "level_frames": a.level_frames}
                              if (a.level_align or a.level_correct) else {}),
+                          **({"resize": a.resize} if a.resize else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
@@ -162,7 +166,8 @@ def main(argv=None) -> int:
         log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
                                     {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
                                      **report.integrity_log_keys(res.get("integrity")),
-                                     **report.alignment_log_keys(res.get("alignment"))})
+                                     **report.alignment_log_keys(res.get("alignment")),
+                                     **({"resize": res["resize"]} if res.get("resize") else {})})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:

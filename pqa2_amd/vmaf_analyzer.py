@@ -165,6 +165,8 @@ class VMAFAnalyzer(QObject):
         self.spatial_align_radius = 8         # -radius ... radius pixels in x and y (pipeline.score_files(spatial_align=))
         self.level_align_enabled = False      # level alignment before scoring: measure the capture's gain / offset / range
         self.level_correct_enabled = False    # ... and undo it (implies the measurement; pipeline.score_files(level_align=))
+        self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
+                                              # size to the reference's before scoring (pipeline.score_files(resize=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -428,7 +430,8 @@ class VMAFAnalyzer(QObject):
         log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
                                     {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
                                      **report.integrity_log_keys(res.get("integrity")),
-                                     **report.alignment_log_keys(res.get("alignment"))})
+                                     **report.alignment_log_keys(res.get("alignment")),
+                                     **({"resize": res["resize"]} if res.get("resize") else {})})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -461,7 +464,8 @@ class VMAFAnalyzer(QObject):
                 **({"align": int(self.align_max_offset)} if self.align_enabled else {}),
                 **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {}),
                 **({"level_align": "apply" if self.level_correct_enabled else "report"}
-                   if (self.level_align_enabled or self.level_correct_enabled) else {})}
+                   if (self.level_align_enabled or self.level_correct_enabled) else {}),
+                **({"resize": self.resize_filter} if self.resize_filter else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -502,6 +506,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--level-correct"]
         elif self.level_align_enabled:
             cmd += ["--level-align"]
+        if self.resize_filter:
+            cmd += ["--resize", str(self.resize_filter)]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
