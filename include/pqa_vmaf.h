@@ -552,6 +552,41 @@ PQA_API int pqa_resample_device(pqa_ctx* ctx, const pqa_resample_spec* spec, con
                                 int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
                                 int32_t n_frames);
 
+/* Sub-pixel registration: the tile-wise gradient moments of n_frames frame pairs of one plane, synchronously -- the
+ * Lucas-Kanade normal equations of every tile, from which pqa2_amd/align.py (solve_geometry, register) estimates a sub-pixel
+ * shift and a scale factor per axis and drives the source window of pqa_resample.  Planes of width x height samples (the
+ * spec's, independent of the context's width and height; each 3 ... 8192), u8 in an 8-bit context, otherwise u16 of the
+ * context's bit depth b (a sample above 2^b - 1 is read as 2^b - 1).  With r = ref, d = dis, a = r + d, e = d - r, at every
+ * pixel 1 <= x <= W - 2, 1 <= y <= H - 2:
+ *     gx = (a[y-1][x+1] + 2 a[y][x+1] + a[y+1][x+1]) - (a[y-1][x-1] + 2 a[y][x-1] + a[y+1][x-1])
+ *     gy = (a[y+1][x-1] + 2 a[y+1][x] + a[y+1][x+1]) - (a[y-1][x-1] + 2 a[y-1][x] + a[y-1][x+1])
+ *     dt = sum_{j,i in -1..1} w_j w_i e[y+j][x+i],  w = (1, 2, 1)
+ * Tile (i, j) of size T = tile (8, 16, 32 or 64) owns the counted pixels with x / T = i, y / T = j; the grid is
+ * tx = ceil(W / T) by ty = ceil(H / T), and
+ *     out[f][j][i][0..5] = sum gx^2, sum gx gy, sum gy^2, sum gx dt, sum gy dt, sum dt^2
+ * Exact int64, no floating point anywhere; a tile with no counted pixel is all zeros.  out (host) is [n_frames][ty][tx][6].
+ * The signs are those of pqa_shift_sse: a captured picture displaced to the right by dx > 0 gives sum gx dt of the sign of
+ * -dx sum gx^2.  Any context, no feature bit; buffers are made on first use, grow only and are freed with the context.
+ * Independent of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL, before any device
+ * call, on a null pointer, a bad struct_size, a tile other than 8 / 16 / 32 / 64, a size outside 3 ... 8192, a row pitch
+ * shorter than a row (or, in device memory, a pitch that is no multiple of the sample size), or a negative frame count.
+ * n_frames == 0 succeeds and writes nothing.  Kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_flow_moments: frames in HOST memory (ref_frames[f] / dis_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample.
+ * pqa_flow_moments_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+typedef struct pqa_flow_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane, 3 ... 8192 */
+  uint32_t tile;          /* 8, 16, 32 or 64 */
+} pqa_flow_spec;
+PQA_API int pqa_flow_moments(pqa_ctx* ctx, const pqa_flow_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                             const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, int64_t* out);
+PQA_API int pqa_flow_moments_device(pqa_ctx* ctx, const pqa_flow_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                    int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                    int32_t n_frames, int64_t* out);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to

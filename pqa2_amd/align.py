@@ -396,3 +396,207 @@ def correction_lut(levels: dict, bit_depth: int, chroma: bool = False) -> np.nda
     if levels["kind"] in LEVEL_MAPS:
         return level_lut(*named_level_map(levels["kind"], bit_depth, chroma), bit_depth)
     return level_lut(levels["gain"], levels["offset"], bit_depth)
+
+
+# ---- sub-pixel and scale registration ------------------------------------------------------------------------------------------
+# The map of one axis of n samples, in edge coordinates X = x + 1/2:  X_dis = n/2 + s (X_ref - n/2) + d.  d > 0: the captured
+# picture is displaced to the right (down), as in best_shift; s > 1: it is larger.  The captured clip resampled onto the
+# reference grid is a same-size pqa_resample call with the source window x0 = d + n (1 - s) / 2, w = n s.  The state of the
+# iteration is that window as Q16 integers, nothing else: every step below is a function of integers.
+Q16 = 65536
+REGISTER_STOP_PX = Fraction(1, 64)   # an increment that moves no frame corner this far ends the iteration at a level
+
+
+def _round_q16(v: Fraction) -> int:
+    return (Fraction(v) * Q16 + Fraction(1, 2)).__floor__()
+
+
+def geometry_window(d, s, n: int):
+    """(x0_q16, w_q16) of the map (d, s) of an axis of n samples: x0 = d + n (1 - s) / 2 and w = n s, each rounded to Q16
+    (half up); d and s are taken as exact Fractions"""
+    d, s = Fraction(d), Fraction(s)
+    return _round_q16(d + n * (1 - s) / 2), _round_q16(n * s)
+
+
+def window_geometry(x0_q16: int, w_q16: int, n: int):
+    """(d, s) as Fractions of the window (x0_q16, w_q16) of an axis of n samples: the inverse of geometry_window, exact"""
+    s = Fraction(int(w_q16), Q16 * n)
+    return Fraction(int(x0_q16), Q16) - n * (1 - s) / 2, s
+
+
+def compose_geometry(d, s, a, e):
+    """(d + s a, s (1 + e)): the map (d, s) after the increment u = a + e p was measured on the clip resampled through it
+    (p: the distance from the frame centre); Fractions, not quantised"""
+    d, s, a, e = Fraction(d), Fraction(s), Fraction(a), Fraction(e)
+    return d + s * a, s * (1 + e)
+
+
+def _solve_fractions(A, b):
+    """x of A x = b by Gaussian elimination in Fractions; None when A is singular"""
+    n = len(b)
+    rows = [[Fraction(v) for v in A[i]] + [Fraction(b[i])] for i in range(n)]
+    for c in range(n):
+        piv = next((r for r in range(c, n) if rows[r][c] != 0), None)
+        if piv is None:
+            return None
+        rows[c], rows[piv] = rows[piv], rows[c]
+        for r in range(n):
+            if r != c and rows[r][c] != 0:
+                k = rows[r][c] / rows[c][c]
+                rows[r] = [x - k * y for x, y in zip(rows[r], rows[c])]
+    return [rows[i][n] / rows[i][i] for i in range(n)]
+
+
+def _tile_centres(n: int, tile: int):
+    """per tile of an axis of n samples: the centre of its counted pixels (1 ... n - 2) relative to the frame centre, in edge
+    coordinates -- (lo + hi + 1) / 2 - n / 2 --, or None when it counts no pixel"""
+    out = []
+    for i in range(-(-n // tile)):
+        lo, hi = max(1, i * tile), min(n - 2, (i + 1) * tile - 1)
+        out.append(Fraction(lo + hi + 1 - n, 2) if lo <= hi else None)
+    return out
+
+
+def solve_geometry(M, width: int, height: int, tile: int):
+    """The increment (a_x, e_x, a_y, e_y), as Fractions, from the tile moments M[ty][tx][6] = sum gx^2, gx gy, gy^2, gx dt,
+    gy dt, dt^2 (pqa_flow_moments, summed over the frames): the remaining displacement of the captured picture is modelled
+    as u = a_x + e_x px, v = a_y + e_y py at the tile centre (px, py), relative to the frame centre, and
+    sum over tiles and pixels of (dt + gx u + gy v)^2 is minimised -- a 4 x 4 system in Fractions.  gx, gy and dt all carry
+    the factor 16 of their stencils, so the result is in pixels.  None when the system is singular: fewer than two tile
+    columns or rows that carry gradient, or a flat picture."""
+    M = np.asarray(M)
+    cxs, cys = _tile_centres(int(width), int(tile)), _tile_centres(int(height), int(tile))
+    if M.shape != (len(cys), len(cxs), 6):
+        raise ValueError(f"M must be [{len(cys)}, {len(cxs)}, 6] for {width}x{height} at tile {tile}")
+    A = [[Fraction(0)] * 4 for _ in range(4)]
+    b = [Fraction(0)] * 4
+    for j, py in enumerate(cys):
+        for i, px in enumerate(cxs):
+            if px is None or py is None:
+                continue
+            gxx, gxy, gyy, gxt, gyt = (int(v) for v in M[j, i, :5])
+            basis = ((1, px), (1, py))           # u = basis[0] . (a_x, e_x), v = basis[1] . (a_y, e_y)
+            G = ((gxx, gxy), (gxy, gyy))
+            for p in range(2):
+                for q in range(2):
+                    for m in range(2):
+                        for k in range(2):
+                            A[2 * p + m][2 * q + k] += G[p][q] * basis[p][m] * basis[q][k]
+                for m in range(2):
+                    b[2 * p + m] += (gxt, gyt)[p] * basis[p][m]
+    sol = _solve_fractions(A, [-v for v in b])
+    return None if sol is None else tuple(sol)
+
+
+def _corner_sq(ax, ex, ay, ey, w, h):
+    """the largest squared displacement u^2 + v^2 over the four frame corners of u = ax + ex px, v = ay + ey py"""
+    return max((ax + sx * ex * w / 2) ** 2 + (ay + sy * ey * h / 2) ** 2 for sx in (-1, 1) for sy in (-1, 1))
+
+
+def register_levels(width: int, height: int, tile: int, levels=None):
+    """[(level l, tile at l)] from the coarsest level to 0.  levels = None: the largest l <= 4 at which the (width >> l) x
+    (height >> l) plane still holds 4 whole tiles each way, the tile halved down to 8 where that takes; an int: that l."""
+    def tile_at(l):
+        t = int(tile)
+        while t > 8 and ((width >> l) // t < 4 or (height >> l) // t < 4):
+            t //= 2
+        return t
+    if levels is None:
+        levels = next((l for l in range(4, 0, -1) if (width >> l) // tile_at(l) >= 4 and (height >> l) // tile_at(l) >= 4), 0)
+    if not 0 <= int(levels) <= 4:
+        raise ValueError("levels must be None or 0 ... 4")
+    return [(l, tile_at(l)) for l in range(int(levels), -1, -1)]
+
+
+def geometry_applied(geometry: dict, min_px: float = 1.0 / 16) -> bool:
+    """whether a register() result is worth undoing: it converged, it moves a frame corner by min_px at least, and the last
+    full-resolution pass left less error than the first"""
+    return bool(geometry["converged"] and geometry["corner_px"] >= min_px and geometry["mse_after"] < geometry["mse_before"])
+
+
+def register(moments, resample, ref, dis, *, filter: str = "bicubic", tile: int = 32, levels=None, max_iters: int = 5,
+             trace=None) -> dict:
+    """Sub-pixel shift and scale of the captured luma planes `dis` against `ref` (two lists of 2-D arrays of one size),
+    coarse to fine.  The two callables do the device work -- moments(ref_planes, dis_planes, tile) -> [n, ty, tx, 6] int64
+    (FeatureEngine.flow_moments) and resample(planes, (height, width), filter, window) -> planes (FeatureEngine.resample) --
+    so the same driver runs on the engine and on the numpy restatement (tests/flow_ref.py), with the same integers.
+
+    Pyramid level l is both clips resized whole-plane to (W >> l, H >> l) with "bilinear" (register_levels picks the levels and
+    the tile of each).  At a level, the capture is resampled with `filter` through the window of the current map, the moments
+    of all frames are summed and solve_geometry gives an increment; it is composed (compose_geometry) and the map
+    re-quantised to its Q16 window (geometry_window) until an increment moves no frame corner by 1/64 pixel, or `max_iters`
+    increments were applied.  From level l to l - 1 the shift doubles and the scale stays.  A level whose system is singular
+    is left as it came; at level 0 that ends the run with converged = False, as does a map outside 1/2 < s < 2,
+    |d| < n / 4.  The first pass of all is one at full resolution on the clips as they are: mse_before.
+
+    Returns {dx, dy, sx, sy (floats of the exact Fractions of the final window), x0_q16, y0_q16, w_q16, h_q16 (the same-size
+    pqa_resample window of the luma plane), corner_px (the largest displacement of a frame corner under the map),
+    mse_before, mse_after (sum dt^2 / 256 per counted pixel of the first and of the last full-resolution pass), iterations
+    (increments applied, all levels), levels (the coarsest level), tile, converged}.  `trace` (a list) receives (level,
+    (x0_q16, y0_q16, w_q16, h_q16), M) of every pass."""
+    ref, dis = list(ref), list(dis)
+    if not ref or len(ref) != len(dis):
+        raise ValueError("register needs as many captured as reference planes, and one at least")
+    H, W = np.shape(ref[0])
+    plan = register_levels(W, H, tile, levels)
+
+    def measure(r, d, t, level, win):
+        M = np.asarray(moments(r, d, t)).sum(axis=0)
+        if trace is not None:
+            trace.append((level, win, M.copy()))
+        return M
+
+    def mse(M):
+        return int(M[:, :, 5].sum()) / (256.0 * len(ref) * (W - 2) * (H - 2))
+    full = (0, 0, W * Q16, H * Q16)
+    mse_before = mse_after = mse(measure(ref, dis, plan[-1][1], 0, full))
+    size = (W >> plan[0][0], H >> plan[0][0])
+    win = (0, 0, size[0] * Q16, size[1] * Q16)      # (x0_q16, y0_q16, w_q16, h_q16) at the size of the current level
+    iterations, converged, failed = 0, False, False
+    for level, t in plan:
+        w, h = W >> level, H >> level
+        if (w, h) != size:            # one level finer: the shift scales with the plane, the scale factor stays
+            (dx, sx), (dy, sy) = window_geometry(win[0], win[2], size[0]), window_geometry(win[1], win[3], size[1])
+            (x0, ww), (y0, wh) = geometry_window(dx * 2, sx, w), geometry_window(dy * 2, sy, h)
+            win, size = (x0, y0, ww, wh), (w, h)
+        if level:
+            r_l, d_l = resample(ref, (h, w), "bilinear", None), resample(dis, (h, w), "bilinear", None)
+        else:
+            r_l, d_l = ref, dis
+        converged = False
+        for it in range(max_iters + 1):
+            fwin = tuple(v / float(Q16) for v in win)
+            warped = d_l if win == (0, 0, w * Q16, h * Q16) else resample(d_l, (h, w), filter, fwin)
+            M = measure(r_l, warped, t, level, win)
+            if level == 0:
+                mse_after = mse(M)
+            inc = solve_geometry(M, w, h, t)
+            if inc is None:
+                failed = level == 0
+                break
+            if _corner_sq(*inc, w, h) < REGISTER_STOP_PX ** 2:
+                converged = True
+                break
+            if it == max_iters:
+                break
+            (dx, sx), (dy, sy) = window_geometry(win[0], win[2], w), window_geometry(win[1], win[3], h)
+            dx, sx = compose_geometry(dx, sx, inc[0], inc[1])
+            dy, sy = compose_geometry(dy, sy, inc[2], inc[3])
+            if not (Fraction(1, 2) < sx < 2 and Fraction(1, 2) < sy < 2 and abs(dx) * 4 < w and abs(dy) * 4 < h):
+                failed = True
+                break
+            (x0, ww), (y0, wh) = geometry_window(dx, sx, w), geometry_window(dy, sy, h)
+            win = (x0, y0, ww, wh)
+            iterations += 1
+        if failed:
+            break
+    if failed:
+        converged = False
+    if size != (W, H):      # the run ended above level 0: report the map at full resolution
+        win, size = full, (W, H)
+    (dx, sx), (dy, sy) = window_geometry(win[0], win[2], W), window_geometry(win[1], win[3], H)
+    corner = max(((sx - 1) * gx * W / 2 + dx) ** 2 + ((sy - 1) * gy * H / 2 + dy) ** 2 for gx in (-1, 1) for gy in (-1, 1))
+    return {"dx": float(dx), "dy": float(dy), "sx": float(sx), "sy": float(sy), "x0_q16": int(win[0]), "y0_q16": int(win[1]),
+            "w_q16": int(win[2]), "h_q16": int(win[3]), "corner_px": float(corner) ** 0.5, "mse_before": float(mse_before),
+            "mse_after": float(mse_after), "iterations": int(iterations), "levels": int(plan[0][0]), "tile": int(tile),
+            "converged": bool(converged)}

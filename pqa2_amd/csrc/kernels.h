@@ -451,5 +451,17 @@ hipError_t launch_resample(hipStream_t stream, Elem elem, int bits, const Resamp
                            int64_t src_row_pitch, int64_t src_frame_pitch, int src_w, int src_h, void* dst, int64_t dst_row_pitch,
                            int64_t dst_frame_pitch, int dst_w, int dst_h, int n_frames);
 
+// ---- sub-pixel registration: tile-wise gradient moments (flow_moments.hip) ------------------------------------------------
+// out[f][j][i][0..5] = sum over the counted pixels (1 <= x <= w - 2, 1 <= y <= h - 2) of tile (i, j) = (x / tile, y / tile) of
+// gx^2, gx gy, gy^2, gx dt, gy dt, dt^2 (gx, gy: Sobel of ref + dis; dt: 3 x 3 binomial of dis - ref), exact int64, for n_frames
+// pairs of one w x h plane (3 ... 8192 each way; frame f at base + f * frame_pitch, pitches in elements; samples of `bits`
+// bits).  tile: 8, 16, 32 or 64.  out: device memory of flow_out_bytes(); every entry is written.
+constexpr int kFlowChunk = 8;   // frame pairs per launch of the two entries
+bool flow_tile_ok(int tile);
+size_t flow_out_bytes(int w, int h, int tile, int n_frames);
+hipError_t launch_flow_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
+                               int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                               int n_frames, int w, int h, int tile, long long* out);
+
 }  // namespace pqa
 

@@ -443,6 +443,49 @@ class FeatureEngine:
         self._check(self.lib.pqa_resample_device(self._ctx, C.byref(sp), src_ptr, src_row_pitch, src_frame_pitch, dst_ptr,
                                                  dst_row_pitch, dst_frame_pitch, int(n_frames)))
 
+    # -- sub-pixel registration ----------------------------------------------------------------
+    @staticmethod
+    def _flow_spec(shape, tile):
+        sp = N.PqaFlowSpec()
+        sp.struct_size = C.sizeof(N.PqaFlowSpec)
+        sp.height, sp.width, sp.tile = (max(0, int(v)) for v in (shape[0], shape[1], tile))
+        return sp
+
+    @staticmethod
+    def _flow_out(n, sp):
+        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
+        return np.zeros((max(int(n), 0), -(-sp.height // t), -(-sp.width // t), 6), np.int64)
+
+    def flow_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
+        """[n, ty, tx, 6] int64: per tile of `tile` x `tile` pixels (8, 16, 32 or 64) the sums of gx^2, gx gy, gy^2, gx dt,
+        gy dt, dt^2 over the pixels 1 <= x <= W - 2, 1 <= y <= H - 2 (gx, gy: Sobel of ref + dis; dt: 3 x 3 binomial of
+        dis - ref), exact (pqa_flow_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory: two lists of 2-D arrays
+        of equal length and one size, which need not be this context's (3 ... 8192 each way); samples of this context's bit
+        depth.  align.solve_geometry reads the sum over the frames."""
+        n = len(ref_frames)
+        if len(dis_frames) != n:
+            raise ValueError("flow_moments needs as many captured as reference frames")
+        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError("flow_moments needs 2-D planes")
+        sp = self._flow_spec(shape, tile)
+        out = self._flow_out(n, sp)
+        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
+        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
+        self._check(self.lib.pqa_flow_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def flow_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                              dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
+        """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_flow_moments_device)."""
+        sp = self._flow_spec(shape, tile)
+        out = self._flow_out(n_frames, sp)
+        self._check(self.lib.pqa_flow_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
+                                                     dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
+        return out
+
     # -- results -----------------------------------------------------------------------------
     def collect(self, first_index: int, count: int) -> np.ndarray:
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)

@@ -34,7 +34,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 integrity: bool = False, integrity_options=None, align: int = 0,
                 align_frames: int | None = None, align_penalty_mse: float | None = None, spatial_align: int = 0,
                 spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8,
-                resize: str | None = None) -> ScoreResult | None:
+                resize: str | None = None, register: str | None = None, register_frames: int = 8,
+                register_min_px: float = 1.0 / 16) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -80,7 +81,21 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     applied} and the same for every plane under `planes` ("y", "u", "v").  "report" changes nothing else: the records are
     those of a run without the option.  "apply" maps every captured plane whose `mismatch` is true through the integer table
     that undoes its chosen map (align.correction_lut, numpy.take on the host) before it is scored; `applied` says so per
-    plane.  `level_align` = None: no measurement."""
+    plane.  `level_align` = None: no measurement.
+    `register` = "bilinear", "bicubic" or "lanczos": before scoring (after the temporal and spatial steps, on the pairs and the
+    window they produced, and before the levels), the sub-pixel displacement and the scale factor per axis of the captured
+    picture are measured on `register_frames` luma pairs spread evenly over the common range -- tile-wise gradient moments
+    (pqa_flow_moments) solved coarse to fine by align.register, which resamples the capture with this filter as it goes.
+    `alignment["geometry"]` holds {dx, dy, sx, sy, x0_q16, y0_q16, w_q16, h_q16, corner_px, mse_before, mse_after, iterations,
+    levels, tile, converged, frames, applied, crop, filter}: the map is X_dis = n/2 + s (X_ref - n/2) + d per axis in edge
+    coordinates, with the signs of `spatial` (dx > 0: displaced to the right).  `applied` = converged and corner_px >=
+    `register_min_px` and mse_after < mse_before.  When applied, every captured plane is resampled onto the reference grid
+    through the window of the map (pqa_resample at equal size; chroma planes with d / 2^shift and the same s -- chroma siting
+    is not modelled, as under `resize`), and both clips are cropped to the reference pixels whose source centre lies inside
+    the captured frame, the margins `crop` = [left, top, right, bottom] rounded up to the chroma step.  Not applied: the
+    records are those of a run without the option.  After `resize` this is a second filter pass over the captured samples,
+    in series with the first: the two are not folded into one.  Rotation is not modelled.  `register` = None: no
+    measurement."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -121,6 +136,23 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         alignment = dict(alignment or {}, spatial=spatial)
         if spatial["applied"]:
             ref_rd, dis_rd = crop_readers(ref_rd, dis_rd, spatial["dx"], spatial["dy"])
+            ri, di = ref_rd.info, dis_rd.info
+    registered = None
+    if register is not None:
+        if register not in N.RESAMPLE_FILTERS:
+            raise ValueError(f"register must be None or one of {sorted(N.RESAMPLE_FILTERS)}")
+        if register_frames is None or register_frames < 1:
+            raise ValueError("register_frames must be positive")
+        if register_min_px is None or not register_min_px >= 0:
+            raise ValueError("register_min_px must not be negative")
+        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
+        geometry = _find_geometry(ref_rd, dis_rd, register, int(register_frames), float(register_min_px), device, make_side)
+        alignment = dict(alignment or {}, geometry=geometry)
+        if geometry["applied"]:
+            registered = _RegisteredReader(dis_rd, geometry, device, make_side)
+            left, top, right, bottom = geometry["crop"]
+            cw, ch = ri.width - left - right, ri.height - top - bottom
+            ref_rd, dis_rd = _CroppedReader(ref_rd, left, top, cw, ch), _CroppedReader(registered, left, top, cw, ch)
             ri, di = ref_rd.info, dis_rd.info
     if level_align is not None:
         if level_align not in ("report", "apply"):
@@ -240,8 +272,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
     ext5 = shard.gather_records(local_ext5, n, world_size, rank, gather_device, width=N.EXT5_DOUBLES) if integrity else None
     if rank != 0:
-        if resampler is not None:
-            resampler.close()
+        for rd in (resampler, registered):
+            if rd is not None:
+                rd.close()
         return None
     ig_result = None
     if integrity:
@@ -292,8 +325,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["alignment"] = alignment
     if resized is not None:
         res["resize"] = resized
-    if resampler is not None:   # on an error its context goes with the reader
-        resampler.close()
+    for rd in (resampler, registered):   # on an error their contexts go with the readers
+        if rd is not None:
+            rd.close()
     return res
 
 
@@ -329,6 +363,90 @@ class _ResampledReader:
             planes = [self._eng.resample([f[p] for f in frames], shape, self._filter) for p, shape in enumerate(self._shapes)]
             self._first, self._run = first, [[planes[p][k] for p in range(len(self._shapes))] for k in range(len(frames))]
         return self._run[i - self._first]
+
+
+class _RegisteredReader:
+    """A captured clip resampled onto the reference grid through the window of a measured geometry (the `geometry` object of
+    _find_geometry): what score_files reads under register= once the map is applied.  Built like _ResampledReader -- a small
+    context of its own, frames fetched in runs of eight, the last run kept --; every plane keeps its size.  The luma window is
+    the measured one; a chroma plane of n_c samples along an axis gets geometry_window(d / 2^shift, s, n_c).  No
+    file-descriptor path.  close() frees the context."""
+    RUN = 8
+
+    def __init__(self, reader, geometry: dict, device, make):
+        from . import align as AL
+        info = self.info = reader.info
+        self._rd, self._filter = reader, geometry["filter"]
+        dx, sx = AL.window_geometry(geometry["x0_q16"], geometry["w_q16"], info.width)
+        dy, sy = AL.window_geometry(geometry["y0_q16"], geometry["h_q16"], info.height)
+        self._shapes = [(info.height, info.width)] + ([(info.chroma_h, info.chroma_w)] * 2 if not info.mono else [])
+        self.windows = [(geometry["x0_q16"], geometry["y0_q16"], geometry["w_q16"], geometry["h_q16"])]
+        if not info.mono:
+            (x0, ww), (y0, wh) = (AL.geometry_window(dx / (1 << info.hshift), sx, info.chroma_w),
+                                  AL.geometry_window(dy / (1 << info.vshift), sy, info.chroma_h))
+            self.windows += [(x0, y0, ww, wh)] * 2
+        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=1, chroma_shift=(info.hshift, info.vshift),
+                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd)
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
+            planes = [self._eng.resample([f[p] for f in frames], shape, self._filter, tuple(v / 65536.0 for v in win))
+                      for p, (shape, win) in enumerate(zip(self._shapes, self.windows))]
+            self._first, self._run = first, [[planes[p][k] for p in range(len(self._shapes))] for k in range(len(frames))]
+        return self._run[i - self._first]
+
+
+def registration_crop(geometry: dict, width: int, height: int, hshift: int = 0, vshift: int = 0):
+    """[left, top, right, bottom]: the margins outside the reference pixels whose source centre -- n/2 + s (x + 1/2 - n/2) + d
+    - 1/2 in captured samples -- lies in 0 ... n - 1, each rounded up to the chroma step (exact, in Fractions)"""
+    from fractions import Fraction
+    from . import align as AL
+
+    def axis(x0_q16, w_q16, n, step):
+        d, s = AL.window_geometry(x0_q16, w_q16, n)
+        half = Fraction(1, 2)
+        lo = ((half - d - Fraction(n, 2)) / s + Fraction(n, 2) - half).__ceil__()        # the first x with a source centre >= 0
+        hi = ((n - half - d - Fraction(n, 2)) / s + Fraction(n, 2) - half).__floor__()    # the last with one <= n - 1
+        lo, hi = max(lo, 0), min(hi, n - 1)
+        return -(-lo // step) * step, -(-(n - 1 - hi) // step) * step
+    left, right = axis(geometry["x0_q16"], geometry["w_q16"], width, 1 << hshift)
+    top, bottom = axis(geometry["y0_q16"], geometry["h_q16"], height, 1 << vshift)
+    return [int(left), int(top), int(right), int(bottom)]
+
+
+REGISTER_TILE = 32     # tile of the registration moments at full resolution (align.register halves it on small levels)
+
+
+def _find_geometry(ref_rd, dis_rd, filter: str, n_frames: int, min_px: float, device, make) -> dict:
+    """the `geometry` object of two opened, paired clips of one size: align.register on a few luma pairs, on a small context
+    of its own"""
+    from . import align as AL
+    ri = ref_rd.info
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError("no frames to align")
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
+               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+    try:
+        geo = AL.register(eng.flow_moments, eng.resample, [ref_rd.frame(i)[0] for i in idx], [dis_rd.frame(i)[0] for i in idx],
+                          filter=filter, tile=REGISTER_TILE, levels=None)
+    finally:
+        eng.close()
+    geo["frames"] = len(idx)
+    geo["filter"] = filter
+    geo["applied"] = AL.geometry_applied(geo, min_px)
+    hs, vs = (0, 0) if ri.mono else (ri.hshift, ri.vshift)
+    geo["crop"] = registration_crop(geo, ri.width, ri.height, hs, vs) if geo["applied"] else [0, 0, 0, 0]
+    return geo
 
 
 class _ShiftedReader:

@@ -134,6 +134,21 @@ def spatial_summary_line(spatial: dict) -> str:
             f"{spatial.get('frames', 0)} frames, searched +-{spatial.get('searched')} px, {what}")
 
 
+def geometry_summary_line(geometry: dict) -> str:
+    """One line for a summary or a status bar: the sub-pixel shift and scale found, their effect and whether they were undone."""
+    if not geometry.get("converged"):
+        what = "no stable estimate: nothing applied"
+    elif geometry.get("applied"):
+        crop = geometry.get("crop", [0, 0, 0, 0])
+        what = f"capture resampled ({geometry.get('filter')}), clips cropped by {crop[0]}/{crop[1]}/{crop[2]}/{crop[3]} px"
+    else:
+        what = "within tolerance: nothing applied"
+    return (f"Registration: capture displaced by ({geometry.get('dx', 0.0):+.3f}, {geometry.get('dy', 0.0):+.3f}) px, scaled by "
+            f"({geometry.get('sx', 1.0):.5f}, {geometry.get('sy', 1.0):.5f}), {geometry.get('corner_px', 0.0):.3f} px at the "
+            f"corners, MSE {geometry.get('mse_before', 0.0):.2f} -> {geometry.get('mse_after', 0.0):.2f}, "
+            f"{geometry.get('iterations', 0)} iterations on {geometry.get('frames', 0)} frames, {what}")
+
+
 def levels_summary_line(levels: dict) -> str:
     """One line for a summary or a status bar: the level mapping found for luma, its error and whether it was undone."""
     if levels.get("degenerate"):

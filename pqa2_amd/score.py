@@ -105,6 +105,12 @@ def main(argv=None) -> int:
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
+    ap.add_argument("--register", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
+                    help="measure the sub-pixel displacement and the scale factor of the captured picture (tile-wise gradient "
+                         "moments, coarse to fine) and, where it matters, resample the capture onto the reference grid with "
+                         "this filter and crop both clips; the JSON's alignment object gets a geometry entry")
+    ap.add_argument("--register-frames", type=int, default=8, metavar="N",
+                    help="with --register: measure N frame pairs spread evenly over the clips (default 8)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -153,6 +159,7 @@ def main(argv=None) -> int:
                           **({"level_align": "apply" if a.level_correct else "report", "level_frames": a.level_frames}
                              if (a.level_align or a.level_correct) else {}),
                           **({"resize": a.resize} if a.resize else {}),
+                          **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
@@ -187,6 +194,8 @@ def main(argv=None) -> int:
             print(report.spatial_summary_line(res["alignment"]["spatial"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("levels"):
             print(report.levels_summary_line(res["alignment"]["levels"]), file=sys.stderr, flush=True)
+        if res.get("alignment") and res["alignment"].get("geometry"):
+            print(report.geometry_summary_line(res["alignment"]["geometry"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

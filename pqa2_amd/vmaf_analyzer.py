@@ -167,6 +167,8 @@ class VMAFAnalyzer(QObject):
         self.level_correct_enabled = False    # ... and undo it (implies the measurement; pipeline.score_files(level_align=))
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
+        self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
+                                              # scale and undo them with this filter (pipeline.score_files(register=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -465,7 +467,8 @@ class VMAFAnalyzer(QObject):
                 **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {}),
                 **({"level_align": "apply" if self.level_correct_enabled else "report"}
                    if (self.level_align_enabled or self.level_correct_enabled) else {}),
-                **({"resize": self.resize_filter} if self.resize_filter else {})}
+                **({"resize": self.resize_filter} if self.resize_filter else {}),
+                **({"register": self.register_filter} if self.register_filter else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -508,6 +511,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--level-align"]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
+        if self.register_filter:
+            cmd += ["--register", str(self.register_filter)]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:
@@ -623,7 +628,7 @@ class VMAFAnalyzer(QObject):
                 results["integrity"] = vmaf_data.get("integrity")
                 results["integrity_log"] = self._integrity_path
             if (self.align_enabled or self.spatial_align_enabled or self.level_align_enabled
-                    or self.level_correct_enabled):   # how the clips were paired, from the log's top level
+                    or self.level_correct_enabled or self.register_filter):   # how the clips were paired, from the log's top level
                 from . import report
                 results["alignment"] = vmaf_data.get("alignment")
                 if results["alignment"] and "offset_frames" in results["alignment"]:
@@ -632,6 +637,8 @@ class VMAFAnalyzer(QObject):
                     self.status_update.emit(report.spatial_summary_line(results["alignment"]["spatial"]))
                 if results["alignment"] and results["alignment"].get("levels"):
                     self.status_update.emit(report.levels_summary_line(results["alignment"]["levels"]))
+                if results["alignment"] and results["alignment"].get("geometry"):
+                    self.status_update.emit(report.geometry_summary_line(results["alignment"]["geometry"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
