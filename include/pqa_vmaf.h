@@ -587,6 +587,49 @@ PQA_API int pqa_flow_moments_device(pqa_ctx* ctx, const pqa_flow_spec* spec, con
                                     int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                     int32_t n_frames, int64_t* out);
 
+/* Colour-matrix alignment: the cross-plane moments of n_frames frame pairs, synchronously -- what a capture chain that decodes
+ * Y'CbCr with one matrix and encodes with another (BT.709 through a BT.601 leg) leaves behind, which no single-plane
+ * measurement sees.  Works on the chroma grid of the context: chroma_shift = (hs, vs), s = 2^(hs + vs), chroma planes of
+ * ceil(width / 2^hs) x ceil(height / 2^vs) samples.  For every chroma sample c,
+ *     z(c) = (1, SYr, Ur, Vr, SYd, Ud, Vd)
+ * with SY the integer sum of the 2^hs x 2^vs luma samples c covers, luma coordinates clamped to the plane (a partial edge
+ * block of an odd-sized frame still has s terms); nothing is divided.  out[f][28], 28 = pqa_colour_sums(), is the upper
+ * triangle of sum_c z z^T, row-major ((0,0), (0,1) ... (0,6), (1,1) ... (6,6)), exact uint64; entry 0 is the number of samples
+ * that entered.  Mask: a sample enters only if every captured luma sample feeding SYd, Ud and Vd all lie in [lo, hi] -- the
+ * chain clips after it converts, and clipped samples bias a linear fit; lo = 0, hi = 2^bit_depth - 1 keeps everything;
+ * reference samples are never masked.  Samples are u8 in an 8-bit context, otherwise u16 of the context's bit depth b (a
+ * sample above 2^b - 1 is read as 2^b - 1).  Any context with n_planes == 3 and chroma shifts of 0 or 1, no feature bit;
+ * buffers are made on first use, grow only and are freed with the context.  Independent of the scoring chain: a call between
+ * two pqa_submit calls changes no record.  PQA_EINVAL, before any device call, on a null pointer, a negative frame count,
+ * n_planes != 3, a chroma shift above 1, lo > hi, hi > 2^b - 1, a row pitch shorter than a row (or, in device memory, a pitch
+ * that is no multiple of the sample size).  n_frames == 0 succeeds and writes nothing.  pqa2_amd/align.py (best_colour,
+ * colour_correction) turns the sums into the 3 x 4 map and its inverse; kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_colour_moments: frames in HOST memory, laid out as for pqa_frame_sad (frames[f * 3 + p]: plane p of frame f, rows
+ * strides[p] bytes apart).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample.
+ * pqa_colour_moments_device: both clips in device memory (pitches in BYTES), under the ordering contract of pqa_submit_device. */
+PQA_API int pqa_colour_sums(void);
+PQA_API int pqa_colour_moments_device(pqa_ctx* ctx, const pqa_device_clip* ref, const pqa_device_clip* dis, int32_t n_frames,
+                                      uint32_t lo, uint32_t hi, uint64_t* out);
+PQA_API int pqa_colour_moments(pqa_ctx* ctx, const void* const* ref_frames, const int64_t ref_strides[3],
+                               const void* const* dis_frames, const int64_t dis_strides[3], int32_t n_frames, uint32_t lo,
+                               uint32_t hi, uint64_t* out);
+
+/* The matrix apply: every frame of src through the 3 x 4 integer matrix m (row-major, Q14; column 0 is the offset in Q14 code
+ * values) into planes of the same sizes, synchronously.  With top = 2^bit_depth - 1 and c = (x >> hs, y >> vs):
+ *     Y'(x, y) = clamp((m[0] + m[1] Y(x, y) + m[2] U(c) + m[3] V(c) + 2^13) >> 14, 0, top)
+ *     U'(c)    = clamp((m[4] s + m[5] SY(c) + s m[6] U(c) + s m[7] V(c) + s 2^13) >> (14 + hs + vs), 0, top)
+ * and V' like U' with m[8 ... 11]; >> is an arithmetic shift.  Chroma is read by replication for luma, luma as the clamped
+ * block sum for chroma: both as in the moments above.  The identity (m[1] = m[6] = m[11] = 16384, the rest 0) returns the
+ * source.  Same contexts, staging, independence and argument rules as the moments; in addition PQA_EINVAL on a null matrix or
+ * an entry out of range: |m[r][0]| < 2^28 (an offset below 2^14 code values), |m[r][1 ... 3]| < 2^16 (gains below 4).  The
+ * destination of pqa_colour_apply_device is written (its plane pointers are const only because the struct is shared); it
+ * may be the source. */
+PQA_API int pqa_colour_apply_device(pqa_ctx* ctx, const int32_t m[12], const pqa_device_clip* src, const pqa_device_clip* dst,
+                                    int32_t n_frames);
+PQA_API int pqa_colour_apply(pqa_ctx* ctx, const int32_t m[12], const void* const* src_frames, const int64_t src_strides[3],
+                             void* const* dst_frames, const int64_t dst_strides[3], int32_t n_frames);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to
@@ -679,6 +722,15 @@ PQA_API int pqa_debug_siti_plane(const void* cur, const void* prev, int64_t row_
  * 1 ... 8192, a non-positive window, a row of more than 32 taps, or cap_taps < *taps (*taps is set then). */
 PQA_API int pqa_debug_resample_table(uint32_t filter, int32_t n_src, int32_t n_dst, int64_t x0_q16, int64_t ext_q16,
                                      int32_t* first, int16_t* coeff, int32_t cap_taps, int32_t* taps);
+
+/* Test hook (needs a device, no context): the two colour kernels on ONE frame pair of any size, 1 ... 16384 each way -- also the
+ * sizes no context accepts.  ref / dis: packed planes Y, U, V (rows width * sample-size bytes apart; chroma planes of
+ * ceil(w / 2^hshift) x ceil(h / 2^vshift)).  sums28 (nullable) receives pqa_colour_moments' 28 sums of the pair under the mask
+ * lo ... hi; with m (nullable) the packed planes applied[3] receive dis through pqa_colour_apply's matrix.  PQA_EINVAL on a
+ * null pointer, a bad size, depth, shift, mask or matrix, PQA_EDEVICE without a device. */
+PQA_API int pqa_debug_colour(uint32_t bit_depth, uint32_t hshift, uint32_t vshift, uint32_t w, uint32_t h,
+                             const void* const ref[3], const void* const dis[3], uint32_t lo, uint32_t hi, uint64_t* sums28,
+                             const int32_t* m, void* const applied[3]);
 
 #ifdef __cplusplus
 }

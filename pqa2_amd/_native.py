@@ -55,12 +55,12 @@ GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 EXPORTS = [
     "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
     "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
-    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_set_luma_gray",
+    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape",
     "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
     "pqa_debug_psnr_hvs_tables", "pqa_debug_psnr_hvs_plane", "pqa_debug_xpsnr_blocks", "pqa_debug_siti_plane",
-    "pqa_debug_resample_table",
+    "pqa_debug_resample_table", "pqa_debug_colour",
 ]
 
 
@@ -100,6 +100,9 @@ class PqaResampleSpec(C.Structure):
 
 
 FLOW_TILES = (8, 16, 32, 64)
+COLOUR_SUMS = 28                                   # pqa_colour_sums(): the upper triangle of a 7 x 7 matrix
+COLOUR_Q = 14                                      # pqa_colour_apply: the matrix is Q14
+COLOUR_MAX_GAIN, COLOUR_MAX_OFFSET = 1 << 16, 1 << 28   # its entries lie strictly inside (-limit, limit)
 
 
 class PqaFlowSpec(C.Structure):
@@ -201,6 +204,14 @@ def load():
     lib.pqa_resample_device.argtypes = [vp, C.POINTER(PqaResampleSpec), vp, i64, i64, vp, i64, i64, i32]
     lib.pqa_flow_moments.argtypes = [vp, C.POINTER(PqaFlowSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32, vp]
     lib.pqa_flow_moments_device.argtypes = [vp, C.POINTER(PqaFlowSpec), vp, i64, i64, vp, i64, i64, i32, vp]
+    lib.pqa_colour_sums.argtypes = []
+    lib.pqa_colour_sums.restype = C.c_int
+    lib.pqa_colour_moments_device.argtypes = [vp, C.POINTER(PqaDeviceClip), C.POINTER(PqaDeviceClip), i32, C.c_uint32, C.c_uint32, vp]
+    lib.pqa_colour_moments.argtypes = [vp, C.POINTER(vp), C.POINTER(i64 * 3), C.POINTER(vp), C.POINTER(i64 * 3), i32, C.c_uint32, C.c_uint32, vp]
+    lib.pqa_colour_apply_device.argtypes = [vp, C.POINTER(i32 * 12), C.POINTER(PqaDeviceClip), C.POINTER(PqaDeviceClip), i32]
+    lib.pqa_colour_apply.argtypes = [vp, C.POINTER(i32 * 12), C.POINTER(vp), C.POINTER(i64 * 3), C.POINTER(vp), C.POINTER(i64 * 3), i32]
+    lib.pqa_debug_colour.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp * 3), C.POINTER(vp * 3),
+                                     C.c_uint32, C.c_uint32, vp, C.POINTER(i32 * 12), C.POINTER(vp * 3)]
     lib.pqa_debug_resample_table.argtypes = [C.c_uint32, i32, i32, i64, i64, vp, vp, i32, C.POINTER(i32)]
     lib.pqa_set_luma_gray.argtypes = [vp, C.c_uint32]
     lib.pqa_reset.argtypes = [vp]
@@ -226,5 +237,6 @@ def load():
     assert lib.pqa_ext3_doubles() == EXT3_DOUBLES
     assert lib.pqa_ext4_doubles() == EXT4_DOUBLES
     assert lib.pqa_ext5_doubles() == EXT5_DOUBLES
+    assert lib.pqa_colour_sums() == COLOUR_SUMS
     _lib = lib
     return lib

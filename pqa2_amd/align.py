@@ -1,7 +1,9 @@
 """Temporal, spatial and level alignment on the host.  Spatial (best_shift, below the temporal part): from the shifted-window luma
 SSE (FeatureEngine.shift_sse, pqa_shift_sse) to the whole-pixel displacement of the captured picture.  Levels (best_levels,
 level_lut, at the end of this file): from the per-level transfer table (FeatureEngine.level_stats, pqa_level_stats) to the gain
-and offset of the captured samples, the named range conversion they amount to and the table that undoes it.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
+and offset of the captured samples, the named range conversion they amount to and the table that undoes it.  Colour (best_colour,
+colour_correction, at the very end): from the cross-plane moments (FeatureEngine.colour_moments, pqa_colour_moments) to the 3 x 4 map of
+the captured planes, the named matrix conversion it amounts to and the Q14 matrix that undoes it.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
 constant frame offset and a per-frame map with repeated and dropped frames.
 
     D[i][c] = sum over luma pixels of (ref_i - dis_{i+k})^2,  k = k_lo + c;  UINT64_MAX where i + k is no captured frame
@@ -600,3 +602,189 @@ def register(moments, resample, ref, dis, *, filter: str = "bicubic", tile: int 
             "w_q16": int(win[2]), "h_q16": int(win[3]), "corner_px": float(corner) ** 0.5, "mse_before": float(mse_before),
             "mse_after": float(mse_after), "iterations": int(iterations), "levels": int(plan[0][0]), "tile": int(tile),
             "converged": bool(converged)}
+
+
+# ---- colour-matrix alignment -------------------------------------------------------------------------------------------------
+# A capture chain that decodes Y'CbCr with one matrix and encodes with another couples the planes:
+# (Yd, Ud, Vd) = A (Yr, Ur, Vr) + b.  The measurement is the Gram matrix of z = (1, SYr, Ur, Vr, SYd, Ud, Vd) over the chroma
+# grid (FeatureEngine.colour_moments, pqa_colour_moments; SY: the sum of the s = 2^(hshift + vshift) luma samples under a chroma
+# sample).  Everything below is in PER-SAMPLE units: a luma component is the block mean SY / s, so the factors of s are divided
+# out of the sums here, exactly.
+COLOUR_STANDARDS = {"bt601": (Fraction(299, 1000), Fraction(114, 1000)), "bt709": (Fraction(2126, 10000), Fraction(722, 10000)),
+                    "bt2020": (Fraction(2627, 10000), Fraction(593, 10000))}
+COLOUR_MAPS = ("identity",) + tuple(f"{x}_to_{y}" for x in COLOUR_STANDARDS for y in COLOUR_STANDARDS if x != y)
+COLOUR_Q = 14                                             # pqa_colour_apply's matrix is Q14
+COLOUR_MAX_GAIN, COLOUR_MAX_OFFSET = 1 << 16, 1 << 28     # its entries lie strictly inside (-limit, limit)
+
+
+def _encode_matrix(kr: Fraction, kb: Fraction):
+    """E: R'G'B' -> (Y', Cb, Cr), Y' in 0 ... 1 and Cb, Cr in -1/2 ... 1/2, for the luma weights (Kr, Kb)"""
+    kg = 1 - kr - kb
+    y = [kr, kg, kb]
+    cb = [(int(i == 2) - y[i]) / (2 * (1 - kb)) for i in range(3)]
+    cr = [(int(i == 0) - y[i]) / (2 * (1 - kr)) for i in range(3)]
+    return [y, cb, cr]
+
+
+def _invert3(A):
+    """the inverse of a 3 x 3 matrix of Fractions, or None when it is singular"""
+    cols = [_solve_fractions(A, [int(i == j) for i in range(3)]) for j in range(3)]
+    if any(c is None for c in cols):
+        return None
+    return [[cols[j][i] for j in range(3)] for i in range(3)]
+
+
+def _matmul3(A, B):
+    return [[sum(A[i][k] * B[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
+
+
+def _code_ranges(bit_depth: int, full_range: bool):
+    """(offsets, spans) of (Y, Cb, Cr) in code values"""
+    f = 1 << (int(bit_depth) - 8)
+    if full_range:
+        top = (1 << int(bit_depth)) - 1
+        return [Fraction(0), Fraction(128 * f), Fraction(128 * f)], [Fraction(top)] * 3
+    return [Fraction(16 * f), Fraction(128 * f), Fraction(128 * f)], [Fraction(219 * f), Fraction(224 * f), Fraction(224 * f)]
+
+
+def named_colour_map(name: str, bit_depth: int, full_range: bool = False):
+    """(A, b) of the fixed map dis = A ref + b over (Y, U, V) in code values, as Fractions (A: 3 x 3 nested lists, b: 3):
+    "identity", or "X_to_Y" for X != Y in bt601 / bt709 / bt2020 -- material whose samples mean standard X, decoded as X and
+    encoded again as Y: E_Y E_X^-1 with E built from (Kr, Kb) (COLOUR_STANDARDS).  Limited range: luma spans 219 f from 16 f and
+    chroma 224 f about 128 f, f = 2^(bit_depth - 8); full range: both span 2^bit_depth - 1, luma from 0, chroma about 128 f."""
+    ident = [[Fraction(int(i == j)) for j in range(3)] for i in range(3)]
+    if name == "identity":
+        return ident, [Fraction(0)] * 3
+    if name not in COLOUR_MAPS:
+        raise ValueError(f"unknown colour map {name!r}")
+    x, y = name.split("_to_")
+    M = _matmul3(_encode_matrix(*COLOUR_STANDARDS[y]), _invert3(_encode_matrix(*COLOUR_STANDARDS[x])))
+    off, span = _code_ranges(bit_depth, full_range)
+    A = [[span[i] * M[i][j] / span[j] for j in range(3)] for i in range(3)]
+    b = [off[i] - sum(A[i][j] * off[j] for j in range(3)) for i in range(3)]
+    return A, b
+
+
+def _colour_gram(G, s: int):
+    """the pooled 7 x 7 Gram matrix in per-sample units (Fractions) of G[n_frames][28]"""
+    G = np.asarray(G)
+    if G.ndim != 2 or G.shape[0] < 1 or G.shape[1] != 28:
+        raise ValueError("G must be [n_frames >= 1, 28]")
+    pooled = [sum(int(x) for x in G[:, e]) for e in range(28)]
+    scale = [1, s, 1, 1, s, 1, 1]
+    S = [[Fraction(0)] * 7 for _ in range(7)]
+    e = 0
+    for i in range(7):
+        for j in range(i, 7):
+            S[i][j] = S[j][i] = Fraction(pooled[e], scale[i] * scale[j])
+            e += 1
+    return S
+
+
+def _colour_sse(S, k: int, coef):
+    """sum over the samples of (z_k - coef . (1, Yr, Ur, Vr))^2 from the Gram matrix alone"""
+    return S[k][k] - 2 * sum(coef[i] * S[i][k] for i in range(4)) + sum(coef[i] * coef[j] * S[i][j] for i in range(4) for j in range(4))
+
+
+def best_colour(G, bit_depth: int, hshift: int, vshift: int, *, full_range: bool = False, min_improvement: float = 2.0,
+                snap: float = 1.25, total_samples: int | None = None) -> dict:
+    """The colour map of a captured clip from G[n_frames][28] (pqa_colour_moments: the upper triangle of the sum of z z^T, z =
+    (1, SYr, Ur, Vr, SYd, Ud, Vd), over the unmasked chroma samples).  The frames are pooled; everything below is Python ints
+    and Fractions, converted to float only in the result.  s = 2^(hshift + vshift); every luma quantity is the BLOCK MEAN
+    SY / s, so a luma MSE here is the error of the block mean: the block-sum residual divided by s^2.
+
+    matrix / offset: the least-squares fit of each captured component on (1, Yr, Ur, Vr) from the normal equations.  The MSE of a
+    map is formed per plane from the Gram matrix alone, without clipping (the measurement masks clipped samples instead:
+    pqa_colour_moments' lo / hi) and pooled with the plane sizes as weights, (s Y + U + V) / (s + 2): mse_identity,
+    mse_matrix (the fit), mse_diagonal (each component fitted on 1 and its own plane only: what level alignment could
+    reach), named = {identity, X_to_Y ...: under named_colour_map()}; the per-plane triples are under `planes`.
+    kind = the named map with the smallest pooled MSE (ties: the order of COLOUR_MAPS), or "matrix" when that MSE exceeds
+    snap * mse_matrix.  cross_plane = mse_diagonal > snap * mse_matrix: when false, level alignment is the right tool.
+    mismatch = mse_identity > min_improvement * (pooled MSE of the chosen map).  map_matrix / map_offset: the chosen map's A
+    and b (the named map's own values, or the fit): what colour_correction() undoes.
+    degenerate = the 4 x 4 system is singular (a flat or monochrome-looking clip) or fewer than 4 samples survived the mask:
+    identity, no mismatch.  samples = the samples that entered; samples_masked_share = 1 - samples / total_samples (None
+    when total_samples is not given); frames = n_frames."""
+    s = 1 << (int(hshift) + int(vshift))
+    S = _colour_gram(G, s)
+    n = S[0][0]
+    weights = [Fraction(s, s + 2), Fraction(1, s + 2), Fraction(1, s + 2)]
+
+    def pooled(triple):
+        return sum(w * m for w, m in zip(weights, triple))
+
+    def map_mse(A, b):
+        return [_colour_sse(S, 4 + k, [b[k]] + list(A[k])) / n for k in range(3)]
+    ident = named_colour_map("identity", bit_depth, full_range)
+    fit = None
+    if n >= 4:
+        rows = [_solve_fractions([S[i][:4] for i in range(4)], [S[i][4 + k] for i in range(4)]) for k in range(3)]
+        if all(r is not None for r in rows):
+            fit = ([list(r[1:]) for r in rows], [r[0] for r in rows])
+    masked = None if total_samples is None else (float(1 - n / int(total_samples)) if total_samples else 0.0)
+    base = {"frames": int(np.asarray(G).shape[0]), "samples": int(n), "samples_masked_share": masked}
+    if fit is None:
+        zero = [0.0, 0.0, 0.0]
+        flat = {k: float(x) for k, x in zip(("mse_identity", "mse_matrix", "mse_diagonal"), (0, 0, 0))}
+        return dict(base, kind="identity", mismatch=False, cross_plane=False, degenerate=True, named={}, **flat,
+                    matrix=[[float(v) for v in r] for r in ident[0]], offset=zero, map_matrix=[[float(v) for v in r] for r in ident[0]],
+                    map_offset=zero, planes={"mse_identity": zero, "mse_matrix": zero, "mse_diagonal": zero, "named": {}})
+    A, b = fit
+    diag = []
+    for k in range(3):   # component k on (1, its own plane)
+        i = 1 + k
+        sol = _solve_fractions([[S[0][0], S[0][i]], [S[i][0], S[i][i]]], [S[0][4 + k], S[i][4 + k]])
+        coef = [Fraction(0)] * 4
+        if sol is None:      # its own plane is flat: the mean is all that can be fitted
+            coef[0] = S[0][4 + k] / n
+        else:
+            coef[0], coef[i] = sol
+        diag.append(_colour_sse(S, 4 + k, coef) / n)
+    named_planes = {name: map_mse(*named_colour_map(name, bit_depth, full_range)) for name in COLOUR_MAPS}
+    named = {name: pooled(t) for name, t in named_planes.items()}
+    fit_planes = map_mse(A, b)
+    mse_matrix, mse_diagonal = pooled(fit_planes), pooled(diag)
+    kind = min(COLOUR_MAPS, key=lambda name: named[name])   # min keeps the first of equals
+    chosen = named[kind]
+    if chosen > Fraction(snap) * mse_matrix:
+        kind, chosen = "matrix", mse_matrix
+    mA, mb = (A, b) if kind == "matrix" else named_colour_map(kind, bit_depth, full_range)
+
+    def floats(M):
+        return [[float(v) for v in r] for r in M]
+    return dict(base, kind=kind, mismatch=bool(named["identity"] > Fraction(min_improvement) * chosen),
+                cross_plane=bool(mse_diagonal > Fraction(snap) * mse_matrix), degenerate=False,
+                mse_identity=float(named["identity"]), mse_matrix=float(mse_matrix), mse_diagonal=float(mse_diagonal),
+                named={k: float(v) for k, v in named.items()}, matrix=floats(A), offset=[float(v) for v in b],
+                map_matrix=floats(mA), map_offset=[float(v) for v in mb],
+                planes={"mse_identity": [float(v) for v in named_planes["identity"]], "mse_matrix": [float(v) for v in fit_planes],
+                        "mse_diagonal": [float(v) for v in diag],
+                        "named": {k: [float(v) for v in t] for k, t in named_planes.items()}})
+
+
+def colour_matrix_q14(A, b):
+    """int32[12] of the map (A, b) as pqa_colour_apply takes it -- rows (offset, gains of Y, U, V), each entry times 2^14
+    rounded half up, once -- or None when an entry leaves the ABI's range (|offset| < 2^28, |gain| < 2^16)"""
+    half = Fraction(1, 2)
+    out = []
+    for i in range(3):
+        row = [(Fraction(b[i]) * (1 << COLOUR_Q) + half).__floor__()] + [(Fraction(A[i][j]) * (1 << COLOUR_Q) + half).__floor__() for j in range(3)]
+        if abs(row[0]) >= COLOUR_MAX_OFFSET or any(abs(v) >= COLOUR_MAX_GAIN for v in row[1:]):
+            return None
+        out += row
+    return np.asarray(out, np.int32)
+
+
+def colour_correction(result: dict, bit_depth: int, full_range: bool = False):
+    """The Q14 int32[12] matrix (colour_matrix_q14) of the INVERSE of the map a best_colour() result chose: ref = A^-1 (dis - b).
+    A named kind inverts the named map's own Fractions, "matrix" the fit (its floats at their exact binary values).  The
+    inverse is formed exactly and rounded once.  None when the matrix is singular or the inverse leaves the ABI's range."""
+    if result["kind"] in COLOUR_MAPS:
+        A, b = named_colour_map(result["kind"], bit_depth, full_range)
+    else:
+        A = [[Fraction(v) for v in r] for r in result["map_matrix"]]
+        b = [Fraction(v) for v in result["map_offset"]]
+    inv = _invert3(A)
+    if inv is None:
+        return None
+    return colour_matrix_q14(inv, [-sum(inv[i][j] * b[j] for j in range(3)) for i in range(3)])

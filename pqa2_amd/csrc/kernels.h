@@ -463,5 +463,26 @@ hipError_t launch_flow_moments(hipStream_t stream, Elem elem, int bits, const vo
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int tile, long long* out);
 
+// ---- colour-matrix alignment: cross-plane moments and the matrix apply (colour_moments.hip) ---------------------------------
+// Both work on the chroma grid ceil(w / 2^hshift) x ceil(h / 2^vshift) of w x h frames (shifts 0 or 1; u8 / u16 samples of
+// `bit_depth` bits, a sample above 2^bit_depth - 1 is read as that); plane p of frame f at base + f * frame_pitch, pitches in
+// elements.  Definitions, bounds and the widening interval: the head of colour_moments.hip.
+// out[f][28]: the upper triangle, row-major, of the sum over the unmasked chroma samples of z z^T, z = (1, SYr, Ur, Vr, SYd,
+// Ud, Vd), exact uint64; device memory of n_frames * 28 words, zeroed by the launch.
+constexpr int kColourSums = 28;
+constexpr int kColourChunk = 8;                  // frames / frame pairs per launch of the entries
+constexpr int64_t kColourMaxGain = 1 << 16;      // |m[r][1..3]| below it (Q14: gains below 4)
+constexpr int64_t kColourMaxOffset = 1 << 28;    // |m[r][0]| below it (Q14 code values)
+bool colour_shift_ok(int hshift, int vshift);
+bool colour_matrix_ok(const int32_t m[12]);
+int colour_flush_steps(int bit_depth, int hshift, int vshift);   // row steps between two widenings of a lane's int32 partials
+hipError_t launch_colour_moments(hipStream_t stream, Elem elem, int bit_depth, int hshift, int vshift, const PlaneRun ref[3],
+                                 const PlaneRun dis[3], int n_frames, int w, int h, unsigned lo, unsigned hi,
+                                 unsigned long long* out);
+// dst = the frame through m[3][4] (Q14, column 0 the offset); reads no sample outside a source plane, writes none outside the
+// plane sizes of dst.
+hipError_t launch_colour_apply(hipStream_t stream, Elem elem, int bit_depth, int hshift, int vshift, const int32_t m[12],
+                               const PlaneRun src[3], const MutPlaneRun dst[3], int n_frames, int w, int h);
+
 }  // namespace pqa
 

@@ -291,4 +291,37 @@ int pqa_debug_resample_table(uint32_t filter, int32_t n_src, int32_t n_dst, int6
   return PQA_OK;
 }
 
+int pqa_debug_colour(uint32_t bit_depth, uint32_t hshift, uint32_t vshift, uint32_t w, uint32_t h, const void* const ref[3],
+                     const void* const dis[3], uint32_t lo, uint32_t hi, uint64_t* sums28, const int32_t* m, void* const applied[3]) {
+  if (!ref || !dis || w < 1 || h < 1 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) ||
+      !colour_shift_ok((int)hshift, (int)vshift) || lo > hi || hi > (1u << bit_depth) - 1u || (m && (!applied || !colour_matrix_ok(m))))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_colour: bad argument");
+  for (int p = 0; p < 3; ++p)
+    if (!ref[p] || !dis[p] || (m && !applied[p])) return fail(nullptr, PQA_EINVAL, "pqa_debug_colour: plane %d pointer is null", p);
+  const int rc = need_device();
+  if (rc != PQA_OK) return rc;
+  const int es = bit_depth > 8 ? 2 : 1;
+  const uint32_t pw[3] = {w, (w + (1u << hshift) - 1) >> hshift, (w + (1u << hshift) - 1) >> hshift};
+  const uint32_t ph[3] = {h, (h + (1u << vshift) - 1) >> vshift, (h + (1u << vshift) - 1) >> vshift};
+  Scratch s;
+  PlaneRun r[3], d[3];
+  MutPlaneRun o[3];
+  for (int p = 0; p < 3; ++p) {
+    const size_t row = (size_t)pw[p] * es;
+    r[p] = PlaneRun{s.plane(ref[p], (int64_t)row, row, ph[p]), (int64_t)pw[p], 0};
+    d[p] = PlaneRun{s.plane(dis[p], (int64_t)row, row, ph[p]), (int64_t)pw[p], 0};
+    o[p] = MutPlaneRun{m ? s.get<uint8_t>(row * ph[p]) : nullptr, (int64_t)pw[p], 0};
+  }
+  unsigned long long* sums = s.get<unsigned long long>(kColourSums);
+  hipError_t e = s.err;
+  const Elem elem = es == 1 ? ELEM_U8 : ELEM_U16;
+  if (e == hipSuccess && sums28)
+    e = launch_colour_moments(nullptr, elem, (int)bit_depth, (int)hshift, (int)vshift, r, d, 1, (int)w, (int)h, lo, hi, sums);
+  if (e == hipSuccess && sums28) e = hipMemcpy(sums28, sums, kColourSums * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && m) e = launch_colour_apply(nullptr, elem, (int)bit_depth, (int)hshift, (int)vshift, m, d, o, 1, (int)w, (int)h);
+  for (int p = 0; p < 3 && e == hipSuccess && m; ++p) e = hipMemcpy(applied[p], o[p].base, (size_t)pw[p] * es * ph[p], hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_colour: %s", hipGetErrorString(e));
+  return PQA_OK;
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the registration moments.  Each has an entry for a clip in HBM and one for frames in host memory; the host
+// temporal / spatial / level alignment, the resampler, the registration moments, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
 // entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
@@ -255,6 +255,57 @@ int fl_check(pqa_ctx* c, const pqa_flow_spec* sp, const void* ref, const void* d
   if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "flow_moments: null clip pointer");
   if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "flow_moments: null output pointer");
   return PQA_OK;
+}
+
+// ---- colour-matrix alignment (colour_moments.hip): argument rules (no device call), the layout of a staged frame --------------
+int cl_check(pqa_ctx* c, const char* who, int32_t n_frames) {
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "%s: negative frame count", who);
+  if (c->n_planes != 3) return fail(c, PQA_EINVAL, "%s needs the chroma planes: n_planes must be 3 (got %d)", who, c->n_planes);
+  if (!colour_shift_ok((int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift))
+    return fail(c, PQA_EINVAL, "%s: chroma shifts %u, %u (0 or 1 each)", who, c->cfg.chroma_hshift, c->cfg.chroma_vshift);
+  return PQA_OK;
+}
+
+int cl_check_clip(pqa_ctx* c, const char* who, const pqa_device_clip* d) {
+  for (int p = 0; p < 3; ++p) {
+    if (!d->plane[p]) return fail(c, PQA_EINVAL, "%splane %d pointer is null", who, p);
+    const int rc = check_device_clip(c, who, d->row_pitch[p], d->frame_pitch[p], (int64_t)c->pw[p] * c->esize);
+    if (rc != PQA_OK) return rc;
+  }
+  return PQA_OK;
+}
+
+int cl_check_host(pqa_ctx* c, const char* who, const char* kind, const void* const* frames, const int64_t strides[3], int n) {
+  for (int p = 0; p < 3; ++p) {
+    const int rc = check_host_frames(c, who, kind, frames + p, 3, n, strides[p], (size_t)c->pw[p] * c->esize, true);
+    if (rc != PQA_OK) return rc;
+  }
+  return PQA_OK;
+}
+
+// A frame as the host entries stage it: plane p at off[p] with rows pitch[p] bytes apart, `bytes` in all; every offset and
+// pitch is a multiple of 16 bytes, so the kernels take their wide loads.
+struct ClLayout {
+  size_t off[3], bytes;
+  int64_t pitch[3];
+};
+ClLayout cl_layout(const pqa_ctx* c) {
+  ClLayout L{};
+  for (int p = 0; p < 3; ++p) {
+    L.off[p] = L.bytes;
+    L.pitch[p] = round_up((int64_t)c->pw[p] * c->esize, 16);
+    L.bytes += (size_t)round_up(L.pitch[p] * c->ph[p], 256);
+  }
+  return L;
+}
+void cl_runs(const pqa_ctx* c, const ClLayout& L, const void* base, PlaneRun run[3]) {
+  for (int p = 0; p < 3; ++p) run[p] = PlaneRun{(const uint8_t*)base + L.off[p], L.pitch[p] / c->esize, (int64_t)(L.bytes / c->esize)};
+}
+void cl_pack(const pqa_ctx* c, const ClLayout& L, uint8_t* pin, const void* const* frames, const int64_t strides[3], int n) {
+  for (int f = 0; f < n; ++f)
+    for (int p = 0; p < 3; ++p)
+      copy_plane_rows(pin + (size_t)f * L.bytes + L.off[p], L.pitch[p], (const uint8_t*)frames[(size_t)f * 3 + p], strides[p],
+                      (size_t)c->pw[p] * c->esize, c->ph[p]);
 }
 
 }  // namespace
@@ -785,6 +836,163 @@ int pqa_flow_moments(pqa_ctx* c, const pqa_flow_spec* spec, const void* const* r
                               c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, tile, dev_out + (size_t)f0 * per_frame);
   }
   return side_finish(c, "flow_moments", e, out, dev_out, flow_out_bytes(w, h, tile, n_frames));
+}
+
+// ---- colour-matrix alignment (colour_moments.hip) ------------------------------------------------------------------------
+
+int pqa_colour_sums(void) { return kColourSums; }
+
+int pqa_colour_moments_device(pqa_ctx* c, const pqa_device_clip* ref, const pqa_device_clip* dis, int32_t n_frames, uint32_t lo,
+                              uint32_t hi, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  int rc = cl_check(c, "colour_moments", n_frames);
+  if (rc != PQA_OK) return rc;
+  const uint32_t top = (1u << c->cfg.bit_depth) - 1u;
+  if (lo > hi || hi > top) return fail(c, PQA_EINVAL, "colour_moments: mask %u ... %u outside 0 ... %u", lo, hi, top);
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "colour_moments: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "colour_moments: null output pointer");
+  if (n_frames == 0) return PQA_OK;
+  rc = cl_check_clip(c, "colour_moments: reference ", ref);
+  if (rc == PQA_OK) rc = cl_check_clip(c, "colour_moments: captured ", dis);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)n_frames * kColourSums * sizeof(uint64_t);
+  rc = side_reserve(c, SIDE_COLOUR_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_COLOUR_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kColourChunk) {
+    PlaneRun r[3], d[3];
+    for (int p = 0; p < 3; ++p) {
+      r[p] = PlaneRun{(const uint8_t*)ref->plane[p] + (int64_t)f0 * ref->frame_pitch[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
+      d[p] = PlaneRun{(const uint8_t*)dis->plane[p] + (int64_t)f0 * dis->frame_pitch[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
+    }
+    e = launch_colour_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, r, d,
+                              chunk_len(n_frames, f0, kColourChunk), c->pw[0], c->ph[0], lo, hi, dev_out + (size_t)f0 * kColourSums);
+  }
+  return side_finish(c, "colour_moments", e, out, dev_out, bytes);
+}
+
+int pqa_colour_moments(pqa_ctx* c, const void* const* ref_frames, const int64_t ref_strides[3], const void* const* dis_frames,
+                       const int64_t dis_strides[3], int32_t n_frames, uint32_t lo, uint32_t hi, uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  int rc = cl_check(c, "colour_moments", n_frames);
+  if (rc != PQA_OK) return rc;
+  const uint32_t top = (1u << c->cfg.bit_depth) - 1u;
+  if (lo > hi || hi > top) return fail(c, PQA_EINVAL, "colour_moments: mask %u ... %u outside 0 ... %u", lo, hi, top);
+  if (n_frames > 0 && (!ref_frames || !dis_frames || !ref_strides || !dis_strides)) return fail(c, PQA_EINVAL, "colour_moments: null frame list");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "colour_moments: null output pointer");
+  if (n_frames == 0) return PQA_OK;
+  rc = cl_check_host(c, "colour_moments: ", "reference ", ref_frames, ref_strides, n_frames);
+  if (rc == PQA_OK) rc = cl_check_host(c, "colour_moments: ", "captured ", dis_frames, dis_strides, n_frames);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  // Three planes a frame, so the frames travel as pqa_flow_moments' planes do: chunks of kColourChunk pairs through the two
+  // grow-only pinned buffers of pqa_resample (reference frames through the first, captured ones through the second) into
+  // device buffers of this entry; every chunk's kernel writes its sums behind the previous chunk's, they come back once.
+  const ClLayout L = cl_layout(c);
+  const int chunk = n_frames < kColourChunk ? n_frames : kColourChunk;
+  const size_t bytes = (size_t)n_frames * kColourSums * sizeof(uint64_t);
+  rc = rs_pin_reserve(c, 0, L.bytes * chunk);
+  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_A, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_B, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_COLOUR_OUT];
+  PlaneRun r[3], d[3];
+  cl_runs(c, L, c->side_buf[SIDE_COLOUR_A], r);
+  cl_runs(c, L, c->side_buf[SIDE_COLOUR_B], d);
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kColourChunk) {
+    const int n = chunk_len(n_frames, f0, kColourChunk);
+    if (f0 > 0) e = hipStreamSynchronize(c->stream);   // the pinned buffers are packed again only after the chunk before has left them
+    if (e != hipSuccess) break;
+    cl_pack(c, L, c->rs_pin[0], ref_frames + (size_t)f0 * 3, ref_strides, n);
+    cl_pack(c, L, c->rs_pin[1], dis_frames + (size_t)f0 * 3, dis_strides, n);
+    e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->rs_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_B], c->rs_pin[1], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_colour_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, r, d, n,
+                                c->pw[0], c->ph[0], lo, hi, dev_out + (size_t)f0 * kColourSums);
+  }
+  return side_finish(c, "colour_moments", e, out, dev_out, bytes);
+}
+
+int pqa_colour_apply_device(pqa_ctx* c, const int32_t m[12], const pqa_device_clip* src, const pqa_device_clip* dst, int32_t n_frames) {
+  if (!c) return PQA_EINVAL;
+  int rc = cl_check(c, "colour_apply", n_frames);
+  if (rc != PQA_OK) return rc;
+  if (!m) return fail(c, PQA_EINVAL, "colour_apply: null matrix");
+  if (!colour_matrix_ok(m)) return fail(c, PQA_EINVAL, "colour_apply: a matrix entry is out of range (|offset| < 2^28, |gain| < 2^16 in Q14)");
+  if (n_frames > 0 && (!src || !dst)) return fail(c, PQA_EINVAL, "colour_apply: null clip pointer");
+  if (n_frames == 0) return PQA_OK;
+  rc = cl_check_clip(c, "colour_apply: source ", src);
+  if (rc == PQA_OK) rc = cl_check_clip(c, "colour_apply: destination ", dst);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int es = c->esize;
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kColourChunk) {
+    PlaneRun s[3];
+    MutPlaneRun d[3];
+    for (int p = 0; p < 3; ++p) {
+      s[p] = PlaneRun{(const uint8_t*)src->plane[p] + (int64_t)f0 * src->frame_pitch[p], src->row_pitch[p] / es, src->frame_pitch[p] / es};
+      d[p] = MutPlaneRun{(uint8_t*)const_cast<void*>(dst->plane[p]) + (int64_t)f0 * dst->frame_pitch[p], dst->row_pitch[p] / es, dst->frame_pitch[p] / es};
+    }
+    e = launch_colour_apply(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, m, s, d,
+                            chunk_len(n_frames, f0, kColourChunk), c->pw[0], c->ph[0]);
+  }
+  return side_finish(c, "colour_apply", e, nullptr, nullptr, 0);
+}
+
+int pqa_colour_apply(pqa_ctx* c, const int32_t m[12], const void* const* src_frames, const int64_t src_strides[3],
+                     void* const* dst_frames, const int64_t dst_strides[3], int32_t n_frames) {
+  if (!c) return PQA_EINVAL;
+  int rc = cl_check(c, "colour_apply", n_frames);
+  if (rc != PQA_OK) return rc;
+  if (!m) return fail(c, PQA_EINVAL, "colour_apply: null matrix");
+  if (!colour_matrix_ok(m)) return fail(c, PQA_EINVAL, "colour_apply: a matrix entry is out of range (|offset| < 2^28, |gain| < 2^16 in Q14)");
+  if (n_frames > 0 && (!src_frames || !dst_frames || !src_strides || !dst_strides)) return fail(c, PQA_EINVAL, "colour_apply: null frame list");
+  if (n_frames == 0) return PQA_OK;
+  rc = cl_check_host(c, "colour_apply: ", "source ", src_frames, src_strides, n_frames);
+  if (rc == PQA_OK) rc = cl_check_host(c, "colour_apply: ", "destination ", (const void* const*)dst_frames, dst_strides, n_frames);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as pqa_resample: a chunk is uploaded, mapped, downloaded and copied out before the next one starts
+  const ClLayout L = cl_layout(c);
+  const int chunk = n_frames < kColourChunk ? n_frames : kColourChunk;
+  rc = rs_pin_reserve(c, 0, L.bytes * chunk);
+  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_A, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_B, L.bytes * chunk);
+  if (rc != PQA_OK) return rc;
+  PlaneRun s[3], dr[3];
+  MutPlaneRun d[3];
+  cl_runs(c, L, c->side_buf[SIDE_COLOUR_A], s);
+  cl_runs(c, L, c->side_buf[SIDE_COLOUR_B], dr);
+  for (int p = 0; p < 3; ++p) d[p] = MutPlaneRun{const_cast<void*>(dr[p].base), dr[p].row_pitch, dr[p].frame_pitch};
+  for (int f0 = 0; f0 < n_frames; f0 += kColourChunk) {
+    const int n = chunk_len(n_frames, f0, kColourChunk);
+    cl_pack(c, L, c->rs_pin[0], src_frames + (size_t)f0 * 3, src_strides, n);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->rs_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_colour_apply(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, m, s, d, n,
+                              c->pw[0], c->ph[0]);
+    rc = side_finish(c, "colour_apply", e, c->rs_pin[1], c->side_buf[SIDE_COLOUR_B], L.bytes * n);
+    if (rc != PQA_OK) return rc;
+    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
+      for (int p = 0; p < 3; ++p)
+        for (int y = 0; y < c->ph[p]; ++y)
+          memcpy((uint8_t*)dst_frames[(size_t)(f0 + f) * 3 + p] + (int64_t)y * dst_strides[p],
+                 c->rs_pin[1] + (size_t)f * L.bytes + L.off[p] + (size_t)y * L.pitch[p], (size_t)c->pw[p] * c->esize);
+  }
+  return PQA_OK;
 }
 
 }  // extern "C"

@@ -486,6 +486,87 @@ class FeatureEngine:
                                                      dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
         return out
 
+    # -- colour-matrix alignment ---------------------------------------------------------------
+    def _frame_list(self, frames, what: str):
+        """(arrays kept alive, ctypes pointer array [n * 3], stride triple) of frames [Y, U, V] in host memory: packed copies
+        unless every plane already has this engine's dtype, unit column stride and one row stride per plane kind"""
+        shapes = [self.plane_shape(p) for p in range(3)]
+        arrs = [[np.asarray(f[p]) for p in range(3)] for f in frames]
+        for i, f in enumerate(arrs):
+            for p in range(3):
+                if f[p].shape != shapes[p]:
+                    raise ValueError(f"{what} frame {i} plane {p} is {f[p].shape}, engine is {shapes[p]}")
+        plain = all(a.dtype == self.dtype and a.strides[1] == a.itemsize and a.strides[0] == arrs[0][p].strides[0] and a.strides[0] > 0
+                    for f in arrs for p, a in enumerate(f))
+        if not plain:
+            arrs = [[np.ascontiguousarray(a, dtype=self.dtype) for a in f] for f in arrs]
+        ptrs = (C.c_void_p * max(3 * len(arrs), 1))()
+        for i, f in enumerate(arrs):
+            for p in range(3):
+                ptrs[3 * i + p] = f[p].ctypes.data
+        itemsize = np.dtype(self.dtype).itemsize
+        strides = (C.c_int64 * 3)(*[arrs[0][p].strides[0] if arrs else shapes[p][1] * itemsize for p in range(3)])
+        return arrs, ptrs, strides
+
+    def _colour_mask(self, lo, hi):
+        top = (1 << self.bit_depth) - 1
+        return (1 if lo is None else int(lo)), (top - 1 if hi is None else int(hi))
+
+    def _device_clip(self, ptrs, row_pitch, frame_pitch):
+        d = N.PqaDeviceClip()
+        for p in range(3):
+            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptrs[p], row_pitch[p], frame_pitch[p]
+        return d
+
+    def colour_moments(self, ref_frames, dis_frames, lo=None, hi=None) -> np.ndarray:
+        """[n, 28] uint64: per frame pair the upper triangle, row-major, of the sum of z z^T over the chroma grid, z = (1, SYr, Ur,
+        Vr, SYd, Ud, Vd), SY = the sum of the luma samples under a chroma sample, exact (pqa_colour_moments; definition:
+        include/pqa_vmaf.h).  A chroma sample enters only if every captured sample it reads lies in lo ... hi (default 1 ...
+        top - 1: clipped samples stay out; 0 and top keep everything).  Frames [Y, U, V] in HOST memory (two lists of equal
+        length); needs n_planes == 3.  align.best_colour reads the result."""
+        n = len(ref_frames)
+        if len(dis_frames) != n:
+            raise ValueError("colour_moments needs as many captured as reference frames")
+        if self.n_planes != 3:
+            raise N.PqaError(N.PQA_EINVAL, "colour_moments needs the chroma planes: n_planes must be 3")
+        lo, hi = self._colour_mask(lo, hi)
+        out = np.zeros((n, N.COLOUR_SUMS), np.uint64)
+        keep_r, rp, rs = self._frame_list(ref_frames, "reference")
+        keep_d, dp, ds = self._frame_list(dis_frames, "captured")
+        self._check(self.lib.pqa_colour_moments(self._ctx, rp, C.byref(rs), dp, C.byref(ds), n, lo, hi, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def colour_moments_resident(self, ref_ptrs, dis_ptrs, row_pitch, frame_pitch, n_frames: int, lo=None, hi=None) -> np.ndarray:
+        """The same for two clips in HBM (ref_ptrs / dis_ptrs: device addresses of frame 0's planes; pitches in bytes per
+        plane, common to both clips; pqa_colour_moments_device)."""
+        lo, hi = self._colour_mask(lo, hi)
+        out = np.zeros((max(int(n_frames), 0), N.COLOUR_SUMS), np.uint64)
+        r, d = self._device_clip(ref_ptrs, row_pitch, frame_pitch), self._device_clip(dis_ptrs, row_pitch, frame_pitch)
+        self._check(self.lib.pqa_colour_moments_device(self._ctx, C.byref(r), C.byref(d), int(n_frames), lo, hi, out.ctypes.data))
+        return out
+
+    def colour_apply(self, frames, m):
+        """A list of frames [Y, U, V]: every frame of `frames` through the 3 x 4 integer matrix m (12 values, Q14; column 0 the
+        offset: align.colour_correction / align.colour_matrix_q14), planes of the same sizes (pqa_colour_apply; definition:
+        include/pqa_vmaf.h).  Frames in HOST memory; needs n_planes == 3."""
+        if self.n_planes != 3:
+            raise N.PqaError(N.PQA_EINVAL, "colour_apply needs the chroma planes: n_planes must be 3")
+        mm = (C.c_int32 * 12)(*[int(v) for v in np.asarray(m).reshape(12)])
+        keep, sp, ss = self._frame_list(frames, "source")
+        out = [[np.empty(self.plane_shape(p), self.dtype) for p in range(3)] for _ in keep]
+        _, dp, ds = self._frame_list(out, "destination")
+        self._check(self.lib.pqa_colour_apply(self._ctx, C.byref(mm), sp, C.byref(ss), dp, C.byref(ds), len(keep)))
+        del keep
+        return out
+
+    def colour_apply_resident(self, m, src_ptrs, dst_ptrs, row_pitch, frame_pitch, n_frames: int):
+        """The same for a clip in HBM into planes in HBM (device addresses of frame 0's planes; pitches in bytes per plane,
+        common to both; pqa_colour_apply_device).  Nothing crosses PCIe; the result can go into submit_resident."""
+        mm = (C.c_int32 * 12)(*[int(v) for v in np.asarray(m).reshape(12)])
+        s, d = self._device_clip(src_ptrs, row_pitch, frame_pitch), self._device_clip(dst_ptrs, row_pitch, frame_pitch)
+        self._check(self.lib.pqa_colour_apply_device(self._ctx, C.byref(mm), C.byref(s), C.byref(d), int(n_frames)))
+
     # -- results -----------------------------------------------------------------------------
     def collect(self, first_index: int, count: int) -> np.ndarray:
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)

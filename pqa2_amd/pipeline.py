@@ -35,7 +35,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 align_frames: int | None = None, align_penalty_mse: float | None = None, spatial_align: int = 0,
                 spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8,
                 resize: str | None = None, register: str | None = None, register_frames: int = 8,
-                register_min_px: float = 1.0 / 16) -> ScoreResult | None:
+                register_min_px: float = 1.0 / 16, colour_align: str | None = None, colour_frames: int = 8,
+                colour_full_range: bool | None = None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -95,7 +96,19 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     the captured frame, the margins `crop` = [left, top, right, bottom] rounded up to the chroma step.  Not applied: the
     records are those of a run without the option.  After `resize` this is a second filter pass over the captured samples,
     in series with the first: the two are not folded into one.  Rotation is not modelled.  `register` = None: no
-    measurement."""
+    measurement.
+    `colour_align` = "report" or "apply": before scoring (after the level step, on the readers and the window it produced), the
+    cross-plane moments of `colour_frames` pairs spread evenly over the common range (pqa_colour_moments, clipped samples
+    masked) are reduced to the 3 x 4 map of the captured (Y, U, V) on the reference's and the named matrix conversion it
+    amounts to -- bt601 / bt709 / bt2020 material decoded with one matrix and encoded with another (align.best_colour).
+    `colour_full_range`: the range the named maps are formed for; None follows the captured clip's Y4M header (XCOLORRANGE=FULL:
+    full range, any other: limited).  `alignment["colour"]` holds {kind, mismatch, cross_plane, degenerate, mse_identity,
+    mse_matrix, mse_diagonal, named, matrix, offset, map_matrix, map_offset, planes, samples, samples_masked_share, frames,
+    full_range, correction, applied}.  "report" changes nothing else: the records are those of a run without the option.
+    "apply", when `mismatch` and `cross_plane` hold and the inverse of the chosen map fits the Q14 matrix of pqa_colour_apply
+    (`correction`: its 12 integers, else null), maps every captured frame through that inverse on the GPU before it is scored;
+    `applied` says so.  Without `cross_plane` the planes are not coupled and `level_align` is the tool.  A monochrome clip is
+    an error.  `colour_align` = None: no measurement."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -164,6 +177,20 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         alignment = dict(alignment or {}, levels=levels)
         if any(lut is not None for lut in luts):
             dis_rd = _LevelledReader(dis_rd, luts)
+    coloured = None
+    if colour_align is not None:
+        if colour_align not in ("report", "apply"):
+            raise ValueError('colour_align must be None, "report" or "apply"')
+        if colour_frames is None or colour_frames < 1:
+            raise ValueError("colour_frames must be positive")
+        if ri.mono:
+            raise ValueError("colour alignment needs the chroma planes, but the clips are monochrome")
+        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
+        full = (di.color_range == "full") if colour_full_range is None else bool(colour_full_range)
+        colour = _find_colour(ref_rd, dis_rd, int(colour_frames), colour_align == "apply", full, device, make_side)
+        alignment = dict(alignment or {}, colour=colour)
+        if colour["applied"]:
+            dis_rd = coloured = _ColourReader(dis_rd, colour["correction"], device, make_side)
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
@@ -272,7 +299,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
     ext5 = shard.gather_records(local_ext5, n, world_size, rank, gather_device, width=N.EXT5_DOUBLES) if integrity else None
     if rank != 0:
-        for rd in (resampler, registered):
+        for rd in (resampler, registered, coloured):
             if rd is not None:
                 rd.close()
         return None
@@ -325,7 +352,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["alignment"] = alignment
     if resized is not None:
         res["resize"] = resized
-    for rd in (resampler, registered):   # on an error their contexts go with the readers
+    for rd in (resampler, registered, coloured):   # on an error their contexts go with the readers
         if rd is not None:
             rd.close()
     return res
@@ -554,6 +581,57 @@ def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make):
         luts.append(AL.correction_lut(lv, ri.bit_depth, chroma=p > 0) if lv["applied"] else None)
         planes["yuv"[p]] = lv
     return dict(planes["y"], planes=planes), luts
+
+
+class _ColourReader:
+    """A captured clip with every frame mapped through a 3 x 4 integer matrix (FeatureEngine.colour_apply): the counterpart of
+    _LevelledReader for a map that couples the planes, and what score_files reads under colour_align="apply".  Built like
+    _RegisteredReader -- a small context of its own, frames fetched in runs of eight, the last run kept.  No file-descriptor
+    path: the mapped samples exist in host arrays only.  close() frees the context."""
+    RUN = 8
+
+    def __init__(self, reader, matrix, device, make):
+        info = self.info = reader.info
+        self._rd, self._m = reader, [int(v) for v in matrix]
+        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=3, chroma_shift=(info.hshift, info.vshift),
+                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd)
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            frames = [self._rd.frame(j)[:3] for j in range(first, min(first + self.RUN, len(self._rd)))]
+            self._first, self._run = first, self._eng.colour_apply(frames, self._m)
+        return self._run[i - self._first]
+
+
+def _find_colour(ref_rd, dis_rd, n_frames: int, apply: bool, full_range: bool, device, make) -> dict:
+    """the `colour` object of two opened, paired colour clips: the cross-plane moments of a few pairs on a small context of its
+    own, reduced by align.best_colour"""
+    from . import align as AL
+    ri = ref_rd.info
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError("no frames to align")
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=3, chroma_shift=(ri.hshift, ri.vshift),
+               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+    try:
+        G = eng.colour_moments([ref_rd.frame(i)[:3] for i in idx], [dis_rd.frame(i)[:3] for i in idx])
+    finally:
+        eng.close()
+    col = AL.best_colour(G, ri.bit_depth, ri.hshift, ri.vshift, full_range=full_range,
+                         total_samples=len(idx) * ri.chroma_w * ri.chroma_h)
+    col["full_range"] = bool(full_range)
+    fix = AL.colour_correction(col, ri.bit_depth, full_range) if (col["mismatch"] and col["cross_plane"]) else None
+    col["correction"] = None if fix is None else [int(v) for v in fix]
+    col["applied"] = bool(apply and fix is not None)
+    return col
 
 
 def spatial_sample(n: int, count: int):

@@ -104,6 +104,14 @@ def alignment_log_keys(alignment: dict | None) -> dict:
             return {k: finite_all(v) if isinstance(v, dict) else (None if isinstance(v, float) and not np.isfinite(v) else v)
                     for k, v in obj.items()}
         out["levels"] = finite_all(alignment["levels"])
+    if alignment.get("colour"):   # lists of floats in there too; any float that is not finite becomes null
+        def finite_deep(v):
+            if isinstance(v, dict):
+                return {k: finite_deep(x) for k, x in v.items()}
+            if isinstance(v, (list, tuple)):
+                return [finite_deep(x) for x in v]
+            return None if isinstance(v, float) and not np.isfinite(v) else v
+        out["colour"] = finite_deep(alignment["colour"])
     return {"alignment": out}
 
 
@@ -147,6 +155,30 @@ def geometry_summary_line(geometry: dict) -> str:
             f"({geometry.get('sx', 1.0):.5f}, {geometry.get('sy', 1.0):.5f}), {geometry.get('corner_px', 0.0):.3f} px at the "
             f"corners, MSE {geometry.get('mse_before', 0.0):.2f} -> {geometry.get('mse_after', 0.0):.2f}, "
             f"{geometry.get('iterations', 0)} iterations on {geometry.get('frames', 0)} frames, {what}")
+
+
+def colour_summary_line(colour: dict) -> str:
+    """One line for a summary or a status bar: the colour map found, its error and whether it was undone."""
+    if colour.get("degenerate"):
+        return f"Colour alignment: flat or monochrome-looking content in {colour.get('frames', 0)} frames: no map measured"
+    kind = colour.get("kind", "identity")
+    if kind == "identity":
+        what = "colour matrix in place"
+    elif kind == "matrix":
+        what = "capture went through a colour matrix that is no named conversion"
+    else:
+        what = "capture decoded as {} and encoded as {}".format(*kind.split("_to_"))
+    if colour.get("applied"):
+        tail = "corrected"
+    elif not colour.get("mismatch"):
+        tail = "nothing to correct"
+    elif not colour.get("cross_plane"):
+        tail = "planes not coupled: a matter for level alignment, not corrected"
+    else:
+        tail = "not corrected"
+    return (f"Colour alignment: {what}, MSE {colour.get('mse_identity', 0.0):.2f} as captured, {colour.get('mse_matrix', 0.0):.2f} "
+            f"after the fit, {colour.get('mse_diagonal', 0.0):.2f} per plane alone, {colour.get('samples', 0)} samples of "
+            f"{colour.get('frames', 0)} frames ({100.0 * (colour.get('samples_masked_share') or 0.0):.1f} % masked), {tail}")
 
 
 def levels_summary_line(levels: dict) -> str:

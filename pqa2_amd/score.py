@@ -102,6 +102,14 @@ def main(argv=None) -> int:
                     help="--level-align, and undo a mapping found on every plane that has one before scoring")
     ap.add_argument("--level-frames", type=int, default=8, metavar="N",
                     help="with --level-align / --level-correct: measure N frame pairs spread evenly over the clips (default 8)")
+    ap.add_argument("--colour-align", action="store_true",
+                    help="measure the colour matrix of the capture (bt601 / bt709 / bt2020 material decoded with one matrix and "
+                         "encoded with another) from the cross-plane moments of a few frame pairs; the JSON's alignment object "
+                         "gets a colour entry")
+    ap.add_argument("--colour-correct", action="store_true",
+                    help="--colour-align, and undo a matrix found on the GPU before scoring")
+    ap.add_argument("--colour-frames", type=int, default=8, metavar="N",
+                    help="with --colour-align / --colour-correct: measure N frame pairs spread evenly over the clips (default 8)")
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
@@ -158,6 +166,8 @@ def main(argv=None) -> int:
                           **({"spatial_align": a.spatial_align, "spatial_frames": a.spatial_frames} if a.spatial_align else {}),
                           **({"level_align": "apply" if a.level_correct else "report", "level_frames": a.level_frames}
                              if (a.level_align or a.level_correct) else {}),
+                          **({"colour_align": "apply" if a.colour_correct else "report", "colour_frames": a.colour_frames}
+                             if (a.colour_align or a.colour_correct) else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
@@ -194,6 +204,8 @@ def main(argv=None) -> int:
             print(report.spatial_summary_line(res["alignment"]["spatial"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("levels"):
             print(report.levels_summary_line(res["alignment"]["levels"]), file=sys.stderr, flush=True)
+        if res.get("alignment") and res["alignment"].get("colour"):
+            print(report.colour_summary_line(res["alignment"]["colour"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("geometry"):
             print(report.geometry_summary_line(res["alignment"]["geometry"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)

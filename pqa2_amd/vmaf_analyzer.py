@@ -165,6 +165,8 @@ class VMAFAnalyzer(QObject):
         self.spatial_align_radius = 8         # -radius ... radius pixels in x and y (pipeline.score_files(spatial_align=))
         self.level_align_enabled = False      # level alignment before scoring: measure the capture's gain / offset / range
         self.level_correct_enabled = False    # ... and undo it (implies the measurement; pipeline.score_files(level_align=))
+        self.colour_align_enabled = False     # colour-matrix alignment before scoring: measure the capture's 3 x 4 colour map
+        self.colour_correct_enabled = False   # ... and undo it (implies the measurement; pipeline.score_files(colour_align=))
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -217,6 +219,10 @@ class VMAFAnalyzer(QObject):
                 self.level_align_enabled = bool(s["level_align_enabled"])
             if "level_correct_enabled" in s:
                 self.level_correct_enabled = bool(s["level_correct_enabled"])
+            if "colour_align_enabled" in s:
+                self.colour_align_enabled = bool(s["colour_align_enabled"])
+            if "colour_correct_enabled" in s:
+                self.colour_correct_enabled = bool(s["colour_correct_enabled"])
 
     set_options_manager = set_options_from_manager
 
@@ -234,7 +240,8 @@ class VMAFAnalyzer(QObject):
                              cambi_full_ref_enabled=False, psnr_hvs_enabled=False, xpsnr_enabled=False,
                              siti_enabled=False, integrity_enabled=False, integrity_options=None,
                              align_enabled=False, align_max_offset=8, spatial_align_enabled=False,
-                             spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False):
+                             spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False,
+                             colour_align_enabled=False, colour_correct_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -257,6 +264,8 @@ class VMAFAnalyzer(QObject):
         self.spatial_align_radius = max(1, min(16, int(spatial_align_radius)))
         self.level_align_enabled = bool(level_align_enabled)
         self.level_correct_enabled = bool(level_correct_enabled)
+        self.colour_align_enabled = bool(colour_align_enabled)
+        self.colour_correct_enabled = bool(colour_correct_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -467,6 +476,8 @@ class VMAFAnalyzer(QObject):
                 **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {}),
                 **({"level_align": "apply" if self.level_correct_enabled else "report"}
                    if (self.level_align_enabled or self.level_correct_enabled) else {}),
+                **({"colour_align": "apply" if self.colour_correct_enabled else "report"}
+                   if (self.colour_align_enabled or self.colour_correct_enabled) else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {})}
 
@@ -509,6 +520,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--level-correct"]
         elif self.level_align_enabled:
             cmd += ["--level-align"]
+        if self.colour_correct_enabled:
+            cmd += ["--colour-correct"]
+        elif self.colour_align_enabled:
+            cmd += ["--colour-align"]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -628,7 +643,8 @@ class VMAFAnalyzer(QObject):
                 results["integrity"] = vmaf_data.get("integrity")
                 results["integrity_log"] = self._integrity_path
             if (self.align_enabled or self.spatial_align_enabled or self.level_align_enabled
-                    or self.level_correct_enabled or self.register_filter):   # how the clips were paired, from the log's top level
+                    or self.level_correct_enabled or self.register_filter or self.colour_align_enabled
+                    or self.colour_correct_enabled):   # how the clips were paired, from the log's top level
                 from . import report
                 results["alignment"] = vmaf_data.get("alignment")
                 if results["alignment"] and "offset_frames" in results["alignment"]:
@@ -637,6 +653,8 @@ class VMAFAnalyzer(QObject):
                     self.status_update.emit(report.spatial_summary_line(results["alignment"]["spatial"]))
                 if results["alignment"] and results["alignment"].get("levels"):
                     self.status_update.emit(report.levels_summary_line(results["alignment"]["levels"]))
+                if results["alignment"] and results["alignment"].get("colour"):
+                    self.status_update.emit(report.colour_summary_line(results["alignment"]["colour"]))
                 if results["alignment"] and results["alignment"].get("geometry"):
                     self.status_update.emit(report.geometry_summary_line(results["alignment"]["geometry"]))
             self.analysis_progress.emit(100)
