@@ -41,10 +41,14 @@ inline int vif_tiles_y(int h) { return (h + kVifTileH - 1) / kVifTileH; }
 // s0_mode: which kernel scale 0 runs (read once per context from PQA_VIF_MFMA in pqa_create: A/B runs and the tests that
 // compare the paths): VIF_S0_AUTO = the march kernel (8-, 10- and 12-bit clips);
 // VIF_S0_VALU = VALU only.
+// uniform: 1 = a wave whose pixels are all inside the image and all in the log branch (sigma1_sq >= sigma_nsq) takes the
+// statistic without its other branch (same bits); 0 = every wave takes the general statistic (PQA_VIF_UNIFORM=0, read in
+// pqa_create: the test partner).
 enum : int { VIF_S0_VALU = 0, VIF_S0_AUTO = 1 };
 hipError_t launch_vif_stat(hipStream_t stream, int scale, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames,
                            int w, int h, float inv_scale, float gain_limit, int border101, double* partials,
-                           MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode = VIF_S0_AUTO, int* n_partials = nullptr);
+                           MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode = VIF_S0_AUTO, int* n_partials = nullptr,
+                           int uniform = 1);
 // Scale 0 (8-, 10-, 12-bit clips: `bits`), both filter passes on the f16 matrix cores (vif_march.hip).  vif_march_prepare uploads its tap
 // table once per device (pqa_create does; synchronous, idempotent; a device that does not keep f16 denormals -- probed once,
 // the operand encoding leans on them -- gets no table and scale 0 stays on the VALU kernel); launch_vif_s0_march returns false when it cannot take
@@ -59,7 +63,7 @@ int vif_march_table(uint16_t* out, int capacity_halfwords);
 void vif_march_shape(int w, int h, int* out6);
 bool launch_vif_s0_march(hipStream_t stream, Elem elem, int bits, PlaneRun ref, PlaneRun dis, int n_frames, int w, int h, float gain_limit,
                          int border101, double* partials, MutPlaneRun next_ref, MutPlaneRun next_dis, int* n_partials,
-                         hipError_t* err);
+                         hipError_t* err, int uniform = 1);
 // Fixed-point VIF (integer_vif.c arithmetic, vif_fixed.hip): same tiling; partials are [n_frames][tiles][8] int64
 // {num_log, den_log, x, x2, n_log, den_non_log, num_non_log, -}; next_ref / next_dis are u16 planes (w/2 x h/2).
 // elem: scale 0 reads the caller's samples (ELEM_U8 at 8 bit, ELEM_U16 above), deeper scales ELEM_U16.

@@ -232,7 +232,7 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
         ProfScope ps(c, s, sp_n, st);
         HIPCHK(c, launch_vif_stat(st, s, ce, cr, cd, sp_n, cw, ch, c->inv_scale,
                                   (float)c->cfg.vif_enhn_gain_limit, c->cfg.vif_border == PQA_VIF_BORDER_INTEGER,
-                                  c->vif_part[s], nr, nd, c->vif_s0_mode, &vif_np[s]));
+                                  c->vif_part[s], nr, nd, c->vif_s0_mode, &vif_np[s], c->vif_uniform));
       }
       if (s == 0 && fork_late) {
         HIPCHK(c, hipEventRecord(c->fork_ev, st));
@@ -1062,6 +1062,8 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->trace = t && t[0] == '1';
     const char* v = getenv("PQA_VIF_MFMA");   // 0: VALU kernels only (the march kernel's test partner); default: march kernel
     c->vif_s0_mode = (v && v[0] == '0') ? VIF_S0_VALU : VIF_S0_AUTO;
+    const char* vu = getenv("PQA_VIF_UNIFORM");   // 0: every wave takes the general VIF statistic (test partner of the all-high fast path)
+    c->vif_uniform = !(vu && vu[0] == '0');
     const char* am = getenv("PQA_ADM_MARCH");  // 0: the LDS-tiled ADM kernel (A/B partner of the march kernel)
     const char* ap = getenv("PQA_ADM_PYRAMID");  // 0: the march kernel one scale per launch (test partner of the pyramid kernel)
     c->adm_mode = (am && am[0] == '0') ? ADM_TILED : (ap && ap[0] == '0') ? ADM_MARCH : ADM_AUTO;

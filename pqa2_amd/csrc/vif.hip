@@ -85,6 +85,7 @@ struct VifStatArgs {
   float* dst_dis;
   int64_t dst_row_pitch_r, dst_frame_pitch_r, dst_row_pitch_d, dst_frame_pitch_d;
   TapPairs taps;
+  int uniform;  // 0: every wave takes the general statistic (PQA_VIF_UNIFORM=0, the test partner of the all-high path)
 };
 
 constexpr int kP2 = 258;  // LDS row pitch in float2: == 2 (mod 32) -> conflict-free ds_read_b128 (see below)
@@ -170,60 +171,105 @@ __device__ __forceinline__ void vif_hstat(const VifStatArgs& a, const f2* sv /* 
     // the pair the four columns' arguments (each in [2, 2^16]) are multiplied first, so the thread takes
     // 6 v_log_f32 instead of 16 and needs no reciprocal for num's ratio (log a/b = log a - log b)
     f2 pn = f2{1.0f, 1.0f}, qn = f2{1.0f, 1.0f}, pd = f2{1.0f, 1.0f};
+    // sigma1_sq of the lane's eight pixels first: one compare each and one ballot tell whether every pixel of the wave's
+    // active lanes is inside the image and in the log branch.  Such a wave takes the statistic without its other branch: the
+    // general path has s1h = s1 there and gden = s1 + eps IS s1 (eps = 1e-10 is below half an ulp of 2, 1.2e-7); wl = 0 with
+    // `low` finite, so num2 and den2 stay +0.  The bits of the general path (tests/test_gpu_vif_uniform.py holds them to ==);
+    // textured material is all-high wave by wave, flat sections and the edges between the two pay for both branches.
+    // (The matching all-low path was built, is bit-identical too, and did not pay: DESIGN.md section 10.)
+    f2 s1v[4];
+    bool any_low = false;
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      const bool vcol = (x0 + seg * 4 + o) < a.w;
-      // the two rows of the pair go through the statistic together: every add / mul / fma is packed,
-      // only max / min / select / rcp / log are per element
-      const f2 mu1 = out[0][o], mu2 = out[1][o];
-      const f2 s1 = out[2][o] - mu1 * mu1;
-      f2 s2 = out[3][o] - mu2 * mu2;
-      const f2 s12 = out[4][o] - mu1 * mu2;
-      s2 = f2{fmaxf(s2.x, 0.0f), fmaxf(s2.y, 0.0f)};
-      // validity and the branch choice: out-of-image positions of edge tiles hold finite values (mirrored real
-      // pixels); they and the positions of the low branch contribute a factor 1 to the log products and a weight 0 / 1
-      // to the low sums.  ONE select does it for all three products: with sigma1_sq replaced by 0 the arguments
-      // become narg = svn (cancels against qn's svn) and darg = 1.  (A select costs the VALU as much as a packed FMA.)
-      // libvmaf's MAX(sigma1_sq, 0) needs no instruction either: the log branch has sigma1_sq >= 2, everything else
-      // continues with 0.
-      const bool vx = vcol && vrow[0], vy = vcol && vrow[1];
-      const bool hx = vx && !(s1.x < sigma_nsq), hy = vy && !(s1.y < sigma_nsq);
-      const bool lx = vx && (s1.x < sigma_nsq), ly = vy && (s1.y < sigma_nsq);
-      const f2 s1h = f2{hx ? s1.x : 0.0f, hy ? s1.y : 0.0f};
-      // g = sigma12 / (sigma1_sq + eps): v_rcp_f32 plus one Newton correction -- exact 1.0 when the two
-      // are equal (identical frames), 2 FMAs instead of a full IEEE division.  (Off the log branch g is sigma12 / eps:
-      // large but finite, clamped below, and multiplied by s1h = 0.)
-      const f2 gden = s1h + f2{eps, eps};
-      const f2 grcp = f2{fast_rcp(gden.x), fast_rcp(gden.y)};
-      f2 g = s12 * grcp;
-      g = __builtin_elementwise_fma(__builtin_elementwise_fma(-g, gden, s12), grcp, g);
-      f2 sv = s2 - g * s12;
-      // vif_statistic_s also has `if (sigma1_sq < eps) {g = 0; sv_sq = sigma2_sq; sigma1_sq = 0}` and
-      // `if (g < 0) {sv_sq = sigma2_sq; g = 0}`.  Both are dead for the result: the first implies
-      // sigma1_sq < sigma_nsq and the second implies sigma12 < 0, and each of those overrides num/den below.
-      // Its third override, `if (sigma2_sq < eps) {g = 0; sv_sq = 0}`, changes nothing measurable either: with
-      // sigma2_sq < 1e-10 Cauchy-Schwarz bounds |sigma12| <= sqrt(sigma1_sq * 1e-10), so g^2 sigma1_sq <= 1e-10 next to
-      // sv_sq + 2 in the log's argument, and sv_sq = sigma2_sq - g sigma12 lies within 1e-10 of 0 and is raised to eps
-      // by the max below in both forms.  (Round 1 kept it as two compares and four selects per pixel pair.)
-      sv = f2{fmaxf(sv.x, eps), fmaxf(sv.y, eps)};
-      // clamp g to [0, gain_limit] with one v_med3_f32: the upper bound is vif_enhn_gain_limit, the lower
-      // bound makes g*g = 0 when sigma12 < 0, i.e. num_val = log2(1) = 0 -- libvmaf's `if (sigma12 < 0) num_val = 0`
-      g = f2{__builtin_amdgcn_fmed3f(g.x, 0.0f, a.gain_limit), __builtin_amdgcn_fmed3f(g.y, 0.0f, a.gain_limit)};
-      const f2 svn = sv + f2{sigma_nsq, sigma_nsq};
-      // num_val = log2(1 + g^2 sigma1_sq / (sv_sq + sigma_nsq)) = log2(narg) - log2(svn)
-      const f2 narg = __builtin_elementwise_fma(g * g, s1h, svn);
-      const f2 darg = __builtin_elementwise_fma(s1h, f2{1.0f / sigma_nsq, 1.0f / sigma_nsq}, f2{1.0f, 1.0f});
-      const f2 low = __builtin_elementwise_fma(s2, f2{-sigma_max_inv, -sigma_max_inv}, f2{1.0f, 1.0f});
-      pn *= narg;
-      qn *= svn;
-      pd *= darg;
-      const f2 wl = f2{lx ? 1.0f : 0.0f, ly ? 1.0f : 0.0f};
-      num2 = __builtin_elementwise_fma(wl, low, num2);
-      den2 += wl;
-      __builtin_amdgcn_sched_barrier(0);  // two pixels' worth of temporaries live at a time
+      const f2 mu1 = out[0][o];
+      s1v[o] = out[2][o] - mu1 * mu1;
+      const bool lx = s1v[o].x < sigma_nsq, ly = s1v[o].y < sigma_nsq;
+      any_low = any_low || lx || ly;
     }
-    num = (num2.x + num2.y) + ((fast_log2(pn.x) - fast_log2(qn.x)) + (fast_log2(pn.y) - fast_log2(qn.y)));
-    den = (den2.x + den2.y) + (fast_log2(pd.x) + fast_log2(pd.y));
+    const bool cols_in = x0 + seg * 4 + 4 <= a.w;
+    const bool rows_in = a.uniform && y0 + TH <= a.h;   // workgroup-uniform
+    // (a ballot counts the active lanes only: lanes with seg >= NSEG are not here)
+    const bool none_low = __builtin_amdgcn_ballot_w64(!cols_in || any_low) == 0ull;
+    if (rows_in && none_low) {
+#pragma unroll
+      for (int o = 0; o < 4; ++o) {
+        const f2 mu1 = out[0][o], mu2 = out[1][o];
+        const f2 s1 = s1v[o];
+        f2 s2 = out[3][o] - mu2 * mu2;
+        const f2 s12 = out[4][o] - mu1 * mu2;
+        s2 = f2{fmaxf(s2.x, 0.0f), fmaxf(s2.y, 0.0f)};
+        const f2 grcp = f2{fast_rcp(s1.x), fast_rcp(s1.y)};
+        f2 g = s12 * grcp;
+        g = __builtin_elementwise_fma(__builtin_elementwise_fma(-g, s1, s12), grcp, g);
+        f2 sv = s2 - g * s12;
+        sv = f2{fmaxf(sv.x, eps), fmaxf(sv.y, eps)};
+        g = f2{__builtin_amdgcn_fmed3f(g.x, 0.0f, a.gain_limit), __builtin_amdgcn_fmed3f(g.y, 0.0f, a.gain_limit)};
+        const f2 svn = sv + f2{sigma_nsq, sigma_nsq};
+        const f2 narg = __builtin_elementwise_fma(g * g, s1, svn);
+        const f2 darg = __builtin_elementwise_fma(s1, f2{1.0f / sigma_nsq, 1.0f / sigma_nsq}, f2{1.0f, 1.0f});
+        pn *= narg;
+        qn *= svn;
+        pd *= darg;
+        __builtin_amdgcn_sched_barrier(0);  // two pixels' worth of temporaries live at a time
+      }
+      num = (fast_log2(pn.x) - fast_log2(qn.x)) + (fast_log2(pn.y) - fast_log2(qn.y));
+      den = fast_log2(pd.x) + fast_log2(pd.y);
+    } else {
+#pragma unroll
+      for (int o = 0; o < 4; ++o) {
+        const bool vcol = (x0 + seg * 4 + o) < a.w;
+        // the two rows of the pair go through the statistic together: every add / mul / fma is packed,
+        // only max / min / select / rcp / log are per element
+        const f2 mu1 = out[0][o], mu2 = out[1][o];
+        const f2 s1 = s1v[o];
+        f2 s2 = out[3][o] - mu2 * mu2;
+        const f2 s12 = out[4][o] - mu1 * mu2;
+        s2 = f2{fmaxf(s2.x, 0.0f), fmaxf(s2.y, 0.0f)};
+        // validity and the branch choice: out-of-image positions of edge tiles hold finite values (mirrored real
+        // pixels); they and the positions of the low branch contribute a factor 1 to the log products and a weight 0 / 1
+        // to the low sums.  ONE select does it for all three products: with sigma1_sq replaced by 0 the arguments
+        // become narg = svn (cancels against qn's svn) and darg = 1.  (A select costs the VALU as much as a packed FMA.)
+        // libvmaf's MAX(sigma1_sq, 0) needs no instruction either: the log branch has sigma1_sq >= 2, everything else
+        // continues with 0.
+        const bool vx = vcol && vrow[0], vy = vcol && vrow[1];
+        const bool hx = vx && !(s1.x < sigma_nsq), hy = vy && !(s1.y < sigma_nsq);
+        const bool lx = vx && (s1.x < sigma_nsq), ly = vy && (s1.y < sigma_nsq);
+        const f2 s1h = f2{hx ? s1.x : 0.0f, hy ? s1.y : 0.0f};
+        // g = sigma12 / (sigma1_sq + eps): v_rcp_f32 plus one Newton correction -- exact 1.0 when the two
+        // are equal (identical frames), 2 FMAs instead of a full IEEE division.  (Off the log branch g is sigma12 / eps:
+        // large but finite, clamped below, and multiplied by s1h = 0.)
+        const f2 gden = s1h + f2{eps, eps};
+        const f2 grcp = f2{fast_rcp(gden.x), fast_rcp(gden.y)};
+        f2 g = s12 * grcp;
+        g = __builtin_elementwise_fma(__builtin_elementwise_fma(-g, gden, s12), grcp, g);
+        f2 sv = s2 - g * s12;
+        // vif_statistic_s also has `if (sigma1_sq < eps) {g = 0; sv_sq = sigma2_sq; sigma1_sq = 0}` and
+        // `if (g < 0) {sv_sq = sigma2_sq; g = 0}`.  Both are dead for the result: the first implies
+        // sigma1_sq < sigma_nsq and the second implies sigma12 < 0, and each of those overrides num/den below.
+        // Its third override, `if (sigma2_sq < eps) {g = 0; sv_sq = 0}`, changes nothing measurable either: with
+        // sigma2_sq < 1e-10 Cauchy-Schwarz bounds |sigma12| <= sqrt(sigma1_sq * 1e-10), so g^2 sigma1_sq <= 1e-10 next to
+        // sv_sq + 2 in the log's argument, and sv_sq = sigma2_sq - g sigma12 lies within 1e-10 of 0 and is raised to eps
+        // by the max below in both forms.  (Round 1 kept it as two compares and four selects per pixel pair.)
+        sv = f2{fmaxf(sv.x, eps), fmaxf(sv.y, eps)};
+        // clamp g to [0, gain_limit] with one v_med3_f32: the upper bound is vif_enhn_gain_limit, the lower
+        // bound makes g*g = 0 when sigma12 < 0, i.e. num_val = log2(1) = 0 -- libvmaf's `if (sigma12 < 0) num_val = 0`
+        g = f2{__builtin_amdgcn_fmed3f(g.x, 0.0f, a.gain_limit), __builtin_amdgcn_fmed3f(g.y, 0.0f, a.gain_limit)};
+        const f2 svn = sv + f2{sigma_nsq, sigma_nsq};
+        // num_val = log2(1 + g^2 sigma1_sq / (sv_sq + sigma_nsq)) = log2(narg) - log2(svn)
+        const f2 narg = __builtin_elementwise_fma(g * g, s1h, svn);
+        const f2 darg = __builtin_elementwise_fma(s1h, f2{1.0f / sigma_nsq, 1.0f / sigma_nsq}, f2{1.0f, 1.0f});
+        const f2 low = __builtin_elementwise_fma(s2, f2{-sigma_max_inv, -sigma_max_inv}, f2{1.0f, 1.0f});
+        pn *= narg;
+        qn *= svn;
+        pd *= darg;
+        const f2 wl = f2{lx ? 1.0f : 0.0f, ly ? 1.0f : 0.0f};
+        num2 = __builtin_elementwise_fma(wl, low, num2);
+        den2 += wl;
+        __builtin_amdgcn_sched_barrier(0);  // two pixels' worth of temporaries live at a time
+      }
+      num = (num2.x + num2.y) + ((fast_log2(pn.x) - fast_log2(qn.x)) + (fast_log2(pn.y) - fast_log2(qn.y)));
+      den = (den2.x + den2.y) + (fast_log2(pd.x) + fast_log2(pd.y));
+    }
   }
   {
     const float part[2] = {num, den};
@@ -367,14 +413,14 @@ int vif_tile_w(int scale) { return kVifTW[scale]; }
 
 hipError_t launch_vif_stat(hipStream_t stream, int scale, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames,
                            int w, int h, float inv_scale, float gain_limit, int border101, double* partials,
-                           MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode, int* n_partials) {
+                           MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode, int* n_partials, int uniform) {
   if (n_partials) *n_partials = vif_tiles_x(scale, w) * vif_tiles_y(h);
   if (n_frames <= 0) return hipSuccess;
   // (the bit depth of 16-bit elements is recognised by the sample scale: 1/4 = 10 bit, 1/16 = 12 bit)
   const int bits = elem == ELEM_U8 ? 8 : (elem == ELEM_U16 && inv_scale == 0.25f) ? 10 : (elem == ELEM_U16 && inv_scale == 0.0625f) ? 12 : 0;
   if (scale == 0 && bits && s0_mode == VIF_S0_AUTO && next_ref.base && next_dis.base) {
     hipError_t err = hipSuccess;
-    if (launch_vif_s0_march(stream, elem, bits, ref, dis, n_frames, w, h, gain_limit, border101, partials, next_ref, next_dis, n_partials, &err))
+    if (launch_vif_s0_march(stream, elem, bits, ref, dis, n_frames, w, h, gain_limit, border101, partials, next_ref, next_dis, n_partials, &err, uniform))
       return err;
     if (n_partials) *n_partials = vif_tiles_x(scale, w) * vif_tiles_y(h);
   }
@@ -387,6 +433,7 @@ hipError_t launch_vif_stat(hipStream_t stream, int scale, Elem elem, PlaneRun re
   a.tiles_x = vif_tiles_x(scale, w);
   a.n_tiles = a.tiles_x * vif_tiles_y(h);
   a.inv_scale = inv_scale; a.gain_limit = gain_limit;
+  a.uniform = uniform;
   a.partials = partials;
   a.dst_ref = (float*)next_ref.base; a.dst_dis = (float*)next_dis.base;
   a.dst_row_pitch_r = next_ref.row_pitch; a.dst_frame_pitch_r = next_ref.frame_pitch;

@@ -92,6 +92,7 @@ struct MarchArgs {
   int n_cb, n_cbg, seg_blocks, n_seg, row_blocks;
   float mean_off, dec_off;                 // -128 * sum(17 taps) / 16 and -128 * sum(9 taps): the mid-grey term of the planes filtered as samples
   const uint4* tab;
+  int uniform;                             // 0: every block takes the general statistic (PQA_VIF_UNIFORM=0, the test partner of the all-high path)
 };
 
 // The pieces of TWO consecutive 16-row blocks after pass 1 (rows 4 (lane >> 4) + i of column (lane & 15)), laid out as the
@@ -103,13 +104,21 @@ struct Pieces {
 
 // vif_statistic_s on two horizontally adjacent pixels, in units U = 16 (see the file comment): accumulates the low-branch
 // sums and the three log products.  Same algebra as vif_hstat (vif.hip), which documents each override that drops out.
+// s1 = sigma1_sq of the pair (xx - mu1 * mu1), formed by the caller, which decides the path on it.
+//
+// HIGH picks one of two evaluations that give the SAME BITS where both apply (pass2 takes the short one only when every
+// pixel of the wave's 16 x 16 block is inside the image and has s1 >= sigma_nsq):
+//   false  both branches of every pixel, blended by selects and 0 / 1 weights.
+//   true   every pixel valid and in the log branch.  The general path has s1h = s1 there, and gden = s1 + eps IS s1 (eps =
+//          2.56e-8 is below half an ulp of 512, 3.05e-5); wl = 0 with `low` finite, so num2 and den2 stay +0.
+// (The matching all-low path -- only `low` and a constant count -- was built, is bit-identical too, and did not pay: DESIGN.md section 10.)
 struct StatAcc {
   f2 num2, den2, pn, qn, pd;
 };
-__device__ __forceinline__ void stat_pair(StatAcc& s, const f2 mu1, const f2 mu2, const f2 xx, const f2 yy, const f2 xy,
+template <bool HIGH>
+__device__ __forceinline__ void stat_pair(StatAcc& s, const f2 s1, const f2 mu1, const f2 mu2, const f2 yy, const f2 xy,
                                           const bool v0, const bool v1, const float gain_limit) {
   const float sigma_nsq = 2.0f * 256.0f, eps = 1.0e-10f * 256.0f, sigma_max_inv = 4.0f / (255.0f * 255.0f * 256.0f);
-  const f2 s1 = xx - mu1 * mu1;
   f2 s2 = yy - mu2 * mu2;
   const f2 s12 = xy - mu1 * mu2;
   s2 = f2{fmaxf(s2.x, 0.0f), fmaxf(s2.y, 0.0f)};
@@ -118,8 +127,8 @@ __device__ __forceinline__ void stat_pair(StatAcc& s, const f2 mu1, const f2 mu2
   const bool lt0 = s1.x < sigma_nsq, lt1 = s1.y < sigma_nsq;
   const bool hx = v0 && !lt0, hy = v1 && !lt1;
   const bool lx = v0 && lt0, ly = v1 && lt1;
-  const f2 s1h = f2{hx ? s1.x : 0.0f, hy ? s1.y : 0.0f};
-  const f2 gden = s1h + f2{eps, eps};
+  const f2 s1h = HIGH ? s1 : f2{hx ? s1.x : 0.0f, hy ? s1.y : 0.0f};
+  const f2 gden = HIGH ? s1 : s1h + f2{eps, eps};
   const f2 grcp = f2{fast_rcp(gden.x), fast_rcp(gden.y)};
   f2 g = s12 * grcp;
   g = __builtin_elementwise_fma(__builtin_elementwise_fma(-g, gden, s12), grcp, g);
@@ -129,13 +138,15 @@ __device__ __forceinline__ void stat_pair(StatAcc& s, const f2 mu1, const f2 mu2
   const f2 svn = sv + f2{sigma_nsq, sigma_nsq};
   const f2 narg = __builtin_elementwise_fma(g * g, s1h, svn);
   const f2 darg = __builtin_elementwise_fma(s1h, f2{1.0f / sigma_nsq, 1.0f / sigma_nsq}, f2{1.0f, 1.0f});
-  const f2 low = __builtin_elementwise_fma(s2, f2{-sigma_max_inv, -sigma_max_inv}, f2{1.0f, 1.0f});
   s.pn *= narg;
   s.qn *= svn;
   s.pd *= darg;
-  const f2 wl = f2{lx ? 1.0f : 0.0f, ly ? 1.0f : 0.0f};
-  s.num2 = __builtin_elementwise_fma(wl, low, s.num2);
-  s.den2 += wl;
+  if constexpr (!HIGH) {
+    const f2 low = __builtin_elementwise_fma(s2, f2{-sigma_max_inv, -sigma_max_inv}, f2{1.0f, 1.0f});
+    const f2 wl = f2{lx ? 1.0f : 0.0f, ly ? 1.0f : 0.0f};
+    s.num2 = __builtin_elementwise_fma(wl, low, s.num2);
+    s.den2 += wl;
+  }
 }
 
 // PQA_MARCH_LDS_TABLES: the tap fragments of the next scale's input (used once per block each) stay in LDS and are read
@@ -435,17 +446,34 @@ __global__ __launch_bounds__(kBlock, PQA_MARCH_OCC) void vif_s0_march_kernel(con
         }
       }
     }
-    // statistic on this lane's 4 pixels (row yo + m, columns x0 + 4 kq + i)
-    const bool vrow = yo + m < a.h;
+    // statistic on this lane's 4 pixels (row yo + m, columns x0 + 4 kq + i).  sigma1_sq of all four first: one compare each
+    // and one ballot tell whether every pixel of the block is in the log branch, and a block that is -- and lies inside the
+    // image -- takes the shortened statistic (stat_pair<true>; same bits).  Textured material is all-high block by block;
+    // flat sections and the edges between the two pay for both branches.
+    const f2 mu1a = f2{V[0][0], V[0][1]}, mu1b = f2{V[0][2], V[0][3]};
+    const f2 s1a = f2{V[2][0], V[2][1]} - mu1a * mu1a, s1b = f2{V[2][2], V[2][3]} - mu1b * mu1b;
+    const f2 mu2a = f2{V[1][0], V[1][1]}, mu2b = f2{V[1][2], V[1][3]};
+    const f2 yya = f2{V[3][0], V[3][1]}, yyb = f2{V[3][2], V[3][3]};
+    const f2 xya = f2{V[4][0], V[4][1]}, xyb = f2{V[4][2], V[4][3]};
+    const float sigma_nsq = 2.0f * 256.0f;
+    const bool some_low = s1a.x < sigma_nsq || s1a.y < sigma_nsq || s1b.x < sigma_nsq || s1b.y < sigma_nsq;
+    const bool inside = a.uniform && yo + 16 <= a.h && x0 + 16 <= a.w;                // wave-uniform (every lane is active here)
     StatAcc st{f2{0.0f, 0.0f}, f2{0.0f, 0.0f}, f2{1.0f, 1.0f}, f2{1.0f, 1.0f}, f2{1.0f, 1.0f}};
-    stat_pair(st, f2{V[0][0], V[0][1]}, f2{V[1][0], V[1][1]}, f2{V[2][0], V[2][1]}, f2{V[3][0], V[3][1]},
-              f2{V[4][0], V[4][1]}, vrow && vcol[0], vrow && vcol[1], a.gain_limit);
-    stat_pair(st, f2{V[0][2], V[0][3]}, f2{V[1][2], V[1][3]}, f2{V[2][2], V[2][3]}, f2{V[3][2], V[3][3]},
-              f2{V[4][2], V[4][3]}, vrow && vcol[2], vrow && vcol[3], a.gain_limit);
-    // the log terms of the lane's four pixels as ONE log per product: in units U = 16 every factor lies in [1, 2^24) (narg <=
-    // sigma2_sq + sv_sq + sigma_nsq by Cauchy-Schwarz, each <= 2^22), four of them below 2^96 -- three v_log_f32 instead of six
-    const float num = (st.num2.x + st.num2.y) + (fast_log2(st.pn.x * st.pn.y) - fast_log2(st.qn.x * st.qn.y));
-    const float den = (st.den2.x + st.den2.y) + fast_log2(st.pd.x * st.pd.y);
+    float num, den;
+    if (inside && __builtin_amdgcn_ballot_w64(some_low) == 0ull) {
+      stat_pair<true>(st, s1a, mu1a, mu2a, yya, xya, true, true, a.gain_limit);
+      stat_pair<true>(st, s1b, mu1b, mu2b, yyb, xyb, true, true, a.gain_limit);
+      num = fast_log2(st.pn.x * st.pn.y) - fast_log2(st.qn.x * st.qn.y);
+      den = fast_log2(st.pd.x * st.pd.y);
+    } else {
+      const bool vrow = yo + m < a.h;
+      stat_pair<false>(st, s1a, mu1a, mu2a, yya, xya, vrow && vcol[0], vrow && vcol[1], a.gain_limit);
+      stat_pair<false>(st, s1b, mu1b, mu2b, yyb, xyb, vrow && vcol[2], vrow && vcol[3], a.gain_limit);
+      // the log terms of the lane's four pixels as ONE log per product: in units U = 16 every factor lies in [1, 2^24) (narg <=
+      // sigma2_sq + sv_sq + sigma_nsq by Cauchy-Schwarz, each <= 2^22), four of them below 2^96 -- three v_log_f32 instead of six
+      num = (st.num2.x + st.num2.y) + (fast_log2(st.pn.x * st.pn.y) - fast_log2(st.qn.x * st.qn.y));
+      den = (st.den2.x + st.den2.y) + fast_log2(st.pd.x * st.pd.y);
+    }
     dnum += (double)num;
     dden += (double)den;
   };
@@ -646,8 +674,9 @@ hipError_t vif_march_prepare() {
 
 bool launch_vif_s0_march(hipStream_t stream, Elem elem, int bits, PlaneRun ref, PlaneRun dis, int n_frames, int w, int h, float gain_limit,
                          int border101, double* partials, MutPlaneRun next_ref, MutPlaneRun next_dis, int* n_partials,
-                         hipError_t* err) {
+                         hipError_t* err, int uniform) {
   MarchArgs a{};
+  a.uniform = uniform;
   a.tab = device_tab();
   if (!a.tab) return false;
   if (!((elem == ELEM_U8 && bits == 8) || (elem == ELEM_U16 && (bits == 10 || bits == 12)))) return false;

@@ -18,10 +18,17 @@ ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--features", type=int, default=7, help="PQA_FEAT_* mask: 1 VIF, 2 ADM, 4 motion (isolate one chain)")
 ap.add_argument("--bits", type=int, default=8)
 ap.add_argument("--fixed", type=int, default=0, help="pqa_config.fixed_point mask")
+ap.add_argument("--bars", type=float, default=0.0, help="flat mid-grey bars over this fraction of the rows at the top and at the bottom "
+                "of ref and dis (letterbox: the rows where the VIF statistic is all in its low branch)")
 a = ap.parse_args()
 w, h = map(int, a.size.split("x"))
 clip = synth_torch.make_clip_cuda(w, h, a.frames, a.bits)
 R, D = clip["ref"][0], clip["dis"][0]
+if a.bars > 0:
+    nb = int(h * a.bars)
+    for P in (R, D):
+        P.view(a.frames, h, w)[:, :nb] = 128 << (a.bits - 8)
+        P.view(a.frames, h, w)[:, h - nb:] = 128 << (a.bits - 8)
 torch.cuda.synchronize()
 
 def bind(spec):
@@ -67,4 +74,5 @@ for rnd in range(a.rounds + 1):
         if rnd:
             times[i].append(dt)
 for p, t in zip(a.libs, times):
-    print(f"{os.path.basename(p.partition('@')[0]) + ('@' + p.partition('@')[2] if '@' in p else ''):44s} median {a.frames / statistics.median(t):9.1f} fps   best {a.frames / min(t):9.1f} fps   ({len(t)} rounds)")
+    # (the path as given, not its basename: the variants of tools/build_variant.sh are all called libpqa_vmaf.so)
+    print(f"{p:44s} median {a.frames / statistics.median(t):9.1f} fps   best {a.frames / min(t):9.1f} fps   ({len(t)} rounds)")
