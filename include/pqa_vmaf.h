@@ -587,6 +587,33 @@ PQA_API int pqa_flow_moments_device(pqa_ctx* ctx, const pqa_flow_spec* spec, con
                                     int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                     int32_t n_frames, int64_t* out);
 
+/* Active-picture detection: the row and column profiles of n_frames planes of ONE clip, synchronously -- what
+ * pqa2_amd/align.py (active_picture, common_window) finds letterbox and pillarbox bars with.  Planes of width x height samples
+ * (the spec's, independent of the context's width and height; each 1 ... 8192), u8 in an 8-bit context, otherwise u16 of the
+ * context's bit depth b (a sample above 2^b - 1 is read as 2^b - 1):
+ *     rows[f][y][0] = sum_x v[y][x]     rows[f][y][1] = sum_x v[y][x]^2
+ *     cols[f][x][0] = sum_y v[y][x]     cols[f][x][1] = sum_y v[y][x]^2
+ * Exact uint64, no floating point anywhere; every sample is read once for both profiles.  out (host) is
+ * [n_frames][height + width][2]: the rows of a frame first, then its columns.  The profile of a window of rows is that of
+ * planes whose base pointer and height select the window.  Any context, no feature bit; buffers are made on first use, grow
+ * only and are freed with the context.  Independent of the scoring chain: a call between two pqa_submit calls changes no
+ * record.  PQA_EINVAL, before any device call, on a null pointer, a bad struct_size, a size outside 1 ... 8192, a row pitch
+ * shorter than a row (or, in device memory, a pitch that is no multiple of the sample size), or a negative frame count.
+ * n_frames == 0 succeeds and writes nothing.  Kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_line_profiles: frames in HOST memory (frames[f] points at a plane, rows row_stride bytes apart; the frames need not be
+ * contiguous).  They travel in chunks of 8 through the first pinned buffer of pqa_resample.
+ * pqa_line_profiles_device: the clip in device memory (frame f at planes + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+typedef struct pqa_profile_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane, 1 ... 8192 */
+} pqa_profile_spec;
+PQA_API int pqa_line_profiles(pqa_ctx* ctx, const pqa_profile_spec* spec, const void* const* frames, int64_t row_stride,
+                              int32_t n_frames, uint64_t* out);
+PQA_API int pqa_line_profiles_device(pqa_ctx* ctx, const pqa_profile_spec* spec, const void* planes, int64_t row_pitch,
+                                     int64_t frame_pitch, int32_t n_frames, uint64_t* out);
+
 /* Colour-matrix alignment: the cross-plane moments of n_frames frame pairs, synchronously -- what a capture chain that decodes
  * Y'CbCr with one matrix and encodes with another (BT.709 through a BT.601 leg) leaves behind, which no single-plane
  * measurement sees.  Works on the chroma grid of the context: chroma_shift = (hs, vs), s = 2^(hs + vs), chroma planes of

@@ -3,7 +3,8 @@ SSE (FeatureEngine.shift_sse, pqa_shift_sse) to the whole-pixel displacement of 
 level_lut, at the end of this file): from the per-level transfer table (FeatureEngine.level_stats, pqa_level_stats) to the gain
 and offset of the captured samples, the named range conversion they amount to and the table that undoes it.  Colour (best_colour,
 colour_correction, at the very end): from the cross-plane moments (FeatureEngine.colour_moments, pqa_colour_moments) to the 3 x 4 map of
-the captured planes, the named matrix conversion it amounts to and the Q14 matrix that undoes it.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
+the captured planes, the named matrix conversion it amounts to and the Q14 matrix that undoes it.  Active picture (active_picture, common_window, after the colour part): from the row and column profiles
+(FeatureEngine.line_profiles, pqa_line_profiles) to the black bars of each clip and the rectangle both share.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
 constant frame offset and a per-frame map with repeated and dropped frames.
 
     D[i][c] = sum over luma pixels of (ref_i - dis_{i+k})^2,  k = k_lo + c;  UINT64_MAX where i + k is no captured frame
@@ -788,3 +789,116 @@ def colour_correction(result: dict, bit_depth: int, full_range: bool = False):
     if inv is None:
         return None
     return colour_matrix_q14(inv, [-sum(inv[i][j] * b[j] for j in range(3)) for i in range(3)])
+
+
+# ---- active picture -------------------------------------------------------------------------------------------------------------
+# Black bars from the row and column profiles of a clip (FeatureEngine.line_profiles, pqa_line_profiles): sums and sums of
+# squares per line, exact integers.  A line of n samples is DARK in a frame iff its sum is at most L n, L = limit 2^(b - 8):
+# its mean does not exceed `limit` in 8-bit code values (24: black at 16 plus what a noisy capture of it adds).  A bar is a
+# run of lines from an edge that are dark in every frame that shows a picture at all.  Python ints and Fractions only.
+ACTIVE_LIMIT = 24
+ACTIVE_TOLERANCE = 16   # bars of the two clips that differ by more than this many lines on a side are another geometry, not a shift
+ACTIVE_MIN_SIZE = 16    # the smallest frame a scoring context accepts, each way
+
+
+def _edge_run(dark, n: int, skip: int):
+    """(lines from the low edge, lines from the high edge) that are dark; the outermost `skip` lines of an edge count as dark
+    whatever they hold, but a run that ends inside them is no bar.  None when the runs meet: no picture line is left."""
+    lo = 0
+    while lo < n and (lo < skip or dark[lo]):
+        lo += 1
+    hi = 0
+    while hi < n and (hi < skip or dark[n - 1 - hi]):
+        hi += 1
+    if lo + hi >= n:
+        return None
+    return (lo if lo > skip else 0), (hi if hi > skip else 0)
+
+
+def active_picture(rows, cols_of, bit_depth: int, *, limit: int = ACTIVE_LIMIT, skip: int = 0) -> dict:
+    """The active picture window of a clip from its line profiles.  rows[f][y] = (sum, sum of squares) of row y of frame f
+    over the full width; cols_of(top, bottom) -> cols[f][x] = the same of column x over the rows top ... H - bottom - 1 only
+    (a column sum over the full height is dragged down by letterbox rows: a dim picture column would pass for a bar).
+    cols_of(0, 0) is the profile that came with `rows` and costs the caller nothing; it is asked for first, for the width.
+
+    Frames whose every row is dark (black frames, fades) are left out; `all_dark` when none remains, or when no picture
+    line remains between the bars.  top = the largest t such that the rows 0 ... t - 1 are dark in every remaining frame,
+    the outermost `skip` rows counting as dark whatever they hold (a caption or timecode line in row 0 of a capture); a run
+    that ends inside the skipped lines is no bar.  bottom likewise; then left and right from cols_of(top, bottom) with n =
+    H - top - bottom.  Returns {left, top, right, bottom, window: [x0, y0, w, h] or None, frames_used, all_dark, bar_noise}:
+    bar_noise = the pooled variance (a Fraction) of the samples in the bars -- the bar rows over the full width and the bar
+    columns over the active rows, without the skipped lines, over the remaining frames; None without bars."""
+    b, limit, skip = int(bit_depth), int(limit), int(skip)
+    if b < 8 or not 0 <= limit <= 255 or skip < 0:
+        raise ValueError("active_picture needs bit_depth >= 8, 0 <= limit <= 255 and skip >= 0")
+    L = limit << (b - 8)
+    R = [[(int(s), int(q)) for s, q in frame] for frame in rows]
+    if not R or not R[0]:
+        raise ValueError("rows must be [n_frames >= 1][H >= 1][2]")
+    H = len(R[0])
+    full = cols_of(0, 0)
+    W = len(full[0])
+    none = {"left": 0, "top": 0, "right": 0, "bottom": 0, "window": None, "frames_used": 0, "all_dark": True, "bar_noise": None}
+    used = [f for f in range(len(R)) if any(R[f][y][0] > L * W for y in range(H))]
+    if not used:
+        return none
+    run = _edge_run([all(R[f][y][0] <= L * W for f in used) for y in range(H)], H, skip)
+    if run is None:
+        return dict(none, frames_used=len(used))
+    top, bottom = run
+    ah = H - top - bottom
+    cols = full if top == 0 and bottom == 0 else cols_of(top, bottom)
+    Cc = [[(int(s), int(q)) for s, q in cols[f]] for f in used]
+    if any(len(c) != W for c in Cc):
+        raise ValueError("cols_of must return [n_frames][W][2]")
+    run = _edge_run([all(c[x][0] <= L * ah for c in Cc) for x in range(W)], W, skip)
+    if run is None:
+        return dict(none, frames_used=len(used))
+    left, right = run
+    # the bars' samples: lines outside the skipped ones
+    bar_rows = [y for y in range(H) if (y < top or y >= H - bottom) and skip <= y < H - skip]
+    bar_cols = [x for x in range(W) if (x < left or x >= W - right) and skip <= x < W - skip]
+    count = len(used) * (len(bar_rows) * W + len(bar_cols) * ah)
+    noise = None
+    if count:
+        s = sum(R[f][y][0] for f in used for y in bar_rows) + sum(c[x][0] for c in Cc for x in bar_cols)
+        q = sum(R[f][y][1] for f in used for y in bar_rows) + sum(c[x][1] for c in Cc for x in bar_cols)
+        noise = Fraction(q, count) - Fraction(s, count) ** 2
+    return {"left": left, "top": top, "right": right, "bottom": bottom, "window": [left, top, W - left - right, ah],
+            "frames_used": len(used), "all_dark": False, "bar_noise": noise}
+
+
+def common_window(ref_ap: dict, dis_ap: dict, width: int, height: int, hshift: int, vshift: int, *,
+                  tolerance: int = ACTIVE_TOLERANCE, min_size: int = ACTIVE_MIN_SIZE) -> dict:
+    """What two active_picture() results of clips of width x height mean for a pair.  Returns {crop: [left, top, right,
+    bottom], same, mismatch, scale, offset, reason}.  crop: per side the larger of the two clips' bars, rounded up to the
+    chroma step (1 << hshift horizontally, 1 << vshift vertically), as registration_crop rounds -- the common inner
+    rectangle; a difference of the bars within `tolerance` lines is a displacement, which is cropped and left to
+    spatial_align.  same: all four bars are equal.  mismatch: a side differs by more than `tolerance` -- the capture has
+    other bars than the reference, a scaler sits in the chain, and cropping through that would score geometry: crop is then
+    all zero.  scale = [w_dis / w_ref, h_dis / h_ref] and offset = [centre_dis - centre_ref] per axis of the two windows, as
+    Fractions (window_geometry of each window against the frame): what `register` or `resize` would have to undo.  reason:
+    None when crop is to be applied, else "all dark" (either clip; scale and offset are None), "windows differ" (mismatch),
+    "no bars" (crop all zero) or "window too small" (less than min_size samples remain on an axis)."""
+    if ref_ap["all_dark"] or dis_ap["all_dark"]:
+        return {"crop": [0, 0, 0, 0], "same": False, "mismatch": False, "scale": None, "offset": None, "reason": "all dark"}
+    sides = ("left", "top", "right", "bottom")
+    rb, db = [int(ref_ap[k]) for k in sides], [int(dis_ap[k]) for k in sides]
+    same = rb == db
+    mismatch = any(abs(r - d) > int(tolerance) for r, d in zip(rb, db))
+    scale, offset = [], []
+    for n, lo in ((int(width), 0), (int(height), 1)):
+        geo = [window_geometry(bars[lo] * Q16, (n - bars[lo] - bars[lo + 2]) * Q16, n) for bars in (rb, db)]
+        scale.append(geo[1][1] / geo[0][1])
+        offset.append(geo[1][0] - geo[0][0])
+    steps = (1 << int(hshift), 1 << int(vshift), 1 << int(hshift), 1 << int(vshift))
+    crop = [-(-max(r, d) // st) * st for r, d, st in zip(rb, db, steps)]
+    if mismatch:
+        crop, reason = [0, 0, 0, 0], "windows differ"
+    elif not any(crop):
+        reason = "no bars"
+    elif width - crop[0] - crop[2] < min_size or height - crop[1] - crop[3] < min_size:
+        reason = "window too small"
+    else:
+        reason = None
+    return {"crop": crop, "same": bool(same), "mismatch": bool(mismatch), "scale": scale, "offset": offset, "reason": reason}

@@ -488,5 +488,18 @@ hipError_t launch_colour_moments(hipStream_t stream, Elem elem, int bit_depth, i
 hipError_t launch_colour_apply(hipStream_t stream, Elem elem, int bit_depth, int hshift, int vshift, const int32_t m[12],
                                const PlaneRun src[3], const MutPlaneRun dst[3], int n_frames, int w, int h);
 
+// ---- active-picture detection: row and column profiles (line_profiles.hip) ---------------------------------------------------
+// out[f][y][0 / 1] = sum / sum of squares of row y, then out[f][h + x][0 / 1] of column x, exact uint64, for n_frames planes
+// of w x h samples (1 ... 8192 each way; frame f at base + f * frame_pitch, pitches in elements; u8 / u16 samples of
+// `bit_depth` bits, a sample above 2^bit_depth - 1 is read as that).  out: device memory of profile_out_bytes(), zeroed by
+// the launch.  A workgroup reads a stripe of kProfStripe columns by a band of kProfBand rows once for both profiles.
+constexpr int kProfStripe = 1024;   // columns of a workgroup: 64 lanes of 16
+constexpr int kProfBand = 64;       // rows of a workgroup: 16 a wave
+constexpr int kProfChunk = 8;       // frames per launch of the two entries
+size_t profile_out_bytes(int w, int h, int n_frames);
+int profile_flush_rows(int bit_depth);   // rows between two widenings of a lane's uint32 column sums
+hipError_t launch_line_profiles(hipStream_t stream, Elem elem, int bit_depth, const void* base, int64_t row_pitch,
+                                int64_t frame_pitch, int n_frames, int w, int h, unsigned long long* out);
+
 }  // namespace pqa
 

@@ -1,5 +1,5 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the registration moments, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
+// temporal / spatial / level alignment, the resampler, the registration moments, the line profiles, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
 // entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
@@ -306,6 +306,19 @@ void cl_pack(const pqa_ctx* c, const ClLayout& L, uint8_t* pin, const void* cons
     for (int p = 0; p < 3; ++p)
       copy_plane_rows(pin + (size_t)f * L.bytes + L.off[p], L.pitch[p], (const uint8_t*)frames[(size_t)f * 3 + p], strides[p],
                       (size_t)c->pw[p] * c->esize, c->ph[p]);
+}
+
+// ---- active-picture detection (line_profiles.hip): argument rules (no device call) -----------------------------------------
+int pr_check(pqa_ctx* c, const pqa_profile_spec* sp, const void* planes, int32_t n_frames, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!sp) return fail(c, PQA_EINVAL, "line_profiles: null spec");
+  if (sp->struct_size != sizeof(pqa_profile_spec)) return fail(c, PQA_EINVAL, "line_profiles: bad struct_size %u", sp->struct_size);
+  for (uint32_t v : {sp->width, sp->height})
+    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "line_profiles: plane size %u outside 1 ... 8192", v);
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "line_profiles: negative frame count");
+  if (n_frames > 0 && !planes) return fail(c, PQA_EINVAL, "line_profiles: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "line_profiles: null output pointer");
+  return PQA_OK;
 }
 
 }  // namespace
@@ -836,6 +849,67 @@ int pqa_flow_moments(pqa_ctx* c, const pqa_flow_spec* spec, const void* const* r
                               c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, tile, dev_out + (size_t)f0 * per_frame);
   }
   return side_finish(c, "flow_moments", e, out, dev_out, flow_out_bytes(w, h, tile, n_frames));
+}
+
+// ---- active-picture detection (line_profiles.hip) ------------------------------------------------------------------------
+
+int pqa_line_profiles_device(pqa_ctx* c, const pqa_profile_spec* spec, const void* planes, int64_t row_pitch, int64_t frame_pitch,
+                             int32_t n_frames, uint64_t* out) {
+  int rc = pr_check(c, spec, planes, n_frames, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
+  rc = check_device_clip(c, "line_profiles: ", row_pitch, frame_pitch, (int64_t)w * es);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = profile_out_bytes(w, h, n_frames), per_frame = profile_out_bytes(w, h, 1) / sizeof(uint64_t);
+  rc = side_reserve(c, SIDE_PROF_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_PROF_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kProfChunk)
+    e = launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)planes + (int64_t)f0 * frame_pitch,
+                             row_pitch / es, frame_pitch / es, chunk_len(n_frames, f0, kProfChunk), w, h, dev_out + (size_t)f0 * per_frame);
+  return side_finish(c, "line_profiles", e, out, dev_out, bytes);
+}
+
+int pqa_line_profiles(pqa_ctx* c, const pqa_profile_spec* spec, const void* const* frames, int64_t row_stride, int32_t n_frames,
+                      uint64_t* out) {
+  int rc = pr_check(c, spec, frames, n_frames, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
+  const size_t row_bytes = (size_t)w * es;
+  rc = check_host_frames(c, "line_profiles: ", "", frames, 1, n_frames, row_stride, row_bytes, true);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // The planes are the call's own size, so they travel as pqa_flow_moments' do: chunks of kProfChunk planes through the first
+  // grow-only pinned buffer of pqa_resample into a device buffer of this entry, rows 16 bytes apart at least, so the kernel
+  // takes its wide loads.  Every chunk's kernel writes its profiles behind the previous chunk's; they come back once.  The
+  // pinned buffer is packed again only after the stream has drained the chunk before: the entry is short, it is not pipelined.
+  const int64_t pitch = round_up((int64_t)row_bytes, 16);
+  const size_t fb = (size_t)pitch * h;
+  const int chunk = n_frames < kProfChunk ? n_frames : kProfChunk;
+  const size_t bytes = profile_out_bytes(w, h, n_frames), per_frame = profile_out_bytes(w, h, 1) / sizeof(uint64_t);
+  rc = rs_pin_reserve(c, 0, fb * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_PROF_SRC, fb * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_PROF_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_PROF_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kProfChunk) {
+    const int n = chunk_len(n_frames, f0, kProfChunk);
+    if (f0 > 0) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) break;
+    for (int f = 0; f < n; ++f) copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)frames[f0 + f], row_stride, row_bytes, h);
+    e = hipMemcpyAsync(c->side_buf[SIDE_PROF_SRC], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_PROF_SRC], pitch / es, (int64_t)(fb / es), n,
+                               w, h, dev_out + (size_t)f0 * per_frame);
+  }
+  return side_finish(c, "line_profiles", e, out, dev_out, bytes);
 }
 
 // ---- colour-matrix alignment (colour_moments.hip) ------------------------------------------------------------------------

@@ -486,6 +486,44 @@ class FeatureEngine:
                                                      dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
         return out
 
+    # -- active-picture detection --------------------------------------------------------------
+    @staticmethod
+    def _profile_spec(shape):
+        sp = N.PqaProfileSpec()
+        sp.struct_size = C.sizeof(N.PqaProfileSpec)
+        sp.height, sp.width = (max(0, int(v)) for v in (shape[0], shape[1]))
+        return sp
+
+    @staticmethod
+    def _profile_split(out, sp):
+        return out[:, :sp.height], out[:, sp.height:]
+
+    def line_profiles(self, frames, shape=None):
+        """(rows [n, H, 2], cols [n, W, 2]) uint64: per row and per column of every plane the sum of its samples and the sum
+        of their squares, exact (pqa_line_profiles; definition: include/pqa_vmaf.h).  Planes in HOST memory: a list of 2-D
+        arrays (views are fine) of `shape` = (height, width), default the first frame's, which need not be this context's
+        (1 ... 8192 each way); samples of this context's bit depth.  align.active_picture reads the result."""
+        n = len(frames)
+        if shape is None:
+            shape = np.shape(frames[0]) if n else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError("line_profiles needs 2-D planes")
+        sp = self._profile_spec(shape)
+        out = np.zeros((n, sp.height + sp.width, 2), np.uint64)
+        keep, ptrs, stride = self._luma_list(frames, "profile", tuple(int(v) for v in shape))
+        self._check(self.lib.pqa_line_profiles(self._ctx, C.byref(sp), ptrs, stride, n, out.ctypes.data))
+        del keep
+        return self._profile_split(out, sp)
+
+    def line_profiles_resident(self, ptr: int, row_pitch: int, frame_pitch: int, shape, n_frames: int):
+        """The same for n_frames planes of `shape` = (height, width) in HBM (device pointer, pitches in bytes;
+        pqa_line_profiles_device)."""
+        sp = self._profile_spec(shape)
+        out = np.zeros((max(int(n_frames), 0), sp.height + sp.width, 2), np.uint64)
+        self._check(self.lib.pqa_line_profiles_device(self._ctx, C.byref(sp), ptr, row_pitch, frame_pitch, int(n_frames),
+                                                      out.ctypes.data))
+        return self._profile_split(out, sp)
+
     # -- colour-matrix alignment ---------------------------------------------------------------
     def _frame_list(self, frames, what: str):
         """(arrays kept alive, ctypes pointer array [n * 3], stride triple) of frames [Y, U, V] in host memory: packed copies

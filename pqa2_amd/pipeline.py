@@ -36,7 +36,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8,
                 resize: str | None = None, register: str | None = None, register_frames: int = 8,
                 register_min_px: float = 1.0 / 16, colour_align: str | None = None, colour_frames: int = 8,
-                colour_full_range: bool | None = None) -> ScoreResult | None:
+                colour_full_range: bool | None = None, active_picture: str | None = None, active_frames: int = 8,
+                active_limit: int = 24, active_skip: int = 0) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -108,7 +109,22 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     "apply", when `mismatch` and `cross_plane` hold and the inverse of the chosen map fits the Q14 matrix of pqa_colour_apply
     (`correction`: its 12 integers, else null), maps every captured frame through that inverse on the GPU before it is scored;
     `applied` says so.  Without `cross_plane` the planes are not coupled and `level_align` is the tool.  A monochrome clip is
-    an error.  `colour_align` = None: no measurement."""
+    an error.  `colour_align` = None: no measurement.
+    `active_picture` = "report" or "apply": before the spatial step (after `resize` and the temporal search, on the pairs it
+    found), the black bars of both clips are measured on the luma of `active_frames` frames spread evenly over the common
+    range: row and column sums (pqa_line_profiles) reduced by align.active_picture -- a line is dark in a frame when its
+    mean does not exceed `active_limit` (in 8-bit code values, 0 ... 255), a bar is a run of lines from an edge that are dark
+    in every frame that is not black altogether, the outermost `active_skip` lines of an edge counting as dark whatever they
+    hold; columns are judged on the active rows only, from a second pass over row-sliced views.  `alignment["active_picture"]`
+    holds {reference, distorted, crop, same, mismatch, scale, offset, applied, reason, frames, limit}: `reference` /
+    `distorted` = {left, top, right, bottom, window, frames_used, all_dark, bar_noise} of each clip, the rest from
+    align.common_window -- `crop` = [left, top, right, bottom], per side the larger bar rounded up to the chroma step;
+    `mismatch` when a side differs by more than 16 lines (`scale` and `offset` of the two windows then say what `register`
+    or `resize` would have to undo; nothing is cropped); `reason` = null, "no bars", "all dark", "windows differ" or "window
+    too small".  "report" changes nothing else: the records are those of a run without the option.  "apply", when `reason`
+    is null, cuts both clips to the common rectangle; every later step and the scoring see the cropped clips, and `applied`
+    says so.  Bars that are not black, that fade or move, and a scaled picture are not modelled.  `active_picture` = None:
+    no measurement."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -137,6 +153,23 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                                     engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
         k = alignment["offset_frames"]
         ref_rd, dis_rd = _ShiftedReader(ref_rd, max(0, -k)), _ShiftedReader(dis_rd, max(0, k))
+    if active_picture is not None:
+        if active_picture not in ("report", "apply"):
+            raise ValueError('active_picture must be None, "report" or "apply"')
+        if active_frames is None or active_frames < 1:
+            raise ValueError("active_frames must be positive")
+        if active_limit is None or not 0 <= active_limit <= 255:
+            raise ValueError("active_limit must be 0 ... 255")
+        if active_skip is None or active_skip < 0:
+            raise ValueError("active_skip must not be negative")
+        active = _find_active(ref_rd, dis_rd, int(active_frames), int(active_limit), int(active_skip), active_picture == "apply",
+                              device, engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+        alignment = dict(alignment or {}, active_picture=active)
+        if active["applied"]:
+            left, top, right, bottom = active["crop"]
+            cw, ch = ri.width - left - right, ri.height - top - bottom
+            ref_rd, dis_rd = _CroppedReader(ref_rd, left, top, cw, ch), _CroppedReader(dis_rd, left, top, cw, ch)
+            ri, di = ref_rd.info, dis_rd.info
     if spatial_align:
         if spatial_align < 0 or spatial_align > 16:
             raise ValueError("spatial_align must be 0 ... 16 pixels")
@@ -632,6 +665,39 @@ def _find_colour(ref_rd, dis_rd, n_frames: int, apply: bool, full_range: bool, d
     col["correction"] = None if fix is None else [int(v) for v in fix]
     col["applied"] = bool(apply and fix is not None)
     return col
+
+
+def _find_active(ref_rd, dis_rd, n_frames: int, limit: int, skip: int, apply: bool, device, make) -> dict:
+    """the `active_picture` object of two opened, paired clips of one size: the line profiles of a few luma planes of each on a
+    small context of its own, reduced by align.active_picture and align.common_window"""
+    from . import align as AL
+    ri = ref_rd.info
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError("no frames to align")
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
+               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+    try:
+        found = []
+        for rd in (ref_rd, dis_rd):
+            lumas = [rd.frame(i)[0] for i in idx]
+            rows, cols = eng.line_profiles(lumas)
+            # the columns of the active rows only: a second pass over row-sliced views, made when there are bar rows
+            found.append(AL.active_picture(rows, lambda t, b: cols if t == 0 and b == 0 else
+                                           eng.line_profiles([y[t:ri.height - b] for y in lumas])[1],
+                                           ri.bit_depth, limit=limit, skip=skip))
+    finally:
+        eng.close()
+    hs, vs = (0, 0) if ri.mono else (ri.hshift, ri.vshift)
+    out = AL.common_window(found[0], found[1], ri.width, ri.height, hs, vs)
+    for key in ("scale", "offset"):
+        out[key] = None if out[key] is None else [float(v) for v in out[key]]
+    for key, ap in zip(("reference", "distorted"), found):
+        out[key] = dict(ap, bar_noise=None if ap["bar_noise"] is None else float(ap["bar_noise"]))
+    out["applied"] = bool(apply and out["reason"] is None)
+    out["frames"] = len(idx)
+    out["limit"] = limit
+    return out
 
 
 def spatial_sample(n: int, count: int):

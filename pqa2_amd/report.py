@@ -157,6 +157,23 @@ def geometry_summary_line(geometry: dict) -> str:
             f"{geometry.get('iterations', 0)} iterations on {geometry.get('frames', 0)} frames, {what}")
 
 
+def active_summary_line(active: dict) -> str:
+    """One line for a summary or a status bar: the bars found in both clips and whether the clips were cropped."""
+    def bars(ap):
+        if ap.get("all_dark"):
+            return "all dark"
+        return "{}/{}/{}/{}".format(*(ap.get(k, 0) for k in ("left", "top", "right", "bottom")))
+    crop = active.get("crop", [0, 0, 0, 0])
+    if active.get("applied"):
+        what = f"clips cropped by {crop[0]}/{crop[1]}/{crop[2]}/{crop[3]} px"
+    elif active.get("reason"):
+        what = f"{active['reason']}: nothing cropped"
+    else:
+        what = f"common margins {crop[0]}/{crop[1]}/{crop[2]}/{crop[3]} px, not cropped"
+    return (f"Active picture: bars (left/top/right/bottom) reference {bars(active.get('reference', {}))}, capture "
+            f"{bars(active.get('distorted', {}))} on {active.get('frames', 0)} frames, {what}")
+
+
 def colour_summary_line(colour: dict) -> str:
     """One line for a summary or a status bar: the colour map found, its error and whether it was undone."""
     if colour.get("degenerate"):

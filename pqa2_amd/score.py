@@ -110,6 +110,19 @@ def main(argv=None) -> int:
                     help="--colour-align, and undo a matrix found on the GPU before scoring")
     ap.add_argument("--colour-frames", type=int, default=8, metavar="N",
                     help="with --colour-align / --colour-correct: measure N frame pairs spread evenly over the clips (default 8)")
+    ap.add_argument("--active-picture", action="store_true",
+                    help="measure the black bars (letterbox, pillarbox) of both clips from the row and column sums of a few "
+                         "luma planes; the JSON's alignment object gets an active_picture entry")
+    ap.add_argument("--active-crop", action="store_true",
+                    help="--active-picture, and score both clips cropped to the common active rectangle when their bars agree")
+    ap.add_argument("--active-frames", type=int, default=8, metavar="N",
+                    help="with --active-picture / --active-crop: measure N frames of each clip spread evenly over it (default 8)")
+    ap.add_argument("--active-limit", type=int, default=24, metavar="V",
+                    help="with --active-picture / --active-crop: a line is dark when its mean does not exceed V in 8-bit code "
+                         "values (default 24)")
+    ap.add_argument("--active-skip", type=int, default=0, metavar="N",
+                    help="with --active-picture / --active-crop: the outermost N lines of every edge count as dark whatever "
+                         "they hold (a caption or timecode line; default 0)")
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
@@ -168,6 +181,9 @@ def main(argv=None) -> int:
                              if (a.level_align or a.level_correct) else {}),
                           **({"colour_align": "apply" if a.colour_correct else "report", "colour_frames": a.colour_frames}
                              if (a.colour_align or a.colour_correct) else {}),
+                          **({"active_picture": "apply" if a.active_crop else "report", "active_frames": a.active_frames,
+                              "active_limit": a.active_limit, "active_skip": a.active_skip}
+                             if (a.active_picture or a.active_crop) else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
@@ -200,6 +216,8 @@ def main(argv=None) -> int:
                 f.write("\n".join(res["ssim_lines"]) + "\n")
         if res.get("alignment") and "offset_frames" in res["alignment"]:
             print(report.alignment_summary_line(res["alignment"]), file=sys.stderr, flush=True)
+        if res.get("alignment") and res["alignment"].get("active_picture"):
+            print(report.active_summary_line(res["alignment"]["active_picture"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("spatial"):
             print(report.spatial_summary_line(res["alignment"]["spatial"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("levels"):

@@ -167,6 +167,8 @@ class VMAFAnalyzer(QObject):
         self.level_correct_enabled = False    # ... and undo it (implies the measurement; pipeline.score_files(level_align=))
         self.colour_align_enabled = False     # colour-matrix alignment before scoring: measure the capture's 3 x 4 colour map
         self.colour_correct_enabled = False   # ... and undo it (implies the measurement; pipeline.score_files(colour_align=))
+        self.active_picture_enabled = False   # active-picture detection before scoring: measure the black bars of both clips
+        self.active_crop_enabled = False      # ... and crop both to the common rectangle (implies the measurement; score_files(active_picture=))
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -223,6 +225,10 @@ class VMAFAnalyzer(QObject):
                 self.colour_align_enabled = bool(s["colour_align_enabled"])
             if "colour_correct_enabled" in s:
                 self.colour_correct_enabled = bool(s["colour_correct_enabled"])
+            if "active_picture_enabled" in s:
+                self.active_picture_enabled = bool(s["active_picture_enabled"])
+            if "active_crop_enabled" in s:
+                self.active_crop_enabled = bool(s["active_crop_enabled"])
 
     set_options_manager = set_options_from_manager
 
@@ -241,7 +247,8 @@ class VMAFAnalyzer(QObject):
                              siti_enabled=False, integrity_enabled=False, integrity_options=None,
                              align_enabled=False, align_max_offset=8, spatial_align_enabled=False,
                              spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False,
-                             colour_align_enabled=False, colour_correct_enabled=False):
+                             colour_align_enabled=False, colour_correct_enabled=False, active_picture_enabled=False,
+                             active_crop_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -266,6 +273,8 @@ class VMAFAnalyzer(QObject):
         self.level_correct_enabled = bool(level_correct_enabled)
         self.colour_align_enabled = bool(colour_align_enabled)
         self.colour_correct_enabled = bool(colour_correct_enabled)
+        self.active_picture_enabled = bool(active_picture_enabled)
+        self.active_crop_enabled = bool(active_crop_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -478,6 +487,8 @@ class VMAFAnalyzer(QObject):
                    if (self.level_align_enabled or self.level_correct_enabled) else {}),
                 **({"colour_align": "apply" if self.colour_correct_enabled else "report"}
                    if (self.colour_align_enabled or self.colour_correct_enabled) else {}),
+                **({"active_picture": "apply" if self.active_crop_enabled else "report"}
+                   if (self.active_picture_enabled or self.active_crop_enabled) else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {})}
 
@@ -524,6 +535,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--colour-correct"]
         elif self.colour_align_enabled:
             cmd += ["--colour-align"]
+        if self.active_crop_enabled:
+            cmd += ["--active-crop"]
+        elif self.active_picture_enabled:
+            cmd += ["--active-picture"]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -644,11 +659,18 @@ class VMAFAnalyzer(QObject):
                 results["integrity_log"] = self._integrity_path
             if (self.align_enabled or self.spatial_align_enabled or self.level_align_enabled
                     or self.level_correct_enabled or self.register_filter or self.colour_align_enabled
-                    or self.colour_correct_enabled):   # how the clips were paired, from the log's top level
+                    or self.colour_correct_enabled or self.active_picture_enabled
+                    or self.active_crop_enabled):   # how the clips were paired, from the log's top level
                 from . import report
                 results["alignment"] = vmaf_data.get("alignment")
                 if results["alignment"] and "offset_frames" in results["alignment"]:
                     self.status_update.emit(report.alignment_summary_line(results["alignment"]))
+                if results["alignment"] and results["alignment"].get("active_picture"):
+                    active = results["alignment"]["active_picture"]
+                    self.status_update.emit(report.active_summary_line(active))
+                    if active.get("applied"):   # the clips were scored without their bars: report the scored size
+                        left, top, right, bottom = active["crop"]
+                        results["width"], results["height"] = width - left - right, height - top - bottom
                 if results["alignment"] and results["alignment"].get("spatial"):
                     self.status_update.emit(report.spatial_summary_line(results["alignment"]["spatial"]))
                 if results["alignment"] and results["alignment"].get("levels"):
