@@ -614,6 +614,35 @@ PQA_API int pqa_line_profiles(pqa_ctx* ctx, const pqa_profile_spec* spec, const 
 PQA_API int pqa_line_profiles_device(pqa_ctx* ctx, const pqa_profile_spec* spec, const void* planes, int64_t row_pitch,
                                      int64_t frame_pitch, int32_t n_frames, uint64_t* out);
 
+/* Distortion map: the tile-wise second-order statistics of n_frames frame pairs of one plane, synchronously -- what
+ * pqa2_amd/distortion.py turns into a tile PSNR, a block SSIM, a list of localised defects and of persistent regions (a
+ * burnt-in logo or clock).  Planes of width x height samples (the spec's, independent of the context's width and height;
+ * each 1 ... 8192), u8 in an 8-bit context, otherwise u16 of the context's bit depth b (a sample above 2^b - 1 is read as
+ * 2^b - 1).  With r = ref, d = dis, tile (i, j) of size T = tile (8, 16, 32 or 64) owns the pixels with x / T = i,
+ * y / T = j; the grid is tx = ceil(W / T) by ty = ceil(H / T), edge tiles hold the pixels that exist, and
+ *     out[f][j][i][0..5] = sum r, sum d, sum r^2, sum d^2, sum r d, sum |d - r|
+ * Exact uint64, no floating point anywhere; the squared error of a tile is sum r^2 - 2 sum r d + sum d^2.  out (host) is
+ * [n_frames][ty][tx][6].  Any context, no feature bit; buffers are made on first use, grow only and are freed with the
+ * context.  Independent of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL, before any
+ * device call, on a null pointer, a bad struct_size, a tile other than 8 / 16 / 32 / 64, a size outside 1 ... 8192, a row
+ * pitch that is negative, shorter than a row or no multiple of the sample size, or a negative frame count.  n_frames == 0
+ * succeeds and writes nothing.  Kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_tile_moments: frames in HOST memory (ref_frames[f] / dis_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample.
+ * pqa_tile_moments_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+typedef struct pqa_tile_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane, 1 ... 8192 */
+  uint32_t tile;          /* 8, 16, 32 or 64 */
+} pqa_tile_spec;
+PQA_API int pqa_tile_moments(pqa_ctx* ctx, const pqa_tile_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                             const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out);
+PQA_API int pqa_tile_moments_device(pqa_ctx* ctx, const pqa_tile_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                    int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                    int32_t n_frames, uint64_t* out);
+
 /* Colour-matrix alignment: the cross-plane moments of n_frames frame pairs, synchronously -- what a capture chain that decodes
  * Y'CbCr with one matrix and encodes with another (BT.709 through a BT.601 leg) leaves behind, which no single-plane
  * measurement sees.  Works on the chroma grid of the context: chroma_shift = (hs, vs), s = 2^(hs + vs), chroma planes of

@@ -501,5 +501,21 @@ int profile_flush_rows(int bit_depth);   // rows between two widenings of a lane
 hipError_t launch_line_profiles(hipStream_t stream, Elem elem, int bit_depth, const void* base, int64_t row_pitch,
                                 int64_t frame_pitch, int n_frames, int w, int h, unsigned long long* out);
 
+// ---- distortion map: tile-wise second-order statistics of a frame pair (tile_moments.hip) ------------------------------------
+// out[f][j][i][0..5] = sum r, sum d, sum r^2, sum d^2, sum r d, sum |d - r| over the pixels of tile (i, j) of `tile` x `tile`
+// pixels (8, 16, 32 or 64; edge tiles hold the pixels that exist), exact uint64, for n_frames plane pairs of w x h samples
+// (1 ... 8192 each way; frame f at base + f * frame_pitch, pitches in elements; u8 / u16 samples of `bits` bits, a sample above
+// 2^bits - 1 is read as that).  out: device memory of tile_out_bytes(); every word is written, nothing needs zeroing.
+constexpr int kTileSums = 6;    // sums a tile
+constexpr int kTileChunk = 8;   // frame pairs per launch of the two entries
+bool tile_size_ok(int tile);
+size_t tile_out_bytes(int w, int h, int tile, int n_frames);
+// bytes of one load (16, 4 or esize) the launch takes for these base addresses and pitches (in elements)
+int tile_load_bytes(int esize, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
+                    int64_t dis_row_pitch, int64_t dis_frame_pitch);
+hipError_t launch_tile_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
+                               int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                               int n_frames, int w, int h, int tile, unsigned long long* out);
+
 }  // namespace pqa
 

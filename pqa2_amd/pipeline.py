@@ -37,7 +37,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 resize: str | None = None, register: str | None = None, register_frames: int = 8,
                 register_min_px: float = 1.0 / 16, colour_align: str | None = None, colour_frames: int = 8,
                 colour_full_range: bool | None = None, active_picture: str | None = None, active_frames: int = 8,
-                active_limit: int = 24, active_skip: int = 0) -> ScoreResult | None:
+                active_limit: int = 24, active_skip: int = 0, distortion_map: int = 0, distortion_planes: str = "y",
+                distortion_dir: str | None = None, distortion_factor=16,
+                distortion_min_mse: float = 4.0) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -124,7 +126,23 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     too small".  "report" changes nothing else: the records are those of a run without the option.  "apply", when `reason`
     is null, cuts both clips to the common rectangle; every later step and the scoring see the cropped clips, and `applied`
     says so.  Bars that are not black, that fade or move, and a scaled picture are not modelled.  `active_picture` = None:
-    no measurement."""
+    no measurement.
+    `distortion_map` = T (8, 16, 32 or 64): a distortion map of the scored clips -- WHERE inside the frame they differ.  After
+    every alignment step, on exactly the readers the scoring loop sees, a second pass reads every frame pair of this rank's
+    shard in chunks of 8 through a context of its own and takes the exact second-order sums of every T x T tile
+    (pqa_tile_moments) of the luma (`distortion_planes` = "y") or of all three planes ("all"; a monochrome clip is an error).
+    The pass reads and uploads both clips a SECOND time: that, and two to three and a half luma PSNR passes a plane, is its
+    cost (README).
+    Only the clip-summed moments and the tile SSE of every frame are kept; sharded runs gather the SSE with the records'
+    transport and rank 0 runs the solver (pqa2_amd/distortion.py) on the whole clip.  `res["distortion"]` holds {tile, grid,
+    planes: {y | cb | cr: {grid, defects, persistent, psnr_all, psnr_excluding, concentration_mean, tile_psnr_min_mean,
+    worst_frame}}, frames}: `defects` the localised events of distortion.find_defects (a tile is hot when its MSE exceeds
+    `distortion_min_mse` in 8-bit code values squared and `distortion_factor` times the frame's median tile MSE), `persistent`
+    the regions hot in at least 9 of 10 frames (a burnt-in logo or clock) with the clip PSNR with (`psnr_all`) and without
+    them (`psnr_excluding`).  The luma adds the per-frame metric columns `tile_psnr_min` and `distortion_concentration`.
+    With `distortion_dir` rank 0 writes distortion_<plane>.pgm (distortion.heatmap_pgm of the clip-mean tile PSNR) and
+    distortion_<plane>.npy (the clip-summed moments, uint64 [ty, tx, 6]) there.  `distortion_map` = 0: nothing is measured and
+    every output is what it was."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -227,6 +245,15 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
+    if distortion_map:
+        if distortion_map not in N.FLOW_TILES:
+            raise ValueError("distortion_map must be 0 or a tile size of 8, 16, 32 or 64")
+        if distortion_planes not in ("y", "all"):
+            raise ValueError('distortion_planes must be "y" or "all"')
+        if distortion_planes == "all" and ri.mono:
+            raise ValueError('distortion_planes="all" needs the chroma planes, but the clips are monochrome')
+        if distortion_factor is None or distortion_factor < 0 or distortion_min_mse is None or distortion_min_mse < 0:
+            raise ValueError("distortion_factor and distortion_min_mse must not be negative")
     if cambi_full_ref and not cambi:
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
@@ -325,6 +352,11 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         eng.close()
         raise
     (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
+    dmap = None
+    if distortion_map:      # a pass of its own over the same readers, after the scoring context is parked
+        dmap = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
+                                engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
+                                gather_device, cancelled)
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
@@ -381,6 +413,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         extra.update(integrity=ig_result)
     res = finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
                          fps=n / elapsed if elapsed > 0 else 0.0, **extra)
+    if dmap is not None:
+        _distortion_result(res, dmap, ri, int(distortion_map), distortion_factor, distortion_min_mse, distortion_dir)
     if alignment is not None:
         res["alignment"] = alignment
     if resized is not None:
@@ -698,6 +732,68 @@ def _find_active(ref_rd, dis_rd, n_frames: int, limit: int, skip: int, apply: bo
     out["frames"] = len(idx)
     out["limit"] = limit
     return out
+
+
+DISTORTION_PLANES = ("y", "cb", "cr")
+
+
+def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes: int, device, make, world_size: int,
+                     rank: int, gather_device, cancelled=None):
+    """the measurement of score_files(distortion_map=): per plane (tile SSE of every frame of the clip, uint64 [n, ty, tx];
+    clip-summed moments, uint64 [ty, tx, 6]), on every rank.  This rank measures its frames [a, b) in chunks of 8 pairs on
+    a small context of its own; the ranks' rows travel as the records do (shard.gather_records: the int64 transport carries
+    uint64 bit-exactly), their summed moments as one row a rank."""
+    from . import distortion as DM
+    ri = ref_rd.info
+    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (n_planes - 1)
+    grids = [DM.tile_counts(w, h, tile).shape for w, h in sizes]
+    sse = [np.zeros((b - a,) + g, np.uint64) for g in grids]
+    sums = [np.zeros(g + (N.TILE_SUMS,), np.uint64) for g in grids]
+    if b > a:
+        eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
+                   features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        try:
+            for i0 in range(a, b, N.TILE_CHUNK):
+                if cancelled is not None and cancelled():
+                    raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
+                idx = range(i0, min(b, i0 + N.TILE_CHUNK))
+                rf, df = [ref_rd.frame(i) for i in idx], [dis_rd.frame(i) for i in idx]
+                for p in range(n_planes):
+                    M = eng.tile_moments([f[p] for f in rf], [f[p] for f in df], tile)
+                    sums[p] += M.sum(axis=0, dtype=np.uint64)
+                    sse[p][i0 - a:i0 - a + len(idx)] = DM.tile_sse(M)
+        finally:
+            eng.close()
+    out = []
+    for p, g in enumerate(grids):
+        cells = g[0] * g[1]
+        S = shard.gather_records(sse[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
+        T = shard.gather_records(sums[p].reshape(1, cells * N.TILE_SUMS).view(np.float64), world_size, world_size, rank,
+                                 gather_device, width=cells * N.TILE_SUMS)
+        out.append((np.ascontiguousarray(S).view(np.uint64).reshape((n,) + g),
+                    np.ascontiguousarray(T).view(np.uint64).sum(axis=0, dtype=np.uint64).reshape(g + (N.TILE_SUMS,))))
+    return out
+
+
+def _distortion_result(res, dmap, info, tile: int, factor, min_mse, out_dir) -> None:
+    """rank 0: the solver on the gathered measurement; adds res["distortion"], the two luma columns and the files"""
+    from . import distortion as DM
+    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(dmap) - 1)
+    planes = {}
+    for name, (S, M_sum), (w, h) in zip(DISTORTION_PLANES, dmap, sizes):
+        found = DM.analyse_plane(S, M_sum, w, h, tile, info.bit_depth, factor=factor, min_mse=min_mse)
+        cols, mean_psnr = found.pop("columns"), found.pop("mean_psnr")
+        planes[name] = found
+        if name == "y":
+            keep = np.asarray(res["frame_indices"])
+            res["metrics"]["tile_psnr_min"] = cols["tile_psnr_min"][keep]
+            res["metrics"]["distortion_concentration"] = cols["concentration"][keep]
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, f"distortion_{name}.pgm"), "wb") as f:
+                f.write(DM.heatmap_pgm(mean_psnr))
+            np.save(os.path.join(out_dir, f"distortion_{name}.npy"), M_sum)
+    res["distortion"] = {"tile": tile, "grid": planes["y"]["grid"], "planes": planes, "frames": int(dmap[0][0].shape[0])}
 
 
 def spatial_sample(n: int, count: int):

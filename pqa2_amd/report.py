@@ -174,6 +174,35 @@ def active_summary_line(active: dict) -> str:
             f"{bars(active.get('distorted', {}))} on {active.get('frames', 0)} frames, {what}")
 
 
+def distortion_log_keys(distortion: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the distortion map's findings (pipeline.score_files(distortion_map=T)); none
+    without them.  Any float that is not finite becomes null."""
+    if not distortion:
+        return {}
+    def finite_deep(v):
+        if isinstance(v, dict):
+            return {k: finite_deep(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [finite_deep(x) for x in v]
+        if isinstance(v, (np.integer, np.floating)):
+            v = v.item()
+        return None if isinstance(v, float) and not np.isfinite(v) else v
+    return {"distortion": finite_deep(distortion)}
+
+
+def distortion_summary_line(distortion: dict) -> str:
+    """One line for a summary or a status bar: the defects and persistent regions found in the luma."""
+    y = distortion.get("planes", {}).get("y", {})
+    worst = y.get("worst_frame") or {}
+    line = (f"Distortion map: {distortion.get('tile', 0)} px tiles on {distortion.get('frames', 0)} frames, "
+            f"{len(y.get('defects', []))} localised defects, {len(y.get('persistent', []))} persistent regions")
+    if y.get("persistent") and y.get("psnr_all") is not None and y.get("psnr_excluding") is not None:
+        line += f" (PSNR {y['psnr_all']:.2f} dB, {y['psnr_excluding']:.2f} dB without them)"
+    if worst:
+        line += f", worst tile {worst.get('tile_psnr_min', 0.0):.2f} dB in frame {worst.get('frame', 0)}"
+    return line
+
+
 def colour_summary_line(colour: dict) -> str:
     """One line for a summary or a status bar: the colour map found, its error and whether it was undone."""
     if colour.get("degenerate"):

@@ -123,6 +123,19 @@ def main(argv=None) -> int:
     ap.add_argument("--active-skip", type=int, default=0, metavar="N",
                     help="with --active-picture / --active-crop: the outermost N lines of every edge count as dark whatever "
                          "they hold (a caption or timecode line; default 0)")
+    ap.add_argument("--distortion-map", type=int, default=0, metavar="T", choices=[0, 8, 16, 32, 64],
+                    help="measure WHERE the clips differ: the second-order sums of every T x T tile (8, 16, 32 or 64) of every "
+                         "scored frame pair, in a second pass over both clips; the JSON gets a top-level distortion object "
+                         "(localised defects, persistent regions such as a burnt-in logo) and two per-frame metrics")
+    ap.add_argument("--distortion-planes", default="y", choices=["y", "all"],
+                    help="with --distortion-map: the luma only (default) or all three planes")
+    ap.add_argument("--distortion-dir", default=None, metavar="DIR",
+                    help="with --distortion-map: write distortion_<plane>.pgm (the clip-mean map, one pixel a tile) and "
+                         "distortion_<plane>.npy (the clip-summed tile moments) into DIR")
+    ap.add_argument("--distortion-factor", type=float, default=16, metavar="F",
+                    help="with --distortion-map: a tile is hot when its MSE exceeds F times the frame's median tile MSE (default 16)")
+    ap.add_argument("--distortion-min-mse", type=float, default=4.0, metavar="V",
+                    help="with --distortion-map: ... and V in 8-bit code values squared (default 4)")
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
@@ -184,6 +197,9 @@ def main(argv=None) -> int:
                           **({"active_picture": "apply" if a.active_crop else "report", "active_frames": a.active_frames,
                               "active_limit": a.active_limit, "active_skip": a.active_skip}
                              if (a.active_picture or a.active_crop) else {}),
+                          **({"distortion_map": a.distortion_map, "distortion_planes": a.distortion_planes,
+                              "distortion_dir": a.distortion_dir, "distortion_factor": a.distortion_factor,
+                              "distortion_min_mse": a.distortion_min_mse} if a.distortion_map else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
@@ -200,7 +216,8 @@ def main(argv=None) -> int:
                                     {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
                                      **report.integrity_log_keys(res.get("integrity")),
                                      **report.alignment_log_keys(res.get("alignment")),
-                                     **({"resize": res["resize"]} if res.get("resize") else {})})
+                                     **({"resize": res["resize"]} if res.get("resize") else {}),
+                                     **report.distortion_log_keys(res.get("distortion"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -226,6 +243,8 @@ def main(argv=None) -> int:
             print(report.colour_summary_line(res["alignment"]["colour"]), file=sys.stderr, flush=True)
         if res.get("alignment") and res["alignment"].get("geometry"):
             print(report.geometry_summary_line(res["alignment"]["geometry"]), file=sys.stderr, flush=True)
+        if res.get("distortion"):
+            print(report.distortion_summary_line(res["distortion"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

@@ -169,6 +169,8 @@ class VMAFAnalyzer(QObject):
         self.colour_correct_enabled = False   # ... and undo it (implies the measurement; pipeline.score_files(colour_align=))
         self.active_picture_enabled = False   # active-picture detection before scoring: measure the black bars of both clips
         self.active_crop_enabled = False      # ... and crop both to the common rectangle (implies the measurement; score_files(active_picture=))
+        self.distortion_map_enabled = False   # distortion map: where inside the frame the clips differ (a second pass over both
+        self.distortion_tile = 32             # clips; score_files(distortion_map=)); its tile size: 8, 16, 32 or 64
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -229,6 +231,10 @@ class VMAFAnalyzer(QObject):
                 self.active_picture_enabled = bool(s["active_picture_enabled"])
             if "active_crop_enabled" in s:
                 self.active_crop_enabled = bool(s["active_crop_enabled"])
+            if "distortion_map_enabled" in s:
+                self.distortion_map_enabled = bool(s["distortion_map_enabled"])
+            if "distortion_tile" in s:
+                self.distortion_tile = int(s["distortion_tile"])
 
     set_options_manager = set_options_from_manager
 
@@ -248,7 +254,7 @@ class VMAFAnalyzer(QObject):
                              align_enabled=False, align_max_offset=8, spatial_align_enabled=False,
                              spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False,
                              colour_align_enabled=False, colour_correct_enabled=False, active_picture_enabled=False,
-                             active_crop_enabled=False):
+                             active_crop_enabled=False, distortion_map_enabled=False, distortion_tile=32):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -275,6 +281,8 @@ class VMAFAnalyzer(QObject):
         self.colour_correct_enabled = bool(colour_correct_enabled)
         self.active_picture_enabled = bool(active_picture_enabled)
         self.active_crop_enabled = bool(active_crop_enabled)
+        self.distortion_map_enabled = bool(distortion_map_enabled)
+        self.distortion_tile = int(distortion_tile)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -451,7 +459,8 @@ class VMAFAnalyzer(QObject):
                                     {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
                                      **report.integrity_log_keys(res.get("integrity")),
                                      **report.alignment_log_keys(res.get("alignment")),
-                                     **({"resize": res["resize"]} if res.get("resize") else {})})
+                                     **({"resize": res["resize"]} if res.get("resize") else {}),
+                                     **report.distortion_log_keys(res.get("distortion"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -489,6 +498,7 @@ class VMAFAnalyzer(QObject):
                    if (self.colour_align_enabled or self.colour_correct_enabled) else {}),
                 **({"active_picture": "apply" if self.active_crop_enabled else "report"}
                    if (self.active_picture_enabled or self.active_crop_enabled) else {}),
+                **({"distortion_map": int(self.distortion_tile)} if self.distortion_map_enabled else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {})}
 
@@ -539,6 +549,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--active-crop"]
         elif self.active_picture_enabled:
             cmd += ["--active-picture"]
+        if self.distortion_map_enabled:
+            cmd += ["--distortion-map", str(int(self.distortion_tile))]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -679,6 +691,11 @@ class VMAFAnalyzer(QObject):
                     self.status_update.emit(report.colour_summary_line(results["alignment"]["colour"]))
                 if results["alignment"] and results["alignment"].get("geometry"):
                     self.status_update.emit(report.geometry_summary_line(results["alignment"]["geometry"]))
+            if self.distortion_map_enabled:   # where the clips differ, from the log's top level
+                from . import report
+                results["distortion"] = vmaf_data.get("distortion")
+                if results["distortion"]:
+                    self.status_update.emit(report.distortion_summary_line(results["distortion"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
