@@ -243,22 +243,25 @@ __device__ __forceinline__ void pyramid_march(const PyramidArgs& a, const Loader
   Raw4<T, EDGE> q[4];
   q[0] = ld.load(2 * i0 + 1); q[1] = ld.load(2 * i0 + 2); q[2] = ld.load(2 * i0 + 3); q[3] = ld.load(2 * i0 + 4);
   // prologue: scale-0 rows i0, i0 + 1 (approximation band only) fill the upper half of the first window
-  Row w0, w1, w2, w3;
+  // The scale-1 window is two pairs of rows, u and v: each iteration computes one pair from the other and the two swap
+  // roles, so the loop below is written for two iterations at a time and no window row, pending set or box sum is copied
+  // at its back-edge.
+  Row u0, u1, v0, v1;
   {
     x0 = ld.convert(q[0]); x1 = ld.convert(q[1]);
     q[0] = ld.load(2 * i0 + 5); q[1] = ld.load(2 * i0 + 6);
-    w2 = band_edges(step0(x2, x3, x0, x1, i0, false, false, false));
+    u0 = band_edges(step0(x2, x3, x0, x1, i0, false, false, false));
     x2 = ld.convert(q[2]); x3 = ld.convert(q[3]);
     q[2] = ld.load(2 * i0 + 7); q[3] = ld.load(2 * i0 + 8);
-    w3 = band_edges(step0(x0, x1, x2, x3, i0 + 1, false, false, false));
+    u1 = band_edges(step0(x0, x1, x2, x3, i0 + 1, false, false, false));
   }
   const auto need0 = [&](int i) { return win0 && i >= a.top0 - 1 && i <= a.bottom0 && i >= 2 * R0 - 1 && i <= 2 * R1; };
   const auto accum0 = [&](int i) { return win0 && i >= a.top0 && i < a.bottom0 && i >= 2 * R0 && i < 2 * R1; };
   const auto need1 = [&](int j) { return win1 && j >= a.top1 - 1 && j <= a.bottom1; };
   const auto accum1 = [&](int j) { return win1 && j >= a.top1 && j < a.bottom1 && j >= R0 && j < R1; };
-  for (int j = j_first; j <= j_last; ++j) {
+  // one scale-1 row j: (w0, w1) = scale-0 rows 2j - 1, 2j from the iteration before; (w2, w3) receive rows 2j + 1, 2j + 2
+  const auto iteration = [&](const int j, Row& w0, Row& w1, Row& w2, Row& w3) {
     const int ia = 2 * j + 1, ib = 2 * j + 2;        // the two new scale-0 rows
-    w0 = w2; w1 = w3;
     x0 = ld.convert(q[0]); x1 = ld.convert(q[1]);
     q[0] = ld.load(2 * ia + 5); q[1] = ld.load(2 * ia + 6);          // rows 2 (ia + 2) + 1, + 2: next iteration's first step
     w2 = band_edges(step0(x2, x3, x0, x1, ia, need0(ia), accum0(ia), accum0(ia - 1)));
@@ -269,7 +272,23 @@ __device__ __forceinline__ void pyramid_march(const PyramidArgs& a, const Loader
     if (j == 0) w0 = w2;                             // row -1 <- row 1
     if (ib == a.oh0) w3 = w2;                        // row oh0 <- row oh0 - 1
     step1(w0, w1, w2, w3, j, need1(j), j >= R0 && j < R1, accum1(j), accum1(j - 1));
-    if (((j - j_first) & 3) == 3) flush();
+  };
+  if constexpr (sizeof(T) == 1) {
+    for (int j = j_first; j <= j_last; j += 2) {
+      iteration(j, u0, u1, v0, v1);
+      if (j + 1 <= j_last) {
+        iteration(j + 1, v0, v1, u0, u1);
+        if (((j + 1 - j_first) & 3) == 3) flush();   // (every fourth row: always the second of a pair)
+      }
+    }
+  } else {
+    // 16-bit samples: the prefetch queue is twice as wide, and with two iterations' worth of names the kernel no longer
+    // fits three waves per SIMD without scratch (48 bytes at 168 VGPRs): one iteration per trip, the pairs handed over by copy
+    for (int j = j_first; j <= j_last; ++j) {
+      iteration(j, u0, u1, v0, v1);
+      u0 = v0; u1 = v1;
+      if (((j - j_first) & 3) == 3) flush();
+    }
   }
   flush();
   const bool col1 = inner && c1 >= a.left1 && c1 < a.right1;

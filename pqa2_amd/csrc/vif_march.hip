@@ -115,12 +115,14 @@ struct Pieces {
 struct StatAcc {
   f2 num2, den2, pn, qn, pd;
 };
+// c - a * b as ONE packed fma whose first operand carries the negation as a source modifier
+__device__ __forceinline__ f2 nfma(const f2 a, const f2 b, const f2 c) { return __builtin_elementwise_fma(-a, b, c); }
 template <bool HIGH>
 __device__ __forceinline__ void stat_pair(StatAcc& s, const f2 s1, const f2 mu1, const f2 mu2, const f2 yy, const f2 xy,
                                           const bool v0, const bool v1, const float gain_limit) {
   const float sigma_nsq = 2.0f * 256.0f, eps = 1.0e-10f * 256.0f, sigma_max_inv = 4.0f / (255.0f * 255.0f * 256.0f);
-  f2 s2 = yy - mu2 * mu2;
-  const f2 s12 = xy - mu1 * mu2;
+  f2 s2 = nfma(mu2, mu2, yy);
+  const f2 s12 = nfma(mu1, mu2, xy);
   s2 = f2{fmaxf(s2.x, 0.0f), fmaxf(s2.y, 0.0f)};
   // one compare per pixel ("low" = sigma1_sq < sigma_nsq; every input is a finite filter output, so no NaN case); the
   // branch masks are lane masks in SGPRs, combined with the validity masks by scalar instructions
@@ -408,6 +410,17 @@ __global__ __launch_bounds__(kBlock, PQA_MARCH_OCC) void vif_s0_march_kernel(con
 #pragma unroll
   for (int i = 0; i < 4; ++i) vcol[i] = x0 + 4 * kq + i < a.w;
   const int ow = a.w >> 1, oh = a.h >> 1;
+  // the part of "this block may take the all-high statistic" that does not change over the march, as a scalar
+  const int cols_inside = __builtin_amdgcn_readfirstlane((a.uniform && x0 + 16 <= a.w) ? 1 : 0);
+  // The next scale's planes: a lane writes the same plane (kq < 2: ref), the same four columns from oc and row m of every
+  // block, so its address is formed ONCE, for the segment's first block, and moves by eight rows per block (one 64-bit add;
+  // the two planes may differ in pitch, so the step is the lane's own).  Which lanes store, and whether as one 16-byte
+  // write, is fixed for the march as well; only rows past oh need a look, and only in the image's last block.
+  const int oc = (x0 >> 1) + 4 * (kq & 1);
+  const bool st_lane = m < 8 && oc < ow, st_full = oc + 4 <= ow;
+  float* dst = kq < 2 ? a.dst_ref + (int64_t)fr * a.dst_frame_pitch_r + (int64_t)((ys >> 1) + m) * a.dst_pitch_r + oc
+                      : a.dst_dis + (int64_t)fr * a.dst_frame_pitch_d + (int64_t)((ys >> 1) + m) * a.dst_pitch_d + oc;
+  const uint64_t dst_step = 8u * (uint64_t)(kq < 2 ? a.dst_pitch_r : a.dst_pitch_d);
 
   // ---- pass 2 + next-scale store + statistic for output rows yo .. yo + 15: the window is the pair of blocks in P;
   // FV / FVD = the tap fragments whose K order matches which half holds the OLDER block
@@ -431,13 +444,14 @@ __global__ __launch_bounds__(kBlock, PQA_MARCH_OCC) void vif_s0_march_kernel(con
       Vd = mma(Al, t0, Vd);
     }
     // next scale's input: lanes m < 8 hold 4 consecutive samples of half-resolution row yo / 2 + m
-    if (m < 8) {
-      const int orow = (yo >> 1) + m, oc = (x0 >> 1) + 4 * (kq & 1);
-      if (orow < oh && oc < ow) {
-        float* __restrict__ dst = kq < 2 ? a.dst_ref + (int64_t)fr * a.dst_frame_pitch_r + (int64_t)orow * a.dst_pitch_r + oc
-                                         : a.dst_dis + (int64_t)fr * a.dst_frame_pitch_d + (int64_t)orow * a.dst_pitch_d + oc;
+    // (dst: the lane's address in this block, see where it is formed)
+    {
+      const int rows_left = oh - (yo >> 1);                  // wave-uniform; only the image's last block can have fewer than 8
+      bool st = st_lane;
+      if (rows_left < 8) st = st && m < rows_left;
+      if (st) {
         const f4 o = Vd * f4{1.0f / 256.0f, 1.0f / 256.0f, 1.0f / 256.0f, 1.0f / 256.0f};
-        if (oc + 4 <= ow) {
+        if (st_full) {
           *reinterpret_cast<f4*>(dst) = o;
         } else {
 #pragma unroll
@@ -445,22 +459,26 @@ __global__ __launch_bounds__(kBlock, PQA_MARCH_OCC) void vif_s0_march_kernel(con
             if (oc + i < ow) dst[i] = o[i];
         }
       }
+      dst += dst_step;
     }
     // statistic on this lane's 4 pixels (row yo + m, columns x0 + 4 kq + i).  sigma1_sq of all four first: one compare each
     // and one ballot tell whether every pixel of the block is in the log branch, and a block that is -- and lies inside the
     // image -- takes the shortened statistic (stat_pair<true>; same bits).  Textured material is all-high block by block;
     // flat sections and the edges between the two pay for both branches.
     const f2 mu1a = f2{V[0][0], V[0][1]}, mu1b = f2{V[0][2], V[0][3]};
-    const f2 s1a = f2{V[2][0], V[2][1]} - mu1a * mu1a, s1b = f2{V[2][2], V[2][3]} - mu1b * mu1b;
+    const f2 s1a = nfma(mu1a, mu1a, f2{V[2][0], V[2][1]}), s1b = nfma(mu1b, mu1b, f2{V[2][2], V[2][3]});
     const f2 mu2a = f2{V[1][0], V[1][1]}, mu2b = f2{V[1][2], V[1][3]};
     const f2 yya = f2{V[3][0], V[3][1]}, yyb = f2{V[3][2], V[3][3]};
     const f2 xya = f2{V[4][0], V[4][1]}, xyb = f2{V[4][2], V[4][3]};
     const float sigma_nsq = 2.0f * 256.0f;
-    const bool some_low = s1a.x < sigma_nsq || s1a.y < sigma_nsq || s1b.x < sigma_nsq || s1b.y < sigma_nsq;
-    const bool inside = a.uniform && yo + 16 <= a.h && x0 + 16 <= a.w;                // wave-uniform (every lane is active here)
+    // "some pixel of the wave is low": the four compares already are 64-bit lane masks in SGPRs, so they are OR-ed there
+    // (every lane is active: the waves with cb >= n_cb have returned)
+    const unsigned long long low_mask = __builtin_amdgcn_ballot_w64(s1a.x < sigma_nsq) | __builtin_amdgcn_ballot_w64(s1a.y < sigma_nsq) |
+                                        __builtin_amdgcn_ballot_w64(s1b.x < sigma_nsq) | __builtin_amdgcn_ballot_w64(s1b.y < sigma_nsq);
+    const bool inside = cols_inside && yo + 16 <= a.h;                                // wave-uniform (every lane is active here)
     StatAcc st{f2{0.0f, 0.0f}, f2{0.0f, 0.0f}, f2{1.0f, 1.0f}, f2{1.0f, 1.0f}, f2{1.0f, 1.0f}};
     float num, den;
-    if (inside && __builtin_amdgcn_ballot_w64(some_low) == 0ull) {
+    if (inside && low_mask == 0ull) {
       stat_pair<true>(st, s1a, mu1a, mu2a, yya, xya, true, true, a.gain_limit);
       stat_pair<true>(st, s1b, mu1b, mu2b, yyb, xyb, true, true, a.gain_limit);
       num = fast_log2(st.pn.x * st.pn.y) - fast_log2(st.qn.x * st.qn.y);
@@ -487,6 +505,9 @@ __global__ __launch_bounds__(kBlock, PQA_MARCH_OCC) void vif_s0_march_kernel(con
   for (int i = 0; i < 6; ++i) { P.hi[i] = u4v{0u, 0u, 0u, 0u}; P.lo[i] = u4v{0u, 0u, 0u, 0u}; }
   const std::integral_constant<int, 0> even{};
   const std::integral_constant<int, 1> odd{};
+  // (The prefetch is handed over by copy, Rc = Rn.  Two named pairs that alternate with the halves, so that nothing is copied
+  // or waited for in front of the next block's loads, were built, are bit-identical and measured -0.4 % on the VIF chain:
+  // DESIGN.md section 10.)
   Raw Rn, Dn;
   load_block(0, Rn, Dn);
   {
