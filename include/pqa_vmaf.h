@@ -643,6 +643,41 @@ PQA_API int pqa_tile_moments_device(pqa_ctx* ctx, const pqa_tile_spec* spec, con
                                     int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                     int32_t n_frames, uint64_t* out);
 
+/* Distortion spectrum: the second moments of the Haar octave bands of n_frames frame pairs of one plane, synchronously -- what
+ * pqa2_amd/spectrum.py turns into a gain, a detail loss and an added noise per octave and orientation: WHAT KIND of difference
+ * the clips have, where the distortion map says where.  Planes of width x height samples (the spec's, independent of the
+ * context's; each 1 ... 8192), u8 in an 8-bit context, otherwise u16 of the context's bit depth b (a sample above 2^b - 1 is
+ * read as 2^b - 1).  A_0 is the plane; for l = 1 ... L = levels (1 ... 6), W_l = floor(W / 2^l), H_l = floor(H / 2^l),
+ * 0 <= i < W_l, 0 <= j < H_l and a = A_{l-1}[2j][2i], b = A_{l-1}[2j][2i+1], c = A_{l-1}[2j+1][2i], e = A_{l-1}[2j+1][2i+1]:
+ *     A_l = a + b + c + e    H_l = a - b + c - e    V_l = a + b - c - e    D_l = a - b - c + e
+ * the unnormalised Haar transform: nothing is divided or rounded, and a coefficient exists only where its whole 2^l x 2^l
+ * support lies inside the plane (the last odd row or column of a level is ignored at that level and deeper).  With r_o, d_o
+ * the coefficients of the reference and the captured plane,
+ *     out[f][l-1][o][0..2] = sum r_o^2, sum d_o^2, sum r_o d_o        o: 0 H, 1 V, 2 D, 3 A
+ * over the level's W_l H_l coefficients, exact; the third is an int64 stored in the word as two's complement.  A level with
+ * W_l = 0 or H_l = 0 is all zeros.  Every sum is at most (2^b - 1)^2 W H 4^l < 2^62.  out (host) is [n_frames][L][4][3];
+ * pqa_band_sums() is 3.  No floating point anywhere.  Any context, no feature bit; buffers are made on first use, grow only and
+ * are freed with the context.  Independent of the scoring chain: a call between two pqa_submit calls changes no record.
+ * PQA_EINVAL, before any device call, on a null pointer, a bad struct_size, levels outside 1 ... 6, a size outside
+ * 1 ... 8192, a row pitch that is negative, shorter than a row or no multiple of the sample size, or a negative frame count.
+ * n_frames == 0 succeeds and writes nothing.  Kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_band_moments: frames in HOST memory (ref_frames[f] / dis_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample.
+ * pqa_band_moments_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+typedef struct pqa_band_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane, 1 ... 8192 */
+  uint32_t levels;        /* L, 1 ... 6 */
+} pqa_band_spec;
+PQA_API int pqa_band_moments(pqa_ctx* ctx, const pqa_band_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                             const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out);
+PQA_API int pqa_band_moments_device(pqa_ctx* ctx, const pqa_band_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                    int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                    int32_t n_frames, uint64_t* out);
+PQA_API int pqa_band_sums(void);
+
 /* Colour-matrix alignment: the cross-plane moments of n_frames frame pairs, synchronously -- what a capture chain that decodes
  * Y'CbCr with one matrix and encodes with another (BT.709 through a BT.601 leg) leaves behind, which no single-plane
  * measurement sees.  Works on the chroma grid of the context: chroma_shift = (hs, vs), s = 2^(hs + vs), chroma planes of

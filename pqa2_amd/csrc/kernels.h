@@ -517,5 +517,20 @@ hipError_t launch_tile_moments(hipStream_t stream, Elem elem, int bits, const vo
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int tile, unsigned long long* out);
 
+// ---- distortion spectrum: second moments of the Haar octave bands of a frame pair (band_moments.hip) --------------------------
+// out[f][l-1][o][0..2] = sum r_o^2, sum d_o^2, sum r_o d_o (the last as int64) over the coefficients of level l = 1 ... levels
+// and orientation o (0 H, 1 V, 2 D, 3 A) of the unnormalised Haar transform whose 2^l x 2^l support lies inside the plane, exact,
+// for n_frames plane pairs of w x h samples (1 ... 8192 each way; frame f at base + f * frame_pitch, pitches in elements; u8 /
+// u16 samples of `bits` bits, a sample above 2^bits - 1 is read as that).  part: device memory of band_part_bytes() for the
+// workgroups' partial sums; out: device memory of band_out_bytes(); every word of both is written, nothing needs zeroing.
+constexpr int kBandSums = 3;    // sums a band
+constexpr int kBandChunk = 8;   // frame pairs per launch of the two entries
+bool band_levels_ok(int levels);
+size_t band_out_bytes(int levels, int n_frames);
+size_t band_part_bytes(int w, int h, int levels, int n_frames);
+hipError_t launch_band_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
+                               int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                               int n_frames, int w, int h, int levels, void* part, unsigned long long* out);
+
 }  // namespace pqa
 

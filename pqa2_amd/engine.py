@@ -529,6 +529,49 @@ class FeatureEngine:
                                                      dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
         return out
 
+    # -- distortion spectrum -------------------------------------------------------------------
+    @staticmethod
+    def _band_spec(shape, levels):
+        sp = N.PqaBandSpec()
+        sp.struct_size = C.sizeof(N.PqaBandSpec)
+        sp.height, sp.width, sp.levels = (max(0, int(v)) for v in (shape[0], shape[1], levels))
+        return sp
+
+    @staticmethod
+    def _band_out(n, sp):
+        lv = sp.levels if 1 <= sp.levels <= 6 else 1      # a bad count is the library's to refuse
+        return np.zeros((max(int(n), 0), lv, 4, N.BAND_SUMS), np.uint64)
+
+    def band_moments(self, ref_frames, dis_frames, levels: int = 4) -> np.ndarray:
+        """[n, L, 4, 3] uint64: per level l = 1 ... L = `levels` (1 ... 6) and orientation (0 H, 1 V, 2 D, 3 A) of the
+        unnormalised Haar transform the sums of r^2, d^2 and r d over the level's coefficients (r: reference, d: captured; the
+        last is an int64: .view(np.int64)), exact (pqa_band_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory:
+        two lists of 2-D arrays of equal length and one size, which need not be this context's (1 ... 8192 each way); samples
+        of this context's bit depth.  spectrum.band_table and spectrum.summary read the result."""
+        n = len(ref_frames)
+        if len(dis_frames) != n:
+            raise ValueError("band_moments needs as many captured as reference frames")
+        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError("band_moments needs 2-D planes")
+        sp = self._band_spec(shape, levels)
+        out = self._band_out(n, sp)
+        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
+        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
+        self._check(self.lib.pqa_band_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def band_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                              dis_frame_pitch: int, shape, n_frames: int, levels: int = 4) -> np.ndarray:
+        """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_band_moments_device)."""
+        sp = self._band_spec(shape, levels)
+        out = self._band_out(n_frames, sp)
+        self._check(self.lib.pqa_band_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
+                                                     dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
+        return out
+
     # -- active-picture detection --------------------------------------------------------------
     @staticmethod
     def _profile_spec(shape):

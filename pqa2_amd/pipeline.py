@@ -39,7 +39,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 colour_full_range: bool | None = None, active_picture: str | None = None, active_frames: int = 8,
                 active_limit: int = 24, active_skip: int = 0, distortion_map: int = 0, distortion_planes: str = "y",
                 distortion_dir: str | None = None, distortion_factor=16,
-                distortion_min_mse: float = 4.0) -> ScoreResult | None:
+                distortion_min_mse: float = 4.0, spectrum: int = 0, spectrum_planes: str = "y", spectrum_min_mse: float = 1.0,
+                spectrum_gain_floor: float = 0.5) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -127,6 +128,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     is null, cuts both clips to the common rectangle; every later step and the scoring see the cropped clips, and `applied`
     says so.  Bars that are not black, that fade or move, and a scaled picture are not modelled.  `active_picture` = None:
     no measurement.
+    `spectrum` = L (1 ... 6): a distortion spectrum of the scored clips -- WHAT KIND of difference they have.  After every
+    alignment step, every frame pair of this rank's shard goes through FeatureEngine.band_moments (pqa_band_moments: the second
+    moments of L Haar octaves in three orientations) for the luma (`spectrum_planes` = "y") or all three planes ("all"; a
+    monochrome clip is an error), in the same pass as the distortion map when both are asked for.  Rank 0 runs the solver
+    (pqa2_amd/spectrum.py): `res["spectrum"]` holds {levels, planes: {y | cb | cr: {bands, summary}}, frames}; `bands` per level
+    the gain, error, detail loss and added noise of H, V, D and A in 8-bit code values squared, `summary` the shares, the
+    bandwidth each way, `kind` (identical, clean: total below `spectrum_min_mse`, loss, noise) and for a loss its `axis`;
+    `spectrum_gain_floor` is the gain a band must keep to count as passed.  The luma adds the per-frame metric columns
+    `detail_gain_h`, `detail_gain_v` and `noise_mse`.  `spectrum` = 0: nothing is measured and the result has none of it.
+
     `distortion_map` = T (8, 16, 32 or 64): a distortion map of the scored clips -- WHERE inside the frame they differ.  After
     every alignment step, on exactly the readers the scoring loop sees, a second pass reads every frame pair of this rank's
     shard in chunks of 8 through a context of its own and takes the exact second-order sums of every T x T tile
@@ -254,6 +265,15 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             raise ValueError('distortion_planes="all" needs the chroma planes, but the clips are monochrome')
         if distortion_factor is None or distortion_factor < 0 or distortion_min_mse is None or distortion_min_mse < 0:
             raise ValueError("distortion_factor and distortion_min_mse must not be negative")
+    if spectrum is None or isinstance(spectrum, bool) or int(spectrum) != spectrum or not 0 <= spectrum <= 6:
+        raise ValueError("spectrum must be 0 or a number of levels, 1 ... 6")
+    if spectrum:
+        if spectrum_planes not in ("y", "all"):
+            raise ValueError('spectrum_planes must be "y" or "all"')
+        if spectrum_planes == "all" and ri.mono:
+            raise ValueError('spectrum_planes="all" needs the chroma planes, but the clips are monochrome')
+        if spectrum_min_mse is None or spectrum_min_mse < 0 or spectrum_gain_floor is None or spectrum_gain_floor < 0:
+            raise ValueError("spectrum_min_mse and spectrum_gain_floor must not be negative")
     if cambi_full_ref and not cambi:
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
@@ -352,11 +372,11 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         eng.close()
         raise
     (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
-    dmap = None
-    if distortion_map:      # a pass of its own over the same readers, after the scoring context is parked
-        dmap = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
-                                engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
-                                gather_device, cancelled)
+    dmap = bands = None
+    if distortion_map or spectrum:      # ONE pass of its own over the same readers, after the scoring context is parked
+        dmap, bands = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
+                                       engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
+                                       gather_device, cancelled, levels=int(spectrum), band_planes=3 if spectrum_planes == "all" else 1)
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
@@ -415,6 +435,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                          fps=n / elapsed if elapsed > 0 else 0.0, **extra)
     if dmap is not None:
         _distortion_result(res, dmap, ri, int(distortion_map), distortion_factor, distortion_min_mse, distortion_dir)
+    if bands is not None:
+        _spectrum_result(res, bands, ri, int(spectrum), spectrum_min_mse, spectrum_gain_floor)
     if alignment is not None:
         res["alignment"] = alignment
     if resized is not None:
@@ -738,17 +760,25 @@ DISTORTION_PLANES = ("y", "cb", "cr")
 
 
 def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes: int, device, make, world_size: int,
-                     rank: int, gather_device, cancelled=None):
-    """the measurement of score_files(distortion_map=): per plane (tile SSE of every frame of the clip, uint64 [n, ty, tx];
-    clip-summed moments, uint64 [ty, tx, 6]), on every rank.  This rank measures its frames [a, b) in chunks of 8 pairs on
-    a small context of its own; the ranks' rows travel as the records do (shard.gather_records: the int64 transport carries
-    uint64 bit-exactly), their summed moments as one row a rank."""
+                     rank: int, gather_device, cancelled=None, levels: int = 0, band_planes: int = 1):
+    """the measurement of score_files(distortion_map=) and of score_files(spectrum=), in one pass that reads every frame pair
+    once, on every rank: (dmap, bands).  dmap (tile > 0, else None): per plane (tile SSE of every frame of the clip, uint64
+    [n, ty, tx]; clip-summed moments, uint64 [ty, tx, 6]).  bands (levels > 0, else None): per plane the band moments of every
+    frame of the clip, uint64 [n, L, 4, 3].  This rank measures its frames [a, b) in chunks of 8 pairs on a small context of
+    its own; the ranks' rows travel as the records do (shard.gather_records: the int64 transport carries uint64 bit-exactly),
+    their summed tile moments as one row a rank."""
     from . import distortion as DM
     ri = ref_rd.info
-    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (n_planes - 1)
-    grids = [DM.tile_counts(w, h, tile).shape for w, h in sizes]
+    if not tile:
+        n_planes = 0
+    if not levels:
+        band_planes = 0
+    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (max(n_planes, band_planes) - 1)
+    grids = [DM.tile_counts(w, h, tile).shape for w, h in sizes[:n_planes]]
     sse = [np.zeros((b - a,) + g, np.uint64) for g in grids]
     sums = [np.zeros(g + (N.TILE_SUMS,), np.uint64) for g in grids]
+    band_rows = [np.zeros((b - a, levels, 4, N.BAND_SUMS), np.uint64) for _ in range(band_planes)]
+    assert N.BAND_CHUNK == N.TILE_CHUNK
     if b > a:
         eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
                    features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
@@ -762,8 +792,15 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
                     M = eng.tile_moments([f[p] for f in rf], [f[p] for f in df], tile)
                     sums[p] += M.sum(axis=0, dtype=np.uint64)
                     sse[p][i0 - a:i0 - a + len(idx)] = DM.tile_sse(M)
+                for p in range(band_planes):
+                    band_rows[p][i0 - a:i0 - a + len(idx)] = eng.band_moments([f[p] for f in rf], [f[p] for f in df], levels)
         finally:
             eng.close()
+    bands = []
+    for p in range(band_planes):
+        cells = levels * 4 * N.BAND_SUMS
+        B = shard.gather_records(band_rows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
+        bands.append(np.ascontiguousarray(B).view(np.uint64).reshape(n, levels, 4, N.BAND_SUMS))
     out = []
     for p, g in enumerate(grids):
         cells = g[0] * g[1]
@@ -772,7 +809,21 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
                                  gather_device, width=cells * N.TILE_SUMS)
         out.append((np.ascontiguousarray(S).view(np.uint64).reshape((n,) + g),
                     np.ascontiguousarray(T).view(np.uint64).sum(axis=0, dtype=np.uint64).reshape(g + (N.TILE_SUMS,))))
-    return out
+    return (out if tile else None), (bands if levels else None)
+
+
+def _spectrum_result(res, bands, info, levels: int, min_mse, gain_floor) -> None:
+    """rank 0: the solver on the gathered band moments; adds res["spectrum"] and the three luma columns"""
+    from . import spectrum as SP
+    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(bands) - 1)
+    planes = {}
+    for name, M, (w, h) in zip(DISTORTION_PLANES, bands, sizes):
+        planes[name] = SP.analyse(M, w, h, info.bit_depth, min_mse=min_mse, gain_floor=gain_floor)
+        if name == "y":
+            keep = np.asarray(res["frame_indices"])
+            for key, col in SP.frame_columns(M, w, h, info.bit_depth).items():
+                res["metrics"][key] = col[keep]
+    res["spectrum"] = {"levels": levels, "planes": planes, "frames": int(bands[0].shape[0])}
 
 
 def _distortion_result(res, dmap, info, tile: int, factor, min_mse, out_dir) -> None:

@@ -190,6 +190,30 @@ def distortion_log_keys(distortion: dict | None) -> dict:
     return {"distortion": finite_deep(distortion)}
 
 
+def spectrum_log_keys(spectrum: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the distortion spectrum (pipeline.score_files(spectrum=L)); none without it.
+    Any float that is not finite becomes null."""
+    if not spectrum:
+        return {}
+    return {"spectrum": distortion_log_keys(spectrum)["distortion"]}
+
+
+def spectrum_summary_line(spectrum: dict) -> str:
+    """One line for a summary or a status bar: what kind of difference the luma has."""
+    s = spectrum.get("planes", {}).get("y", {}).get("summary", {})
+    line = f"Distortion spectrum: {spectrum.get('levels', 0)} octaves on {spectrum.get('frames', 0)} frames, {s.get('kind', '?')}"
+    if s.get("kind") == "loss":
+        line += f" ({s.get('axis')})"
+    if s.get("kind") in ("loss", "noise", "clean"):
+        line += (f", MSE {s.get('total_mse', 0.0):.2f}: {100.0 * s.get('loss_share', 0.0):.0f} % detail loss, "
+                 f"{100.0 * s.get('noise_share', 0.0):.0f} % added noise")
+        for key, name in (("bandwidth_h", "horizontal"), ("bandwidth_v", "vertical")):
+            bw = s.get(key) or {}
+            if bw.get("level"):
+                line += f", {name} detail passes up to 1/{1 << bw['level']} cycles per pixel"
+    return line
+
+
 def distortion_summary_line(distortion: dict) -> str:
     """One line for a summary or a status bar: the defects and persistent regions found in the luma."""
     y = distortion.get("planes", {}).get("y", {})

@@ -136,6 +136,17 @@ def main(argv=None) -> int:
                     help="with --distortion-map: a tile is hot when its MSE exceeds F times the frame's median tile MSE (default 16)")
     ap.add_argument("--distortion-min-mse", type=float, default=4.0, metavar="V",
                     help="with --distortion-map: ... and V in 8-bit code values squared (default 4)")
+    ap.add_argument("--spectrum", type=int, default=0, metavar="L", choices=[0, 1, 2, 3, 4, 5, 6],
+                    help="measure WHAT KIND of difference the clips have: the second moments of L Haar octaves (1 ... 6) in three "
+                         "orientations of every scored frame pair, in a second pass over both clips (shared with "
+                         "--distortion-map); the JSON gets a top-level spectrum object (gain, detail loss and added noise per "
+                         "band, the bandwidth each way, loss / noise) and three per-frame metrics")
+    ap.add_argument("--spectrum-planes", default="y", choices=["y", "all"],
+                    help="with --spectrum: the luma only (default) or all three planes")
+    ap.add_argument("--spectrum-min-mse", type=float, default=1.0, metavar="V",
+                    help="with --spectrum: below a total MSE of V in 8-bit code values squared the clips count as clean (default 1)")
+    ap.add_argument("--spectrum-gain-floor", type=float, default=0.5, metavar="G",
+                    help="with --spectrum: a band whose gain is at least G counts as passed by the chain (default 0.5)")
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
@@ -200,6 +211,9 @@ def main(argv=None) -> int:
                           **({"distortion_map": a.distortion_map, "distortion_planes": a.distortion_planes,
                               "distortion_dir": a.distortion_dir, "distortion_factor": a.distortion_factor,
                               "distortion_min_mse": a.distortion_min_mse} if a.distortion_map else {}),
+                          **({"spectrum": a.spectrum, "spectrum_planes": a.spectrum_planes,
+                              "spectrum_min_mse": a.spectrum_min_mse, "spectrum_gain_floor": a.spectrum_gain_floor}
+                             if a.spectrum else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
@@ -217,7 +231,8 @@ def main(argv=None) -> int:
                                      **report.integrity_log_keys(res.get("integrity")),
                                      **report.alignment_log_keys(res.get("alignment")),
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
-                                     **report.distortion_log_keys(res.get("distortion"))})
+                                     **report.distortion_log_keys(res.get("distortion")),
+                                     **report.spectrum_log_keys(res.get("spectrum"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -245,6 +260,8 @@ def main(argv=None) -> int:
             print(report.geometry_summary_line(res["alignment"]["geometry"]), file=sys.stderr, flush=True)
         if res.get("distortion"):
             print(report.distortion_summary_line(res["distortion"]), file=sys.stderr, flush=True)
+        if res.get("spectrum"):
+            print(report.spectrum_summary_line(res["spectrum"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

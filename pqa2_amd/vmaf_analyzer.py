@@ -171,6 +171,8 @@ class VMAFAnalyzer(QObject):
         self.active_crop_enabled = False      # ... and crop both to the common rectangle (implies the measurement; score_files(active_picture=))
         self.distortion_map_enabled = False   # distortion map: where inside the frame the clips differ (a second pass over both
         self.distortion_tile = 32             # clips; score_files(distortion_map=)); its tile size: 8, 16, 32 or 64
+        self.spectrum_enabled = False         # distortion spectrum: what kind of difference the clips have (the same second
+        self.spectrum_levels = 4              # pass; score_files(spectrum=)); its number of octaves: 1 ... 6
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -235,6 +237,10 @@ class VMAFAnalyzer(QObject):
                 self.distortion_map_enabled = bool(s["distortion_map_enabled"])
             if "distortion_tile" in s:
                 self.distortion_tile = int(s["distortion_tile"])
+            if "spectrum_enabled" in s:
+                self.spectrum_enabled = bool(s["spectrum_enabled"])
+            if "spectrum_levels" in s:
+                self.spectrum_levels = int(s["spectrum_levels"])
 
     set_options_manager = set_options_from_manager
 
@@ -254,7 +260,8 @@ class VMAFAnalyzer(QObject):
                              align_enabled=False, align_max_offset=8, spatial_align_enabled=False,
                              spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False,
                              colour_align_enabled=False, colour_correct_enabled=False, active_picture_enabled=False,
-                             active_crop_enabled=False, distortion_map_enabled=False, distortion_tile=32):
+                             active_crop_enabled=False, distortion_map_enabled=False, distortion_tile=32,
+                             spectrum_enabled=False, spectrum_levels=4):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -283,6 +290,8 @@ class VMAFAnalyzer(QObject):
         self.active_crop_enabled = bool(active_crop_enabled)
         self.distortion_map_enabled = bool(distortion_map_enabled)
         self.distortion_tile = int(distortion_tile)
+        self.spectrum_enabled = bool(spectrum_enabled)
+        self.spectrum_levels = int(spectrum_levels)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -460,7 +469,8 @@ class VMAFAnalyzer(QObject):
                                      **report.integrity_log_keys(res.get("integrity")),
                                      **report.alignment_log_keys(res.get("alignment")),
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
-                                     **report.distortion_log_keys(res.get("distortion"))})
+                                     **report.distortion_log_keys(res.get("distortion")),
+                                     **report.spectrum_log_keys(res.get("spectrum"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -499,6 +509,7 @@ class VMAFAnalyzer(QObject):
                 **({"active_picture": "apply" if self.active_crop_enabled else "report"}
                    if (self.active_picture_enabled or self.active_crop_enabled) else {}),
                 **({"distortion_map": int(self.distortion_tile)} if self.distortion_map_enabled else {}),
+                **({"spectrum": int(self.spectrum_levels)} if self.spectrum_enabled else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {})}
 
@@ -551,6 +562,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--active-picture"]
         if self.distortion_map_enabled:
             cmd += ["--distortion-map", str(int(self.distortion_tile))]
+        if self.spectrum_enabled:
+            cmd += ["--spectrum", str(int(self.spectrum_levels))]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -696,6 +709,11 @@ class VMAFAnalyzer(QObject):
                 results["distortion"] = vmaf_data.get("distortion")
                 if results["distortion"]:
                     self.status_update.emit(report.distortion_summary_line(results["distortion"]))
+            if self.spectrum_enabled:   # what kind of difference the clips have, from the log's top level
+                from . import report
+                results["spectrum"] = vmaf_data.get("spectrum")
+                if results["spectrum"]:
+                    self.status_update.emit(report.spectrum_summary_line(results["spectrum"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
