@@ -678,6 +678,43 @@ PQA_API int pqa_band_moments_device(pqa_ctx* ctx, const pqa_band_spec* spec, con
                                     int32_t n_frames, uint64_t* out);
 PQA_API int pqa_band_sums(void);
 
+/* Temporal distortion: the tile-wise second-order statistics of the frame DIFFERENCES of n_frames frame pairs of one plane,
+ * synchronously -- what pqa2_amd/temporal.py turns into a temporal gain, a blend weight, a temporal loss and noise and a list
+ * of pops: whether the MOTION of the captured clip is wrong, where the distortion map and spectrum say whether its pictures
+ * are.  Planes of width x height samples (the spec's, independent of the context's width and height; each 1 ... 8192), u8 in an
+ * 8-bit context, otherwise u16 of the context's bit depth b (a sample above 2^b - 1 is read as 2^b - 1).  With R_f the
+ * reference and D_f the captured plane of frame f, for every transition k = 1 ... n_frames - 1 and every pixel
+ *     a = R_k - R_{k-1}    b = D_k - D_{k-1}    e = D_k - R_k        (signed integers)
+ * tile (i, j) of size T = tile (8, 16, 32 or 64) owns the pixels with x / T = i, y / T = j; the grid is tx = ceil(W / T) by
+ * ty = ceil(H / T), edge tiles hold the pixels that exist, and
+ *     out[k-1][j][i][0..6] = sum a, sum b, sum a^2, sum b^2, sum a b, sum a e, sum e^2
+ * Exact, no floating point anywhere: words 0, 1, 4 and 5 are int64 stored in the word as two's complement, words 2, 3 and 6
+ * uint64; every sum is below 4095^2 * 4096 < 2^36 in magnitude.  out (host) is [max(n_frames - 1, 0)][ty][tx][7];
+ * pqa_temporal_sums() is 7.  Any context, no feature bit; buffers are made on first use, grow only and are freed with the
+ * context.  Independent of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL, before any
+ * device call, on a null pointer, a bad struct_size, a tile other than 8 / 16 / 32 / 64, a size outside 1 ... 8192, a row
+ * pitch that is negative, shorter than a row or no multiple of the sample size, or a negative frame count.  n_frames of 0 or 1
+ * succeeds and writes nothing.  Kernel and accumulator bounds: DESIGN.md section 5.  PQA_TEMPORAL_WALK=1 in the environment at
+ * pqa_create selects the kernel's other traversal (a workgroup walks through time; the A/B partner): the same integers.
+ *
+ * pqa_temporal_moments: frames in HOST memory (ref_frames[f] / dis_frames[f] point at planes, rows *_row_stride bytes apart;
+ * the frames need not be contiguous).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample, every
+ * frame once: the last pair of a chunk stays on the device as the predecessor of the next chunk's first.
+ * pqa_temporal_moments_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart),
+ * under the ordering contract of pqa_submit_device. */
+typedef struct pqa_temporal_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane, 1 ... 8192 */
+  uint32_t tile;          /* 8, 16, 32 or 64 */
+} pqa_temporal_spec;
+PQA_API int pqa_temporal_moments(pqa_ctx* ctx, const pqa_temporal_spec* spec, const void* const* ref_frames,
+                                 int64_t ref_row_stride, const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames,
+                                 uint64_t* out);
+PQA_API int pqa_temporal_moments_device(pqa_ctx* ctx, const pqa_temporal_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                        int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                        int32_t n_frames, uint64_t* out);
+PQA_API int pqa_temporal_sums(void);
+
 /* Colour-matrix alignment: the cross-plane moments of n_frames frame pairs, synchronously -- what a capture chain that decodes
  * Y'CbCr with one matrix and encodes with another (BT.709 through a BT.601 leg) leaves behind, which no single-plane
  * measurement sees.  Works on the chroma grid of the context: chroma_shift = (hs, vs), s = 2^(hs + vs), chroma planes of

@@ -532,5 +532,20 @@ hipError_t launch_band_moments(hipStream_t stream, Elem elem, int bits, const vo
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int levels, void* part, unsigned long long* out);
 
+// ---- temporal distortion: tile-wise second-order statistics of the frame differences of a clip pair (temporal_moments.hip) ----
+// With a = R_k - R_{k-1}, b = D_k - D_{k-1}, e = D_k - R_k (signed) for the transitions k = 1 ... n_frames - 1:
+// out[k-1][j][i][0..6] = sum a, sum b, sum a^2, sum b^2, sum a b, sum a e, sum e^2 over the pixels of tile (i, j) of `tile` x
+// `tile` pixels (8, 16, 32 or 64; edge tiles hold the pixels that exist), exact (words 0, 1, 4, 5 as int64), for n_frames plane
+// pairs of w x h samples (1 ... 8192 each way; frame f at base + f * frame_pitch, pitches in elements; u8 / u16 samples of
+// `bits` bits, a sample above 2^bits - 1 is read as that).  out: device memory of temporal_out_bytes(); every word is written,
+// nothing needs zeroing.  n_frames <= 1 launches nothing.  walk: the A/B partner in which a workgroup walks through the launch's
+// transitions with its block of the previous pair in registers, instead of a workgroup per transition; the same integers.
+constexpr int kTemporalSums = 7;    // sums a tile
+constexpr int kTemporalChunk = 8;   // frame pairs per launch of the two entries (the host entry keeps one more as predecessor)
+size_t temporal_out_bytes(int w, int h, int tile, int n_frames);
+hipError_t launch_temporal_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
+                                   int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                   int n_frames, int w, int h, int tile, bool walk, unsigned long long* out);
+
 }  // namespace pqa
 

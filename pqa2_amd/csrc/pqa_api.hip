@@ -1071,6 +1071,8 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->motion_mode = (mm && mm[0] == '0') ? MOTION_TILED : MOTION_AUTO;
     const char* xm = getenv("PQA_XSSE_MFMA");  // 0: the plain-VALU cross-SSE kernel for 8-bit clips too (test partner of the MFMA kernel)
     c->xsse_mfma = !(xm && xm[0] == '0');
+    const char* tw = getenv("PQA_TEMPORAL_WALK");  // 1: a workgroup of the temporal moments walks through time (A/B partner of a workgroup per transition)
+    c->temporal_walk = tw && tw[0] == '1';
   }
   for (int i = 0; i < 2; ++i) {
     CREATE_HIP(hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));

@@ -1,5 +1,5 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the registration moments, the line profiles, the tile moments, the band moments, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
+// temporal / spatial / level alignment, the resampler, the registration moments, the line profiles, the tile moments, the band moments, the temporal moments, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
 // entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
@@ -346,6 +346,20 @@ int bd_check(pqa_ctx* c, const pqa_band_spec* sp, const void* ref, const void* d
   if (n_frames < 0) return fail(c, PQA_EINVAL, "band_moments: negative frame count");
   if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "band_moments: null clip pointer");
   if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "band_moments: null output pointer");
+  return PQA_OK;
+}
+
+// ---- temporal distortion (temporal_moments.hip): argument rules (no device call) ---------------------------------------------
+int tm_check(pqa_ctx* c, const pqa_temporal_spec* sp, const void* ref, const void* dis, int32_t n_frames, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!sp) return fail(c, PQA_EINVAL, "temporal_moments: null spec");
+  if (sp->struct_size != sizeof(pqa_temporal_spec)) return fail(c, PQA_EINVAL, "temporal_moments: bad struct_size %u", sp->struct_size);
+  if (sp->tile > 64 || !tile_size_ok((int)sp->tile)) return fail(c, PQA_EINVAL, "temporal_moments: tile %u is not 8, 16, 32 or 64", sp->tile);
+  for (uint32_t v : {sp->width, sp->height})
+    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "temporal_moments: plane size %u outside 1 ... 8192", v);
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "temporal_moments: negative frame count");
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "temporal_moments: null clip pointer");
+  if (n_frames > 1 && !out) return fail(c, PQA_EINVAL, "temporal_moments: null output pointer");
   return PQA_OK;
 }
 
@@ -1030,6 +1044,96 @@ int pqa_band_moments(pqa_ctx* c, const pqa_band_spec* spec, const void* const* r
                               c->side_buf[SIDE_BAND_PART], dev_out + (size_t)f0 * per_frame);
   }
   return side_finish(c, "band_moments", e, out, dev_out, bytes);
+}
+
+// ---- temporal distortion (temporal_moments.hip) ------------------------------------------------------------------------------
+
+int pqa_temporal_sums(void) { return kTemporalSums; }
+
+int pqa_temporal_moments_device(pqa_ctx* c, const pqa_temporal_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                int32_t n_frames, uint64_t* out) {
+  int rc = tm_check(c, spec, ref, dis, n_frames, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
+  rc = check_device_clip(c, "temporal_moments: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
+  if (rc == PQA_OK) rc = check_device_clip(c, "temporal_moments: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames <= 1) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = temporal_out_bytes(w, h, tile, n_frames), per_tr = temporal_out_bytes(w, h, tile, 2) / sizeof(uint64_t);
+  rc = side_reserve(c, SIDE_TEMPORAL_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_TEMPORAL_OUT];
+  hipError_t e = hipSuccess;
+  // transitions t0 + 1 ... t0 + kTemporalChunk a launch: frames t0 ... t0 + kTemporalChunk, the first as predecessor only
+  for (int t0 = 0; t0 < n_frames - 1 && e == hipSuccess; t0 += kTemporalChunk)
+    e = launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)t0 * ref_frame_pitch,
+                                ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)t0 * dis_frame_pitch,
+                                dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames - 1, t0, kTemporalChunk) + 1, w, h, tile,
+                                c->temporal_walk, dev_out + (size_t)t0 * per_tr);
+  return side_finish(c, "temporal_moments", e, out, dev_out, bytes);
+}
+
+int pqa_temporal_moments(pqa_ctx* c, const pqa_temporal_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                         const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
+  int rc = tm_check(c, spec, ref_frames, dis_frames, n_frames, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
+  const size_t row_bytes = (size_t)w * es;
+  rc = check_host_frames(c, "temporal_moments: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "temporal_moments: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
+  if (rc != PQA_OK) return rc;
+  if (n_frames > 0 && (ref_row_stride % es || dis_row_stride % es))
+    return fail(c, PQA_EINVAL, "temporal_moments: stride is not a multiple of the sample size");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames <= 1) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // The planes travel as pqa_tile_moments' do, through the same buffers, every frame once: chunks of kTemporalChunk pairs through
+  // the two grow-only pinned buffers of pqa_resample into the two device buffers of pqa_flow_moments, rows 16 bytes apart at
+  // least, so the kernel takes its wide loads.  The device buffers hold one slot more than a chunk: a chunk lands in slots
+  // 1 ... n, and before the next chunk's upload overwrites them the last pair is copied to slot 0 on the stream, where it is
+  // the predecessor of the next chunk's first.  So the first chunk's launch starts at slot 1 (n - 1 transitions) and every
+  // later one at slot 0 (n transitions).  Every launch writes its sums behind the previous one's; they come back once.  A
+  // pinned buffer is packed again only after the stream has drained the chunk before.
+  const int64_t pitch = round_up((int64_t)row_bytes, 16);
+  const size_t fb = (size_t)pitch * h;
+  const int chunk = n_frames < kTemporalChunk ? n_frames : kTemporalChunk;
+  const size_t bytes = temporal_out_bytes(w, h, tile, n_frames), per_tr = temporal_out_bytes(w, h, tile, 2) / sizeof(uint64_t);
+  rc = rs_pin_reserve(c, 0, fb * chunk);
+  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * (chunk + 1));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * (chunk + 1));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TEMPORAL_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_TEMPORAL_OUT];
+  auto* dref = (uint8_t*)c->side_buf[SIDE_FLOW_REF];
+  auto* ddis = (uint8_t*)c->side_buf[SIDE_FLOW_DIS];
+  hipError_t e = hipSuccess;
+  int prev_n = 0;   // frames of the chunk before: its last pair is in slot prev_n
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kTemporalChunk) {
+    const int n = chunk_len(n_frames, f0, kTemporalChunk);
+    if (f0 > 0) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) break;
+    for (int f = 0; f < n; ++f) {
+      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
+      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
+    }
+    if (prev_n > 0) {   // the seam: slot prev_n >= 1, so source and destination never overlap
+      e = hipMemcpyAsync(dref, dref + (size_t)prev_n * fb, fb, hipMemcpyDeviceToDevice, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(ddis, ddis + (size_t)prev_n * fb, fb, hipMemcpyDeviceToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(dref + fb, c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ddis + fb, c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
+    const size_t first = prev_n > 0 ? 0 : fb;   // the slot of the launch's first frame
+    if (e == hipSuccess)
+      e = launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, dref + first, pitch / es, (int64_t)(fb / es), ddis + first,
+                                  pitch / es, (int64_t)(fb / es), n + (prev_n > 0 ? 1 : 0), w, h, tile, c->temporal_walk,
+                                  dev_out + (size_t)(f0 > 0 ? f0 - 1 : 0) * per_tr);
+    prev_n = n;
+  }
+  return side_finish(c, "temporal_moments", e, out, dev_out, bytes);
 }
 
 // ---- active-picture detection (line_profiles.hip) ------------------------------------------------------------------------

@@ -572,6 +572,51 @@ class FeatureEngine:
                                                      dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
         return out
 
+    # -- temporal distortion -------------------------------------------------------------------
+    @staticmethod
+    def _temporal_spec(shape, tile):
+        sp = N.PqaTemporalSpec()
+        sp.struct_size = C.sizeof(N.PqaTemporalSpec)
+        sp.height, sp.width, sp.tile = (max(0, int(v)) for v in (shape[0], shape[1], tile))
+        return sp
+
+    @staticmethod
+    def _temporal_out(n, sp):
+        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
+        return np.zeros((max(int(n) - 1, 0), -(-sp.height // t), -(-sp.width // t), N.TEMPORAL_SUMS), np.uint64)
+
+    def temporal_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
+        """[n - 1, ty, tx, 7] uint64: per transition k = 1 ... n - 1 and tile of `tile` x `tile` pixels (8, 16, 32 or 64; edge
+        tiles hold the pixels that exist) the sums of a, b, a^2, b^2, a b, a e and e^2 with a = R_k - R_{k-1},
+        b = D_k - D_{k-1}, e = D_k - R_k (R: reference, D: captured), exact (pqa_temporal_moments; definition:
+        include/pqa_vmaf.h).  Words 0, 1, 4 and 5 (N.TEMPORAL_SIGNED) are int64: read them through .view(np.int64).  Planes in
+        HOST memory: two lists of 2-D arrays of equal length and one size, which need not be this context's (1 ... 8192 each
+        way); samples of this context's bit depth.  Fewer than two frames give an empty result.  temporal.frame_table and
+        temporal.summary read the result."""
+        n = len(ref_frames)
+        if len(dis_frames) != n:
+            raise ValueError("temporal_moments needs as many captured as reference frames")
+        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError("temporal_moments needs 2-D planes")
+        sp = self._temporal_spec(shape, tile)
+        out = self._temporal_out(n, sp)
+        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
+        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
+        self._check(self.lib.pqa_temporal_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def temporal_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                                  dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
+        """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_temporal_moments_device)."""
+        sp = self._temporal_spec(shape, tile)
+        out = self._temporal_out(n_frames, sp)
+        self._check(self.lib.pqa_temporal_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
+                                                         dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
+        return out
+
     # -- active-picture detection --------------------------------------------------------------
     @staticmethod
     def _profile_spec(shape):

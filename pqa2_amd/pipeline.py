@@ -40,7 +40,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 active_limit: int = 24, active_skip: int = 0, distortion_map: int = 0, distortion_planes: str = "y",
                 distortion_dir: str | None = None, distortion_factor=16,
                 distortion_min_mse: float = 4.0, spectrum: int = 0, spectrum_planes: str = "y", spectrum_min_mse: float = 1.0,
-                spectrum_gain_floor: float = 0.5) -> ScoreResult | None:
+                spectrum_gain_floor: float = 0.5, temporal: int = 0, temporal_planes: str = "y", temporal_min_mse: float = 1.0,
+                temporal_blend_min: float = 1 / 16, temporal_still_mse: float = 0.25,
+                temporal_pop_factor: float = 4) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -137,6 +139,18 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     bandwidth each way, `kind` (identical, clean: total below `spectrum_min_mse`, loss, noise) and for a loss its `axis`;
     `spectrum_gain_floor` is the gain a band must keep to count as passed.  The luma adds the per-frame metric columns
     `detail_gain_h`, `detail_gain_v` and `noise_mse`.  `spectrum` = 0: nothing is measured and the result has none of it.
+    `temporal` = T (8, 16, 32 or 64): the temporal distortion of the scored clips -- whether their MOTION is wrong, which no
+    per-frame map or spectrum shows.  After every alignment step, in the same pass as the distortion map and the spectrum when
+    those are asked for, every transition of this rank's shard goes through FeatureEngine.temporal_moments
+    (pqa_temporal_moments: the exact second-order sums of the frame differences of both clips per T x T tile) for the luma
+    (`temporal_planes` = "y") or all three planes ("all"; a monochrome clip is an error); a rank whose chunk starts at frame
+    a > 0 also reads frame a - 1.  Rank 0 runs the solver (pqa2_amd/temporal.py): `res["temporal"]` holds {tile, planes:
+    {y | cb | cr: {summary, frames}}, frames}; `summary` the temporal gain, loss and noise, the blend weight, the noise where
+    the reference stands still (tile transitions that move by at most `temporal_still_mse`), the pops (transitions whose
+    noise exceeds `temporal_pop_factor` times the median) with their period and `kind` (identical, clean: temporal MSE below
+    `temporal_min_mse`, blend: weight at least `temporal_blend_min`, loss, noise); `frames` one row a transition.  The luma
+    adds the per-frame metric columns `temporal_gain`, `temporal_noise_mse` and `blend_weight` (frame 0 has no transition:
+    1, 0 and 0, as `motion` is 0 there).  `temporal` = 0: nothing is measured and the result has none of it.
 
     `distortion_map` = T (8, 16, 32 or 64): a distortion map of the scored clips -- WHERE inside the frame they differ.  After
     every alignment step, on exactly the readers the scoring loop sees, a second pass reads every frame pair of this rank's
@@ -274,6 +288,15 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             raise ValueError('spectrum_planes="all" needs the chroma planes, but the clips are monochrome')
         if spectrum_min_mse is None or spectrum_min_mse < 0 or spectrum_gain_floor is None or spectrum_gain_floor < 0:
             raise ValueError("spectrum_min_mse and spectrum_gain_floor must not be negative")
+    if temporal is None or isinstance(temporal, bool) or (temporal and temporal not in N.FLOW_TILES):
+        raise ValueError("temporal must be 0 or a tile size of 8, 16, 32 or 64")
+    if temporal:
+        if temporal_planes not in ("y", "all"):
+            raise ValueError('temporal_planes must be "y" or "all"')
+        if temporal_planes == "all" and ri.mono:
+            raise ValueError('temporal_planes="all" needs the chroma planes, but the clips are monochrome')
+        if any(v is None or v < 0 for v in (temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)):
+            raise ValueError("temporal_min_mse, temporal_blend_min, temporal_still_mse and temporal_pop_factor must not be negative")
     if cambi_full_ref and not cambi:
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
@@ -372,11 +395,13 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         eng.close()
         raise
     (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
-    dmap = bands = None
-    if distortion_map or spectrum:      # ONE pass of its own over the same readers, after the scoring context is parked
-        dmap, bands = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
-                                       engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
-                                       gather_device, cancelled, levels=int(spectrum), band_planes=3 if spectrum_planes == "all" else 1)
+    dmap = bands = tmom = None
+    if distortion_map or spectrum or temporal:      # ONE pass of its own over the same readers, after the scoring context is parked
+        dmap, bands, tmom = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
+                                             engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
+                                             gather_device, cancelled, levels=int(spectrum),
+                                             band_planes=3 if spectrum_planes == "all" else 1, temporal_tile=int(temporal),
+                                             temporal_planes=3 if temporal_planes == "all" else 1)
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
@@ -437,6 +462,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         _distortion_result(res, dmap, ri, int(distortion_map), distortion_factor, distortion_min_mse, distortion_dir)
     if bands is not None:
         _spectrum_result(res, bands, ri, int(spectrum), spectrum_min_mse, spectrum_gain_floor)
+    if tmom is not None:
+        _temporal_result(res, tmom, ri, int(temporal), temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)
     if alignment is not None:
         res["alignment"] = alignment
     if resized is not None:
@@ -760,9 +787,13 @@ DISTORTION_PLANES = ("y", "cb", "cr")
 
 
 def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes: int, device, make, world_size: int,
-                     rank: int, gather_device, cancelled=None, levels: int = 0, band_planes: int = 1):
-    """the measurement of score_files(distortion_map=) and of score_files(spectrum=), in one pass that reads every frame pair
-    once, on every rank: (dmap, bands).  dmap (tile > 0, else None): per plane (tile SSE of every frame of the clip, uint64
+                     rank: int, gather_device, cancelled=None, levels: int = 0, band_planes: int = 1, temporal_tile: int = 0,
+                     temporal_planes: int = 1):
+    """the measurement of score_files(distortion_map=), of score_files(spectrum=) and of score_files(temporal=), in one pass
+    that reads every frame pair once, on every rank: (dmap, bands, temporal).  temporal (temporal_tile > 0, else None): per
+    plane the temporal moments of every transition of the clip, uint64 [n - 1, ty, tx, 7]; a rank whose chunk starts at frame
+    a > 0 also reads frame a - 1, so transition a is measured by the rank that owns frame a and the result does not depend
+    on the number of ranks.  dmap (tile > 0, else None): per plane (tile SSE of every frame of the clip, uint64
     [n, ty, tx]; clip-summed moments, uint64 [ty, tx, 6]).  bands (levels > 0, else None): per plane the band moments of every
     frame of the clip, uint64 [n, L, 4, 3].  This rank measures its frames [a, b) in chunks of 8 pairs on a small context of
     its own; the ranks' rows travel as the records do (shard.gather_records: the int64 transport carries uint64 bit-exactly),
@@ -773,7 +804,12 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
         n_planes = 0
     if not levels:
         band_planes = 0
-    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (max(n_planes, band_planes) - 1)
+    if not temporal_tile:
+        temporal_planes = 0
+    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (max(n_planes, band_planes, temporal_planes) - 1)
+    tgrids = [DM.tile_counts(w, h, temporal_tile).shape for w, h in sizes[:temporal_planes]]
+    trows = [np.zeros((b - a,) + g + (N.TEMPORAL_SUMS,), np.uint64) for g in tgrids]   # row i - a: the transition INTO frame i
+    assert N.TEMPORAL_CHUNK == N.TILE_CHUNK
     grids = [DM.tile_counts(w, h, tile).shape for w, h in sizes[:n_planes]]
     sse = [np.zeros((b - a,) + g, np.uint64) for g in grids]
     sums = [np.zeros(g + (N.TILE_SUMS,), np.uint64) for g in grids]
@@ -788,6 +824,13 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
                     raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
                 idx = range(i0, min(b, i0 + N.TILE_CHUNK))
                 rf, df = [ref_rd.frame(i) for i in idx], [dis_rd.frame(i) for i in idx]
+                if temporal_planes and i0 > 0:      # the predecessor of the chunk's first frame: one extra read a chunk
+                    prf, pdf = [ref_rd.frame(i0 - 1)] + rf, [dis_rd.frame(i0 - 1)] + df
+                    for p in range(temporal_planes):
+                        trows[p][i0 - a:i0 - a + len(idx)] = eng.temporal_moments([f[p] for f in prf], [f[p] for f in pdf], temporal_tile)
+                elif temporal_planes and len(idx) > 1:
+                    for p in range(temporal_planes):
+                        trows[p][1:len(idx)] = eng.temporal_moments([f[p] for f in rf], [f[p] for f in df], temporal_tile)
                 for p in range(n_planes):
                     M = eng.tile_moments([f[p] for f in rf], [f[p] for f in df], tile)
                     sums[p] += M.sum(axis=0, dtype=np.uint64)
@@ -809,7 +852,27 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
                                  gather_device, width=cells * N.TILE_SUMS)
         out.append((np.ascontiguousarray(S).view(np.uint64).reshape((n,) + g),
                     np.ascontiguousarray(T).view(np.uint64).sum(axis=0, dtype=np.uint64).reshape(g + (N.TILE_SUMS,))))
-    return (out if tile else None), (bands if levels else None)
+    tmom = []
+    for p, g in enumerate(tgrids):
+        cells = g[0] * g[1] * N.TEMPORAL_SUMS
+        T = shard.gather_records(trows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
+        tmom.append(np.ascontiguousarray(T).view(np.uint64).reshape((n,) + g + (N.TEMPORAL_SUMS,))[1:])   # frame 0 has no transition
+    return (out if tile else None), (bands if levels else None), (tmom if temporal_tile else None)
+
+
+def _temporal_result(res, tmom, info, tile: int, min_mse, blend_min, still_mse, pop_factor) -> None:
+    """rank 0: the solver on the gathered temporal moments; adds res["temporal"] and the three luma columns"""
+    from . import temporal as TP
+    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(tmom) - 1)
+    planes = {}
+    for name, M, (w, h) in zip(DISTORTION_PLANES, tmom, sizes):
+        planes[name] = TP.analyse(M, w, h, tile, info.bit_depth, min_mse=min_mse, blend_min=blend_min, still_mse=still_mse,
+                                  pop_factor=pop_factor)
+        if name == "y":
+            keep = np.asarray(res["frame_indices"])
+            for key, col in TP.frame_columns(M, w, h, info.bit_depth).items():
+                res["metrics"][key] = col[keep]
+    res["temporal"] = {"tile": tile, "planes": planes, "frames": int(tmom[0].shape[0]) + 1}
 
 
 def _spectrum_result(res, bands, info, levels: int, min_mse, gain_floor) -> None:

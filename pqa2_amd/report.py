@@ -214,6 +214,32 @@ def spectrum_summary_line(spectrum: dict) -> str:
     return line
 
 
+def temporal_log_keys(temporal: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the temporal distortion (pipeline.score_files(temporal=T)); none without it.
+    Any float that is not finite becomes null."""
+    if not temporal:
+        return {}
+    return {"temporal": distortion_log_keys(temporal)["distortion"]}
+
+
+def temporal_summary_line(temporal: dict) -> str:
+    """One line for a summary or a status bar: what is wrong with the motion of the luma."""
+    s = temporal.get("planes", {}).get("y", {}).get("summary", {})
+    line = (f"Temporal distortion: {temporal.get('tile', 0)} px tiles on {temporal.get('frames', 0)} frames, {s.get('kind', '?')}")
+    if s.get("kind") == "blend":
+        line += f" (weight {s.get('blend_weight') or 0.0:.3f} of the previous frame)"
+    if s.get("kind") in ("blend", "loss", "noise", "clean"):
+        line += (f", temporal MSE {s.get('temporal_mse', 0.0):.2f} against a motion of {s.get('motion_mse', 0.0):.2f}: "
+                 f"{100.0 * s.get('loss_share', 0.0):.0f} % loss, {100.0 * s.get('noise_share', 0.0):.0f} % noise")
+        if s.get("still_noise_mse") is not None:
+            line += f", {s['still_noise_mse']:.2f} where nothing moves"
+        if s.get("pops"):
+            line += f", {len(s['pops'])} pops"
+            if s.get("pop_period"):
+                line += f" every {s['pop_period']} frames"
+    return line
+
+
 def distortion_summary_line(distortion: dict) -> str:
     """One line for a summary or a status bar: the defects and persistent regions found in the luma."""
     y = distortion.get("planes", {}).get("y", {})

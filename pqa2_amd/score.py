@@ -147,6 +147,23 @@ def main(argv=None) -> int:
                     help="with --spectrum: below a total MSE of V in 8-bit code values squared the clips count as clean (default 1)")
     ap.add_argument("--spectrum-gain-floor", type=float, default=0.5, metavar="G",
                     help="with --spectrum: a band whose gain is at least G counts as passed by the chain (default 0.5)")
+    ap.add_argument("--temporal", type=int, default=0, metavar="T", choices=[0, 8, 16, 32, 64],
+                    help="measure whether the MOTION of the capture is wrong: the second-order sums of the frame differences of "
+                         "both clips per T x T tile (8, 16, 32 or 64) of every transition, in a second pass over both clips "
+                         "(shared with --distortion-map and --spectrum); the JSON gets a top-level temporal object (temporal "
+                         "gain, loss and noise, blend weight, pops, blend / loss / noise) and three per-frame metrics")
+    ap.add_argument("--temporal-planes", default="y", choices=["y", "all"],
+                    help="with --temporal: the luma only (default) or all three planes")
+    ap.add_argument("--temporal-min-mse", type=float, default=1.0, metavar="V",
+                    help="with --temporal: below a temporal MSE of V in 8-bit code values squared the clips count as clean, and no "
+                         "transition below it is a pop (default 1)")
+    ap.add_argument("--temporal-blend-min", type=float, default=1 / 16, metavar="B",
+                    help="with --temporal: a weight of the previous frame of at least B counts as a blend (default 1/16)")
+    ap.add_argument("--temporal-still-mse", type=float, default=0.25, metavar="V",
+                    help="with --temporal: a tile stands still in a transition when its reference moves by at most V in 8-bit code "
+                         "values squared (default 1/4)")
+    ap.add_argument("--temporal-pop-factor", type=float, default=4, metavar="F",
+                    help="with --temporal: a transition pops when its noise exceeds F times the clip's median (default 4)")
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
@@ -214,6 +231,9 @@ def main(argv=None) -> int:
                           **({"spectrum": a.spectrum, "spectrum_planes": a.spectrum_planes,
                               "spectrum_min_mse": a.spectrum_min_mse, "spectrum_gain_floor": a.spectrum_gain_floor}
                              if a.spectrum else {}),
+                          **({"temporal": a.temporal, "temporal_planes": a.temporal_planes, "temporal_min_mse": a.temporal_min_mse,
+                              "temporal_blend_min": a.temporal_blend_min, "temporal_still_mse": a.temporal_still_mse,
+                              "temporal_pop_factor": a.temporal_pop_factor} if a.temporal else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
@@ -232,7 +252,8 @@ def main(argv=None) -> int:
                                      **report.alignment_log_keys(res.get("alignment")),
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
                                      **report.distortion_log_keys(res.get("distortion")),
-                                     **report.spectrum_log_keys(res.get("spectrum"))})
+                                     **report.spectrum_log_keys(res.get("spectrum")),
+                                     **report.temporal_log_keys(res.get("temporal"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -262,6 +283,8 @@ def main(argv=None) -> int:
             print(report.distortion_summary_line(res["distortion"]), file=sys.stderr, flush=True)
         if res.get("spectrum"):
             print(report.spectrum_summary_line(res["spectrum"]), file=sys.stderr, flush=True)
+        if res.get("temporal"):
+            print(report.temporal_summary_line(res["temporal"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

@@ -173,6 +173,8 @@ class VMAFAnalyzer(QObject):
         self.distortion_tile = 32             # clips; score_files(distortion_map=)); its tile size: 8, 16, 32 or 64
         self.spectrum_enabled = False         # distortion spectrum: what kind of difference the clips have (the same second
         self.spectrum_levels = 4              # pass; score_files(spectrum=)); its number of octaves: 1 ... 6
+        self.temporal_enabled = False         # temporal distortion: whether the motion of the capture is wrong (the same second
+        self.temporal_tile = 32               # pass; score_files(temporal=)); its tile size: 8, 16, 32 or 64
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -241,6 +243,10 @@ class VMAFAnalyzer(QObject):
                 self.spectrum_enabled = bool(s["spectrum_enabled"])
             if "spectrum_levels" in s:
                 self.spectrum_levels = int(s["spectrum_levels"])
+            if "temporal_enabled" in s:
+                self.temporal_enabled = bool(s["temporal_enabled"])
+            if "temporal_tile" in s:
+                self.temporal_tile = int(s["temporal_tile"])
 
     set_options_manager = set_options_from_manager
 
@@ -261,7 +267,7 @@ class VMAFAnalyzer(QObject):
                              spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False,
                              colour_align_enabled=False, colour_correct_enabled=False, active_picture_enabled=False,
                              active_crop_enabled=False, distortion_map_enabled=False, distortion_tile=32,
-                             spectrum_enabled=False, spectrum_levels=4):
+                             spectrum_enabled=False, spectrum_levels=4, temporal_enabled=False, temporal_tile=32):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -292,6 +298,8 @@ class VMAFAnalyzer(QObject):
         self.distortion_tile = int(distortion_tile)
         self.spectrum_enabled = bool(spectrum_enabled)
         self.spectrum_levels = int(spectrum_levels)
+        self.temporal_enabled = bool(temporal_enabled)
+        self.temporal_tile = int(temporal_tile)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -470,7 +478,8 @@ class VMAFAnalyzer(QObject):
                                      **report.alignment_log_keys(res.get("alignment")),
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
                                      **report.distortion_log_keys(res.get("distortion")),
-                                     **report.spectrum_log_keys(res.get("spectrum"))})
+                                     **report.spectrum_log_keys(res.get("spectrum")),
+                                     **report.temporal_log_keys(res.get("temporal"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -510,6 +519,7 @@ class VMAFAnalyzer(QObject):
                    if (self.active_picture_enabled or self.active_crop_enabled) else {}),
                 **({"distortion_map": int(self.distortion_tile)} if self.distortion_map_enabled else {}),
                 **({"spectrum": int(self.spectrum_levels)} if self.spectrum_enabled else {}),
+                **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {})}
 
@@ -564,6 +574,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--distortion-map", str(int(self.distortion_tile))]
         if self.spectrum_enabled:
             cmd += ["--spectrum", str(int(self.spectrum_levels))]
+        if self.temporal_enabled:
+            cmd += ["--temporal", str(int(self.temporal_tile))]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -714,6 +726,11 @@ class VMAFAnalyzer(QObject):
                 results["spectrum"] = vmaf_data.get("spectrum")
                 if results["spectrum"]:
                     self.status_update.emit(report.spectrum_summary_line(results["spectrum"]))
+            if self.temporal_enabled:   # whether the motion is wrong, from the log's top level
+                from . import report
+                results["temporal"] = vmaf_data.get("temporal")
+                if results["temporal"]:
+                    self.status_update.emit(report.temporal_summary_line(results["temporal"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
