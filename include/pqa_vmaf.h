@@ -715,6 +715,39 @@ PQA_API int pqa_temporal_moments_device(pqa_ctx* ctx, const pqa_temporal_spec* s
                                         int32_t n_frames, uint64_t* out);
 PQA_API int pqa_temporal_sums(void);
 
+/* Coding-grid detection: the gradient energy per LINE of n_frames frame pairs of one plane, synchronously -- what
+ * pqa2_amd/grid.py turns into the period and phase of a block grid: the one artefact an encoder leg leaves and no other leg
+ * does, which neither the tile moments (per tile) nor the band moments (per octave) localise.  Planes of width x height samples
+ * (the spec's, independent of the context's width and height; each 1 ... 8192), u8 in an 8-bit context, otherwise u16 of the
+ * context's bit depth b (a sample above 2^b - 1 is read as 2^b - 1).  With R the reference and D the captured plane of a frame:
+ *     column line x = 1 ... W - 1, the boundary between the columns x - 1 and x:
+ *         a = R[y][x] - R[y][x-1]   b = D[y][x] - D[y][x-1]   cols[x] = (sum_y a^2, sum_y b^2, sum_y a b)
+ *     row line y = 1 ... H - 1, the boundary between the rows y - 1 and y:
+ *         a = R[y][x] - R[y-1][x]   b = D[y][x] - D[y-1][x]   rows[y] = (sum_x a^2, sum_x b^2, sum_x a b)
+ * and line 0 of each axis is zero (a 1-wide or 1-high plane gives zeros on that axis).  out (host) is [n_frames][H + W][3],
+ * the H row lines first, then the W column lines.  Exact, no floating point anywhere: words 0 and 1 are uint64, word 2 is int64
+ * stored in the word as two's complement (as pqa_temporal_moments does); every sum is below 8192 * 4095^2 < 2^37 in magnitude.
+ * pqa_edge_sums() is 3.  Any context, no feature bit; buffers are made on first use, grow only and are freed with the context.
+ * Independent of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL, before any device
+ * call, on a null pointer, a bad struct_size, a size outside 1 ... 8192, a row pitch that is negative, shorter than a row or no
+ * multiple of the sample size, or a negative frame count.  n_frames == 0 succeeds and writes nothing.  Kernel and accumulator
+ * bounds: DESIGN.md section 5.
+ *
+ * pqa_edge_profiles: frames in HOST memory (ref_frames[f] / dis_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample.
+ * pqa_edge_profiles_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+typedef struct pqa_edge_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane, 1 ... 8192 */
+} pqa_edge_spec;
+PQA_API int pqa_edge_profiles(pqa_ctx* ctx, const pqa_edge_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                              const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out);
+PQA_API int pqa_edge_profiles_device(pqa_ctx* ctx, const pqa_edge_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                     int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                     int32_t n_frames, uint64_t* out);
+PQA_API int pqa_edge_sums(void);
+
 /* Colour-matrix alignment: the cross-plane moments of n_frames frame pairs, synchronously -- what a capture chain that decodes
  * Y'CbCr with one matrix and encodes with another (BT.709 through a BT.601 leg) leaves behind, which no single-plane
  * measurement sees.  Works on the chroma grid of the context: chroma_shift = (hs, vs), s = 2^(hs + vs), chroma planes of

@@ -547,5 +547,23 @@ hipError_t launch_temporal_moments(hipStream_t stream, Elem elem, int bits, cons
                                    int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                    int n_frames, int w, int h, int tile, bool walk, unsigned long long* out);
 
+// ---- coding-grid detection: gradient energy per line of a frame pair (edge_profiles.hip) -------------------------------------
+// With a / b the difference of a sample of the reference / captured plane and its upper neighbour (row line y = 1 ... h - 1,
+// summed over x) or its left neighbour (column line x = 1 ... w - 1, summed over y): out[f][y][0..2] = sum a^2, sum b^2,
+// sum a b (the last as int64) of row line y, then out[f][h + x][0..2] of column line x; line 0 of each axis is zero.  Exact, for
+// n_frames plane pairs of w x h samples (1 ... 8192 each way; frame f at base + f * frame_pitch, pitches in elements; u8 / u16
+// samples of `bits` bits, a sample above 2^bits - 1 is read as that).  out: device memory of edge_out_bytes(), zeroed by the
+// launch.  A workgroup reads a stripe of kEdgeStripe columns by a band of kEdgeBand rows (and the row above each wave's run).
+constexpr int kEdgeStripe = 1024;   // columns of a workgroup: 64 lanes of 16
+constexpr int kEdgeBand = 64;       // rows of a workgroup: a run of 16 consecutive rows a wave
+constexpr int kEdgeSums = 3;        // sums a line
+constexpr int kEdgeChunk = 8;       // frame pairs per launch of the two entries
+size_t edge_out_bytes(int w, int h, int n_frames);
+// rows between two widenings of a lane's 32-bit column sums: floor((2^32 - 1) / top^2), signed floor((2^31 - 1) / top^2)
+int edge_flush_rows(int bit_depth, bool is_signed);
+hipError_t launch_edge_profiles(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
+                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                int n_frames, int w, int h, unsigned long long* out);
+
 }  // namespace pqa
 

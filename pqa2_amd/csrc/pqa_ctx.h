@@ -53,6 +53,7 @@ enum SideBuf {
   SIDE_TILE_OUT,                                                               // pqa_tile_moments[_device], tile_moments.hip: the sums (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS)
   SIDE_BAND_PART, SIDE_BAND_OUT,                                               // pqa_band_moments[_device], band_moments.hip: the workgroups' partial sums of a chunk, the sums (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS)
   SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS, one slot more than a chunk: the predecessor)
+  SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS)
   kSideBufs
 };
 
@@ -166,7 +167,7 @@ struct pqa_ctx {
   bool temporal_walk = false;        // PQA_TEMPORAL_WALK, read once in pqa_create: 1 takes the walking form of temporal_moments.hip (A/B partner; the same integers)
   pqa::RsCached rs_cache[pqa::kRsCached];   // pqa_resample[_device]: the tables of the last few (filter, geometry, window)
   int rs_next = 0;                          // the slot the next new table replaces
-  uint8_t* rs_pin[2] = {nullptr, nullptr};  // pqa_resample: grow-only pinned chunks of source / resampled planes (any plane size); pqa_flow_moments: of reference / captured planes; pqa_colour_moments / pqa_colour_apply: of reference / captured (source / result) frames; pqa_line_profiles: of planes (the first); pqa_tile_moments, pqa_band_moments, pqa_temporal_moments: of reference / captured planes
+  uint8_t* rs_pin[2] = {nullptr, nullptr};  // pqa_resample: grow-only pinned chunks of source / resampled planes (any plane size); pqa_flow_moments: of reference / captured planes; pqa_colour_moments / pqa_colour_apply: of reference / captured (source / result) frames; pqa_line_profiles: of planes (the first); pqa_tile_moments, pqa_band_moments, pqa_temporal_moments, pqa_edge_profiles: of reference / captured planes
   size_t rs_pin_cap[2] = {0, 0};
   void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use
   size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes

@@ -1,5 +1,5 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the registration moments, the line profiles, the tile moments, the band moments, the temporal moments, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
+// temporal / spatial / level alignment, the resampler, the registration moments, the line profiles, the tile moments, the band moments, the temporal moments, the edge profiles, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
 // entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
@@ -360,6 +360,19 @@ int tm_check(pqa_ctx* c, const pqa_temporal_spec* sp, const void* ref, const voi
   if (n_frames < 0) return fail(c, PQA_EINVAL, "temporal_moments: negative frame count");
   if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "temporal_moments: null clip pointer");
   if (n_frames > 1 && !out) return fail(c, PQA_EINVAL, "temporal_moments: null output pointer");
+  return PQA_OK;
+}
+
+// ---- coding-grid detection (edge_profiles.hip): argument rules (no device call) ----------------------------------------------
+int eg_check(pqa_ctx* c, const pqa_edge_spec* sp, const void* ref, const void* dis, int32_t n_frames, const uint64_t* out) {
+  if (!c) return PQA_EINVAL;
+  if (!sp) return fail(c, PQA_EINVAL, "edge_profiles: null spec");
+  if (sp->struct_size != sizeof(pqa_edge_spec)) return fail(c, PQA_EINVAL, "edge_profiles: bad struct_size %u", sp->struct_size);
+  for (uint32_t v : {sp->width, sp->height})
+    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "edge_profiles: plane size %u outside 1 ... 8192", v);
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "edge_profiles: negative frame count");
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "edge_profiles: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "edge_profiles: null output pointer");
   return PQA_OK;
 }
 
@@ -1134,6 +1147,81 @@ int pqa_temporal_moments(pqa_ctx* c, const pqa_temporal_spec* spec, const void* 
     prev_n = n;
   }
   return side_finish(c, "temporal_moments", e, out, dev_out, bytes);
+}
+
+// ---- coding-grid detection (edge_profiles.hip) -------------------------------------------------------------------------------
+
+int pqa_edge_sums(void) { return kEdgeSums; }
+
+int pqa_edge_profiles_device(pqa_ctx* c, const pqa_edge_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
+                             const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, uint64_t* out) {
+  int rc = eg_check(c, spec, ref, dis, n_frames, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
+  rc = check_device_clip(c, "edge_profiles: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
+  if (rc == PQA_OK) rc = check_device_clip(c, "edge_profiles: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = edge_out_bytes(w, h, n_frames), per_frame = edge_out_bytes(w, h, 1) / sizeof(uint64_t);
+  rc = side_reserve(c, SIDE_EDGE_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_EDGE_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kEdgeChunk)
+    e = launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch,
+                             ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch,
+                             dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames, f0, kEdgeChunk), w, h,
+                             dev_out + (size_t)f0 * per_frame);
+  return side_finish(c, "edge_profiles", e, out, dev_out, bytes);
+}
+
+int pqa_edge_profiles(pqa_ctx* c, const pqa_edge_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
+  int rc = eg_check(c, spec, ref_frames, dis_frames, n_frames, out);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
+  const size_t row_bytes = (size_t)w * es;
+  rc = check_host_frames(c, "edge_profiles: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "edge_profiles: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
+  if (rc != PQA_OK) return rc;
+  if (n_frames > 0 && (ref_row_stride % es || dis_row_stride % es))
+    return fail(c, PQA_EINVAL, "edge_profiles: stride is not a multiple of the sample size");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // The planes travel exactly as pqa_tile_moments' do, through the same buffers: chunks of kEdgeChunk pairs through the two
+  // grow-only pinned buffers of pqa_resample into the two device buffers of pqa_flow_moments, rows 16 bytes apart at least, so
+  // the kernel takes its wide loads.  Every chunk's kernel writes its profiles behind the previous chunk's; they come back
+  // once.  A pinned buffer is packed again only after the stream has drained the chunk before.
+  const int64_t pitch = round_up((int64_t)row_bytes, 16);
+  const size_t fb = (size_t)pitch * h;
+  const int chunk = n_frames < kEdgeChunk ? n_frames : kEdgeChunk;
+  const size_t bytes = edge_out_bytes(w, h, n_frames), per_frame = edge_out_bytes(w, h, 1) / sizeof(uint64_t);
+  rc = rs_pin_reserve(c, 0, fb * chunk);
+  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_EDGE_OUT, bytes);
+  if (rc != PQA_OK) return rc;
+  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_EDGE_OUT];
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kEdgeChunk) {
+    const int n = chunk_len(n_frames, f0, kEdgeChunk);
+    if (f0 > 0) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) break;
+    for (int f = 0; f < n; ++f) {
+      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
+      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
+    }
+    e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_REF], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_DIS], c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_FLOW_REF], pitch / es, (int64_t)(fb / es),
+                               c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, dev_out + (size_t)f0 * per_frame);
+  }
+  return side_finish(c, "edge_profiles", e, out, dev_out, bytes);
 }
 
 // ---- active-picture detection (line_profiles.hip) ------------------------------------------------------------------------

@@ -655,6 +655,47 @@ class FeatureEngine:
                                                       out.ctypes.data))
         return self._profile_split(out, sp)
 
+    # -- coding-grid detection -----------------------------------------------------------------
+    @staticmethod
+    def _edge_spec(shape):
+        sp = N.PqaEdgeSpec()
+        sp.struct_size = C.sizeof(N.PqaEdgeSpec)
+        sp.height, sp.width = (max(0, int(v)) for v in (shape[0], shape[1]))
+        return sp
+
+    def edge_profiles(self, ref_frames, dis_frames, shape=None):
+        """(rows [n, H, 3], cols [n, W, 3]) uint64: per row line y (the boundary between the rows y - 1 and y) and per column
+        line x (between the columns x - 1 and x) of every frame pair the sums of a^2, b^2 and a b, with a / b the difference
+        of a reference / captured sample across the line, exact (pqa_edge_profiles; definition: include/pqa_vmaf.h).  Line 0
+        of each axis is zero; word 2 is int64: read it through .view(np.int64).  Planes in HOST memory: two lists of 2-D arrays
+        (views are fine) of equal length and of `shape` = (height, width), default the first frame's, which need not be this
+        context's (1 ... 8192 each way); samples of this context's bit depth.  grid.summary reads the result."""
+        n = len(ref_frames)
+        if len(dis_frames) != n:
+            raise ValueError("edge_profiles needs as many captured as reference frames")
+        if shape is None:
+            shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError("edge_profiles needs 2-D planes")
+        shape = tuple(int(v) for v in shape)
+        sp = self._edge_spec(shape)
+        out = np.zeros((n, sp.height + sp.width, N.EDGE_SUMS), np.uint64)
+        keep_r, rp, rs = self._luma_list(ref_frames, "reference", shape)
+        keep_d, dp, ds = self._luma_list(dis_frames, "captured", shape)
+        self._check(self.lib.pqa_edge_profiles(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
+        del keep_r, keep_d
+        return self._profile_split(out, sp)
+
+    def edge_profiles_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                               dis_frame_pitch: int, shape, n_frames: int):
+        """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_edge_profiles_device)."""
+        sp = self._edge_spec(shape)
+        out = np.zeros((max(int(n_frames), 0), sp.height + sp.width, N.EDGE_SUMS), np.uint64)
+        self._check(self.lib.pqa_edge_profiles_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
+                                                      dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
+        return self._profile_split(out, sp)
+
     # -- colour-matrix alignment ---------------------------------------------------------------
     def _frame_list(self, frames, what: str):
         """(arrays kept alive, ctypes pointer array [n * 3], stride triple) of frames [Y, U, V] in host memory: packed copies

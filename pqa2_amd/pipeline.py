@@ -42,7 +42,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 distortion_min_mse: float = 4.0, spectrum: int = 0, spectrum_planes: str = "y", spectrum_min_mse: float = 1.0,
                 spectrum_gain_floor: float = 0.5, temporal: int = 0, temporal_planes: str = "y", temporal_min_mse: float = 1.0,
                 temporal_blend_min: float = 1 / 16, temporal_still_mse: float = 0.25,
-                temporal_pop_factor: float = 4) -> ScoreResult | None:
+                temporal_pop_factor: float = 4, coding_grid: bool = False, grid_planes: str = "y", grid_periods=(4, 64),
+                grid_z2: float = 25.0) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -151,6 +152,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     `temporal_min_mse`, blend: weight at least `temporal_blend_min`, loss, noise); `frames` one row a transition.  The luma
     adds the per-frame metric columns `temporal_gain`, `temporal_noise_mse` and `blend_weight` (frame 0 has no transition:
     1, 0 and 0, as `motion` is 0 there).  `temporal` = 0: nothing is measured and the result has none of it.
+    `coding_grid` = True: whether the difference between the scored clips is a BLOCK GRID, the artefact of an encoder leg.  After
+    every alignment step, in the same pass as the distortion map, the spectrum and the temporal distortion when those are asked
+    for, every frame pair of this rank's shard goes through FeatureEngine.edge_profiles (pqa_edge_profiles: the exact gradient
+    energy of both clips and their cross term per row and column line) for the luma (`grid_planes` = "y") or all three planes
+    ("all"; a monochrome clip is an error).  Rank 0 runs the solver (pqa2_amd/grid.py) over the periods `grid_periods` =
+    (lo, hi), 4 <= lo <= hi <= 64, accepting from z^2 >= `grid_z2`: `res["coding_grid"]` holds {planes: {y | cb | cr:
+    {summary, frames}}}; `summary` the `kind` (identical, none, grid), `block` [Px, Py], `phase` and `aligned` -- phases are in
+    the coordinates of the SCORED window, after any crop or shift applied here, not of the file -- and the same search on each
+    clip alone (`reference_grid`, `captured_grid`); `frames` one row a frame.  The luma adds the per-frame metric columns
+    `blockiness_x` and `blockiness_y` (1 where there is no grid).  False: nothing is measured and the result has none of it.
 
     `distortion_map` = T (8, 16, 32 or 64): a distortion map of the scored clips -- WHERE inside the frame they differ.  After
     every alignment step, on exactly the readers the scoring loop sees, a second pass reads every frame pair of this rank's
@@ -297,6 +308,19 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             raise ValueError('temporal_planes="all" needs the chroma planes, but the clips are monochrome')
         if any(v is None or v < 0 for v in (temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)):
             raise ValueError("temporal_min_mse, temporal_blend_min, temporal_still_mse and temporal_pop_factor must not be negative")
+    if coding_grid:
+        if grid_planes not in ("y", "all"):
+            raise ValueError('grid_planes must be "y" or "all"')
+        if grid_planes == "all" and ri.mono:
+            raise ValueError('grid_planes="all" needs the chroma planes, but the clips are monochrome')
+        try:
+            g_lo, g_hi = (int(v) for v in grid_periods)
+        except (TypeError, ValueError):
+            raise ValueError("grid_periods must be a pair (lo, hi) with 4 <= lo <= hi <= 64") from None
+        if g_lo < 4 or g_hi < g_lo or g_hi > 64:
+            raise ValueError("grid_periods must be a pair (lo, hi) with 4 <= lo <= hi <= 64")
+        if grid_z2 is None or grid_z2 < 0:
+            raise ValueError("grid_z2 must not be negative")
     if cambi_full_ref and not cambi:
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
@@ -395,13 +419,14 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         eng.close()
         raise
     (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
-    dmap = bands = tmom = None
-    if distortion_map or spectrum or temporal:      # ONE pass of its own over the same readers, after the scoring context is parked
-        dmap, bands, tmom = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
-                                             engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
-                                             gather_device, cancelled, levels=int(spectrum),
-                                             band_planes=3 if spectrum_planes == "all" else 1, temporal_tile=int(temporal),
-                                             temporal_planes=3 if temporal_planes == "all" else 1)
+    dmap = bands = tmom = edges = None
+    if distortion_map or spectrum or temporal or coding_grid:      # ONE pass of its own over the same readers, after the scoring context is parked
+        dmap, bands, tmom, edges = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
+                                                    engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
+                                                    gather_device, cancelled, levels=int(spectrum),
+                                                    band_planes=3 if spectrum_planes == "all" else 1, temporal_tile=int(temporal),
+                                                    temporal_planes=3 if temporal_planes == "all" else 1,
+                                                    edge_planes=(3 if grid_planes == "all" else 1) if coding_grid else 0)
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
     ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
@@ -464,6 +489,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         _spectrum_result(res, bands, ri, int(spectrum), spectrum_min_mse, spectrum_gain_floor)
     if tmom is not None:
         _temporal_result(res, tmom, ri, int(temporal), temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)
+    if edges is not None:
+        _grid_result(res, edges, ri, range(g_lo, g_hi + 1), grid_z2)
     if alignment is not None:
         res["alignment"] = alignment
     if resized is not None:
@@ -788,9 +815,11 @@ DISTORTION_PLANES = ("y", "cb", "cr")
 
 def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes: int, device, make, world_size: int,
                      rank: int, gather_device, cancelled=None, levels: int = 0, band_planes: int = 1, temporal_tile: int = 0,
-                     temporal_planes: int = 1):
-    """the measurement of score_files(distortion_map=), of score_files(spectrum=) and of score_files(temporal=), in one pass
-    that reads every frame pair once, on every rank: (dmap, bands, temporal).  temporal (temporal_tile > 0, else None): per
+                     temporal_planes: int = 1, edge_planes: int = 0):
+    """the measurement of score_files(distortion_map=), of score_files(spectrum=), of score_files(temporal=) and of
+    score_files(coding_grid=), in one pass that reads every frame pair once, on every rank: (dmap, bands, temporal, edges).
+    edges (edge_planes > 0, else None): per plane the edge profiles of every frame of the clip, uint64 (rows [n, H, 3],
+    cols [n, W, 3]).  temporal (temporal_tile > 0, else None): per
     plane the temporal moments of every transition of the clip, uint64 [n - 1, ty, tx, 7]; a rank whose chunk starts at frame
     a > 0 also reads frame a - 1, so transition a is measured by the rank that owns frame a and the result does not depend
     on the number of ranks.  dmap (tile > 0, else None): per plane (tile SSE of every frame of the clip, uint64
@@ -806,7 +835,9 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
         band_planes = 0
     if not temporal_tile:
         temporal_planes = 0
-    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (max(n_planes, band_planes, temporal_planes) - 1)
+    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (max(n_planes, band_planes, temporal_planes, edge_planes) - 1)
+    edge_rows = [np.zeros((b - a, h + w, N.EDGE_SUMS), np.uint64) for w, h in sizes[:edge_planes]]   # a frame: H row lines, W column lines
+    assert N.EDGE_CHUNK == N.TILE_CHUNK
     tgrids = [DM.tile_counts(w, h, temporal_tile).shape for w, h in sizes[:temporal_planes]]
     trows = [np.zeros((b - a,) + g + (N.TEMPORAL_SUMS,), np.uint64) for g in tgrids]   # row i - a: the transition INTO frame i
     assert N.TEMPORAL_CHUNK == N.TILE_CHUNK
@@ -837,6 +868,9 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
                     sse[p][i0 - a:i0 - a + len(idx)] = DM.tile_sse(M)
                 for p in range(band_planes):
                     band_rows[p][i0 - a:i0 - a + len(idx)] = eng.band_moments([f[p] for f in rf], [f[p] for f in df], levels)
+                for p in range(edge_planes):
+                    er, ec = eng.edge_profiles([f[p] for f in rf], [f[p] for f in df])
+                    edge_rows[p][i0 - a:i0 - a + len(idx)] = np.concatenate([er, ec], axis=1)
         finally:
             eng.close()
     bands = []
@@ -857,7 +891,27 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
         cells = g[0] * g[1] * N.TEMPORAL_SUMS
         T = shard.gather_records(trows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
         tmom.append(np.ascontiguousarray(T).view(np.uint64).reshape((n,) + g + (N.TEMPORAL_SUMS,))[1:])   # frame 0 has no transition
-    return (out if tile else None), (bands if levels else None), (tmom if temporal_tile else None)
+    edges = []
+    for p, (w, h) in enumerate(sizes[:edge_planes]):
+        cells = (h + w) * N.EDGE_SUMS
+        E = shard.gather_records(edge_rows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
+        E = np.ascontiguousarray(E).view(np.uint64).reshape(n, h + w, N.EDGE_SUMS)
+        edges.append((E[:, :h], E[:, h:]))
+    return (out if tile else None), (bands if levels else None), (tmom if temporal_tile else None), (edges if edge_planes else None)
+
+
+def _grid_result(res, edges, info, periods, z2_min) -> None:
+    """rank 0: the solver on the gathered edge profiles; adds res["coding_grid"] and the two luma columns"""
+    from . import grid as GD
+    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(edges) - 1)
+    planes = {}
+    for name, (rows, cols), (w, h) in zip(DISTORTION_PLANES, edges, sizes):
+        planes[name] = GD.analyse(rows, cols, w, h, info.bit_depth, periods=periods, z2_min=z2_min)
+        if name == "y":
+            keep = np.asarray(res["frame_indices"])
+            for key, col in GD.frame_columns(planes[name]["frames"]).items():
+                res["metrics"][key] = col[keep]
+    res["coding_grid"] = {"planes": planes}
 
 
 def _temporal_result(res, tmom, info, tile: int, min_mse, blend_min, still_mse, pop_factor) -> None:

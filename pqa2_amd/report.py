@@ -240,6 +240,31 @@ def temporal_summary_line(temporal: dict) -> str:
     return line
 
 
+def grid_log_keys(coding_grid: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the coding-grid detection (pipeline.score_files(coding_grid=True)); none
+    without it.  Any float that is not finite becomes null."""
+    if not coding_grid:
+        return {}
+    return {"coding_grid": distortion_log_keys(coding_grid)["distortion"]}
+
+
+def grid_summary_line(coding_grid: dict) -> str:
+    """One line for a summary or a status bar: the block grid found in the luma."""
+    s = coding_grid.get("planes", {}).get("y", {}).get("summary", {})
+    line = f"Coding grid: {s.get('kind', '?')}"
+    if s.get("kind") == "grid":
+        px, py = s.get("block") or (None, None)
+        fx, fy = s.get("phase") or (None, None)
+        line += (f", blocks of {px or '?'} x {py or '?'} at phase ({'?' if fx is None else fx}, {'?' if fy is None else fy})"
+                 f"{'' if s.get('aligned') else ': cropped or shifted after the encode'}")
+        z = [g["z2"] for g in (s.get("x"), s.get("y")) if g]
+        if z:
+            line += f", z^2 {max(z):.0f}"
+    if any((s.get("reference_grid") or {}).get(k) for k in ("x", "y")):
+        line += "; the reference has a grid of its own"
+    return line
+
+
 def distortion_summary_line(distortion: dict) -> str:
     """One line for a summary or a status bar: the defects and persistent regions found in the luma."""
     y = distortion.get("planes", {}).get("y", {})

@@ -164,6 +164,19 @@ def main(argv=None) -> int:
                          "values squared (default 1/4)")
     ap.add_argument("--temporal-pop-factor", type=float, default=4, metavar="F",
                     help="with --temporal: a transition pops when its noise exceeds F times the clip's median (default 4)")
+    ap.add_argument("--coding-grid", action="store_true",
+                    help="detect a block grid in the difference between the clips, the artefact of an encoder leg: the gradient "
+                         "energy of both clips per row and column line, in a second pass over both clips (shared with "
+                         "--distortion-map, --spectrum and --temporal); the JSON gets a top-level coding_grid object (period and "
+                         "phase each way, in the coordinates of the scored window) and two per-frame metrics")
+    ap.add_argument("--grid-planes", default="y", choices=["y", "all"],
+                    help="with --coding-grid: the luma only (default) or all three planes")
+    ap.add_argument("--grid-min-period", type=int, default=4, metavar="P",
+                    help="with --coding-grid: the smallest block size searched, at least 4 (default 4)")
+    ap.add_argument("--grid-max-period", type=int, default=64, metavar="P",
+                    help="with --coding-grid: the largest block size searched, at most 64 (default 64)")
+    ap.add_argument("--grid-z2", type=float, default=25.0, metavar="Z",
+                    help="with --coding-grid: a period is accepted when the squared z score of its votes is at least Z (default 25)")
     ap.add_argument("--resize", default=None, metavar="FILTER", choices=["bilinear", "bicubic", "lanczos"],
                     help="resample a distorted clip whose frame size differs from the reference's to it before scoring "
                          "(exact-integer polyphase filter: bilinear, bicubic or lanczos); the JSON gets a top-level resize object")
@@ -234,6 +247,9 @@ def main(argv=None) -> int:
                           **({"temporal": a.temporal, "temporal_planes": a.temporal_planes, "temporal_min_mse": a.temporal_min_mse,
                               "temporal_blend_min": a.temporal_blend_min, "temporal_still_mse": a.temporal_still_mse,
                               "temporal_pop_factor": a.temporal_pop_factor} if a.temporal else {}),
+                          **({"coding_grid": True, "grid_planes": a.grid_planes,
+                              "grid_periods": (a.grid_min_period, a.grid_max_period), "grid_z2": a.grid_z2}
+                             if a.coding_grid else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
@@ -253,7 +269,8 @@ def main(argv=None) -> int:
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
                                      **report.distortion_log_keys(res.get("distortion")),
                                      **report.spectrum_log_keys(res.get("spectrum")),
-                                     **report.temporal_log_keys(res.get("temporal"))})
+                                     **report.temporal_log_keys(res.get("temporal")),
+                                     **report.grid_log_keys(res.get("coding_grid"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -285,6 +302,8 @@ def main(argv=None) -> int:
             print(report.spectrum_summary_line(res["spectrum"]), file=sys.stderr, flush=True)
         if res.get("temporal"):
             print(report.temporal_summary_line(res["temporal"]), file=sys.stderr, flush=True)
+        if res.get("coding_grid"):
+            print(report.grid_summary_line(res["coding_grid"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

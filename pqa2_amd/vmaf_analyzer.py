@@ -175,6 +175,8 @@ class VMAFAnalyzer(QObject):
         self.spectrum_levels = 4              # pass; score_files(spectrum=)); its number of octaves: 1 ... 6
         self.temporal_enabled = False         # temporal distortion: whether the motion of the capture is wrong (the same second
         self.temporal_tile = 32               # pass; score_files(temporal=)); its tile size: 8, 16, 32 or 64
+        self.coding_grid_enabled = False      # coding-grid detection: whether the difference is a block grid (the same second
+                                              # pass; score_files(coding_grid=))
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -247,6 +249,8 @@ class VMAFAnalyzer(QObject):
                 self.temporal_enabled = bool(s["temporal_enabled"])
             if "temporal_tile" in s:
                 self.temporal_tile = int(s["temporal_tile"])
+            if "coding_grid_enabled" in s:
+                self.coding_grid_enabled = bool(s["coding_grid_enabled"])
 
     set_options_manager = set_options_from_manager
 
@@ -267,7 +271,8 @@ class VMAFAnalyzer(QObject):
                              spatial_align_radius=8, level_align_enabled=False, level_correct_enabled=False,
                              colour_align_enabled=False, colour_correct_enabled=False, active_picture_enabled=False,
                              active_crop_enabled=False, distortion_map_enabled=False, distortion_tile=32,
-                             spectrum_enabled=False, spectrum_levels=4, temporal_enabled=False, temporal_tile=32):
+                             spectrum_enabled=False, spectrum_levels=4, temporal_enabled=False, temporal_tile=32,
+                             coding_grid_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -300,6 +305,7 @@ class VMAFAnalyzer(QObject):
         self.spectrum_levels = int(spectrum_levels)
         self.temporal_enabled = bool(temporal_enabled)
         self.temporal_tile = int(temporal_tile)
+        self.coding_grid_enabled = bool(coding_grid_enabled)
 
     def terminate_analysis(self):
         """Terminate a running analysis (legal from another thread, like the reference's)."""
@@ -479,7 +485,8 @@ class VMAFAnalyzer(QObject):
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
                                      **report.distortion_log_keys(res.get("distortion")),
                                      **report.spectrum_log_keys(res.get("spectrum")),
-                                     **report.temporal_log_keys(res.get("temporal"))})
+                                     **report.temporal_log_keys(res.get("temporal")),
+                                     **report.grid_log_keys(res.get("coding_grid"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -520,6 +527,7 @@ class VMAFAnalyzer(QObject):
                 **({"distortion_map": int(self.distortion_tile)} if self.distortion_map_enabled else {}),
                 **({"spectrum": int(self.spectrum_levels)} if self.spectrum_enabled else {}),
                 **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
+                **({"coding_grid": True} if self.coding_grid_enabled else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {})}
 
@@ -576,6 +584,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--spectrum", str(int(self.spectrum_levels))]
         if self.temporal_enabled:
             cmd += ["--temporal", str(int(self.temporal_tile))]
+        if self.coding_grid_enabled:
+            cmd += ["--coding-grid"]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -731,6 +741,11 @@ class VMAFAnalyzer(QObject):
                 results["temporal"] = vmaf_data.get("temporal")
                 if results["temporal"]:
                     self.status_update.emit(report.temporal_summary_line(results["temporal"]))
+            if self.coding_grid_enabled:   # whether the difference is a block grid, from the log's top level
+                from . import report
+                results["coding_grid"] = vmaf_data.get("coding_grid")
+                if results["coding_grid"]:
+                    self.status_update.emit(report.grid_summary_line(results["coding_grid"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
