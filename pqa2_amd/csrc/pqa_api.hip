@@ -1322,7 +1322,7 @@ void pqa_destroy(pqa_ctx* c) {
   }
   for (void* b : c->side_buf)
     if (b) hipFree(b);
-  for (uint8_t* b : c->rs_pin)
+  for (uint8_t* b : c->side_pin)
     if (b) hipHostFree(b);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   for (int i = 0; i < 2; ++i) {

@@ -13,6 +13,7 @@
 
 #include "host_pack.h"
 #include "host_ring.h"
+#include "host_stage.h"
 #include "kernels.h"
 
 namespace pqa {
@@ -47,13 +48,14 @@ enum SideBuf {
   SIDE_LEVEL_OUT,                                                              // pqa_level_stats[_device], level_stats.hip
   SIDE_RS_TABLE0, SIDE_RS_TABLE1, SIDE_RS_TABLE2, SIDE_RS_TABLE3,              // pqa_resample[_device], resample.hip: cached tables
   SIDE_RS_SRC, SIDE_RS_DST,                                                    // pqa_resample: a chunk of uploaded / resampled planes
-  SIDE_FLOW_REF, SIDE_FLOW_DIS, SIDE_FLOW_OUT,                                 // pqa_flow_moments[_device], flow_moments.hip
+  SIDE_PAIR_REF, SIDE_PAIR_DIS,                                                // the pair staging (pair_run, pqa_side.hip): a chunk of uploaded reference / captured planes of the call's own size
+  SIDE_FLOW_OUT,                                                               // pqa_flow_moments[_device], flow_moments.hip: the sums
   SIDE_COLOUR_A, SIDE_COLOUR_B, SIDE_COLOUR_OUT,                               // pqa_colour_moments / pqa_colour_apply, colour_moments.hip: a chunk of reference / captured (source / result) frames, the sums
   SIDE_PROF_SRC, SIDE_PROF_OUT,                                                // pqa_line_profiles[_device], line_profiles.hip: a chunk of uploaded planes, the profiles
-  SIDE_TILE_OUT,                                                               // pqa_tile_moments[_device], tile_moments.hip: the sums (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS)
-  SIDE_BAND_PART, SIDE_BAND_OUT,                                               // pqa_band_moments[_device], band_moments.hip: the workgroups' partial sums of a chunk, the sums (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS)
-  SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS, one slot more than a chunk: the predecessor)
-  SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles (the planes travel through SIDE_FLOW_REF / SIDE_FLOW_DIS)
+  SIDE_TILE_OUT,                                                               // pqa_tile_moments[_device], tile_moments.hip: the sums
+  SIDE_BAND_PART, SIDE_BAND_OUT,                                               // pqa_band_moments[_device], band_moments.hip: the workgroups' partial sums of a chunk, the sums
+  SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums
+  SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles
   kSideBufs
 };
 
@@ -167,8 +169,8 @@ struct pqa_ctx {
   bool temporal_walk = false;        // PQA_TEMPORAL_WALK, read once in pqa_create: 1 takes the walking form of temporal_moments.hip (A/B partner; the same integers)
   pqa::RsCached rs_cache[pqa::kRsCached];   // pqa_resample[_device]: the tables of the last few (filter, geometry, window)
   int rs_next = 0;                          // the slot the next new table replaces
-  uint8_t* rs_pin[2] = {nullptr, nullptr};  // pqa_resample: grow-only pinned chunks of source / resampled planes (any plane size); pqa_flow_moments: of reference / captured planes; pqa_colour_moments / pqa_colour_apply: of reference / captured (source / result) frames; pqa_line_profiles: of planes (the first); pqa_tile_moments, pqa_band_moments, pqa_temporal_moments, pqa_edge_profiles: of reference / captured planes
-  size_t rs_pin_cap[2] = {0, 0};
+  uint8_t* side_pin[2] = {nullptr, nullptr};   // the side analyses' two grow-only pinned chunks (side_pin_reserve, pqa_side.hip): the chunk a host entry packs before its upload (pqa_resample, pqa_colour_apply: the second takes the chunk that comes back), of any plane size
+  size_t side_pin_cap[2] = {0, 0};
   void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use
   size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes
   // motion continuity
@@ -235,16 +237,6 @@ int dev_alloc(pqa_ctx* c, T** out, size_t count) {
   c->allocs.push_back(p);
   *out = (T*)p;
   return PQA_OK;
-}
-
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-inline void copy_plane_rows(uint8_t* dst, int64_t dst_pitch, const uint8_t* src, int64_t src_pitch, size_t row_bytes, int h) {
-  if (dst_pitch == src_pitch) {
-    memcpy(dst, src, (size_t)dst_pitch * (h - 1) + row_bytes);
-    return;
-  }
-  for (int y = 0; y < h; ++y) memcpy(dst + (int64_t)y * dst_pitch, src + (int64_t)y * src_pitch, row_bytes);
 }
 
 }  // namespace pqa

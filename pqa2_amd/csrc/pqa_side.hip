@@ -1,6 +1,9 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the registration moments, the line profiles, the tile moments, the band moments, the temporal moments, the edge profiles, the colour moments and matrix apply.  Each has an entry for a clip in HBM and one for frames in host memory; the host
-// entries share one staging path (stage_frames), every entry ends in one epilogue (side_finish).
+// temporal / spatial / level alignment, the resampler, the colour moments and matrix apply, and the spec-driven analyses of
+// planes of the call's own size (registration moments, tile / band / temporal moments, edge and line profiles).  Each has an
+// entry for a clip in HBM and one for frames in host memory.  Host frames of the context's size take the luma-halves staging
+// (stage_frames); the spec-driven analyses share one checker and one driver per kind of clip (spec_check, pair_run), whose
+// host side is host_stage.h.  Every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
 
@@ -116,6 +119,19 @@ int side_reserve(pqa_ctx* c, SideBuf which, size_t bytes) {
   return PQA_OK;
 }
 
+// one of the two grow-only pinned chunks of the side analyses
+int side_pin_reserve(pqa_ctx* c, int which, size_t bytes) {
+  if (c->side_pin_cap[which] >= bytes) return PQA_OK;
+  if (c->side_pin[which]) {
+    HIPCHK(c, hipHostFree(c->side_pin[which]));
+    c->side_pin[which] = nullptr;
+    c->side_pin_cap[which] = 0;
+  }
+  HIPCHK(c, hipHostMalloc((void**)&c->side_pin[which], bytes, hipHostMallocDefault));
+  c->side_pin_cap[which] = bytes;
+  return PQA_OK;
+}
+
 // the launch of pqa_frame_sad[_device]: n frames (at most B) of a device clip against the anchor planes, results to out
 int frame_sad_launch(pqa_ctx* c, const void* const anchor[3], const int64_t anchor_pitch_bytes[3], const pqa_device_clip* f,
                      int n, uint64_t* out) {
@@ -190,7 +206,7 @@ int lv_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int
 }
 
 
-// ---- resampler (resample.hip): argument rules (no device call), tables, pinned chunks ---------------------------------
+// ---- resampler (resample.hip): argument rules (no device call), tables ------------------------------------------------
 int rs_check(pqa_ctx* c, const pqa_resample_spec* sp) {
   if (!c) return PQA_EINVAL;
   if (!sp) return fail(c, PQA_EINVAL, "resample: null spec");
@@ -231,30 +247,230 @@ int rs_tables(pqa_ctx* c, const pqa_resample_spec* sp, int* slot) {
   return PQA_OK;
 }
 
-int rs_pin_reserve(pqa_ctx* c, int which, size_t bytes) {
-  if (c->rs_pin_cap[which] >= bytes) return PQA_OK;
-  if (c->rs_pin[which]) {
-    HIPCHK(c, hipHostFree(c->rs_pin[which]));
-    c->rs_pin[which] = nullptr;
-    c->rs_pin_cap[which] = 0;
-  }
-  HIPCHK(c, hipHostMalloc((void**)&c->rs_pin[which], bytes, hipHostMallocDefault));
-  c->rs_pin_cap[which] = bytes;
+// ---- the spec-driven analyses of a clip pair (or, pqa_line_profiles, of one clip): planes of the call's own size -----------
+// pqa_flow_moments, pqa_tile_moments, pqa_band_moments, pqa_temporal_moments, pqa_edge_profiles and pqa_line_profiles differ
+// in their spec, their kernel and what a PairJob names; one checker, one driver for clips in HBM and one for host frames.
+
+// The argument rules, in the order in which they fire (no device call): null spec, struct_size, `rule` (the entry's own, on
+// its third field), plane size, negative count, null clips, null out.  dis: the second clip, or the first again when there
+// is only one; `out` may be null below out_from frames.
+template <class Spec, class Rule>
+int spec_check(pqa_ctx* c, const char* who, const Spec* sp, uint32_t min_size, const void* ref, const void* dis, int32_t n_frames,
+               const void* out, int out_from, Rule rule) {
+  if (!c) return PQA_EINVAL;
+  if (!sp) return fail(c, PQA_EINVAL, "%s: null spec", who);
+  if (sp->struct_size != sizeof(Spec)) return fail(c, PQA_EINVAL, "%s: bad struct_size %u", who, sp->struct_size);
+  const int rc = rule();
+  if (rc != PQA_OK) return rc;
+  for (uint32_t v : {sp->width, sp->height})
+    if (v < min_size || v > 8192) return fail(c, PQA_EINVAL, "%s: plane size %u outside %u ... 8192", who, v, min_size);
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "%s: negative frame count", who);
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "%s: null clip pointer", who);
+  if (n_frames >= out_from && !out) return fail(c, PQA_EINVAL, "%s: null output pointer", who);
   return PQA_OK;
 }
 
-// ---- registration moments (flow_moments.hip): argument rules (no device call) --------------------------------------------
-int fl_check(pqa_ctx* c, const pqa_flow_spec* sp, const void* ref, const void* dis, int32_t n_frames, const int64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!sp) return fail(c, PQA_EINVAL, "flow_moments: null spec");
-  if (sp->struct_size != sizeof(pqa_flow_spec)) return fail(c, PQA_EINVAL, "flow_moments: bad struct_size %u", sp->struct_size);
-  if (sp->tile > 64 || !flow_tile_ok((int)sp->tile)) return fail(c, PQA_EINVAL, "flow_moments: tile %u is not 8, 16, 32 or 64", sp->tile);
-  for (uint32_t v : {sp->width, sp->height})
-    if (v < 3 || v > 8192) return fail(c, PQA_EINVAL, "flow_moments: plane size %u outside 3 ... 8192", v);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "flow_moments: negative frame count");
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "flow_moments: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "flow_moments: null output pointer");
-  return PQA_OK;
+struct HostClip {   // a list of planes in host memory, rows `stride` bytes apart
+  const void* const* at;
+  int64_t stride;
+};
+struct DevClip {   // planes in HBM, pitches in bytes
+  const void* at;
+  int64_t row_pitch, frame_pitch;
+};
+
+// What an analysis asks of a driver.  carry 0: a result per frame.  carry 1 (pqa_temporal_moments): a result per transition,
+// so a launch also reads the frame in front of its first transition, and fewer than two frames are no work.
+struct PairJob {
+  const char* who;   // opens every message
+  int w, h;
+  int32_t n_frames;
+  int chunk, carry;   // chunk: results per launch
+  SideBuf out_buf;
+  size_t out_bytes;   // of all results: they come back once
+  void* out;
+  bool whole_samples = true;       // host frames: refuse a stride that is no multiple of the sample size
+  SideBuf part_buf = kSideBufs;    // a workspace of part_bytes that the launches share (pqa_band_moments)
+  size_t part_bytes = 0;
+};
+
+int job_reserve(pqa_ctx* c, const PairJob& j) {
+  const int rc = j.part_buf != kSideBufs ? side_reserve(c, j.part_buf, j.part_bytes) : PQA_OK;
+  return rc == PQA_OK ? side_reserve(c, j.out_buf, j.out_bytes) : rc;
+}
+
+// Clips in HBM (dis null: one clip).  launch(ref run, dis run, n frames, index of the first result) queues a kernel.
+template <class Launch>
+int pair_run(pqa_ctx* c, const PairJob& j, const DevClip& ref, const DevClip* dis, Launch launch) {
+  const int es = c->esize;
+  char who[48];
+  snprintf(who, sizeof who, dis ? "%s: reference " : "%s: ", j.who);
+  int rc = check_device_clip(c, who, ref.row_pitch, ref.frame_pitch, (int64_t)j.w * es);
+  if (rc == PQA_OK && dis) {
+    snprintf(who, sizeof who, "%s: captured ", j.who);
+    rc = check_device_clip(c, who, dis->row_pitch, dis->frame_pitch, (int64_t)j.w * es);
+  }
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (j.n_frames <= j.carry) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = job_reserve(c, j);
+  if (rc != PQA_OK) return rc;
+  const auto run = [&](const DevClip* k, int f0) {
+    return k ? PlaneRun{(const uint8_t*)k->at + (int64_t)f0 * k->frame_pitch, k->row_pitch / es, k->frame_pitch / es} : PlaneRun{};
+  };
+  const int results = j.n_frames - j.carry;
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < results && e == hipSuccess; f0 += j.chunk)   // the launches share what they share in stream order
+    e = launch(run(&ref, f0), run(dis, f0), chunk_len(results, f0, j.chunk) + j.carry, f0);
+  return side_finish(c, j.who, e, j.out, c->side_buf[j.out_buf], j.out_bytes);
+}
+
+// Host frames (dis null: one clip).  The planes are the call's own size, so they travel in chunks through the two grow-only
+// pinned chunks (the reference planes through the first, the captured ones through the second) into the pair staging's two
+// device buffers -- one clip: through the first into SIDE_PROF_SRC -- as host_stage.h lays out: packed rows, a chunk
+// launched before the next is packed, with carry 1 the last pair of a chunk kept as predecessor of the next.  Every entry
+// here is synchronous, so no two calls are ever in flight in these buffers.  Every launch writes its results behind the
+// previous one's; they come back once.
+template <class Launch>
+int pair_run(pqa_ctx* c, const PairJob& j, const HostClip& ref, const HostClip* dis, Launch launch) {
+  const int es = c->esize;
+  const host::PlaneLayout L = host::plane_layout((size_t)j.w * es, j.h);
+  char who[48];
+  snprintf(who, sizeof who, "%s: ", j.who);
+  int rc = check_host_frames(c, who, dis ? "reference " : "", ref.at, 1, j.n_frames, ref.stride, L.row_bytes, true);
+  if (rc == PQA_OK && dis) rc = check_host_frames(c, who, "captured ", dis->at, 1, j.n_frames, dis->stride, L.row_bytes, true);
+  if (rc != PQA_OK) return rc;
+  if (j.whole_samples && j.n_frames > 0 && (ref.stride % es || (dis && dis->stride % es)))
+    return fail(c, PQA_EINVAL, "%s: stride is not a multiple of the sample size", j.who);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (j.n_frames <= j.carry) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t fb = L.frame_bytes, slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk);
+  const SideBuf ref_buf = dis ? SIDE_PAIR_REF : SIDE_PROF_SRC;
+  rc = side_pin_reserve(c, 0, fb * slots);
+  if (rc == PQA_OK && dis) rc = side_pin_reserve(c, 1, fb * slots);
+  if (rc == PQA_OK) rc = side_reserve(c, ref_buf, fb * (slots + j.carry));
+  if (rc == PQA_OK && dis) rc = side_reserve(c, SIDE_PAIR_DIS, fb * (slots + j.carry));
+  if (rc == PQA_OK) rc = job_reserve(c, j);
+  if (rc != PQA_OK) return rc;
+  uint8_t* const dev[2] = {(uint8_t*)c->side_buf[ref_buf], dis ? (uint8_t*)c->side_buf[SIDE_PAIR_DIS] : nullptr};
+  const int clips = dis ? 2 : 1;
+  const auto copy = [&](int to_slot, const uint8_t* const from[2], size_t from_off, size_t bytes, hipMemcpyKind kind) {
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < clips && e == hipSuccess; ++k)
+      e = hipMemcpyAsync(dev[k] + (size_t)to_slot * fb, from[k] + from_off, bytes, kind, c->stream);
+    return e;
+  };
+  const hipError_t e = host::stage_walk(
+      L, c->side_pin, ref.at, ref.stride, dis ? dis->at : nullptr, dis ? dis->stride : 0, j.n_frames, j.chunk, j.carry, c->cancelled,
+      [&] { return hipStreamSynchronize(c->stream); },
+      [&](int from_slot) { return copy(0, dev, (size_t)from_slot * fb, fb, hipMemcpyDeviceToDevice); },   // from_slot >= 1: no overlap
+      [&](int slot, int n) { return copy(slot, c->side_pin, 0, fb * n, hipMemcpyHostToDevice); },
+      [&](int slot, int n, int out_index) {
+        const auto run = [&](uint8_t* base) { return PlaneRun{base ? base + (size_t)slot * fb : nullptr, L.pitch / es, (int64_t)(fb / es)}; };
+        return launch(run(dev[0]), run(dev[1]), n, out_index);
+      });
+  return side_finish(c, j.who, e, j.out, c->side_buf[j.out_buf], j.out_bytes);
+}
+
+// ---- the spec-driven analyses (spec_check, pair_run above) ----------------------------------------------------------------
+// Clip is HostClip or DevClip: both entries of an analysis are one body, which checks, sizes its results and names its launch.
+// A launch's results lie `at` results into the analysis' output buffer.
+
+// registration moments (flow_moments.hip); this one lets a stride that is no multiple of the sample size pass
+template <class Clip>
+int flow_moments(pqa_ctx* c, const pqa_flow_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, int64_t* out) {
+  const int rc = spec_check(c, "flow_moments", sp, 3, ref.at, dis.at, n_frames, out, 1, [&] {
+    return sp->tile > 64 || !flow_tile_ok((int)sp->tile) ? fail(c, PQA_EINVAL, "flow_moments: tile %u is not 8, 16, 32 or 64", sp->tile) : PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height, tile = (int)sp->tile;
+  const size_t per_frame = flow_out_bytes(w, h, tile, 1) / sizeof(long long);
+  const PairJob j{"flow_moments", w, h, n_frames, kFlowChunk, 0, SIDE_FLOW_OUT, flow_out_bytes(w, h, tile, n_frames), out, false};
+  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
+    return launch_flow_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
+                               d.frame_pitch, n, w, h, tile, (long long*)c->side_buf[SIDE_FLOW_OUT] + (size_t)at * per_frame);
+  });
+}
+
+// distortion map (tile_moments.hip)
+template <class Clip>
+int tile_moments(pqa_ctx* c, const pqa_tile_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, uint64_t* out) {
+  const int rc = spec_check(c, "tile_moments", sp, 1, ref.at, dis.at, n_frames, out, 1, [&] {
+    return sp->tile > 64 || !tile_size_ok((int)sp->tile) ? fail(c, PQA_EINVAL, "tile_moments: tile %u is not 8, 16, 32 or 64", sp->tile) : PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height, tile = (int)sp->tile;
+  const size_t per_frame = tile_out_bytes(w, h, tile, 1) / sizeof(uint64_t);
+  const PairJob j{"tile_moments", w, h, n_frames, kTileChunk, 0, SIDE_TILE_OUT, tile_out_bytes(w, h, tile, n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
+    return launch_tile_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
+                               d.frame_pitch, n, w, h, tile, (unsigned long long*)c->side_buf[SIDE_TILE_OUT] + (size_t)at * per_frame);
+  });
+}
+
+// distortion spectrum (band_moments.hip); the launches share the workgroups' partial sums of a chunk
+template <class Clip>
+int band_moments(pqa_ctx* c, const pqa_band_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, uint64_t* out) {
+  const int rc = spec_check(c, "band_moments", sp, 1, ref.at, dis.at, n_frames, out, 1, [&] {
+    return sp->levels > 6 || !band_levels_ok((int)sp->levels) ? fail(c, PQA_EINVAL, "band_moments: %u levels outside 1 ... 6", sp->levels) : PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height, levels = (int)sp->levels;
+  const size_t per_frame = band_out_bytes(levels, 1) / sizeof(uint64_t);
+  const PairJob j{"band_moments", w, h, n_frames, kBandChunk, 0, SIDE_BAND_OUT, band_out_bytes(levels, n_frames), out, true, SIDE_BAND_PART,
+                  band_part_bytes(w, h, levels, n_frames < kBandChunk ? n_frames : kBandChunk)};
+  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
+    return launch_band_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
+                               d.frame_pitch, n, w, h, levels, c->side_buf[SIDE_BAND_PART],
+                               (unsigned long long*)c->side_buf[SIDE_BAND_OUT] + (size_t)at * per_frame);
+  });
+}
+
+// temporal distortion (temporal_moments.hip): a result per transition, so `out` may be null below two frames
+template <class Clip>
+int temporal_moments(pqa_ctx* c, const pqa_temporal_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, uint64_t* out) {
+  const int rc = spec_check(c, "temporal_moments", sp, 1, ref.at, dis.at, n_frames, out, 2, [&] {
+    return sp->tile > 64 || !tile_size_ok((int)sp->tile) ? fail(c, PQA_EINVAL, "temporal_moments: tile %u is not 8, 16, 32 or 64", sp->tile) : PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height, tile = (int)sp->tile;
+  const size_t per_transition = temporal_out_bytes(w, h, tile, 2) / sizeof(uint64_t);
+  const PairJob j{"temporal_moments", w, h, n_frames, kTemporalChunk, 1, SIDE_TEMPORAL_OUT, temporal_out_bytes(w, h, tile, n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
+    return launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
+                                   d.frame_pitch, n, w, h, tile, c->temporal_walk,
+                                   (unsigned long long*)c->side_buf[SIDE_TEMPORAL_OUT] + (size_t)at * per_transition);
+  });
+}
+
+// coding-grid detection (edge_profiles.hip)
+template <class Clip>
+int edge_profiles(pqa_ctx* c, const pqa_edge_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, uint64_t* out) {
+  const int rc = spec_check(c, "edge_profiles", sp, 1, ref.at, dis.at, n_frames, out, 1, [] { return PQA_OK; });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height;
+  const size_t per_frame = edge_out_bytes(w, h, 1) / sizeof(uint64_t);
+  const PairJob j{"edge_profiles", w, h, n_frames, kEdgeChunk, 0, SIDE_EDGE_OUT, edge_out_bytes(w, h, n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
+    return launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
+                                d.frame_pitch, n, w, h, (unsigned long long*)c->side_buf[SIDE_EDGE_OUT] + (size_t)at * per_frame);
+  });
+}
+
+// active-picture detection (line_profiles.hip): one clip; a stride that is no multiple of the sample size passes here too
+template <class Clip>
+int line_profiles(pqa_ctx* c, const pqa_profile_spec* sp, const Clip& planes, int32_t n_frames, uint64_t* out) {
+  const int rc = spec_check(c, "line_profiles", sp, 1, planes.at, planes.at, n_frames, out, 1, [] { return PQA_OK; });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height;
+  const size_t per_frame = profile_out_bytes(w, h, 1) / sizeof(uint64_t);
+  const PairJob j{"line_profiles", w, h, n_frames, kProfChunk, 0, SIDE_PROF_OUT, profile_out_bytes(w, h, n_frames), out, false};
+  return pair_run(c, j, planes, (const Clip*)nullptr, [&](PlaneRun r, PlaneRun, int n, int at) {
+    return launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, n, w, h,
+                                (unsigned long long*)c->side_buf[SIDE_PROF_OUT] + (size_t)at * per_frame);
+  });
 }
 
 // ---- colour-matrix alignment (colour_moments.hip): argument rules (no device call), the layout of a staged frame --------------
@@ -306,74 +522,6 @@ void cl_pack(const pqa_ctx* c, const ClLayout& L, uint8_t* pin, const void* cons
     for (int p = 0; p < 3; ++p)
       copy_plane_rows(pin + (size_t)f * L.bytes + L.off[p], L.pitch[p], (const uint8_t*)frames[(size_t)f * 3 + p], strides[p],
                       (size_t)c->pw[p] * c->esize, c->ph[p]);
-}
-
-// ---- active-picture detection (line_profiles.hip): argument rules (no device call) -----------------------------------------
-int pr_check(pqa_ctx* c, const pqa_profile_spec* sp, const void* planes, int32_t n_frames, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!sp) return fail(c, PQA_EINVAL, "line_profiles: null spec");
-  if (sp->struct_size != sizeof(pqa_profile_spec)) return fail(c, PQA_EINVAL, "line_profiles: bad struct_size %u", sp->struct_size);
-  for (uint32_t v : {sp->width, sp->height})
-    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "line_profiles: plane size %u outside 1 ... 8192", v);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "line_profiles: negative frame count");
-  if (n_frames > 0 && !planes) return fail(c, PQA_EINVAL, "line_profiles: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "line_profiles: null output pointer");
-  return PQA_OK;
-}
-
-// ---- distortion map (tile_moments.hip): argument rules (no device call) ----------------------------------------------------
-int tl_check(pqa_ctx* c, const pqa_tile_spec* sp, const void* ref, const void* dis, int32_t n_frames, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!sp) return fail(c, PQA_EINVAL, "tile_moments: null spec");
-  if (sp->struct_size != sizeof(pqa_tile_spec)) return fail(c, PQA_EINVAL, "tile_moments: bad struct_size %u", sp->struct_size);
-  if (sp->tile > 64 || !tile_size_ok((int)sp->tile)) return fail(c, PQA_EINVAL, "tile_moments: tile %u is not 8, 16, 32 or 64", sp->tile);
-  for (uint32_t v : {sp->width, sp->height})
-    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "tile_moments: plane size %u outside 1 ... 8192", v);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "tile_moments: negative frame count");
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "tile_moments: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "tile_moments: null output pointer");
-  return PQA_OK;
-}
-
-// ---- distortion spectrum (band_moments.hip): argument rules (no device call) ------------------------------------------------
-int bd_check(pqa_ctx* c, const pqa_band_spec* sp, const void* ref, const void* dis, int32_t n_frames, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!sp) return fail(c, PQA_EINVAL, "band_moments: null spec");
-  if (sp->struct_size != sizeof(pqa_band_spec)) return fail(c, PQA_EINVAL, "band_moments: bad struct_size %u", sp->struct_size);
-  if (sp->levels > 6 || !band_levels_ok((int)sp->levels)) return fail(c, PQA_EINVAL, "band_moments: %u levels outside 1 ... 6", sp->levels);
-  for (uint32_t v : {sp->width, sp->height})
-    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "band_moments: plane size %u outside 1 ... 8192", v);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "band_moments: negative frame count");
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "band_moments: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "band_moments: null output pointer");
-  return PQA_OK;
-}
-
-// ---- temporal distortion (temporal_moments.hip): argument rules (no device call) ---------------------------------------------
-int tm_check(pqa_ctx* c, const pqa_temporal_spec* sp, const void* ref, const void* dis, int32_t n_frames, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!sp) return fail(c, PQA_EINVAL, "temporal_moments: null spec");
-  if (sp->struct_size != sizeof(pqa_temporal_spec)) return fail(c, PQA_EINVAL, "temporal_moments: bad struct_size %u", sp->struct_size);
-  if (sp->tile > 64 || !tile_size_ok((int)sp->tile)) return fail(c, PQA_EINVAL, "temporal_moments: tile %u is not 8, 16, 32 or 64", sp->tile);
-  for (uint32_t v : {sp->width, sp->height})
-    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "temporal_moments: plane size %u outside 1 ... 8192", v);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "temporal_moments: negative frame count");
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "temporal_moments: null clip pointer");
-  if (n_frames > 1 && !out) return fail(c, PQA_EINVAL, "temporal_moments: null output pointer");
-  return PQA_OK;
-}
-
-// ---- coding-grid detection (edge_profiles.hip): argument rules (no device call) ----------------------------------------------
-int eg_check(pqa_ctx* c, const pqa_edge_spec* sp, const void* ref, const void* dis, int32_t n_frames, const uint64_t* out) {
-  if (!c) return PQA_EINVAL;
-  if (!sp) return fail(c, PQA_EINVAL, "edge_profiles: null spec");
-  if (sp->struct_size != sizeof(pqa_edge_spec)) return fail(c, PQA_EINVAL, "edge_profiles: bad struct_size %u", sp->struct_size);
-  for (uint32_t v : {sp->width, sp->height})
-    if (v < 1 || v > 8192) return fail(c, PQA_EINVAL, "edge_profiles: plane size %u outside 1 ... 8192", v);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "edge_profiles: negative frame count");
-  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "edge_profiles: null clip pointer");
-  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "edge_profiles: null output pointer");
-  return PQA_OK;
 }
 
 }  // namespace
@@ -807,482 +955,94 @@ int pqa_resample(pqa_ctx* c, const pqa_resample_spec* spec, const void* const* s
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  // A source plane may be larger than the context's: the chunks of kRsChunk planes travel through pinned buffers and device
-  // buffers of this entry's own, all grow-only.  Rows are packed 16 bytes apart at least, so the kernel loads and stores
-  // four samples at a time.  A chunk is uploaded, resampled, downloaded and copied out before the next one starts.
-  const int64_t sp = round_up((int64_t)src_row, 16), dp = round_up((int64_t)dst_row, 16);
-  const size_t sf = (size_t)sp * sh, df = (size_t)dp * dh;
+  // A source plane may be larger than the context's: the chunks of kRsChunk planes travel through the side analyses' two
+  // pinned chunks (out through the first, back through the second) and device buffers of this entry's own, all grow-only,
+  // in the packed layout of host_stage.h, so the kernel loads and stores four samples at a time.  A chunk is uploaded,
+  // resampled, downloaded and copied out before the next one starts.
+  const host::PlaneLayout S = host::plane_layout(src_row, sh), D = host::plane_layout(dst_row, dh);
+  const int64_t sp = S.pitch, dp = D.pitch;
+  const size_t sf = S.frame_bytes, df = D.frame_bytes;
   const int chunk = n_frames < kRsChunk ? n_frames : kRsChunk;
-  rc = rs_pin_reserve(c, 0, sf * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, df * chunk);
+  rc = side_pin_reserve(c, 0, sf * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, df * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_RS_SRC, sf * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_RS_DST, df * chunk);
   if (rc != PQA_OK) return rc;
   for (int f0 = 0; f0 < n_frames; f0 += kRsChunk) {
     const int n = chunk_len(n_frames, f0, kRsChunk);
-    for (int f = 0; f < n; ++f) copy_plane_rows(c->rs_pin[0] + (size_t)f * sf, sp, (const uint8_t*)src_frames[f0 + f], src_row_stride, src_row, sh);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_RS_SRC], c->rs_pin[0], sf * n, hipMemcpyHostToDevice, c->stream);
+    host::pack_planes(c->side_pin[0], S, src_frames + f0, src_row_stride, n);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_RS_SRC], c->side_pin[0], sf * n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
       e = launch_resample(c->stream, c->elem, (int)c->cfg.bit_depth, c->rs_cache[slot].plan, (const int*)c->side_buf[SIDE_RS_TABLE0 + slot],
                           c->side_buf[SIDE_RS_SRC], sp / es, (int64_t)(sf / es), sw, sh, c->side_buf[SIDE_RS_DST], dp / es,
                           (int64_t)(df / es), dw, dh, n);
-    rc = side_finish(c, "resample", e, c->rs_pin[1], c->side_buf[SIDE_RS_DST], df * n);
+    rc = side_finish(c, "resample", e, c->side_pin[1], c->side_buf[SIDE_RS_DST], df * n);
     if (rc != PQA_OK) return rc;
     for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
       for (int y = 0; y < dh; ++y)
-        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->rs_pin[1] + (size_t)f * df + (size_t)y * dp, dst_row);
+        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * df + (size_t)y * dp, dst_row);
   }
   return PQA_OK;
 }
 
-// ---- registration moments (flow_moments.hip) ---------------------------------------------------------------------------
+// ---- the spec-driven analyses: flow_moments() ... line_profiles() above ------------------------------------------------------
 
 int pqa_flow_moments_device(pqa_ctx* c, const pqa_flow_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
                             const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int64_t* out) {
-  int rc = fl_check(c, spec, ref, dis, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
-  rc = check_device_clip(c, "flow_moments: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
-  if (rc == PQA_OK) rc = check_device_clip(c, "flow_moments: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = side_reserve(c, SIDE_FLOW_OUT, flow_out_bytes(w, h, tile, n_frames));
-  if (rc != PQA_OK) return rc;
-  const size_t per_frame = flow_out_bytes(w, h, tile, 1) / sizeof(long long);
-  auto* dev_out = (long long*)c->side_buf[SIDE_FLOW_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kFlowChunk)
-    e = launch_flow_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch,
-                            ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch,
-                            dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames, f0, kFlowChunk), w, h, tile,
-                            dev_out + (size_t)f0 * per_frame);
-  return side_finish(c, "flow_moments", e, out, dev_out, flow_out_bytes(w, h, tile, n_frames));
+  return flow_moments(c, spec, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, out);
 }
-
 int pqa_flow_moments(pqa_ctx* c, const pqa_flow_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, int64_t* out) {
-  int rc = fl_check(c, spec, ref_frames, dis_frames, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
-  const size_t row_bytes = (size_t)w * es;
-  rc = check_host_frames(c, "flow_moments: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "flow_moments: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // The planes are the call's own size, so they travel as pqa_resample's do: chunks of kFlowChunk pairs through its two
-  // grow-only pinned buffers (the reference planes through the first, the captured ones through the second) into device
-  // buffers of this entry.  Every chunk's kernel writes its sums behind the previous chunk's; they come back once.  A pinned
-  // buffer is packed again only after the stream has drained the chunk before: the entry is short, it is not pipelined.
-  const int64_t pitch = round_up((int64_t)row_bytes, 16);
-  const size_t fb = (size_t)pitch * h;
-  const int chunk = n_frames < kFlowChunk ? n_frames : kFlowChunk;
-  rc = rs_pin_reserve(c, 0, fb * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_OUT, flow_out_bytes(w, h, tile, n_frames));
-  if (rc != PQA_OK) return rc;
-  const size_t per_frame = flow_out_bytes(w, h, tile, 1) / sizeof(long long);
-  auto* dev_out = (long long*)c->side_buf[SIDE_FLOW_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kFlowChunk) {
-    const int n = chunk_len(n_frames, f0, kFlowChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    for (int f = 0; f < n; ++f) {
-      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
-      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
-    }
-    e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_REF], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_DIS], c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_flow_moments(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_FLOW_REF], pitch / es, (int64_t)(fb / es),
-                              c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, tile, dev_out + (size_t)f0 * per_frame);
-  }
-  return side_finish(c, "flow_moments", e, out, dev_out, flow_out_bytes(w, h, tile, n_frames));
+  return flow_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
 }
-
-// ---- distortion map (tile_moments.hip) -------------------------------------------------------------------------------------
 
 int pqa_tile_moments_device(pqa_ctx* c, const pqa_tile_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
                             const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, uint64_t* out) {
-  int rc = tl_check(c, spec, ref, dis, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
-  rc = check_device_clip(c, "tile_moments: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
-  if (rc == PQA_OK) rc = check_device_clip(c, "tile_moments: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = tile_out_bytes(w, h, tile, n_frames), per_frame = tile_out_bytes(w, h, tile, 1) / sizeof(uint64_t);
-  rc = side_reserve(c, SIDE_TILE_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_TILE_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kTileChunk)
-    e = launch_tile_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch,
-                            ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch,
-                            dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames, f0, kTileChunk), w, h, tile,
-                            dev_out + (size_t)f0 * per_frame);
-  return side_finish(c, "tile_moments", e, out, dev_out, bytes);
+  return tile_moments(c, spec, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, out);
 }
-
 int pqa_tile_moments(pqa_ctx* c, const pqa_tile_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  int rc = tl_check(c, spec, ref_frames, dis_frames, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
-  const size_t row_bytes = (size_t)w * es;
-  rc = check_host_frames(c, "tile_moments: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "tile_moments: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (n_frames > 0 && (ref_row_stride % es || dis_row_stride % es))
-    return fail(c, PQA_EINVAL, "tile_moments: stride is not a multiple of the sample size");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // The planes travel exactly as pqa_flow_moments' do, through the same buffers: chunks of kTileChunk pairs through the two
-  // grow-only pinned buffers of pqa_resample into the two device buffers of pqa_flow_moments (every entry here is synchronous,
-  // so no two of them are ever in flight), rows 16 bytes apart at least, so the kernel takes its wide loads.  Every chunk's
-  // kernel writes its sums behind the previous chunk's; they come back once.  A pinned buffer is packed again only after the
-  // stream has drained the chunk before.
-  const int64_t pitch = round_up((int64_t)row_bytes, 16);
-  const size_t fb = (size_t)pitch * h;
-  const int chunk = n_frames < kTileChunk ? n_frames : kTileChunk;
-  const size_t bytes = tile_out_bytes(w, h, tile, n_frames), per_frame = tile_out_bytes(w, h, tile, 1) / sizeof(uint64_t);
-  rc = rs_pin_reserve(c, 0, fb * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TILE_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_TILE_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kTileChunk) {
-    const int n = chunk_len(n_frames, f0, kTileChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    for (int f = 0; f < n; ++f) {
-      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
-      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
-    }
-    e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_REF], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_DIS], c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_tile_moments(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_FLOW_REF], pitch / es, (int64_t)(fb / es),
-                              c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, tile, dev_out + (size_t)f0 * per_frame);
-  }
-  return side_finish(c, "tile_moments", e, out, dev_out, bytes);
+  return tile_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
 }
-
-// ---- distortion spectrum (band_moments.hip) --------------------------------------------------------------------------------
 
 int pqa_band_sums(void) { return kBandSums; }
-
 int pqa_band_moments_device(pqa_ctx* c, const pqa_band_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
                             const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, uint64_t* out) {
-  int rc = bd_check(c, spec, ref, dis, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, levels = (int)spec->levels;
-  rc = check_device_clip(c, "band_moments: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
-  if (rc == PQA_OK) rc = check_device_clip(c, "band_moments: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int chunk = n_frames < kBandChunk ? n_frames : kBandChunk;
-  const size_t bytes = band_out_bytes(levels, n_frames), per_frame = band_out_bytes(levels, 1) / sizeof(uint64_t);
-  rc = side_reserve(c, SIDE_BAND_PART, band_part_bytes(w, h, levels, chunk));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_BAND_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_BAND_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kBandChunk)   // the chunks share the partials: the stream keeps them in order
-    e = launch_band_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch,
-                            ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch,
-                            dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames, f0, kBandChunk), w, h, levels,
-                            c->side_buf[SIDE_BAND_PART], dev_out + (size_t)f0 * per_frame);
-  return side_finish(c, "band_moments", e, out, dev_out, bytes);
+  return band_moments(c, spec, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, out);
 }
-
 int pqa_band_moments(pqa_ctx* c, const pqa_band_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  int rc = bd_check(c, spec, ref_frames, dis_frames, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, levels = (int)spec->levels;
-  const size_t row_bytes = (size_t)w * es;
-  rc = check_host_frames(c, "band_moments: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "band_moments: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (n_frames > 0 && (ref_row_stride % es || dis_row_stride % es))
-    return fail(c, PQA_EINVAL, "band_moments: stride is not a multiple of the sample size");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // The planes travel exactly as pqa_tile_moments' do, through the same buffers: chunks of kBandChunk pairs through the two
-  // grow-only pinned buffers of pqa_resample into the two device buffers of pqa_flow_moments, rows 16 bytes apart at least, so
-  // the kernel takes its wide loads.  Every chunk's sums land behind the previous chunk's; they come back once.  A pinned
-  // buffer is packed again only after the stream has drained the chunk before.
-  const int64_t pitch = round_up((int64_t)row_bytes, 16);
-  const size_t fb = (size_t)pitch * h;
-  const int chunk = n_frames < kBandChunk ? n_frames : kBandChunk;
-  const size_t bytes = band_out_bytes(levels, n_frames), per_frame = band_out_bytes(levels, 1) / sizeof(uint64_t);
-  rc = rs_pin_reserve(c, 0, fb * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_BAND_PART, band_part_bytes(w, h, levels, chunk));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_BAND_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_BAND_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kBandChunk) {
-    const int n = chunk_len(n_frames, f0, kBandChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    for (int f = 0; f < n; ++f) {
-      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
-      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
-    }
-    e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_REF], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_DIS], c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_band_moments(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_FLOW_REF], pitch / es, (int64_t)(fb / es),
-                              c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, levels,
-                              c->side_buf[SIDE_BAND_PART], dev_out + (size_t)f0 * per_frame);
-  }
-  return side_finish(c, "band_moments", e, out, dev_out, bytes);
+  return band_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
 }
 
-// ---- temporal distortion (temporal_moments.hip) ------------------------------------------------------------------------------
-
 int pqa_temporal_sums(void) { return kTemporalSums; }
-
 int pqa_temporal_moments_device(pqa_ctx* c, const pqa_temporal_spec* spec, const void* ref, int64_t ref_row_pitch,
                                 int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                 int32_t n_frames, uint64_t* out) {
-  int rc = tm_check(c, spec, ref, dis, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
-  rc = check_device_clip(c, "temporal_moments: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
-  if (rc == PQA_OK) rc = check_device_clip(c, "temporal_moments: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames <= 1) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = temporal_out_bytes(w, h, tile, n_frames), per_tr = temporal_out_bytes(w, h, tile, 2) / sizeof(uint64_t);
-  rc = side_reserve(c, SIDE_TEMPORAL_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_TEMPORAL_OUT];
-  hipError_t e = hipSuccess;
-  // transitions t0 + 1 ... t0 + kTemporalChunk a launch: frames t0 ... t0 + kTemporalChunk, the first as predecessor only
-  for (int t0 = 0; t0 < n_frames - 1 && e == hipSuccess; t0 += kTemporalChunk)
-    e = launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)t0 * ref_frame_pitch,
-                                ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)t0 * dis_frame_pitch,
-                                dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames - 1, t0, kTemporalChunk) + 1, w, h, tile,
-                                c->temporal_walk, dev_out + (size_t)t0 * per_tr);
-  return side_finish(c, "temporal_moments", e, out, dev_out, bytes);
+  return temporal_moments(c, spec, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, out);
 }
-
 int pqa_temporal_moments(pqa_ctx* c, const pqa_temporal_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                          const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  int rc = tm_check(c, spec, ref_frames, dis_frames, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height, tile = (int)spec->tile;
-  const size_t row_bytes = (size_t)w * es;
-  rc = check_host_frames(c, "temporal_moments: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "temporal_moments: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (n_frames > 0 && (ref_row_stride % es || dis_row_stride % es))
-    return fail(c, PQA_EINVAL, "temporal_moments: stride is not a multiple of the sample size");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames <= 1) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // The planes travel as pqa_tile_moments' do, through the same buffers, every frame once: chunks of kTemporalChunk pairs through
-  // the two grow-only pinned buffers of pqa_resample into the two device buffers of pqa_flow_moments, rows 16 bytes apart at
-  // least, so the kernel takes its wide loads.  The device buffers hold one slot more than a chunk: a chunk lands in slots
-  // 1 ... n, and before the next chunk's upload overwrites them the last pair is copied to slot 0 on the stream, where it is
-  // the predecessor of the next chunk's first.  So the first chunk's launch starts at slot 1 (n - 1 transitions) and every
-  // later one at slot 0 (n transitions).  Every launch writes its sums behind the previous one's; they come back once.  A
-  // pinned buffer is packed again only after the stream has drained the chunk before.
-  const int64_t pitch = round_up((int64_t)row_bytes, 16);
-  const size_t fb = (size_t)pitch * h;
-  const int chunk = n_frames < kTemporalChunk ? n_frames : kTemporalChunk;
-  const size_t bytes = temporal_out_bytes(w, h, tile, n_frames), per_tr = temporal_out_bytes(w, h, tile, 2) / sizeof(uint64_t);
-  rc = rs_pin_reserve(c, 0, fb * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * (chunk + 1));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * (chunk + 1));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TEMPORAL_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_TEMPORAL_OUT];
-  auto* dref = (uint8_t*)c->side_buf[SIDE_FLOW_REF];
-  auto* ddis = (uint8_t*)c->side_buf[SIDE_FLOW_DIS];
-  hipError_t e = hipSuccess;
-  int prev_n = 0;   // frames of the chunk before: its last pair is in slot prev_n
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kTemporalChunk) {
-    const int n = chunk_len(n_frames, f0, kTemporalChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    for (int f = 0; f < n; ++f) {
-      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
-      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
-    }
-    if (prev_n > 0) {   // the seam: slot prev_n >= 1, so source and destination never overlap
-      e = hipMemcpyAsync(dref, dref + (size_t)prev_n * fb, fb, hipMemcpyDeviceToDevice, c->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(ddis, ddis + (size_t)prev_n * fb, fb, hipMemcpyDeviceToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(dref + fb, c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ddis + fb, c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
-    const size_t first = prev_n > 0 ? 0 : fb;   // the slot of the launch's first frame
-    if (e == hipSuccess)
-      e = launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, dref + first, pitch / es, (int64_t)(fb / es), ddis + first,
-                                  pitch / es, (int64_t)(fb / es), n + (prev_n > 0 ? 1 : 0), w, h, tile, c->temporal_walk,
-                                  dev_out + (size_t)(f0 > 0 ? f0 - 1 : 0) * per_tr);
-    prev_n = n;
-  }
-  return side_finish(c, "temporal_moments", e, out, dev_out, bytes);
+  return temporal_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
 }
-
-// ---- coding-grid detection (edge_profiles.hip) -------------------------------------------------------------------------------
 
 int pqa_edge_sums(void) { return kEdgeSums; }
-
 int pqa_edge_profiles_device(pqa_ctx* c, const pqa_edge_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
                              const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, uint64_t* out) {
-  int rc = eg_check(c, spec, ref, dis, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
-  rc = check_device_clip(c, "edge_profiles: reference ", ref_row_pitch, ref_frame_pitch, (int64_t)w * es);
-  if (rc == PQA_OK) rc = check_device_clip(c, "edge_profiles: captured ", dis_row_pitch, dis_frame_pitch, (int64_t)w * es);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = edge_out_bytes(w, h, n_frames), per_frame = edge_out_bytes(w, h, 1) / sizeof(uint64_t);
-  rc = side_reserve(c, SIDE_EDGE_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_EDGE_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kEdgeChunk)
-    e = launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch,
-                             ref_row_pitch / es, ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch,
-                             dis_row_pitch / es, dis_frame_pitch / es, chunk_len(n_frames, f0, kEdgeChunk), w, h,
-                             dev_out + (size_t)f0 * per_frame);
-  return side_finish(c, "edge_profiles", e, out, dev_out, bytes);
+  return edge_profiles(c, spec, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, out);
 }
-
 int pqa_edge_profiles(pqa_ctx* c, const pqa_edge_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                       const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  int rc = eg_check(c, spec, ref_frames, dis_frames, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
-  const size_t row_bytes = (size_t)w * es;
-  rc = check_host_frames(c, "edge_profiles: ", "reference ", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "edge_profiles: ", "captured ", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (n_frames > 0 && (ref_row_stride % es || dis_row_stride % es))
-    return fail(c, PQA_EINVAL, "edge_profiles: stride is not a multiple of the sample size");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // The planes travel exactly as pqa_tile_moments' do, through the same buffers: chunks of kEdgeChunk pairs through the two
-  // grow-only pinned buffers of pqa_resample into the two device buffers of pqa_flow_moments, rows 16 bytes apart at least, so
-  // the kernel takes its wide loads.  Every chunk's kernel writes its profiles behind the previous chunk's; they come back
-  // once.  A pinned buffer is packed again only after the stream has drained the chunk before.
-  const int64_t pitch = round_up((int64_t)row_bytes, 16);
-  const size_t fb = (size_t)pitch * h;
-  const int chunk = n_frames < kEdgeChunk ? n_frames : kEdgeChunk;
-  const size_t bytes = edge_out_bytes(w, h, n_frames), per_frame = edge_out_bytes(w, h, 1) / sizeof(uint64_t);
-  rc = rs_pin_reserve(c, 0, fb * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_REF, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_FLOW_DIS, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_EDGE_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_EDGE_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kEdgeChunk) {
-    const int n = chunk_len(n_frames, f0, kEdgeChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    for (int f = 0; f < n; ++f) {
-      copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)ref_frames[f0 + f], ref_row_stride, row_bytes, h);
-      copy_plane_rows(c->rs_pin[1] + (size_t)f * fb, pitch, (const uint8_t*)dis_frames[f0 + f], dis_row_stride, row_bytes, h);
-    }
-    e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_REF], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_FLOW_DIS], c->rs_pin[1], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_FLOW_REF], pitch / es, (int64_t)(fb / es),
-                               c->side_buf[SIDE_FLOW_DIS], pitch / es, (int64_t)(fb / es), n, w, h, dev_out + (size_t)f0 * per_frame);
-  }
-  return side_finish(c, "edge_profiles", e, out, dev_out, bytes);
+  return edge_profiles(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
 }
-
-// ---- active-picture detection (line_profiles.hip) ------------------------------------------------------------------------
 
 int pqa_line_profiles_device(pqa_ctx* c, const pqa_profile_spec* spec, const void* planes, int64_t row_pitch, int64_t frame_pitch,
                              int32_t n_frames, uint64_t* out) {
-  int rc = pr_check(c, spec, planes, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
-  rc = check_device_clip(c, "line_profiles: ", row_pitch, frame_pitch, (int64_t)w * es);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = profile_out_bytes(w, h, n_frames), per_frame = profile_out_bytes(w, h, 1) / sizeof(uint64_t);
-  rc = side_reserve(c, SIDE_PROF_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_PROF_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kProfChunk)
-    e = launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint8_t*)planes + (int64_t)f0 * frame_pitch,
-                             row_pitch / es, frame_pitch / es, chunk_len(n_frames, f0, kProfChunk), w, h, dev_out + (size_t)f0 * per_frame);
-  return side_finish(c, "line_profiles", e, out, dev_out, bytes);
+  return line_profiles(c, spec, DevClip{planes, row_pitch, frame_pitch}, n_frames, out);
 }
-
 int pqa_line_profiles(pqa_ctx* c, const pqa_profile_spec* spec, const void* const* frames, int64_t row_stride, int32_t n_frames,
                       uint64_t* out) {
-  int rc = pr_check(c, spec, frames, n_frames, out);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize, w = (int)spec->width, h = (int)spec->height;
-  const size_t row_bytes = (size_t)w * es;
-  rc = check_host_frames(c, "line_profiles: ", "", frames, 1, n_frames, row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // The planes are the call's own size, so they travel as pqa_flow_moments' do: chunks of kProfChunk planes through the first
-  // grow-only pinned buffer of pqa_resample into a device buffer of this entry, rows 16 bytes apart at least, so the kernel
-  // takes its wide loads.  Every chunk's kernel writes its profiles behind the previous chunk's; they come back once.  The
-  // pinned buffer is packed again only after the stream has drained the chunk before: the entry is short, it is not pipelined.
-  const int64_t pitch = round_up((int64_t)row_bytes, 16);
-  const size_t fb = (size_t)pitch * h;
-  const int chunk = n_frames < kProfChunk ? n_frames : kProfChunk;
-  const size_t bytes = profile_out_bytes(w, h, n_frames), per_frame = profile_out_bytes(w, h, 1) / sizeof(uint64_t);
-  rc = rs_pin_reserve(c, 0, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_PROF_SRC, fb * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_PROF_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_PROF_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kProfChunk) {
-    const int n = chunk_len(n_frames, f0, kProfChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) break;
-    for (int f = 0; f < n; ++f) copy_plane_rows(c->rs_pin[0] + (size_t)f * fb, pitch, (const uint8_t*)frames[f0 + f], row_stride, row_bytes, h);
-    e = hipMemcpyAsync(c->side_buf[SIDE_PROF_SRC], c->rs_pin[0], fb * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_PROF_SRC], pitch / es, (int64_t)(fb / es), n,
-                               w, h, dev_out + (size_t)f0 * per_frame);
-  }
-  return side_finish(c, "line_profiles", e, out, dev_out, bytes);
+  return line_profiles(c, spec, HostClip{frames, row_stride}, n_frames, out);
 }
 
 // ---- colour-matrix alignment (colour_moments.hip) ------------------------------------------------------------------------
@@ -1337,14 +1097,14 @@ int pqa_colour_moments(pqa_ctx* c, const void* const* ref_frames, const int64_t 
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   HIPCHK(c, hipSetDevice(c->device));
-  // Three planes a frame, so the frames travel as pqa_flow_moments' planes do: chunks of kColourChunk pairs through the two
-  // grow-only pinned buffers of pqa_resample (reference frames through the first, captured ones through the second) into
+  // Three planes a frame, so this entry keeps a loop of its own beside pair_run: chunks of kColourChunk pairs through the side
+  // analyses' two pinned chunks (reference frames through the first, captured ones through the second) into
   // device buffers of this entry; every chunk's kernel writes its sums behind the previous chunk's, they come back once.
   const ClLayout L = cl_layout(c);
   const int chunk = n_frames < kColourChunk ? n_frames : kColourChunk;
   const size_t bytes = (size_t)n_frames * kColourSums * sizeof(uint64_t);
-  rc = rs_pin_reserve(c, 0, L.bytes * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, L.bytes * chunk);
+  rc = side_pin_reserve(c, 0, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, L.bytes * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_A, L.bytes * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_B, L.bytes * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_OUT, bytes);
@@ -1358,10 +1118,10 @@ int pqa_colour_moments(pqa_ctx* c, const void* const* ref_frames, const int64_t 
     const int n = chunk_len(n_frames, f0, kColourChunk);
     if (f0 > 0) e = hipStreamSynchronize(c->stream);   // the pinned buffers are packed again only after the chunk before has left them
     if (e != hipSuccess) break;
-    cl_pack(c, L, c->rs_pin[0], ref_frames + (size_t)f0 * 3, ref_strides, n);
-    cl_pack(c, L, c->rs_pin[1], dis_frames + (size_t)f0 * 3, dis_strides, n);
-    e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->rs_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_B], c->rs_pin[1], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    cl_pack(c, L, c->side_pin[0], ref_frames + (size_t)f0 * 3, ref_strides, n);
+    cl_pack(c, L, c->side_pin[1], dis_frames + (size_t)f0 * 3, dis_strides, n);
+    e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->side_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_B], c->side_pin[1], L.bytes * n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
       e = launch_colour_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, r, d, n,
                                 c->pw[0], c->ph[0], lo, hi, dev_out + (size_t)f0 * kColourSums);
@@ -1414,8 +1174,8 @@ int pqa_colour_apply(pqa_ctx* c, const int32_t m[12], const void* const* src_fra
   // as pqa_resample: a chunk is uploaded, mapped, downloaded and copied out before the next one starts
   const ClLayout L = cl_layout(c);
   const int chunk = n_frames < kColourChunk ? n_frames : kColourChunk;
-  rc = rs_pin_reserve(c, 0, L.bytes * chunk);
-  if (rc == PQA_OK) rc = rs_pin_reserve(c, 1, L.bytes * chunk);
+  rc = side_pin_reserve(c, 0, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, L.bytes * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_A, L.bytes * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_B, L.bytes * chunk);
   if (rc != PQA_OK) return rc;
@@ -1426,18 +1186,18 @@ int pqa_colour_apply(pqa_ctx* c, const int32_t m[12], const void* const* src_fra
   for (int p = 0; p < 3; ++p) d[p] = MutPlaneRun{const_cast<void*>(dr[p].base), dr[p].row_pitch, dr[p].frame_pitch};
   for (int f0 = 0; f0 < n_frames; f0 += kColourChunk) {
     const int n = chunk_len(n_frames, f0, kColourChunk);
-    cl_pack(c, L, c->rs_pin[0], src_frames + (size_t)f0 * 3, src_strides, n);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->rs_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    cl_pack(c, L, c->side_pin[0], src_frames + (size_t)f0 * 3, src_strides, n);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->side_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
       e = launch_colour_apply(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, m, s, d, n,
                               c->pw[0], c->ph[0]);
-    rc = side_finish(c, "colour_apply", e, c->rs_pin[1], c->side_buf[SIDE_COLOUR_B], L.bytes * n);
+    rc = side_finish(c, "colour_apply", e, c->side_pin[1], c->side_buf[SIDE_COLOUR_B], L.bytes * n);
     if (rc != PQA_OK) return rc;
     for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
       for (int p = 0; p < 3; ++p)
         for (int y = 0; y < c->ph[p]; ++y)
           memcpy((uint8_t*)dst_frames[(size_t)(f0 + f) * 3 + p] + (int64_t)y * dst_strides[p],
-                 c->rs_pin[1] + (size_t)f * L.bytes + L.off[p] + (size_t)y * L.pitch[p], (size_t)c->pw[p] * c->esize);
+                 c->side_pin[1] + (size_t)f * L.bytes + L.off[p] + (size_t)y * L.pitch[p], (size_t)c->pw[p] * c->esize);
   }
   return PQA_OK;
 }

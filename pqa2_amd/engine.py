@@ -443,18 +443,62 @@ class FeatureEngine:
         self._check(self.lib.pqa_resample_device(self._ctx, C.byref(sp), src_ptr, src_row_pitch, src_frame_pitch, dst_ptr,
                                                  dst_row_pitch, dst_frame_pitch, int(n_frames)))
 
+    # -- the spec-driven analyses: planes of the call's own size -------------------------------
+    @staticmethod
+    def _plane_spec(cls, shape, **third):
+        """the spec `cls` of planes of `shape` = (height, width); `third`: its third field (tile or levels)"""
+        sp = cls()
+        sp.struct_size = C.sizeof(cls)
+        sp.height, sp.width = (max(0, int(v)) for v in (shape[0], shape[1]))
+        for name, v in third.items():
+            setattr(sp, name, max(0, int(v)))
+        return sp
+
+    def _plane_call(self, name, lists, shape, spec_of, out_of):
+        """(out, spec) of pqa_<name> over planes in host memory.  lists: (reference frames, captured frames) or (frames,);
+        shape: (height, width) or None for the first frame's; spec_of(shape) and out_of(n, spec) build the spec and the
+        zeroed result array."""
+        n = len(lists[0])
+        if len(lists[-1]) != n:
+            raise ValueError(f"{name} needs as many captured as reference frames")
+        if shape is None:
+            shape = np.shape(lists[0][0]) if n else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError(f"{name} needs 2-D planes")
+        shape = tuple(int(v) for v in shape)
+        sp = spec_of(shape)
+        out = out_of(n, sp)
+        keep, args = [], []
+        for frames, what in zip(lists, ("reference", "captured") if len(lists) == 2 else ("profile",)):
+            arrs, ptrs, stride = self._luma_list(frames, what, shape)
+            keep.append(arrs)
+            args += [ptrs, stride]
+        self._check(getattr(self.lib, "pqa_" + name)(self._ctx, C.byref(sp), *args, n, out.ctypes.data))
+        del keep
+        return out, sp
+
+    def _plane_call_resident(self, name, clips, n_frames, sp, out):
+        """`out` of pqa_<name>_device; clips: (pointer, row pitch, frame pitch) of every clip, flat"""
+        self._check(getattr(self.lib, f"pqa_{name}_device")(self._ctx, C.byref(sp), *clips, int(n_frames), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _tiles_out(n, sp, sums, dtype=np.uint64):
+        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
+        return np.zeros((max(int(n), 0), -(-sp.height // t), -(-sp.width // t), sums), dtype)
+
+    @staticmethod
+    def _lines_out(n, sp, sums):
+        return np.zeros((max(int(n), 0), sp.height + sp.width, sums), np.uint64)
+
     # -- sub-pixel registration ----------------------------------------------------------------
     @staticmethod
     def _flow_spec(shape, tile):
-        sp = N.PqaFlowSpec()
-        sp.struct_size = C.sizeof(N.PqaFlowSpec)
-        sp.height, sp.width, sp.tile = (max(0, int(v)) for v in (shape[0], shape[1], tile))
-        return sp
+        return FeatureEngine._plane_spec(N.PqaFlowSpec, shape, tile=tile)
 
     @staticmethod
     def _flow_out(n, sp):
-        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
-        return np.zeros((max(int(n), 0), -(-sp.height // t), -(-sp.width // t), 6), np.int64)
+        return FeatureEngine._tiles_out(n, sp, 6, np.int64)
 
     def flow_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
         """[n, ty, tx, 6] int64: per tile of `tile` x `tile` pixels (8, 16, 32 or 64) the sums of gx^2, gx gy, gy^2, gx dt,
@@ -462,42 +506,24 @@ class FeatureEngine:
         dis - ref), exact (pqa_flow_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory: two lists of 2-D arrays
         of equal length and one size, which need not be this context's (3 ... 8192 each way); samples of this context's bit
         depth.  align.solve_geometry reads the sum over the frames."""
-        n = len(ref_frames)
-        if len(dis_frames) != n:
-            raise ValueError("flow_moments needs as many captured as reference frames")
-        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError("flow_moments needs 2-D planes")
-        sp = self._flow_spec(shape, tile)
-        out = self._flow_out(n, sp)
-        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
-        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
-        self._check(self.lib.pqa_flow_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
-        del keep_r, keep_d
-        return out
+        return self._plane_call("flow_moments", (ref_frames, dis_frames), None, lambda s: self._flow_spec(s, tile), self._flow_out)[0]
 
     def flow_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                               dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_flow_moments_device)."""
         sp = self._flow_spec(shape, tile)
-        out = self._flow_out(n_frames, sp)
-        self._check(self.lib.pqa_flow_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
-                                                     dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
-        return out
+        return self._plane_call_resident("flow_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
+                                         n_frames, sp, self._flow_out(n_frames, sp))
 
     # -- distortion map ------------------------------------------------------------------------
     @staticmethod
     def _tile_spec(shape, tile):
-        sp = N.PqaTileSpec()
-        sp.struct_size = C.sizeof(N.PqaTileSpec)
-        sp.height, sp.width, sp.tile = (max(0, int(v)) for v in (shape[0], shape[1], tile))
-        return sp
+        return FeatureEngine._plane_spec(N.PqaTileSpec, shape, tile=tile)
 
     @staticmethod
     def _tile_out(n, sp):
-        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
-        return np.zeros((max(int(n), 0), -(-sp.height // t), -(-sp.width // t), N.TILE_SUMS), np.uint64)
+        return FeatureEngine._tiles_out(n, sp, N.TILE_SUMS)
 
     def tile_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
         """[n, ty, tx, 6] uint64: per tile of `tile` x `tile` pixels (8, 16, 32 or 64; edge tiles hold the pixels that exist)
@@ -505,37 +531,20 @@ class FeatureEngine:
         include/pqa_vmaf.h).  Planes in HOST memory: two lists of 2-D arrays of equal length and one size, which need not be
         this context's (1 ... 8192 each way); samples of this context's bit depth.  distortion.tile_metrics and
         distortion.find_defects read the result."""
-        n = len(ref_frames)
-        if len(dis_frames) != n:
-            raise ValueError("tile_moments needs as many captured as reference frames")
-        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError("tile_moments needs 2-D planes")
-        sp = self._tile_spec(shape, tile)
-        out = self._tile_out(n, sp)
-        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
-        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
-        self._check(self.lib.pqa_tile_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
-        del keep_r, keep_d
-        return out
+        return self._plane_call("tile_moments", (ref_frames, dis_frames), None, lambda s: self._tile_spec(s, tile), self._tile_out)[0]
 
     def tile_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                               dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_tile_moments_device)."""
         sp = self._tile_spec(shape, tile)
-        out = self._tile_out(n_frames, sp)
-        self._check(self.lib.pqa_tile_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
-                                                     dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
-        return out
+        return self._plane_call_resident("tile_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
+                                         n_frames, sp, self._tile_out(n_frames, sp))
 
     # -- distortion spectrum -------------------------------------------------------------------
     @staticmethod
     def _band_spec(shape, levels):
-        sp = N.PqaBandSpec()
-        sp.struct_size = C.sizeof(N.PqaBandSpec)
-        sp.height, sp.width, sp.levels = (max(0, int(v)) for v in (shape[0], shape[1], levels))
-        return sp
+        return FeatureEngine._plane_spec(N.PqaBandSpec, shape, levels=levels)
 
     @staticmethod
     def _band_out(n, sp):
@@ -548,42 +557,24 @@ class FeatureEngine:
         last is an int64: .view(np.int64)), exact (pqa_band_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory:
         two lists of 2-D arrays of equal length and one size, which need not be this context's (1 ... 8192 each way); samples
         of this context's bit depth.  spectrum.band_table and spectrum.summary read the result."""
-        n = len(ref_frames)
-        if len(dis_frames) != n:
-            raise ValueError("band_moments needs as many captured as reference frames")
-        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError("band_moments needs 2-D planes")
-        sp = self._band_spec(shape, levels)
-        out = self._band_out(n, sp)
-        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
-        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
-        self._check(self.lib.pqa_band_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
-        del keep_r, keep_d
-        return out
+        return self._plane_call("band_moments", (ref_frames, dis_frames), None, lambda s: self._band_spec(s, levels), self._band_out)[0]
 
     def band_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                               dis_frame_pitch: int, shape, n_frames: int, levels: int = 4) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_band_moments_device)."""
         sp = self._band_spec(shape, levels)
-        out = self._band_out(n_frames, sp)
-        self._check(self.lib.pqa_band_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
-                                                     dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
-        return out
+        return self._plane_call_resident("band_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
+                                         n_frames, sp, self._band_out(n_frames, sp))
 
     # -- temporal distortion -------------------------------------------------------------------
     @staticmethod
     def _temporal_spec(shape, tile):
-        sp = N.PqaTemporalSpec()
-        sp.struct_size = C.sizeof(N.PqaTemporalSpec)
-        sp.height, sp.width, sp.tile = (max(0, int(v)) for v in (shape[0], shape[1], tile))
-        return sp
+        return FeatureEngine._plane_spec(N.PqaTemporalSpec, shape, tile=tile)
 
     @staticmethod
     def _temporal_out(n, sp):
-        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
-        return np.zeros((max(int(n) - 1, 0), -(-sp.height // t), -(-sp.width // t), N.TEMPORAL_SUMS), np.uint64)
+        return FeatureEngine._tiles_out(int(n) - 1, sp, N.TEMPORAL_SUMS)
 
     def temporal_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
         """[n - 1, ty, tx, 7] uint64: per transition k = 1 ... n - 1 and tile of `tile` x `tile` pixels (8, 16, 32 or 64; edge
@@ -593,37 +584,21 @@ class FeatureEngine:
         HOST memory: two lists of 2-D arrays of equal length and one size, which need not be this context's (1 ... 8192 each
         way); samples of this context's bit depth.  Fewer than two frames give an empty result.  temporal.frame_table and
         temporal.summary read the result."""
-        n = len(ref_frames)
-        if len(dis_frames) != n:
-            raise ValueError("temporal_moments needs as many captured as reference frames")
-        shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError("temporal_moments needs 2-D planes")
-        sp = self._temporal_spec(shape, tile)
-        out = self._temporal_out(n, sp)
-        keep_r, rp, rs = self._luma_list(ref_frames, "reference", tuple(shape))
-        keep_d, dp, ds = self._luma_list(dis_frames, "captured", tuple(shape))
-        self._check(self.lib.pqa_temporal_moments(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
-        del keep_r, keep_d
-        return out
+        return self._plane_call("temporal_moments", (ref_frames, dis_frames), None, lambda s: self._temporal_spec(s, tile),
+                                self._temporal_out)[0]
 
     def temporal_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                                   dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_temporal_moments_device)."""
         sp = self._temporal_spec(shape, tile)
-        out = self._temporal_out(n_frames, sp)
-        self._check(self.lib.pqa_temporal_moments_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
-                                                         dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
-        return out
+        return self._plane_call_resident("temporal_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
+                                         n_frames, sp, self._temporal_out(n_frames, sp))
 
     # -- active-picture detection --------------------------------------------------------------
     @staticmethod
     def _profile_spec(shape):
-        sp = N.PqaProfileSpec()
-        sp.struct_size = C.sizeof(N.PqaProfileSpec)
-        sp.height, sp.width = (max(0, int(v)) for v in (shape[0], shape[1]))
-        return sp
+        return FeatureEngine._plane_spec(N.PqaProfileSpec, shape)
 
     @staticmethod
     def _profile_split(out, sp):
@@ -634,34 +609,20 @@ class FeatureEngine:
         of their squares, exact (pqa_line_profiles; definition: include/pqa_vmaf.h).  Planes in HOST memory: a list of 2-D
         arrays (views are fine) of `shape` = (height, width), default the first frame's, which need not be this context's
         (1 ... 8192 each way); samples of this context's bit depth.  align.active_picture reads the result."""
-        n = len(frames)
-        if shape is None:
-            shape = np.shape(frames[0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError("line_profiles needs 2-D planes")
-        sp = self._profile_spec(shape)
-        out = np.zeros((n, sp.height + sp.width, 2), np.uint64)
-        keep, ptrs, stride = self._luma_list(frames, "profile", tuple(int(v) for v in shape))
-        self._check(self.lib.pqa_line_profiles(self._ctx, C.byref(sp), ptrs, stride, n, out.ctypes.data))
-        del keep
-        return self._profile_split(out, sp)
+        return self._profile_split(*self._plane_call("line_profiles", (frames,), shape, self._profile_spec,
+                                                     lambda n, sp: self._lines_out(n, sp, 2)))
 
     def line_profiles_resident(self, ptr: int, row_pitch: int, frame_pitch: int, shape, n_frames: int):
         """The same for n_frames planes of `shape` = (height, width) in HBM (device pointer, pitches in bytes;
         pqa_line_profiles_device)."""
         sp = self._profile_spec(shape)
-        out = np.zeros((max(int(n_frames), 0), sp.height + sp.width, 2), np.uint64)
-        self._check(self.lib.pqa_line_profiles_device(self._ctx, C.byref(sp), ptr, row_pitch, frame_pitch, int(n_frames),
-                                                      out.ctypes.data))
-        return self._profile_split(out, sp)
+        return self._profile_split(self._plane_call_resident("line_profiles", (ptr, row_pitch, frame_pitch), n_frames, sp,
+                                                             self._lines_out(n_frames, sp, 2)), sp)
 
     # -- coding-grid detection -----------------------------------------------------------------
     @staticmethod
     def _edge_spec(shape):
-        sp = N.PqaEdgeSpec()
-        sp.struct_size = C.sizeof(N.PqaEdgeSpec)
-        sp.height, sp.width = (max(0, int(v)) for v in (shape[0], shape[1]))
-        return sp
+        return FeatureEngine._plane_spec(N.PqaEdgeSpec, shape)
 
     def edge_profiles(self, ref_frames, dis_frames, shape=None):
         """(rows [n, H, 3], cols [n, W, 3]) uint64: per row line y (the boundary between the rows y - 1 and y) and per column
@@ -670,31 +631,17 @@ class FeatureEngine:
         of each axis is zero; word 2 is int64: read it through .view(np.int64).  Planes in HOST memory: two lists of 2-D arrays
         (views are fine) of equal length and of `shape` = (height, width), default the first frame's, which need not be this
         context's (1 ... 8192 each way); samples of this context's bit depth.  grid.summary reads the result."""
-        n = len(ref_frames)
-        if len(dis_frames) != n:
-            raise ValueError("edge_profiles needs as many captured as reference frames")
-        if shape is None:
-            shape = np.shape(ref_frames[0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError("edge_profiles needs 2-D planes")
-        shape = tuple(int(v) for v in shape)
-        sp = self._edge_spec(shape)
-        out = np.zeros((n, sp.height + sp.width, N.EDGE_SUMS), np.uint64)
-        keep_r, rp, rs = self._luma_list(ref_frames, "reference", shape)
-        keep_d, dp, ds = self._luma_list(dis_frames, "captured", shape)
-        self._check(self.lib.pqa_edge_profiles(self._ctx, C.byref(sp), rp, rs, dp, ds, n, out.ctypes.data))
-        del keep_r, keep_d
-        return self._profile_split(out, sp)
+        return self._profile_split(*self._plane_call("edge_profiles", (ref_frames, dis_frames), shape, self._edge_spec,
+                                                     lambda n, sp: self._lines_out(n, sp, N.EDGE_SUMS)))
 
     def edge_profiles_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                                dis_frame_pitch: int, shape, n_frames: int):
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_edge_profiles_device)."""
         sp = self._edge_spec(shape)
-        out = np.zeros((max(int(n_frames), 0), sp.height + sp.width, N.EDGE_SUMS), np.uint64)
-        self._check(self.lib.pqa_edge_profiles_device(self._ctx, C.byref(sp), ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr,
-                                                      dis_row_pitch, dis_frame_pitch, int(n_frames), out.ctypes.data))
-        return self._profile_split(out, sp)
+        return self._profile_split(self._plane_call_resident("edge_profiles", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch,
+                                                                               dis_frame_pitch), n_frames, sp,
+                                                             self._lines_out(n_frames, sp, N.EDGE_SUMS)), sp)
 
     # -- colour-matrix alignment ---------------------------------------------------------------
     def _frame_list(self, frames, what: str):

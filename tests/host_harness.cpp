@@ -1,18 +1,23 @@
-// CPU harness for the library's device-free host code (pqa2_amd/csrc/host_pack.h, host_ring.h): built with
+// CPU harness for the library's device-free host code (pqa2_amd/csrc/host_pack.h, host_ring.h, host_stage.h): built with
 // -fsanitize=thread and with -fsanitize=address,undefined by tests/test_host_sanitizers.py and driven through the call
 // sequences the GPU tests put the real library through (tests/test_gpu_configs.py PQA_ESTATE cases, the truncated-file cases
-// of tests/test_gpu_engine.py, a cancel flag raised from another thread).  Memory / race safety only: no parity claim.
+// of tests/test_gpu_engine.py, a cancel flag raised from another thread; the pair staging of the side analyses against fake
+// device buffers of exactly the reserved sizes, as tests/test_gpu_pair_entries.py and the chunk tests of the six analyses put
+// it).  Memory / race safety, and for the pair staging which frames a launch sees: no parity claim.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fcntl.h>
+#include <memory>
 #include <random>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "../pqa2_amd/csrc/host_pack.h"
 #include "../pqa2_amd/csrc/host_ring.h"
+#include "../pqa2_amd/csrc/host_stage.h"
 
 using namespace pqa::host;
 
@@ -189,6 +194,119 @@ static void ring_scenarios() {
   }
 }
 
+// ---- the pair staging (host_stage.h) ---------------------------------------------------------------------------------------
+// The device is two heap buffers of exactly the bytes pqa_side.hip reserves; the callables copy as the HIP calls there do and
+// log themselves.  A launch notes which source frames lie in the slots it was given.
+static uint8_t sample_of(int clip, int frame, int y, size_t x) { return (uint8_t)(clip * 131 + frame * 7 + y * 31 + (int)x * 3 + 1); }
+
+struct StageCase {
+  size_t row_bytes;
+  int h;
+  int64_t stride_extra;   // 0: the source rows lie a packed pitch apart (copy_plane_rows takes its single memcpy)
+  int n_frames, carry, clips;
+  char fail_in = 0;       // 'D', 'S', 'U' or 'L': that callable returns 7 in the second chunk
+  bool cancel = false;    // the first launch raises the cancel flag
+};
+
+struct Launched { int out_index; std::vector<int> seen[2]; };
+
+static void stage_case(const StageCase& k) {
+  const int chunk = 8, slots = k.n_frames < chunk ? k.n_frames : chunk;
+  const PlaneLayout L = plane_layout(k.row_bytes, k.h);
+  CHECK(L.pitch % 16 == 0 && L.pitch >= (int64_t)k.row_bytes && L.pitch < (int64_t)k.row_bytes + 16 && L.frame_bytes == (size_t)L.pitch * k.h);
+  const int64_t stride = L.pitch + k.stride_extra;
+  // every source frame is an allocation of its own that ends with the last sample of its last row
+  std::vector<std::unique_ptr<uint8_t[]>> src[2];
+  std::vector<const void*> list[2];
+  std::unique_ptr<uint8_t[]> pin[2], dev[2];
+  for (int c = 0; c < k.clips; ++c) {
+    for (int f = 0; f < k.n_frames; ++f) {
+      src[c].emplace_back(new uint8_t[(size_t)stride * (k.h - 1) + k.row_bytes]);
+      for (int y = 0; y < k.h; ++y)
+        for (size_t x = 0; x < (size_t)(y < k.h - 1 ? stride : (int64_t)k.row_bytes); ++x)
+          src[c][f][(size_t)y * stride + x] = x < k.row_bytes ? sample_of(c, f, y, x) : 0xee;
+      list[c].push_back(src[c][f].get());
+    }
+    pin[c].reset(new uint8_t[L.frame_bytes * slots]);
+    dev[c].reset(new uint8_t[L.frame_bytes * (slots + k.carry)]);
+  }
+  uint8_t* const pins[2] = {pin[0].get(), pin[1].get()};
+  const size_t fb = L.frame_bytes;
+  std::string log;
+  std::vector<Launched> launches;
+  std::atomic<int> cancelled{0};
+  int chunk_no = 0;   // of the chunk a callable belongs to: upload() opens a chunk's device work, drain() the chunk's host work
+  const auto fails = [&](char who) { log += who; return k.fail_in == who && chunk_no == 1 ? 7 : 0; };
+  const int rc = stage_walk(
+      L, pins, list[0].data(), stride, k.clips == 2 ? list[1].data() : nullptr, stride, k.n_frames, chunk, k.carry, cancelled,
+      [&] { ++chunk_no; return fails('D'); },
+      [&](int from) {
+        CHECK(from >= 1 && from < slots + k.carry);
+        for (int c = 0; c < k.clips; ++c) memcpy(dev[c].get(), dev[c].get() + (size_t)from * fb, fb);
+        return fails('S');
+      },
+      [&](int slot, int n) {
+        CHECK(slot == k.carry && n >= 1 && n <= slots);
+        for (int c = 0; c < k.clips; ++c) memcpy(dev[c].get() + (size_t)slot * fb, pins[c], fb * n);
+        return fails('U');
+      },
+      [&](int slot, int n, int out_index) {
+        CHECK(slot >= 0 && n >= 1 && slot + n <= slots + k.carry);
+        Launched l{out_index, {}};
+        for (int c = 0; c < k.clips; ++c)
+          for (int i = 0; i < n; ++i) {   // the frame whose samples lie in slot + i
+            const uint8_t* plane = dev[c].get() + (size_t)(slot + i) * fb;
+            const int f = (plane[0] - sample_of(c, 0, 0, 0)) / 7;
+            CHECK(f >= 0 && f < k.n_frames);
+            for (int y = 0; y < k.h; ++y) CHECK(!memcmp(plane + (size_t)y * L.pitch, src[c][f].get() + (size_t)y * stride, k.row_bytes));
+            l.seen[c].push_back(f);
+          }
+        launches.push_back(l);
+        if (k.cancel) cancelled.store(1);
+        return fails('L');
+      });
+  // the calls, restated: per chunk drain (not the first), seam (carry 1, not the first), upload, launch
+  std::string want;
+  bool failed = false;
+  const int n_chunks = (k.n_frames + chunk - 1) / chunk;
+  for (int i = 0; i < n_chunks; ++i) {
+    for (char who : {'D', 'S', 'U', 'L'}) {
+      if ((who == 'D' && i == 0) || (who == 'S' && (i == 0 || !k.carry))) continue;
+      want += who;
+      if (i == 1 && who == k.fail_in) { failed = true; goto done; }
+    }
+    if (k.cancel) break;
+  }
+done:
+  CHECK(log == want);
+  CHECK(rc == (failed ? 7 : 0));
+  if (k.fail_in || k.cancel) return;
+  // the results, restated: result r is written once, in order, by a launch that saw frames r ... r + carry of both clips where
+  // the kernel reads them -- at plane r - out_index (and the next) of the launch
+  int next = 0;
+  for (const Launched& l : launches) {
+    CHECK(l.out_index == next);
+    for (int c = 0; c < k.clips; ++c)
+      for (size_t i = 0; i < l.seen[c].size(); ++i) CHECK(l.seen[c][i] == l.out_index + (int)i);
+    next += (int)l.seen[0].size() - k.carry;
+  }
+  CHECK(next == (k.n_frames > k.carry ? k.n_frames - k.carry : 0));
+}
+
+static void stage_scenarios() {
+  for (size_t row_bytes : {1, 15, 16, 17, 33})
+    for (int h : {1, 3})
+      for (int64_t extra : {0, 7})
+        for (int n : {0, 1, 2, 8, 9, 16, 17})
+          for (int carry : {0, 1})
+            for (int clips : {2, 1}) stage_case(StageCase{row_bytes, h, extra, n, carry, clips});
+  for (int carry : {0, 1})
+    for (int clips : {2, 1}) {
+      for (char who : {'D', 'S', 'U', 'L'}) stage_case(StageCase{17, 3, 7, 17, carry, clips, who});
+      stage_case(StageCase{17, 3, 7, 17, carry, clips, 0, true});
+    }
+}
+
 // proof that the sanitizer under which this binary was built is alive: a real data race / a real heap overflow, on request
 static int g_plain = 0;
 static void selftest(const char* what) {
@@ -208,6 +326,7 @@ int main(int argc, char** argv) {
   if (argc > 2 && !strcmp(argv[1], "--selftest")) { selftest(argv[2]); return 0; }
   const char* dir = argc > 1 ? argv[1] : "/tmp";
   ring_scenarios();
+  stage_scenarios();
   pack_scenarios(dir);
   printf("host harness ok\n");
   return 0;
