@@ -52,6 +52,9 @@ enum {
   PQA_FEAT_ADM = 1u << 1,    /* libvmaf float ADM, 4 scales        (same call site)               */
   PQA_FEAT_MOTION = 1u << 2, /* libvmaf motion (SAD of blurred ref) (same call site)              */
   PQA_FEAT_PSNR = 1u << 3,   /* FFmpeg psnr filter: per-plane SSE   (:1027-1034)                  */
+  /* A plane narrower or lower than 8 samples holds no 8 x 8 window (a chroma plane of a small frame at a chroma shift of
+   * 2, e.g. 5 x 5 for 19 x 19): no SSIM is computed for it and its PQA_REC_SSIM slot is exactly 0.0, as vf_ssim.c's
+   * ssim_plane returns for it; the plane's SSE (PQA_FEAT_PSNR) is unaffected. */
   PQA_FEAT_SSIM = 1u << 4,   /* FFmpeg ssim filter: per-plane SSIM  (:1057-1064)                  */
   PQA_FEAT_VMAF = PQA_FEAT_VIF | PQA_FEAT_ADM | PQA_FEAT_MOTION,
   PQA_FEAT_ALL = PQA_FEAT_VMAF | PQA_FEAT_PSNR | PQA_FEAT_SSIM,  /* stays 31: the features of the 24-double record */

@@ -107,6 +107,9 @@ def _run(w, h, bpc, hs, vs, refs, diss, features=256, **kw):
 CASES = [(64, 48, 8, 1, 1), (161, 161, 10, 1, 0), (161, 161, 12, 0, 0), (352, 288, 12, 1, 1), (352, 288, 8, 1, 0),
          (1039, 913, 8, 1, 1), (1039, 913, 10, 0, 0), (1280, 720, 10, 1, 1), (1920, 1080, 12, 1, 1), (1920, 1080, 8, 1, 0),
          (3840, 2160, 8, 1, 1), (3840, 2160, 10, 1, 1)]
+# the six layouts beside 4:4:4 / 4:2:2 / 4:2:0 (rolled pixel loops, `break` at the picture edge), at two odd sizes
+CASES += [(w, h, bpc, hs, vs) for (hs, vs) in [(2, 2), (2, 1), (2, 0), (1, 2), (0, 1), (0, 2)]
+          for (w, h) in [(161, 161), (1039, 913)] for bpc in ((8, 10, 12) if (hs, vs) in [(2, 2), (0, 1)] else (8, 10))]
 
 
 @pytest.mark.parametrize("w,h,bpc,hs,vs", CASES)

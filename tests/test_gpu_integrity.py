@@ -91,7 +91,10 @@ def test_create_defaults_and_threshold_rules():
 @pytest.mark.parametrize("bpc", [8, 10, 12])
 @pytest.mark.parametrize("w,h,hs,vs,planes", [(16, 16, 1, 1, 3), (16, 16, 0, 0, 1), (17, 19, 1, 1, 3), (64, 48, 1, 0, 3),
                                               (125, 61, 0, 0, 3), (321, 241, 1, 1, 3), (321, 241, 1, 1, 1), (352, 288, 1, 0, 3),
-                                              (641, 359, 2, 2, 3), (1920, 1080, 1, 1, 3), (1920, 1080, 0, 0, 3)])
+                                              (641, 359, 2, 2, 3), (1920, 1080, 1, 1, 3), (1920, 1080, 0, 0, 3)] +
+                         # the mixed layouts: the two chroma shifts differ
+                         [(w, h, hs, vs, 3) for (hs, vs) in [(2, 0), (0, 2), (1, 2), (2, 1), (0, 1)]
+                          for (w, h) in [(17, 19), (64, 48)]])
 @pytest.mark.parametrize("kind", ["noise", "extreme", "dark"])
 def test_rows_equal_the_restatement_as_integers(bpc, w, h, hs, vs, planes, kind):
     n = 3 if w * h > 1_000_000 else 4

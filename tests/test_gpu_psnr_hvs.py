@@ -99,6 +99,9 @@ def _check(row, ref, dis, bpc, tag):
 
 CASES = [(16, 16, 8, 1, 1), (64, 48, 10, 1, 0), (161, 161, 12, 0, 0), (352, 288, 8, 1, 1), (1039, 913, 10, 1, 1),
          (1039, 913, 12, 1, 0), (1280, 720, 8, 0, 0), (1920, 1080, 12, 1, 1), (3840, 2160, 8, 1, 1), (3840, 2160, 10, 1, 1)]
+# the mixed layouts (the two chroma shifts differ), at sizes that leave partial blocks in every plane
+CASES += [(w, h, bpc, hs, vs) for (hs, vs) in [(2, 0), (0, 2), (1, 2), (2, 1), (0, 1)] for (w, h) in [(37, 41), (233, 57)]
+          for bpc in (8, 12)]
 
 
 @pytest.mark.parametrize("w,h,bpc,hs,vs", CASES)
@@ -127,6 +130,15 @@ def test_identical_frames_give_inf():
     refs, _ = _frames(w, h, bpc, 1, 1, 2, seed=3)
     _, _, ext2 = _run(w, h, bpc, 1, 1, refs, refs)
     assert np.isposinf(ext2[:, :4]).all() and (ext2[:, 4:7] == 0).all()
+
+
+@pytest.mark.parametrize("hs,vs", [(2, 0), (0, 2), (2, 2), (1, 2), (2, 1)])
+def test_16x16_with_a_shift_of_two_is_rejected(hs, vs):
+    from pqa2_amd import _native as N
+    refs, diss = _frames(16, 16, 8, hs, vs, 1, seed=1)
+    with pytest.raises(N.PqaError, match="psnr_hvs needs every plane >= 8x8") as e:
+        _run(16, 16, 8, hs, vs, refs, diss)
+    assert e.value.code == N.PQA_EINVAL
 
 
 @pytest.mark.parametrize("bpc", [8, 10])

@@ -98,10 +98,16 @@ def test_hook_flat_and_dark_content(kind):
         assert wsse == R.frame([refs[1][0]], [diss[1][0]], refs[0][0], None, bpc)[0][0]
 
 
+# the mixed layouts (the two shifts differ, so the chroma blocks are not square: cbx != cby); pqa_create's block-grid
+# check accepts every one of them at these sizes
+MIXED = [(w, h, hs, vs, bpc, 3) for (hs, vs) in [(2, 0), (0, 2), (1, 2), (2, 1), (0, 1)] for (w, h) in [(352, 288), (45, 45)]
+         for bpc in (8, 10)]
+
+
 @pytest.mark.parametrize("w,h,hs,vs,bpc,planes", [(352, 288, 1, 1, 8, 3), (640, 480, 1, 0, 10, 3), (642, 480, 0, 0, 12, 3),
                                                   (1920, 1080, 1, 1, 10, 3), (2560, 1440, 1, 1, 8, 3),
                                                   (3840, 2160, 1, 1, 8, 3), (45, 45, 1, 1, 8, 3), (44, 44, 1, 1, 8, 3),
-                                                  (1280, 720, 1, 1, 8, 1), (2050, 1152, 2, 2, 10, 3)])
+                                                  (1280, 720, 1, 1, 8, 1), (2050, 1152, 2, 2, 10, 3)] + MIXED)
 @pytest.mark.parametrize("hfr", [False, True])
 def test_full_path_equals_the_restatement(w, h, hs, vs, bpc, planes, hfr):
     refs, diss = _frames(w, h, bpc, hs, vs, 4, seed=11, planes=planes)
