@@ -312,8 +312,26 @@ PQA_API int pqa_submit_device(pqa_ctx* ctx, int64_t first_index, int32_t n_frame
  * names the two inputs).  NV12: 8-bit Y plane + ONE plane of interleaved U,V pairs at half
  * resolution in both directions.  P01X: the same layout with 16-bit little-endian samples whose value sits in the UPPER
  * bit_depth bits (P010 for a 10-bit context, P012 for a 12-bit one).  Frame f's planes start at luma + f * luma_frame_pitch
- * and chroma + f * chroma_frame_pitch; pitches in BYTES.  chroma may be NULL when the context has n_planes == 1. */
-enum { PQA_SURFACE_NV12 = 1, PQA_SURFACE_P01X = 2 };
+ * and chroma + f * chroma_frame_pitch; pitches in BYTES.  chroma may be NULL when the context has n_planes == 1.
+ *
+ * Packed capture formats: what a capture card delivers (the reference's default pixel format for DeckLink devices is
+ * uyvy422, app/options_manager.py:78; v210 is the card's 10-bit format).  All three are 4:2:2: with cw = ceil(w / 2) the
+ * chroma planes are cw x h, chroma shifts (1, 0).  For a packed clip luma / luma_row_pitch / luma_frame_pitch describe the
+ * PACKED frames and the chroma fields are ignored.
+ *   PQA_SURFACE_UYVY, 8 bit: macropixel k of a row is the four bytes U_k, Y_2k, V_k, Y_2k+1; a row holds cw macropixels (the
+ *     last Y of an odd-width row is present and never used).  Minimum row pitch 4 * cw bytes.
+ *   PQA_SURFACE_YUYV, 8 bit (YUY2): the same with the bytes Y_2k, U_k, Y_2k+1, V_k.
+ *   PQA_SURFACE_V210, 10 bit: a row is groups of 6 pixels in four little-endian 32-bit words, three 10-bit components per
+ *     word in bits 0-9, 10-19, 20-29 (bits 30-31 are undefined and influence nothing):
+ *         w0 = U0 | Y0 << 10 | V0 << 20     w1 = Y1 | U1 << 10 | Y2 << 20
+ *         w2 = V1 | Y3 << 10 | U2 << 20     w3 = Y4 | V2 << 10 | Y5 << 20
+ *     ceil(w / 6) groups per row (components beyond w / cw in the last group are present and never used).  Minimum row
+ *     pitch 16 * ceil(w / 6) bytes; base and pitches are multiples of 4.  Files pad rows to ((w + 47) / 48) * 128 bytes.
+ *     The unpacked samples are LSB-aligned uint16 0 ... 1023.
+ * A format fits a context when the bit depths agree: NV12 / UYVY / YUYV 8, V210 10, P01X 10 or 12.  No row is read beyond
+ * its minimum bytes: a caller's last row may end at the end of its allocation.
+ * PQA_SURFACE_PLANAR names planar planes in pqa_host_clip (pqa_submit_packed) only. */
+enum { PQA_SURFACE_PLANAR = 0, PQA_SURFACE_NV12 = 1, PQA_SURFACE_P01X = 2, PQA_SURFACE_UYVY = 3, PQA_SURFACE_YUYV = 4, PQA_SURFACE_V210 = 5 };
 typedef struct pqa_surface_clip {
   uint32_t struct_size;        /* sizeof(pqa_surface_clip) */
   uint32_t format;             /* PQA_SURFACE_* */
@@ -328,9 +346,39 @@ typedef struct pqa_surface_clip {
  * context's own staging; nothing crosses PCIe).  The context must be 4:2:0 (chroma shifts 1, 1) when n_planes == 3.
  * prev_ref (nullable) carries, as its frame 0, the reference frame first_index-1 -- the motion halo of a frame-sharded
  * rank; NULL continues from the last frame the context saw, as pqa_submit_device does.  Same record semantics as the
- * other submit calls. */
+ * other submit calls.
+ * Each of ref, dis and prev_ref may instead be a packed capture clip (PQA_SURFACE_UYVY / _YUYV / _V210, chosen per side): it
+ * is unpacked on the device into the context's own staging (unpack.hip; never scored in place), and the records are
+ * bit-identical to a planar submission of the same samples.  With n_planes == 3 a packed side needs the context's chroma
+ * shifts to be (1, 0) and an NV12 / P01X side (1, 1), so the two kinds mix only in a luma-only context (n_planes == 1:
+ * no chroma is decoded).  PQA_EINVAL, before any device call, on a format that does not fit the context's bit depth, a
+ * row pitch below the format's minimum, or a v210 base / pitch that is not a multiple of 4. */
 PQA_API int pqa_submit_surfaces(pqa_ctx* ctx, int64_t first_index, int32_t n_frames, const pqa_surface_clip* ref,
                                 const pqa_surface_clip* dis, const pqa_surface_clip* prev_ref);
+
+/* A clip in HOST memory for pqa_submit_packed.  format PQA_SURFACE_PLANAR: frames[] holds n_frames * n_planes plane
+ * pointers, frame-major (frame f's plane p at frames[f * n_planes + p]), rows strides[p] bytes apart as in pqa_submit.
+ * A packed format (PQA_SURFACE_UYVY / _YUYV / _V210, fitting the context's bit depth): frames[] holds n_frames pointers
+ * to packed frames, rows strides[0] bytes apart. */
+typedef struct pqa_host_clip {
+  uint32_t struct_size;        /* sizeof(pqa_host_clip) */
+  uint32_t format;             /* PQA_SURFACE_PLANAR or a packed format */
+  const void* const* frames;
+  int64_t strides[3];
+} pqa_host_clip;
+
+/* Submit n_frames consecutive frame pairs from HOST memory where either side (independently) is a packed capture clip.
+ * The packed bytes are copied into pinned memory as they are, cross PCIe once and are unpacked in device memory: nothing is
+ * de-interleaved on the host, and a v210 frame moves 8/3 bytes per pixel where its planar form moves 4.  Frames pending
+ * from pqa_submit are flushed first, as pqa_submit_surfaces does; the frames then travel in chunks of at most 8 through
+ * grow-only pinned and device buffers of this entry's own (two alternating sets, allocated on first use, so that a chunk is
+ * copied and uploaded while the kernels of the chunk before run).  Synchronous on the host side: on
+ * return the caller's buffers are free, the kernels are queued and the records are collected as usual.  With
+ * n_planes == 3 the context must be 4:2:2 (chroma shifts 1, 0) when a side is packed.  PQA_EINVAL, before any device
+ * call, on a null pointer, a struct_size or format mismatch, or a stride below a row (v210: no multiple of 4);
+ * PQA_ESTATE, before anything is copied, when a record slot of the run is still uncollected. */
+PQA_API int pqa_submit_packed(pqa_ctx* ctx, int64_t first_index, int32_t n_frames, const pqa_host_clip* ref,
+                              const pqa_host_clip* dis);
 
 /* Host-memory variant of the halo for the pqa_submit path.  pqa_set_motion_halo(c, p, s) is
  * pqa_set_ref_history(c, &p, 1, s); p == NULL restarts the chain (n_prev = 0). */
@@ -554,6 +602,31 @@ PQA_API int pqa_resample(pqa_ctx* ctx, const pqa_resample_spec* spec, const void
 PQA_API int pqa_resample_device(pqa_ctx* ctx, const pqa_resample_spec* spec, const void* src, int64_t src_row_pitch,
                                 int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
                                 int32_t n_frames);
+
+/* Packed capture frames -> planes, synchronously: n_frames frames of width x height in one of the packed formats above
+ * (PQA_SURFACE_UYVY / _YUYV / _V210) become a Y plane of width x height and U, V planes of ceil(width / 2) x height samples
+ * (u8; v210: LSB-aligned u16).  The planes are the same integers a planar file of the clip holds, so there is nothing to
+ * pin.  Any context, no feature bit; the size and the sample format are the call's own (each size 1 ... 8192), independent
+ * of the context's.  This is how the side analyses of resident clips, pqa_resample or pqa_submit_device get planes from a
+ * packed capture.  No source row is read beyond the format's minimum row bytes and no destination row is written beyond
+ * its samples.  PQA_EINVAL, before any device call, on a null spec, a bad struct_size or format, a size outside 1 ... 8192,
+ * a negative frame count, a null source or luma destination, a row pitch below a row, a v210 base / pitch that is not a
+ * multiple of 4, or a destination that is not made of whole samples.  n_frames == 0 succeeds and writes nothing.
+ *
+ * pqa_unpack_device: both clips in device memory under the ordering contract of pqa_submit_device; the planes of dst are
+ * WRITTEN (its pointers are const only because the struct is shared).  dst->plane[1] and dst->plane[2] both NULL: luma only,
+ * no chroma is decoded.
+ * pqa_unpack: frames in HOST memory (src_frames[f]: a packed frame, rows src_row_stride bytes apart; dst_planes[f * 3 + p]:
+ * plane p of frame f, rows dst_strides[p] bytes apart; dst_planes[f * 3 + 1] and [f * 3 + 2] NULL in frame 0: luma only).
+ * They travel in chunks of 8 through the pinned buffers of pqa_resample and device buffers of this entry's own. */
+typedef struct pqa_unpack_spec {
+  uint32_t struct_size, format; /* sizeof(pqa_unpack_spec); PQA_SURFACE_UYVY / _YUYV / _V210 */
+  uint32_t width, height;       /* of the luma plane, 1 ... 8192 */
+} pqa_unpack_spec;
+PQA_API int pqa_unpack_device(pqa_ctx* ctx, const pqa_unpack_spec* spec, const void* src, int64_t src_row_pitch,
+                              int64_t src_frame_pitch, int32_t n_frames, const pqa_device_clip* dst);
+PQA_API int pqa_unpack(pqa_ctx* ctx, const pqa_unpack_spec* spec, const void* const* src_frames, int64_t src_row_stride,
+                       int32_t n_frames, void* const* dst_planes, const int64_t dst_strides[3]);
 
 /* Sub-pixel registration: the tile-wise gradient moments of n_frames frame pairs of one plane, synchronously -- the
  * Lucas-Kanade normal equations of every tile, from which pqa2_amd/align.py (solve_geometry, register) estimates a sub-pixel

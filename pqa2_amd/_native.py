@@ -54,8 +54,8 @@ GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 # every symbol include/pqa_vmaf.h declares
 EXPORTS = [
     "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
-    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
-    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
+    "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_submit_packed", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
+    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape",
     "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
@@ -80,12 +80,24 @@ class PqaDeviceClip(C.Structure):
 
 
 SURFACE_NV12, SURFACE_P01X = 1, 2
+# packed capture formats (4:2:2; UYVY / YUYV 8 bit, V210 10 bit); PLANAR: planar planes in a PqaHostClip only
+SURFACE_PLANAR, SURFACE_UYVY, SURFACE_YUYV, SURFACE_V210 = 0, 3, 4, 5
+PACKED_FORMATS = {"uyvy422": SURFACE_UYVY, "yuyv422": SURFACE_YUYV, "v210": SURFACE_V210}
+PACKED_BIT_DEPTH = {SURFACE_UYVY: 8, SURFACE_YUYV: 8, SURFACE_V210: 10}
 
 
 class PqaSurfaceClip(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("luma", C.c_void_p), ("chroma", C.c_void_p),
                 ("luma_row_pitch", C.c_int64), ("luma_frame_pitch", C.c_int64),
                 ("chroma_row_pitch", C.c_int64), ("chroma_frame_pitch", C.c_int64)]
+
+
+class PqaHostClip(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("frames", C.POINTER(C.c_void_p)), ("strides", C.c_int64 * 3)]
+
+
+class PqaUnpackSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
 RESAMPLE_BILINEAR, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS3 = 0, 1, 2
@@ -207,6 +219,7 @@ def load():
     lib.pqa_submit_device.argtypes = [vp, i64, i32, C.POINTER(PqaDeviceClip), C.POINTER(PqaDeviceClip), vp, i64]
     lib.pqa_submit_surfaces.argtypes = [vp, i64, i32, C.POINTER(PqaSurfaceClip), C.POINTER(PqaSurfaceClip),
                                         C.POINTER(PqaSurfaceClip)]
+    lib.pqa_submit_packed.argtypes = [vp, i64, i32, C.POINTER(PqaHostClip), C.POINTER(PqaHostClip)]
     lib.pqa_set_motion_halo.argtypes = [vp, vp, i64]
     lib.pqa_flush.argtypes = [vp]
     lib.pqa_collect.argtypes = [vp, i64, i32, vp]
@@ -239,6 +252,8 @@ def load():
     lib.pqa_level_bins.argtypes = [vp]
     lib.pqa_resample.argtypes = [vp, C.POINTER(PqaResampleSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32]
     lib.pqa_resample_device.argtypes = [vp, C.POINTER(PqaResampleSpec), vp, i64, i64, vp, i64, i64, i32]
+    lib.pqa_unpack_device.argtypes = [vp, C.POINTER(PqaUnpackSpec), vp, i64, i64, i32, C.POINTER(PqaDeviceClip)]
+    lib.pqa_unpack.argtypes = [vp, C.POINTER(PqaUnpackSpec), C.POINTER(vp), i64, i32, C.POINTER(vp), C.POINTER(i64 * 3)]
     lib.pqa_flow_moments.argtypes = [vp, C.POINTER(PqaFlowSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32, vp]
     lib.pqa_flow_moments_device.argtypes = [vp, C.POINTER(PqaFlowSpec), vp, i64, i64, vp, i64, i64, i32, vp]
     lib.pqa_line_profiles.argtypes = [vp, C.POINTER(PqaProfileSpec), C.POINTER(vp), i64, i32, vp]

@@ -798,6 +798,22 @@ struct PlaneSrc {
   int64_t off;
 };
 
+// The helpers that pack large frames, made on first use (a context of small frames never starts a thread).
+void ensure_pack_pool(pqa_ctx* c) {
+  if (c->pack_pool_tried) return;
+  c->pack_pool_tried = true;
+  // threads packing a frame, the caller included.  Default 8: plain host buffers reach the PCIe ceiling with 4, frames
+  // read from files (pread out of the page cache) or out of a memory-mapped file scale further (2160p through
+  // analyze_videos: 880 frames/s with 4, 1 370 with 8; beyond that the box's noise decides, profiles/r04o_pack_threads.txt)
+  const char* e = getenv("PQA_PACK_THREADS");
+  int n = e ? atoi(e) : 8;
+  const int hw = (int)std::thread::hardware_concurrency();
+  if (hw > 0 && n > hw) n = hw;
+  if (n > 1) {
+    try { c->pack_pool.reset(new PackPool(n - 1)); } catch (...) { c->pack_pool.reset(); }   // serial packing then
+  }
+}
+
 // n consecutive frame pairs (frame k's planes lie k * frame_step[side] bytes after src's; memory sources: n == 1) into
 // staging slots and onto the copy stream.  A run is cut into chunks that fit the current staging half; within a chunk the
 // helpers pack frame k + 1 while the caller queues the upload of frame k (PackPool::run_frames): one fork / join per
@@ -872,19 +888,7 @@ int submit_run(pqa_ctx* c, int64_t first_index, int n_frames, const PlaneSrc (&s
             }
           }
       }
-      if (c->slot_bytes >= (4u << 20) && !c->pack_pool_tried) {
-        c->pack_pool_tried = true;
-        // threads packing a frame, the caller included.  Default 8: plain host buffers reach the PCIe ceiling with 4, frames
-        // read from files (pread out of the page cache) or out of a memory-mapped file scale further (2160p through
-        // analyze_videos: 880 frames/s with 4, 1 370 with 8; beyond that the box's noise decides, profiles/r04o_pack_threads.txt)
-        const char* e = getenv("PQA_PACK_THREADS");
-        int n = e ? atoi(e) : 8;
-        const int hw = (int)std::thread::hardware_concurrency();
-        if (hw > 0 && n > hw) n = hw;
-        if (n > 1) {
-          try { c->pack_pool.reset(new PackPool(n - 1)); } catch (...) { c->pack_pool.reset(); }   // serial packing then
-        }
-      }
+      if (c->slot_bytes >= (4u << 20)) ensure_pack_pool(c);
       if (c->pack_pool && c->slot_bytes >= (4u << 20)) {
         ok = c->pack_pool->run_frames(c->pack_tasks.data(), (int)c->pack_tasks.size(), m, upload);
       } else {
@@ -1284,6 +1288,7 @@ void pqa_destroy(pqa_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
+  if (c->pk_stream) hipStreamSynchronize(c->pk_stream);
   for (int i = 0; i < 2; ++i) if (c->aux[i]) hipStreamSynchronize(c->aux[i]);
   prof_drain(c);
   for (void* p : c->allocs) hipFree(p);
@@ -1320,6 +1325,15 @@ void pqa_destroy(pqa_ctx* c) {
     if (L.dev) hipFree(L.dev);
     if (L.copied) hipEventDestroy(L.copied);
   }
+  for (int i = 0; i < 2; ++i) {
+    for (int sd = 0; sd < 2; ++sd) {
+      if (c->pk_pin[i][sd]) hipHostFree(c->pk_pin[i][sd]);
+      if (c->pk_dev[i][sd]) hipFree(c->pk_dev[i][sd]);
+    }
+    if (c->pk_copied[i]) hipEventDestroy(c->pk_copied[i]);
+    if (c->pk_computed[i]) hipEventDestroy(c->pk_computed[i]);
+  }
+  if (c->pk_stream) hipStreamDestroy(c->pk_stream);
   for (void* b : c->side_buf)
     if (b) hipFree(b);
   for (uint8_t* b : c->side_pin)
@@ -1384,6 +1398,46 @@ int pqa_submit_device(pqa_ctx* c, int64_t first_index, int32_t n_frames, const p
   return PQA_OK;
 }
 
+namespace {
+// does a surface / packed format fit a context of bpc bits?
+bool surface_fits(uint32_t format, int bpc) {
+  if (host::packed_format(format)) return host::packed_bit_depth(format) == bpc;
+  return format == (bpc <= 8 ? (uint32_t)PQA_SURFACE_NV12 : (uint32_t)PQA_SURFACE_P01X);
+}
+
+// the rules of a packed clip's rows (`who`: "surface", "reference clip"); no device call
+int check_packed_rows(pqa_ctx* c, const char* who, uint32_t format, const void* base, int64_t row_pitch, int64_t frame_pitch) {
+  const int64_t min_row = host::packed_min_row_bytes(format, c->pw[0]);
+  if (row_pitch < min_row)
+    return fail(c, PQA_EINVAL, "%s: packed row pitch %lld is smaller than a row of %lld bytes", who, (long long)row_pitch, (long long)min_row);
+  if (format == PQA_SURFACE_V210 && (((uintptr_t)base | (uintptr_t)row_pitch | (uintptr_t)frame_pitch) & 3))
+    return fail(c, PQA_EINVAL, "%s: v210 base and pitches must be multiples of 4", who);
+  return PQA_OK;
+}
+
+// n packed frames -> the planes of side sd of the surf_dev slots (luma only in a luma-only context)
+hipError_t unpack_to_slots(pqa_ctx* c, int sd, uint32_t format, const void* src, int64_t row_pitch, int64_t frame_pitch, int n,
+                           pqa_device_clip* out) {
+  void* dst[3] = {nullptr, nullptr, nullptr};
+  int64_t rp[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
+  for (int p = 0; p < c->n_planes; ++p) {
+    dst[p] = c->surf_dev + c->plane_off[sd][p];
+    rp[p] = c->slot_row_pitch[p];
+    fp[p] = (int64_t)c->slot_bytes;
+    out->plane[p] = dst[p]; out->row_pitch[p] = rp[p]; out->frame_pitch[p] = fp[p];
+  }
+  return launch_unpack(c->stream, (int)format, src, row_pitch, frame_pitch, dst, rp, fp, c->pw[0], c->ph[0], n);
+}
+
+int ensure_surf_dev(pqa_ctx* c) {
+  if (c->surf_dev) return PQA_OK;
+  slot_layout(c);
+  HIPCHK(c, hipMalloc((void**)&c->surf_dev, c->slot_bytes * (size_t)c->B));
+  c->allocs.push_back(c->surf_dev);
+  return PQA_OK;
+}
+}  // namespace
+
 int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const pqa_surface_clip* ref,
                         const pqa_surface_clip* dis, const pqa_surface_clip* prev_ref) {
   if (!c) return PQA_EINVAL;
@@ -1393,53 +1447,76 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)",
                 n_frames, c->capacity);
   const int bpc = (int)c->cfg.bit_depth;
-  const uint32_t want = bpc <= 8 ? (uint32_t)PQA_SURFACE_NV12 : (uint32_t)PQA_SURFACE_P01X;
   const pqa_surface_clip* all[3] = {ref, dis, prev_ref};
+  bool any_packed = false, any_decoder = false;
   for (int i = 0; i < 3; ++i) {
     const pqa_surface_clip* s = all[i];
     if (!s) continue;
     if (s->struct_size != sizeof(pqa_surface_clip)) return fail(c, PQA_EINVAL, "pqa_surface_clip.struct_size mismatch");
-    if (s->format != want)
-      return fail(c, PQA_EINVAL, "surface format %u does not fit a %d-bit context (NV12 for 8 bit, P01X above)", s->format, bpc);
+    if (!surface_fits(s->format, bpc))
+      return fail(c, PQA_EINVAL,
+                  "surface format %u does not fit a %d-bit context (NV12, UYVY, YUYV for 8 bit; P01X above, V210 for 10 bit)",
+                  s->format, bpc);
+    if (host::packed_format(s->format)) {
+      if (!s->luma) return fail(c, PQA_EINVAL, "surface luma pointer / pitch");
+      const int rc = check_packed_rows(c, "surface", s->format, s->luma, s->luma_row_pitch, s->luma_frame_pitch);
+      if (rc != PQA_OK) return rc;
+      if (i < 2) any_packed = true;
+      continue;
+    }
+    if (i < 2) any_decoder = true;
     if (!s->luma || s->luma_row_pitch < (int64_t)c->pw[0] * c->esize || s->luma_row_pitch % c->esize)
       return fail(c, PQA_EINVAL, "surface luma pointer / pitch");
     if (i < 2 && c->n_planes == 3 &&
         (!s->chroma || s->chroma_row_pitch < (int64_t)c->pw[1] * 2 * c->esize || s->chroma_row_pitch % c->esize))
       return fail(c, PQA_EINVAL, "surface chroma pointer / pitch");
   }
-  if (c->n_planes == 3 && (c->cfg.chroma_hshift != 1 || c->cfg.chroma_vshift != 1))
+  if (c->n_planes == 3 && any_decoder && (c->cfg.chroma_hshift != 1 || c->cfg.chroma_vshift != 1))
     return fail(c, PQA_EINVAL, "decoder surfaces are 4:2:0: the context's chroma shifts must be 1, 1");
+  if (c->n_planes == 3 && any_packed && (c->cfg.chroma_hshift != 1 || c->cfg.chroma_vshift != 0))
+    return fail(c, PQA_EINVAL, "packed capture formats are 4:2:2: the context's chroma shifts must be 1, 0");
   HIPCHK(c, hipSetDevice(c->device));
   int rc = flush_pending(c);
   if (rc != PQA_OK) return rc;
   if ((rc = check_slots_free(c, first_index, n_frames)) != PQA_OK) return rc;   // before anything is unpacked
-  const bool shift_luma = bpc > 8;
+  const bool shift_luma = bpc > 8;   // of a decoder surface
   const int shift = 16 - bpc;
   // Unpacked planes go to a device buffer of B slots.  One buffer is enough: unpack and scoring run on the same stream,
   // so the next batch's unpack starts when this batch's kernels are done.
-  const bool stage = shift_luma || c->n_planes == 3;
-  if (stage && !c->surf_dev) {
-    slot_layout(c);
-    HIPCHK(c, hipMalloc((void**)&c->surf_dev, c->slot_bytes * (size_t)c->B));
-    c->allocs.push_back(c->surf_dev);
-  }
-  if (prev_ref && (c->cfg.features & PQA_FEAT_MOTION)) {
-    if (shift_luma) {   // the halo frame goes where a previous batch would have left it, shifted down
+  const bool stage = shift_luma || c->n_planes == 3 || any_packed;
+  if (stage && (rc = ensure_surf_dev(c)) != PQA_OK) return rc;
+  const bool prev_packed = prev_ref && host::packed_format(prev_ref->format);
+  const bool prev_staged = prev_ref && (prev_packed || shift_luma);   // not usable where it lies
+  if (prev_staged && (c->cfg.features & PQA_FEAT_MOTION)) {
+    // the halo frame goes where a previous batch would have left it, unpacked / shifted down
+    if (prev_packed) {
+      void* dst[3] = {c->last_luma, nullptr, nullptr};
+      const int64_t rp[3] = {c->last_luma_pitch, 0, 0}, fp[3] = {0, 0, 0};
+      HIPCHK(c, launch_unpack(c->stream, (int)prev_ref->format, prev_ref->luma, prev_ref->luma_row_pitch, 0, dst, rp, fp, c->pw[0],
+                              c->ph[0], 1));
+    } else {
       HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->last_luma, c->last_luma_pitch,
                                       0, c->pw[0], c->ph[0], shift, 1));
-      c->halo_armed = true;
     }
+    c->halo_armed = true;
   }
-  // xpsnr's and siti's reference frame first-1, shifted down likewise
-  const bool shift_prev = prev_ref && (c->cfg.features & (PQA_FEAT_XPSNR | PQA_FEAT_SITI)) && shift_luma;
+  // xpsnr's and siti's reference frame first-1, unpacked / shifted down likewise
+  const bool shift_prev = prev_staged && (c->cfg.features & (PQA_FEAT_XPSNR | PQA_FEAT_SITI));
   const int64_t shift_prev_pitch = round_up((int64_t)c->pw[0] * c->esize, 64);
   if (shift_prev) {
     if (!c->xp_prev) {
       HIPCHK(c, hipMalloc((void**)&c->xp_prev, (size_t)shift_prev_pitch * c->ph[0]));
       c->allocs.push_back(c->xp_prev);
     }
-    HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->xp_prev, shift_prev_pitch, 0,
-                                    c->pw[0], c->ph[0], shift, 1));
+    if (prev_packed) {
+      void* dst[3] = {c->xp_prev, nullptr, nullptr};
+      const int64_t rp[3] = {shift_prev_pitch, 0, 0}, fp[3] = {0, 0, 0};
+      HIPCHK(c, launch_unpack(c->stream, (int)prev_ref->format, prev_ref->luma, prev_ref->luma_row_pitch, 0, dst, rp, fp, c->pw[0],
+                              c->ph[0], 1));
+    } else {
+      HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->xp_prev, shift_prev_pitch, 0,
+                                      c->pw[0], c->ph[0], shift, 1));
+    }
   }
   const int n_launch = (n_frames + c->B - 1) / c->B;   // equal launches, as in pqa_submit_device
   const int per = n_launch ? (n_frames + n_launch - 1) / n_launch : 0;
@@ -1452,6 +1529,10 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     for (int sd = 0; sd < 2; ++sd) {
       const pqa_surface_clip* s = side[sd];
       const uint8_t* luma = (const uint8_t*)s->luma + (int64_t)done * s->luma_frame_pitch;
+      if (host::packed_format(s->format)) {   // a packed clip is never scored in place
+        HIPCHK(c, unpack_to_slots(c, sd, s->format, luma, s->luma_row_pitch, s->luma_frame_pitch, n, out[sd]));
+        continue;
+      }
       if (shift_luma) {
         uint8_t* dst = c->surf_dev + c->plane_off[sd][0];
         HIPCHK(c, launch_ingest_shift16(c->stream, luma, s->luma_row_pitch, s->luma_frame_pitch, dst, c->slot_row_pitch[0],
@@ -1473,10 +1554,10 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
         out[sd]->frame_pitch[1] = out[sd]->frame_pitch[2] = (int64_t)c->slot_bytes;
       }
     }
-    // the halo of the first batch: an NV12 luma plane is usable as it is; a shifted one was armed above
+    // the halo of the first batch: an NV12 luma plane is usable as it is; an unpacked / shifted one was armed above
     const void* prev = nullptr;
     int64_t prev_pitch = 0;
-    if (done == 0 && prev_ref && !shift_luma) { prev = prev_ref->luma; prev_pitch = prev_ref->luma_row_pitch; }
+    if (done == 0 && prev_ref && !prev_staged) { prev = prev_ref->luma; prev_pitch = prev_ref->luma_row_pitch; }
     if (done == 0 && shift_prev) {   // the same frame as the armed halo
       prev = c->xp_prev; prev_pitch = shift_prev_pitch;
     }
@@ -1484,6 +1565,169 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     if (rc != PQA_OK) return rc;
     done += n;
   }
+  return PQA_OK;
+}
+
+namespace {
+// one side of pqa_submit_packed: the argument rules (no device call) and how a chunk of it is staged
+int host_clip_check(pqa_ctx* c, const char* who, const pqa_host_clip* h, int n_frames, host::ClipLayout* L) {
+  if (h->struct_size != sizeof(pqa_host_clip)) return fail(c, PQA_EINVAL, "submit_packed: %s clip: pqa_host_clip.struct_size mismatch", who);
+  const bool packed = host::packed_format(h->format);
+  if (!packed && h->format != PQA_SURFACE_PLANAR)
+    return fail(c, PQA_EINVAL, "submit_packed: %s clip: format %u is neither planar nor a packed capture format", who, h->format);
+  if (packed && host::packed_bit_depth(h->format) != (int)c->cfg.bit_depth)
+    return fail(c, PQA_EINVAL, "submit_packed: %s clip: format %u does not fit a %d-bit context (UYVY, YUYV: 8 bit; V210: 10 bit)", who,
+                h->format, (int)c->cfg.bit_depth);
+  if (n_frames > 0 && !h->frames) return fail(c, PQA_EINVAL, "submit_packed: %s clip: null frame list", who);
+  if (packed) {
+    char name[48];
+    snprintf(name, sizeof name, "submit_packed: %s clip", who);
+    for (int f = 0; f < n_frames; ++f) {
+      if (!h->frames[f]) return fail(c, PQA_EINVAL, "%s: frame %d pointer is null", name, f);
+      const int rc = check_packed_rows(c, name, h->format, h->frames[f], h->strides[0], 0);
+      if (rc != PQA_OK) return rc;
+    }
+    *L = host::packed_layout(h->format, c->pw[0], c->ph[0]);
+    return PQA_OK;
+  }
+  size_t rb[3] = {0, 0, 0};
+  for (int p = 0; p < c->n_planes; ++p) {
+    rb[p] = (size_t)c->pw[p] * c->esize;
+    if (n_frames > 0 && (h->strides[p] < 0 || (size_t)h->strides[p] < rb[p]))
+      return fail(c, PQA_EINVAL, "submit_packed: %s clip: plane %d stride smaller than a row", who, p);
+  }
+  for (int64_t i = 0; i < (int64_t)n_frames * c->n_planes; ++i)
+    if (!h->frames[i]) return fail(c, PQA_EINVAL, "submit_packed: %s clip: plane pointer %lld is null", who, (long long)i);
+  *L = host::clip_layout(c->n_planes, rb, c->ph, 64, 256);   // the slot layout of the other host paths
+  return PQA_OK;
+}
+
+int packed_reserve(pqa_ctx* c, int set, int sd, size_t bytes) {
+  if (c->pk_pin_cap[set][sd] < bytes) {
+    if (c->pk_pin[set][sd]) {
+      HIPCHK(c, hipHostFree(c->pk_pin[set][sd]));
+      c->pk_pin[set][sd] = nullptr;
+      c->pk_pin_cap[set][sd] = 0;
+    }
+    HIPCHK(c, hipHostMalloc((void**)&c->pk_pin[set][sd], bytes, hipHostMallocDefault));
+    c->pk_pin_cap[set][sd] = bytes;
+  }
+  if (c->pk_dev_cap[set][sd] < bytes) {
+    if (c->pk_dev[set][sd]) {
+      HIPCHK(c, hipFree(c->pk_dev[set][sd]));
+      c->pk_dev[set][sd] = nullptr;
+      c->pk_dev_cap[set][sd] = 0;
+    }
+    HIPCHK(c, hipMalloc((void**)&c->pk_dev[set][sd], bytes));
+    c->pk_dev_cap[set][sd] = bytes;
+  }
+  return PQA_OK;
+}
+}  // namespace
+
+int pqa_submit_packed(pqa_ctx* c, int64_t first_index, int32_t n_frames, const pqa_host_clip* ref, const pqa_host_clip* dis) {
+  if (!c) return PQA_EINVAL;
+  if (!ref || !dis || n_frames < 0 || first_index < 0) return fail(c, PQA_EINVAL, "bad argument");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames > c->capacity)
+    return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)",
+                n_frames, c->capacity);
+  const pqa_host_clip* side[2] = {ref, dis};
+  host::ClipLayout L[2];
+  bool any_packed = false;
+  for (int sd = 0; sd < 2; ++sd) {
+    const int rc = host_clip_check(c, sd ? "captured" : "reference", side[sd], n_frames, &L[sd]);
+    if (rc != PQA_OK) return rc;
+    any_packed = any_packed || host::packed_format(side[sd]->format);
+  }
+  if (c->n_planes == 3 && any_packed && (c->cfg.chroma_hshift != 1 || c->cfg.chroma_vshift != 0))
+    return fail(c, PQA_EINVAL, "packed capture formats are 4:2:2: the context's chroma shifts must be 1, 0");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = flush_pending(c);
+  if (rc != PQA_OK) return rc;
+  if ((rc = check_slots_free(c, first_index, n_frames)) != PQA_OK) return rc;   // the whole run, before anything is copied
+  if (n_frames == 0) return PQA_OK;
+  const int chunk = n_frames < c->HB ? n_frames : c->HB;
+  if (any_packed && (rc = ensure_surf_dev(c)) != PQA_OK) return rc;
+  if (!c->pk_stream) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->pk_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) {
+      HIPCHK(c, hipEventCreateWithFlags(&c->pk_copied[i], hipEventDisableTiming));
+      HIPCHK(c, hipEventCreateWithFlags(&c->pk_computed[i], hipEventDisableTiming));
+    }
+  }
+  // Chunks alternate between the two sets: chunk k + 1 is packed while chunk k is uploaded, and uploaded (on pk_stream) while
+  // the kernels of chunk k run (on the context's stream).
+  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+    const int m = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+    const int set = c->pk_set;
+    if (c->pk_copied_pending[set]) {   // the set's pinned chunks still feed an earlier upload (a larger chunk must not free them)
+      HIPCHK(c, hipEventSynchronize(c->pk_copied[set]));
+      c->pk_copied_pending[set] = false;
+    }
+    if (c->pk_computed_pending[set] &&
+        (c->pk_dev_cap[set][0] < L[0].frame_bytes * (size_t)m || c->pk_dev_cap[set][1] < L[1].frame_bytes * (size_t)m)) {
+      HIPCHK(c, hipEventSynchronize(c->pk_computed[set]));   // the device copies are about to be replaced by larger ones
+      c->pk_computed_pending[set] = false;
+    }
+    for (int sd = 0; sd < 2; ++sd)
+      if ((rc = packed_reserve(c, set, sd, L[sd].frame_bytes * (size_t)m)) != PQA_OK) return rc;
+    // large frames are packed in ~1 MiB tasks by the pack pool of the pqa_submit path, small ones here
+    bool pooled = false;
+    if (L[0].frame_bytes + L[1].frame_bytes >= (4u << 20)) {
+      try {   // no exception may cross the C ABI
+        ensure_pack_pool(c);
+        if (c->pack_pool) {
+          c->pack_tasks.clear();
+          for (int sd = 0; sd < 2; ++sd)
+            host::pack_clip_tasks(c->pack_tasks, c->pk_pin[set][sd], L[sd], side[sd]->frames, side[sd]->strides, f0, m, 1u << 20);
+          pooled = c->pack_pool->run(c->pack_tasks.data(), (int)c->pack_tasks.size());   // memory sources cannot come up short
+        }
+      } catch (...) {
+        return fail(c, PQA_ENOMEM, "out of host memory while staging frame %lld", (long long)(first_index + f0));
+      }
+    }
+    if (c->pk_computed_pending[set]) {   // the set's device copies are still read by an earlier chunk's kernels
+      HIPCHK(c, hipStreamWaitEvent(c->pk_stream, c->pk_computed[set], 0));
+      c->pk_computed_pending[set] = false;
+    }
+    for (int sd = 0; sd < 2; ++sd) {
+      if (!pooled) host::pack_clip(c->pk_pin[set][sd], L[sd], side[sd]->frames, side[sd]->strides, f0, m);
+      HIPCHK(c, hipMemcpyAsync(c->pk_dev[set][sd], c->pk_pin[set][sd], L[sd].frame_bytes * (size_t)m, hipMemcpyHostToDevice, c->pk_stream));
+    }
+    HIPCHK(c, hipEventRecord(c->pk_copied[set], c->pk_stream));
+    c->pk_copied_pending[set] = true;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->pk_copied[set], 0));
+    c->pk_set ^= 1;
+    const int n_launch = (m + c->B - 1) / c->B;   // equal launches, as in pqa_submit_device
+    const int per = (m + n_launch - 1) / n_launch;
+    for (int done = 0; done < m;) {
+      const int n = m - done < per ? m - done : per;
+      pqa_device_clip clip[2] = {};
+      for (int sd = 0; sd < 2; ++sd) {
+        const uint8_t* base = c->pk_dev[set][sd] + (size_t)done * L[sd].frame_bytes;
+        if (host::packed_format(side[sd]->format)) {
+          HIPCHK(c, unpack_to_slots(c, sd, side[sd]->format, base, L[sd].plane[0].pitch, (int64_t)L[sd].frame_bytes, n, &clip[sd]));
+        } else {   // planar planes are scored where they were uploaded
+          for (int p = 0; p < c->n_planes; ++p) {
+            clip[sd].plane[p] = base + L[sd].off[p];
+            clip[sd].row_pitch[p] = L[sd].plane[p].pitch;
+            clip[sd].frame_pitch[p] = (int64_t)L[sd].frame_bytes;
+          }
+        }
+      }
+      rc = process_batch(c, first_index + f0 + done, n, &clip[0], &clip[1], nullptr, 0);
+      if (rc != PQA_OK) {   // whatever was queued still reads the set
+        c->pk_computed_pending[set] = hipEventRecord(c->pk_computed[set], c->stream) == hipSuccess;
+        return rc;
+      }
+      done += n;
+    }
+    HIPCHK(c, hipEventRecord(c->pk_computed[set], c->stream));
+    c->pk_computed_pending[set] = true;
+  }
+  // the caller's buffers are free: everything was copied into the pinned chunks above
   return PQA_OK;
 }
 
@@ -1773,6 +2017,8 @@ int pqa_reset(pqa_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+  if (c->pk_stream) HIPCHK(c, hipStreamSynchronize(c->pk_stream));
+  c->pk_copied_pending[0] = c->pk_copied_pending[1] = c->pk_computed_pending[0] = c->pk_computed_pending[1] = false;
   c->cancelled.store(0);
   c->done_seq = c->batch_seq;
   c->ring.reset();

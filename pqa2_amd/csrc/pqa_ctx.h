@@ -13,6 +13,7 @@
 
 #include "host_pack.h"
 #include "host_ring.h"
+#include "host_packed.h"
 #include "host_stage.h"
 #include "kernels.h"
 
@@ -56,6 +57,7 @@ enum SideBuf {
   SIDE_BAND_PART, SIDE_BAND_OUT,                                               // pqa_band_moments[_device], band_moments.hip: the workgroups' partial sums of a chunk, the sums
   SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums
   SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles
+  SIDE_UNPACK_SRC, SIDE_UNPACK_DST,                                            // pqa_unpack, unpack.hip: a chunk of uploaded packed frames / of unpacked planes
   kSideBufs
 };
 
@@ -189,6 +191,16 @@ struct pqa_ctx {
   std::thread pin_thread;            // pins the second staging half while the first one fills (ensure_staging)
   hipError_t pin_err = hipSuccess;   // its result; read after joining it (staging_half_ready)
   uint8_t* surf_dev = nullptr;   // pqa_submit_surfaces: B slots of unpacked planes (device only, allocated on first use)
+  // pqa_submit_packed: two sets (chunks alternate) of a grow-only pinned chunk and its device copy per side, allocated on first
+  // use; uploads run on a stream of their own.  copied: the upload out of a set's pinned chunks is done (the host packs them
+  // again, the kernels may read the device copy); computed: the kernels that read a set's device copy are done
+  uint8_t* pk_pin[2][2] = {};   // [set][side]
+  uint8_t* pk_dev[2][2] = {};
+  size_t pk_pin_cap[2][2] = {}, pk_dev_cap[2][2] = {};
+  hipStream_t pk_stream = nullptr;
+  hipEvent_t pk_copied[2] = {nullptr, nullptr}, pk_computed[2] = {nullptr, nullptr};
+  bool pk_copied_pending[2] = {false, false}, pk_computed_pending[2] = {false, false};
+  int pk_set = 0;
   std::unique_ptr<pqa::host::PackPool> pack_pool;
   bool pack_pool_tried = false;
   std::vector<pqa::host::PackTask> pack_tasks;

@@ -7,6 +7,8 @@
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
 
+#include "ingest.h"
+
 #include <climits>
 #include <cstdio>
 
@@ -981,6 +983,104 @@ int pqa_resample(pqa_ctx* c, const pqa_resample_spec* spec, const void* const* s
     for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
       for (int y = 0; y < dh; ++y)
         memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * df + (size_t)y * dp, dst_row);
+  }
+  return PQA_OK;
+}
+
+// ---- packed capture formats (unpack.hip) -----------------------------------------------------------------------------------
+
+namespace {
+// The argument rules both entries share, in spec_check's order (no device call); then the rows of the packed source.
+int unpack_check(pqa_ctx* c, const pqa_unpack_spec* sp, const void* src, const void* dst, int32_t n_frames, int64_t src_row,
+                 int64_t src_frame) {
+  const int rc = spec_check(c, "unpack", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    return host::packed_format(sp->format) ? PQA_OK : fail(c, PQA_EINVAL, "unpack: format %u is not a packed capture format (UYVY 3, YUYV 4, V210 5)", sp->format);
+  });
+  if (rc != PQA_OK || n_frames == 0) return rc;
+  const int64_t min_row = host::packed_min_row_bytes(sp->format, (int)sp->width);
+  if (src_row < min_row)
+    return fail(c, PQA_EINVAL, "unpack: source pitch %lld is smaller than a packed row of %lld bytes", (long long)src_row, (long long)min_row);
+  if (sp->format == PQA_SURFACE_V210 && ((src_row | src_frame) & 3)) return fail(c, PQA_EINVAL, "unpack: v210 pitch is not a multiple of 4");
+  return PQA_OK;
+}
+}  // namespace
+
+int pqa_unpack_device(pqa_ctx* c, const pqa_unpack_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
+                      int32_t n_frames, const pqa_device_clip* dst) {
+  int rc = unpack_check(c, spec, src, dst, n_frames, src_row_pitch, src_frame_pitch);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  if (!dst->plane[0]) return fail(c, PQA_EINVAL, "unpack: null luma destination");
+  if (!dst->plane[1] != !dst->plane[2]) return fail(c, PQA_EINVAL, "unpack: chroma destinations: both or neither");
+  if (spec->format == PQA_SURFACE_V210 && ((uintptr_t)src & 3)) return fail(c, PQA_EINVAL, "unpack: v210 source is not 4-byte aligned");
+  const int es = host::packed_sample_bytes(spec->format), w = (int)spec->width, h = (int)spec->height;
+  void* planes[3] = {nullptr, nullptr, nullptr};
+  for (int p = 0; p < (dst->plane[1] ? 3 : 1); ++p) {
+    planes[p] = const_cast<void*>(dst->plane[p]);
+    if (((uintptr_t)planes[p] | (uintptr_t)dst->row_pitch[p] | (uintptr_t)dst->frame_pitch[p]) & (uintptr_t)(es - 1))
+      return fail(c, PQA_EINVAL, "unpack: plane %d destination is not made of whole samples", p);
+    if (dst->row_pitch[p] < (int64_t)(p ? (w + 1) / 2 : w) * es) return fail(c, PQA_EINVAL, "unpack: plane %d destination pitch smaller than a row", p);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipError_t e = hipSuccess;
+  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid) {
+    void* at[3] = {nullptr, nullptr, nullptr};
+    for (int p = 0; p < 3; ++p)
+      if (planes[p]) at[p] = (uint8_t*)planes[p] + (int64_t)f0 * dst->frame_pitch[p];
+    e = launch_unpack(c->stream, (int)spec->format, (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch,
+                      at, dst->row_pitch, dst->frame_pitch, w, h, chunk_len(n_frames, f0, kGrid));
+  }
+  return side_finish(c, "unpack", e, nullptr, nullptr, 0);
+}
+
+int pqa_unpack(pqa_ctx* c, const pqa_unpack_spec* spec, const void* const* src_frames, int64_t src_row_stride, int32_t n_frames,
+               void* const* dst_planes, const int64_t dst_strides[3]) {
+  int rc = unpack_check(c, spec, src_frames, dst_planes, n_frames, src_row_stride, 0);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  if (!dst_strides) return fail(c, PQA_EINVAL, "unpack: null destination strides");
+  const int es = host::packed_sample_bytes(spec->format), w = (int)spec->width, h = (int)spec->height;
+  const int np = dst_planes[1] && dst_planes[2] ? 3 : 1;
+  if (np == 1 && (dst_planes[1] || dst_planes[2])) return fail(c, PQA_EINVAL, "unpack: chroma destinations: both or neither");
+  for (int f = 0; f < n_frames; ++f) {   // before anything is queued
+    if (!src_frames[f]) return fail(c, PQA_EINVAL, "unpack: source frame %d pointer is null", f);
+    if (spec->format == PQA_SURFACE_V210 && ((uintptr_t)src_frames[f] & 3)) return fail(c, PQA_EINVAL, "unpack: v210 source frame %d is not 4-byte aligned", f);
+    for (int p = 0; p < np; ++p)
+      if (!dst_planes[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "unpack: destination plane %d of frame %d is null", p, f);
+  }
+  for (int p = 0; p < np; ++p)
+    if (dst_strides[p] < (int64_t)(p ? (w + 1) / 2 : w) * es) return fail(c, PQA_EINVAL, "unpack: plane %d destination stride smaller than a row", p);
+  HIPCHK(c, hipSetDevice(c->device));
+  // Chunks of kRsChunk frames: packed bytes out through the first pinned chunk of the side analyses, planes back through
+  // the second, device buffers of this entry's own; a chunk is uploaded, unpacked, downloaded and copied out before the next.
+  const host::ClipLayout S = host::packed_layout(spec->format, w, h), D = host::unpacked_layout(spec->format, w, h, np);
+  const int chunk = n_frames < kRsChunk ? n_frames : kRsChunk;
+  rc = side_pin_reserve(c, 0, S.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, D.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_UNPACK_SRC, S.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_UNPACK_DST, D.frame_bytes * chunk);
+  if (rc != PQA_OK) return rc;
+  const int64_t src_strides[3] = {src_row_stride, 0, 0};
+  for (int f0 = 0; f0 < n_frames; f0 += kRsChunk) {
+    const int n = chunk_len(n_frames, f0, kRsChunk);
+    host::pack_clip(c->side_pin[0], S, src_frames, src_strides, f0, n);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_UNPACK_SRC], c->side_pin[0], S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+      void* at[3] = {nullptr, nullptr, nullptr};
+      int64_t rp[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
+      for (int p = 0; p < np; ++p) {
+        at[p] = (uint8_t*)c->side_buf[SIDE_UNPACK_DST] + D.off[p];
+        rp[p] = D.plane[p].pitch;
+        fp[p] = (int64_t)D.frame_bytes;
+      }
+      e = launch_unpack(c->stream, (int)spec->format, c->side_buf[SIDE_UNPACK_SRC], S.plane[0].pitch, (int64_t)S.frame_bytes, at, rp, fp, w, h, n);
+    }
+    rc = side_finish(c, "unpack", e, c->side_pin[1], c->side_buf[SIDE_UNPACK_DST], D.frame_bytes * n);
+    if (rc != PQA_OK) return rc;
+    host::unpack_clip_out(c->side_pin[1], D, dst_planes, dst_strides, f0, n);
   }
   return PQA_OK;
 }

@@ -268,6 +268,99 @@ class FeatureEngine:
         self._check(self.lib.pqa_submit_surfaces(self._ctx, first_index, n_frames, C.byref(ref), C.byref(dis),
                                                  C.byref(prev_ref) if prev_ref is not None else None))
 
+    # -- packed capture formats ----------------------------------------------------------------
+    @staticmethod
+    def _packed_format(fmt) -> int:
+        """PQA_SURFACE_* of a packed format given by name ("uyvy422", "yuyv422", "v210") or by constant"""
+        f = N.PACKED_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+        if f not in N.PACKED_BIT_DEPTH:
+            raise ValueError(f"packed format must be one of {sorted(N.PACKED_FORMATS)}, not {fmt!r}")
+        return int(f)
+
+    @staticmethod
+    def _unpack_spec(fmt: int, shape):
+        sp = N.PqaUnpackSpec()
+        sp.struct_size, sp.format = C.sizeof(N.PqaUnpackSpec), fmt
+        sp.width, sp.height = max(0, int(shape[1])), max(0, int(shape[0]))
+        return sp
+
+    def unpack(self, frames, fmt, shape, luma_only: bool = False):
+        """A list of (Y, U, V) -- or (Y,) with luma_only -- per frame: packed capture frames in HOST memory unpacked on the
+        GPU (pqa_unpack).  frames: 2-D uint8 arrays of packed rows (the rows of a frame may be padded; v210: 4-byte
+        aligned); fmt: "uyvy422", "yuyv422" or "v210"; shape = (height, width) of the luma plane.  Y is height x width, U and
+        V are height x ceil(width / 2); uint8, v210: uint16 values 0 ... 1023.  The size is the call's own."""
+        f = self._packed_format(fmt)
+        arrs = [np.asarray(a) for a in frames]
+        if any(a.ndim != 2 or a.dtype != np.uint8 or a.strides[1] != 1 or a.strides[0] != arrs[0].strides[0] for a in arrs):
+            arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrs]
+        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
+            raise ValueError("unpack needs 2-D arrays of packed rows of one size")
+        sp = self._unpack_spec(f, shape)
+        h, w = int(shape[0]), int(shape[1])
+        dt = np.uint16 if N.PACKED_BIT_DEPTH[f] > 8 else np.uint8
+        n, cw = len(arrs), (w + 1) // 2
+        out = [tuple(np.empty((h, w if p == 0 else cw), dt) for p in range(1 if luma_only else 3)) for _ in arrs]
+        sptr, dptr = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(3 * n, 1))()
+        for i, (a, o) in enumerate(zip(arrs, out)):
+            sptr[i] = a.ctypes.data
+            for p, plane in enumerate(o):
+                dptr[3 * i + p] = plane.ctypes.data
+        item = np.dtype(dt).itemsize
+        ds = (C.c_int64 * 3)(w * item, cw * item, cw * item)
+        self._check(self.lib.pqa_unpack(self._ctx, C.byref(sp), sptr, arrs[0].strides[0] if arrs else 0, n, dptr, C.byref(ds)))
+        return out
+
+    def unpack_resident(self, fmt, shape, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, n_frames: int, dst_ptrs,
+                        dst_row_pitch, dst_frame_pitch):
+        """The same for frames in HBM (device pointers, pitches in bytes; pqa_unpack_device): n_frames packed frames at
+        src_ptr become the planes at dst_ptrs = (Y, U, V) or (Y,) for luma only.  Nothing crosses PCIe; the planes can go
+        straight into submit_resident or any *_resident analysis."""
+        sp = self._unpack_spec(self._packed_format(fmt), shape)
+        d = N.PqaDeviceClip()
+        for p, ptr in enumerate(dst_ptrs):
+            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptr or None, dst_row_pitch[p], dst_frame_pitch[p]
+        self._check(self.lib.pqa_unpack_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch, int(n_frames),
+                                               C.byref(d)))
+
+    def _host_clip(self, side, keep):
+        """the pqa_host_clip of one side of submit_packed: (frames, format name or None)"""
+        frames, fmt = side
+        h = N.PqaHostClip()
+        h.struct_size = C.sizeof(N.PqaHostClip)
+        if fmt is None or fmt == "planar":
+            h.format = N.SURFACE_PLANAR
+            ptrs = (C.c_void_p * max(len(frames) * self.n_planes, 1))()
+            for f, planes in enumerate(frames):
+                k, pp, ss = self._planes([np.ascontiguousarray(planes[p], dtype=self.dtype) for p in range(self.n_planes)])
+                keep += k
+                for p in range(self.n_planes):
+                    ptrs[f * self.n_planes + p] = pp[p]
+                    h.strides[p] = ss[p]
+        else:
+            h.format = self._packed_format(fmt)
+            arrs = [np.asarray(a) for a in frames]
+            if any(a.ndim != 2 or a.dtype != np.uint8 or a.strides[1] != 1 or a.strides[0] != arrs[0].strides[0] for a in arrs):
+                arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrs]
+            if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
+                raise ValueError("submit_packed needs 2-D arrays of packed rows of one size")
+            keep += arrs
+            ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+            h.strides[0] = arrs[0].strides[0] if arrs else 0
+        keep.append(ptrs)
+        h.frames = C.cast(ptrs, C.POINTER(C.c_void_p))
+        return h
+
+    def submit_packed(self, first_index: int, ref, dis):
+        """Consecutive frame pairs from HOST memory where either side is a packed capture clip (pqa_submit_packed).  Each
+        side is (frames, format): format "uyvy422", "yuyv422" or "v210" with frames = 2-D uint8 arrays of packed rows, or
+        None for planar frames (sequences of Y[,U,V] planes as submit() takes them).  The packed bytes cross PCIe as they
+        are and are unpacked on the GPU; on return the arrays may be reused."""
+        if len(ref[0]) != len(dis[0]):
+            raise ValueError("submit_packed needs as many reference as captured frames")
+        keep = []
+        r, d = self._host_clip(ref, keep), self._host_clip(dis, keep)
+        self._check(self.lib.pqa_submit_packed(self._ctx, int(first_index), len(ref[0]), C.byref(r), C.byref(d)))
+
     def set_luma_gray(self, mode: int):
         """N.GRAY_LUMA: statistics of the luma samples; N.GRAY_BT601_FULL: of the limited -> full range gray the
         reference's cv2 path sees (8-bit units for every bit depth; thresholds in those units)."""

@@ -43,7 +43,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 spectrum_gain_floor: float = 0.5, temporal: int = 0, temporal_planes: str = "y", temporal_min_mse: float = 1.0,
                 temporal_blend_min: float = 1 / 16, temporal_still_mse: float = 0.25,
                 temporal_pop_factor: float = 4, coding_grid: bool = False, grid_planes: str = "y", grid_periods=(4, 64),
-                grid_z2: float = 25.0) -> ScoreResult | None:
+                grid_z2: float = 25.0, chroma_mismatch: str = "error") -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -178,13 +178,31 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     them (`psnr_excluding`).  The luma adds the per-frame metric columns `tile_psnr_min` and `distortion_concentration`.
     With `distortion_dir` rank 0 writes distortion_<plane>.pgm (distortion.heatmap_pgm of the clip-mean tile PSNR) and
     distortion_<plane>.npy (the clip-summed moments, uint64 [ty, tx, 6]) there.  `distortion_map` = 0: nothing is measured and
-    every output is what it was."""
+    every output is what it was.
+    Packed capture files (.uyvy, .yuyv / .yuy2, .v210; yuvio.PackedReader) are 4:2:2 clips like any other to every step above,
+    which read them through a numpy unpack; the scoring loop itself hands a clip that reaches it unwrapped (or only
+    frame-shifted) to the GPU as packed bytes in runs of eight (FeatureEngine.submit_packed: unpacked in HBM, bit-identical
+    records).  `chroma_mismatch`: "error" (default) refuses clips that differ in pixel format; "luma" accepts clips that differ
+    ONLY in chroma subsampling (a 4:2:2 capture against a 4:2:0 master) and scores both as luma-only clips -- VMAF and luma
+    PSNR / SSIM, the chroma keys absent as for a monochrome Y4M; a bit-depth difference stays an error, and chroma is not
+    converted between layouts.  Then, or when a packed file is read, the result carries `input` = {"reference": pix_fmt,
+    "distorted": pix_fmt, "planes_scored": "y" | "yuv", "packed_upload": bool}."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
     dis_rd = open_video(distorted_path, **raw_kwargs)
     ri, di = ref_rd.info, dis_rd.info
+    if chroma_mismatch not in ("error", "luma"):
+        raise ValueError('chroma_mismatch must be "error" or "luma"')
+    input_info = None
+    if ri.packed or di.packed:
+        input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False}
+    if (chroma_mismatch == "luma" and ri.bit_depth == di.bit_depth
+            and (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono)):
+        input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "y", "packed_upload": False}
+        ref_rd, dis_rd = _LumaReader(ref_rd), _LumaReader(dis_rd)
+        ri, di = ref_rd.info, dis_rd.info
     if resize is not None and resize not in N.RESAMPLE_FILTERS:
         raise ValueError(f"resize must be None or one of {sorted(N.RESAMPLE_FILTERS)}")
     if resize is None and (ri.width, ri.height) != (di.width, di.height):
@@ -373,11 +391,24 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         # k + 1 overlaps the upload of frame k inside the library); 8 = a staging half, and the grain of progress / cancel
         by_run = (by_fd and hasattr(eng, "submit_file_run") and all(hasattr(r, "run_stride") for r in (ref_rd, dis_rd))
                   and os.environ.get("PQA_FD_RUN", "1") != "0")   # PQA_FD_RUN=0: frame by frame (A/B partner)
+        # a packed capture file that reaches this loop unwrapped goes down as packed bytes, 8 frames a call (pqa_submit_packed)
+        by_packed = hasattr(eng, "submit_packed") and any(hasattr(r, "packed_frame") for r in (ref_rd, dis_rd))
+        if input_info is not None:
+            input_info["packed_upload"] = bool(by_packed)
+            input_info["planes_scored"] = "y" if n_planes == 1 else "yuv"
         i = a
         while i < b:
             if cancelled is not None and cancelled():
                 eng.cancel()
                 raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
+            if by_packed:
+                m = min(8, b - i)
+                eng.submit_packed(i, *[([r.packed_frame(j) for j in range(i, i + m)], r.info.packed) if hasattr(r, "packed_frame")
+                                       else ([r.frame(j)[:n_planes] for j in range(i, i + m)], None) for r in (ref_rd, dis_rd)])
+                i += m
+                if progress is not None:
+                    progress(i - a, b - a)
+                continue
             m = 1
             if by_run:
                 m = min(8, b - i)
@@ -495,6 +526,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["alignment"] = alignment
     if resized is not None:
         res["resize"] = resized
+    if input_info is not None:
+        res["input"] = input_info
     for rd in (resampler, registered, coloured):   # on an error their contexts go with the readers
         if rd is not None:
             rd.close()
@@ -619,12 +652,32 @@ def _find_geometry(ref_rd, dis_rd, filter: str, n_frames: int, min_px: float, de
     return geo
 
 
+class _LumaReader:
+    """The luma of a clip as a monochrome clip: what score_files reads under chroma_mismatch="luma".  A packed capture file
+    keeps its packed frames on offer: a luma-only context decodes no chroma from them."""
+
+    def __init__(self, reader):
+        import dataclasses
+        self._rd = reader
+        self.info = dataclasses.replace(reader.info, mono=True, hshift=0, vshift=0)
+        if hasattr(reader, "packed_frame"):
+            self.packed_frame = reader.packed_frame
+
+    def __len__(self):
+        return len(self._rd)
+
+    def frame(self, i: int):
+        return self._rd.frame(i)[:1]
+
+
 class _ShiftedReader:
     """A clip from its frame `start` on: what score_files reads once the alignment offset is known."""
 
     def __init__(self, reader, start: int):
         self._rd, self._start = reader, int(start)
         self.info = reader.info
+        if hasattr(reader, "packed_frame"):   # a packed capture file stays one (the scoring loop's submit_packed)
+            self.packed_frame = lambda i: reader.packed_frame(i + self._start)
         for name in ("fileno", "plane_offsets", "run_stride"):   # the file-descriptor submit path, where the reader has it
             if hasattr(reader, name):
                 setattr(self, name, getattr(self, "_" + name))

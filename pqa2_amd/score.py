@@ -186,6 +186,11 @@ def main(argv=None) -> int:
                          "this filter and crop both clips; the JSON's alignment object gets a geometry entry")
     ap.add_argument("--register-frames", type=int, default=8, metavar="N",
                     help="with --register: measure N frame pairs spread evenly over the clips (default 8)")
+    ap.add_argument("--chroma-mismatch", default="error", choices=["error", "luma"],
+                    help="clips that differ only in chroma subsampling (a 4:2:2 capture such as .uyvy / .v210 against a 4:2:0 "
+                         "master): refuse them (default) or score their luma only -- VMAF and luma PSNR / SSIM; the JSON gets a "
+                         "top-level input object.  Headerless packed files (.uyvy, .yuyv, .yuy2, .v210) take their frame size "
+                         "from a _WxH name hint, as raw .yuv does")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the record gather; gloo + --share-device rehearses N ranks on one GPU")
     ap.add_argument("--share-device", action="store_true", help="every rank uses device 0 (rehearsal on a one-GPU box)")
@@ -251,6 +256,7 @@ def main(argv=None) -> int:
                               "grid_periods": (a.grid_min_period, a.grid_max_period), "grid_z2": a.grid_z2}
                              if a.coding_grid else {}),
                           **({"resize": a.resize} if a.resize else {}),
+                          **({"chroma_mismatch": a.chroma_mismatch} if a.chroma_mismatch != "error" else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
@@ -267,6 +273,7 @@ def main(argv=None) -> int:
                                      **report.integrity_log_keys(res.get("integrity")),
                                      **report.alignment_log_keys(res.get("alignment")),
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
+                                     **({"input": res["input"]} if res.get("input") else {}),
                                      **report.distortion_log_keys(res.get("distortion")),
                                      **report.spectrum_log_keys(res.get("spectrum")),
                                      **report.temporal_log_keys(res.get("temporal")),

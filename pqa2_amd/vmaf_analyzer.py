@@ -181,6 +181,8 @@ class VMAFAnalyzer(QObject):
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
                                               # scale and undo them with this filter (pipeline.score_files(register=))
+        self.chroma_mismatch = "error"        # "luma": clips that differ only in chroma subsampling (a 4:2:2 capture against a
+                                              # 4:2:0 master) are scored on their luma (pipeline.score_files(chroma_mismatch=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -483,6 +485,7 @@ class VMAFAnalyzer(QObject):
                                      **report.integrity_log_keys(res.get("integrity")),
                                      **report.alignment_log_keys(res.get("alignment")),
                                      **({"resize": res["resize"]} if res.get("resize") else {}),
+                                     **({"input": res["input"]} if res.get("input") else {}),
                                      **report.distortion_log_keys(res.get("distortion")),
                                      **report.spectrum_log_keys(res.get("spectrum")),
                                      **report.temporal_log_keys(res.get("temporal")),
@@ -529,7 +532,8 @@ class VMAFAnalyzer(QObject):
                 **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
                 **({"coding_grid": True} if self.coding_grid_enabled else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
-                **({"register": self.register_filter} if self.register_filter else {})}
+                **({"register": self.register_filter} if self.register_filter else {}),
+                **({"chroma_mismatch": self.chroma_mismatch} if self.chroma_mismatch != "error" else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -590,6 +594,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
             cmd += ["--register", str(self.register_filter)]
+        if self.chroma_mismatch != "error":
+            cmd += ["--chroma-mismatch", str(self.chroma_mismatch)]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:

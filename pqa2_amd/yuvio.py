@@ -1,4 +1,5 @@
-"""Planar YUV containers the scoring path reads: YUV4MPEG2 (.y4m) and headerless raw (.yuv).
+"""The containers the scoring path reads: YUV4MPEG2 (.y4m), headerless planar raw (.yuv) and headerless packed 4:2:2
+capture files (.uyvy, .yuyv / .yuy2, .v210).
 
 The reference hands file paths to ffmpeg (app/vmaf_analyzer.py:411-419), which demuxes and
 decodes them.  This engine has no decoder of its own; it consumes what a decoder emits --
@@ -38,6 +39,7 @@ class VideoInfo:
     n_frames: int = 0
     chroma_tag: str = "420jpeg"
     color_range: str | None = None   # "limited" / "full" when the container says so (Y4M XCOLORRANGE=...), else None
+    packed: str | None = None        # "uyvy422" / "yuyv422" / "v210" when the file holds packed frames (PackedReader)
 
     @property
     def dtype(self):
@@ -68,6 +70,8 @@ class VideoInfo:
 
     @property
     def pix_fmt(self) -> str:
+        if self.packed:
+            return self.packed
         base = "gray" if self.mono else {(1, 1): "yuv420p", (1, 0): "yuv422p", (0, 0): "yuv444p"}[(self.hshift, self.vshift)]
         if self.bit_depth > 8:
             base += f"{self.bit_depth}le"
@@ -264,6 +268,89 @@ class RawYUVReader:
             yield self.frame(i)
 
 
+PACKED_EXTENSIONS = {".uyvy": "uyvy422", ".yuyv": "yuyv422", ".yuy2": "yuyv422", ".v210": "v210"}
+
+
+def packed_row_bytes(fmt: str, width: int) -> int:
+    """the bytes of a packed row that hold samples: ceil(w / 2) macropixels of 4 bytes; v210: ceil(w / 6) groups of 16"""
+    return 16 * ((width + 5) // 6) if fmt == "v210" else 4 * ((width + 1) // 2)
+
+
+def packed_file_stride(fmt: str, width: int) -> int:
+    """bytes from row to row in a headerless file: v210 pads rows to 48 pixels (128 bytes), as FFmpeg and the cards do"""
+    return ((width + 47) // 48) * 128 if fmt == "v210" else packed_row_bytes(fmt, width)
+
+
+def unpack_packed(fmt: str, rows: np.ndarray, width: int):
+    """[Y, U, V] of packed rows (2-D uint8, a row per line): the numpy statement of the three formats
+    (include/pqa_vmaf.h); Y is h x width, U and V h x ceil(width / 2); uint8, v210: uint16 0 ... 1023."""
+    h, cw = rows.shape[0], (width + 1) // 2
+    if fmt in ("uyvy422", "yuyv422"):
+        m = rows[:, :4 * cw].reshape(h, cw, 4)
+        yo, uo = (1, 0) if fmt == "uyvy422" else (0, 1)
+        y = np.stack([m[:, :, yo], m[:, :, yo + 2]], axis=2).reshape(h, 2 * cw)[:, :width]
+        return [np.ascontiguousarray(y), np.ascontiguousarray(m[:, :, uo]), np.ascontiguousarray(m[:, :, uo + 2])]
+    if fmt != "v210":
+        raise ValueError(f"unknown packed format {fmt!r}")
+    g = (width + 5) // 6
+    wd = np.ascontiguousarray(rows[:, :16 * g]).view("<u4").reshape(h, g, 4)
+    lo, mid, hi = (wd & 1023).astype(np.uint16), ((wd >> 10) & 1023).astype(np.uint16), ((wd >> 20) & 1023).astype(np.uint16)
+    # w0 = U0 Y0 V0, w1 = Y1 U1 Y2, w2 = V1 Y3 U2, w3 = Y4 V2 Y5
+    y = np.stack([mid[:, :, 0], lo[:, :, 1], hi[:, :, 1], mid[:, :, 2], lo[:, :, 3], hi[:, :, 3]], axis=2).reshape(h, 6 * g)
+    u = np.stack([lo[:, :, 0], mid[:, :, 1], hi[:, :, 2]], axis=2).reshape(h, 3 * g)
+    v = np.stack([hi[:, :, 0], lo[:, :, 2], mid[:, :, 3]], axis=2).reshape(h, 3 * g)
+    return [np.ascontiguousarray(y[:, :width]), np.ascontiguousarray(u[:, :cw]), np.ascontiguousarray(v[:, :cw])]
+
+
+class PackedReader:
+    """Headerless packed 4:2:2 capture files: .uyvy, .yuyv / .yuy2 (8 bit) and .v210 (10 bit; rows padded to 128 bytes per 48
+    pixels).  Geometry from arguments or a `_WxH` name hint, as RawYUVReader; the frame count from the file size.
+    frame(i) gives planar [Y, U, V] through a numpy unpack (what the alignment steps, the side analyses and every wrapper
+    reader read); packed_frame(i) the packed rows as they lie in the file, which the scoring loop hands to the GPU as they
+    are (FeatureEngine.submit_packed)."""
+
+    def __init__(self, path: str, width: int | None = None, height: int | None = None, bit_depth: int | None = None,
+                 fps: int = 30, fmt: str | None = None):
+        fmt = fmt or PACKED_EXTENSIONS.get(os.path.splitext(path)[1].lower())
+        if fmt not in ("uyvy422", "yuyv422", "v210"):
+            raise ValueError(f"not a packed capture file (.uyvy, .yuyv, .yuy2, .v210): {path}")
+        m = re.search(r"(\d{2,5})x(\d{2,5})", os.path.basename(path))
+        if (width is None or height is None) and not m:
+            raise ValueError(f"a packed capture file needs a geometry (WxH in the file name or arguments): {path}")
+        width = width or int(m.group(1))
+        height = height or int(m.group(2))
+        depth = 10 if fmt == "v210" else 8
+        if bit_depth is not None and bit_depth != depth:
+            raise ValueError(f"{fmt} is {depth} bit, not {bit_depth}")
+        self.path, self.format = path, fmt
+        self.info = VideoInfo(width, height, depth, 1, 0, False, fps, 1, chroma_tag="422" if depth == 8 else "422p10", packed=fmt)
+        self.row_stride = packed_file_stride(fmt, width)
+        self.packed_frame_bytes = self.row_stride * height
+        size = os.path.getsize(path)
+        if size == 0 or size % self.packed_frame_bytes:
+            raise ValueError(f"{path}: {size} bytes is not a whole number of {fmt} frames of {width}x{height} "
+                             f"({self.packed_frame_bytes} bytes each, rows {self.row_stride} bytes apart)")
+        self._mm = np.memmap(path, dtype=np.uint8, mode="r")
+        self.info.n_frames = size // self.packed_frame_bytes
+
+    def __len__(self):
+        return self.info.n_frames
+
+    def packed_frame(self, i: int) -> np.ndarray:
+        """the packed rows of frame i, (height, row_stride) uint8, viewing the mapped file"""
+        if not 0 <= i < self.info.n_frames:
+            raise IndexError(i)
+        off = i * self.packed_frame_bytes
+        return self._mm[off:off + self.packed_frame_bytes].reshape(self.info.height, self.row_stride)
+
+    def frame(self, i: int):
+        return unpack_packed(self.format, self.packed_frame(i), self.info.width)
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self.frame(i)
+
+
 def write_y4m(path: str, frames, info: VideoInfo) -> None:
     """frames: iterable of [Y,U,V] plane lists matching `info`."""
     with open(path, "wb") as f:
@@ -276,12 +363,14 @@ def write_y4m(path: str, frames, info: VideoInfo) -> None:
 
 
 def open_video(path: str, **raw_kwargs):
-    """Reader for .y4m / .yuv; anything else is decoded by a system ffmpeg into a temp Y4M."""
+    """Reader for .y4m / .yuv / packed capture files (.uyvy, .yuyv, .yuy2, .v210); anything else is decoded by a system ffmpeg into a temp Y4M."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".y4m":
         return Y4MReader(path)
     if ext == ".yuv":
         return RawYUVReader(path, **raw_kwargs)
+    if ext in PACKED_EXTENSIONS:
+        return PackedReader(path, **raw_kwargs)
     with open(path, "rb") as f:
         if f.read(9) == b"YUV4MPEG2":
             return Y4MReader(path)
