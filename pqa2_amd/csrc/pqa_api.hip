@@ -133,6 +133,446 @@ int wait_batch(pqa_ctx* c, uint64_t seq) {
 }
 
 // ---- the batch: every kernel for n consecutive device-resident frames -------------------------
+struct RunPair { PlaneRun ref, dis; };
+struct MutRunPair { MutPlaneRun ref{nullptr, 0, 0}, dis{nullptr, 0, 0}; };
+struct Pred { const void* base = nullptr; int64_t pitch = 0; };   // a plane in front of the batch, pitch in elements; null: none
+
+PlaneRun clip_run(const pqa_device_clip* clip, int p, int es) {
+  return PlaneRun{clip->plane[p], clip->row_pitch[p] / es, clip->frame_pitch[p] / es};
+}
+PlaneRun run_at(PlaneRun r, int64_t elems, int es) {   // r from `elems` samples further on
+  return PlaneRun{(const uint8_t*)r.base + elems * es, r.row_pitch, r.frame_pitch};
+}
+PlaneRun frames_from(PlaneRun r, int64_t f, int es) { return run_at(r, f * r.frame_pitch, es); }   // the run starting at frame f
+RunPair level_in(const Level& L) { return RunPair{{L.ref, L.pitch, L.frame_pitch}, {L.dis, L.pitch, L.frame_pitch}}; }
+MutRunPair level_out(const Level& L) { return MutRunPair{{L.ref, L.pitch, L.frame_pitch}, {L.dis, L.pitch, L.frame_pitch}}; }
+
+// One batch as its steps see it: computed once by process_batch.  The counts below the streams are what the chains wrote, for
+// the finalize kernel.
+struct Batch {
+  int64_t first;
+  int n, e0, sp_n, k;        // sp_n frames, e0 + i * k, get spatial features (libvmaf n_subsample: index % k == 0)
+  int es, w, h, capacity;
+  PlaneRun r[3]{}, d[3]{};   // every frame of the reference / the distorted clip, per plane
+  PlaneRun rs[3]{}, ds[3]{}; // the frames that get spatial features
+  const pqa_device_clip *ref, *dis;
+  Pred prev;                 // the caller's reference luma first-1
+  hipStream_t st, st_adm, st_misc;
+  bool multi, fork_late;
+  int vif_np[4], adm_np[4], motion_np;   // partials written per frame
+  int n_sse = 0, n_ssim = 0;
+  bool sse_a[3] = {false, false, false}, sse_b[3] = {false, false, false}, sse_t[3] = {false, false, false};
+  int slot(int64_t f) const { return (int)((first + f) % capacity); }   // the ring slot of frame f of the batch
+};
+
+// fork: the ADM chain and the motion/PSNR/SSIM kernels are independent of the VIF chain; on their own
+// streams they fill the SIMD time the VALU-bound VIF kernels leave while waiting, and the small deep-scale
+// grids overlap instead of running one after another
+int fork_streams(pqa_ctx* c, const Batch& b) {
+  HIPCHK(c, hipEventRecord(c->fork_ev, b.st));
+  HIPCHK(c, hipStreamWaitEvent(b.st_adm, c->fork_ev, 0));
+  HIPCHK(c, hipStreamWaitEvent(b.st_misc, c->fork_ev, 0));
+  return PQA_OK;
+}
+
+int join_streams(pqa_ctx* c, const Batch& b) {
+  HIPCHK(c, hipEventRecord(c->join_ev[0], b.st_adm));
+  HIPCHK(c, hipEventRecord(c->join_ev[1], b.st_misc));
+  HIPCHK(c, hipStreamWaitEvent(b.st, c->join_ev[0], 0));
+  HIPCHK(c, hipStreamWaitEvent(b.st, c->join_ev[1], 0));
+  return PQA_OK;
+}
+
+// One scale of a pyramid walk: reads `in` (w x h, elements `elem`), writes `out` (the next level; null at the last scale).
+struct Scale { int s; Elem elem; RunPair in; int w, h; MutRunPair out; };
+
+// One walk down a four-level pyramid: launch(k) queues scale k.s.  `first` is the scale the walk starts at, on the caller's
+// planes (scale 0) or on those of lv[first.s]; the levels below hold elements `deep`.
+template <typename Launch>
+int walk_pyramid(const Level (&lv)[4], Scale first, Elem deep, Launch launch) {
+  for (Scale k = first; k.s < 4; ++k.s) {
+    k.out = k.s < 3 ? level_out(lv[k.s + 1]) : MutRunPair{};
+    const int rc = launch(k);
+    if (rc != PQA_OK) return rc;
+    if (k.s < 3) {
+      const Level& L = lv[k.s + 1];
+      k.in = level_in(L);
+      k.elem = deep;
+      k.w = L.w; k.h = L.h;
+    }
+  }
+  return PQA_OK;
+}
+
+int run_vif(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_VIF) || b.sp_n == 0) return PQA_OK;
+  const Scale top{0, c->elem, RunPair{b.rs[0], b.ds[0]}, b.w, b.h, {}};
+  if (c->vif_fixed)   // the pyramid buffers hold u16 planes in this mode (same element pitches, half the bytes)
+    return walk_pyramid(c->vif_lv, top, ELEM_U16, [&](const Scale& k) -> int {
+      ProfScope ps(c, k.s, b.sp_n, b.st);
+      HIPCHK(c, launch_vif_fixed(b.st, k.s, (int)c->cfg.bit_depth, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h,
+                                 c->cfg.vif_enhn_gain_limit, c->vif_lut, c->vif_fx_part[k.s], k.out.ref, k.out.dis));
+      return PQA_OK;
+    });
+  return walk_pyramid(c->vif_lv, top, ELEM_F32, [&](const Scale& k) -> int {
+    {
+      ProfScope ps(c, k.s, b.sp_n, b.st);
+      HIPCHK(c, launch_vif_stat(b.st, k.s, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h, c->inv_scale,
+                                (float)c->cfg.vif_enhn_gain_limit, c->cfg.vif_border == PQA_VIF_BORDER_INTEGER, c->vif_part[k.s],
+                                k.out.ref, k.out.dis, c->vif_s0_mode, &b.vif_np[k.s], c->vif_uniform));
+    }
+    // mode 2: the other chains start behind VIF scale 0 (the dominant launch runs alone, its figures stay its own) and
+    // overlap VIF scales 1-3 only
+    return k.s == 0 && b.fork_late ? fork_streams(c, b) : PQA_OK;
+  });
+}
+
+int run_adm(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_ADM) || b.sp_n == 0) return PQA_OK;
+  Scale top{0, c->elem, RunPair{b.rs[0], b.ds[0]}, b.w, b.h, {}};
+  if (c->adm_fixed)   // the approximation-band buffers hold int32 planes in this mode (same 4-byte elements)
+    return walk_pyramid(c->adm_lv, top, ELEM_F32, [&](const Scale& k) -> int {
+      ProfScope ps(c, 7 + k.s, b.sp_n, b.st_adm);
+      HIPCHK(c, launch_adm_fixed(b.st_adm, k.s, (int)c->cfg.bit_depth, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h,
+                                 c->cfg.adm_enhn_gain_limit, c->adm_div_lut, k.out.ref, k.out.dis, c->adm_fx_part[k.s]));
+      return PQA_OK;
+    });
+  if (c->adm_mode == ADM_AUTO) {   // scales 0 and 1 in one launch when the geometry allows (adm_pyramid.hip)
+    const Level& L2 = c->adm_lv[2];
+    hipError_t perr = hipSuccess;
+    int np = 0;
+    ProfScope ps(c, 7, b.sp_n, b.st_adm);
+    if (launch_adm_pyramid(b.st_adm, top.elem, top.in.ref, top.in.dis, b.sp_n, top.w, top.h, c->inv_scale,
+                           (float)c->cfg.adm_enhn_gain_limit, level_out(L2).ref, level_out(L2).dis, c->adm_part[0], c->adm_part[1],
+                           &np, &perr)) {
+      HIPCHK(c, perr);
+      b.adm_np[0] = b.adm_np[1] = np;
+      top = Scale{2, ELEM_F32, level_in(L2), L2.w, L2.h, {}};
+    }
+  }
+  return walk_pyramid(c->adm_lv, top, ELEM_F32, [&](const Scale& k) -> int {
+    ProfScope ps(c, 7 + k.s, b.sp_n, b.st_adm);
+    HIPCHK(c, launch_adm_scale(b.st_adm, k.s, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h, c->inv_scale,
+                               (float)c->cfg.adm_enhn_gain_limit, k.out.ref, k.out.dis, c->adm_part[k.s], c->adm_mode, &b.adm_np[k.s]));
+    return PQA_OK;
+  });
+}
+
+// Frame `frame` as a chain holds it (planes[slot]), or none.
+Pred held(const host::FrameChain& chain, const HistPlane* planes, int64_t frame, int es) {
+  const int j = chain.find(frame);
+  return j < 0 ? Pred{} : Pred{planes[j].base, planes[j].pitch / es};
+}
+
+int run_motion(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_MOTION)) return PQA_OK;
+  // reference luma in front of the batch: the caller's halo, the armed halo, or the last frame of the previous batch
+  const Pred p0 = b.prev.base ? b.prev : held(c->mo_chain, &c->mo_hist, b.first - 1, b.es);
+  ProfScope ps(c, 11, b.n, b.st_misc);
+  if (c->motion_fixed)
+    HIPCHK(c, launch_motion_fixed(b.st_misc, (int)c->cfg.bit_depth, c->elem, b.r[0], p0.base, p0.pitch, b.n, b.w, b.h,
+                                  c->motion_fx_part));
+  else
+    HIPCHK(c, launch_motion(b.st_misc, c->elem, b.r[0], p0.base, p0.pitch, b.n, b.w, b.h, c->inv_scale, c->motion_part,
+                            c->motion_mode, &b.motion_np));
+  return PQA_OK;
+}
+
+int run_psnr_ssim(pqa_ctx* c, Batch& b) {
+  const uint32_t feat = c->cfg.features;
+  const int es = b.es;
+  const bool both = (feat & PQA_FEAT_PSNR) && (feat & PQA_FEAT_SSIM);
+  if (feat & PQA_FEAT_PSNR) {
+    b.n_sse = c->n_planes;
+    ProfScope ps(c, 12, b.n, b.st_misc);
+    for (int p = 0; p < c->n_planes; ++p) {
+      const PlaneRun a = b.d[p], r = b.r[p];
+      const int pw = c->pw[p], ph = c->ph[p];
+      if (both && c->ssim_tiles_n[p] > 0) {
+        // the SSIM kernel delivers the squared error of the 4-aligned part; only remainder strips are left
+        b.sse_t[p] = true;
+        const int w4 = (pw >> 2) << 2, h4 = (ph >> 2) << 2;
+        if (w4 < pw) {
+          HIPCHK(c, launch_sse(b.st_misc, c->elem, run_at(a, w4, es), run_at(r, w4, es), b.n, pw - w4, ph, c->sse_part[p]));
+          b.sse_a[p] = true;
+        }
+        if (h4 < ph) {
+          HIPCHK(c, launch_sse(b.st_misc, c->elem, run_at(a, h4 * a.row_pitch, es), run_at(r, h4 * r.row_pitch, es), b.n, w4,
+                               ph - h4, c->sse_part_b[p]));
+          b.sse_b[p] = true;
+        }
+      } else {
+        HIPCHK(c, launch_sse(b.st_misc, c->elem, a, r, b.n, pw, ph, c->sse_part[p]));
+        b.sse_a[p] = true;
+      }
+    }
+  }
+  if (feat & PQA_FEAT_SSIM) {
+    b.n_ssim = c->n_planes;
+    ProfScope ps(c, 13, b.n, b.st_misc);
+    for (int p = 0; p < c->n_planes; ++p)
+      HIPCHK(c, launch_ssim(b.st_misc, c->elem, b.d[p], b.r[p], b.n, c->pw[p], c->ph[p], (1 << c->cfg.bit_depth) - 1,
+                            c->ssim_part[p], b.sse_t[p] ? c->sse_tile_part[p] : nullptr));
+  }
+  return PQA_OK;
+}
+
+// Extension features run on the frames that get spatial features; the extension rows of the other frames are NaN.
+int fill_ext_nan(pqa_ctx* c, Batch& b) {
+  if (b.k > 1 && (c->cfg.features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)))
+    HIPCHK(c, launch_ext_fill_nan(b.st_misc, c->ext, b.slot(0), b.n, c->capacity, PQA_EXT_DOUBLES));
+  return PQA_OK;
+}
+
+// The SSIM family, ssf_sb frames at a time (the MS-SSIM pyramid is sized for that many).
+int run_ssim_family(pqa_ctx* c, Batch& b) {
+  const bool fs = c->cfg.features & PQA_FEAT_FLOAT_SSIM, ms = c->cfg.features & PQA_FEAT_MS_SSIM;
+  if (!fs && !ms) return PQA_OK;
+  const hipStream_t st = b.st_misc;
+  for (int s0 = 0; s0 < b.sp_n; s0 += c->ssf_sb) {
+    const int m = b.sp_n - s0 < c->ssf_sb ? b.sp_n - s0 : c->ssf_sb;
+    const PlaneRun r0 = frames_from(b.rs[0], s0, b.es), d0 = frames_from(b.ds[0], s0, b.es);
+    SsfFinalizeArgs sa{};
+    sa.n_frames = m;
+    sa.ext = c->ext;
+    sa.ext_stride = PQA_EXT_DOUBLES;
+    sa.slot_base = b.slot(b.e0 + (int64_t)s0 * b.k);
+    sa.slot_step = b.k;
+    sa.capacity = c->capacity;
+    if (fs) {
+      sa.fs_part = c->fs_part; sa.fs_tiles = c->fs_tiles;
+      const int dw = (b.w + c->fs_box - 1) / c->fs_box, dh = (b.h + c->fs_box - 1) / c->fs_box;
+      sa.fs_norm = 1.0 / ((double)(dw - 10) * (dh - 10));
+      ProfScope ps(c, 16, m, st);
+      HIPCHK(c, launch_ssf_map(st, c->elem, r0, d0, m, b.w, b.h, c->fs_box, c->inv_scale, c->fs_part));
+      if (!ms) HIPCHK(c, launch_ssf_finalize(st, sa));
+    }
+    if (ms) {
+      ProfScope ps(c, 15, m, st);
+      RunPair cur{r0, d0};
+      Elem ce = c->elem;
+      for (int j = 0; j < kMsScales; ++j) {
+        const Level& L = c->ms_lv[j];
+        sa.ms_part[j] = c->ms_part[j]; sa.ms_tiles[j] = c->ms_tiles[j];
+        sa.ms_norm[j] = 1.0 / ((double)(L.w - 10) * (L.h - 10));
+        if (j == 0) {   // scale 0 writes scale 1's planes in the same launch (the caller's pair is read once)
+          const MutRunPair N = level_out(c->ms_lv[1]);
+          HIPCHK(c, launch_ssf_map(st, ce, cur.ref, cur.dis, m, L.w, L.h, 1, c->inv_scale, c->ms_part[0], N.ref, N.dis));
+        } else {
+          HIPCHK(c, launch_ssf_map(st, ce, cur.ref, cur.dis, m, L.w, L.h, 1, c->inv_scale, c->ms_part[j]));
+        }
+        if (j + 1 < kMsScales) {
+          const MutRunPair N = level_out(c->ms_lv[j + 1]);
+          if (j > 0) HIPCHK(c, launch_ssf_down(st, ce, cur.ref, cur.dis, m, L.w, L.h, c->inv_scale, N.ref, N.dis));
+          cur = level_in(c->ms_lv[j + 1]);
+          ce = ELEM_F32;
+        }
+      }
+      HIPCHK(c, launch_ssf_finalize(st, sa));
+    }
+  }
+  return PQA_OK;
+}
+
+// CIEDE2000 on Y, U, V of the frames that get spatial features; the epilogue writes slots 20 / 21 of their rows only.
+int run_ciede(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_CIEDE) || b.sp_n == 0) return PQA_OK;
+  CiedeFinalizeArgs ca{};
+  ca.n_frames = b.sp_n;
+  ca.ext = c->ext;
+  ca.ext_stride = PQA_EXT_DOUBLES;
+  ca.slot_base = b.slot(b.e0);
+  ca.slot_step = b.k;
+  ca.capacity = c->capacity;
+  ca.partials = c->ciede_part;
+  ca.n_tiles = c->ciede_tiles_n;
+  ca.norm = 1.0 / ((double)b.w * b.h);
+  ProfScope ps(c, 4, b.sp_n, b.st_misc);
+  HIPCHK(c, launch_ciede(b.st_misc, c->elem, b.rs, b.ds, b.sp_n, b.w, b.h, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift,
+                         (int)c->cfg.bit_depth, c->ciede_part));
+  HIPCHK(c, launch_ciede_finalize(b.st_misc, ca));
+  return PQA_OK;
+}
+
+// CAMBI of the distorted (and, FULL_REF, the reference) luma, cambi_sb frames at a time; slots 22 / 23 of their rows.
+int run_cambi(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_CAMBI)) return PQA_OK;
+  for (int s0 = 0; s0 < b.sp_n; s0 += c->cambi_sb) {
+    const int m = b.sp_n - s0 < c->cambi_sb ? b.sp_n - s0 : c->cambi_sb;
+    const int slot_base = b.slot(b.e0 + (int64_t)s0 * b.k);
+    HIPCHK(c, launch_cambi(b.st_misc, c->elem, frames_from(b.ds[0], s0, b.es), m, b.w, b.h, (int)c->cfg.bit_depth, c->cambi_prm,
+                           c->cambi_wk, c->ext, PQA_EXT_DOUBLES, PQA_EXT_CAMBI, slot_base, b.k, c->capacity));
+    if (c->cfg.features & PQA_FEAT_CAMBI_FULL_REF)
+      HIPCHK(c, launch_cambi(b.st_misc, c->elem, frames_from(b.rs[0], s0, b.es), m, b.w, b.h, (int)c->cfg.bit_depth, c->cambi_prm,
+                             c->cambi_wk, c->ext, PQA_EXT_DOUBLES, PQA_EXT_CAMBI_SOURCE, slot_base, b.k, c->capacity));
+  }
+  return PQA_OK;
+}
+
+// PSNR-HVS on Y, Cb, Cr of the frames that get spatial features, into slots 0..6 of their ext2 rows.
+int run_psnr_hvs(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_PSNR_HVS)) return PQA_OK;
+  if (b.k > 1) HIPCHK(c, launch_ext_fill_nan(b.st_misc, c->ext2, b.slot(0), b.n, c->capacity, PQA_EXT2_DOUBLES));
+  if (b.sp_n == 0) return PQA_OK;
+  PsnrHvsFinalizeArgs pa{};
+  pa.n_frames = b.sp_n;
+  pa.ext2 = c->ext2;
+  pa.ext_stride = PQA_EXT2_DOUBLES;
+  pa.slot_base = b.slot(b.e0);
+  pa.slot_step = b.k;
+  pa.capacity = c->capacity;
+  pa.partials = c->phv_part;
+  for (int p = 0; p < 4; ++p) pa.tile0[p] = c->phv_geo.tile0[p];
+  for (int p = 0; p < 3; ++p) pa.blocks[p] = c->phv_geo.nbx[p] * c->phv_geo.nby[p];
+  pa.peak = (double)((1 << c->cfg.bit_depth) - 1);
+  HIPCHK(c, launch_psnr_hvs(b.st_misc, c->elem, b.rs, b.ds, b.sp_n, c->phv_geo, c->phv_part));
+  HIPCHK(c, launch_psnr_hvs_finalize(b.st_misc, pa));
+  return PQA_OK;
+}
+
+// XPSNR on every frame: its predecessors come from the batch, the caller's halo, the kept pair or the armed history.
+int run_xpsnr(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_XPSNR)) return PQA_OK;
+  const Pred h1 = b.prev.base ? b.prev : held(c->xp_chain, c->xp_hist, b.first - 1, b.es);
+  const Pred h2 = held(c->xp_chain, c->xp_hist, b.first - 2, b.es);
+  XpFinalizeArgs xa{};
+  xa.n_frames = b.n;
+  xa.blk = c->xp_blk;
+  xa.wbuf = c->xp_w;
+  xa.ext3 = c->ext3;
+  xa.ext_stride = PQA_EXT3_DOUBLES;
+  xa.slot_base = b.slot(0);
+  xa.capacity = c->capacity;
+  xa.g = c->xp_geo;
+  HIPCHK(c, launch_xpsnr_blocks(b.st_misc, c->elem, b.r, b.d, b.n, h1.base, h1.pitch, h2.base, h2.pitch,
+                                (c->cfg.features & PQA_FEAT_XPSNR_HFR) != 0, c->xp_geo, c->xp_blk));
+  HIPCHK(c, launch_xpsnr_finalize(b.st_misc, xa));
+  return PQA_OK;
+}
+
+// SI / TI of both clips on every frame; frame first-1 of each clip: the caller's halo (reference), the kept or the armed
+// plane; none at a chain start.
+int run_siti(pqa_ctx* c, Batch& b) {
+  const uint32_t feat = c->cfg.features;
+  if (!(feat & PQA_FEAT_SITI)) return PQA_OK;
+  const Pred p[2] = {held(c->st_chain[0], &c->st_hist[0], b.first - 1, b.es),
+                     b.prev.base ? b.prev : held(c->st_chain[1], &c->st_hist[1], b.first - 1, b.es)};
+  const void* sp0[2] = {p[0].base, p[1].base};
+  const int64_t spp[2] = {p[0].pitch, p[1].pitch};
+  const PlaneRun sc[2] = {b.d[0], b.r[0]};
+  const bool sfull[2] = {(feat & PQA_FEAT_SITI_DIS_FULL) != 0, (feat & PQA_FEAT_SITI_REF_FULL) != 0};
+  HIPCHK(c, launch_siti(b.st_misc, c->elem, sc, sp0, spp, sfull, 2, b.n, b.w, b.h, c->st_part, c->ext4, PQA_EXT4_DOUBLES, b.slot(0),
+                        c->capacity, nullptr));
+  return PQA_OK;
+}
+
+// SAD of every plane of the distorted frames against their predecessors, and the black count; frame first-1: the kept or the
+// armed planes, none at a chain start.
+int run_integrity(pqa_ctx* c, Batch& b) {
+  if (!(c->cfg.features & PQA_FEAT_INTEGRITY)) return PQA_OK;
+  const bool have = c->ig_chain.find(b.first - 1) == 0;
+  const void* ip0[3] = {nullptr, nullptr, nullptr};
+  int64_t ipp[3] = {0, 0, 0};
+  for (int p = 0; have && p < c->n_planes; ++p) {
+    ip0[p] = c->ig_hist[p].base;
+    ipp[p] = c->ig_hist[p].pitch / b.es;
+  }
+  HIPCHK(c, launch_integrity(b.st_misc, c->elem, b.d, ip0, ipp, c->pw, c->ph, c->n_planes, b.n, false, c->black_thr, c->ig_part,
+                             c->ext5, PQA_EXT5_DOUBLES, b.slot(0), c->capacity, nullptr));
+  return PQA_OK;
+}
+
+int run_finalize(pqa_ctx* c, Batch& b) {
+  const uint32_t feat = c->cfg.features;
+  FinalizeArgs fa{};
+  for (int s = 0; s < 4; ++s) {
+    fa.vif_part[s] = c->vif_part[s]; fa.vif_tiles[s] = c->vif_fixed ? c->vif_tiles[s] : b.vif_np[s];
+    fa.vif_fx_part[s] = c->vif_fixed ? c->vif_fx_part[s] : nullptr;
+    fa.adm_part[s] = c->adm_part[s]; fa.adm_tiles[s] = c->adm_fixed ? c->adm_tiles[s] : b.adm_np[s]; fa.adm_area[s] = c->adm_area[s];
+    fa.adm_fx_part[s] = c->adm_fixed ? c->adm_fx_part[s] : nullptr;
+    fa.adm_fx_tiles_x[s] = adm_tiles_x(c->adm_fx[s].band_w);
+    fa.adm_fx_top[s] = c->adm_fx[s].top; fa.adm_fx_bottom[s] = c->adm_fx[s].bottom;
+    fa.adm_fx_num_shift[s] = c->adm_fx[s].num_row_shift; fa.adm_fx_den_shift[s] = c->adm_fx[s].den_row_shift;
+  }
+  fa.motion_part = c->motion_part;
+  fa.motion_tiles = c->motion_fixed ? c->motion_tiles_n : b.motion_np;
+  fa.motion_norm = (double)c->inv_scale / ((double)b.w * b.h);
+  fa.motion_fx_part = c->motion_fixed ? c->motion_fx_part : nullptr;
+  fa.motion_wh = (unsigned)b.w * (unsigned)b.h;
+  for (int p = 0; p < 3; ++p) {
+    fa.sse_part[p] = c->sse_part[p];
+    fa.sse_use_a[p] = b.sse_a[p] ? 1 : 0;
+    fa.sse_part_b[p] = b.sse_b[p] ? c->sse_part_b[p] : nullptr;
+    fa.sse_tile_part[p] = b.sse_t[p] ? c->sse_tile_part[p] : nullptr;
+    fa.ssim_part[p] = c->ssim_part[p]; fa.ssim_tiles[p] = c->ssim_tiles_n[p]; fa.ssim_norm[p] = c->ssim_norm[p];
+  }
+  fa.adm_fx_acc = c->adm_fx_acc;
+  fa.records = c->records;
+  fa.record_stride = PQA_RECORD_DOUBLES;
+  fa.capacity = c->capacity;
+  // one launch over `frames` rows from slot_base on, every step-th, for the features of `on`
+  const auto finalize_rows = [&](int frames, int slot_base, int step, uint32_t on) {
+    fa.n_frames = frames;
+    fa.slot_base = slot_base; fa.slot_step = step;
+    fa.has_vif = !!(on & PQA_FEAT_VIF); fa.has_adm = !!(on & PQA_FEAT_ADM); fa.has_motion = !!(on & PQA_FEAT_MOTION);
+    fa.n_sse_planes = (on & PQA_FEAT_PSNR) ? b.n_sse : 0; fa.n_ssim_planes = (on & PQA_FEAT_SSIM) ? b.n_ssim : 0;
+    return launch_finalize(b.st, fa);
+  };
+  const uint32_t spatial = PQA_FEAT_VIF | PQA_FEAT_ADM;
+  ProfScope ps(c, 14, b.n, b.st);
+  if (b.k > 1) {   // the spatial features on their frames, the others on every frame
+    if (b.sp_n > 0 && (feat & spatial)) HIPCHK(c, finalize_rows(b.sp_n, b.slot(b.e0), b.k, feat & spatial));
+    HIPCHK(c, finalize_rows(b.n, b.slot(0), 1, feat & ~spatial));
+  } else {
+    HIPCHK(c, finalize_rows(b.n, b.slot(0), 1, feat));
+  }
+  return PQA_OK;
+}
+
+// A history plane for plane p of a clip, rows padded to 64 bytes.
+int hist_alloc(pqa_ctx* c, HistPlane* hp, int p) {
+  hp->pitch = round_up((int64_t)c->pw[p] * c->esize, 64);
+  return dev_alloc(c, &hp->base, (size_t)hp->pitch * c->ph[p]);
+}
+
+// The caller's host plane p (rows `stride` bytes apart) into a history plane, before it is armed; the stream is idle.
+hipError_t hist_arm(pqa_ctx* c, const HistPlane& dst, const void* src, int64_t stride, int p) {
+  return hipMemcpy2D(dst.base, dst.pitch, src, stride, (size_t)c->pw[p] * c->esize, c->ph[p], hipMemcpyHostToDevice);
+}
+
+// A keep copy: plane p of a device frame (pitch in bytes) into a history plane, on the main stream.
+hipError_t hist_keep(pqa_ctx* c, const HistPlane& dst, const void* src, int64_t src_pitch, int p) {
+  return hipMemcpy2DAsync(dst.base, dst.pitch, src, src_pitch, (size_t)c->pw[p] * c->esize, c->ph[p], hipMemcpyDeviceToDevice,
+                          c->stream);
+}
+
+// What a chain's end() asks for: frames of the first np planes of `clip`, or the caller's prev plane, into planes[slot][np].
+int keep_chain(pqa_ctx* c, const Batch& b, host::FrameChain& chain, const HistPlane* planes, const pqa_device_clip* clip,
+               int np) {
+  host::FrameChain::Copy cp[host::FrameChain::kMaxDepth];
+  const int m = chain.end(b.first, b.n, b.prev.base != nullptr, cp);
+  for (int i = 0; i < m; ++i)
+    for (int p = 0; p < np; ++p) {
+      const bool from_prev = cp[i].src == host::FrameChain::kFromPrev;
+      const void* src = from_prev ? b.prev.base : (const uint8_t*)clip->plane[p] + (int64_t)cp[i].src * clip->frame_pitch[p];
+      HIPCHK(c, hist_keep(c, planes[cp[i].slot * np + p], src, from_prev ? b.prev.pitch * b.es : clip->row_pitch[p], p));
+    }
+  return PQA_OK;
+}
+
+// The last frames of this batch, kept so that the next one continues the chains (behind the join: this batch's kernels have
+// read the old planes; behind the batch event: pqa_collect does not wait for these copies).
+int keep_histories(pqa_ctx* c, const Batch& b) {
+  const uint32_t feat = c->cfg.features;
+  int rc = PQA_OK;
+  if (feat & PQA_FEAT_MOTION) rc = keep_chain(c, b, c->mo_chain, &c->mo_hist, b.ref, 1);
+  if (rc == PQA_OK && (feat & PQA_FEAT_XPSNR)) rc = keep_chain(c, b, c->xp_chain, c->xp_hist, b.ref, 1);
+  if (rc == PQA_OK && (feat & PQA_FEAT_SITI)) rc = keep_chain(c, b, c->st_chain[0], &c->st_hist[0], b.dis, 1);
+  if (rc == PQA_OK && (feat & PQA_FEAT_SITI)) rc = keep_chain(c, b, c->st_chain[1], &c->st_hist[1], b.ref, 1);
+  if (rc == PQA_OK && (feat & PQA_FEAT_INTEGRITY)) rc = keep_chain(c, b, c->ig_chain, c->ig_hist, b.dis, c->n_planes);
+  return rc;
+}
+
 int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, const pqa_device_clip* dis,
                   const void* prev, int64_t prev_pitch_bytes) {
   const uint32_t feat = c->cfg.features;
@@ -142,558 +582,57 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
       return fail(c, PQA_EINVAL, "plane %d pitch is not a multiple of the sample size", p);
     if (!ref->plane[p] || !dis->plane[p]) return fail(c, PQA_EINVAL, "plane %d pointer is null", p);
   }
-  {
-    const int rc = check_slots_free(c, first, n);
-    if (rc != PQA_OK) return rc;
-  }
+  int rc = check_slots_free(c, first, n);
+  if (rc != PQA_OK) return rc;
   c->started = true;
-  const PlaneRun rY{ref->plane[0], ref->row_pitch[0] / es, ref->frame_pitch[0] / es};
-  const PlaneRun dY{dis->plane[0], dis->row_pitch[0] / es, dis->frame_pitch[0] / es};
-  const int w = c->pw[0], h = c->ph[0];
-  hipStream_t st = c->stream;
-  // fork: the ADM chain and the motion/PSNR/SSIM kernels are independent of the VIF chain; on their own
-  // streams they fill the SIMD time the VALU-bound VIF kernels leave while waiting, and the small deep-scale
-  // grids overlap instead of running one after another
+  if (prev && prev_pitch_bytes % es && (feat & (PQA_FEAT_MOTION | PQA_FEAT_XPSNR | PQA_FEAT_SITI)))
+    return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
+
+  Batch b{};
+  b.first = first; b.n = n; b.es = es; b.w = c->pw[0]; b.h = c->ph[0]; b.capacity = c->capacity;
+  b.ref = ref; b.dis = dis;
+  if (prev) b.prev = Pred{prev, prev_pitch_bytes / es};
+  // frames that get spatial features (libvmaf n_subsample: index % k == 0)
+  b.k = c->k_sub; b.e0 = 0; b.sp_n = n;
+  if (b.k > 1) {
+    b.e0 = (int)((b.k - first % b.k) % b.k);
+    b.sp_n = b.e0 < n ? (n - b.e0 + b.k - 1) / b.k : 0;
+  }
+  for (int p = 0; p < c->n_planes; ++p) {
+    b.r[p] = clip_run(ref, p, es);
+    b.d[p] = clip_run(dis, p, es);
+    b.rs[p] = frames_from(b.r[p], b.e0, es); b.rs[p].frame_pitch *= b.k;
+    b.ds[p] = frames_from(b.d[p], b.e0, es); b.ds[p].frame_pitch *= b.k;
+  }
   // (with EVERY kernel event-timed -- the breakdown pass of bench.py -- the chains stay on one stream, so that a kernel's
   // figure is its own and not its share of a crowded device; a subset mask, as in the timed region, changes nothing)
-  const bool multi = c->multi_stream && !(c->prof && c->prof_mask == 0xffffffffu);
-  // mode 2: the other chains start behind VIF scale 0 (the dominant launch runs alone, its figures stay its own) and
-  // overlap VIF scales 1-3 only; the fork event is then recorded right after that launch
-  hipStream_t st_adm = multi ? c->aux[0] : st, st_misc = multi ? c->aux[1] : st;
+  b.multi = c->multi_stream && !(c->prof && c->prof_mask == 0xffffffffu);
+  b.st = c->stream;
+  b.st_adm = b.multi ? c->aux[0] : b.st; b.st_misc = b.multi ? c->aux[1] : b.st;
+  b.fork_late = b.multi && c->multi_stream == 2 && (feat & PQA_FEAT_VIF) && !c->vif_fixed && b.sp_n > 0;   // run_vif forks
+  for (int s = 0; s < 4; ++s) { b.vif_np[s] = c->vif_tiles[s]; b.adm_np[s] = c->adm_tiles[s]; }
+  b.motion_np = c->motion_tiles_n;
+  // the frames in front of this batch: armed planes are bound, a batch that does not continue a chain starts one (the chain
+  // of a feature that is off is never read)
+  for (host::FrameChain* ch : {&c->mo_chain, &c->xp_chain, &c->st_chain[0], &c->st_chain[1], &c->ig_chain}) ch->begin(first);
 
-  // frames that get spatial features (libvmaf n_subsample: index % k == 0)
-  const int k = c->k_sub;
-  int e0 = 0, sp_n = n;
-  if (k > 1) {
-    e0 = (int)((k - first % k) % k);
-    sp_n = e0 < n ? (n - e0 + k - 1) / k : 0;
-  }
-  const bool fork_late = multi && c->multi_stream == 2 && (feat & PQA_FEAT_VIF) && !c->vif_fixed && sp_n > 0;
-  if (multi && !fork_late) {
-    HIPCHK(c, hipEventRecord(c->fork_ev, st));
-    HIPCHK(c, hipStreamWaitEvent(st_adm, c->fork_ev, 0));
-    HIPCHK(c, hipStreamWaitEvent(st_misc, c->fork_ev, 0));
-  }
-  const auto sub = [&](PlaneRun r) {
-    return PlaneRun{(const uint8_t*)r.base + (int64_t)e0 * r.frame_pitch * es, r.row_pitch, r.frame_pitch * k};
-  };
-  const PlaneRun rYs = k > 1 ? sub(rY) : rY, dYs = k > 1 ? sub(dY) : dY;
-
-  // motion: reference luma in front of the batch (caller's halo, the armed halo, or the last frame of the previous batch)
-  const void* p0 = prev;
-  int64_t p0_pitch = prev_pitch_bytes;
-  if (feat & PQA_FEAT_MOTION) {
-    if (!p0 && (c->halo_armed || (c->have_last && c->last_index == first - 1))) {
-      p0 = c->last_luma;
-      p0_pitch = c->last_luma_pitch;
-    }
-    if (p0 && p0_pitch % es) return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
-  }
-  int vif_np[4] = {c->vif_tiles[0], c->vif_tiles[1], c->vif_tiles[2], c->vif_tiles[3]};   // partial pairs written per frame
-  int adm_np[4] = {c->adm_tiles[0], c->adm_tiles[1], c->adm_tiles[2], c->adm_tiles[3]};   // partial sextets written per frame
-  int motion_np = c->motion_tiles_n;                                                       // motion partials written per frame
-
-  if ((feat & PQA_FEAT_VIF) && sp_n > 0 && c->vif_fixed) {
-    PlaneRun cr = rYs, cd = dYs;
-    Elem ce = c->elem;
-    int cw = w, ch = h;
-    for (int s = 0; s < 4; ++s) {
-      MutPlaneRun nr{nullptr, 0, 0}, nd{nullptr, 0, 0};
-      if (s < 3) {  // the pyramid buffers hold u16 planes in this mode (same element pitches, half the bytes)
-        Level& L = c->vif_lv[s + 1];
-        nr = MutPlaneRun{L.ref, L.pitch, L.frame_pitch};
-        nd = MutPlaneRun{L.dis, L.pitch, L.frame_pitch};
-      }
-      {
-        ProfScope ps(c, s, sp_n, st);
-        HIPCHK(c, launch_vif_fixed(st, s, (int)c->cfg.bit_depth, ce, cr, cd, sp_n, cw, ch, c->cfg.vif_enhn_gain_limit,
-                                   c->vif_lut, c->vif_fx_part[s], nr, nd));
-      }
-      if (s < 3) {
-        Level& L = c->vif_lv[s + 1];
-        cr = PlaneRun{L.ref, L.pitch, L.frame_pitch};
-        cd = PlaneRun{L.dis, L.pitch, L.frame_pitch};
-        ce = ELEM_U16;
-        cw = L.w; ch = L.h;
-      }
-    }
-  } else if ((feat & PQA_FEAT_VIF) && sp_n > 0) {
-    PlaneRun cr = rYs, cd = dYs;
-    Elem ce = c->elem;
-    int cw = w, ch = h;
-    for (int s = 0; s < 4; ++s) {
-      MutPlaneRun nr{nullptr, 0, 0}, nd{nullptr, 0, 0};
-      if (s < 3) {
-        Level& L = c->vif_lv[s + 1];
-        nr = MutPlaneRun{L.ref, L.pitch, L.frame_pitch};
-        nd = MutPlaneRun{L.dis, L.pitch, L.frame_pitch};
-      }
-      {
-        ProfScope ps(c, s, sp_n, st);
-        HIPCHK(c, launch_vif_stat(st, s, ce, cr, cd, sp_n, cw, ch, c->inv_scale,
-                                  (float)c->cfg.vif_enhn_gain_limit, c->cfg.vif_border == PQA_VIF_BORDER_INTEGER,
-                                  c->vif_part[s], nr, nd, c->vif_s0_mode, &vif_np[s], c->vif_uniform));
-      }
-      if (s == 0 && fork_late) {
-        HIPCHK(c, hipEventRecord(c->fork_ev, st));
-        HIPCHK(c, hipStreamWaitEvent(st_adm, c->fork_ev, 0));
-        HIPCHK(c, hipStreamWaitEvent(st_misc, c->fork_ev, 0));
-      }
-      if (s < 3) {
-        Level& L = c->vif_lv[s + 1];
-        cr = PlaneRun{L.ref, L.pitch, L.frame_pitch};
-        cd = PlaneRun{L.dis, L.pitch, L.frame_pitch};
-        ce = ELEM_F32;
-        cw = L.w; ch = L.h;
-      }
-    }
-  }
-  if ((feat & PQA_FEAT_ADM) && sp_n > 0 && c->adm_fixed) {
-    PlaneRun cr = rYs, cd = dYs;
-    Elem ce = c->elem;
-    int cw = w, ch = h;
-    for (int s = 0; s < 4; ++s) {
-      MutPlaneRun lr{nullptr, 0, 0}, ld{nullptr, 0, 0};
-      if (s < 3) {  // the approximation-band buffers hold int32 planes in this mode (same 4-byte elements)
-        Level& L = c->adm_lv[s + 1];
-        lr = MutPlaneRun{L.ref, L.pitch, L.frame_pitch};
-        ld = MutPlaneRun{L.dis, L.pitch, L.frame_pitch};
-      }
-      {
-        ProfScope ps(c, 7 + s, sp_n, st_adm);
-        HIPCHK(c, launch_adm_fixed(st_adm, s, (int)c->cfg.bit_depth, ce, cr, cd, sp_n, cw, ch,
-                                   c->cfg.adm_enhn_gain_limit, c->adm_div_lut, lr, ld, c->adm_fx_part[s]));
-      }
-      if (s < 3) {
-        Level& L = c->adm_lv[s + 1];
-        cr = PlaneRun{L.ref, L.pitch, L.frame_pitch};
-        cd = PlaneRun{L.dis, L.pitch, L.frame_pitch};
-        ce = ELEM_F32;
-        cw = L.w; ch = L.h;
-      }
-    }
-  } else if ((feat & PQA_FEAT_ADM) && sp_n > 0) {
-    PlaneRun cr = rYs, cd = dYs;
-    Elem ce = c->elem;
-    int cw = w, ch = h;
-    int s = 0;
-    if (c->adm_mode == ADM_AUTO) {   // scales 0 and 1 in one launch when the geometry allows (adm_pyramid.hip)
-      Level& L2 = c->adm_lv[2];
-      hipError_t perr = hipSuccess;
-      int np = 0;
-      ProfScope ps(c, 7, sp_n, st_adm);
-      if (launch_adm_pyramid(st_adm, ce, cr, cd, sp_n, cw, ch, c->inv_scale, (float)c->cfg.adm_enhn_gain_limit,
-                             MutPlaneRun{L2.ref, L2.pitch, L2.frame_pitch}, MutPlaneRun{L2.dis, L2.pitch, L2.frame_pitch},
-                             c->adm_part[0], c->adm_part[1], &np, &perr)) {
-        HIPCHK(c, perr);
-        adm_np[0] = adm_np[1] = np;
-        cr = PlaneRun{L2.ref, L2.pitch, L2.frame_pitch};
-        cd = PlaneRun{L2.dis, L2.pitch, L2.frame_pitch};
-        ce = ELEM_F32;
-        cw = L2.w; ch = L2.h;
-        s = 2;
-      }
-    }
-    for (; s < 4; ++s) {
-      MutPlaneRun lr{nullptr, 0, 0}, ld{nullptr, 0, 0};
-      if (s < 3) {
-        Level& L = c->adm_lv[s + 1];
-        lr = MutPlaneRun{L.ref, L.pitch, L.frame_pitch};
-        ld = MutPlaneRun{L.dis, L.pitch, L.frame_pitch};
-      }
-      {
-        ProfScope ps(c, 7 + s, sp_n, st_adm);
-        HIPCHK(c, launch_adm_scale(st_adm, s, ce, cr, cd, sp_n, cw, ch, c->inv_scale,
-                                   (float)c->cfg.adm_enhn_gain_limit, lr, ld, c->adm_part[s], c->adm_mode, &adm_np[s]));
-      }
-      if (s < 3) {
-        Level& L = c->adm_lv[s + 1];
-        cr = PlaneRun{L.ref, L.pitch, L.frame_pitch};
-        cd = PlaneRun{L.dis, L.pitch, L.frame_pitch};
-        ce = ELEM_F32;
-        cw = L.w; ch = L.h;
-      }
-    }
-  }
-  if (feat & PQA_FEAT_MOTION) {
-    ProfScope ps(c, 11, n, st_misc);
-    if (c->motion_fixed)
-      HIPCHK(c, launch_motion_fixed(st_misc, (int)c->cfg.bit_depth, c->elem, rY, p0, p0 ? p0_pitch / es : 0, n, w, h,
-                                    c->motion_fx_part));
-    else
-      HIPCHK(c, launch_motion(st_misc, c->elem, rY, p0, p0 ? p0_pitch / es : 0, n, w, h, c->inv_scale, c->motion_part,
-                              c->motion_mode, &motion_np));
-  }
-  int n_sse = 0, n_ssim = 0;
-  bool sse_a[3] = {false, false, false}, sse_b[3] = {false, false, false}, sse_t[3] = {false, false, false};
-  const bool both = (feat & PQA_FEAT_PSNR) && (feat & PQA_FEAT_SSIM);
-  if (feat & PQA_FEAT_PSNR) {
-    n_sse = c->n_planes;
-    ProfScope ps(c, 12, n, st_misc);
-    for (int p = 0; p < c->n_planes; ++p) {
-      const PlaneRun a{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-      const PlaneRun b{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-      const int pw = c->pw[p], ph = c->ph[p];
-      if (both && c->ssim_tiles_n[p] > 0) {
-        // the SSIM kernel delivers the squared error of the 4-aligned part; only remainder strips are left
-        sse_t[p] = true;
-        const int w4 = (pw >> 2) << 2, h4 = (ph >> 2) << 2;
-        if (w4 < pw) {
-          const PlaneRun ar{(const uint8_t*)a.base + (int64_t)w4 * es, a.row_pitch, a.frame_pitch};
-          const PlaneRun br{(const uint8_t*)b.base + (int64_t)w4 * es, b.row_pitch, b.frame_pitch};
-          HIPCHK(c, launch_sse(st_misc, c->elem, ar, br, n, pw - w4, ph, c->sse_part[p]));
-          sse_a[p] = true;
-        }
-        if (h4 < ph) {
-          const PlaneRun ab{(const uint8_t*)a.base + (int64_t)h4 * a.row_pitch * es, a.row_pitch, a.frame_pitch};
-          const PlaneRun bb{(const uint8_t*)b.base + (int64_t)h4 * b.row_pitch * es, b.row_pitch, b.frame_pitch};
-          HIPCHK(c, launch_sse(st_misc, c->elem, ab, bb, n, w4, ph - h4, c->sse_part_b[p]));
-          sse_b[p] = true;
-        }
-      } else {
-        HIPCHK(c, launch_sse(st_misc, c->elem, a, b, n, pw, ph, c->sse_part[p]));
-        sse_a[p] = true;
-      }
-    }
-  }
-  if (feat & PQA_FEAT_SSIM) {
-    n_ssim = c->n_planes;
-    ProfScope ps(c, 13, n, st_misc);
-    for (int p = 0; p < c->n_planes; ++p) {
-      const PlaneRun a{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-      const PlaneRun b{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-      HIPCHK(c, launch_ssim(st_misc, c->elem, a, b, n, c->pw[p], c->ph[p], (1 << c->cfg.bit_depth) - 1, c->ssim_part[p],
-                            sse_t[p] ? c->sse_tile_part[p] : nullptr));
-    }
-  }
-
-  // extension features run on the frames that get spatial features; the extension rows of the other frames are NaN
-  if (k > 1 && (feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)))
-    HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext, (int)(first % c->capacity), n, c->capacity, PQA_EXT_DOUBLES));
-  if ((feat & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM))) {
-    // the SSIM family, ssf_sb frames at a time (the MS-SSIM pyramid is sized for that many)
-    const bool fs = feat & PQA_FEAT_FLOAT_SSIM, ms = feat & PQA_FEAT_MS_SSIM;
-    for (int s0 = 0; s0 < sp_n; s0 += c->ssf_sb) {
-      const int m = sp_n - s0 < c->ssf_sb ? sp_n - s0 : c->ssf_sb;
-      const PlaneRun r0{(const uint8_t*)rYs.base + (int64_t)s0 * rYs.frame_pitch * es, rYs.row_pitch, rYs.frame_pitch};
-      const PlaneRun d0{(const uint8_t*)dYs.base + (int64_t)s0 * dYs.frame_pitch * es, dYs.row_pitch, dYs.frame_pitch};
-      SsfFinalizeArgs sa{};
-      sa.n_frames = m;
-      sa.ext = c->ext;
-      sa.ext_stride = PQA_EXT_DOUBLES;
-      sa.slot_base = (int)((first + e0 + (int64_t)s0 * k) % c->capacity);
-      sa.slot_step = k;
-      sa.capacity = c->capacity;
-      if (fs) {
-        sa.fs_part = c->fs_part; sa.fs_tiles = c->fs_tiles;
-        const int dw = (w + c->fs_box - 1) / c->fs_box, dh = (h + c->fs_box - 1) / c->fs_box;
-        sa.fs_norm = 1.0 / ((double)(dw - 10) * (dh - 10));
-        ProfScope ps(c, 16, m, st_misc);
-        HIPCHK(c, launch_ssf_map(st_misc, c->elem, r0, d0, m, w, h, c->fs_box, c->inv_scale, c->fs_part));
-        if (!ms) HIPCHK(c, launch_ssf_finalize(st_misc, sa));
-      }
-      if (ms) {
-        ProfScope ps(c, 15, m, st_misc);
-        PlaneRun cr = r0, cd = d0;
-        Elem ce = c->elem;
-        for (int j = 0; j < kMsScales; ++j) {
-          const Level& L = c->ms_lv[j];
-          sa.ms_part[j] = c->ms_part[j]; sa.ms_tiles[j] = c->ms_tiles[j];
-          sa.ms_norm[j] = 1.0 / ((double)(L.w - 10) * (L.h - 10));
-          if (j == 0) {   // scale 0 writes scale 1's planes in the same launch (the caller's pair is read once)
-            const Level& N = c->ms_lv[1];
-            HIPCHK(c, launch_ssf_map(st_misc, ce, cr, cd, m, L.w, L.h, 1, c->inv_scale, c->ms_part[0],
-                                     MutPlaneRun{N.ref, N.pitch, N.frame_pitch}, MutPlaneRun{N.dis, N.pitch, N.frame_pitch}));
-          } else {
-            HIPCHK(c, launch_ssf_map(st_misc, ce, cr, cd, m, L.w, L.h, 1, c->inv_scale, c->ms_part[j]));
-          }
-          if (j + 1 < kMsScales) {
-            const Level& N = c->ms_lv[j + 1];
-            if (j > 0)
-              HIPCHK(c, launch_ssf_down(st_misc, ce, cr, cd, m, L.w, L.h, c->inv_scale, MutPlaneRun{N.ref, N.pitch, N.frame_pitch},
-                                        MutPlaneRun{N.dis, N.pitch, N.frame_pitch}));
-            cr = PlaneRun{N.ref, N.pitch, N.frame_pitch};
-            cd = PlaneRun{N.dis, N.pitch, N.frame_pitch};
-            ce = ELEM_F32;
-          }
-        }
-        HIPCHK(c, launch_ssf_finalize(st_misc, sa));
-      }
-    }
-  }
-  if ((feat & PQA_FEAT_CIEDE) && sp_n > 0) {
-    // CIEDE2000 on Y, U, V of the frames that get spatial features; the epilogue writes slots 20 / 21 of their rows only
-    PlaneRun r3[3], d3[3];
-    for (int p = 0; p < 3; ++p) {
-      const PlaneRun rp{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-      const PlaneRun dp{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-      r3[p] = k > 1 ? sub(rp) : rp;
-      d3[p] = k > 1 ? sub(dp) : dp;
-    }
-    CiedeFinalizeArgs ca{};
-    ca.n_frames = sp_n;
-    ca.ext = c->ext;
-    ca.ext_stride = PQA_EXT_DOUBLES;
-    ca.slot_base = (int)((first + e0) % c->capacity);
-    ca.slot_step = k;
-    ca.capacity = c->capacity;
-    ca.partials = c->ciede_part;
-    ca.n_tiles = c->ciede_tiles_n;
-    ca.norm = 1.0 / ((double)w * h);
-    ProfScope ps(c, 4, sp_n, st_misc);
-    HIPCHK(c, launch_ciede(st_misc, c->elem, r3, d3, sp_n, w, h, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift,
-                           (int)c->cfg.bit_depth, c->ciede_part));
-    HIPCHK(c, launch_ciede_finalize(st_misc, ca));
-  }
-  if ((feat & PQA_FEAT_CAMBI) && sp_n > 0) {
-    // CAMBI of the distorted (and, FULL_REF, the reference) luma, cambi_sb frames at a time; slots 22 / 23 of their rows
-    const bool full = feat & PQA_FEAT_CAMBI_FULL_REF;
-    for (int s0 = 0; s0 < sp_n; s0 += c->cambi_sb) {
-      const int m = sp_n - s0 < c->cambi_sb ? sp_n - s0 : c->cambi_sb;
-      const int slot_base = (int)((first + e0 + (int64_t)s0 * k) % c->capacity);
-      const PlaneRun d0{(const uint8_t*)dYs.base + (int64_t)s0 * dYs.frame_pitch * es, dYs.row_pitch, dYs.frame_pitch};
-      HIPCHK(c, launch_cambi(st_misc, c->elem, d0, m, w, h, (int)c->cfg.bit_depth, c->cambi_prm, c->cambi_wk, c->ext,
-                             PQA_EXT_DOUBLES, PQA_EXT_CAMBI, slot_base, k, c->capacity));
-      if (full) {
-        const PlaneRun r0{(const uint8_t*)rYs.base + (int64_t)s0 * rYs.frame_pitch * es, rYs.row_pitch, rYs.frame_pitch};
-        HIPCHK(c, launch_cambi(st_misc, c->elem, r0, m, w, h, (int)c->cfg.bit_depth, c->cambi_prm, c->cambi_wk, c->ext,
-                               PQA_EXT_DOUBLES, PQA_EXT_CAMBI_SOURCE, slot_base, k, c->capacity));
-      }
-    }
-  }
-  if (feat & PQA_FEAT_PSNR_HVS) {
-    // PSNR-HVS on Y, Cb, Cr of the frames that get spatial features, into slots 0..6 of their ext2 rows
-    if (k > 1)
-      HIPCHK(c, launch_ext_fill_nan(st_misc, c->ext2, (int)(first % c->capacity), n, c->capacity, PQA_EXT2_DOUBLES));
-    if (sp_n > 0) {
-      PlaneRun r3[3], d3[3];
-      for (int p = 0; p < 3; ++p) {
-        const PlaneRun rp{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-        const PlaneRun dp{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-        r3[p] = k > 1 ? sub(rp) : rp;
-        d3[p] = k > 1 ? sub(dp) : dp;
-      }
-      PsnrHvsFinalizeArgs pa{};
-      pa.n_frames = sp_n;
-      pa.ext2 = c->ext2;
-      pa.ext_stride = PQA_EXT2_DOUBLES;
-      pa.slot_base = (int)((first + e0) % c->capacity);
-      pa.slot_step = k;
-      pa.capacity = c->capacity;
-      pa.partials = c->phv_part;
-      for (int p = 0; p < 4; ++p) pa.tile0[p] = c->phv_geo.tile0[p];
-      for (int p = 0; p < 3; ++p) pa.blocks[p] = c->phv_geo.nbx[p] * c->phv_geo.nby[p];
-      pa.peak = (double)((1 << c->cfg.bit_depth) - 1);
-      HIPCHK(c, launch_psnr_hvs(st_misc, c->elem, r3, d3, sp_n, c->phv_geo, c->phv_part));
-      HIPCHK(c, launch_psnr_hvs_finalize(st_misc, pa));
-    }
-  }
-  // XPSNR on every frame: its predecessors come from the batch, the caller's halo, the kept pair or the armed history
-  int xp_h1 = -1;   // xp_hist slot that held frame first-1 (-1: the caller's plane or none)
-  if (feat & PQA_FEAT_XPSNR) {
-    if (c->xp_armed >= 0) {
-      c->xp_hist_idx[0] = c->xp_armed >= 1 ? first - 1 : -1;
-      c->xp_hist_idx[1] = c->xp_armed >= 2 ? first - 2 : -1;
-      c->xp_armed = -1;
-    } else if (c->xp_last != first - 1) {   // a chain start: zero planes
-      c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
-    }
-    const auto held = [&](int64_t idx) {   // -1 marks an empty slot: frames before 0 are never held
-      return idx < 0 ? -1 : c->xp_hist_idx[0] == idx ? 0 : c->xp_hist_idx[1] == idx ? 1 : -1;
-    };
-    xp_h1 = held(first - 1);
-    const int j2 = held(first - 2);
-    const void* h1 = nullptr;
-    int64_t hp1 = 0;
-    if (prev) {
-      if (prev_pitch_bytes % es) return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
-      h1 = prev; hp1 = prev_pitch_bytes / es;
-    } else if (xp_h1 >= 0) {
-      h1 = c->xp_hist[xp_h1]; hp1 = c->xp_hist_pitch / es;
-    }
-    const void* h2 = j2 >= 0 ? c->xp_hist[j2] : nullptr;
-    const int64_t hp2 = j2 >= 0 ? c->xp_hist_pitch / es : 0;
-    PlaneRun r3[3], d3[3];
-    for (int p = 0; p < c->n_planes; ++p) {
-      r3[p] = PlaneRun{ref->plane[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-      d3[p] = PlaneRun{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-    }
-    XpFinalizeArgs xa{};
-    xa.n_frames = n;
-    xa.blk = c->xp_blk;
-    xa.wbuf = c->xp_w;
-    xa.ext3 = c->ext3;
-    xa.ext_stride = PQA_EXT3_DOUBLES;
-    xa.slot_base = (int)(first % c->capacity);
-    xa.capacity = c->capacity;
-    xa.g = c->xp_geo;
-    HIPCHK(c, launch_xpsnr_blocks(st_misc, c->elem, r3, d3, n, h1, hp1, h2, hp2, (feat & PQA_FEAT_XPSNR_HFR) != 0,
-                                  c->xp_geo, c->xp_blk));
-    HIPCHK(c, launch_xpsnr_finalize(st_misc, xa));
-  }
-  if (feat & PQA_FEAT_SITI) {
-    // SI / TI of both clips on every frame; frame first-1 of each clip: the caller's halo (reference), the kept or the
-    // armed plane; none at a chain start
-    const void* sp0[2] = {nullptr, nullptr};
-    int64_t spp[2] = {0, 0};
-    for (int z = 0; z < 2; ++z) {
-      if (c->st_armed[z]) {
-        c->st_hist_idx[z] = first - 1;
-        c->st_armed[z] = false;
-      }
-      if (c->st_hist_idx[z] >= 0 && c->st_hist_idx[z] == first - 1) {
-        sp0[z] = c->st_hist[z];
-        spp[z] = c->st_hist_pitch / es;
-      }
-    }
-    if (prev) {
-      if (prev_pitch_bytes % es) return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
-      sp0[1] = prev;
-      spp[1] = prev_pitch_bytes / es;
-    }
-    const PlaneRun sc[2] = {dY, rY};
-    const bool sfull[2] = {(feat & PQA_FEAT_SITI_DIS_FULL) != 0, (feat & PQA_FEAT_SITI_REF_FULL) != 0};
-    HIPCHK(c, launch_siti(st_misc, c->elem, sc, sp0, spp, sfull, 2, n, w, h, c->st_part, c->ext4, PQA_EXT4_DOUBLES,
-                          (int)(first % c->capacity), c->capacity, nullptr));
-  }
-  if (feat & PQA_FEAT_INTEGRITY) {
-    // SAD of every plane of the distorted frames against their predecessors, and the black count; frame first-1: the kept
-    // or the armed planes, none at a chain start
-    if (c->ig_armed) {
-      c->ig_hist_idx = first - 1;
-      c->ig_armed = false;
-    }
-    const bool have = c->ig_hist_idx >= 0 && c->ig_hist_idx == first - 1;
-    PlaneRun cur[3] = {};
-    const void* ip0[3] = {nullptr, nullptr, nullptr};
-    int64_t ipp[3] = {0, 0, 0};
-    for (int p = 0; p < c->n_planes; ++p) {
-      cur[p] = PlaneRun{dis->plane[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-      if (have) {
-        ip0[p] = c->ig_hist[p];
-        ipp[p] = c->ig_hist_pitch[p] / es;
-      }
-    }
-    HIPCHK(c, launch_integrity(st_misc, c->elem, cur, ip0, ipp, c->pw, c->ph, c->n_planes, n, false, c->black_thr,
-                               c->ig_part, c->ext5, PQA_EXT5_DOUBLES, (int)(first % c->capacity), c->capacity, nullptr));
-  }
-
-  if (multi) {  // join
-    HIPCHK(c, hipEventRecord(c->join_ev[0], st_adm));
-    HIPCHK(c, hipEventRecord(c->join_ev[1], st_misc));
-    HIPCHK(c, hipStreamWaitEvent(st, c->join_ev[0], 0));
-    HIPCHK(c, hipStreamWaitEvent(st, c->join_ev[1], 0));
-  }
-
-  FinalizeArgs fa{};
-  for (int s = 0; s < 4; ++s) {
-    fa.vif_part[s] = c->vif_part[s]; fa.vif_tiles[s] = c->vif_fixed ? c->vif_tiles[s] : vif_np[s];
-    fa.vif_fx_part[s] = c->vif_fixed ? c->vif_fx_part[s] : nullptr;
-    fa.adm_part[s] = c->adm_part[s]; fa.adm_tiles[s] = c->adm_fixed ? c->adm_tiles[s] : adm_np[s]; fa.adm_area[s] = c->adm_area[s];
-    fa.adm_fx_part[s] = c->adm_fixed ? c->adm_fx_part[s] : nullptr;
-    fa.adm_fx_tiles_x[s] = adm_tiles_x(c->adm_fx[s].band_w);
-    fa.adm_fx_top[s] = c->adm_fx[s].top; fa.adm_fx_bottom[s] = c->adm_fx[s].bottom;
-    fa.adm_fx_num_shift[s] = c->adm_fx[s].num_row_shift; fa.adm_fx_den_shift[s] = c->adm_fx[s].den_row_shift;
-  }
-  fa.motion_part = c->motion_part;
-  fa.motion_tiles = c->motion_fixed ? c->motion_tiles_n : motion_np;
-  fa.motion_norm = (double)c->inv_scale / ((double)w * h);
-  fa.motion_fx_part = c->motion_fixed ? c->motion_fx_part : nullptr;
-  fa.motion_wh = (unsigned)w * (unsigned)h;
-  for (int p = 0; p < 3; ++p) {
-    fa.sse_part[p] = c->sse_part[p];
-    fa.sse_use_a[p] = sse_a[p] ? 1 : 0;
-    fa.sse_part_b[p] = sse_b[p] ? c->sse_part_b[p] : nullptr;
-    fa.sse_tile_part[p] = sse_t[p] ? c->sse_tile_part[p] : nullptr;
-    fa.ssim_part[p] = c->ssim_part[p]; fa.ssim_tiles[p] = c->ssim_tiles_n[p]; fa.ssim_norm[p] = c->ssim_norm[p];
-  }
-  fa.adm_fx_acc = c->adm_fx_acc;
-  fa.records = c->records;
-  fa.record_stride = PQA_RECORD_DOUBLES;
-  fa.capacity = c->capacity;
-  {
-    ProfScope ps(c, 14, n, st);
-    if (k > 1) {
-      if (sp_n > 0 && (feat & (PQA_FEAT_VIF | PQA_FEAT_ADM))) {
-        FinalizeArgs f1 = fa;
-        f1.n_frames = sp_n;
-        f1.has_vif = !!(feat & PQA_FEAT_VIF); f1.has_adm = !!(feat & PQA_FEAT_ADM);
-        f1.slot_base = (int)((first + e0) % c->capacity); f1.slot_step = k;
-        HIPCHK(c, launch_finalize(st, f1));
-      }
-      FinalizeArgs f2 = fa;
-      f2.n_frames = n;
-      f2.has_motion = !!(feat & PQA_FEAT_MOTION); f2.n_sse_planes = n_sse; f2.n_ssim_planes = n_ssim;
-      f2.slot_base = (int)(first % c->capacity); f2.slot_step = 1;
-      HIPCHK(c, launch_finalize(st, f2));
-    } else {
-      fa.n_frames = n;
-      fa.has_vif = !!(feat & PQA_FEAT_VIF); fa.has_adm = !!(feat & PQA_FEAT_ADM);
-      fa.has_motion = !!(feat & PQA_FEAT_MOTION); fa.n_sse_planes = n_sse; fa.n_ssim_planes = n_ssim;
-      fa.slot_base = (int)(first % c->capacity); fa.slot_step = 1;
-      HIPCHK(c, launch_finalize(st, fa));
-    }
-  }
+  // the VIF chain on the main stream, the ADM chain on the second, everything else in this order on the third
+  static int (*const kSteps[])(pqa_ctx*, Batch&) = {run_vif,   run_adm,   run_motion,   run_psnr_ssim, fill_ext_nan, run_ssim_family,
+                                                    run_ciede, run_cambi, run_psnr_hvs, run_xpsnr,     run_siti,     run_integrity};
+  if (b.multi && !b.fork_late && (rc = fork_streams(c, b)) != PQA_OK) return rc;
+  for (const auto step : kSteps)
+    if ((rc = step(c, b)) != PQA_OK) return rc;
+  if (b.multi && (rc = join_streams(c, b)) != PQA_OK) return rc;
+  if ((rc = run_finalize(c, b)) != PQA_OK) return rc;
   {  // the records of this batch are complete here: one event per batch, so pqa_collect waits for ITS batch only
     const uint64_t seq = c->batch_seq + 1;
     const int e = (int)(seq % kBatchEvents);
-    HIPCHK(c, hipEventRecord(c->batch_ev[e], st));
+    HIPCHK(c, hipEventRecord(c->batch_ev[e], b.st));
     c->batch_ev_seq[e] = seq;
     c->batch_seq = seq;
     claim_slots(c, first, n, seq);
   }
-  if (feat & PQA_FEAT_MOTION) {
-    // keep the last reference luma so the next batch continues the motion chain
-    const uint8_t* src = (const uint8_t*)ref->plane[0] + (int64_t)(n - 1) * ref->frame_pitch[0];
-    HIPCHK(c, hipMemcpy2DAsync(c->last_luma, c->last_luma_pitch, src, ref->row_pitch[0], (size_t)w * es, h,
-                               hipMemcpyDeviceToDevice, st));
-    c->have_last = true;
-    c->halo_armed = false;
-    c->last_index = first + n - 1;
-  }
-  if (feat & PQA_FEAT_XPSNR) {
-    // keep the chain's last two reference luma planes (behind the join: this batch's kernels have read the old ones)
-    const size_t row_bytes = (size_t)w * es;
-    const auto keep = [&](int slot, const void* src, int64_t pitch, int64_t idx) -> hipError_t {
-      c->xp_hist_idx[slot] = idx;
-      return hipMemcpy2DAsync(c->xp_hist[slot], c->xp_hist_pitch, src, pitch, row_bytes, h, hipMemcpyDeviceToDevice, st);
-    };
-    const auto frame = [&](int f) { return (const uint8_t*)ref->plane[0] + (int64_t)f * ref->frame_pitch[0]; };
-    if (n >= 2) {
-      HIPCHK(c, keep(0, frame(n - 2), ref->row_pitch[0], first + n - 2));
-      HIPCHK(c, keep(1, frame(n - 1), ref->row_pitch[0], first + n - 1));
-    } else if (n == 1) {
-      int older = xp_h1;   // frame first-1 stays where it is, or comes from the caller's plane
-      if (older < 0 && prev) {
-        older = 0;
-        HIPCHK(c, keep(0, prev, prev_pitch_bytes, first - 1));
-      }
-      const int slot = older == 0 ? 1 : 0;
-      if (older < 0) c->xp_hist_idx[1] = -1;
-      HIPCHK(c, keep(slot, frame(0), ref->row_pitch[0], first));
-    }
-    c->xp_last = first + n - 1;
-  }
-  if (feat & PQA_FEAT_SITI) {
-    // keep each clip's last luma plane (behind the join: this batch's kernels have read the old ones)
-    const pqa_device_clip* side[2] = {dis, ref};
-    for (int z = 0; z < 2; ++z) {
-      const uint8_t* src = (const uint8_t*)side[z]->plane[0] + (int64_t)(n - 1) * side[z]->frame_pitch[0];
-      HIPCHK(c, hipMemcpy2DAsync(c->st_hist[z], c->st_hist_pitch, src, side[z]->row_pitch[0], (size_t)w * es, h,
-                                 hipMemcpyDeviceToDevice, st));
-      c->st_hist_idx[z] = first + n - 1;
-    }
-  }
-  if (feat & PQA_FEAT_INTEGRITY) {
-    // keep every plane of the last distorted frame (behind the join: this batch's kernel has read the old ones)
-    for (int p = 0; p < c->n_planes; ++p) {
-      const uint8_t* src = (const uint8_t*)dis->plane[p] + (int64_t)(n - 1) * dis->frame_pitch[p];
-      HIPCHK(c, hipMemcpy2DAsync(c->ig_hist[p], c->ig_hist_pitch[p], src, dis->row_pitch[p], (size_t)c->pw[p] * es, c->ph[p],
-                                 hipMemcpyDeviceToDevice, st));
-    }
-    c->ig_hist_idx = first + n - 1;
-  }
-  return PQA_OK;
+  return keep_histories(c, b);
 }
 
 // One frame pair as the library lays it out itself (pinned staging, its device copy, unpacked decoder surfaces): ref
@@ -1157,8 +1096,7 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
       CREATE_TRY(dev_alloc(c, &c->motion_part, (size_t)(c->motion_tiles_n > mp ? c->motion_tiles_n : mp) * B));
     }
     if (c->motion_fixed) CREATE_TRY(dev_alloc(c, &c->motion_fx_part, (size_t)c->motion_tiles_n * B));
-    c->last_luma_pitch = round_up((int64_t)w * c->esize, 64);
-    CREATE_TRY(dev_alloc(c, &c->last_luma, (size_t)c->last_luma_pitch * h));
+    CREATE_TRY(hist_alloc(c, &c->mo_hist, 0));
   }
   for (int p = 0; p < c->n_planes; ++p) {
     if (cfg->features & PQA_FEAT_PSNR) {
@@ -1245,15 +1183,13 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     xpsnr_geometry(c->pw[0], c->ph[0], c->pw[1], c->ph[1], c->n_planes, (int)cfg->bit_depth, &c->xp_geo);
     CREATE_TRY(dev_alloc(c, &c->xp_blk, (size_t)c->xp_geo.n_blk * kXpBlockVals * B));
     CREATE_TRY(dev_alloc(c, &c->xp_w, (size_t)c->xp_geo.n_blk * B));
-    c->xp_hist_pitch = round_up((int64_t)w * c->esize, 64);
-    for (int j = 0; j < 2; ++j) CREATE_TRY(dev_alloc(c, &c->xp_hist[j], (size_t)c->xp_hist_pitch * h));
+    for (int j = 0; j < 2; ++j) CREATE_TRY(hist_alloc(c, &c->xp_hist[j], 0));
     CREATE_TRY(dev_alloc(c, &c->ext3, (size_t)c->capacity * PQA_EXT3_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext3, 0, c->capacity, c->capacity, PQA_EXT3_DOUBLES));
   }
   if (cfg->features & PQA_FEAT_SITI) {
     CREATE_TRY(dev_alloc(c, &c->st_part, (size_t)siti_partials(w, h) * 2 * 4 * B));
-    c->st_hist_pitch = round_up((int64_t)w * c->esize, 64);
-    for (int z = 0; z < 2; ++z) CREATE_TRY(dev_alloc(c, &c->st_hist[z], (size_t)c->st_hist_pitch * h));
+    for (int z = 0; z < 2; ++z) CREATE_TRY(hist_alloc(c, &c->st_hist[z], 0));
     CREATE_TRY(dev_alloc(c, &c->ext4, (size_t)c->capacity * PQA_EXT4_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext4, 0, c->capacity, c->capacity, PQA_EXT4_DOUBLES));
   }
@@ -1263,10 +1199,7 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
   }
   if (cfg->features & PQA_FEAT_INTEGRITY) {
     CREATE_TRY(dev_alloc(c, &c->ig_part, (size_t)B * 3 * kIntegrityBlocks * 2));
-    for (int p = 0; p < c->n_planes; ++p) {
-      c->ig_hist_pitch[p] = round_up((int64_t)c->pw[p] * c->esize, 64);
-      CREATE_TRY(dev_alloc(c, &c->ig_hist[p], (size_t)c->ig_hist_pitch[p] * c->ph[p]));
-    }
+    for (int p = 0; p < c->n_planes; ++p) CREATE_TRY(hist_alloc(c, &c->ig_hist[p], p));
     CREATE_TRY(dev_alloc(c, &c->ext5, (size_t)c->capacity * PQA_EXT5_DOUBLES));
     CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext5, 0, c->capacity, c->capacity, PQA_EXT5_DOUBLES));
   }
@@ -1490,15 +1423,15 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
   if (prev_staged && (c->cfg.features & PQA_FEAT_MOTION)) {
     // the halo frame goes where a previous batch would have left it, unpacked / shifted down
     if (prev_packed) {
-      void* dst[3] = {c->last_luma, nullptr, nullptr};
-      const int64_t rp[3] = {c->last_luma_pitch, 0, 0}, fp[3] = {0, 0, 0};
+      void* dst[3] = {c->mo_hist.base, nullptr, nullptr};
+      const int64_t rp[3] = {c->mo_hist.pitch, 0, 0}, fp[3] = {0, 0, 0};
       HIPCHK(c, launch_unpack(c->stream, (int)prev_ref->format, prev_ref->luma, prev_ref->luma_row_pitch, 0, dst, rp, fp, c->pw[0],
                               c->ph[0], 1));
     } else {
-      HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->last_luma, c->last_luma_pitch,
+      HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->mo_hist.base, c->mo_hist.pitch,
                                       0, c->pw[0], c->ph[0], shift, 1));
     }
-    c->halo_armed = true;
+    c->mo_chain.arm(1);
   }
   // xpsnr's and siti's reference frame first-1, unpacked / shifted down likewise
   const bool shift_prev = prev_staged && (c->cfg.features & (PQA_FEAT_XPSNR | PQA_FEAT_SITI));
@@ -1792,29 +1725,23 @@ int set_history(pqa_ctx* c, const void* const* prev, int n_prev, int64_t row_str
   int rc = flush_pending(c);
   if (rc != PQA_OK) return rc;
   if (n_prev == 0) {   // a chain start
-    c->halo_armed = false;
-    c->have_last = false;
-    c->xp_armed = -1;
-    c->xp_last = -1;
-    c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
-    c->st_armed[1] = false;
-    c->st_hist_idx[1] = -1;
+    c->mo_chain.restart();
+    c->xp_chain.restart();
+    c->st_chain[1].restart();
     return PQA_OK;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
   if (mot) {
-    HIPCHK(c, hipMemcpy2D(c->last_luma, c->last_luma_pitch, prev[0], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
-    c->halo_armed = true;
+    HIPCHK(c, hist_arm(c, c->mo_hist, prev[0], row_stride, 0));
+    c->mo_chain.arm(1);
   }
   if (xp) {
-    for (int j = 0; j < n_prev; ++j)
-      HIPCHK(c, hipMemcpy2D(c->xp_hist[j], c->xp_hist_pitch, prev[j], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
-    c->xp_armed = n_prev;
+    for (int j = 0; j < n_prev; ++j) HIPCHK(c, hist_arm(c, c->xp_hist[j], prev[j], row_stride, 0));
+    c->xp_chain.arm(n_prev);
   }
   if (si) {
-    HIPCHK(c, hipMemcpy2D(c->st_hist[1], c->st_hist_pitch, prev[0], row_stride, row_bytes, c->ph[0], hipMemcpyHostToDevice));
-    c->st_armed[1] = true;
+    HIPCHK(c, hist_arm(c, c->st_hist[1], prev[0], row_stride, 0));
+    c->st_chain[1].arm(1);
   }
   return PQA_OK;
 }
@@ -1845,14 +1772,12 @@ int pqa_set_dis_history(pqa_ctx* c, const void* prev_dis_luma_host, int64_t row_
   int rc = flush_pending(c);
   if (rc != PQA_OK) return rc;
   if (!prev_dis_luma_host) {   // a chain start of the distorted clip
-    c->st_armed[0] = false;
-    c->st_hist_idx[0] = -1;
+    c->st_chain[0].restart();
     return PQA_OK;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy2D(c->st_hist[0], c->st_hist_pitch, prev_dis_luma_host, row_stride, (size_t)c->pw[0] * c->esize,
-                        c->ph[0], hipMemcpyHostToDevice));
-  c->st_armed[0] = true;
+  HIPCHK(c, hist_arm(c, c->st_hist[0], prev_dis_luma_host, row_stride, 0));
+  c->st_chain[0].arm(1);
   return PQA_OK;
 }
 
@@ -1877,15 +1802,12 @@ int pqa_set_dis_history_planes(pqa_ctx* c, const void* const planes[3], const in
   int rc = flush_pending(c);
   if (rc != PQA_OK) return rc;
   if (!planes) {   // a chain start
-    c->ig_armed = false;
-    c->ig_hist_idx = -1;
+    c->ig_chain.restart();
     return PQA_OK;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int p = 0; p < c->n_planes; ++p)
-    HIPCHK(c, hipMemcpy2D(c->ig_hist[p], c->ig_hist_pitch[p], planes[p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
-                          hipMemcpyHostToDevice));
-  c->ig_armed = true;
+  for (int p = 0; p < c->n_planes; ++p) HIPCHK(c, hist_arm(c, c->ig_hist[p], planes[p], strides[p], p));
+  c->ig_chain.arm(1);
   return PQA_OK;
 }
 
@@ -2023,16 +1945,7 @@ int pqa_reset(pqa_ctx* c) {
   c->done_seq = c->batch_seq;
   c->ring.reset();
   c->pending = 0;
-  c->have_last = false;
-  c->halo_armed = false;
-  c->last_index = -1;
-  c->xp_armed = -1;
-  c->xp_last = -1;
-  c->xp_hist_idx[0] = c->xp_hist_idx[1] = -1;
-  c->st_armed[0] = c->st_armed[1] = false;
-  c->st_hist_idx[0] = c->st_hist_idx[1] = -1;
-  c->ig_armed = false;
-  c->ig_hist_idx = -1;
+  for (host::FrameChain* ch : {&c->mo_chain, &c->xp_chain, &c->st_chain[0], &c->st_chain[1], &c->ig_chain}) ch->restart();
   c->started = false;
   c->err.clear();
   return PQA_OK;

@@ -1,6 +1,7 @@
 // The context behind the C ABI and what its three host units share: pqa_api.hip (context lifetime, the submit paths, collect,
 // profiling), pqa_side.hip (the one-shot analyses that leave the scoring chain alone) and pqa_debug.hip (the pqa_debug_*
-// entries).  Private to the library: callers see include/pqa_vmaf.h only.
+// entries).  Private to the library: callers see include/pqa_vmaf.h only.  What needs no device lives in headers of its own:
+// host_pack.h, host_ring.h, host_stage.h, host_chain.h (these four tests/host_harness.cpp drives on the CPU) and host_packed.h.
 #pragma once
 #include "../../include/pqa_vmaf.h"
 
@@ -11,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_chain.h"
 #include "host_pack.h"
 #include "host_ring.h"
 #include "host_packed.h"
@@ -24,6 +26,12 @@ struct Level {
   int64_t pitch = 0, frame_pitch = 0;  // elements (float)
   float* ref = nullptr;
   float* dis = nullptr;
+};
+
+// A plane a feature keeps on the device in front of the next batch; which frame it holds: the host::FrameChain beside it.
+struct HistPlane {
+  uint8_t* base = nullptr;
+  int64_t pitch = 0;  // bytes
 };
 
 struct Half {
@@ -131,30 +139,23 @@ struct pqa_ctx {
   pqa::XpsnrGeometry xp_geo{};
   unsigned long long* xp_blk = nullptr;   // [B][xp_geo.n_blk][kXpBlockVals]
   double* xp_w = nullptr;                 // [B][xp_geo.n_blk] weights
-  uint8_t* xp_hist[2] = {nullptr, nullptr};   // reference luma planes the chain keeps (the last two of the last batch)
-  int64_t xp_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
-  int64_t xp_hist_pitch = 0;                  // bytes
+  pqa::HistPlane xp_hist[2];              // reference luma planes the chain keeps (the last two of the last batch)
+  pqa::host::FrameChain xp_chain{2};      // ... and which frames they are; pqa_set_ref_history arms them
   uint8_t* xp_prev = nullptr;        // pqa_submit_surfaces: its shifted prev_ref (allocated on first use)
-  int64_t xp_last = -1;              // last frame of the previous batch (the chain continues at xp_last + 1)
-  int xp_armed = -1;                 // pqa_set_ref_history: planes armed in xp_hist[0..n) for the next batch (-1: none)
   // SI / TI (PQA_FEAT_SITI; siti.hip): nothing is allocated unless the bit is set
   double* ext4 = nullptr;            // [capacity][PQA_EXT4_DOUBLES] ring beside `records`
   double* st_part = nullptr;         // [B][2][siti_partials][4]
-  uint8_t* st_hist[2] = {nullptr, nullptr};   // the last luma plane of each clip's chain (0: distorted, 1: reference)
-  int64_t st_hist_idx[2] = {-1, -1};          // their frame indices (-1: empty)
-  int64_t st_hist_pitch = 0;                  // bytes
-  bool st_armed[2] = {false, false};          // pqa_set_dis_history / the reference history armed st_hist[z] as frame first-1
+  pqa::HistPlane st_hist[2];              // the last luma plane of each clip's chain (0: distorted, 1: reference)
+  pqa::host::FrameChain st_chain[2];      // pqa_set_dis_history / the reference history arm them
   // capture integrity (PQA_FEAT_INTEGRITY; integrity.hip): nothing is allocated unless the bit is set
   double* ext5 = nullptr;            // [capacity][PQA_EXT5_DOUBLES] ring beside `records`
   unsigned long long* ig_part = nullptr;      // [B][3][kIntegrityBlocks][2]
-  uint8_t* ig_hist[3] = {nullptr, nullptr, nullptr};   // the planes of the last distorted frame of the chain
-  int64_t ig_hist_pitch[3] = {0, 0, 0};       // bytes
-  int64_t ig_hist_idx = -1;                   // its frame index (-1: empty)
-  bool ig_armed = false;                      // pqa_set_dis_history_planes armed ig_hist as frame first-1
+  pqa::HistPlane ig_hist[3];              // the planes of the last distorted frame of the chain
+  pqa::host::FrameChain ig_chain;         // one index for the three; pqa_set_dis_history_planes arms them
   uint32_t black_thr = 0;                     // pqa_set_black_threshold
   bool started = false;                       // a batch was launched since pqa_create / pqa_reset
   // pqa_frame_sad / pqa_frame_sad_device (allocated on first use)
-  uint8_t* ig_anchor[3] = {nullptr, nullptr, nullptr};  // the anchor frame's planes (pitches: ig_hist_pitch)
+  uint8_t* ig_anchor[3] = {nullptr, nullptr, nullptr};  // the anchor frame's planes (pitches: those of ig_hist)
   uint8_t* ig_stage = nullptr;                // FB frames of host planes (slot layout: ig_stage_off, ig_stage_bytes)
   size_t ig_stage_off[3] = {0, 0, 0}, ig_stage_bytes = 0;
   unsigned long long* ig_out = nullptr;       // [B][3] results of one launch
@@ -175,11 +176,9 @@ struct pqa_ctx {
   size_t side_pin_cap[2] = {0, 0};
   void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use
   size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes
-  // motion continuity
-  uint8_t* last_luma = nullptr;
-  int64_t last_luma_pitch = 0;  // bytes
-  int64_t last_index = -1;
-  bool have_last = false, halo_armed = false;
+  // motion continuity: the last reference luma of the chain; pqa_set_motion_halo / pqa_set_ref_history arm it
+  pqa::HistPlane mo_hist;
+  pqa::host::FrameChain mo_chain;
   // host staging (pqa_submit path)
   pqa::Half half[2];
   int cur_half = 0, pending = 0;

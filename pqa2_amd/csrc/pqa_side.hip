@@ -582,11 +582,11 @@ int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t 
     size_t off = 0;
     for (int p = 0; p < c->n_planes; ++p) {
       c->ig_stage_off[p] = off;
-      off += (size_t)round_up(c->ig_hist_pitch[p] * c->ph[p], 256);
+      off += (size_t)round_up(c->ig_hist[p].pitch * c->ph[p], 256);
     }
     c->ig_stage_bytes = off;
     for (int p = 0; p < c->n_planes; ++p) {
-      const int rc = dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist_pitch[p] * c->ph[p]);
+      const int rc = dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist[p].pitch * c->ph[p]);
       if (rc != PQA_OK) return rc;
     }
     const int rc = dev_alloc(c, &c->ig_stage, off * (size_t)FB);
@@ -594,23 +594,24 @@ int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t 
   }
   // plain synchronous copies from the caller's (pageable) planes: this call is rare and short, it is not pipelined
   for (int p = 0; p < c->n_planes; ++p)
-    HIPCHK(c, hipMemcpy2D(c->ig_anchor[p], c->ig_hist_pitch[p], anchor_planes[p], anchor_strides[p], (size_t)c->pw[p] * c->esize,
+    HIPCHK(c, hipMemcpy2D(c->ig_anchor[p], c->ig_hist[p].pitch, anchor_planes[p], anchor_strides[p], (size_t)c->pw[p] * c->esize,
                           c->ph[p], hipMemcpyHostToDevice));
   const void* anchor[3] = {c->ig_anchor[0], c->ig_anchor[1], c->ig_anchor[2]};
+  const int64_t anchor_pitch[3] = {c->ig_hist[0].pitch, c->ig_hist[1].pitch, c->ig_hist[2].pitch};
   for (int done = 0; done < n_frames;) {
     if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
     const int n = chunk_len(n_frames, done, FB);
     pqa_device_clip f{};
     for (int p = 0; p < c->n_planes; ++p) {
       for (int k = 0; k < n; ++k)
-        HIPCHK(c, hipMemcpy2D(c->ig_stage + (size_t)k * c->ig_stage_bytes + c->ig_stage_off[p], c->ig_hist_pitch[p],
+        HIPCHK(c, hipMemcpy2D(c->ig_stage + (size_t)k * c->ig_stage_bytes + c->ig_stage_off[p], c->ig_hist[p].pitch,
                               frames[(size_t)(done + k) * 3 + p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
                               hipMemcpyHostToDevice));
       f.plane[p] = c->ig_stage + c->ig_stage_off[p];
-      f.row_pitch[p] = c->ig_hist_pitch[p];
+      f.row_pitch[p] = c->ig_hist[p].pitch;
       f.frame_pitch[p] = (int64_t)c->ig_stage_bytes;
     }
-    const int rc = frame_sad_launch(c, anchor, c->ig_hist_pitch, &f, n, out + (size_t)done * 3);
+    const int rc = frame_sad_launch(c, anchor, anchor_pitch, &f, n, out + (size_t)done * 3);
     if (rc != PQA_OK) return rc;
     done += n;
   }

@@ -1,9 +1,12 @@
-// CPU harness for the library's device-free host code (pqa2_amd/csrc/host_pack.h, host_ring.h, host_stage.h): built with
+// CPU harness for the library's device-free host code (pqa2_amd/csrc/host_pack.h, host_ring.h, host_stage.h, host_chain.h): built with
 // -fsanitize=thread and with -fsanitize=address,undefined by tests/test_host_sanitizers.py and driven through the call
 // sequences the GPU tests put the real library through (tests/test_gpu_configs.py PQA_ESTATE cases, the truncated-file cases
 // of tests/test_gpu_engine.py, a cancel flag raised from another thread; the pair staging of the side analyses against fake
 // device buffers of exactly the reserved sizes, as tests/test_gpu_pair_entries.py and the chunk tests of the six analyses put
-// it).  Memory / race safety, and for the pair staging which frames a launch sees: no parity claim.
+// it; the frame histories of motion, xpsnr, siti and the integrity SAD through the shard, reset and split-call sequences of
+// tests/test_gpu_xpsnr.py, test_gpu_siti.py and test_gpu_integrity.py, and a random walk beside the four state machines the
+// one type replaced).  Memory / race safety, for the pair staging which frames a launch sees, for the histories which frame a
+// batch reads as its predecessor: no parity claim.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "../pqa2_amd/csrc/host_chain.h"
 #include "../pqa2_amd/csrc/host_pack.h"
 #include "../pqa2_amd/csrc/host_ring.h"
 #include "../pqa2_amd/csrc/host_stage.h"
@@ -307,6 +311,221 @@ static void stage_scenarios() {
     }
 }
 
+// ---- the frame histories (host_chain.h) ------------------------------------------------------------------------------------
+// A history plane is modelled by the frame number last copied into it.  Planes the caller arms hold a token until the next
+// batch says which frames they are.
+constexpr int64_t kNoFrame = -1000, kArmToken = -100;   // nothing read / never written; armed plane j holds kArmToken - j
+
+// A chain as pqa_api.hip drives it: begin and the lookups of a step, end and its keep copies.
+struct ChainSim {
+  FrameChain ch;
+  bool takes_prev;
+  int64_t plane[2] = {kNoFrame, kNoFrame};
+  int64_t read[2] = {kNoFrame, kNoFrame};   // what the last batch read as frames first-1, first-2
+  FrameChain::Copy cp[FrameChain::kMaxDepth];
+  int n_cp = 0;
+  ChainSim(int depth, bool prev) : ch(depth), takes_prev(prev) {}
+  void arm(int n) {
+    for (int j = 0; j < n; ++j) plane[j] = kArmToken - j;
+    ch.arm(n);
+  }
+  void batch(int64_t first, int n, bool prev) {
+    ch.begin(first);
+    for (int j = 0; j < 2; ++j) {
+      const int slot = ch.find(first - 1 - j);
+      read[j] = j == 0 && prev && takes_prev ? first - 1 : slot >= 0 ? plane[slot] : kNoFrame;
+    }
+    n_cp = ch.end(first, n, prev && takes_prev, cp);
+    for (int i = 0; i < n_cp; ++i) {
+      CHECK(cp[i].slot >= 0 && cp[i].slot < 2 && (cp[i].src == FrameChain::kFromPrev ? prev : cp[i].src >= 0 && cp[i].src < n));
+      plane[cp[i].slot] = cp[i].src == FrameChain::kFromPrev ? first - 1 : first + cp[i].src;
+    }
+  }
+  bool copies(std::initializer_list<std::pair<int, int>> want) const {
+    int i = 0;
+    for (const auto& w : want)
+      if (i >= n_cp || cp[i].slot != w.first || cp[i++].src != w.second) return false;
+    return i == n_cp;
+  }
+};
+
+// The four state machines as pqa_api.hip spelled them before FrameChain, variable by variable: motion, xpsnr, siti (z = 0 the
+// distorted clip, which takes no caller's plane; z = 1 the reference), integrity.
+struct OldChains {
+  int64_t last_luma = kNoFrame, last_index = -1;
+  bool have_last = false, halo_armed = false;
+  int64_t xp_hist[2] = {kNoFrame, kNoFrame}, xp_hist_idx[2] = {-1, -1}, xp_last = -1;
+  int xp_armed = -1;
+  int64_t st_hist[2] = {kNoFrame, kNoFrame}, st_hist_idx[2] = {-1, -1};
+  bool st_armed[2] = {false, false};
+  int64_t ig_hist = kNoFrame, ig_hist_idx = -1;
+  bool ig_armed = false;
+  int64_t read[5][2];   // per feature (motion, xpsnr, siti z = 0, siti z = 1, integrity): frames first-1, first-2 as read
+
+  void restart() {   // pqa_reset; the n_prev == 0 / NULL branches of the setters clear the same variables, feature by feature
+    have_last = halo_armed = false; last_index = -1;
+    xp_armed = -1; xp_last = -1; xp_hist_idx[0] = xp_hist_idx[1] = -1;
+    st_armed[0] = st_armed[1] = false; st_hist_idx[0] = st_hist_idx[1] = -1;
+    ig_armed = false; ig_hist_idx = -1;
+  }
+  void arm(int n_prev) {   // set_history, pqa_set_dis_history and pqa_set_dis_history_planes in one
+    last_luma = kArmToken; halo_armed = true;
+    for (int j = 0; j < n_prev; ++j) xp_hist[j] = kArmToken - j;
+    xp_armed = n_prev;
+    for (int z = 0; z < 2; ++z) { st_hist[z] = kArmToken; st_armed[z] = true; }
+    ig_hist = kArmToken; ig_armed = true;
+  }
+  void batch(int64_t first, int n, bool prev) {
+    for (auto& r : read) r[0] = r[1] = kNoFrame;
+    // motion
+    if (prev) read[0][0] = first - 1;
+    else if (halo_armed || (have_last && last_index == first - 1)) read[0][0] = last_luma;
+    // xpsnr
+    if (xp_armed >= 0) {
+      xp_hist_idx[0] = xp_armed >= 1 ? first - 1 : -1;
+      xp_hist_idx[1] = xp_armed >= 2 ? first - 2 : -1;
+      xp_armed = -1;
+    } else if (xp_last != first - 1) {
+      xp_hist_idx[0] = xp_hist_idx[1] = -1;
+    }
+    const auto held = [&](int64_t idx) { return idx < 0 ? -1 : xp_hist_idx[0] == idx ? 0 : xp_hist_idx[1] == idx ? 1 : -1; };
+    const int xp_h1 = held(first - 1), j2 = held(first - 2);
+    if (prev) read[1][0] = first - 1;
+    else if (xp_h1 >= 0) read[1][0] = xp_hist[xp_h1];
+    if (j2 >= 0) read[1][1] = xp_hist[j2];
+    // siti
+    for (int z = 0; z < 2; ++z) {
+      if (st_armed[z]) { st_hist_idx[z] = first - 1; st_armed[z] = false; }
+      if (st_hist_idx[z] >= 0 && st_hist_idx[z] == first - 1) read[2 + z][0] = st_hist[z];
+    }
+    if (prev) read[3][0] = first - 1;
+    // integrity
+    if (ig_armed) { ig_hist_idx = first - 1; ig_armed = false; }
+    if (ig_hist_idx >= 0 && ig_hist_idx == first - 1) read[4][0] = ig_hist;
+    // the keep copies at the end of the batch
+    last_luma = first + n - 1; have_last = true; halo_armed = false; last_index = first + n - 1;
+    const auto keep = [&](int slot, int64_t frame) { xp_hist_idx[slot] = frame; xp_hist[slot] = frame; };
+    if (n >= 2) {
+      keep(0, first + n - 2);
+      keep(1, first + n - 1);
+    } else if (n == 1) {
+      int older = xp_h1;
+      if (older < 0 && prev) { older = 0; keep(0, first - 1); }
+      const int slot = older == 0 ? 1 : 0;
+      if (older < 0) xp_hist_idx[1] = -1;
+      keep(slot, first);
+    }
+    xp_last = first + n - 1;
+    for (int z = 0; z < 2; ++z) st_hist[z] = st_hist_idx[z] = first + n - 1;
+    ig_hist = ig_hist_idx = first + n - 1;
+  }
+};
+
+static void chain_scenarios() {
+  {   // a shard that starts at frame 5 with two armed planes, in batches of two (tests/test_gpu_xpsnr.py); then with one
+    ChainSim x(2, true);
+    x.arm(2);
+    x.batch(5, 2, false);
+    CHECK(x.read[0] == kArmToken && x.read[1] == kArmToken - 1 && x.copies({{0, 0}, {1, 1}}));
+    x.batch(7, 2, false);
+    CHECK(x.read[0] == 6 && x.read[1] == 5);
+    x.ch.restart();
+    x.arm(1);
+    x.batch(5, 2, false);
+    CHECK(x.read[0] == kArmToken && x.read[1] == kNoFrame);
+  }
+  for (int depth : {1, 2}) {   // arm, then restart (NULL / n_prev = 0): a chain start; a reset in the middle of a chain likewise
+    ChainSim x(depth, false);
+    x.arm(1);
+    x.ch.restart();
+    x.batch(5, 1, false);
+    CHECK(x.read[0] == kNoFrame && x.read[1] == kNoFrame);
+    x.batch(6, 3, false);
+    CHECK(x.read[0] == 5 && x.read[1] == kNoFrame);
+    x.ch.restart();
+    x.batch(9, 2, false);
+    CHECK(x.read[0] == kNoFrame && x.read[1] == kNoFrame);
+  }
+  {   // one-frame batches, the first with a caller's plane: it goes to slot 0, the frame to slot 1, then the slots alternate
+    ChainSim x(2, true);
+    x.batch(3, 1, true);
+    CHECK(x.read[0] == 2 && x.read[1] == kNoFrame && x.copies({{0, FrameChain::kFromPrev}, {1, 0}}));
+    x.batch(4, 1, false);
+    CHECK(x.read[0] == 3 && x.read[1] == 2 && x.copies({{0, 0}}));
+    x.batch(5, 1, true);   // the kept frame 4 stays where it is although the caller gave it again
+    CHECK(x.read[0] == 4 && x.read[1] == 3 && x.copies({{1, 0}}));
+    // without one: the older slot is left empty
+    ChainSim y(2, true);
+    y.batch(3, 1, false);
+    CHECK(y.read[0] == kNoFrame && y.read[1] == kNoFrame && y.copies({{0, 0}}) && y.ch.find(3) == 0 && y.ch.find(2) == -1);
+    y.batch(4, 1, false);
+    CHECK(y.read[0] == 3 && y.read[1] == kNoFrame && y.copies({{1, 0}}));
+    // a chain that takes no caller's plane (siti's distorted clip, integrity) does not see it
+    ChainSim z(1, false);
+    z.batch(3, 1, true);
+    CHECK(z.read[0] == kNoFrame && z.copies({{0, 0}}));
+  }
+  for (int depth : {1, 2}) {   // frames 0..2, then 7..8 with no reset and nothing armed: a chain start; 9 continues it
+    ChainSim x(depth, true);
+    x.batch(0, 2, false);
+    CHECK(x.read[0] == kNoFrame && x.read[1] == kNoFrame && x.ch.find(-1) == -1);
+    x.batch(2, 1, false);
+    CHECK(x.read[0] == 1 && x.read[1] == (depth == 2 ? 0 : kNoFrame));
+    x.batch(7, 2, false);
+    CHECK(x.read[0] == kNoFrame && x.read[1] == kNoFrame);
+    x.batch(9, 1, false);
+    CHECK(x.read[0] == 8 && x.read[1] == (depth == 2 ? 7 : kNoFrame));
+  }
+  // a random walk over arm / restart / batch: the five chains of a context beside the parent's variables.  After every batch
+  // both read the same planes as frames first-1 and first-2, and those are the right frames or none.  (A plane armed in front
+  // of frame 0 would be frame -1, which no chain holds; the walk does not arm there.)
+  for (unsigned seed : {1u, 2u, 3u}) {
+    std::mt19937 rng(seed);
+    ChainSim sims[5] = {{1, true}, {2, true}, {1, false}, {1, true}, {1, false}};
+    OldChains old;
+    int armed = -1;              // planes armed since the last batch or restart (-1: none)
+    int64_t last = -1;           // last frame of the previous batch (-1: a chain start)
+    bool have2[5] = {};          // frame last-1 is there for the next batch (depth 2)
+    for (int step = 0; step < 4000; ++step) {
+      const unsigned what = rng() % 8;
+      if (what == 0) {
+        const int n = 1 + (int)(rng() % 2);
+        for (auto& s : sims) s.arm(n);
+        old.arm(n);
+        armed = n;
+      } else if (what == 1) {
+        for (auto& s : sims) s.ch.restart();
+        old.restart();
+        armed = -1; last = -1;
+      } else {
+        const bool jump = last < 0 || rng() % 4 == 0;
+        int64_t first = jump ? (int64_t)(rng() % 40) : last + 1;
+        if (armed >= 0 && first < 2) first = 2;
+        const int n = 1 + (int)(rng() % 4);
+        const bool prev = first >= 1 && rng() % 3 == 0;
+        const bool continues = armed < 0 && last >= 0 && last == first - 1;
+        // the armed planes are frames first-1, first-2 of this batch
+        const auto label = [&](int64_t& p) { if (armed >= 0 && p <= kArmToken && p > kArmToken - armed) p = first - 1 - (kArmToken - p); };
+        for (auto& s : sims) { label(s.plane[0]); label(s.plane[1]); }
+        label(old.last_luma); label(old.xp_hist[0]); label(old.xp_hist[1]); label(old.st_hist[0]); label(old.st_hist[1]); label(old.ig_hist);
+        old.batch(first, n, prev);
+        for (int i = 0; i < 5; ++i) {
+          ChainSim& s = sims[i];
+          s.batch(first, n, prev);
+          const bool two = i == 1;
+          const int64_t want1 = (prev && s.takes_prev) || armed >= 1 || continues ? first - 1 : kNoFrame;
+          const int64_t want2 = two && (armed >= 2 || (continues && have2[i])) ? first - 2 : kNoFrame;
+          CHECK(s.read[0] == want1 && s.read[1] == want2);
+          CHECK(old.read[i][0] == want1 && old.read[i][1] == want2);
+          have2[i] = n >= 2 || want1 != kNoFrame;
+        }
+        armed = -1;
+        last = first + n - 1;
+      }
+    }
+  }
+}
+
 // proof that the sanitizer under which this binary was built is alive: a real data race / a real heap overflow, on request
 static int g_plain = 0;
 static void selftest(const char* what) {
@@ -326,6 +545,7 @@ int main(int argc, char** argv) {
   if (argc > 2 && !strcmp(argv[1], "--selftest")) { selftest(argv[2]); return 0; }
   const char* dir = argc > 1 ? argv[1] : "/tmp";
   ring_scenarios();
+  chain_scenarios();
   stage_scenarios();
   pack_scenarios(dir);
   printf("host harness ok\n");

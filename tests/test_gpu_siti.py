@@ -315,6 +315,23 @@ def test_reset_and_null_history_restart_the_chains():
     assert (first[0, [1, 3]] == 0.0).all() and first[0, 0] == base[2, 0] and first[0, 2] == base[2, 2]
     assert again[0, 1] == base[3, 1] and again[0, 3] == base[3, 3]
     assert again[1, 1] == 0.0 and again[1, 3] > 0.0
+    # a jump in the frame index with no reset and nothing armed (frames 0..2, then 7..8) starts every chain -- motion, xpsnr,
+    # siti and the integrity differences -- exactly as a fresh context does
+    refs, diss = _frames(w, h, bpc, 1, 1, 5, seed=22)
+    feats = N.FEAT_VMAF | N.FEAT_XPSNR | N.FEAT_SITI | N.FEAT_INTEGRITY
+    with FeatureEngine(w, h, bit_depth=bpc, n_planes=3, features=feats, max_batch=2) as eng:
+        for i in range(3):
+            eng.submit(i, refs[i], diss[i])
+        for i in (3, 4):
+            eng.submit(i + 4, refs[i], diss[i])
+        jumped = eng.collect_ext5(7, 2)
+    with FeatureEngine(w, h, bit_depth=bpc, n_planes=3, features=feats, max_batch=2) as eng:
+        for i in (3, 4):
+            eng.submit(i - 3, refs[i], diss[i])
+        fresh = eng.collect_ext5(0, 2)
+    for j in (0, 3, 4, 5):
+        assert np.array_equal(_bits(jumped[j]), _bits(fresh[j])), j
+    assert fresh[0][0, N.REC_MOTION] == 0.0 and fresh[4][0, N.EXT4_TI] == 0.0 and np.isnan(fresh[5][0, :3]).all()
 
 
 def test_other_outputs_unchanged_and_nan_without_the_bit():

@@ -1,9 +1,10 @@
 """ThreadSanitizer and AddressSanitizer + UBSan over the library's own host code (SURVEY section 5 "race detection /
 sanitizers").  The device-free parts of the submit path (csrc/pqa_api.hip; the context: csrc/pqa_ctx.h) -- the pack pool that preads frames into staging
-(pqa2_amd/csrc/host_pack.h) and the record-ring bookkeeping (host_ring.h) -- are headers of their own; tests/host_harness.cpp
+(pqa2_amd/csrc/host_pack.h), the record-ring bookkeeping (host_ring.h) and the frame histories in front of a batch
+(host_chain.h) -- are headers of their own; tests/host_harness.cpp
 drives them on the CPU through the call sequences the GPU tests use (memory and file sources, runs of frames with in-order
 hand-over, a truncated file, a failing upload callback, a cancel flag from another thread, the PQA_ESTATE sequences, ring
-wrap).  GPU AddressSanitizer is not available on this pool, so this is where the host code gets its sanitizer coverage.
+wrap, armed / kept / restarted histories and a random walk of them beside the state machines they replaced).  GPU AddressSanitizer is not available on this pool, so this is where the host code gets its sanitizer coverage.
 Memory / race safety only -- nothing here is a parity claim."""
 import os
 import shutil
