@@ -628,6 +628,52 @@ PQA_API int pqa_unpack_device(pqa_ctx* ctx, const pqa_unpack_spec* spec, const v
 PQA_API int pqa_unpack(pqa_ctx* ctx, const pqa_unpack_spec* spec, const void* const* src_frames, int64_t src_row_stride,
                        int32_t n_frames, void* const* dst_planes, const int64_t dst_strides[3]);
 
+/* Pixel-format conversion, synchronously: n_frames planes of ONE kind (luma, or a chroma plane) change their chroma layout,
+ * chroma siting and sample depth in one pass with one rounding -- what scoring a 4:2:2 capture (uyvy422, yuyv422, v210) against
+ * a yuv420p master needs first, where ffmpeg would insert swscale.  The plane belongs to a frame of luma_width x luma_height
+ * (each 1 ... 8192).  A layout is (hshift, vshift), each 0 ... 2 (the nine the library accepts); a luma plane is 0, 0 -> 0, 0.
+ * A plane has ceil(luma >> shift) samples along an axis.  Siting per axis and side: PQA_SITE_COSITED or PQA_SITE_CENTRE,
+ * ignored where the shift is 0.  src_bits, dst_bits: 8, 10 or 12; samples are u8 at 8 bit, otherwise little-endian u16; a
+ * source sample above 2^src_bits - 1 is read as 2^src_bits - 1.
+ * Per axis, positions in HALF luma samples, F = 1 << shift: sample k of a plane sits at P(k) = 2 F k + (centre ? F - 1 : 0);
+ * W = max(F_src, F_dst); destination sample i takes every source sample j with the weight w = 2 W - |P_src(j) - P_dst(i)| where
+ * that is positive (a triangle of half-width W luma samples), j folded onto clamp(j, 0, n_src - 1) (edge replication).  The
+ * weights of a destination sample sum to S = 2 W^2 / F_src, a power of two of at most 32, over at most 8 taps.  4:2:2 -> 4:2:0
+ * vertically centred: [1 3 3 1] / 8 at rows 2i - 1 ... 2i + 2, co-sited [1 2 1] / 4; 4:2:0 centred -> 4:2:2: [3 1] / 4 and
+ * [1 3] / 4 alternating; identity [2] / 2.  Both axes share one rounding, which carries the depth change:
+ *     acc = sum_y sum_x w_y w_x s (at most 1024 * 4095, int32), t = log2(S_x S_y), d = dst_bits - src_bits,
+ *     t > d: out = min((acc + 2^(t-d-1)) >> (t - d), 2^dst_bits - 1); otherwise out = acc << (d - t).
+ * Identity returns the source; a constant plane c becomes c << d (d < 0: min((c + 2^(-d-1)) >> -d, max)); a plane linear in
+ * the luma position stays linear in the interior; 10 -> 8 bit of 1023 gives 255.  Triangle and rounding are this library's
+ * own, not swscale's; the distance to swscale is not pinned.  PQA_CONVERT_GENERIC in flags: the general kernel whatever the
+ * layout (the test partner of the fast paths; the same integers).
+ * Any context, no feature bit, no record, no profile id; sizes and sample formats are the call's own, independent of the
+ * context's and of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL, before any device
+ * call, on a null pointer, a bad struct_size, unknown flag bits, a bad depth, shift or site value, a size outside 1 ... 8192,
+ * a negative frame count, a row pitch below a row or, in device memory, a base or pitch that is no multiple of the sample
+ * size.  n_frames == 0 succeeds and writes nothing.  No source row is read beyond its samples and no destination byte beyond
+ * a row's samples is written.  Kernel and fast paths: DESIGN.md section 5.
+ *
+ * pqa_format_convert: frames in HOST memory (src_frames[f] / dst_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 through the pinned buffers of pqa_resample and device buffers
+ * of this entry's own, grow-only and freed with the context.
+ * pqa_format_convert_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device; the converted planes can go straight into pqa_submit_device. */
+enum { PQA_SITE_COSITED = 0, PQA_SITE_CENTRE = 1 };
+enum { PQA_CONVERT_GENERIC = 1 }; /* flags: the general path whatever the layout (test partner; same integers) */
+typedef struct pqa_convert_spec {
+  uint32_t struct_size, flags;
+  uint32_t src_bits, dst_bits;                            /* 8, 10, 12 */
+  uint32_t luma_width, luma_height;                       /* of the frame the plane belongs to, 1 ... 8192 */
+  uint8_t src_hshift, src_vshift, dst_hshift, dst_vshift; /* 0 ... 2 */
+  uint8_t src_hsite, src_vsite, dst_hsite, dst_vsite;     /* PQA_SITE_* */
+} pqa_convert_spec;
+PQA_API int pqa_format_convert(pqa_ctx* ctx, const pqa_convert_spec* spec, const void* const* src_frames, int64_t src_row_stride,
+                               void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames);
+PQA_API int pqa_format_convert_device(pqa_ctx* ctx, const pqa_convert_spec* spec, const void* src, int64_t src_row_pitch,
+                                      int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
+                                      int32_t n_frames);
+
 /* Sub-pixel registration: the tile-wise gradient moments of n_frames frame pairs of one plane, synchronously -- the
  * Lucas-Kanade normal equations of every tile, from which pqa2_amd/align.py (solve_geometry, register) estimates a sub-pixel
  * shift and a scale factor per axis and drives the source window of pqa_resample.  Planes of width x height samples (the

@@ -565,5 +565,22 @@ hipError_t launch_edge_profiles(hipStream_t stream, Elem elem, int bits, const v
                                 int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                 int n_frames, int w, int h, unsigned long long* out);
 
-}  // namespace pqa
+// ---- pixel-format conversion: chroma layout, siting and depth in one pass (format_convert.hip) ----------------------------------
+// n_frames planes of one kind of a luma_w x luma_h frame (1 ... 8192 each way) go from the layout `src` to the layout `dst`:
+// chroma shifts 0 ... 2, siting per axis (kSiteCosited / kSiteCentre, void where the shift is 0), samples of 8 / 10 / 12 bits
+// (u8 at 8 bit, otherwise u16; a source sample above 2^bits - 1 is read as that).  Definition (triangle taps in exact integers,
+// one rounding that carries the depth change): the head of format_convert.hip.  Frame f at base + f * frame_pitch, pitches in
+// BYTES.  generic: the general kernel whatever the layout (the fast paths' test partner; the same integers).  Reads no source
+// sample outside the plane, writes no byte outside the samples of a destination row.  hipErrorInvalidValue, before any launch,
+// on a layout or size out of range, more than 65535 frames, a side that is not made of whole samples or a pitch below a row.
+constexpr int kSiteCosited = 0, kSiteCentre = 1;   // the PQA_SITE_* values
+constexpr int kConvertChunk = 8;                   // frames per chunk of the host entry
+struct ConvertLayout {
+  int bits, hshift, vshift, hsite, vsite;
+};
+inline int convert_plane_size(int luma, int shift) { return (luma + (1 << shift) - 1) >> shift; }
+hipError_t launch_format_convert(hipStream_t stream, const ConvertLayout& src, const ConvertLayout& dst, int luma_w, int luma_h,
+                                 bool generic, const void* src_planes, int64_t src_row_pitch, int64_t src_frame_pitch, void* dst_planes,
+                                 int64_t dst_row_pitch, int64_t dst_frame_pitch, int n_frames);
 
+}  // namespace pqa

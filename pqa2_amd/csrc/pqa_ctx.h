@@ -66,6 +66,7 @@ enum SideBuf {
   SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums
   SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles
   SIDE_UNPACK_SRC, SIDE_UNPACK_DST,                                            // pqa_unpack, unpack.hip: a chunk of uploaded packed frames / of unpacked planes
+  SIDE_CONVERT_SRC, SIDE_CONVERT_DST,                                          // pqa_format_convert, format_convert.hip: a chunk of uploaded / of converted planes
   kSideBufs
 };
 

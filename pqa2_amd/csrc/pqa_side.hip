@@ -256,6 +256,11 @@ int rs_tables(pqa_ctx* c, const pqa_resample_spec* sp, int* slot) {
 // The argument rules, in the order in which they fire (no device call): null spec, struct_size, `rule` (the entry's own, on
 // its third field), plane size, negative count, null clips, null out.  dis: the second clip, or the first again when there
 // is only one; `out` may be null below out_from frames.
+// the two sizes that spec_check holds against 1 ... 8192: the plane's, or (pqa_convert_spec) the luma frame's
+template <class Spec>
+void spec_sizes(const Spec* sp, uint32_t out[2]) { out[0] = sp->width; out[1] = sp->height; }
+void spec_sizes(const pqa_convert_spec* sp, uint32_t out[2]) { out[0] = sp->luma_width; out[1] = sp->luma_height; }
+
 template <class Spec, class Rule>
 int spec_check(pqa_ctx* c, const char* who, const Spec* sp, uint32_t min_size, const void* ref, const void* dis, int32_t n_frames,
                const void* out, int out_from, Rule rule) {
@@ -264,7 +269,9 @@ int spec_check(pqa_ctx* c, const char* who, const Spec* sp, uint32_t min_size, c
   if (sp->struct_size != sizeof(Spec)) return fail(c, PQA_EINVAL, "%s: bad struct_size %u", who, sp->struct_size);
   const int rc = rule();
   if (rc != PQA_OK) return rc;
-  for (uint32_t v : {sp->width, sp->height})
+  uint32_t sizes[2];
+  spec_sizes(sp, sizes);
+  for (uint32_t v : sizes)
     if (v < min_size || v > 8192) return fail(c, PQA_EINVAL, "%s: plane size %u outside %u ... 8192", who, v, min_size);
   if (n_frames < 0) return fail(c, PQA_EINVAL, "%s: negative frame count", who);
   if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "%s: null clip pointer", who);
@@ -1082,6 +1089,95 @@ int pqa_unpack(pqa_ctx* c, const pqa_unpack_spec* spec, const void* const* src_f
     rc = side_finish(c, "unpack", e, c->side_pin[1], c->side_buf[SIDE_UNPACK_DST], D.frame_bytes * n);
     if (rc != PQA_OK) return rc;
     host::unpack_clip_out(c->side_pin[1], D, dst_planes, dst_strides, f0, n);
+  }
+  return PQA_OK;
+}
+
+// ---- pixel-format conversion (format_convert.hip) ---------------------------------------------------------------------------
+
+namespace {
+// The argument rules both entries share, in spec_check's order (no device call).
+int convert_check(pqa_ctx* c, const pqa_convert_spec* sp, const void* src, const void* dst, int32_t n_frames) {
+  return spec_check(c, "format_convert", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (sp->flags & ~(uint32_t)PQA_CONVERT_GENERIC) return fail(c, PQA_EINVAL, "format_convert: unknown flag bits %#x", sp->flags);
+    for (uint32_t b : {sp->src_bits, sp->dst_bits})
+      if (b != 8 && b != 10 && b != 12) return fail(c, PQA_EINVAL, "format_convert: bit depth %u is not 8, 10 or 12", b);
+    for (uint8_t s : {sp->src_hshift, sp->src_vshift, sp->dst_hshift, sp->dst_vshift})
+      if (s > 2) return fail(c, PQA_EINVAL, "format_convert: chroma shift %u outside 0 ... 2", (unsigned)s);
+    for (uint8_t s : {sp->src_hsite, sp->src_vsite, sp->dst_hsite, sp->dst_vsite})
+      if (s != PQA_SITE_COSITED && s != PQA_SITE_CENTRE) return fail(c, PQA_EINVAL, "format_convert: siting %u is not PQA_SITE_COSITED or _CENTRE", (unsigned)s);
+    return (int)PQA_OK;
+  });
+}
+ConvertLayout convert_side(const pqa_convert_spec* sp, bool dst) {
+  return dst ? ConvertLayout{(int)sp->dst_bits, sp->dst_hshift, sp->dst_vshift, sp->dst_hsite, sp->dst_vsite}
+             : ConvertLayout{(int)sp->src_bits, sp->src_hshift, sp->src_vshift, sp->src_hsite, sp->src_vsite};
+}
+}  // namespace
+
+int pqa_format_convert_device(pqa_ctx* c, const pqa_convert_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
+                              void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
+  int rc = convert_check(c, spec, src, dst, n_frames);
+  if (rc != PQA_OK) return rc;
+  const ConvertLayout S = convert_side(spec, false), D = convert_side(spec, true);
+  const int ses = S.bits > 8 ? 2 : 1, des = D.bits > 8 ? 2 : 1;
+  const int64_t src_row = (int64_t)convert_plane_size((int)spec->luma_width, S.hshift) * ses;
+  const int64_t dst_row = (int64_t)convert_plane_size((int)spec->luma_width, D.hshift) * des;
+  if (((uintptr_t)src | (uintptr_t)src_row_pitch | (uintptr_t)src_frame_pitch) & (uintptr_t)(ses - 1))
+    return fail(c, PQA_EINVAL, "format_convert: source base or pitch is not a multiple of the sample size");
+  if (((uintptr_t)dst | (uintptr_t)dst_row_pitch | (uintptr_t)dst_frame_pitch) & (uintptr_t)(des - 1))
+    return fail(c, PQA_EINVAL, "format_convert: destination base or pitch is not a multiple of the sample size");
+  if (src_row_pitch < src_row) return fail(c, PQA_EINVAL, "format_convert: source pitch smaller than a row");
+  if (dst_row_pitch < dst_row) return fail(c, PQA_EINVAL, "format_convert: destination pitch smaller than a row");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipError_t e = hipSuccess;
+  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid)
+    e = launch_format_convert(c->stream, S, D, (int)spec->luma_width, (int)spec->luma_height, (spec->flags & PQA_CONVERT_GENERIC) != 0,
+                              (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch,
+                              (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch, dst_frame_pitch, chunk_len(n_frames, f0, kGrid));
+  return side_finish(c, "format_convert", e, nullptr, nullptr, 0);
+}
+
+int pqa_format_convert(pqa_ctx* c, const pqa_convert_spec* spec, const void* const* src_frames, int64_t src_row_stride,
+                       void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames) {
+  int rc = convert_check(c, spec, src_frames, dst_frames, n_frames);
+  if (rc != PQA_OK) return rc;
+  const ConvertLayout SL = convert_side(spec, false), DL = convert_side(spec, true);
+  const int lw = (int)spec->luma_width, lh = (int)spec->luma_height;
+  const size_t src_row = (size_t)convert_plane_size(lw, SL.hshift) * (SL.bits > 8 ? 2 : 1);
+  const size_t dst_row = (size_t)convert_plane_size(lw, DL.hshift) * (DL.bits > 8 ? 2 : 1);
+  const int sh = convert_plane_size(lh, SL.vshift), dh = convert_plane_size(lh, DL.vshift);
+  rc = check_host_frames(c, "format_convert: ", "source ", src_frames, 1, n_frames, src_row_stride, src_row, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "format_convert: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, dst_row, true);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // As pqa_unpack: chunks of kConvertChunk planes out through the first pinned chunk of the side analyses and back through the
+  // second, device buffers of this entry's own, all grow-only, in the packed layout of host_stage.h (rows 16 bytes apart at
+  // least, so the fast paths apply); a chunk is uploaded, converted, downloaded and copied out before the next.
+  const host::PlaneLayout S = host::plane_layout(src_row, sh), D = host::plane_layout(dst_row, dh);
+  const int chunk = n_frames < kConvertChunk ? n_frames : kConvertChunk;
+  rc = side_pin_reserve(c, 0, S.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, D.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_CONVERT_SRC, S.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_CONVERT_DST, D.frame_bytes * chunk);
+  if (rc != PQA_OK) return rc;
+  for (int f0 = 0; f0 < n_frames; f0 += kConvertChunk) {
+    const int n = chunk_len(n_frames, f0, kConvertChunk);
+    host::pack_planes(c->side_pin[0], S, src_frames + f0, src_row_stride, n);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_CONVERT_SRC], c->side_pin[0], S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_format_convert(c->stream, SL, DL, lw, lh, (spec->flags & PQA_CONVERT_GENERIC) != 0, c->side_buf[SIDE_CONVERT_SRC], S.pitch,
+                                (int64_t)S.frame_bytes, c->side_buf[SIDE_CONVERT_DST], D.pitch, (int64_t)D.frame_bytes, n);
+    rc = side_finish(c, "format_convert", e, c->side_pin[1], c->side_buf[SIDE_CONVERT_DST], D.frame_bytes * n);
+    if (rc != PQA_OK) return rc;
+    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
+      for (int y = 0; y < dh; ++y)
+        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * D.frame_bytes + (size_t)y * D.pitch, dst_row);
   }
   return PQA_OK;
 }

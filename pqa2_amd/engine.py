@@ -322,6 +322,59 @@ class FeatureEngine:
         self._check(self.lib.pqa_unpack_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch, int(n_frames),
                                                C.byref(d)))
 
+    # -- pixel-format conversion ---------------------------------------------------------------
+    @staticmethod
+    def _convert_spec(luma_shape, src, dst, generic: bool):
+        """the pqa_convert_spec of planes of a luma_shape = (height, width) frame; src / dst = (hshift, vshift, hsite, vsite, bits)"""
+        sp = N.PqaConvertSpec()
+        sp.struct_size, sp.flags = C.sizeof(N.PqaConvertSpec), N.CONVERT_GENERIC if generic else 0
+        sp.luma_width, sp.luma_height = max(0, int(luma_shape[1])), max(0, int(luma_shape[0]))
+        # a value the library must refuse still has to fit its field
+        sp.src_hshift, sp.src_vshift, sp.src_hsite, sp.src_vsite = (int(v) & 0xFF for v in src[:4])
+        sp.dst_hshift, sp.dst_vshift, sp.dst_hsite, sp.dst_vsite = (int(v) & 0xFF for v in dst[:4])
+        sp.src_bits, sp.dst_bits = max(0, int(src[4])), max(0, int(dst[4]))
+        return sp
+
+    @staticmethod
+    def convert_plane_shape(luma_shape, hshift: int, vshift: int):
+        """(rows, samples a row) of a plane of chroma shifts (hshift, vshift) in a frame of luma_shape = (height, width)"""
+        return -(-int(luma_shape[0]) >> vshift), -(-int(luma_shape[1]) >> hshift)
+
+    def format_convert(self, frames, luma_shape, src, dst, generic: bool = False):
+        """A list of 2-D arrays: every plane of `frames` (planes of ONE kind, of a frame of luma_shape = (height, width), in HOST
+        memory) converted from the layout src = (hshift, vshift, hsite, vsite, bits) to dst = (...) in one pass with one
+        rounding (pqa_format_convert; definition: include/pqa_vmaf.h).  Shifts 0 ... 2, sitings N.SITE_COSITED / N.SITE_CENTRE
+        (void where the shift is 0), bits 8 / 10 / 12 (uint8 at 8 bit, else uint16).  A luma plane is (0, 0, *, *, bits) on both
+        sides: a depth change only.  generic: the general kernel whatever the layout (the same integers).  Sizes and sample
+        formats are the call's own, not this context's."""
+        sp = self._convert_spec(luma_shape, src, dst, generic)
+        sdt = np.uint8 if int(src[4]) <= 8 else np.dtype("<u2")
+        ddt = np.uint8 if int(dst[4]) <= 8 else np.dtype("<u2")
+        arrs = [np.asarray(f) for f in frames]
+        if any(a.ndim != 2 or a.dtype != sdt or a.strides[1] != a.itemsize or a.strides[0] < 0 or a.strides[0] != arrs[0].strides[0]
+               for a in arrs):
+            arrs = [np.ascontiguousarray(a, dtype=sdt) for a in arrs]
+        src_shape = self.convert_plane_shape(luma_shape, int(src[0]) & 3, int(src[1]) & 3)
+        if any(a.ndim != 2 or a.shape != src_shape for a in arrs):
+            raise ValueError(f"format_convert needs 2-D planes of {src_shape[0]} x {src_shape[1]} samples")
+        dst_shape = self.convert_plane_shape(luma_shape, int(dst[0]) & 3, int(dst[1]) & 3)
+        out = [np.empty(dst_shape, ddt) for _ in arrs]
+        sptr, dptr = (C.c_void_p * max(len(arrs), 1))(), (C.c_void_p * max(len(arrs), 1))()
+        for i, (a, o) in enumerate(zip(arrs, out)):
+            sptr[i], dptr[i] = a.ctypes.data, o.ctypes.data
+        self._check(self.lib.pqa_format_convert(self._ctx, C.byref(sp), sptr,
+                                                arrs[0].strides[0] if arrs else src_shape[1] * np.dtype(sdt).itemsize, dptr,
+                                                dst_shape[1] * np.dtype(ddt).itemsize, len(arrs)))
+        return out
+
+    def format_convert_resident(self, luma_shape, src, dst, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, dst_ptr: int,
+                                dst_row_pitch: int, dst_frame_pitch: int, n_frames: int, generic: bool = False):
+        """The same for planes in HBM (device pointers, pitches in bytes; pqa_format_convert_device): n_frames planes at
+        src_ptr become the planes at dst_ptr.  Nothing crosses PCIe; the result can go into submit_resident."""
+        sp = self._convert_spec(luma_shape, src, dst, generic)
+        self._check(self.lib.pqa_format_convert_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch,
+                                                       dst_ptr or None, dst_row_pitch, dst_frame_pitch, int(n_frames)))
+
     def _host_clip(self, side, keep):
         """the pqa_host_clip of one side of submit_packed: (frames, format name or None)"""
         frames, fmt = side

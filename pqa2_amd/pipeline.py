@@ -43,7 +43,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 spectrum_gain_floor: float = 0.5, temporal: int = 0, temporal_planes: str = "y", temporal_min_mse: float = 1.0,
                 temporal_blend_min: float = 1 / 16, temporal_still_mse: float = 0.25,
                 temporal_pop_factor: float = 4, coding_grid: bool = False, grid_planes: str = "y", grid_periods=(4, 64),
-                grid_z2: float = 25.0, chroma_mismatch: str = "error") -> ScoreResult | None:
+                grid_z2: float = 25.0, chroma_mismatch: str = "error", chroma_siting: str | None = None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -185,16 +185,26 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     records).  `chroma_mismatch`: "error" (default) refuses clips that differ in pixel format; "luma" accepts clips that differ
     ONLY in chroma subsampling (a 4:2:2 capture against a 4:2:0 master) and scores both as luma-only clips -- VMAF and luma
     PSNR / SSIM, the chroma keys absent as for a monochrome Y4M; a bit-depth difference stays an error, and chroma is not
-    converted between layouts.  Then, or when a packed file is read, the result carries `input` = {"reference": pix_fmt,
-    "distorted": pix_fmt, "planes_scored": "y" | "yuv", "packed_upload": bool}."""
+    converted between layouts.  "convert": when the clips differ in chroma layout OR bit depth (8 / 10 / 12), the DISTORTED clip --
+    the side ffmpeg would convert for libvmaf -- is converted on the GPU to the reference's layout, siting and depth, all three
+    planes (FeatureEngine.format_convert: one pass, one rounding; triangle taps of this library's own, not swscale's), before
+    `resize` and every alignment step, and all three planes are scored; a monochrome clip against a colour clip stays an error.
+    The siting of each clip follows its header (yuvio.VideoInfo.chroma_siting); `chroma_siting` = "left" (co-sited
+    horizontally, centred vertically), "center" (centred both ways) or "topleft" (co-sited both ways) overrides BOTH clips'
+    on their subsampled axes.  Under "convert" a packed file is read through the numpy unpack (`packed_upload` false).  Then,
+    under "luma", or when a packed file is read, the result carries `input` = {"reference": pix_fmt, "distorted": pix_fmt,
+    "planes_scored": "y" | "yuv", "packed_upload": bool}; a conversion adds "conversion": {"side": "distorted", "from": pix_fmt,
+    "to": pix_fmt, "bit_depth": [from, to], "siting": {"from": [h, v], "to": [h, v]}}."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
     ref_rd = open_video(reference_path, **raw_kwargs)
     dis_rd = open_video(distorted_path, **raw_kwargs)
     ri, di = ref_rd.info, dis_rd.info
-    if chroma_mismatch not in ("error", "luma"):
-        raise ValueError('chroma_mismatch must be "error" or "luma"')
+    if chroma_mismatch not in ("error", "luma", "convert"):
+        raise ValueError('chroma_mismatch must be "error" or "luma" or "convert"')
+    if chroma_siting is not None and chroma_siting not in CHROMA_SITINGS:
+        raise ValueError('chroma_siting must be None, "left", "center" or "topleft"')
     input_info = None
     if ri.packed or di.packed:
         input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False}
@@ -203,6 +213,17 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "y", "packed_upload": False}
         ref_rd, dis_rd = _LumaReader(ref_rd), _LumaReader(dis_rd)
         ri, di = ref_rd.info, dis_rd.info
+    converter = None
+    if (chroma_mismatch == "convert" and ri.mono == di.mono and not ri.mono
+            and ri.bit_depth in N.CONVERT_BIT_DEPTHS and di.bit_depth in N.CONVERT_BIT_DEPTHS
+            and (ri.hshift, ri.vshift, ri.bit_depth) != (di.hshift, di.vshift, di.bit_depth)):
+        dis_rd = converter = _ConvertedReader(dis_rd, ri, chroma_siting, device,
+                                              engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+        input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "yuv", "packed_upload": False,
+                      "conversion": {"side": "distorted", "from": di.pix_fmt, "to": converter.info.pix_fmt,
+                                     "bit_depth": [di.bit_depth, ri.bit_depth],
+                                     "siting": {"from": list(converter.src_siting), "to": list(converter.dst_siting)}}}
+        di = dis_rd.info
     if resize is not None and resize not in N.RESAMPLE_FILTERS:
         raise ValueError(f"resize must be None or one of {sorted(N.RESAMPLE_FILTERS)}")
     if resize is None and (ri.width, ri.height) != (di.width, di.height):
@@ -465,7 +486,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
     ext5 = shard.gather_records(local_ext5, n, world_size, rank, gather_device, width=N.EXT5_DOUBLES) if integrity else None
     if rank != 0:
-        for rd in (resampler, registered, coloured):
+        for rd in (converter, resampler, registered, coloured):
             if rd is not None:
                 rd.close()
         return None
@@ -528,7 +549,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["resize"] = resized
     if input_info is not None:
         res["input"] = input_info
-    for rd in (resampler, registered, coloured):   # on an error their contexts go with the readers
+    for rd in (converter, resampler, registered, coloured):   # on an error their contexts go with the readers
         if rd is not None:
             rd.close()
     return res
@@ -565,6 +586,54 @@ class _ResampledReader:
             frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
             planes = [self._eng.resample([f[p] for f in frames], shape, self._filter) for p, shape in enumerate(self._shapes)]
             self._first, self._run = first, [[planes[p][k] for p in range(len(self._shapes))] for k in range(len(frames))]
+        return self._run[i - self._first]
+
+
+CHROMA_SITINGS = {"left": (0, 1), "center": (1, 1), "topleft": (0, 0)}   # chroma_siting= -> (hsite, vsite)
+
+
+class _ConvertedReader:
+    """A captured clip in the reference's pixel format -- chroma layout, chroma siting and bit depth --: what score_files reads
+    under chroma_mismatch="convert".  Built like _ResampledReader: a small context of its own, frames fetched in runs of
+    eight, one FeatureEngine.format_convert call per plane kind (the luma: a depth change only, skipped when the depths agree;
+    U and V in ONE call as 2n planes), the last run kept.  `info` carries the reference's shifts, depth and chroma tag.  A
+    packed capture file is read through its numpy unpack: its packed frames are not on offer.  No file-descriptor path.
+    close() frees the context."""
+    RUN = 8
+
+    def __init__(self, reader, ref_info, siting, device, make):
+        import dataclasses
+        src = reader.info
+        self._rd = reader
+        self.info = dataclasses.replace(src, bit_depth=ref_info.bit_depth, hshift=ref_info.hshift, vshift=ref_info.vshift,
+                                        chroma_tag=ref_info.chroma_tag, packed=None)
+        forced = CHROMA_SITINGS[siting] if siting is not None else None
+        self.src_siting, self.dst_siting = ([(s[0] if i.hshift else 0, s[1] if i.vshift else 0) for i, s in
+                                             ((src, forced or src.chroma_siting), (ref_info, forced or ref_info.chroma_siting))])
+        self._luma_shape = (src.height, src.width)
+        self._src = (src.hshift, src.vshift, *self.src_siting, src.bit_depth)
+        self._dst = (ref_info.hshift, ref_info.vshift, *self.dst_siting, ref_info.bit_depth)
+        self._eng = make(src.width, src.height, bit_depth=ref_info.bit_depth, n_planes=1, chroma_shift=(ref_info.hshift, ref_info.vshift),
+                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd)
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
+            n = len(frames)
+            if self._src[4] != self._dst[4]:
+                luma = self._eng.format_convert([f[0] for f in frames], self._luma_shape, (0, 0, 0, 0, self._src[4]), (0, 0, 0, 0, self._dst[4]))
+            else:
+                luma = [f[0] for f in frames]
+            chroma = self._eng.format_convert([f[1] for f in frames] + [f[2] for f in frames], self._luma_shape, self._src, self._dst)
+            self._first, self._run = first, [[luma[k], chroma[k], chroma[n + k]] for k in range(n)]
         return self._run[i - self._first]
 
 

@@ -186,9 +186,15 @@ def main(argv=None) -> int:
                          "this filter and crop both clips; the JSON's alignment object gets a geometry entry")
     ap.add_argument("--register-frames", type=int, default=8, metavar="N",
                     help="with --register: measure N frame pairs spread evenly over the clips (default 8)")
-    ap.add_argument("--chroma-mismatch", default="error", choices=["error", "luma"],
-                    help="clips that differ only in chroma subsampling (a 4:2:2 capture such as .uyvy / .v210 against a 4:2:0 "
-                         "master): refuse them (default) or score their luma only -- VMAF and luma PSNR / SSIM; the JSON gets a "
+    ap.add_argument("--chroma-siting", default=None, choices=["left", "center", "topleft"],
+                    help="with --chroma-mismatch convert: where both clips' subsampled chroma sits (left: co-sited horizontally, "
+                         "centred vertically, MPEG-2; center: centred both ways, JPEG; topleft: co-sited both ways) instead of "
+                         "what each file's header implies")
+    ap.add_argument("--chroma-mismatch", default="error", choices=["error", "luma", "convert"],
+                    help="clips that differ in chroma subsampling (a 4:2:2 capture such as .uyvy / .v210 against a 4:2:0 "
+                         "master): refuse them (default), score their luma only -- VMAF and luma PSNR / SSIM --, or convert the "
+                         "distorted clip on the GPU to the reference's chroma layout, siting and bit depth (8 / 10 / 12) and score "
+                         "all three planes; the JSON gets a "
                          "top-level input object.  Headerless packed files (.uyvy, .yuyv, .yuy2, .v210) take their frame size "
                          "from a _WxH name hint, as raw .yuv does")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -257,6 +263,7 @@ def main(argv=None) -> int:
                              if a.coding_grid else {}),
                           **({"resize": a.resize} if a.resize else {}),
                           **({"chroma_mismatch": a.chroma_mismatch} if a.chroma_mismatch != "error" else {}),
+                          **({"chroma_siting": a.chroma_siting} if a.chroma_siting else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects

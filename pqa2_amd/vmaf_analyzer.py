@@ -182,7 +182,11 @@ class VMAFAnalyzer(QObject):
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
                                               # scale and undo them with this filter (pipeline.score_files(register=))
         self.chroma_mismatch = "error"        # "luma": clips that differ only in chroma subsampling (a 4:2:2 capture against a
-                                              # 4:2:0 master) are scored on their luma (pipeline.score_files(chroma_mismatch=))
+                                              # 4:2:0 master) are scored on their luma (pipeline.score_files(chroma_mismatch=));
+                                              # "convert": the distorted clip is converted on the GPU to the reference's chroma
+                                              # layout, siting and bit depth, and all three planes are scored
+        self.chroma_siting = None             # "left" / "center" / "topleft": with "convert", the siting of both clips' chroma
+                                              # instead of what the files imply (pipeline.score_files(chroma_siting=))
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -533,7 +537,8 @@ class VMAFAnalyzer(QObject):
                 **({"coding_grid": True} if self.coding_grid_enabled else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {}),
-                **({"chroma_mismatch": self.chroma_mismatch} if self.chroma_mismatch != "error" else {})}
+                **({"chroma_mismatch": self.chroma_mismatch} if self.chroma_mismatch != "error" else {}),
+                **({"chroma_siting": self.chroma_siting} if self.chroma_siting else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -596,6 +601,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--register", str(self.register_filter)]
         if self.chroma_mismatch != "error":
             cmd += ["--chroma-mismatch", str(self.chroma_mismatch)]
+        if self.chroma_siting:
+            cmd += ["--chroma-siting", str(self.chroma_siting)]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:

@@ -78,6 +78,24 @@ class VideoInfo:
         return base
 
     @property
+    def chroma_siting(self):
+        """(hsite, vsite), 0 = co-sited with a luma sample, 1 = centred between luma samples, of the subsampled axes (an
+        axis that is not subsampled: 0), from `chroma_tag`: 420jpeg centre / centre; 420mpeg2, bare 420 and 420pNN co-sited
+        horizontally, centred vertically; 420paldv co-sited both ways (its Cb and Cr lines alternate, Cr a luma line above
+        Cb: that is NOT modelled, both planes count as co-sited); 4:2:2 (422*, the packed capture formats) co-sited
+        horizontally.  Layouts Y4M has no tag for follow the mpeg2 convention."""
+        if self.mono:
+            return (0, 0)
+        tag = self.chroma_tag or ""
+        if tag.startswith("420jpeg"):
+            site = (1, 1)
+        elif tag.startswith("420paldv"):
+            site = (0, 0)
+        else:
+            site = (0, 1)
+        return (site[0] if self.hshift else 0, site[1] if self.vshift else 0)
+
+    @property
     def fps(self) -> float:
         return self.fps_num / self.fps_den if self.fps_den else 0.0
 
