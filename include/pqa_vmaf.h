@@ -946,6 +946,12 @@ PQA_API int pqa_debug_vif_march_table(uint16_t* out, int32_t capacity_halfwords)
  * of the first pass.  bench.py prices `roofline.mfma` with it instead of mirroring the rule. */
 PQA_API int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* out6);
 
+/* Test / measurement hook: how the context runs VIF scale 1, 2 or 3 for a launch of n_frames frames, under the switches it
+ * read at pqa_create (PQA_VIF_STRIP, PQA_VIF_STRIP_SEG): out4 = {strips (tile columns), tile rows, tile rows per segment,
+ * segments per strip}.  A workgroup of the strip kernel marches down one segment of one strip; tile rows per segment = 0
+ * means the tiled kernel runs there (one workgroup per tile).  PQA_EINVAL on a null pointer, another scale or n_frames = 0. */
+PQA_API int pqa_debug_vif_strip_shape(pqa_ctx* ctx, uint32_t scale, uint32_t n_frames, int32_t* out4);
+
 /* Test hook (needs a device): the CIEDE2000 device function of the PQA_FEAT_CIEDE kernel on n Lab pairs
  * lab_pairs[n][6] = {L1, a1, b1, L2, a2, b2}: the inputs are converted to f32, de_out[n] receives the f32 results widened.
  * PQA_EDEVICE without a device (text in pqa_last_error(NULL)), PQA_EINVAL on a null pointer or n < 0. */

@@ -44,11 +44,18 @@ inline int vif_tiles_y(int h) { return (h + kVifTileH - 1) / kVifTileH; }
 // uniform: 1 = a wave whose pixels are all inside the image and all in the log branch (sigma1_sq >= sigma_nsq) takes the
 // statistic without its other branch (same bits); 0 = every wave takes the general statistic (PQA_VIF_UNIFORM=0, read in
 // pqa_create: the test partner).
+// strip_seg: scales 1-3 on f32 planes, the strip kernel (a workgroup marches down `segment` tile rows of one tile column; same
+// tiles, same partial slots, same bits): 0 = where vif_strip_shape's rule finds the launch large enough, n > 0 = segments of
+// n tile rows whatever the launch (PQA_VIF_STRIP_SEG: tests cross segment boundaries on small frames), < 0 = the tiled kernel
+// (PQA_VIF_STRIP=0, the test partner; or a scale outside PQA_VIF_STRIP's mask).
 enum : int { VIF_S0_VALU = 0, VIF_S0_AUTO = 1 };
 hipError_t launch_vif_stat(hipStream_t stream, int scale, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames,
                            int w, int h, float inv_scale, float gain_limit, int border101, double* partials,
                            MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode = VIF_S0_AUTO, int* n_partials = nullptr,
-                           int uniform = 1);
+                           int uniform = 1, int strip_seg = 0);
+// {strips (tile columns), tile rows, tile rows per segment, segments per strip} of a launch of n_frames w x h planes at `scale`
+// under strip_seg; segment 0 = the tiled kernel runs.  Host arithmetic only.
+void vif_strip_shape(int scale, int w, int h, int n_frames, int strip_seg, int* out4);
 // Scale 0 (8-, 10-, 12-bit clips: `bits`), both filter passes on the f16 matrix cores (vif_march.hip).  vif_march_prepare uploads its tap
 // table once per device (pqa_create does; synchronous, idempotent; a device that does not keep f16 denormals -- probed once,
 // the operand encoding leans on them -- gets no table and scale 0 stays on the VALU kernel); launch_vif_s0_march returns false when it cannot take

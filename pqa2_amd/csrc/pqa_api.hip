@@ -219,7 +219,8 @@ int run_vif(pqa_ctx* c, Batch& b) {
       ProfScope ps(c, k.s, b.sp_n, b.st);
       HIPCHK(c, launch_vif_stat(b.st, k.s, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h, c->inv_scale,
                                 (float)c->cfg.vif_enhn_gain_limit, c->cfg.vif_border == PQA_VIF_BORDER_INTEGER, c->vif_part[k.s],
-                                k.out.ref, k.out.dis, c->vif_s0_mode, &b.vif_np[k.s], c->vif_uniform));
+                                k.out.ref, k.out.dis, c->vif_s0_mode, &b.vif_np[k.s], c->vif_uniform,
+                                (c->vif_strip_mask >> k.s & 1) ? c->vif_strip_seg : -1));
     }
     // mode 2: the other chains start behind VIF scale 0 (the dominant launch runs alone, its figures stay its own) and
     // overlap VIF scales 1-3 only
@@ -1007,6 +1008,14 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->vif_s0_mode = (v && v[0] == '0') ? VIF_S0_VALU : VIF_S0_AUTO;
     const char* vu = getenv("PQA_VIF_UNIFORM");   // 0: every wave takes the general VIF statistic (test partner of the all-high fast path)
     c->vif_uniform = !(vu && vu[0] == '0');
+    // PQA_VIF_STRIP: 0 = vif_stat_kernel at every scale (the strip kernel's test partner); a number = the scales that may run
+    // the strip kernel as a bit mask (2: scale 1, 6: scales 1 and 2, 14: scales 1-3; per-scale A/B runs and the tests); default:
+    // scale 1, the one scale at which the strip kernel measured faster.
+    // PQA_VIF_STRIP_SEG=n: segments of n tile rows whatever the launch size (small test frames cross segment boundaries).
+    const char* vs = getenv("PQA_VIF_STRIP");
+    if (vs && vs[0]) c->vif_strip_mask = atoi(vs) & 0xe;
+    const char* vg = getenv("PQA_VIF_STRIP_SEG");
+    c->vif_strip_seg = vg ? std::max(0, atoi(vg)) : 0;
     const char* am = getenv("PQA_ADM_MARCH");  // 0: the LDS-tiled ADM kernel (A/B partner of the march kernel)
     const char* ap = getenv("PQA_ADM_PYRAMID");  // 0: the march kernel one scale per launch (test partner of the pyramid kernel)
     c->adm_mode = (am && am[0] == '0') ? ADM_TILED : (ap && ap[0] == '0') ? ADM_MARCH : ADM_AUTO;

@@ -218,7 +218,9 @@ struct pqa_ctx {
   int multi_stream = 0;              // 0 one stream; 1 three streams from the start of a batch; 2 three streams behind VIF scale 0
   int vif_s0_mode = pqa::VIF_S0_AUTO;   // PQA_VIF_MFMA, read once in pqa_create
   int vif_uniform = 1;                  // PQA_VIF_UNIFORM, read once in pqa_create: 0 = no all-high fast path in the VIF statistic
-  int adm_mode = pqa::ADM_AUTO;         // PQA_ADM_MARCH, read once in pqa_create
+  int vif_strip_mask = 0x2;             // PQA_VIF_STRIP, read once in pqa_create: bit s = scale s may run the strip kernel (0 = none; default: scale 1)
+  int vif_strip_seg = 0;                // PQA_VIF_STRIP_SEG, read once in pqa_create: tile rows per segment; 0 = vif_strip_shape's rule
+  int adm_mode = pqa::ADM_AUTO;        // PQA_ADM_MARCH, read once in pqa_create
   int motion_mode = pqa::MOTION_AUTO;   // PQA_MOTION_MARCH, read once in pqa_create
   bool trace = false;   // PQA_TRACE=1: synchronise after every launch and name it on stderr (localises a stall)
   bool prof = false;

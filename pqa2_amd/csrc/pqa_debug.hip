@@ -1,5 +1,5 @@
 // The pqa_debug_* entries of the C ABI: single kernels and host tables exposed to the tests, on the default stream with
-// scratch memory of their own (no context).  Declarations: include/pqa_vmaf.h.
+// scratch memory of their own (no context; pqa_debug_vif_strip_shape alone reads one's switches).  Declarations: include/pqa_vmaf.h.
 #include "pqa_ctx.h"
 
 using namespace pqa;
@@ -54,6 +54,19 @@ int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* out6) {
   int shape[6];
   vif_march_shape((int)width, (int)height, shape);
   for (int i = 0; i < 6; ++i) out6[i] = shape[i];
+  return PQA_OK;
+}
+
+int pqa_debug_vif_strip_shape(pqa_ctx* ctx, uint32_t scale, uint32_t n_frames, int32_t* out4) {
+  if (!ctx) return PQA_EINVAL;
+  if (!out4 || scale < 1 || scale > 3 || n_frames == 0 || n_frames > 65536)
+    return fail(ctx, PQA_EINVAL, "pqa_debug_vif_strip_shape: bad argument");
+  const Level& L = ctx->vif_lv[scale];
+  int shape[4];
+  // what run_vif passes to launch_vif_stat at this scale
+  const int strip_seg = ctx->vif_fixed ? -1 : (ctx->vif_strip_mask >> scale & 1) ? ctx->vif_strip_seg : -1;
+  vif_strip_shape((int)scale, L.w, L.h, (int)n_frames, strip_seg, shape);
+  for (int i = 0; i < 4; ++i) out4[i] = shape[i];
   return PQA_OK;
 }
 

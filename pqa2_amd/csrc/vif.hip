@@ -17,7 +17,9 @@
 //      stage (finalize.hip) keeps a frame's record independent of batch size and rank count.
 // HBM traffic: the two input planes once (halo re-reads hit L2) + the half-resolution planes written once.
 //
-// Which kernel runs where (launch_vif_stat at the bottom): scales 1-3: vif_stat_kernel (VALU);
+// Which kernel runs where (launch_vif_stat at the bottom): scales 1-3: vif_strip_kernel where the launch is large enough for
+// its segment rule (vif_strip_shape): the same tile, marched down a strip with the vertical window carried in registers;
+// vif_stat_kernel (VALU) otherwise, and as the strip kernel's test partner (PQA_VIF_STRIP=0);
 // scale 0 (8-, 10- and 12-bit clips): vif_s0_march_kernel in vif_march.hip (both filter passes on the f16 matrix cores), with
 // vif_stat_kernel as its test partner (PQA_VIF_MFMA=0) and its fallback (no tap table, next-scale planes whose pitches its
 // 16-byte stores cannot take).  The round-2 kernel that put only the vertical pass on the matrix cores left the build in
@@ -392,6 +394,210 @@ __global__ __launch_bounds__(kBlock, 3) void vif_stat_kernel(const VifStatArgs a
   vif_hstat<N, TW, ND>(a, &sv[0][0][0], &sd[0][0], red, fr, tile, x0, y0);
 }
 
+// ---- strip march (scales 1-3, f32 planes) --------------------------------------------------------
+// One input row of the vertical pass in scatter form: row j of the current tile's window (plane row y0 - R + j) goes to every
+// row pair it belongs to -- pair p of the current tile takes tap k = j - 2p, pair p of the tile below tap k - 8 -- and to the
+// fused decimation's even rows likewise.  j is a constant after unrolling; rows arrive in increasing order, so every pair sees
+// the FMAs of vif_stat_kernel in vif_stat_kernel's order (the zero halves at k = 0 and k = N included).
+template <int N, int ND>
+__device__ __forceinline__ void vif_strip_row(const TapPairs& taps, const int j, f2 x /* {ref, dis} */, f2 (&cur)[4][5],
+                                              f2 (&cd)[4], f2 (&nxt)[4][5], f2 (&nd)[4]) {
+  constexpr int R = N / 2, RD = ND / 2, S = kVifTileH;
+  // the sample pair as ONE 64-bit register, whatever the vectoriser would rather pair up: {r, r}, {d, d} and the products'
+  // broadcasts are then op_sel forms of v_pk_fma_f32; from lone 32-bit registers each broadcast costs two v_mov
+  asm volatile("" : "+v"(x));
+  const f2 xx = x * x;
+  const float r = x.x, d = x.y, rr = xx.x, dd = xx.y, rd = x.x * x.y;
+  if (ND) {
+#pragma unroll
+    for (int q = 0; q < S / 2; ++q) {
+      const int kd = j - (2 * q + R - RD);
+      if (kd >= 0 && kd < ND) cd[q] = __builtin_elementwise_fma(taps.dt[kd], x, cd[q]);
+      if (kd - S >= 0 && kd - S < ND) nd[q] = __builtin_elementwise_fma(taps.dt[kd - S], x, nd[q]);
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < S / 2; ++p) {
+    const int k = j - 2 * p;
+    if (k >= 0 && k <= N) {
+      const f2 c = taps.vt[k];
+      cur[p][0] = __builtin_elementwise_fma(c, f2{r, r}, cur[p][0]);
+      cur[p][1] = __builtin_elementwise_fma(c, f2{d, d}, cur[p][1]);
+      cur[p][2] = __builtin_elementwise_fma(c, f2{rr, rr}, cur[p][2]);
+      cur[p][3] = __builtin_elementwise_fma(c, f2{dd, dd}, cur[p][3]);
+      cur[p][4] = __builtin_elementwise_fma(c, f2{rd, rd}, cur[p][4]);
+    }
+    if (k - S >= 0 && k - S <= N) {
+      const f2 c = taps.vt[k - S];
+      nxt[p][0] = __builtin_elementwise_fma(c, f2{r, r}, nxt[p][0]);
+      nxt[p][1] = __builtin_elementwise_fma(c, f2{d, d}, nxt[p][1]);
+      nxt[p][2] = __builtin_elementwise_fma(c, f2{rr, rr}, nxt[p][2]);
+      nxt[p][3] = __builtin_elementwise_fma(c, f2{dd, dd}, nxt[p][3]);
+      nxt[p][4] = __builtin_elementwise_fma(c, f2{rd, rd}, nxt[p][4]);
+    }
+  }
+}
+
+// One step of the march: the 8 new rows of the window (j = N - 1 ... N + 6) complete the current tile's accumulators and start
+// those of the tile below.
+template <int N, int ND>
+__device__ __forceinline__ void vif_strip_rows(const TapPairs& taps, const f2 (&xc)[8], f2 (&cur)[4][5], f2 (&cd)[4],
+                                               f2 (&nxt)[4][5], f2 (&nd)[4]) {
+  constexpr int NRP = kVifTileH / 2;
+#pragma unroll
+  for (int p = 0; p < NRP; ++p) {
+#pragma unroll
+    for (int s = 0; s < 5; ++s) nxt[p][s] = f2{0.0f, 0.0f};
+    nd[p] = f2{0.0f, 0.0f};
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    vif_strip_row<N, ND>(taps, N - 1 + i, xc[i], cur, cd, nxt, nd);
+    if (i & 1) __builtin_amdgcn_sched_barrier(0);   // two rows' products live at a time, not all eight
+  }
+}
+
+// ... and the finished tile's accumulators go to LDS in vif_stat_kernel's layout.
+template <int ND>
+__device__ __forceinline__ void vif_strip_store(const f2 (&cur)[4][5], const f2 (&cd)[4], f2* sv, f2* sd, const int col) {
+  constexpr int NRP = kVifTileH / 2;
+#pragma unroll
+  for (int p = 0; p < NRP; ++p)
+#pragma unroll
+    for (int s = 0; s < 5; ++s) sv[(s * NRP + p) * kP2 + col] = cur[p][s];
+  if (ND) {
+#pragma unroll
+    for (int q = 0; q < NRP; ++q) sd[q * kP2 + col] = cd[q];
+  }
+}
+
+// The kernel's VifStatArgs, read again from the kernel-argument segment (it is the first argument: offset 0).  The march keeps
+// 60-odd scalar registers of state of its own; with all 48 tap registers resident beside them through the whole loop -- where
+// loop-invariant loads end up -- the compiler spills scalars into lanes of a VGPR and fetches them back one v_readlane at a
+// time, 70 VALU instructions a step.  Read through a pointer the optimiser cannot see through, the vertical taps are loaded
+// (scalar cache) before the vertical pass and the horizontal ones before vif_hstat, and neither outlives its pass.
+__device__ __forceinline__ const VifStatArgs& vif_strip_kernargs() {
+  auto p = __builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const VifStatArgs*)p;
+}
+
+// A workgroup owns one tile column (a strip) and seg_len consecutive tile rows of one frame and marches down them 8 output
+// rows per step.  A step loads only the 8 rows that are new to the window (the first step's N - 1 rows above them are the
+// prologue), forms x, x*x, r*d of a row once, and hands the rows the tile below shares to that tile's accumulators -- a second
+// register set; the two sets swap roles from step to step, so nothing is copied.  The loads of step t + 1 are issued before
+// step t's rows are consumed and fly under its FMAs, its horizontal pass and its statistic.  Everything behind the vertical
+// pass is vif_hstat, and a tile's partial lands in vif_stat_kernel's slot: the records are vif_stat_kernel's bit for bit,
+// whatever seg_len is (tests/test_gpu_vif_strip.py).
+template <int N, int TW, int ND>
+__global__ __launch_bounds__(kBlock, 3) void vif_strip_kernel(const VifStatArgs a, const int tiles_y, const int seg_len,
+                                                              const int n_segs) {
+  constexpr int R = N / 2, TH = kVifTileH, COLS = TW + N - 1, NSEG = TW / 4, S = 8;
+  static_assert(ND == 0 || ND / 2 <= R, "decimation window must sit inside the statistic window");
+  static_assert(COLS <= 256 && COLS <= kP2, "one column per thread");
+  static_assert(TW % 4 == 0 && NSEG <= 64 && TH == S, "segment map");
+  static_assert(N - 1 <= S, "the prologue fits one load group; a row feeds at most the tile below");
+  __shared__ f2 sv[5][TH / 2][kP2];
+  __shared__ f2 sd[ND ? TH / 2 : 1][ND ? kP2 : 1];
+  __shared__ double red[12];
+
+  const int wg = xcd_remap(blockIdx.x, a.tiles_x * n_segs);
+  const int tx = wg % a.tiles_x, sg = wg / a.tiles_x;
+  const int fr = blockIdx.y;
+  const int ty0 = sg * seg_len, ty1 = min(ty0 + seg_len, tiles_y);
+  const float* __restrict__ ref = (const float*)a.ref + (int64_t)fr * a.frame_pitch_r;
+  const float* __restrict__ dis = (const float*)a.dis + (int64_t)fr * a.frame_pitch_d;
+  const int x0 = tx * TW;
+  // thread <-> column.  (The threads past COLS -- two, at scale 3 -- march along on a mirrored column into LDS columns nobody
+  // reads, kP2 > 256: no divergent region, whose merges would keep the finished tile's registers alive across vif_hstat.)
+  const int col = threadIdx.x;
+
+  // formed once per segment: the lane's column offset, the row pitches and both descriptors
+  const unsigned gx = (unsigned)mirror_fold(x0 - R + col, a.w, a.fold_w);
+  const unsigned pitch_r = (unsigned)a.row_pitch_r, pitch_d = (unsigned)a.row_pitch_d;
+  const auto rsrc_r = make_rsrc(ref, (unsigned)a.h * pitch_r * (unsigned)sizeof(float));
+  const auto rsrc_d = make_rsrc(dis, (unsigned)a.h * pitch_d * (unsigned)sizeof(float));
+
+  f2 accA[S / 2][5], accB[S / 2][5], dA[S / 2], dB[S / 2];
+  f2 xn[S];   // the rows in flight, {ref, dis}: each load writes its half of the pair the vertical pass reads
+  // the 8 new rows of the tile at y0: plane rows y0 + R ... y0 + R + 7, each folded on the scalar unit.
+  // `more` = false (the segment's last step: nobody takes the rows) sends every lane past the end of the buffer instead of
+  // branching round the loads: such a load fetches nothing and returns 0, and the step stays one basic block -- with a
+  // branch in it the FMAs sink below the loads and the sample pairs cross the block boundary as lone registers.
+  auto issue = [&](const int y0, const bool more) __attribute__((always_inline)) {
+    const int ylo = y0 + R;
+    const unsigned gxs = more ? gx : 0x3fffffffu;
+    unsigned ro_r[S], ro_d[S];
+    // (the pitches as values of this step: as loop invariants their eight multiples each are hoisted out of the march, and with
+    // the taps resident the scalar registers do not hold them -- they come back lane by lane from a spill register)
+    unsigned sp_r = pitch_r, sp_d = pitch_d;
+    asm volatile("" : "+s"(sp_r), "+s"(sp_d));
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      const unsigned gy = (unsigned)mirror_fold(ylo + i, a.h, a.fold_h);   // as vif_stat_kernel folds it: same row, same sample
+      ro_r[i] = gy * sp_r; ro_d[i] = gy * sp_d;
+    }
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      xn[i].x = buf_load<float>(rsrc_r, gxs, ro_r[i]);
+      xn[i].y = buf_load<float>(rsrc_d, gxs, ro_d[i]);
+      // in the order the next step takes them: its waits then count down row by row, and the one that also covers this
+      // step's stores (vmcnt(0): the tile partial of wave 0 among them) comes with the last row, not with the first
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  {
+    // prologue: the N - 1 rows above the first step's, into the first tile's accumulators
+    f2 px[N - 1];
+#pragma unroll
+    for (int j = 0; j < N - 1; ++j) {
+      const unsigned gy = (unsigned)mirror_fold(ty0 * TH - R + j, a.h, a.fold_h);
+      px[j].x = buf_load<float>(rsrc_r, gx, gy * pitch_r);
+      px[j].y = buf_load<float>(rsrc_d, gx, gy * pitch_d);
+    }
+    issue(ty0 * TH, true);
+#pragma unroll
+    for (int p = 0; p < S / 2; ++p) {
+#pragma unroll
+      for (int s = 0; s < 5; ++s) accA[p][s] = accB[p][s] = f2{0.0f, 0.0f};
+      dA[p] = dB[p] = f2{0.0f, 0.0f};
+    }
+#pragma unroll
+    for (int j = 0; j < N - 1; ++j) vif_strip_row<N, ND>(a.taps, j, px[j], accA, dA, accB, dB);
+  }
+
+  auto step = [&](const int ty, f2 (&cur)[S / 2][5], f2 (&cd)[S / 2], f2 (&nxt)[S / 2][5], f2 (&nd)[S / 2]) __attribute__((always_inline)) {
+    vif_strip_rows<N, ND>(vif_strip_kernargs().taps, xn, cur, cd, nxt, nd);
+    // the next step's rows go into the registers this step's have left: in flight under the LDS hand-over and vif_hstat
+    issue((ty + 1) * TH, ty + 1 < ty1);
+    // LDS still holds the tile above until every wave is through its vif_hstat.  The wait stands here, behind this step's
+    // FMAs, not at the end of the step before: wave 0's tail (the block sum, the tile partial) then runs beside the other
+    // waves' vertical pass instead of holding them.
+    __syncthreads();
+    vif_strip_store<ND>(cur, cd, &sv[0][0][0], &sd[0][0], col);
+    __syncthreads();
+    // (likewise: what vif_hstat derives from the strip and the frame -- store bases, column predicates -- is formed per tile,
+    // as in vif_stat_kernel, not kept in scalar registers through the vertical pass)
+    int x0s = x0, frs = fr;
+    asm volatile("" : "+s"(x0s), "+s"(frs));
+    vif_hstat<N, TW, ND>(vif_strip_kernargs(), &sv[0][0][0], &sd[0][0], red, frs, ty * a.tiles_x + tx, x0s, ty * TH);
+  };
+  // two steps per trip: the register sets swap roles in the source, so only the set that is being filled for the tile below
+  // is live across vif_hstat (one step per trip with a branch on the step's parity keeps both alive and spills)
+  for (int ty = ty0; ty < ty1; ty += 2) {
+    step(ty, accA, dA, accB, dB);
+    if (ty + 1 >= ty1) break;
+    step(ty + 1, accB, dB, accA, dA);
+  }
+}
+
+template <int N, int TW, int ND>
+hipError_t launch_strip_n(hipStream_t stream, const VifStatArgs& a, int n_frames, const int (&shape)[4]) {
+  const dim3 grid(shape[0] * shape[3], n_frames), block(kBlock);
+  hipLaunchKernelGGL((vif_strip_kernel<N, TW, ND>), grid, block, 0, stream, a, shape[1], shape[2], shape[3]);
+  return hipGetLastError();
+}
 
 template <int N, int TW, int ND>
 hipError_t launch_stat_n(hipStream_t stream, Elem elem, const VifStatArgs& a, int n_frames) {
@@ -411,9 +617,33 @@ constexpr int kVifTW[4] = {240, 248, 252, 252};
 
 int vif_tile_w(int scale) { return kVifTW[scale]; }
 
+void vif_strip_shape(int scale, int w, int h, int n_frames, int strip_seg, int* out) {
+  const int strips = vif_tiles_x(scale, w), tiles_y = vif_tiles_y(h);
+  int seg = 0;
+  if (scale >= 1 && scale <= 3 && strip_seg > 0) {
+    seg = strip_seg < tiles_y ? strip_seg : tiles_y;
+  } else if (scale >= 1 && scale <= 3 && strip_seg == 0) {
+    // Two costs pull the segment length apart.  A segment's first tile forms the window rows above it again and its last
+    // step's hand-over goes to nobody (at scale 1 the prologue's FMAs are a sixth of a step's instructions); and a launch of
+    // few long workgroups ends with CUs idle (a round is 3 workgroups on each of 256 CUs, and the last workgroups run alone).
+    // Swept from 4 to 34 tile rows at 2160p (profiles/r27a_vif_strip_ab.txt), 9 was the fastest in both sweeps, 7 ... 14
+    // within 3 % of it.  So: evenly long segments of at most 9 tile rows, shorter where the launch would otherwise have fewer
+    // than eight rounds.  A launch too small for eight rounds of two-row segments keeps vif_stat_kernel.
+    constexpr int kSegRows = 9;
+    const double round = 3.0 * 256;
+    for (int s = tiles_y < kSegRows ? tiles_y : kSegRows; s >= 2 && !seg; --s) {
+      const int n = (tiles_y + s - 1) / s;
+      if ((tiles_y + n - 1) / n != s) continue;   // as many segments come evenly shorter
+      if ((double)strips * n * n_frames >= 8.0 * round) seg = s;
+    }
+  }
+  const int n_segs = seg ? (tiles_y + seg - 1) / seg : 0;
+  out[0] = strips; out[1] = tiles_y; out[2] = seg; out[3] = n_segs;
+}
+
 hipError_t launch_vif_stat(hipStream_t stream, int scale, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames,
                            int w, int h, float inv_scale, float gain_limit, int border101, double* partials,
-                           MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode, int* n_partials, int uniform) {
+                           MutPlaneRun next_ref, MutPlaneRun next_dis, int s0_mode, int* n_partials, int uniform, int strip_seg) {
   if (n_partials) *n_partials = vif_tiles_x(scale, w) * vif_tiles_y(h);
   if (n_frames <= 0) return hipSuccess;
   // (the bit depth of 16-bit elements is recognised by the sample scale: 1/4 = 10 bit, 1/16 = 12 bit)
@@ -442,6 +672,15 @@ hipError_t launch_vif_stat(hipStream_t stream, int scale, Elem elem, PlaneRun re
   const Taps nxt = scale < 3 ? gaussian_taps(kVifN[scale + 1]) : Taps{};
   a.taps = tap_pairs(cur, kVifN[scale], scale < 3 ? &nxt : nullptr, scale < 3 ? kVifN[scale + 1] : 0);
   if (scale < 3 && (!a.dst_ref || !a.dst_dis)) return hipErrorInvalidValue;
+  if (elem == ELEM_F32 && scale >= 1) {
+    int shape[4];
+    vif_strip_shape(scale, w, h, n_frames, strip_seg, shape);
+    if (shape[2]) switch (scale) {
+      case 1: return launch_strip_n<9, 248, 5>(stream, a, n_frames, shape);
+      case 2: return launch_strip_n<5, 252, 3>(stream, a, n_frames, shape);
+      case 3: return launch_strip_n<3, 252, 0>(stream, a, n_frames, shape);
+    }
+  }
   switch (scale) {
     case 0: return launch_stat_n<17, 240, 9>(stream, elem, a, n_frames);
     case 1: return launch_stat_n<9, 248, 5>(stream, elem, a, n_frames);
