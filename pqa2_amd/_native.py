@@ -47,6 +47,16 @@ EXT4_DOUBLES = 8
 # start / no such plane), the number of luma samples <= the black threshold
 EXT5_SAD_PREV, EXT5_BLACK_COUNT, EXT5_RESERVED = 0, 3, 4
 EXT5_DOUBLES = 8
+# the extension record blocks, in the order pqa_collect_ext5 takes them: (name, doubles per frame, the feature bits that own
+# it).  The one place on this side where a block is declared (pqa_ctx.h has the library's table); collect_blocks, score_files
+# and finish_records go by index into it.
+EXT_BLOCKS = (
+    ("ext", EXT_DOUBLES, FEAT_FLOAT_SSIM | FEAT_MS_SSIM | FEAT_CIEDE | FEAT_CAMBI),
+    ("ext2", EXT2_DOUBLES, FEAT_PSNR_HVS),
+    ("ext3", EXT3_DOUBLES, FEAT_XPSNR),
+    ("ext4", EXT4_DOUBLES, FEAT_SITI),
+    ("ext5", EXT5_DOUBLES, FEAT_INTEGRITY),
+)
 PSNR_HVS_TABLE_FLOATS = 384                  # pqa_debug_psnr_hvs_tables: CSF[3][8][8], then M[3][8][8]
 PROF_KERNELS = 17
 GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray

@@ -4,6 +4,7 @@
 #include "pqa_ctx.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -204,6 +205,46 @@ int walk_pyramid(const Level (&lv)[4], Scale first, Elem deep, Launch launch) {
   return PQA_OK;
 }
 
+// A history plane for plane p of a clip, rows padded to 64 bytes.
+int hist_alloc(pqa_ctx* c, HistPlane* hp, int p) {
+  hp->pitch = round_up((int64_t)c->pw[p] * c->esize, 64);
+  return dev_alloc(c, &hp->base, (size_t)hp->pitch * c->ph[p]);
+}
+
+// VIF pyramid (floor halving): f32 planes of scales 1-3, rows padded to 64 B, and the partials of every scale.
+int alloc_vif(pqa_ctx* c) {
+  const bool on = c->cfg.features & PQA_FEAT_VIF;
+  if (on && !c->vif_fixed) HIPCHK(c, vif_march_prepare());
+  if (c->vif_fixed) {
+    std::vector<uint16_t> lut(32768);
+    vif_fixed_log2_table(lut.data());
+    PQACHK(dev_alloc(c, &c->vif_lut, lut.size()));
+    HIPCHK(c, hipMemcpy(c->vif_lut, lut.data(), lut.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  int vw = c->pw[0], vh = c->ph[0];
+  for (int s = 0; s < 4; ++s) {
+    if (s > 0) {
+      vw /= 2; vh /= 2;
+      Level& V = c->vif_lv[s];
+      V.w = vw; V.h = vh; V.pitch = round_up(vw, 16); V.frame_pitch = V.pitch * vh;
+      if (on) {
+        PQACHK(dev_alloc(c, &V.ref, (size_t)V.frame_pitch * c->B));
+        PQACHK(dev_alloc(c, &V.dis, (size_t)V.frame_pitch * c->B));
+      }
+    }
+    if (vw < 2 || vh < 2) return fail(c, PQA_EINVAL, "frame too small for 4 VIF scales");
+    c->vif_tiles[s] = vif_tiles_x(s, vw) * vif_tiles_y(vh);
+    if (s == 0) {   // scale 0 may run the march kernel, which writes one partial pair per wave segment
+      const int mp = vif_march_partials_max(vw, vh);
+      c->vif_part_cap0 = c->vif_tiles[0] > mp ? c->vif_tiles[0] : mp;
+    }
+    if (on && !c->vif_fixed)
+      PQACHK(dev_alloc(c, &c->vif_part[s], (size_t)(s == 0 ? c->vif_part_cap0 : c->vif_tiles[s]) * 2 * c->B));
+    if (on && c->vif_fixed) PQACHK(dev_alloc(c, &c->vif_fx_part[s], (size_t)c->vif_tiles[s] * kVifFxPartials * c->B));
+  }
+  return PQA_OK;
+}
+
 int run_vif(pqa_ctx* c, Batch& b) {
   if (!(c->cfg.features & PQA_FEAT_VIF) || b.sp_n == 0) return PQA_OK;
   const Scale top{0, c->elem, RunPair{b.rs[0], b.ds[0]}, b.w, b.h, {}};
@@ -226,6 +267,44 @@ int run_vif(pqa_ctx* c, Batch& b) {
     // overlap VIF scales 1-3 only
     return k.s == 0 && b.fork_late ? fork_streams(c, b) : PQA_OK;
   });
+}
+
+// ADM approximation bands (ceil halving): f32 planes of scales 1-3, rows padded to 64 B, and the partials of every scale.
+int alloc_adm(pqa_ctx* c) {
+  const bool on = c->cfg.features & PQA_FEAT_ADM;
+  const int w = c->pw[0], h = c->ph[0], B = c->B;
+  if (c->adm_fixed) {
+    std::vector<int32_t> lut(65537);
+    adm_fixed_div_table(lut.data());
+    PQACHK(dev_alloc(c, &c->adm_div_lut, lut.size()));
+    HIPCHK(c, hipMemcpy(c->adm_div_lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    PQACHK(dev_alloc(c, &c->adm_fx_acc, (size_t)c->capacity * 24));
+    HIPCHK(c, hipMemsetAsync(c->adm_fx_acc, 0, (size_t)c->capacity * 24 * sizeof(long long), c->stream));
+  }
+  int aw = w, ah = h;
+  for (int s = 0; s < 4; ++s) {
+    if (s > 0) {
+      aw = (aw + 1) / 2; ah = (ah + 1) / 2;
+      Level& A = c->adm_lv[s];
+      A.w = aw; A.h = ah; A.pitch = round_up(aw, 16); A.frame_pitch = A.pitch * ah;
+      if (on) {
+        PQACHK(dev_alloc(c, &A.ref, (size_t)A.frame_pitch * B));
+        PQACHK(dev_alloc(c, &A.dis, (size_t)A.frame_pitch * B));
+      }
+    }
+    const int bw = (aw + 1) / 2, bh = (ah + 1) / 2;  // band size produced at ADM scale s
+    c->adm_tiles[s] = adm_tiles_x(bw) * adm_tiles_y(bh);
+    const int left = (int)(bw * 0.1 - 0.5), top = (int)(bh * 0.1 - 0.5);
+    c->adm_area[s] = (float)((bh - 2 * top) * (bw - 2 * left));
+    c->adm_fx[s] = adm_fixed_scale_params(s, bw, bh);
+    if (on && !c->adm_fixed) {   // one sextet per tile (adm.hip) or per wave segment (adm_march.hip)
+      int mp = adm_march_partials(bw, bh);
+      if (s < 2 && adm_pyramid_takes(c->elem, w, h)) { const int pp = adm_pyramid_partials(w, h); mp = pp > mp ? pp : mp; }
+      PQACHK(dev_alloc(c, &c->adm_part[s], (size_t)(c->adm_tiles[s] > mp ? c->adm_tiles[s] : mp) * 6 * B));
+    }
+    if (on && c->adm_fixed) PQACHK(dev_alloc(c, &c->adm_fx_part[s], (size_t)c->adm_tiles[s] * kAdmFxRows * 6 * B));
+  }
+  return PQA_OK;
 }
 
 int run_adm(pqa_ctx* c, Batch& b) {
@@ -259,10 +338,31 @@ int run_adm(pqa_ctx* c, Batch& b) {
   });
 }
 
+// The frame histories: the feature that reads one, its chain and planes ([slot][np]), the clip (distorted or reference), np.
+struct History { uint32_t feature; host::FrameChain* chain; const HistPlane* planes; bool dis; int np; };
+std::array<History, 5> histories(pqa_ctx* c) {
+  return {{{PQA_FEAT_MOTION, &c->mo_chain, &c->mo_hist, false, 1},
+           {PQA_FEAT_XPSNR, &c->xp_chain, c->xp_hist, false, 1},
+           {PQA_FEAT_SITI, &c->st_chain[0], &c->st_hist[0], true, 1},
+           {PQA_FEAT_SITI, &c->st_chain[1], &c->st_hist[1], false, 1},
+           {PQA_FEAT_INTEGRITY, &c->ig_chain, c->ig_hist, true, c->n_planes}}};
+}
+
 // Frame `frame` as a chain holds it (planes[slot]), or none.
 Pred held(const host::FrameChain& chain, const HistPlane* planes, int64_t frame, int es) {
   const int j = chain.find(frame);
   return j < 0 ? Pred{} : Pred{planes[j].base, planes[j].pitch / es};
+}
+
+// Motion: one partial per tile (motion.hip) or per wave segment (motion_march.hip), and the plane its chain keeps.
+int alloc_motion(pqa_ctx* c) {
+  const int w = c->pw[0], h = c->ph[0];
+  c->motion_tiles_n = motion_tiles(w, h);
+  if (!(c->cfg.features & PQA_FEAT_MOTION)) return PQA_OK;
+  const int mp = motion_march_partials(w, h);
+  PQACHK(dev_alloc(c, &c->motion_part, (size_t)(c->motion_tiles_n > mp ? c->motion_tiles_n : mp) * c->B));
+  if (c->motion_fixed) PQACHK(dev_alloc(c, &c->motion_fx_part, (size_t)c->motion_tiles_n * c->B));
+  return hist_alloc(c, &c->mo_hist, 0);
 }
 
 int run_motion(pqa_ctx* c, Batch& b) {
@@ -276,6 +376,24 @@ int run_motion(pqa_ctx* c, Batch& b) {
   else
     HIPCHK(c, launch_motion(b.st_misc, c->elem, b.r[0], p0.base, p0.pitch, b.n, b.w, b.h, c->inv_scale, c->motion_part,
                             c->motion_mode, &b.motion_np));
+  return PQA_OK;
+}
+
+int alloc_psnr_ssim(pqa_ctx* c) {
+  const uint32_t feat = c->cfg.features;
+  for (int p = 0; p < c->n_planes; ++p) {
+    if (feat & PQA_FEAT_PSNR) {
+      PQACHK(dev_alloc(c, &c->sse_part[p], (size_t)kSseBlocksPerPlane * c->B));
+      PQACHK(dev_alloc(c, &c->sse_part_b[p], (size_t)kSseBlocksPerPlane * c->B));
+    }
+    if (feat & PQA_FEAT_SSIM) {
+      c->ssim_tiles_n[p] = ssim_tiles(c->pw[p], c->ph[p]);
+      const int ww = (c->pw[p] >> 2) - 1, wh = (c->ph[p] >> 2) - 1;
+      c->ssim_norm[p] = (ww > 0 && wh > 0) ? 1.0 / ((double)ww * wh) : 0.0;
+      PQACHK(dev_alloc(c, &c->ssim_part[p], (size_t)(c->ssim_tiles_n[p] ? c->ssim_tiles_n[p] : 1) * c->B));
+      PQACHK(dev_alloc(c, &c->sse_tile_part[p], (size_t)(c->ssim_tiles_n[p] ? c->ssim_tiles_n[p] : 1) * c->B));
+    }
+  }
   return PQA_OK;
 }
 
@@ -318,10 +436,68 @@ int run_psnr_ssim(pqa_ctx* c, Batch& b) {
   return PQA_OK;
 }
 
-// Extension features run on the frames that get spatial features; the extension rows of the other frames are NaN.
+// The partials of the luma statistics, the extension rings of the blocks whose features are on (NaN until a batch writes a
+// row) and the record ring (zeros).  The last part of pqa_create: every fill the parts have queued is done when it returns.
+int alloc_rings(pqa_ctx* c) {
+  try {
+    c->ring.init(c->capacity);
+  } catch (...) {
+    return fail(c, PQA_ENOMEM, "out of host memory");
+  }
+  PQACHK(dev_alloc(c, &c->luma_part, (size_t)kLumaBlocks * 3 * c->B));
+  PQACHK(dev_alloc(c, &c->luma_out, (size_t)3 * (c->B > kLumaOutFrames ? c->B : kLumaOutFrames)));
+  PQACHK(dev_alloc(c, &c->records, (size_t)c->capacity * PQA_RECORD_DOUBLES));
+  for (int i = 0; i < kExtBlocks; ++i) {
+    if (!(c->cfg.features & kExtBlock[i].features)) continue;
+    PQACHK(dev_alloc(c, &c->ext[i], (size_t)c->capacity * kExtBlock[i].doubles));
+    HIPCHK(c, launch_ext_fill_nan(c->stream, c->ext[i], 0, c->capacity, c->capacity, kExtBlock[i].doubles));
+  }
+  HIPCHK(c, hipMemsetAsync(c->records, 0, (size_t)c->capacity * PQA_RECORD_DOUBLES * sizeof(double), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PQA_OK;
+}
+
+// The blocks written on the frames that get spatial features only: with n_subsample > 1 the rows of the batch are NaN first.
 int fill_ext_nan(pqa_ctx* c, Batch& b) {
-  if (b.k > 1 && (c->cfg.features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)))
-    HIPCHK(c, launch_ext_fill_nan(b.st_misc, c->ext, b.slot(0), b.n, c->capacity, PQA_EXT_DOUBLES));
+  for (int i = 0; b.k > 1 && i < kExtBlocks; ++i)
+    if (kExtBlock[i].spatial && c->ext[i])
+      HIPCHK(c, launch_ext_fill_nan(b.st_misc, c->ext[i], b.slot(0), b.n, c->capacity, kExtBlock[i].doubles));
+  return PQA_OK;
+}
+
+int alloc_ssim_family(pqa_ctx* c) {
+  const uint32_t feat = c->cfg.features;
+  const int w = c->pw[0], h = c->ph[0], B = c->B;
+  // MS-SSIM scales 1..4 hold ~5.3 bytes per luma sample and frame (22 MB per 2160p frame): the pyramid is walked ssf_sb
+  // frames at a time, at most 320 MiB of planes
+  size_t per_frame = 0;
+  int sw = w, sh = h;
+  for (int j = 0; j < kMsScales; ++j) {
+    Level& L = c->ms_lv[j];
+    L.w = sw; L.h = sh;
+    if (j > 0) { L.pitch = round_up(sw, 16); L.frame_pitch = L.pitch * sh; per_frame += (size_t)L.frame_pitch * 2 * sizeof(float); }
+    c->ms_tiles[j] = ssf_tiles(sw, sh);
+    sw = (sw + 1) / 2; sh = (sh + 1) / 2;
+  }
+  c->ssf_sb = B;
+  if ((feat & PQA_FEAT_MS_SSIM) && per_frame) {
+    const int64_t sb = (int64_t)(320ll << 20) / (int64_t)per_frame;
+    c->ssf_sb = (int)(sb < 1 ? 1 : sb < B ? sb : B);
+  }
+  const int SB = c->ssf_sb;
+  for (int j = 0; (feat & PQA_FEAT_MS_SSIM) && j < kMsScales; ++j) {
+    Level& L = c->ms_lv[j];
+    if (j > 0) {
+      PQACHK(dev_alloc(c, &L.ref, (size_t)L.frame_pitch * SB));
+      PQACHK(dev_alloc(c, &L.dis, (size_t)L.frame_pitch * SB));
+    }
+    PQACHK(dev_alloc(c, &c->ms_part[j], (size_t)c->ms_tiles[j] * 4 * SB));
+  }
+  if (feat & PQA_FEAT_FLOAT_SSIM) {
+    c->fs_box = ssf_decimation(w, h);
+    c->fs_tiles = ssf_tiles((w + c->fs_box - 1) / c->fs_box, (h + c->fs_box - 1) / c->fs_box);
+    PQACHK(dev_alloc(c, &c->fs_part, (size_t)c->fs_tiles * 4 * SB));
+  }
   return PQA_OK;
 }
 
@@ -335,7 +511,7 @@ int run_ssim_family(pqa_ctx* c, Batch& b) {
     const PlaneRun r0 = frames_from(b.rs[0], s0, b.es), d0 = frames_from(b.ds[0], s0, b.es);
     SsfFinalizeArgs sa{};
     sa.n_frames = m;
-    sa.ext = c->ext;
+    sa.ext = c->ext[BLK_MAIN];
     sa.ext_stride = PQA_EXT_DOUBLES;
     sa.slot_base = b.slot(b.e0 + (int64_t)s0 * b.k);
     sa.slot_step = b.k;
@@ -375,12 +551,17 @@ int run_ssim_family(pqa_ctx* c, Batch& b) {
   return PQA_OK;
 }
 
+int alloc_ciede(pqa_ctx* c) {
+  c->ciede_tiles_n = ciede_tiles(c->pw[1], c->ph[1]);
+  return dev_alloc(c, &c->ciede_part, (size_t)c->ciede_tiles_n * c->B);
+}
+
 // CIEDE2000 on Y, U, V of the frames that get spatial features; the epilogue writes slots 20 / 21 of their rows only.
 int run_ciede(pqa_ctx* c, Batch& b) {
   if (!(c->cfg.features & PQA_FEAT_CIEDE) || b.sp_n == 0) return PQA_OK;
   CiedeFinalizeArgs ca{};
   ca.n_frames = b.sp_n;
-  ca.ext = c->ext;
+  ca.ext = c->ext[BLK_MAIN];
   ca.ext_stride = PQA_EXT_DOUBLES;
   ca.slot_base = b.slot(b.e0);
   ca.slot_step = b.k;
@@ -395,6 +576,23 @@ int run_ciede(pqa_ctx* c, Batch& b) {
   return PQA_OK;
 }
 
+// CAMBI's work planes: 7 bytes per sample of the five scales (~77 MB per 2160p frame), at most ~512 MiB per pass.
+int alloc_cambi(pqa_ctx* c) {
+  c->cambi_prm = cambi_params(c->pw[0], c->ph[0]);
+  const CambiParams& cp = c->cambi_prm;
+  HIPCHK(c, cambi_prepare(cp, (int)c->cfg.bit_depth));
+  const int64_t per_frame = cp.off[kCambiScales] * 7 + (int64_t)cp.chunk[kCambiScales] * 8;
+  const int64_t sb = (int64_t)(512ll << 20) / per_frame;
+  c->cambi_sb = (int)(sb < 1 ? 1 : sb < c->B ? sb : c->B);
+  const size_t SB = (size_t)c->cambi_sb;
+  PQACHK(dev_alloc(c, &c->cambi_wk.plane, (size_t)cp.off[kCambiScales] * SB));
+  PQACHK(dev_alloc(c, &c->cambi_wk.mask, (size_t)cp.off[kCambiScales] * SB));
+  PQACHK(dev_alloc(c, &c->cambi_wk.cmap, (size_t)cp.off[kCambiScales] * SB));
+  PQACHK(dev_alloc(c, &c->cambi_wk.hist, (size_t)kCambiScales * 2048 * SB));
+  PQACHK(dev_alloc(c, &c->cambi_wk.sel, (size_t)kCambiScales * 4 * SB));
+  return dev_alloc(c, &c->cambi_wk.partials, (size_t)cp.chunk[kCambiScales] * SB);
+}
+
 // CAMBI of the distorted (and, FULL_REF, the reference) luma, cambi_sb frames at a time; slots 22 / 23 of their rows.
 int run_cambi(pqa_ctx* c, Batch& b) {
   if (!(c->cfg.features & PQA_FEAT_CAMBI)) return PQA_OK;
@@ -402,22 +600,26 @@ int run_cambi(pqa_ctx* c, Batch& b) {
     const int m = b.sp_n - s0 < c->cambi_sb ? b.sp_n - s0 : c->cambi_sb;
     const int slot_base = b.slot(b.e0 + (int64_t)s0 * b.k);
     HIPCHK(c, launch_cambi(b.st_misc, c->elem, frames_from(b.ds[0], s0, b.es), m, b.w, b.h, (int)c->cfg.bit_depth, c->cambi_prm,
-                           c->cambi_wk, c->ext, PQA_EXT_DOUBLES, PQA_EXT_CAMBI, slot_base, b.k, c->capacity));
+                           c->cambi_wk, c->ext[BLK_MAIN], PQA_EXT_DOUBLES, PQA_EXT_CAMBI, slot_base, b.k, c->capacity));
     if (c->cfg.features & PQA_FEAT_CAMBI_FULL_REF)
       HIPCHK(c, launch_cambi(b.st_misc, c->elem, frames_from(b.rs[0], s0, b.es), m, b.w, b.h, (int)c->cfg.bit_depth, c->cambi_prm,
-                             c->cambi_wk, c->ext, PQA_EXT_DOUBLES, PQA_EXT_CAMBI_SOURCE, slot_base, b.k, c->capacity));
+                             c->cambi_wk, c->ext[BLK_MAIN], PQA_EXT_DOUBLES, PQA_EXT_CAMBI_SOURCE, slot_base, b.k, c->capacity));
   }
   return PQA_OK;
 }
 
-// PSNR-HVS on Y, Cb, Cr of the frames that get spatial features, into slots 0..6 of their ext2 rows.
+int alloc_psnr_hvs(pqa_ctx* c) {
+  HIPCHK(c, psnr_hvs_prepare());
+  psnr_hvs_geometry(c->pw, c->ph, &c->phv_geo);
+  return dev_alloc(c, &c->phv_part, (size_t)c->phv_geo.tile0[3] * c->B);
+}
+
+// PSNR-HVS on Y, Cb, Cr of the frames that get spatial features, into slots 0..6 of their rows of the second block.
 int run_psnr_hvs(pqa_ctx* c, Batch& b) {
-  if (!(c->cfg.features & PQA_FEAT_PSNR_HVS)) return PQA_OK;
-  if (b.k > 1) HIPCHK(c, launch_ext_fill_nan(b.st_misc, c->ext2, b.slot(0), b.n, c->capacity, PQA_EXT2_DOUBLES));
-  if (b.sp_n == 0) return PQA_OK;
+  if (!(c->cfg.features & PQA_FEAT_PSNR_HVS) || b.sp_n == 0) return PQA_OK;
   PsnrHvsFinalizeArgs pa{};
   pa.n_frames = b.sp_n;
-  pa.ext2 = c->ext2;
+  pa.ext2 = c->ext[BLK_PSNR_HVS];
   pa.ext_stride = PQA_EXT2_DOUBLES;
   pa.slot_base = b.slot(b.e0);
   pa.slot_step = b.k;
@@ -431,6 +633,14 @@ int run_psnr_hvs(pqa_ctx* c, Batch& b) {
   return PQA_OK;
 }
 
+int alloc_xpsnr(pqa_ctx* c) {
+  xpsnr_geometry(c->pw[0], c->ph[0], c->pw[1], c->ph[1], c->n_planes, (int)c->cfg.bit_depth, &c->xp_geo);
+  PQACHK(dev_alloc(c, &c->xp_blk, (size_t)c->xp_geo.n_blk * kXpBlockVals * c->B));
+  PQACHK(dev_alloc(c, &c->xp_w, (size_t)c->xp_geo.n_blk * c->B));
+  for (int j = 0; j < 2; ++j) PQACHK(hist_alloc(c, &c->xp_hist[j], 0));
+  return PQA_OK;
+}
+
 // XPSNR on every frame: its predecessors come from the batch, the caller's halo, the kept pair or the armed history.
 int run_xpsnr(pqa_ctx* c, Batch& b) {
   if (!(c->cfg.features & PQA_FEAT_XPSNR)) return PQA_OK;
@@ -440,7 +650,7 @@ int run_xpsnr(pqa_ctx* c, Batch& b) {
   xa.n_frames = b.n;
   xa.blk = c->xp_blk;
   xa.wbuf = c->xp_w;
-  xa.ext3 = c->ext3;
+  xa.ext3 = c->ext[BLK_XPSNR];
   xa.ext_stride = PQA_EXT3_DOUBLES;
   xa.slot_base = b.slot(0);
   xa.capacity = c->capacity;
@@ -448,6 +658,12 @@ int run_xpsnr(pqa_ctx* c, Batch& b) {
   HIPCHK(c, launch_xpsnr_blocks(b.st_misc, c->elem, b.r, b.d, b.n, h1.base, h1.pitch, h2.base, h2.pitch,
                                 (c->cfg.features & PQA_FEAT_XPSNR_HFR) != 0, c->xp_geo, c->xp_blk));
   HIPCHK(c, launch_xpsnr_finalize(b.st_misc, xa));
+  return PQA_OK;
+}
+
+int alloc_siti(pqa_ctx* c) {
+  PQACHK(dev_alloc(c, &c->st_part, (size_t)siti_partials(c->pw[0], c->ph[0]) * 2 * 4 * c->B));
+  for (int z = 0; z < 2; ++z) PQACHK(hist_alloc(c, &c->st_hist[z], 0));
   return PQA_OK;
 }
 
@@ -462,8 +678,14 @@ int run_siti(pqa_ctx* c, Batch& b) {
   const int64_t spp[2] = {p[0].pitch, p[1].pitch};
   const PlaneRun sc[2] = {b.d[0], b.r[0]};
   const bool sfull[2] = {(feat & PQA_FEAT_SITI_DIS_FULL) != 0, (feat & PQA_FEAT_SITI_REF_FULL) != 0};
-  HIPCHK(c, launch_siti(b.st_misc, c->elem, sc, sp0, spp, sfull, 2, b.n, b.w, b.h, c->st_part, c->ext4, PQA_EXT4_DOUBLES, b.slot(0),
+  HIPCHK(c, launch_siti(b.st_misc, c->elem, sc, sp0, spp, sfull, 2, b.n, b.w, b.h, c->st_part, c->ext[BLK_SITI], PQA_EXT4_DOUBLES, b.slot(0),
                         c->capacity, nullptr));
+  return PQA_OK;
+}
+
+int alloc_integrity(pqa_ctx* c) {
+  PQACHK(dev_alloc(c, &c->ig_part, (size_t)c->B * 3 * kIntegrityBlocks * 2));
+  for (int p = 0; p < c->n_planes; ++p) PQACHK(hist_alloc(c, &c->ig_hist[p], p));
   return PQA_OK;
 }
 
@@ -479,7 +701,7 @@ int run_integrity(pqa_ctx* c, Batch& b) {
     ipp[p] = c->ig_hist[p].pitch / b.es;
   }
   HIPCHK(c, launch_integrity(b.st_misc, c->elem, b.d, ip0, ipp, c->pw, c->ph, c->n_planes, b.n, false, c->black_thr, c->ig_part,
-                             c->ext5, PQA_EXT5_DOUBLES, b.slot(0), c->capacity, nullptr));
+                             c->ext[BLK_INTEGRITY], PQA_EXT5_DOUBLES, b.slot(0), c->capacity, nullptr));
   return PQA_OK;
 }
 
@@ -530,12 +752,6 @@ int run_finalize(pqa_ctx* c, Batch& b) {
   return PQA_OK;
 }
 
-// A history plane for plane p of a clip, rows padded to 64 bytes.
-int hist_alloc(pqa_ctx* c, HistPlane* hp, int p) {
-  hp->pitch = round_up((int64_t)c->pw[p] * c->esize, 64);
-  return dev_alloc(c, &hp->base, (size_t)hp->pitch * c->ph[p]);
-}
-
 // The caller's host plane p (rows `stride` bytes apart) into a history plane, before it is armed; the stream is idle.
 hipError_t hist_arm(pqa_ctx* c, const HistPlane& dst, const void* src, int64_t stride, int p) {
   return hipMemcpy2D(dst.base, dst.pitch, src, stride, (size_t)c->pw[p] * c->esize, c->ph[p], hipMemcpyHostToDevice);
@@ -564,14 +780,9 @@ int keep_chain(pqa_ctx* c, const Batch& b, host::FrameChain& chain, const HistPl
 // The last frames of this batch, kept so that the next one continues the chains (behind the join: this batch's kernels have
 // read the old planes; behind the batch event: pqa_collect does not wait for these copies).
 int keep_histories(pqa_ctx* c, const Batch& b) {
-  const uint32_t feat = c->cfg.features;
-  int rc = PQA_OK;
-  if (feat & PQA_FEAT_MOTION) rc = keep_chain(c, b, c->mo_chain, &c->mo_hist, b.ref, 1);
-  if (rc == PQA_OK && (feat & PQA_FEAT_XPSNR)) rc = keep_chain(c, b, c->xp_chain, c->xp_hist, b.ref, 1);
-  if (rc == PQA_OK && (feat & PQA_FEAT_SITI)) rc = keep_chain(c, b, c->st_chain[0], &c->st_hist[0], b.dis, 1);
-  if (rc == PQA_OK && (feat & PQA_FEAT_SITI)) rc = keep_chain(c, b, c->st_chain[1], &c->st_hist[1], b.ref, 1);
-  if (rc == PQA_OK && (feat & PQA_FEAT_INTEGRITY)) rc = keep_chain(c, b, c->ig_chain, c->ig_hist, b.dis, c->n_planes);
-  return rc;
+  for (const History& h : histories(c))
+    if (c->cfg.features & h.feature) PQACHK(keep_chain(c, b, *h.chain, h.planes, h.dis ? b.dis : b.ref, h.np));
+  return PQA_OK;
 }
 
 int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, const pqa_device_clip* dis,
@@ -615,7 +826,7 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
   b.motion_np = c->motion_tiles_n;
   // the frames in front of this batch: armed planes are bound, a batch that does not continue a chain starts one (the chain
   // of a feature that is off is never read)
-  for (host::FrameChain* ch : {&c->mo_chain, &c->xp_chain, &c->st_chain[0], &c->st_chain[1], &c->ig_chain}) ch->begin(first);
+  for (const History& h : histories(c)) h.chain->begin(first);
 
   // the VIF chain on the main stream, the ADM chain on the second, everything else in this order on the third
   static int (*const kSteps[])(pqa_ctx*, Batch&) = {run_vif,   run_adm,   run_motion,   run_psnr_ssim, fill_ext_nan, run_ssim_family,
@@ -860,38 +1071,9 @@ int submit_one(pqa_ctx* c, int64_t frame_index, const PlaneSrc (&src)[2][3]) {
   return submit_run(c, frame_index, 1, src, no_step);
 }
 
-}  // namespace
-
-// ================================================================================================
-extern "C" {
-
-const char* pqa_version(void) { return "pqa_vmaf 0.2.0 (gfx950; libvmaf-float VIF/ADM/motion, FFmpeg psnr/ssim; VIF scale 0 on the f16 matrix cores)"; }
-int pqa_record_doubles(void) { return PQA_RECORD_DOUBLES; }
-int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
-int pqa_ext2_doubles(void) { return PQA_EXT2_DOUBLES; }
-int pqa_ext3_doubles(void) { return PQA_EXT3_DOUBLES; }
-int pqa_ext4_doubles(void) { return PQA_EXT4_DOUBLES; }
-int pqa_ext5_doubles(void) { return PQA_EXT5_DOUBLES; }
-
-void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
-  if (!cfg) return;
-  memset(cfg, 0, sizeof *cfg);
-  cfg->struct_size = sizeof *cfg;
-  cfg->width = width; cfg->height = height;
-  cfg->bit_depth = 8;
-  cfg->n_planes = 1;
-  cfg->chroma_hshift = cfg->chroma_vshift = 1;
-  cfg->features = PQA_FEAT_VMAF;
-  cfg->max_batch = 0;  // auto
-  cfg->result_capacity = 16384;
-  cfg->n_subsample = 1;
-  cfg->vif_enhn_gain_limit = 100.0;
-  cfg->adm_enhn_gain_limit = 100.0;
-}
-
-int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
-  if (!cfg || !out) return fail(nullptr, PQA_EINVAL, "null argument");
-  *out = nullptr;
+// ---- pqa_create, in parts -----------------------------------------------------------------------
+// What a configuration must satisfy, the first failing rule reported; no device call.
+int check_config(const pqa_config* cfg) {
   if (cfg->struct_size != sizeof(pqa_config)) return fail(nullptr, PQA_EINVAL, "pqa_config.struct_size mismatch");
   if (cfg->width < 16 || cfg->height < 16 || cfg->width > 16384 || cfg->height > 16384)
     return fail(nullptr, PQA_EINVAL, "unsupported frame size %ux%u (16..16384)", cfg->width, cfg->height);
@@ -947,6 +1129,89 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     return fail(nullptr, PQA_EINVAL, "siti supports bit depth 8 or 10 (got %u)", cfg->bit_depth);
   if (cfg->vif_border > PQA_VIF_BORDER_INTEGER || (cfg->fixed_point & ~(uint32_t)PQA_FIXED_ALL))
     return fail(nullptr, PQA_EINVAL, "bad vif_border %u / fixed_point 0x%x", cfg->vif_border, cfg->fixed_point);
+  return PQA_OK;
+}
+
+// The environment switches, read once per context.
+void read_switches(pqa_ctx* c) {
+  // PQA_MULTI_STREAM=1: the ADM chain and the motion / PSNR / SSIM kernels on their own streams beside the VIF chain.
+  // With the ADM march kernel (memory-bound at scales 0 / 1) that is worth +2 ... +4 % at 2160p (profiles/r04h_batch_sweep.txt,
+  // r04j_prio.txt) -- but a kernel's launch then lasts as long as its share of a crowded device allows (VIF scale 0: 1.23 ms
+  // instead of 0.76), so the per-kernel figures stop describing the kernels; stream priorities changed nothing.  Off by default.
+  const char* e = getenv("PQA_MULTI_STREAM");
+  c->multi_stream = (e && e[0] == '1') ? 1 : (e && e[0] == '2') ? 2 : 0;
+  const char* t = getenv("PQA_TRACE");
+  c->trace = t && t[0] == '1';
+  const char* v = getenv("PQA_VIF_MFMA");   // 0: VALU kernels only (the march kernel's test partner); default: march kernel
+  c->vif_s0_mode = (v && v[0] == '0') ? VIF_S0_VALU : VIF_S0_AUTO;
+  const char* vu = getenv("PQA_VIF_UNIFORM");   // 0: every wave takes the general VIF statistic (test partner of the all-high fast path)
+  c->vif_uniform = !(vu && vu[0] == '0');
+  // PQA_VIF_STRIP: 0 = vif_stat_kernel at every scale (the strip kernel's test partner); a number = the scales that may run
+  // the strip kernel as a bit mask (2: scale 1, 6: scales 1 and 2, 14: scales 1-3; per-scale A/B runs and the tests); default:
+  // scale 1, the one scale at which the strip kernel measured faster.
+  // PQA_VIF_STRIP_SEG=n: segments of n tile rows whatever the launch size (small test frames cross segment boundaries).
+  const char* vs = getenv("PQA_VIF_STRIP");
+  if (vs && vs[0]) c->vif_strip_mask = atoi(vs) & 0xe;
+  const char* vg = getenv("PQA_VIF_STRIP_SEG");
+  c->vif_strip_seg = vg ? std::max(0, atoi(vg)) : 0;
+  const char* am = getenv("PQA_ADM_MARCH");  // 0: the LDS-tiled ADM kernel (A/B partner of the march kernel)
+  const char* ap = getenv("PQA_ADM_PYRAMID");  // 0: the march kernel one scale per launch (test partner of the pyramid kernel)
+  c->adm_mode = (am && am[0] == '0') ? ADM_TILED : (ap && ap[0] == '0') ? ADM_MARCH : ADM_AUTO;
+  const char* mm = getenv("PQA_MOTION_MARCH");  // 0: the LDS-tiled motion kernel (test partner of the march kernel)
+  c->motion_mode = (mm && mm[0] == '0') ? MOTION_TILED : MOTION_AUTO;
+  const char* xm = getenv("PQA_XSSE_MFMA");  // 0: the plain-VALU cross-SSE kernel for 8-bit clips too (test partner of the MFMA kernel)
+  c->xsse_mfma = !(xm && xm[0] == '0');
+  const char* tw = getenv("PQA_TEMPORAL_WALK");  // 1: a workgroup of the temporal moments walks through time (A/B partner of a workgroup per transition)
+  c->temporal_walk = tw && tw[0] == '1';
+}
+
+// The context's own streams and the events of a batch.
+int create_streams(pqa_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+  c->stream = c->own_stream;
+  for (int i = 0; i < 2; ++i) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(&c->join_ev[i], hipEventDisableTiming));
+  }
+  HIPCHK(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+  for (int i = 0; i < kBatchEvents; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->batch_ev[i], hipEventDisableTiming));
+  return PQA_OK;
+}
+
+}  // namespace
+
+// ================================================================================================
+extern "C" {
+
+const char* pqa_version(void) { return "pqa_vmaf 0.2.0 (gfx950; libvmaf-float VIF/ADM/motion, FFmpeg psnr/ssim; VIF scale 0 on the f16 matrix cores)"; }
+int pqa_record_doubles(void) { return PQA_RECORD_DOUBLES; }
+int pqa_ext_doubles(void) { return PQA_EXT_DOUBLES; }
+int pqa_ext2_doubles(void) { return PQA_EXT2_DOUBLES; }
+int pqa_ext3_doubles(void) { return PQA_EXT3_DOUBLES; }
+int pqa_ext4_doubles(void) { return PQA_EXT4_DOUBLES; }
+int pqa_ext5_doubles(void) { return PQA_EXT5_DOUBLES; }
+
+void pqa_config_init(pqa_config* cfg, uint32_t width, uint32_t height) {
+  if (!cfg) return;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->struct_size = sizeof *cfg;
+  cfg->width = width; cfg->height = height;
+  cfg->bit_depth = 8;
+  cfg->n_planes = 1;
+  cfg->chroma_hshift = cfg->chroma_vshift = 1;
+  cfg->features = PQA_FEAT_VMAF;
+  cfg->max_batch = 0;  // auto
+  cfg->result_capacity = 16384;
+  cfg->n_subsample = 1;
+  cfg->vif_enhn_gain_limit = 100.0;
+  cfg->adm_enhn_gain_limit = 100.0;
+}
+
+int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
+  if (!cfg || !out) return fail(nullptr, PQA_EINVAL, "null argument");
+  *out = nullptr;
+  PQACHK(check_config(cfg));
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, PQA_EDEVICE, "no HIP device visible (this library has no CPU fallback)");
@@ -981,245 +1246,27 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->pw[p] = (int)((cfg->width + (1u << cfg->chroma_hshift) - 1) >> cfg->chroma_hshift);
     c->ph[p] = (int)((cfg->height + (1u << cfg->chroma_vshift) - 1) >> cfg->chroma_vshift);
   }
-
-  auto bail = [&](int rc) {
-    g_create_error = c->err;
-    pqa_destroy(c);
-    return rc;
-  };
-#define CREATE_TRY(expr) do { int rc_ = (expr); if (rc_ != PQA_OK) return bail(rc_); } while (0)
-#define CREATE_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-    fail(c, e_ == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    return bail(e_ == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE); } } while (0)
-
-  CREATE_HIP(hipSetDevice(c->device));
-  CREATE_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-  c->stream = c->own_stream;
-  {
-    // PQA_MULTI_STREAM=1: the ADM chain and the motion / PSNR / SSIM kernels on their own streams beside the VIF chain.
-    // With the ADM march kernel (memory-bound at scales 0 / 1) that is worth +2 ... +4 % at 2160p (profiles/r04h_batch_sweep.txt,
-    // r04j_prio.txt) -- but a kernel's launch then lasts as long as its share of a crowded device allows (VIF scale 0: 1.23 ms
-    // instead of 0.76), so the per-kernel figures stop describing the kernels; stream priorities changed nothing.  Off by default.
-    const char* e = getenv("PQA_MULTI_STREAM");
-    c->multi_stream = (e && e[0] == '1') ? 1 : (e && e[0] == '2') ? 2 : 0;
-    const char* t = getenv("PQA_TRACE");
-    c->trace = t && t[0] == '1';
-    const char* v = getenv("PQA_VIF_MFMA");   // 0: VALU kernels only (the march kernel's test partner); default: march kernel
-    c->vif_s0_mode = (v && v[0] == '0') ? VIF_S0_VALU : VIF_S0_AUTO;
-    const char* vu = getenv("PQA_VIF_UNIFORM");   // 0: every wave takes the general VIF statistic (test partner of the all-high fast path)
-    c->vif_uniform = !(vu && vu[0] == '0');
-    // PQA_VIF_STRIP: 0 = vif_stat_kernel at every scale (the strip kernel's test partner); a number = the scales that may run
-    // the strip kernel as a bit mask (2: scale 1, 6: scales 1 and 2, 14: scales 1-3; per-scale A/B runs and the tests); default:
-    // scale 1, the one scale at which the strip kernel measured faster.
-    // PQA_VIF_STRIP_SEG=n: segments of n tile rows whatever the launch size (small test frames cross segment boundaries).
-    const char* vs = getenv("PQA_VIF_STRIP");
-    if (vs && vs[0]) c->vif_strip_mask = atoi(vs) & 0xe;
-    const char* vg = getenv("PQA_VIF_STRIP_SEG");
-    c->vif_strip_seg = vg ? std::max(0, atoi(vg)) : 0;
-    const char* am = getenv("PQA_ADM_MARCH");  // 0: the LDS-tiled ADM kernel (A/B partner of the march kernel)
-    const char* ap = getenv("PQA_ADM_PYRAMID");  // 0: the march kernel one scale per launch (test partner of the pyramid kernel)
-    c->adm_mode = (am && am[0] == '0') ? ADM_TILED : (ap && ap[0] == '0') ? ADM_MARCH : ADM_AUTO;
-    const char* mm = getenv("PQA_MOTION_MARCH");  // 0: the LDS-tiled motion kernel (test partner of the march kernel)
-    c->motion_mode = (mm && mm[0] == '0') ? MOTION_TILED : MOTION_AUTO;
-    const char* xm = getenv("PQA_XSSE_MFMA");  // 0: the plain-VALU cross-SSE kernel for 8-bit clips too (test partner of the MFMA kernel)
-    c->xsse_mfma = !(xm && xm[0] == '0');
-    const char* tw = getenv("PQA_TEMPORAL_WALK");  // 1: a workgroup of the temporal moments walks through time (A/B partner of a workgroup per transition)
-    c->temporal_walk = tw && tw[0] == '1';
-  }
-  for (int i = 0; i < 2; ++i) {
-    CREATE_HIP(hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
-    CREATE_HIP(hipEventCreateWithFlags(&c->join_ev[i], hipEventDisableTiming));
-  }
-  CREATE_HIP(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-  for (int i = 0; i < kBatchEvents; ++i) CREATE_HIP(hipEventCreateWithFlags(&c->batch_ev[i], hipEventDisableTiming));
-  try {
-    c->ring.init(c->capacity);
-  } catch (...) {
-    fail(c, PQA_ENOMEM, "out of host memory");
-    return bail(PQA_ENOMEM);
-  }
-
   c->vif_fixed = (cfg->features & PQA_FEAT_VIF) && (cfg->fixed_point & PQA_FIXED_VIF);
   c->motion_fixed = (cfg->features & PQA_FEAT_MOTION) && (cfg->fixed_point & PQA_FIXED_MOTION);
   c->adm_fixed = (cfg->features & PQA_FEAT_ADM) && (cfg->fixed_point & PQA_FIXED_ADM);
-  if (c->adm_fixed) {
-    std::vector<int32_t> lut(65537);
-    adm_fixed_div_table(lut.data());
-    CREATE_TRY(dev_alloc(c, &c->adm_div_lut, lut.size()));
-    CREATE_HIP(hipMemcpy(c->adm_div_lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  if ((cfg->features & PQA_FEAT_VIF) && !c->vif_fixed) CREATE_HIP(vif_march_prepare());
-  if (c->vif_fixed) {
-    std::vector<uint16_t> lut(32768);
-    vif_fixed_log2_table(lut.data());
-    CREATE_TRY(dev_alloc(c, &c->vif_lut, lut.size()));
-    CREATE_HIP(hipMemcpy(c->vif_lut, lut.data(), lut.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  }
-  const int w = c->pw[0], h = c->ph[0], B = c->B;
-  // VIF pyramid (floor halving) and ADM approximation bands (ceil halving), f32, rows padded to 64 B
-  int vw = w, vh = h, aw = w, ah = h;
-  for (int s = 0; s < 4; ++s) {
-    if (s > 0) {
-      vw /= 2; vh /= 2;
-      aw = (aw + 1) / 2; ah = (ah + 1) / 2;
-      Level& V = c->vif_lv[s];
-      V.w = vw; V.h = vh; V.pitch = round_up(vw, 16); V.frame_pitch = V.pitch * vh;
-      Level& A = c->adm_lv[s];
-      A.w = aw; A.h = ah; A.pitch = round_up(aw, 16); A.frame_pitch = A.pitch * ah;
-      if (cfg->features & PQA_FEAT_VIF) {
-        CREATE_TRY(dev_alloc(c, &V.ref, (size_t)V.frame_pitch * B));
-        CREATE_TRY(dev_alloc(c, &V.dis, (size_t)V.frame_pitch * B));
-      }
-      if (cfg->features & PQA_FEAT_ADM) {
-        CREATE_TRY(dev_alloc(c, &A.ref, (size_t)A.frame_pitch * B));
-        CREATE_TRY(dev_alloc(c, &A.dis, (size_t)A.frame_pitch * B));
-      }
-    }
-    if (vw < 2 || vh < 2) { fail(c, PQA_EINVAL, "frame too small for 4 VIF scales"); return bail(PQA_EINVAL); }
-    c->vif_tiles[s] = vif_tiles_x(s, vw) * vif_tiles_y(vh);
-    if (s == 0) {   // scale 0 may run the march kernel, which writes one partial pair per wave segment
-      const int mp = vif_march_partials_max(vw, vh);
-      c->vif_part_cap0 = c->vif_tiles[0] > mp ? c->vif_tiles[0] : mp;
-    }
-    const int bw = (aw + 1) / 2, bh = (ah + 1) / 2;  // band size produced at ADM scale s
-    c->adm_tiles[s] = adm_tiles_x(bw) * adm_tiles_y(bh);
-    const int left = (int)(bw * 0.1 - 0.5), top = (int)(bh * 0.1 - 0.5);
-    c->adm_area[s] = (float)((bh - 2 * top) * (bw - 2 * left));
-    if ((cfg->features & PQA_FEAT_VIF) && !c->vif_fixed)
-      CREATE_TRY(dev_alloc(c, &c->vif_part[s], (size_t)(s == 0 ? c->vif_part_cap0 : c->vif_tiles[s]) * 2 * B));
-    if ((cfg->features & PQA_FEAT_VIF) && c->vif_fixed)
-      CREATE_TRY(dev_alloc(c, &c->vif_fx_part[s], (size_t)c->vif_tiles[s] * kVifFxPartials * B));
-    c->adm_fx[s] = adm_fixed_scale_params(s, bw, bh);
-    if ((cfg->features & PQA_FEAT_ADM) && !c->adm_fixed) {   // one sextet per tile (adm.hip) or per wave segment (adm_march.hip)
-      int mp = adm_march_partials(bw, bh);
-      if (s < 2 && adm_pyramid_takes(c->elem, w, h)) { const int pp = adm_pyramid_partials(w, h); mp = pp > mp ? pp : mp; }
-      CREATE_TRY(dev_alloc(c, &c->adm_part[s], (size_t)(c->adm_tiles[s] > mp ? c->adm_tiles[s] : mp) * 6 * B));
-    }
-    if ((cfg->features & PQA_FEAT_ADM) && c->adm_fixed)
-      CREATE_TRY(dev_alloc(c, &c->adm_fx_part[s], (size_t)c->adm_tiles[s] * kAdmFxRows * 6 * B));
-  }
-  c->motion_tiles_n = motion_tiles(w, h);
-  if (cfg->features & PQA_FEAT_MOTION) {
-    {   // one partial per tile (motion.hip) or per wave segment (motion_march.hip)
-      const int mp = motion_march_partials(w, h);
-      CREATE_TRY(dev_alloc(c, &c->motion_part, (size_t)(c->motion_tiles_n > mp ? c->motion_tiles_n : mp) * B));
-    }
-    if (c->motion_fixed) CREATE_TRY(dev_alloc(c, &c->motion_fx_part, (size_t)c->motion_tiles_n * B));
-    CREATE_TRY(hist_alloc(c, &c->mo_hist, 0));
-  }
-  for (int p = 0; p < c->n_planes; ++p) {
-    if (cfg->features & PQA_FEAT_PSNR) {
-      CREATE_TRY(dev_alloc(c, &c->sse_part[p], (size_t)kSseBlocksPerPlane * B));
-      CREATE_TRY(dev_alloc(c, &c->sse_part_b[p], (size_t)kSseBlocksPerPlane * B));
-    }
-    if (cfg->features & PQA_FEAT_SSIM) {
-      c->ssim_tiles_n[p] = ssim_tiles(c->pw[p], c->ph[p]);
-      const int ww = (c->pw[p] >> 2) - 1, wh = (c->ph[p] >> 2) - 1;
-      c->ssim_norm[p] = (ww > 0 && wh > 0) ? 1.0 / ((double)ww * wh) : 0.0;
-      CREATE_TRY(dev_alloc(c, &c->ssim_part[p], (size_t)(c->ssim_tiles_n[p] ? c->ssim_tiles_n[p] : 1) * B));
-      CREATE_TRY(dev_alloc(c, &c->sse_tile_part[p], (size_t)(c->ssim_tiles_n[p] ? c->ssim_tiles_n[p] : 1) * B));
+  // blackdetect's default pixel_black_th = 0.10 on a limited-range clip: 37 / 151 / 606
+  const double f = (double)(1 << (cfg->bit_depth - 8));
+  c->black_thr = (uint32_t)(16.0 * f + 0.10 * 219.0 * f);
+  read_switches(c);
+  // each part for the contexts with one of its feature bits (0: all); the streams first, alloc_rings last: it waits for the fills
+  static const struct { uint32_t features; int (*make)(pqa_ctx*); } kParts[] = {
+      {0, create_streams}, {0, alloc_vif}, {0, alloc_adm}, {0, alloc_motion}, {0, alloc_psnr_ssim},
+      {PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM, alloc_ssim_family}, {PQA_FEAT_CIEDE, alloc_ciede}, {PQA_FEAT_CAMBI, alloc_cambi},
+      {PQA_FEAT_PSNR_HVS, alloc_psnr_hvs}, {PQA_FEAT_XPSNR, alloc_xpsnr}, {PQA_FEAT_SITI, alloc_siti},
+      {PQA_FEAT_INTEGRITY, alloc_integrity}, {0, alloc_rings}};
+  for (const auto& part : kParts) {
+    if (part.features && !(cfg->features & part.features)) continue;
+    if (const int rc = part.make(c); rc != PQA_OK) {
+      g_create_error = c->err;
+      pqa_destroy(c);
+      return rc;
     }
   }
-  CREATE_TRY(dev_alloc(c, &c->luma_part, (size_t)kLumaBlocks * 3 * B));
-  CREATE_TRY(dev_alloc(c, &c->luma_out, (size_t)3 * (B > kLumaOutFrames ? B : kLumaOutFrames)));
-  if (c->adm_fixed) {
-    CREATE_TRY(dev_alloc(c, &c->adm_fx_acc, (size_t)c->capacity * 24));
-    CREATE_HIP(hipMemsetAsync(c->adm_fx_acc, 0, (size_t)c->capacity * 24 * sizeof(long long), c->stream));
-  }
-  CREATE_TRY(dev_alloc(c, &c->records, (size_t)c->capacity * PQA_RECORD_DOUBLES));
-  if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM)) {
-    // MS-SSIM scales 1..4 hold ~5.3 bytes per luma sample and frame (22 MB per 2160p frame): the pyramid is walked ssf_sb
-    // frames at a time, at most 320 MiB of planes
-    size_t per_frame = 0;
-    int sw = w, sh = h;
-    for (int j = 0; j < kMsScales; ++j) {
-      Level& L = c->ms_lv[j];
-      L.w = sw; L.h = sh;
-      if (j > 0) { L.pitch = round_up(sw, 16); L.frame_pitch = L.pitch * sh; per_frame += (size_t)L.frame_pitch * 2 * sizeof(float); }
-      c->ms_tiles[j] = ssf_tiles(sw, sh);
-      sw = (sw + 1) / 2; sh = (sh + 1) / 2;
-    }
-    c->ssf_sb = B;
-    if ((cfg->features & PQA_FEAT_MS_SSIM) && per_frame) {
-      const int64_t sb = (int64_t)(320ll << 20) / (int64_t)per_frame;
-      c->ssf_sb = (int)(sb < 1 ? 1 : sb < B ? sb : B);
-    }
-    const int SB = c->ssf_sb;
-    if (cfg->features & PQA_FEAT_MS_SSIM) {
-      for (int j = 0; j < kMsScales; ++j) {
-        Level& L = c->ms_lv[j];
-        if (j > 0) {
-          CREATE_TRY(dev_alloc(c, &L.ref, (size_t)L.frame_pitch * SB));
-          CREATE_TRY(dev_alloc(c, &L.dis, (size_t)L.frame_pitch * SB));
-        }
-        CREATE_TRY(dev_alloc(c, &c->ms_part[j], (size_t)c->ms_tiles[j] * 4 * SB));
-      }
-    }
-    if (cfg->features & PQA_FEAT_FLOAT_SSIM) {
-      c->fs_box = ssf_decimation(w, h);
-      c->fs_tiles = ssf_tiles((w + c->fs_box - 1) / c->fs_box, (h + c->fs_box - 1) / c->fs_box);
-      CREATE_TRY(dev_alloc(c, &c->fs_part, (size_t)c->fs_tiles * 4 * SB));
-    }
-  }
-  if (cfg->features & PQA_FEAT_CIEDE) {
-    c->ciede_tiles_n = ciede_tiles(c->pw[1], c->ph[1]);
-    CREATE_TRY(dev_alloc(c, &c->ciede_part, (size_t)c->ciede_tiles_n * B));
-  }
-  if (cfg->features & PQA_FEAT_CAMBI) {
-    // work planes: 7 bytes per sample of the five scales (~77 MB per 2160p frame), at most ~512 MiB per pass
-    c->cambi_prm = cambi_params(w, h);
-    const CambiParams& cp = c->cambi_prm;
-    CREATE_HIP(cambi_prepare(cp, (int)cfg->bit_depth));
-    const int64_t per_frame = cp.off[kCambiScales] * 7 + (int64_t)cp.chunk[kCambiScales] * 8;
-    const int64_t sb = (int64_t)(512ll << 20) / per_frame;
-    c->cambi_sb = (int)(sb < 1 ? 1 : sb < B ? sb : B);
-    const size_t SB = (size_t)c->cambi_sb;
-    CREATE_TRY(dev_alloc(c, &c->cambi_wk.plane, (size_t)cp.off[kCambiScales] * SB));
-    CREATE_TRY(dev_alloc(c, &c->cambi_wk.mask, (size_t)cp.off[kCambiScales] * SB));
-    CREATE_TRY(dev_alloc(c, &c->cambi_wk.cmap, (size_t)cp.off[kCambiScales] * SB));
-    CREATE_TRY(dev_alloc(c, &c->cambi_wk.hist, (size_t)kCambiScales * 2048 * SB));
-    CREATE_TRY(dev_alloc(c, &c->cambi_wk.sel, (size_t)kCambiScales * 4 * SB));
-    CREATE_TRY(dev_alloc(c, &c->cambi_wk.partials, (size_t)cp.chunk[kCambiScales] * SB));
-  }
-  if (cfg->features & PQA_FEAT_PSNR_HVS) {
-    CREATE_HIP(psnr_hvs_prepare());
-    psnr_hvs_geometry(c->pw, c->ph, &c->phv_geo);
-    CREATE_TRY(dev_alloc(c, &c->phv_part, (size_t)c->phv_geo.tile0[3] * B));
-    CREATE_TRY(dev_alloc(c, &c->ext2, (size_t)c->capacity * PQA_EXT2_DOUBLES));
-    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext2, 0, c->capacity, c->capacity, PQA_EXT2_DOUBLES));
-  }
-  if (cfg->features & PQA_FEAT_XPSNR) {
-    xpsnr_geometry(c->pw[0], c->ph[0], c->pw[1], c->ph[1], c->n_planes, (int)cfg->bit_depth, &c->xp_geo);
-    CREATE_TRY(dev_alloc(c, &c->xp_blk, (size_t)c->xp_geo.n_blk * kXpBlockVals * B));
-    CREATE_TRY(dev_alloc(c, &c->xp_w, (size_t)c->xp_geo.n_blk * B));
-    for (int j = 0; j < 2; ++j) CREATE_TRY(hist_alloc(c, &c->xp_hist[j], 0));
-    CREATE_TRY(dev_alloc(c, &c->ext3, (size_t)c->capacity * PQA_EXT3_DOUBLES));
-    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext3, 0, c->capacity, c->capacity, PQA_EXT3_DOUBLES));
-  }
-  if (cfg->features & PQA_FEAT_SITI) {
-    CREATE_TRY(dev_alloc(c, &c->st_part, (size_t)siti_partials(w, h) * 2 * 4 * B));
-    for (int z = 0; z < 2; ++z) CREATE_TRY(hist_alloc(c, &c->st_hist[z], 0));
-    CREATE_TRY(dev_alloc(c, &c->ext4, (size_t)c->capacity * PQA_EXT4_DOUBLES));
-    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext4, 0, c->capacity, c->capacity, PQA_EXT4_DOUBLES));
-  }
-  {  // blackdetect's default pixel_black_th = 0.10 on a limited-range clip: 37 / 151 / 606
-    const double f = (double)(1 << (cfg->bit_depth - 8));
-    c->black_thr = (uint32_t)(16.0 * f + 0.10 * 219.0 * f);
-  }
-  if (cfg->features & PQA_FEAT_INTEGRITY) {
-    CREATE_TRY(dev_alloc(c, &c->ig_part, (size_t)B * 3 * kIntegrityBlocks * 2));
-    for (int p = 0; p < c->n_planes; ++p) CREATE_TRY(hist_alloc(c, &c->ig_hist[p], p));
-    CREATE_TRY(dev_alloc(c, &c->ext5, (size_t)c->capacity * PQA_EXT5_DOUBLES));
-    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext5, 0, c->capacity, c->capacity, PQA_EXT5_DOUBLES));
-  }
-  if (cfg->features & (PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI)) {
-    CREATE_TRY(dev_alloc(c, &c->ext, (size_t)c->capacity * PQA_EXT_DOUBLES));
-    CREATE_HIP(launch_ext_fill_nan(c->stream, c->ext, 0, c->capacity, c->capacity, PQA_EXT_DOUBLES));
-  }
-  CREATE_HIP(hipMemsetAsync(c->records, 0, (size_t)c->capacity * PQA_RECORD_DOUBLES * sizeof(double), c->stream));
-  CREATE_HIP(hipStreamSynchronize(c->stream));
-#undef CREATE_TRY
-#undef CREATE_HIP
   *out = c;
   return PQA_OK;
 }
@@ -1896,9 +1943,7 @@ int pqa_collect_ext5(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   const size_t rec_bytes = PQA_RECORD_DOUBLES * sizeof(double);
-  const struct ExtRing { double* out; const double* dev; int doubles; } rings[5] = {
-      {ext, c->ext, PQA_EXT_DOUBLES},    {ext2, c->ext2, PQA_EXT2_DOUBLES}, {ext3, c->ext3, PQA_EXT3_DOUBLES},
-      {ext4, c->ext4, PQA_EXT4_DOUBLES}, {ext5, c->ext5, PQA_EXT5_DOUBLES}};
+  double* const outs[kExtBlocks] = {ext, ext2, ext3, ext4, ext5};
   int64_t row = first_index % c->capacity;
   int done = 0;
   while (done < count) {
@@ -1922,13 +1967,14 @@ int pqa_collect_ext5(pqa_ctx* c, int64_t first_index, int32_t count, double* rec
           adm_fixed_epilogue(c->adm_fx[s], &acc[(size_t)f * 24 + s * 6], &rec[PQA_REC_ADM_NUM + s], &rec[PQA_REC_ADM_DEN + s]);
         }
     }
-    for (const ExtRing& x : rings) {   // an extension ring has the record ring's slots
-      if (!x.out) continue;
-      double* dst = x.out + (size_t)done * x.doubles;
-      if (x.dev)
-        HIPCHK(c, hipMemcpy(dst, x.dev + (size_t)row * x.doubles, (size_t)n * x.doubles * sizeof(double), hipMemcpyDeviceToHost));
-      else   // a context without the features of this ring: nothing it runs has a slot there
-        std::fill(dst, dst + (size_t)n * x.doubles, __builtin_nan(""));
+    for (int i = 0; i < kExtBlocks; ++i) {   // an extension ring has the record ring's slots
+      if (!outs[i]) continue;
+      const size_t doubles = kExtBlock[i].doubles;
+      double* dst = outs[i] + (size_t)done * doubles;
+      if (c->ext[i])
+        HIPCHK(c, hipMemcpy(dst, c->ext[i] + (size_t)row * doubles, (size_t)n * doubles * sizeof(double), hipMemcpyDeviceToHost));
+      else   // a context without the features of this block: nothing it runs has a slot there
+        std::fill(dst, dst + (size_t)n * doubles, __builtin_nan(""));
     }
     done += n;
     row = 0;
@@ -1954,7 +2000,7 @@ int pqa_reset(pqa_ctx* c) {
   c->done_seq = c->batch_seq;
   c->ring.reset();
   c->pending = 0;
-  for (host::FrameChain* ch : {&c->mo_chain, &c->xp_chain, &c->st_chain[0], &c->st_chain[1], &c->ig_chain}) ch->restart();
+  for (const History& h : histories(c)) h.chain->restart();
   c->started = false;
   c->err.clear();
   return PQA_OK;

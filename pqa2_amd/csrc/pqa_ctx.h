@@ -47,6 +47,21 @@ struct ProfEv {
 };
 
 constexpr int kBatchEvents = 64;  // ring of per-batch completion events
+
+// The extension record blocks: rings of [capacity][doubles] beside the record ring, pqa_ctx::ext below.  A block exists in a
+// context whose feature mask has one of its bits (pqa_create allocates and NaN-fills it; collecting hands out NaN rows
+// for the others).  `spatial`: written on the frames that get spatial features only, so with n_subsample > 1 a batch fills
+// its rows with NaN first (fill_ext_nan).  A new block is one row here and one in _native.EXT_BLOCKS.
+struct ExtBlock { int doubles; uint32_t features; bool spatial; };
+enum { BLK_MAIN = 0, BLK_PSNR_HVS, BLK_XPSNR, BLK_SITI, BLK_INTEGRITY, kExtBlocks };   // in the order the collect entry points take them
+constexpr ExtBlock kExtBlock[kExtBlocks] = {
+    {PQA_EXT_DOUBLES, PQA_FEAT_FLOAT_SSIM | PQA_FEAT_MS_SSIM | PQA_FEAT_CIEDE | PQA_FEAT_CAMBI, true},   // ssim_family, ciede, cambi
+    {PQA_EXT2_DOUBLES, PQA_FEAT_PSNR_HVS, true},     // psnr_hvs.hip
+    {PQA_EXT3_DOUBLES, PQA_FEAT_XPSNR, false},       // xpsnr.hip
+    {PQA_EXT4_DOUBLES, PQA_FEAT_SITI, false},        // siti.hip
+    {PQA_EXT5_DOUBLES, PQA_FEAT_INTEGRITY, false},   // integrity.hip
+};
+
 constexpr int kLumaOutFrames = 2048;  // luma statistics kept on the device between host copies
 
 // The grow-only device buffers of the side analyses, pqa_ctx::side_buf below (side_reserve, pqa_side.hip).
@@ -116,40 +131,37 @@ struct pqa_ctx {
   int ssim_tiles_n[3] = {};
   double ssim_norm[3] = {};
   double* records = nullptr;
-  // SSIM family (PQA_FEAT_FLOAT_SSIM / PQA_FEAT_MS_SSIM; ssim_family.hip): nothing is allocated unless one of the bits is set
-  double* ext = nullptr;             // [capacity][PQA_EXT_DOUBLES] ring beside `records`
+  double* ext[pqa::kExtBlocks] = {};   // the extension rings beside `records` (pqa::kExtBlock); null: no feature of the block is on
+  // The opt-in features below allocate nothing unless one of their bits is set (the alloc_* functions of pqa_api.hip).
+  // SSIM family (PQA_FEAT_FLOAT_SSIM / PQA_FEAT_MS_SSIM; ssim_family.hip)
   pqa::Level ms_lv[pqa::kMsScales];            // MS-SSIM scales 1..4: f32 planes for ssf_sb frames
   double* ms_part[pqa::kMsScales] = {};   // [ssf_sb][tiles][4] per scale
   int ms_tiles[pqa::kMsScales] = {};
   double* fs_part = nullptr;         // float_ssim: [ssf_sb][tiles][4]
   int fs_tiles = 0, fs_box = 1;
   int ssf_sb = 0;                    // frames per pass through the pyramid (bounds its memory at 2160p)
-  // CIEDE2000 (PQA_FEAT_CIEDE; ciede.hip): nothing is allocated unless the bit is set
+  // CIEDE2000 (PQA_FEAT_CIEDE; ciede.hip)
   double* ciede_part = nullptr;      // [B][ciede_tiles]
   int ciede_tiles_n = 0;
-  // CAMBI (PQA_FEAT_CAMBI; cambi.hip): nothing is allocated unless the bit is set
+  // CAMBI (PQA_FEAT_CAMBI; cambi.hip)
   pqa::CambiParams cambi_prm{};
   pqa::CambiWork cambi_wk{};
   int cambi_sb = 0;                  // frames per pass (bounds the work planes at 2160p)
-  // PSNR-HVS (PQA_FEAT_PSNR_HVS; psnr_hvs.hip): nothing is allocated unless the bit is set
-  double* ext2 = nullptr;            // [capacity][PQA_EXT2_DOUBLES] ring beside `records`
+  // PSNR-HVS (PQA_FEAT_PSNR_HVS; psnr_hvs.hip)
   pqa::PsnrHvsGeometry phv_geo{};
   double* phv_part = nullptr;        // [B][phv_geo.tile0[3]]
-  // XPSNR (PQA_FEAT_XPSNR; xpsnr.hip): nothing is allocated unless the bit is set
-  double* ext3 = nullptr;            // [capacity][PQA_EXT3_DOUBLES] ring beside `records`
+  // XPSNR (PQA_FEAT_XPSNR; xpsnr.hip)
   pqa::XpsnrGeometry xp_geo{};
   unsigned long long* xp_blk = nullptr;   // [B][xp_geo.n_blk][kXpBlockVals]
   double* xp_w = nullptr;                 // [B][xp_geo.n_blk] weights
   pqa::HistPlane xp_hist[2];              // reference luma planes the chain keeps (the last two of the last batch)
   pqa::host::FrameChain xp_chain{2};      // ... and which frames they are; pqa_set_ref_history arms them
   uint8_t* xp_prev = nullptr;        // pqa_submit_surfaces: its shifted prev_ref (allocated on first use)
-  // SI / TI (PQA_FEAT_SITI; siti.hip): nothing is allocated unless the bit is set
-  double* ext4 = nullptr;            // [capacity][PQA_EXT4_DOUBLES] ring beside `records`
+  // SI / TI (PQA_FEAT_SITI; siti.hip)
   double* st_part = nullptr;         // [B][2][siti_partials][4]
   pqa::HistPlane st_hist[2];              // the last luma plane of each clip's chain (0: distorted, 1: reference)
   pqa::host::FrameChain st_chain[2];      // pqa_set_dis_history / the reference history arm them
-  // capture integrity (PQA_FEAT_INTEGRITY; integrity.hip): nothing is allocated unless the bit is set
-  double* ext5 = nullptr;            // [capacity][PQA_EXT5_DOUBLES] ring beside `records`
+  // capture integrity (PQA_FEAT_INTEGRITY; integrity.hip)
   unsigned long long* ig_part = nullptr;      // [B][3][kIntegrityBlocks][2]
   pqa::HistPlane ig_hist[3];              // the planes of the last distorted frame of the chain
   pqa::host::FrameChain ig_chain;         // one index for the three; pqa_set_dis_history_planes arms them
@@ -241,6 +253,13 @@ int fail(pqa_ctx* c, int code, const char* fmt, ...);
     if (e_ != hipSuccess)                                                                        \
       return pqa::fail((c), e_ == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "%s failed: %s", #expr, \
                   hipGetErrorString(e_));                                                        \
+  } while (0)
+
+// a call that has set the error itself: its code goes up
+#define PQACHK(expr)                   \
+  do {                                 \
+    const int rc_ = (expr);            \
+    if (rc_ != PQA_OK) return rc_;     \
   } while (0)
 
 template <typename T>

@@ -876,59 +876,35 @@ class FeatureEngine:
         self._check(self.lib.pqa_collect(self._ctx, first_index, count, out.ctypes.data))
         return out
 
-    def collect_ext(self, first_index: int, count: int):
-        """(records [count, 24], ext [count, EXT_DOUBLES]): collect() plus the extension rows of the same frames
-        (pqa_collect_ext; float_ssim / float_ms_ssim slots, NaN where the context does not run them)."""
+    def collect_blocks(self, first_index: int, count: int, blocks=()):
+        """(records [count, 24], {i: rows [count, width of block i]}): collect() plus the rows of the same frames in the
+        extension blocks asked for (indices into N.EXT_BLOCKS; NaN where the context does not run the block's features).
+        One pqa_collect_ext5 call with NULL for every other block: nothing is allocated or copied for those."""
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
-        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
-        self._check(self.lib.pqa_collect_ext(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data))
-        return out, ext
+        got = {i: np.zeros((count, N.EXT_BLOCKS[i][1]), np.float64) for i in sorted(set(blocks))}
+        ptrs = [got[i].ctypes.data if i in got else None for i in range(len(N.EXT_BLOCKS))]
+        self._check(self.lib.pqa_collect_ext5(self._ctx, first_index, count, out.ctypes.data, *ptrs))
+        return out, got
+
+    def _collect_first(self, first_index: int, count: int, n_blocks: int):
+        out, got = self.collect_blocks(first_index, count, range(n_blocks))
+        return (out, *(got[i] for i in range(n_blocks)))
+
+    # (records, ext, ..., extN): the first N blocks of N.EXT_BLOCKS, as pqa_collect_ext ... pqa_collect_ext5 hand them out
+    def collect_ext(self, first_index: int, count: int):
+        return self._collect_first(first_index, count, 1)
 
     def collect_ext2(self, first_index: int, count: int):
-        """(records [count, 24], ext [count, EXT_DOUBLES], ext2 [count, EXT2_DOUBLES]): collect_ext() plus the second
-        extension rows of the same frames (pqa_collect_ext2; psnr_hvs slots, NaN where the context does not run it)."""
-        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
-        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
-        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
-        self._check(self.lib.pqa_collect_ext2(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
-                                              ext2.ctypes.data))
-        return out, ext, ext2
+        return self._collect_first(first_index, count, 2)
 
     def collect_ext3(self, first_index: int, count: int):
-        """(records, ext, ext2, ext3 [count, EXT3_DOUBLES]): collect_ext2() plus the third extension rows of the same
-        frames (pqa_collect_ext3; xpsnr slots, NaN where the context does not run it)."""
-        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
-        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
-        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
-        ext3 = np.zeros((count, N.EXT3_DOUBLES), np.float64)
-        self._check(self.lib.pqa_collect_ext3(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
-                                              ext2.ctypes.data, ext3.ctypes.data))
-        return out, ext, ext2, ext3
+        return self._collect_first(first_index, count, 3)
 
     def collect_ext4(self, first_index: int, count: int):
-        """(records, ext, ext2, ext3, ext4 [count, EXT4_DOUBLES]): collect_ext3() plus the fourth extension rows of the
-        same frames (pqa_collect_ext4; siti slots, NaN where the context does not run it)."""
-        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
-        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
-        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
-        ext3 = np.zeros((count, N.EXT3_DOUBLES), np.float64)
-        ext4 = np.zeros((count, N.EXT4_DOUBLES), np.float64)
-        self._check(self.lib.pqa_collect_ext4(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
-                                              ext2.ctypes.data, ext3.ctypes.data, ext4.ctypes.data))
-        return out, ext, ext2, ext3, ext4
+        return self._collect_first(first_index, count, 4)
 
     def collect_ext5(self, first_index: int, count: int):
-        """(records, ext, ext2, ext3, ext4, ext5 [count, EXT5_DOUBLES]): collect_ext4() plus the fifth extension rows of
-        the same frames (pqa_collect_ext5; integrity slots, NaN where the context does not run it)."""
-        out = np.zeros((count, N.RECORD_DOUBLES), np.float64)
-        ext = np.zeros((count, N.EXT_DOUBLES), np.float64)
-        ext2 = np.zeros((count, N.EXT2_DOUBLES), np.float64)
-        ext3 = np.zeros((count, N.EXT3_DOUBLES), np.float64)
-        ext4 = np.zeros((count, N.EXT4_DOUBLES), np.float64)
-        ext5 = np.zeros((count, N.EXT5_DOUBLES), np.float64)
-        self._check(self.lib.pqa_collect_ext5(self._ctx, first_index, count, out.ctypes.data, ext.ctypes.data,
-                                              ext2.ctypes.data, ext3.ctypes.data, ext4.ctypes.data, ext5.ctypes.data))
-        return out, ext, ext2, ext3, ext4, ext5
+        return self._collect_first(first_index, count, 5)
 
     def flush(self):
         self._check(self.lib.pqa_flush(self._ctx))

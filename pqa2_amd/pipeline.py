@@ -446,27 +446,17 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             i += m
             if progress is not None:
                 progress(i - a, b - a)
-        local_ext = local_ext2 = local_ext3 = local_ext4 = local_ext5 = None
-        if integrity:  # the fifth extension record is read only when integrity is on
-            local, local_ext, local_ext2, local_ext3, local_ext4, local_ext5 = eng.collect_ext5(a, b - a) if b > a else (
-                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
-                np.zeros((0, N.EXT3_DOUBLES)), np.zeros((0, N.EXT4_DOUBLES)), np.zeros((0, N.EXT5_DOUBLES)))
-        elif siti:       # the fourth extension record is read only when siti is on
-            local, local_ext, local_ext2, local_ext3, local_ext4 = eng.collect_ext4(a, b - a) if b > a else (
-                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
-                np.zeros((0, N.EXT3_DOUBLES)), np.zeros((0, N.EXT4_DOUBLES)))
-        elif xpsnr:    # the third extension record is read only when xpsnr is on
-            local, local_ext, local_ext2, local_ext3 = eng.collect_ext3(a, b - a) if b > a else (
-                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)),
-                np.zeros((0, N.EXT3_DOUBLES)))
-        elif psnr_hvs:   # the second extension record is read only when psnr_hvs is on: default calls stay as they were
-            local, local_ext, local_ext2 = eng.collect_ext2(a, b - a) if b > a else (
-                np.zeros((0, N.RECORD_DOUBLES)), np.zeros((0, N.EXT_DOUBLES)), np.zeros((0, N.EXT2_DOUBLES)))
-        elif want_ext:
-            local, local_ext = eng.collect_ext(a, b - a) if b > a else (np.zeros((0, N.RECORD_DOUBLES)),
-                                                                          np.zeros((0, N.EXT_DOUBLES)))
+        # the extension blocks (N.EXT_BLOCKS) this run reads, in one call; a default run stays on pqa_collect
+        want = [i for i, on in enumerate((want_ext, psnr_hvs, xpsnr, siti, integrity)) if on]
+        if b <= a:
+            local, local_blk = np.zeros((0, N.RECORD_DOUBLES)), {i: np.zeros((0, N.EXT_BLOCKS[i][1])) for i in want}
+        elif want and hasattr(eng, "collect_blocks"):
+            local, local_blk = eng.collect_blocks(a, b - a, want)
+        elif want:   # an engine_factory product from before collect_blocks: its collect_extN that reaches the last wanted block
+            got = getattr(eng, f"collect_ext{want[-1] + 1 if want[-1] else ''}")(a, b - a)
+            local, local_blk = got[0], {i: got[1 + i] for i in want}
         else:
-            local = eng.collect(a, b - a) if b > a else np.zeros((0, N.RECORD_DOUBLES))
+            local, local_blk = eng.collect(a, b - a), {}
     except BaseException:
         eng.close()
         raise
@@ -480,11 +470,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                                                     temporal_planes=3 if temporal_planes == "all" else 1,
                                                     edge_planes=(3 if grid_planes == "all" else 1) if coding_grid else 0)
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
-    ext = shard.gather_records(local_ext, n, world_size, rank, gather_device, width=N.EXT_DOUBLES) if want_ext else None
-    ext2 = shard.gather_records(local_ext2, n, world_size, rank, gather_device, width=N.EXT2_DOUBLES) if psnr_hvs else None
-    ext3 = shard.gather_records(local_ext3, n, world_size, rank, gather_device, width=N.EXT3_DOUBLES) if xpsnr else None
-    ext4 = shard.gather_records(local_ext4, n, world_size, rank, gather_device, width=N.EXT4_DOUBLES) if siti else None
-    ext5 = shard.gather_records(local_ext5, n, world_size, rank, gather_device, width=N.EXT5_DOUBLES) if integrity else None
+    blk = {i: shard.gather_records(local_blk[i], n, world_size, rank, gather_device, width=N.EXT_BLOCKS[i][1]) for i in want}
     if rank != 0:
         for rd in (converter, resampler, registered, coloured):
             if rd is not None:
@@ -497,6 +483,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         # inside a still run only, come from the distorted file through a context of its own, made on first use
         plane_sizes = [(di.width, di.height)] + ([(di.chroma_w, di.chroma_h)] * 2 if n_planes == 3 else [])
         sad_eng, cache = [], {}
+        ext5 = blk.pop(want[-1])   # the last block: its rows go into ig_result, not into finish_records
 
         def anchored_sad(anchor, i):
             if (anchor, i) not in cache:
@@ -518,19 +505,10 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             for e in sad_eng:
                 e.close()
     elapsed = time.perf_counter() - t_start
-    extra = {"ext": ext, "float_ssim": bool(float_ssim), "ms_ssim": bool(ms_ssim)} if want_ext else {}
-    if ciede:
-        extra["ciede"] = True
-    if cambi:
-        extra["cambi"] = True
-    if cambi_full_ref:
-        extra["cambi_full_ref"] = True
-    if psnr_hvs:
-        extra.update(ext2=ext2, psnr_hvs=True)
-    if xpsnr:
-        extra.update(ext3=ext3, xpsnr=True)
-    if siti:
-        extra.update(ext4=ext4, siti=True)
+    extra = {N.EXT_BLOCKS[i][0]: rows for i, rows in blk.items()}   # finish_records takes a block under its name in the table
+    flags = dict(float_ssim=float_ssim, ms_ssim=ms_ssim, ciede=ciede, cambi=cambi, cambi_full_ref=cambi_full_ref,
+                 psnr_hvs=psnr_hvs, xpsnr=xpsnr, siti=siti)
+    extra.update({k: True for k, v in flags.items() if v})
     if integrity:
         extra.update(integrity=ig_result)
     res = finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
@@ -1166,9 +1144,13 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         sv = rec[:, N.REC_SSIM:N.REC_SSIM + n_planes]
         ssim_lines = report.ssim_stats_lines(sv, plane_sizes)
         metrics["ssim"] = report.ssim_all(sv, plane_sizes)
+
+    def need(block, i, what):   # block i of N.EXT_BLOCKS, a row for every frame
+        if block is None or block.shape != (n, N.EXT_BLOCKS[i][1]):
+            raise ValueError(f"{what} extension records of every frame")
+
     if float_ssim or ms_ssim or ciede or cambi:
-        if ext is None or ext.shape != (n, N.EXT_DOUBLES):
-            raise ValueError("float_ssim / ms_ssim / ciede2000 / cambi need the extension records of every frame")
+        need(ext, 0, "float_ssim / ms_ssim / ciede2000 / cambi need the")
         if float_ssim:
             metrics["float_ssim"] = ext[:, N.EXT_FLOAT_SSIM].copy()
         if ms_ssim:
@@ -1184,15 +1166,13 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
                     metrics["cambi_full_reference"] = np.where(np.isnan(metrics["cambi"]) | np.isnan(src), np.nan,
                                                                np.maximum(metrics["cambi"] - src, 0.0))
     if psnr_hvs:
-        if ext2 is None or ext2.shape != (n, N.EXT2_DOUBLES):
-            raise ValueError("psnr_hvs needs the second extension records of every frame")
+        need(ext2, 1, "psnr_hvs needs the second")
         for key, slot in (("psnr_hvs_y", N.EXT2_PSNR_HVS_Y), ("psnr_hvs_cb", N.EXT2_PSNR_HVS_CB),
                           ("psnr_hvs_cr", N.EXT2_PSNR_HVS_CR), ("psnr_hvs", N.EXT2_PSNR_HVS)):
             metrics[key] = ext2[:, slot].copy()
     xpsnr_lines = xpsnr_summary = None
     if xpsnr:
-        if ext3 is None or ext3.shape != (n, N.EXT3_DOUBLES):
-            raise ValueError("xpsnr needs the third extension records of every frame")
+        need(ext3, 2, "xpsnr needs the third")
         for p, key in enumerate(("xpsnr_y", "xpsnr_u", "xpsnr_v")[:n_planes]):
             metrics[key] = ext3[:, N.EXT3_XPSNR_Y + p].copy()
         db = ext3[:, N.EXT3_XPSNR_Y:N.EXT3_XPSNR_Y + n_planes]
@@ -1200,8 +1180,7 @@ def finish_records(rec: np.ndarray, mdl: M.VmafModel, info, *, psnr: bool, ssim:
         xpsnr_lines = report.xpsnr_stats_lines(db)
         xpsnr_summary = report.xpsnr_summary(wsse, db, plane_sizes, info.bit_depth)
     if siti:
-        if ext4 is None or ext4.shape != (n, N.EXT4_DOUBLES):
-            raise ValueError("siti needs the fourth extension records of every frame")
+        need(ext4, 3, "siti needs the fourth")
         for key, slot in SITI_KEYS:
             metrics[key] = ext4[:, slot].copy()
     if integrity is not None:

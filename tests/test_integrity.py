@@ -289,6 +289,10 @@ class IntegrityEngine(OracleEngine):
         super().submit(index, ref_planes, dis_planes)
         self.dis[index] = [np.array(p) for p in dis_planes]
 
+    def collect_blocks(self, first, count, blocks):
+        got = self.collect_ext5(first, count)
+        return got[0], {i: got[1 + i] for i in blocks}
+
     def collect_ext5(self, first, count):
         from pqa2_amd import _native as N
         assert self.features & N.FEAT_INTEGRITY and self.thr is not None

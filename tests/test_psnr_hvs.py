@@ -241,6 +241,10 @@ class PsnrHvsEngine(OracleEngine):
         super().submit(index, ref_planes, dis_planes)
         self.frames[index] = ([np.array(p) for p in ref_planes], [np.array(p) for p in dis_planes])
 
+    def collect_blocks(self, first, count, blocks):
+        got = self.collect_ext2(first, count)
+        return got[0], {i: got[1 + i] for i in blocks}
+
     def collect_ext2(self, first, count):
         from pqa2_amd import _native as N
         ext = np.full((count, N.EXT_DOUBLES), np.nan)

@@ -175,6 +175,10 @@ class SitiEngine(OracleEngine):
         super().submit(index, ref_planes, dis_planes)
         self.frames[index] = (np.array(ref_planes[0]), np.array(dis_planes[0]))
 
+    def collect_blocks(self, first, count, blocks):
+        got = self.collect_ext4(first, count)
+        return got[0], {i: got[1 + i] for i in blocks}
+
     def collect_ext4(self, first, count):
         from pqa2_amd import _native as N
         idx = sorted(self.frames)

@@ -134,6 +134,10 @@ class SsimFamilyEngine(OracleEngine):
         super().submit(index, ref_planes, dis_planes)
         self.lumas[index] = (np.array(ref_planes[0]), np.array(dis_planes[0]))
 
+    def collect_blocks(self, first, count, blocks):
+        got = self.collect_ext(first, count)
+        return got[0], {i: got[1 + i] for i in blocks}
+
     def collect_ext(self, first, count):
         from pqa2_amd import _native as N
         ext = np.full((count, N.EXT_DOUBLES), np.nan)

@@ -93,7 +93,7 @@ def xpsnr_lines(ref_path, dis_path, use_gpu):
                            chroma_shift=(info.hshift, info.vshift), features=feats) as eng:
             for i in range(n):
                 eng.submit(i, rd.frame(i)[:planes], dd.frame(i)[:planes])
-            ext3 = eng.collect_ext3(0, n)[3]
+            ext3 = eng.collect_blocks(0, n, [2])[1][2]
         out["HIP kernels (csrc/xpsnr.hip)"] = report.xpsnr_stats_lines(ext3[:, :planes])
     return out
 

@@ -219,7 +219,7 @@ def psnr_hvs_columns(ref_path, dis_path, use_gpu, n):
                            chroma_shift=(info.hshift, info.vshift), features=N.FEAT_PSNR_HVS) as eng:
             for i, (r, d) in enumerate(frames):
                 eng.submit(i, r, d)
-            ext2 = eng.collect_ext2(0, n)[2]
+            ext2 = eng.collect_blocks(0, n, [1])[1][1]
         out["HIP kernel (csrc/psnr_hvs.hip)"] = {k: ext2[:, s] for k, s in zip(
             PSNR_HVS_KEYS, (N.EXT2_PSNR_HVS_Y, N.EXT2_PSNR_HVS_CB, N.EXT2_PSNR_HVS_CR, N.EXT2_PSNR_HVS))}
     return out

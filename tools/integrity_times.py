@@ -41,7 +41,7 @@ def run(w, h, feats, clip, n, rounds):
             us = t0.elapsed_time(t1) * 1e3 / n
             best = us if best is None else min(best, us)
         if feats & N.FEAT_INTEGRITY:     # the rows are what they should be: exact SADs of the resident frames
-            ext5 = eng.collect_ext5(0, n)[5]
+            ext5 = eng.collect_blocks(0, n, [4])[1][4]
             d = clip["dis"][0]
             want = (d[1:3].to(torch.int32) - d[0:2].to(torch.int32)).abs().sum(dim=(1, 2)).cpu().numpy()
             assert np.isnan(ext5[0, 0]) and (ext5[1:3, 0] == want).all() and (ext5[1:, :3] > 0).all()

@@ -39,7 +39,7 @@ def run(w, h, feats, clip, n, rounds):
             us = t0.elapsed_time(t1) * 1e3 / n
             best = us if best is None else min(best, us)
         if feats & N.FEAT_PSNR_HVS:
-            ext2 = eng.collect_ext2(0, n)[2]
+            ext2 = eng.collect_blocks(0, n, [1])[1][1]
             assert (ext2[:, :7] > 0).all() and torch.isfinite(torch.from_numpy(ext2[:, :7])).all()
     return best
 

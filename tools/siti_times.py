@@ -39,7 +39,7 @@ def run(w, h, feats, clip, n, rounds):
             us = t0.elapsed_time(t1) * 1e3 / n
             best = us if best is None else min(best, us)
         if feats & N.FEAT_SITI:
-            ext4 = eng.collect_ext4(0, n)[4]
+            ext4 = eng.collect_blocks(0, n, [3])[1][3]
             assert (ext4[:, 0] > 0).all() and (ext4[1:, 1] > 0).all() and torch.isfinite(torch.from_numpy(ext4[:, :4])).all()
     return best
 

@@ -41,7 +41,7 @@ def run(w, h, feats, clip, n, rounds):
             us = t0.elapsed_time(t1) * 1e3 / n
             best = us if best is None else min(best, us)
         if feats & N.FEAT_XPSNR:
-            ext3 = eng.collect_ext3(0, n)[3]
+            ext3 = eng.collect_blocks(0, n, [2])[1][2]
             assert (ext3[:, :6] > 0).all() and torch.isfinite(torch.from_numpy(ext3[:, :6])).all()
     return best
 
