@@ -11,7 +11,7 @@
 // Work.  A WAVE owns a block of 64 x 64 pixels, which holds the whole support of every coefficient of the six levels that
 // starts in it: no halo, no neighbour.  A workgroup of 256 threads is four such blocks, 128 x 128 pixels.  A lane owns 16 bytes
 // of R consecutive rows of both planes -- 16 x 4 samples of u8, 8 x 8 of u16 -- by one 16-byte load, four 4-byte loads or sample
-// by sample, whichever the base addresses and pitches of BOTH planes allow (tile_load_bytes of tile_moments.hip).  A lane whose
+// by sample, whichever the base addresses and pitches of BOTH planes allow (load_bytes of plane_scan.h).  A lane whose
 // 16 bytes would cross the end of the row reads sample by sample with the index held at the row's last sample, and a row
 // below the plane is read as the plane's last row: every address is a real sample's, nothing past a row's last sample is
 // touched.  Padding is NOT neutral for a Haar difference (a zero next to a sample is an edge), so nothing that was not
@@ -34,8 +34,7 @@
 // point anywhere.
 #include <type_traits>
 
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -45,50 +44,15 @@ constexpr int kBandGroup = 2 * kBandBlock; // pixels a workgroup covers each way
 constexpr int kBandMaxLevels = 6;
 constexpr int kBandWords = 4 * kBandSums;  // sums a level: 12
 
-struct BandArgs {
-  const void* ref;
-  const void* dis;
-  int64_t ref_rp, ref_fp, dis_rp, dis_fp;   // elements
-  int w, h, levels, gx, gy;
+struct BandArgs : PairPlanes {
+  int levels, gx, gy;
   unsigned top;
   long long* part;   // [frame][gy][gx][levels][4][3]
 };
 
-struct BandQuad {
-  unsigned d[4];
-};
-
-// the S = 16 / sizeof(T) samples x ... x + S - 1 of a row of w samples as four packed dwords.  VB: bytes of one load where
-// the whole 16 bytes lie inside the row (`full`); otherwise sample by sample, a sample past the end read as the row's last
-// one: it is a real address, and no coefficient that counts sees it.
-template <typename T, int VB>
-__device__ __forceinline__ BandQuad band_load(const T* row, int x, int w, bool full) {
-  constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-  BandQuad q;
-  if (full && VB == 16) {
-    const uint4 u = *reinterpret_cast<const uint4*>(row + x);
-    q.d[0] = u.x; q.d[1] = u.y; q.d[2] = u.z; q.d[3] = u.w;
-  } else if (full && VB == 4) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q.d[k] = *reinterpret_cast<const unsigned*>(row + x + k * PER);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      unsigned u = 0u;
-#pragma unroll 1   // rolled: unrolled, every sample's address is live at once
-      for (int s = PER - 1; s >= 0; --s) {
-        const int xx = x + k * PER + s;
-        u = (u << BITS) | (unsigned)row[xx < w ? xx : w - 1];
-      }
-      q.d[k] = u;
-    }
-  }
-  return q;
-}
-
 // sample k of a lane's row, clamped
 template <typename T>
-__device__ __forceinline__ int band_sample(const BandQuad& q, int k, unsigned top) {
+__device__ __forceinline__ int band_sample(const PackedQuad& q, int k, unsigned top) {
   constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
   const unsigned s = (q.d[k / PER] >> (BITS * (k % PER))) & ((1u << BITS) - 1u);
   return (int)(sizeof(T) == 1 ? s : (s < top ? s : top));
@@ -160,7 +124,7 @@ __device__ __forceinline__ void band_cross(int& ar, int& ad, int lv, int lane, i
 // level 1 inside a lane: R packed rows of S samples become R/2 x S/2 sums in r / d; (cx, cy): the lane's first coefficient
 // of this level in the plane
 template <typename T, typename Acc, int R, int S>
-__device__ __forceinline__ void band_lane_first(const BandQuad (&qr)[R], const BandQuad (&qd)[R], unsigned top, int (&r)[R / 2][S / 2],
+__device__ __forceinline__ void band_lane_first(const PackedQuad (&qr)[R], const PackedQuad (&qd)[R], unsigned top, int (&r)[R / 2][S / 2],
                                                 int (&d)[R / 2][S / 2], int cx, int cy, int wl, int hl, long long (&acc)[kBandWords]) {
   Acc part[kBandWords];
 #pragma unroll
@@ -221,13 +185,12 @@ __global__ __launch_bounds__(kBlock) void band_moments_kernel(const BandArgs a) 
     const T* pr = (const T*)a.ref + (int64_t)f * a.ref_fp;
     const T* pd = (const T*)a.dis + (int64_t)f * a.dis_fp;
     const int px = bx0 + (lane % LPR) * S, py = by0 + (lane / LPR) * R;   // the lane's first sample
-    BandQuad qr[R], qd[R];
-    const bool full = px + S <= a.w;
+    PackedQuad qr[R], qd[R];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
       const int y = py + k < a.h ? py + k : a.h - 1;   // a row below the plane: the last one, for no coefficient that counts
-      qr[k] = band_load<T, VB>(pr + (int64_t)y * a.ref_rp, px, a.w, full);
-      qd[k] = band_load<T, VB>(pd + (int64_t)y * a.dis_rp, px, a.w, full);
+      qr[k] = quad_load<T, VB, kTailRepeat>(pr + (int64_t)y * a.ref_rp, px, a.w);
+      qd[k] = quad_load<T, VB, kTailRepeat>(pd + (int64_t)y * a.dis_rp, px, a.w);
     }
     const int L = a.levels;
     long long acc[kBandWords];
@@ -292,14 +255,6 @@ hipError_t launch_v(hipStream_t stream, const BandArgs& a, int n_frames) {
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t stream, const BandArgs& a, int n_frames) {
-  const int vb = tile_load_bytes((int)sizeof(T), a.ref, a.ref_rp, a.ref_fp, a.dis, a.dis_rp, a.dis_fp);
-  if (vb == 16) return launch_v<T, 16>(stream, a, n_frames);
-  if (vb == 4) return launch_v<T, 4>(stream, a, n_frames);
-  return launch_v<T, (int)sizeof(T)>(stream, a, n_frames);
-}
-
 }  // namespace
 
 bool band_levels_ok(int levels) { return levels >= 1 && levels <= kBandMaxLevels; }
@@ -316,19 +271,17 @@ hipError_t launch_band_moments(hipStream_t stream, Elem elem, int bits, const vo
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int levels, void* part, unsigned long long* out) {
   if (n_frames <= 0) return hipSuccess;
-  if ((bits != 8 && bits != 10 && bits != 12) || (elem == ELEM_U8) != (bits == 8) || !band_levels_ok(levels) || w < 1 || h < 1 ||
-      w > 8192 || h > 8192)
-    return hipErrorInvalidValue;
   BandArgs a{};
-  a.ref = ref; a.dis = dis;
-  a.ref_rp = ref_row_pitch; a.ref_fp = ref_frame_pitch; a.dis_rp = dis_row_pitch; a.dis_fp = dis_frame_pitch;
-  a.w = w; a.h = h; a.levels = levels;
+  if (!band_levels_ok(levels) ||
+      !pair_planes(a, elem, bits, ref, ref_row_pitch, ref_frame_pitch, dis, dis_row_pitch, dis_frame_pitch, w, h))
+    return hipErrorInvalidValue;
+  a.levels = levels;
   a.gx = (w + kBandGroup - 1) / kBandGroup; a.gy = (h + kBandGroup - 1) / kBandGroup;
   a.top = (1u << bits) - 1u;
   a.part = (long long*)part;
-  hipError_t e = hipErrorInvalidValue;
-  if (elem == ELEM_U8) e = launch_t<uint8_t>(stream, a, n_frames);
-  if (elem == ELEM_U16) e = launch_t<uint16_t>(stream, a, n_frames);
+  const hipError_t e = dispatch(elem, load_bytes(elem, a), [&](auto t, auto vb) {
+    return launch_v<decltype(t), decltype(vb)::value>(stream, a, n_frames);
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(band_finish_kernel, dim3(levels * kBandWords, n_frames), dim3(64), 0, stream, (const long long*)part,
                      a.gx * a.gy, levels * kBandWords, out);

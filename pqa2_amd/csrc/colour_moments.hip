@@ -36,8 +36,7 @@
 // Luma in int32: |m00| < 2^28 and three products below 2^16 * 2^12 each, plus 2^13, stay below 2^31.  Chroma in int64.  The
 // shifts are arithmetic.  A workgroup owns 256 x 16 chroma samples and the luma under them; every input sample is read once
 // (a clamped edge sample again by its own lane), every output sample written once, rows and columns outside a plane never.
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -69,11 +68,6 @@ struct ColApplyArgs {
   int m[12];
 };
 
-template <typename T, int N>
-struct alignas(sizeof(T) * N) ColVec {
-  T s[N];
-};
-
 // What a lane reads of one clip at one chroma row: four chroma samples, the block sums of the luma under them and its
 // smallest and largest sample; KEEP: the luma samples themselves too.
 template <int HS, int VS, bool KEEP>
@@ -96,8 +90,8 @@ __device__ __forceinline__ void col_load(ColBlock<HS, VS, KEEP>& b, const T* Y, 
   const T* ur = U + (int64_t)cy * urp;
   const T* vr = V + (int64_t)cy * vrp;
   if (fast) {
-    const ColVec<T, kColLane> uu = *reinterpret_cast<const ColVec<T, kColLane>*>(ur + cx0);
-    const ColVec<T, kColLane> vv = *reinterpret_cast<const ColVec<T, kColLane>*>(vr + cx0);
+    const SampleVec<T, kColLane> uu = *reinterpret_cast<const SampleVec<T, kColLane>*>(ur + cx0);
+    const SampleVec<T, kColLane> vv = *reinterpret_cast<const SampleVec<T, kColLane>*>(vr + cx0);
 #pragma unroll
     for (int k = 0; k < kColLane; ++k) {
       b.u[k] = col_sample(uu.s[k], top);
@@ -123,7 +117,7 @@ __device__ __forceinline__ void col_load(ColBlock<HS, VS, KEEP>& b, const T* Y, 
     const T* row = Y + (int64_t)ly * yrp;
     unsigned s[NX];
     if (fast) {
-      const ColVec<T, NX> r = *reinterpret_cast<const ColVec<T, NX>*>(row + lx0);
+      const SampleVec<T, NX> r = *reinterpret_cast<const SampleVec<T, NX>*>(row + lx0);
 #pragma unroll
       for (int i = 0; i < NX; ++i) s[i] = col_sample(r.s[i], top);
     } else {
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void colour_apply_kernel(const ColApplyArgs
     for (int j = 0; j < NY; ++j) {
       const int ly = (cy << VS) + j;
       if (ly >= a.h) break;
-      ColVec<T, NX> o;
+      SampleVec<T, NX> o;
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         const int k = i >> HS;
@@ -267,14 +261,14 @@ __global__ __launch_bounds__(kBlock) void colour_apply_kernel(const ColApplyArgs
       }
       T* row = Yo + (int64_t)ly * a.drp[0];
       if (fast) {
-        *reinterpret_cast<ColVec<T, NX>*>(row + lx0) = o;
+        *reinterpret_cast<SampleVec<T, NX>*>(row + lx0) = o;
       } else {
 #pragma unroll
         for (int i = 0; i < NX; ++i)
           if (lx0 + i < a.w) row[lx0 + i] = o.s[i];
       }
     }
-    ColVec<T, kColLane> ou, ov;
+    SampleVec<T, kColLane> ou, ov;
 #pragma unroll
     for (int k = 0; k < kColLane; ++k) {
       const long long sy = (long long)b.sy[k], su = (long long)S * b.u[k], sv = (long long)S * b.v[k];
@@ -286,8 +280,8 @@ __global__ __launch_bounds__(kBlock) void colour_apply_kernel(const ColApplyArgs
     T* urow = Uo + (int64_t)cy * a.drp[1];
     T* vrow = Vo + (int64_t)cy * a.drp[2];
     if (fast) {
-      *reinterpret_cast<ColVec<T, kColLane>*>(urow + cx0) = ou;
-      *reinterpret_cast<ColVec<T, kColLane>*>(vrow + cx0) = ov;
+      *reinterpret_cast<SampleVec<T, kColLane>*>(urow + cx0) = ou;
+      *reinterpret_cast<SampleVec<T, kColLane>*>(vrow + cx0) = ov;
     } else {
 #pragma unroll
       for (int k = 0; k < kColLane; ++k)

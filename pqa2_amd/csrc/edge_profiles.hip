@@ -15,7 +15,7 @@
 // of both planes in registers, so a vertical difference costs no load of its own; before its first row it loads the row above
 // its run (the row itself at the top of the plane: the differences of row line 0 are then zero).  A lane owns kEdgeLane = 16
 // columns of the stripe whatever the load width: with loads of V samples (16 bytes, 4 bytes or one sample, whichever the base
-// addresses and pitches of BOTH clips allow -- tile_load_bytes of tile_moments.hip; the host decides once per launch) load j of a
+// addresses and pitches of BOTH clips allow -- load_bytes of plane_scan.h; the host decides once per launch) load j of a
 // row covers the columns x0 + (64 j + lane) V ... + V - 1, j < 16 / V.  A load that would cross the end of the row is read
 // sample by sample and takes zeros past the end, so nothing beyond a row's last sample is touched.  A wave loads kEdgeRows = 2
 // rows of both planes before it works on them.
@@ -37,7 +37,7 @@
 // there is.  After a barrier the workgroup adds the non-zero entries of its table to the zeroed output with 64-bit integer
 // global atomics: the bands of a stripe meet there.
 // Rows.  A lane adds the products of its 16 columns in 32 bits (16 top^2 <= 16 * 4095^2 < 2^29).  The two unsigned sums go
-// through the DPP steps of line_profiles.hip's wave sum: 16 lanes, 256 products, stay below 256 * 4095^2 = 4 292 870 400 < 2^32.
+// through the DPP steps of wave_sum_u32 (plane_scan.h): 16 lanes, 256 products, stay below 256 * 4095^2 = 4 292 870 400 < 2^32.
 // The signed sum does NOT fit that way (256 * 4095^2 > 2^31): it stops one DPP step earlier, at the sums of 8 lanes,
 // 128 * 4095^2 = 2 146 435 200 <= 2^31 - 1 = 2 147 483 647 in magnitude, and the eight of them are read and added in 64 bits.
 // One lane adds the triple to the output with 64-bit atomics: the stripes of a row meet there.  Every lane of a wave runs every
@@ -46,8 +46,7 @@
 // (__mul24 and an add; the squares too); see DESIGN.md section 5 for why not the packed dot products.
 // Integer sums do not depend on order: the result is independent of scheduling, base address, pitch and tail.  No floating
 // point anywhere.  Output: a line of 8192 samples of +-4095 keeps |sum| <= 2^13 * 4095^2 < 2^37.
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -56,68 +55,11 @@ constexpr int kEdgeLane = kEdgeStripe / 64;   // columns of a lane
 constexpr int kEdgeRows = 2;                  // rows of both planes a wave loads before it works on them
 constexpr int kEdgeRun = kEdgeBand / (kBlock / 64);   // consecutive rows of a wave
 
-struct EdgeArgs {
-  const void *ref, *dis;
-  int64_t ref_rp, ref_fp, dis_rp, dis_fp;   // elements
-  int w, h, flush_u, flush_s;
+struct EdgeArgs : PairPlanes {
+  int flush_u, flush_s;
   unsigned top;
   unsigned long long* out;   // [frame][h + w][3], zeroed
 };
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) EdgeVec {
-  T s[V];
-};
-
-// the samples x ... x + V - 1 of a row that ends before x1, none above top; zeros past the end
-template <typename T, int V>
-__device__ __forceinline__ EdgeVec<T, V> edge_load(const T* row, int x, int x1, unsigned top) {
-  EdgeVec<T, V> v;
-  if (x + V <= x1) {
-    v = *reinterpret_cast<const EdgeVec<T, V>*>(row + x);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v.s[k] = x + k < x1 ? row[x + k] : (T)0;
-  }
-  if constexpr (sizeof(T) > 1) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v.s[k] = (T)min((unsigned)v.s[k], top);
-  }
-  return v;
-}
-
-// Wave64 sums of one 32-bit value per lane, exact, returned wave-uniform in 64 bits; the DPP controls of wave_sum_f32
-// (pqa_device.h) with an integer add.  Every lane of the wave must be active.
-template <int CTRL>
-__device__ __forceinline__ unsigned edge_dpp_add(unsigned v) {
-  return v + (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-// unsigned: four steps leave the sum of each row of 16 lanes in its lane 15; each must fit 32 bits
-__device__ __forceinline__ unsigned long long edge_wave_sum_u32(unsigned v) {
-  v = edge_dpp_add<0xb1>(v);    // quad_perm:[1,0,3,2]
-  v = edge_dpp_add<0x4e>(v);    // quad_perm:[2,3,0,1]
-  v = edge_dpp_add<0x114>(v);   // row_shr:4
-  v = edge_dpp_add<0x118>(v);   // row_shr:8   -> lane 15 of each row holds the row sum
-  return (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 15) + (unsigned)__builtin_amdgcn_readlane((int)v, 31) +
-         (unsigned)__builtin_amdgcn_readlane((int)v, 47) + (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-// signed: three steps leave the sum of lanes 16 r ... 16 r + 7 in lane 16 r + 7 and of lanes 16 r + 8 ... 16 r + 15 in lane
-// 16 r + 15 (two's complement adds: the unsigned add above is the signed one); each must fit int32, 8 lanes of at most
-// 16 top^2 in magnitude: 128 * 4095^2 = 2 146 435 200 <= 2^31 - 1.  One step more (256 * 4095^2) would not.
-__device__ __forceinline__ long long edge_wave_sum_i32(int s) {
-  unsigned v = (unsigned)s;
-  v = edge_dpp_add<0xb1>(v);
-  v = edge_dpp_add<0x4e>(v);
-  v = edge_dpp_add<0x114>(v);   // lanes 4 ... 15 of a row: their quad and the one before
-  long long t = 0;
-#pragma unroll
-  for (int l = 7; l < 64; l += 8) t += (long long)__builtin_amdgcn_readlane((int)v, l);
-  return t;
-}
-
-__device__ __forceinline__ void edge_lds_add(unsigned long long* p, unsigned long long v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // VB: bytes of one load
 template <typename T, int VB>
@@ -149,8 +91,8 @@ __global__ __launch_bounds__(kBlock) void edge_profiles_kernel(const EdgeArgs a)
     for (int j = 0; j < NL; ++j)
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        edge_lds_add(tab + kEdgeSums * col_of(j, k), ca[j * V + k]);
-        edge_lds_add(tab + kEdgeSums * col_of(j, k) + 1, cb[j * V + k]);
+        lds_add(tab + kEdgeSums * col_of(j, k), ca[j * V + k]);
+        lds_add(tab + kEdgeSums * col_of(j, k) + 1, cb[j * V + k]);
         ca[j * V + k] = cb[j * V + k] = 0u;
       }
   };
@@ -159,25 +101,25 @@ __global__ __launch_bounds__(kBlock) void edge_profiles_kernel(const EdgeArgs a)
     for (int j = 0; j < NL; ++j)
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        edge_lds_add(tab + kEdgeSums * col_of(j, k) + 2, (unsigned long long)(long long)cx[j * V + k]);
+        lds_add(tab + kEdgeSums * col_of(j, k) + 2, (unsigned long long)(long long)cx[j * V + k]);
         cx[j * V + k] = 0;
       }
   };
 
-  EdgeVec<T, V> pr[NL], pd[NL];   // the row above the one in work
+  SampleVec<T, V> pr[NL], pd[NL];   // the row above the one in work
   if (ya < yb) {
     const int yp = max(ya - 1, 0);
     const T *rrow = ref + (int64_t)yp * a.ref_rp, *drow = dis + (int64_t)yp * a.dis_rp;
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
-      pr[j] = edge_load<T, V>(rrow, x0 + col_of(j, 0), x1, a.top);
-      pd[j] = edge_load<T, V>(drow, x0 + col_of(j, 0), x1, a.top);
+      pr[j] = vec_load<T, V>(rrow, x0 + col_of(j, 0), x1, a.top);
+      pd[j] = vec_load<T, V>(drow, x0 + col_of(j, 0), x1, a.top);
     }
   }
 
   int since_u = 0, since_s = 0;   // rows in the 32-bit column sums
   for (int y = ya; y < yb; y += kEdgeRows) {   // wave-uniform
-    EdgeVec<T, V> cr[kEdgeRows][NL], cd[kEdgeRows][NL];
+    SampleVec<T, V> cr[kEdgeRows][NL], cd[kEdgeRows][NL];
     unsigned lr[kEdgeRows][NL], ld[kEdgeRows][NL];   // lane 0: the samples left of its loads
 #pragma unroll
     for (int r = 0; r < kEdgeRows; ++r) {
@@ -186,8 +128,8 @@ __global__ __launch_bounds__(kBlock) void edge_profiles_kernel(const EdgeArgs a)
         const T *rrow = ref + (int64_t)yy * a.ref_rp, *drow = dis + (int64_t)yy * a.dis_rp;
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-          cr[r][j] = edge_load<T, V>(rrow, x0 + col_of(j, 0), x1, a.top);
-          cd[r][j] = edge_load<T, V>(drow, x0 + col_of(j, 0), x1, a.top);
+          cr[r][j] = vec_load<T, V>(rrow, x0 + col_of(j, 0), x1, a.top);
+          cd[r][j] = vec_load<T, V>(drow, x0 + col_of(j, 0), x1, a.top);
           const int xg = x0 + j * 64 * V;   // lane 0's first column of load j
           lr[r][j] = ld[r][j] = 0u;
           if (lane == 0 && xg > 0 && xg <= x1) {   // column xg - 1 < x1 <= w exists
@@ -231,8 +173,8 @@ __global__ __launch_bounds__(kBlock) void edge_profiles_kernel(const EdgeArgs a)
         pr[j] = cr[r][j];
         pd[j] = cd[r][j];
       }
-      const unsigned long long A = edge_wave_sum_u32(sa), B = edge_wave_sum_u32(sb);
-      const long long X = edge_wave_sum_i32(sx);
+      const unsigned long long A = wave_sum_u32(sa), B = wave_sum_u32(sb);
+      const long long X = wave_sum_i32(sx);
       if (lane == 0 && (A | B)) {   // row line 0 and a flat row add nothing
         atomicAdd(rows + kEdgeSums * (int64_t)yy, A);
         atomicAdd(rows + kEdgeSums * (int64_t)yy + 1, B);
@@ -269,15 +211,6 @@ hipError_t launch_v(hipStream_t stream, const EdgeArgs& a, int n_frames) {
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t stream, const EdgeArgs& a, int n_frames) {
-  // the widest load every row start of BOTH clips is aligned to; a stripe starts a multiple of 16 bytes into its row
-  const int vb = tile_load_bytes((int)sizeof(T), a.ref, a.ref_rp, a.ref_fp, a.dis, a.dis_rp, a.dis_fp);
-  if (vb == 16) return launch_v<T, 16>(stream, a, n_frames);
-  if (vb == 4) return launch_v<T, 4>(stream, a, n_frames);
-  return launch_v<T, (int)sizeof(T)>(stream, a, n_frames);
-}
-
 }  // namespace
 
 size_t edge_out_bytes(int w, int h, int n_frames) {
@@ -293,20 +226,18 @@ hipError_t launch_edge_profiles(hipStream_t stream, Elem elem, int bits, const v
                                 int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                 int n_frames, int w, int h, unsigned long long* out) {
   if (n_frames <= 0) return hipSuccess;
-  if (w < 1 || h < 1 || w > 8192 || h > 8192 || (bits != 8 && bits != 10 && bits != 12) || (elem == ELEM_U8) != (bits == 8))
+  EdgeArgs a{};
+  if (!pair_planes(a, elem, bits, ref, ref_row_pitch, ref_frame_pitch, dis, dis_row_pitch, dis_frame_pitch, w, h))
     return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(out, 0, edge_out_bytes(w, h, n_frames), stream);
   if (e != hipSuccess) return e;
-  EdgeArgs a{};
-  a.ref = ref; a.ref_rp = ref_row_pitch; a.ref_fp = ref_frame_pitch;
-  a.dis = dis; a.dis_rp = dis_row_pitch; a.dis_fp = dis_frame_pitch;
-  a.w = w; a.h = h; a.out = out;
+  a.out = out;
   a.top = (1u << bits) - 1u;
   a.flush_u = edge_flush_rows(bits, false);   // >= 256
   a.flush_s = edge_flush_rows(bits, true);    // >= 128
-  if (elem == ELEM_U8) return launch_t<uint8_t>(stream, a, n_frames);
-  if (elem == ELEM_U16) return launch_t<uint16_t>(stream, a, n_frames);
-  return hipErrorInvalidValue;
+  // a stripe starts a multiple of 16 bytes into its row
+  return dispatch(elem, load_bytes(elem, a),
+                  [&](auto t, auto vb) { return launch_v<decltype(t), decltype(vb)::value>(stream, a, n_frames); });
 }
 
 }  // namespace pqa

@@ -26,8 +26,7 @@
 //   12 bit: |gx| <= 32 760, |dt| <= 65 520: gx dt <= 2 146 435 200 < 2^31 but dt^2 = 4 292 870 400 > 2^31: products and lane
 //   sums are int64 in the u16 instance (a sample above m is read as m so that the bounds hold).
 //   A tile of 64 x 64 pixels sums at most 4096 * 65 520^2 < 2^45.
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -37,11 +36,8 @@ constexpr int kFlowLds = kFlowBlock + 2;     // with the halo
 constexpr int kFlowPitch = kFlowLds + 1;     // dwords a row of the LDS tile
 constexpr int kFlowRows = kFlowBlock / (kBlock / 64);   // rows a wave walks: 16
 
-struct FlowArgs {
-  const void* ref;
-  const void* dis;
-  int64_t ref_rp, ref_fp, dis_rp, dis_fp;   // elements
-  int w, h, tile, tx, ty, maxv;
+struct FlowArgs : PairPlanes {
+  int tile, tx, ty, maxv;
   long long* out;   // [frame][ty][tx][6]
 };
 
@@ -141,13 +137,11 @@ hipError_t launch_flow_moments(hipStream_t stream, Elem elem, int bits, const vo
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int tile, long long* out) {
   if (n_frames <= 0) return hipSuccess;
-  if ((bits != 8 && bits != 10 && bits != 12) || (elem == ELEM_U8) != (bits == 8) || !flow_tile_ok(tile) || w < 3 || h < 3 ||
-      w > 8192 || h > 8192)
-    return hipErrorInvalidValue;
   FlowArgs a{};
-  a.ref = ref; a.dis = dis;
-  a.ref_rp = ref_row_pitch; a.ref_fp = ref_frame_pitch; a.dis_rp = dis_row_pitch; a.dis_fp = dis_frame_pitch;
-  a.w = w; a.h = h; a.tile = tile; a.tx = (w + tile - 1) / tile; a.ty = (h + tile - 1) / tile; a.maxv = (1 << bits) - 1;
+  if (!flow_tile_ok(tile) || w < 3 || h < 3 ||
+      !pair_planes(a, elem, bits, ref, ref_row_pitch, ref_frame_pitch, dis, dis_row_pitch, dis_frame_pitch, w, h))
+    return hipErrorInvalidValue;
+  a.tile = tile; a.tx = (w + tile - 1) / tile; a.ty = (h + tile - 1) / tile; a.maxv = (1 << bits) - 1;
   a.out = out;
   const dim3 grid((w + kFlowBlock - 1) / kFlowBlock, (h + kFlowBlock - 1) / kFlowBlock, n_frames);
   if (elem == ELEM_U8) hipLaunchKernelGGL(flow_moments_kernel<uint8_t>, grid, dim3(kBlock), 0, stream, a);

@@ -517,9 +517,6 @@ constexpr int kTileSums = 6;    // sums a tile
 constexpr int kTileChunk = 8;   // frame pairs per launch of the two entries
 bool tile_size_ok(int tile);
 size_t tile_out_bytes(int w, int h, int tile, int n_frames);
-// bytes of one load (16, 4 or esize) the launch takes for these base addresses and pitches (in elements)
-int tile_load_bytes(int esize, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
-                    int64_t dis_row_pitch, int64_t dis_frame_pitch);
 hipError_t launch_tile_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int tile, unsigned long long* out);

@@ -25,8 +25,9 @@
 // and once at the end of the span; at the end a wave whose lanes all hold the same level adds them up with shuffles and one
 // lane updates LDS.  A flat span costs one update a wave; 64-pixel runs at 8 bit cost one update per lane and load (16
 // samples) instead of 16; noise costs one update per sample, on mostly different addresses.
-#include "kernels.h"
-#include "pqa_device.h"
+#include <climits>
+
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -34,11 +35,8 @@ namespace {
 constexpr int kLevelSpan = 32768;   // samples of one workgroup: the bound the u32 accumulators rest on
 constexpr int kLevelSeg = 16384;    // widest column segment, a multiple of every load width
 
-struct LevelArgs {
-  const void* ref;
-  const void* dis;
-  int64_t ref_rp, ref_fp, dis_rp, dis_fp;   // elements
-  int w, h, L, segs, rows;
+struct LevelArgs : PairPlanes {
+  int L, segs, rows;
   unsigned long long* out;   // [frame][L][3], zeroed
 };
 
@@ -46,10 +44,6 @@ struct Run {
   unsigned key = 0, cnt = 0, sd = 0;
   unsigned long long sd2 = 0;
 };
-
-__device__ __forceinline__ void lds_add(unsigned long long* p, unsigned long long v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 __device__ __forceinline__ void run_flush(unsigned long long* tab, int L, const Run& r) {
   lds_add(tab + r.key, ((unsigned long long)r.cnt << 32) | r.sd);
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void level_stats_kernel(const LevelArgs a) 
         run_step(tab, L, run, rr[x], dd[x]);
       } else {
         if (x + V <= x1) {
-          struct alignas(VB) Vec { T s[V]; };
+          using Vec = SampleVec<T, V>;
           const Vec vr = *reinterpret_cast<const Vec*>(rr + x), vd = *reinterpret_cast<const Vec*>(dd + x);
 #pragma unroll
           for (int k = 0; k < V; ++k) run_step(tab, L, run, vr.s[k], vd.s[k]);
@@ -150,17 +144,6 @@ hipError_t launch_v(hipStream_t stream, const LevelArgs& a, int n_frames) {
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t stream, const LevelArgs& a, int n_frames) {
-  constexpr int64_t es = sizeof(T);
-  // the widest load every row start of both planes is aligned to; a segment starts a multiple of 16 bytes into its row
-  const uint64_t bits = (uint64_t)(uintptr_t)a.ref | (uint64_t)(uintptr_t)a.dis | (uint64_t)(a.ref_rp * es) |
-                        (uint64_t)(a.dis_rp * es) | (uint64_t)(a.ref_fp * es) | (uint64_t)(a.dis_fp * es);
-  if (bits % 16 == 0) return launch_v<T, 16>(stream, a, n_frames);
-  if (bits % 4 == 0) return launch_v<T, 4>(stream, a, n_frames);
-  return launch_v<T, (int)es>(stream, a, n_frames);
-}
-
 }  // namespace
 
 size_t level_out_bytes(int bit_depth, int n_frames) {
@@ -171,22 +154,22 @@ hipError_t launch_level_stats(hipStream_t stream, Elem elem, int bit_depth, cons
                               int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                               int n_frames, int w, int h, unsigned long long* out) {
   if (n_frames <= 0) return hipSuccess;
-  if (w < 1 || h < 1 || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (elem == ELEM_U8) != (bit_depth == 8))
+  LevelArgs a{};
+  // no bound on w and h here: a column segment and a span bound what a workgroup sees
+  if (!pair_planes(a, elem, bit_depth, ref, ref_row_pitch, ref_frame_pitch, dis, dis_row_pitch, dis_frame_pitch, w, h, INT_MAX))
     return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(out, 0, level_out_bytes(bit_depth, n_frames), stream);
   if (e != hipSuccess) return e;
-  LevelArgs a{};
-  a.ref = ref; a.dis = dis; a.ref_rp = ref_row_pitch; a.ref_fp = ref_frame_pitch; a.dis_rp = dis_row_pitch;
-  a.dis_fp = dis_frame_pitch; a.w = w; a.h = h; a.L = 1 << bit_depth; a.out = out;
+  a.L = 1 << bit_depth; a.out = out;
   a.segs = (w + kLevelSeg - 1) / kLevelSeg;
   const int seg_w = w < kLevelSeg ? w : kLevelSeg;
   // rows * seg_w <= kLevelSpan samples a workgroup; a quarter of that at 8 bit, where the 256-level table costs little to
   // merge and more workgroups fill the chip on a single frame
   a.rows = (bit_depth == 8 ? kLevelSpan / 4 : kLevelSpan) / seg_w;
   if (a.rows < 1) a.rows = 1;   // seg_w <= kLevelSeg <= kLevelSpan: one row never exceeds the span
-  if (elem == ELEM_U8) return launch_t<uint8_t>(stream, a, n_frames);
-  if (elem == ELEM_U16) return launch_t<uint16_t>(stream, a, n_frames);
-  return hipErrorInvalidValue;
+  // a segment starts a multiple of 16 bytes into its row
+  return dispatch(elem, load_bytes(elem, a),
+                  [&](auto t, auto vb) { return launch_v<decltype(t), decltype(vb)::value>(stream, a, n_frames); });
 }
 
 }  // namespace pqa

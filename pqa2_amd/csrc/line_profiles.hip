@@ -22,13 +22,12 @@
 // all there is.  After a barrier the workgroup adds the non-zero entries of its table to the zeroed output with 64-bit integer
 // global atomics: the bands of a stripe meet there.
 // Rows.  A lane adds the 16 samples of its columns and their squares in uint32 (16 top^2 <= 16 * 4095^2 < 2^29), the wave adds
-// the lanes with the DPP steps of pqa_device.h's wave sum (wave_sum_u32 below: the sums of 16 lanes, 256 samples, stay below 256 * 4095^2
+// the lanes with the DPP steps of pqa_device.h's wave sum (wave_sum_u32 of plane_scan.h: the sums of 16 lanes, 256 samples, stay below 256 * 4095^2
 // = 4 292 870 400 < 2^32; the four of them are added in 64 bits), and one lane adds the pair to the output with 64-bit
 // atomics: the stripes of a row meet there.  Every lane of a wave runs every row step: the DPP steps read all 64 lanes.
 // Integer sums do not depend on order: the result is independent of scheduling, base address, pitch and tail.  No floating
 // point anywhere.  Output: a plane of 8192 x 8192 samples of 4095 keeps a line's squares below 2^13 * 2^24 = 2^37.
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -43,46 +42,6 @@ struct ProfArgs {
   unsigned top;
   unsigned long long* out;   // [frame][h + w][2], zeroed
 };
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) ProfVec {
-  T s[V];
-};
-
-// the samples x ... x + V - 1 of a row that ends before x1; zeros past the end
-template <typename T, int V>
-__device__ __forceinline__ ProfVec<T, V> prof_load(const T* row, int x, int x1) {
-  ProfVec<T, V> v;
-  if (x + V <= x1) {
-    v = *reinterpret_cast<const ProfVec<T, V>*>(row + x);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v.s[k] = x + k < x1 ? row[x + k] : (T)0;
-  }
-  return v;
-}
-
-// Wave64 sum of one uint32 per lane, exact, returned wave-uniform in 64 bits: the first four DPP steps of wave_sum_f32
-// (pqa_device.h; the same controls, an integer add in place of dpp_add's float one) leave the sum of each row of 16 lanes in
-// its lane 15 -- every one of them must fit 32 bits -- and the four row sums are read and added in 64 bits.  Every lane of the
-// wave must be active.  It lives here and not beside wave_sum_f32 because pqa_device.h is part of the source hash the
-// committed counters of the VIF and ADM kernels are tied to (bench.py, kernel_source_hash).
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_add_u32(unsigned v) {
-  return v + (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ unsigned long long wave_sum_u32(unsigned v) {
-  v = dpp_add_u32<0xb1>(v);    // quad_perm:[1,0,3,2]
-  v = dpp_add_u32<0x4e>(v);    // quad_perm:[2,3,0,1]
-  v = dpp_add_u32<0x114>(v);   // row_shr:4
-  v = dpp_add_u32<0x118>(v);   // row_shr:8   -> lane 15 of each row holds the row sum
-  return (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)v, 15) + (unsigned)__builtin_amdgcn_readlane((int)v, 31) +
-         (unsigned)__builtin_amdgcn_readlane((int)v, 47) + (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-__device__ __forceinline__ void prof_lds_add(unsigned long long* p, unsigned long long v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // VB: bytes of one load
 template <typename T, int VB>
@@ -108,23 +67,23 @@ __global__ __launch_bounds__(kBlock) void line_profiles_kernel(const ProfArgs a)
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         const int col = (j * 64 + lane) * V + k;   // < kProfStripe
-        prof_lds_add(tab + 2 * col, cs[j * V + k]);
-        prof_lds_add(tab + 2 * col + 1, cq[j * V + k]);
+        lds_add(tab + 2 * col, cs[j * V + k]);
+        lds_add(tab + 2 * col + 1, cq[j * V + k]);
         cs[j * V + k] = cq[j * V + k] = 0u;
       }
   };
 
   int since = 0;   // rows in the uint32 column sums
   for (int y = y0 + wv; y < y1; y += kWaves * kProfRows) {   // wave-uniform
-    ProfVec<T, V> v[kProfRows][NL];
+    SampleVec<T, V> v[kProfRows][NL];
 #pragma unroll
     for (int r = 0; r < kProfRows; ++r) {
       const int yy = y + kWaves * r;
       const T* row = plane + (int64_t)yy * a.rp;
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
-        if (yy < y1) v[r][j] = prof_load<T, V>(row, x0 + (j * 64 + lane) * V, x1);
-        else v[r][j] = ProfVec<T, V>{};
+        if (yy < y1) v[r][j] = vec_load<T, V>(row, x0 + (j * 64 + lane) * V, x1);
+        else v[r][j] = SampleVec<T, V>{};
       }
     }
 #pragma unroll
@@ -174,16 +133,6 @@ hipError_t launch_v(hipStream_t stream, const ProfArgs& a, int n_frames) {
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t stream, const ProfArgs& a, int n_frames) {
-  constexpr int64_t es = sizeof(T);
-  // the widest load every row start is aligned to; a stripe starts a multiple of 16 bytes into its row
-  const uint64_t bits = (uint64_t)(uintptr_t)a.base | (uint64_t)(a.rp * es) | (uint64_t)(a.fp * es);
-  if (bits % 16 == 0) return launch_v<T, 16>(stream, a, n_frames);
-  if (bits % 4 == 0) return launch_v<T, 4>(stream, a, n_frames);
-  return launch_v<T, (int)es>(stream, a, n_frames);
-}
-
 }  // namespace
 
 size_t profile_out_bytes(int w, int h, int n_frames) {
@@ -198,18 +147,16 @@ int profile_flush_rows(int bit_depth) {
 hipError_t launch_line_profiles(hipStream_t stream, Elem elem, int bit_depth, const void* base, int64_t row_pitch,
                                 int64_t frame_pitch, int n_frames, int w, int h, unsigned long long* out) {
   if (n_frames <= 0) return hipSuccess;
-  if (w < 1 || h < 1 || w > 8192 || h > 8192 || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) ||
-      (elem == ELEM_U8) != (bit_depth == 8))
-    return hipErrorInvalidValue;
+  if (!scan_shape_ok(elem, bit_depth, w, h)) return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(out, 0, profile_out_bytes(w, h, n_frames), stream);
   if (e != hipSuccess) return e;
   ProfArgs a{};
   a.base = base; a.rp = row_pitch; a.fp = frame_pitch; a.w = w; a.h = h; a.out = out;
   a.top = (1u << bit_depth) - 1u;
   a.flush = profile_flush_rows(bit_depth);   // >= 256 > kProfRows
-  if (elem == ELEM_U8) return launch_t<uint8_t>(stream, a, n_frames);
-  if (elem == ELEM_U16) return launch_t<uint16_t>(stream, a, n_frames);
-  return hipErrorInvalidValue;
+  // a stripe starts a multiple of 16 bytes into its row
+  return dispatch(elem, load_bytes(elem, base, row_pitch, frame_pitch),
+                  [&](auto t, auto vb) { return launch_v<decltype(t), decltype(vb)::value>(stream, a, n_frames); });
 }
 
 }  // namespace pqa

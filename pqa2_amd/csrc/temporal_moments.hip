@@ -13,7 +13,7 @@
 // of one transition at a time, wave w its rows 16 w ... 16 w + 15; a lane owns 16 bytes of one row of the four planes
 // R_k, R_{k-1}, D_k, D_{k-1} -- 16 samples of u8, 8 of u16 -- as four packed dwords each: one pass at 8 bit, two at 10 / 12 bit
 // (all loaded before any is added up).  The dwords arrive by one 16-byte load, four 4-byte loads or sample by sample, whichever
-// the base addresses and pitches of BOTH clips allow (tile_load_bytes of tile_moments.hip).  A lane whose 16 bytes would cross
+// the base addresses and pitches of BOTH clips allow (load_bytes of plane_scan.h).  A lane whose 16 bytes would cross
 // the end of the row reads sample by sample and takes zeros past the end; a lane below the plane takes zeros.  A zero in all
 // four planes adds nothing to any sum, so an edge tile holds the pixels that exist and nothing past a row's last sample is
 // touched.
@@ -54,8 +54,7 @@
 // barrier a thread per (tile, sum) adds the tile's segments top to bottom in int64 and stores the word.  Every output word is
 // written once: no zeroing.  A whole 64 x 64 tile of 4095^2 is below 2^36.  Integer sums: the result does not depend on order,
 // base address, pitch, load width or launch shape.  No floating point.
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -64,51 +63,17 @@ constexpr int kTmpBlock = 64;   // pixels a workgroup covers each way
 constexpr int kTmpRows = kTmpBlock / (kBlock / 64);   // rows of a wave: 16
 constexpr int kTmpRaw = 14;     // raw sums of a lane
 
-struct TemporalArgs {
-  const void* ref;
-  const void* dis;
-  int64_t ref_rp, ref_fp, dis_rp, dis_fp;   // elements
-  int w, h, tile, tx, ty, n_trans;
+struct TemporalArgs : PairPlanes {
+  int tile, tx, ty, n_trans;
   unsigned top2;   // top in both halves of a dword
   unsigned long long* out;   // [transition][ty][tx][7]
 };
 
 typedef unsigned short tmp_u16x2 __attribute__((ext_vector_type(2)));
 
-struct TmpQuad {
-  unsigned d[4];
-};
-
 template <typename T> struct TmpWide;
 template <> struct TmpWide<uint8_t> { using type = int; };
 template <> struct TmpWide<uint16_t> { using type = long long; };
-
-// the S = 16 / sizeof(T) samples x ... x + S - 1 of a row that ends before x1 as four packed dwords; zeros past the end.
-// VB: bytes of one load where the whole 16 bytes lie inside the row.
-template <typename T, int VB>
-__device__ __forceinline__ TmpQuad tmp_load(const T* row, int x, int x1) {
-  constexpr int S = 16 / (int)sizeof(T), PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-  TmpQuad q;
-  if (x + S <= x1 && VB == 16) {
-    const uint4 v = *reinterpret_cast<const uint4*>(row + x);
-    q.d[0] = v.x; q.d[1] = v.y; q.d[2] = v.z; q.d[3] = v.w;
-  } else if (x + S <= x1 && VB == 4) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q.d[k] = *reinterpret_cast<const unsigned*>(row + x + k * PER);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      unsigned v = 0u;
-#pragma unroll
-      for (int s = 0; s < PER; ++s) {
-        const int xx = x + k * PER + s;
-        if (xx < x1) v |= (unsigned)row[xx] << (BITS * s);
-      }
-      q.d[k] = v;
-    }
-  }
-  return q;
-}
 
 // adds the 14 raw sums of one dword of packed samples of each plane to acc: rk / rp: R_k / R_{k-1}, dk / dp: D_k / D_{k-1}
 template <typename T>
@@ -167,18 +132,18 @@ __device__ __forceinline__ void tmp_combine(const unsigned (&q)[kTmpRaw], int (&
 
 // the lane's 16 bytes of its P rows of one frame pair
 template <typename T, int VB, int P, int RPW>
-__device__ __forceinline__ void tmp_load_pair(const TemporalArgs& a, int f, int y0, int x, TmpQuad (&qr)[P], TmpQuad (&qd)[P]) {
+__device__ __forceinline__ void tmp_load_pair(const TemporalArgs& a, int f, int y0, int x, PackedQuad (&qr)[P], PackedQuad (&qd)[P]) {
   const T* pr = (const T*)a.ref + (int64_t)f * a.ref_fp;
   const T* pd = (const T*)a.dis + (int64_t)f * a.dis_fp;
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int y = y0 + p * RPW;
-    if (y < a.h) {   // y >= 0, x >= 0; tmp_load keeps x below w
-      qr[p] = tmp_load<T, VB>(pr + (int64_t)y * a.ref_rp, x, a.w);
-      qd[p] = tmp_load<T, VB>(pd + (int64_t)y * a.dis_rp, x, a.w);
+    if (y < a.h) {   // y >= 0, x >= 0; quad_load keeps x below w
+      qr[p] = quad_load<T, VB, kTailZeros>(pr + (int64_t)y * a.ref_rp, x, a.w);
+      qd[p] = quad_load<T, VB, kTailZeros>(pd + (int64_t)y * a.dis_rp, x, a.w);
     } else {
-      qr[p] = TmpQuad{};
-      qd[p] = TmpQuad{};
+      qr[p] = PackedQuad{};
+      qd[p] = PackedQuad{};
     }
   }
 }
@@ -202,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void temporal_moments_kernel(const Temporal
   const int y0 = by0 + wv * kTmpRows + lrow;
   const int tr0 = WALK ? 0 : blockIdx.z, tr1 = WALK ? a.n_trans : tr0 + 1;   // transition tr: frames tr and tr + 1
 
-  TmpQuad qrk[P], qrp[P], qdk[P], qdp[P];
+  PackedQuad qrk[P], qrp[P], qdk[P], qdp[P];
   tmp_load_pair<T, VB, P, RPW>(a, tr0, y0, bx0 + xc, qrp, qdp);
   for (int tr = tr0; tr < tr1; ++tr) {
     tmp_load_pair<T, VB, P, RPW>(a, tr + 1, y0, bx0 + xc, qrk, qdk);
@@ -275,14 +240,6 @@ hipError_t launch_v(hipStream_t stream, const TemporalArgs& a, bool walk) {
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t stream, const TemporalArgs& a, bool walk) {
-  const int vb = tile_load_bytes((int)sizeof(T), a.ref, a.ref_rp, a.ref_fp, a.dis, a.dis_rp, a.dis_fp);
-  if (vb == 16) return launch_v<T, 16>(stream, a, walk);
-  if (vb == 4) return launch_v<T, 4>(stream, a, walk);
-  return launch_v<T, (int)sizeof(T)>(stream, a, walk);
-}
-
 }  // namespace
 
 size_t temporal_out_bytes(int w, int h, int tile, int n_frames) {
@@ -294,19 +251,16 @@ hipError_t launch_temporal_moments(hipStream_t stream, Elem elem, int bits, cons
                                    int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                    int n_frames, int w, int h, int tile, bool walk, unsigned long long* out) {
   if (n_frames <= 1) return hipSuccess;
-  if ((bits != 8 && bits != 10 && bits != 12) || (elem == ELEM_U8) != (bits == 8) || !tile_size_ok(tile) || w < 1 || h < 1 ||
-      w > 8192 || h > 8192)
-    return hipErrorInvalidValue;
   TemporalArgs a{};
-  a.ref = ref; a.dis = dis;
-  a.ref_rp = ref_row_pitch; a.ref_fp = ref_frame_pitch; a.dis_rp = dis_row_pitch; a.dis_fp = dis_frame_pitch;
-  a.w = w; a.h = h; a.tile = tile; a.tx = (w + tile - 1) / tile; a.ty = (h + tile - 1) / tile;
+  if (!tile_size_ok(tile) ||
+      !pair_planes(a, elem, bits, ref, ref_row_pitch, ref_frame_pitch, dis, dis_row_pitch, dis_frame_pitch, w, h))
+    return hipErrorInvalidValue;
+  a.tile = tile; a.tx = (w + tile - 1) / tile; a.ty = (h + tile - 1) / tile;
   a.n_trans = n_frames - 1;
   a.top2 = ((1u << bits) - 1u) * 0x00010001u;
   a.out = out;
-  if (elem == ELEM_U8) return launch_t<uint8_t>(stream, a, walk);
-  if (elem == ELEM_U16) return launch_t<uint16_t>(stream, a, walk);
-  return hipErrorInvalidValue;
+  return dispatch(elem, load_bytes(elem, a),
+                  [&](auto t, auto vb) { return launch_v<decltype(t), decltype(vb)::value>(stream, a, walk); });
 }
 
 }  // namespace pqa

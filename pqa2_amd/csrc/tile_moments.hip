@@ -32,8 +32,7 @@
 // segment's six sums to LDS; after a barrier a thread per (tile, sum) adds the tile's T / min(T, 16) segments top to bottom
 // in uint64 and stores the result.  Every output word is written once: no zeroing.  A whole 64 x 64 tile of 4095^2 is below
 // 2^36.  Integer sums: the result does not depend on order, base address, pitch, load width or launch shape.  No floating point.
-#include "kernels.h"
-#include "pqa_device.h"
+#include "plane_scan.h"
 
 namespace pqa {
 namespace {
@@ -41,51 +40,17 @@ namespace {
 constexpr int kTileBlock = 64;   // pixels a workgroup covers each way
 constexpr int kTileRows = kTileBlock / (kBlock / 64);   // rows of a wave: 16
 
-struct TileArgs {
-  const void* ref;
-  const void* dis;
-  int64_t ref_rp, ref_fp, dis_rp, dis_fp;   // elements
-  int w, h, tile, tx, ty;
+struct TileArgs : PairPlanes {
+  int tile, tx, ty;
   unsigned top2;   // top in both halves of a dword
   unsigned long long* out;   // [frame][ty][tx][6]
 };
 
 typedef unsigned short tile_u16x2 __attribute__((ext_vector_type(2)));
 
-struct TileQuad {
-  unsigned d[4];
-};
-
 template <typename T> struct TileWide;
 template <> struct TileWide<uint8_t> { using type = unsigned; };
 template <> struct TileWide<uint16_t> { using type = unsigned long long; };
-
-// the S = 16 / sizeof(T) samples x ... x + S - 1 of a row that ends before x1 as four packed dwords; zeros past the end.
-// VB: bytes of one load where the whole 16 bytes lie inside the row.
-template <typename T, int VB>
-__device__ __forceinline__ TileQuad tile_load(const T* row, int x, int x1) {
-  constexpr int S = 16 / (int)sizeof(T), PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-  TileQuad q;
-  if (x + S <= x1 && VB == 16) {
-    const uint4 v = *reinterpret_cast<const uint4*>(row + x);
-    q.d[0] = v.x; q.d[1] = v.y; q.d[2] = v.z; q.d[3] = v.w;
-  } else if (x + S <= x1 && VB == 4) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q.d[k] = *reinterpret_cast<const unsigned*>(row + x + k * PER);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      unsigned v = 0u;
-#pragma unroll
-      for (int s = 0; s < PER; ++s) {
-        const int xx = x + k * PER + s;
-        if (xx < x1) v |= (unsigned)row[xx] << (BITS * s);
-      }
-      q.d[k] = v;
-    }
-  }
-  return q;
-}
 
 // adds the six sums of two dwords of packed samples to acc
 template <typename T>
@@ -128,16 +93,16 @@ __global__ __launch_bounds__(kBlock) void tile_moments_kernel(const TileArgs a) 
   const int lrow = lane / LPR, xc = (lane % LPR) * S;   // the lane's row of a pass, its first column in the block
   const int seg_rows = a.tile < kTileRows ? a.tile : kTileRows;
 
-  TileQuad qr[P], qd[P];
+  PackedQuad qr[P], qd[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int y = by0 + wv * kTileRows + p * RPW + lrow;
-    if (y < a.h) {   // y >= 0, bx0 + xc >= 0; tile_load keeps x below w
-      qr[p] = tile_load<T, VB>(pr + (int64_t)y * a.ref_rp, bx0 + xc, a.w);
-      qd[p] = tile_load<T, VB>(pd + (int64_t)y * a.dis_rp, bx0 + xc, a.w);
+    if (y < a.h) {   // y >= 0, bx0 + xc >= 0; quad_load keeps x below w
+      qr[p] = quad_load<T, VB, kTailZeros>(pr + (int64_t)y * a.ref_rp, bx0 + xc, a.w);
+      qd[p] = quad_load<T, VB, kTailZeros>(pd + (int64_t)y * a.dis_rp, bx0 + xc, a.w);
     } else {
-      qr[p] = TileQuad{};
-      qd[p] = TileQuad{};
+      qr[p] = PackedQuad{};
+      qd[p] = PackedQuad{};
     }
   }
 
@@ -197,14 +162,6 @@ hipError_t launch_v(hipStream_t stream, const TileArgs& a, int n_frames) {
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t stream, const TileArgs& a, int n_frames) {
-  const int vb = tile_load_bytes((int)sizeof(T), a.ref, a.ref_rp, a.ref_fp, a.dis, a.dis_rp, a.dis_fp);
-  if (vb == 16) return launch_v<T, 16>(stream, a, n_frames);
-  if (vb == 4) return launch_v<T, 4>(stream, a, n_frames);
-  return launch_v<T, (int)sizeof(T)>(stream, a, n_frames);
-}
-
 }  // namespace
 
 bool tile_size_ok(int tile) { return tile == 8 || tile == 16 || tile == 32 || tile == 64; }
@@ -214,30 +171,19 @@ size_t tile_out_bytes(int w, int h, int tile, int n_frames) {
          sizeof(unsigned long long);
 }
 
-// the widest load every lane of both planes is aligned to; a lane starts a multiple of 16 bytes into its row
-int tile_load_bytes(int esize, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
-                    int64_t dis_row_pitch, int64_t dis_frame_pitch) {
-  const uint64_t bits = (uint64_t)(uintptr_t)ref | (uint64_t)(uintptr_t)dis |
-                        (uint64_t)((ref_row_pitch | ref_frame_pitch | dis_row_pitch | dis_frame_pitch) * esize);
-  return bits % 16 == 0 ? 16 : bits % 4 == 0 ? 4 : esize;
-}
-
 hipError_t launch_tile_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                int n_frames, int w, int h, int tile, unsigned long long* out) {
   if (n_frames <= 0) return hipSuccess;
-  if ((bits != 8 && bits != 10 && bits != 12) || (elem == ELEM_U8) != (bits == 8) || !tile_size_ok(tile) || w < 1 || h < 1 ||
-      w > 8192 || h > 8192)
-    return hipErrorInvalidValue;
   TileArgs a{};
-  a.ref = ref; a.dis = dis;
-  a.ref_rp = ref_row_pitch; a.ref_fp = ref_frame_pitch; a.dis_rp = dis_row_pitch; a.dis_fp = dis_frame_pitch;
-  a.w = w; a.h = h; a.tile = tile; a.tx = (w + tile - 1) / tile; a.ty = (h + tile - 1) / tile;
+  if (!tile_size_ok(tile) ||
+      !pair_planes(a, elem, bits, ref, ref_row_pitch, ref_frame_pitch, dis, dis_row_pitch, dis_frame_pitch, w, h))
+    return hipErrorInvalidValue;
+  a.tile = tile; a.tx = (w + tile - 1) / tile; a.ty = (h + tile - 1) / tile;
   a.top2 = ((1u << bits) - 1u) * 0x00010001u;
   a.out = out;
-  if (elem == ELEM_U8) return launch_t<uint8_t>(stream, a, n_frames);
-  if (elem == ELEM_U16) return launch_t<uint16_t>(stream, a, n_frames);
-  return hipErrorInvalidValue;
+  return dispatch(elem, load_bytes(elem, a),
+                  [&](auto t, auto vb) { return launch_v<decltype(t), decltype(vb)::value>(stream, a, n_frames); });
 }
 
 }  // namespace pqa

@@ -85,6 +85,28 @@ def test_tails_pitches_and_depths(bpc):
         assert np.array_equal(_resident(eng, cbuf, dbuf2, 4, 3), want)
 
 
+@pytest.mark.parametrize("bpc,lead,pad,load", [(8, 0, 7, 16), (8, 4, 7, 4), (8, 1, 6, 1), (10, 0, 7, 16), (10, 2, 7, 4), (10, 1, 6, 2)])
+def test_every_load_width_with_a_row_that_ends_inside_a_load(bpc, lead, pad, load):
+    """201 x 72: full loads, a row that ends one sample into a load of 16 / 8 / 4 / 2 samples, 18 rows a wave.  Rows of 208
+    samples from an aligned base: the 16-byte loads; the base 4 bytes in: the word loads (at 10 bit 201 = 100 * 2 + 1, the tail
+    the 50-sample rows above do not have); rows of 207 samples, base one sample in: sample by sample"""
+    import torch
+    w, h = 201, 72
+    ref, dis = R.random_pair(90 + bpc + lead, 2, w, h, bpc)
+    rbuf, _ = _padded(ref, pad=pad, lead=lead)
+    dbuf, _ = _padded(dis, pad=pad, lead=lead)
+    es = rbuf.dtype.itemsize
+    tr = torch.from_numpy(rbuf.view(np.uint8).reshape(-1)).cuda()
+    td = torch.from_numpy(dbuf.view(np.uint8).reshape(-1)).cuda()
+    torch.cuda.synchronize()
+    pr, pd = tr.data_ptr() + lead * es, td.data_ptr() + lead * es
+    bits = pr | pd | rbuf.strides[1] | rbuf.strides[0] | dbuf.strides[1] | dbuf.strides[0]
+    assert (16 if bits % 16 == 0 else 4 if bits % 4 == 0 else es) == load      # load_bytes of plane_scan.h
+    with _engine(w, h, bpc) as eng:
+        got = eng.level_stats_resident(pr, rbuf.strides[1], rbuf.strides[0], pd, dbuf.strides[1], dbuf.strides[0], 2)
+    assert np.array_equal(got, R.level_stats(ref, dis, bpc))
+
+
 def test_chroma_plane_of_a_420_context():
     """plane = 1 of a 50 x 18 4:2:0 context: 25 x 9 samples; luma-sized frames are refused for it"""
     ref, dis = R.random_pair(21, 2, 25, 9)

@@ -44,7 +44,7 @@ def _resident(eng, rbuf, rlead, dbuf, dlead, n, shape, tile):
     torch.cuda.synchronize()
     pr, pd = tr.data_ptr() + rlead * es, td.data_ptr() + dlead * es
     bits = pr | pd | rbuf.strides[1] | rbuf.strides[0] | dbuf.strides[1] | dbuf.strides[0]
-    load = 16 if bits % 16 == 0 else 4 if bits % 4 == 0 else es      # launch_t of temporal_moments.hip
+    load = 16 if bits % 16 == 0 else 4 if bits % 4 == 0 else es      # load_bytes of plane_scan.h
     got = eng.temporal_moments_resident(pr, rbuf.strides[1], rbuf.strides[0], pd, dbuf.strides[1], dbuf.strides[0], shape, n, tile)
     return got, load
 
