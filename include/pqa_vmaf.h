@@ -952,6 +952,13 @@ PQA_API int pqa_debug_vif_march_shape(uint32_t width, uint32_t height, int32_t* 
  * means the tiled kernel runs there (one workgroup per tile).  PQA_EINVAL on a null pointer, another scale or n_frames = 0. */
 PQA_API int pqa_debug_vif_strip_shape(pqa_ctx* ctx, uint32_t scale, uint32_t n_frames, int32_t* out4);
 
+/* Test hook (host only): where the ADM march kernels compute anything at all for a width x height frame -- the dependency
+ * cone of libvmaf's 10 % accumulation windows (pqa2_amd/csrc/adm_need.h; PQA_ADM_CONE=0 at pqa_create computes whole bands
+ * instead).  out20 = per ADM scale 0 .. 3 {row lo, row hi, column lo, column hi} of the coefficient positions (half-open),
+ * then {row lo, row hi, column lo, column hi} of the input samples they read.  PQA_EINVAL on a null pointer or a size of
+ * 0 or above 65536. */
+PQA_API int pqa_debug_adm_need(uint32_t width, uint32_t height, int32_t* out20);
+
 /* Test hook (needs a device): the CIEDE2000 device function of the PQA_FEAT_CIEDE kernel on n Lab pairs
  * lab_pairs[n][6] = {L1, a1, b1, L2, a2, b2}: the inputs are converted to f32, de_out[n] receives the f32 results widened.
  * PQA_EDEVICE without a device (text in pqa_last_error(NULL)), PQA_EINVAL on a null pointer or n < 0. */

@@ -67,7 +67,7 @@ EXPORTS = [
     "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_submit_packed", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
     "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
-    "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape",
+    "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape", "pqa_debug_adm_need",
     "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
     "pqa_debug_psnr_hvs_tables", "pqa_debug_psnr_hvs_plane", "pqa_debug_xpsnr_blocks", "pqa_debug_siti_plane",
     "pqa_debug_resample_table", "pqa_debug_colour",
@@ -314,6 +314,7 @@ def load():
     lib.pqa_debug_vif_march_table.argtypes = [vp, i32]
     lib.pqa_debug_vif_march_shape.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(i32 * 6)]
     lib.pqa_debug_vif_strip_shape.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i32 * 4)]
+    lib.pqa_debug_adm_need.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(i32 * 20)]
     lib.pqa_debug_ciede2000.argtypes = [vp, i32, vp]
     lib.pqa_debug_cambi_params.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, i32]
     lib.pqa_debug_cambi_cmap.argtypes = [vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int64, vp]

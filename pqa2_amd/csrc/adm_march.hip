@@ -21,7 +21,11 @@
 //            rolling pair of registers: row i - 1 is finished (threshold, numerator cubes) right after row i's sum exists.
 // Rows are partitioned into segments at the rows of libvmaf's accumulation window [top, bottom) (10 % crop): segments
 // outside it -- and whole stripes outside [left, right) -- only owe the approximation band the next scale reads (the low
-// half of both passes: 12 of the 32 packed FMAs, no decouple, no masking).  A segment inside recomputes ONE row above and
+// half of both passes: 12 of the 32 packed FMAs, no decouple, no masking), and the next scale, cropped by the same rule,
+// reads it only inside the dependency cone of the deeper windows (adm_need.h): such segments march the needed rows only,
+// a stripe without a needed column is idle, and no column outside the range is stored.  What is never written is never
+// read by a lane whose sums count: a halo lane may load a stale column, and its values end in masked columns only.
+// A segment inside recomputes ONE row above and
 // ONE below (the masking box's neighbours): (L + 2) / L instead of 16 / 14 vertically; horizontally 64 lanes for 60 columns
 // as before.  Column masks are applied once per wave (to the lane's sums), row masks do not exist.
 // Stripes that touch the left / right image edge (mirrored input columns) and planes whose rows are not aligned for the
@@ -29,6 +33,7 @@
 #include <type_traits>
 
 #include "adm_chain.h"
+#include "adm_need.h"
 #include "kernels.h"
 #include "pqa_device.h"
 
@@ -50,6 +55,7 @@ struct AdmMarchArgs {
   int left, top, right, bottom;            // accumulation window in band coordinates
   int reg_start[4];                        // row regions [0, top), [top, bottom), [bottom, oh): starts, reg_start[3] = oh
   int seg_rows[3], seg_first[4];           // rows per segment of a region; first segment id of a region, seg_first[3] = total
+  int need_r0, need_r1, need_c0, need_c1;  // band rows / columns at which anything must be computed (adm_need.h)
   float inv_scale, gain_limit, rf_hv, rf_d, k_hv, k_d;
   float* ll_ref;
   float* ll_dis;
@@ -275,11 +281,15 @@ __global__ __launch_bounds__(kBlock, PQA_ADM_MARCH_OCC) void adm_march_kernel(co
   const int stripe = sg * 4 + wave;
   double* __restrict__ part = a.partials + ((int64_t)fr * a.n_part + (int64_t)id * 4 + wave) * 6;
   const int region = seg >= a.seg_first[2] ? 2 : seg >= a.seg_first[1] ? 1 : 0;
-  const int r0 = a.reg_start[region] + (seg - a.seg_first[region]) * a.seg_rows[region];
-  const int r1 = min(r0 + a.seg_rows[region], a.reg_start[region + 1]);
+  int r0 = a.reg_start[region] + (seg - a.seg_first[region]) * a.seg_rows[region];
+  int r1 = min(r0 + a.seg_rows[region], a.reg_start[region + 1]);
+  // above and below the window only the needed rows are owed (the window itself lies inside the needed range); the
+  // segments and their partial slots stay those of the whole band, so the sums over the slots group as they always did
+  if (region != 1) { r0 = max(r0, a.need_r0); r1 = min(r1, a.need_r1); }
   const int cs = stripe * kStripe;
   const bool in_win = region == 1 && cs < a.right && cs + kStripe > a.left;   // wave-uniform
-  if (stripe >= a.n_stripes || (!in_win && !a.ll_ref)) {   // idle wave of the last group / nothing owed at the last scale
+  const bool owed = a.ll_ref && r0 < r1 && cs < a.need_c1 && cs + kStripe > a.need_c0;   // a band the next scale reads
+  if (stripe >= a.n_stripes || (!in_win && !owed)) {   // idle: a wave of the last group beyond the band / nothing owed
     if (lane < 6) part[lane] = 0.0;
     return;
   }
@@ -288,8 +298,8 @@ __global__ __launch_bounds__(kBlock, PQA_ADM_MARCH_OCC) void adm_march_kernel(co
   float* __restrict__ ll_r = a.ll_ref ? a.ll_ref + (int64_t)fr * a.ll_frame_pitch_r : nullptr;
   float* __restrict__ ll_d = a.ll_ref ? a.ll_dis + (int64_t)fr * a.ll_frame_pitch_d : nullptr;
   const int c = cs - kHalo + lane;
-  // lanes with a band column of their own store it; the others carry an offset no buffer is large enough for
-  const unsigned ll_voff = (lane >= kHalo && lane < kHalo + kStripe && c < a.ow) ? (unsigned)c * 4u : 0x80000000u;
+  // lanes with a needed band column of their own store it; the others carry an offset no buffer is large enough for
+  const unsigned ll_voff = (lane >= kHalo && lane < kHalo + kStripe && c >= a.need_c0 && c < a.need_c1) ? (unsigned)c * 4u : 0x80000000u;
   // every input column of the stripe (halo lanes included) inside the image and rows aligned for two-sample loads?
   const bool fast = a.aligned && cs >= kHalo && 2 * (cs + kStripe + kHalo - 1) + 1 < a.w;   // wave-uniform
   const unsigned bytes_r = (unsigned)a.h * a.pitch_r * (unsigned)sizeof(T), bytes_d = (unsigned)a.h * a.pitch_d * (unsigned)sizeof(T);
@@ -360,7 +370,7 @@ int adm_march_partials(int band_w, int band_h) {
 
 bool launch_adm_march(hipStream_t stream, int scale, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames, int w, int h,
                       float inv_scale, float gain_limit, MutPlaneRun ll_ref, MutPlaneRun ll_dis, double* partials,
-                      int* n_partials, hipError_t* err) {
+                      int* n_partials, bool cone, hipError_t* err) {
   const int es = elem == ELEM_U8 ? 1 : elem == ELEM_U16 ? 2 : 4;
   // 32-bit buffer offsets: a plane (and an approximation band) must stay below 2 GiB
   if ((int64_t)ref.row_pitch * h * es >= (1ll << 31) || (int64_t)dis.row_pitch * h * es >= (1ll << 31)) return false;
@@ -385,6 +395,9 @@ bool launch_adm_march(hipStream_t stream, int scale, Elem elem, PlaneRun ref, Pl
   const Partition p = partition_rows(a.oh, a.top, a.bottom, a.n_stripes);
   for (int r = 0; r < 4; ++r) { a.reg_start[r] = p.reg_start[r]; a.seg_first[r] = p.seg_first[r]; }
   for (int r = 0; r < 3; ++r) a.seg_rows[r] = p.seg_rows[r];
+  AdmSpan need_rows, need_cols;
+  adm_need_scale(scale, w, h, cone, &need_rows, &need_cols);
+  a.need_r0 = need_rows.lo; a.need_r1 = need_rows.hi; a.need_c0 = need_cols.lo; a.need_c1 = need_cols.hi;
   a.inv_scale = inv_scale; a.gain_limit = gain_limit;
   a.rf_hv = 1.0f / adm_dwt_quant_step(scale, 1);
   a.rf_d = 1.0f / adm_dwt_quant_step(scale, 2);

@@ -20,12 +20,15 @@
 // A wave owns 60 scale-1 columns (lanes 2..61) = 120 scale-0 columns = 240 input columns and a segment of scale-1 rows
 // [R0, R1); it computes scale-0 rows 2 R0 - 3 .. 2 R1 + 2 (three above and below for scale 1's window and box) and scale-1
 // rows R0 - 1 .. R1.  The decouple / masking chain of a row runs only where some coefficient of it can reach an accumulated
-// threshold (wave-uniform tests against libvmaf's 10 % crop); elsewhere a row costs the low half of the filters.
+// threshold (wave-uniform tests against libvmaf's 10 % crop); elsewhere a row costs the low half of the filters -- and is
+// marched at all only inside the dependency cone of the deeper scales' windows (adm_need.h): a segment clamps its scale-1
+// rows to the needed range, a stripe without a needed column is idle, and the band is stored only inside the range.
 // Taken for frames whose width and height are multiples of 4 and at least 128 (every broadcast format; the band mirrors then
 // touch one column / row per scale); everything else runs one scale per launch.
 #include <type_traits>
 
 #include "adm_chain.h"
+#include "adm_need.h"
 #include "kernels.h"
 #include "pqa_device.h"
 
@@ -47,6 +50,7 @@ struct PyramidArgs {
   int n_stripes, n_sg, seg_rows, n_seg;    // seg_rows: scale-1 rows per segment
   int n_frames;
   int left0, top0, right0, bottom0, left1, top1, right1, bottom1;
+  int nr0, nr1, nc0, nc1;                  // scale-1 rows / columns at which anything must be computed (adm_need.h)
   float inv_scale;
   Consts k0, k1;
   float* ll_ref;                           // approximation band of scale 1 (ow1 x oh1): the input of scale 2
@@ -141,7 +145,7 @@ __device__ __forceinline__ void pyramid_march(const PyramidArgs& a, const Loader
   float* __restrict__ ll_d = a.ll_dis + (int64_t)fr * a.ll_frame_pitch_d;
   const rsrc_t ll_rs_r = make_rsrc(ll_r, (unsigned)a.oh1 * a.ll_pitch_r * 4u);
   const rsrc_t ll_rs_d = make_rsrc(ll_d, (unsigned)a.oh1 * a.ll_pitch_d * 4u);
-  const unsigned ll_voff = (inner && c1 < a.ow1) ? (unsigned)c1 * 4u : 0x80000000u;   // others: no buffer is that large
+  const unsigned ll_voff = (inner && c1 >= a.nc0 && c1 < a.nc1) ? (unsigned)c1 * 4u : 0x80000000u;   // others: no buffer is that large
 
   float accA[6] = {0, 0, 0, 0, 0, 0}, accB[6] = {0, 0, 0, 0, 0, 0}, acc1[6] = {0, 0, 0, 0, 0, 0};   // num h v d, den h v d
   // The per-lane double sums (12 of them = 24 registers) live in LDS, one slot per thread and sum: a flush is a read, an add
@@ -236,7 +240,13 @@ __device__ __forceinline__ void pyramid_march(const PyramidArgs& a, const Loader
 
   // ---- the march.  Scale-1 row j needs scale-0 rows 2j - 1 .. 2j + 2; per iteration: scale-0 rows 2j + 1 and 2j + 2, then
   // scale-1 row j.  Scale-0 row i reads input rows 2i - 1 .. 2i + 2: two carried, two new (prefetched one iteration ahead).
-  const int j_first = R0 - 1, j_last = R1 < a.oh1 ? R1 : R1 - 1;
+  // Of the segment's rows only [Ra, Rb), those inside the needed range, are marched (with the row above and the row below
+  // where the segment continues): nothing reads the rest.  The march starts an even number of rows below the segment's own
+  // start j_seg and the flushes keep their phase against j_seg, so every row that accumulates is summed in the group of
+  // rows it always was; the rows left out accumulated nothing.
+  const int Ra = max(R0, a.nr0), Rb = min(R1, a.nr1);
+  const int j_seg = R0 - 1;
+  const int j_first = j_seg + ((Ra - R0) & ~1), j_last = Rb < R1 ? Rb - 1 : R1 < a.oh1 ? R1 : R1 - 1;
   const int i0 = 2 * j_first - 1;                    // first scale-0 row computed: 2 R0 - 3
   Row4 x0, x1, x2, x3;
   x2 = ld.convert(ld.load(2 * i0 - 1)); x3 = ld.convert(ld.load(2 * i0));
@@ -271,14 +281,14 @@ __device__ __forceinline__ void pyramid_march(const PyramidArgs& a, const Loader
     // band-level mirror of the ROWS just outside the scale-0 band (first / last segment of a frame)
     if (j == 0) w0 = w2;                             // row -1 <- row 1
     if (ib == a.oh0) w3 = w2;                        // row oh0 <- row oh0 - 1
-    step1(w0, w1, w2, w3, j, need1(j), j >= R0 && j < R1, accum1(j), accum1(j - 1));
+    step1(w0, w1, w2, w3, j, need1(j), j >= Ra && j < Rb, accum1(j), accum1(j - 1));
   };
   if constexpr (sizeof(T) == 1) {
     for (int j = j_first; j <= j_last; j += 2) {
       iteration(j, u0, u1, v0, v1);
       if (j + 1 <= j_last) {
         iteration(j + 1, v0, v1, u0, u1);
-        if (((j + 1 - j_first) & 3) == 3) flush();   // (every fourth row: always the second of a pair)
+        if (((j + 1 - j_seg) & 3) == 3) flush();     // (every fourth row: always the second of a pair)
       }
     }
   } else {
@@ -287,7 +297,7 @@ __device__ __forceinline__ void pyramid_march(const PyramidArgs& a, const Loader
     for (int j = j_first; j <= j_last; ++j) {
       iteration(j, u0, u1, v0, v1);
       u0 = v0; u1 = v1;
-      if (((j - j_first) & 3) == 3) flush();
+      if (((j - j_seg) & 3) == 3) flush();
     }
   }
   flush();
@@ -316,7 +326,8 @@ __global__ __launch_bounds__(kBlock, PQA_ADM_PYRAMID_OCC) void adm_pyramid_kerne
   // drew the middle of the frame worked while the others idled.  Consecutive ids go to the XCDs round-robin, which deals
   // every XCD the same mix.  And the ORDER is longest-first: a wave lives ~75 us and a launch is under three rounds of
   // them, so whatever is dispatched last decides the tail -- the segments in the middle of the frame (full chain) of ALL
-  // frames go first, those at its top and bottom (approximation band only, a third of the cost) last.
+  // frames go first, those at its top and bottom (approximation band only, a third of the cost -- and only the rows a
+  // deeper scale's window can reach; the outermost are idle) last.
 #ifdef PQA_ADM_PYRAMID_PLAIN_ORDER
   const int sg = blockIdx.x % a.n_sg, seg = (blockIdx.x / a.n_sg) % a.n_seg, fr = blockIdx.x / (a.n_sg * a.n_seg);
 #else
@@ -329,11 +340,12 @@ __global__ __launch_bounds__(kBlock, PQA_ADM_PYRAMID_OCC) void adm_pyramid_kerne
   const int stripe = sg * 4 + wave;
   double* __restrict__ part0 = a.part0 + ((int64_t)fr * a.n_part + (int64_t)id * 4 + wave) * 6;
   double* __restrict__ part1 = a.part1 + ((int64_t)fr * a.n_part + (int64_t)id * 4 + wave) * 6;
-  if (stripe >= a.n_stripes) {   // idle wave of the last group
+  const int R0 = seg * a.seg_rows, R1 = min(R0 + a.seg_rows, a.oh1);
+  // idle: a wave of the last group beyond the band, a stripe without a needed column, a segment without a needed row
+  if (stripe >= a.n_stripes || stripe * kP1 >= a.nc1 || (stripe + 1) * kP1 <= a.nc0 || min(R1, a.nr1) <= max(R0, a.nr0)) {
     if (lane < 6) { part0[lane] = 0.0; part1[lane] = 0.0; }
     return;
   }
-  const int R0 = seg * a.seg_rows, R1 = min(R0 + a.seg_rows, a.oh1);
   const T* __restrict__ ref = (const T*)a.ref + (int64_t)fr * a.frame_pitch_r;
   const T* __restrict__ dis = (const T*)a.dis + (int64_t)fr * a.frame_pitch_d;
   const unsigned bytes_r = (unsigned)a.h * a.pitch_r * (unsigned)sizeof(T), bytes_d = (unsigned)a.h * a.pitch_d * (unsigned)sizeof(T);
@@ -369,7 +381,7 @@ int adm_pyramid_partials(int w, int h) {
 
 bool launch_adm_pyramid(hipStream_t stream, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames, int w, int h, float inv_scale,
                         float gain_limit, MutPlaneRun ll_ref, MutPlaneRun ll_dis, double* partials0, double* partials1,
-                        int* n_partials, hipError_t* err) {
+                        int* n_partials, bool cone, hipError_t* err) {
   if (!adm_pyramid_takes(elem, w, h) || !ll_ref.base || !ll_dis.base) return false;
   const int es = elem == ELEM_U8 ? 1 : 2;
   if ((int64_t)ref.row_pitch * h * es >= (1ll << 31) || (int64_t)dis.row_pitch * h * es >= (1ll << 31)) return false;
@@ -393,6 +405,13 @@ bool launch_adm_pyramid(hipStream_t stream, Elem elem, PlaneRun ref, PlaneRun di
   a.left1 = (int)(a.ow1 * border - 0.5); a.top1 = (int)(a.oh1 * border - 0.5);
   a.right1 = a.ow1 - a.left1; a.bottom1 = a.oh1 - a.top1;
   if (a.top0 < 2 || a.top1 < 2) return false;   // the rows beside the band's first / last row must not reach a threshold
+  // The kernel derives the scale-0 rows / columns it computes from the scale-1 range (2 lo - 1 .. 2 hi); where that would
+  // not cover scale 0's own needed range, the whole band is marched.
+  AdmNeed need = adm_need(w, h, cone);
+  if (need.rows[0].lo < 2 * need.rows[1].lo - 1 || need.rows[0].hi > 2 * need.rows[1].hi + 1 ||
+      need.cols[0].lo < 2 * need.cols[1].lo - 1 || need.cols[0].hi > 2 * need.cols[1].hi + 1)
+    need = adm_need(w, h, false);
+  a.nr0 = need.rows[1].lo; a.nr1 = need.rows[1].hi; a.nc0 = need.cols[1].lo; a.nc1 = need.cols[1].hi;
   a.inv_scale = inv_scale;
   for (int s = 0; s < 2; ++s) {
     Consts& k = s ? a.k1 : a.k0;

@@ -324,7 +324,7 @@ int run_adm(pqa_ctx* c, Batch& b) {
     ProfScope ps(c, 7, b.sp_n, b.st_adm);
     if (launch_adm_pyramid(b.st_adm, top.elem, top.in.ref, top.in.dis, b.sp_n, top.w, top.h, c->inv_scale,
                            (float)c->cfg.adm_enhn_gain_limit, level_out(L2).ref, level_out(L2).dis, c->adm_part[0], c->adm_part[1],
-                           &np, &perr)) {
+                           &np, c->adm_cone, &perr)) {
       HIPCHK(c, perr);
       b.adm_np[0] = b.adm_np[1] = np;
       top = Scale{2, ELEM_F32, level_in(L2), L2.w, L2.h, {}};
@@ -333,7 +333,8 @@ int run_adm(pqa_ctx* c, Batch& b) {
   return walk_pyramid(c->adm_lv, top, ELEM_F32, [&](const Scale& k) -> int {
     ProfScope ps(c, 7 + k.s, b.sp_n, b.st_adm);
     HIPCHK(c, launch_adm_scale(b.st_adm, k.s, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h, c->inv_scale,
-                               (float)c->cfg.adm_enhn_gain_limit, k.out.ref, k.out.dis, c->adm_part[k.s], c->adm_mode, &b.adm_np[k.s]));
+                               (float)c->cfg.adm_enhn_gain_limit, k.out.ref, k.out.dis, c->adm_part[k.s], c->adm_mode, &b.adm_np[k.s],
+                               c->adm_cone));
     return PQA_OK;
   });
 }
@@ -1157,6 +1158,8 @@ void read_switches(pqa_ctx* c) {
   const char* am = getenv("PQA_ADM_MARCH");  // 0: the LDS-tiled ADM kernel (A/B partner of the march kernel)
   const char* ap = getenv("PQA_ADM_PYRAMID");  // 0: the march kernel one scale per launch (test partner of the pyramid kernel)
   c->adm_mode = (am && am[0] == '0') ? ADM_TILED : (ap && ap[0] == '0') ? ADM_MARCH : ADM_AUTO;
+  const char* ac = getenv("PQA_ADM_CONE");  // 0: the march kernels compute the whole approximation band (test partner of the cone, adm_need.h)
+  c->adm_cone = !(ac && ac[0] == '0');
   const char* mm = getenv("PQA_MOTION_MARCH");  // 0: the LDS-tiled motion kernel (test partner of the march kernel)
   c->motion_mode = (mm && mm[0] == '0') ? MOTION_TILED : MOTION_AUTO;
   const char* xm = getenv("PQA_XSSE_MFMA");  // 0: the plain-VALU cross-SSE kernel for 8-bit clips too (test partner of the MFMA kernel)

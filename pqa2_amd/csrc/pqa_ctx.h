@@ -233,6 +233,7 @@ struct pqa_ctx {
   int vif_strip_mask = 0x2;             // PQA_VIF_STRIP, read once in pqa_create: bit s = scale s may run the strip kernel (0 = none; default: scale 1)
   int vif_strip_seg = 0;                // PQA_VIF_STRIP_SEG, read once in pqa_create: tile rows per segment; 0 = vif_strip_shape's rule
   int adm_mode = pqa::ADM_AUTO;        // PQA_ADM_MARCH, read once in pqa_create
+  bool adm_cone = true;                // PQA_ADM_CONE, read once in pqa_create: approximation bands only inside the dependency cone
   int motion_mode = pqa::MOTION_AUTO;   // PQA_MOTION_MARCH, read once in pqa_create
   bool trace = false;   // PQA_TRACE=1: synchronise after every launch and name it on stderr (localises a stall)
   bool prof = false;

@@ -1,5 +1,6 @@
 // The pqa_debug_* entries of the C ABI: single kernels and host tables exposed to the tests, on the default stream with
 // scratch memory of their own (no context; pqa_debug_vif_strip_shape alone reads one's switches).  Declarations: include/pqa_vmaf.h.
+#include "adm_need.h"
 #include "pqa_ctx.h"
 
 using namespace pqa;
@@ -67,6 +68,17 @@ int pqa_debug_vif_strip_shape(pqa_ctx* ctx, uint32_t scale, uint32_t n_frames, i
   const int strip_seg = ctx->vif_fixed ? -1 : (ctx->vif_strip_mask >> scale & 1) ? ctx->vif_strip_seg : -1;
   vif_strip_shape((int)scale, L.w, L.h, (int)n_frames, strip_seg, shape);
   for (int i = 0; i < 4; ++i) out4[i] = shape[i];
+  return PQA_OK;
+}
+
+int pqa_debug_adm_need(uint32_t width, uint32_t height, int32_t* out20) {
+  if (!out20 || width == 0 || height == 0 || width > 65536 || height > 65536) return PQA_EINVAL;
+  const AdmNeed n = adm_need((int)width, (int)height);
+  for (int s = 0; s < 4; ++s) {
+    out20[4 * s + 0] = n.rows[s].lo; out20[4 * s + 1] = n.rows[s].hi;
+    out20[4 * s + 2] = n.cols[s].lo; out20[4 * s + 3] = n.cols[s].hi;
+  }
+  out20[16] = n.in_rows.lo; out20[17] = n.in_rows.hi; out20[18] = n.in_cols.lo; out20[19] = n.in_cols.hi;
   return PQA_OK;
 }
 
