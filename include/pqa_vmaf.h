@@ -674,6 +674,34 @@ PQA_API int pqa_format_convert_device(pqa_ctx* ctx, const pqa_convert_spec* spec
                                       int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
                                       int32_t n_frames);
 
+/* Transfer-curve alignment: n_frames planes through an integer table, synchronously -- the correction that undoes a gamma
+ * mismatch, a contrast enhancer or a black-stretch curve once pqa2_amd/align.py (best_curve, curve_lut) has turned the table
+ * of pqa_level_stats into a monotone curve and its inverse.  Planes of width x height samples (the spec's, independent of the
+ * context's width and height; each 1 ... 8192), u8 in an 8-bit context, otherwise little-endian u16.  table: a HOST pointer to
+ * L = pqa_level_bins(ctx) entries of the sample type, none above 2^bit_depth - 1, and
+ *     dst[y][x] = table[min(src[y][x], L - 1)].
+ * Any table, monotone or not.  The destination may be exactly the source (same base and pitches).
+ * Any context, no feature bit, no record, no profile id; independent of the scoring chain: a call between two pqa_submit
+ * calls changes no record.  PQA_EINVAL, before any device call, on a null pointer, a bad struct_size, a size outside
+ * 1 ... 8192, a negative frame count, a row pitch below a row, in device memory a base or pitch that is no multiple of the
+ * sample size, or a table entry above 2^bit_depth - 1.  n_frames == 0 succeeds and writes nothing.  No source byte past a
+ * row's last sample is read and no destination byte past it is written.  Kernel: DESIGN.md section 5.
+ *
+ * pqa_table_apply: frames in HOST memory (src_frames[f] / dst_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 through the pinned buffers of pqa_resample and device buffers
+ * of this entry's own, grow-only and freed with the context.
+ * pqa_table_apply_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device; the mapped planes can go straight into pqa_submit_device. */
+typedef struct pqa_table_spec {
+  uint32_t struct_size;   /* sizeof(pqa_table_spec) */
+  uint32_t width, height; /* of this plane, 1 ... 8192 */
+} pqa_table_spec;
+PQA_API int pqa_table_apply(pqa_ctx* ctx, const pqa_table_spec* spec, const void* table, const void* const* src_frames,
+                            int64_t src_row_stride, void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames);
+PQA_API int pqa_table_apply_device(pqa_ctx* ctx, const pqa_table_spec* spec, const void* table, const void* src, int64_t src_row_pitch,
+                                   int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
+                                   int32_t n_frames);
+
 /* Sub-pixel registration: the tile-wise gradient moments of n_frames frame pairs of one plane, synchronously -- the
  * Lucas-Kanade normal equations of every tile, from which pqa2_amd/align.py (solve_geometry, register) estimates a sub-pixel
  * shift and a scale factor per axis and drives the source window of pqa_resample.  Planes of width x height samples (the

@@ -1,7 +1,8 @@
 """Temporal, spatial and level alignment on the host.  Spatial (best_shift, below the temporal part): from the shifted-window luma
 SSE (FeatureEngine.shift_sse, pqa_shift_sse) to the whole-pixel displacement of the captured picture.  Levels (best_levels,
 level_lut, at the end of this file): from the per-level transfer table (FeatureEngine.level_stats, pqa_level_stats) to the gain
-and offset of the captured samples, the named range conversion they amount to and the table that undoes it.  Colour (best_colour,
+and offset of the captured samples, the named range conversion they amount to and the table that undoes it; a transfer curve
+(best_curve, curve_lut, behind them): the monotone curve of the same table and its inverse, for FeatureEngine.table_apply.  Colour (best_colour,
 colour_correction, at the very end): from the cross-plane moments (FeatureEngine.colour_moments, pqa_colour_moments) to the 3 x 4 map of
 the captured planes, the named matrix conversion it amounts to and the Q14 matrix that undoes it.  Active picture (active_picture, common_window, after the colour part): from the row and column profiles
 (FeatureEngine.line_profiles, pqa_line_profiles) to the black bars of each clip and the rectangle both share.  Temporal: from the banded cross-frame SSE matrix (FeatureEngine.cross_sse, pqa_cross_sse) to a
@@ -16,6 +17,7 @@ This replaces the reference's hand-tuned `frame_offset` spin box (app/bookend_al
 alignment methods its options tab offers and nothing implements."""
 from __future__ import annotations
 
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -326,22 +328,9 @@ def _map_sse(a, b, top, T0, T1, T2):
     return sse
 
 
-def best_levels(T, bit_depth: int, *, chroma: bool = False, min_improvement: float = 2.0, snap: float = 1.25) -> dict:
-    """The level mapping of a captured plane from T[n_frames][L][3] (pqa_level_stats; L = 2^bit_depth): T[f][v] = (count, sum
-    of dis, sum of dis^2) over the pixels whose reference sample is v.  The frames are pooled; everything below is Python
-    ints and Fractions, converted to float only in the result.  top = L - 1.
-
-    gain, offset: the least-squares a, b of dis = a * ref + b from the joint moments, refitted once over only those populated
-    reference levels whose predicted captured value a * v + b lies in [1, top - 1], so that clipping at 0 or top does not
-    bias the fit (the first fit is kept when fewer than two such levels remain).  levels_used = the levels of the final fit.
-    The MSE of a map (a, b) is taken against clamp(a * v + b, 0, top).  mse_identity; mse_affine (the fitted map);
-    mse_curve = sum_v (T2 - T1^2 / T0) / N, the residual about the conditional mean: the floor any per-level correction
-    could reach.  named = {identity, limited_to_full, full_to_limited: MSE under named_level_map()}.
-    kind = the named map with the smallest MSE (ties: the order above), or "affine" when that MSE exceeds snap * mse_affine.
-    mismatch = mse_identity > min_improvement * (MSE of the chosen map).  map_gain / map_offset = the chosen map's a, b (the
-    named map's own values, or the fitted ones): what correction_lut() undoes.
-    degenerate = fewer than two reference levels are populated: no fit is made, gain = 1, offset = 0, kind = "identity",
-    mismatch false.  frames = n_frames."""
+def _levels_exact(T, bit_depth: int, chroma: bool, min_improvement: float, snap: float):
+    """(the best_levels() result, what best_curve() goes on with in exact numbers: the pooled columns T0 / T1 / T2, n_pix, the
+    fitted gain, the MSE of the chosen map and of the identity)"""
     T = np.asarray(T)
     L = 1 << int(bit_depth)
     if T.ndim != 3 or T.shape[0] < 1 or T.shape[1:] != (L, 3):
@@ -374,11 +363,31 @@ def best_levels(T, bit_depth: int, *, chroma: bool = False, min_improvement: flo
     if not degenerate and chosen > Fraction(snap) * mse_affine:
         kind, chosen = "affine", mse_affine
     ma, mb = (a, b) if kind == "affine" else named_level_map(kind, bit_depth, chroma)
-    return {"gain": float(a), "offset": float(b), "kind": kind,
-            "mismatch": bool(not degenerate and named["identity"] > Fraction(min_improvement) * chosen),
-            "mse_identity": float(named["identity"]), "mse_affine": float(mse_affine), "mse_curve": float(curve),
-            "named": {k: float(x) for k, x in named.items()}, "map_gain": float(ma), "map_offset": float(mb),
-            "levels_used": len(used), "frames": int(T.shape[0]), "degenerate": bool(degenerate)}
+    out = {"gain": float(a), "offset": float(b), "kind": kind,
+           "mismatch": bool(not degenerate and named["identity"] > Fraction(min_improvement) * chosen),
+           "mse_identity": float(named["identity"]), "mse_affine": float(mse_affine), "mse_curve": float(curve),
+           "named": {k: float(x) for k, x in named.items()}, "map_gain": float(ma), "map_offset": float(mb),
+           "levels_used": len(used), "frames": int(T.shape[0]), "degenerate": bool(degenerate)}
+    return out, {"T0": T0, "T1": T1, "T2": T2, "n_pix": n_pix, "gain": a, "chosen": chosen, "identity": named["identity"]}
+
+
+def best_levels(T, bit_depth: int, *, chroma: bool = False, min_improvement: float = 2.0, snap: float = 1.25) -> dict:
+    """The level mapping of a captured plane from T[n_frames][L][3] (pqa_level_stats; L = 2^bit_depth): T[f][v] = (count, sum
+    of dis, sum of dis^2) over the pixels whose reference sample is v.  The frames are pooled; everything below is Python
+    ints and Fractions, converted to float only in the result.  top = L - 1.
+
+    gain, offset: the least-squares a, b of dis = a * ref + b from the joint moments, refitted once over only those populated
+    reference levels whose predicted captured value a * v + b lies in [1, top - 1], so that clipping at 0 or top does not
+    bias the fit (the first fit is kept when fewer than two such levels remain).  levels_used = the levels of the final fit.
+    The MSE of a map (a, b) is taken against clamp(a * v + b, 0, top).  mse_identity; mse_affine (the fitted map);
+    mse_curve = sum_v (T2 - T1^2 / T0) / N, the residual about the conditional mean: the floor any per-level correction
+    could reach.  named = {identity, limited_to_full, full_to_limited: MSE under named_level_map()}.
+    kind = the named map with the smallest MSE (ties: the order above), or "affine" when that MSE exceeds snap * mse_affine.
+    mismatch = mse_identity > min_improvement * (MSE of the chosen map).  map_gain / map_offset = the chosen map's a, b (the
+    named map's own values, or the fitted ones): what correction_lut() undoes.
+    degenerate = fewer than two reference levels are populated: no fit is made, gain = 1, offset = 0, kind = "identity",
+    mismatch false.  frames = n_frames."""
+    return _levels_exact(T, bit_depth, chroma, min_improvement, snap)[0]
 
 
 def level_lut(gain, offset, bit_depth: int) -> np.ndarray:
@@ -399,6 +408,157 @@ def correction_lut(levels: dict, bit_depth: int, chroma: bool = False) -> np.nda
     if levels["kind"] in LEVEL_MAPS:
         return level_lut(*named_level_map(levels["kind"], bit_depth, chroma), bit_depth)
     return level_lut(levels["gain"], levels["offset"], bit_depth)
+
+
+# ---- transfer-curve alignment ------------------------------------------------------------------------------------------------
+# A gamma leg, a contrast enhancer or a black stretch is no gain and offset: the forward table T of pqa_level_stats is turned
+# into a monotone curve g (captured level as a function of the reference level) and its inverse as an integer table, which
+# FeatureEngine.table_apply puts the captured planes through.  The forward direction is deliberate: E[dis | ref = v] is unbiased
+# under dis = g(ref) + noise, whereas E[ref | dis] shrinks towards the mean under coding noise and would "correct" a clip whose
+# levels are fine.
+def table_sse(T) -> int:
+    """sum over the frames and levels of T2 - 2 v T1 + v^2 T0, a Python int: the squared error of the pairs T was made from"""
+    T = np.asarray(T)
+    return sum(int(T[f, v, 2]) - 2 * v * int(T[f, v, 1]) + v * v * int(T[f, v, 0]) for f in range(T.shape[0]) for v in range(T.shape[1]))
+
+
+def isotonic(values, weights) -> list:
+    """The weighted isotonic regression (non-decreasing) of `values`, as Fractions: pool adjacent violators.  A block is pooled
+    with its predecessor only while its mean is strictly below the predecessor's, so equal means stay blocks of their own."""
+    blocks = []   # [sum of weight * value, sum of weight, members]
+    for x, w in zip(values, weights):
+        w = Fraction(w)
+        if w <= 0:
+            raise ValueError("isotonic needs positive weights")
+        blocks.append([Fraction(x) * w, w, 1])
+        while len(blocks) > 1 and blocks[-1][0] * blocks[-2][1] < blocks[-2][0] * blocks[-1][1]:
+            s, w1, n = blocks.pop()
+            blocks[-1][0] += s
+            blocks[-1][1] += w1
+            blocks[-1][2] += n
+    out = []
+    for s, w, n in blocks:
+        out += [s / w] * n
+    return out
+
+
+def _curve(T0, T1, top: int, min_count: int):
+    """(knots, g over every level 0 ... top as Fractions) of the pooled columns T0 / T1, or None when no curve can be formed:
+    fewer than two knots, or a g that is constant over them"""
+    knots = [v for v in range(top + 1) if T0[v] >= max(1, int(min_count))]
+    if len(knots) < 2:
+        return None
+    gk = isotonic([Fraction(T1[v], T0[v]) for v in knots], [T0[v] for v in knots])
+    if gk[0] == gk[-1]:
+        return None
+    g = [None] * (top + 1)
+    for v in range(knots[0]):                        # slope 1 outside the knots, clamped to the range
+        g[v] = max(Fraction(0), gk[0] - (knots[0] - v))
+    for v in range(knots[-1] + 1, top + 1):
+        g[v] = min(Fraction(top), gk[-1] + (v - knots[-1]))
+    for (v0, g0), (v1, g1) in zip(zip(knots, gk), zip(knots[1:], gk[1:])):
+        step = (g1 - g0) / (v1 - v0)
+        for v in range(v0, v1):
+            g[v] = g0 + step * (v - v0)
+    g[knots[-1]] = gk[-1]
+    return knots, g
+
+
+def _pooled(T, bit_depth: int):
+    T = np.asarray(T)
+    L = 1 << int(bit_depth)
+    if T.ndim != 3 or T.shape[0] < 1 or T.shape[1:] != (L, 3):
+        raise ValueError("T must be [n_frames >= 1, 2^bit_depth, 3]")
+    return ([sum(int(x) for x in T[:, v, k]) for v in range(L)] for k in range(3))
+
+
+def _curve_gamma(knots, g, T0, lo: int, hi: int):
+    """the T0-weighted least-squares slope of ln g against ln v, both normalised to (lo, hi), over the knots strictly inside on
+    both axes; a float, or None when fewer than two such knots exist"""
+    pts = []
+    for v in knots:
+        x, y = (v - lo) / (hi - lo), float((g[v] - lo) / (hi - lo))
+        if 0 < x < 1 and 0 < y < 1:
+            pts.append((math.log(x), math.log(y), float(T0[v])))
+    n = sum(w for _, _, w in pts)
+    if len(pts) < 2:
+        return None
+    mx, my = sum(w * x for x, _, w in pts) / n, sum(w * y for _, y, w in pts) / n
+    sxx = sum(w * (x - mx) ** 2 for x, _, w in pts)
+    return None if sxx <= 0 else sum(w * (x - mx) * (y - my) for x, y, w in pts) / sxx
+
+
+def best_curve(T, bit_depth: int, *, chroma: bool = False, full_range: bool = True, min_count: int = 16, curve_snap: float = 1.1,
+               curve_min_gain: float = 0.5, min_improvement: float = 2.0, snap: float = 1.25) -> dict:
+    """best_levels() of T[n_frames][L][3] (pqa_level_stats, pooled over the frames), and on top of it the monotone transfer
+    curve g of the captured levels on the reference's.  Exact ints and Fractions up to the floats of the result.
+
+    Knots are the reference levels v with T0[v] >= min_count; g at the knots is the T0-weighted isotonic regression
+    (isotonic(): non-decreasing) of the conditional means T1 / T0; between knots g is linear, below the first and above the
+    last it continues with slope 1, clamped to [0, top].  curve_degenerate = no curve is formed: fewer than two knots, a g
+    that is constant, a best_levels() result that is degenerate, or a fitted gain that is not positive (the capture does not
+    follow the reference at all: independent pictures).  knots = the number of knots.
+    mse_monotone = sum_v (T2 - 2 g T1 + g^2 T0) / N: it lies between mse_curve (the floor) and mse_affine wherever every
+    populated level is a knot.  None when curve_degenerate.
+    kind becomes "curve" when the MSE of the map best_levels() chose exceeds curve_snap * mse_monotone AND exceeds mse_monotone
+    by at least curve_min_gain * 4^(bit_depth - 8); the second condition keeps noise-free affine clips, whose only residual is
+    rounding (about 1/12), out of "curve".  mismatch is then mse_identity > min_improvement * mse_monotone.  Otherwise the
+    best_levels() result stands as it is.
+    gamma: a float, reported only -- the T0-weighted least-squares slope of ln g against ln v over the interior knots, both
+    normalised to (0, top), or to (16 s, 235 s) with full_range=False, s = 2^(bit_depth - 8) as in named_level_map; None for
+    a chroma plane, when curve_degenerate, or with fewer than two interior knots."""
+    out, ex = _levels_exact(T, bit_depth, chroma, min_improvement, snap)
+    T0, T1, T2, n_pix = ex["T0"], ex["T1"], ex["T2"], ex["n_pix"]
+    top = (1 << int(bit_depth)) - 1
+    cv = None if out["degenerate"] or ex["gain"] <= 0 else _curve(T0, T1, top, min_count)
+    out.update(mse_monotone=None, knots=0, gamma=None, curve_degenerate=cv is None)
+    if cv is None:
+        return out
+    knots, g = cv
+    mono = sum(T2[v] - 2 * g[v] * T1[v] + g[v] * g[v] * T0[v] for v in range(top + 1) if T0[v]) / n_pix
+    s = 1 << (int(bit_depth) - 8)
+    lo, hi = (0, top) if full_range else (16 * s, 235 * s)
+    out.update(mse_monotone=float(mono), knots=len(knots), gamma=None if chroma else _curve_gamma(knots, g, T0, lo, hi))
+    if ex["chosen"] > Fraction(curve_snap) * mono and ex["chosen"] - mono >= Fraction(curve_min_gain) * s * s:
+        out.update(kind="curve", mismatch=bool(ex["identity"] > Fraction(min_improvement) * mono))
+    return out
+
+
+def curve_lut(T, bit_depth: int, min_count: int = 16) -> np.ndarray:
+    """The inverse of best_curve()'s g as an integer table over the captured levels d = 0 ... top (uint8 at 8 bit, else uint16):
+    what FeatureEngine.table_apply puts a captured plane through.  For every d:
+      1. the v whose g(v) is nearest d -- the candidates are the last v with g(v) <= d (v = 0 when there is none) and its
+         successor; the lower one wins a tie;
+      2. that v widened to the whole run of levels with the same g (a plateau: clipped or crushed levels);
+      3. the entry is the T0-weighted mean of the run, rounded half up, or the run's midpoint (rounded half up) when the run
+         holds no pixel.
+    Non-decreasing by construction.  ValueError when no curve can be formed (best_curve(): curve_degenerate)."""
+    T0, T1, _ = _pooled(T, bit_depth)
+    top = (1 << int(bit_depth)) - 1
+    cv = _curve(T0, T1, top, min_count)
+    if cv is None:
+        raise ValueError("curve_lut: no curve can be formed from this table")
+    g = cv[1]
+    run_of, entry = [0] * (top + 1), []     # level -> index of its run; run -> its entry
+    v = 0
+    while v <= top:
+        e = v
+        while e < top and g[e + 1] == g[v]:
+            e += 1
+        n = sum(T0[v:e + 1])
+        num, den = (sum(u * T0[u] for u in range(v, e + 1)), n) if n else (v + e, 2)
+        entry.append((2 * num + den) // (2 * den))
+        for u in range(v, e + 1):
+            run_of[u] = len(entry) - 1
+        v = e + 1
+    lut, v = [], 0
+    for d in range(top + 1):
+        while v < top and g[v + 1] <= d:    # the last v with g(v) <= d; g is non-decreasing, and so is v in d
+            v += 1
+        pick = v + 1 if v < top and g[v] <= d and g[v + 1] - d < d - g[v] else v
+        lut.append(entry[run_of[pick]])
+    assert all(a <= b for a, b in zip(lut, lut[1:])), "curve_lut: the table must be non-decreasing"
+    return np.asarray(lut, np.uint8 if bit_depth <= 8 else np.uint16)
 
 
 # ---- sub-pixel and scale registration ------------------------------------------------------------------------------------------

@@ -593,4 +593,15 @@ hipError_t launch_format_convert(hipStream_t stream, const ConvertLayout& src, c
                                  bool generic, const void* src_planes, int64_t src_row_pitch, int64_t src_frame_pitch, void* dst_planes,
                                  int64_t dst_row_pitch, int64_t dst_frame_pitch, int n_frames);
 
+// ---- transfer-curve alignment: planes through an integer table (table_apply.hip) ---------------------------------------------
+// dst[y][x] = table[min(src[y][x], L - 1)], L = 2^bit_depth, for n_frames planes of w x h samples (1 ... 8192 each way; u8 at
+// 8 bit, otherwise u16).  table: L entries of the sample type in DEVICE memory, 16-byte aligned; any table, monotone or not.
+// Frame f at base + f * frame_pitch, pitches in BYTES; dst may be exactly src.  Reads no source byte past a row's last sample,
+// writes no destination byte past it.  hipErrorInvalidValue, before any launch, on a null pointer, a size or depth out of
+// range, more than 65535 frames, a side that is not made of whole samples or a pitch below a row.
+constexpr int kTableChunk = 8;   // frames per chunk of the host entry
+hipError_t launch_table_apply(hipStream_t stream, Elem elem, int bit_depth, const void* table, const void* src, int64_t src_row_pitch,
+                              int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int n_frames, int w,
+                              int h);
+
 }  // namespace pqa

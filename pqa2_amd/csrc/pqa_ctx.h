@@ -82,6 +82,7 @@ enum SideBuf {
   SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles
   SIDE_UNPACK_SRC, SIDE_UNPACK_DST,                                            // pqa_unpack, unpack.hip: a chunk of uploaded packed frames / of unpacked planes
   SIDE_CONVERT_SRC, SIDE_CONVERT_DST,                                          // pqa_format_convert, format_convert.hip: a chunk of uploaded / of converted planes
+  SIDE_TABLE_LUT, SIDE_TABLE_SRC, SIDE_TABLE_DST,                              // pqa_table_apply[_device], table_apply.hip: the table; pqa_table_apply: a chunk of uploaded / of mapped planes
   kSideBufs
 };
 

@@ -1182,6 +1182,94 @@ int pqa_format_convert(pqa_ctx* c, const pqa_convert_spec* spec, const void* con
   return PQA_OK;
 }
 
+// ---- transfer-curve alignment: planes through an integer table (table_apply.hip) ----------------------------------------------
+
+namespace {
+// The argument rules both entries share, in spec_check's order and then the table's (no device call).
+int table_check(pqa_ctx* c, const pqa_table_spec* sp, const void* table, const void* src, const void* dst, int32_t n_frames) {
+  const int rc = spec_check(c, "table_apply", sp, 1, src, dst, n_frames, sp, 1, [] { return (int)PQA_OK; });
+  if (rc != PQA_OK) return rc;
+  if (!table) return fail(c, PQA_EINVAL, "table_apply: null table");
+  const unsigned top = (1u << c->cfg.bit_depth) - 1u;
+  for (unsigned v = 0; v <= top; ++v) {
+    const unsigned t = c->esize == 1 ? ((const uint8_t*)table)[v] : ((const uint16_t*)table)[v];
+    if (t > top) return fail(c, PQA_EINVAL, "table_apply: table entry %u is %u, above %u", v, t, top);
+  }
+  return PQA_OK;
+}
+// the table onto the stream, in front of the launches that read it; pageable memory: the copy has left `table` on return
+hipError_t table_upload(pqa_ctx* c, const void* table) {
+  return hipMemcpyAsync(c->side_buf[SIDE_TABLE_LUT], table, ((size_t)c->esize) << c->cfg.bit_depth, hipMemcpyHostToDevice, c->stream);
+}
+}  // namespace
+
+int pqa_table_apply_device(pqa_ctx* c, const pqa_table_spec* spec, const void* table, const void* src, int64_t src_row_pitch,
+                           int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
+  int rc = table_check(c, spec, table, src, dst, n_frames);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize;
+  const int64_t row = (int64_t)spec->width * es;
+  if (((uintptr_t)src | (uintptr_t)src_row_pitch | (uintptr_t)src_frame_pitch) & (uintptr_t)(es - 1))
+    return fail(c, PQA_EINVAL, "table_apply: source base or pitch is not a multiple of the sample size");
+  if (((uintptr_t)dst | (uintptr_t)dst_row_pitch | (uintptr_t)dst_frame_pitch) & (uintptr_t)(es - 1))
+    return fail(c, PQA_EINVAL, "table_apply: destination base or pitch is not a multiple of the sample size");
+  if (src_row_pitch < row) return fail(c, PQA_EINVAL, "table_apply: source pitch smaller than a row");
+  if (dst_row_pitch < row) return fail(c, PQA_EINVAL, "table_apply: destination pitch smaller than a row");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = side_reserve(c, SIDE_TABLE_LUT, (size_t)es << c->cfg.bit_depth);
+  if (rc != PQA_OK) return rc;
+  hipError_t e = table_upload(c, table);
+  constexpr int kGrid = 32768;   // frames per launch (the grid's y)
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid)
+    e = launch_table_apply(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_TABLE_LUT],
+                           (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch,
+                           (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch, dst_frame_pitch, chunk_len(n_frames, f0, kGrid),
+                           (int)spec->width, (int)spec->height);
+  return side_finish(c, "table_apply", e, nullptr, nullptr, 0);
+}
+
+int pqa_table_apply(pqa_ctx* c, const pqa_table_spec* spec, const void* table, const void* const* src_frames, int64_t src_row_stride,
+                    void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames) {
+  int rc = table_check(c, spec, table, src_frames, dst_frames, n_frames);
+  if (rc != PQA_OK) return rc;
+  const int w = (int)spec->width, h = (int)spec->height;
+  const size_t row = (size_t)w * c->esize;
+  rc = check_host_frames(c, "table_apply: ", "source ", src_frames, 1, n_frames, src_row_stride, row, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "table_apply: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, row, true);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // As pqa_format_convert: chunks of kTableChunk planes out through the first pinned chunk of the side analyses and back through
+  // the second, device buffers of this entry's own, all grow-only, in the packed layout of host_stage.h (rows 16 bytes apart at
+  // least, so the 16-byte loads and stores apply); a chunk is uploaded, mapped, downloaded and copied out before the next.
+  const host::PlaneLayout P = host::plane_layout(row, h);
+  const int chunk = n_frames < kTableChunk ? n_frames : kTableChunk;
+  rc = side_pin_reserve(c, 0, P.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, P.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TABLE_LUT, (size_t)c->esize << c->cfg.bit_depth);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TABLE_SRC, P.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TABLE_DST, P.frame_bytes * chunk);
+  if (rc != PQA_OK) return rc;
+  for (int f0 = 0; f0 < n_frames; f0 += kTableChunk) {
+    const int n = chunk_len(n_frames, f0, kTableChunk);
+    host::pack_planes(c->side_pin[0], P, src_frames + f0, src_row_stride, n);
+    hipError_t e = f0 == 0 ? table_upload(c, table) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_TABLE_SRC], c->side_pin[0], P.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_table_apply(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_TABLE_LUT], c->side_buf[SIDE_TABLE_SRC], P.pitch,
+                             (int64_t)P.frame_bytes, c->side_buf[SIDE_TABLE_DST], P.pitch, (int64_t)P.frame_bytes, n, w, h);
+    rc = side_finish(c, "table_apply", e, c->side_pin[1], c->side_buf[SIDE_TABLE_DST], P.frame_bytes * n);
+    if (rc != PQA_OK) return rc;
+    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
+      for (int y = 0; y < h; ++y)
+        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * P.frame_bytes + (size_t)y * P.pitch, row);
+  }
+  return PQA_OK;
+}
+
 // ---- the spec-driven analyses: flow_moments() ... line_profiles() above ------------------------------------------------------
 
 int pqa_flow_moments_device(pqa_ctx* c, const pqa_flow_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,

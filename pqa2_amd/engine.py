@@ -545,6 +545,49 @@ class FeatureEngine:
                                                     dis_frame_pitch, int(n_frames), int(plane), out.ctypes.data))
         return out
 
+    def _table(self, table):
+        """(array kept alive, pointer) of a table of L = 2^bit_depth entries of this engine's sample type; an entry the type
+        cannot hold is refused here, one above 2^bit_depth - 1 by the library"""
+        t = np.asarray(table)
+        if t.shape != (1 << self.bit_depth,) or t.dtype.kind not in "ui":
+            raise ValueError(f"table_apply needs a table of {1 << self.bit_depth} integers")
+        if t.size and (int(t.min()) < 0 or int(t.max()) > np.iinfo(self.dtype).max):
+            raise N.PqaError(N.PQA_EINVAL, "table_apply: a table entry does not fit the sample type")
+        t = np.ascontiguousarray(t, dtype=self.dtype)
+        return t, t.ctypes.data
+
+    def table_apply(self, frames, table, plane: int | None = 0):
+        """A list of new 2-D arrays: every plane of `frames` (HOST memory) through the integer table, out = table[min(sample,
+        L - 1)], L = 2^bit_depth (pqa_table_apply; definition: include/pqa_vmaf.h).  Any table of L entries none of which
+        exceeds 2^bit_depth - 1, monotone or not; align.curve_lut makes the one that undoes a transfer curve.  The planes have
+        the size of `plane` of this context, or with plane=None any one size of their own."""
+        arrs = [np.asarray(f) for f in frames]
+        shape = self.plane_shape(int(plane)) if plane is not None else (arrs[0].shape if arrs else (self.height, self.width))
+        if len(shape) != 2:
+            raise ValueError("table_apply needs 2-D planes")
+        keep_t, tp = self._table(table)
+        sp = self._plane_spec(N.PqaTableSpec, shape)
+        keep, sptr, sstride = self._luma_list(arrs, "source", tuple(int(v) for v in shape))
+        out = [np.empty(shape, self.dtype) for _ in keep]
+        dptr = (C.c_void_p * max(len(out), 1))()
+        for i, o in enumerate(out):
+            dptr[i] = o.ctypes.data
+        self._check(self.lib.pqa_table_apply(self._ctx, C.byref(sp), tp, sptr, sstride, dptr,
+                                             int(shape[1]) * np.dtype(self.dtype).itemsize, len(keep)))
+        del keep, keep_t
+        return out
+
+    def table_apply_resident(self, table, shape, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, dst_ptr: int,
+                             dst_row_pitch: int, dst_frame_pitch: int, n_frames: int):
+        """The same for n_frames planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_table_apply_device); dst may be exactly src.  Nothing but the table crosses PCIe; the result can go into
+        submit_resident."""
+        keep_t, tp = self._table(table)
+        sp = self._plane_spec(N.PqaTableSpec, shape)
+        self._check(self.lib.pqa_table_apply_device(self._ctx, C.byref(sp), tp, src_ptr or None, src_row_pitch, src_frame_pitch,
+                                                    dst_ptr or None, dst_row_pitch, dst_frame_pitch, int(n_frames)))
+        del keep_t
+
     # -- resampling --------------------------------------------------------------------------
     def _resample_spec(self, src_shape, dst_shape, filter, window):
         """the pqa_resample_spec of planes src_shape -> dst_shape ((height, width) each); window = (x0, y0, w, h) in source

@@ -33,7 +33,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 psnr_hvs: bool = False, xpsnr: bool = False, siti: bool = False,
                 integrity: bool = False, integrity_options=None, align: int = 0,
                 align_frames: int | None = None, align_penalty_mse: float | None = None, spatial_align: int = 0,
-                spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8,
+                spatial_frames: int = 8, level_align: str | None = None, level_frames: int = 8, level_curve: bool = False,
                 resize: str | None = None, register: str | None = None, register_frames: int = 8,
                 register_min_px: float = 1.0 / 16, colour_align: str | None = None, colour_frames: int = 8,
                 colour_full_range: bool | None = None, active_picture: str | None = None, active_frames: int = 8,
@@ -90,6 +90,15 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     those of a run without the option.  "apply" maps every captured plane whose `mismatch` is true through the integer table
     that undoes its chosen map (align.correction_lut, numpy.take on the host) before it is scored; `applied` says so per
     plane.  `level_align` = None: no measurement.
+    `level_curve` = True, on top of `level_align`: a transfer-curve mismatch -- a gamma leg, a contrast enhancer, a black
+    stretch -- is fitted as a monotone curve of the same table (align.best_curve).  `levels` and every plane under `planes`
+    gain {mse_monotone, knots, gamma, curve_degenerate, curve_applied, mse_after}, and `kind` becomes "curve" where the curve
+    leaves clearly less error than the map chosen above (gamma: reported only; normalised to the captured clip's range as
+    `colour_full_range` is read).  Under "apply" a plane of kind "curve" with `mismatch` is first checked: the inverse table
+    (align.curve_lut) is applied to the sampled captured planes on the GPU (pqa_table_apply), pqa_level_stats runs again and
+    `mse_after` is the identity MSE of that second table; only if it lies below `mse_identity` does every captured plane go
+    through the table before it is scored (`curve_applied` and `applied`), otherwise the plane is left as it is.  Planes of
+    another kind keep the host path above.  False: every result and record is what it is without the option.
     `register` = "bilinear", "bicubic" or "lanczos": before scoring (after the temporal and spatial steps, on the pairs and the
     window they produced, and before the levels), the sub-pixel displacement and the scale factor per axis of the captured
     picture are measured on `register_frames` luma pairs spread evenly over the common range -- tile-wise gradient moments
@@ -293,16 +302,22 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             cw, ch = ri.width - left - right, ri.height - top - bottom
             ref_rd, dis_rd = _CroppedReader(ref_rd, left, top, cw, ch), _CroppedReader(registered, left, top, cw, ch)
             ri, di = ref_rd.info, dis_rd.info
+    tabled = None
     if level_align is not None:
         if level_align not in ("report", "apply"):
             raise ValueError('level_align must be None, "report" or "apply"')
         if level_frames is None or level_frames < 1:
             raise ValueError("level_frames must be positive")
-        levels, luts = _find_levels(ref_rd, dis_rd, int(level_frames), level_align == "apply", device,
-                                    engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
+        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
+        levels, luts, curves = _find_levels(ref_rd, dis_rd, int(level_frames), level_align == "apply", device, make_side,
+                                            curve=bool(level_curve), full_range=di.color_range == "full")
         alignment = dict(alignment or {}, levels=levels)
         if any(lut is not None for lut in luts):
             dis_rd = _LevelledReader(dis_rd, luts)
+        if any(t is not None for t in curves):
+            dis_rd = tabled = _TableReader(dis_rd, curves, device, make_side)
+    elif level_curve:
+        raise ValueError('level_curve needs level_align="report" or "apply"')
     coloured = None
     if colour_align is not None:
         if colour_align not in ("report", "apply"):
@@ -472,7 +487,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     blk = {i: shard.gather_records(local_blk[i], n, world_size, rank, gather_device, width=N.EXT_BLOCKS[i][1]) for i in want}
     if rank != 0:
-        for rd in (converter, resampler, registered, coloured):
+        for rd in (converter, resampler, registered, tabled, coloured):
             if rd is not None:
                 rd.close()
         return None
@@ -527,7 +542,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["resize"] = resized
     if input_info is not None:
         res["input"] = input_info
-    for rd in (converter, resampler, registered, coloured):   # on an error their contexts go with the readers
+    for rd in (converter, resampler, registered, tabled, coloured):   # on an error their contexts go with the readers
         if rd is not None:
             rd.close()
     return res
@@ -801,9 +816,10 @@ class _LevelledReader:
         return [p if k >= len(self._luts) or self._luts[k] is None else np.take(self._luts[k], p) for k, p in enumerate(planes)]
 
 
-def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make):
-    """(the `levels` object, [a correction table or None per plane]) of two opened, paired clips: the per-level transfer
-    table of a few pairs of every plane on a small context of its own"""
+def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make, curve: bool = False, full_range: bool = True):
+    """(the `levels` object, [a correction table or None per plane], [a curve table or None per plane]) of two opened, paired
+    clips: the per-level transfer table of a few pairs of every plane on a small context of its own.  curve: the monotone
+    curve on top (align.best_curve), and under `apply` the check of its inverse on the sampled pairs"""
     from . import align as AL
     ri = ref_rd.info
     idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
@@ -815,15 +831,63 @@ def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make):
     try:
         refs, caps = [ref_rd.frame(i) for i in idx], [dis_rd.frame(i) for i in idx]
         tables = [eng.level_stats([f[p] for f in refs], [f[p] for f in caps], p) for p in range(n_planes)]
+        checked = {}   # plane -> (its curve table, the squared error that is left on the sampled pairs)
+        if curve:
+            found = [AL.best_curve(T, ri.bit_depth, chroma=p > 0, full_range=full_range) for p, T in enumerate(tables)]
+            for p, lv in enumerate(found):
+                if apply and lv["kind"] == "curve" and lv["mismatch"]:
+                    table = AL.curve_lut(tables[p], ri.bit_depth)
+                    mapped = eng.table_apply([f[p] for f in caps], table, p)
+                    checked[p] = table, AL.table_sse(eng.level_stats([f[p] for f in refs], mapped, p))
+        else:
+            found = [AL.best_levels(T, ri.bit_depth, chroma=p > 0) for p, T in enumerate(tables)]
     finally:
         eng.close()
-    planes, luts = {}, []
-    for p, T in enumerate(tables):
-        lv = AL.best_levels(T, ri.bit_depth, chroma=p > 0)
-        lv["applied"] = bool(apply and lv["mismatch"])
-        luts.append(AL.correction_lut(lv, ri.bit_depth, chroma=p > 0) if lv["applied"] else None)
+    planes, luts, curves = {}, [], []
+    for p, lv in enumerate(found):
+        is_curve = lv["kind"] == "curve"
+        if curve:
+            n_pix = sum(int(x) for x in tables[p][:, :, 0].ravel())
+            lv["mse_after"] = checked[p][1] / n_pix if p in checked else None   # int / int: correctly rounded
+            lv["curve_applied"] = bool(p in checked and checked[p][1] < AL.table_sse(tables[p]))
+        lv["applied"] = lv["curve_applied"] if is_curve else bool(apply and lv["mismatch"])
+        luts.append(AL.correction_lut(lv, ri.bit_depth, chroma=p > 0) if lv["applied"] and not is_curve else None)
+        curves.append(checked[p][0] if is_curve and lv["applied"] else None)
         planes["yuv"[p]] = lv
-    return dict(planes["y"], planes=planes), luts
+    return dict(planes["y"], planes=planes), luts, curves
+
+
+class _TableReader:
+    """A captured clip with its sample levels mapped back through a transfer curve: plane p of every frame goes through the
+    integer table tables[p] on the GPU (FeatureEngine.table_apply; None: the plane is passed on as it is).  What score_files
+    reads under level_align="apply" with level_curve for the planes of kind "curve".  Built like _ColourReader -- a small
+    context of its own, frames fetched in runs of eight, the last run kept, one call per corrected plane and run.  No
+    file-descriptor path: the mapped samples exist in host arrays only.  close() frees the context."""
+    RUN = 8
+
+    def __init__(self, reader, tables, device, make):
+        info = self.info = reader.info
+        self._rd, self._tables = reader, list(tables)
+        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=1 if info.mono else 3,
+                         chroma_shift=(info.hshift, info.vshift), features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd)
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            frames = [list(self._rd.frame(j)) for j in range(first, min(first + self.RUN, len(self._rd)))]
+            for p, table in enumerate(self._tables):
+                if table is not None:
+                    for f, mapped in zip(frames, self._eng.table_apply([f[p] for f in frames], table, p)):
+                        f[p] = mapped
+            self._first, self._run = first, frames
+        return self._run[i - self._first]
 
 
 class _ColourReader:

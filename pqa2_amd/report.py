@@ -309,14 +309,20 @@ def levels_summary_line(levels: dict) -> str:
     kind = levels.get("kind", "identity")
     what = {"identity": "levels in place", "limited_to_full": "capture expanded from limited to full range",
             "full_to_limited": "capture compressed from full to limited range"}.get(kind, "capture levels scaled and offset")
+    if kind == "curve":   # pipeline.score_files(level_curve=True) only
+        gamma = levels.get("gamma")
+        what = "capture levels follow a transfer curve" + (f", gamma {gamma:.3f}" if gamma is not None else "")
     planes = levels.get("planes") or {"y": levels}
     done = [k for k in planes if planes[k].get("applied")]
     if done:
         tail = "corrected on " + ", ".join(k.upper() for k in done)
     else:
         tail = "not corrected" if levels.get("mismatch") else "nothing to correct"
+    fitted = f"{levels.get('mse_affine', 0.0):.2f} after the fit"
+    if kind == "curve":
+        fitted += f", {levels.get('mse_monotone') or 0.0:.2f} about the curve"
     return (f"Level alignment: {what} (gain {levels.get('gain', 1.0):.4f}, offset {levels.get('offset', 0.0):+.2f}), MSE "
-            f"{levels.get('mse_identity', 0.0):.2f} as captured, {levels.get('mse_affine', 0.0):.2f} after the fit, "
+            f"{levels.get('mse_identity', 0.0):.2f} as captured, {fitted}, "
             f"{levels.get('frames', 0)} frames, {tail}")
 
 

@@ -100,6 +100,10 @@ def main(argv=None) -> int:
                          "per-level transfer table of a few frame pairs; the JSON's alignment object gets a levels entry")
     ap.add_argument("--level-correct", action="store_true",
                     help="--level-align, and undo a mapping found on every plane that has one before scoring")
+    ap.add_argument("--level-curve", action="store_true",
+                    help="--level-align, and fit a monotone transfer curve on top (a gamma mismatch, a contrast enhancer, a black "
+                         "stretch); with --level-correct a plane whose curve lowers the error goes through its inverse table on the "
+                         "GPU before scoring")
     ap.add_argument("--level-frames", type=int, default=8, metavar="N",
                     help="with --level-align / --level-correct: measure N frame pairs spread evenly over the clips (default 8)")
     ap.add_argument("--colour-align", action="store_true",
@@ -243,7 +247,8 @@ def main(argv=None) -> int:
                           **({"align": a.align, "align_frames": a.align_frames} if a.align else {}),
                           **({"spatial_align": a.spatial_align, "spatial_frames": a.spatial_frames} if a.spatial_align else {}),
                           **({"level_align": "apply" if a.level_correct else "report", "level_frames": a.level_frames}
-                             if (a.level_align or a.level_correct) else {}),
+                             if (a.level_align or a.level_correct or a.level_curve) else {}),
+                          **({"level_curve": True} if a.level_curve else {}),
                           **({"colour_align": "apply" if a.colour_correct else "report", "colour_frames": a.colour_frames}
                              if (a.colour_align or a.colour_correct) else {}),
                           **({"active_picture": "apply" if a.active_crop else "report", "active_frames": a.active_frames,

@@ -165,6 +165,7 @@ class VMAFAnalyzer(QObject):
         self.spatial_align_radius = 8         # -radius ... radius pixels in x and y (pipeline.score_files(spatial_align=))
         self.level_align_enabled = False      # level alignment before scoring: measure the capture's gain / offset / range
         self.level_correct_enabled = False    # ... and undo it (implies the measurement; pipeline.score_files(level_align=))
+        self.level_curve_enabled = False      # ... with a monotone transfer curve on top: gamma, contrast enhancer (implies the measurement; score_files(level_curve=))
         self.colour_align_enabled = False     # colour-matrix alignment before scoring: measure the capture's 3 x 4 colour map
         self.colour_correct_enabled = False   # ... and undo it (implies the measurement; pipeline.score_files(colour_align=))
         self.active_picture_enabled = False   # active-picture detection before scoring: measure the black bars of both clips
@@ -235,6 +236,8 @@ class VMAFAnalyzer(QObject):
                 self.level_align_enabled = bool(s["level_align_enabled"])
             if "level_correct_enabled" in s:
                 self.level_correct_enabled = bool(s["level_correct_enabled"])
+            if "level_curve_enabled" in s:
+                self.level_curve_enabled = bool(s["level_curve_enabled"])
             if "colour_align_enabled" in s:
                 self.colour_align_enabled = bool(s["colour_align_enabled"])
             if "colour_correct_enabled" in s:
@@ -278,7 +281,7 @@ class VMAFAnalyzer(QObject):
                              colour_align_enabled=False, colour_correct_enabled=False, active_picture_enabled=False,
                              active_crop_enabled=False, distortion_map_enabled=False, distortion_tile=32,
                              spectrum_enabled=False, spectrum_levels=4, temporal_enabled=False, temporal_tile=32,
-                             coding_grid_enabled=False):
+                             coding_grid_enabled=False, level_curve_enabled=False):
         self.pool_method = pool_method
         self.enable_motion_score = enable_motion_score
         self.enable_temporal_features = enable_temporal_features
@@ -301,6 +304,7 @@ class VMAFAnalyzer(QObject):
         self.spatial_align_radius = max(1, min(16, int(spatial_align_radius)))
         self.level_align_enabled = bool(level_align_enabled)
         self.level_correct_enabled = bool(level_correct_enabled)
+        self.level_curve_enabled = bool(level_curve_enabled)
         self.colour_align_enabled = bool(colour_align_enabled)
         self.colour_correct_enabled = bool(colour_correct_enabled)
         self.active_picture_enabled = bool(active_picture_enabled)
@@ -526,7 +530,8 @@ class VMAFAnalyzer(QObject):
                 **({"align": int(self.align_max_offset)} if self.align_enabled else {}),
                 **({"spatial_align": int(self.spatial_align_radius)} if self.spatial_align_enabled else {}),
                 **({"level_align": "apply" if self.level_correct_enabled else "report"}
-                   if (self.level_align_enabled or self.level_correct_enabled) else {}),
+                   if (self.level_align_enabled or self.level_correct_enabled or self.level_curve_enabled) else {}),
+                **({"level_curve": True} if self.level_curve_enabled else {}),
                 **({"colour_align": "apply" if self.colour_correct_enabled else "report"}
                    if (self.colour_align_enabled or self.colour_correct_enabled) else {}),
                 **({"active_picture": "apply" if self.active_crop_enabled else "report"}
@@ -579,6 +584,8 @@ class VMAFAnalyzer(QObject):
             cmd += ["--level-correct"]
         elif self.level_align_enabled:
             cmd += ["--level-align"]
+        if self.level_curve_enabled:
+            cmd += ["--level-curve"]
         if self.colour_correct_enabled:
             cmd += ["--colour-correct"]
         elif self.colour_align_enabled:
@@ -718,7 +725,7 @@ class VMAFAnalyzer(QObject):
                 results["integrity"] = vmaf_data.get("integrity")
                 results["integrity_log"] = self._integrity_path
             if (self.align_enabled or self.spatial_align_enabled or self.level_align_enabled
-                    or self.level_correct_enabled or self.register_filter or self.colour_align_enabled
+                    or self.level_correct_enabled or self.level_curve_enabled or self.register_filter or self.colour_align_enabled
                     or self.colour_correct_enabled or self.active_picture_enabled
                     or self.active_crop_enabled):   # how the clips were paired, from the log's top level
                 from . import report
