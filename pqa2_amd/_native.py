@@ -65,7 +65,7 @@ GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 EXPORTS = [
     "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
     "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_submit_packed", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
-    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
+    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape", "pqa_debug_adm_need",
     "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
@@ -94,6 +94,8 @@ SURFACE_NV12, SURFACE_P01X = 1, 2
 SURFACE_PLANAR, SURFACE_UYVY, SURFACE_YUYV, SURFACE_V210 = 0, 3, 4, 5
 PACKED_FORMATS = {"uyvy422": SURFACE_UYVY, "yuyv422": SURFACE_YUYV, "v210": SURFACE_V210}
 PACKED_BIT_DEPTH = {SURFACE_UYVY: 8, SURFACE_YUYV: 8, SURFACE_V210: 10}
+# packed RGB captures (4 bytes a pixel; r210 10 bit): pqa_rgb_convert only
+SURFACE_BGRA, SURFACE_ARGB, SURFACE_RGBA, SURFACE_ABGR, SURFACE_R210 = 6, 7, 8, 9, 10
 
 
 class PqaSurfaceClip(C.Structure):
@@ -113,6 +115,14 @@ class PqaUnpackSpec(C.Structure):
 SITE_COSITED, SITE_CENTRE = 0, 1     # PQA_SITE_*: where a subsampled chroma sample sits along an axis
 CONVERT_GENERIC = 1                  # pqa_convert_spec.flags: the general kernel whatever the layout
 CONVERT_BIT_DEPTHS = (8, 10, 12)
+RGB_GENERIC = 1                      # pqa_rgb_spec.flags: the general kernel whatever the layout
+RGB_BIT_DEPTHS = (8, 10)             # pqa_rgb_spec.dst_bits
+
+
+class PqaRgbSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("dst_bits", C.c_uint32), ("hshift", C.c_uint32), ("vshift", C.c_uint32), ("hsite", C.c_uint32), ("vsite", C.c_uint32),
+                ("flags", C.c_uint32), ("m", C.c_int32 * 12)]
 
 
 class PqaTableSpec(C.Structure):
@@ -281,6 +291,8 @@ def load():
     lib.pqa_unpack_device.argtypes = [vp, C.POINTER(PqaUnpackSpec), vp, i64, i64, i32, C.POINTER(PqaDeviceClip)]
     lib.pqa_format_convert.argtypes = [vp, C.POINTER(PqaConvertSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32]
     lib.pqa_format_convert_device.argtypes = [vp, C.POINTER(PqaConvertSpec), vp, i64, i64, vp, i64, i64, i32]
+    lib.pqa_rgb_convert_device.argtypes = [vp, C.POINTER(PqaRgbSpec), vp, i64, i64, i32, C.POINTER(PqaDeviceClip)]
+    lib.pqa_rgb_convert.argtypes = [vp, C.POINTER(PqaRgbSpec), C.POINTER(vp), i64, i32, C.POINTER(vp), C.POINTER(i64 * 3)]
     lib.pqa_table_apply.argtypes = [vp, C.POINTER(PqaTableSpec), vp, C.POINTER(vp), i64, C.POINTER(vp), i64, i32]
     lib.pqa_table_apply_device.argtypes = [vp, C.POINTER(PqaTableSpec), vp, vp, i64, i64, vp, i64, i64, i32]
     lib.pqa_unpack.argtypes = [vp, C.POINTER(PqaUnpackSpec), C.POINTER(vp), i64, i32, C.POINTER(vp), C.POINTER(i64 * 3)]

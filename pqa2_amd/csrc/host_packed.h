@@ -1,5 +1,5 @@
-// Host side of the packed capture formats (pqa_submit_packed, pqa_unpack; unpack.hip has the kernel), free of any device
-// call: the row and file geometry of UYVY / YUYV / v210, how one side of a chunk of frames -- planar planes or packed frames
+// Host side of the packed capture formats (pqa_submit_packed, pqa_unpack, pqa_rgb_convert; unpack.hip and rgb_convert.hip have
+// the kernels), free of any device call: the row and file geometry of UYVY / YUYV / v210 and of the packed RGB formats, how one side of a chunk of frames -- planar planes or packed frames
 // -- lies in a pinned buffer, the copy of a caller's frames into it and the copy of unpacked planes back out.  Packed bytes
 // are copied as they are: nothing is de-interleaved on the host.  Header-only and plain C++17, as host_stage.h is, so that
 // a CPU program drives it under AddressSanitizer + UBSan (tests/packed_harness.cpp).
@@ -24,6 +24,32 @@ inline int64_t packed_min_row_bytes(uint32_t f, int w) {
 // rows of a headerless file: v210 pads to 48 pixels (128 bytes), the 8-bit formats do not pad
 inline int64_t packed_file_stride(uint32_t f, int w) {
   return f == FMT_V210 ? (((int64_t)w + 47) / 48) * 128 : packed_min_row_bytes(f, w);
+}
+
+// Packed RGB captures (pqa_rgb_convert; rgb_convert.hip has the kernel): a pixel is 4 bytes in every format.
+enum { FMT_BGRA = 6, FMT_ARGB = 7, FMT_RGBA = 8, FMT_ABGR = 9, FMT_R210 = 10 };   // the PQA_SURFACE_* values
+inline bool rgb_format(uint32_t f) { return f >= FMT_BGRA && f <= FMT_R210; }
+inline int rgb_bit_depth(uint32_t f) { return f == FMT_R210 ? 10 : 8; }
+inline int64_t rgb_min_row_bytes(int w) { return 4 * (int64_t)w; }
+// rows of a headerless file: r210 pads to 64 pixels (256 bytes), the 8-bit formats do not pad
+inline int64_t rgb_file_stride(uint32_t f, int w) { return f == FMT_R210 ? (((int64_t)w + 63) / 64) * 256 : rgb_min_row_bytes(w); }
+// the byte of R, G, B in a pixel of the 8-bit formats (r210: unused, zeros)
+inline void rgb_byte_order(uint32_t f, int at[3]) {
+  static const int order[4][3] = {{2, 1, 0}, {1, 2, 3}, {0, 1, 2}, {3, 2, 1}};   // BGRA, ARGB, RGBA, ABGR
+  for (int k = 0; k < 3; ++k) at[k] = f >= FMT_BGRA && f <= FMT_ABGR ? order[f - FMT_BGRA][k] : 0;
+}
+// The bound that makes int32 arithmetic legal in rgb_convert.hip: for every row c of the Q14 matrix m[3][4] (column 0 the
+// offset), the extreme of |A_c| = |m[c][0] + m[c][1] R + m[c][2] G + m[c][3] B| over the cube [0, 2^src_bits - 1]^3, times the
+// tap weights' sum S_x S_y (8 an axis of shift 1, else 1), plus the rounding half 2^(13 + log2(S_x S_y)), stays below 2^31.
+inline bool rgb_matrix_fits(const int32_t m[12], int src_bits, int hshift, int vshift) {
+  const int64_t top = ((int64_t)1 << src_bits) - 1, s = (int64_t)1 << (3 * (hshift + vshift));
+  for (int c = 0; c < 3; ++c) {
+    int64_t hi = m[4 * c], lo = m[4 * c];
+    for (int k = 1; k < 4; ++k) (m[4 * c + k] > 0 ? hi : lo) += (int64_t)m[4 * c + k] * top;
+    const int64_t ext = (hi < 0 ? -hi : hi) > (lo < 0 ? -lo : lo) ? (hi < 0 ? -hi : hi) : (lo < 0 ? -lo : lo);
+    if (ext * s + (s << 13) >= ((int64_t)1 << 31)) return false;
+  }
+  return true;
 }
 
 // One side of a chunk as it is staged: n_planes planes per frame (a packed frame is one "plane" of its minimum row bytes),
@@ -58,6 +84,18 @@ inline ClipLayout unpacked_layout(uint32_t format, int w, int h, int n_planes) {
   const size_t es = (size_t)packed_sample_bytes(format);
   const size_t rb[3] = {(size_t)w * es, (size_t)((w + 1) / 2) * es, (size_t)((w + 1) / 2) * es};
   const int rows[3] = {h, h, h};
+  return clip_layout(n_planes, rb, rows, 16, 16);
+}
+
+inline ClipLayout rgb_layout(int w, int h) {
+  const size_t rb[3] = {(size_t)rgb_min_row_bytes(w), 0, 0};
+  const int rows[3] = {h, 0, 0};
+  return clip_layout(1, rb, rows, 16, 16);
+}
+// the planes an RGB frame of w x h converts to: Y of w x h, U and V of cw x ch, samples of es bytes
+inline ClipLayout converted_layout(int w, int h, int cw, int ch, int es, int n_planes) {
+  const size_t rb[3] = {(size_t)w * es, (size_t)cw * es, (size_t)cw * es};
+  const int rows[3] = {h, ch, ch};
   return clip_layout(n_planes, rb, rows, 16, 16);
 }
 

@@ -593,6 +593,21 @@ hipError_t launch_format_convert(hipStream_t stream, const ConvertLayout& src, c
                                  bool generic, const void* src_planes, int64_t src_row_pitch, int64_t src_frame_pitch, void* dst_planes,
                                  int64_t dst_row_pitch, int64_t dst_frame_pitch, int n_frames);
 
+// ---- packed RGB captures -> Y'CbCr planes: unpack, matrix, range, depth, subsampling, siting in one pass (rgb_convert.hip) ----
+// n_frames packed frames of w x h pixels (1 ... 8192 each way; format: host::FMT_BGRA ... FMT_R210, 4 bytes a pixel) become the
+// planes dst[0..2] = Y, U, V of the layout `dst` (bits 8 / 10, chroma shifts 0 / 1, siting per axis; chroma planes of
+// convert_plane_size() samples; u8 at 8 bit, otherwise u16) through the Q14 matrix m[3][4], column 0 the offset.  dst[1] and
+// dst[2] both null: luma only.  Definition, the int32 bound and the fast paths: the head of rgb_convert.hip.  Frame f at
+// base + f * frame_pitch, pitches in BYTES.  generic: the general kernel whatever the layout (the fast paths' test partner; the
+// same integers).  Reads no source row beyond 4 * w bytes, writes no byte outside the samples of a destination row.
+// hipErrorInvalidValue, before any launch, on a format, layout or size out of range, more than 65535 frames, a matrix beyond
+// host::rgb_matrix_fits, one chroma destination of two, an r210 base or pitch that is no multiple of 4, a destination that is not
+// made of whole samples or a pitch below a row.
+constexpr int kRgbChunk = 8;   // frames per chunk of the host entry
+hipError_t launch_rgb_convert(hipStream_t stream, int format, const ConvertLayout& dst, bool generic, const int32_t m[12],
+                              const void* src, int64_t src_row_pitch, int64_t src_frame_pitch, void* const dst_planes[3],
+                              const int64_t dst_row_pitch[3], const int64_t dst_frame_pitch[3], int w, int h, int n_frames);
+
 // ---- transfer-curve alignment: planes through an integer table (table_apply.hip) ---------------------------------------------
 // dst[y][x] = table[min(src[y][x], L - 1)], L = 2^bit_depth, for n_frames planes of w x h samples (1 ... 8192 each way; u8 at
 // 8 bit, otherwise u16).  table: L entries of the sample type in DEVICE memory, 16-byte aligned; any table, monotone or not.

@@ -83,6 +83,7 @@ enum SideBuf {
   SIDE_UNPACK_SRC, SIDE_UNPACK_DST,                                            // pqa_unpack, unpack.hip: a chunk of uploaded packed frames / of unpacked planes
   SIDE_CONVERT_SRC, SIDE_CONVERT_DST,                                          // pqa_format_convert, format_convert.hip: a chunk of uploaded / of converted planes
   SIDE_TABLE_LUT, SIDE_TABLE_SRC, SIDE_TABLE_DST,                              // pqa_table_apply[_device], table_apply.hip: the table; pqa_table_apply: a chunk of uploaded / of mapped planes
+  SIDE_RGB_SRC, SIDE_RGB_DST,                                                  // pqa_rgb_convert, rgb_convert.hip: a chunk of uploaded packed RGB frames / of converted planes
   kSideBufs
 };
 

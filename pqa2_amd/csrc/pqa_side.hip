@@ -1182,6 +1182,125 @@ int pqa_format_convert(pqa_ctx* c, const pqa_convert_spec* spec, const void* con
   return PQA_OK;
 }
 
+// ---- packed RGB captures -> Y'CbCr planes (rgb_convert.hip) -------------------------------------------------------------------
+
+namespace {
+// The argument rules both entries share, in spec_check's order (no device call); then the rows of the packed source.
+int rgb_check(pqa_ctx* c, const pqa_rgb_spec* sp, const void* src, const void* dst, int32_t n_frames, int64_t src_row, int64_t src_frame) {
+  const int rc = spec_check(c, "rgb_convert", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (!host::rgb_format(sp->format))
+      return fail(c, PQA_EINVAL, "rgb_convert: format %u is not a packed RGB format (BGRA 6, ARGB 7, RGBA 8, ABGR 9, R210 10)", sp->format);
+    if (sp->flags & ~(uint32_t)PQA_RGB_GENERIC) return fail(c, PQA_EINVAL, "rgb_convert: unknown flag bits %#x", sp->flags);
+    if (sp->dst_bits != 8 && sp->dst_bits != 10) return fail(c, PQA_EINVAL, "rgb_convert: destination bit depth %u is not 8 or 10", sp->dst_bits);
+    for (uint32_t s : {sp->hshift, sp->vshift})
+      if (s > 1) return fail(c, PQA_EINVAL, "rgb_convert: chroma shift %u outside 0 ... 1", s);
+    for (uint32_t s : {sp->hsite, sp->vsite})
+      if (s != PQA_SITE_COSITED && s != PQA_SITE_CENTRE) return fail(c, PQA_EINVAL, "rgb_convert: siting %u is not PQA_SITE_COSITED or _CENTRE", s);
+    if (!host::rgb_matrix_fits(sp->m, host::rgb_bit_depth(sp->format), (int)sp->hshift, (int)sp->vshift))
+      return fail(c, PQA_EINVAL, "rgb_convert: the matrix leaves int32 (extreme |A| times the tap sum %d plus the rounding half reaches 2^31)",
+                  1 << (3 * (sp->hshift + sp->vshift)));
+    return (int)PQA_OK;
+  });
+  if (rc != PQA_OK || n_frames == 0) return rc;
+  const int64_t min_row = host::rgb_min_row_bytes((int)sp->width);
+  if (src_row < min_row)
+    return fail(c, PQA_EINVAL, "rgb_convert: source pitch %lld is smaller than a packed row of %lld bytes", (long long)src_row, (long long)min_row);
+  if (sp->format == PQA_SURFACE_R210 && ((src_row | src_frame) & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 pitch is not a multiple of 4");
+  return PQA_OK;
+}
+ConvertLayout rgb_side(const pqa_rgb_spec* sp) {
+  return ConvertLayout{(int)sp->dst_bits, (int)sp->hshift, (int)sp->vshift, (int)sp->hsite, (int)sp->vsite};
+}
+}  // namespace
+
+int pqa_rgb_convert_device(pqa_ctx* c, const pqa_rgb_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
+                           int32_t n_frames, const pqa_device_clip* dst) {
+  int rc = rgb_check(c, spec, src, dst, n_frames, src_row_pitch, src_frame_pitch);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  if (!dst->plane[0]) return fail(c, PQA_EINVAL, "rgb_convert: null luma destination");
+  if (!dst->plane[1] != !dst->plane[2]) return fail(c, PQA_EINVAL, "rgb_convert: chroma destinations: both or neither");
+  if (spec->format == PQA_SURFACE_R210 && ((uintptr_t)src & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 source is not 4-byte aligned");
+  const ConvertLayout D = rgb_side(spec);
+  const int es = D.bits > 8 ? 2 : 1, w = (int)spec->width, h = (int)spec->height, cw = convert_plane_size(w, D.hshift);
+  void* planes[3] = {nullptr, nullptr, nullptr};
+  for (int p = 0; p < (dst->plane[1] ? 3 : 1); ++p) {
+    planes[p] = const_cast<void*>(dst->plane[p]);
+    if (((uintptr_t)planes[p] | (uintptr_t)dst->row_pitch[p] | (uintptr_t)dst->frame_pitch[p]) & (uintptr_t)(es - 1))
+      return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination is not made of whole samples", p);
+    if (dst->row_pitch[p] < (int64_t)(p ? cw : w) * es) return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination pitch smaller than a row", p);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipError_t e = hipSuccess;
+  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid) {
+    void* at[3] = {nullptr, nullptr, nullptr};
+    for (int p = 0; p < 3; ++p)
+      if (planes[p]) at[p] = (uint8_t*)planes[p] + (int64_t)f0 * dst->frame_pitch[p];
+    e = launch_rgb_convert(c->stream, (int)spec->format, D, (spec->flags & PQA_RGB_GENERIC) != 0, spec->m,
+                           (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch, at, dst->row_pitch,
+                           dst->frame_pitch, w, h, chunk_len(n_frames, f0, kGrid));
+  }
+  return side_finish(c, "rgb_convert", e, nullptr, nullptr, 0);
+}
+
+int pqa_rgb_convert(pqa_ctx* c, const pqa_rgb_spec* spec, const void* const* src_frames, int64_t src_row_stride, int32_t n_frames,
+                    void* const* dst_planes, const int64_t dst_strides[3]) {
+  int rc = rgb_check(c, spec, src_frames, dst_planes, n_frames, src_row_stride, 0);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  if (!dst_strides) return fail(c, PQA_EINVAL, "rgb_convert: null destination strides");
+  const ConvertLayout DL = rgb_side(spec);
+  const int es = DL.bits > 8 ? 2 : 1, w = (int)spec->width, h = (int)spec->height;
+  const int cw = convert_plane_size(w, DL.hshift), ch = convert_plane_size(h, DL.vshift);
+  const int np = dst_planes[1] && dst_planes[2] ? 3 : 1;
+  if (np == 1 && (dst_planes[1] || dst_planes[2])) return fail(c, PQA_EINVAL, "rgb_convert: chroma destinations: both or neither");
+  for (int f = 0; f < n_frames; ++f) {   // before anything is queued
+    if (!src_frames[f]) return fail(c, PQA_EINVAL, "rgb_convert: source frame %d pointer is null", f);
+    if (spec->format == PQA_SURFACE_R210 && ((uintptr_t)src_frames[f] & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 source frame %d is not 4-byte aligned", f);
+    for (int p = 0; p < np; ++p)
+      if (!dst_planes[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "rgb_convert: destination plane %d of frame %d is null", p, f);
+  }
+  for (int p = 0; p < np; ++p) {
+    if (dst_strides[p] & (int64_t)(es - 1)) return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination is not made of whole samples", p);
+    if (dst_strides[p] < (int64_t)(p ? cw : w) * es) return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination stride smaller than a row", p);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  // As pqa_unpack: chunks of kRgbChunk frames, packed bytes out through the first pinned chunk of the side analyses, planes back
+  // through the second, device buffers of this entry's own (rows 16 bytes apart at least, so the fast paths apply); a chunk is
+  // uploaded, converted, downloaded and copied out before the next.
+  const host::ClipLayout S = host::rgb_layout(w, h), D = host::converted_layout(w, h, cw, ch, es, np);
+  const int chunk = n_frames < kRgbChunk ? n_frames : kRgbChunk;
+  rc = side_pin_reserve(c, 0, S.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, D.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RGB_SRC, S.frame_bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RGB_DST, D.frame_bytes * chunk);
+  if (rc != PQA_OK) return rc;
+  const int64_t src_strides[3] = {src_row_stride, 0, 0};
+  for (int f0 = 0; f0 < n_frames; f0 += kRgbChunk) {
+    const int n = chunk_len(n_frames, f0, kRgbChunk);
+    host::pack_clip(c->side_pin[0], S, src_frames, src_strides, f0, n);
+    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_RGB_SRC], c->side_pin[0], S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+      void* at[3] = {nullptr, nullptr, nullptr};
+      int64_t rp[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
+      for (int p = 0; p < np; ++p) {
+        at[p] = (uint8_t*)c->side_buf[SIDE_RGB_DST] + D.off[p];
+        rp[p] = D.plane[p].pitch;
+        fp[p] = (int64_t)D.frame_bytes;
+      }
+      e = launch_rgb_convert(c->stream, (int)spec->format, DL, (spec->flags & PQA_RGB_GENERIC) != 0, spec->m, c->side_buf[SIDE_RGB_SRC],
+                             S.plane[0].pitch, (int64_t)S.frame_bytes, at, rp, fp, w, h, n);
+    }
+    rc = side_finish(c, "rgb_convert", e, c->side_pin[1], c->side_buf[SIDE_RGB_DST], D.frame_bytes * n);
+    if (rc != PQA_OK) return rc;
+    host::unpack_clip_out(c->side_pin[1], D, dst_planes, dst_strides, f0, n);
+  }
+  return PQA_OK;
+}
+
 // ---- transfer-curve alignment: planes through an integer table (table_apply.hip) ----------------------------------------------
 
 namespace {

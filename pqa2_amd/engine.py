@@ -375,6 +375,65 @@ class FeatureEngine:
         self._check(self.lib.pqa_format_convert_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch,
                                                        dst_ptr or None, dst_row_pitch, dst_frame_pitch, int(n_frames)))
 
+    # -- packed RGB captures -------------------------------------------------------------------
+    @staticmethod
+    def _rgb_spec(fmt, shape, dst, m, generic: bool):
+        """the pqa_rgb_spec of frames of shape = (height, width); dst = (hshift, vshift, hsite, vsite, bits); m: 12 Q14 integers"""
+        from . import rgb as R
+        if isinstance(fmt, str) and fmt not in R.FORMATS:
+            raise ValueError(f"unknown packed RGB format {fmt!r} (one of {', '.join(R.FORMATS)})")
+        sp = N.PqaRgbSpec()
+        sp.struct_size, sp.format = C.sizeof(N.PqaRgbSpec), R.FORMATS[fmt] if isinstance(fmt, str) else max(0, int(fmt))
+        sp.width, sp.height = max(0, int(shape[1])), max(0, int(shape[0]))
+        # a value the library must refuse still has to fit its field
+        sp.hshift, sp.vshift, sp.hsite, sp.vsite = (int(v) & 0xFFFFFFFF for v in dst[:4])
+        sp.dst_bits, sp.flags = max(0, int(dst[4])), N.RGB_GENERIC if generic else 0
+        if len(m) != 12:
+            raise ValueError("rgb_convert needs a matrix of 12 integers (rows of offset, R, G, B in Q14)")
+        for k, v in enumerate(m):
+            sp.m[k] = int(v)
+        return sp
+
+    def rgb_convert(self, frames, fmt, shape, dst, m, luma_only: bool = False, generic: bool = False):
+        """A list of [Y, U, V] -- or [Y] with luma_only -- per frame: packed RGB frames in HOST memory converted on the GPU
+        (pqa_rgb_convert; definition: include/pqa_vmaf.h).  frames: 2-D uint8 arrays of packed rows (the rows of a frame may be
+        padded; r210: 4-byte aligned); fmt: "bgra", "argb", "rgba", "abgr" or "r210"; shape = (height, width) in pixels;
+        dst = (hshift, vshift, hsite, vsite, bits), shifts 0 / 1, sitings N.SITE_COSITED / N.SITE_CENTRE, bits 8 / 10 (uint8,
+        else uint16); m: the Q14 matrix (pqa2_amd.rgb.conversion_matrix).  generic: the general kernel whatever the layout
+        (the same integers).  The size is the call's own, not this context's."""
+        sp = self._rgb_spec(fmt, shape, dst, m, generic)
+        arrs = [np.asarray(a) for a in frames]
+        if any(a.ndim != 2 or a.dtype != np.uint8 or a.strides[1] != 1 or a.strides[0] != arrs[0].strides[0] for a in arrs):
+            arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrs]
+        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
+            raise ValueError("rgb_convert needs 2-D arrays of packed rows of one size")
+        h, w = int(shape[0]), int(shape[1])
+        ch, cw = self.convert_plane_shape((h, w), int(dst[0]) & 1, int(dst[1]) & 1)
+        dt = np.uint16 if int(dst[4]) > 8 else np.uint8
+        n = len(arrs)
+        out = [[np.empty((h, w) if p == 0 else (ch, cw), dt) for p in range(1 if luma_only else 3)] for _ in arrs]
+        sptr, dptr = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(3 * n, 1))()
+        for i, (a, o) in enumerate(zip(arrs, out)):
+            sptr[i] = a.ctypes.data
+            for p, plane in enumerate(o):
+                dptr[3 * i + p] = plane.ctypes.data
+        item = np.dtype(dt).itemsize
+        ds = (C.c_int64 * 3)(w * item, cw * item, cw * item)
+        self._check(self.lib.pqa_rgb_convert(self._ctx, C.byref(sp), sptr, arrs[0].strides[0] if arrs else 0, n, dptr, C.byref(ds)))
+        return out
+
+    def rgb_convert_resident(self, fmt, shape, dst, m, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, n_frames: int, dst_ptrs,
+                             dst_row_pitch, dst_frame_pitch, generic: bool = False):
+        """The same for frames in HBM (device pointers, pitches in bytes; pqa_rgb_convert_device): n_frames packed frames at
+        src_ptr become the planes at dst_ptrs = (Y, U, V) or (Y,) for luma only.  Nothing crosses PCIe; the planes can go
+        straight into submit_resident or any *_resident analysis."""
+        sp = self._rgb_spec(fmt, shape, dst, m, generic)
+        d = N.PqaDeviceClip()
+        for p, ptr in enumerate(dst_ptrs):
+            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptr or None, dst_row_pitch[p], dst_frame_pitch[p]
+        self._check(self.lib.pqa_rgb_convert_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch, int(n_frames),
+                                                    C.byref(d)))
+
     def _host_clip(self, side, keep):
         """the pqa_host_clip of one side of submit_packed: (frames, format name or None)"""
         frames, fmt = side

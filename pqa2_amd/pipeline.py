@@ -43,7 +43,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 spectrum_gain_floor: float = 0.5, temporal: int = 0, temporal_planes: str = "y", temporal_min_mse: float = 1.0,
                 temporal_blend_min: float = 1 / 16, temporal_still_mse: float = 0.25,
                 temporal_pop_factor: float = 4, coding_grid: bool = False, grid_planes: str = "y", grid_periods=(4, 64),
-                grid_z2: float = 25.0, chroma_mismatch: str = "error", chroma_siting: str | None = None) -> ScoreResult | None:
+                grid_z2: float = 25.0, chroma_mismatch: str = "error", chroma_siting: str | None = None,
+                rgb_matrix: str | None = None, rgb_range: str | None = None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -203,7 +204,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     on their subsampled axes.  Under "convert" a packed file is read through the numpy unpack (`packed_upload` false).  Then,
     under "luma", or when a packed file is read, the result carries `input` = {"reference": pix_fmt, "distorted": pix_fmt,
     "planes_scored": "y" | "yuv", "packed_upload": bool}; a conversion adds "conversion": {"side": "distorted", "from": pix_fmt,
-    "to": pix_fmt, "bit_depth": [from, to], "siting": {"from": [h, v], "to": [h, v]}}."""
+    "to": pix_fmt, "bit_depth": [from, to], "siting": {"from": [h, v], "to": [h, v]}}.
+    Packed RGB captures (.bgra, .argb, .rgba, .abgr, .r210; yuvio.RgbReader) have no Y'CbCr form to refuse, so whatever
+    `chroma_mismatch` says an RGB clip is converted on the GPU, before any other step reads it, to the OTHER clip's layout, siting
+    (`chroma_siting` overrides as above) and depth (8 or 10; a 12-bit partner is a ValueError) in one pass with one rounding
+    (FeatureEngine.rgb_convert; matrix and taps of this library's own, not swscale's); two RGB clips both go to 4:4:4 at the
+    reference's depth.  `rgb_matrix`: "bt601", "bt709" or "bt2020"; None: bt601 up to 576 lines, else bt709.  `rgb_range`: "full"
+    or "limited" R'G'B'; None: full for the 8-bit formats, limited for r210, which is what the cards deliver.  The Y'CbCr range
+    follows the partner's header (XCOLORRANGE=FULL: full, else limited).  `input` then carries "conversion": {"side", "from", "to",
+    "matrix", "rgb_range", "yuv_range", "bit_depth": [from, to], "siting": {"to": [h, v]}, "coefficients": [12 Q14 integers]} (a
+    list of two such objects when both clips are RGB), planes_scored "yuv", packed_upload false."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -214,8 +224,32 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         raise ValueError('chroma_mismatch must be "error" or "luma" or "convert"')
     if chroma_siting is not None and chroma_siting not in CHROMA_SITINGS:
         raise ValueError('chroma_siting must be None, "left", "center" or "topleft"')
+    from . import rgb as RGB
+    from .align import COLOUR_STANDARDS
+    if rgb_matrix is not None and rgb_matrix not in COLOUR_STANDARDS:
+        raise ValueError(f"rgb_matrix must be None or one of {sorted(COLOUR_STANDARDS)}")
+    if rgb_range is not None and rgb_range not in RGB.RANGES:
+        raise ValueError('rgb_range must be None, "full" or "limited"')
     input_info = None
-    if ri.packed or di.packed:
+    rgb_readers = []
+    if ri.packed in RGB.FORMATS or di.packed in RGB.FORMATS:
+        make = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
+        both = ri.packed in RGB.FORMATS and di.packed in RGB.FORMATS
+        plain = yuvio_info_444(ri) if both else None       # two RGB clips: 4:4:4 at the reference's depth
+        conversions = []
+        pix = {"reference": ri.pix_fmt, "distorted": di.pix_fmt}
+        if ri.packed in RGB.FORMATS:
+            ref_rd = _RgbReader(ref_rd, plain or di, chroma_siting, device, make, rgb_matrix, rgb_range, "reference")
+            rgb_readers.append(ref_rd)
+            conversions.append(ref_rd.conversion)
+        if di.packed in RGB.FORMATS:
+            dis_rd = _RgbReader(dis_rd, plain or ri, chroma_siting, device, make, rgb_matrix, rgb_range, "distorted")
+            rgb_readers.append(dis_rd)
+            conversions.append(dis_rd.conversion)
+        ri, di = ref_rd.info, dis_rd.info
+        input_info = {**pix, "planes_scored": "yuv", "packed_upload": False,
+                      "conversion": conversions[0] if len(conversions) == 1 else conversions}
+    elif ri.packed or di.packed:
         input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False}
     if (chroma_mismatch == "luma" and ri.bit_depth == di.bit_depth
             and (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono)):
@@ -487,7 +521,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     blk = {i: shard.gather_records(local_blk[i], n, world_size, rank, gather_device, width=N.EXT_BLOCKS[i][1]) for i in want}
     if rank != 0:
-        for rd in (converter, resampler, registered, tabled, coloured):
+        for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured):
             if rd is not None:
                 rd.close()
         return None
@@ -542,7 +576,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["resize"] = resized
     if input_info is not None:
         res["input"] = input_info
-    for rd in (converter, resampler, registered, tabled, coloured):   # on an error their contexts go with the readers
+    for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured):   # on an error their contexts go with the readers
         if rd is not None:
             rd.close()
     return res
@@ -628,6 +662,68 @@ class _ConvertedReader:
             chroma = self._eng.format_convert([f[1] for f in frames] + [f[2] for f in frames], self._luma_shape, self._src, self._dst)
             self._first, self._run = first, [[luma[k], chroma[k], chroma[n + k]] for k in range(n)]
         return self._run[i - self._first]
+
+
+def yuvio_info_444(info):
+    """the 4:4:4 Y'CbCr clip of an RGB clip's own size and depth: what two RGB clips are both converted to"""
+    import dataclasses
+    return dataclasses.replace(info, hshift=0, vshift=0, mono=False, chroma_tag="444" if info.bit_depth == 8 else f"444p{info.bit_depth}",
+                               color_range=None, packed=None)
+
+
+class _RgbReader:
+    """A packed RGB clip (yuvio.RgbReader) as Y'CbCr planes in the pixel format of its partner -- chroma layout, siting, depth and
+    range --: what score_files reads in place of an RGB file.  Built like _ConvertedReader: a small context of its own, packed
+    frames fetched in runs of eight, ONE FeatureEngine.rgb_convert call a run (unpack, matrix, range, depth, subsampling and
+    siting in one pass with one rounding), the last run kept.  `info` carries the partner's shifts, depth, chroma tag and
+    range; `conversion` is the object score_files reports.  No file-descriptor path.  close() frees the context."""
+    RUN = 8
+
+    def __init__(self, reader, partner, siting, device, make, matrix, rgb_range, side):
+        import dataclasses
+        from . import rgb as RGB
+        src = reader.info
+        if partner.bit_depth not in N.RGB_BIT_DEPTHS:
+            raise ValueError(f"a packed RGB clip is converted to 8 or 10 bit, not to the {partner.bit_depth}-bit {partner.pix_fmt} "
+                             "of the other clip")
+        if partner.mono:
+            raise ValueError("a packed RGB clip cannot be scored against a monochrome clip")
+        self._rd, self.format = reader, src.packed
+        self.info = dataclasses.replace(src, bit_depth=partner.bit_depth, hshift=partner.hshift, vshift=partner.vshift,
+                                        chroma_tag=partner.chroma_tag, color_range=partner.color_range, packed=None)
+        forced = CHROMA_SITINGS[siting] if siting is not None else None
+        s = forced or partner.chroma_siting
+        self.dst_siting = (s[0] if partner.hshift else 0, s[1] if partner.vshift else 0)
+        self.matrix = matrix or RGB.default_matrix(src.height)
+        self.rgb_range = rgb_range or RGB.default_range(self.format)
+        self.yuv_range = "full" if partner.color_range == "full" else "limited"
+        self.coefficients = RGB.conversion_matrix(self.matrix, src.bit_depth, self.rgb_range == "full", partner.bit_depth,
+                                                  self.yuv_range == "full")
+        self._shape = (src.height, src.width)
+        self._dst = (partner.hshift, partner.vshift, *self.dst_siting, partner.bit_depth)
+        self.conversion = {"side": side, "from": src.pix_fmt, "to": self.info.pix_fmt, "matrix": self.matrix, "rgb_range": self.rgb_range,
+                           "yuv_range": self.yuv_range, "bit_depth": [src.bit_depth, partner.bit_depth],
+                           "siting": {"to": list(self.dst_siting)}, "coefficients": [int(v) for v in self.coefficients]}
+        self._eng = make(src.width, src.height, bit_depth=partner.bit_depth, n_planes=1, chroma_shift=(partner.hshift, partner.vshift),
+                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd)
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            packed = [self._rd.packed_frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
+            self._first, self._run = first, self._eng.rgb_convert(packed, self.format, self._shape, self._dst, self.coefficients)
+        return self._run[i - self._first]
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self.frame(i)
 
 
 class _RegisteredReader:

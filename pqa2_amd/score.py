@@ -194,6 +194,13 @@ def main(argv=None) -> int:
                     help="with --chroma-mismatch convert: where both clips' subsampled chroma sits (left: co-sited horizontally, "
                          "centred vertically, MPEG-2; center: centred both ways, JPEG; topleft: co-sited both ways) instead of "
                          "what each file's header implies")
+    ap.add_argument("--rgb-matrix", default=None, choices=["bt601", "bt709", "bt2020"],
+                    help="a packed RGB capture (.bgra, .argb, .rgba, .abgr, .r210) is converted on the GPU to the other clip's "
+                         "Y'CbCr layout, siting, depth and range with this matrix (default: bt601 up to 576 lines, else bt709); "
+                         "the JSON's input object gets a conversion entry")
+    ap.add_argument("--rgb-range", default=None, choices=["full", "limited"],
+                    help="the range of the R'G'B' code values of a packed RGB capture (default: full for the 8-bit formats, "
+                         "limited for r210)")
     ap.add_argument("--chroma-mismatch", default="error", choices=["error", "luma", "convert"],
                     help="clips that differ in chroma subsampling (a 4:2:2 capture such as .uyvy / .v210 against a 4:2:0 "
                          "master): refuse them (default), score their luma only -- VMAF and luma PSNR / SSIM --, or convert the "
@@ -269,6 +276,8 @@ def main(argv=None) -> int:
                           **({"resize": a.resize} if a.resize else {}),
                           **({"chroma_mismatch": a.chroma_mismatch} if a.chroma_mismatch != "error" else {}),
                           **({"chroma_siting": a.chroma_siting} if a.chroma_siting else {}),
+                          **({"rgb_matrix": a.rgb_matrix} if a.rgb_matrix else {}),
+                          **({"rgb_range": a.rgb_range} if a.rgb_range else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects

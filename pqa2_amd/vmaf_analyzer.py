@@ -188,6 +188,9 @@ class VMAFAnalyzer(QObject):
                                               # layout, siting and bit depth, and all three planes are scored
         self.chroma_siting = None             # "left" / "center" / "topleft": with "convert", the siting of both clips' chroma
                                               # instead of what the files imply (pipeline.score_files(chroma_siting=))
+        self.rgb_matrix = None                # "bt601" / "bt709" / "bt2020": the matrix a packed RGB capture (.bgra ... .r210) is
+                                              # converted with (pipeline.score_files(rgb_matrix=)); None: by the picture height
+        self.rgb_range = None                 # "full" / "limited" R'G'B' of such a capture; None: full at 8 bit, limited for r210
         self.last_fps = 0.0
         self._engine_factory = None           # tests inject a stand-in; product code leaves it None
 
@@ -543,7 +546,9 @@ class VMAFAnalyzer(QObject):
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {}),
                 **({"chroma_mismatch": self.chroma_mismatch} if self.chroma_mismatch != "error" else {}),
-                **({"chroma_siting": self.chroma_siting} if self.chroma_siting else {})}
+                **({"chroma_siting": self.chroma_siting} if self.chroma_siting else {}),
+                **({"rgb_matrix": self.rgb_matrix} if self.rgb_matrix else {}),
+                **({"rgb_range": self.rgb_range} if self.rgb_range else {})}
 
     def _run_child_job(self, ref, dis, model, json_path, psnr_path, ssim_path, total_frames):
         """Frame-sharded run: one process per GPU under torch.distributed.run, driven like the
@@ -610,6 +615,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--chroma-mismatch", str(self.chroma_mismatch)]
         if self.chroma_siting:
             cmd += ["--chroma-siting", str(self.chroma_siting)]
+        if self.rgb_matrix:
+            cmd += ["--rgb-matrix", str(self.rgb_matrix)]
+        if self.rgb_range:
+            cmd += ["--rgb-range", str(self.rgb_range)]
         if self.child_backend != "nccl":
             cmd += ["--backend", self.child_backend]
         if self.child_share_device:

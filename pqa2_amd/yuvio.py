@@ -39,7 +39,7 @@ class VideoInfo:
     n_frames: int = 0
     chroma_tag: str = "420jpeg"
     color_range: str | None = None   # "limited" / "full" when the container says so (Y4M XCOLORRANGE=...), else None
-    packed: str | None = None        # "uyvy422" / "yuyv422" / "v210" when the file holds packed frames (PackedReader)
+    packed: str | None = None        # "uyvy422" / "yuyv422" / "v210" when the file holds packed frames (PackedReader); "bgra" ... "r210": packed RGB (RgbReader)
 
     @property
     def dtype(self):
@@ -369,6 +369,61 @@ class PackedReader:
             yield self.frame(i)
 
 
+RGB_EXTENSIONS = {".bgra", ".argb", ".rgba", ".abgr", ".r210"}
+
+
+class RgbReader:
+    """Headerless packed RGB capture files: .bgra, .argb, .rgba, .abgr (8 bit, rows of 4 * width bytes) and .r210 (10 bit,
+    big-endian words; rows padded to 256 bytes per 64 pixels).  Geometry from arguments or a `_WxH` name hint, as PackedReader;
+    the frame count from the file size.  packed_frame(i) gives the packed rows as they lie in the file.  An RGB file has no
+    Y'CbCr planes of its own: frame(i) raises, and pipeline._RgbReader (what score_files wraps this reader in) converts the
+    frames on the GPU to the layout, depth and range of the other clip."""
+
+    def __init__(self, path: str, width: int | None = None, height: int | None = None, bit_depth: int | None = None,
+                 fps: int = 30, fmt: str | None = None):
+        from . import rgb
+        ext = os.path.splitext(path)[1].lower()
+        fmt = fmt or (ext[1:] if ext in RGB_EXTENSIONS else None)
+        if fmt not in rgb.FORMATS:
+            raise ValueError(f"not a packed RGB file (.bgra, .argb, .rgba, .abgr, .r210): {path}")
+        m = re.search(r"(\d{2,5})x(\d{2,5})", os.path.basename(path))
+        if (width is None or height is None) and not m:
+            raise ValueError(f"a packed capture file needs a geometry (WxH in the file name or arguments): {path}")
+        width = width or int(m.group(1))
+        height = height or int(m.group(2))
+        depth = rgb.BIT_DEPTH[fmt]
+        if bit_depth is not None and bit_depth != depth:
+            raise ValueError(f"{fmt} is {depth} bit, not {bit_depth}")
+        self.path, self.format = path, fmt
+        self.info = VideoInfo(width, height, depth, 0, 0, False, fps, 1, chroma_tag="444" if depth == 8 else "444p10", packed=fmt)
+        self.row_stride = rgb.file_stride(fmt, width)
+        self.packed_frame_bytes = self.row_stride * height
+        size = os.path.getsize(path)
+        if size == 0 or size % self.packed_frame_bytes:
+            raise ValueError(f"{path}: {size} bytes is not a whole number of {fmt} frames of {width}x{height} "
+                             f"({self.packed_frame_bytes} bytes each, rows {self.row_stride} bytes apart)")
+        self._mm = np.memmap(path, dtype=np.uint8, mode="r")
+        self.info.n_frames = size // self.packed_frame_bytes
+
+    def __len__(self):
+        return self.info.n_frames
+
+    def packed_frame(self, i: int) -> np.ndarray:
+        """the packed rows of frame i, (height, row_stride) uint8, viewing the mapped file"""
+        if not 0 <= i < self.info.n_frames:
+            raise IndexError(i)
+        off = i * self.packed_frame_bytes
+        return self._mm[off:off + self.packed_frame_bytes].reshape(self.info.height, self.row_stride)
+
+    def frame(self, i: int):
+        raise TypeError(f"{self.path}: a packed RGB file has no Y'CbCr planes of its own; pqa2_amd.pipeline._RgbReader converts it "
+                        "(score_files wraps an RGB clip in one)")
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self.frame(i)
+
+
 def write_y4m(path: str, frames, info: VideoInfo) -> None:
     """frames: iterable of [Y,U,V] plane lists matching `info`."""
     with open(path, "wb") as f:
@@ -381,7 +436,8 @@ def write_y4m(path: str, frames, info: VideoInfo) -> None:
 
 
 def open_video(path: str, **raw_kwargs):
-    """Reader for .y4m / .yuv / packed capture files (.uyvy, .yuyv, .yuy2, .v210); anything else is decoded by a system ffmpeg into a temp Y4M."""
+    """Reader for .y4m / .yuv / packed capture files (.uyvy, .yuyv, .yuy2, .v210; RGB: .bgra, .argb, .rgba, .abgr, .r210); anything
+    else is decoded by a system ffmpeg into a temp Y4M."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".y4m":
         return Y4MReader(path)
@@ -389,6 +445,8 @@ def open_video(path: str, **raw_kwargs):
         return RawYUVReader(path, **raw_kwargs)
     if ext in PACKED_EXTENSIONS:
         return PackedReader(path, **raw_kwargs)
+    if ext in RGB_EXTENSIONS:
+        return RgbReader(path, **raw_kwargs)
     with open(path, "rb") as f:
         if f.read(9) == b"YUV4MPEG2":
             return Y4MReader(path)
