@@ -997,6 +997,44 @@ PQA_API int pqa_colour_apply_device(pqa_ctx* ctx, const int32_t m[12], const pqa
 PQA_API int pqa_colour_apply(pqa_ctx* ctx, const int32_t m[12], const void* const* src_frames, const int64_t src_strides[3],
                              void* const* dst_frames, const int64_t dst_strides[3], int32_t n_frames);
 
+/* Delta E ITP (ITU-R BT.2124): the colour difference of n_frames frame pairs in ICtCp (BT.2100), synchronously -- the one
+ * colour metric here that means something on a PQ or HLG clip (PQA_FEAT_CIEDE decodes every clip as BT.709 / sRGB).  For every
+ * luma pixel, for the reference and the captured frame (chroma read by replication):
+ *     (Y, Cb, Cr, 1) in code values  -- yuv_to_rgb -->  R'G'B'  -- transfer -->  display light F in cd/m2
+ *     F  -- rgb_to_lms -->  LMS / 10000, clamped at 0  -- ST 2084 inverse EOTF -->  L'M'S'  -- BT.2100 -->  (I, Ct, Cp)
+ * and dE = sqrt(dI^2 + dT^2 + dP^2) with dI = 720 (I_ref - I_dis), dT = 360 (Ct_ref - Ct_dis), dP = 720 (Cp_ref - Cp_dis); 1 is
+ * about one just-noticeable difference.  Transfers: PQA_ITP_PQ, the ST 2084 EOTF of R'G'B' clamped to [0, 1]; PQA_ITP_HLG, the
+ * BT.2100 HLG inverse OETF of max(E', 0) and the OOTF F = peak Ys^(gamma - 1) E, gamma = 1.2 + 0.42 log10(peak / 1000), Ys =
+ * 0.2627 R + 0.6780 G + 0.0593 B; PQA_ITP_BT1886, F = peak max(E', 0)^2.4.  The matrices are the caller's (pqa2_amd/itp.py
+ * builds them from the matrix coefficients, range, depth and primaries); a neutral sample -- chroma at the point where the
+ * three rows of yuv_to_rgb agree -- has Ct = Cp = 0 exactly when the rows of each matrix agree on it to within f32 rounding.
+ * out[f][8], 8 = pqa_itp_sums(), doubles: sum of dE, sum of dI^2, sum of dT^2, sum of dP^2, max dE, the number of pixels with dE >
+ * threshold, the number of pixels (width x height), the sum of I of the reference.  f32 per pixel, the hardware log2 / exp2;
+ * errors: DESIGN.md section 5.  A frame's row does not depend on the number of frames of the call, on pitches or on alignment.
+ * Samples are u8 in an 8-bit context, otherwise u16.  Any context with n_planes == 3, every chroma layout it accepts, no feature
+ * bit; buffers are made on first use, grow only and are freed with the context.  Independent of the scoring chain: a call
+ * between two pqa_submit calls changes no record.  PQA_EINVAL, before any device call, on a null pointer, n_planes != 3, an
+ * unknown transfer, a coefficient that is not finite, peak <= 0 (or not finite) for HLG / BT.1886, a threshold that is
+ * negative or not finite, a negative frame count, a row pitch shorter than a row (or, in device memory, a pitch that is no
+ * multiple of the sample size).  n_frames == 0 succeeds and writes nothing.
+ *
+ * pqa_delta_itp: frames in HOST memory, laid out as for pqa_colour_moments; they travel in chunks of 8 pairs through the pinned
+ * buffers of pqa_resample.  pqa_delta_itp_device: both clips in device memory (pitches in BYTES), under the ordering contract
+ * of pqa_submit_device. */
+enum { PQA_ITP_PQ = 0, PQA_ITP_HLG = 1, PQA_ITP_BT1886 = 2 };
+typedef struct pqa_itp_spec {
+  uint32_t transfer;    /* PQA_ITP_PQ 0, PQA_ITP_HLG 1, PQA_ITP_BT1886 2 */
+  float yuv_to_rgb[12]; /* rows of [Y Cb Cr 1] in code values -> R'G'B', nominal range 0..1 */
+  float rgb_to_lms[9];  /* linear display light in cd/m2 -> LMS / 10000 */
+  float peak;           /* Lw, cd/m2: HLG and BT.1886; ignored for PQ */
+  float threshold;      /* dE above which a pixel is counted */
+} pqa_itp_spec;
+PQA_API int pqa_itp_sums(void);
+PQA_API int pqa_delta_itp_device(pqa_ctx* ctx, const pqa_itp_spec* spec, const pqa_device_clip* ref, const pqa_device_clip* dis,
+                                 int32_t n_frames, double* out);
+PQA_API int pqa_delta_itp(pqa_ctx* ctx, const pqa_itp_spec* spec, const void* const* ref_frames, const int64_t ref_strides[3],
+                          const void* const* dis_frames, const int64_t dis_strides[3], int32_t n_frames, double* out);
+
 /* What "gray" means to the two luma-statistics calls above.  PQA_GRAY_LUMA (default): the luma samples as they are.
  * PQA_GRAY_BT601_FULL: gray = clamp(round((Y - 16 s) * 255 / (219 s)), 0, 255), s = 2^(bit_depth - 8) -- what the
  * reference's cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) sees for a limited-range clip (cv2.VideoCapture has expanded it to
@@ -1047,6 +1085,11 @@ PQA_API int pqa_debug_adm_need(uint32_t width, uint32_t height, int32_t* out20);
  * lab_pairs[n][6] = {L1, a1, b1, L2, a2, b2}: the inputs are converted to f32, de_out[n] receives the f32 results widened.
  * PQA_EDEVICE without a device (text in pqa_last_error(NULL)), PQA_EINVAL on a null pointer or n < 0. */
 PQA_API int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out);
+
+/* Test hook (needs a device): the ICtCp device function of the pqa_delta_itp kernel on n code triples yuv_triples[n][3] =
+ * {Y, Cb, Cr} (f32): itp_out[n][3] receives (720 I, 360 Ct, 720 Cp) as f32.  The spec's threshold is not read.  PQA_EDEVICE
+ * without a device (text in pqa_last_error(NULL)), PQA_EINVAL on a null pointer, n < 0 or a spec pqa_delta_itp refuses. */
+PQA_API int pqa_debug_itp(const pqa_itp_spec* spec, const float* yuv_triples, int32_t n, float* itp_out);
 
 /* Test hook (no device needed): the host-built tables the PQA_FEAT_CAMBI kernels use at w x h and bit_depth (8 or 10):
  * out[PQA_CAMBI_PARAM_INTS] = {adjusted window size, r, pixels_in_window, mask threshold, tvi_for_diff[1..4],

@@ -65,10 +65,10 @@ GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 EXPORTS = [
     "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
     "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_submit_packed", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
-    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_set_luma_gray",
+    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_itp_sums", "pqa_delta_itp", "pqa_delta_itp_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape", "pqa_debug_adm_need",
-    "pqa_debug_ciede2000", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
+    "pqa_debug_ciede2000", "pqa_debug_itp", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
     "pqa_debug_psnr_hvs_tables", "pqa_debug_psnr_hvs_plane", "pqa_debug_xpsnr_blocks", "pqa_debug_siti_plane",
     "pqa_debug_resample_table", "pqa_debug_colour",
 ]
@@ -192,6 +192,15 @@ class PqaEdgeSpec(C.Structure):
 
 EDGE_STRIPE, EDGE_BAND = 1024, 64                  # columns / rows a workgroup of edge_profiles.hip reads (kernels.h)
 EDGE_SUMS, EDGE_CHUNK = 3, 8                       # sums a line (the third is int64) / frame pairs a launch
+
+
+ITP_PQ, ITP_HLG, ITP_BT1886 = 0, 1, 2                # pqa_itp_spec.transfer
+ITP_SUMS, ITP_CHUNK = 8, 8                         # pqa_itp_sums(): doubles a frame / frame pairs a launch
+
+
+class PqaItpSpec(C.Structure):
+    _fields_ = [("transfer", C.c_uint32), ("yuv_to_rgb", C.c_float * 12), ("rgb_to_lms", C.c_float * 9), ("peak", C.c_float),
+                ("threshold", C.c_float)]
 
 
 class PqaError(RuntimeError):
@@ -320,6 +329,11 @@ def load():
     lib.pqa_colour_moments.argtypes = [vp, C.POINTER(vp), C.POINTER(i64 * 3), C.POINTER(vp), C.POINTER(i64 * 3), i32, C.c_uint32, C.c_uint32, vp]
     lib.pqa_colour_apply_device.argtypes = [vp, C.POINTER(i32 * 12), C.POINTER(PqaDeviceClip), C.POINTER(PqaDeviceClip), i32]
     lib.pqa_colour_apply.argtypes = [vp, C.POINTER(i32 * 12), C.POINTER(vp), C.POINTER(i64 * 3), C.POINTER(vp), C.POINTER(i64 * 3), i32]
+    lib.pqa_itp_sums.argtypes = []
+    lib.pqa_itp_sums.restype = C.c_int
+    lib.pqa_delta_itp_device.argtypes = [vp, C.POINTER(PqaItpSpec), C.POINTER(PqaDeviceClip), C.POINTER(PqaDeviceClip), i32, vp]
+    lib.pqa_delta_itp.argtypes = [vp, C.POINTER(PqaItpSpec), C.POINTER(vp), C.POINTER(i64 * 3), C.POINTER(vp), C.POINTER(i64 * 3), i32, vp]
+    lib.pqa_debug_itp.argtypes = [C.POINTER(PqaItpSpec), vp, i32, vp]
     lib.pqa_debug_colour.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp * 3), C.POINTER(vp * 3),
                                      C.c_uint32, C.c_uint32, vp, C.POINTER(i32 * 12), C.POINTER(vp * 3)]
     lib.pqa_debug_resample_table.argtypes = [C.c_uint32, i32, i32, i64, i64, vp, vp, i32, C.POINTER(i32)]
@@ -350,5 +364,6 @@ def load():
     assert lib.pqa_ext4_doubles() == EXT4_DOUBLES
     assert lib.pqa_ext5_doubles() == EXT5_DOUBLES
     assert lib.pqa_colour_sums() == COLOUR_SUMS
+    assert lib.pqa_itp_sums() == ITP_SUMS
     _lib = lib
     return lib

@@ -8,6 +8,8 @@
 
 #include <vector>
 
+struct pqa_itp_spec;   // include/pqa_vmaf.h
+
 namespace pqa {
 
 enum Elem : int { ELEM_U8 = 0, ELEM_U16 = 1, ELEM_F32 = 2 };
@@ -270,6 +272,33 @@ struct CiedeFinalizeArgs {
 hipError_t launch_ciede_finalize(hipStream_t stream, const CiedeFinalizeArgs& args);
 // The kernel's CIEDE2000 device function on n Lab pairs [n][6] (f32, device pointers) -> de_out[n] (pqa_debug_ciede2000).
 hipError_t launch_ciede_debug(hipStream_t stream, const float* lab_pairs, int n, float* de_out);
+
+// ---- Delta E ITP, ITU-R BT.2124 (delta_itp.hip) ---------------------------------------------------------------------------
+constexpr int kItpSums = 8;      // per frame: sum dE, sum dI^2, sum dT^2, sum dP^2, max dE, pixels above the threshold, pixels, sum I of the reference
+constexpr int kItpChunk = 8;     // frame pairs per launch of the entries
+// A pqa_itp_spec as the kernels take it: both matrices rewritten about the neutral axis (the head of delta_itp.hip).
+//   R' = gy Y + cu (Cb - u0) + cv (Cr - v0) + o    L = ls G + lr (R - G) + lb (B - G)    (one entry per row)
+struct ItpCoef {
+  int transfer;
+  float u0, v0;
+  float gy[3], cu[3], cv[3], o[3];
+  float ls[3], lr[3], lb[3];
+  float peak, gamma_m1, threshold;   // gamma_m1: the HLG system gamma - 1 at `peak`
+};
+void itp_prepare(const pqa_itp_spec& spec, ItpCoef* coef);
+// what is wrong with a spec (the argument rules of pqa_delta_itp; no device call), or null
+const char* itp_spec_error(const pqa_itp_spec& spec);
+// tiles of a cw x ch chroma plane (the 64 x 4 tile of ciede_kernel; kItpSums doubles each)
+int itp_tiles(int cw, int ch);
+// The partial sums of every tile of n_frames frame pairs (planes Y, Cb, Cr of u8 / u16 samples; chroma ceil(w / 2^hshift) x
+// ceil(h / 2^vshift), upsampled by replication) into partials[n_frames][itp_tiles][kItpSums]; then, per frame, their fixed-order
+// sums into out[n_frames][kItpSums].
+hipError_t launch_delta_itp(hipStream_t stream, Elem elem, const ItpCoef& coef, const PlaneRun ref[3], const PlaneRun dis[3],
+                            int n_frames, int w, int h, int hshift, int vshift, double* partials);
+hipError_t launch_delta_itp_finalize(hipStream_t stream, const double* partials, int n_tiles, int n_frames, double* out);
+// The kernel's device function on n code triples [n][3] = (Y, Cb, Cr) (f32, device pointers) -> itp_out[n][3] = (720 I, 360 Ct,
+// 720 Cp) (pqa_debug_itp).
+hipError_t launch_delta_itp_debug(hipStream_t stream, const ItpCoef& coef, const float* yuv, int n, float* itp_out);
 
 // ---- CAMBI: libvmaf cambi banding index (cambi.hip) --------------------------------------------------------------------
 constexpr int kCambiScales = 5, kCambiDiffs = 4;

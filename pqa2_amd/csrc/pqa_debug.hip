@@ -101,6 +101,25 @@ int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out) {
   return PQA_OK;
 }
 
+int pqa_debug_itp(const pqa_itp_spec* spec, const float* yuv_triples, int32_t n, float* itp_out) {
+  if (!spec || n < 0 || (n > 0 && (!yuv_triples || !itp_out))) return fail(nullptr, PQA_EINVAL, "bad argument");
+  if (const char* what = itp_spec_error(*spec)) return fail(nullptr, PQA_EINVAL, "pqa_debug_itp: %s", what);
+  const int rc = need_device();
+  if (rc != PQA_OK) return rc;
+  if (n == 0) return PQA_OK;
+  ItpCoef k;
+  itp_prepare(*spec, &k);
+  Scratch s;
+  float* d_in = s.get<float>((size_t)n * 3);
+  float* d_out = s.get<float>((size_t)n * 3);
+  hipError_t e = s.err;
+  if (e == hipSuccess) e = hipMemcpy(d_in, yuv_triples, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_delta_itp_debug(nullptr, k, d_in, n, d_out);
+  if (e == hipSuccess) e = hipMemcpy(itp_out, d_out, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(nullptr, PQA_EDEVICE, "pqa_debug_itp: %s", hipGetErrorString(e));
+  return PQA_OK;
+}
+
 int pqa_debug_cambi_params(uint32_t w, uint32_t h, uint32_t bit_depth, int32_t* out, int32_t cap) {
   if (!out || cap < PQA_CAMBI_PARAM_INTS) return fail(nullptr, PQA_EINVAL, "pqa_debug_cambi_params: null or short output");
   if (w < 16 || h < 16 || w > 16384 || h > 16384 || (bit_depth != 8 && bit_depth != 10))

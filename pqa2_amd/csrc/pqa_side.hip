@@ -1,5 +1,5 @@
 // The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the colour moments and matrix apply, and the spec-driven analyses of
+// temporal / spatial / level alignment, the resampler, the colour moments and matrix apply, Delta E ITP, and the spec-driven analyses of
 // planes of the call's own size (registration moments, tile / band / temporal moments, edge and line profiles).  Each has an
 // entry for a clip in HBM and one for frames in host memory.  Host frames of the context's size take the luma-halves staging
 // (stage_frames); the spec-driven analyses share one checker and one driver per kind of clip (spec_check, pair_run), whose
@@ -1604,6 +1604,116 @@ int pqa_colour_apply(pqa_ctx* c, const int32_t m[12], const void* const* src_fra
                  c->side_pin[1] + (size_t)f * L.bytes + L.off[p] + (size_t)y * L.pitch[p], (size_t)c->pw[p] * c->esize);
   }
   return PQA_OK;
+}
+
+// ---- Delta E ITP (delta_itp.hip) -----------------------------------------------------------------------------------------
+
+int pqa_itp_sums(void) { return kItpSums; }
+
+}  // extern "C"
+
+namespace {
+
+// the argument rules both entries share, in the order in which they fire (no device call)
+int itp_check(pqa_ctx* c, const pqa_itp_spec* sp, int32_t n_frames) {
+  if (!sp) return fail(c, PQA_EINVAL, "delta_itp: null spec");
+  if (c->n_planes != 3) return fail(c, PQA_EINVAL, "delta_itp needs the chroma planes: n_planes must be 3 (got %d)", c->n_planes);
+  if (c->elem != ELEM_U8 && c->elem != ELEM_U16) return fail(c, PQA_EINVAL, "delta_itp: u8 or u16 samples only");
+  if (const char* what = itp_spec_error(*sp)) return fail(c, PQA_EINVAL, "delta_itp: %s", what);
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "delta_itp: negative frame count");
+  return PQA_OK;
+}
+
+// kernel and epilogue of n staged or resident frame pairs; their rows go `at` frames into the output buffer
+hipError_t itp_launch(pqa_ctx* c, const ItpCoef& k, const PlaneRun r[3], const PlaneRun d[3], int n, int at) {
+  const int tiles = itp_tiles(c->pw[1], c->ph[1]);
+  auto* part = (double*)c->side_buf[SIDE_ITP_PART];
+  hipError_t e = launch_delta_itp(c->stream, c->elem, k, r, d, n, c->pw[0], c->ph[0], (int)c->cfg.chroma_hshift,
+                                  (int)c->cfg.chroma_vshift, part);
+  if (e == hipSuccess) e = launch_delta_itp_finalize(c->stream, part, tiles, n, (double*)c->side_buf[SIDE_ITP_OUT] + (size_t)at * kItpSums);
+  return e;
+}
+
+int itp_reserve(pqa_ctx* c, int32_t n_frames) {
+  const int chunk = n_frames < kItpChunk ? n_frames : kItpChunk;
+  const int rc = side_reserve(c, SIDE_ITP_PART, (size_t)chunk * itp_tiles(c->pw[1], c->ph[1]) * kItpSums * sizeof(double));
+  return rc == PQA_OK ? side_reserve(c, SIDE_ITP_OUT, (size_t)n_frames * kItpSums * sizeof(double)) : rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pqa_delta_itp_device(pqa_ctx* c, const pqa_itp_spec* spec, const pqa_device_clip* ref, const pqa_device_clip* dis,
+                         int32_t n_frames, double* out) {
+  if (!c) return PQA_EINVAL;
+  int rc = itp_check(c, spec, n_frames);
+  if (rc != PQA_OK) return rc;
+  if (n_frames > 0 && (!ref || !dis)) return fail(c, PQA_EINVAL, "delta_itp: null clip pointer");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "delta_itp: null output pointer");
+  if (n_frames == 0) return PQA_OK;
+  rc = cl_check_clip(c, "delta_itp: reference ", ref);
+  if (rc == PQA_OK) rc = cl_check_clip(c, "delta_itp: captured ", dis);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = itp_reserve(c, n_frames);
+  if (rc != PQA_OK) return rc;
+  ItpCoef k;
+  itp_prepare(*spec, &k);
+  const int es = c->esize;
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kItpChunk) {
+    PlaneRun r[3], d[3];
+    for (int p = 0; p < 3; ++p) {
+      r[p] = PlaneRun{(const uint8_t*)ref->plane[p] + (int64_t)f0 * ref->frame_pitch[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
+      d[p] = PlaneRun{(const uint8_t*)dis->plane[p] + (int64_t)f0 * dis->frame_pitch[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
+    }
+    e = itp_launch(c, k, r, d, chunk_len(n_frames, f0, kItpChunk), f0);
+  }
+  return side_finish(c, "delta_itp", e, out, c->side_buf[SIDE_ITP_OUT], (size_t)n_frames * kItpSums * sizeof(double));
+}
+
+int pqa_delta_itp(pqa_ctx* c, const pqa_itp_spec* spec, const void* const* ref_frames, const int64_t ref_strides[3],
+                  const void* const* dis_frames, const int64_t dis_strides[3], int32_t n_frames, double* out) {
+  if (!c) return PQA_EINVAL;
+  int rc = itp_check(c, spec, n_frames);
+  if (rc != PQA_OK) return rc;
+  if (n_frames > 0 && (!ref_frames || !dis_frames || !ref_strides || !dis_strides)) return fail(c, PQA_EINVAL, "delta_itp: null frame list");
+  if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "delta_itp: null output pointer");
+  if (n_frames == 0) return PQA_OK;
+  rc = cl_check_host(c, "delta_itp: ", "reference ", ref_frames, ref_strides, n_frames);
+  if (rc == PQA_OK) rc = cl_check_host(c, "delta_itp: ", "captured ", dis_frames, dis_strides, n_frames);
+  if (rc != PQA_OK) return rc;
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as pqa_colour_moments: chunks of kItpChunk pairs through the side analyses' two pinned chunks into device buffers of this
+  // entry; every chunk's epilogue writes its rows behind the previous chunk's, they come back once
+  const ClLayout L = cl_layout(c);
+  const int chunk = n_frames < kItpChunk ? n_frames : kItpChunk;
+  rc = side_pin_reserve(c, 0, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_ITP_REF, L.bytes * chunk);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_ITP_DIS, L.bytes * chunk);
+  if (rc == PQA_OK) rc = itp_reserve(c, n_frames);
+  if (rc != PQA_OK) return rc;
+  ItpCoef k;
+  itp_prepare(*spec, &k);
+  PlaneRun r[3], d[3];
+  cl_runs(c, L, c->side_buf[SIDE_ITP_REF], r);
+  cl_runs(c, L, c->side_buf[SIDE_ITP_DIS], d);
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kItpChunk) {
+    const int n = chunk_len(n_frames, f0, kItpChunk);
+    if (f0 > 0) e = hipStreamSynchronize(c->stream);   // the pinned buffers are packed again only after the chunk before has left them
+    if (e != hipSuccess) break;
+    cl_pack(c, L, c->side_pin[0], ref_frames + (size_t)f0 * 3, ref_strides, n);
+    cl_pack(c, L, c->side_pin[1], dis_frames + (size_t)f0 * 3, dis_strides, n);
+    e = hipMemcpyAsync(c->side_buf[SIDE_ITP_REF], c->side_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_ITP_DIS], c->side_pin[1], L.bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = itp_launch(c, k, r, d, n, f0);
+  }
+  return side_finish(c, "delta_itp", e, out, c->side_buf[SIDE_ITP_OUT], (size_t)n_frames * kItpSums * sizeof(double));
 }
 
 }  // extern "C"

@@ -972,6 +972,36 @@ class FeatureEngine:
         s, d = self._device_clip(src_ptrs, row_pitch, frame_pitch), self._device_clip(dst_ptrs, row_pitch, frame_pitch)
         self._check(self.lib.pqa_colour_apply_device(self._ctx, C.byref(mm), C.byref(s), C.byref(d), int(n_frames)))
 
+    # -- Delta E ITP ---------------------------------------------------------------------------
+    def delta_itp(self, ref_frames, dis_frames, spec) -> np.ndarray:
+        """[n, 8] float64: per frame pair the sums of the BT.2124 colour difference in ICtCp -- sum dE, sum dI^2, sum dT^2, sum
+        dP^2, max dE, pixels above the threshold, pixels, the reference's sum of I (pqa_delta_itp; definition:
+        include/pqa_vmaf.h).  `spec`: itp.spec(...) (transfer, the two matrices, peak, threshold).  Frames [Y, Cb, Cr] in HOST
+        memory (two lists of equal length); needs n_planes == 3.  itp.summary reads the result."""
+        from . import itp as ITP
+        n = len(ref_frames)
+        if len(dis_frames) != n:
+            raise ValueError("delta_itp needs as many captured as reference frames")
+        if self.n_planes != 3:
+            raise N.PqaError(N.PQA_EINVAL, "delta_itp needs the chroma planes: n_planes must be 3")
+        sp = spec if isinstance(spec, N.PqaItpSpec) else ITP.native_spec(spec)
+        out = np.zeros((n, N.ITP_SUMS), np.float64)
+        keep_r, rp, rs = self._frame_list(ref_frames, "reference")
+        keep_d, dp, ds = self._frame_list(dis_frames, "captured")
+        self._check(self.lib.pqa_delta_itp(self._ctx, C.byref(sp), rp, C.byref(rs), dp, C.byref(ds), n, out.ctypes.data))
+        del keep_r, keep_d
+        return out
+
+    def delta_itp_resident(self, ref_ptrs, dis_ptrs, row_pitch, frame_pitch, n_frames: int, spec) -> np.ndarray:
+        """The same for two clips in HBM (ref_ptrs / dis_ptrs: device addresses of frame 0's planes; pitches in bytes per
+        plane, common to both clips; pqa_delta_itp_device)."""
+        from . import itp as ITP
+        sp = spec if isinstance(spec, N.PqaItpSpec) else ITP.native_spec(spec)
+        out = np.zeros((max(int(n_frames), 0), N.ITP_SUMS), np.float64)
+        r, d = self._device_clip(ref_ptrs, row_pitch, frame_pitch), self._device_clip(dis_ptrs, row_pitch, frame_pitch)
+        self._check(self.lib.pqa_delta_itp_device(self._ctx, C.byref(sp), C.byref(r), C.byref(d), int(n_frames), out.ctypes.data))
+        return out
+
     # -- results -----------------------------------------------------------------------------
     def collect(self, first_index: int, count: int) -> np.ndarray:
         out = np.zeros((count, N.RECORD_DOUBLES), np.float64)

@@ -44,7 +44,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 temporal_blend_min: float = 1 / 16, temporal_still_mse: float = 0.25,
                 temporal_pop_factor: float = 4, coding_grid: bool = False, grid_planes: str = "y", grid_periods=(4, 64),
                 grid_z2: float = 25.0, chroma_mismatch: str = "error", chroma_siting: str | None = None,
-                rgb_matrix: str | None = None, rgb_range: str | None = None) -> ScoreResult | None:
+                rgb_matrix: str | None = None, rgb_range: str | None = None, delta_itp: str | None = None,
+                itp_matrix: str | None = None, itp_range: str | None = None, itp_peak: float | None = None,
+                itp_threshold: float = 1.0) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -60,6 +62,16 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     `siti`: FFmpeg's siti filter (ITU-T P.910 SI / TI) of the distorted and of the reference luma on every frame as the
     extra columns siti_si / siti_ti / siti_si_source / siti_ti_source (fourth extension record); a clip whose Y4M header
     says XCOLORRANGE=FULL is taken as full range, any other as limited range.
+    `delta_itp` = "pq" | "hlg" | "bt1886": the ITU-R BT.2124 colour difference Delta E ITP of every pixel, for clips with that
+    transfer (itp.py; csrc/delta_itp.hip) -- the colour metric that means something on an HDR clip, where `ciede` (BT.709 / sRGB
+    into CIELAB) does not.  It runs after every alignment and conversion step, on the clips as scored, in a pass of its own
+    over the readers on a small three-plane context, 8 pairs a call, sharded over the ranks like the records (the result does
+    not depend on their number).  Adds the per-frame columns delta_e_itp (mean), delta_e_itp_max and itp_above_jnd (share of
+    pixels above `itp_threshold`, default 1 = about one just-noticeable difference) and the result's `delta_itp` object: the
+    spec used, coefficients included, and itp.summary.  `itp_matrix`: "bt601" | "bt709" | "bt2020" (default bt2020 for pq /
+    hlg, rgb.default_matrix(height) for bt1886); `itp_range`: "full" | "limited" (default: the reference header's, else
+    limited); `itp_peak`: Lw in cd/m2 for hlg (default 1000) and bt1886 (default 100).  A monochrome clip is an error.  None:
+    nothing is measured and nothing is read twice.
     `integrity`: FFmpeg's freezedetect, blackdetect and scdet on the DISTORTED clip (fifth extension record; every plane of
     a colour clip): the extra columns scd_mafd / scd_score / black_ratio / freeze_mafd and, under the result's `integrity`
     key, the event lists freezes / blacks / scene_changes (integrity.py); `integrity_options`: FFmpeg's option names
@@ -409,6 +421,17 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             raise ValueError("grid_periods must be a pair (lo, hi) with 4 <= lo <= hi <= 64")
         if grid_z2 is None or grid_z2 < 0:
             raise ValueError("grid_z2 must not be negative")
+    itp_spec = None
+    if delta_itp is not None:
+        from . import itp as ITP
+        if delta_itp not in ITP.TRANSFERS:
+            raise ValueError('delta_itp must be None, "pq", "hlg" or "bt1886"')
+        if ri.mono:
+            raise ValueError("delta_itp needs the chroma planes, but the clips are monochrome")
+        if itp_range not in (None, "full", "limited"):
+            raise ValueError('itp_range must be None, "full" or "limited"')
+        itp_full = (ri.color_range == "full") if itp_range is None else itp_range == "full"
+        itp_spec = ITP.spec(delta_itp, itp_matrix, itp_full, ri.bit_depth, itp_peak, itp_threshold, height=ri.height)
     if cambi_full_ref and not cambi:
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
@@ -518,6 +541,10 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                                                     band_planes=3 if spectrum_planes == "all" else 1, temporal_tile=int(temporal),
                                                     temporal_planes=3 if temporal_planes == "all" else 1,
                                                     edge_planes=(3 if grid_planes == "all" else 1) if coding_grid else 0)
+    itp_rows = None
+    if itp_spec is not None:      # a pass of its own over the same readers: every pixel of every plane, on the clips as scored
+        itp_rows = _itp_pass(ref_rd, dis_rd, a, b, n, itp_spec, device, engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)),
+                             world_size, rank, gather_device, cancelled)
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     blk = {i: shard.gather_records(local_blk[i], n, world_size, rank, gather_device, width=N.EXT_BLOCKS[i][1]) for i in want}
     if rank != 0:
@@ -570,6 +597,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         _temporal_result(res, tmom, ri, int(temporal), temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)
     if edges is not None:
         _grid_result(res, edges, ri, range(g_lo, g_hi + 1), grid_z2)
+    if itp_rows is not None:
+        _itp_result(res, itp_rows, itp_spec)
     if alignment is not None:
         res["alignment"] = alignment
     if resized is not None:
@@ -1158,6 +1187,39 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
         E = np.ascontiguousarray(E).view(np.uint64).reshape(n, h + w, N.EDGE_SUMS)
         edges.append((E[:, :h], E[:, h:]))
     return (out if tile else None), (bands if levels else None), (tmom if temporal_tile else None), (edges if edge_planes else None)
+
+
+def _itp_pass(ref_rd, dis_rd, a: int, b: int, n: int, spec: dict, device, make, world_size: int, rank: int, gather_device,
+              cancelled=None) -> np.ndarray:
+    """the measurement of score_files(delta_itp=): the rows [n, 8] of FeatureEngine.delta_itp for every frame pair of the clip,
+    on every rank.  This rank measures its frames [a, b) in chunks of 8 pairs on a small three-plane context of its own; a
+    frame's row depends on that frame pair alone, so the gathered rows (shard.gather_records) do not depend on the number of
+    ranks."""
+    from . import itp as ITP
+    ri = ref_rd.info
+    rows = np.zeros((b - a, N.ITP_SUMS), np.float64)
+    if b > a:
+        sp = ITP.native_spec(spec)
+        eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=3, chroma_shift=(ri.hshift, ri.vshift),
+                   features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        try:
+            for i0 in range(a, b, N.ITP_CHUNK):
+                if cancelled is not None and cancelled():
+                    raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
+                idx = range(i0, min(b, i0 + N.ITP_CHUNK))
+                rows[i0 - a:i0 - a + len(idx)] = eng.delta_itp([ref_rd.frame(i)[:3] for i in idx], [dis_rd.frame(i)[:3] for i in idx], sp)
+        finally:
+            eng.close()
+    return shard.gather_records(rows, n, world_size, rank, gather_device, width=N.ITP_SUMS)
+
+
+def _itp_result(res, rows, spec: dict) -> None:
+    """rank 0: adds res["delta_itp"] (the spec used, coefficients included, and itp.summary) and the three per-frame columns"""
+    from . import itp as ITP
+    keep = np.asarray(res["frame_indices"])
+    for key, col in ITP.frame_columns(rows).items():
+        res["metrics"][key] = col[keep]
+    res["delta_itp"] = {"spec": dict(spec), "summary": ITP.summary(rows, spec["threshold"])}
 
 
 def _grid_result(res, edges, info, periods, z2_min) -> None:

@@ -248,6 +248,26 @@ def grid_log_keys(coding_grid: dict | None) -> dict:
     return {"coding_grid": distortion_log_keys(coding_grid)["distortion"]}
 
 
+def itp_log_keys(delta_itp: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the BT.2124 colour difference (pipeline.score_files(delta_itp=)): the spec
+    used, its coefficients included, and itp.summary; none without it.  Any float that is not finite becomes null."""
+    if not delta_itp:
+        return {}
+    return {"delta_itp": distortion_log_keys(delta_itp)["distortion"]}
+
+
+def itp_summary_line(delta_itp: dict) -> str:
+    """One line for a summary or a status bar: the pooled Delta E ITP and what it is made of."""
+    sp, s = delta_itp.get("spec", {}), delta_itp.get("summary", {})
+    line = (f"Delta E ITP ({sp.get('transfer', '?')}, {sp.get('matrix', '?')}, {sp.get('range', '?')} range): {s.get('kind', '?')}, "
+            f"mean {s.get('mean', 0.0):.3f}, max {s.get('max', 0.0):.2f}, {100.0 * s.get('above_jnd', 0.0):.1f} % of the pixels "
+            f"above {s.get('threshold', 1.0):g}")
+    if s.get("kind") not in ("identical", None):
+        line += (f", {100.0 * s.get('luminance_share', 0.0):.0f} % luminance / {100.0 * s.get('chroma_share', 0.0):.0f} % chroma, "
+                 f"worst frame {s.get('worst_frame', 0)} (mean {s.get('worst_frame_mean', 0.0):.3f})")
+    return line
+
+
 def grid_summary_line(coding_grid: dict) -> str:
     """One line for a summary or a status bar: the block grid found in the luma."""
     s = coding_grid.get("planes", {}).get("y", {}).get("summary", {})

@@ -201,6 +201,20 @@ def main(argv=None) -> int:
     ap.add_argument("--rgb-range", default=None, choices=["full", "limited"],
                     help="the range of the R'G'B' code values of a packed RGB capture (default: full for the 8-bit formats, "
                          "limited for r210)")
+    ap.add_argument("--delta-itp", default=None, metavar="TRANSFER", choices=["pq", "hlg", "bt1886"],
+                    help="the ITU-R BT.2124 colour difference Delta E ITP of every pixel in ICtCp, for clips with this transfer "
+                         "(pq: ST 2084; hlg: through the 1000 cd/m2 reference display; bt1886: SDR at 100 cd/m2), in a pass of its "
+                         "own over both clips as scored; three per-frame metrics (delta_e_itp, delta_e_itp_max, itp_above_jnd) "
+                         "and a top-level delta_itp object.  1 is about one just-noticeable difference")
+    ap.add_argument("--itp-matrix", default=None, choices=["bt601", "bt709", "bt2020"],
+                    help="with --delta-itp: the Y'CbCr matrix (and primaries) of the clips (default: bt2020 for pq and hlg; "
+                         "bt601 up to 576 lines, else bt709 for bt1886)")
+    ap.add_argument("--itp-range", default=None, choices=["full", "limited"],
+                    help="with --delta-itp: the range of the code values (default: what the reference's header says, else limited)")
+    ap.add_argument("--itp-peak", type=float, default=None, metavar="CD_M2",
+                    help="with --delta-itp: the display's peak luminance Lw for hlg (default 1000) and bt1886 (default 100)")
+    ap.add_argument("--itp-threshold", type=float, default=1.0, metavar="DE",
+                    help="with --delta-itp: a pixel is counted as visibly different above this Delta E ITP (default 1)")
     ap.add_argument("--chroma-mismatch", default="error", choices=["error", "luma", "convert"],
                     help="clips that differ in chroma subsampling (a 4:2:2 capture such as .uyvy / .v210 against a 4:2:0 "
                          "master): refuse them (default), score their luma only -- VMAF and luma PSNR / SSIM --, or convert the "
@@ -278,6 +292,8 @@ def main(argv=None) -> int:
                           **({"chroma_siting": a.chroma_siting} if a.chroma_siting else {}),
                           **({"rgb_matrix": a.rgb_matrix} if a.rgb_matrix else {}),
                           **({"rgb_range": a.rgb_range} if a.rgb_range else {}),
+                          **({"delta_itp": a.delta_itp, "itp_matrix": a.itp_matrix, "itp_range": a.itp_range, "itp_peak": a.itp_peak,
+                              "itp_threshold": a.itp_threshold} if a.delta_itp else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
@@ -298,7 +314,8 @@ def main(argv=None) -> int:
                                      **report.distortion_log_keys(res.get("distortion")),
                                      **report.spectrum_log_keys(res.get("spectrum")),
                                      **report.temporal_log_keys(res.get("temporal")),
-                                     **report.grid_log_keys(res.get("coding_grid"))})
+                                     **report.grid_log_keys(res.get("coding_grid")),
+                                     **report.itp_log_keys(res.get("delta_itp"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -332,6 +349,8 @@ def main(argv=None) -> int:
             print(report.temporal_summary_line(res["temporal"]), file=sys.stderr, flush=True)
         if res.get("coding_grid"):
             print(report.grid_summary_line(res["coding_grid"]), file=sys.stderr, flush=True)
+        if res.get("delta_itp"):
+            print(report.itp_summary_line(res["delta_itp"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

@@ -178,6 +178,10 @@ class VMAFAnalyzer(QObject):
         self.temporal_tile = 32               # pass; score_files(temporal=)); its tile size: 8, 16, 32 or 64
         self.coding_grid_enabled = False      # coding-grid detection: whether the difference is a block grid (the same second
                                               # pass; score_files(coding_grid=))
+        self.delta_itp = None                 # "pq" / "hlg" / "bt1886": the BT.2124 colour difference Delta E ITP of clips with this
+                                              # transfer, a pass of its own over both clips (pipeline.score_files(delta_itp=))
+        self.itp_matrix = None                # its Y'CbCr matrix and primaries: "bt601" / "bt709" / "bt2020"; None: by the transfer
+        self.itp_peak = None                  # its display peak Lw in cd/m2 (hlg, bt1886); None: 1000 / 100
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -500,7 +504,8 @@ class VMAFAnalyzer(QObject):
                                      **report.distortion_log_keys(res.get("distortion")),
                                      **report.spectrum_log_keys(res.get("spectrum")),
                                      **report.temporal_log_keys(res.get("temporal")),
-                                     **report.grid_log_keys(res.get("coding_grid"))})
+                                     **report.grid_log_keys(res.get("coding_grid")),
+                                     **report.itp_log_keys(res.get("delta_itp"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -543,6 +548,7 @@ class VMAFAnalyzer(QObject):
                 **({"spectrum": int(self.spectrum_levels)} if self.spectrum_enabled else {}),
                 **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
                 **({"coding_grid": True} if self.coding_grid_enabled else {}),
+                **({"delta_itp": self.delta_itp, "itp_matrix": self.itp_matrix, "itp_peak": self.itp_peak} if self.delta_itp else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {}),
                 **({"chroma_mismatch": self.chroma_mismatch} if self.chroma_mismatch != "error" else {}),
@@ -607,6 +613,12 @@ class VMAFAnalyzer(QObject):
             cmd += ["--temporal", str(int(self.temporal_tile))]
         if self.coding_grid_enabled:
             cmd += ["--coding-grid"]
+        if self.delta_itp:
+            cmd += ["--delta-itp", str(self.delta_itp)]
+            if self.itp_matrix:
+                cmd += ["--itp-matrix", str(self.itp_matrix)]
+            if self.itp_peak is not None:
+                cmd += ["--itp-peak", str(float(self.itp_peak))]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -775,6 +787,11 @@ class VMAFAnalyzer(QObject):
                 results["coding_grid"] = vmaf_data.get("coding_grid")
                 if results["coding_grid"]:
                     self.status_update.emit(report.grid_summary_line(results["coding_grid"]))
+            if self.delta_itp:   # whether the colour error is visible, from the log's top level
+                from . import report
+                results["delta_itp"] = vmaf_data.get("delta_itp")
+                if results["delta_itp"]:
+                    self.status_update.emit(report.itp_summary_line(results["delta_itp"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
