@@ -303,7 +303,19 @@ PQA_API int pqa_submit_fd_run(pqa_ctx* ctx, int64_t first_index, int32_t n_frame
  * pqa_luma_stats_device.
  * prev_ref_luma (nullable, device pointer, prev_row_pitch bytes) is the reference luma of frame
  * first_index-1 -- the one-frame halo a frame-sharded rank needs for motion.  When NULL the context
- * continues from the last frame it saw if that was first_index-1, else motion(first_index) = 0. */
+ * continues from the last frame it saw if that was first_index-1, else motion(first_index) = 0.
+ * The rules of a plane that is scored where it lies (PQA_EINVAL before anything is launched; the context stays usable), with
+ * es the sample size, plane p being pw x ph samples and its span = row_pitch x ph bytes:
+ *   - pointers are not NULL; row and frame pitches are multiples of es (a frame pitch may be anything else: 0, negative,
+ *     smaller than a frame when frames interleave inside the rows);
+ *   - row_pitch >= pw * es: no negative, zero or overlapping rows;
+ *   - span < 2^32: the VIF, ADM and motion kernels address a plane with unsigned 32-bit byte offsets from its base.  A plane
+ *     cut out of a wider buffer with a larger span must be copied first.  From 2^31 bytes on those features run on their
+ *     tiled kernels (the march kernels take planes below 2 GiB), with the same results to rounding;
+ *   - with PQA_FEAT_SITI in the mask, the luma span < 2^31: the siti kernel has no such partner;
+ *   - prev_ref_luma, where a feature in the mask reads it (motion, xpsnr, siti), follows the rules of luma plane 0 with
+ *     prev_row_pitch.
+ * pqa_submit_surfaces applies the same rules to an NV12 luma plane, which is scored in place. */
 PQA_API int pqa_submit_device(pqa_ctx* ctx, int64_t first_index, int32_t n_frames, const pqa_device_clip* ref,
                       const pqa_device_clip* dis, const void* prev_ref_luma, int64_t prev_row_pitch);
 
@@ -1080,6 +1092,17 @@ PQA_API int pqa_debug_vif_strip_shape(pqa_ctx* ctx, uint32_t scale, uint32_t n_f
  * then {row lo, row hi, column lo, column hi} of the input samples they read.  PQA_EINVAL on a null pointer or a size of
  * 0 or above 65536. */
 PQA_API int pqa_debug_adm_need(uint32_t width, uint32_t height, int32_t* out20);
+
+/* Test hook (host only): per frame of width x height at bit_depth, what the context's workspace sizing functions return for
+ * the four march kernels ("sized") and the number of partial slots a launch of each writes ("written": the launcher's own
+ * count, from a launch of no frames; 0 where the launcher does not take such planes).  out (cap >= PQA_PARTIAL_COUNT_INTS) =
+ *   [0] sized, [1] written: the scale-0 VIF march kernel (vif_march_partials_max; pairs of doubles),
+ *   [2 + 2 s] sized, [3 + 2 s] written: the ADM march kernel at scale s = 0 .. 3 (adm_march_partials; sextets),
+ *   [10] sized (0 where the context does not size for it), [11] written: the ADM pyramid kernel (adm_pyramid_partials),
+ *   [12] sized, [13] written: the motion march kernel (motion_march_partials; doubles).
+ * PQA_EINVAL on a null or short output, a size outside 16 .. 16384 or a bit depth other than 8, 10, 12. */
+enum { PQA_PARTIAL_COUNT_INTS = 14 };
+PQA_API int pqa_debug_partial_counts(uint32_t width, uint32_t height, uint32_t bit_depth, int32_t* out, int32_t cap);
 
 /* Test hook (needs a device): the CIEDE2000 device function of the PQA_FEAT_CIEDE kernel on n Lab pairs
  * lab_pairs[n][6] = {L1, a1, b1, L2, a2, b2}: the inputs are converted to f32, de_out[n] receives the f32 results widened.

@@ -33,6 +33,7 @@ EXT_FLOAT_SSIM, EXT_FLOAT_SSIM_LCS, EXT_MS_SSIM, EXT_MS_SSIM_L, EXT_MS_SSIM_C, E
 EXT_CIEDE2000, EXT_CIEDE_MEAN_DE = 20, 21   # ciede2000 = 45 - 20 log10(mean dE00), and the mean itself
 EXT_CAMBI, EXT_CAMBI_SOURCE = 22, 23         # cambi of the distorted luma, and of the reference luma (FULL_REF; NaN without)
 CAMBI_PARAM_INTS = 22                        # pqa_debug_cambi_params
+PARTIAL_COUNT_INTS = 14                      # pqa_debug_partial_counts
 EXT_DOUBLES = 24
 # second extension record (pqa_collect_ext2): psnr_hvs_y / _cb / _cr, psnr_hvs, the three plane MSEs; NaN where not run
 EXT2_PSNR_HVS_Y, EXT2_PSNR_HVS_CB, EXT2_PSNR_HVS_CR, EXT2_PSNR_HVS, EXT2_PSNR_HVS_MSE, EXT2_RESERVED = 0, 1, 2, 3, 4, 7
@@ -68,6 +69,7 @@ EXPORTS = [
     "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_itp_sums", "pqa_delta_itp", "pqa_delta_itp_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape", "pqa_debug_adm_need",
+    "pqa_debug_partial_counts",
     "pqa_debug_ciede2000", "pqa_debug_itp", "pqa_debug_cambi_params", "pqa_debug_cambi_cmap", "pqa_debug_psnr_hvs_dct8x8",
     "pqa_debug_psnr_hvs_tables", "pqa_debug_psnr_hvs_plane", "pqa_debug_xpsnr_blocks", "pqa_debug_siti_plane",
     "pqa_debug_resample_table", "pqa_debug_colour",
@@ -347,6 +349,7 @@ def load():
     lib.pqa_debug_vif_march_shape.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(i32 * 6)]
     lib.pqa_debug_vif_strip_shape.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i32 * 4)]
     lib.pqa_debug_adm_need.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(i32 * 20)]
+    lib.pqa_debug_partial_counts.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i32 * PARTIAL_COUNT_INTS), i32]
     lib.pqa_debug_ciede2000.argtypes = [vp, i32, vp]
     lib.pqa_debug_cambi_params.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, i32]
     lib.pqa_debug_cambi_cmap.argtypes = [vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int64, vp]

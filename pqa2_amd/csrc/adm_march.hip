@@ -409,6 +409,7 @@ bool launch_adm_march(hipStream_t stream, int scale, Elem elem, PlaneRun ref, Pl
   a.partials = partials;
   a.n_part = a.n_sg * 4 * p.seg_first[3];
   if (n_partials) *n_partials = a.n_part;
+  if (n_frames <= 0) { *err = hipSuccess; return true; }   // nothing to launch: the caller asked for the count alone
   a.n_frames = n_frames;
   const dim3 grid((unsigned)a.n_sg * p.seg_first[3] * n_frames), block(kBlock);
   switch (elem) {

@@ -427,6 +427,7 @@ bool launch_adm_pyramid(hipStream_t stream, Elem elem, PlaneRun ref, PlaneRun di
   a.part0 = partials0; a.part1 = partials1;
   a.n_part = a.n_sg * 4 * a.n_seg;
   if (n_partials) *n_partials = a.n_part;
+  if (n_frames <= 0) { *err = hipSuccess; return true; }   // nothing to launch: the caller asked for the count alone
   a.n_frames = n_frames;
   const dim3 grid((unsigned)a.n_sg * a.n_seg * n_frames), block(kBlock);
   if (elem == ELEM_U16) hipLaunchKernelGGL((adm_pyramid_kernel<uint16_t>), grid, block, 0, stream, a);

@@ -61,9 +61,11 @@ void vif_strip_shape(int scale, int w, int h, int n_frames, int strip_seg, int* 
 // Scale 0 (8-, 10-, 12-bit clips: `bits`), both filter passes on the f16 matrix cores (vif_march.hip).  vif_march_prepare uploads its tap
 // table once per device (pqa_create does; synchronous, idempotent; a device that does not keep f16 denormals -- probed once,
 // the operand encoding leans on them -- gets no table and scale 0 stays on the VALU kernel); launch_vif_s0_march returns false when it cannot take
-// the planes (no table, pitches the stores cannot take) and launch_vif_stat then falls back to the tiled kernels.
-// vif_march_partials_max: upper bound of *n_partials for a w x h frame (workspace sizing).
+// the planes (no table, pitches the stores cannot take, planes of 2 GiB and more) and launch_vif_stat then falls back to the tiled kernels.
+// vif_march_partials: *n_partials of a w x h frame (one pair per wave: four stripes a workgroup x segments);
+// vif_march_partials_max: its upper bound (workspace sizing).
 hipError_t vif_march_prepare();
+int vif_march_partials(int w, int h);
 int vif_march_partials_max(int w, int h);
 // host: the per-lane tap-matrix fragments the march kernel reads ([fragment][lane 0..63][8 f16 bit patterns]) -- no device
 // needed; returns the number of fragments, 0 when a tap does not split exactly, -(halfwords needed) when `out` is too small
@@ -106,6 +108,7 @@ hipError_t launch_adm_scale(hipStream_t stream, int scale, Elem elem, PlaneRun r
                             bool cone = true);
 // The march kernel (adm_march.hip).  adm_march_partials: sextets per frame it writes for a band_w x band_h band (workspace
 // sizing; a function of the geometry only).  launch_adm_march returns false when it cannot take the planes.
+// n_frames = 0 (here, in launch_adm_pyramid and in launch_motion_march): *n_partials is filled and nothing is launched.
 int adm_march_partials(int band_w, int band_h);
 bool launch_adm_march(hipStream_t stream, int scale, Elem elem, PlaneRun ref, PlaneRun dis, int n_frames, int w, int h,
                       float inv_scale, float gain_limit, MutPlaneRun ll_ref, MutPlaneRun ll_dis, double* partials,

@@ -205,6 +205,7 @@ bool launch_motion_march(hipStream_t stream, Elem elem, PlaneRun ref, const void
   a.partials = partials;
   a.n_part = a.n_sg * 4 * a.n_seg;
   if (n_partials) *n_partials = a.n_part;
+  if (n_frames <= 0) { *err = hipSuccess; return true; }   // nothing to launch: the caller asked for the count alone
   const dim3 grid(a.n_sg * a.n_seg, n_frames), block(kBlock);
   if (elem == ELEM_U16) hipLaunchKernelGGL((motion_march_kernel<uint16_t>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((motion_march_kernel<uint8_t>), grid, block, 0, stream, a);

@@ -317,7 +317,11 @@ int run_adm(pqa_ctx* c, Batch& b) {
                                  c->cfg.adm_enhn_gain_limit, c->adm_div_lut, k.out.ref, k.out.dis, c->adm_fx_part[k.s]));
       return PQA_OK;
     });
-  if (c->adm_mode == ADM_AUTO) {   // scales 0 and 1 in one launch when the geometry allows (adm_pyramid.hip)
+  // A caller's plane of 2 GiB and more: launch_adm_march would refuse scale 0 alone; the whole chain goes tiled, so that the
+  // records are those of PQA_ADM_MARCH=0 (a context's mode is one for all scales: kernels.h).
+  const int64_t span = (b.rs[0].row_pitch > b.ds[0].row_pitch ? b.rs[0].row_pitch : b.ds[0].row_pitch) * b.h * b.es;
+  const int adm_mode = span >= (1ll << 31) ? (int)ADM_TILED : c->adm_mode;
+  if (adm_mode == ADM_AUTO) {   // scales 0 and 1 in one launch when the geometry allows (adm_pyramid.hip)
     const Level& L2 = c->adm_lv[2];
     hipError_t perr = hipSuccess;
     int np = 0;
@@ -333,7 +337,7 @@ int run_adm(pqa_ctx* c, Batch& b) {
   return walk_pyramid(c->adm_lv, top, ELEM_F32, [&](const Scale& k) -> int {
     ProfScope ps(c, 7 + k.s, b.sp_n, b.st_adm);
     HIPCHK(c, launch_adm_scale(b.st_adm, k.s, k.elem, k.in.ref, k.in.dis, b.sp_n, k.w, k.h, c->inv_scale,
-                               (float)c->cfg.adm_enhn_gain_limit, k.out.ref, k.out.dis, c->adm_part[k.s], c->adm_mode, &b.adm_np[k.s],
+                               (float)c->cfg.adm_enhn_gain_limit, k.out.ref, k.out.dis, c->adm_part[k.s], adm_mode, &b.adm_np[k.s],
                                c->adm_cone));
     return PQA_OK;
   });
@@ -786,20 +790,45 @@ int keep_histories(pqa_ctx* c, const Batch& b) {
   return PQA_OK;
 }
 
+// The rows of a plane the kernels read where it lies (`who`: "reference plane 1", "halo"; plane p of the context, row pitch in
+// bytes): no row pitch below a row, and a span (row pitch x rows) the kernels can address.  The VIF, ADM and motion kernels
+// form unsigned 32-bit byte offsets from the plane's base (pqa_device.h), so a span ends at 2^32 - 1; from 2^31 on their
+// launchers go tiled by themselves.  The siti kernel stops at 2^31 and has no partner.  Every other feature's kernels add
+// 64-bit row offsets to a pointer.  No device call.
+int check_plane_rows(pqa_ctx* c, const char* who, int p, int64_t row_pitch) {
+  const int64_t row = (int64_t)c->pw[p] * c->esize, rows = c->ph[p];
+  if (row_pitch < row)
+    return fail(c, PQA_EINVAL, "%s: row pitch %lld is below a row of %lld bytes", who, (long long)row_pitch, (long long)row);
+  if (row_pitch > ((1ll << 32) - 1) / rows)
+    return fail(c, PQA_EINVAL, "%s spans %lld rows of pitch %lld: the limit of a plane is 2^32 - 1 bytes (32-bit offsets)", who,
+                (long long)rows, (long long)row_pitch);
+  if (p == 0 && (c->cfg.features & PQA_FEAT_SITI) && row_pitch > ((1ll << 31) - 1) / rows)
+    return fail(c, PQA_EINVAL, "siti: %s spans %lld rows of pitch %lld: the limit of its kernel is 2^31 - 1 bytes", who,
+                (long long)rows, (long long)row_pitch);
+  return PQA_OK;
+}
+
 int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, const pqa_device_clip* dis,
                   const void* prev, int64_t prev_pitch_bytes) {
   const uint32_t feat = c->cfg.features;
   const int es = c->esize;
+  int rc = PQA_OK;
   for (int p = 0; p < c->n_planes; ++p) {
     if (ref->row_pitch[p] % es || dis->row_pitch[p] % es || ref->frame_pitch[p] % es || dis->frame_pitch[p] % es)
       return fail(c, PQA_EINVAL, "plane %d pitch is not a multiple of the sample size", p);
     if (!ref->plane[p] || !dis->plane[p]) return fail(c, PQA_EINVAL, "plane %d pointer is null", p);
+    char who[32];
+    snprintf(who, sizeof who, "reference plane %d", p);
+    if ((rc = check_plane_rows(c, who, p, ref->row_pitch[p])) != PQA_OK) return rc;
+    snprintf(who, sizeof who, "distorted plane %d", p);
+    if ((rc = check_plane_rows(c, who, p, dis->row_pitch[p])) != PQA_OK) return rc;
   }
-  int rc = check_slots_free(c, first, n);
-  if (rc != PQA_OK) return rc;
+  if (prev && (feat & (PQA_FEAT_MOTION | PQA_FEAT_XPSNR | PQA_FEAT_SITI))) {
+    if (prev_pitch_bytes % es) return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
+    if ((rc = check_plane_rows(c, "halo plane", 0, prev_pitch_bytes)) != PQA_OK) return rc;
+  }
+  if ((rc = check_slots_free(c, first, n)) != PQA_OK) return rc;
   c->started = true;
-  if (prev && prev_pitch_bytes % es && (feat & (PQA_FEAT_MOTION | PQA_FEAT_XPSNR | PQA_FEAT_SITI)))
-    return fail(c, PQA_EINVAL, "halo pitch is not a multiple of the sample size");
 
   Batch b{};
   b.first = first; b.n = n; b.es = es; b.w = c->pw[0]; b.h = c->ph[0]; b.capacity = c->capacity;
@@ -1459,6 +1488,13 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     if (i < 2) any_decoder = true;
     if (!s->luma || s->luma_row_pitch < (int64_t)c->pw[0] * c->esize || s->luma_row_pitch % c->esize)
       return fail(c, PQA_EINVAL, "surface luma pointer / pitch");
+    // an NV12 luma plane is scored where it lies: the rules of pqa_submit_device, before anything is unpacked (the halo's
+    // where a feature in the mask reads it, as in process_batch)
+    if (bpc <= 8 && (i < 2 || (c->cfg.features & (PQA_FEAT_MOTION | PQA_FEAT_XPSNR | PQA_FEAT_SITI)))) {
+      static const char* const kWho[3] = {"reference surface luma", "distorted surface luma", "halo surface luma"};
+      const int rc = check_plane_rows(c, kWho[i], 0, s->luma_row_pitch);
+      if (rc != PQA_OK) return rc;
+    }
     if (i < 2 && c->n_planes == 3 &&
         (!s->chroma || s->chroma_row_pitch < (int64_t)c->pw[1] * 2 * c->esize || s->chroma_row_pitch % c->esize))
       return fail(c, PQA_EINVAL, "surface chroma pointer / pitch");

@@ -82,6 +82,40 @@ int pqa_debug_adm_need(uint32_t width, uint32_t height, int32_t* out20) {
   return PQA_OK;
 }
 
+int pqa_debug_partial_counts(uint32_t width, uint32_t height, uint32_t bit_depth, int32_t* out, int32_t cap) {
+  static_assert(PQA_PARTIAL_COUNT_INTS == 14, "pqa_debug_partial_counts layout");
+  if (!out || cap < PQA_PARTIAL_COUNT_INTS || width < 16 || height < 16 || width > 16384 || height > 16384 ||
+      (bit_depth != 8 && bit_depth != 10 && bit_depth != 12))
+    return fail(nullptr, PQA_EINVAL, "pqa_debug_partial_counts: bad argument");
+  const int w = (int)width, h = (int)height;
+  const Elem elem = bit_depth > 8 ? ELEM_U16 : ELEM_U8;
+  // "written" is what the launcher itself reports for a launch of no frames (it fills *n_partials and launches nothing);
+  // 0 where it does not take the planes
+  hipError_t err = hipSuccess;
+  int np = 0;
+  out[0] = vif_march_partials_max(w, h);
+  out[1] = vif_march_partials(w, h);   // launch_vif_s0_march's own n_part (it needs a device for its tap table)
+  int aw = w, ah = h;                  // the levels of alloc_adm (ceil halving)
+  for (int s = 0; s < 4; ++s) {
+    if (s > 0) { aw = (aw + 1) / 2; ah = (ah + 1) / 2; }
+    out[2 + 2 * s] = adm_march_partials((aw + 1) / 2, (ah + 1) / 2);
+    const PlaneRun in{nullptr, aw, 0};
+    np = 0;
+    out[3 + 2 * s] = launch_adm_march(nullptr, s, s ? ELEM_F32 : elem, in, in, 0, aw, ah, 1.0f, 100.0f, MutPlaneRun{nullptr, 0, 0},
+                                      MutPlaneRun{nullptr, 0, 0}, nullptr, &np, true, &err) ? np : 0;
+  }
+  static float band[4];                // launch_adm_pyramid wants an approximation band; a launch of no frames writes none
+  const PlaneRun luma{nullptr, w, 0};
+  const MutPlaneRun ll{band, (int64_t)((w / 4 + 15) / 16 * 16), 0};
+  out[10] = adm_pyramid_takes(elem, w, h) ? adm_pyramid_partials(w, h) : 0;
+  np = 0;
+  out[11] = launch_adm_pyramid(nullptr, elem, luma, luma, 0, w, h, 1.0f, 100.0f, ll, ll, nullptr, nullptr, &np, true, &err) ? np : 0;
+  out[12] = motion_march_partials(w, h);
+  np = 0;
+  out[13] = launch_motion_march(nullptr, elem, luma, nullptr, 0, 0, w, h, nullptr, &np, &err) ? np : 0;
+  return PQA_OK;
+}
+
 int pqa_debug_ciede2000(const double* lab_pairs, int32_t n, double* de_out) {
   if (n < 0 || (n > 0 && (!lab_pairs || !de_out))) return fail(nullptr, PQA_EINVAL, "bad argument");
   const int rc = need_device();

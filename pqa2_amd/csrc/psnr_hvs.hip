@@ -259,8 +259,8 @@ __global__ __launch_bounds__(kBlock) void phv_kernel(const PhvArgs a) {
     const T* dr = dcol + (int64_t)by * 7 * rpd;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      s[i] = (int)rr[i * rpr];
-      d[i] = (int)dr[i * rpd];
+      s[i] = (int)rr[(int64_t)i * rpr];   // 64-bit: seven rows of a pitch near 2^31 samples leave `int`
+      d[i] = (int)dr[(int64_t)i * rpd];
     }
     const float gs = phv_g(s), gd = phv_g(d);
     // od_bin_fdct8x8: column j -> row j of the intermediate, transpose, column j of that -> coefficient row j

@@ -651,6 +651,12 @@ int vif_march_partials_max(int w, int h) {
   return n_cbg * 4 * ((row_blocks + kMinSegBlocks - 1) / kMinSegBlocks);
 }
 
+int vif_march_partials(int w, int h) {
+  int shape[6];
+  vif_march_shape(w, h, shape);
+  return (shape[0] + 3) / 4 * 4 * shape[3];
+}
+
 hipError_t vif_march_prepare() {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -702,7 +708,8 @@ bool launch_vif_s0_march(hipStream_t stream, Elem elem, int bits, PlaneRun ref, 
   if (!a.tab) return false;
   if (!((elem == ELEM_U8 && bits == 8) || (elem == ELEM_U16 && (bits == 10 || bits == 12)))) return false;
   const int es = elem == ELEM_U16 ? 2 : 1;
-  if (ref.row_pitch * es >= (1ll << 31) || dis.row_pitch * es >= (1ll << 31)) return false;
+  // 32-bit buffer offsets, as in the ADM and motion march kernels: a plane must stay below 2 GiB (the tiled kernel takes over)
+  if ((int64_t)ref.row_pitch * h * es >= (1ll << 31) || (int64_t)dis.row_pitch * h * es >= (1ll << 31)) return false;
   a.ref = ref.base; a.dis = dis.base;
   a.pitch_r = (unsigned)(ref.row_pitch * es); a.pitch_d = (unsigned)(dis.row_pitch * es);
   a.frame_pitch_r = ref.frame_pitch * es; a.frame_pitch_d = dis.frame_pitch * es;
@@ -741,7 +748,7 @@ bool launch_vif_s0_march(hipStream_t stream, Elem elem, int bits, PlaneRun ref, 
     vif_march_shape(w, h, shape);
     a.n_cb = shape[0]; a.n_cbg = (a.n_cb + 3) / 4; a.row_blocks = shape[1]; a.seg_blocks = shape[2]; a.n_seg = shape[3];
   }
-  a.n_part = a.n_cbg * 4 * a.n_seg;
+  a.n_part = vif_march_partials(w, h);   // n_cbg * 4 * n_seg
   if (n_partials) *n_partials = a.n_part;
   const dim3 grid(a.n_cbg * a.n_seg, n_frames), block(kBlock);
   if (bits == 12) hipLaunchKernelGGL((vif_s0_march_kernel<uint16_t, true>), grid, block, 0, stream, a);

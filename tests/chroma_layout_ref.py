@@ -140,7 +140,7 @@ def no_break_pad(w, hs):
 
 
 # ---- FFmpeg PSNR / SSIM ---------------------------------------------------------------------------------------------
-PSNR_SSIM_CASES = [(19, 19, 8), (45, 39, 8), (150, 86, 8), (45, 39, 10), (45, 41, 8)]
+PSNR_SSIM_CASES = [(19, 19, 8), (45, 39, 8), (150, 86, 8), (45, 39, 10), (45, 41, 8), (45, 39, 12), (150, 86, 12)]
 
 
 def offset_pair(w, h, bpc, hs, vs, seed, n=1):

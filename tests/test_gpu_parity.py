@@ -142,7 +142,7 @@ def test_identical_and_static_closed_forms():
     np.testing.assert_allclose(rec[:, 17:20], 1.0, atol=1e-12)
 
 
-@pytest.mark.parametrize("bpc,w,h", [(8, 322, 242), (8, 64, 48), (10, 200, 120), (8, 1920, 1080)])
+@pytest.mark.parametrize("bpc,w,h", [(8, 322, 242), (8, 64, 48), (10, 200, 120), (8, 1920, 1080), (12, 64, 48), (12, 322, 242)])
 def test_psnr_sse_bit_exact_and_ssim(oracle32, bpc, w, h):
     from pqa2_amd import _native as N
     from pqa2_amd.engine import sse_from_records
@@ -158,6 +158,106 @@ def test_psnr_sse_bit_exact_and_ssim(oracle32, bpc, w, h):
             assert int(sse[i, p]) == oracle32.sse_plane(diss[i][p], refs[i][p], bpc), (i, p)
             exp = oracle32.ssim_plane(diss[i][p], refs[i][p], bpc)
             assert abs(rec[i, 17 + p] - exp) < 1e-9, (i, p, rec[i, 17 + p], exp)
+
+
+def _extreme_pairs(w, h, bpc):
+    """(name, ref, dis) luma planes at the ends of the sample range; every pair but the last differs by `top` everywhere."""
+    top = (1 << bpc) - 1
+    dt = np.uint8 if bpc <= 8 else np.uint16
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = []
+    for period in (1, 4):
+        board = ((((xx // period) + (yy // period)) % 2) * top).astype(dt)
+        out.append((f"checkerboard of period {period}", board, (top - board).astype(dt)))
+    out.append(("flat top against flat 0", np.full((h, w), top, dt), np.zeros((h, w), dt)))
+    out.append(("top against top", np.full((h, w), top, dt), np.full((h, w), top, dt)))
+    return out
+
+
+@pytest.mark.parametrize("bpc", [8, 10, 12])
+@pytest.mark.parametrize("w,h", [(66, 50), (322, 242)])
+def test_psnr_ssim_sample_extremes(oracle32, bpc, w, h):
+    """0 / top checkerboards against their inverses, flat top against flat 0, top against top: the largest ss, s12 and
+    vars * 64 the SSIM kernel forms and the largest squared differences of both SSE paths (the SSIM kernel's block sums with
+    PSNR | SSIM, sse_kernel alone and on the remainder strips: neither size is a multiple of 4).  Chroma planes (4:2:0) hold
+    the same patterns."""
+    from pqa2_amd import _native as N
+    from pqa2_amd.engine import sse_from_records
+    top = (1 << bpc) - 1
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    pairs = list(zip(_extreme_pairs(w, h, bpc), _extreme_pairs(cw, ch, bpc)))
+    n = len(pairs)
+    refs = [[y[1], c[1], c[1]] for y, c in pairs]
+    diss = [[y[2], c[2], c[2]] for y, c in pairs]
+    recs = {}
+    for feats in (N.FEAT_PSNR | N.FEAT_SSIM, N.FEAT_PSNR):
+        with _engine(w, h, bit_depth=bpc, n_planes=3, features=feats, max_batch=3) as eng:
+            for i in range(n):
+                eng.submit(i, refs[i], diss[i])
+            recs[feats] = eng.collect(0, n)
+    rec = recs[N.FEAT_PSNR | N.FEAT_SSIM]
+    for i, ((name, _, _), _) in enumerate(pairs):
+        for p, (pw, ph) in enumerate(((w, h), (cw, ch), (cw, ch))):
+            want = 0 if name == "top against top" else pw * ph * top * top
+            assert oracle32.sse_plane(diss[i][p], refs[i][p], bpc) == want, (name, p)
+            for feats, r in recs.items():
+                assert int(sse_from_records(r)[i, p]) == want, (name, p, feats)
+            exp = oracle32.ssim_plane(diss[i][p], refs[i][p], bpc)
+            assert abs(rec[i, 17 + p] - exp) < 1e-9, (name, p, rec[i, 17 + p], exp)
+            if name == "top against top":
+                assert exp == 1.0
+            else:
+                assert exp < 0.05, (name, p, exp)     # nothing in common: the ends of the range in every window
+
+
+@pytest.mark.parametrize("bpc", [8, 10])
+def test_psnr_ssim_unaligned_resident_planes(oracle32, bpc):
+    """Three device-resident planes whose bases sit 0 ... 3 samples into their allocations and whose row pitches are odd
+    numbers of samples: every combination of the `aligned` (16 bytes) and `aligned4` tests that choose the kernels' load
+    paths fails or holds.  Bit-equal to the host path (whose staging is 64-byte aligned), and equal to the oracle."""
+    import torch
+    from pqa2_amd import _native as N
+    from pqa2_amd.engine import sse_from_records
+    w, h, n = 150, 86, 2
+    es = 1 if bpc <= 8 else 2
+    feats = N.FEAT_PSNR | N.FEAT_SSIM
+    refs, diss = synth.make_clip(w, h, n, bpc, chroma=True)
+    with _engine(w, h, bit_depth=bpc, n_planes=3, features=feats) as eng:
+        for i in range(n):
+            eng.submit(i, refs[i], diss[i])
+        host = eng.collect(0, n)
+    sse = sse_from_records(host)
+    for i in range(n):
+        for p in range(3):
+            assert int(sse[i, p]) == oracle32.sse_plane(diss[i][p], refs[i][p], bpc), (i, p)
+            assert abs(host[i, 17 + p] - oracle32.ssim_plane(diss[i][p], refs[i][p], bpc)) < 1e-9, (i, p)
+
+    def resident(clip, p, off, pitch):
+        """(tensor, device pointer of frame 0) of plane p of every frame: rows `pitch` samples apart, `off` samples in"""
+        ph, pw = clip[0][p].shape
+        buf = np.zeros(off + n * ph * pitch + 8, clip[0][p].dtype)
+        buf[off:off + n * ph * pitch].reshape(n, ph, pitch)[:, :, :pw] = np.stack([f[p] for f in clip])
+        t = torch.from_numpy(buf.view(np.int16) if es == 2 else buf).cuda()
+        return t, t.data_ptr() + off * es
+
+    for off in range(4):
+        keep, rp, dp, row_pitch, frame_pitch = [], [], [], [], []
+        for p in range(3):
+            ph, pw = refs[0][p].shape
+            pitch = pw + 3 + (pw % 2)            # odd, and not the width
+            assert pitch % 2 == 1
+            for clip, ptrs in ((refs, rp), (diss, dp)):
+                t, ptr = resident(clip, p, off + p, pitch)      # a different base alignment per plane
+                keep.append(t)
+                ptrs.append(ptr)
+            row_pitch.append(pitch * es)
+            frame_pitch.append(ph * pitch * es)
+        torch.cuda.synchronize()
+        with _engine(w, h, bit_depth=bpc, n_planes=3, features=feats) as eng:
+            eng.submit_resident(0, n, rp, dp, row_pitch, frame_pitch)
+            dev = eng.collect(0, n)
+        assert np.array_equal(host, dev), (bpc, off)
+        del keep
 
 
 def test_constant_offset_sse_closed_form():
