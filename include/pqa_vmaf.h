@@ -770,6 +770,49 @@ PQA_API int pqa_table_apply_device(pqa_ctx* ctx, const pqa_table_spec* spec, con
                                    int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
                                    int32_t n_frames);
 
+/* Overlay masking: n_frames planes of one clip through a feathered mask, synchronously, in exact integers -- the correction that
+ * takes a burnt-in overlay (a channel logo, a clock, a timecode, an OSD) out of the scores once pqa2_amd/distortion.py
+ * (persistent_regions, overlay_mask) has found it: both clips are blended towards one flat value there, or the captured clip
+ * towards the reference's own samples.  Planes of width x height samples (the spec's, independent of the context's width and
+ * height; each 1 ... 8192), u8 in an 8-bit context, otherwise little-endian u16.
+ * nodes: a HOST pointer to a grid A[gy][gx] of uint16, each 0 ... 256, whose nodes lie Gx = 1 << step_log2_x and
+ * Gy = 1 << step_log2_y samples apart (steps 0 ... 6, the call's own, so that luma at step 3 and 4:2:0 chroma at step 2 share
+ * one grid): gx = ((width + Gx - 1) >> step_log2_x) + 1 columns, gy rows likewise.  For sample (x, y), i = x >> step_log2_x,
+ * fx = x & (Gx - 1), j = y >> step_log2_y, fy = y & (Gy - 1):
+ *     a   = (A[j][i] (Gx - fx)(Gy - fy) + A[j][i+1] fx (Gy - fy) + A[j+1][i] (Gx - fx) fy + A[j+1][i+1] fx fy
+ *            + ((Gx Gy) >> 1)) >> (step_log2_x + step_log2_y)
+ *     dst = (src (256 - a) + fill a + 128) >> 8
+ * fill: the spec's constant (at most 2^bit_depth - 1), or with a fill plane the sample of that plane at (x, y); the fill plane
+ * has the geometry of src and a base and pitches of its own.  a = 0 returns src exactly, a = 256 returns fill exactly.  u16:
+ * where a > 0 a source sample above 2^bit_depth - 1 is read as 2^bit_depth - 1, and so is every fill sample; where a = 0 the
+ * source sample is copied as it is.
+ * The destination may be exactly the source (same base and pitches): then only the bounding rectangle of the samples with
+ * a > 0 is read and written.  Otherwise the whole plane is written.  The destination may not be the fill plane.
+ * Any context, no feature bit, no record, no profile id; independent of the scoring chain: a call between two pqa_submit
+ * calls changes no record.  PQA_EINVAL, before any device call, on a null pointer, a bad struct_size, a size outside
+ * 1 ... 8192, a step above 6, a node above 256, a fill above 2^bit_depth - 1, a negative frame count, a row pitch below a
+ * row, in device memory a base or pitch that is no multiple of the sample size, or a destination equal to the fill plane.
+ * n_frames == 0 succeeds and writes nothing.  No source byte past a row's last sample is read and no destination byte past it
+ * is written.  Kernel: DESIGN.md section 5.
+ *
+ * pqa_mask_blend: frames in HOST memory (src_frames[f] / fill_frames[f] / dst_frames[f] point at planes, rows *_row_stride
+ * bytes apart; fill_frames null: the constant).  They travel in chunks of 8 through the pinned buffers of pqa_resample and
+ * device buffers of this entry's own, grow-only and freed with the context.
+ * pqa_mask_blend_device: the clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart; fill null:
+ * the constant), under the ordering contract of pqa_submit_device; the blended planes can go straight into pqa_submit_device. */
+typedef struct pqa_mask_spec {
+  uint32_t struct_size;              /* sizeof(pqa_mask_spec) */
+  uint32_t width, height;            /* of this plane, 1 ... 8192 */
+  uint32_t step_log2_x, step_log2_y; /* 0 ... 6 */
+  uint32_t fill;                     /* the constant fill, at most 2^bit_depth - 1 (checked with a fill plane too, then unused) */
+} pqa_mask_spec;
+PQA_API int pqa_mask_blend(pqa_ctx* ctx, const pqa_mask_spec* spec, const uint16_t* nodes, const void* const* src_frames,
+                           int64_t src_row_stride, const void* const* fill_frames, int64_t fill_row_stride, void* const* dst_frames,
+                           int64_t dst_row_stride, int32_t n_frames);
+PQA_API int pqa_mask_blend_device(pqa_ctx* ctx, const pqa_mask_spec* spec, const uint16_t* nodes, const void* src, int64_t src_row_pitch,
+                                  int64_t src_frame_pitch, const void* fill, int64_t fill_row_pitch, int64_t fill_frame_pitch, void* dst,
+                                  int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames);
+
 /* Sub-pixel registration: the tile-wise gradient moments of n_frames frame pairs of one plane, synchronously -- the
  * Lucas-Kanade normal equations of every tile, from which pqa2_amd/align.py (solve_geometry, register) estimates a sub-pixel
  * shift and a scale factor per axis and drives the source window of pqa_resample.  Planes of width x height samples (the

@@ -651,4 +651,31 @@ hipError_t launch_table_apply(hipStream_t stream, Elem elem, int bit_depth, cons
                               int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int n_frames, int w,
                               int h);
 
+// ---- overlay masking: planes through a feathered mask (mask_blend.hip) ---------------------------------------------------------
+// dst = (src (256 - a) + fill a + 128) >> 8 for n_frames planes of w x h samples (1 ... 8192 each way; u8 at 8 bit, otherwise
+// u16), a interpolated from a grid of nodes 0 ... 256 that lie 1 << sx by 1 << sy samples apart (0 ... kMaskMaxStep each),
+// mask_grid(w, sx) columns by mask_grid(h, sy) rows of uint16 in DEVICE memory; the definition heads mask_blend.hip.  fill: a
+// plane of the same geometry with pitches of its own, or null for fill_const (at most 2^bit_depth - 1).  Frame f at base +
+// f * frame_pitch, pitches in BYTES.  Of the grid only the rows bounds.row0 ... are read, at their place in it.  dst may be
+// exactly src (same base and pitches): then only bounds.rect, the samples with a > 0 as mask_node_bounds gives them, is
+// launched (x0 >= x1: nothing is); otherwise the whole plane is written.
+// Reads no source byte past a row's last sample, writes no destination byte past it.  hipErrorInvalidValue, before any launch,
+// on a null pointer, a size, depth, step or fill out of range, more than 65535 frames, a side that is not made of whole
+// samples, a pitch below a row or dst == fill.
+constexpr int kMaskChunk = 8;     // frames per chunk of the host entry
+constexpr int kMaskMaxStep = 6;
+inline int mask_grid(int size, int step_log2) { return ((size + (1 << step_log2) - 1) >> step_log2) + 1; }
+// What the host learns from one pass over a grid.  rect = {x0, y0, x1, y1}: the bounding rectangle of the samples on which a
+// non-zero node weighs (x0 >= x1: there is none).  The node rows row0 ... row0 + rows - 1 hold every non-zero node: only they
+// need to be in device memory.
+struct MaskBounds {
+  int rect[4];
+  int row0, rows;
+};
+bool mask_node_bounds(const uint16_t* nodes, int w, int h, int sx, int sy, MaskBounds* bounds);   // false: a node above 256
+hipError_t launch_mask_blend(hipStream_t stream, Elem elem, int bit_depth, const uint16_t* nodes, int sx, int sy, unsigned fill_const,
+                             const MaskBounds& bounds, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch, const void* fill,
+                             int64_t fill_row_pitch, int64_t fill_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
+                             int n_frames, int w, int h);
+
 }  // namespace pqa

@@ -85,6 +85,7 @@ enum SideBuf {
   SIDE_TABLE_LUT, SIDE_TABLE_SRC, SIDE_TABLE_DST,                              // pqa_table_apply[_device], table_apply.hip: the table; pqa_table_apply: a chunk of uploaded / of mapped planes
   SIDE_RGB_SRC, SIDE_RGB_DST,                                                  // pqa_rgb_convert, rgb_convert.hip: a chunk of uploaded packed RGB frames / of converted planes
   SIDE_ITP_REF, SIDE_ITP_DIS, SIDE_ITP_PART, SIDE_ITP_OUT,                      // pqa_delta_itp[_device], delta_itp.hip: a chunk of uploaded reference / captured frames, the tiles' partial sums of a chunk, the sums
+  SIDE_MASK_NODES, SIDE_MASK_SRC, SIDE_MASK_FILL,                              // pqa_mask_blend[_device], mask_blend.hip: the node grid; pqa_mask_blend: a chunk of uploaded planes (blended where they lie) / of fill planes
   kSideBufs
 };
 

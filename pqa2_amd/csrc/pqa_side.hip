@@ -1389,6 +1389,123 @@ int pqa_table_apply(pqa_ctx* c, const pqa_table_spec* spec, const void* table, c
   return PQA_OK;
 }
 
+// ---- overlay masking: planes through a feathered mask (mask_blend.hip) ---------------------------------------------------------
+
+namespace {
+// The argument rules both entries share, in spec_check's order and then the grid's (no device call); bounds: what one pass over the grid tells (kernels.h).
+int mask_check(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const void* src, const void* dst, int32_t n_frames, MaskBounds* bounds) {
+  const int rc = spec_check(c, "mask_blend", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (sp->step_log2_x > (uint32_t)kMaskMaxStep || sp->step_log2_y > (uint32_t)kMaskMaxStep)
+      return fail(c, PQA_EINVAL, "mask_blend: steps %u, %u above %d", sp->step_log2_x, sp->step_log2_y, kMaskMaxStep);
+    const uint32_t top = (1u << c->cfg.bit_depth) - 1u;
+    return sp->fill > top ? fail(c, PQA_EINVAL, "mask_blend: fill %u above %u", sp->fill, top) : (int)PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  if (!nodes) return fail(c, PQA_EINVAL, "mask_blend: null node grid");
+  if (!mask_node_bounds(nodes, (int)sp->width, (int)sp->height, (int)sp->step_log2_x, (int)sp->step_log2_y, bounds))
+    return fail(c, PQA_EINVAL, "mask_blend: a node is above 256");
+  return PQA_OK;
+}
+size_t mask_node_bytes(const pqa_mask_spec* sp) {
+  return (size_t)mask_grid((int)sp->width, (int)sp->step_log2_x) * mask_grid((int)sp->height, (int)sp->step_log2_y) * sizeof(uint16_t);
+}
+// the grid's rows that hold a non-zero node onto the stream, at their place in the grid, in front of the launches that read
+// them; pageable memory: the copy has left `nodes` on return
+hipError_t mask_upload(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const MaskBounds& b) {
+  if (!b.rows) return hipSuccess;
+  const size_t gx = (size_t)mask_grid((int)sp->width, (int)sp->step_log2_x), first = (size_t)b.row0 * gx;
+  return hipMemcpyAsync((uint16_t*)c->side_buf[SIDE_MASK_NODES] + first, nodes + first, (size_t)b.rows * gx * sizeof(uint16_t),
+                        hipMemcpyHostToDevice, c->stream);
+}
+}  // namespace
+
+int pqa_mask_blend_device(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t* nodes, const void* src, int64_t src_row_pitch,
+                          int64_t src_frame_pitch, const void* fill, int64_t fill_row_pitch, int64_t fill_frame_pitch, void* dst,
+                          int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
+  MaskBounds bounds;
+  int rc = mask_check(c, spec, nodes, src, dst, n_frames, &bounds);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize;
+  const int64_t row = (int64_t)spec->width * es;
+  if (((uintptr_t)src | (uintptr_t)src_row_pitch | (uintptr_t)src_frame_pitch) & (uintptr_t)(es - 1))
+    return fail(c, PQA_EINVAL, "mask_blend: source base or pitch is not a multiple of the sample size");
+  if (((uintptr_t)dst | (uintptr_t)dst_row_pitch | (uintptr_t)dst_frame_pitch) & (uintptr_t)(es - 1))
+    return fail(c, PQA_EINVAL, "mask_blend: destination base or pitch is not a multiple of the sample size");
+  if (src_row_pitch < row) return fail(c, PQA_EINVAL, "mask_blend: source pitch smaller than a row");
+  if (dst_row_pitch < row) return fail(c, PQA_EINVAL, "mask_blend: destination pitch smaller than a row");
+  if (fill) {
+    if (((uintptr_t)fill | (uintptr_t)fill_row_pitch | (uintptr_t)fill_frame_pitch) & (uintptr_t)(es - 1))
+      return fail(c, PQA_EINVAL, "mask_blend: fill base or pitch is not a multiple of the sample size");
+    if (fill_row_pitch < row) return fail(c, PQA_EINVAL, "mask_blend: fill pitch smaller than a row");
+    if (fill == dst) return fail(c, PQA_EINVAL, "mask_blend: the destination is the fill plane");
+  }
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = side_reserve(c, SIDE_MASK_NODES, mask_node_bytes(spec));
+  if (rc != PQA_OK) return rc;
+  hipError_t e = mask_upload(c, spec, nodes, bounds);
+  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid)
+    e = launch_mask_blend(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint16_t*)c->side_buf[SIDE_MASK_NODES], (int)spec->step_log2_x,
+                          (int)spec->step_log2_y, spec->fill, bounds, (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch,
+                          src_frame_pitch, fill ? (const uint8_t*)fill + (int64_t)f0 * fill_frame_pitch : nullptr, fill_row_pitch,
+                          fill_frame_pitch, (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch, dst_frame_pitch,
+                          chunk_len(n_frames, f0, kGrid), (int)spec->width, (int)spec->height);
+  return side_finish(c, "mask_blend", e, nullptr, nullptr, 0);
+}
+
+int pqa_mask_blend(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t* nodes, const void* const* src_frames, int64_t src_row_stride,
+                   const void* const* fill_frames, int64_t fill_row_stride, void* const* dst_frames, int64_t dst_row_stride,
+                   int32_t n_frames) {
+  MaskBounds bounds;
+  int rc = mask_check(c, spec, nodes, src_frames, dst_frames, n_frames, &bounds);
+  if (rc != PQA_OK) return rc;
+  const int w = (int)spec->width, h = (int)spec->height;
+  const size_t row = (size_t)w * c->esize;
+  rc = check_host_frames(c, "mask_blend: ", "source ", src_frames, 1, n_frames, src_row_stride, row, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "mask_blend: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, row, true);
+  if (rc == PQA_OK && fill_frames) rc = check_host_frames(c, "mask_blend: ", "fill ", fill_frames, 1, n_frames, fill_row_stride, row, true);
+  if (rc != PQA_OK) return rc;
+  for (int f = 0; fill_frames && f < n_frames; ++f)
+    if (fill_frames[f] == dst_frames[f]) return fail(c, PQA_EINVAL, "mask_blend: destination frame %d is its fill plane", f);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // As pqa_table_apply: chunks of kMaskChunk planes out through the first pinned chunk of the side analyses (the source planes,
+  // the fill planes behind them) and back through the second, in the packed layout of host_stage.h.  The uploaded source planes
+  // are blended where they lie: the launch covers the mask's rectangle only, the rest of a plane comes back as it went.
+  const host::PlaneLayout P = host::plane_layout(row, h);
+  const int chunk = n_frames < kMaskChunk ? n_frames : kMaskChunk;
+  const size_t chunk_bytes = P.frame_bytes * chunk;
+  rc = side_pin_reserve(c, 0, chunk_bytes * (fill_frames ? 2 : 1));
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, chunk_bytes);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_MASK_NODES, mask_node_bytes(spec));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_MASK_SRC, chunk_bytes);
+  if (rc == PQA_OK && fill_frames) rc = side_reserve(c, SIDE_MASK_FILL, chunk_bytes);
+  if (rc != PQA_OK) return rc;
+  for (int f0 = 0; f0 < n_frames; f0 += kMaskChunk) {
+    const int n = chunk_len(n_frames, f0, kMaskChunk);
+    host::pack_planes(c->side_pin[0], P, src_frames + f0, src_row_stride, n);
+    if (fill_frames) host::pack_planes(c->side_pin[0] + chunk_bytes, P, fill_frames + f0, fill_row_stride, n);
+    hipError_t e = f0 == 0 ? mask_upload(c, spec, nodes, bounds) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_MASK_SRC], c->side_pin[0], P.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && fill_frames)
+      e = hipMemcpyAsync(c->side_buf[SIDE_MASK_FILL], c->side_pin[0] + chunk_bytes, P.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_mask_blend(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint16_t*)c->side_buf[SIDE_MASK_NODES], (int)spec->step_log2_x,
+                            (int)spec->step_log2_y, spec->fill, bounds, c->side_buf[SIDE_MASK_SRC], P.pitch, (int64_t)P.frame_bytes,
+                            fill_frames ? c->side_buf[SIDE_MASK_FILL] : nullptr, P.pitch, (int64_t)P.frame_bytes, c->side_buf[SIDE_MASK_SRC],
+                            P.pitch, (int64_t)P.frame_bytes, n, w, h);
+    rc = side_finish(c, "mask_blend", e, c->side_pin[1], c->side_buf[SIDE_MASK_SRC], P.frame_bytes * n);
+    if (rc != PQA_OK) return rc;
+    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
+      for (int y = 0; y < h; ++y)
+        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * P.frame_bytes + (size_t)y * P.pitch, row);
+  }
+  return PQA_OK;
+}
+
 // ---- the spec-driven analyses: flow_moments() ... line_profiles() above ------------------------------------------------------
 
 int pqa_flow_moments_device(pqa_ctx* c, const pqa_flow_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,

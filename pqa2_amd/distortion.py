@@ -255,6 +255,15 @@ def find_defects(S, counts, *, factor=16, min_mse=4.0, tile: int, bit_depth: int
     return sorted(out, key=lambda ev: (ev["first"], ev["box"][1], ev["box"][0]))
 
 
+def persistent_tiles(hot, share=0.9) -> np.ndarray:
+    """bool [ty, tx]: the tiles that are hot in at least `share` of the n frames of hot [n, ty, tx] (and in one at least),
+    compared in integers"""
+    hot = np.asarray(hot, bool)
+    r = _ratio(share, 1000)
+    times = hot.sum(axis=0).astype(np.int64)
+    return (times * r.denominator >= r.numerator * hot.shape[0]) & (times > 0)
+
+
 def persistent_regions(hot, S, counts, *, share=0.9, tile: int, bit_depth: int = 8, width: int | None = None,
                        height: int | None = None) -> dict:
     """Overlay candidates: the tiles that are hot (hot_tiles) in at least `share` of the frames -- a channel logo, a clock or
@@ -271,9 +280,8 @@ def persistent_regions(hot, S, counts, *, share=0.9, tile: int, bit_depth: int =
     if width is None or height is None:
         width, height = plane_size(counts, tile)
     n = S.shape[0]
-    r = _ratio(share, 1000)
     times = hot.sum(axis=0).astype(np.int64)
-    mask = (times * r.denominator >= r.numerator * n) & (times > 0)
+    mask = persistent_tiles(hot, share)
     per_tile = S.sum(axis=0, dtype=np.uint64)      # a tile over the clip: below 2^37 n, exact; the plane's total need not fit
     sse_all = sum(int(v) for v in per_tile.ravel())
     pix_all = int(counts.sum()) * n
@@ -317,3 +325,126 @@ def analyse_plane(S, M_sum, width: int, height: int, tile: int, bit_depth: int, 
             "worst_frame": None if worst is None else {"frame": worst, "tile_psnr_min": float(cols["tile_psnr_min"][worst]),
                                                        "tile": [int(v) for v in cols["tile_psnr_min_at"][worst]]},
             "columns": cols, "mean_psnr": mean_psnr}
+
+
+# ---- overlay masking: the node grid FeatureEngine.mask_blend takes (pqa_mask_blend, csrc/mask_blend.hip) ----------------------
+# A grid of nodes 0 ... 256, `node` = 1 << step_log2 luma samples apart each way, ((size + node - 1) >> step_log2) + 1 of them
+# along an axis; alpha at a sample is their bilinear interpolation (mask_alpha).  Chroma planes take the same grid at step_log2
+# minus their shift: a chroma sample then sees the alpha of the luma sample it sits on.
+
+MASK_FULL = 256
+
+
+def _step_log2(node: int, chroma_shift=(0, 0)) -> int:
+    node = int(node)
+    if node < 1 or node > 64 or node & (node - 1):
+        raise ValueError(f"node must be a power of two from 1 to 64, not {node}")
+    s = node.bit_length() - 1
+    for sh in chroma_shift:
+        if int(sh) < 0 or s - int(sh) < 0:
+            raise ValueError(f"nodes {node} samples apart cannot serve a chroma plane subsampled by {1 << int(sh)}")
+    return s
+
+
+def mask_alpha(nodes, width: int, height: int, step_log2_x: int, step_log2_y: int) -> np.ndarray:
+    """int64 [height, width]: alpha 0 ... 256 of every sample of a plane under a node grid, as include/pqa_vmaf.h defines it"""
+    A = np.asarray(nodes).astype(np.int64)
+    sx, sy = int(step_log2_x), int(step_log2_y)
+    gx, gy = 1 << sx, 1 << sy
+    if A.shape != (((height + gy - 1) >> sy) + 1, ((width + gx - 1) >> sx) + 1):
+        raise ValueError("node grid and plane size disagree")
+    x, y = np.arange(width, dtype=np.int64), np.arange(height, dtype=np.int64)
+    i, fx, j, fy = x >> sx, x & (gx - 1), y >> sy, y & (gy - 1)
+    E0 = A[j] * (gy - fy)[:, None] + A[j + 1] * fy[:, None]      # [height, nodes along x]
+    return (E0[:, i] * (gx - fx) + E0[:, i + 1] * fx + ((gx * gy) >> 1)) >> (sx + sy)
+
+
+def grow_tiles(mask: np.ndarray, times: int) -> np.ndarray:
+    """a bool map grown `times` times by its 8-neighbourhood"""
+    m = np.asarray(mask, bool).copy()
+    for _ in range(int(times)):
+        p = np.pad(m, 1)
+        m = np.zeros_like(m)
+        for dj in range(3):
+            for di in range(3):
+                m |= p[dj:dj + m.shape[0], di:di + m.shape[1]]
+    return m
+
+
+def _mask_result(inside: np.ndarray, boxes, width: int, height: int, node: int, feather: int, step: int) -> dict:
+    """the feathered grid around the nodes `inside`, and what the builders report about it"""
+    feather = int(feather)
+    if feather < 0 or feather % node:
+        raise ValueError(f"feather {feather} is no multiple of the node step {node}")
+    K = feather // node
+    nodes = np.where(inside, MASK_FULL, 0).astype(np.uint16)
+    reach = inside
+    for s in range(1, K):      # Chebyshev distance s from the inside set
+        wider = grow_tiles(reach, 1)
+        nodes[wider & ~reach] = MASK_FULL - (MASK_FULL * s) // K
+        reach = wider
+    bounds = None
+    js, is_ = np.nonzero(nodes)
+    if len(js):      # node i weighs on the samples strictly between nodes i - 1 and i + 1
+        bounds = [max(0, ((int(is_.min()) - 1) << step) + 1), max(0, ((int(js.min()) - 1) << step) + 1),
+                  min(width, (int(is_.max()) + 1) << step), min(height, (int(js.max()) + 1) << step)]
+        if bounds[0] >= bounds[2] or bounds[1] >= bounds[3]:
+            bounds = None
+    covered = int(np.count_nonzero(mask_alpha(nodes, width, height, step, step))) if bounds else 0
+    return {"nodes": nodes, "step_log2": step, "boxes": boxes, "bounds": bounds, "share": covered / (width * height)}
+
+
+def overlay_mask(tiles, width: int, height: int, tile: int, *, grow: int = 1, feather: int = 16, node: int = 8,
+                 chroma_shift=(0, 0)) -> dict:
+    """The node grid that masks the tiles `tiles` (bool [ty, tx] over tiles of `tile` x `tile` luma samples, e.g.
+    persistent_tiles) out of a width x height picture, in integers.  The tiles are grown `grow` times by their 8-neighbourhood.
+    A node is inside when its position (node gx, node gy) lies in the closed square [i tile, (i + 1) tile] x [j tile, (j + 1)
+    tile] of a masked tile (i, j) -- a partial last tile counts with its full square -- so every sample of a masked tile has
+    alpha = 256 exactly; `tile` must be a multiple of `node`.  Nodes at Chebyshev distance s node steps from the inside set,
+    1 <= s < feather / node, hold 256 - (256 s) // (feather / node), all others 0; feather is a multiple of node, 0 (or node)
+    is a hard edge.  chroma_shift: the (horizontal, vertical) subsampling the grid has to serve at step_log2 - shift.
+    Returns {nodes uint16 [gy, gx], step_log2, boxes, bounds, share}: boxes the 4-neighbour components of the grown tiles as
+    [x0, y0, x1, y1] in pixels, bounds the rectangle of the samples a non-zero node weighs on (None: there is none), share
+    the exact fraction of samples with alpha > 0."""
+    tile, width, height = int(tile), int(width), int(height)
+    step = _step_log2(node, chroma_shift)
+    if tile < 1 or tile % node:
+        raise ValueError(f"tile {tile} is no multiple of the node step {node}")
+    t = np.asarray(tiles, bool)
+    if width < 1 or height < 1 or t.shape != (-(-height // tile), -(-width // tile)):
+        raise ValueError("tile map and plane size disagree")
+    if int(grow) < 0:
+        raise ValueError("grow must not be negative")
+    t = grow_tiles(t, grow)
+    gy, gx = ((height + node - 1) >> step) + 1, ((width + node - 1) >> step) + 1
+    inside = np.zeros((gy, gx), bool)
+    r = tile // node
+    for j, i in zip(*np.nonzero(t)):
+        inside[j * r:(j + 1) * r + 1, i * r:(i + 1) * r + 1] = True      # slices past the grid's edge end there
+    boxes = [_box(comp, tile, width, height) for comp in _components(t)]
+    return _mask_result(inside, boxes, width, height, node, feather, step)
+
+
+def overlay_mask_from_boxes(boxes, width: int, height: int, *, feather: int = 16, node: int = 8, chroma_shift=(0, 0)) -> dict:
+    """The same grid from boxes [x0, y0, x1, y1] in luma pixels (x1, y1 exclusive) the user names.  A box is snapped outward
+    to multiples of `node` and of the chroma step and its nodes are the inside set; nothing is grown.  `boxes` comes back
+    snapped and clipped to the picture."""
+    width, height = int(width), int(height)
+    step = _step_log2(node, chroma_shift)
+    if width < 1 or height < 1:
+        raise ValueError("the picture has no samples")
+    gy, gx = ((height + node - 1) >> step) + 1, ((width + node - 1) >> step) + 1
+    inside = np.zeros((gy, gx), bool)
+    out = []
+    for b in boxes:
+        if len(b) != 4:
+            raise ValueError(f"a box is [x0, y0, x1, y1], not {list(b)}")
+        x0, y0, x1, y1 = (int(v) for v in b)
+        if not (0 <= x0 < x1 <= width and 0 <= y0 < y1 <= height):
+            raise ValueError(f"box {[x0, y0, x1, y1]} is empty or leaves the {width}x{height} picture")
+        gxs = [max(node, 1 << int(chroma_shift[0])), max(node, 1 << int(chroma_shift[1]))]
+        x0, y0 = x0 // gxs[0] * gxs[0], y0 // gxs[1] * gxs[1]
+        x1, y1 = -(-x1 // gxs[0]) * gxs[0], -(-y1 // gxs[1]) * gxs[1]
+        inside[y0 >> step:(y1 >> step) + 1, x0 >> step:(x1 >> step) + 1] = True
+        out.append([x0, y0, min(x1, width), min(y1, height)])
+    return _mask_result(inside, out, width, height, node, feather, step)

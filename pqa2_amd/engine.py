@@ -647,6 +647,65 @@ class FeatureEngine:
                                                     dst_ptr or None, dst_row_pitch, dst_frame_pitch, int(n_frames)))
         del keep_t
 
+    # -- overlay masking ---------------------------------------------------------------------
+    def _mask(self, nodes, steps, fill, shape):
+        """(node grid kept alive, its pointer, pqa_mask_spec) of a mask over planes of `shape` = (height, width): nodes a 2-D
+        array of integers 0 ... 256 with the rows and columns include/pqa_vmaf.h asks of steps = (step_log2_x, step_log2_y); a
+        value uint16 cannot hold is refused here, one above 256 by the library"""
+        sx, sy = (int(v) for v in steps)
+        g = np.asarray(nodes)
+        if g.ndim != 2 or g.dtype.kind not in "ui":
+            raise ValueError("mask_blend needs a 2-D grid of integer nodes")
+        if g.size and (int(g.min()) < 0 or int(g.max()) > 0xffff):
+            raise N.PqaError(N.PQA_EINVAL, "mask_blend: a node does not fit uint16")
+        if 0 <= sx <= N.MASK_MAX_STEP and 0 <= sy <= N.MASK_MAX_STEP and 1 <= shape[0] <= 8192 and 1 <= shape[1] <= 8192:
+            want = (((shape[0] + (1 << sy) - 1) >> sy) + 1, ((shape[1] + (1 << sx) - 1) >> sx) + 1)
+            if g.shape != want:   # the library cannot see the size of what the pointer points at
+                raise ValueError(f"mask_blend needs a grid of {want} nodes for planes of {tuple(shape)} at steps {(sx, sy)}, not {g.shape}")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        sp = self._plane_spec(N.PqaMaskSpec, shape, step_log2_x=sx, step_log2_y=sy, fill=0 if fill is None else fill)
+        return g, g.ctypes.data, sp
+
+    def mask_blend(self, frames, nodes, steps, fill, plane: int | None = 0):
+        """A list of new 2-D arrays: every plane of `frames` (HOST memory) through the feathered mask of `nodes` (integers
+        0 ... 256, `steps` = (step_log2_x, step_log2_y) samples apart as powers of two), out = (src (256 - a) + fill a + 128)
+        >> 8 with a interpolated from the four nodes around a sample (pqa_mask_blend; definition: include/pqa_vmaf.h).  fill:
+        an integer of at most 2^bit_depth - 1, or a list of as many planes as `frames` whose samples are the fill.
+        distortion.overlay_mask makes the grid.  The planes have the size of `plane` of this context, or with plane=None any
+        one size of their own."""
+        arrs = [np.asarray(f) for f in frames]
+        shape = self.plane_shape(int(plane)) if plane is not None else (arrs[0].shape if arrs else (self.height, self.width))
+        if len(shape) != 2:
+            raise ValueError("mask_blend needs 2-D planes")
+        shape = tuple(int(v) for v in shape)
+        const = isinstance(fill, (int, np.integer))
+        if not const and len(fill) != len(arrs):
+            raise ValueError("mask_blend needs as many fill planes as frames")
+        keep_g, gp, sp = self._mask(nodes, steps, fill if const else 0, shape)
+        keep, sptr, sstride = self._luma_list(arrs, "source", shape)
+        keep_f, fptr, fstride = (None, None, 0) if const else self._luma_list(fill, "fill", shape)
+        out = [np.empty(shape, self.dtype) for _ in keep]
+        dptr = (C.c_void_p * max(len(out), 1))()
+        for i, o in enumerate(out):
+            dptr[i] = o.ctypes.data
+        self._check(self.lib.pqa_mask_blend(self._ctx, C.byref(sp), gp, sptr, sstride, fptr, fstride, dptr,
+                                            shape[1] * np.dtype(self.dtype).itemsize, len(keep)))
+        del keep, keep_f, keep_g
+        return out
+
+    def mask_blend_resident(self, nodes, steps, fill, shape, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, dst_ptr: int,
+                            dst_row_pitch: int, dst_frame_pitch: int, n_frames: int, fill_ptr: int = 0, fill_row_pitch: int = 0,
+                            fill_frame_pitch: int = 0):
+        """The same for n_frames planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_mask_blend_device).  fill: the constant; with fill_ptr the fill plane in HBM instead.  dst may be exactly src --
+        then only the bounding rectangle of the mask is read and written -- but not the fill plane.  Nothing but the node grid
+        crosses PCIe; the result can go into submit_resident."""
+        keep_g, gp, sp = self._mask(nodes, steps, fill, shape)
+        self._check(self.lib.pqa_mask_blend_device(self._ctx, C.byref(sp), gp, src_ptr or None, src_row_pitch, src_frame_pitch,
+                                                   fill_ptr or None, fill_row_pitch, fill_frame_pitch, dst_ptr or None,
+                                                   dst_row_pitch, dst_frame_pitch, int(n_frames)))
+        del keep_g
+
     # -- resampling --------------------------------------------------------------------------
     def _resample_spec(self, src_shape, dst_shape, filter, window):
         """the pqa_resample_spec of planes src_shape -> dst_shape ((height, width) each); window = (x0, y0, w, h) in source

@@ -46,7 +46,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 grid_z2: float = 25.0, chroma_mismatch: str = "error", chroma_siting: str | None = None,
                 rgb_matrix: str | None = None, rgb_range: str | None = None, delta_itp: str | None = None,
                 itp_matrix: str | None = None, itp_range: str | None = None, itp_peak: float | None = None,
-                itp_threshold: float = 1.0) -> ScoreResult | None:
+                itp_threshold: float = 1.0, overlay_mask: str | None = None, overlay_boxes=None, overlay_frames: int = 32,
+                overlay_tile: int = 16, overlay_grow: int = 1, overlay_feather: int = 16,
+                overlay_share: float = 0.9) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -225,7 +227,25 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     or "limited" R'G'B'; None: full for the 8-bit formats, limited for r210, which is what the cards deliver.  The Y'CbCr range
     follows the partner's header (XCOLORRANGE=FULL: full, else limited).  `input` then carries "conversion": {"side", "from", "to",
     "matrix", "rgb_range", "yuv_range", "bit_depth": [from, to], "siting": {"to": [h, v]}, "coefficients": [12 Q14 integers]} (a
-    list of two such objects when both clips are RGB), planes_scored "yuv", packed_upload false."""
+    list of two such objects when both clips are RGB), planes_scored "yuv", packed_upload false.
+
+    `overlay_mask`: None, "report", "neutral" or "reference" -- a burnt-in overlay (a channel logo, a clock, a timecode, an OSD)
+    taken out of the scores.  After every alignment step `overlay_frames` frame pairs spread evenly over the clips are read,
+    the tile moments of their luma at `overlay_tile` (8, 16, 32 or 64) give the tiles that are hot in at least
+    `overlay_share` of them (distortion.hot_tiles, persistent_tiles), and distortion.overlay_mask grows them `overlay_grow`
+    tiles and feathers `overlay_feather` luma samples (a multiple of 8) around them; with `overlay_boxes` = [[x0, y0, x1, y1],
+    ...] (luma pixels of the scored window, x1 and y1 exclusive) the mask is built from the boxes and nothing is detected.
+    Every rank does the same.  "neutral" blends BOTH clips, every plane, towards one constant per plane inside the mask (luma:
+    the rounded mean of the sampled reference frames over the masked tiles; chroma: mid-grey) -- a flat region adds nothing
+    to VIF and ADM but also removes the reference's motion there, so the score reads slightly low; "reference" leaves the
+    reference alone and blends the captured planes towards the reference's own samples -- the region counts as transmitted
+    perfectly, so the score reads high.  The blend is FeatureEngine.mask_blend (pqa_mask_blend), and
+    everything downstream -- the scores and the map, spectrum, temporal, grid and Delta E ITP passes -- sees the masked clips.
+    "report" finds the mask and applies nothing.  The result carries `overlay` = {mode, detected, regions, boxes, share, fill,
+    tile, grow, feather, frames_sampled, applied}: `regions` as distortion.persistent_regions gives them, `boxes` the masked
+    boxes in pixels, `share` the fraction of luma samples the mask touches, `fill` the constants per plane or "reference",
+    `applied` false under "report" and when no tile is persistent.  None: nothing is read or changed and the result has no such
+    object."""
     from . import integrity as IG
     from .engine import FeatureEngine
     raw_kwargs = raw_kwargs or {}
@@ -378,6 +398,30 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         alignment = dict(alignment or {}, colour=colour)
         if colour["applied"]:
             dis_rd = coloured = _ColourReader(dis_rd, colour["correction"], device, make_side)
+    overlay = None
+    masked = []
+    if overlay_mask is not None or overlay_boxes is not None:
+        if overlay_mask not in ("report", "neutral", "reference"):
+            raise ValueError('overlay_mask must be None, "report", "neutral" or "reference"')
+        if overlay_frames is None or overlay_frames < 1:
+            raise ValueError("overlay_frames must be positive")
+        if overlay_tile not in N.FLOW_TILES:
+            raise ValueError("overlay_tile must be a tile size of 8, 16, 32 or 64")
+        if overlay_grow is None or overlay_grow < 0:
+            raise ValueError("overlay_grow must not be negative")
+        if overlay_feather is None or overlay_feather < 0 or overlay_feather % OVERLAY_NODE:
+            raise ValueError(f"overlay_feather must be a multiple of {OVERLAY_NODE}, or 0")
+        if overlay_share is None or not 0 < overlay_share <= 1:
+            raise ValueError("overlay_share must lie in (0, 1]")
+        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
+        overlay, mask = _find_overlay(ref_rd, dis_rd, overlay_mask, overlay_boxes, int(overlay_frames), int(overlay_tile),
+                                      int(overlay_grow), int(overlay_feather), overlay_share, device, make_side)
+        if overlay["applied"] and overlay_mask == "neutral":
+            masked = [_MaskedReader(rd, mask, overlay["fill"], None, device, make_side) for rd in (ref_rd, dis_rd)]
+            ref_rd, dis_rd = masked
+        elif overlay["applied"]:
+            masked = [_MaskedReader(dis_rd, mask, None, ref_rd, device, make_side)]
+            dis_rd = masked[0]
     n = min(len(ref_rd), len(dis_rd))
     if n <= 0:
         raise ValueError("no frames to analyse")
@@ -548,7 +592,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     rec = shard.gather_records(local, n, world_size, rank, gather_device)
     blk = {i: shard.gather_records(local_blk[i], n, world_size, rank, gather_device, width=N.EXT_BLOCKS[i][1]) for i in want}
     if rank != 0:
-        for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured):
+        for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured, *masked):
             if rd is not None:
                 rd.close()
         return None
@@ -605,7 +649,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
         res["resize"] = resized
     if input_info is not None:
         res["input"] = input_info
-    for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured):   # on an error their contexts go with the readers
+    if overlay is not None:
+        res["overlay"] = overlay
+    for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured, *masked):   # on an error their contexts go with the readers
         if rd is not None:
             rd.close()
     return res
@@ -1040,6 +1086,89 @@ class _ColourReader:
             first = i - i % self.RUN
             frames = [self._rd.frame(j)[:3] for j in range(first, min(first + self.RUN, len(self._rd)))]
             self._first, self._run = first, self._eng.colour_apply(frames, self._m)
+        return self._run[i - self._first]
+
+
+OVERLAY_NODE = 8      # luma samples between the nodes of an overlay mask: 4:2:0 chroma takes the same grid at step 4
+
+
+def _find_overlay(ref_rd, dis_rd, mode: str, boxes, n_frames: int, tile: int, grow: int, feather: int, share, device, make):
+    """(the `overlay` object, the mask of distortion.overlay_mask or None) of two opened, paired clips of one size.  Without
+    `boxes`: the luma tile moments of a few pairs on a small context of its own, the tiles hot in `share` of them, grown and
+    feathered.  The neutral luma fill is the rounded mean of the sampled reference frames over the samples with alpha = 256:
+    from the tiles' sums of r, which is exact, or under `boxes` from the frames themselves."""
+    from . import distortion as D
+    ri = ref_rd.info
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError("no frames to analyse")
+    shift = (0, 0) if ri.mono else (ri.hshift, ri.vshift)
+    refs = [ref_rd.frame(i)[0] for i in idx]
+    regions = []
+    if boxes is not None:
+        mask = D.overlay_mask_from_boxes(boxes, ri.width, ri.height, feather=feather, node=OVERLAY_NODE, chroma_shift=shift)
+        full = D.mask_alpha(mask["nodes"], ri.width, ri.height, mask["step_log2"], mask["step_log2"]) == D.MASK_FULL
+        total, count = sum(int(np.asarray(r)[full].sum(dtype=np.uint64)) for r in refs), int(full.sum()) * len(refs)
+    else:
+        eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, features=N.FEAT_PSNR, device=device, max_batch=8,
+                   result_capacity=16)
+        try:
+            Mo = eng.tile_moments(refs, [dis_rd.frame(i)[0] for i in idx], tile)
+        finally:
+            eng.close()
+        S, counts = D.tile_sse(Mo), D.tile_counts(ri.width, ri.height, tile)
+        hot = D.hot_tiles(S, counts, tile=tile, bit_depth=ri.bit_depth)
+        regions = D.persistent_regions(hot, S, counts, share=share, tile=tile, bit_depth=ri.bit_depth, width=ri.width,
+                                       height=ri.height)["regions"]
+        tiles = D.persistent_tiles(hot, share)
+        mask = D.overlay_mask(tiles, ri.width, ri.height, tile, grow=grow, feather=feather, node=OVERLAY_NODE, chroma_shift=shift)
+        grown = D.grow_tiles(tiles, grow)
+        total = sum(int(v) for v in Mo[..., D.SUM_R].sum(axis=0, dtype=np.uint64)[grown])      # a tile over the sample: below 2^30, exact
+        count = int(counts[grown].sum()) * len(idx)
+    luma = (2 * total + count) // (2 * count) if count else 1 << (ri.bit_depth - 1)
+    fill = [int(luma)] + ([] if ri.mono else [1 << (ri.bit_depth - 1)] * 2)
+    found = mask["bounds"] is not None
+    overlay = {"mode": mode, "detected": boxes is None, "regions": regions, "boxes": mask["boxes"], "share": mask["share"],
+               "fill": "reference" if mode == "reference" else fill, "tile": tile, "grow": grow, "feather": feather,
+               "frames_sampled": len(idx), "applied": bool(found and mode != "report")}
+    return overlay, (mask if found else None)
+
+
+class _MaskedReader:
+    """A clip with a burnt-in overlay blended out: plane p of every frame goes through the feathered mask on the GPU
+    (FeatureEngine.mask_blend) towards the constant fills[p] -- or, with `partner`, towards the partner clip's own plane p of
+    the same frame.  The chroma planes take the luma grid at the step their subsampling leaves.  What score_files reads under
+    overlay_mask="neutral" (both clips) and "reference" (the captured clip, partner: the reference).  Built like _TableReader --
+    a small context of its own, frames fetched in runs of eight, the last run kept, one call per plane and run.  No
+    file-descriptor path: the blended samples exist in host arrays only.  close() frees the context."""
+    RUN = 8
+
+    def __init__(self, reader, mask, fills, partner, device, make):
+        info = self.info = reader.info
+        self._rd, self._partner, self._fills = reader, partner, fills
+        self._nodes, s = mask["nodes"], mask["step_log2"]
+        self._steps = [(s, s)] + ([] if info.mono else [(s - info.hshift, s - info.vshift)] * 2)
+        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=1 if info.mono else 3,
+                         chroma_shift=(info.hshift, info.vshift), features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
+        self._first, self._run = 0, []
+
+    def __len__(self):
+        return len(self._rd) if self._partner is None else min(len(self._rd), len(self._partner))
+
+    def close(self):
+        self._eng.close()
+
+    def frame(self, i: int):
+        if not self._first <= i < self._first + len(self._run):
+            first = i - i % self.RUN
+            span = range(first, min(first + self.RUN, len(self)))
+            frames = [list(self._rd.frame(j)) for j in span]
+            towards = [self._partner.frame(j) for j in span] if self._partner is not None else None
+            for p, steps in enumerate(self._steps):
+                fill = [t[p] for t in towards] if towards is not None else self._fills[p]
+                for f, blended in zip(frames, self._eng.mask_blend([f[p] for f in frames], self._nodes, steps, fill, p)):
+                    f[p] = blended
+            self._first, self._run = first, frames
         return self._run[i - self._first]
 
 

@@ -256,6 +256,26 @@ def itp_log_keys(delta_itp: dict | None) -> dict:
     return {"delta_itp": distortion_log_keys(delta_itp)["distortion"]}
 
 
+def overlay_log_keys(overlay: dict | None) -> dict:
+    """Top-level key of the JSON log that carries the overlay mask (pipeline.score_files(overlay_mask=)): what was found, what
+    was masked and towards what; none without it."""
+    if not overlay:
+        return {}
+    return {"overlay": distortion_log_keys(overlay)["distortion"]}
+
+
+def overlay_summary_line(overlay: dict) -> str:
+    """One line for a summary or a status bar: the burnt-in overlay and what was done about it."""
+    boxes = overlay.get("boxes") or []
+    how = "given" if not overlay.get("detected", True) else f"persistent in {overlay.get('frames_sampled', 0)} sampled frames"
+    if not boxes:
+        return f"Overlay mask ({overlay.get('mode', '?')}): no region {how}, nothing masked"
+    fill = overlay.get("fill")
+    done = (f"blended towards {'the reference' if fill == 'reference' else fill}" if overlay.get("applied") else "reported only")
+    return (f"Overlay mask ({overlay.get('mode', '?')}): {len(boxes)} region{'s' if len(boxes) != 1 else ''} {how}, first "
+            f"{boxes[0]}, {100.0 * overlay.get('share', 0.0):.1f} % of the picture under the mask, {done}")
+
+
 def itp_summary_line(delta_itp: dict) -> str:
     """One line for a summary or a status bar: the pooled Delta E ITP and what it is made of."""
     sp, s = delta_itp.get("spec", {}), delta_itp.get("summary", {})

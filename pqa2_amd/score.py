@@ -215,6 +215,20 @@ def main(argv=None) -> int:
                     help="with --delta-itp: the display's peak luminance Lw for hlg (default 1000) and bt1886 (default 100)")
     ap.add_argument("--itp-threshold", type=float, default=1.0, metavar="DE",
                     help="with --delta-itp: a pixel is counted as visibly different above this Delta E ITP (default 1)")
+    ap.add_argument("--overlay-mask", default=None, metavar="MODE", choices=["report", "neutral", "reference"],
+                    help="take a burnt-in overlay (a channel logo, a clock, a timecode) out of the scores: find the tiles that "
+                         "differ in nearly every sampled frame and report them (report), blend both clips towards one flat value "
+                         "there (neutral: reads slightly low, the region loses its motion) or blend the distorted clip towards "
+                         "the reference there (reference: reads high, the region counts as perfect); the JSON gets a top-level "
+                         "overlay object")
+    ap.add_argument("--overlay-box", action="append", default=None, metavar="X0,Y0,X1,Y1",
+                    help="with --overlay-mask: mask this box of luma pixels (X1, Y1 exclusive; repeatable) instead of detecting")
+    ap.add_argument("--overlay-frames", type=int, default=32, metavar="N", help="with --overlay-mask: frame pairs sampled (default 32)")
+    ap.add_argument("--overlay-tile", type=int, default=16, choices=[8, 16, 32, 64], help="with --overlay-mask: tile size (default 16)")
+    ap.add_argument("--overlay-grow", type=int, default=1, metavar="TILES",
+                    help="with --overlay-mask: tiles added around the detected ones (default 1)")
+    ap.add_argument("--overlay-feather", type=int, default=16, metavar="PX",
+                    help="with --overlay-mask: width of the mask's soft edge in luma pixels, a multiple of 8 (default 16; 0: hard)")
     ap.add_argument("--chroma-mismatch", default="error", choices=["error", "luma", "convert"],
                     help="clips that differ in chroma subsampling (a 4:2:2 capture such as .uyvy / .v210 against a 4:2:0 "
                          "master): refuse them (default), score their luma only -- VMAF and luma PSNR / SSIM --, or convert the "
@@ -253,6 +267,14 @@ def main(argv=None) -> int:
             last[0] = now
             print(f"frame= {done * world} fps=0 q=0.0 size=N/A", file=sys.stderr, flush=True)
 
+    overlay_boxes = None
+    if a.overlay_box:
+        try:
+            overlay_boxes = [[int(v) for v in b.split(",")] for b in a.overlay_box]
+        except ValueError:
+            ap.error("--overlay-box takes four integers X0,Y0,X1,Y1")
+        if not a.overlay_mask:
+            ap.error("--overlay-box needs --overlay-mask")
     ig_opts = {k: getattr(a, k) for k in IG_OPTIONS if getattr(a, k) is not None}
     want_ig = bool(a.integrity or a.integrity_log or ig_opts)
     try:
@@ -295,6 +317,9 @@ def main(argv=None) -> int:
                           **({"delta_itp": a.delta_itp, "itp_matrix": a.itp_matrix, "itp_range": a.itp_range, "itp_peak": a.itp_peak,
                               "itp_threshold": a.itp_threshold} if a.delta_itp else {}),
                           **({"register": a.register, "register_frames": a.register_frames} if a.register else {}),
+                          **({"overlay_mask": a.overlay_mask, "overlay_boxes": overlay_boxes, "overlay_frames": a.overlay_frames,
+                              "overlay_tile": a.overlay_tile, "overlay_grow": a.overlay_grow, "overlay_feather": a.overlay_feather}
+                             if a.overlay_mask else {}),
                           **({"integrity": True, "integrity_options": ig_opts} if want_ig else {}))
     except Exception as e:  # one line on stderr, non-zero exit: what the caller's returncode check expects
         print(f"pqa2_amd.score: error: {e}", file=sys.stderr, flush=True)
@@ -315,7 +340,8 @@ def main(argv=None) -> int:
                                      **report.spectrum_log_keys(res.get("spectrum")),
                                      **report.temporal_log_keys(res.get("temporal")),
                                      **report.grid_log_keys(res.get("coding_grid")),
-                                     **report.itp_log_keys(res.get("delta_itp"))})
+                                     **report.itp_log_keys(res.get("delta_itp")),
+                                     **report.overlay_log_keys(res.get("overlay"))})
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:
@@ -351,6 +377,8 @@ def main(argv=None) -> int:
             print(report.grid_summary_line(res["coding_grid"]), file=sys.stderr, flush=True)
         if res.get("delta_itp"):
             print(report.itp_summary_line(res["delta_itp"]), file=sys.stderr, flush=True)
+        if res.get("overlay"):
+            print(report.overlay_summary_line(res["overlay"]), file=sys.stderr, flush=True)
         print(f"VMAF score: {log['pooled_metrics']['vmaf']['mean']:.6f}", file=sys.stderr, flush=True)
     return 0
 

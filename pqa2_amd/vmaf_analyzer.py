@@ -182,6 +182,9 @@ class VMAFAnalyzer(QObject):
                                               # transfer, a pass of its own over both clips (pipeline.score_files(delta_itp=))
         self.itp_matrix = None                # its Y'CbCr matrix and primaries: "bt601" / "bt709" / "bt2020"; None: by the transfer
         self.itp_peak = None                  # its display peak Lw in cd/m2 (hlg, bt1886); None: 1000 / 100
+        self.overlay_mask = None              # "report" / "neutral" / "reference": find a burnt-in overlay (logo, clock, timecode)
+                                              # and blend it out of the scores (pipeline.score_files(overlay_mask=))
+        self.overlay_boxes = None             # [[x0, y0, x1, y1], ...] in luma pixels: mask these instead of detecting
         self.resize_filter = None             # "bilinear" / "bicubic" / "lanczos": resample a distorted clip of another frame
                                               # size to the reference's before scoring (pipeline.score_files(resize=))
         self.register_filter = None           # "bilinear" / "bicubic" / "lanczos": measure the capture's sub-pixel shift and
@@ -505,7 +508,8 @@ class VMAFAnalyzer(QObject):
                                      **report.spectrum_log_keys(res.get("spectrum")),
                                      **report.temporal_log_keys(res.get("temporal")),
                                      **report.grid_log_keys(res.get("coding_grid")),
-                                     **report.itp_log_keys(res.get("delta_itp"))})
+                                     **report.itp_log_keys(res.get("delta_itp")),
+                                     **report.overlay_log_keys(res.get("overlay"))})
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:
@@ -549,6 +553,7 @@ class VMAFAnalyzer(QObject):
                 **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
                 **({"coding_grid": True} if self.coding_grid_enabled else {}),
                 **({"delta_itp": self.delta_itp, "itp_matrix": self.itp_matrix, "itp_peak": self.itp_peak} if self.delta_itp else {}),
+                **({"overlay_mask": self.overlay_mask, "overlay_boxes": self.overlay_boxes} if self.overlay_mask else {}),
                 **({"resize": self.resize_filter} if self.resize_filter else {}),
                 **({"register": self.register_filter} if self.register_filter else {}),
                 **({"chroma_mismatch": self.chroma_mismatch} if self.chroma_mismatch != "error" else {}),
@@ -619,6 +624,10 @@ class VMAFAnalyzer(QObject):
                 cmd += ["--itp-matrix", str(self.itp_matrix)]
             if self.itp_peak is not None:
                 cmd += ["--itp-peak", str(float(self.itp_peak))]
+        if self.overlay_mask:
+            cmd += ["--overlay-mask", str(self.overlay_mask)]
+            for box in self.overlay_boxes or []:
+                cmd += ["--overlay-box", ",".join(str(int(v)) for v in box)]
         if self.resize_filter:
             cmd += ["--resize", str(self.resize_filter)]
         if self.register_filter:
@@ -792,6 +801,11 @@ class VMAFAnalyzer(QObject):
                 results["delta_itp"] = vmaf_data.get("delta_itp")
                 if results["delta_itp"]:
                     self.status_update.emit(report.itp_summary_line(results["delta_itp"]))
+            if self.overlay_mask:   # the burnt-in overlay and what was done about it, from the log's top level
+                from . import report
+                results["overlay"] = vmaf_data.get("overlay")
+                if results["overlay"]:
+                    self.status_update.emit(report.overlay_summary_line(results["overlay"]))
             self.analysis_progress.emit(100)
             self.status_update.emit(f"VMAF analysis complete! Score: {vmaf_score:.2f}")
             self.analysis_complete.emit(results)
