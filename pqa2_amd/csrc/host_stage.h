@@ -1,7 +1,8 @@
-// Host side of the pair staging of the side analyses (pqa_side.hip), free of any device call: the packed layout of a plane of
-// the call's own size, the packing of a chunk of planes into a pinned buffer, and the walk over the chunks of a clip pair.  The
-// device is reached only through callables the caller passes in.  Header-only and plain C++17, as host_pack.h is, so that
-// the CPU harness drives it under ThreadSanitizer / AddressSanitizer (tests/host_harness.cpp); pqa_ctx.h includes it as is.
+// Host side of the staging of the side analyses and plane transforms (pqa_side.hip), free of any device call: how a chunk of
+// frames of the call's own size lies in a pinned buffer, the copy of a caller's frames into it and of results back out, the
+// walk over the chunks of a clip pair (stage_walk) and the walk of a transform (transform_walk).  The device is reached only
+// through callables the caller passes in.  Header-only and plain C++17, as host_pack.h is, so that the CPU harness drives it
+// under ThreadSanitizer / AddressSanitizer (tests/host_harness.cpp); pqa_ctx.h includes it as is.
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -35,31 +36,77 @@ inline PlaneLayout plane_layout(size_t row_bytes, int h) {
   return PlaneLayout{row_bytes, h, pitch, (size_t)pitch * h};
 }
 
-// frames[0 .. n) (rows `stride` bytes apart) into slots 0 .. n - 1 of a pinned buffer
-inline void pack_planes(uint8_t* pin, const PlaneLayout& L, const void* const* frames, int64_t stride, int n) {
-  for (int f = 0; f < n; ++f) copy_plane_rows(pin + (size_t)f * L.frame_bytes, L.pitch, (const uint8_t*)frames[f], stride, L.row_bytes, L.h);
+// One side of a chunk as it is staged: n_planes planes per frame (a packed frame is one "plane" of its minimum row bytes),
+// plane p of frame f at f * frame_bytes + off[p].
+struct ClipLayout {
+  int n_planes = 0;
+  PlaneLayout plane[3] = {};
+  size_t off[3] = {0, 0, 0};
+  size_t frame_bytes = 0;
+};
+// rows row_align bytes apart at least, planes plane_align
+inline ClipLayout clip_layout(int n_planes, const size_t row_bytes[3], const int rows[3], int64_t row_align, int64_t plane_align) {
+  ClipLayout L;
+  L.n_planes = n_planes;
+  size_t off = 0;
+  for (int p = 0; p < n_planes; ++p) {
+    const int64_t pitch = round_up((int64_t)row_bytes[p], row_align);
+    L.plane[p] = PlaneLayout{row_bytes[p], rows[p], pitch, (size_t)pitch * rows[p]};
+    L.off[p] = off;
+    off += (size_t)round_up((int64_t)L.plane[p].frame_bytes, plane_align);
+  }
+  L.frame_bytes = off;
+  return L;
+}
+// one plane a frame, as plane_layout stages it
+inline ClipLayout plane_clip(size_t row_bytes, int h) {
+  ClipLayout L;
+  L.n_planes = 1;
+  L.plane[0] = plane_layout(row_bytes, h);
+  L.frame_bytes = L.plane[0].frame_bytes;
+  return L;
 }
 
-// n_frames planes of `ref` and of `dis` (null: the one-clip form, which leaves pin[1] alone) onto the device in chunks of at
-// most `chunk`, each chunk launched before the next is packed.  For every chunk:
+// frames f0 ... f0 + n - 1 of a caller's clip into slots 0 ... n - 1 of a pinned buffer.  `frames` holds L.n_planes
+// pointers per frame, frame-major; rows strides[p] bytes apart.  Only the L.plane[p].row_bytes bytes of a row that hold
+// samples are read: the caller's last row may end at the end of its allocation.
+inline void pack_clip(uint8_t* pin, const ClipLayout& L, const void* const* frames, const int64_t strides[3], int f0, int n) {
+  for (int f = 0; f < n; ++f)
+    for (int p = 0; p < L.n_planes; ++p)
+      copy_plane_rows(pin + (size_t)f * L.frame_bytes + L.off[p], L.plane[p].pitch,
+                      (const uint8_t*)frames[(size_t)(f0 + f) * L.n_planes + p], strides[p], L.plane[p].row_bytes, L.plane[p].h);
+}
+
+// The way back: slots 0 ... n - 1 of a pinned buffer into a caller's planes (`step` pointers per frame, frame-major, of which
+// the first L.n_planes are written), row by row: the bytes between a destination row's end and the next row stay as they are.
+inline void unpack_clip_out(const uint8_t* pin, const ClipLayout& L, void* const* planes, const int64_t strides[3], int step, int f0, int n) {
+  for (int f = 0; f < n; ++f)
+    for (int p = 0; p < L.n_planes; ++p)
+      for (int y = 0; y < L.plane[p].h; ++y)
+        memcpy((uint8_t*)planes[(size_t)(f0 + f) * step + p] + (int64_t)y * strides[p],
+               pin + (size_t)f * L.frame_bytes + L.off[p] + (size_t)y * L.plane[p].pitch, L.plane[p].row_bytes);
+}
+
+// n_frames frames of `ref` and of `dis` (null: the one-clip form, which leaves pin[1] alone), L.n_planes pointers a frame, onto
+// the device in chunks of at most `chunk`, each chunk launched before the next is packed.  For every chunk:
 //   drain()                      not before the first chunk: the pinned buffers are packed again only after the device has
 //                                read the chunk before (the staging is not pipelined)
-//   pack                         the chunk's planes into slots 0 ... n - 1 of pin[0] (and pin[1])
+//   pack                         the chunk's frames into slots 0 ... n - 1 of pin[0] (and pin[1])
 //   seam(from_slot)              carry 1, not in the first chunk: device slot from_slot moves to device slot 0
-//   upload(slot, n)              the n packed planes to device slots slot ... slot + n - 1
-//   launch(slot, n, out_index)   n planes from device slot `slot` on; the results go `out_index` results into the output
+//   upload(slot, n)              the n packed frames to device slots slot ... slot + n - 1
+//   launch(slot, n, out_index)   n frames from device slot `slot` on; the results go `out_index` results into the output
 // carry 0: a result per frame.  A chunk lands in slots 0 ... n - 1 and its launch writes results f0 ... f0 + n - 1.
 // carry 1: a result per transition from a frame to the next.  The device buffers hold one slot more than a chunk: a chunk lands
-// in slots 1 ... n, and before the next chunk overwrites them its last plane moves to slot 0 (only a full chunk has a
+// in slots 1 ... n, and before the next chunk overwrites them its last frame moves to slot 0 (only a full chunk has a
 // successor, so that is slot `chunk`), where it is the predecessor of the next chunk's first.  So the first launch starts at
-// slot 1 (n planes, n - 1 transitions from transition 0 on) and every later one at slot 0 (n + 1 planes, n transitions from
+// slot 1 (n frames, n - 1 transitions from transition 0 on) and every later one at slot 0 (n + 1 frames, n transitions from
 // f0 - 1 on).
 // Stops at the first callable that returns something other than E{} (success) and returns that; stops before a chunk when
 // `cancelled` is set and returns E{}.
 template <class Drain, class Seam, class Upload, class Launch>
-auto stage_walk(const PlaneLayout& L, uint8_t* const pin[2], const void* const* ref, int64_t ref_stride, const void* const* dis,
-                int64_t dis_stride, int n_frames, int chunk, int carry, const std::atomic<int>& cancelled, Drain drain, Seam seam,
-                Upload upload, Launch launch) -> decltype(drain()) {
+auto stage_walk(const ClipLayout& L, uint8_t* const pin[2], const void* const* ref, const int64_t ref_strides[3],
+                const void* const* dis, const int64_t dis_strides[3], int n_frames, int chunk, int carry,
+                const std::atomic<int>& cancelled, Drain drain, Seam seam, Upload upload, Launch launch) -> decltype(drain()) {
   using E = decltype(drain());
   E e{};
   for (int f0 = 0; f0 < n_frames && e == E{} && !cancelled.load(); f0 += chunk) {
@@ -67,13 +114,42 @@ auto stage_walk(const PlaneLayout& L, uint8_t* const pin[2], const void* const* 
     const int kept = carry && f0 > 0 ? 1 : 0;   // the predecessor from the chunk before
     if (f0 > 0) e = drain();
     if (e != E{}) break;
-    pack_planes(pin[0], L, ref + f0, ref_stride, n);
-    if (dis) pack_planes(pin[1], L, dis + f0, dis_stride, n);
+    pack_clip(pin[0], L, ref, ref_strides, f0, n);
+    if (dis) pack_clip(pin[1], L, dis, dis_strides, f0, n);
     if (kept) e = seam(chunk);
     if (e == E{}) e = upload(carry, n);
     if (e == E{}) e = launch(carry - kept, n + kept, f0 - kept);
   }
   return e;
+}
+
+// A transform: n_frames frames of `src` (layout S) to as many of `dst` (layout D, dst_step pointers a frame), in chunks of at
+// most `chunk`; `aux` (null: none) is a second input a frame, of the source's layout.  A chunk is through before the next is
+// packed.  For every chunk of n frames from f0 on:
+//   pack             the source frames into slots 0 ... n - 1 of pin[0], those of aux behind a whole chunk of them
+//   upload(f0, n)    the packed frames to the device (f0 == 0: whatever else the launches read goes in front)
+//   launch(n)        not after a failed upload
+//   finish(e, n)     ALWAYS, with what upload and launch made of it: brings the n result frames to pin[1] and waits for the
+//                    device, so that nothing still reads or writes the pinned buffers
+//   copy out         the result frames from pin[1] into dst, sample bytes only
+// Stops at the first finish() that returns something other than R{} (success), before the copy out, and returns that.
+template <class Upload, class Launch, class Finish>
+auto transform_walk(const ClipLayout& S, const ClipLayout& D, uint8_t* const pin[2], const void* const* src, const int64_t src_strides[3],
+                    const void* const* aux, const int64_t aux_strides[3], void* const* dst, const int64_t dst_strides[3], int dst_step,
+                    int n_frames, int chunk, Upload upload, Launch launch, Finish finish) -> decltype(finish(upload(0, 0), 0)) {
+  using R = decltype(finish(upload(0, 0), 0));
+  const size_t aux_at = S.frame_bytes * (size_t)(n_frames < chunk ? n_frames : chunk);
+  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+    const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+    pack_clip(pin[0], S, src, src_strides, f0, n);
+    if (aux) pack_clip(pin[0] + aux_at, S, aux, aux_strides, f0, n);
+    auto e = upload(f0, n);
+    if (e == decltype(e){}) e = launch(n);
+    const R rc = finish(e, n);
+    if (rc != R{}) return rc;
+    unpack_clip_out(pin[1], D, dst, dst_strides, dst_step, f0, n);
+  }
+  return R{};
 }
 
 }  // namespace host

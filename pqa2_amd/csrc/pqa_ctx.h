@@ -66,26 +66,26 @@ constexpr int kLumaOutFrames = 2048;  // luma statistics kept on the device betw
 
 // The grow-only device buffers of the side analyses, pqa_ctx::side_buf below (side_reserve, pqa_side.hip).
 enum SideBuf {
-  SIDE_XSSE_PART = 0, SIDE_XSSE_NORM_REF, SIDE_XSSE_NORM_DIS, SIDE_XSSE_OUT,   // pqa_cross_sse[_device], cross_sse.hip
+  // The one pair of staging buffers for host frames of the call's own size (pair_run, transform_run): an analysis uploads a chunk
+  // of reference frames into A and of captured frames into B; a transform uploads a chunk of source frames into A and writes the
+  // result into B (pqa_mask_blend: blends in A, the fill planes lie in B).  Every such entry is synchronous and leaves with the
+  // stream drained, and none reads what a call before it left there, so they all share the pair.
+  SIDE_STAGE_A = 0, SIDE_STAGE_B,
+  SIDE_XSSE_PART, SIDE_XSSE_NORM_REF, SIDE_XSSE_NORM_DIS, SIDE_XSSE_OUT,       // pqa_cross_sse[_device], cross_sse.hip
   SIDE_XSSE_REF, SIDE_XSSE_DIS,                                                // pqa_cross_sse: its two rings of uploaded frames
   SIDE_SHIFT_PART, SIDE_SHIFT_ROWSQ, SIDE_SHIFT_OUT,                           // pqa_shift_sse[_device], shift_sse.hip
   SIDE_LEVEL_OUT,                                                              // pqa_level_stats[_device], level_stats.hip
   SIDE_RS_TABLE0, SIDE_RS_TABLE1, SIDE_RS_TABLE2, SIDE_RS_TABLE3,              // pqa_resample[_device], resample.hip: cached tables
-  SIDE_RS_SRC, SIDE_RS_DST,                                                    // pqa_resample: a chunk of uploaded / resampled planes
-  SIDE_PAIR_REF, SIDE_PAIR_DIS,                                                // the pair staging (pair_run, pqa_side.hip): a chunk of uploaded reference / captured planes of the call's own size
   SIDE_FLOW_OUT,                                                               // pqa_flow_moments[_device], flow_moments.hip: the sums
-  SIDE_COLOUR_A, SIDE_COLOUR_B, SIDE_COLOUR_OUT,                               // pqa_colour_moments / pqa_colour_apply, colour_moments.hip: a chunk of reference / captured (source / result) frames, the sums
-  SIDE_PROF_SRC, SIDE_PROF_OUT,                                                // pqa_line_profiles[_device], line_profiles.hip: a chunk of uploaded planes, the profiles
+  SIDE_COLOUR_OUT,                                                             // pqa_colour_moments[_device], colour_moments.hip: the sums
+  SIDE_PROF_OUT,                                                               // pqa_line_profiles[_device], line_profiles.hip: the profiles
   SIDE_TILE_OUT,                                                               // pqa_tile_moments[_device], tile_moments.hip: the sums
   SIDE_BAND_PART, SIDE_BAND_OUT,                                               // pqa_band_moments[_device], band_moments.hip: the workgroups' partial sums of a chunk, the sums
   SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums
   SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles
-  SIDE_UNPACK_SRC, SIDE_UNPACK_DST,                                            // pqa_unpack, unpack.hip: a chunk of uploaded packed frames / of unpacked planes
-  SIDE_CONVERT_SRC, SIDE_CONVERT_DST,                                          // pqa_format_convert, format_convert.hip: a chunk of uploaded / of converted planes
-  SIDE_TABLE_LUT, SIDE_TABLE_SRC, SIDE_TABLE_DST,                              // pqa_table_apply[_device], table_apply.hip: the table; pqa_table_apply: a chunk of uploaded / of mapped planes
-  SIDE_RGB_SRC, SIDE_RGB_DST,                                                  // pqa_rgb_convert, rgb_convert.hip: a chunk of uploaded packed RGB frames / of converted planes
-  SIDE_ITP_REF, SIDE_ITP_DIS, SIDE_ITP_PART, SIDE_ITP_OUT,                      // pqa_delta_itp[_device], delta_itp.hip: a chunk of uploaded reference / captured frames, the tiles' partial sums of a chunk, the sums
-  SIDE_MASK_NODES, SIDE_MASK_SRC, SIDE_MASK_FILL,                              // pqa_mask_blend[_device], mask_blend.hip: the node grid; pqa_mask_blend: a chunk of uploaded planes (blended where they lie) / of fill planes
+  SIDE_TABLE_LUT,                                                              // pqa_table_apply[_device], table_apply.hip: the table
+  SIDE_ITP_PART, SIDE_ITP_OUT,                                                 // pqa_delta_itp[_device], delta_itp.hip: the tiles' partial sums of a chunk, the sums
+  SIDE_MASK_NODES,                                                             // pqa_mask_blend[_device], mask_blend.hip: the node grid
   kSideBufs
 };
 
@@ -189,9 +189,9 @@ struct pqa_ctx {
   bool temporal_walk = false;        // PQA_TEMPORAL_WALK, read once in pqa_create: 1 takes the walking form of temporal_moments.hip (A/B partner; the same integers)
   pqa::RsCached rs_cache[pqa::kRsCached];   // pqa_resample[_device]: the tables of the last few (filter, geometry, window)
   int rs_next = 0;                          // the slot the next new table replaces
-  uint8_t* side_pin[2] = {nullptr, nullptr};   // the side analyses' two grow-only pinned chunks (side_pin_reserve, pqa_side.hip): the chunk a host entry packs before its upload (pqa_resample, pqa_colour_apply: the second takes the chunk that comes back), of any plane size
+  uint8_t* side_pin[2] = {nullptr, nullptr};   // the side analyses' two grow-only pinned chunks (side_pin_reserve, pqa_side.hip), of any frame size: an analysis packs a chunk of reference frames into the first and of captured frames into the second; a transform packs its source chunk (pqa_mask_blend: the fill planes behind it) into the first and takes the result back through the second
   size_t side_pin_cap[2] = {0, 0};
-  void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use
+  void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use; all host staging shares SIDE_STAGE_A / _B
   size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes
   // motion continuity: the last reference luma of the chain; pqa_set_motion_halo / pqa_set_ref_history arm it
   pqa::HistPlane mo_hist;

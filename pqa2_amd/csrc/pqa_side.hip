@@ -1,9 +1,11 @@
-// The one-shot analyses of the C ABI that leave the scoring chain alone: anchored frame differences, luma statistics,
-// temporal / spatial / level alignment, the resampler, the colour moments and matrix apply, Delta E ITP, and the spec-driven analyses of
-// planes of the call's own size (registration moments, tile / band / temporal moments, edge and line profiles).  Each has an
-// entry for a clip in HBM and one for frames in host memory.  Host frames of the context's size take the luma-halves staging
-// (stage_frames); the spec-driven analyses share one checker and one driver per kind of clip (spec_check, pair_run), whose
-// host side is host_stage.h.  Every entry ends in one epilogue (side_finish).
+// The one-shot analyses and plane transforms of the C ABI that leave the scoring chain alone: anchored frame differences, luma
+// statistics, temporal / spatial / level alignment, the colour moments, Delta E ITP, the spec-driven analyses of planes of the
+// call's own size (registration moments, tile / band / temporal moments, edge and line profiles), and the transforms (resampler,
+// packed unpack, format and RGB converters, table apply, mask blend, colour-matrix apply).  Each has an entry for a clip in HBM
+// and one for frames in host memory.  Host frames of the context's size take the luma-halves staging (stage_frames); frames of
+// the call's own size take one staging path, whose host side is host_stage.h: the analyses share one checker and one driver
+// per kind of clip (spec_check, pair_run), the transforms one driver per kind of clip (transform_run).  Every entry ends in one
+// epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
 
@@ -279,27 +281,84 @@ int spec_check(pqa_ctx* c, const char* who, const Spec* sp, uint32_t min_size, c
   return PQA_OK;
 }
 
-struct HostClip {   // a list of planes in host memory, rows `stride` bytes apart
+struct HostClip {   // a list of frames in host memory, rows of plane p strides[p] bytes apart (one plane: the address of its stride)
   const void* const* at;
-  int64_t stride;
+  const int64_t* strides;
 };
 struct DevClip {   // planes in HBM, pitches in bytes
   const void* at;
   int64_t row_pitch, frame_pitch;
 };
 
+// ---- clips in HBM as the launches take them ---------------------------------------------------------------------------------
+constexpr int kFrameCap = 32768;   // frames per launch of a transform that has no chunk of its own (a dimension of the grid)
+
+pqa_device_clip one_plane(const void* base, int64_t row_pitch, int64_t frame_pitch) {
+  return pqa_device_clip{{base, nullptr, nullptr}, {row_pitch, 0, 0}, {frame_pitch, 0, 0}};
+}
+// a clip from its frame f0 on: every plane advances by its own frame pitch
+pqa_device_clip clip_from(const pqa_device_clip& k, int f0) {
+  pqa_device_clip at = k;
+  for (int p = 0; p < 3; ++p)
+    if (k.plane[p]) at.plane[p] = (const uint8_t*)k.plane[p] + (int64_t)f0 * k.frame_pitch[p];
+  return at;
+}
+// a chunk staged at `base` in layout L
+pqa_device_clip staged_clip(const host::ClipLayout& L, const void* base) {
+  pqa_device_clip k{};
+  for (int p = 0; p < L.n_planes; ++p) {
+    k.plane[p] = (const uint8_t*)base + L.off[p];
+    k.row_pitch[p] = L.plane[p].pitch;
+    k.frame_pitch[p] = (int64_t)L.frame_bytes;
+  }
+  return k;
+}
+// PlaneRun[3] or MutPlaneRun[3] (pitches in samples of es bytes) of a clip from its frame f0 on
+template <class Run>
+void plane_runs(const pqa_device_clip& k, int f0, int es, Run run[3]) {
+  const pqa_device_clip at = clip_from(k, f0);
+  for (int p = 0; p < 3; ++p) run[p] = Run{const_cast<void*>(at.plane[p]), at.row_pitch[p] / es, at.frame_pitch[p] / es};
+}
+// launch(f0, n) over n_frames frames in runs of at most cap: stops at the first error and, where `stop` is given, before a run once it is set
+template <class Launch>
+hipError_t launch_runs(int n_frames, int cap, const std::atomic<int>* stop, Launch launch) {
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !(stop && stop->load()); f0 += cap) e = launch(f0, chunk_len(n_frames, f0, cap));
+  return e;
+}
+// A plane in HBM of samples of es bytes (not always the context's): its base and both pitches are whole samples.
+bool whole_samples(const void* base, int64_t row_pitch, int64_t frame_pitch, int es) {
+  return !(((uintptr_t)base | (uintptr_t)row_pitch | (uintptr_t)frame_pitch) & (uintptr_t)(es - 1));
+}
+// The rules of the planes of pqa_format_convert_device, pqa_table_apply_device and pqa_mask_blend_device, in their order: every
+// plane is whole samples, then every row pitch holds a row.
+struct DevPlane {
+  const char* kind;   // "source", "destination", "fill"
+  const void* base;
+  int64_t row_pitch, frame_pitch, row_bytes;
+  int es;
+};
+int check_device_planes(pqa_ctx* c, const char* who, std::initializer_list<DevPlane> planes) {
+  for (const DevPlane& p : planes)
+    if (!whole_samples(p.base, p.row_pitch, p.frame_pitch, p.es))
+      return fail(c, PQA_EINVAL, "%s: %s base or pitch is not a multiple of the sample size", who, p.kind);
+  for (const DevPlane& p : planes)
+    if (p.row_pitch < p.row_bytes) return fail(c, PQA_EINVAL, "%s: %s pitch smaller than a row", who, p.kind);
+  return PQA_OK;
+}
+
 // What an analysis asks of a driver.  carry 0: a result per frame.  carry 1 (pqa_temporal_moments): a result per transition,
 // so a launch also reads the frame in front of its first transition, and fewer than two frames are no work.
 struct PairJob {
   const char* who;   // opens every message
-  int w, h;
+  host::ClipLayout L;   // a frame as the host entry stages it: one plane, or three (pqa_colour_moments, pqa_delta_itp)
   int32_t n_frames;
   int chunk, carry;   // chunk: results per launch
   SideBuf out_buf;
   size_t out_bytes;   // of all results: they come back once
   void* out;
   bool whole_samples = true;       // host frames: refuse a stride that is no multiple of the sample size
-  SideBuf part_buf = kSideBufs;    // a workspace of part_bytes that the launches share (pqa_band_moments)
+  SideBuf part_buf = kSideBufs;    // a workspace of part_bytes that the launches share (pqa_band_moments, pqa_delta_itp)
   size_t part_bytes = 0;
 };
 
@@ -308,16 +367,33 @@ int job_reserve(pqa_ctx* c, const PairJob& j) {
   return rc == PQA_OK ? side_reserve(c, j.out_buf, j.out_bytes) : rc;
 }
 
-// Clips in HBM (dis null: one clip).  launch(ref run, dis run, n frames, index of the first result) queues a kernel.
+// Three-plane clips in HBM, after the entry's own rules.  launch(ref runs, dis runs, n frames, index of the first result) queues
+// a kernel; `stop`: launch_runs.
+template <class Launch>
+int pair_run(pqa_ctx* c, const PairJob& j, const pqa_device_clip& ref, const pqa_device_clip& dis, const std::atomic<int>* stop, Launch launch) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = job_reserve(c, j);
+  if (rc != PQA_OK) return rc;
+  const hipError_t e = launch_runs(j.n_frames, j.chunk, stop, [&](int f0, int n) {
+    PlaneRun r[3], d[3];
+    plane_runs(ref, f0, c->esize, r);
+    plane_runs(dis, f0, c->esize, d);
+    return launch(r, d, n, f0);
+  });
+  return side_finish(c, j.who, e, j.out, c->side_buf[j.out_buf], j.out_bytes);
+}
+
+// One-plane clips in HBM (dis null: one clip), with their rules.
 template <class Launch>
 int pair_run(pqa_ctx* c, const PairJob& j, const DevClip& ref, const DevClip* dis, Launch launch) {
   const int es = c->esize;
+  const int64_t row_bytes = (int64_t)j.L.plane[0].row_bytes;
   char who[48];
   snprintf(who, sizeof who, dis ? "%s: reference " : "%s: ", j.who);
-  int rc = check_device_clip(c, who, ref.row_pitch, ref.frame_pitch, (int64_t)j.w * es);
+  int rc = check_device_clip(c, who, ref.row_pitch, ref.frame_pitch, row_bytes);
   if (rc == PQA_OK && dis) {
     snprintf(who, sizeof who, "%s: captured ", j.who);
-    rc = check_device_clip(c, who, dis->row_pitch, dis->frame_pitch, (int64_t)j.w * es);
+    rc = check_device_clip(c, who, dis->row_pitch, dis->frame_pitch, row_bytes);
   }
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
@@ -325,45 +401,45 @@ int pair_run(pqa_ctx* c, const PairJob& j, const DevClip& ref, const DevClip* di
   HIPCHK(c, hipSetDevice(c->device));
   rc = job_reserve(c, j);
   if (rc != PQA_OK) return rc;
-  const auto run = [&](const DevClip* k, int f0) {
-    return k ? PlaneRun{(const uint8_t*)k->at + (int64_t)f0 * k->frame_pitch, k->row_pitch / es, k->frame_pitch / es} : PlaneRun{};
-  };
   const int results = j.n_frames - j.carry;
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < results && e == hipSuccess; f0 += j.chunk)   // the launches share what they share in stream order
-    e = launch(run(&ref, f0), run(dis, f0), chunk_len(results, f0, j.chunk) + j.carry, f0);
+  const hipError_t e = launch_runs(results, j.chunk, nullptr, [&](int f0, int n) {   // the launches share what they share in stream order
+    PlaneRun r[3] = {}, d[3] = {};
+    plane_runs(one_plane(ref.at, ref.row_pitch, ref.frame_pitch), f0, es, r);
+    if (dis) plane_runs(one_plane(dis->at, dis->row_pitch, dis->frame_pitch), f0, es, d);
+    return launch(r, d, n + j.carry, f0);
+  });
   return side_finish(c, j.who, e, j.out, c->side_buf[j.out_buf], j.out_bytes);
 }
 
-// Host frames (dis null: one clip).  The planes are the call's own size, so they travel in chunks through the two grow-only
-// pinned chunks (the reference planes through the first, the captured ones through the second) into the pair staging's two
-// device buffers -- one clip: through the first into SIDE_PROF_SRC -- as host_stage.h lays out: packed rows, a chunk
-// launched before the next is packed, with carry 1 the last pair of a chunk kept as predecessor of the next.  Every entry
-// here is synchronous, so no two calls are ever in flight in these buffers.  Every launch writes its results behind the
-// previous one's; they come back once.
+// Host frames (dis null: one clip), with their rules.  The frames are the call's own size, so they travel in chunks through the
+// two grow-only pinned chunks (the reference frames through the first, the captured ones through the second) into the two
+// staging buffers (SIDE_STAGE_A, SIDE_STAGE_B) as host_stage.h lays out: packed rows, a chunk launched before the next is
+// packed, with carry 1 the last pair of a chunk kept as predecessor of the next.  Every entry here is synchronous, so no two
+// calls are ever in flight in these buffers, and no call reads what another left there.  Every launch writes its results
+// behind the previous one's; they come back once.
 template <class Launch>
 int pair_run(pqa_ctx* c, const PairJob& j, const HostClip& ref, const HostClip* dis, Launch launch) {
-  const int es = c->esize;
-  const host::PlaneLayout L = host::plane_layout((size_t)j.w * es, j.h);
+  const int es = c->esize, np = j.L.n_planes;
   char who[48];
   snprintf(who, sizeof who, "%s: ", j.who);
-  int rc = check_host_frames(c, who, dis ? "reference " : "", ref.at, 1, j.n_frames, ref.stride, L.row_bytes, true);
-  if (rc == PQA_OK && dis) rc = check_host_frames(c, who, "captured ", dis->at, 1, j.n_frames, dis->stride, L.row_bytes, true);
+  int rc = PQA_OK;
+  for (const HostClip* k : {&ref, dis})
+    for (int p = 0; k && p < np && rc == PQA_OK; ++p)
+      rc = check_host_frames(c, who, !dis ? "" : k == &ref ? "reference " : "captured ", k->at + p, np, j.n_frames, k->strides[p], j.L.plane[p].row_bytes, true);
   if (rc != PQA_OK) return rc;
-  if (j.whole_samples && j.n_frames > 0 && (ref.stride % es || (dis && dis->stride % es)))
+  if (j.whole_samples && j.n_frames > 0 && (ref.strides[0] % es || (dis && dis->strides[0] % es)))
     return fail(c, PQA_EINVAL, "%s: stride is not a multiple of the sample size", j.who);
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (j.n_frames <= j.carry) return PQA_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t fb = L.frame_bytes, slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk);
-  const SideBuf ref_buf = dis ? SIDE_PAIR_REF : SIDE_PROF_SRC;
+  const size_t fb = j.L.frame_bytes, slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk);
   rc = side_pin_reserve(c, 0, fb * slots);
   if (rc == PQA_OK && dis) rc = side_pin_reserve(c, 1, fb * slots);
-  if (rc == PQA_OK) rc = side_reserve(c, ref_buf, fb * (slots + j.carry));
-  if (rc == PQA_OK && dis) rc = side_reserve(c, SIDE_PAIR_DIS, fb * (slots + j.carry));
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_STAGE_A, fb * (slots + j.carry));
+  if (rc == PQA_OK && dis) rc = side_reserve(c, SIDE_STAGE_B, fb * (slots + j.carry));
   if (rc == PQA_OK) rc = job_reserve(c, j);
   if (rc != PQA_OK) return rc;
-  uint8_t* const dev[2] = {(uint8_t*)c->side_buf[ref_buf], dis ? (uint8_t*)c->side_buf[SIDE_PAIR_DIS] : nullptr};
+  uint8_t* const dev[2] = {(uint8_t*)c->side_buf[SIDE_STAGE_A], dis ? (uint8_t*)c->side_buf[SIDE_STAGE_B] : nullptr};
   const int clips = dis ? 2 : 1;
   const auto copy = [&](int to_slot, const uint8_t* const from[2], size_t from_off, size_t bytes, hipMemcpyKind kind) {
     hipError_t e = hipSuccess;
@@ -372,20 +448,22 @@ int pair_run(pqa_ctx* c, const PairJob& j, const HostClip& ref, const HostClip* 
     return e;
   };
   const hipError_t e = host::stage_walk(
-      L, c->side_pin, ref.at, ref.stride, dis ? dis->at : nullptr, dis ? dis->stride : 0, j.n_frames, j.chunk, j.carry, c->cancelled,
+      j.L, c->side_pin, ref.at, ref.strides, dis ? dis->at : nullptr, dis ? dis->strides : nullptr, j.n_frames, j.chunk, j.carry, c->cancelled,
       [&] { return hipStreamSynchronize(c->stream); },
       [&](int from_slot) { return copy(0, dev, (size_t)from_slot * fb, fb, hipMemcpyDeviceToDevice); },   // from_slot >= 1: no overlap
       [&](int slot, int n) { return copy(slot, c->side_pin, 0, fb * n, hipMemcpyHostToDevice); },
       [&](int slot, int n, int out_index) {
-        const auto run = [&](uint8_t* base) { return PlaneRun{base ? base + (size_t)slot * fb : nullptr, L.pitch / es, (int64_t)(fb / es)}; };
-        return launch(run(dev[0]), run(dev[1]), n, out_index);
+        PlaneRun r[3] = {}, d[3] = {};
+        plane_runs(staged_clip(j.L, dev[0]), slot, es, r);
+        if (dis) plane_runs(staged_clip(j.L, dev[1]), slot, es, d);
+        return launch(r, d, n, out_index);
       });
   return side_finish(c, j.who, e, j.out, c->side_buf[j.out_buf], j.out_bytes);
 }
 
 // ---- the spec-driven analyses (spec_check, pair_run above) ----------------------------------------------------------------
 // Clip is HostClip or DevClip: both entries of an analysis are one body, which checks, sizes its results and names its launch.
-// A launch's results lie `at` results into the analysis' output buffer.
+// A launch's results lie `at` results into the analysis' output buffer; r and d are its runs of planes (the first of three).
 
 // registration moments (flow_moments.hip); this one lets a stride that is no multiple of the sample size pass
 template <class Clip>
@@ -396,10 +474,10 @@ int flow_moments(pqa_ctx* c, const pqa_flow_spec* sp, const Clip& ref, const Cli
   if (rc != PQA_OK) return rc;
   const int w = (int)sp->width, h = (int)sp->height, tile = (int)sp->tile;
   const size_t per_frame = flow_out_bytes(w, h, tile, 1) / sizeof(long long);
-  const PairJob j{"flow_moments", w, h, n_frames, kFlowChunk, 0, SIDE_FLOW_OUT, flow_out_bytes(w, h, tile, n_frames), out, false};
-  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
-    return launch_flow_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
-                               d.frame_pitch, n, w, h, tile, (long long*)c->side_buf[SIDE_FLOW_OUT] + (size_t)at * per_frame);
+  const PairJob j{"flow_moments", host::plane_clip((size_t)w * c->esize, h), n_frames, kFlowChunk, 0, SIDE_FLOW_OUT, flow_out_bytes(w, h, tile, n_frames), out, false};
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_flow_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch,
+                               d->frame_pitch, n, w, h, tile, (long long*)c->side_buf[SIDE_FLOW_OUT] + (size_t)at * per_frame);
   });
 }
 
@@ -412,10 +490,10 @@ int tile_moments(pqa_ctx* c, const pqa_tile_spec* sp, const Clip& ref, const Cli
   if (rc != PQA_OK) return rc;
   const int w = (int)sp->width, h = (int)sp->height, tile = (int)sp->tile;
   const size_t per_frame = tile_out_bytes(w, h, tile, 1) / sizeof(uint64_t);
-  const PairJob j{"tile_moments", w, h, n_frames, kTileChunk, 0, SIDE_TILE_OUT, tile_out_bytes(w, h, tile, n_frames), out};
-  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
-    return launch_tile_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
-                               d.frame_pitch, n, w, h, tile, (unsigned long long*)c->side_buf[SIDE_TILE_OUT] + (size_t)at * per_frame);
+  const PairJob j{"tile_moments", host::plane_clip((size_t)w * c->esize, h), n_frames, kTileChunk, 0, SIDE_TILE_OUT, tile_out_bytes(w, h, tile, n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_tile_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch,
+                               d->frame_pitch, n, w, h, tile, (unsigned long long*)c->side_buf[SIDE_TILE_OUT] + (size_t)at * per_frame);
   });
 }
 
@@ -428,11 +506,11 @@ int band_moments(pqa_ctx* c, const pqa_band_spec* sp, const Clip& ref, const Cli
   if (rc != PQA_OK) return rc;
   const int w = (int)sp->width, h = (int)sp->height, levels = (int)sp->levels;
   const size_t per_frame = band_out_bytes(levels, 1) / sizeof(uint64_t);
-  const PairJob j{"band_moments", w, h, n_frames, kBandChunk, 0, SIDE_BAND_OUT, band_out_bytes(levels, n_frames), out, true, SIDE_BAND_PART,
+  const PairJob j{"band_moments", host::plane_clip((size_t)w * c->esize, h), n_frames, kBandChunk, 0, SIDE_BAND_OUT, band_out_bytes(levels, n_frames), out, true, SIDE_BAND_PART,
                   band_part_bytes(w, h, levels, n_frames < kBandChunk ? n_frames : kBandChunk)};
-  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
-    return launch_band_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
-                               d.frame_pitch, n, w, h, levels, c->side_buf[SIDE_BAND_PART],
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_band_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch,
+                               d->frame_pitch, n, w, h, levels, c->side_buf[SIDE_BAND_PART],
                                (unsigned long long*)c->side_buf[SIDE_BAND_OUT] + (size_t)at * per_frame);
   });
 }
@@ -446,10 +524,10 @@ int temporal_moments(pqa_ctx* c, const pqa_temporal_spec* sp, const Clip& ref, c
   if (rc != PQA_OK) return rc;
   const int w = (int)sp->width, h = (int)sp->height, tile = (int)sp->tile;
   const size_t per_transition = temporal_out_bytes(w, h, tile, 2) / sizeof(uint64_t);
-  const PairJob j{"temporal_moments", w, h, n_frames, kTemporalChunk, 1, SIDE_TEMPORAL_OUT, temporal_out_bytes(w, h, tile, n_frames), out};
-  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
-    return launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
-                                   d.frame_pitch, n, w, h, tile, c->temporal_walk,
+  const PairJob j{"temporal_moments", host::plane_clip((size_t)w * c->esize, h), n_frames, kTemporalChunk, 1, SIDE_TEMPORAL_OUT, temporal_out_bytes(w, h, tile, n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_temporal_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch,
+                                   d->frame_pitch, n, w, h, tile, c->temporal_walk,
                                    (unsigned long long*)c->side_buf[SIDE_TEMPORAL_OUT] + (size_t)at * per_transition);
   });
 }
@@ -461,10 +539,10 @@ int edge_profiles(pqa_ctx* c, const pqa_edge_spec* sp, const Clip& ref, const Cl
   if (rc != PQA_OK) return rc;
   const int w = (int)sp->width, h = (int)sp->height;
   const size_t per_frame = edge_out_bytes(w, h, 1) / sizeof(uint64_t);
-  const PairJob j{"edge_profiles", w, h, n_frames, kEdgeChunk, 0, SIDE_EDGE_OUT, edge_out_bytes(w, h, n_frames), out};
-  return pair_run(c, j, ref, &dis, [&](PlaneRun r, PlaneRun d, int n, int at) {
-    return launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, d.base, d.row_pitch,
-                                d.frame_pitch, n, w, h, (unsigned long long*)c->side_buf[SIDE_EDGE_OUT] + (size_t)at * per_frame);
+  const PairJob j{"edge_profiles", host::plane_clip((size_t)w * c->esize, h), n_frames, kEdgeChunk, 0, SIDE_EDGE_OUT, edge_out_bytes(w, h, n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_edge_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch,
+                                d->frame_pitch, n, w, h, (unsigned long long*)c->side_buf[SIDE_EDGE_OUT] + (size_t)at * per_frame);
   });
 }
 
@@ -475,9 +553,9 @@ int line_profiles(pqa_ctx* c, const pqa_profile_spec* sp, const Clip& planes, in
   if (rc != PQA_OK) return rc;
   const int w = (int)sp->width, h = (int)sp->height;
   const size_t per_frame = profile_out_bytes(w, h, 1) / sizeof(uint64_t);
-  const PairJob j{"line_profiles", w, h, n_frames, kProfChunk, 0, SIDE_PROF_OUT, profile_out_bytes(w, h, n_frames), out, false};
-  return pair_run(c, j, planes, (const Clip*)nullptr, [&](PlaneRun r, PlaneRun, int n, int at) {
-    return launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, r.base, r.row_pitch, r.frame_pitch, n, w, h,
+  const PairJob j{"line_profiles", host::plane_clip((size_t)w * c->esize, h), n_frames, kProfChunk, 0, SIDE_PROF_OUT, profile_out_bytes(w, h, n_frames), out, false};
+  return pair_run(c, j, planes, (const Clip*)nullptr, [&](const PlaneRun* r, const PlaneRun*, int n, int at) {
+    return launch_line_profiles(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, n, w, h,
                                 (unsigned long long*)c->side_buf[SIDE_PROF_OUT] + (size_t)at * per_frame);
   });
 }
@@ -508,29 +586,350 @@ int cl_check_host(pqa_ctx* c, const char* who, const char* kind, const void* con
   return PQA_OK;
 }
 
-// A frame as the host entries stage it: plane p at off[p] with rows pitch[p] bytes apart, `bytes` in all; every offset and
-// pitch is a multiple of 16 bytes, so the kernels take their wide loads.
-struct ClLayout {
-  size_t off[3], bytes;
-  int64_t pitch[3];
+// A three-plane frame of the context's size as the host entries stage it: rows 16 bytes apart at least and planes 256, so the
+// kernels take their wide loads.
+host::ClipLayout cl_frame(const pqa_ctx* c) {
+  const size_t rb[3] = {(size_t)c->pw[0] * c->esize, (size_t)c->pw[1] * c->esize, (size_t)c->pw[2] * c->esize};
+  return host::clip_layout(3, rb, c->ph, 16, 256);
+}
+
+// ---- the plane transforms: n frames of a source clip to n frames of a destination clip ----------------------------------------
+// pqa_resample, pqa_unpack, pqa_format_convert, pqa_rgb_convert, pqa_table_apply, pqa_mask_blend and pqa_colour_apply differ in
+// their rules, their layouts and their launch; one driver for clips in HBM and one for host frames, which an entry reaches
+// after its rules.  front() queues what the launches read besides the frames (a table, a node grid) in front of the first;
+// launch(source, second input, destination, n frames) queues a kernel on clips in HBM (pitches in bytes).
+struct TransformJob {
+  const char* who;
+  int32_t n_frames;
+  int cap, chunk;                  // frames per launch of clips in HBM; host frames per chunk
+  host::ClipLayout S, D;           // host frames: a source and a destination frame as they are staged
+  int dst_step = 1;                // host frames: pointers per destination frame
+  bool in_place = false;           // host frames: the launch leaves the result where the source was uploaded (pqa_mask_blend)
+  SideBuf side_buf = kSideBufs;    // what front() uploads into, of side_bytes
+  size_t side_bytes = 0;
 };
-ClLayout cl_layout(const pqa_ctx* c) {
-  ClLayout L{};
-  for (int p = 0; p < 3; ++p) {
-    L.off[p] = L.bytes;
-    L.pitch[p] = round_up((int64_t)c->pw[p] * c->esize, 16);
-    L.bytes += (size_t)round_up(L.pitch[p] * c->ph[p], 256);
+const auto no_front = [] { return hipSuccess; };
+
+template <class Front, class Launch>
+int transform_run(pqa_ctx* c, const TransformJob& j, const pqa_device_clip& src, const pqa_device_clip* aux, const pqa_device_clip& dst,
+                  Front front, Launch launch) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = j.side_buf != kSideBufs ? side_reserve(c, j.side_buf, j.side_bytes) : PQA_OK;
+  if (rc != PQA_OK) return rc;
+  hipError_t e = front();
+  if (e == hipSuccess)
+    e = launch_runs(j.n_frames, j.cap, nullptr, [&](int f0, int n) {
+      return launch(clip_from(src, f0), aux ? clip_from(*aux, f0) : pqa_device_clip{}, clip_from(dst, f0), n);
+    });
+  return side_finish(c, j.who, e, nullptr, nullptr, 0);
+}
+
+// Host frames travel as host::transform_walk lays out: a chunk goes out through the first of the side analyses' two pinned
+// chunks into SIDE_STAGE_A (a second input behind it, into SIDE_STAGE_B), the launch writes SIDE_STAGE_B (in_place: blends
+// where the source lies; a second input needs that), and the result comes back through the second pinned chunk and is copied
+// out before the next chunk is packed: one side_finish per chunk.  Rows lie 16 bytes apart at least, so the kernels' wide
+// paths apply.  Nothing in the staging buffers outlives the call.
+template <class Front, class Launch>
+int transform_run(pqa_ctx* c, const TransformJob& j, const HostClip& src, const HostClip* aux, const HostClip& dst, Front front, Launch launch) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk), sb = j.S.frame_bytes * slots, db = j.D.frame_bytes * slots;
+  int rc = side_pin_reserve(c, 0, sb * (aux ? 2 : 1));
+  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, db);
+  if (rc == PQA_OK && j.side_buf != kSideBufs) rc = side_reserve(c, j.side_buf, j.side_bytes);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_STAGE_A, sb);
+  if (rc == PQA_OK && (aux || !j.in_place)) rc = side_reserve(c, SIDE_STAGE_B, aux ? sb : db);
+  if (rc != PQA_OK) return rc;
+  void* const a = c->side_buf[SIDE_STAGE_A];
+  void* const b = c->side_buf[SIDE_STAGE_B];
+  const pqa_device_clip s = staged_clip(j.S, a), x = aux ? staged_clip(j.S, b) : pqa_device_clip{}, d = staged_clip(j.D, j.in_place ? a : b);
+  return host::transform_walk(
+      j.S, j.D, c->side_pin, src.at, src.strides, aux ? aux->at : nullptr, aux ? aux->strides : nullptr, (void* const*)dst.at, dst.strides,
+      j.dst_step, j.n_frames, j.chunk,
+      [&](int f0, int n) {
+        hipError_t e = f0 == 0 ? front() : hipSuccess;
+        if (e == hipSuccess) e = hipMemcpyAsync(a, c->side_pin[0], j.S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && aux) e = hipMemcpyAsync(b, c->side_pin[0] + sb, j.S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+        return e;
+      },
+      [&](int n) { return launch(s, x, d, n); },
+      [&](hipError_t e, int n) { return side_finish(c, j.who, e, c->side_pin[1], d.plane[0], j.D.frame_bytes * n); });
+}
+
+// The destination rules that pqa_unpack[_device] and pqa_rgb_convert[_device] share, after `cancelled` (no device call).  A
+// destination has a luma plane of w samples a row and, or not, two chroma planes of cw; samples of es bytes.  aligned: the name
+// of a format whose source must lie on 4 bytes ("v210", "r210"), or null.  *np: 1 or 3.
+int packed_dst_check(pqa_ctx* c, const char* who, const char* aligned, const void* src, const pqa_device_clip* dst, int es, int w, int cw, int* np) {
+  if (!dst->plane[0]) return fail(c, PQA_EINVAL, "%s: null luma destination", who);
+  if (!dst->plane[1] != !dst->plane[2]) return fail(c, PQA_EINVAL, "%s: chroma destinations: both or neither", who);
+  if (aligned && ((uintptr_t)src & 3)) return fail(c, PQA_EINVAL, "%s: %s source is not 4-byte aligned", who, aligned);
+  *np = dst->plane[1] ? 3 : 1;
+  for (int p = 0; p < *np; ++p) {
+    if (!whole_samples(dst->plane[p], dst->row_pitch[p], dst->frame_pitch[p], es))
+      return fail(c, PQA_EINVAL, "%s: plane %d destination is not made of whole samples", who, p);
+    if (dst->row_pitch[p] < (int64_t)(p ? cw : w) * es) return fail(c, PQA_EINVAL, "%s: plane %d destination pitch smaller than a row", who, p);
   }
-  return L;
+  return PQA_OK;
 }
-void cl_runs(const pqa_ctx* c, const ClLayout& L, const void* base, PlaneRun run[3]) {
-  for (int p = 0; p < 3; ++p) run[p] = PlaneRun{(const uint8_t*)base + L.off[p], L.pitch[p] / c->esize, (int64_t)(L.bytes / c->esize)};
+// whole_strides: refuse a destination stride that is not whole samples (pqa_rgb_convert does, pqa_unpack does not)
+int packed_dst_check(pqa_ctx* c, const char* who, const char* aligned, const void* const* src_frames, void* const* dst_planes,
+                     const int64_t dst_strides[3], int32_t n_frames, int es, int w, int cw, bool whole_strides, int* np) {
+  if (!dst_strides) return fail(c, PQA_EINVAL, "%s: null destination strides", who);
+  *np = dst_planes[1] && dst_planes[2] ? 3 : 1;
+  if (*np == 1 && (dst_planes[1] || dst_planes[2])) return fail(c, PQA_EINVAL, "%s: chroma destinations: both or neither", who);
+  for (int f = 0; f < n_frames; ++f) {   // before anything is queued
+    if (!src_frames[f]) return fail(c, PQA_EINVAL, "%s: source frame %d pointer is null", who, f);
+    if (aligned && ((uintptr_t)src_frames[f] & 3)) return fail(c, PQA_EINVAL, "%s: %s source frame %d is not 4-byte aligned", who, aligned, f);
+    for (int p = 0; p < *np; ++p)
+      if (!dst_planes[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "%s: destination plane %d of frame %d is null", who, p, f);
+  }
+  for (int p = 0; p < *np; ++p) {
+    if (whole_strides && (dst_strides[p] & (int64_t)(es - 1))) return fail(c, PQA_EINVAL, "%s: plane %d destination is not made of whole samples", who, p);
+    if (dst_strides[p] < (int64_t)(p ? cw : w) * es) return fail(c, PQA_EINVAL, "%s: plane %d destination stride smaller than a row", who, p);
+  }
+  return PQA_OK;
 }
-void cl_pack(const pqa_ctx* c, const ClLayout& L, uint8_t* pin, const void* const* frames, const int64_t strides[3], int n) {
-  for (int f = 0; f < n; ++f)
-    for (int p = 0; p < 3; ++p)
-      copy_plane_rows(pin + (size_t)f * L.bytes + L.off[p], L.pitch[p], (const uint8_t*)frames[(size_t)f * 3 + p], strides[p],
-                      (size_t)c->pw[p] * c->esize, c->ph[p]);
+
+// ---- the transforms and the three-plane analyses: the rules an entry pair shares and one body for both (entries below) ------------
+
+// resampler (resample.hip).  A source plane may be larger than the context's, so host frames cannot take the luma halves.
+template <class Clip>
+int resample_run(pqa_ctx* c, const pqa_resample_spec* sp, int slot, const Clip& src, const Clip& dst, int32_t n_frames) {
+  const int es = c->esize, sw = (int)sp->src_width, sh = (int)sp->src_height, dw = (int)sp->dst_width, dh = (int)sp->dst_height;
+  const TransformJob j{"resample", n_frames, kRsChunk, kRsChunk, host::plane_clip((size_t)sw * es, sh), host::plane_clip((size_t)dw * es, dh)};
+  return transform_run(c, j, src, nullptr, dst, no_front, [&](const pqa_device_clip& s, const pqa_device_clip&, const pqa_device_clip& d, int n) {
+    return launch_resample(c->stream, c->elem, (int)c->cfg.bit_depth, c->rs_cache[slot].plan, (const int*)c->side_buf[SIDE_RS_TABLE0 + slot],
+                           s.plane[0], s.row_pitch[0] / es, s.frame_pitch[0] / es, sw, sh, const_cast<void*>(d.plane[0]), d.row_pitch[0] / es,
+                           d.frame_pitch[0] / es, dw, dh, n);
+  });
+}
+
+// The argument rules both entries share, in spec_check's order (no device call); then the rows of the packed source.
+int unpack_check(pqa_ctx* c, const pqa_unpack_spec* sp, const void* src, const void* dst, int32_t n_frames, int64_t src_row,
+                 int64_t src_frame) {
+  const int rc = spec_check(c, "unpack", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    return host::packed_format(sp->format) ? PQA_OK : fail(c, PQA_EINVAL, "unpack: format %u is not a packed capture format (UYVY 3, YUYV 4, V210 5)", sp->format);
+  });
+  if (rc != PQA_OK || n_frames == 0) return rc;
+  const int64_t min_row = host::packed_min_row_bytes(sp->format, (int)sp->width);
+  if (src_row < min_row)
+    return fail(c, PQA_EINVAL, "unpack: source pitch %lld is smaller than a packed row of %lld bytes", (long long)src_row, (long long)min_row);
+  if (sp->format == PQA_SURFACE_V210 && ((src_row | src_frame) & 3)) return fail(c, PQA_EINVAL, "unpack: v210 pitch is not a multiple of 4");
+  return PQA_OK;
+}
+
+// np: the planes of the destination, 1 or 3
+template <class Clip>
+int unpack_run(pqa_ctx* c, const pqa_unpack_spec* sp, int np, const Clip& src, const Clip& dst, int32_t n_frames) {
+  const int w = (int)sp->width, h = (int)sp->height;
+  const TransformJob j{"unpack", n_frames, kFrameCap, kRsChunk, host::packed_layout(sp->format, w, h), host::unpacked_layout(sp->format, w, h, np), 3};
+  return transform_run(c, j, src, nullptr, dst, no_front, [&](const pqa_device_clip& s, const pqa_device_clip&, const pqa_device_clip& d, int n) {
+    void* const at[3] = {const_cast<void*>(d.plane[0]), const_cast<void*>(d.plane[1]), const_cast<void*>(d.plane[2])};
+    return launch_unpack(c->stream, (int)sp->format, s.plane[0], s.row_pitch[0], s.frame_pitch[0], at, d.row_pitch, d.frame_pitch, w, h, n);
+  });
+}
+
+// The argument rules both entries share, in spec_check's order (no device call).
+int convert_check(pqa_ctx* c, const pqa_convert_spec* sp, const void* src, const void* dst, int32_t n_frames) {
+  return spec_check(c, "format_convert", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (sp->flags & ~(uint32_t)PQA_CONVERT_GENERIC) return fail(c, PQA_EINVAL, "format_convert: unknown flag bits %#x", sp->flags);
+    for (uint32_t b : {sp->src_bits, sp->dst_bits})
+      if (b != 8 && b != 10 && b != 12) return fail(c, PQA_EINVAL, "format_convert: bit depth %u is not 8, 10 or 12", b);
+    for (uint8_t s : {sp->src_hshift, sp->src_vshift, sp->dst_hshift, sp->dst_vshift})
+      if (s > 2) return fail(c, PQA_EINVAL, "format_convert: chroma shift %u outside 0 ... 2", (unsigned)s);
+    for (uint8_t s : {sp->src_hsite, sp->src_vsite, sp->dst_hsite, sp->dst_vsite})
+      if (s != PQA_SITE_COSITED && s != PQA_SITE_CENTRE) return fail(c, PQA_EINVAL, "format_convert: siting %u is not PQA_SITE_COSITED or _CENTRE", (unsigned)s);
+    return (int)PQA_OK;
+  });
+}
+ConvertLayout convert_side(const pqa_convert_spec* sp, bool dst) {
+  return dst ? ConvertLayout{(int)sp->dst_bits, sp->dst_hshift, sp->dst_vshift, sp->dst_hsite, sp->dst_vsite}
+             : ConvertLayout{(int)sp->src_bits, sp->src_hshift, sp->src_vshift, sp->src_hsite, sp->src_vsite};
+}
+
+struct ConvertPlanes {   // the source and the destination plane of a spec: layouts, bytes of a row, rows
+  ConvertLayout S, D;
+  size_t src_row, dst_row;
+  int src_h, dst_h;
+};
+ConvertPlanes convert_planes(const pqa_convert_spec* sp) {
+  const ConvertLayout S = convert_side(sp, false), D = convert_side(sp, true);
+  const int lw = (int)sp->luma_width, lh = (int)sp->luma_height;
+  return ConvertPlanes{S, D, (size_t)convert_plane_size(lw, S.hshift) * (S.bits > 8 ? 2 : 1), (size_t)convert_plane_size(lw, D.hshift) * (D.bits > 8 ? 2 : 1),
+                       convert_plane_size(lh, S.vshift), convert_plane_size(lh, D.vshift)};
+}
+template <class Clip>
+int convert_run(pqa_ctx* c, const pqa_convert_spec* sp, const ConvertPlanes& P, const Clip& src, const Clip& dst, int32_t n_frames) {
+  const TransformJob j{"format_convert", n_frames, kFrameCap, kConvertChunk, host::plane_clip(P.src_row, P.src_h), host::plane_clip(P.dst_row, P.dst_h)};
+  return transform_run(c, j, src, nullptr, dst, no_front, [&](const pqa_device_clip& s, const pqa_device_clip&, const pqa_device_clip& d, int n) {
+    return launch_format_convert(c->stream, P.S, P.D, (int)sp->luma_width, (int)sp->luma_height, (sp->flags & PQA_CONVERT_GENERIC) != 0, s.plane[0],
+                                 s.row_pitch[0], s.frame_pitch[0], const_cast<void*>(d.plane[0]), d.row_pitch[0], d.frame_pitch[0], n);
+  });
+}
+
+// The argument rules both entries share, in spec_check's order (no device call); then the rows of the packed source.
+int rgb_check(pqa_ctx* c, const pqa_rgb_spec* sp, const void* src, const void* dst, int32_t n_frames, int64_t src_row, int64_t src_frame) {
+  const int rc = spec_check(c, "rgb_convert", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (!host::rgb_format(sp->format))
+      return fail(c, PQA_EINVAL, "rgb_convert: format %u is not a packed RGB format (BGRA 6, ARGB 7, RGBA 8, ABGR 9, R210 10)", sp->format);
+    if (sp->flags & ~(uint32_t)PQA_RGB_GENERIC) return fail(c, PQA_EINVAL, "rgb_convert: unknown flag bits %#x", sp->flags);
+    if (sp->dst_bits != 8 && sp->dst_bits != 10) return fail(c, PQA_EINVAL, "rgb_convert: destination bit depth %u is not 8 or 10", sp->dst_bits);
+    for (uint32_t s : {sp->hshift, sp->vshift})
+      if (s > 1) return fail(c, PQA_EINVAL, "rgb_convert: chroma shift %u outside 0 ... 1", s);
+    for (uint32_t s : {sp->hsite, sp->vsite})
+      if (s != PQA_SITE_COSITED && s != PQA_SITE_CENTRE) return fail(c, PQA_EINVAL, "rgb_convert: siting %u is not PQA_SITE_COSITED or _CENTRE", s);
+    if (!host::rgb_matrix_fits(sp->m, host::rgb_bit_depth(sp->format), (int)sp->hshift, (int)sp->vshift))
+      return fail(c, PQA_EINVAL, "rgb_convert: the matrix leaves int32 (extreme |A| times the tap sum %d plus the rounding half reaches 2^31)",
+                  1 << (3 * (sp->hshift + sp->vshift)));
+    return (int)PQA_OK;
+  });
+  if (rc != PQA_OK || n_frames == 0) return rc;
+  const int64_t min_row = host::rgb_min_row_bytes((int)sp->width);
+  if (src_row < min_row)
+    return fail(c, PQA_EINVAL, "rgb_convert: source pitch %lld is smaller than a packed row of %lld bytes", (long long)src_row, (long long)min_row);
+  if (sp->format == PQA_SURFACE_R210 && ((src_row | src_frame) & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 pitch is not a multiple of 4");
+  return PQA_OK;
+}
+ConvertLayout rgb_side(const pqa_rgb_spec* sp) {
+  return ConvertLayout{(int)sp->dst_bits, (int)sp->hshift, (int)sp->vshift, (int)sp->hsite, (int)sp->vsite};
+}
+
+// np: the planes of the destination, 1 or 3
+template <class Clip>
+int rgb_run(pqa_ctx* c, const pqa_rgb_spec* sp, int np, const Clip& src, const Clip& dst, int32_t n_frames) {
+  const ConvertLayout D = rgb_side(sp);
+  const int w = (int)sp->width, h = (int)sp->height;
+  const TransformJob j{"rgb_convert", n_frames, kFrameCap, kRgbChunk, host::rgb_layout(w, h),
+                       host::converted_layout(w, h, convert_plane_size(w, D.hshift), convert_plane_size(h, D.vshift), D.bits > 8 ? 2 : 1, np), 3};
+  return transform_run(c, j, src, nullptr, dst, no_front, [&](const pqa_device_clip& s, const pqa_device_clip&, const pqa_device_clip& d, int n) {
+    void* const at[3] = {const_cast<void*>(d.plane[0]), const_cast<void*>(d.plane[1]), const_cast<void*>(d.plane[2])};
+    return launch_rgb_convert(c->stream, (int)sp->format, D, (sp->flags & PQA_RGB_GENERIC) != 0, sp->m, s.plane[0], s.row_pitch[0], s.frame_pitch[0], at,
+                              d.row_pitch, d.frame_pitch, w, h, n);
+  });
+}
+
+// The argument rules both entries share, in spec_check's order and then the table's (no device call).
+int table_check(pqa_ctx* c, const pqa_table_spec* sp, const void* table, const void* src, const void* dst, int32_t n_frames) {
+  const int rc = spec_check(c, "table_apply", sp, 1, src, dst, n_frames, sp, 1, [] { return (int)PQA_OK; });
+  if (rc != PQA_OK) return rc;
+  if (!table) return fail(c, PQA_EINVAL, "table_apply: null table");
+  const unsigned top = (1u << c->cfg.bit_depth) - 1u;
+  for (unsigned v = 0; v <= top; ++v) {
+    const unsigned t = c->esize == 1 ? ((const uint8_t*)table)[v] : ((const uint16_t*)table)[v];
+    if (t > top) return fail(c, PQA_EINVAL, "table_apply: table entry %u is %u, above %u", v, t, top);
+  }
+  return PQA_OK;
+}
+// the table onto the stream, in front of the launches that read it; pageable memory: the copy has left `table` on return
+hipError_t table_upload(pqa_ctx* c, const void* table) {
+  return hipMemcpyAsync(c->side_buf[SIDE_TABLE_LUT], table, ((size_t)c->esize) << c->cfg.bit_depth, hipMemcpyHostToDevice, c->stream);
+}
+
+template <class Clip>
+int table_run(pqa_ctx* c, const pqa_table_spec* sp, const void* table, const Clip& src, const Clip& dst, int32_t n_frames) {
+  const int w = (int)sp->width, h = (int)sp->height;
+  const host::ClipLayout P = host::plane_clip((size_t)w * c->esize, h);
+  const TransformJob j{"table_apply", n_frames, kFrameCap, kTableChunk, P, P, 1, false, SIDE_TABLE_LUT, (size_t)c->esize << c->cfg.bit_depth};
+  return transform_run(c, j, src, nullptr, dst, [&] { return table_upload(c, table); },
+                       [&](const pqa_device_clip& s, const pqa_device_clip&, const pqa_device_clip& d, int n) {
+                         return launch_table_apply(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_TABLE_LUT], s.plane[0], s.row_pitch[0],
+                                                   s.frame_pitch[0], const_cast<void*>(d.plane[0]), d.row_pitch[0], d.frame_pitch[0], n, w, h);
+                       });
+}
+
+// The argument rules both entries share, in spec_check's order and then the grid's (no device call); bounds: what one pass over the grid tells (kernels.h).
+int mask_check(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const void* src, const void* dst, int32_t n_frames, MaskBounds* bounds) {
+  const int rc = spec_check(c, "mask_blend", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (sp->step_log2_x > (uint32_t)kMaskMaxStep || sp->step_log2_y > (uint32_t)kMaskMaxStep)
+      return fail(c, PQA_EINVAL, "mask_blend: steps %u, %u above %d", sp->step_log2_x, sp->step_log2_y, kMaskMaxStep);
+    const uint32_t top = (1u << c->cfg.bit_depth) - 1u;
+    return sp->fill > top ? fail(c, PQA_EINVAL, "mask_blend: fill %u above %u", sp->fill, top) : (int)PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  if (!nodes) return fail(c, PQA_EINVAL, "mask_blend: null node grid");
+  if (!mask_node_bounds(nodes, (int)sp->width, (int)sp->height, (int)sp->step_log2_x, (int)sp->step_log2_y, bounds))
+    return fail(c, PQA_EINVAL, "mask_blend: a node is above 256");
+  return PQA_OK;
+}
+size_t mask_node_bytes(const pqa_mask_spec* sp) {
+  return (size_t)mask_grid((int)sp->width, (int)sp->step_log2_x) * mask_grid((int)sp->height, (int)sp->step_log2_y) * sizeof(uint16_t);
+}
+// the grid's rows that hold a non-zero node onto the stream, at their place in the grid, in front of the launches that read
+// them; pageable memory: the copy has left `nodes` on return
+hipError_t mask_upload(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const MaskBounds& b) {
+  if (!b.rows) return hipSuccess;
+  const size_t gx = (size_t)mask_grid((int)sp->width, (int)sp->step_log2_x), first = (size_t)b.row0 * gx;
+  return hipMemcpyAsync((uint16_t*)c->side_buf[SIDE_MASK_NODES] + first, nodes + first, (size_t)b.rows * gx * sizeof(uint16_t),
+                        hipMemcpyHostToDevice, c->stream);
+}
+
+// fill null: the spec's fill value.  Host frames are blended where they were uploaded: the launch covers the mask's rectangle
+// only, the rest of a plane comes back as it went.
+template <class Clip>
+int mask_run(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const MaskBounds& bounds, const Clip& src, const Clip* fill, const Clip& dst,
+             int32_t n_frames) {
+  const int w = (int)sp->width, h = (int)sp->height;
+  const host::ClipLayout P = host::plane_clip((size_t)w * c->esize, h);
+  const TransformJob j{"mask_blend", n_frames, kFrameCap, kMaskChunk, P, P, 1, true, SIDE_MASK_NODES, mask_node_bytes(sp)};
+  return transform_run(c, j, src, fill, dst, [&] { return mask_upload(c, sp, nodes, bounds); },
+                       [&](const pqa_device_clip& s, const pqa_device_clip& x, const pqa_device_clip& d, int n) {
+                         return launch_mask_blend(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint16_t*)c->side_buf[SIDE_MASK_NODES],
+                                                  (int)sp->step_log2_x, (int)sp->step_log2_y, sp->fill, bounds, s.plane[0], s.row_pitch[0],
+                                                  s.frame_pitch[0], x.plane[0], x.row_pitch[0], x.frame_pitch[0], const_cast<void*>(d.plane[0]),
+                                                  d.row_pitch[0], d.frame_pitch[0], n, w, h);
+                       });
+}
+
+// colour-matrix alignment (colour_moments.hip)
+PairJob colour_job(pqa_ctx* c, int32_t n_frames, uint64_t* out) {
+  return PairJob{"colour_moments", cl_frame(c), n_frames, kColourChunk, 0, SIDE_COLOUR_OUT, (size_t)n_frames * kColourSums * sizeof(uint64_t), out, false};
+}
+// a launch's sums lie `at` frames into the output buffer
+auto colour_launch(pqa_ctx* c, uint32_t lo, uint32_t hi) {
+  return [=](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_colour_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, r, d, n, c->pw[0],
+                                 c->ph[0], lo, hi, (unsigned long long*)c->side_buf[SIDE_COLOUR_OUT] + (size_t)at * kColourSums);
+  };
+}
+template <class Clip>
+int colour_apply_run(pqa_ctx* c, const int32_t m[12], const Clip& src, const Clip& dst, int32_t n_frames) {
+  const host::ClipLayout L = cl_frame(c);
+  const TransformJob j{"colour_apply", n_frames, kColourChunk, kColourChunk, L, L, 3};
+  return transform_run(c, j, src, nullptr, dst, no_front, [&](const pqa_device_clip& s, const pqa_device_clip&, const pqa_device_clip& d, int n) {
+    PlaneRun sr[3];
+    MutPlaneRun dr[3];
+    plane_runs(s, 0, c->esize, sr);
+    plane_runs(d, 0, c->esize, dr);
+    return launch_colour_apply(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, m, sr, dr, n, c->pw[0], c->ph[0]);
+  });
+}
+
+// the argument rules both entries share, in the order in which they fire (no device call)
+int itp_check(pqa_ctx* c, const pqa_itp_spec* sp, int32_t n_frames) {
+  if (!sp) return fail(c, PQA_EINVAL, "delta_itp: null spec");
+  if (c->n_planes != 3) return fail(c, PQA_EINVAL, "delta_itp needs the chroma planes: n_planes must be 3 (got %d)", c->n_planes);
+  if (c->elem != ELEM_U8 && c->elem != ELEM_U16) return fail(c, PQA_EINVAL, "delta_itp: u8 or u16 samples only");
+  if (const char* what = itp_spec_error(*sp)) return fail(c, PQA_EINVAL, "delta_itp: %s", what);
+  if (n_frames < 0) return fail(c, PQA_EINVAL, "delta_itp: negative frame count");
+  return PQA_OK;
+}
+
+// the tiles' partial sums of a chunk are the workspace the launches share
+PairJob itp_job(pqa_ctx* c, int32_t n_frames, double* out) {
+  const int chunk = n_frames < kItpChunk ? n_frames : kItpChunk;
+  return PairJob{"delta_itp", cl_frame(c), n_frames, kItpChunk, 0, SIDE_ITP_OUT, (size_t)n_frames * kItpSums * sizeof(double), out, false, SIDE_ITP_PART,
+                 (size_t)chunk * itp_tiles(c->pw[1], c->ph[1]) * kItpSums * sizeof(double)};
+}
+// kernel and epilogue of n staged or resident frame pairs; their rows go `at` frames into the output buffer
+auto itp_launch(pqa_ctx* c, const pqa_itp_spec* sp) {
+  ItpCoef k;
+  itp_prepare(*sp, &k);
+  return [=](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    auto* part = (double*)c->side_buf[SIDE_ITP_PART];
+    hipError_t e = launch_delta_itp(c->stream, c->elem, k, r, d, n, c->pw[0], c->ph[0], (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, part);
+    if (e == hipSuccess)
+      e = launch_delta_itp_finalize(c->stream, part, itp_tiles(c->pw[1], c->ph[1]), n, (double*)c->side_buf[SIDE_ITP_OUT] + (size_t)at * kItpSums);
+    return e;
+  };
 }
 
 }  // namespace
@@ -937,14 +1336,7 @@ int pqa_resample_device(pqa_ctx* c, const pqa_resample_spec* spec, const void* s
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kRsChunk)
-    e = launch_resample(c->stream, c->elem, (int)c->cfg.bit_depth, c->rs_cache[slot].plan, (const int*)c->side_buf[SIDE_RS_TABLE0 + slot],
-                        (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch / es, src_frame_pitch / es,
-                        (int)spec->src_width, (int)spec->src_height, (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch / es,
-                        dst_frame_pitch / es, (int)spec->dst_width, (int)spec->dst_height, chunk_len(n_frames, f0, kRsChunk));
-  return side_finish(c, "resample", e, nullptr, nullptr, 0);
+  return resample_run(c, spec, slot, one_plane(src, src_row_pitch, src_frame_pitch), one_plane(dst, dst_row_pitch, dst_frame_pitch), n_frames);
 }
 
 int pqa_resample(pqa_ctx* c, const pqa_resample_spec* spec, const void* const* src_frames, int64_t src_row_stride,
@@ -953,9 +1345,7 @@ int pqa_resample(pqa_ctx* c, const pqa_resample_spec* spec, const void* const* s
   if (rc != PQA_OK) return rc;
   if (n_frames < 0) return fail(c, PQA_EINVAL, "resample: negative frame count");
   if (n_frames > 0 && (!src_frames || !dst_frames)) return fail(c, PQA_EINVAL, "resample: null frame list");
-  const int es = c->esize;
-  const int sw = (int)spec->src_width, sh = (int)spec->src_height, dw = (int)spec->dst_width, dh = (int)spec->dst_height;
-  const size_t src_row = (size_t)sw * es, dst_row = (size_t)dw * es;
+  const size_t src_row = (size_t)spec->src_width * c->esize, dst_row = (size_t)spec->dst_width * c->esize;
   rc = check_host_frames(c, "resample: ", "source ", src_frames, 1, n_frames, src_row_stride, src_row, true);
   if (rc == PQA_OK) rc = check_host_frames(c, "resample: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, dst_row, true);
   if (rc != PQA_OK) return rc;
@@ -964,54 +1354,10 @@ int pqa_resample(pqa_ctx* c, const pqa_resample_spec* spec, const void* const* s
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // A source plane may be larger than the context's: the chunks of kRsChunk planes travel through the side analyses' two
-  // pinned chunks (out through the first, back through the second) and device buffers of this entry's own, all grow-only,
-  // in the packed layout of host_stage.h, so the kernel loads and stores four samples at a time.  A chunk is uploaded,
-  // resampled, downloaded and copied out before the next one starts.
-  const host::PlaneLayout S = host::plane_layout(src_row, sh), D = host::plane_layout(dst_row, dh);
-  const int64_t sp = S.pitch, dp = D.pitch;
-  const size_t sf = S.frame_bytes, df = D.frame_bytes;
-  const int chunk = n_frames < kRsChunk ? n_frames : kRsChunk;
-  rc = side_pin_reserve(c, 0, sf * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, df * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RS_SRC, sf * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RS_DST, df * chunk);
-  if (rc != PQA_OK) return rc;
-  for (int f0 = 0; f0 < n_frames; f0 += kRsChunk) {
-    const int n = chunk_len(n_frames, f0, kRsChunk);
-    host::pack_planes(c->side_pin[0], S, src_frames + f0, src_row_stride, n);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_RS_SRC], c->side_pin[0], sf * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_resample(c->stream, c->elem, (int)c->cfg.bit_depth, c->rs_cache[slot].plan, (const int*)c->side_buf[SIDE_RS_TABLE0 + slot],
-                          c->side_buf[SIDE_RS_SRC], sp / es, (int64_t)(sf / es), sw, sh, c->side_buf[SIDE_RS_DST], dp / es,
-                          (int64_t)(df / es), dw, dh, n);
-    rc = side_finish(c, "resample", e, c->side_pin[1], c->side_buf[SIDE_RS_DST], df * n);
-    if (rc != PQA_OK) return rc;
-    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
-      for (int y = 0; y < dh; ++y)
-        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * df + (size_t)y * dp, dst_row);
-  }
-  return PQA_OK;
+  return resample_run(c, spec, slot, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_frames, &dst_row_stride}, n_frames);
 }
 
 // ---- packed capture formats (unpack.hip) -----------------------------------------------------------------------------------
-
-namespace {
-// The argument rules both entries share, in spec_check's order (no device call); then the rows of the packed source.
-int unpack_check(pqa_ctx* c, const pqa_unpack_spec* sp, const void* src, const void* dst, int32_t n_frames, int64_t src_row,
-                 int64_t src_frame) {
-  const int rc = spec_check(c, "unpack", sp, 1, src, dst, n_frames, sp, 1, [&] {
-    return host::packed_format(sp->format) ? PQA_OK : fail(c, PQA_EINVAL, "unpack: format %u is not a packed capture format (UYVY 3, YUYV 4, V210 5)", sp->format);
-  });
-  if (rc != PQA_OK || n_frames == 0) return rc;
-  const int64_t min_row = host::packed_min_row_bytes(sp->format, (int)sp->width);
-  if (src_row < min_row)
-    return fail(c, PQA_EINVAL, "unpack: source pitch %lld is smaller than a packed row of %lld bytes", (long long)src_row, (long long)min_row);
-  if (sp->format == PQA_SURFACE_V210 && ((src_row | src_frame) & 3)) return fail(c, PQA_EINVAL, "unpack: v210 pitch is not a multiple of 4");
-  return PQA_OK;
-}
-}  // namespace
 
 int pqa_unpack_device(pqa_ctx* c, const pqa_unpack_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
                       int32_t n_frames, const pqa_device_clip* dst) {
@@ -1019,28 +1365,11 @@ int pqa_unpack_device(pqa_ctx* c, const pqa_unpack_spec* spec, const void* src, 
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  if (!dst->plane[0]) return fail(c, PQA_EINVAL, "unpack: null luma destination");
-  if (!dst->plane[1] != !dst->plane[2]) return fail(c, PQA_EINVAL, "unpack: chroma destinations: both or neither");
-  if (spec->format == PQA_SURFACE_V210 && ((uintptr_t)src & 3)) return fail(c, PQA_EINVAL, "unpack: v210 source is not 4-byte aligned");
-  const int es = host::packed_sample_bytes(spec->format), w = (int)spec->width, h = (int)spec->height;
-  void* planes[3] = {nullptr, nullptr, nullptr};
-  for (int p = 0; p < (dst->plane[1] ? 3 : 1); ++p) {
-    planes[p] = const_cast<void*>(dst->plane[p]);
-    if (((uintptr_t)planes[p] | (uintptr_t)dst->row_pitch[p] | (uintptr_t)dst->frame_pitch[p]) & (uintptr_t)(es - 1))
-      return fail(c, PQA_EINVAL, "unpack: plane %d destination is not made of whole samples", p);
-    if (dst->row_pitch[p] < (int64_t)(p ? (w + 1) / 2 : w) * es) return fail(c, PQA_EINVAL, "unpack: plane %d destination pitch smaller than a row", p);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipError_t e = hipSuccess;
-  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid) {
-    void* at[3] = {nullptr, nullptr, nullptr};
-    for (int p = 0; p < 3; ++p)
-      if (planes[p]) at[p] = (uint8_t*)planes[p] + (int64_t)f0 * dst->frame_pitch[p];
-    e = launch_unpack(c->stream, (int)spec->format, (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch,
-                      at, dst->row_pitch, dst->frame_pitch, w, h, chunk_len(n_frames, f0, kGrid));
-  }
-  return side_finish(c, "unpack", e, nullptr, nullptr, 0);
+  int np = 0;
+  rc = packed_dst_check(c, "unpack", spec->format == PQA_SURFACE_V210 ? "v210" : nullptr, src, dst, host::packed_sample_bytes(spec->format),
+                        (int)spec->width, ((int)spec->width + 1) / 2, &np);
+  if (rc != PQA_OK) return rc;
+  return unpack_run(c, spec, np, one_plane(src, src_row_pitch, src_frame_pitch), *dst, n_frames);
 }
 
 int pqa_unpack(pqa_ctx* c, const pqa_unpack_spec* spec, const void* const* src_frames, int64_t src_row_stride, int32_t n_frames,
@@ -1049,169 +1378,42 @@ int pqa_unpack(pqa_ctx* c, const pqa_unpack_spec* spec, const void* const* src_f
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  if (!dst_strides) return fail(c, PQA_EINVAL, "unpack: null destination strides");
-  const int es = host::packed_sample_bytes(spec->format), w = (int)spec->width, h = (int)spec->height;
-  const int np = dst_planes[1] && dst_planes[2] ? 3 : 1;
-  if (np == 1 && (dst_planes[1] || dst_planes[2])) return fail(c, PQA_EINVAL, "unpack: chroma destinations: both or neither");
-  for (int f = 0; f < n_frames; ++f) {   // before anything is queued
-    if (!src_frames[f]) return fail(c, PQA_EINVAL, "unpack: source frame %d pointer is null", f);
-    if (spec->format == PQA_SURFACE_V210 && ((uintptr_t)src_frames[f] & 3)) return fail(c, PQA_EINVAL, "unpack: v210 source frame %d is not 4-byte aligned", f);
-    for (int p = 0; p < np; ++p)
-      if (!dst_planes[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "unpack: destination plane %d of frame %d is null", p, f);
-  }
-  for (int p = 0; p < np; ++p)
-    if (dst_strides[p] < (int64_t)(p ? (w + 1) / 2 : w) * es) return fail(c, PQA_EINVAL, "unpack: plane %d destination stride smaller than a row", p);
-  HIPCHK(c, hipSetDevice(c->device));
-  // Chunks of kRsChunk frames: packed bytes out through the first pinned chunk of the side analyses, planes back through
-  // the second, device buffers of this entry's own; a chunk is uploaded, unpacked, downloaded and copied out before the next.
-  const host::ClipLayout S = host::packed_layout(spec->format, w, h), D = host::unpacked_layout(spec->format, w, h, np);
-  const int chunk = n_frames < kRsChunk ? n_frames : kRsChunk;
-  rc = side_pin_reserve(c, 0, S.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, D.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_UNPACK_SRC, S.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_UNPACK_DST, D.frame_bytes * chunk);
+  int np = 0;
+  rc = packed_dst_check(c, "unpack", spec->format == PQA_SURFACE_V210 ? "v210" : nullptr, src_frames, dst_planes, dst_strides, n_frames,
+                        host::packed_sample_bytes(spec->format), (int)spec->width, ((int)spec->width + 1) / 2, false, &np);
   if (rc != PQA_OK) return rc;
-  const int64_t src_strides[3] = {src_row_stride, 0, 0};
-  for (int f0 = 0; f0 < n_frames; f0 += kRsChunk) {
-    const int n = chunk_len(n_frames, f0, kRsChunk);
-    host::pack_clip(c->side_pin[0], S, src_frames, src_strides, f0, n);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_UNPACK_SRC], c->side_pin[0], S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-      void* at[3] = {nullptr, nullptr, nullptr};
-      int64_t rp[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
-      for (int p = 0; p < np; ++p) {
-        at[p] = (uint8_t*)c->side_buf[SIDE_UNPACK_DST] + D.off[p];
-        rp[p] = D.plane[p].pitch;
-        fp[p] = (int64_t)D.frame_bytes;
-      }
-      e = launch_unpack(c->stream, (int)spec->format, c->side_buf[SIDE_UNPACK_SRC], S.plane[0].pitch, (int64_t)S.frame_bytes, at, rp, fp, w, h, n);
-    }
-    rc = side_finish(c, "unpack", e, c->side_pin[1], c->side_buf[SIDE_UNPACK_DST], D.frame_bytes * n);
-    if (rc != PQA_OK) return rc;
-    host::unpack_clip_out(c->side_pin[1], D, dst_planes, dst_strides, f0, n);
-  }
-  return PQA_OK;
+  return unpack_run(c, spec, np, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_planes, dst_strides}, n_frames);
 }
 
 // ---- pixel-format conversion (format_convert.hip) ---------------------------------------------------------------------------
-
-namespace {
-// The argument rules both entries share, in spec_check's order (no device call).
-int convert_check(pqa_ctx* c, const pqa_convert_spec* sp, const void* src, const void* dst, int32_t n_frames) {
-  return spec_check(c, "format_convert", sp, 1, src, dst, n_frames, sp, 1, [&] {
-    if (sp->flags & ~(uint32_t)PQA_CONVERT_GENERIC) return fail(c, PQA_EINVAL, "format_convert: unknown flag bits %#x", sp->flags);
-    for (uint32_t b : {sp->src_bits, sp->dst_bits})
-      if (b != 8 && b != 10 && b != 12) return fail(c, PQA_EINVAL, "format_convert: bit depth %u is not 8, 10 or 12", b);
-    for (uint8_t s : {sp->src_hshift, sp->src_vshift, sp->dst_hshift, sp->dst_vshift})
-      if (s > 2) return fail(c, PQA_EINVAL, "format_convert: chroma shift %u outside 0 ... 2", (unsigned)s);
-    for (uint8_t s : {sp->src_hsite, sp->src_vsite, sp->dst_hsite, sp->dst_vsite})
-      if (s != PQA_SITE_COSITED && s != PQA_SITE_CENTRE) return fail(c, PQA_EINVAL, "format_convert: siting %u is not PQA_SITE_COSITED or _CENTRE", (unsigned)s);
-    return (int)PQA_OK;
-  });
-}
-ConvertLayout convert_side(const pqa_convert_spec* sp, bool dst) {
-  return dst ? ConvertLayout{(int)sp->dst_bits, sp->dst_hshift, sp->dst_vshift, sp->dst_hsite, sp->dst_vsite}
-             : ConvertLayout{(int)sp->src_bits, sp->src_hshift, sp->src_vshift, sp->src_hsite, sp->src_vsite};
-}
-}  // namespace
 
 int pqa_format_convert_device(pqa_ctx* c, const pqa_convert_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
                               void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
   int rc = convert_check(c, spec, src, dst, n_frames);
   if (rc != PQA_OK) return rc;
-  const ConvertLayout S = convert_side(spec, false), D = convert_side(spec, true);
-  const int ses = S.bits > 8 ? 2 : 1, des = D.bits > 8 ? 2 : 1;
-  const int64_t src_row = (int64_t)convert_plane_size((int)spec->luma_width, S.hshift) * ses;
-  const int64_t dst_row = (int64_t)convert_plane_size((int)spec->luma_width, D.hshift) * des;
-  if (((uintptr_t)src | (uintptr_t)src_row_pitch | (uintptr_t)src_frame_pitch) & (uintptr_t)(ses - 1))
-    return fail(c, PQA_EINVAL, "format_convert: source base or pitch is not a multiple of the sample size");
-  if (((uintptr_t)dst | (uintptr_t)dst_row_pitch | (uintptr_t)dst_frame_pitch) & (uintptr_t)(des - 1))
-    return fail(c, PQA_EINVAL, "format_convert: destination base or pitch is not a multiple of the sample size");
-  if (src_row_pitch < src_row) return fail(c, PQA_EINVAL, "format_convert: source pitch smaller than a row");
-  if (dst_row_pitch < dst_row) return fail(c, PQA_EINVAL, "format_convert: destination pitch smaller than a row");
+  const ConvertPlanes P = convert_planes(spec);
+  rc = check_device_planes(c, "format_convert", {{"source", src, src_row_pitch, src_frame_pitch, (int64_t)P.src_row, P.S.bits > 8 ? 2 : 1},
+                                                 {"destination", dst, dst_row_pitch, dst_frame_pitch, (int64_t)P.dst_row, P.D.bits > 8 ? 2 : 1}});
+  if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipError_t e = hipSuccess;
-  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid)
-    e = launch_format_convert(c->stream, S, D, (int)spec->luma_width, (int)spec->luma_height, (spec->flags & PQA_CONVERT_GENERIC) != 0,
-                              (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch,
-                              (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch, dst_frame_pitch, chunk_len(n_frames, f0, kGrid));
-  return side_finish(c, "format_convert", e, nullptr, nullptr, 0);
+  return convert_run(c, spec, P, one_plane(src, src_row_pitch, src_frame_pitch), one_plane(dst, dst_row_pitch, dst_frame_pitch), n_frames);
 }
 
 int pqa_format_convert(pqa_ctx* c, const pqa_convert_spec* spec, const void* const* src_frames, int64_t src_row_stride,
                        void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames) {
   int rc = convert_check(c, spec, src_frames, dst_frames, n_frames);
   if (rc != PQA_OK) return rc;
-  const ConvertLayout SL = convert_side(spec, false), DL = convert_side(spec, true);
-  const int lw = (int)spec->luma_width, lh = (int)spec->luma_height;
-  const size_t src_row = (size_t)convert_plane_size(lw, SL.hshift) * (SL.bits > 8 ? 2 : 1);
-  const size_t dst_row = (size_t)convert_plane_size(lw, DL.hshift) * (DL.bits > 8 ? 2 : 1);
-  const int sh = convert_plane_size(lh, SL.vshift), dh = convert_plane_size(lh, DL.vshift);
-  rc = check_host_frames(c, "format_convert: ", "source ", src_frames, 1, n_frames, src_row_stride, src_row, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "format_convert: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, dst_row, true);
+  const ConvertPlanes P = convert_planes(spec);
+  rc = check_host_frames(c, "format_convert: ", "source ", src_frames, 1, n_frames, src_row_stride, P.src_row, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "format_convert: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, P.dst_row, true);
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // As pqa_unpack: chunks of kConvertChunk planes out through the first pinned chunk of the side analyses and back through the
-  // second, device buffers of this entry's own, all grow-only, in the packed layout of host_stage.h (rows 16 bytes apart at
-  // least, so the fast paths apply); a chunk is uploaded, converted, downloaded and copied out before the next.
-  const host::PlaneLayout S = host::plane_layout(src_row, sh), D = host::plane_layout(dst_row, dh);
-  const int chunk = n_frames < kConvertChunk ? n_frames : kConvertChunk;
-  rc = side_pin_reserve(c, 0, S.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, D.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_CONVERT_SRC, S.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_CONVERT_DST, D.frame_bytes * chunk);
-  if (rc != PQA_OK) return rc;
-  for (int f0 = 0; f0 < n_frames; f0 += kConvertChunk) {
-    const int n = chunk_len(n_frames, f0, kConvertChunk);
-    host::pack_planes(c->side_pin[0], S, src_frames + f0, src_row_stride, n);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_CONVERT_SRC], c->side_pin[0], S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_format_convert(c->stream, SL, DL, lw, lh, (spec->flags & PQA_CONVERT_GENERIC) != 0, c->side_buf[SIDE_CONVERT_SRC], S.pitch,
-                                (int64_t)S.frame_bytes, c->side_buf[SIDE_CONVERT_DST], D.pitch, (int64_t)D.frame_bytes, n);
-    rc = side_finish(c, "format_convert", e, c->side_pin[1], c->side_buf[SIDE_CONVERT_DST], D.frame_bytes * n);
-    if (rc != PQA_OK) return rc;
-    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
-      for (int y = 0; y < dh; ++y)
-        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * D.frame_bytes + (size_t)y * D.pitch, dst_row);
-  }
-  return PQA_OK;
+  return convert_run(c, spec, P, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_frames, &dst_row_stride}, n_frames);
 }
 
 // ---- packed RGB captures -> Y'CbCr planes (rgb_convert.hip) -------------------------------------------------------------------
-
-namespace {
-// The argument rules both entries share, in spec_check's order (no device call); then the rows of the packed source.
-int rgb_check(pqa_ctx* c, const pqa_rgb_spec* sp, const void* src, const void* dst, int32_t n_frames, int64_t src_row, int64_t src_frame) {
-  const int rc = spec_check(c, "rgb_convert", sp, 1, src, dst, n_frames, sp, 1, [&] {
-    if (!host::rgb_format(sp->format))
-      return fail(c, PQA_EINVAL, "rgb_convert: format %u is not a packed RGB format (BGRA 6, ARGB 7, RGBA 8, ABGR 9, R210 10)", sp->format);
-    if (sp->flags & ~(uint32_t)PQA_RGB_GENERIC) return fail(c, PQA_EINVAL, "rgb_convert: unknown flag bits %#x", sp->flags);
-    if (sp->dst_bits != 8 && sp->dst_bits != 10) return fail(c, PQA_EINVAL, "rgb_convert: destination bit depth %u is not 8 or 10", sp->dst_bits);
-    for (uint32_t s : {sp->hshift, sp->vshift})
-      if (s > 1) return fail(c, PQA_EINVAL, "rgb_convert: chroma shift %u outside 0 ... 1", s);
-    for (uint32_t s : {sp->hsite, sp->vsite})
-      if (s != PQA_SITE_COSITED && s != PQA_SITE_CENTRE) return fail(c, PQA_EINVAL, "rgb_convert: siting %u is not PQA_SITE_COSITED or _CENTRE", s);
-    if (!host::rgb_matrix_fits(sp->m, host::rgb_bit_depth(sp->format), (int)sp->hshift, (int)sp->vshift))
-      return fail(c, PQA_EINVAL, "rgb_convert: the matrix leaves int32 (extreme |A| times the tap sum %d plus the rounding half reaches 2^31)",
-                  1 << (3 * (sp->hshift + sp->vshift)));
-    return (int)PQA_OK;
-  });
-  if (rc != PQA_OK || n_frames == 0) return rc;
-  const int64_t min_row = host::rgb_min_row_bytes((int)sp->width);
-  if (src_row < min_row)
-    return fail(c, PQA_EINVAL, "rgb_convert: source pitch %lld is smaller than a packed row of %lld bytes", (long long)src_row, (long long)min_row);
-  if (sp->format == PQA_SURFACE_R210 && ((src_row | src_frame) & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 pitch is not a multiple of 4");
-  return PQA_OK;
-}
-ConvertLayout rgb_side(const pqa_rgb_spec* sp) {
-  return ConvertLayout{(int)sp->dst_bits, (int)sp->hshift, (int)sp->vshift, (int)sp->hsite, (int)sp->vsite};
-}
-}  // namespace
 
 int pqa_rgb_convert_device(pqa_ctx* c, const pqa_rgb_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
                            int32_t n_frames, const pqa_device_clip* dst) {
@@ -1219,30 +1421,11 @@ int pqa_rgb_convert_device(pqa_ctx* c, const pqa_rgb_spec* spec, const void* src
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  if (!dst->plane[0]) return fail(c, PQA_EINVAL, "rgb_convert: null luma destination");
-  if (!dst->plane[1] != !dst->plane[2]) return fail(c, PQA_EINVAL, "rgb_convert: chroma destinations: both or neither");
-  if (spec->format == PQA_SURFACE_R210 && ((uintptr_t)src & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 source is not 4-byte aligned");
-  const ConvertLayout D = rgb_side(spec);
-  const int es = D.bits > 8 ? 2 : 1, w = (int)spec->width, h = (int)spec->height, cw = convert_plane_size(w, D.hshift);
-  void* planes[3] = {nullptr, nullptr, nullptr};
-  for (int p = 0; p < (dst->plane[1] ? 3 : 1); ++p) {
-    planes[p] = const_cast<void*>(dst->plane[p]);
-    if (((uintptr_t)planes[p] | (uintptr_t)dst->row_pitch[p] | (uintptr_t)dst->frame_pitch[p]) & (uintptr_t)(es - 1))
-      return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination is not made of whole samples", p);
-    if (dst->row_pitch[p] < (int64_t)(p ? cw : w) * es) return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination pitch smaller than a row", p);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipError_t e = hipSuccess;
-  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid) {
-    void* at[3] = {nullptr, nullptr, nullptr};
-    for (int p = 0; p < 3; ++p)
-      if (planes[p]) at[p] = (uint8_t*)planes[p] + (int64_t)f0 * dst->frame_pitch[p];
-    e = launch_rgb_convert(c->stream, (int)spec->format, D, (spec->flags & PQA_RGB_GENERIC) != 0, spec->m,
-                           (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch, at, dst->row_pitch,
-                           dst->frame_pitch, w, h, chunk_len(n_frames, f0, kGrid));
-  }
-  return side_finish(c, "rgb_convert", e, nullptr, nullptr, 0);
+  int np = 0;
+  rc = packed_dst_check(c, "rgb_convert", spec->format == PQA_SURFACE_R210 ? "r210" : nullptr, src, dst, spec->dst_bits > 8 ? 2 : 1, (int)spec->width,
+                        convert_plane_size((int)spec->width, (int)spec->hshift), &np);
+  if (rc != PQA_OK) return rc;
+  return rgb_run(c, spec, np, one_plane(src, src_row_pitch, src_frame_pitch), *dst, n_frames);
 }
 
 int pqa_rgb_convert(pqa_ctx* c, const pqa_rgb_spec* spec, const void* const* src_frames, int64_t src_row_stride, int32_t n_frames,
@@ -1251,76 +1434,14 @@ int pqa_rgb_convert(pqa_ctx* c, const pqa_rgb_spec* spec, const void* const* src
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  if (!dst_strides) return fail(c, PQA_EINVAL, "rgb_convert: null destination strides");
-  const ConvertLayout DL = rgb_side(spec);
-  const int es = DL.bits > 8 ? 2 : 1, w = (int)spec->width, h = (int)spec->height;
-  const int cw = convert_plane_size(w, DL.hshift), ch = convert_plane_size(h, DL.vshift);
-  const int np = dst_planes[1] && dst_planes[2] ? 3 : 1;
-  if (np == 1 && (dst_planes[1] || dst_planes[2])) return fail(c, PQA_EINVAL, "rgb_convert: chroma destinations: both or neither");
-  for (int f = 0; f < n_frames; ++f) {   // before anything is queued
-    if (!src_frames[f]) return fail(c, PQA_EINVAL, "rgb_convert: source frame %d pointer is null", f);
-    if (spec->format == PQA_SURFACE_R210 && ((uintptr_t)src_frames[f] & 3)) return fail(c, PQA_EINVAL, "rgb_convert: r210 source frame %d is not 4-byte aligned", f);
-    for (int p = 0; p < np; ++p)
-      if (!dst_planes[(size_t)f * 3 + p]) return fail(c, PQA_EINVAL, "rgb_convert: destination plane %d of frame %d is null", p, f);
-  }
-  for (int p = 0; p < np; ++p) {
-    if (dst_strides[p] & (int64_t)(es - 1)) return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination is not made of whole samples", p);
-    if (dst_strides[p] < (int64_t)(p ? cw : w) * es) return fail(c, PQA_EINVAL, "rgb_convert: plane %d destination stride smaller than a row", p);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  // As pqa_unpack: chunks of kRgbChunk frames, packed bytes out through the first pinned chunk of the side analyses, planes back
-  // through the second, device buffers of this entry's own (rows 16 bytes apart at least, so the fast paths apply); a chunk is
-  // uploaded, converted, downloaded and copied out before the next.
-  const host::ClipLayout S = host::rgb_layout(w, h), D = host::converted_layout(w, h, cw, ch, es, np);
-  const int chunk = n_frames < kRgbChunk ? n_frames : kRgbChunk;
-  rc = side_pin_reserve(c, 0, S.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, D.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RGB_SRC, S.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_RGB_DST, D.frame_bytes * chunk);
+  int np = 0;
+  rc = packed_dst_check(c, "rgb_convert", spec->format == PQA_SURFACE_R210 ? "r210" : nullptr, src_frames, dst_planes, dst_strides, n_frames,
+                        spec->dst_bits > 8 ? 2 : 1, (int)spec->width, convert_plane_size((int)spec->width, (int)spec->hshift), true, &np);
   if (rc != PQA_OK) return rc;
-  const int64_t src_strides[3] = {src_row_stride, 0, 0};
-  for (int f0 = 0; f0 < n_frames; f0 += kRgbChunk) {
-    const int n = chunk_len(n_frames, f0, kRgbChunk);
-    host::pack_clip(c->side_pin[0], S, src_frames, src_strides, f0, n);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_RGB_SRC], c->side_pin[0], S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-      void* at[3] = {nullptr, nullptr, nullptr};
-      int64_t rp[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
-      for (int p = 0; p < np; ++p) {
-        at[p] = (uint8_t*)c->side_buf[SIDE_RGB_DST] + D.off[p];
-        rp[p] = D.plane[p].pitch;
-        fp[p] = (int64_t)D.frame_bytes;
-      }
-      e = launch_rgb_convert(c->stream, (int)spec->format, DL, (spec->flags & PQA_RGB_GENERIC) != 0, spec->m, c->side_buf[SIDE_RGB_SRC],
-                             S.plane[0].pitch, (int64_t)S.frame_bytes, at, rp, fp, w, h, n);
-    }
-    rc = side_finish(c, "rgb_convert", e, c->side_pin[1], c->side_buf[SIDE_RGB_DST], D.frame_bytes * n);
-    if (rc != PQA_OK) return rc;
-    host::unpack_clip_out(c->side_pin[1], D, dst_planes, dst_strides, f0, n);
-  }
-  return PQA_OK;
+  return rgb_run(c, spec, np, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_planes, dst_strides}, n_frames);
 }
 
 // ---- transfer-curve alignment: planes through an integer table (table_apply.hip) ----------------------------------------------
-
-namespace {
-// The argument rules both entries share, in spec_check's order and then the table's (no device call).
-int table_check(pqa_ctx* c, const pqa_table_spec* sp, const void* table, const void* src, const void* dst, int32_t n_frames) {
-  const int rc = spec_check(c, "table_apply", sp, 1, src, dst, n_frames, sp, 1, [] { return (int)PQA_OK; });
-  if (rc != PQA_OK) return rc;
-  if (!table) return fail(c, PQA_EINVAL, "table_apply: null table");
-  const unsigned top = (1u << c->cfg.bit_depth) - 1u;
-  for (unsigned v = 0; v <= top; ++v) {
-    const unsigned t = c->esize == 1 ? ((const uint8_t*)table)[v] : ((const uint16_t*)table)[v];
-    if (t > top) return fail(c, PQA_EINVAL, "table_apply: table entry %u is %u, above %u", v, t, top);
-  }
-  return PQA_OK;
-}
-// the table onto the stream, in front of the launches that read it; pageable memory: the copy has left `table` on return
-hipError_t table_upload(pqa_ctx* c, const void* table) {
-  return hipMemcpyAsync(c->side_buf[SIDE_TABLE_LUT], table, ((size_t)c->esize) << c->cfg.bit_depth, hipMemcpyHostToDevice, c->stream);
-}
-}  // namespace
 
 int pqa_table_apply_device(pqa_ctx* c, const pqa_table_spec* spec, const void* table, const void* src, int64_t src_row_pitch,
                            int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
@@ -1328,96 +1449,27 @@ int pqa_table_apply_device(pqa_ctx* c, const pqa_table_spec* spec, const void* t
   if (rc != PQA_OK) return rc;
   const int es = c->esize;
   const int64_t row = (int64_t)spec->width * es;
-  if (((uintptr_t)src | (uintptr_t)src_row_pitch | (uintptr_t)src_frame_pitch) & (uintptr_t)(es - 1))
-    return fail(c, PQA_EINVAL, "table_apply: source base or pitch is not a multiple of the sample size");
-  if (((uintptr_t)dst | (uintptr_t)dst_row_pitch | (uintptr_t)dst_frame_pitch) & (uintptr_t)(es - 1))
-    return fail(c, PQA_EINVAL, "table_apply: destination base or pitch is not a multiple of the sample size");
-  if (src_row_pitch < row) return fail(c, PQA_EINVAL, "table_apply: source pitch smaller than a row");
-  if (dst_row_pitch < row) return fail(c, PQA_EINVAL, "table_apply: destination pitch smaller than a row");
+  rc = check_device_planes(c, "table_apply", {{"source", src, src_row_pitch, src_frame_pitch, row, es}, {"destination", dst, dst_row_pitch, dst_frame_pitch, row, es}});
+  if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = side_reserve(c, SIDE_TABLE_LUT, (size_t)es << c->cfg.bit_depth);
-  if (rc != PQA_OK) return rc;
-  hipError_t e = table_upload(c, table);
-  constexpr int kGrid = 32768;   // frames per launch (the grid's y)
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid)
-    e = launch_table_apply(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_TABLE_LUT],
-                           (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch, src_frame_pitch,
-                           (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch, dst_frame_pitch, chunk_len(n_frames, f0, kGrid),
-                           (int)spec->width, (int)spec->height);
-  return side_finish(c, "table_apply", e, nullptr, nullptr, 0);
+  return table_run(c, spec, table, one_plane(src, src_row_pitch, src_frame_pitch), one_plane(dst, dst_row_pitch, dst_frame_pitch), n_frames);
 }
 
 int pqa_table_apply(pqa_ctx* c, const pqa_table_spec* spec, const void* table, const void* const* src_frames, int64_t src_row_stride,
                     void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames) {
   int rc = table_check(c, spec, table, src_frames, dst_frames, n_frames);
   if (rc != PQA_OK) return rc;
-  const int w = (int)spec->width, h = (int)spec->height;
-  const size_t row = (size_t)w * c->esize;
+  const size_t row = (size_t)spec->width * c->esize;
   rc = check_host_frames(c, "table_apply: ", "source ", src_frames, 1, n_frames, src_row_stride, row, true);
   if (rc == PQA_OK) rc = check_host_frames(c, "table_apply: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, row, true);
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // As pqa_format_convert: chunks of kTableChunk planes out through the first pinned chunk of the side analyses and back through
-  // the second, device buffers of this entry's own, all grow-only, in the packed layout of host_stage.h (rows 16 bytes apart at
-  // least, so the 16-byte loads and stores apply); a chunk is uploaded, mapped, downloaded and copied out before the next.
-  const host::PlaneLayout P = host::plane_layout(row, h);
-  const int chunk = n_frames < kTableChunk ? n_frames : kTableChunk;
-  rc = side_pin_reserve(c, 0, P.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, P.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TABLE_LUT, (size_t)c->esize << c->cfg.bit_depth);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TABLE_SRC, P.frame_bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_TABLE_DST, P.frame_bytes * chunk);
-  if (rc != PQA_OK) return rc;
-  for (int f0 = 0; f0 < n_frames; f0 += kTableChunk) {
-    const int n = chunk_len(n_frames, f0, kTableChunk);
-    host::pack_planes(c->side_pin[0], P, src_frames + f0, src_row_stride, n);
-    hipError_t e = f0 == 0 ? table_upload(c, table) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_TABLE_SRC], c->side_pin[0], P.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_table_apply(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_TABLE_LUT], c->side_buf[SIDE_TABLE_SRC], P.pitch,
-                             (int64_t)P.frame_bytes, c->side_buf[SIDE_TABLE_DST], P.pitch, (int64_t)P.frame_bytes, n, w, h);
-    rc = side_finish(c, "table_apply", e, c->side_pin[1], c->side_buf[SIDE_TABLE_DST], P.frame_bytes * n);
-    if (rc != PQA_OK) return rc;
-    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
-      for (int y = 0; y < h; ++y)
-        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * P.frame_bytes + (size_t)y * P.pitch, row);
-  }
-  return PQA_OK;
+  return table_run(c, spec, table, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_frames, &dst_row_stride}, n_frames);
 }
 
 // ---- overlay masking: planes through a feathered mask (mask_blend.hip) ---------------------------------------------------------
-
-namespace {
-// The argument rules both entries share, in spec_check's order and then the grid's (no device call); bounds: what one pass over the grid tells (kernels.h).
-int mask_check(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const void* src, const void* dst, int32_t n_frames, MaskBounds* bounds) {
-  const int rc = spec_check(c, "mask_blend", sp, 1, src, dst, n_frames, sp, 1, [&] {
-    if (sp->step_log2_x > (uint32_t)kMaskMaxStep || sp->step_log2_y > (uint32_t)kMaskMaxStep)
-      return fail(c, PQA_EINVAL, "mask_blend: steps %u, %u above %d", sp->step_log2_x, sp->step_log2_y, kMaskMaxStep);
-    const uint32_t top = (1u << c->cfg.bit_depth) - 1u;
-    return sp->fill > top ? fail(c, PQA_EINVAL, "mask_blend: fill %u above %u", sp->fill, top) : (int)PQA_OK;
-  });
-  if (rc != PQA_OK) return rc;
-  if (!nodes) return fail(c, PQA_EINVAL, "mask_blend: null node grid");
-  if (!mask_node_bounds(nodes, (int)sp->width, (int)sp->height, (int)sp->step_log2_x, (int)sp->step_log2_y, bounds))
-    return fail(c, PQA_EINVAL, "mask_blend: a node is above 256");
-  return PQA_OK;
-}
-size_t mask_node_bytes(const pqa_mask_spec* sp) {
-  return (size_t)mask_grid((int)sp->width, (int)sp->step_log2_x) * mask_grid((int)sp->height, (int)sp->step_log2_y) * sizeof(uint16_t);
-}
-// the grid's rows that hold a non-zero node onto the stream, at their place in the grid, in front of the launches that read
-// them; pageable memory: the copy has left `nodes` on return
-hipError_t mask_upload(pqa_ctx* c, const pqa_mask_spec* sp, const uint16_t* nodes, const MaskBounds& b) {
-  if (!b.rows) return hipSuccess;
-  const size_t gx = (size_t)mask_grid((int)sp->width, (int)sp->step_log2_x), first = (size_t)b.row0 * gx;
-  return hipMemcpyAsync((uint16_t*)c->side_buf[SIDE_MASK_NODES] + first, nodes + first, (size_t)b.rows * gx * sizeof(uint16_t),
-                        hipMemcpyHostToDevice, c->stream);
-}
-}  // namespace
 
 int pqa_mask_blend_device(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t* nodes, const void* src, int64_t src_row_pitch,
                           int64_t src_frame_pitch, const void* fill, int64_t fill_row_pitch, int64_t fill_frame_pitch, void* dst,
@@ -1427,32 +1479,15 @@ int pqa_mask_blend_device(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t*
   if (rc != PQA_OK) return rc;
   const int es = c->esize;
   const int64_t row = (int64_t)spec->width * es;
-  if (((uintptr_t)src | (uintptr_t)src_row_pitch | (uintptr_t)src_frame_pitch) & (uintptr_t)(es - 1))
-    return fail(c, PQA_EINVAL, "mask_blend: source base or pitch is not a multiple of the sample size");
-  if (((uintptr_t)dst | (uintptr_t)dst_row_pitch | (uintptr_t)dst_frame_pitch) & (uintptr_t)(es - 1))
-    return fail(c, PQA_EINVAL, "mask_blend: destination base or pitch is not a multiple of the sample size");
-  if (src_row_pitch < row) return fail(c, PQA_EINVAL, "mask_blend: source pitch smaller than a row");
-  if (dst_row_pitch < row) return fail(c, PQA_EINVAL, "mask_blend: destination pitch smaller than a row");
-  if (fill) {
-    if (((uintptr_t)fill | (uintptr_t)fill_row_pitch | (uintptr_t)fill_frame_pitch) & (uintptr_t)(es - 1))
-      return fail(c, PQA_EINVAL, "mask_blend: fill base or pitch is not a multiple of the sample size");
-    if (fill_row_pitch < row) return fail(c, PQA_EINVAL, "mask_blend: fill pitch smaller than a row");
-    if (fill == dst) return fail(c, PQA_EINVAL, "mask_blend: the destination is the fill plane");
-  }
+  rc = check_device_planes(c, "mask_blend", {{"source", src, src_row_pitch, src_frame_pitch, row, es}, {"destination", dst, dst_row_pitch, dst_frame_pitch, row, es}});
+  if (rc == PQA_OK && fill) rc = check_device_planes(c, "mask_blend", {{"fill", fill, fill_row_pitch, fill_frame_pitch, row, es}});
+  if (rc != PQA_OK) return rc;
+  if (fill && fill == dst) return fail(c, PQA_EINVAL, "mask_blend: the destination is the fill plane");
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = side_reserve(c, SIDE_MASK_NODES, mask_node_bytes(spec));
-  if (rc != PQA_OK) return rc;
-  hipError_t e = mask_upload(c, spec, nodes, bounds);
-  constexpr int kGrid = 32768;   // frames per launch (the grid's z)
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kGrid)
-    e = launch_mask_blend(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint16_t*)c->side_buf[SIDE_MASK_NODES], (int)spec->step_log2_x,
-                          (int)spec->step_log2_y, spec->fill, bounds, (const uint8_t*)src + (int64_t)f0 * src_frame_pitch, src_row_pitch,
-                          src_frame_pitch, fill ? (const uint8_t*)fill + (int64_t)f0 * fill_frame_pitch : nullptr, fill_row_pitch,
-                          fill_frame_pitch, (uint8_t*)dst + (int64_t)f0 * dst_frame_pitch, dst_row_pitch, dst_frame_pitch,
-                          chunk_len(n_frames, f0, kGrid), (int)spec->width, (int)spec->height);
-  return side_finish(c, "mask_blend", e, nullptr, nullptr, 0);
+  const pqa_device_clip fill_clip = one_plane(fill, fill_row_pitch, fill_frame_pitch);
+  return mask_run(c, spec, nodes, bounds, one_plane(src, src_row_pitch, src_frame_pitch), fill ? &fill_clip : nullptr,
+                  one_plane(dst, dst_row_pitch, dst_frame_pitch), n_frames);
 }
 
 int pqa_mask_blend(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t* nodes, const void* const* src_frames, int64_t src_row_stride,
@@ -1461,8 +1496,7 @@ int pqa_mask_blend(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t* nodes,
   MaskBounds bounds;
   int rc = mask_check(c, spec, nodes, src_frames, dst_frames, n_frames, &bounds);
   if (rc != PQA_OK) return rc;
-  const int w = (int)spec->width, h = (int)spec->height;
-  const size_t row = (size_t)w * c->esize;
+  const size_t row = (size_t)spec->width * c->esize;
   rc = check_host_frames(c, "mask_blend: ", "source ", src_frames, 1, n_frames, src_row_stride, row, true);
   if (rc == PQA_OK) rc = check_host_frames(c, "mask_blend: ", "destination ", (const void* const*)dst_frames, 1, n_frames, dst_row_stride, row, true);
   if (rc == PQA_OK && fill_frames) rc = check_host_frames(c, "mask_blend: ", "fill ", fill_frames, 1, n_frames, fill_row_stride, row, true);
@@ -1471,39 +1505,9 @@ int pqa_mask_blend(pqa_ctx* c, const pqa_mask_spec* spec, const uint16_t* nodes,
     if (fill_frames[f] == dst_frames[f]) return fail(c, PQA_EINVAL, "mask_blend: destination frame %d is its fill plane", f);
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // As pqa_table_apply: chunks of kMaskChunk planes out through the first pinned chunk of the side analyses (the source planes,
-  // the fill planes behind them) and back through the second, in the packed layout of host_stage.h.  The uploaded source planes
-  // are blended where they lie: the launch covers the mask's rectangle only, the rest of a plane comes back as it went.
-  const host::PlaneLayout P = host::plane_layout(row, h);
-  const int chunk = n_frames < kMaskChunk ? n_frames : kMaskChunk;
-  const size_t chunk_bytes = P.frame_bytes * chunk;
-  rc = side_pin_reserve(c, 0, chunk_bytes * (fill_frames ? 2 : 1));
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, chunk_bytes);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_MASK_NODES, mask_node_bytes(spec));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_MASK_SRC, chunk_bytes);
-  if (rc == PQA_OK && fill_frames) rc = side_reserve(c, SIDE_MASK_FILL, chunk_bytes);
-  if (rc != PQA_OK) return rc;
-  for (int f0 = 0; f0 < n_frames; f0 += kMaskChunk) {
-    const int n = chunk_len(n_frames, f0, kMaskChunk);
-    host::pack_planes(c->side_pin[0], P, src_frames + f0, src_row_stride, n);
-    if (fill_frames) host::pack_planes(c->side_pin[0] + chunk_bytes, P, fill_frames + f0, fill_row_stride, n);
-    hipError_t e = f0 == 0 ? mask_upload(c, spec, nodes, bounds) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_MASK_SRC], c->side_pin[0], P.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && fill_frames)
-      e = hipMemcpyAsync(c->side_buf[SIDE_MASK_FILL], c->side_pin[0] + chunk_bytes, P.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_mask_blend(c->stream, c->elem, (int)c->cfg.bit_depth, (const uint16_t*)c->side_buf[SIDE_MASK_NODES], (int)spec->step_log2_x,
-                            (int)spec->step_log2_y, spec->fill, bounds, c->side_buf[SIDE_MASK_SRC], P.pitch, (int64_t)P.frame_bytes,
-                            fill_frames ? c->side_buf[SIDE_MASK_FILL] : nullptr, P.pitch, (int64_t)P.frame_bytes, c->side_buf[SIDE_MASK_SRC],
-                            P.pitch, (int64_t)P.frame_bytes, n, w, h);
-    rc = side_finish(c, "mask_blend", e, c->side_pin[1], c->side_buf[SIDE_MASK_SRC], P.frame_bytes * n);
-    if (rc != PQA_OK) return rc;
-    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
-      for (int y = 0; y < h; ++y)
-        memcpy((uint8_t*)dst_frames[f0 + f] + (int64_t)y * dst_row_stride, c->side_pin[1] + (size_t)f * P.frame_bytes + (size_t)y * P.pitch, row);
-  }
-  return PQA_OK;
+  const HostClip fill_clip{fill_frames, &fill_row_stride};
+  return mask_run(c, spec, nodes, bounds, HostClip{src_frames, &src_row_stride}, fill_frames ? &fill_clip : nullptr,
+                  HostClip{(const void* const*)dst_frames, &dst_row_stride}, n_frames);
 }
 
 // ---- the spec-driven analyses: flow_moments() ... line_profiles() above ------------------------------------------------------
@@ -1514,7 +1518,7 @@ int pqa_flow_moments_device(pqa_ctx* c, const pqa_flow_spec* spec, const void* r
 }
 int pqa_flow_moments(pqa_ctx* c, const pqa_flow_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, int64_t* out) {
-  return flow_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
+  return flow_moments(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
 }
 
 int pqa_tile_moments_device(pqa_ctx* c, const pqa_tile_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
@@ -1523,7 +1527,7 @@ int pqa_tile_moments_device(pqa_ctx* c, const pqa_tile_spec* spec, const void* r
 }
 int pqa_tile_moments(pqa_ctx* c, const pqa_tile_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  return tile_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
+  return tile_moments(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
 }
 
 int pqa_band_sums(void) { return kBandSums; }
@@ -1533,7 +1537,7 @@ int pqa_band_moments_device(pqa_ctx* c, const pqa_band_spec* spec, const void* r
 }
 int pqa_band_moments(pqa_ctx* c, const pqa_band_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  return band_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
+  return band_moments(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
 }
 
 int pqa_temporal_sums(void) { return kTemporalSums; }
@@ -1544,7 +1548,7 @@ int pqa_temporal_moments_device(pqa_ctx* c, const pqa_temporal_spec* spec, const
 }
 int pqa_temporal_moments(pqa_ctx* c, const pqa_temporal_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                          const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  return temporal_moments(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
+  return temporal_moments(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
 }
 
 int pqa_edge_sums(void) { return kEdgeSums; }
@@ -1554,7 +1558,7 @@ int pqa_edge_profiles_device(pqa_ctx* c, const pqa_edge_spec* spec, const void* 
 }
 int pqa_edge_profiles(pqa_ctx* c, const pqa_edge_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                       const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
-  return edge_profiles(c, spec, HostClip{ref_frames, ref_row_stride}, HostClip{dis_frames, dis_row_stride}, n_frames, out);
+  return edge_profiles(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
 }
 
 int pqa_line_profiles_device(pqa_ctx* c, const pqa_profile_spec* spec, const void* planes, int64_t row_pitch, int64_t frame_pitch,
@@ -1563,7 +1567,7 @@ int pqa_line_profiles_device(pqa_ctx* c, const pqa_profile_spec* spec, const voi
 }
 int pqa_line_profiles(pqa_ctx* c, const pqa_profile_spec* spec, const void* const* frames, int64_t row_stride, int32_t n_frames,
                       uint64_t* out) {
-  return line_profiles(c, spec, HostClip{frames, row_stride}, n_frames, out);
+  return line_profiles(c, spec, HostClip{frames, &row_stride}, n_frames, out);
 }
 
 // ---- colour-matrix alignment (colour_moments.hip) ------------------------------------------------------------------------
@@ -1584,70 +1588,21 @@ int pqa_colour_moments_device(pqa_ctx* c, const pqa_device_clip* ref, const pqa_
   if (rc == PQA_OK) rc = cl_check_clip(c, "colour_moments: captured ", dis);
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)n_frames * kColourSums * sizeof(uint64_t);
-  rc = side_reserve(c, SIDE_COLOUR_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  const int es = c->esize;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_COLOUR_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kColourChunk) {
-    PlaneRun r[3], d[3];
-    for (int p = 0; p < 3; ++p) {
-      r[p] = PlaneRun{(const uint8_t*)ref->plane[p] + (int64_t)f0 * ref->frame_pitch[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-      d[p] = PlaneRun{(const uint8_t*)dis->plane[p] + (int64_t)f0 * dis->frame_pitch[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-    }
-    e = launch_colour_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, r, d,
-                              chunk_len(n_frames, f0, kColourChunk), c->pw[0], c->ph[0], lo, hi, dev_out + (size_t)f0 * kColourSums);
-  }
-  return side_finish(c, "colour_moments", e, out, dev_out, bytes);
+  return pair_run(c, colour_job(c, n_frames, out), *ref, *dis, nullptr, colour_launch(c, lo, hi));
 }
 
 int pqa_colour_moments(pqa_ctx* c, const void* const* ref_frames, const int64_t ref_strides[3], const void* const* dis_frames,
                        const int64_t dis_strides[3], int32_t n_frames, uint32_t lo, uint32_t hi, uint64_t* out) {
   if (!c) return PQA_EINVAL;
-  int rc = cl_check(c, "colour_moments", n_frames);
+  const int rc = cl_check(c, "colour_moments", n_frames);
   if (rc != PQA_OK) return rc;
   const uint32_t top = (1u << c->cfg.bit_depth) - 1u;
   if (lo > hi || hi > top) return fail(c, PQA_EINVAL, "colour_moments: mask %u ... %u outside 0 ... %u", lo, hi, top);
   if (n_frames > 0 && (!ref_frames || !dis_frames || !ref_strides || !dis_strides)) return fail(c, PQA_EINVAL, "colour_moments: null frame list");
   if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "colour_moments: null output pointer");
   if (n_frames == 0) return PQA_OK;
-  rc = cl_check_host(c, "colour_moments: ", "reference ", ref_frames, ref_strides, n_frames);
-  if (rc == PQA_OK) rc = cl_check_host(c, "colour_moments: ", "captured ", dis_frames, dis_strides, n_frames);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  // Three planes a frame, so this entry keeps a loop of its own beside pair_run: chunks of kColourChunk pairs through the side
-  // analyses' two pinned chunks (reference frames through the first, captured ones through the second) into
-  // device buffers of this entry; every chunk's kernel writes its sums behind the previous chunk's, they come back once.
-  const ClLayout L = cl_layout(c);
-  const int chunk = n_frames < kColourChunk ? n_frames : kColourChunk;
-  const size_t bytes = (size_t)n_frames * kColourSums * sizeof(uint64_t);
-  rc = side_pin_reserve(c, 0, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_A, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_B, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_OUT, bytes);
-  if (rc != PQA_OK) return rc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_COLOUR_OUT];
-  PlaneRun r[3], d[3];
-  cl_runs(c, L, c->side_buf[SIDE_COLOUR_A], r);
-  cl_runs(c, L, c->side_buf[SIDE_COLOUR_B], d);
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kColourChunk) {
-    const int n = chunk_len(n_frames, f0, kColourChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);   // the pinned buffers are packed again only after the chunk before has left them
-    if (e != hipSuccess) break;
-    cl_pack(c, L, c->side_pin[0], ref_frames + (size_t)f0 * 3, ref_strides, n);
-    cl_pack(c, L, c->side_pin[1], dis_frames + (size_t)f0 * 3, dis_strides, n);
-    e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->side_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_B], c->side_pin[1], L.bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_colour_moments(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, r, d, n,
-                                c->pw[0], c->ph[0], lo, hi, dev_out + (size_t)f0 * kColourSums);
-  }
-  return side_finish(c, "colour_moments", e, out, dev_out, bytes);
+  const HostClip ref{ref_frames, ref_strides}, dis{dis_frames, dis_strides};
+  return pair_run(c, colour_job(c, n_frames, out), ref, &dis, colour_launch(c, lo, hi));   // the frame rules, `cancelled` and the staging
 }
 
 int pqa_colour_apply_device(pqa_ctx* c, const int32_t m[12], const pqa_device_clip* src, const pqa_device_clip* dst, int32_t n_frames) {
@@ -1662,20 +1617,7 @@ int pqa_colour_apply_device(pqa_ctx* c, const int32_t m[12], const pqa_device_cl
   if (rc == PQA_OK) rc = cl_check_clip(c, "colour_apply: destination ", dst);
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int es = c->esize;
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kColourChunk) {
-    PlaneRun s[3];
-    MutPlaneRun d[3];
-    for (int p = 0; p < 3; ++p) {
-      s[p] = PlaneRun{(const uint8_t*)src->plane[p] + (int64_t)f0 * src->frame_pitch[p], src->row_pitch[p] / es, src->frame_pitch[p] / es};
-      d[p] = MutPlaneRun{(uint8_t*)const_cast<void*>(dst->plane[p]) + (int64_t)f0 * dst->frame_pitch[p], dst->row_pitch[p] / es, dst->frame_pitch[p] / es};
-    }
-    e = launch_colour_apply(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, m, s, d,
-                            chunk_len(n_frames, f0, kColourChunk), c->pw[0], c->ph[0]);
-  }
-  return side_finish(c, "colour_apply", e, nullptr, nullptr, 0);
+  return colour_apply_run(c, m, *src, *dst, n_frames);
 }
 
 int pqa_colour_apply(pqa_ctx* c, const int32_t m[12], const void* const* src_frames, const int64_t src_strides[3],
@@ -1691,75 +1633,12 @@ int pqa_colour_apply(pqa_ctx* c, const int32_t m[12], const void* const* src_fra
   if (rc == PQA_OK) rc = cl_check_host(c, "colour_apply: ", "destination ", (const void* const*)dst_frames, dst_strides, n_frames);
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as pqa_resample: a chunk is uploaded, mapped, downloaded and copied out before the next one starts
-  const ClLayout L = cl_layout(c);
-  const int chunk = n_frames < kColourChunk ? n_frames : kColourChunk;
-  rc = side_pin_reserve(c, 0, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_A, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_COLOUR_B, L.bytes * chunk);
-  if (rc != PQA_OK) return rc;
-  PlaneRun s[3], dr[3];
-  MutPlaneRun d[3];
-  cl_runs(c, L, c->side_buf[SIDE_COLOUR_A], s);
-  cl_runs(c, L, c->side_buf[SIDE_COLOUR_B], dr);
-  for (int p = 0; p < 3; ++p) d[p] = MutPlaneRun{const_cast<void*>(dr[p].base), dr[p].row_pitch, dr[p].frame_pitch};
-  for (int f0 = 0; f0 < n_frames; f0 += kColourChunk) {
-    const int n = chunk_len(n_frames, f0, kColourChunk);
-    cl_pack(c, L, c->side_pin[0], src_frames + (size_t)f0 * 3, src_strides, n);
-    hipError_t e = hipMemcpyAsync(c->side_buf[SIDE_COLOUR_A], c->side_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-      e = launch_colour_apply(c->stream, c->elem, (int)c->cfg.bit_depth, (int)c->cfg.chroma_hshift, (int)c->cfg.chroma_vshift, m, s, d, n,
-                              c->pw[0], c->ph[0]);
-    rc = side_finish(c, "colour_apply", e, c->side_pin[1], c->side_buf[SIDE_COLOUR_B], L.bytes * n);
-    if (rc != PQA_OK) return rc;
-    for (int f = 0; f < n; ++f)   // row by row: the bytes between a destination row's end and the next row stay as they are
-      for (int p = 0; p < 3; ++p)
-        for (int y = 0; y < c->ph[p]; ++y)
-          memcpy((uint8_t*)dst_frames[(size_t)(f0 + f) * 3 + p] + (int64_t)y * dst_strides[p],
-                 c->side_pin[1] + (size_t)f * L.bytes + L.off[p] + (size_t)y * L.pitch[p], (size_t)c->pw[p] * c->esize);
-  }
-  return PQA_OK;
+  return colour_apply_run(c, m, HostClip{src_frames, src_strides}, HostClip{(const void* const*)dst_frames, dst_strides}, n_frames);
 }
 
 // ---- Delta E ITP (delta_itp.hip) -----------------------------------------------------------------------------------------
 
 int pqa_itp_sums(void) { return kItpSums; }
-
-}  // extern "C"
-
-namespace {
-
-// the argument rules both entries share, in the order in which they fire (no device call)
-int itp_check(pqa_ctx* c, const pqa_itp_spec* sp, int32_t n_frames) {
-  if (!sp) return fail(c, PQA_EINVAL, "delta_itp: null spec");
-  if (c->n_planes != 3) return fail(c, PQA_EINVAL, "delta_itp needs the chroma planes: n_planes must be 3 (got %d)", c->n_planes);
-  if (c->elem != ELEM_U8 && c->elem != ELEM_U16) return fail(c, PQA_EINVAL, "delta_itp: u8 or u16 samples only");
-  if (const char* what = itp_spec_error(*sp)) return fail(c, PQA_EINVAL, "delta_itp: %s", what);
-  if (n_frames < 0) return fail(c, PQA_EINVAL, "delta_itp: negative frame count");
-  return PQA_OK;
-}
-
-// kernel and epilogue of n staged or resident frame pairs; their rows go `at` frames into the output buffer
-hipError_t itp_launch(pqa_ctx* c, const ItpCoef& k, const PlaneRun r[3], const PlaneRun d[3], int n, int at) {
-  const int tiles = itp_tiles(c->pw[1], c->ph[1]);
-  auto* part = (double*)c->side_buf[SIDE_ITP_PART];
-  hipError_t e = launch_delta_itp(c->stream, c->elem, k, r, d, n, c->pw[0], c->ph[0], (int)c->cfg.chroma_hshift,
-                                  (int)c->cfg.chroma_vshift, part);
-  if (e == hipSuccess) e = launch_delta_itp_finalize(c->stream, part, tiles, n, (double*)c->side_buf[SIDE_ITP_OUT] + (size_t)at * kItpSums);
-  return e;
-}
-
-int itp_reserve(pqa_ctx* c, int32_t n_frames) {
-  const int chunk = n_frames < kItpChunk ? n_frames : kItpChunk;
-  const int rc = side_reserve(c, SIDE_ITP_PART, (size_t)chunk * itp_tiles(c->pw[1], c->ph[1]) * kItpSums * sizeof(double));
-  return rc == PQA_OK ? side_reserve(c, SIDE_ITP_OUT, (size_t)n_frames * kItpSums * sizeof(double)) : rc;
-}
-
-}  // namespace
-
-extern "C" {
 
 int pqa_delta_itp_device(pqa_ctx* c, const pqa_itp_spec* spec, const pqa_device_clip* ref, const pqa_device_clip* dis,
                          int32_t n_frames, double* out) {
@@ -1773,64 +1652,19 @@ int pqa_delta_itp_device(pqa_ctx* c, const pqa_itp_spec* spec, const pqa_device_
   if (rc == PQA_OK) rc = cl_check_clip(c, "delta_itp: captured ", dis);
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = itp_reserve(c, n_frames);
-  if (rc != PQA_OK) return rc;
-  ItpCoef k;
-  itp_prepare(*spec, &k);
-  const int es = c->esize;
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kItpChunk) {
-    PlaneRun r[3], d[3];
-    for (int p = 0; p < 3; ++p) {
-      r[p] = PlaneRun{(const uint8_t*)ref->plane[p] + (int64_t)f0 * ref->frame_pitch[p], ref->row_pitch[p] / es, ref->frame_pitch[p] / es};
-      d[p] = PlaneRun{(const uint8_t*)dis->plane[p] + (int64_t)f0 * dis->frame_pitch[p], dis->row_pitch[p] / es, dis->frame_pitch[p] / es};
-    }
-    e = itp_launch(c, k, r, d, chunk_len(n_frames, f0, kItpChunk), f0);
-  }
-  return side_finish(c, "delta_itp", e, out, c->side_buf[SIDE_ITP_OUT], (size_t)n_frames * kItpSums * sizeof(double));
+  return pair_run(c, itp_job(c, n_frames, out), *ref, *dis, &c->cancelled, itp_launch(c, spec));
 }
 
 int pqa_delta_itp(pqa_ctx* c, const pqa_itp_spec* spec, const void* const* ref_frames, const int64_t ref_strides[3],
                   const void* const* dis_frames, const int64_t dis_strides[3], int32_t n_frames, double* out) {
   if (!c) return PQA_EINVAL;
-  int rc = itp_check(c, spec, n_frames);
+  const int rc = itp_check(c, spec, n_frames);
   if (rc != PQA_OK) return rc;
   if (n_frames > 0 && (!ref_frames || !dis_frames || !ref_strides || !dis_strides)) return fail(c, PQA_EINVAL, "delta_itp: null frame list");
   if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "delta_itp: null output pointer");
   if (n_frames == 0) return PQA_OK;
-  rc = cl_check_host(c, "delta_itp: ", "reference ", ref_frames, ref_strides, n_frames);
-  if (rc == PQA_OK) rc = cl_check_host(c, "delta_itp: ", "captured ", dis_frames, dis_strides, n_frames);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as pqa_colour_moments: chunks of kItpChunk pairs through the side analyses' two pinned chunks into device buffers of this
-  // entry; every chunk's epilogue writes its rows behind the previous chunk's, they come back once
-  const ClLayout L = cl_layout(c);
-  const int chunk = n_frames < kItpChunk ? n_frames : kItpChunk;
-  rc = side_pin_reserve(c, 0, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_pin_reserve(c, 1, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_ITP_REF, L.bytes * chunk);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_ITP_DIS, L.bytes * chunk);
-  if (rc == PQA_OK) rc = itp_reserve(c, n_frames);
-  if (rc != PQA_OK) return rc;
-  ItpCoef k;
-  itp_prepare(*spec, &k);
-  PlaneRun r[3], d[3];
-  cl_runs(c, L, c->side_buf[SIDE_ITP_REF], r);
-  cl_runs(c, L, c->side_buf[SIDE_ITP_DIS], d);
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += kItpChunk) {
-    const int n = chunk_len(n_frames, f0, kItpChunk);
-    if (f0 > 0) e = hipStreamSynchronize(c->stream);   // the pinned buffers are packed again only after the chunk before has left them
-    if (e != hipSuccess) break;
-    cl_pack(c, L, c->side_pin[0], ref_frames + (size_t)f0 * 3, ref_strides, n);
-    cl_pack(c, L, c->side_pin[1], dis_frames + (size_t)f0 * 3, dis_strides, n);
-    e = hipMemcpyAsync(c->side_buf[SIDE_ITP_REF], c->side_pin[0], L.bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->side_buf[SIDE_ITP_DIS], c->side_pin[1], L.bytes * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = itp_launch(c, k, r, d, n, f0);
-  }
-  return side_finish(c, "delta_itp", e, out, c->side_buf[SIDE_ITP_OUT], (size_t)n_frames * kItpSums * sizeof(double));
+  const HostClip ref{ref_frames, ref_strides}, dis{dis_frames, dis_strides};
+  return pair_run(c, itp_job(c, n_frames, out), ref, &dis, itp_launch(c, spec));   // the frame rules, `cancelled` and the staging
 }
 
 }  // extern "C"

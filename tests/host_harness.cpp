@@ -210,6 +210,7 @@ struct StageCase {
   int n_frames, carry, clips;
   char fail_in = 0;       // 'D', 'S', 'U' or 'L': that callable returns 7 in the second chunk
   bool cancel = false;    // the first launch raises the cancel flag
+  int planes = 1;         // per frame; 3: as pqa_colour_moments stages them (plane p is 5 * p bytes a row wider, planes 256 bytes apart)
 };
 
 struct Launched { int out_index; std::vector<int> seen[2]; };
@@ -218,31 +219,42 @@ static void stage_case(const StageCase& k) {
   const int chunk = 8, slots = k.n_frames < chunk ? k.n_frames : chunk;
   const PlaneLayout L = plane_layout(k.row_bytes, k.h);
   CHECK(L.pitch % 16 == 0 && L.pitch >= (int64_t)k.row_bytes && L.pitch < (int64_t)k.row_bytes + 16 && L.frame_bytes == (size_t)L.pitch * k.h);
-  const int64_t stride = L.pitch + k.stride_extra;
-  // every source frame is an allocation of its own that ends with the last sample of its last row
+  const int np = k.planes;
+  const size_t rb[3] = {k.row_bytes, k.row_bytes + 5, k.row_bytes + 10};
+  const int rows[3] = {k.h, k.h, k.h};
+  const ClipLayout C = np == 1 ? plane_clip(k.row_bytes, k.h) : clip_layout(np, rb, rows, 16, 256);
+  CHECK(C.n_planes == np && C.plane[0].pitch == L.pitch && (np == 3 || C.frame_bytes == L.frame_bytes));
+  int64_t strides[3];
+  for (int p = 0; p < np; ++p) {
+    strides[p] = C.plane[p].pitch + k.stride_extra;
+    CHECK(C.off[p] % (np == 1 ? 16 : 256) == 0 && C.off[p] + C.plane[p].frame_bytes <= (p + 1 < np ? C.off[p + 1] : C.frame_bytes));
+  }
+  // every source plane is an allocation of its own that ends with the last sample of its last row
   std::vector<std::unique_ptr<uint8_t[]>> src[2];
   std::vector<const void*> list[2];
   std::unique_ptr<uint8_t[]> pin[2], dev[2];
   for (int c = 0; c < k.clips; ++c) {
-    for (int f = 0; f < k.n_frames; ++f) {
-      src[c].emplace_back(new uint8_t[(size_t)stride * (k.h - 1) + k.row_bytes]);
-      for (int y = 0; y < k.h; ++y)
-        for (size_t x = 0; x < (size_t)(y < k.h - 1 ? stride : (int64_t)k.row_bytes); ++x)
-          src[c][f][(size_t)y * stride + x] = x < k.row_bytes ? sample_of(c, f, y, x) : 0xee;
-      list[c].push_back(src[c][f].get());
-    }
-    pin[c].reset(new uint8_t[L.frame_bytes * slots]);
-    dev[c].reset(new uint8_t[L.frame_bytes * (slots + k.carry)]);
+    for (int f = 0; f < k.n_frames; ++f)
+      for (int p = 0; p < np; ++p) {
+        const int64_t stride = strides[p];
+        src[c].emplace_back(new uint8_t[(size_t)stride * (k.h - 1) + rb[p]]);
+        for (int y = 0; y < k.h; ++y)
+          for (size_t x = 0; x < (size_t)(y < k.h - 1 ? stride : (int64_t)rb[p]); ++x)
+            src[c].back()[(size_t)y * stride + x] = x < rb[p] ? sample_of(c, f, y, x + 5 * p) : 0xee;
+        list[c].push_back(src[c].back().get());
+      }
+    pin[c].reset(new uint8_t[C.frame_bytes * slots]);
+    dev[c].reset(new uint8_t[C.frame_bytes * (slots + k.carry)]);
   }
   uint8_t* const pins[2] = {pin[0].get(), pin[1].get()};
-  const size_t fb = L.frame_bytes;
+  const size_t fb = C.frame_bytes;
   std::string log;
   std::vector<Launched> launches;
   std::atomic<int> cancelled{0};
   int chunk_no = 0;   // of the chunk a callable belongs to: upload() opens a chunk's device work, drain() the chunk's host work
   const auto fails = [&](char who) { log += who; return k.fail_in == who && chunk_no == 1 ? 7 : 0; };
   const int rc = stage_walk(
-      L, pins, list[0].data(), stride, k.clips == 2 ? list[1].data() : nullptr, stride, k.n_frames, chunk, k.carry, cancelled,
+      C, pins, list[0].data(), strides, k.clips == 2 ? list[1].data() : nullptr, strides, k.n_frames, chunk, k.carry, cancelled,
       [&] { ++chunk_no; return fails('D'); },
       [&](int from) {
         CHECK(from >= 1 && from < slots + k.carry);
@@ -262,7 +274,9 @@ static void stage_case(const StageCase& k) {
             const uint8_t* plane = dev[c].get() + (size_t)(slot + i) * fb;
             const int f = (plane[0] - sample_of(c, 0, 0, 0)) / 7;
             CHECK(f >= 0 && f < k.n_frames);
-            for (int y = 0; y < k.h; ++y) CHECK(!memcmp(plane + (size_t)y * L.pitch, src[c][f].get() + (size_t)y * stride, k.row_bytes));
+            for (int p = 0; p < np; ++p)
+              for (int y = 0; y < k.h; ++y)
+                CHECK(!memcmp(plane + C.off[p] + (size_t)y * C.plane[p].pitch, src[c][(size_t)f * np + p].get() + (size_t)y * strides[p], rb[p]));
             l.seen[c].push_back(f);
           }
         launches.push_back(l);
@@ -304,10 +318,136 @@ static void stage_scenarios() {
         for (int n : {0, 1, 2, 8, 9, 16, 17})
           for (int carry : {0, 1})
             for (int clips : {2, 1}) stage_case(StageCase{row_bytes, h, extra, n, carry, clips});
+  // three planes a frame (pqa_colour_moments, pqa_delta_itp: two clips, a result per frame)
+  for (size_t row_bytes : {1, 15, 16, 17, 33})
+    for (int h : {1, 3})
+      for (int64_t extra : {0, 7})
+        for (int n : {0, 1, 8, 9, 17}) stage_case(StageCase{row_bytes, h, extra, n, 0, 2, 0, false, 3});
+  for (char who : {'D', 'U', 'L'}) stage_case(StageCase{17, 3, 7, 17, 0, 2, who, false, 3});
+  stage_case(StageCase{17, 3, 7, 17, 0, 2, 0, true, 3});
   for (int carry : {0, 1})
     for (int clips : {2, 1}) {
       for (char who : {'D', 'S', 'U', 'L'}) stage_case(StageCase{17, 3, 7, 17, carry, clips, who});
       stage_case(StageCase{17, 3, 7, 17, carry, clips, 0, true});
+    }
+}
+
+// ---- the transform staging (host_stage.h: transform_walk) ------------------------------------------------------------------------
+// The device is the two heap buffers pqa_side.hip reserves for a transform (source chunk / result chunk; in place: source
+// chunk / second input), the pinned chunks two more.  The "kernel" copies: destination plane p is source plane p % src_planes
+// (so one packed plane fans out to three, as pqa_unpack's does); in place it leaves the source where it lies and checks that
+// the second input beside it belongs to the same frame.
+struct TransformCase {
+  int n_frames, src_planes, dst_planes, dst_step;
+  size_t row_bytes;
+  int h;
+  int64_t stride_extra;
+  bool aux;            // a second input a frame; the result stays where the source was uploaded
+  char fail_in = 0;    // 'U', 'L' or 'F': that callable returns 7 in the second chunk
+};
+
+static void transform_case(const TransformCase& k) {
+  const int chunk = 8, slots = k.n_frames < chunk ? k.n_frames : chunk, sp = k.src_planes, dp = k.dst_planes;
+  const size_t srb[3] = {k.row_bytes, k.row_bytes + 5, k.row_bytes + 10};
+  const size_t drb[3] = {srb[0], srb[1 % sp], srb[2 % sp]};
+  const int rows[3] = {k.h, k.h, k.h};
+  const ClipLayout S = sp == 1 ? plane_clip(srb[0], k.h) : clip_layout(sp, srb, rows, 16, 256);
+  const ClipLayout D = k.aux ? S : dp == 1 ? plane_clip(drb[0], k.h) : clip_layout(dp, drb, rows, 16, 16);   // in place: one layout
+  int64_t ss[3] = {0, 0, 0}, ds[3] = {0, 0, 0};
+  for (int p = 0; p < sp; ++p) ss[p] = S.plane[p].pitch + k.stride_extra;
+  for (int p = 0; p < dp; ++p) ds[p] = (int64_t)drb[p] + k.stride_extra;
+  // sources (clip 1: the second input) end at their last sample; destinations carry sentinels between the rows and behind the last
+  std::vector<std::unique_ptr<uint8_t[]>> src[2], dst;
+  std::vector<const void*> list[2];
+  std::vector<void*> out((size_t)k.n_frames * k.dst_step, nullptr);
+  const auto dst_bytes = [&](int p) { return (size_t)ds[p] * k.h + 8; };
+  for (int f = 0; f < k.n_frames; ++f) {
+    for (int c = 0; c < (k.aux ? 2 : 1); ++c)
+      for (int p = 0; p < sp; ++p) {
+        src[c].emplace_back(new uint8_t[(size_t)ss[p] * (k.h - 1) + srb[p]]);
+        for (int y = 0; y < k.h; ++y)
+          for (size_t x = 0; x < (size_t)(y < k.h - 1 ? ss[p] : (int64_t)srb[p]); ++x)
+            src[c].back()[(size_t)y * ss[p] + x] = x < srb[p] ? sample_of(c, f, y, x + 5 * p) : 0xee;
+        list[c].push_back(src[c].back().get());
+      }
+    for (int p = 0; p < dp; ++p) {
+      dst.emplace_back(new uint8_t[dst_bytes(p)]);
+      memset(dst.back().get(), 0xEE, dst_bytes(p));
+      out[(size_t)f * k.dst_step + p] = dst.back().get();
+    }
+  }
+  const size_t sb = S.frame_bytes * slots, db = D.frame_bytes * slots;
+  std::unique_ptr<uint8_t[]> pin0(new uint8_t[sb * (k.aux ? 2 : 1)]), pin1(new uint8_t[db]), a(new uint8_t[sb]), b(new uint8_t[k.aux ? sb : db]);
+  uint8_t* const pins[2] = {pin0.get(), pin1.get()};
+  std::string log;
+  int chunk_no = -1, uploaded = 0;
+  const auto fails = [&](char who) { log += who; return k.fail_in == who && chunk_no == 1 ? 7 : 0; };
+  const int rc = transform_walk(
+      S, D, pins, list[0].data(), ss, k.aux ? list[1].data() : nullptr, ss, out.data(), ds, k.dst_step, k.n_frames, chunk,
+      [&](int f0, int n) {
+        ++chunk_no;
+        CHECK(f0 == chunk_no * chunk && n >= 1 && n <= slots && f0 + n <= k.n_frames);
+        memcpy(a.get(), pins[0], S.frame_bytes * n);
+        if (k.aux) memcpy(b.get(), pins[0] + sb, S.frame_bytes * n);
+        uploaded = n;
+        return fails('U');
+      },
+      [&](int n) {
+        CHECK(n == uploaded);
+        for (int f = 0; f < n; ++f)
+          for (int p = 0; p < dp; ++p)
+            for (int y = 0; y < k.h; ++y) {
+              const uint8_t* from = a.get() + (size_t)f * S.frame_bytes + S.off[p % sp] + (size_t)y * S.plane[p % sp].pitch;
+              if (k.aux)   // the second input of the same frame lies beside the source
+                CHECK(!memcmp(b.get() + (from - a.get()), src[1][(size_t)(chunk_no * chunk + f) * sp + p].get() + (size_t)y * ss[p], srb[p]));
+              else
+                memcpy(b.get() + (size_t)f * D.frame_bytes + D.off[p] + (size_t)y * D.plane[p].pitch, from, drb[p]);
+            }
+        return fails('L');
+      },
+      [&](int e, int n) {
+        CHECK(n == uploaded);
+        memcpy(pins[1], k.aux ? a.get() : b.get(), D.frame_bytes * n);
+        const int own = fails('F');
+        return e ? e : own;
+      });
+  // the calls, restated: per chunk upload, launch (not after a failed upload), finish (always)
+  std::string want;
+  const int n_chunks = (k.n_frames + chunk - 1) / chunk;
+  int done = k.n_frames;   // frames of the chunks that came through
+  for (int i = 0; i < n_chunks; ++i) {
+    const bool hit = i == 1 && k.fail_in;
+    want += hit && k.fail_in == 'U' ? "UF" : "ULF";
+    if (hit) { done = chunk; break; }
+  }
+  CHECK(log == want);
+  CHECK(rc == (k.fail_in ? 7 : 0));
+  // every destination frame of a chunk that came through holds its own source frame, the others nothing; every sentinel survives
+  for (int f = 0; f < k.n_frames; ++f)
+    for (int p = 0; p < dp; ++p) {
+      const uint8_t* o = (const uint8_t*)out[(size_t)f * k.dst_step + p];
+      for (size_t i = 0; i < dst_bytes(p); ++i) {
+        const int y = (int)(i / (size_t)ds[p]);
+        const size_t x = i % (size_t)ds[p];
+        const bool sample = f < done && y < k.h && x < drb[p];
+        CHECK(o[i] == (sample ? sample_of(0, f, y, x + 5 * (p % sp)) : 0xEE));
+      }
+    }
+}
+
+static void transform_scenarios() {
+  const int shapes[][3] = {{1, 1, 1}, {1, 1, 3}, {1, 3, 3}, {3, 3, 3}};   // source planes, destination planes, destination pointer step
+  for (const auto& sh : shapes)
+    for (size_t row_bytes : {1, 15, 16, 17, 33})
+      for (int h : {1, 3})
+        for (int64_t extra : {0, 7})
+          for (int n : {0, 1, 8, 9, 17})
+            for (bool aux : {false, true})
+              if (!aux || sh[0] == sh[1]) transform_case(TransformCase{n, sh[0], sh[1], sh[2], row_bytes, h, extra, aux});
+  for (const auto& sh : shapes)
+    for (char who : {'U', 'L', 'F'}) {
+      transform_case(TransformCase{17, sh[0], sh[1], sh[2], 17, 3, 7, false, who});
+      if (sh[0] == sh[1]) transform_case(TransformCase{17, sh[0], sh[1], sh[2], 17, 3, 7, true, who});
     }
 }
 
@@ -547,6 +687,7 @@ int main(int argc, char** argv) {
   ring_scenarios();
   chain_scenarios();
   stage_scenarios();
+  transform_scenarios();
   pack_scenarios(dir);
   printf("host harness ok\n");
   return 0;

@@ -129,7 +129,7 @@ static void planar_round_trip(int w, int h, int es, int n_planes) {
       memset(out_keep.back().get(), 0xEE, out_bytes[3 * f + p]);
       out[3 * f + p] = out_keep.back().get();
     }
-  unpack_clip_out(pin.get(), L, out.data(), out_strides, f0, m);
+  unpack_clip_out(pin.get(), L, out.data(), out_strides, 3, f0, m);
   for (int f = f0; f < f0 + m; ++f)
     for (int p = 0; p < n_planes; ++p)
       for (int y = 0; y < h; ++y) {

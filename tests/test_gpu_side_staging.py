@@ -242,3 +242,69 @@ def test_cross_sse_argument_rules_speak():
                 assert call(**kw) == Nt.PQA_EINVAL, kw
                 assert word in lib.pqa_last_error(ctx) and lib.pqa_last_error(ctx).startswith(b"cross_sse: "), kw
         assert host() == Nt.PQA_OK and out[:6].tolist() == [2 ** 64 - 1, 0, 0, 0, 0, 2 ** 64 - 1]
+
+
+# ---- the staging of the plane transforms and of the analyses of planes of the call's own size ---------------------------
+N9 = 9    # two chunks of the host entries (8 frames a chunk), the second partial
+
+
+@pytest.mark.parametrize("fmt,lay,bits", [("bgra", "420left", 8), ("r210", "422", 10)])
+def test_rgb_convert_across_the_chunk(fmt, lay, bits):
+    """9 different host frames of 17 x 5: the ninth travels in a second chunk, through pinned and device buffers the first
+    chunk has used, and lands behind the eighth in the caller's planes -- three planes and luma only"""
+    from tests import rgb_ref as R
+    from tests import test_gpu_rgb as TR
+    w, h = 17, 5
+    dst, m = (*TR.LAYOUTS[lay], bits), TR._matrix("bt709", fmt, bits)
+    frames = TR._frames(300 + bits, fmt, w, h, n=N9, stride=R.file_stride(fmt, w))
+    assert _distinct(np.stack(frames))
+    want = [R.convert(fr, fmt, w, h, m, dst) for fr in frames]
+    with TR._engine() as eng:
+        TR._same(eng.rgb_convert(frames, fmt, (h, w), dst, m), want, (fmt, lay, "three planes"))
+        TR._same(eng.rgb_convert(frames, fmt, (h, w), dst, m, luma_only=True), [[p[0]] for p in want], (fmt, lay, "luma only"))
+
+
+def _interleaved_calls():
+    """(name, call on an engine) in the order of the test below; every call has 9 frames of its own size"""
+    from tests import format_convert_ref as FR
+    rng = np.random.default_rng(77)
+    u8 = lambda h, w: [rng.integers(0, 256, (h, w), dtype=np.uint8) for _ in range(N9)]
+    small, lut, blend, fill = u8(9, 33), rng.permutation(256).astype(np.uint8), u8(9, 33), u8(9, 33)
+    nodes = rng.integers(0, 257, (4, 10)).astype(np.uint16)    # steps of 4 samples over 33 x 9
+    table_in, packed, chroma = u8(16, 16), u8(6, 68), u8(12, 17)    # UYVY rows of 34 pixels; the 4:2:2 chroma plane of 34 x 12
+    ref3 = [[a, b, c] for a, b, c in zip(u8(H, W), u8(H // 2, W // 2), u8(H // 2, W // 2))]
+    dis3 = [[a, b, c] for a, b, c in zip(u8(H, W), u8(H // 2, W // 2), u8(H // 2, W // 2))]
+    matrix = [3 << 14, 15000, -700, 900, 2 << 14, 300, 16000, -500, 1 << 14, -400, 600, 17000]
+    resample = ("resample", lambda e: e.resample(small, (32, 64)))
+    return [resample,
+            ("table_apply", lambda e: e.table_apply(table_in, lut, plane=None)),
+            ("mask_blend", lambda e: e.mask_blend(blend, nodes, (2, 2), fill, plane=None)),
+            ("unpack", lambda e: e.unpack(packed, "uyvy422", (6, 34))),
+            ("format_convert", lambda e: e.format_convert(chroma, (12, 34), (1, 0, FR.COSITED, 0, 8), (1, 1, FR.COSITED, FR.CENTRE, 8))),
+            ("colour_moments", lambda e: e.colour_moments(ref3, dis3)),
+            ("colour_apply", lambda e: e.colour_apply(dis3, matrix)),
+            ("tile_moments", lambda e: e.tile_moments([f[0] for f in ref3], [f[0] for f in dis3])),
+            ("line_profiles", lambda e: e.line_profiles([f[0] for f in dis3])),
+            ("resample again", resample[1])]
+
+
+def _flat(result):
+    """the arrays of a result, whatever its nesting"""
+    if isinstance(result, np.ndarray):
+        return [result]
+    return [a for part in result for a in _flat(part)]
+
+
+def test_entries_interleaved_on_one_context():
+    """the entries that stage host frames of their own size, one after the other on one context, each with two chunks: every
+    call both grows and under-fills the staging buffers the call before it left, and returns what it returns on a fresh context"""
+    calls = _interleaved_calls()
+    with _engine(n_planes=3, chroma_shift=(1, 1)) as eng:
+        got = [_flat(call(eng)) for _, call in calls]
+    for (name, call), mine in zip(calls, got):
+        with _engine(n_planes=3, chroma_shift=(1, 1)) as fresh:
+            want = _flat(call(fresh))
+        assert len(mine) == len(want) and len(want) >= 1, name
+        for k, (a, b) in enumerate(zip(mine, want)):
+            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), (name, k)
+    assert _distinct(np.stack(got[0])) and _distinct(np.stack(got[1]))    # the frames of a call differ: one in the wrong slot shows
