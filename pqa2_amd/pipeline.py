@@ -4,14 +4,21 @@ frame pair, gather, apply the model.  Works as a single process (world_size 1) o
 frame-sharded torch.distributed job (one process per GPU)."""
 from __future__ import annotations
 
+import dataclasses
+import math
 import os
 import time
+from collections import namedtuple
+from contextlib import closing
 
 import numpy as np
 
 from . import _native as N
 from . import model as M
 from . import report, shard
+from .readers import (CHROMA_SITINGS, _ColourReader, _ConvertedReader, _CroppedReader, _LevelledReader, _LumaReader,  # noqa: F401
+                      _MaskedReader, _RegisteredReader, _ResampledReader, _RgbReader, _ShiftedReader, _TableReader,
+                      _clip_context, _side_context, crop_readers, yuvio_info_444)
 from .yuvio import open_video
 
 
@@ -246,217 +253,365 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     boxes in pixels, `share` the fraction of luma samples the mask touches, `fill` the constants per plane or "reference",
     `applied` false under "report" and when no tile is persistent.  None: nothing is read or changed and the result has no such
     object."""
-    from . import integrity as IG
     from .engine import FeatureEngine
+    make_side = engine_factory or FeatureEngine
+    make = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, reuse=True, **kw))   # a parked context of this configuration
     raw_kwargs = raw_kwargs or {}
-    ref_rd = open_video(reference_path, **raw_kwargs)
-    dis_rd = open_video(distorted_path, **raw_kwargs)
-    ri, di = ref_rd.info, dis_rd.info
+    st = _Clips(open_video(reference_path, **raw_kwargs), open_video(distorted_path, **raw_kwargs), device, make_side)
+    _check_formats(chroma_mismatch, chroma_siting, rgb_matrix, rgb_range)
+    _wrap_rgb(st, chroma_siting, rgb_matrix, rgb_range)
+    _match_chroma(st, chroma_mismatch, chroma_siting)
+    _match_size(st, resize)
+    _align_time(st, align, align_frames, align_penalty_mse)
+    _crop_active(st, active_picture, active_frames, active_limit, active_skip)
+    _align_shift(st, spatial_align, spatial_frames)
+    _register(st, register, register_frames, register_min_px)
+    _align_levels(st, level_align, level_frames, level_curve)
+    _align_colour(st, colour_align, colour_frames, colour_full_range)
+    _mask_overlay(st, overlay_mask, overlay_boxes, overlay_frames, overlay_tile, overlay_grow, overlay_feather, overlay_share)
+    passes = dict(distortion_map=distortion_map, distortion_planes=distortion_planes, distortion_factor=distortion_factor,
+                  distortion_min_mse=distortion_min_mse, distortion_dir=distortion_dir, spectrum=spectrum, spectrum_planes=spectrum_planes,
+                  spectrum_min_mse=spectrum_min_mse, spectrum_gain_floor=spectrum_gain_floor, temporal=temporal,
+                  temporal_planes=temporal_planes, temporal_min_mse=temporal_min_mse, temporal_blend_min=temporal_blend_min,
+                  temporal_still_mse=temporal_still_mse, temporal_pop_factor=temporal_pop_factor, coding_grid=coding_grid,
+                  grid_planes=grid_planes, grid_periods=grid_periods, grid_z2=grid_z2)
+    n, periods, itp_spec = _check_passes(st, delta_itp=delta_itp, itp_matrix=itp_matrix, itp_range=itp_range, itp_peak=itp_peak,
+                                         itp_threshold=itp_threshold, **passes)
+    flags = dict(float_ssim=float_ssim, ms_ssim=ms_ssim, ciede=ciede, cambi=cambi, cambi_full_ref=cambi_full_ref,
+                 psnr_hvs=psnr_hvs, xpsnr=xpsnr, siti=siti)
+    plan = _feature_mask(st, model, psnr=psnr, ssim=ssim, integrity=integrity, integrity_options=integrity_options, **flags)
+    a, b = shard.shard_bounds(n, world_size, rank)
+    t_start = time.perf_counter()
+    local, local_blk = _score_shard(st, make, plan, a, b, max_batch=max_batch, n_subsample=n_subsample, fixed_point=fixed_point,
+                                    xpsnr=xpsnr, siti=siti, integrity=integrity, progress=progress, cancelled=cancelled)
+    to = (world_size, rank, gather_device)
+    measured = _run_passes(st, a, b, n, to, cancelled, itp_spec, **passes)
+    rec = shard.gather_records(local, n, *to)
+    blk = {i: shard.gather_records(local_blk[i], n, *to, width=N.EXT_BLOCKS[i][1]) for i in plan.want}
+    if rank != 0:
+        st.close()
+        return None
+    ig_result = _integrity_events(st, make, blk.pop(plan.want[-1]), n, plan.n_planes, plan.ig_opts) if integrity else None   # the last block
+    elapsed = time.perf_counter() - t_start
+    res = _result(st, rec, blk, plan, flags, ig_result, measured, periods, itp_spec, psnr=psnr, ssim=ssim, n_subsample=n_subsample,
+                  fps=n / elapsed if elapsed > 0 else 0.0, **passes)
+    st.close()   # on an error their contexts go with the readers
+    return res
+
+
+# what _feature_mask settles: model, planes to score, PQA_FEAT_* mask, extension blocks (N.EXT_BLOCKS) to collect, integrity's two
+_Plan = namedtuple("_Plan", "mdl n_planes feats want ig_opts ig_thr")
+
+
+def _score_shard(st: _Clips, make, plan: _Plan, a: int, b: int, *, max_batch, n_subsample, fixed_point, xpsnr, siti, integrity,
+                 progress, cancelled):
+    """frames [a, b) through a scoring context: (their records, {i: the rows of extension block i}).  An error closes the
+    context; a healthy one is parked for the next analysis of this geometry"""
+    ri, mdl = st.ri, plan.mdl
+    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=plan.n_planes,
+               chroma_shift=(ri.hshift, ri.vshift), features=plan.feats, device=st.device, max_batch=max_batch,
+               result_capacity=max(b - a, 16), n_subsample=n_subsample,
+               vif_enhn_gain_limit=mdl.vif_enhn_gain_limit, adm_enhn_gain_limit=mdl.adm_enhn_gain_limit,
+               vif_border=mdl.vif_border, **({"fixed_point": int(fixed_point)} if fixed_point else {}))
+    try:
+        _arm_histories(st, eng, a, plan.n_planes, xpsnr, siti, integrity, plan.ig_thr)
+        _submit_frames(st, eng, a, b, plan.n_planes, progress, cancelled)
+        got = _collect(eng, a, b, plan.want)
+    except BaseException:
+        eng.close()
+        raise
+    (eng.release if hasattr(eng, "release") else eng.close)()
+    return got
+
+
+def _run_passes(st: _Clips, a: int, b: int, n: int, to, cancelled, itp_spec, *, distortion_map, distortion_planes, spectrum,
+                spectrum_planes, temporal, temporal_planes, coding_grid, grid_planes, **_):
+    """(dmap, bands, tmom, edges, itp_rows), None where not asked for: the passes of their own over the readers the scoring
+    loop saw, after the scoring context is parked.  to: (world_size, rank, gather_device)"""
+    dmap = bands = tmom = edges = itp_rows = None
+    if distortion_map or spectrum or temporal or coding_grid:      # ONE pass for the four of them
+        dmap, bands, tmom, edges = _distortion_pass(st.ref, st.dis, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1,
+                                                    st.device, st.make, *to, cancelled, levels=int(spectrum),
+                                                    band_planes=3 if spectrum_planes == "all" else 1, temporal_tile=int(temporal),
+                                                    temporal_planes=3 if temporal_planes == "all" else 1,
+                                                    edge_planes=(3 if grid_planes == "all" else 1) if coding_grid else 0)
+    if itp_spec is not None:      # every pixel of every plane, on the clips as scored
+        itp_rows = _itp_pass(st.ref, st.dis, a, b, n, itp_spec, st.device, st.make, *to, cancelled)
+    return dmap, bands, tmom, edges, itp_rows
+
+
+def _result(st: _Clips, rec, blk, plan: _Plan, flags: dict, ig_result, measured, periods, itp_spec, *, psnr, ssim, n_subsample, fps,
+            distortion_map, distortion_factor, distortion_min_mse, distortion_dir, spectrum, spectrum_min_mse, spectrum_gain_floor,
+            temporal, temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor, grid_z2, **_) -> ScoreResult:
+    """rank 0: finish_records on the gathered rows, the solvers on what _run_passes measured, the objects the steps left in `st`"""
+    ri = st.ri
+    extra = {N.EXT_BLOCKS[i][0]: rows for i, rows in blk.items()}   # finish_records takes a block under its name in the table
+    extra.update({k: True for k, v in flags.items() if v})
+    if ig_result is not None:
+        extra.update(integrity=ig_result)
+    res = finish_records(rec, plan.mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=plan.n_planes, fps=fps, **extra)
+    dmap, bands, tmom, edges, itp_rows = measured
+    if dmap is not None:
+        _distortion_result(res, dmap, ri, int(distortion_map), distortion_factor, distortion_min_mse, distortion_dir)
+    if bands is not None:
+        _spectrum_result(res, bands, ri, int(spectrum), spectrum_min_mse, spectrum_gain_floor)
+    if tmom is not None:
+        _temporal_result(res, tmom, ri, int(temporal), temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)
+    if edges is not None:
+        _grid_result(res, edges, ri, periods, grid_z2)
+    if itp_rows is not None:
+        _itp_result(res, itp_rows, itp_spec)
+    for key in ("alignment", "resize", "input", "overlay"):
+        if getattr(st, key) is not None:
+            res[key] = getattr(st, key)
+    return res
+
+
+@dataclasses.dataclass
+class _Clips:
+    """What the steps of score_files hand on: the two readers as the next step is to read them, the objects the result
+    reports, and the wrapped readers that own a GPU context, in the order they were made."""
+    ref: object
+    dis: object
+    device: object
+    make: object                   # the maker of the small side contexts
+    alignment: dict | None = None
+    input: dict | None = None
+    resize: dict | None = None
+    overlay: dict | None = None
+    owned: list = dataclasses.field(default_factory=list)
+
+    ri = property(lambda self: self.ref.info)
+    di = property(lambda self: self.dis.info)
+
+    def own(self, reader):      # a reader with a context of its own: close() reaches it
+        self.owned.append(reader)
+        return reader
+
+    def close(self):
+        for rd in self.owned:
+            rd.close()
+
+
+def _check_formats(chroma_mismatch, chroma_siting, rgb_matrix, rgb_range) -> None:
+    from . import rgb as RGB
+    from .align import COLOUR_STANDARDS
     if chroma_mismatch not in ("error", "luma", "convert"):
         raise ValueError('chroma_mismatch must be "error" or "luma" or "convert"')
     if chroma_siting is not None and chroma_siting not in CHROMA_SITINGS:
         raise ValueError('chroma_siting must be None, "left", "center" or "topleft"')
-    from . import rgb as RGB
-    from .align import COLOUR_STANDARDS
     if rgb_matrix is not None and rgb_matrix not in COLOUR_STANDARDS:
         raise ValueError(f"rgb_matrix must be None or one of {sorted(COLOUR_STANDARDS)}")
     if rgb_range is not None and rgb_range not in RGB.RANGES:
         raise ValueError('rgb_range must be None, "full" or "limited"')
-    input_info = None
-    rgb_readers = []
+
+
+def _wrap_rgb(st: _Clips, siting, matrix, rgb_range) -> None:
+    """a packed RGB clip becomes Y'CbCr planes in its partner's format; `input` for every packed file"""
+    from . import rgb as RGB
+    ri, di = st.ri, st.di
     if ri.packed in RGB.FORMATS or di.packed in RGB.FORMATS:
-        make = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
         both = ri.packed in RGB.FORMATS and di.packed in RGB.FORMATS
         plain = yuvio_info_444(ri) if both else None       # two RGB clips: 4:4:4 at the reference's depth
         conversions = []
-        pix = {"reference": ri.pix_fmt, "distorted": di.pix_fmt}
         if ri.packed in RGB.FORMATS:
-            ref_rd = _RgbReader(ref_rd, plain or di, chroma_siting, device, make, rgb_matrix, rgb_range, "reference")
-            rgb_readers.append(ref_rd)
-            conversions.append(ref_rd.conversion)
+            st.ref = st.own(_RgbReader(st.ref, plain or di, siting, st.device, st.make, matrix, rgb_range, "reference"))
+            conversions.append(st.ref.conversion)
         if di.packed in RGB.FORMATS:
-            dis_rd = _RgbReader(dis_rd, plain or ri, chroma_siting, device, make, rgb_matrix, rgb_range, "distorted")
-            rgb_readers.append(dis_rd)
-            conversions.append(dis_rd.conversion)
-        ri, di = ref_rd.info, dis_rd.info
-        input_info = {**pix, "planes_scored": "yuv", "packed_upload": False,
-                      "conversion": conversions[0] if len(conversions) == 1 else conversions}
+            st.dis = st.own(_RgbReader(st.dis, plain or ri, siting, st.device, st.make, matrix, rgb_range, "distorted"))
+            conversions.append(st.dis.conversion)
+        st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "yuv", "packed_upload": False,
+                    "conversion": conversions[0] if len(conversions) == 1 else conversions}
     elif ri.packed or di.packed:
-        input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False}
-    if (chroma_mismatch == "luma" and ri.bit_depth == di.bit_depth
+        st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False}
+
+
+def _match_chroma(st: _Clips, mode: str, siting) -> None:
+    """chroma_mismatch: "luma" scores both clips as luma-only clips, "convert" takes the distorted clip to the reference's
+    layout, siting and depth"""
+    ri, di = st.ri, st.di
+    if (mode == "luma" and ri.bit_depth == di.bit_depth
             and (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono)):
-        input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "y", "packed_upload": False}
-        ref_rd, dis_rd = _LumaReader(ref_rd), _LumaReader(dis_rd)
-        ri, di = ref_rd.info, dis_rd.info
-    converter = None
-    if (chroma_mismatch == "convert" and ri.mono == di.mono and not ri.mono
+        st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "y", "packed_upload": False}
+        st.ref, st.dis = _LumaReader(st.ref), _LumaReader(st.dis)
+    if (mode == "convert" and ri.mono == di.mono and not ri.mono
             and ri.bit_depth in N.CONVERT_BIT_DEPTHS and di.bit_depth in N.CONVERT_BIT_DEPTHS
             and (ri.hshift, ri.vshift, ri.bit_depth) != (di.hshift, di.vshift, di.bit_depth)):
-        dis_rd = converter = _ConvertedReader(dis_rd, ri, chroma_siting, device,
-                                              engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
-        input_info = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "yuv", "packed_upload": False,
-                      "conversion": {"side": "distorted", "from": di.pix_fmt, "to": converter.info.pix_fmt,
-                                     "bit_depth": [di.bit_depth, ri.bit_depth],
-                                     "siting": {"from": list(converter.src_siting), "to": list(converter.dst_siting)}}}
-        di = dis_rd.info
+        st.dis = converter = st.own(_ConvertedReader(st.dis, ri, siting, st.device, st.make))
+        st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "yuv", "packed_upload": False,
+                    "conversion": {"side": "distorted", "from": di.pix_fmt, "to": converter.info.pix_fmt,
+                                   "bit_depth": [di.bit_depth, ri.bit_depth],
+                                   "siting": {"from": list(converter.src_siting), "to": list(converter.dst_siting)}}}
+
+
+def _match_size(st: _Clips, resize) -> None:
+    """the clips must agree in size and pixel format by now; resize= takes the distorted clip to the reference's size"""
+    ri, di = st.ri, st.di
     if resize is not None and resize not in N.RESAMPLE_FILTERS:
         raise ValueError(f"resize must be None or one of {sorted(N.RESAMPLE_FILTERS)}")
     if resize is None and (ri.width, ri.height) != (di.width, di.height):
         raise ValueError(f"reference is {ri.width}x{ri.height} but distorted is {di.width}x{di.height}")
     if ri.bit_depth != di.bit_depth or (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono):
         raise ValueError("reference and distorted clips differ in pixel format")
-    resized = resampler = None
     if resize is not None:
-        resized = {"filter": resize, "from": [di.width, di.height], "to": [ri.width, ri.height],
-                   "applied": (ri.width, ri.height) != (di.width, di.height)}
-        if resized["applied"]:
-            dis_rd = resampler = _ResampledReader(dis_rd, ri, resize, device,
-                                                  engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
-            di = dis_rd.info
-    alignment = None
+        st.resize = {"filter": resize, "from": [di.width, di.height], "to": [ri.width, ri.height],
+                     "applied": (ri.width, ri.height) != (di.width, di.height)}
+        if st.resize["applied"]:
+            st.dis = st.own(_ResampledReader(st.dis, ri, resize, st.device, st.make))
+
+
+def _align_time(st: _Clips, align, align_frames, penalty_mse) -> None:
     if align:
         if align < 0 or align > 64:
             raise ValueError("align must be 0 ... 64 frames")
-        alignment = _find_alignment(ref_rd, dis_rd, int(align), align_frames, align_penalty_mse, device,
-                                    engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
-        k = alignment["offset_frames"]
-        ref_rd, dis_rd = _ShiftedReader(ref_rd, max(0, -k)), _ShiftedReader(dis_rd, max(0, k))
-    if active_picture is not None:
-        if active_picture not in ("report", "apply"):
+        st.alignment = _find_alignment(st.ref, st.dis, int(align), align_frames, penalty_mse, st.device, st.make)
+        k = st.alignment["offset_frames"]
+        st.ref, st.dis = _ShiftedReader(st.ref, max(0, -k)), _ShiftedReader(st.dis, max(0, k))
+
+
+def _crop_window(st: _Clips, crop, dis_rd=None) -> None:
+    """both clips cut by the margins [left, top, right, bottom] (dis_rd: the captured clip to cut, when a step has just made it)"""
+    left, top, right, bottom = crop
+    cw, ch = st.ri.width - left - right, st.ri.height - top - bottom
+    st.ref, st.dis = _CroppedReader(st.ref, left, top, cw, ch), _CroppedReader(st.dis if dis_rd is None else dis_rd, left, top, cw, ch)
+
+
+def _crop_active(st: _Clips, mode, frames, limit, skip) -> None:
+    if mode is not None:
+        if mode not in ("report", "apply"):
             raise ValueError('active_picture must be None, "report" or "apply"')
-        if active_frames is None or active_frames < 1:
+        if frames is None or frames < 1:
             raise ValueError("active_frames must be positive")
-        if active_limit is None or not 0 <= active_limit <= 255:
+        if limit is None or not 0 <= limit <= 255:
             raise ValueError("active_limit must be 0 ... 255")
-        if active_skip is None or active_skip < 0:
+        if skip is None or skip < 0:
             raise ValueError("active_skip must not be negative")
-        active = _find_active(ref_rd, dis_rd, int(active_frames), int(active_limit), int(active_skip), active_picture == "apply",
-                              device, engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
-        alignment = dict(alignment or {}, active_picture=active)
+        active = _find_active(st.ref, st.dis, int(frames), int(limit), int(skip), mode == "apply", st.device, st.make)
+        st.alignment = dict(st.alignment or {}, active_picture=active)
         if active["applied"]:
-            left, top, right, bottom = active["crop"]
-            cw, ch = ri.width - left - right, ri.height - top - bottom
-            ref_rd, dis_rd = _CroppedReader(ref_rd, left, top, cw, ch), _CroppedReader(dis_rd, left, top, cw, ch)
-            ri, di = ref_rd.info, dis_rd.info
-    if spatial_align:
-        if spatial_align < 0 or spatial_align > 16:
+            _crop_window(st, active["crop"])
+
+
+def _align_shift(st: _Clips, R, frames) -> None:
+    if R:
+        if R < 0 or R > 16:
             raise ValueError("spatial_align must be 0 ... 16 pixels")
-        if spatial_frames is None or spatial_frames < 1:
+        if frames is None or frames < 1:
             raise ValueError("spatial_frames must be positive")
-        if ri.width <= 2 * spatial_align or ri.height <= 2 * spatial_align:
-            raise ValueError(f"spatial_align {spatial_align} needs a frame larger than {2 * spatial_align} pixels each way")
-        spatial = _find_shift(ref_rd, dis_rd, int(spatial_align), int(spatial_frames), device,
-                              engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)))
-        alignment = dict(alignment or {}, spatial=spatial)
+        if st.ri.width <= 2 * R or st.ri.height <= 2 * R:
+            raise ValueError(f"spatial_align {R} needs a frame larger than {2 * R} pixels each way")
+        spatial = _find_shift(st.ref, st.dis, int(R), int(frames), st.device, st.make)
+        st.alignment = dict(st.alignment or {}, spatial=spatial)
         if spatial["applied"]:
-            ref_rd, dis_rd = crop_readers(ref_rd, dis_rd, spatial["dx"], spatial["dy"])
-            ri, di = ref_rd.info, dis_rd.info
-    registered = None
-    if register is not None:
-        if register not in N.RESAMPLE_FILTERS:
+            st.ref, st.dis = crop_readers(st.ref, st.dis, spatial["dx"], spatial["dy"])
+
+
+def _register(st: _Clips, filter, frames, min_px) -> None:
+    if filter is not None:
+        if filter not in N.RESAMPLE_FILTERS:
             raise ValueError(f"register must be None or one of {sorted(N.RESAMPLE_FILTERS)}")
-        if register_frames is None or register_frames < 1:
+        if frames is None or frames < 1:
             raise ValueError("register_frames must be positive")
-        if register_min_px is None or not register_min_px >= 0:
+        if min_px is None or not min_px >= 0:
             raise ValueError("register_min_px must not be negative")
-        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
-        geometry = _find_geometry(ref_rd, dis_rd, register, int(register_frames), float(register_min_px), device, make_side)
-        alignment = dict(alignment or {}, geometry=geometry)
+        geometry = _find_geometry(st.ref, st.dis, filter, int(frames), float(min_px), st.device, st.make)
+        st.alignment = dict(st.alignment or {}, geometry=geometry)
         if geometry["applied"]:
-            registered = _RegisteredReader(dis_rd, geometry, device, make_side)
-            left, top, right, bottom = geometry["crop"]
-            cw, ch = ri.width - left - right, ri.height - top - bottom
-            ref_rd, dis_rd = _CroppedReader(ref_rd, left, top, cw, ch), _CroppedReader(registered, left, top, cw, ch)
-            ri, di = ref_rd.info, dis_rd.info
-    tabled = None
-    if level_align is not None:
-        if level_align not in ("report", "apply"):
+            _crop_window(st, geometry["crop"], st.own(_RegisteredReader(st.dis, geometry, st.device, st.make)))
+
+
+def _align_levels(st: _Clips, mode, frames, curve) -> None:
+    if mode is not None:
+        if mode not in ("report", "apply"):
             raise ValueError('level_align must be None, "report" or "apply"')
-        if level_frames is None or level_frames < 1:
+        if frames is None or frames < 1:
             raise ValueError("level_frames must be positive")
-        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
-        levels, luts, curves = _find_levels(ref_rd, dis_rd, int(level_frames), level_align == "apply", device, make_side,
-                                            curve=bool(level_curve), full_range=di.color_range == "full")
-        alignment = dict(alignment or {}, levels=levels)
+        levels, luts, curves = _find_levels(st.ref, st.dis, int(frames), mode == "apply", st.device, st.make,
+                                            curve=bool(curve), full_range=st.di.color_range == "full")
+        st.alignment = dict(st.alignment or {}, levels=levels)
         if any(lut is not None for lut in luts):
-            dis_rd = _LevelledReader(dis_rd, luts)
+            st.dis = _LevelledReader(st.dis, luts)
         if any(t is not None for t in curves):
-            dis_rd = tabled = _TableReader(dis_rd, curves, device, make_side)
-    elif level_curve:
+            st.dis = st.own(_TableReader(st.dis, curves, st.device, st.make))
+    elif curve:
         raise ValueError('level_curve needs level_align="report" or "apply"')
-    coloured = None
-    if colour_align is not None:
-        if colour_align not in ("report", "apply"):
+
+
+def _align_colour(st: _Clips, mode, frames, full_range) -> None:
+    if mode is not None:
+        if mode not in ("report", "apply"):
             raise ValueError('colour_align must be None, "report" or "apply"')
-        if colour_frames is None or colour_frames < 1:
+        if frames is None or frames < 1:
             raise ValueError("colour_frames must be positive")
-        if ri.mono:
+        if st.ri.mono:
             raise ValueError("colour alignment needs the chroma planes, but the clips are monochrome")
-        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
-        full = (di.color_range == "full") if colour_full_range is None else bool(colour_full_range)
-        colour = _find_colour(ref_rd, dis_rd, int(colour_frames), colour_align == "apply", full, device, make_side)
-        alignment = dict(alignment or {}, colour=colour)
+        full = (st.di.color_range == "full") if full_range is None else bool(full_range)
+        colour = _find_colour(st.ref, st.dis, int(frames), mode == "apply", full, st.device, st.make)
+        st.alignment = dict(st.alignment or {}, colour=colour)
         if colour["applied"]:
-            dis_rd = coloured = _ColourReader(dis_rd, colour["correction"], device, make_side)
-    overlay = None
-    masked = []
-    if overlay_mask is not None or overlay_boxes is not None:
-        if overlay_mask not in ("report", "neutral", "reference"):
+            st.dis = st.own(_ColourReader(st.dis, colour["correction"], st.device, st.make))
+
+
+def _mask_overlay(st: _Clips, mode, boxes, frames, tile, grow, feather, share) -> None:
+    if mode is not None or boxes is not None:
+        if mode not in ("report", "neutral", "reference"):
             raise ValueError('overlay_mask must be None, "report", "neutral" or "reference"')
-        if overlay_frames is None or overlay_frames < 1:
+        if frames is None or frames < 1:
             raise ValueError("overlay_frames must be positive")
-        if overlay_tile not in N.FLOW_TILES:
+        if tile not in N.FLOW_TILES:
             raise ValueError("overlay_tile must be a tile size of 8, 16, 32 or 64")
-        if overlay_grow is None or overlay_grow < 0:
+        if grow is None or grow < 0:
             raise ValueError("overlay_grow must not be negative")
-        if overlay_feather is None or overlay_feather < 0 or overlay_feather % OVERLAY_NODE:
+        if feather is None or feather < 0 or feather % OVERLAY_NODE:
             raise ValueError(f"overlay_feather must be a multiple of {OVERLAY_NODE}, or 0")
-        if overlay_share is None or not 0 < overlay_share <= 1:
+        if share is None or not 0 < share <= 1:
             raise ValueError("overlay_share must lie in (0, 1]")
-        make_side = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw))
-        overlay, mask = _find_overlay(ref_rd, dis_rd, overlay_mask, overlay_boxes, int(overlay_frames), int(overlay_tile),
-                                      int(overlay_grow), int(overlay_feather), overlay_share, device, make_side)
-        if overlay["applied"] and overlay_mask == "neutral":
-            masked = [_MaskedReader(rd, mask, overlay["fill"], None, device, make_side) for rd in (ref_rd, dis_rd)]
-            ref_rd, dis_rd = masked
-        elif overlay["applied"]:
-            masked = [_MaskedReader(dis_rd, mask, None, ref_rd, device, make_side)]
-            dis_rd = masked[0]
-    n = min(len(ref_rd), len(dis_rd))
+        st.overlay, mask = _find_overlay(st.ref, st.dis, mode, boxes, int(frames), int(tile), int(grow), int(feather), share,
+                                         st.device, st.make)
+        if st.overlay["applied"] and mode == "neutral":
+            st.ref, st.dis = [st.own(_MaskedReader(rd, mask, st.overlay["fill"], None, st.device, st.make)) for rd in (st.ref, st.dis)]
+        elif st.overlay["applied"]:
+            st.dis = st.own(_MaskedReader(st.dis, mask, None, st.ref, st.device, st.make))
+
+
+def _check_planes(name: str, value, mono: bool) -> None:
+    if value not in ("y", "all"):
+        raise ValueError(f'{name} must be "y" or "all"')
+    if value == "all" and mono:
+        raise ValueError(f'{name}="all" needs the chroma planes, but the clips are monochrome')
+
+
+def _check_passes(st: _Clips, *, distortion_map, distortion_planes, distortion_factor, distortion_min_mse, spectrum, spectrum_planes,
+                  spectrum_min_mse, spectrum_gain_floor, temporal, temporal_planes, temporal_min_mse, temporal_blend_min,
+                  temporal_still_mse, temporal_pop_factor, coding_grid, grid_planes, grid_periods, grid_z2, delta_itp, itp_matrix,
+                  itp_range, itp_peak, itp_threshold, **_):
+    """(the number of frame pairs, the grid periods to search or None, the Delta E ITP spec or None): the options of the
+    passes that run after the scoring, checked on the clips as every alignment step left them"""
+    ri = st.ri
+    n = min(len(st.ref), len(st.dis))
     if n <= 0:
         raise ValueError("no frames to analyse")
     if distortion_map:
         if distortion_map not in N.FLOW_TILES:
             raise ValueError("distortion_map must be 0 or a tile size of 8, 16, 32 or 64")
-        if distortion_planes not in ("y", "all"):
-            raise ValueError('distortion_planes must be "y" or "all"')
-        if distortion_planes == "all" and ri.mono:
-            raise ValueError('distortion_planes="all" needs the chroma planes, but the clips are monochrome')
+        _check_planes("distortion_planes", distortion_planes, ri.mono)
         if distortion_factor is None or distortion_factor < 0 or distortion_min_mse is None or distortion_min_mse < 0:
             raise ValueError("distortion_factor and distortion_min_mse must not be negative")
     if spectrum is None or isinstance(spectrum, bool) or int(spectrum) != spectrum or not 0 <= spectrum <= 6:
         raise ValueError("spectrum must be 0 or a number of levels, 1 ... 6")
     if spectrum:
-        if spectrum_planes not in ("y", "all"):
-            raise ValueError('spectrum_planes must be "y" or "all"')
-        if spectrum_planes == "all" and ri.mono:
-            raise ValueError('spectrum_planes="all" needs the chroma planes, but the clips are monochrome')
+        _check_planes("spectrum_planes", spectrum_planes, ri.mono)
         if spectrum_min_mse is None or spectrum_min_mse < 0 or spectrum_gain_floor is None or spectrum_gain_floor < 0:
             raise ValueError("spectrum_min_mse and spectrum_gain_floor must not be negative")
     if temporal is None or isinstance(temporal, bool) or (temporal and temporal not in N.FLOW_TILES):
         raise ValueError("temporal must be 0 or a tile size of 8, 16, 32 or 64")
     if temporal:
-        if temporal_planes not in ("y", "all"):
-            raise ValueError('temporal_planes must be "y" or "all"')
-        if temporal_planes == "all" and ri.mono:
-            raise ValueError('temporal_planes="all" needs the chroma planes, but the clips are monochrome')
+        _check_planes("temporal_planes", temporal_planes, ri.mono)
         if any(v is None or v < 0 for v in (temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)):
             raise ValueError("temporal_min_mse, temporal_blend_min, temporal_still_mse and temporal_pop_factor must not be negative")
+    periods = None
     if coding_grid:
-        if grid_planes not in ("y", "all"):
-            raise ValueError('grid_planes must be "y" or "all"')
-        if grid_planes == "all" and ri.mono:
-            raise ValueError('grid_planes="all" needs the chroma planes, but the clips are monochrome')
+        _check_planes("grid_planes", grid_planes, ri.mono)
         try:
             g_lo, g_hi = (int(v) for v in grid_periods)
         except (TypeError, ValueError):
@@ -465,6 +620,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             raise ValueError("grid_periods must be a pair (lo, hi) with 4 <= lo <= hi <= 64")
         if grid_z2 is None or grid_z2 < 0:
             raise ValueError("grid_z2 must not be negative")
+        periods = range(g_lo, g_hi + 1)
     itp_spec = None
     if delta_itp is not None:
         from . import itp as ITP
@@ -476,6 +632,14 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
             raise ValueError('itp_range must be None, "full" or "limited"')
         itp_full = (ri.color_range == "full") if itp_range is None else itp_range == "full"
         itp_spec = ITP.spec(delta_itp, itp_matrix, itp_full, ri.bit_depth, itp_peak, itp_threshold, height=ri.height)
+    return n, periods, itp_spec
+
+
+def _feature_mask(st: _Clips, model, *, psnr, ssim, integrity, integrity_options, float_ssim, ms_ssim, ciede, cambi, cambi_full_ref,
+                  psnr_hvs, xpsnr, siti):
+    """the _Plan of the scoring context: the checks of the feature options, the model, the planes and the feature mask"""
+    from . import integrity as IG
+    ri, di = st.ri, st.di
     if cambi_full_ref and not cambi:
         raise ValueError("cambi_full_ref needs cambi")
     if ciede and ri.mono:
@@ -497,56 +661,56 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     if siti:
         feats |= N.FEAT_SITI | (N.FEAT_SITI_REF_FULL if ri.color_range == "full" else 0)
         feats |= N.FEAT_SITI_DIS_FULL if di.color_range == "full" else 0
+    ig_opts = ig_thr = None
     if integrity:
         feats |= N.FEAT_INTEGRITY
         ig_opts = IG.options(integrity_options)
         ig_thr = IG.black_threshold(di.bit_depth, di.color_range == "full", ig_opts["pixel_black_th"])
-    a, b = shard.shard_bounds(n, world_size, rank)
-    t_start = time.perf_counter()
+    want = [i for i, on in enumerate((want_ext, psnr_hvs, xpsnr, siti, integrity)) if on]
+    return _Plan(mdl, n_planes, feats, want, ig_opts, ig_thr)
 
-    make = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, reuse=True, **kw))   # a parked context of this configuration
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=n_planes,
-               chroma_shift=(ri.hshift, ri.vshift), features=feats, device=device, max_batch=max_batch,
-               result_capacity=max(b - a, 16), n_subsample=n_subsample,
-               vif_enhn_gain_limit=mdl.vif_enhn_gain_limit, adm_enhn_gain_limit=mdl.adm_enhn_gain_limit,
-               vif_border=mdl.vif_border, **({"fixed_point": int(fixed_point)} if fixed_point else {}))
-    try:
-        if a > 0 and xpsnr:   # xpsnr's temporal term reads two frames back: frames a-1 and a-2 (motion's halo is a-1)
-            eng.set_ref_history([ref_rd.frame(a - 1)[0]] + ([ref_rd.frame(a - 2)[0]] if a >= 2 else []))
-        elif a > 0:
-            eng.set_motion_halo(ref_rd.frame(a - 1)[0])   # one-frame halo in front of this rank's chunk
-        if integrity:
-            eng.set_black_threshold(ig_thr)
-        if a > 0 and integrity:   # the differences continue from every plane of the distorted frame a-1 (siti's TI too)
-            eng.set_dis_history_planes(dis_rd.frame(a - 1)[:n_planes])
-        elif a > 0 and siti:    # siti's TI of the distorted clip continues from its frame a-1 (the reference's: the halo)
-            eng.set_dis_history(dis_rd.frame(a - 1)[0])
-        # both clips are files of packed planes (.y4m): the library reads them straight into its pinned staging (pqa_submit_fd:
-        # one copy, no page faults) instead of copying frames out of the readers' mappings
-        by_fd = all(hasattr(r, "fileno") and hasattr(r, "plane_offsets") for r in (ref_rd, dis_rd)) and hasattr(eng, "submit_file")
-        # ... and a run of frames that lie equally spaced in both files goes down in ONE call (pqa_submit_fd_run: reading frame
-        # k + 1 overlaps the upload of frame k inside the library); 8 = a staging half, and the grain of progress / cancel
-        by_run = (by_fd and hasattr(eng, "submit_file_run") and all(hasattr(r, "run_stride") for r in (ref_rd, dis_rd))
-                  and os.environ.get("PQA_FD_RUN", "1") != "0")   # PQA_FD_RUN=0: frame by frame (A/B partner)
-        # a packed capture file that reaches this loop unwrapped goes down as packed bytes, 8 frames a call (pqa_submit_packed)
-        by_packed = hasattr(eng, "submit_packed") and any(hasattr(r, "packed_frame") for r in (ref_rd, dis_rd))
-        if input_info is not None:
-            input_info["packed_upload"] = bool(by_packed)
-            input_info["planes_scored"] = "y" if n_planes == 1 else "yuv"
-        i = a
-        while i < b:
-            if cancelled is not None and cancelled():
-                eng.cancel()
-                raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
-            if by_packed:
-                m = min(8, b - i)
-                eng.submit_packed(i, *[([r.packed_frame(j) for j in range(i, i + m)], r.info.packed) if hasattr(r, "packed_frame")
-                                       else ([r.frame(j)[:n_planes] for j in range(i, i + m)], None) for r in (ref_rd, dis_rd)])
-                i += m
-                if progress is not None:
-                    progress(i - a, b - a)
-                continue
-            m = 1
+
+def _arm_histories(st: _Clips, eng, a: int, n_planes: int, xpsnr, siti, integrity, ig_thr) -> None:
+    """a rank whose chunk starts at frame a > 0 continues from the frames in front of it"""
+    ref_rd, dis_rd = st.ref, st.dis
+    if a > 0 and xpsnr:   # xpsnr's temporal term reads two frames back: frames a-1 and a-2 (motion's halo is a-1)
+        eng.set_ref_history([ref_rd.frame(a - 1)[0]] + ([ref_rd.frame(a - 2)[0]] if a >= 2 else []))
+    elif a > 0:
+        eng.set_motion_halo(ref_rd.frame(a - 1)[0])   # one-frame halo in front of this rank's chunk
+    if integrity:
+        eng.set_black_threshold(ig_thr)
+    if a > 0 and integrity:   # the differences continue from every plane of the distorted frame a-1 (siti's TI too)
+        eng.set_dis_history_planes(dis_rd.frame(a - 1)[:n_planes])
+    elif a > 0 and siti:    # siti's TI of the distorted clip continues from its frame a-1 (the reference's: the halo)
+        eng.set_dis_history(dis_rd.frame(a - 1)[0])
+
+
+def _submit_frames(st: _Clips, eng, a: int, b: int, n_planes: int, progress, cancelled) -> None:
+    """frames [a, b) of both clips into the scoring context, by the cheapest route the readers offer"""
+    ref_rd, dis_rd = st.ref, st.dis
+    # both clips are files of packed planes (.y4m): the library reads them straight into its pinned staging (pqa_submit_fd:
+    # one copy, no page faults) instead of copying frames out of the readers' mappings
+    by_fd = all(hasattr(r, "fileno") and hasattr(r, "plane_offsets") for r in (ref_rd, dis_rd)) and hasattr(eng, "submit_file")
+    # ... and a run of frames that lie equally spaced in both files goes down in ONE call (pqa_submit_fd_run: reading frame
+    # k + 1 overlaps the upload of frame k inside the library); 8 = a staging half, and the grain of progress / cancel
+    by_run = (by_fd and hasattr(eng, "submit_file_run") and all(hasattr(r, "run_stride") for r in (ref_rd, dis_rd))
+              and os.environ.get("PQA_FD_RUN", "1") != "0")   # PQA_FD_RUN=0: frame by frame (A/B partner)
+    # a packed capture file that reaches this loop unwrapped goes down as packed bytes, 8 frames a call (pqa_submit_packed)
+    by_packed = hasattr(eng, "submit_packed") and any(hasattr(r, "packed_frame") for r in (ref_rd, dis_rd))
+    if st.input is not None:
+        st.input["packed_upload"] = bool(by_packed)
+        st.input["planes_scored"] = "y" if n_planes == 1 else "yuv"
+    i = a
+    while i < b:
+        if cancelled is not None and cancelled():
+            eng.cancel()
+            raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
+        m = 1
+        if by_packed:
+            m = min(8, b - i)
+            eng.submit_packed(i, *[([r.packed_frame(j) for j in range(i, i + m)], r.info.packed) if hasattr(r, "packed_frame")
+                                   else ([r.frame(j)[:n_planes] for j in range(i, i + m)], None) for r in (ref_rd, dis_rd)])
+        else:
             if by_run:
                 m = min(8, b - i)
                 rs, ds = ref_rd.run_stride(i, m), dis_rd.run_stride(i, m)
@@ -559,286 +723,50 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 eng.submit_file(i, ref_rd.fileno(), ref_rd.plane_offsets(i)[:n_planes], dis_rd.fileno(), dis_rd.plane_offsets(i)[:n_planes])
             else:
                 eng.submit(i, ref_rd.frame(i)[:n_planes], dis_rd.frame(i)[:n_planes])
-            i += m
-            if progress is not None:
-                progress(i - a, b - a)
-        # the extension blocks (N.EXT_BLOCKS) this run reads, in one call; a default run stays on pqa_collect
-        want = [i for i, on in enumerate((want_ext, psnr_hvs, xpsnr, siti, integrity)) if on]
-        if b <= a:
-            local, local_blk = np.zeros((0, N.RECORD_DOUBLES)), {i: np.zeros((0, N.EXT_BLOCKS[i][1])) for i in want}
-        elif want and hasattr(eng, "collect_blocks"):
-            local, local_blk = eng.collect_blocks(a, b - a, want)
-        elif want:   # an engine_factory product from before collect_blocks: its collect_extN that reaches the last wanted block
-            got = getattr(eng, f"collect_ext{want[-1] + 1 if want[-1] else ''}")(a, b - a)
-            local, local_blk = got[0], {i: got[1 + i] for i in want}
-        else:
-            local, local_blk = eng.collect(a, b - a), {}
-    except BaseException:
-        eng.close()
-        raise
-    (eng.release if hasattr(eng, "release") else eng.close)()   # healthy: parked for the next analysis of this geometry
-    dmap = bands = tmom = edges = None
-    if distortion_map or spectrum or temporal or coding_grid:      # ONE pass of its own over the same readers, after the scoring context is parked
-        dmap, bands, tmom, edges = _distortion_pass(ref_rd, dis_rd, a, b, n, int(distortion_map), 3 if distortion_planes == "all" else 1, device,
-                                                    engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)), world_size, rank,
-                                                    gather_device, cancelled, levels=int(spectrum),
-                                                    band_planes=3 if spectrum_planes == "all" else 1, temporal_tile=int(temporal),
-                                                    temporal_planes=3 if temporal_planes == "all" else 1,
-                                                    edge_planes=(3 if grid_planes == "all" else 1) if coding_grid else 0)
-    itp_rows = None
-    if itp_spec is not None:      # a pass of its own over the same readers: every pixel of every plane, on the clips as scored
-        itp_rows = _itp_pass(ref_rd, dis_rd, a, b, n, itp_spec, device, engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, **kw)),
-                             world_size, rank, gather_device, cancelled)
-    rec = shard.gather_records(local, n, world_size, rank, gather_device)
-    blk = {i: shard.gather_records(local_blk[i], n, world_size, rank, gather_device, width=N.EXT_BLOCKS[i][1]) for i in want}
-    if rank != 0:
-        for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured, *masked):
-            if rd is not None:
-                rd.close()
-        return None
-    ig_result = None
-    if integrity:
-        # the state machines run here on the gathered rows of the whole clip (a freeze or a scene score that crosses a shard
-        # boundary needs nothing else: every shard was armed with its frame a-1); freezedetect's anchored SADs, asked for
-        # inside a still run only, come from the distorted file through a context of its own, made on first use
-        plane_sizes = [(di.width, di.height)] + ([(di.chroma_w, di.chroma_h)] * 2 if n_planes == 3 else [])
-        sad_eng, cache = [], {}
-        ext5 = blk.pop(want[-1])   # the last block: its rows go into ig_result, not into finish_records
-
-        def anchored_sad(anchor, i):
-            if (anchor, i) not in cache:
-                if not sad_eng:
-                    sad_eng.append(make(di.width, di.height, bit_depth=di.bit_depth, n_planes=n_planes,
-                                        chroma_shift=(di.hshift, di.vshift), features=N.FEAT_INTEGRITY, device=device,
-                                        max_batch=8, result_capacity=16))
-                cache.clear()
-                hi = min(n, i + 8)    # a still run asks for consecutive frames against one anchor: fetch a few at once
-                got = sad_eng[0].frame_sad(dis_rd.frame(anchor)[:n_planes], [dis_rd.frame(j)[:n_planes] for j in range(i, hi)])
-                for j in range(i, hi):
-                    cache[(anchor, j)] = got[j - i, :n_planes].astype(np.float64)
-            return cache[(anchor, i)]
-        try:
-            ig_result = IG.analyze(ext5[:, N.EXT5_SAD_PREV:N.EXT5_SAD_PREV + n_planes], ext5[:, N.EXT5_BLACK_COUNT],
-                                   width=di.width, height=di.height, plane_sizes=plane_sizes, bit_depth=di.bit_depth,
-                                   fps_num=di.fps_num, fps_den=di.fps_den, opts=ig_opts, anchored_sad=anchored_sad)
-        finally:
-            for e in sad_eng:
-                e.close()
-    elapsed = time.perf_counter() - t_start
-    extra = {N.EXT_BLOCKS[i][0]: rows for i, rows in blk.items()}   # finish_records takes a block under its name in the table
-    flags = dict(float_ssim=float_ssim, ms_ssim=ms_ssim, ciede=ciede, cambi=cambi, cambi_full_ref=cambi_full_ref,
-                 psnr_hvs=psnr_hvs, xpsnr=xpsnr, siti=siti)
-    extra.update({k: True for k, v in flags.items() if v})
-    if integrity:
-        extra.update(integrity=ig_result)
-    res = finish_records(rec, mdl, ri, psnr=psnr, ssim=ssim, n_subsample=n_subsample, n_planes=n_planes,
-                         fps=n / elapsed if elapsed > 0 else 0.0, **extra)
-    if dmap is not None:
-        _distortion_result(res, dmap, ri, int(distortion_map), distortion_factor, distortion_min_mse, distortion_dir)
-    if bands is not None:
-        _spectrum_result(res, bands, ri, int(spectrum), spectrum_min_mse, spectrum_gain_floor)
-    if tmom is not None:
-        _temporal_result(res, tmom, ri, int(temporal), temporal_min_mse, temporal_blend_min, temporal_still_mse, temporal_pop_factor)
-    if edges is not None:
-        _grid_result(res, edges, ri, range(g_lo, g_hi + 1), grid_z2)
-    if itp_rows is not None:
-        _itp_result(res, itp_rows, itp_spec)
-    if alignment is not None:
-        res["alignment"] = alignment
-    if resized is not None:
-        res["resize"] = resized
-    if input_info is not None:
-        res["input"] = input_info
-    if overlay is not None:
-        res["overlay"] = overlay
-    for rd in (*rgb_readers, converter, resampler, registered, tabled, coloured, *masked):   # on an error their contexts go with the readers
-        if rd is not None:
-            rd.close()
-    return res
+        i += m
+        if progress is not None:
+            progress(i - a, b - a)
 
 
-class _ResampledReader:
-    """A captured clip resampled to the reference's frame size: what score_files reads under resize=.  Every plane is resized
-    to the reference's plane of the same kind (FeatureEngine.resample) on a small context of its own, as _find_shift makes
-    one; frames are fetched in runs of eight, so that a run is one upload, one launch and one download per plane kind, and the
-    last run is kept.  `info` carries the reference's width and height.  No file-descriptor path: the resampled samples exist
-    in host arrays only, so the frames go down through FeatureEngine.submit.  close() frees the context (as does dropping the
-    reader)."""
-    RUN = 8
-
-    def __init__(self, reader, ref_info, filter: str, device, make):
-        import dataclasses
-        src = reader.info
-        self._rd, self._filter = reader, filter
-        self.info = dataclasses.replace(src, width=ref_info.width, height=ref_info.height)
-        self._shapes = [(self.info.height, self.info.width)] + ([(self.info.chroma_h, self.info.chroma_w)] * 2 if not src.mono else [])
-        self._eng = make(ref_info.width, ref_info.height, bit_depth=src.bit_depth, n_planes=1, chroma_shift=(src.hshift, src.vshift),
-                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd)
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
-            planes = [self._eng.resample([f[p] for f in frames], shape, self._filter) for p, shape in enumerate(self._shapes)]
-            self._first, self._run = first, [[planes[p][k] for p in range(len(self._shapes))] for k in range(len(frames))]
-        return self._run[i - self._first]
+def _collect(eng, a: int, b: int, want):
+    """(the records of frames [a, b), {i: the rows of extension block i for i in want})"""
+    if b <= a:
+        return np.zeros((0, N.RECORD_DOUBLES)), {i: np.zeros((0, N.EXT_BLOCKS[i][1])) for i in want}
+    if want and hasattr(eng, "collect_blocks"):
+        return eng.collect_blocks(a, b - a, want)
+    if want:   # an engine_factory product from before collect_blocks: its collect_extN that reaches the last wanted block
+        got = getattr(eng, f"collect_ext{want[-1] + 1 if want[-1] else ''}")(a, b - a)
+        return got[0], {i: got[1 + i] for i in want}
+    return eng.collect(a, b - a), {}
 
 
-CHROMA_SITINGS = {"left": (0, 1), "center": (1, 1), "topleft": (0, 0)}   # chroma_siting= -> (hsite, vsite)
+def _integrity_events(st: _Clips, make, ext5, n: int, n_planes: int, ig_opts) -> dict:
+    # rank 0: the state machines run here on the gathered rows `ext5` of the whole clip (a freeze or a scene score that crosses a shard
+    # boundary needs nothing else: every shard was armed with its frame a-1); freezedetect's anchored SADs, asked for
+    # inside a still run only, come from the distorted file through a context of its own, made on first use
+    from . import integrity as IG
+    dis_rd, di = st.dis, st.di
+    sad_eng, cache = [], {}
 
-
-class _ConvertedReader:
-    """A captured clip in the reference's pixel format -- chroma layout, chroma siting and bit depth --: what score_files reads
-    under chroma_mismatch="convert".  Built like _ResampledReader: a small context of its own, frames fetched in runs of
-    eight, one FeatureEngine.format_convert call per plane kind (the luma: a depth change only, skipped when the depths agree;
-    U and V in ONE call as 2n planes), the last run kept.  `info` carries the reference's shifts, depth and chroma tag.  A
-    packed capture file is read through its numpy unpack: its packed frames are not on offer.  No file-descriptor path.
-    close() frees the context."""
-    RUN = 8
-
-    def __init__(self, reader, ref_info, siting, device, make):
-        import dataclasses
-        src = reader.info
-        self._rd = reader
-        self.info = dataclasses.replace(src, bit_depth=ref_info.bit_depth, hshift=ref_info.hshift, vshift=ref_info.vshift,
-                                        chroma_tag=ref_info.chroma_tag, packed=None)
-        forced = CHROMA_SITINGS[siting] if siting is not None else None
-        self.src_siting, self.dst_siting = ([(s[0] if i.hshift else 0, s[1] if i.vshift else 0) for i, s in
-                                             ((src, forced or src.chroma_siting), (ref_info, forced or ref_info.chroma_siting))])
-        self._luma_shape = (src.height, src.width)
-        self._src = (src.hshift, src.vshift, *self.src_siting, src.bit_depth)
-        self._dst = (ref_info.hshift, ref_info.vshift, *self.dst_siting, ref_info.bit_depth)
-        self._eng = make(src.width, src.height, bit_depth=ref_info.bit_depth, n_planes=1, chroma_shift=(ref_info.hshift, ref_info.vshift),
-                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd)
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
-            n = len(frames)
-            if self._src[4] != self._dst[4]:
-                luma = self._eng.format_convert([f[0] for f in frames], self._luma_shape, (0, 0, 0, 0, self._src[4]), (0, 0, 0, 0, self._dst[4]))
-            else:
-                luma = [f[0] for f in frames]
-            chroma = self._eng.format_convert([f[1] for f in frames] + [f[2] for f in frames], self._luma_shape, self._src, self._dst)
-            self._first, self._run = first, [[luma[k], chroma[k], chroma[n + k]] for k in range(n)]
-        return self._run[i - self._first]
-
-
-def yuvio_info_444(info):
-    """the 4:4:4 Y'CbCr clip of an RGB clip's own size and depth: what two RGB clips are both converted to"""
-    import dataclasses
-    return dataclasses.replace(info, hshift=0, vshift=0, mono=False, chroma_tag="444" if info.bit_depth == 8 else f"444p{info.bit_depth}",
-                               color_range=None, packed=None)
-
-
-class _RgbReader:
-    """A packed RGB clip (yuvio.RgbReader) as Y'CbCr planes in the pixel format of its partner -- chroma layout, siting, depth and
-    range --: what score_files reads in place of an RGB file.  Built like _ConvertedReader: a small context of its own, packed
-    frames fetched in runs of eight, ONE FeatureEngine.rgb_convert call a run (unpack, matrix, range, depth, subsampling and
-    siting in one pass with one rounding), the last run kept.  `info` carries the partner's shifts, depth, chroma tag and
-    range; `conversion` is the object score_files reports.  No file-descriptor path.  close() frees the context."""
-    RUN = 8
-
-    def __init__(self, reader, partner, siting, device, make, matrix, rgb_range, side):
-        import dataclasses
-        from . import rgb as RGB
-        src = reader.info
-        if partner.bit_depth not in N.RGB_BIT_DEPTHS:
-            raise ValueError(f"a packed RGB clip is converted to 8 or 10 bit, not to the {partner.bit_depth}-bit {partner.pix_fmt} "
-                             "of the other clip")
-        if partner.mono:
-            raise ValueError("a packed RGB clip cannot be scored against a monochrome clip")
-        self._rd, self.format = reader, src.packed
-        self.info = dataclasses.replace(src, bit_depth=partner.bit_depth, hshift=partner.hshift, vshift=partner.vshift,
-                                        chroma_tag=partner.chroma_tag, color_range=partner.color_range, packed=None)
-        forced = CHROMA_SITINGS[siting] if siting is not None else None
-        s = forced or partner.chroma_siting
-        self.dst_siting = (s[0] if partner.hshift else 0, s[1] if partner.vshift else 0)
-        self.matrix = matrix or RGB.default_matrix(src.height)
-        self.rgb_range = rgb_range or RGB.default_range(self.format)
-        self.yuv_range = "full" if partner.color_range == "full" else "limited"
-        self.coefficients = RGB.conversion_matrix(self.matrix, src.bit_depth, self.rgb_range == "full", partner.bit_depth,
-                                                  self.yuv_range == "full")
-        self._shape = (src.height, src.width)
-        self._dst = (partner.hshift, partner.vshift, *self.dst_siting, partner.bit_depth)
-        self.conversion = {"side": side, "from": src.pix_fmt, "to": self.info.pix_fmt, "matrix": self.matrix, "rgb_range": self.rgb_range,
-                           "yuv_range": self.yuv_range, "bit_depth": [src.bit_depth, partner.bit_depth],
-                           "siting": {"to": list(self.dst_siting)}, "coefficients": [int(v) for v in self.coefficients]}
-        self._eng = make(src.width, src.height, bit_depth=partner.bit_depth, n_planes=1, chroma_shift=(partner.hshift, partner.vshift),
-                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd)
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            packed = [self._rd.packed_frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
-            self._first, self._run = first, self._eng.rgb_convert(packed, self.format, self._shape, self._dst, self.coefficients)
-        return self._run[i - self._first]
-
-    def __iter__(self):
-        for i in range(len(self)):
-            yield self.frame(i)
-
-
-class _RegisteredReader:
-    """A captured clip resampled onto the reference grid through the window of a measured geometry (the `geometry` object of
-    _find_geometry): what score_files reads under register= once the map is applied.  Built like _ResampledReader -- a small
-    context of its own, frames fetched in runs of eight, the last run kept --; every plane keeps its size.  The luma window is
-    the measured one; a chroma plane of n_c samples along an axis gets geometry_window(d / 2^shift, s, n_c).  No
-    file-descriptor path.  close() frees the context."""
-    RUN = 8
-
-    def __init__(self, reader, geometry: dict, device, make):
-        from . import align as AL
-        info = self.info = reader.info
-        self._rd, self._filter = reader, geometry["filter"]
-        dx, sx = AL.window_geometry(geometry["x0_q16"], geometry["w_q16"], info.width)
-        dy, sy = AL.window_geometry(geometry["y0_q16"], geometry["h_q16"], info.height)
-        self._shapes = [(info.height, info.width)] + ([(info.chroma_h, info.chroma_w)] * 2 if not info.mono else [])
-        self.windows = [(geometry["x0_q16"], geometry["y0_q16"], geometry["w_q16"], geometry["h_q16"])]
-        if not info.mono:
-            (x0, ww), (y0, wh) = (AL.geometry_window(dx / (1 << info.hshift), sx, info.chroma_w),
-                                  AL.geometry_window(dy / (1 << info.vshift), sy, info.chroma_h))
-            self.windows += [(x0, y0, ww, wh)] * 2
-        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=1, chroma_shift=(info.hshift, info.vshift),
-                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd)
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            frames = [self._rd.frame(j) for j in range(first, min(first + self.RUN, len(self._rd)))]
-            planes = [self._eng.resample([f[p] for f in frames], shape, self._filter, tuple(v / 65536.0 for v in win))
-                      for p, (shape, win) in enumerate(zip(self._shapes, self.windows))]
-            self._first, self._run = first, [[planes[p][k] for p in range(len(self._shapes))] for k in range(len(frames))]
-        return self._run[i - self._first]
+    def anchored_sad(anchor, i):
+        if (anchor, i) not in cache:
+            if not sad_eng:
+                sad_eng.append(make(di.width, di.height, bit_depth=di.bit_depth, n_planes=n_planes,
+                                    chroma_shift=(di.hshift, di.vshift), features=N.FEAT_INTEGRITY, device=st.device,
+                                    max_batch=8, result_capacity=16))
+            cache.clear()
+            hi = min(n, i + 8)    # a still run asks for consecutive frames against one anchor: fetch a few at once
+            got = sad_eng[0].frame_sad(dis_rd.frame(anchor)[:n_planes], [dis_rd.frame(j)[:n_planes] for j in range(i, hi)])
+            for j in range(i, hi):
+                cache[(anchor, j)] = got[j - i, :n_planes].astype(np.float64)
+        return cache[(anchor, i)]
+    try:
+        return IG.analyze(ext5[:, N.EXT5_SAD_PREV:N.EXT5_SAD_PREV + n_planes], ext5[:, N.EXT5_BLACK_COUNT],
+                          width=di.width, height=di.height, plane_sizes=_plane_sizes(di, n_planes), bit_depth=di.bit_depth,
+                          fps_num=di.fps_num, fps_den=di.fps_den, opts=ig_opts, anchored_sad=anchored_sad)
+    finally:
+        for e in sad_eng:
+            e.close()
 
 
 def registration_crop(geometry: dict, width: int, height: int, hshift: int = 0, vshift: int = 0):
@@ -867,16 +795,10 @@ def _find_geometry(ref_rd, dis_rd, filter: str, n_frames: int, min_px: float, de
     of its own"""
     from . import align as AL
     ri = ref_rd.info
-    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
-    if not idx:
-        raise ValueError("no frames to align")
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
-               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-    try:
+    idx = _sample(ref_rd, dis_rd, n_frames, "no frames to align")
+    with closing(_clip_context(make, device, ri)) as eng:
         geo = AL.register(eng.flow_moments, eng.resample, [ref_rd.frame(i)[0] for i in idx], [dis_rd.frame(i)[0] for i in idx],
                           filter=filter, tile=REGISTER_TILE, levels=None)
-    finally:
-        eng.close()
     geo["frames"] = len(idx)
     geo["filter"] = filter
     geo["applied"] = AL.geometry_applied(geo, min_px)
@@ -885,121 +807,15 @@ def _find_geometry(ref_rd, dis_rd, filter: str, n_frames: int, min_px: float, de
     return geo
 
 
-class _LumaReader:
-    """The luma of a clip as a monochrome clip: what score_files reads under chroma_mismatch="luma".  A packed capture file
-    keeps its packed frames on offer: a luma-only context decodes no chroma from them."""
-
-    def __init__(self, reader):
-        import dataclasses
-        self._rd = reader
-        self.info = dataclasses.replace(reader.info, mono=True, hshift=0, vshift=0)
-        if hasattr(reader, "packed_frame"):
-            self.packed_frame = reader.packed_frame
-
-    def __len__(self):
-        return len(self._rd)
-
-    def frame(self, i: int):
-        return self._rd.frame(i)[:1]
-
-
-class _ShiftedReader:
-    """A clip from its frame `start` on: what score_files reads once the alignment offset is known."""
-
-    def __init__(self, reader, start: int):
-        self._rd, self._start = reader, int(start)
-        self.info = reader.info
-        if hasattr(reader, "packed_frame"):   # a packed capture file stays one (the scoring loop's submit_packed)
-            self.packed_frame = lambda i: reader.packed_frame(i + self._start)
-        for name in ("fileno", "plane_offsets", "run_stride"):   # the file-descriptor submit path, where the reader has it
-            if hasattr(reader, name):
-                setattr(self, name, getattr(self, "_" + name))
-
-    def __len__(self):
-        return max(0, len(self._rd) - self._start)
-
-    def frame(self, i: int):
-        return self._rd.frame(i + self._start)
-
-    def _fileno(self):
-        return self._rd.fileno()
-
-    def _plane_offsets(self, i: int):
-        return self._rd.plane_offsets(i + self._start)
-
-    def _run_stride(self, i: int, n: int):
-        return self._rd.run_stride(i + self._start, n)
-
-
-class _CroppedReader:
-    """A clip cut to the window of `width` x `height` luma pixels at (x0, y0): what score_files reads once the spatial shift
-    is known.  Frames are strided views of the wrapped reader's planes (nothing is copied); chroma planes are cut at
-    (x0 >> hshift, y0 >> vshift) to the chroma size of the window.  No file-descriptor path: rows of a window do not lie
-    packed in the file, so the frames go down through FeatureEngine.submit."""
-
-    def __init__(self, reader, x0: int, y0: int, width: int, height: int):
-        import dataclasses
-        src = reader.info
-        if x0 < 0 or y0 < 0 or width < 1 or height < 1 or x0 + width > src.width or y0 + height > src.height:
-            raise ValueError("crop window outside the frame")
-        self._rd, self._x0, self._y0 = reader, int(x0), int(y0)
-        self.info = dataclasses.replace(src, width=int(width), height=int(height))
-
-    def __len__(self):
-        return len(self._rd)
-
-    def windows(self):
-        """[(y0, x0, h, w)] of every plane, in samples of that plane"""
-        i = self.info
-        out = [(self._y0, self._x0, i.height, i.width)]
-        if not i.mono:
-            out += [(self._y0 >> i.vshift, self._x0 >> i.hshift, i.chroma_h, i.chroma_w)] * 2
-        return out
-
-    def frame(self, i: int):
-        planes = self._rd.frame(i)
-        return [p[y:y + h, x:x + w] for p, (y, x, h, w) in zip(planes, self.windows())]
-
-
-def crop_readers(ref_rd, dis_rd, dx: int, dy: int):
-    """both clips cut to their common window under the displacement (dx, dy) of the captured picture: reference pixel (x, y)
-    meets captured pixel (x + dx, y + dy)"""
-    w, h = ref_rd.info.width - abs(dx), ref_rd.info.height - abs(dy)
-    x0, y0 = max(0, -dx), max(0, -dy)
-    return _CroppedReader(ref_rd, x0, y0, w, h), _CroppedReader(dis_rd, x0 + dx, y0 + dy, w, h)
-
-
-class _LevelledReader:
-    """A captured clip with its sample levels mapped back onto the reference's: plane p of every frame goes through the
-    integer table luts[p] (numpy.take; None: the plane is passed on as it is).  What score_files reads under
-    level_align="apply".  No file-descriptor path: the mapped samples exist in host arrays only, so the frames go down
-    through FeatureEngine.submit."""
-
-    def __init__(self, reader, luts):
-        self._rd, self._luts = reader, list(luts)
-        self.info = reader.info
-
-    def __len__(self):
-        return len(self._rd)
-
-    def frame(self, i: int):
-        planes = self._rd.frame(i)
-        return [p if k >= len(self._luts) or self._luts[k] is None else np.take(self._luts[k], p) for k, p in enumerate(planes)]
-
-
 def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make, curve: bool = False, full_range: bool = True):
     """(the `levels` object, [a correction table or None per plane], [a curve table or None per plane]) of two opened, paired
     clips: the per-level transfer table of a few pairs of every plane on a small context of its own.  curve: the monotone
     curve on top (align.best_curve), and under `apply` the check of its inverse on the sampled pairs"""
     from . import align as AL
     ri = ref_rd.info
-    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
-    if not idx:
-        raise ValueError("no frames to align")
+    idx = _sample(ref_rd, dis_rd, n_frames, "no frames to align")
     n_planes = 1 if ri.mono else 3
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=n_planes, chroma_shift=(ri.hshift, ri.vshift),
-               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-    try:
+    with closing(_clip_context(make, device, ri, n_planes)) as eng:
         refs, caps = [ref_rd.frame(i) for i in idx], [dis_rd.frame(i) for i in idx]
         tables = [eng.level_stats([f[p] for f in refs], [f[p] for f in caps], p) for p in range(n_planes)]
         checked = {}   # plane -> (its curve table, the squared error that is left on the sampled pairs)
@@ -1012,8 +828,6 @@ def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make, curve
                     checked[p] = table, AL.table_sse(eng.level_stats([f[p] for f in refs], mapped, p))
         else:
             found = [AL.best_levels(T, ri.bit_depth, chroma=p > 0) for p, T in enumerate(tables)]
-    finally:
-        eng.close()
     planes, luts, curves = {}, [], []
     for p, lv in enumerate(found):
         is_curve = lv["kind"] == "curve"
@@ -1028,67 +842,6 @@ def _find_levels(ref_rd, dis_rd, n_frames: int, apply: bool, device, make, curve
     return dict(planes["y"], planes=planes), luts, curves
 
 
-class _TableReader:
-    """A captured clip with its sample levels mapped back through a transfer curve: plane p of every frame goes through the
-    integer table tables[p] on the GPU (FeatureEngine.table_apply; None: the plane is passed on as it is).  What score_files
-    reads under level_align="apply" with level_curve for the planes of kind "curve".  Built like _ColourReader -- a small
-    context of its own, frames fetched in runs of eight, the last run kept, one call per corrected plane and run.  No
-    file-descriptor path: the mapped samples exist in host arrays only.  close() frees the context."""
-    RUN = 8
-
-    def __init__(self, reader, tables, device, make):
-        info = self.info = reader.info
-        self._rd, self._tables = reader, list(tables)
-        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=1 if info.mono else 3,
-                         chroma_shift=(info.hshift, info.vshift), features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd)
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            frames = [list(self._rd.frame(j)) for j in range(first, min(first + self.RUN, len(self._rd)))]
-            for p, table in enumerate(self._tables):
-                if table is not None:
-                    for f, mapped in zip(frames, self._eng.table_apply([f[p] for f in frames], table, p)):
-                        f[p] = mapped
-            self._first, self._run = first, frames
-        return self._run[i - self._first]
-
-
-class _ColourReader:
-    """A captured clip with every frame mapped through a 3 x 4 integer matrix (FeatureEngine.colour_apply): the counterpart of
-    _LevelledReader for a map that couples the planes, and what score_files reads under colour_align="apply".  Built like
-    _RegisteredReader -- a small context of its own, frames fetched in runs of eight, the last run kept.  No file-descriptor
-    path: the mapped samples exist in host arrays only.  close() frees the context."""
-    RUN = 8
-
-    def __init__(self, reader, matrix, device, make):
-        info = self.info = reader.info
-        self._rd, self._m = reader, [int(v) for v in matrix]
-        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=3, chroma_shift=(info.hshift, info.vshift),
-                         features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd)
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            frames = [self._rd.frame(j)[:3] for j in range(first, min(first + self.RUN, len(self._rd)))]
-            self._first, self._run = first, self._eng.colour_apply(frames, self._m)
-        return self._run[i - self._first]
-
-
 OVERLAY_NODE = 8      # luma samples between the nodes of an overlay mask: 4:2:0 chroma takes the same grid at step 4
 
 
@@ -1099,9 +852,7 @@ def _find_overlay(ref_rd, dis_rd, mode: str, boxes, n_frames: int, tile: int, gr
     from the tiles' sums of r, which is exact, or under `boxes` from the frames themselves."""
     from . import distortion as D
     ri = ref_rd.info
-    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
-    if not idx:
-        raise ValueError("no frames to analyse")
+    idx = _sample(ref_rd, dis_rd, n_frames, "no frames to analyse")
     shift = (0, 0) if ri.mono else (ri.hshift, ri.vshift)
     refs = [ref_rd.frame(i)[0] for i in idx]
     regions = []
@@ -1110,12 +861,9 @@ def _find_overlay(ref_rd, dis_rd, mode: str, boxes, n_frames: int, tile: int, gr
         full = D.mask_alpha(mask["nodes"], ri.width, ri.height, mask["step_log2"], mask["step_log2"]) == D.MASK_FULL
         total, count = sum(int(np.asarray(r)[full].sum(dtype=np.uint64)) for r in refs), int(full.sum()) * len(refs)
     else:
-        eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, features=N.FEAT_PSNR, device=device, max_batch=8,
-                   result_capacity=16)
-        try:
+        # the one context made without chroma_shift, as it always was (a one-plane context reads no chroma)
+        with closing(_side_context(make, device, ri.width, ri.height, ri.bit_depth, None)) as eng:
             Mo = eng.tile_moments(refs, [dis_rd.frame(i)[0] for i in idx], tile)
-        finally:
-            eng.close()
         S, counts = D.tile_sse(Mo), D.tile_counts(ri.width, ri.height, tile)
         hot = D.hot_tiles(S, counts, tile=tile, bit_depth=ri.bit_depth)
         regions = D.persistent_regions(hot, S, counts, share=share, tile=tile, bit_depth=ri.bit_depth, width=ri.width,
@@ -1134,58 +882,14 @@ def _find_overlay(ref_rd, dis_rd, mode: str, boxes, n_frames: int, tile: int, gr
     return overlay, (mask if found else None)
 
 
-class _MaskedReader:
-    """A clip with a burnt-in overlay blended out: plane p of every frame goes through the feathered mask on the GPU
-    (FeatureEngine.mask_blend) towards the constant fills[p] -- or, with `partner`, towards the partner clip's own plane p of
-    the same frame.  The chroma planes take the luma grid at the step their subsampling leaves.  What score_files reads under
-    overlay_mask="neutral" (both clips) and "reference" (the captured clip, partner: the reference).  Built like _TableReader --
-    a small context of its own, frames fetched in runs of eight, the last run kept, one call per plane and run.  No
-    file-descriptor path: the blended samples exist in host arrays only.  close() frees the context."""
-    RUN = 8
-
-    def __init__(self, reader, mask, fills, partner, device, make):
-        info = self.info = reader.info
-        self._rd, self._partner, self._fills = reader, partner, fills
-        self._nodes, s = mask["nodes"], mask["step_log2"]
-        self._steps = [(s, s)] + ([] if info.mono else [(s - info.hshift, s - info.vshift)] * 2)
-        self._eng = make(info.width, info.height, bit_depth=info.bit_depth, n_planes=1 if info.mono else 3,
-                         chroma_shift=(info.hshift, info.vshift), features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        self._first, self._run = 0, []
-
-    def __len__(self):
-        return len(self._rd) if self._partner is None else min(len(self._rd), len(self._partner))
-
-    def close(self):
-        self._eng.close()
-
-    def frame(self, i: int):
-        if not self._first <= i < self._first + len(self._run):
-            first = i - i % self.RUN
-            span = range(first, min(first + self.RUN, len(self)))
-            frames = [list(self._rd.frame(j)) for j in span]
-            towards = [self._partner.frame(j) for j in span] if self._partner is not None else None
-            for p, steps in enumerate(self._steps):
-                fill = [t[p] for t in towards] if towards is not None else self._fills[p]
-                for f, blended in zip(frames, self._eng.mask_blend([f[p] for f in frames], self._nodes, steps, fill, p)):
-                    f[p] = blended
-            self._first, self._run = first, frames
-        return self._run[i - self._first]
-
-
 def _find_colour(ref_rd, dis_rd, n_frames: int, apply: bool, full_range: bool, device, make) -> dict:
     """the `colour` object of two opened, paired colour clips: the cross-plane moments of a few pairs on a small context of its
     own, reduced by align.best_colour"""
     from . import align as AL
     ri = ref_rd.info
-    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
-    if not idx:
-        raise ValueError("no frames to align")
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=3, chroma_shift=(ri.hshift, ri.vshift),
-               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-    try:
+    idx = _sample(ref_rd, dis_rd, n_frames, "no frames to align")
+    with closing(_clip_context(make, device, ri, 3)) as eng:
         G = eng.colour_moments([ref_rd.frame(i)[:3] for i in idx], [dis_rd.frame(i)[:3] for i in idx])
-    finally:
-        eng.close()
     col = AL.best_colour(G, ri.bit_depth, ri.hshift, ri.vshift, full_range=full_range,
                          total_samples=len(idx) * ri.chroma_w * ri.chroma_h)
     col["full_range"] = bool(full_range)
@@ -1200,12 +904,8 @@ def _find_active(ref_rd, dis_rd, n_frames: int, limit: int, skip: int, apply: bo
     small context of its own, reduced by align.active_picture and align.common_window"""
     from . import align as AL
     ri = ref_rd.info
-    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
-    if not idx:
-        raise ValueError("no frames to align")
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
-               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-    try:
+    idx = _sample(ref_rd, dis_rd, n_frames, "no frames to align")
+    with closing(_clip_context(make, device, ri)) as eng:
         found = []
         for rd in (ref_rd, dis_rd):
             lumas = [rd.frame(i)[0] for i in idx]
@@ -1214,8 +914,6 @@ def _find_active(ref_rd, dis_rd, n_frames: int, limit: int, skip: int, apply: bo
             found.append(AL.active_picture(rows, lambda t, b: cols if t == 0 and b == 0 else
                                            eng.line_profiles([y[t:ri.height - b] for y in lumas])[1],
                                            ri.bit_depth, limit=limit, skip=skip))
-    finally:
-        eng.close()
     hs, vs = (0, 0) if ri.mono else (ri.hshift, ri.vshift)
     out = AL.common_window(found[0], found[1], ri.width, ri.height, hs, vs)
     for key in ("scale", "offset"):
@@ -1229,6 +927,34 @@ def _find_active(ref_rd, dis_rd, n_frames: int, limit: int, skip: int, apply: bo
 
 
 DISTORTION_PLANES = ("y", "cb", "cr")
+
+
+def _plane_sizes(info, k: int):
+    """[(width, height)] of the first k planes of a clip"""
+    return [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (k - 1)
+
+
+def _gather_u64(rows: np.ndarray, total: int, world_size: int, rank: int, gather_device) -> np.ndarray:
+    """this rank's uint64 rows [m, ...] -> the uint64 rows [total, ...] of all ranks: they travel as the records do
+    (shard.gather_records: the int64 transport carries the float64 view of a uint64 bit-exactly)"""
+    cells = math.prod(rows.shape[1:])
+    G = shard.gather_records(rows.reshape(rows.shape[0], cells).view(np.float64), total, world_size, rank, gather_device, width=cells)
+    return np.ascontiguousarray(G).view(np.uint64).reshape((total,) + rows.shape[1:])
+
+
+def _add_columns(res, columns: dict) -> None:
+    """per-frame columns of every frame of the clip into res["metrics"], at the frames the result keeps"""
+    keep = np.asarray(res["frame_indices"])
+    for key, col in columns.items():
+        res["metrics"][key] = col[keep]
+
+
+def _sample(ref_rd, dis_rd, n_frames: int, error: str):
+    """the frame numbers a sampled measurement reads (spatial_sample over the common range); none: ValueError(error)"""
+    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
+    if not idx:
+        raise ValueError(error)
+    return idx
 
 
 def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes: int, device, make, world_size: int,
@@ -1253,7 +979,7 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
         band_planes = 0
     if not temporal_tile:
         temporal_planes = 0
-    sizes = [(ri.width, ri.height)] + [(ri.chroma_w, ri.chroma_h)] * (max(n_planes, band_planes, temporal_planes, edge_planes) - 1)
+    sizes = _plane_sizes(ri, max(n_planes, band_planes, temporal_planes, edge_planes))
     edge_rows = [np.zeros((b - a, h + w, N.EDGE_SUMS), np.uint64) for w, h in sizes[:edge_planes]]   # a frame: H row lines, W column lines
     assert N.EDGE_CHUNK == N.TILE_CHUNK
     tgrids = [DM.tile_counts(w, h, temporal_tile).shape for w, h in sizes[:temporal_planes]]
@@ -1265,9 +991,7 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
     band_rows = [np.zeros((b - a, levels, 4, N.BAND_SUMS), np.uint64) for _ in range(band_planes)]
     assert N.BAND_CHUNK == N.TILE_CHUNK
     if b > a:
-        eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
-                   features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        try:
+        with closing(_clip_context(make, device, ri)) as eng:
             for i0 in range(a, b, N.TILE_CHUNK):
                 if cancelled is not None and cancelled():
                     raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
@@ -1289,31 +1013,13 @@ def _distortion_pass(ref_rd, dis_rd, a: int, b: int, n: int, tile: int, n_planes
                 for p in range(edge_planes):
                     er, ec = eng.edge_profiles([f[p] for f in rf], [f[p] for f in df])
                     edge_rows[p][i0 - a:i0 - a + len(idx)] = np.concatenate([er, ec], axis=1)
-        finally:
-            eng.close()
-    bands = []
-    for p in range(band_planes):
-        cells = levels * 4 * N.BAND_SUMS
-        B = shard.gather_records(band_rows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
-        bands.append(np.ascontiguousarray(B).view(np.uint64).reshape(n, levels, 4, N.BAND_SUMS))
-    out = []
-    for p, g in enumerate(grids):
-        cells = g[0] * g[1]
-        S = shard.gather_records(sse[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
-        T = shard.gather_records(sums[p].reshape(1, cells * N.TILE_SUMS).view(np.float64), world_size, world_size, rank,
-                                 gather_device, width=cells * N.TILE_SUMS)
-        out.append((np.ascontiguousarray(S).view(np.uint64).reshape((n,) + g),
-                    np.ascontiguousarray(T).view(np.uint64).sum(axis=0, dtype=np.uint64).reshape(g + (N.TILE_SUMS,))))
-    tmom = []
-    for p, g in enumerate(tgrids):
-        cells = g[0] * g[1] * N.TEMPORAL_SUMS
-        T = shard.gather_records(trows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
-        tmom.append(np.ascontiguousarray(T).view(np.uint64).reshape((n,) + g + (N.TEMPORAL_SUMS,))[1:])   # frame 0 has no transition
+    to = (world_size, rank, gather_device)
+    bands = [_gather_u64(rows, n, *to) for rows in band_rows]
+    out = [(_gather_u64(S, n, *to), _gather_u64(T[None], world_size, *to).sum(axis=0, dtype=np.uint64)) for S, T in zip(sse, sums)]
+    tmom = [_gather_u64(rows, n, *to)[1:] for rows in trows]   # frame 0 has no transition
     edges = []
-    for p, (w, h) in enumerate(sizes[:edge_planes]):
-        cells = (h + w) * N.EDGE_SUMS
-        E = shard.gather_records(edge_rows[p].reshape(b - a, cells).view(np.float64), n, world_size, rank, gather_device, width=cells)
-        E = np.ascontiguousarray(E).view(np.uint64).reshape(n, h + w, N.EDGE_SUMS)
+    for rows, (w, h) in zip(edge_rows, sizes):
+        E = _gather_u64(rows, n, *to)
         edges.append((E[:, :h], E[:, h:]))
     return (out if tile else None), (bands if levels else None), (tmom if temporal_tile else None), (edges if edge_planes else None)
 
@@ -1329,84 +1035,66 @@ def _itp_pass(ref_rd, dis_rd, a: int, b: int, n: int, spec: dict, device, make, 
     rows = np.zeros((b - a, N.ITP_SUMS), np.float64)
     if b > a:
         sp = ITP.native_spec(spec)
-        eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=3, chroma_shift=(ri.hshift, ri.vshift),
-                   features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-        try:
+        with closing(_clip_context(make, device, ri, 3)) as eng:
             for i0 in range(a, b, N.ITP_CHUNK):
                 if cancelled is not None and cancelled():
                     raise N.PqaCancelled(N.PQA_ECANCELLED, "cancelled")
                 idx = range(i0, min(b, i0 + N.ITP_CHUNK))
                 rows[i0 - a:i0 - a + len(idx)] = eng.delta_itp([ref_rd.frame(i)[:3] for i in idx], [dis_rd.frame(i)[:3] for i in idx], sp)
-        finally:
-            eng.close()
     return shard.gather_records(rows, n, world_size, rank, gather_device, width=N.ITP_SUMS)
 
 
 def _itp_result(res, rows, spec: dict) -> None:
     """rank 0: adds res["delta_itp"] (the spec used, coefficients included, and itp.summary) and the three per-frame columns"""
     from . import itp as ITP
-    keep = np.asarray(res["frame_indices"])
-    for key, col in ITP.frame_columns(rows).items():
-        res["metrics"][key] = col[keep]
+    _add_columns(res, ITP.frame_columns(rows))
     res["delta_itp"] = {"spec": dict(spec), "summary": ITP.summary(rows, spec["threshold"])}
 
 
 def _grid_result(res, edges, info, periods, z2_min) -> None:
     """rank 0: the solver on the gathered edge profiles; adds res["coding_grid"] and the two luma columns"""
     from . import grid as GD
-    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(edges) - 1)
     planes = {}
-    for name, (rows, cols), (w, h) in zip(DISTORTION_PLANES, edges, sizes):
+    for name, (rows, cols), (w, h) in zip(DISTORTION_PLANES, edges, _plane_sizes(info, len(edges))):
         planes[name] = GD.analyse(rows, cols, w, h, info.bit_depth, periods=periods, z2_min=z2_min)
         if name == "y":
-            keep = np.asarray(res["frame_indices"])
-            for key, col in GD.frame_columns(planes[name]["frames"]).items():
-                res["metrics"][key] = col[keep]
+            _add_columns(res, GD.frame_columns(planes[name]["frames"]))
     res["coding_grid"] = {"planes": planes}
 
 
 def _temporal_result(res, tmom, info, tile: int, min_mse, blend_min, still_mse, pop_factor) -> None:
     """rank 0: the solver on the gathered temporal moments; adds res["temporal"] and the three luma columns"""
     from . import temporal as TP
-    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(tmom) - 1)
     planes = {}
-    for name, M, (w, h) in zip(DISTORTION_PLANES, tmom, sizes):
+    for name, M, (w, h) in zip(DISTORTION_PLANES, tmom, _plane_sizes(info, len(tmom))):
         planes[name] = TP.analyse(M, w, h, tile, info.bit_depth, min_mse=min_mse, blend_min=blend_min, still_mse=still_mse,
                                   pop_factor=pop_factor)
         if name == "y":
-            keep = np.asarray(res["frame_indices"])
-            for key, col in TP.frame_columns(M, w, h, info.bit_depth).items():
-                res["metrics"][key] = col[keep]
+            _add_columns(res, TP.frame_columns(M, w, h, info.bit_depth))
     res["temporal"] = {"tile": tile, "planes": planes, "frames": int(tmom[0].shape[0]) + 1}
 
 
 def _spectrum_result(res, bands, info, levels: int, min_mse, gain_floor) -> None:
     """rank 0: the solver on the gathered band moments; adds res["spectrum"] and the three luma columns"""
     from . import spectrum as SP
-    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(bands) - 1)
     planes = {}
-    for name, M, (w, h) in zip(DISTORTION_PLANES, bands, sizes):
+    for name, M, (w, h) in zip(DISTORTION_PLANES, bands, _plane_sizes(info, len(bands))):
         planes[name] = SP.analyse(M, w, h, info.bit_depth, min_mse=min_mse, gain_floor=gain_floor)
         if name == "y":
-            keep = np.asarray(res["frame_indices"])
-            for key, col in SP.frame_columns(M, w, h, info.bit_depth).items():
-                res["metrics"][key] = col[keep]
+            _add_columns(res, SP.frame_columns(M, w, h, info.bit_depth))
     res["spectrum"] = {"levels": levels, "planes": planes, "frames": int(bands[0].shape[0])}
 
 
 def _distortion_result(res, dmap, info, tile: int, factor, min_mse, out_dir) -> None:
     """rank 0: the solver on the gathered measurement; adds res["distortion"], the two luma columns and the files"""
     from . import distortion as DM
-    sizes = [(info.width, info.height)] + [(info.chroma_w, info.chroma_h)] * (len(dmap) - 1)
     planes = {}
-    for name, (S, M_sum), (w, h) in zip(DISTORTION_PLANES, dmap, sizes):
+    for name, (S, M_sum), (w, h) in zip(DISTORTION_PLANES, dmap, _plane_sizes(info, len(dmap))):
         found = DM.analyse_plane(S, M_sum, w, h, tile, info.bit_depth, factor=factor, min_mse=min_mse)
         cols, mean_psnr = found.pop("columns"), found.pop("mean_psnr")
         planes[name] = found
         if name == "y":
-            keep = np.asarray(res["frame_indices"])
-            res["metrics"]["tile_psnr_min"] = cols["tile_psnr_min"][keep]
-            res["metrics"]["distortion_concentration"] = cols["concentration"][keep]
+            _add_columns(res, {"tile_psnr_min": cols["tile_psnr_min"], "distortion_concentration": cols["concentration"]})
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, f"distortion_{name}.pgm"), "wb") as f:
@@ -1425,15 +1113,9 @@ def _find_shift(ref_rd, dis_rd, R: int, n_frames: int, device, make) -> dict:
     -R ... R in both directions on a small context of its own"""
     from . import align as AL
     ri = ref_rd.info
-    idx = spatial_sample(min(len(ref_rd), len(dis_rd)), n_frames)
-    if not idx:
-        raise ValueError("no frames to align")
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
-               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-    try:
+    idx = _sample(ref_rd, dis_rd, n_frames, "no frames to align")
+    with closing(_clip_context(make, device, ri)) as eng:
         S = eng.shift_sse([ref_rd.frame(i)[0] for i in idx], [dis_rd.frame(i)[0] for i in idx], R)
-    finally:
-        eng.close()
     sp = AL.best_shift(S, R, (ri.width - 2 * R) * (ri.height - 2 * R))
     sp["frames"] = len(idx)
     sp["applied"] = bool(not sp["at_edge"] and (sp["dx"], sp["dy"]) != (0, 0))
@@ -1452,12 +1134,8 @@ def _find_alignment(ref_rd, dis_rd, K: int, align_frames, penalty_mse, device, m
         n_ref, n_dis = min(n_ref, int(align_frames)), min(n_dis, int(align_frames) + K)
     if n_ref <= 0 or n_dis <= 0:
         raise ValueError("no frames to align")
-    eng = make(ri.width, ri.height, bit_depth=ri.bit_depth, n_planes=1, chroma_shift=(ri.hshift, ri.vshift),
-               features=N.FEAT_PSNR, device=device, max_batch=8, result_capacity=16)
-    try:
+    with closing(_clip_context(make, device, ri)) as eng:
         D = eng.cross_sse([ref_rd.frame(i)[0] for i in range(n_ref)], [dis_rd.frame(j)[0] for j in range(n_dis)], -K, K)
-    finally:
-        eng.close()
     return AL.align(D, n_ref, n_dis, ri.width * ri.height, k_lo=-K, fps=ri.fps, bit_depth=ri.bit_depth,
                     penalty_mse=penalty_mse)
 

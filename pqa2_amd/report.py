@@ -264,6 +264,15 @@ def overlay_log_keys(overlay: dict | None) -> dict:
     return {"overlay": distortion_log_keys(overlay)["distortion"]}
 
 
+def result_log_keys(res) -> dict:
+    """The top-level keys of the JSON log that a pipeline.ScoreResult carries besides the frames: build_vmaf_log's extra_top."""
+    return {"model": res["model_name"], **xpsnr_log_keys(res.get("xpsnr_summary")), **integrity_log_keys(res.get("integrity")),
+            **alignment_log_keys(res.get("alignment")), **{k: res[k] for k in ("resize", "input") if res.get(k)},
+            **distortion_log_keys(res.get("distortion")), **spectrum_log_keys(res.get("spectrum")),
+            **temporal_log_keys(res.get("temporal")), **grid_log_keys(res.get("coding_grid")),
+            **itp_log_keys(res.get("delta_itp")), **overlay_log_keys(res.get("overlay"))}
+
+
 def overlay_summary_line(overlay: dict) -> str:
     """One line for a summary or a status bar: the burnt-in overlay and what was done about it."""
     boxes = overlay.get("boxes") or []

@@ -330,18 +330,7 @@ def main(argv=None) -> int:
             if dist.is_initialized():
                 dist.destroy_process_group()
     if rank == 0:
-        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
-                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
-                                     **report.integrity_log_keys(res.get("integrity")),
-                                     **report.alignment_log_keys(res.get("alignment")),
-                                     **({"resize": res["resize"]} if res.get("resize") else {}),
-                                     **({"input": res["input"]} if res.get("input") else {}),
-                                     **report.distortion_log_keys(res.get("distortion")),
-                                     **report.spectrum_log_keys(res.get("spectrum")),
-                                     **report.temporal_log_keys(res.get("temporal")),
-                                     **report.grid_log_keys(res.get("coding_grid")),
-                                     **report.itp_log_keys(res.get("delta_itp")),
-                                     **report.overlay_log_keys(res.get("overlay"))})
+        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"], report.result_log_keys(res))
         report.write_vmaf_json(a.json, log)
         if a.integrity_log and res.get("integrity_lines") is not None:
             with open(a.integrity_log, "w") as f:

@@ -498,18 +498,7 @@ class VMAFAnalyzer(QObject):
             self._fail("VMAF analysis was terminated by user")
             return False
         self.last_fps = res["fps"]
-        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"],
-                                    {"model": res["model_name"], **report.xpsnr_log_keys(res.get("xpsnr_summary")),
-                                     **report.integrity_log_keys(res.get("integrity")),
-                                     **report.alignment_log_keys(res.get("alignment")),
-                                     **({"resize": res["resize"]} if res.get("resize") else {}),
-                                     **({"input": res["input"]} if res.get("input") else {}),
-                                     **report.distortion_log_keys(res.get("distortion")),
-                                     **report.spectrum_log_keys(res.get("spectrum")),
-                                     **report.temporal_log_keys(res.get("temporal")),
-                                     **report.grid_log_keys(res.get("coding_grid")),
-                                     **report.itp_log_keys(res.get("delta_itp")),
-                                     **report.overlay_log_keys(res.get("overlay"))})
+        log = report.build_vmaf_log(res["metrics"], res["fps"], res["frame_indices"], report.result_log_keys(res))
         report.write_vmaf_json(json_path, log)
         if self.integrity_enabled and self._integrity_path and res.get("integrity_lines") is not None:
             with open(self._integrity_path, "w") as f:

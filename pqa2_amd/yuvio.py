@@ -376,7 +376,7 @@ class RgbReader:
     """Headerless packed RGB capture files: .bgra, .argb, .rgba, .abgr (8 bit, rows of 4 * width bytes) and .r210 (10 bit,
     big-endian words; rows padded to 256 bytes per 64 pixels).  Geometry from arguments or a `_WxH` name hint, as PackedReader;
     the frame count from the file size.  packed_frame(i) gives the packed rows as they lie in the file.  An RGB file has no
-    Y'CbCr planes of its own: frame(i) raises, and pipeline._RgbReader (what score_files wraps this reader in) converts the
+    Y'CbCr planes of its own: frame(i) raises, and readers._RgbReader (what score_files wraps this reader in) converts the
     frames on the GPU to the layout, depth and range of the other clip."""
 
     def __init__(self, path: str, width: int | None = None, height: int | None = None, bit_depth: int | None = None,
