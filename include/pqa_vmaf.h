@@ -976,6 +976,45 @@ PQA_API int pqa_temporal_moments_device(pqa_ctx* ctx, const pqa_temporal_spec* s
                                         int32_t n_frames, uint64_t* out);
 PQA_API int pqa_temporal_sums(void);
 
+/* Field alignment: the field-against-field squared errors of n_frames frame pairs of one plane, synchronously -- what
+ * pqa2_amd/fields.py turns into the field structure of a capture: a progressive programme carried over an interlaced link
+ * comes back with one field taken from the neighbouring frame, with both fields in the wrong line positions, or with one
+ * field dropped and the other line-doubled, and a full-reference tool can tell which from exact sums.  Planes of width x
+ * height samples (the spec's, independent of the context's width and height; width 1 ... 8192, height 2 ... 8192), u8 in an
+ * 8-bit context, otherwise u16 of the context's bit depth b (a sample above 2^b - 1 is read as 2^b - 1).  With R_f the
+ * reference and D_f the captured plane of frame f, h2 = floor(height / 2) row pairs (the last row of an odd-height plane is
+ * counted nowhere) and
+ *     E(A, p, B, q) = sum_{i < h2} sum_{x < width} (A[2 i + p][x] - B[2 i + q][x])^2        p, q in {0, 1}
+ * every transition k = 1 ... n_frames - 1 has 14 words:
+ *     out[k-1][2 p + q]     = E(D_k, p, R_k, q)        captured field p against reference field q of the same frame
+ *     out[k-1][4 + 2 p + q] = E(D_k, p, R_{k-1}, q)    the captured field shows the PREVIOUS reference frame (offset -1)
+ *     out[k-1][8 + 2 p + q] = E(D_{k-1}, p, R_k, q)    the previous captured frame's field shows THIS reference frame (offset +1)
+ *     out[k-1][12]          = E(D_k, 0, D_k, 1)        comb of the captured frame
+ *     out[k-1][13]          = E(R_k, 0, R_k, 1)        comb of the reference frame
+ * So captured frame t and parity p have six candidates (q, j), j the reference frame minus the captured frame: j = 0 in record
+ * t - 1, word 2 p + q; j = -1 in record t - 1, word 4 + 2 p + q; j = +1 in record t, word 8 + 2 p + q; all six exist for
+ * t = 1 ... n_frames - 2.  Exact uint64, no floating point anywhere; every word is below 4096 * 8192 * 4095^2 < 2^50.  out
+ * (host) is [max(n_frames - 1, 0)][14].  Any context, no feature bit; buffers are made on first use, grow only and are freed
+ * with the context.  Independent of the scoring chain: a call between two pqa_submit calls changes no record.  PQA_EINVAL,
+ * before any device call, on a null pointer, a bad struct_size, a height below 2, a size above 8192 or a width of 0, a row
+ * pitch that is negative, shorter than a row or no multiple of the sample size, or a negative frame count.  n_frames of 0 or 1
+ * succeeds and writes nothing (out may then be null).  Kernel and accumulator bounds: DESIGN.md section 5.
+ *
+ * pqa_field_moments: frames in HOST memory (ref_frames[f] / dis_frames[f] point at planes, rows *_row_stride bytes apart; the
+ * frames need not be contiguous).  They travel in chunks of 8 pairs through the pinned buffers of pqa_resample, every frame
+ * once: the last pair of a chunk stays on the device as the predecessor of the next chunk's first.
+ * pqa_field_moments_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart),
+ * under the ordering contract of pqa_submit_device. */
+typedef struct pqa_field_spec {
+  uint32_t struct_size;
+  uint32_t width, height; /* of THIS plane: width 1 ... 8192, height 2 ... 8192 */
+} pqa_field_spec;
+PQA_API int pqa_field_moments(pqa_ctx* ctx, const pqa_field_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                              const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out);
+PQA_API int pqa_field_moments_device(pqa_ctx* ctx, const pqa_field_spec* spec, const void* ref, int64_t ref_row_pitch,
+                                     int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                     int32_t n_frames, uint64_t* out);
+
 /* Coding-grid detection: the gradient energy per LINE of n_frames frame pairs of one plane, synchronously -- what
  * pqa2_amd/grid.py turns into the period and phase of a block grid: the one artefact an encoder leg leaves and no other leg
  * does, which neither the tile moments (per tile) nor the band moments (per octave) localise.  Planes of width x height samples

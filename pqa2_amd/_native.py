@@ -66,7 +66,7 @@ GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 EXPORTS = [
     "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
     "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_submit_packed", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
-    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_mask_blend", "pqa_mask_blend_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_itp_sums", "pqa_delta_itp", "pqa_delta_itp_device", "pqa_set_luma_gray",
+    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_mask_blend", "pqa_mask_blend_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_field_moments", "pqa_field_moments_device", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_itp_sums", "pqa_delta_itp", "pqa_delta_itp_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape", "pqa_debug_adm_need",
     "pqa_debug_partial_counts",
@@ -194,6 +194,14 @@ class PqaTemporalSpec(C.Structure):
 
 TEMPORAL_SUMS, TEMPORAL_CHUNK = 7, 8               # sums a tile / frame pairs a chunk of temporal_moments.hip (kernels.h)
 TEMPORAL_SIGNED = (0, 1, 4, 5)                     # the words of a tile that are int64: sum a, sum b, sum a b, sum a e
+
+
+class PqaFieldSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+FIELD_SUMS, FIELD_CHUNK = 14, 8                    # words a transition / frame pairs a chunk of field_moments.hip (kernels.h)
+FIELD_COLS, FIELD_ROWS = 128, 128                  # columns / rows of a workgroup's block there
 
 
 class PqaEdgeSpec(C.Structure):
@@ -328,6 +336,8 @@ def load():
     lib.pqa_temporal_moments.argtypes = [vp, C.POINTER(PqaTemporalSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32, vp]
     lib.pqa_temporal_moments_device.argtypes = [vp, C.POINTER(PqaTemporalSpec), vp, i64, i64, vp, i64, i64, i32, vp]
     lib.pqa_temporal_sums.argtypes = []
+    lib.pqa_field_moments.argtypes = [vp, C.POINTER(PqaFieldSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32, vp]
+    lib.pqa_field_moments_device.argtypes = [vp, C.POINTER(PqaFieldSpec), vp, i64, i64, vp, i64, i64, i32, vp]
     lib.pqa_temporal_sums.restype = C.c_int
     lib.pqa_edge_profiles.argtypes = [vp, C.POINTER(PqaEdgeSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32, vp]
     lib.pqa_edge_profiles_device.argtypes = [vp, C.POINTER(PqaEdgeSpec), vp, i64, i64, vp, i64, i64, i32, vp]

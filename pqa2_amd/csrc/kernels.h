@@ -589,6 +589,23 @@ hipError_t launch_temporal_moments(hipStream_t stream, Elem elem, int bits, cons
                                    int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
                                    int n_frames, int w, int h, int tile, bool walk, unsigned long long* out);
 
+// ---- field alignment: field-against-field squared errors of a clip pair (field_moments.hip) ----------------------------------
+// With E(A, p, B, q) = sum over the row pairs i < h / 2 and the columns of (A[2 i + p][x] - B[2 i + q][x])^2, for the transitions
+// k = 1 ... n_frames - 1: out[k-1][2 p + q] = E(D_k, p, R_k, q), out[k-1][4 + 2 p + q] = E(D_k, p, R_{k-1}, q),
+// out[k-1][8 + 2 p + q] = E(D_{k-1}, p, R_k, q), out[k-1][12] = E(D_k, 0, D_k, 1), out[k-1][13] = E(R_k, 0, R_k, 1), exact
+// uint64, for n_frames plane pairs of w x h samples (w 1 ... 8192, h 2 ... 8192; the last row of an odd height is not counted;
+// frame f at base + f * frame_pitch, pitches in elements; u8 / u16 samples of `bits` bits, a sample above 2^bits - 1 is read as
+// that).  out: device memory of field_out_bytes(), zeroed by the launch.  n_frames <= 1 launches nothing.  A workgroup reads a
+// block of kFieldCols columns by kFieldRows rows of the four planes of a transition.
+constexpr int kFieldSums = 14;    // words a transition
+constexpr int kFieldChunk = 8;    // frame pairs per launch of the two entries (the host entry keeps one more as predecessor)
+constexpr int kFieldCols = 128;   // columns of a workgroup's block
+constexpr int kFieldRows = 128;   // rows of a workgroup's block: 64 row pairs
+size_t field_out_bytes(int n_frames);
+hipError_t launch_field_moments(hipStream_t stream, Elem elem, int bits, const void* ref, int64_t ref_row_pitch,
+                                int64_t ref_frame_pitch, const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch,
+                                int n_frames, int w, int h, unsigned long long* out);
+
 // ---- coding-grid detection: gradient energy per line of a frame pair (edge_profiles.hip) -------------------------------------
 // With a / b the difference of a sample of the reference / captured plane and its upper neighbour (row line y = 1 ... h - 1,
 // summed over x) or its left neighbour (column line x = 1 ... w - 1, summed over y): out[f][y][0..2] = sum a^2, sum b^2,

@@ -82,6 +82,7 @@ enum SideBuf {
   SIDE_TILE_OUT,                                                               // pqa_tile_moments[_device], tile_moments.hip: the sums
   SIDE_BAND_PART, SIDE_BAND_OUT,                                               // pqa_band_moments[_device], band_moments.hip: the workgroups' partial sums of a chunk, the sums
   SIDE_TEMPORAL_OUT,                                                           // pqa_temporal_moments[_device], temporal_moments.hip: the sums
+  SIDE_FIELD_OUT,                                                              // pqa_field_moments[_device], field_moments.hip: the sums
   SIDE_EDGE_OUT,                                                               // pqa_edge_profiles[_device], edge_profiles.hip: the profiles
   SIDE_TABLE_LUT,                                                              // pqa_table_apply[_device], table_apply.hip: the table
   SIDE_ITP_PART, SIDE_ITP_OUT,                                                 // pqa_delta_itp[_device], delta_itp.hip: the tiles' partial sums of a chunk, the sums

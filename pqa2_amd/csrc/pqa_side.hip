@@ -532,6 +532,21 @@ int temporal_moments(pqa_ctx* c, const pqa_temporal_spec* sp, const Clip& ref, c
   });
 }
 
+// field alignment (field_moments.hip): a result per transition, so `out` may be null below two frames; a plane has a row pair
+template <class Clip>
+int field_moments(pqa_ctx* c, const pqa_field_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, uint64_t* out) {
+  const int rc = spec_check(c, "field_moments", sp, 1, ref.at, dis.at, n_frames, out, 2, [&] {
+    return sp->height < 2 ? fail(c, PQA_EINVAL, "field_moments: height %u has no row pair", sp->height) : PQA_OK;
+  });
+  if (rc != PQA_OK) return rc;
+  const int w = (int)sp->width, h = (int)sp->height;
+  const PairJob j{"field_moments", host::plane_clip((size_t)w * c->esize, h), n_frames, kFieldChunk, 1, SIDE_FIELD_OUT, field_out_bytes(n_frames), out};
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_field_moments(c->stream, c->elem, (int)c->cfg.bit_depth, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch,
+                                d->frame_pitch, n, w, h, (unsigned long long*)c->side_buf[SIDE_FIELD_OUT] + (size_t)at * kFieldSums);
+  });
+}
+
 // coding-grid detection (edge_profiles.hip)
 template <class Clip>
 int edge_profiles(pqa_ctx* c, const pqa_edge_spec* sp, const Clip& ref, const Clip& dis, int32_t n_frames, uint64_t* out) {
@@ -1549,6 +1564,15 @@ int pqa_temporal_moments_device(pqa_ctx* c, const pqa_temporal_spec* spec, const
 int pqa_temporal_moments(pqa_ctx* c, const pqa_temporal_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
                          const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
   return temporal_moments(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
+}
+
+int pqa_field_moments_device(pqa_ctx* c, const pqa_field_spec* spec, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch,
+                             const void* dis, int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, uint64_t* out) {
+  return field_moments(c, spec, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, out);
+}
+int pqa_field_moments(pqa_ctx* c, const pqa_field_spec* spec, const void* const* ref_frames, int64_t ref_row_stride,
+                      const void* const* dis_frames, int64_t dis_row_stride, int32_t n_frames, uint64_t* out) {
+  return field_moments(c, spec, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, out);
 }
 
 int pqa_edge_sums(void) { return kEdgeSums; }

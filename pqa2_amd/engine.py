@@ -926,6 +926,33 @@ class FeatureEngine:
         return self._profile_split(self._plane_call_resident("line_profiles", (ptr, row_pitch, frame_pitch), n_frames, sp,
                                                              self._lines_out(n_frames, sp, 2)), sp)
 
+    # -- field alignment -------------------------------------------------------------------------
+    @staticmethod
+    def _field_spec(shape):
+        return FeatureEngine._plane_spec(N.PqaFieldSpec, shape)
+
+    @staticmethod
+    def _field_out(n, sp):
+        return np.zeros((max(int(n) - 1, 0), N.FIELD_SUMS), np.uint64)
+
+    def field_moments(self, ref_frames, dis_frames, shape=None) -> np.ndarray:
+        """[n - 1, 14] uint64: per transition k = 1 ... n - 1 the squared errors of field against field, E(A, p, B, q) summed
+        over the row pairs: words 2 p + q: captured field p of frame k against reference field q of frame k; 4 + 2 p + q:
+        against reference frame k - 1; 8 + 2 p + q: captured frame k - 1 against reference frame k; 12 / 13: the comb of the
+        captured / reference frame k, exact (pqa_field_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory: two
+        lists of 2-D arrays (views are fine) of equal length and of `shape` = (height, width), default the first frame's,
+        which need not be this context's (width 1 ... 8192, height 2 ... 8192); samples of this context's bit depth.  Fewer
+        than two frames give an empty result.  fields.segments and fields.summary read the result."""
+        return self._plane_call("field_moments", (ref_frames, dis_frames), shape, self._field_spec, self._field_out)[0]
+
+    def field_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
+                               dis_frame_pitch: int, shape, n_frames: int) -> np.ndarray:
+        """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_field_moments_device)."""
+        sp = self._field_spec(shape)
+        return self._plane_call_resident("field_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
+                                         n_frames, sp, self._field_out(n_frames, sp))
+
     # -- coding-grid detection -----------------------------------------------------------------
     @staticmethod
     def _edge_spec(shape):

@@ -18,7 +18,7 @@ from . import model as M
 from . import report, shard
 from .readers import (CHROMA_SITINGS, _ColourReader, _ConvertedReader, _CroppedReader, _LevelledReader, _LumaReader,  # noqa: F401
                       _MaskedReader, _RegisteredReader, _ResampledReader, _RgbReader, _ShiftedReader, _TableReader,
-                      _clip_context, _side_context, crop_readers, yuvio_info_444)
+                      _WovenReader, _clip_context, _side_context, crop_readers, yuvio_info_444)
 from .yuvio import open_video
 
 
@@ -55,7 +55,8 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 itp_matrix: str | None = None, itp_range: str | None = None, itp_peak: float | None = None,
                 itp_threshold: float = 1.0, overlay_mask: str | None = None, overlay_boxes=None, overlay_frames: int = 32,
                 overlay_tile: int = 16, overlay_grow: int = 1, overlay_feather: int = 16,
-                overlay_share: float = 0.9) -> ScoreResult | None:
+                overlay_share: float = 0.9, field_align: str | None = None, field_frames: int | None = None,
+                field_penalty_mse: float | None = None) -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -147,6 +148,22 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     (`correction`: its 12 integers, else null), maps every captured frame through that inverse on the GPU before it is scored;
     `applied` says so.  Without `cross_plane` the planes are not coupled and `level_align` is the tool.  A monochrome clip is
     an error.  `colour_align` = None: no measurement.
+    `field_align` = "report" or "apply": the FIELD STRUCTURE of the capture -- a progressive programme carried over an
+    interlaced link comes back with the rows of one parity from the neighbouring frame (field shift), with both fields in the
+    wrong line positions (field swap) or with one field dropped and the other line-doubled (single field).  After the temporal
+    search and before the active picture, the luma of the first `field_frames` frames of the common range (None: all of them)
+    goes through FeatureEngine.field_moments (pqa_field_moments: the exact squared errors of every captured field against both
+    reference fields of the same, the previous and the next frame) in calls of at most 65 frames that overlap by one; every
+    rank does the same.  fields.summary reduces them (`field_penalty_mse`: the cost of a change of state, default that of
+    `align_penalty_mse`): `alignment["fields"]` holds {kind, state, segments, flips, top, bottom, mse_before, mse_after,
+    comb_ratio, static, weavable, frames, transitions, declared, applied, reason}; `declared` = {"reference", "distorted"}: the
+    I tags of the Y4M headers (None where there is none), which inform and decide nothing; `reason` = null, "report",
+    "progressive", "not weavable" or "too few frames".  "report" changes nothing else: the records are those of a run without
+    the option.  "apply" acts only when `weavable` holds and some segment survived as non-identity: the captured clip is
+    re-woven on the host from row slices of its own frames (fields.weave_plan, every plane by the same row-parity rule) and
+    the reference starts at the plan's first output frame (the object gains `u_lo`, `u_hi` and `unfilled`: the output frames
+    [u_lo, u_hi) and the [frame, parity] of every field lost at a flip, which stays as captured).  single_field and
+    vertical_shift are reported, never applied.  `field_align` = None: no measurement.
     `active_picture` = "report" or "apply": before the spatial step (after `resize` and the temporal search, on the pairs it
     found), the black bars of both clips are measured on the luma of `active_frames` frames spread evenly over the common
     range: row and column sums (pqa_line_profiles) reduced by align.active_picture -- a line is dark in a frame when its
@@ -263,6 +280,7 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     _match_chroma(st, chroma_mismatch, chroma_siting)
     _match_size(st, resize)
     _align_time(st, align, align_frames, align_penalty_mse)
+    _align_fields(st, field_align, field_frames, field_penalty_mse)
     _crop_active(st, active_picture, active_frames, active_limit, active_skip)
     _align_shift(st, spatial_align, spatial_frames)
     _register(st, register, register_frames, register_min_px)
@@ -467,6 +485,22 @@ def _align_time(st: _Clips, align, align_frames, penalty_mse) -> None:
         st.alignment = _find_alignment(st.ref, st.dis, int(align), align_frames, penalty_mse, st.device, st.make)
         k = st.alignment["offset_frames"]
         st.ref, st.dis = _ShiftedReader(st.ref, max(0, -k)), _ShiftedReader(st.dis, max(0, k))
+
+
+def _align_fields(st: _Clips, mode, frames, penalty_mse) -> None:
+    if mode is not None:
+        if mode not in ("report", "apply"):
+            raise ValueError('field_align must be None, "report" or "apply"')
+        if frames is not None and frames < 3:
+            raise ValueError("field_frames must be None or at least 3")
+        if penalty_mse is not None and not penalty_mse >= 0:
+            raise ValueError("field_penalty_mse must not be negative")
+        if st.ri.height < 2:
+            raise ValueError("field_align needs a frame of at least two rows")
+        fields, plan = _find_fields(st.ref, st.dis, frames, penalty_mse, mode == "apply", st.device, st.make)
+        st.alignment = dict(st.alignment or {}, fields=fields)
+        if fields["applied"]:
+            st.ref, st.dis = _ShiftedReader(st.ref, plan["u_lo"]), _WovenReader(st.dis, plan)
 
 
 def _crop_window(st: _Clips, crop, dis_rd=None) -> None:
@@ -1121,6 +1155,34 @@ def _find_shift(ref_rd, dis_rd, R: int, n_frames: int, device, make) -> dict:
     sp["applied"] = bool(not sp["at_edge"] and (sp["dx"], sp["dy"]) != (0, 0))
     sp["chroma_exact"] = bool(ri.mono or (sp["dx"] % (1 << ri.hshift) == 0 and sp["dy"] % (1 << ri.vshift) == 0))
     return sp
+
+
+FIELD_CALL = 65   # frames a call of the field measurement: 64 transitions; consecutive calls share a frame
+
+
+def _find_fields(ref_rd, dis_rd, n_frames, penalty_mse, apply: bool, device, make):
+    """(the `fields` object, the weave plan or None) of two opened, paired clips: the field moments of the luma of the first
+    n_frames frames of the common range (None: all) on a small context of its own, reduced by fields.summary"""
+    from . import fields as FL
+    ri = ref_rd.info
+    n_all = min(len(ref_rd), len(dis_rd))
+    n = n_all if n_frames is None else min(n_all, int(n_frames))
+    parts = []
+    with closing(_clip_context(make, device, ri)) as eng:
+        for a in range(0, max(n - 1, 0), FIELD_CALL - 1):
+            span = range(a, min(a + FIELD_CALL, n))
+            parts.append(eng.field_moments([ref_rd.frame(i)[0] for i in span], [dis_rd.frame(i)[0] for i in span]))
+    X = np.concatenate(parts) if parts else np.zeros((0, N.FIELD_SUMS), np.uint64)
+    out = FL.summary(X, ri.width, ri.height, ri.bit_depth, penalty_mse)
+    moved = any(g["kind"] != "progressive" for g in out["segments"])
+    reason = ("too few frames" if n < 3 else "report" if not apply else "progressive" if not moved else
+              None if out["weavable"] else "not weavable")
+    plan = FL.weave_plan([(g["first"], g["last"], g["state"]) for g in out["segments"]], n_all) if reason is None else None
+    out.update(frames=n, transitions=int(X.shape[0]), declared={"reference": ri.interlace, "distorted": dis_rd.info.interlace},
+               applied=reason is None, reason=reason)
+    if plan is not None:   # what the weave does: the output frames [u_lo, u_hi) and the fields left as captured
+        out.update(u_lo=plan["u_lo"], u_hi=plan["u_hi"], unfilled=[list(v) for v in plan["unfilled"]])
+    return out, plan
 
 
 def _find_alignment(ref_rd, dis_rd, K: int, align_frames, penalty_mse, device, make) -> dict:

@@ -1,6 +1,6 @@
 """The reader wrappers of pipeline.score_files: each wraps a reader (yuvio.open_video's, or another wrapper) once a step has
-changed a clip and offers `info`, len() and frame(i).  Four are plain host views (_LumaReader, _ShiftedReader, _CroppedReader,
-_LevelledReader); seven put the frames through a GPU transform on a small context of their own, eight at a time (_RunReader)."""
+changed a clip and offers `info`, len() and frame(i).  Five are plain host views (_LumaReader, _ShiftedReader, _CroppedReader,
+_WovenReader, _LevelledReader); seven put the frames through a GPU transform on a small context of their own, eight at a time (_RunReader)."""
 from __future__ import annotations
 
 import dataclasses
@@ -305,6 +305,35 @@ class _CroppedReader:
     def frame(self, i: int):
         planes = self._rd.frame(i)
         return [p[y:y + h, x:x + w] for p, (y, x, h, w) in zip(planes, self.windows())]
+
+
+class _WovenReader:
+    """A captured clip with its fields put back where they belong: what score_files reads under field_align="apply".  `plan` is
+    fields.weave_plan's: output frame i is frame u = u_lo + i, and its rows of parity r are the rows of parity p of captured
+    frame t, (t, p) = plan["sources"][i][r] -- row slices [r::2] and [p::2] of host arrays.  EVERY plane follows the same rule: in
+    interlaced 4:2:0 chroma row c belongs to field c & 1.  A row that has no partner (the last row of an odd-height plane when
+    the parities are swapped) stays as captured frame u has it.  No context of its own and no file-descriptor path: the woven
+    samples exist in host arrays only, so the frames go down through FeatureEngine.submit."""
+
+    def __init__(self, reader, plan: dict):
+        self._rd, self._plan = reader, plan
+        self.info = reader.info
+
+    def __len__(self):
+        return self._plan["u_hi"] - self._plan["u_lo"]
+
+    def frame(self, i: int):
+        u = self._plan["u_lo"] + i
+        sources = self._plan["sources"][i]
+        if all(src == (u, r) for r, src in enumerate(sources)):
+            return self._rd.frame(u)
+        out = [np.array(p) for p in self._rd.frame(u)]
+        for r, (t, p) in enumerate(sources):
+            if (t, p) != (u, r):
+                for dst, src in zip(out, self._rd.frame(t)):
+                    rows = min(len(dst[r::2]), len(src[p::2]))
+                    dst[r::2][:rows] = src[p::2][:rows]
+        return out
 
 
 def crop_readers(ref_rd, dis_rd, dx: int, dy: int):

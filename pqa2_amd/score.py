@@ -127,6 +127,18 @@ def main(argv=None) -> int:
     ap.add_argument("--active-skip", type=int, default=0, metavar="N",
                     help="with --active-picture / --active-crop: the outermost N lines of every edge count as dark whatever "
                          "they hold (a caption or timecode line; default 0)")
+    ap.add_argument("--field-align", action="store_true",
+                    help="measure the field structure of the capture (a field from the neighbouring frame, swapped fields, a "
+                         "line-doubled field) from the exact field-against-field errors of the luma; the JSON's alignment "
+                         "object gets a fields entry")
+    ap.add_argument("--field-correct", action="store_true",
+                    help="--field-align, and re-weave the captured clip from its own fields before scoring when the fault is "
+                         "reversible (field shift, field swap)")
+    ap.add_argument("--field-frames", type=int, default=None, metavar="N",
+                    help="with --field-align / --field-correct: measure the first N frames of the common range (default: all)")
+    ap.add_argument("--field-penalty-mse", type=float, default=None, metavar="X",
+                    help="with --field-align / --field-correct: what a change of field structure costs, as an MSE of one frame "
+                         "(default: that of the temporal alignment)")
     ap.add_argument("--distortion-map", type=int, default=0, metavar="T", choices=[0, 8, 16, 32, 64],
                     help="measure WHERE the clips differ: the second-order sums of every T x T tile (8, 16, 32 or 64) of every "
                          "scored frame pair, in a second pass over both clips; the JSON gets a top-level distortion object "
@@ -297,6 +309,8 @@ def main(argv=None) -> int:
                           **({"active_picture": "apply" if a.active_crop else "report", "active_frames": a.active_frames,
                               "active_limit": a.active_limit, "active_skip": a.active_skip}
                              if (a.active_picture or a.active_crop) else {}),
+                          **({"field_align": "apply" if a.field_correct else "report", "field_frames": a.field_frames,
+                              "field_penalty_mse": a.field_penalty_mse} if (a.field_align or a.field_correct) else {}),
                           **({"distortion_map": a.distortion_map, "distortion_planes": a.distortion_planes,
                               "distortion_dir": a.distortion_dir, "distortion_factor": a.distortion_factor,
                               "distortion_min_mse": a.distortion_min_mse} if a.distortion_map else {}),

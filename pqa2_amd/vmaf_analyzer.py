@@ -170,6 +170,8 @@ class VMAFAnalyzer(QObject):
         self.colour_correct_enabled = False   # ... and undo it (implies the measurement; pipeline.score_files(colour_align=))
         self.active_picture_enabled = False   # active-picture detection before scoring: measure the black bars of both clips
         self.active_crop_enabled = False      # ... and crop both to the common rectangle (implies the measurement; score_files(active_picture=))
+        self.field_align_enabled = False      # field alignment before scoring: measure the field structure of the capture
+        self.field_correct_enabled = False    # ... and re-weave a field shift or swap (implies the measurement; score_files(field_align=))
         self.distortion_map_enabled = False   # distortion map: where inside the frame the clips differ (a second pass over both
         self.distortion_tile = 32             # clips; score_files(distortion_map=)); its tile size: 8, 16, 32 or 64
         self.spectrum_enabled = False         # distortion spectrum: what kind of difference the clips have (the same second
@@ -256,6 +258,10 @@ class VMAFAnalyzer(QObject):
                 self.active_picture_enabled = bool(s["active_picture_enabled"])
             if "active_crop_enabled" in s:
                 self.active_crop_enabled = bool(s["active_crop_enabled"])
+            if "field_align_enabled" in s:
+                self.field_align_enabled = bool(s["field_align_enabled"])
+            if "field_correct_enabled" in s:
+                self.field_correct_enabled = bool(s["field_correct_enabled"])
             if "distortion_map_enabled" in s:
                 self.distortion_map_enabled = bool(s["distortion_map_enabled"])
             if "distortion_tile" in s:
@@ -537,6 +543,8 @@ class VMAFAnalyzer(QObject):
                    if (self.colour_align_enabled or self.colour_correct_enabled) else {}),
                 **({"active_picture": "apply" if self.active_crop_enabled else "report"}
                    if (self.active_picture_enabled or self.active_crop_enabled) else {}),
+                **({"field_align": "apply" if self.field_correct_enabled else "report"}
+                   if (self.field_align_enabled or self.field_correct_enabled) else {}),
                 **({"distortion_map": int(self.distortion_tile)} if self.distortion_map_enabled else {}),
                 **({"spectrum": int(self.spectrum_levels)} if self.spectrum_enabled else {}),
                 **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
@@ -599,6 +607,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--active-crop"]
         elif self.active_picture_enabled:
             cmd += ["--active-picture"]
+        if self.field_correct_enabled:
+            cmd += ["--field-correct"]
+        elif self.field_align_enabled:
+            cmd += ["--field-align"]
         if self.distortion_map_enabled:
             cmd += ["--distortion-map", str(int(self.distortion_tile))]
         if self.spectrum_enabled:
@@ -746,7 +758,8 @@ class VMAFAnalyzer(QObject):
             if (self.align_enabled or self.spatial_align_enabled or self.level_align_enabled
                     or self.level_correct_enabled or self.level_curve_enabled or self.register_filter or self.colour_align_enabled
                     or self.colour_correct_enabled or self.active_picture_enabled
-                    or self.active_crop_enabled):   # how the clips were paired, from the log's top level
+                    or self.active_crop_enabled or self.field_align_enabled
+                    or self.field_correct_enabled):   # how the clips were paired, from the log's top level
                 from . import report
                 results["alignment"] = vmaf_data.get("alignment")
                 if results["alignment"] and "offset_frames" in results["alignment"]:

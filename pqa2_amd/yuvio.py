@@ -40,6 +40,7 @@ class VideoInfo:
     chroma_tag: str = "420jpeg"
     color_range: str | None = None   # "limited" / "full" when the container says so (Y4M XCOLORRANGE=...), else None
     packed: str | None = None        # "uyvy422" / "yuyv422" / "v210" when the file holds packed frames (PackedReader); "bgra" ... "r210": packed RGB (RgbReader)
+    interlace: str | None = None     # the Y4M I tag: "p" progressive, "t" / "b" top / bottom field first, "m" mixed; None: the header has none
 
     @property
     def dtype(self):
@@ -126,6 +127,8 @@ class Y4MReader:
                     raise ValueError(f"unsupported Y4M chroma tag C{v}")
                 info.hshift, info.vshift, info.bit_depth, info.mono = _Y4M_CHROMA[v]
                 info.chroma_tag = v
+            elif k == "I" and v in ("p", "t", "b", "m"):
+                info.interlace = v
             elif k == "X" and v.upper().startswith("COLORRANGE="):   # FFmpeg's Y4M extension
                 info.color_range = {"FULL": "full", "LIMITED": "limited"}.get(v.split("=", 1)[1].upper())
         if info.width <= 0 or info.height <= 0:
@@ -427,7 +430,7 @@ class RgbReader:
 def write_y4m(path: str, frames, info: VideoInfo) -> None:
     """frames: iterable of [Y,U,V] plane lists matching `info`."""
     with open(path, "wb") as f:
-        f.write(f"YUV4MPEG2 W{info.width} H{info.height} F{info.fps_num}:{info.fps_den} Ip A1:1 C{info.chroma_tag}"
+        f.write(f"YUV4MPEG2 W{info.width} H{info.height} F{info.fps_num}:{info.fps_den} I{info.interlace or 'p'} A1:1 C{info.chroma_tag}"
                 f"{' XCOLORRANGE=' + info.color_range.upper() if info.color_range else ''}\n".encode())
         for planes in frames:
             f.write(b"FRAME\n")
