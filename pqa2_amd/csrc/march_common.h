@@ -38,6 +38,28 @@ __device__ __forceinline__ float residual(const unsigned hi_pair, const float v)
   return r;
 }
 
+// PQA_SPLIT_FUSED_LO: the lo pieces of a pair in two instructions (v_fma_mixlo_f16 / v_fma_mixhi_f16: the residual and its
+// rounding to f16 in one, written into one half of the destination) instead of two residuals and a packed conversion.  The
+// residual is exact in f32, so the one rounding is the same rne to f16 -- as long as the instruction keeps f16 denormals,
+// which split_fused_probe_kernel (vif_march.hip) checks against lo_pair_cvt before the kernel may run.
+// Off: bit-identical and 12 instructions shorter per block, but no faster.
+#ifndef PQA_SPLIT_FUSED_LO
+#define PQA_SPLIT_FUSED_LO 0
+#endif
+
+// {rne_f16(x0 - hi.lo), rne_f16(x1 - hi.hi)} for the f16 roundings hi of x0, x1: residuals, then one packed conversion
+__device__ __forceinline__ unsigned lo_pair_cvt(const unsigned hi_pair, const float x0, const float x1) {
+  const f2 r = f2{residual<0>(hi_pair, x0), residual<1>(hi_pair, x1)};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(r, h2));
+}
+// the same with the fused instructions; mixhi keeps the half that mixlo wrote (tied operand)
+__device__ __forceinline__ unsigned lo_pair_fused(const unsigned hi_pair, const float x0, const float x1) {
+  unsigned r;
+  asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi_pair), "s"(-1.0f), "v"(x0));
+  asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(hi_pair), "s"(-1.0f), "v"(x1));
+  return r;
+}
+
 // Four f32 values v * s + b (s an exact power of two; b removes the mid-grey term of the mean planes, see pass1) -> two
 // f16 pieces each: hi = rne(x), lo = rne(x - hi).
 // hi / lo: {piece(x0), piece(x1)}, {piece(x2), piece(x3)} -- the element order of an MFMA operand.
@@ -47,12 +69,10 @@ __device__ __forceinline__ void split4(const f4 v, const float s, const float b,
   const f2 xb = __builtin_elementwise_fma(f2{v[2], v[3]}, f2{s, s}, f2{b, b});
   const unsigned h0 = __builtin_bit_cast(unsigned, __builtin_convertvector(xa, h2));
   const unsigned h1 = __builtin_bit_cast(unsigned, __builtin_convertvector(xb, h2));
-  const f2 ra = f2{residual<0>(h0, xa[0]), residual<1>(h0, xa[1])};
-  const f2 rb = f2{residual<0>(h1, xb[0]), residual<1>(h1, xb[1])};
   hi[2 * HALF] = h0;
   hi[2 * HALF + 1] = h1;
-  lo[2 * HALF] = __builtin_bit_cast(unsigned, __builtin_convertvector(ra, h2));
-  lo[2 * HALF + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(rb, h2));
+  lo[2 * HALF] = PQA_SPLIT_FUSED_LO ? lo_pair_fused(h0, xa[0], xa[1]) : lo_pair_cvt(h0, xa[0], xa[1]);
+  lo[2 * HALF + 1] = PQA_SPLIT_FUSED_LO ? lo_pair_fused(h1, xb[0], xb[1]) : lo_pair_cvt(h1, xb[0], xb[1]);
 }
 
 

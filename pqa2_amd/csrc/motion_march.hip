@@ -17,12 +17,13 @@
 //   vertical pass in SCATTER form: a new difference row adds c[k] * d to the five output rows it belongs to; an output row
 //            is complete two rows later.  With four rows per step a 5-row window touches at most two steps, so what crosses
 //            a step is four partial rows -- loop-carried registers, no rolling window to copy;
-//   horizontal pass: columns 2c - 2, 2c - 1 and 2c + 2, 2c + 3 are the neighbouring lanes' pairs, fetched with DPP wave
-//            shifts (4 per completed row);
-//   |.| accumulates per lane and column in f32 for 16 rows, then in double; row validity is a wave-uniform 0 / 1 weight in
-//            an SGPR, column validity is applied once to the lane's sums.
+//   horizontal pass: columns 2c - 2, 2c - 1 and 2c + 2, 2c + 3 are the neighbouring lanes' pairs, read through DPP wave
+//            shifts by the multiplies and FMAs that use them (6 per completed row, taps_dpp);
+//   |.| accumulates per lane and column in f32 for 16 rows, then in double; row validity is a wave-uniform 0 / 1 weight
+//            that only the last step of a segment can need, column validity is applied once to the lane's sums.
 // A segment of R rows feeds R + 4 rows ((R + 4) / R instead of 20 / 16).
 #include <cmath>
+#include <type_traits>
 
 #include "kernels.h"
 #include "pqa_device.h"
@@ -53,6 +54,19 @@ __device__ __forceinline__ float from_right(float v) {  // lane l <- lane l + 1
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
 
+// PQA_MOTION_DPP_TAPS: the horizontal taps live in five VGPRs, so that every wave-shifted operand folds into its multiply
+// or FMA as a DPP source (v_mul_f32_dpp / v_fmac_f32_dpp take a VGPR second factor only) instead of a v_mov_b32_dpp of
+// its own (taps_dpp).  Operands, order and rounding of every chain are unchanged.
+#ifndef PQA_MOTION_DPP_TAPS
+#define PQA_MOTION_DPP_TAPS 1
+#endif
+// PQA_MOTION_ROW_WEIGHT_PEEL: the 0 / 1 row weight only matters at the ends of a segment.  The first step completes four
+// rows above the segment (weight 0: it only seeds the vertical sums), the steps whose four rows all lie inside add |h|
+// (the same bits as fma(1, |h|, sad)), and at most one last step keeps the weighted form.
+#ifndef PQA_MOTION_ROW_WEIGHT_PEEL
+#define PQA_MOTION_ROW_WEIGHT_PEEL 1
+#endif
+
 // the lane's two samples of one row of one image, as loaded (one register in the fast path) and as floats (exact integers:
 // v_cvt_f32_ubyte0 / 1 extract and convert a byte in one instruction)
 template <typename T, bool EDGE>
@@ -73,15 +87,47 @@ struct PairLoader {
   }
   static __device__ __forceinline__ f2 to_float(const Raw r) {
     if constexpr (EDGE) return f2{(float)r.a, (float)r.b};
-    else if constexpr (sizeof(T) == 1) return f2{(float)(r.a & 0xffu), (float)((r.a >> 8) & 0xffu)};
+    else if constexpr (sizeof(T) == 1 && PQA_MOTION_ROW_WEIGHT_PEEL) {
+      // the compiler knows the loaded halfword's upper bits and turns the second byte into a shift and an integer
+      // conversion once the first step is peeled off the loop; the byte-selecting conversion is spelled out instead
+      float hi;
+      asm("v_cvt_f32_ubyte1_e32 %0, %1" : "=v"(hi) : "v"(r.a));
+      return f2{(float)(r.a & 0xffu), hi};
+    } else if constexpr (sizeof(T) == 1) return f2{(float)(r.a & 0xffu), (float)((r.a >> 8) & 0xffu)};
     else return f2{(float)(r.a & 0xffffu), (float)(r.a >> 16)};
   }
 };
+
+enum StepKind { STEP_SEED, STEP_FULL, STEP_WEIGHTED };
+
+// The horizontal pass of one completed row {m0, m1}: h0 = t4 q0 + (t3 m1 + (t2 m0 + (t1 l1 + t0 l0))) and
+// h1 = t4 q1 + (t3 q0 + (t2 m1 + (t1 m0 + t0 l1))), l / q the left / right neighbour's pair -- the chains of the plain
+// form below, term by term, with every neighbour read as the DPP source of its own multiply or FMA (bound_ctrl: lane 0's
+// left and lane 63's right neighbour read 0, as the moves gave).  The compiler does not see into the block, so the two
+// wait states a DPP read needs after a VALU write of the same register are spent here.
+__device__ __forceinline__ void taps_dpp(const float m0, const float m1, const float t0, const float t1, const float t2, const float t3,
+                                         const float t4, float& h0, float& h1) {
+  asm("s_nop 1\n\t"
+      "v_mul_f32_dpp %0, %2, %4 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_mul_f32_dpp %1, %3, %4 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_fmac_f32_dpp %0, %3, %5 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_fmac_f32_e32 %1, %5, %2\n\t"
+      "v_fmac_f32_e32 %0, %6, %2\n\t"
+      "v_fmac_f32_e32 %1, %6, %3\n\t"
+      "v_fmac_f32_e32 %0, %7, %3\n\t"
+      "v_fmac_f32_dpp %1, %2, %7 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_fmac_f32_dpp %0, %2, %8 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_fmac_f32_dpp %1, %3, %8 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+      : "=&v"(h0), "=&v"(h1)
+      : "v"(m0), "v"(m1), "v"(t0), "v"(t1), "v"(t2), "v"(t3), "v"(t4));
+}
 
 template <typename T, bool EDGE>
 __device__ __forceinline__ double march(const MotionMarchArgs& a, const PairLoader<T, EDGE>& cur, const PairLoader<T, EDGE>& prv,
                                         const int r0, const int r1, const int x_first /* the lane's first column */) {
   const float c0 = a.c[0], c1 = a.c[1], c2 = a.c[2], c3 = a.c[3], c4 = a.c[4];
+  float t0 = c0, t1 = c1, t2 = c2, t3 = c3, t4 = c4;   // the horizontal pass's copies
+  if (PQA_MOTION_DPP_TAPS) asm("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3), "+v"(t4));   // ... in VGPRs
   // partial vertical sums of the four output rows that are still waiting for input rows ({column 2c, column 2c + 1} each)
   f2 p0 = f2{0.0f, 0.0f}, p1 = p0, p2 = p0, p3 = p0;
   float sad0 = 0.0f, sad1 = 0.0f;
@@ -91,8 +137,9 @@ __device__ __forceinline__ double march(const MotionMarchArgs& a, const PairLoad
   typename PairLoader<T, EDGE>::Raw cs[4], ps[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) { cs[j] = cur.load(r0 - 2 + j); ps[j] = prv.load(r0 - 2 + j); }
-  int step = 0;
-  for (int y = r0 - 2; y < r1 + 2; y += 4, ++step) {   // this step feeds rows y .. y + 3 and completes rows y - 2 .. y + 1
+  // one step: feeds rows y .. y + 3 and completes rows y - 2 .. y + 1
+  auto step_at = [&](const int y, const auto kind_c) {
+    constexpr StepKind kind = decltype(kind_c)::value;
     f2 d[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) d[j] = PairLoader<T, EDGE>::to_float(cs[j]) - PairLoader<T, EDGE>::to_float(ps[j]);   // exact integers
@@ -111,20 +158,51 @@ __device__ __forceinline__ double march(const MotionMarchArgs& a, const PairLoad
     p1 = __builtin_elementwise_fma(k2, d[3], __builtin_elementwise_fma(k1, d[2], k0 * d[1]));                                              // row y + 3
     p2 = __builtin_elementwise_fma(k1, d[3], k0 * d[2]);                                                                                    // row y + 4
     p3 = k0 * d[3];                                                                                                                         // row y + 5
+    if constexpr (kind == STEP_SEED) return;   // every completed row lies above the segment
     // horizontal pass and |.| of the completed rows; a row outside [r0, min(r1, h)) weighs 0 (wave-uniform)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int yo = y - 2 + j;
-      // 0 / 1 as a float, formed with integer (scalar) operations so that it stays in an SGPR
-      const float wrow = __builtin_bit_cast(float, (unsigned)-(int)(yo >= r0 && yo < y_end) & 0x3f800000u);
       const float m0 = o[j].x, m1 = o[j].y;
-      const float l0 = from_left(m0), l1 = from_left(m1), q0 = from_right(m0), q1 = from_right(m1);
-      const float h0 = fmaf(c4, q0, fmaf(c3, m1, fmaf(c2, m0, fmaf(c1, l1, c0 * l0))));
-      const float h1 = fmaf(c4, q1, fmaf(c3, q0, fmaf(c2, m1, fmaf(c1, m0, c0 * l1))));
-      sad0 = fmaf(wrow, fabsf(h0), sad0);
-      sad1 = fmaf(wrow, fabsf(h1), sad1);
+      float h0, h1;
+      if constexpr (PQA_MOTION_DPP_TAPS) {
+        taps_dpp(m0, m1, t0, t1, t2, t3, t4, h0, h1);
+      } else {
+        const float l0 = from_left(m0), l1 = from_left(m1), q0 = from_right(m0), q1 = from_right(m1);
+        h0 = fmaf(c4, q0, fmaf(c3, m1, fmaf(c2, m0, fmaf(c1, l1, c0 * l0))));
+        h1 = fmaf(c4, q1, fmaf(c3, q0, fmaf(c2, m1, fmaf(c1, m0, c0 * l1))));
+      }
+      if constexpr (kind == STEP_FULL) {
+        sad0 += fabsf(h0);
+        sad1 += fabsf(h1);
+      } else {
+        // 0 / 1 as a float, formed with integer (scalar) operations so that it stays in an SGPR
+        const float wrow = __builtin_bit_cast(float, (unsigned)-(int)(yo >= r0 && yo < y_end) & 0x3f800000u);
+        sad0 = fmaf(wrow, fabsf(h0), sad0);
+        sad1 = fmaf(wrow, fabsf(h1), sad1);
+      }
     }
-    if ((step & 3) == 3) { dsad0 += (double)sad0; dsad1 += (double)sad1; sad0 = 0.0f; sad1 = 0.0f; }
+  };
+  if (PQA_MOTION_ROW_WEIGHT_PEEL) {
+    int y = r0 - 2, step = 1;
+    step_at(y, std::integral_constant<StepKind, STEP_SEED>{});
+    // The f32 sums of four steps go to the doubles BEFORE the step behind them rather than after their last one (the same
+    // additions in the same order; the sums of the last steps go below, one addition of +0 earlier or not at all): with
+    // the branch in front, the step itself is one basic block and the loop's back edge carries no work.
+    for (y += 4; y + 1 < y_end; y += 4, ++step) {   // rows y - 2 .. y + 1 all inside [r0, y_end)
+      if ((step & 3) == 0) { dsad0 += (double)sad0; dsad1 += (double)sad1; sad0 = 0.0f; sad1 = 0.0f; }
+      step_at(y, std::integral_constant<StepKind, STEP_FULL>{});
+    }
+    if (y < r1 + 2) {   // the last rows of a segment whose length is no multiple of 4
+      if ((step & 3) == 0) { dsad0 += (double)sad0; dsad1 += (double)sad1; sad0 = 0.0f; sad1 = 0.0f; }
+      step_at(y, std::integral_constant<StepKind, STEP_WEIGHTED>{});
+    }
+  } else {
+    int step = 0;
+    for (int y = r0 - 2; y < r1 + 2; y += 4, ++step) {
+      step_at(y, std::integral_constant<StepKind, STEP_WEIGHTED>{});
+      if ((step & 3) == 3) { dsad0 += (double)sad0; dsad1 += (double)sad1; sad0 = 0.0f; sad1 = 0.0f; }
+    }
   }
   dsad0 += (double)sad0;
   dsad1 += (double)sad1;

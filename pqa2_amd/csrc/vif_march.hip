@@ -551,6 +551,41 @@ __global__ void f16_tiny_probe_kernel(int* ok) {
   if (d[0] == want && d[3] == want) atomicAdd(ok, 1);
 }
 
+// The fused lo pieces (PQA_SPLIT_FUSED_LO, march_common.h) must round like the residual-and-convert sequence they replace,
+// f16 denormals included.  Sixteen values whose residual against their f16 rounding is zero, an f16 denormal, half the
+// smallest denormal, or exactly halfway between two f16 values (denormal and normal, even and odd neighbour), with both
+// signs and in both halves of the pair: a lane counts when the two sequences agree in every bit and a residual above half
+// the smallest denormal did not come out as zero.
+__global__ void split_fused_probe_kernel(int* ok) {
+  constexpr float e12 = 0x1p-12f, e16 = 0x1p-16f, e17 = 0x1p-17f, e23 = 0x1p-23f, e24 = 0x1p-24f, e25 = 0x1p-25f;
+  const float xs[16] = {0.5f,                              // residual 0
+                        1.0f + e12,                        // normal residual
+                        1.0f + e12 + e23,                  // halfway between two normal f16, even below
+                        1.0f + e12 + 3.0f * e23,           // halfway, even above
+                        0x1p-4f + e16,                     // denormal residual
+                        0x1p-4f + e16 + e24,               // denormal residual with the last bit set
+                        0x1p-4f + e16 + e25,               // halfway between two denormals, even below
+                        0x1p-4f + e16 + e24 + e25,         // halfway, even above
+                        0x1p-4f - e17,                     // negative denormal residual
+                        0x1p-4f + e24,                     // the smallest denormal
+                        0x1p-4f + e25,                     // half the smallest denormal: rounds to zero
+                        0x1p-4f + 3.0f * e25,              // 1.5 of it: rounds to 2^-23
+                        0x1p-4f + e25 + 0x1p-27f,          // just above half: rounds to 2^-24
+                        3.0f * e24,                        // a denormal hi piece, residual 0
+                        1024.0f + 0.25f,                   // wide value (ulp of hi = 1)
+                        -(2048.0f - 0.5f + 0x1p-12f)};
+  const int lane = threadIdx.x;
+  const float sgn = (lane & 16) ? -1.0f : 1.0f;
+  const float x = sgn * xs[lane & 15], y = -sgn * xs[(lane + 5) & 15];
+  const float x0 = (lane & 32) ? y : x, x1 = (lane & 32) ? x : y;
+  const h2 hp = __builtin_convertvector(f2{x0, x1}, h2);
+  const unsigned h = __builtin_bit_cast(unsigned, hp);
+  const unsigned a = lo_pair_cvt(h, x0, x1), b = lo_pair_fused(h, x0, x1);
+  const float r0 = fabsf(x0 - (float)hp[0]), r1 = fabsf(x1 - (float)hp[1]);
+  const bool kept = (r0 <= e25 || (b & 0x7fffu) != 0u) && (r1 <= e25 || (b & 0x7fff0000u) != 0u);
+  if (a == b && kept) atomicAdd(ok, 1);
+}
+
 // ---- host: the per-lane tap-matrix fragments ------------------------------------------------------------------------
 bool build_table(uint16_t* out /* [kMarchFrags][64][8] */) {
   float c17[17], c9[9];
@@ -672,25 +707,36 @@ hipError_t vif_march_prepare() {
     (void)hipFree(d);
     return e;
   }
-  {  // the probe (see f16_tiny_probe_kernel): without kept denormals scale 0 stays on the VALU kernel, and says so once
+  {  // the probes (see f16_tiny_probe_kernel, split_fused_probe_kernel): without kept denormals scale 0 stays on the VALU
+     // kernel, and says so once
     int* ok = nullptr;
-    int seen = 0;
-    if ((e = hipMalloc((void**)&ok, sizeof(int))) == hipSuccess) {
-      e = hipMemset(ok, 0, sizeof(int));
+    int seen[2] = {0, 0};
+    if ((e = hipMalloc((void**)&ok, sizeof(seen))) == hipSuccess) {
+      e = hipMemset(ok, 0, sizeof(seen));
       if (e == hipSuccess) {
         hipLaunchKernelGGL(f16_tiny_probe_kernel, dim3(1), dim3(64), 0, 0, ok);
         e = hipGetLastError();
       }
-      if (e == hipSuccess) e = hipMemcpy(&seen, ok, sizeof(int), hipMemcpyDeviceToHost);
+      if (e == hipSuccess && PQA_SPLIT_FUSED_LO) {
+        hipLaunchKernelGGL(split_fused_probe_kernel, dim3(1), dim3(64), 0, 0, ok + 1);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpy(seen, ok, sizeof(seen), hipMemcpyDeviceToHost);
       (void)hipFree(ok);
     }
     if (e != hipSuccess) {
       (void)hipFree(d);
       return e;
     }
-    if (seen != 64) {
+    if (seen[0] != 64) {
       fprintf(stderr, "pqa_vmaf: device %d does not keep f16 denormals (%d of 64 probe lanes exact): VIF scale 0 runs the "
-                      "VALU kernel instead of the matrix-core kernel\n", dev, seen);
+                      "VALU kernel instead of the matrix-core kernel\n", dev, seen[0]);
+      (void)hipFree(d);
+      return hipSuccess;
+    }
+    if (PQA_SPLIT_FUSED_LO && seen[1] != 64) {
+      fprintf(stderr, "pqa_vmaf: device %d rounds the fused f16 low pieces differently (%d of 64 probe lanes equal): VIF "
+                      "scale 0 runs the VALU kernel instead of the matrix-core kernel\n", dev, seen[1]);
       (void)hipFree(d);
       return hipSuccess;
     }
