@@ -68,8 +68,9 @@ inline ClipLayout plane_clip(size_t row_bytes, int h) {
 }
 
 // frames f0 ... f0 + n - 1 of a caller's clip into slots 0 ... n - 1 of a pinned buffer.  `frames` holds L.n_planes
-// pointers per frame, frame-major; rows strides[p] bytes apart.  Only the L.plane[p].row_bytes bytes of a row that hold
-// samples are read: the caller's last row may end at the end of its allocation.
+// pointers per frame, frame-major; rows strides[p] bytes apart (negative: the rows lie bottom-up in the caller's memory).
+// Only the L.plane[p].row_bytes bytes of a row that hold samples are read: the caller's last row may end at the end of its
+// allocation.
 inline void pack_clip(uint8_t* pin, const ClipLayout& L, const void* const* frames, const int64_t strides[3], int f0, int n) {
   for (int f = 0; f < n; ++f)
     for (int p = 0; p < L.n_planes; ++p)
@@ -87,13 +88,17 @@ inline void unpack_clip_out(const uint8_t* pin, const ClipLayout& L, void* const
                pin + (size_t)f * L.frame_bytes + L.off[p] + (size_t)y * L.plane[p].pitch, L.plane[p].row_bytes);
 }
 
-// n_frames frames of `ref` and of `dis` (null: the one-clip form, which leaves pin[1] alone), L.n_planes pointers a frame, onto
-// the device in chunks of at most `chunk`, each chunk launched before the next is packed.  For every chunk:
-//   drain()                      not before the first chunk: the pinned buffers are packed again only after the device has
-//                                read the chunk before (the staging is not pipelined)
-//   pack                         the chunk's frames into slots 0 ... n - 1 of pin[0] (and pin[1])
+// n_frames frames of `ref` and of `dis` (null: the one-clip form), L.n_planes pointers a frame, onto the device in chunks of
+// at most `chunk`, each chunk launched before the next is packed.  Clip 0 is `ref` and clip 1 `dis`.  A pair packs clip k into
+// pin[k]; the one-clip form packs chunk i into pin[i & 1], so that a chunk is packed under the upload of the chunk before.
+// For every chunk:
+//   drain(b)                     not before the first chunk, once per pinned buffer b the chunk packs: the buffer is packed
+//                                again only after the upload that last read it has left it; the kernel of the chunk before
+//                                may still run
 //   seam(from_slot)              carry 1, not in the first chunk: device slot from_slot moves to device slot 0
-//   upload(slot, n)              the n packed frames to device slots slot ... slot + n - 1
+//   pack, upload(b, k, slot, n)  per clip k: its n frames into slots 0 ... n - 1 of pin[b], then those to the clip's device
+//                                slots slot ... slot + n - 1, in stream order behind the seam and the launch of the chunk
+//                                before; the second clip is packed under the upload of the first
 //   launch(slot, n, out_index)   n frames from device slot `slot` on; the results go `out_index` results into the output
 // carry 0: a result per frame.  A chunk lands in slots 0 ... n - 1 and its launch writes results f0 ... f0 + n - 1.
 // carry 1: a result per transition from a frame to the next.  The device buffers hold one slot more than a chunk: a chunk lands
@@ -106,18 +111,23 @@ inline void unpack_clip_out(const uint8_t* pin, const ClipLayout& L, void* const
 template <class Drain, class Seam, class Upload, class Launch>
 auto stage_walk(const ClipLayout& L, uint8_t* const pin[2], const void* const* ref, const int64_t ref_strides[3],
                 const void* const* dis, const int64_t dis_strides[3], int n_frames, int chunk, int carry,
-                const std::atomic<int>& cancelled, Drain drain, Seam seam, Upload upload, Launch launch) -> decltype(drain()) {
-  using E = decltype(drain());
+                const std::atomic<int>& cancelled, Drain drain, Seam seam, Upload upload, Launch launch) -> decltype(drain(0)) {
+  using E = decltype(drain(0));
   E e{};
   for (int f0 = 0; f0 < n_frames && e == E{} && !cancelled.load(); f0 += chunk) {
     const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
     const int kept = carry && f0 > 0 ? 1 : 0;   // the predecessor from the chunk before
-    if (f0 > 0) e = drain();
+    const int b = dis ? 0 : (f0 / chunk) & 1;
+    if (f0 > 0) e = drain(b);
+    if (e == E{} && f0 > 0 && dis) e = drain(1);
+    if (e == E{} && kept) e = seam(chunk);
     if (e != E{}) break;
-    pack_clip(pin[0], L, ref, ref_strides, f0, n);
-    if (dis) pack_clip(pin[1], L, dis, dis_strides, f0, n);
-    if (kept) e = seam(chunk);
-    if (e == E{}) e = upload(carry, n);
+    pack_clip(pin[b], L, ref, ref_strides, f0, n);
+    e = upload(b, 0, carry, n);
+    if (e == E{} && dis) {
+      pack_clip(pin[1], L, dis, dis_strides, f0, n);
+      e = upload(1, 1, carry, n);
+    }
     if (e == E{}) e = launch(carry - kept, n + kept, f0 - kept);
   }
   return e;

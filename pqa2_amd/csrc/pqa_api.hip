@@ -450,7 +450,6 @@ int alloc_rings(pqa_ctx* c) {
     return fail(c, PQA_ENOMEM, "out of host memory");
   }
   PQACHK(dev_alloc(c, &c->luma_part, (size_t)kLumaBlocks * 3 * c->B));
-  PQACHK(dev_alloc(c, &c->luma_out, (size_t)3 * (c->B > kLumaOutFrames ? c->B : kLumaOutFrames)));
   PQACHK(dev_alloc(c, &c->records, (size_t)c->capacity * PQA_RECORD_DOUBLES));
   for (int i = 0; i < kExtBlocks; ++i) {
     if (!(c->cfg.features & kExtBlock[i].features)) continue;
@@ -1341,12 +1340,6 @@ void pqa_destroy(pqa_ctx* c) {
     if (H.computed) hipEventDestroy(H.computed);
   }
   for (int i = 0; i < 2; ++i) {
-    Half& L = c->luma_half[i];
-    if (L.pinned) hipHostFree(L.pinned);
-    if (L.dev) hipFree(L.dev);
-    if (L.copied) hipEventDestroy(L.copied);
-  }
-  for (int i = 0; i < 2; ++i) {
     for (int sd = 0; sd < 2; ++sd) {
       if (c->pk_pin[i][sd]) hipHostFree(c->pk_pin[i][sd]);
       if (c->pk_dev[i][sd]) hipFree(c->pk_dev[i][sd]);
@@ -1359,6 +1352,8 @@ void pqa_destroy(pqa_ctx* c) {
     if (b) hipFree(b);
   for (uint8_t* b : c->side_pin)
     if (b) hipHostFree(b);
+  for (hipEvent_t e : c->side_pin_sent)
+    if (e) hipEventDestroy(e);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   for (int i = 0; i < 2; ++i) {
     if (c->aux[i]) hipStreamDestroy(c->aux[i]);

@@ -62,15 +62,15 @@ constexpr ExtBlock kExtBlock[kExtBlocks] = {
     {PQA_EXT5_DOUBLES, PQA_FEAT_INTEGRITY, false},   // integrity.hip
 };
 
-constexpr int kLumaOutFrames = 2048;  // luma statistics kept on the device between host copies
-
 // The grow-only device buffers of the side analyses, pqa_ctx::side_buf below (side_reserve, pqa_side.hip).
 enum SideBuf {
-  // The one pair of staging buffers for host frames of the call's own size (pair_run, transform_run): an analysis uploads a chunk
-  // of reference frames into A and of captured frames into B; a transform uploads a chunk of source frames into A and writes the
-  // result into B (pqa_mask_blend: blends in A, the fill planes lie in B).  Every such entry is synchronous and leaves with the
-  // stream drained, and none reads what a call before it left there, so they all share the pair.
+  // The one pair of staging buffers for host frames, of the context's size or the call's own (pair_run, transform_run): an analysis
+  // uploads a chunk of reference frames into A and of captured frames into B; a transform uploads a chunk of source frames into A
+  // and writes the result into B (pqa_mask_blend: blends in A, the fill planes lie in B); pqa_frame_sad copies a chunk of frames into A.  Every such entry is synchronous and
+  // leaves with the stream drained, and none reads what a call before it left there, so they all share the pair.
   SIDE_STAGE_A = 0, SIDE_STAGE_B,
+  SIDE_SAD_OUT,                                                                // pqa_frame_sad[_device], integrity.hip: the sums
+  SIDE_LUMA_OUT,                                                               // pqa_luma_stats[_device], luma_stats.hip: the sums
   SIDE_XSSE_PART, SIDE_XSSE_NORM_REF, SIDE_XSSE_NORM_DIS, SIDE_XSSE_OUT,       // pqa_cross_sse[_device], cross_sse.hip
   SIDE_XSSE_REF, SIDE_XSSE_DIS,                                                // pqa_cross_sse: its two rings of uploaded frames
   SIDE_SHIFT_PART, SIDE_SHIFT_ROWSQ, SIDE_SHIFT_OUT,                           // pqa_shift_sse[_device], shift_sse.hip
@@ -172,26 +172,22 @@ struct pqa_ctx {
   pqa::host::FrameChain ig_chain;         // one index for the three; pqa_set_dis_history_planes arms them
   uint32_t black_thr = 0;                     // pqa_set_black_threshold
   bool started = false;                       // a batch was launched since pqa_create / pqa_reset
-  // pqa_frame_sad / pqa_frame_sad_device (allocated on first use)
+  // pqa_frame_sad (allocated on first use)
   uint8_t* ig_anchor[3] = {nullptr, nullptr, nullptr};  // the anchor frame's planes (pitches: those of ig_hist)
-  uint8_t* ig_stage = nullptr;                // FB frames of host planes (slot layout: ig_stage_off, ig_stage_bytes)
-  size_t ig_stage_off[3] = {0, 0, 0}, ig_stage_bytes = 0;
-  unsigned long long* ig_out = nullptr;       // [B][3] results of one launch
   unsigned long long* luma_part = nullptr;
-  unsigned long long* luma_out = nullptr;
-  // host frames of the side analyses (pqa_luma_stats, pqa_cross_sse, pqa_shift_sse, pqa_level_stats): two pinned + two device
-  // halves of LB luma planes (luma_staging_ensure; `computed` is not used here: one stream orders uploads and kernels)
-  pqa::Half luma_half[2];
-  int64_t luma_pitch = 0;
-  int LB = 0;
-  bool luma_ready = false;
   uint32_t luma_gray = PQA_GRAY_LUMA;
   bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
   bool temporal_walk = false;        // PQA_TEMPORAL_WALK, read once in pqa_create: 1 takes the walking form of temporal_moments.hip (A/B partner; the same integers)
   pqa::RsCached rs_cache[pqa::kRsCached];   // pqa_resample[_device]: the tables of the last few (filter, geometry, window)
   int rs_next = 0;                          // the slot the next new table replaces
-  uint8_t* side_pin[2] = {nullptr, nullptr};   // the side analyses' two grow-only pinned chunks (side_pin_reserve, pqa_side.hip), of any frame size: an analysis packs a chunk of reference frames into the first and of captured frames into the second; a transform packs its source chunk (pqa_mask_blend: the fill planes behind it) into the first and takes the result back through the second
+  // The side analyses' two grow-only pinned chunks (side_pin_reserve, pqa_side.hip), of any frame size: all their host frames go
+  // through these (but pqa_frame_sad's, which the runtime copies).  An analysis of a clip pair packs a chunk of reference frames into the first and of captured frames into the
+  // second; an analysis of one clip and pqa_cross_sse pack their chunks into the two in turn; a transform packs its source chunk
+  // (pqa_mask_blend: the fill planes behind it) into the first and takes the result back through the second.
+  uint8_t* side_pin[2] = {nullptr, nullptr};
   size_t side_pin_cap[2] = {0, 0};
+  hipEvent_t side_pin_sent[2] = {nullptr, nullptr};   // recorded behind the upload that last read a chunk; the chunk is packed again once it has passed
+  bool side_pin_busy[2] = {false, false};             // such an upload may be in flight
   void* side_buf[pqa::kSideBufs] = {};    // the side analyses' grow-only device buffers (SideBuf above), allocated on first use; all host staging shares SIDE_STAGE_A / _B
   size_t side_cap[pqa::kSideBufs] = {};   // their sizes in bytes
   // motion continuity: the last reference luma of the chain; pqa_set_motion_halo / pqa_set_ref_history arm it

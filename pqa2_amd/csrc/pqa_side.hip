@@ -2,10 +2,11 @@
 // statistics, temporal / spatial / level alignment, the colour moments, Delta E ITP, the spec-driven analyses of planes of the
 // call's own size (registration moments, tile / band / temporal moments, edge and line profiles), and the transforms (resampler,
 // packed unpack, format and RGB converters, table apply, mask blend, colour-matrix apply).  Each has an entry for a clip in HBM
-// and one for frames in host memory.  Host frames of the context's size take the luma-halves staging (stage_frames); frames of
-// the call's own size take one staging path, whose host side is host_stage.h: the analyses share one checker and one driver
-// per kind of clip (spec_check, pair_run), the transforms one driver per kind of clip (transform_run).  Every entry ends in one
-// epilogue (side_finish).
+// and one for frames in host memory.  Host frames, of the context's size or of the call's own, take one staging path, whose host
+// side is host_stage.h: two pinned chunks and two staging buffers.  The analyses share one driver per kind of clip (pair_run) and,
+// where a spec names the plane, one checker (spec_check); the transforms share one driver per kind of clip (transform_run);
+// pqa_cross_sse, whose two clips differ in length, walks its own tiles over the same pinned chunks, and pqa_frame_sad has the
+// runtime copy its frames into the first staging buffer.  Every entry ends in one epilogue (side_finish).
 // Declarations: include/pqa_vmaf.h; the context: pqa_ctx.h.
 #include "pqa_ctx.h"
 
@@ -13,6 +14,8 @@
 
 #include <climits>
 #include <cstdio>
+#include <functional>
+#include <type_traits>
 
 using namespace pqa;
 
@@ -42,67 +45,14 @@ int check_host_frames(pqa_ctx* c, const char* who, const char* kind, const void*
   return PQA_OK;
 }
 
-// ---- host frames onto the stream ---------------------------------------------------------------------------------------
-// the two pinned + two device halves of LB luma planes that the host entries pack their frames into
-int luma_staging_ensure(pqa_ctx* c) {
-  if (c->luma_ready) return PQA_OK;   // lazily: most contexts never detect bookends
-  c->luma_pitch = round_up((int64_t)c->pw[0] * c->esize, 64);
-  c->LB = c->B < 8 ? c->B : 8;
-  const size_t half = (size_t)c->luma_pitch * c->ph[0] * c->LB;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-    Half& H = c->luma_half[i];
-    if (!H.pinned) e = hipHostMalloc((void**)&H.pinned, half, hipHostMallocDefault);
-    if (e == hipSuccess && !H.dev) e = hipMalloc((void**)&H.dev, half);
-    if (e == hipSuccess && !H.copied) e = hipEventCreateWithFlags(&H.copied, hipEventDisableTiming);
-  }
-  if (e != hipSuccess) {   // all six or none: a half-made set must not make every later call fail on a null handle
-    for (Half& H : c->luma_half) {
-      if (H.pinned) hipHostFree(H.pinned);
-      if (H.dev) hipFree(H.dev);
-      if (H.copied) hipEventDestroy(H.copied);
-      H = Half{};
-    }
-    return fail(c, e == hipErrorOutOfMemory ? PQA_ENOMEM : PQA_EDEVICE, "luma staging allocation failed: %s", hipGetErrorString(e));
-  }
-  c->luma_ready = true;
-  return PQA_OK;
-}
-
-// n planes of row_bytes x h from frames[0 .. n) (rows `stride` bytes apart) through pinned half hf onto the stream: waits
-// until the upload that last used the half has left it, packs, queues the upload, records the half's event.  The planes
-// land in device half hf, one after the other -- or, with ring_base, frame k in slot (first + k) % ring_slots of that ring,
-// each uploaded as soon as it is packed (a ring may wrap inside a chunk).  A plane smaller than the luma plane travels
-// with the luma pitches.
-hipError_t stage_frames(pqa_ctx* c, int hf, const void* const* frames, int64_t stride, int n, size_t row_bytes, int h,
-                        uint8_t* ring_base = nullptr, int ring_slots = 1, int64_t first = 0) {
-  Half& H = c->luma_half[hf];
-  const size_t frame_bytes = (size_t)c->luma_pitch * c->ph[0];
-  hipError_t e = hipSuccess;
-  if (H.copied_pending) {
-    e = hipEventSynchronize(H.copied);
-    H.copied_pending = false;
-  }
-  for (int f = 0; f < n && e == hipSuccess; ++f) {
-    uint8_t* pin = H.pinned + (size_t)f * frame_bytes;
-    copy_plane_rows(pin, c->luma_pitch, (const uint8_t*)frames[f], stride, row_bytes, h);
-    if (ring_base)
-      e = hipMemcpyAsync(ring_base + (size_t)((first + f) % ring_slots) * frame_bytes, pin, frame_bytes, hipMemcpyHostToDevice,
-                         c->stream);
-  }
-  if (e == hipSuccess && !ring_base) e = hipMemcpyAsync(H.dev, H.pinned, (size_t)n * frame_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(H.copied, c->stream);
-  H.copied_pending = e == hipSuccess;
-  return e;
-}
-
+// ---- the epilogue, the grow-only buffers ----------------------------------------------------------------------------------
 // The end of every entry, after its launches (e: the first error among them): the results go to the caller unless
 // something failed or the call was cancelled, and the stream is ALWAYS synchronised -- nothing queued on it may still point
-// at the pinned halves or at `out` when the call returns.
+// at the pinned chunks or at `out` when the call returns.
 int side_finish(pqa_ctx* c, const char* what, hipError_t e, void* out, const void* dev_out, size_t bytes) {
   if (e == hipSuccess && !c->cancelled.load() && bytes) e = hipMemcpyAsync(out, dev_out, bytes, hipMemcpyDeviceToHost, c->stream);
   const hipError_t es = hipStreamSynchronize(c->stream);
-  c->luma_half[0].copied_pending = c->luma_half[1].copied_pending = false;
+  c->side_pin_busy[0] = c->side_pin_busy[1] = false;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (e != hipSuccess) return fail(c, PQA_EDEVICE, "%s failed: %s", what, hipGetErrorString(e));
   if (es != hipSuccess) return fail(c, PQA_EDEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
@@ -123,8 +73,9 @@ int side_reserve(pqa_ctx* c, SideBuf which, size_t bytes) {
   return PQA_OK;
 }
 
-// one of the two grow-only pinned chunks of the side analyses
+// one of the two grow-only pinned chunks of the side analyses, with its event
 int side_pin_reserve(pqa_ctx* c, int which, size_t bytes) {
+  if (!c->side_pin_sent[which]) HIPCHK(c, hipEventCreateWithFlags(&c->side_pin_sent[which], hipEventDisableTiming));
   if (c->side_pin_cap[which] >= bytes) return PQA_OK;
   if (c->side_pin[which]) {
     HIPCHK(c, hipHostFree(c->side_pin[which]));
@@ -136,23 +87,18 @@ int side_pin_reserve(pqa_ctx* c, int which, size_t bytes) {
   return PQA_OK;
 }
 
-// the launch of pqa_frame_sad[_device]: n frames (at most B) of a device clip against the anchor planes, results to out
-int frame_sad_launch(pqa_ctx* c, const void* const anchor[3], const int64_t anchor_pitch_bytes[3], const pqa_device_clip* f,
-                     int n, uint64_t* out) {
-  const int es = c->esize;
-  PlaneRun cur[3] = {};
-  int64_t app[3] = {0, 0, 0};
-  for (int p = 0; p < c->n_planes; ++p) {
-    cur[p] = PlaneRun{f->plane[p], f->row_pitch[p] / es, f->frame_pitch[p] / es};
-    app[p] = anchor_pitch_bytes[p] / es;
-  }
-  if (!c->ig_out) {
-    const int rc = dev_alloc(c, &c->ig_out, (size_t)c->B * 3);
-    if (rc != PQA_OK) return rc;
-  }
-  const hipError_t e = launch_integrity(c->stream, c->elem, cur, anchor, app, c->pw, c->ph, c->n_planes, n, true, c->black_thr,
-                                        c->ig_part, nullptr, 0, 0, 1, c->ig_out);
-  return side_finish(c, "frame_sad", e, out, c->ig_out, (size_t)n * 3 * sizeof(uint64_t));
+// A pinned chunk is packed again while the kernels of the chunk before still run: before the pack the host waits only until
+// the upload that last read the chunk has left it (pin_wait), which the chunk's event, recorded behind that upload (pin_mark),
+// tells.  The stream orders everything else: a kernel before the next upload into the device slots it reads.
+hipError_t pin_wait(pqa_ctx* c, int which) {
+  if (!c->side_pin_busy[which]) return hipSuccess;
+  c->side_pin_busy[which] = false;
+  return hipEventSynchronize(c->side_pin_sent[which]);
+}
+hipError_t pin_mark(pqa_ctx* c, int which) {
+  const hipError_t e = hipEventRecord(c->side_pin_sent[which], c->stream);
+  c->side_pin_busy[which] = e == hipSuccess;
+  return e;
 }
 
 // ---- temporal alignment (cross_sse.hip): argument rules (no device call) and workspaces ------------------------------
@@ -190,13 +136,10 @@ int sh_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int
   return PQA_OK;
 }
 
-int sh_prepare(pqa_ctx* c, int radius, int32_t n_frames) {
-  const int chunk = n_frames < kShiftChunk ? n_frames : kShiftChunk;
-  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
-  int rc = side_reserve(c, SIDE_SHIFT_PART, shift_part_bytes(c->elem, c->pw[0], c->ph[0], radius, chunk));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_SHIFT_ROWSQ, shift_rowsq_bytes(c->ph[0], radius, chunk));
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_SHIFT_OUT, (size_t)n_frames * n * sizeof(uint64_t));
-  return rc;
+// the workspaces of a launch of at most `chunk` frame pairs
+int sh_prepare(pqa_ctx* c, int radius, int chunk) {
+  const int rc = side_reserve(c, SIDE_SHIFT_PART, shift_part_bytes(c->elem, c->pw[0], c->ph[0], radius, chunk));
+  return rc == PQA_OK ? side_reserve(c, SIDE_SHIFT_ROWSQ, shift_rowsq_bytes(c->ph[0], radius, chunk)) : rc;
 }
 
 // ---- level alignment (level_stats.hip): argument rules ---------------------------------------------------------------
@@ -208,7 +151,6 @@ int lv_check(pqa_ctx* c, const void* ref, const void* dis, int32_t n_frames, int
   if (n_frames > 0 && !out) return fail(c, PQA_EINVAL, "level_stats: null output pointer");
   return PQA_OK;
 }
-
 
 // ---- resampler (resample.hip): argument rules (no device call), tables ------------------------------------------------
 int rs_check(pqa_ctx* c, const pqa_resample_spec* sp) {
@@ -285,6 +227,8 @@ struct HostClip {   // a list of frames in host memory, rows of plane p strides[
   const void* const* at;
   const int64_t* strides;
 };
+template <class Clip>
+constexpr bool kHostFrames = std::is_same<Clip, HostClip>::value;
 struct DevClip {   // planes in HBM, pitches in bytes
   const void* at;
   int64_t row_pitch, frame_pitch;
@@ -360,12 +304,22 @@ struct PairJob {
   bool whole_samples = true;       // host frames: refuse a stride that is no multiple of the sample size
   SideBuf part_buf = kSideBufs;    // a workspace of part_bytes that the launches share (pqa_band_moments, pqa_delta_itp)
   size_t part_bytes = 0;
+  // what the five oldest entries answer differently, each as it always has:
+  bool bottom_up = false;          // host frames: a negative stride passes, and the rows are then copied bottom-up
+  bool row_holds = true;           // one-plane clips in HBM: refuse a row pitch smaller than a row (pqa_luma_stats_device: no such rule)
+  bool bare = false;               // a rule's message opens with nothing, not with "<who>: " (pqa_luma_stats)
+  std::function<int()> prepare;    // reserves the workspaces one part_buf cannot name (pqa_shift_sse)
 };
 
 int job_reserve(pqa_ctx* c, const PairJob& j) {
-  const int rc = j.part_buf != kSideBufs ? side_reserve(c, j.part_buf, j.part_bytes) : PQA_OK;
-  return rc == PQA_OK ? side_reserve(c, j.out_buf, j.out_bytes) : rc;
+  int rc = j.part_buf != kSideBufs ? side_reserve(c, j.part_buf, j.part_bytes) : PQA_OK;
+  if (rc == PQA_OK) rc = side_reserve(c, j.out_buf, j.out_bytes);
+  return rc == PQA_OK && j.prepare ? j.prepare() : rc;
 }
+
+// Host frames of the context's size travel in chunks of at most 8 and of no more than a batch of the scoring path: the
+// per-batch workspaces (luma_part, ig_part) hold that many, and so do kShiftChunk and kLevelChunk.
+int ctx_chunk(const pqa_ctx* c) { return c->B < 8 ? c->B : 8; }
 
 // Three-plane clips in HBM, after the entry's own rules.  launch(ref runs, dis runs, n frames, index of the first result) queues
 // a kernel; `stop`: launch_runs.
@@ -389,11 +343,13 @@ int pair_run(pqa_ctx* c, const PairJob& j, const DevClip& ref, const DevClip* di
   const int es = c->esize;
   const int64_t row_bytes = (int64_t)j.L.plane[0].row_bytes;
   char who[48];
+  const int64_t min_row = j.row_holds ? row_bytes : INT64_MIN;
   snprintf(who, sizeof who, dis ? "%s: reference " : "%s: ", j.who);
-  int rc = check_device_clip(c, who, ref.row_pitch, ref.frame_pitch, row_bytes);
+  if (j.bare) who[0] = 0;
+  int rc = check_device_clip(c, who, ref.row_pitch, ref.frame_pitch, min_row);
   if (rc == PQA_OK && dis) {
     snprintf(who, sizeof who, "%s: captured ", j.who);
-    rc = check_device_clip(c, who, dis->row_pitch, dis->frame_pitch, row_bytes);
+    rc = check_device_clip(c, who, dis->row_pitch, dis->frame_pitch, min_row);
   }
   if (rc != PQA_OK) return rc;
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
@@ -411,21 +367,23 @@ int pair_run(pqa_ctx* c, const PairJob& j, const DevClip& ref, const DevClip* di
   return side_finish(c, j.who, e, j.out, c->side_buf[j.out_buf], j.out_bytes);
 }
 
-// Host frames (dis null: one clip), with their rules.  The frames are the call's own size, so they travel in chunks through the
-// two grow-only pinned chunks (the reference frames through the first, the captured ones through the second) into the two
-// staging buffers (SIDE_STAGE_A, SIDE_STAGE_B) as host_stage.h lays out: packed rows, a chunk launched before the next is
-// packed, with carry 1 the last pair of a chunk kept as predecessor of the next.  Every entry here is synchronous, so no two
-// calls are ever in flight in these buffers, and no call reads what another left there.  Every launch writes its results
-// behind the previous one's; they come back once.
+// Host frames (dis null: one clip), with their rules.  The frames are of any size, so they travel in chunks through the two
+// grow-only pinned chunks (the reference frames through the first, the captured ones through the second) into the two staging
+// buffers (SIDE_STAGE_A, SIDE_STAGE_B) as host_stage.h lays out: packed rows, a chunk launched before the next is packed -- under
+// that launch's kernel: the host waits for the uploads out of the pinned chunks only (pin_wait) --, with carry 1 the last pair
+// of a chunk kept as predecessor of the next.  Every entry here is synchronous, so no two calls are ever in flight in these
+// buffers, and no call reads what another left there.  Every launch writes its results behind the previous one's; they come
+// back once.
 template <class Launch>
 int pair_run(pqa_ctx* c, const PairJob& j, const HostClip& ref, const HostClip* dis, Launch launch) {
   const int es = c->esize, np = j.L.n_planes;
   char who[48];
   snprintf(who, sizeof who, "%s: ", j.who);
+  if (j.bare) who[0] = 0;
   int rc = PQA_OK;
   for (const HostClip* k : {&ref, dis})
     for (int p = 0; k && p < np && rc == PQA_OK; ++p)
-      rc = check_host_frames(c, who, !dis ? "" : k == &ref ? "reference " : "captured ", k->at + p, np, j.n_frames, k->strides[p], j.L.plane[p].row_bytes, true);
+      rc = check_host_frames(c, who, !dis ? "" : k == &ref ? "reference " : "captured ", k->at + p, np, j.n_frames, k->strides[p], j.L.plane[p].row_bytes, !j.bottom_up);
   if (rc != PQA_OK) return rc;
   if (j.whole_samples && j.n_frames > 0 && (ref.strides[0] % es || (dis && dis->strides[0] % es)))
     return fail(c, PQA_EINVAL, "%s: stride is not a multiple of the sample size", j.who);
@@ -434,24 +392,25 @@ int pair_run(pqa_ctx* c, const PairJob& j, const HostClip& ref, const HostClip* 
   HIPCHK(c, hipSetDevice(c->device));
   const size_t fb = j.L.frame_bytes, slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk);
   rc = side_pin_reserve(c, 0, fb * slots);
-  if (rc == PQA_OK && dis) rc = side_pin_reserve(c, 1, fb * slots);
+  if (rc == PQA_OK && (dis || j.n_frames > j.chunk)) rc = side_pin_reserve(c, 1, fb * slots);   // one clip: its chunks alternate
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_STAGE_A, fb * (slots + j.carry));
   if (rc == PQA_OK && dis) rc = side_reserve(c, SIDE_STAGE_B, fb * (slots + j.carry));
   if (rc == PQA_OK) rc = job_reserve(c, j);
   if (rc != PQA_OK) return rc;
   uint8_t* const dev[2] = {(uint8_t*)c->side_buf[SIDE_STAGE_A], dis ? (uint8_t*)c->side_buf[SIDE_STAGE_B] : nullptr};
-  const int clips = dis ? 2 : 1;
-  const auto copy = [&](int to_slot, const uint8_t* const from[2], size_t from_off, size_t bytes, hipMemcpyKind kind) {
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < clips && e == hipSuccess; ++k)
-      e = hipMemcpyAsync(dev[k] + (size_t)to_slot * fb, from[k] + from_off, bytes, kind, c->stream);
-    return e;
-  };
   const hipError_t e = host::stage_walk(
       j.L, c->side_pin, ref.at, ref.strides, dis ? dis->at : nullptr, dis ? dis->strides : nullptr, j.n_frames, j.chunk, j.carry, c->cancelled,
-      [&] { return hipStreamSynchronize(c->stream); },
-      [&](int from_slot) { return copy(0, dev, (size_t)from_slot * fb, fb, hipMemcpyDeviceToDevice); },   // from_slot >= 1: no overlap
-      [&](int slot, int n) { return copy(slot, c->side_pin, 0, fb * n, hipMemcpyHostToDevice); },
+      [&](int b) { return pin_wait(c, b); },
+      [&](int from_slot) {   // from_slot >= 1: no overlap
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < (dis ? 2 : 1) && e == hipSuccess; ++k)
+          e = hipMemcpyAsync(dev[k], dev[k] + (size_t)from_slot * fb, fb, hipMemcpyDeviceToDevice, c->stream);
+        return e;
+      },
+      [&](int b, int k, int slot, int n) {
+        const hipError_t e = hipMemcpyAsync(dev[k] + (size_t)slot * fb, c->side_pin[b], fb * n, hipMemcpyHostToDevice, c->stream);
+        return e == hipSuccess ? pin_mark(c, b) : e;
+      },
       [&](int slot, int n, int out_index) {
         PlaneRun r[3] = {}, d[3] = {};
         plane_runs(staged_clip(j.L, dev[0]), slot, es, r);
@@ -575,6 +534,56 @@ int line_profiles(pqa_ctx* c, const pqa_profile_spec* sp, const Clip& planes, in
   });
 }
 
+// ---- the analyses of a plane of the context's size (pair_run above) ---------------------------------------------------------------
+// pqa_luma_stats, pqa_shift_sse and pqa_level_stats are older than spec_check: each has its own rules (sh_check, lv_check, the
+// entries' "bad argument") and keeps what it has always answered (PairJob: bottom_up, row_holds, bare).  A launch of the entry
+// for clips in HBM takes what it always took; host frames travel ctx_chunk() at a time.
+host::ClipLayout ctx_plane(const pqa_ctx* c, int plane) { return host::plane_clip((size_t)c->pw[plane] * c->esize, c->ph[plane]); }
+
+// luma statistics (luma_stats.hip): one clip
+template <class Clip>
+int luma_stats(pqa_ctx* c, const Clip& luma, int32_t n_frames, uint32_t threshold, uint64_t* out) {
+  const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
+  PairJob j{"luma_stats", ctx_plane(c, 0), n_frames, kHostFrames<Clip> ? ctx_chunk(c) : c->B, 0, SIDE_LUMA_OUT, (size_t)n_frames * 3 * sizeof(uint64_t), out, false};
+  j.bottom_up = j.bare = true;
+  j.row_holds = false;
+  return pair_run(c, j, luma, (const Clip*)nullptr, [&](const PlaneRun* r, const PlaneRun*, int n, int at) {
+    return launch_luma_stats(c->stream, c->elem, *r, n, c->pw[0], c->ph[0], threshold, gray_bpc, c->luma_part,
+                             (unsigned long long*)c->side_buf[SIDE_LUMA_OUT] + (size_t)at * 3);
+  });
+}
+
+// spatial alignment (shift_sse.hip); no frames: PQA_OK before a pitch or a stride is looked at
+template <class Clip>
+int shift_sse(pqa_ctx* c, const Clip& ref, const Clip& dis, int32_t n_frames, int32_t radius, uint64_t* out) {
+  const int rc = sh_check(c, ref.at, dis.at, n_frames, radius, out);
+  if (rc != PQA_OK || n_frames == 0) return rc;
+  const size_t per_frame = (size_t)(2 * radius + 1) * (2 * radius + 1);
+  const int chunk = kHostFrames<Clip> ? ctx_chunk(c) : kShiftChunk;
+  PairJob j{"shift_sse", ctx_plane(c, 0), n_frames, chunk, 0, SIDE_SHIFT_OUT, (size_t)n_frames * per_frame * sizeof(uint64_t), out, false};
+  j.bottom_up = true;
+  j.prepare = [&] { return sh_prepare(c, radius, n_frames < chunk ? n_frames : chunk); };
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_shift_sse(c->stream, c->elem, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch, d->frame_pitch, n, c->pw[0], c->ph[0],
+                            radius, c->side_buf[SIDE_SHIFT_PART], (unsigned long long*)c->side_buf[SIDE_SHIFT_ROWSQ],
+                            (unsigned long long*)c->side_buf[SIDE_SHIFT_OUT] + (size_t)at * per_frame);
+  });
+}
+
+// level alignment (level_stats.hip): a plane of the context, at its own size; no frames: as above
+template <class Clip>
+int level_stats(pqa_ctx* c, const Clip& ref, const Clip& dis, int32_t n_frames, int32_t plane, uint64_t* out) {
+  const int rc = lv_check(c, ref.at, dis.at, n_frames, plane, out);
+  if (rc != PQA_OK || n_frames == 0) return rc;
+  const int bpc = (int)c->cfg.bit_depth;
+  const size_t per_frame = (size_t)3 << bpc;
+  const PairJob j{"level_stats", ctx_plane(c, plane), n_frames, kHostFrames<Clip> ? ctx_chunk(c) : kLevelChunk, 0, SIDE_LEVEL_OUT, level_out_bytes(bpc, n_frames), out, false};
+  return pair_run(c, j, ref, &dis, [&](const PlaneRun* r, const PlaneRun* d, int n, int at) {
+    return launch_level_stats(c->stream, c->elem, bpc, r->base, r->row_pitch, r->frame_pitch, d->base, d->row_pitch, d->frame_pitch, n, c->pw[plane],
+                              c->ph[plane], (unsigned long long*)c->side_buf[SIDE_LEVEL_OUT] + (size_t)at * per_frame);
+  });
+}
+
 // ---- colour-matrix alignment (colour_moments.hip): argument rules (no device call), the layout of a staged frame --------------
 int cl_check(pqa_ctx* c, const char* who, int32_t n_frames) {
   if (n_frames < 0) return fail(c, PQA_EINVAL, "%s: negative frame count", who);
@@ -601,11 +610,25 @@ int cl_check_host(pqa_ctx* c, const char* who, const char* kind, const void* con
   return PQA_OK;
 }
 
-// A three-plane frame of the context's size as the host entries stage it: rows 16 bytes apart at least and planes 256, so the
-// kernels take their wide loads.
+// A frame of the context's size, all its planes (three here; pqa_frame_sad: one or three), as the host entries stage it: rows
+// 16 bytes apart at least and planes 256, so the kernels take their wide loads.
 host::ClipLayout cl_frame(const pqa_ctx* c) {
   const size_t rb[3] = {(size_t)c->pw[0] * c->esize, (size_t)c->pw[1] * c->esize, (size_t)c->pw[2] * c->esize};
-  return host::clip_layout(3, rb, c->ph, 16, 256);
+  return host::clip_layout(c->n_planes, rb, c->ph, 16, 256);
+}
+
+// anchored frame differences (integrity.hip): one clip of whole frames against the anchor planes (pitches in bytes), after the
+// entry's own rules; `chunk` frames a launch (ig_part holds a batch)
+PairJob sad_job(pqa_ctx* c, int32_t n_frames, int chunk, uint64_t* out) {
+  return PairJob{"frame_sad", cl_frame(c), n_frames, chunk, 0, SIDE_SAD_OUT, (size_t)n_frames * 3 * sizeof(uint64_t), out, false};
+}
+auto sad_launch(pqa_ctx* c, const void* const* anchor, const int64_t* anchor_pitch_bytes) {
+  return [=](const PlaneRun* cur, const PlaneRun*, int n, int at) {
+    int64_t app[3] = {0, 0, 0};
+    for (int p = 0; p < c->n_planes; ++p) app[p] = anchor_pitch_bytes[p] / c->esize;
+    return launch_integrity(c->stream, c->elem, cur, anchor, app, c->pw, c->ph, c->n_planes, n, true, c->black_thr, c->ig_part, nullptr, 0, 0, 1,
+                            (unsigned long long*)c->side_buf[SIDE_SAD_OUT] + (size_t)at * 3);
+  };
 }
 
 // ---- the plane transforms: n frames of a source clip to n frames of a destination clip ----------------------------------------
@@ -706,7 +729,7 @@ int packed_dst_check(pqa_ctx* c, const char* who, const char* aligned, const voi
 
 // ---- the transforms and the three-plane analyses: the rules an entry pair shares and one body for both (entries below) ------------
 
-// resampler (resample.hip).  A source plane may be larger than the context's, so host frames cannot take the luma halves.
+// resampler (resample.hip)
 template <class Clip>
 int resample_run(pqa_ctx* c, const pqa_resample_spec* sp, int slot, const Clip& src, const Clip& dst, int32_t n_frames) {
   const int es = c->esize, sw = (int)sp->src_width, sh = (int)sp->src_height, dw = (int)sp->dst_width, dh = (int)sp->dst_height;
@@ -967,16 +990,7 @@ int pqa_frame_sad_device(pqa_ctx* c, const void* const anchor_planes[3], const i
     if (rc != PQA_OK) return rc;
   }
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  for (int done = 0; done < n_frames;) {
-    const int n = chunk_len(n_frames, done, c->B);
-    pqa_device_clip f = *frames;
-    for (int p = 0; p < c->n_planes; ++p) f.plane[p] = (const uint8_t*)frames->plane[p] + (int64_t)done * frames->frame_pitch[p];
-    const int rc = frame_sad_launch(c, anchor_planes, anchor_row_pitch, &f, n, out + (size_t)done * 3);
-    if (rc != PQA_OK) return rc;
-    done += n;
-  }
-  return PQA_OK;
+  return pair_run(c, sad_job(c, n_frames, c->B, out), *frames, *frames, nullptr, sad_launch(c, anchor_planes, anchor_row_pitch));
 }
 
 int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t anchor_strides[3], const void* const* frames,
@@ -998,50 +1012,42 @@ int pqa_frame_sad(pqa_ctx* c, const void* const anchor_planes[3], const int64_t 
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const int FB = c->B < 8 ? c->B : 8;   // frames per upload and launch
-  if (!c->ig_stage) {   // lazily: a healthy clip never asks for an anchored difference
-    size_t off = 0;
-    for (int p = 0; p < c->n_planes; ++p) {
-      c->ig_stage_off[p] = off;
-      off += (size_t)round_up(c->ig_hist[p].pitch * c->ph[p], 256);
-    }
-    c->ig_stage_bytes = off;
-    for (int p = 0; p < c->n_planes; ++p) {
-      const int rc = dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist[p].pitch * c->ph[p]);
-      if (rc != PQA_OK) return rc;
-    }
-    const int rc = dev_alloc(c, &c->ig_stage, off * (size_t)FB);
+  for (int p = 0; p < c->n_planes; ++p) {   // lazily: a healthy clip never asks for an anchored difference
+    const int rc = c->ig_anchor[p] ? PQA_OK : dev_alloc(c, &c->ig_anchor[p], (size_t)c->ig_hist[p].pitch * c->ph[p]);
     if (rc != PQA_OK) return rc;
   }
-  // plain synchronous copies from the caller's (pageable) planes: this call is rare and short, it is not pipelined
+  // the anchor: plain synchronous copies from the caller's (pageable) planes, once a call
   for (int p = 0; p < c->n_planes; ++p)
     HIPCHK(c, hipMemcpy2D(c->ig_anchor[p], c->ig_hist[p].pitch, anchor_planes[p], anchor_strides[p], (size_t)c->pw[p] * c->esize,
                           c->ph[p], hipMemcpyHostToDevice));
-  const void* anchor[3] = {c->ig_anchor[0], c->ig_anchor[1], c->ig_anchor[2]};
+  const void* const anchor[3] = {c->ig_anchor[0], c->ig_anchor[1], c->ig_anchor[2]};
   const int64_t anchor_pitch[3] = {c->ig_hist[0].pitch, c->ig_hist[1].pitch, c->ig_hist[2].pitch};
-  for (int done = 0; done < n_frames;) {
-    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-    const int n = chunk_len(n_frames, done, FB);
-    pqa_device_clip f{};
-    for (int p = 0; p < c->n_planes; ++p) {
-      for (int k = 0; k < n; ++k)
-        HIPCHK(c, hipMemcpy2D(c->ig_stage + (size_t)k * c->ig_stage_bytes + c->ig_stage_off[p], c->ig_hist[p].pitch,
-                              frames[(size_t)(done + k) * 3 + p], strides[p], (size_t)c->pw[p] * c->esize, c->ph[p],
-                              hipMemcpyHostToDevice));
-      f.plane[p] = c->ig_stage + c->ig_stage_off[p];
-      f.row_pitch[p] = c->ig_hist[p].pitch;
-      f.frame_pitch[p] = (int64_t)c->ig_stage_bytes;
-    }
-    const int rc = frame_sad_launch(c, anchor, anchor_pitch, &f, n, out + (size_t)done * 3);
-    if (rc != PQA_OK) return rc;
-    done += n;
+  // The frames take the same synchronous copies into SIDE_STAGE_A, laid out as every staged frame is: for whole frames in one
+  // or two chunks the runtime's pageable copy is twice as fast as a pack into a pinned chunk and its upload (DESIGN.md,
+  // "The pair staging").  A copy has left the caller's plane on return; a chunk's kernel is waited for before the buffer is
+  // written again.
+  const PairJob j = sad_job(c, n_frames, ctx_chunk(c), out);
+  int rc = side_reserve(c, SIDE_STAGE_A, j.L.frame_bytes * (size_t)(n_frames < j.chunk ? n_frames : j.chunk));
+  if (rc == PQA_OK) rc = job_reserve(c, j);
+  if (rc != PQA_OK) return rc;
+  auto* const stage = (uint8_t*)c->side_buf[SIDE_STAGE_A];
+  const auto launch = sad_launch(c, anchor, anchor_pitch);
+  PlaneRun cur[3];
+  plane_runs(staged_clip(j.L, stage), 0, c->esize, cur);
+  hipError_t e = hipSuccess;
+  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += j.chunk) {
+    const int n = chunk_len(n_frames, f0, j.chunk);
+    if (f0 > 0) e = hipStreamSynchronize(c->stream);
+    for (int f = 0; f < n; ++f)
+      for (int p = 0; p < c->n_planes && e == hipSuccess; ++p)   // a frame of the list is three pointers whatever n_planes is
+        e = hipMemcpy2D(stage + (size_t)f * j.L.frame_bytes + j.L.off[p], j.L.plane[p].pitch, frames[(size_t)(f0 + f) * 3 + p], strides[p],
+                        j.L.plane[p].row_bytes, c->ph[p], hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch(cur, nullptr, n, f0);
   }
-  return PQA_OK;
+  return side_finish(c, j.who, e, out, c->side_buf[j.out_buf], j.out_bytes);
 }
 
 // ---- luma statistics ---------------------------------------------------------------------------------------------------
-// Launches write their results side by side into luma_out (kLumaOutFrames frames); the host copy and the sync happen once
-// per kLumaOutFrames frames, not once per launch.
 
 int pqa_set_luma_gray(pqa_ctx* c, uint32_t mode) {
   if (!c) return PQA_EINVAL;
@@ -1054,64 +1060,14 @@ int pqa_luma_stats_device(pqa_ctx* c, const void* luma, int64_t row_pitch, int64
                           uint32_t threshold, uint64_t* out) {
   if (!c) return PQA_EINVAL;
   if (!luma || n_frames < 0 || (n_frames > 0 && !out)) return fail(c, PQA_EINVAL, "bad argument");
-  const int chk = check_device_clip(c, "", row_pitch, frame_pitch, INT64_MIN);   // this entry has no rule on the row pitch
-  if (chk != PQA_OK) return chk;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
-  for (int done = 0; done < n_frames;) {
-    const int group = chunk_len(n_frames, done, kLumaOutFrames);
-    hipError_t e = hipSuccess;
-    for (int g0 = 0; g0 < group && e == hipSuccess;) {
-      const int n = chunk_len(group, g0, c->B);
-      const PlaneRun run{(const uint8_t*)luma + (int64_t)(done + g0) * frame_pitch, row_pitch / c->esize, frame_pitch / c->esize};
-      e = launch_luma_stats(c->stream, c->elem, run, n, c->pw[0], c->ph[0], threshold, gray_bpc, c->luma_part,
-                            c->luma_out + (size_t)g0 * 3);
-      g0 += n;
-    }
-    const int rc = side_finish(c, "luma statistics chunk", e, out + (size_t)done * 3, c->luma_out, (size_t)group * 3 * sizeof(uint64_t));
-    if (rc != PQA_OK) return rc;
-    done += group;
-  }
-  return PQA_OK;
+  return luma_stats(c, DevClip{luma, row_pitch, frame_pitch}, n_frames, threshold, out);
 }
 
 int pqa_luma_stats(pqa_ctx* c, const void* const* luma_frames, int64_t row_stride, int32_t n_frames, uint32_t threshold,
                    uint64_t* out) {
   if (!c) return PQA_EINVAL;
   if (n_frames < 0 || (n_frames > 0 && (!luma_frames || !out))) return fail(c, PQA_EINVAL, "bad argument");
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  int rc = check_host_frames(c, "", "", luma_frames, 1, n_frames, row_stride, row_bytes, false);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = luma_staging_ensure(c);
-  if (rc != PQA_OK) return rc;
-  const int h = c->ph[0];
-  const size_t frame_bytes = (size_t)c->luma_pitch * h;
-  const int gray_bpc = c->luma_gray == PQA_GRAY_BT601_FULL ? (int)c->cfg.bit_depth : 0;
-  // Chunks of LB frames alternate between the two halves; every chunk's kernel writes its results next to the previous
-  // ones in luma_out: no device-to-host copy sits between the chunks (into the caller's pageable `out` it would block the
-  // host until the kernel in front of it is done, and the next chunk could not be packed under that kernel).
-  int hf = 0;
-  for (int done = 0; done < n_frames;) {
-    const int group = chunk_len(n_frames, done, kLumaOutFrames);
-    hipError_t e = hipSuccess;
-    for (int g0 = 0; g0 < group && e == hipSuccess && !c->cancelled.load(); hf ^= 1) {
-      const int n = chunk_len(group, g0, c->LB);
-      e = stage_frames(c, hf, luma_frames + done + g0, row_stride, n, row_bytes, h);
-      if (e == hipSuccess) {
-        const PlaneRun run{c->luma_half[hf].dev, c->luma_pitch / c->esize, (int64_t)(frame_bytes / c->esize)};
-        e = launch_luma_stats(c->stream, c->elem, run, n, c->pw[0], h, threshold, gray_bpc, c->luma_part,
-                              c->luma_out + (size_t)g0 * 3);
-      }
-      g0 += n;
-    }
-    rc = side_finish(c, "luma statistics chunk", e, out + (size_t)done * 3, c->luma_out, (size_t)group * 3 * sizeof(uint64_t));
-    if (rc != PQA_OK) return rc;
-    done += group;
-  }
-  return PQA_OK;
+  return luma_stats(c, HostClip{luma_frames, &row_stride}, n_frames, threshold, out);
 }
 
 // ---- temporal alignment (cross_sse.hip) --------------------------------------------------------------------------------
@@ -1163,33 +1119,39 @@ int pqa_cross_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_str
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_ref == 0) return PQA_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  rc = luma_staging_ensure(c);
-  if (rc != PQA_OK) return rc;
-  const int span = k_hi - k_lo + 1, h = c->ph[0], es = c->esize;
+  const int span = k_hi - k_lo + 1, h = c->ph[0], es = c->esize, chunk = ctx_chunk(c);
   const bool mfma = c->xsse_mfma && c->elem == ELEM_U8;
-  rc = xs_prepare(c, mfma, span, 1, n_ref, n_dis);
-  const size_t frame_bytes = (size_t)c->luma_pitch * h;
+  const host::ClipLayout L = ctx_plane(c, 0);
+  const size_t frame_bytes = L.frame_bytes;
   const int dis_ring = 31 + span;   // the captured frames one reference tile meets
+  rc = xs_prepare(c, mfma, span, 1, n_ref, n_dis);
+  for (int k = 0; k < 2 && rc == PQA_OK; ++k) rc = side_pin_reserve(c, k, frame_bytes * chunk);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_XSSE_REF, frame_bytes * 32);
   if (rc == PQA_OK) rc = side_reserve(c, SIDE_XSSE_DIS, frame_bytes * dis_ring);
   if (rc != PQA_OK) return rc;
-  const XsseClip ref{c->side_buf[SIDE_XSSE_REF], c->luma_pitch / es, (int64_t)(frame_bytes / es), 32, n_ref};
-  const XsseClip dis{c->side_buf[SIDE_XSSE_DIS], c->luma_pitch / es, (int64_t)(frame_bytes / es), dis_ring, n_dis};
+  const XsseClip ref{c->side_buf[SIDE_XSSE_REF], L.plane[0].pitch / es, (int64_t)(frame_bytes / es), 32, n_ref};
+  const XsseClip dis{c->side_buf[SIDE_XSSE_DIS], L.plane[0].pitch / es, (int64_t)(frame_bytes / es), dis_ring, n_dis};
   auto* nr = (unsigned long long*)c->side_buf[SIDE_XSSE_NORM_REF];
   auto* nd = (unsigned long long*)c->side_buf[SIDE_XSSE_NORM_DIS];
   auto* dev_out = (unsigned long long*)c->side_buf[SIDE_XSSE_OUT];
   // Every frame crosses PCIe once: reference tile b replaces tile b - 1 in its 32 slots, and the captured window only ever
   // moves forward, so a tile uploads the captured frames between the previous window's end and its own.  Frames travel in
-  // chunks of LB that alternate between the two pinned halves, as in pqa_luma_stats; the stream orders a tile's uploads
-  // before its kernels and those before the next tile's uploads into the same slots.
+  // chunks that alternate between the two pinned chunks, each packed once its last upload has left it (pin_wait) and so under
+  // the uploads of the chunk before; the stream orders a tile's uploads before its kernels and those before the next tile's
+  // uploads into the same slots.
   hipError_t e = hipSuccess;
-  int hf = 0;
+  int pin = 0;
   const auto live = [&] { return e == hipSuccess && !c->cancelled.load(); };
   const auto upload = [&](const void* const* frames, int64_t stride, const XsseClip& clip, int64_t first, int64_t last,
                           unsigned long long* norms) {   // frames first ... last - 1 into their ring slots
-    for (int64_t f0 = first; f0 < last && live(); hf ^= 1) {
-      const int n = (int)(last - f0 < c->LB ? last - f0 : c->LB);
-      e = stage_frames(c, hf, frames + f0, stride, n, row_bytes, h, (uint8_t*)clip.base, clip.ring, f0);
+    for (int64_t f0 = first; f0 < last && live(); pin ^= 1) {
+      const int n = chunk_len((int)last, (int)f0, chunk);
+      e = pin_wait(c, pin);
+      if (e == hipSuccess) host::pack_clip(c->side_pin[pin], L, frames, &stride, (int)f0, n);
+      for (int f = 0; f < n && e == hipSuccess; ++f)   // a ring may wrap inside a chunk: every frame to its own slot
+        e = hipMemcpyAsync((uint8_t*)clip.base + (size_t)((f0 + f) % clip.ring) * frame_bytes, c->side_pin[pin] + (size_t)f * frame_bytes, frame_bytes,
+                           hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = pin_mark(c, pin);
       // the frames of a chunk lie in consecutive slots unless the ring wraps inside it: one norm launch per frame
       for (int f = 0; mfma && f < n && e == hipSuccess; ++f) e = launch_xsse_norms(c->stream, clip, f0 + f, 1, c->pw[0], h, norms);
       f0 += n;
@@ -1218,59 +1180,11 @@ int pqa_cross_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_str
 
 int pqa_shift_sse_device(pqa_ctx* c, const void* ref_luma, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis_luma,
                          int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t radius, uint64_t* out) {
-  int rc = sh_check(c, ref_luma, dis_luma, n_frames, radius, out);
-  if (rc != PQA_OK) return rc;
-  if (n_frames == 0) return PQA_OK;
-  const int es = c->esize;
-  const int64_t row_bytes = (int64_t)c->pw[0] * es;
-  rc = check_device_clip(c, "shift_sse: ", ref_row_pitch, ref_frame_pitch, row_bytes);
-  if (rc == PQA_OK) rc = check_device_clip(c, "shift_sse: ", dis_row_pitch, dis_frame_pitch, row_bytes);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = sh_prepare(c, radius, n_frames);
-  if (rc != PQA_OK) return rc;
-  const size_t n = (size_t)(2 * radius + 1) * (2 * radius + 1);
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_SHIFT_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kShiftChunk)
-    e = launch_shift_sse(c->stream, c->elem, (const uint8_t*)ref_luma + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
-                         ref_frame_pitch / es, (const uint8_t*)dis_luma + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
-                         dis_frame_pitch / es, chunk_len(n_frames, f0, kShiftChunk), c->pw[0], c->ph[0], radius,
-                         c->side_buf[SIDE_SHIFT_PART], (unsigned long long*)c->side_buf[SIDE_SHIFT_ROWSQ], dev_out + (size_t)f0 * n);
-  return side_finish(c, "shift_sse", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+  return shift_sse(c, DevClip{ref_luma, ref_row_pitch, ref_frame_pitch}, DevClip{dis_luma, dis_row_pitch, dis_frame_pitch}, n_frames, radius, out);
 }
-
 int pqa_shift_sse(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
                   int64_t dis_row_stride, int32_t n_frames, int32_t radius, uint64_t* out) {
-  int rc = sh_check(c, ref_frames, dis_frames, n_frames, radius, out);
-  if (rc != PQA_OK) return rc;
-  if (n_frames == 0) return PQA_OK;
-  const size_t row_bytes = (size_t)c->pw[0] * c->esize;
-  rc = check_host_frames(c, "shift_sse: ", "", ref_frames, 1, n_frames, ref_row_stride, row_bytes, false);
-  if (rc == PQA_OK) rc = check_host_frames(c, "shift_sse: ", "", dis_frames, 1, n_frames, dis_row_stride, row_bytes, false);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = luma_staging_ensure(c);
-  if (rc == PQA_OK) rc = sh_prepare(c, radius, n_frames);   // LB <= kShiftChunk: the workspaces of a full chunk hold every chunk here
-  if (rc != PQA_OK) return rc;
-  const int h = c->ph[0], es = c->esize;
-  const size_t frame_bytes = (size_t)c->luma_pitch * h, n = (size_t)(2 * radius + 1) * (2 * radius + 1);
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_SHIFT_OUT];
-  hipError_t e = hipSuccess;
-  // Chunks of LB (<= 8) pairs: the reference frames go through pinned / device half 0, the captured ones through half 1.
-  // The stream orders a chunk's kernel before the next chunk's uploads into the same device halves.
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += c->LB) {
-    const int m = chunk_len(n_frames, f0, c->LB);
-    e = stage_frames(c, 0, ref_frames + f0, ref_row_stride, m, row_bytes, h);
-    if (e == hipSuccess) e = stage_frames(c, 1, dis_frames + f0, dis_row_stride, m, row_bytes, h);
-    if (e == hipSuccess)
-      e = launch_shift_sse(c->stream, c->elem, c->luma_half[0].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es),
-                           c->luma_half[1].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es), m, c->pw[0], h, radius,
-                           c->side_buf[SIDE_SHIFT_PART], (unsigned long long*)c->side_buf[SIDE_SHIFT_ROWSQ], dev_out + (size_t)f0 * n);
-  }
-  return side_finish(c, "shift_sse", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+  return shift_sse(c, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, radius, out);
 }
 
 // ---- level alignment (level_stats.hip) ---------------------------------------------------------------------------------
@@ -1279,59 +1193,11 @@ int pqa_level_bins(const pqa_ctx* c) { return c ? 1 << c->cfg.bit_depth : PQA_EI
 
 int pqa_level_stats_device(pqa_ctx* c, const void* ref, int64_t ref_row_pitch, int64_t ref_frame_pitch, const void* dis,
                            int64_t dis_row_pitch, int64_t dis_frame_pitch, int32_t n_frames, int32_t plane, uint64_t* out) {
-  int rc = lv_check(c, ref, dis, n_frames, plane, out);
-  if (rc != PQA_OK) return rc;
-  if (n_frames == 0) return PQA_OK;
-  const int es = c->esize, bpc = (int)c->cfg.bit_depth;
-  const int64_t row_bytes = (int64_t)c->pw[plane] * es;
-  rc = check_device_clip(c, "level_stats: ", ref_row_pitch, ref_frame_pitch, row_bytes);
-  if (rc == PQA_OK) rc = check_device_clip(c, "level_stats: ", dis_row_pitch, dis_frame_pitch, row_bytes);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = side_reserve(c, SIDE_LEVEL_OUT, level_out_bytes(bpc, n_frames));
-  if (rc != PQA_OK) return rc;
-  const size_t n = (size_t)3 << bpc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_LEVEL_OUT];
-  hipError_t e = hipSuccess;
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += kLevelChunk)
-    e = launch_level_stats(c->stream, c->elem, bpc, (const uint8_t*)ref + (int64_t)f0 * ref_frame_pitch, ref_row_pitch / es,
-                           ref_frame_pitch / es, (const uint8_t*)dis + (int64_t)f0 * dis_frame_pitch, dis_row_pitch / es,
-                           dis_frame_pitch / es, chunk_len(n_frames, f0, kLevelChunk), c->pw[plane], c->ph[plane],
-                           dev_out + (size_t)f0 * n);
-  return side_finish(c, "level_stats", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+  return level_stats(c, DevClip{ref, ref_row_pitch, ref_frame_pitch}, DevClip{dis, dis_row_pitch, dis_frame_pitch}, n_frames, plane, out);
 }
-
 int pqa_level_stats(pqa_ctx* c, const void* const* ref_frames, int64_t ref_row_stride, const void* const* dis_frames,
                     int64_t dis_row_stride, int32_t n_frames, int32_t plane, uint64_t* out) {
-  int rc = lv_check(c, ref_frames, dis_frames, n_frames, plane, out);
-  if (rc != PQA_OK) return rc;
-  if (n_frames == 0) return PQA_OK;
-  const size_t row_bytes = (size_t)c->pw[plane] * c->esize;
-  rc = check_host_frames(c, "level_stats: ", "", ref_frames, 1, n_frames, ref_row_stride, row_bytes, true);
-  if (rc == PQA_OK) rc = check_host_frames(c, "level_stats: ", "", dis_frames, 1, n_frames, dis_row_stride, row_bytes, true);
-  if (rc != PQA_OK) return rc;
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int bpc = (int)c->cfg.bit_depth;
-  rc = luma_staging_ensure(c);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_LEVEL_OUT, level_out_bytes(bpc, n_frames));
-  if (rc != PQA_OK) return rc;
-  // a chroma plane is no larger than the luma plane, so it travels through the luma staging with the luma pitches
-  const int w = c->pw[plane], h = c->ph[plane], es = c->esize;
-  const size_t frame_bytes = (size_t)c->luma_pitch * c->ph[0], n = (size_t)3 << bpc;
-  auto* dev_out = (unsigned long long*)c->side_buf[SIDE_LEVEL_OUT];
-  hipError_t e = hipSuccess;
-  // chunks of LB (<= kLevelChunk) pairs, staged as in pqa_shift_sse: reference frames through half 0, captured ones through half 1
-  for (int f0 = 0; f0 < n_frames && e == hipSuccess && !c->cancelled.load(); f0 += c->LB) {
-    const int m = chunk_len(n_frames, f0, c->LB);
-    e = stage_frames(c, 0, ref_frames + f0, ref_row_stride, m, row_bytes, h);
-    if (e == hipSuccess) e = stage_frames(c, 1, dis_frames + f0, dis_row_stride, m, row_bytes, h);
-    if (e == hipSuccess)
-      e = launch_level_stats(c->stream, c->elem, bpc, c->luma_half[0].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es),
-                             c->luma_half[1].dev, c->luma_pitch / es, (int64_t)(frame_bytes / es), m, w, h, dev_out + (size_t)f0 * n);
-  }
-  return side_finish(c, "level_stats", e, out, dev_out, (size_t)n_frames * n * sizeof(uint64_t));
+  return level_stats(c, HostClip{ref_frames, &ref_row_stride}, HostClip{dis_frames, &dis_row_stride}, n_frames, plane, out);
 }
 
 // ---- resampler (resample.hip) ------------------------------------------------------------------------------------------

@@ -200,7 +200,9 @@ static void ring_scenarios() {
 
 // ---- the pair staging (host_stage.h) ---------------------------------------------------------------------------------------
 // The device is two heap buffers of exactly the bytes pqa_side.hip reserves; the callables copy as the HIP calls there do and
-// log themselves.  A launch notes which source frames lie in the slots it was given.
+// log themselves.  A launch notes which source frames lie in the slots it was given.  For each pinned buffer the model notes
+// whether an upload out of it is in flight: upload sets the flag, drain clears it, and a buffer that was just packed must not
+// carry it.
 static uint8_t sample_of(int clip, int frame, int y, size_t x) { return (uint8_t)(clip * 131 + frame * 7 + y * 31 + (int)x * 3 + 1); }
 
 struct StageCase {
@@ -243,27 +245,35 @@ static void stage_case(const StageCase& k) {
             src[c].back()[(size_t)y * stride + x] = x < rb[p] ? sample_of(c, f, y, x + 5 * p) : 0xee;
         list[c].push_back(src[c].back().get());
       }
-    pin[c].reset(new uint8_t[C.frame_bytes * slots]);
     dev[c].reset(new uint8_t[C.frame_bytes * (slots + k.carry)]);
   }
+  for (auto& b : pin) b.reset(new uint8_t[C.frame_bytes * slots]);   // one clip: its chunks alternate between the two
   uint8_t* const pins[2] = {pin[0].get(), pin[1].get()};
   const size_t fb = C.frame_bytes;
   std::string log;
   std::vector<Launched> launches;
   std::atomic<int> cancelled{0};
   int chunk_no = 0;   // of the chunk a callable belongs to: upload() opens a chunk's device work, drain() the chunk's host work
+  bool in_flight[2] = {false, false};
   const auto fails = [&](char who) { log += who; return k.fail_in == who && chunk_no == 1 ? 7 : 0; };
   const int rc = stage_walk(
       C, pins, list[0].data(), strides, k.clips == 2 ? list[1].data() : nullptr, strides, k.n_frames, chunk, k.carry, cancelled,
-      [&] { ++chunk_no; return fails('D'); },
+      [&](int b) {   // once per pinned buffer the chunk packs: a pair 0 then 1, one clip the chunk's parity
+        if (k.clips == 1 || b == 0) ++chunk_no;
+        CHECK(k.clips == 2 ? (b == 0 || b == 1) : b == (chunk_no & 1));
+        in_flight[b] = false;
+        return fails('D');
+      },
       [&](int from) {
         CHECK(from >= 1 && from < slots + k.carry);
         for (int c = 0; c < k.clips; ++c) memcpy(dev[c].get(), dev[c].get() + (size_t)from * fb, fb);
         return fails('S');
       },
-      [&](int slot, int n) {
-        CHECK(slot == k.carry && n >= 1 && n <= slots);
-        for (int c = 0; c < k.clips; ++c) memcpy(dev[c].get() + (size_t)slot * fb, pins[c], fb * n);
+      [&](int b, int c, int slot, int n) {
+        CHECK(c < k.clips && b == (k.clips == 2 ? c : chunk_no & 1) && slot == k.carry && n >= 1 && n <= slots);
+        CHECK(!in_flight[b]);   // the pack in front of this upload wrote the buffer
+        memcpy(dev[c].get() + (size_t)slot * fb, pins[b], fb * n);
+        in_flight[b] = true;
         return fails('U');
       },
       [&](int slot, int n, int out_index) {
@@ -272,7 +282,7 @@ static void stage_case(const StageCase& k) {
         for (int c = 0; c < k.clips; ++c)
           for (int i = 0; i < n; ++i) {   // the frame whose samples lie in slot + i
             const uint8_t* plane = dev[c].get() + (size_t)(slot + i) * fb;
-            const int f = (plane[0] - sample_of(c, 0, 0, 0)) / 7;
+            const int f = (uint8_t)(plane[0] - sample_of(c, 0, 0, 0)) / 7;   // 24 frames at most: 7 f stays below 256
             CHECK(f >= 0 && f < k.n_frames);
             for (int p = 0; p < np; ++p)
               for (int y = 0; y < k.h; ++y)
@@ -283,15 +293,18 @@ static void stage_case(const StageCase& k) {
         if (k.cancel) cancelled.store(1);
         return fails('L');
       });
-  // the calls, restated: per chunk drain (not the first), seam (carry 1, not the first), upload, launch
+  // the calls, restated: per chunk drain (not the first), seam (carry 1, not the first), upload, launch; drain and upload
+  // once per pinned buffer, so twice for a pair
   std::string want;
   bool failed = false;
   const int n_chunks = (k.n_frames + chunk - 1) / chunk;
   for (int i = 0; i < n_chunks; ++i) {
     for (char who : {'D', 'S', 'U', 'L'}) {
       if ((who == 'D' && i == 0) || (who == 'S' && (i == 0 || !k.carry))) continue;
-      want += who;
-      if (i == 1 && who == k.fail_in) { failed = true; goto done; }
+      for (int c = 0; c < (who == 'D' || who == 'U' ? k.clips : 1); ++c) {
+        want += who;
+        if (i == 1 && who == k.fail_in) { failed = true; goto done; }
+      }
     }
     if (k.cancel) break;
   }
@@ -315,7 +328,7 @@ static void stage_scenarios() {
   for (size_t row_bytes : {1, 15, 16, 17, 33})
     for (int h : {1, 3})
       for (int64_t extra : {0, 7})
-        for (int n : {0, 1, 2, 8, 9, 16, 17})
+        for (int n : {0, 1, 2, 8, 9, 16, 17, 24})
           for (int carry : {0, 1})
             for (int clips : {2, 1}) stage_case(StageCase{row_bytes, h, extra, n, carry, clips});
   // three planes a frame (pqa_colour_moments, pqa_delta_itp: two clips, a result per frame)
