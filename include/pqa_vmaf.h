@@ -770,6 +770,45 @@ PQA_API int pqa_table_apply_device(pqa_ctx* ctx, const pqa_table_spec* spec, con
                                    int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
                                    int32_t n_frames);
 
+/* Deinterlacing: the planes of an interlaced clip to progressive ones, synchronously, in exact integers -- what lets a capture
+ * that really is interlaced (1080i: two moments in time a frame) be scored against a progressive master.  One field of a source
+ * frame is kept and the other interpolated: from the kept field alone (mode 0, intra) or motion-adaptively from the fields before
+ * and after it (mode 1, adaptive; the w3fdif taps inside yadif's temporal clamp that FFmpeg ships as bwdif -- the arithmetic as
+ * this library states it heads pqa2_amd/csrc/deinterlace.hip and is restated in tests/deinterlace_ref.py; parity with FFmpeg is
+ * not pinned).  first: the parity of the rows whose field comes first in time.  rate 0 (frame): output t keeps the field `first`
+ * of source frame t; rate 1 (field): outputs 2 t and 2 t + 1 keep the fields first and 1 - first of source frame t.  A source
+ * frame before the first is the first and one after the last is the last.  Planes of width x height samples (the spec's,
+ * independent of the context's), u8 in an 8-bit context, otherwise little-endian u16; a sample above 2^bit_depth - 1 is read as
+ * that.  n_frames counts SOURCE frames; dst holds n_frames or 2 n_frames planes.
+ * Any context, no feature bit, no record, no profile id; independent of the scoring chain: a call between two pqa_submit
+ * calls changes no record.  PQA_EINVAL, before any device call, on a null pointer, a bad struct_size, a mode, first or rate
+ * above 1, a width outside 1 ... 8192 or a height outside 2 ... 8192, a negative frame count, a row pitch that is negative or
+ * below a row, a base or pitch that is no multiple of the sample size, or a destination that is the source (there is no in-place
+ * form).  n_frames == 0 succeeds and writes nothing.  No source byte past a row's last sample is read and no destination byte
+ * past it is written.  Kernel: DESIGN.md section 5.
+ *
+ * pqa_deinterlace: frames in HOST memory (src_frames[f] / dst_frames[k] point at planes, rows *_row_stride bytes apart).  Every
+ * source frame crosses PCIe once: the frames travel in chunks of 8 and the last two of a chunk stay in device memory as the
+ * predecessors of the next.
+ * pqa_deinterlace_device: both clips in device memory (frame f at base + f * frame_pitch, rows row_pitch BYTES apart), under
+ * the ordering contract of pqa_submit_device. */
+typedef struct pqa_deint_spec {
+  uint32_t struct_size;   /* sizeof(pqa_deint_spec) */
+  uint32_t width, height; /* of this plane: width 1 ... 8192, height 2 ... 8192 */
+  uint32_t mode;          /* 0 intra, 1 adaptive */
+  uint32_t first;         /* 0 top field first, 1 bottom field first */
+  uint32_t rate;          /* 0 frame: n_frames outputs, 1 field: 2 n_frames outputs */
+} pqa_deint_spec;
+PQA_API int pqa_deinterlace(pqa_ctx* ctx, const pqa_deint_spec* spec, const void* const* src_frames, int64_t src_row_stride,
+                            void* const* dst_frames, int64_t dst_row_stride, int32_t n_frames);
+PQA_API int pqa_deinterlace_device(pqa_ctx* ctx, const pqa_deint_spec* spec, const void* src, int64_t src_row_pitch,
+                                   int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch,
+                                   int32_t n_frames);
+/* what the binding states of the kernel: source frames a launch, bytes of a row and rows of a workgroup's block */
+PQA_API int pqa_deint_chunk(void);
+PQA_API int pqa_deint_block_bytes(void);
+PQA_API int pqa_deint_block_rows(void);
+
 /* Overlay masking: n_frames planes of one clip through a feathered mask, synchronously, in exact integers -- the correction that
  * takes a burnt-in overlay (a channel logo, a clock, a timecode, an OSD) out of the scores once pqa2_amd/distortion.py
  * (persistent_regions, overlay_mask) has found it: both clips are blended towards one flat value there, or the captured clip

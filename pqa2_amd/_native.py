@@ -66,7 +66,7 @@ GRAY_LUMA, GRAY_BT601_FULL = 0, 1   # pqa_set_luma_gray
 EXPORTS = [
     "pqa_version", "pqa_record_doubles", "pqa_ext_doubles", "pqa_ext2_doubles", "pqa_ext3_doubles", "pqa_ext4_doubles", "pqa_ext5_doubles", "pqa_config_init", "pqa_create", "pqa_destroy", "pqa_set_stream",
     "pqa_submit", "pqa_submit_fd", "pqa_submit_fd_run", "pqa_submit_device", "pqa_submit_surfaces", "pqa_submit_packed", "pqa_set_motion_halo", "pqa_set_ref_history", "pqa_set_dis_history", "pqa_set_dis_history_planes", "pqa_set_black_threshold", "pqa_frame_sad", "pqa_frame_sad_device", "pqa_flush", "pqa_collect", "pqa_collect_ext", "pqa_collect_ext2", "pqa_collect_ext3", "pqa_collect_ext4", "pqa_collect_ext5", "pqa_sync",
-    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_mask_blend", "pqa_mask_blend_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_field_moments", "pqa_field_moments_device", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_itp_sums", "pqa_delta_itp", "pqa_delta_itp_device", "pqa_set_luma_gray",
+    "pqa_cancel", "pqa_reset", "pqa_last_error", "pqa_luma_stats_device", "pqa_luma_stats", "pqa_cross_sse_device", "pqa_cross_sse", "pqa_shift_sse_device", "pqa_shift_sse", "pqa_level_stats_device", "pqa_level_stats", "pqa_level_bins", "pqa_resample", "pqa_resample_device", "pqa_unpack", "pqa_unpack_device", "pqa_format_convert", "pqa_format_convert_device", "pqa_rgb_convert", "pqa_rgb_convert_device", "pqa_table_apply", "pqa_table_apply_device", "pqa_deinterlace", "pqa_deinterlace_device", "pqa_deint_chunk", "pqa_deint_block_bytes", "pqa_deint_block_rows", "pqa_mask_blend", "pqa_mask_blend_device", "pqa_flow_moments", "pqa_flow_moments_device", "pqa_line_profiles", "pqa_line_profiles_device", "pqa_tile_moments", "pqa_tile_moments_device", "pqa_band_moments", "pqa_band_moments_device", "pqa_band_sums", "pqa_temporal_moments", "pqa_temporal_moments_device", "pqa_temporal_sums", "pqa_field_moments", "pqa_field_moments_device", "pqa_edge_profiles", "pqa_edge_profiles_device", "pqa_edge_sums", "pqa_colour_sums", "pqa_colour_moments", "pqa_colour_moments_device", "pqa_colour_apply", "pqa_colour_apply_device", "pqa_itp_sums", "pqa_delta_itp", "pqa_delta_itp_device", "pqa_set_luma_gray",
     "pqa_profile_enable",
     "pqa_profile_read", "pqa_profile_kernel_name", "pqa_debug_vif_march_table", "pqa_debug_vif_march_shape", "pqa_debug_vif_strip_shape", "pqa_debug_adm_need",
     "pqa_debug_partial_counts",
@@ -129,6 +129,17 @@ class PqaRgbSpec(C.Structure):
 
 class PqaTableSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class PqaDeintSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("mode", C.c_uint32),
+                ("first", C.c_uint32), ("rate", C.c_uint32)]
+
+
+DEINT_MODES = {"intra": 0, "adaptive": 1}          # pqa_deint_spec.mode
+DEINT_RATES = {"frame": 0, "field": 1}             # pqa_deint_spec.rate
+DEINT_CHUNK = 8                                    # source frames a launch of deinterlace.hip (kernels.h; pqa_deint_chunk())
+DEINT_BLOCK_BYTES, DEINT_BLOCK_ROWS = 1024, 64     # bytes of a row / rows a workgroup there writes (pqa_deint_block_*())
 
 
 MASK_MAX_STEP, MASK_FULL = 6, 256     # pqa_mask_spec: the largest step_log2, the node value that is all fill
@@ -322,6 +333,10 @@ def load():
     lib.pqa_rgb_convert.argtypes = [vp, C.POINTER(PqaRgbSpec), C.POINTER(vp), i64, i32, C.POINTER(vp), C.POINTER(i64 * 3)]
     lib.pqa_table_apply.argtypes = [vp, C.POINTER(PqaTableSpec), vp, C.POINTER(vp), i64, C.POINTER(vp), i64, i32]
     lib.pqa_table_apply_device.argtypes = [vp, C.POINTER(PqaTableSpec), vp, vp, i64, i64, vp, i64, i64, i32]
+    lib.pqa_deinterlace.argtypes = [vp, C.POINTER(PqaDeintSpec), C.POINTER(vp), i64, C.POINTER(vp), i64, i32]
+    lib.pqa_deinterlace_device.argtypes = [vp, C.POINTER(PqaDeintSpec), vp, i64, i64, vp, i64, i64, i32]
+    for fn in (lib.pqa_deint_chunk, lib.pqa_deint_block_bytes, lib.pqa_deint_block_rows):
+        fn.argtypes, fn.restype = [], C.c_int
     lib.pqa_mask_blend.argtypes = [vp, C.POINTER(PqaMaskSpec), vp, C.POINTER(vp), i64, C.POINTER(vp), i64, C.POINTER(vp), i64, i32]
     lib.pqa_mask_blend_device.argtypes = [vp, C.POINTER(PqaMaskSpec), vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i32]
     lib.pqa_unpack.argtypes = [vp, C.POINTER(PqaUnpackSpec), C.POINTER(vp), i64, i32, C.POINTER(vp), C.POINTER(i64 * 3)]

@@ -1,8 +1,9 @@
 // Host side of the staging of the side analyses and plane transforms (pqa_side.hip), free of any device call: how a chunk of
 // frames of the call's own size lies in a pinned buffer, the copy of a caller's frames into it and of results back out, the
-// walk over the chunks of a clip pair (stage_walk) and the walk of a transform (transform_walk).  The device is reached only
-// through callables the caller passes in.  Header-only and plain C++17, as host_pack.h is, so that the CPU harness drives it
-// under ThreadSanitizer / AddressSanitizer (tests/host_harness.cpp); pqa_ctx.h includes it as is.
+// walk over the chunks of a clip pair (stage_walk), the walk of a transform (transform_walk) and that of a transform with a
+// window in time (window_walk).  The device is reached only through callables the caller passes in.  Header-only and plain
+// C++17, as host_pack.h is, so that the CPU harnesses drive it under ThreadSanitizer / AddressSanitizer
+// (tests/host_harness.cpp, tests/window_harness.cpp); pqa_ctx.h includes it as is.
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -158,6 +159,44 @@ auto transform_walk(const ClipLayout& S, const ClipLayout& D, uint8_t* const pin
     const R rc = finish(e, n);
     if (rc != R{}) return rc;
     unpack_clip_out(pin[1], D, dst, dst_strides, dst_step, f0, n);
+  }
+  return R{};
+}
+
+// A transform with a window in time: the outputs of source frame t read the frames t - 1, t and t + 1 (the first frame is its
+// own predecessor and the last its own successor), `per` output frames a source frame, and every source frame is packed and
+// uploaded ONCE.  The device buffer holds chunk + 2 slots (chunk >= 2): a chunk of n frames from f0 on lands in slots
+// 2 ... n + 1, and before the next chunk overwrites them its last two frames move to slots 0 and 1 (only a full chunk has a
+// successor, so those are slots chunk and chunk + 1), where they are the frames f0 - 2 and f0 - 1 of the next.  A chunk's
+// launch emits the outputs of the source frames f0 - 1 ... f0 + n - 2 -- the first chunk's from frame 0 on --, and the clip's
+// last chunk also those of the last frame.  For every chunk:
+//   pack                            the source frames into slots 0 ... n - 1 of pin[0]
+//   seam(from_slot)                 not in the first chunk: device slots from_slot, from_slot + 1 move to slots 0, 1
+//   upload(slot, n)                 the packed frames to the device slots slot ... slot + n - 1
+//   launch(slot, count, t0, m)      the frames the kernel may read are the `count` from device slot `slot` on (it clamps t - 1
+//                                   and t + 1 to them itself); it emits the outputs of m of them from the t0-th on, m * per
+//                                   frames, into the device's output slots 0 ...
+//   finish(e, frames)               ALWAYS, with what the calls before made of it: brings `frames` result frames to pin[1] and
+//                                   waits for the device, so that nothing still reads or writes the pinned buffers
+//   copy out                        the result frames from pin[1] into dst, sample bytes only
+// Stops at the first finish() that returns something other than R{} (success), before the copy out, and returns that.
+template <class Seam, class Upload, class Launch, class Finish>
+auto window_walk(const ClipLayout& S, const ClipLayout& D, uint8_t* const pin[2], const void* const* src, const int64_t src_strides[3],
+                 void* const* dst, const int64_t dst_strides[3], int dst_step, int n_frames, int chunk, int per, Seam seam, Upload upload,
+                 Launch launch, Finish finish) -> decltype(finish(upload(0, 0), 0)) {
+  using R = decltype(finish(upload(0, 0), 0));
+  for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+    const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+    const int kept = f0 > 0 ? 2 : 0;                      // predecessors from the chunk before
+    const int from = f0 > 0 ? f0 - 1 : 0;                 // the first source frame this launch emits
+    const int m = f0 + n - 1 + (f0 + n == n_frames ? 1 : 0) - from;
+    pack_clip(pin[0], S, src, src_strides, f0, n);
+    auto e = kept ? seam(chunk) : decltype(upload(0, 0)){};
+    if (e == decltype(e){}) e = upload(2, n);
+    if (e == decltype(e){} && m > 0) e = launch(2 - kept, kept + n, from - (f0 - kept), m);
+    const R rc = finish(e, m * per);
+    if (rc != R{}) return rc;
+    unpack_clip_out(pin[1], D, dst, dst_strides, dst_step, from * per, m * per);
   }
   return R{};
 }

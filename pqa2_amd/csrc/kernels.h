@@ -668,6 +668,24 @@ hipError_t launch_table_apply(hipStream_t stream, Elem elem, int bit_depth, cons
                               int64_t src_frame_pitch, void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int n_frames, int w,
                               int h);
 
+// ---- deinterlacing: a kept field and a motion-adaptive interpolated one (deinterlace.hip) ---------------------------------------
+// Output planes of the source frames t0 ... t0 + n - 1 of a clip of `count` planes of w x h samples at `src` (w 1 ... 8192,
+// h 2 ... 8192; u8 at 8 bit, otherwise u16, a source sample above 2^bits - 1 is read as that); the neighbours t - 1 and t + 1
+// are clamped to 0 ... count - 1 by the kernel.  per 1: one output a source frame, the field of parity `first` kept; per 2: two,
+// `first` and then 1 - first.  mode 0 intra, 1 adaptive; the arithmetic heads deinterlace.hip.  dst: n * per planes, the first
+// one that of t0.  Frame f at base + f * frame_pitch, pitches in BYTES; dst may not overlap src.  uniform: the still-picture fast
+// path (the same integers).  A workgroup writes kDeintColBytes bytes of kDeintWaves * kDeintBand rows.  Reads no source byte past
+// a row's last sample, writes no destination byte past it.  hipErrorInvalidValue, before any launch, on a null pointer, a size,
+// depth, mode, parity or rate out of range, t0 ... t0 + n - 1 outside the clip, more than 32767 frames, a side that is not made
+// of whole samples or a pitch below a row.
+constexpr int kDeintChunk = 8;          // source frames per launch of the two entries
+constexpr int kDeintColBytes = 1024;    // bytes of a row a wave marches down: 64 lanes of 16
+constexpr int kDeintBand = 16;          // rows of a wave's band
+constexpr int kDeintWaves = 4;          // bands of a workgroup, one below the other
+hipError_t launch_deinterlace(hipStream_t stream, Elem elem, int bit_depth, int mode, int first, int per, bool uniform, const void* src,
+                              int64_t src_row_pitch, int64_t src_frame_pitch, int count, int t0, int n, void* dst, int64_t dst_row_pitch,
+                              int64_t dst_frame_pitch, int w, int h);
+
 // ---- overlay masking: planes through a feathered mask (mask_blend.hip) ---------------------------------------------------------
 // dst = (src (256 - a) + fill a + 128) >> 8 for n_frames planes of w x h samples (1 ... 8192 each way; u8 at 8 bit, otherwise
 // u16), a interpolated from a grid of nodes 0 ... 256 that lie 1 << sx by 1 << sy samples apart (0 ... kMaskMaxStep each),

@@ -1194,6 +1194,8 @@ void read_switches(pqa_ctx* c) {
   c->xsse_mfma = !(xm && xm[0] == '0');
   const char* tw = getenv("PQA_TEMPORAL_WALK");  // 1: a workgroup of the temporal moments walks through time (A/B partner of a workgroup per transition)
   c->temporal_walk = tw && tw[0] == '1';
+  const char* du = getenv("PQA_DEINT_UNIFORM");  // 0: every wave of the deinterlacer takes the general path (test partner of the still-picture fast path)
+  c->deint_uniform = !(du && du[0] == '0');
 }
 
 // The context's own streams and the events of a batch.

@@ -177,6 +177,7 @@ struct pqa_ctx {
   unsigned long long* luma_part = nullptr;
   uint32_t luma_gray = PQA_GRAY_LUMA;
   bool xsse_mfma = true;             // PQA_XSSE_MFMA, read once in pqa_create (8-bit clips; deeper clips always take the VALU path)
+  bool deint_uniform = true;         // PQA_DEINT_UNIFORM, read once in pqa_create: 0 = no still-picture fast path in deinterlace.hip (test partner; the same integers)
   bool temporal_walk = false;        // PQA_TEMPORAL_WALK, read once in pqa_create: 1 takes the walking form of temporal_moments.hip (A/B partner; the same integers)
   pqa::RsCached rs_cache[pqa::kRsCached];   // pqa_resample[_device]: the tables of the last few (filter, geometry, window)
   int rs_next = 0;                          // the slot the next new table replaces

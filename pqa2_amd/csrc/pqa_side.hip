@@ -1,7 +1,7 @@
 // The one-shot analyses and plane transforms of the C ABI that leave the scoring chain alone: anchored frame differences, luma
 // statistics, temporal / spatial / level alignment, the colour moments, Delta E ITP, the spec-driven analyses of planes of the
 // call's own size (registration moments, tile / band / temporal moments, edge and line profiles), and the transforms (resampler,
-// packed unpack, format and RGB converters, table apply, mask blend, colour-matrix apply).  Each has an entry for a clip in HBM
+// packed unpack, format and RGB converters, table apply, deinterlacer, mask blend, colour-matrix apply).  Each has an entry for a clip in HBM
 // and one for frames in host memory.  Host frames, of the context's size or of the call's own, take one staging path, whose host
 // side is host_stage.h: two pinned chunks and two staging buffers.  The analyses share one driver per kind of clip (pair_run) and,
 // where a spec names the plane, one checker (spec_check); the transforms share one driver per kind of clip (transform_run);
@@ -645,8 +645,14 @@ struct TransformJob {
   bool in_place = false;           // host frames: the launch leaves the result where the source was uploaded (pqa_mask_blend)
   SideBuf side_buf = kSideBufs;    // what front() uploads into, of side_bytes
   size_t side_bytes = 0;
+  int per = 1;                     // a windowed launch: destination frames per source frame
 };
 const auto no_front = [] { return hipSuccess; };
+// A launch with a window in time (pqa_deinterlace) is launch(clip, destination, count, t0, m): the outputs of the m source frames
+// from the t0-th on of the `count` frames of `clip`, whose neighbours in time it reads and clamps to the clip itself, go to
+// `destination`, per frames each.
+template <class Launch>
+constexpr bool kWindowed = std::is_invocable<Launch, const pqa_device_clip&, const pqa_device_clip&, int, int, int>::value;
 
 template <class Front, class Launch>
 int transform_run(pqa_ctx* c, const TransformJob& j, const pqa_device_clip& src, const pqa_device_clip* aux, const pqa_device_clip& dst,
@@ -657,7 +663,8 @@ int transform_run(pqa_ctx* c, const TransformJob& j, const pqa_device_clip& src,
   hipError_t e = front();
   if (e == hipSuccess)
     e = launch_runs(j.n_frames, j.cap, nullptr, [&](int f0, int n) {
-      return launch(clip_from(src, f0), aux ? clip_from(*aux, f0) : pqa_device_clip{}, clip_from(dst, f0), n);
+      if constexpr (kWindowed<Launch>) return launch(src, clip_from(dst, f0 * j.per), j.n_frames, f0, n);
+      else return launch(clip_from(src, f0), aux ? clip_from(*aux, f0) : pqa_device_clip{}, clip_from(dst, f0), n);
     });
   return side_finish(c, j.who, e, nullptr, nullptr, 0);
 }
@@ -666,31 +673,44 @@ int transform_run(pqa_ctx* c, const TransformJob& j, const pqa_device_clip& src,
 // chunks into SIDE_STAGE_A (a second input behind it, into SIDE_STAGE_B), the launch writes SIDE_STAGE_B (in_place: blends
 // where the source lies; a second input needs that), and the result comes back through the second pinned chunk and is copied
 // out before the next chunk is packed: one side_finish per chunk.  Rows lie 16 bytes apart at least, so the kernels' wide
-// paths apply.  Nothing in the staging buffers outlives the call.
+// paths apply.  Nothing in the staging buffers outlives the call.  A windowed launch (kWindowed; it has no front and no second
+// input) travels as host::window_walk lays out instead: SIDE_STAGE_A holds two slots more than a chunk, the last two frames of a
+// chunk stay there as the predecessors of the next, and a chunk brings back the outputs of up to a chunk plus one source frames.
 template <class Front, class Launch>
 int transform_run(pqa_ctx* c, const TransformJob& j, const HostClip& src, const HostClip* aux, const HostClip& dst, Front front, Launch launch) {
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk), sb = j.S.frame_bytes * slots, db = j.D.frame_bytes * slots;
+  constexpr bool windowed = kWindowed<Launch>;   // host::window_walk: two slots of predecessors, a launch one source frame late
+  const size_t slots = (size_t)(j.n_frames < j.chunk ? j.n_frames : j.chunk), sb = j.S.frame_bytes * slots,
+               db = j.D.frame_bytes * (slots + (windowed ? 1 : 0)) * j.per;
   int rc = side_pin_reserve(c, 0, sb * (aux ? 2 : 1));
   if (rc == PQA_OK) rc = side_pin_reserve(c, 1, db);
   if (rc == PQA_OK && j.side_buf != kSideBufs) rc = side_reserve(c, j.side_buf, j.side_bytes);
-  if (rc == PQA_OK) rc = side_reserve(c, SIDE_STAGE_A, sb);
+  if (rc == PQA_OK) rc = side_reserve(c, SIDE_STAGE_A, sb + (windowed ? 2 * j.S.frame_bytes : 0));
   if (rc == PQA_OK && (aux || !j.in_place)) rc = side_reserve(c, SIDE_STAGE_B, aux ? sb : db);
   if (rc != PQA_OK) return rc;
   void* const a = c->side_buf[SIDE_STAGE_A];
   void* const b = c->side_buf[SIDE_STAGE_B];
   const pqa_device_clip s = staged_clip(j.S, a), x = aux ? staged_clip(j.S, b) : pqa_device_clip{}, d = staged_clip(j.D, j.in_place ? a : b);
-  return host::transform_walk(
-      j.S, j.D, c->side_pin, src.at, src.strides, aux ? aux->at : nullptr, aux ? aux->strides : nullptr, (void* const*)dst.at, dst.strides,
-      j.dst_step, j.n_frames, j.chunk,
-      [&](int f0, int n) {
-        hipError_t e = f0 == 0 ? front() : hipSuccess;
-        if (e == hipSuccess) e = hipMemcpyAsync(a, c->side_pin[0], j.S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && aux) e = hipMemcpyAsync(b, c->side_pin[0] + sb, j.S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
-        return e;
-      },
-      [&](int n) { return launch(s, x, d, n); },
-      [&](hipError_t e, int n) { return side_finish(c, j.who, e, c->side_pin[1], d.plane[0], j.D.frame_bytes * n); });
+  const auto finish = [&](hipError_t e, int n) { return side_finish(c, j.who, e, c->side_pin[1], d.plane[0], j.D.frame_bytes * n); };
+  if constexpr (windowed) {
+    const size_t fb = j.S.frame_bytes;
+    return host::window_walk(
+        j.S, j.D, c->side_pin, src.at, src.strides, (void* const*)dst.at, dst.strides, j.dst_step, j.n_frames, j.chunk, j.per,
+        [&](int from_slot) { return hipMemcpyAsync(a, (const uint8_t*)a + fb * from_slot, 2 * fb, hipMemcpyDeviceToDevice, c->stream); },
+        [&](int slot, int n) { return hipMemcpyAsync((uint8_t*)a + fb * slot, c->side_pin[0], fb * n, hipMemcpyHostToDevice, c->stream); },
+        [&](int slot, int count, int t0, int m) { return launch(clip_from(s, slot), d, count, t0, m); }, finish);
+  } else {
+    return host::transform_walk(
+        j.S, j.D, c->side_pin, src.at, src.strides, aux ? aux->at : nullptr, aux ? aux->strides : nullptr, (void* const*)dst.at, dst.strides,
+        j.dst_step, j.n_frames, j.chunk,
+        [&](int f0, int n) {
+          hipError_t e = f0 == 0 ? front() : hipSuccess;
+          if (e == hipSuccess) e = hipMemcpyAsync(a, c->side_pin[0], j.S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+          if (e == hipSuccess && aux) e = hipMemcpyAsync(b, c->side_pin[0] + sb, j.S.frame_bytes * n, hipMemcpyHostToDevice, c->stream);
+          return e;
+        },
+        [&](int n) { return launch(s, x, d, n); }, finish);
+  }
 }
 
 // The destination rules that pqa_unpack[_device] and pqa_rgb_convert[_device] share, after `cancelled` (no device call).  A
@@ -872,6 +892,29 @@ int table_run(pqa_ctx* c, const pqa_table_spec* sp, const void* table, const Cli
                          return launch_table_apply(c->stream, c->elem, (int)c->cfg.bit_depth, c->side_buf[SIDE_TABLE_LUT], s.plane[0], s.row_pitch[0],
                                                    s.frame_pitch[0], const_cast<void*>(d.plane[0]), d.row_pitch[0], d.frame_pitch[0], n, w, h);
                        });
+}
+
+// deinterlacer (deinterlace.hip).  The argument rules both entries share, in spec_check's order (no device call); a plane has a
+// row of each parity from height 2 on.
+int deint_check(pqa_ctx* c, const pqa_deint_spec* sp, const void* src, const void* dst, int32_t n_frames) {
+  return spec_check(c, "deinterlace", sp, 1, src, dst, n_frames, sp, 1, [&] {
+    if (sp->mode > 1) return fail(c, PQA_EINVAL, "deinterlace: bad mode %u", sp->mode);
+    if (sp->first > 1) return fail(c, PQA_EINVAL, "deinterlace: bad first %u", sp->first);
+    if (sp->rate > 1) return fail(c, PQA_EINVAL, "deinterlace: bad rate %u", sp->rate);
+    return sp->height == 1 ? fail(c, PQA_EINVAL, "deinterlace: height 1 has one field only") : (int)PQA_OK;
+  });
+}
+
+template <class Clip>
+int deint_run(pqa_ctx* c, const pqa_deint_spec* sp, const Clip& src, const Clip& dst, int32_t n_frames) {
+  const int w = (int)sp->width, h = (int)sp->height;
+  const host::ClipLayout P = host::plane_clip((size_t)w * c->esize, h);
+  TransformJob j{"deinterlace", n_frames, kDeintChunk, kDeintChunk, P, P};
+  j.per = 1 + (int)sp->rate;
+  return transform_run(c, j, src, nullptr, dst, no_front, [&](const pqa_device_clip& s, const pqa_device_clip& d, int count, int t0, int m) {
+    return launch_deinterlace(c->stream, c->elem, (int)c->cfg.bit_depth, (int)sp->mode, (int)sp->first, j.per, c->deint_uniform, s.plane[0],
+                              s.row_pitch[0], s.frame_pitch[0], count, t0, m, const_cast<void*>(d.plane[0]), d.row_pitch[0], d.frame_pitch[0], w, h);
+  });
 }
 
 // The argument rules both entries share, in spec_check's order and then the grid's (no device call); bounds: what one pass over the grid tells (kernels.h).
@@ -1348,6 +1391,47 @@ int pqa_table_apply(pqa_ctx* c, const pqa_table_spec* spec, const void* table, c
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   if (n_frames == 0) return PQA_OK;
   return table_run(c, spec, table, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_frames, &dst_row_stride}, n_frames);
+}
+
+// ---- deinterlacing: a kept field and an interpolated one (deinterlace.hip) ------------------------------------------------------
+
+int pqa_deint_chunk(void) { return kDeintChunk; }
+int pqa_deint_block_bytes(void) { return kDeintColBytes; }
+int pqa_deint_block_rows(void) { return kDeintWaves * kDeintBand; }
+
+int pqa_deinterlace_device(pqa_ctx* c, const pqa_deint_spec* spec, const void* src, int64_t src_row_pitch, int64_t src_frame_pitch,
+                           void* dst, int64_t dst_row_pitch, int64_t dst_frame_pitch, int32_t n_frames) {
+  int rc = deint_check(c, spec, src, dst, n_frames);
+  if (rc != PQA_OK) return rc;
+  const int es = c->esize;
+  const int64_t row = (int64_t)spec->width * es;
+  rc = check_device_planes(c, "deinterlace", {{"source", src, src_row_pitch, src_frame_pitch, row, es}, {"destination", dst, dst_row_pitch, dst_frame_pitch, row, es}});
+  if (rc != PQA_OK) return rc;
+  if (n_frames > 0 && dst == src) return fail(c, PQA_EINVAL, "deinterlace: the destination is the source");
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  return deint_run(c, spec, one_plane(src, src_row_pitch, src_frame_pitch), one_plane(dst, dst_row_pitch, dst_frame_pitch), n_frames);
+}
+
+int pqa_deinterlace(pqa_ctx* c, const pqa_deint_spec* spec, const void* const* src_frames, int64_t src_row_stride, void* const* dst_frames,
+                    int64_t dst_row_stride, int32_t n_frames) {
+  int rc = deint_check(c, spec, src_frames, dst_frames, n_frames);
+  if (rc != PQA_OK) return rc;
+  const size_t row = (size_t)spec->width * c->esize;
+  const int n_out = n_frames * (1 + (int)spec->rate);
+  rc = check_host_frames(c, "deinterlace: ", "source ", src_frames, 1, n_frames, src_row_stride, row, true);
+  if (rc == PQA_OK) rc = check_host_frames(c, "deinterlace: ", "destination ", (const void* const*)dst_frames, 1, n_out, dst_row_stride, row, true);
+  if (rc != PQA_OK) return rc;
+  if (n_frames > 0 && (src_row_stride % c->esize || dst_row_stride % c->esize))
+    return fail(c, PQA_EINVAL, "deinterlace: stride is not a multiple of the sample size");
+  std::vector<const void*> sources(src_frames, src_frames + n_frames);
+  std::sort(sources.begin(), sources.end(), std::less<const void*>());   // no in-place form: the window reads rows after they would be written
+  for (int k = 0; k < n_out; ++k)
+    if (std::binary_search(sources.begin(), sources.end(), (const void*)dst_frames[k], std::less<const void*>()))
+      return fail(c, PQA_EINVAL, "deinterlace: destination frame %d is a source frame", k);
+  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames == 0) return PQA_OK;
+  return deint_run(c, spec, HostClip{src_frames, &src_row_stride}, HostClip{(const void* const*)dst_frames, &dst_row_stride}, n_frames);
 }
 
 // ---- overlay masking: planes through a feathered mask (mask_blend.hip) ---------------------------------------------------------

@@ -647,6 +647,48 @@ class FeatureEngine:
                                                     dst_ptr or None, dst_row_pitch, dst_frame_pitch, int(n_frames)))
         del keep_t
 
+    # -- deinterlacing -----------------------------------------------------------------------
+    def _deint_spec(self, shape, mode, first, rate):
+        """pqa_deint_spec of planes of `shape` = (height, width); a mode or rate by name, a field parity 0 / 1"""
+        if mode not in N.DEINT_MODES:
+            raise ValueError(f"deinterlace mode {mode!r} is none of {sorted(N.DEINT_MODES)}")
+        if rate not in N.DEINT_RATES:
+            raise ValueError(f"deinterlace rate {rate!r} is none of {sorted(N.DEINT_RATES)}")
+        if first not in (0, 1):
+            raise ValueError(f"deinterlace first {first!r} is neither 0 (top field first) nor 1")
+        return self._plane_spec(N.PqaDeintSpec, shape, mode=N.DEINT_MODES[mode], first=first, rate=N.DEINT_RATES[rate])
+
+    def deinterlace(self, frames, mode: str = "adaptive", first: int = 0, rate: str = "frame", shape=None):
+        """A list of new 2-D arrays: the planes of an interlaced clip (HOST memory, in time order) deinterlaced in exact
+        integers (pqa_deinterlace; definition: include/pqa_vmaf.h).  mode "intra" interpolates the dropped field from the kept
+        one, "adaptive" from the fields before and after it where the picture is still; first: the parity of the rows that
+        come first in time (0: top field first); rate "frame": one output a source frame, the field `first` kept; "field":
+        two, `first` and then the other.  The planes have any one size of their own (`shape`, or the first frame's), at least
+        two rows; every source frame is uploaded once."""
+        arrs = [np.asarray(f) for f in frames]
+        shape = tuple(int(v) for v in (shape if shape is not None else (arrs[0].shape if arrs else (self.height, self.width))))
+        if len(shape) != 2:
+            raise ValueError("deinterlace needs 2-D planes")
+        sp = self._deint_spec(shape, mode, first, rate)
+        keep, sptr, sstride = self._luma_list(arrs, "source", shape)
+        out = [np.empty(shape, self.dtype) for _ in range(len(keep) * (1 + sp.rate))]
+        dptr = (C.c_void_p * max(len(out), 1))()
+        for i, o in enumerate(out):
+            dptr[i] = o.ctypes.data
+        self._check(self.lib.pqa_deinterlace(self._ctx, C.byref(sp), sptr, sstride, dptr,
+                                             shape[1] * np.dtype(self.dtype).itemsize, len(keep)))
+        del keep
+        return out
+
+    def deinterlace_resident(self, shape, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, dst_ptr: int, dst_row_pitch: int,
+                             dst_frame_pitch: int, n_frames: int, mode: str = "adaptive", first: int = 0, rate: str = "frame"):
+        """The same for n_frames SOURCE planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
+        pqa_deinterlace_device); dst holds n_frames planes, or 2 n_frames at rate "field", and may not be src.  Nothing crosses
+        PCIe; the result can go into submit_resident."""
+        sp = self._deint_spec(shape, mode, first, rate)
+        self._check(self.lib.pqa_deinterlace_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch,
+                                                    dst_ptr or None, dst_row_pitch, dst_frame_pitch, int(n_frames)))
+
     # -- overlay masking ---------------------------------------------------------------------
     def _mask(self, nodes, steps, fill, shape):
         """(node grid kept alive, its pointer, pqa_mask_spec) of a mask over planes of `shape` = (height, width): nodes a 2-D

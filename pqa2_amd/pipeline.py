@@ -16,7 +16,7 @@ import numpy as np
 from . import _native as N
 from . import model as M
 from . import report, shard
-from .readers import (CHROMA_SITINGS, _ColourReader, _ConvertedReader, _CroppedReader, _LevelledReader, _LumaReader,  # noqa: F401
+from .readers import (CHROMA_SITINGS, _ColourReader, _ConvertedReader, _CroppedReader, _DeinterlacedReader, _LevelledReader, _LumaReader,  # noqa: F401
                       _MaskedReader, _RegisteredReader, _ResampledReader, _RgbReader, _ShiftedReader, _TableReader,
                       _WovenReader, _clip_context, _side_context, crop_readers, yuvio_info_444)
 from .yuvio import open_video
@@ -56,7 +56,9 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
                 itp_threshold: float = 1.0, overlay_mask: str | None = None, overlay_boxes=None, overlay_frames: int = 32,
                 overlay_tile: int = 16, overlay_grow: int = 1, overlay_feather: int = 16,
                 overlay_share: float = 0.9, field_align: str | None = None, field_frames: int | None = None,
-                field_penalty_mse: float | None = None) -> ScoreResult | None:
+                field_penalty_mse: float | None = None, field_repair: bool = False, deinterlace: str | None = None,
+                deinterlace_rate: str = "frame", deinterlace_order: str | None = None,
+                deinterlace_side: str = "distorted") -> ScoreResult | None:
     """Returns the ScoreResult on rank 0 (None on other ranks).  `progress(frames_done, frames_total)`
     is called as frames are submitted; `cancelled()` is polled between frames (True -> PqaCancelled).
     `fixed_point`: PQA_FIXED_* mask -- extractors to run in libvmaf's fixed-point arithmetic (include/pqa_vmaf.h).
@@ -269,18 +271,34 @@ def score_files(reference_path: str, distorted_path: str, model: str | None = "v
     tile, grow, feather, frames_sampled, applied}: `regions` as distortion.persistent_regions gives them, `boxes` the masked
     boxes in pixels, `share` the fraction of luma samples the mask touches, `fill` the constants per plane or "reference",
     `applied` false under "report" and when no tile is persistent.  None: nothing is read or changed and the result has no such
-    object."""
+    object.
+
+    `deinterlace`: None, "adaptive" or "intra" -- a clip that really is interlaced (1080i: two moments in time a frame) is
+    deinterlaced on the GPU in exact integers (FeatureEngine.deinterlace, pqa_deinterlace: one field of a frame kept, the other
+    interpolated from the fields before and after it where the picture is still -- "adaptive" -- or from the kept field alone --
+    "intra"), every plane, directly after an RGB clip became Y'CbCr and before any step that works vertically.
+    `deinterlace_side`: "distorted" (a progressive master against an interlaced capture) or "both" (an interlaced clip on either
+    side).  `deinterlace_rate`: "frame" -- a frame per frame, the first field kept -- or "field" -- a frame per field: twice the
+    frames at twice the frame rate (a 50p master against a 25i capture).  `deinterlace_order`: "tff" or "bff", the field that comes
+    first in time; None reads the clip's own Y4M I tag (t / b), and a clip without one is a ValueError.  `input` then carries
+    "deinterlace": {"side", "mode", "rate", "order", "declared": {"reference", "distorted"}, "frames": [from, to]} (the frames of
+    the deinterlaced clip(s) before and after).  None: nothing changes.
+    `field_repair` (with field_align="apply"): when the field structure found is single_field for the whole clip -- one field was
+    dropped and the other line-doubled --, the captured clip goes through deinterlace mode "intra" keeping the parity that both
+    captured parities show, and `fields` carries applied true and repair "intra".  False: single_field is reported only."""
     from .engine import FeatureEngine
     make_side = engine_factory or FeatureEngine
     make = engine_factory or (lambda *aa, **kw: FeatureEngine(*aa, reuse=True, **kw))   # a parked context of this configuration
     raw_kwargs = raw_kwargs or {}
     st = _Clips(open_video(reference_path, **raw_kwargs), open_video(distorted_path, **raw_kwargs), device, make_side)
     _check_formats(chroma_mismatch, chroma_siting, rgb_matrix, rgb_range)
+    _check_deinterlace(deinterlace, deinterlace_rate, deinterlace_order, deinterlace_side)
     _wrap_rgb(st, chroma_siting, rgb_matrix, rgb_range)
+    _deinterlace(st, deinterlace, deinterlace_rate, deinterlace_order, deinterlace_side)   # nothing vertical may touch woven fields
     _match_chroma(st, chroma_mismatch, chroma_siting)
     _match_size(st, resize)
     _align_time(st, align, align_frames, align_penalty_mse)
-    _align_fields(st, field_align, field_frames, field_penalty_mse)
+    _align_fields(st, field_align, field_frames, field_penalty_mse, field_repair)
     _crop_active(st, active_picture, active_frames, active_limit, active_skip)
     _align_shift(st, spatial_align, spatial_frames)
     _register(st, register, register_frames, register_min_px)
@@ -444,13 +462,51 @@ def _wrap_rgb(st: _Clips, siting, matrix, rgb_range) -> None:
         st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False}
 
 
+DEINTERLACE_ORDERS = {"tff": 0, "bff": 1}      # deinterlace_order= -> the parity of the rows that come first in time
+_ORDER_TAGS = {"t": "tff", "b": "bff"}         # the Y4M I tag
+
+
+def _check_deinterlace(mode, rate, order, side) -> None:
+    if mode is not None and mode not in N.DEINT_MODES:
+        raise ValueError(f"deinterlace must be None or one of {sorted(N.DEINT_MODES)}")
+    if rate not in N.DEINT_RATES:
+        raise ValueError(f"deinterlace_rate must be one of {sorted(N.DEINT_RATES)}")
+    if order is not None and order not in DEINTERLACE_ORDERS:
+        raise ValueError(f"deinterlace_order must be None or one of {sorted(DEINTERLACE_ORDERS)}")
+    if side not in ("distorted", "both"):
+        raise ValueError('deinterlace_side must be "distorted" or "both"')
+
+
+def _deinterlace(st: _Clips, mode, rate, order, side) -> None:
+    """deinterlace=: the distorted clip, or both, through the GPU deinterlacer; `input` reports it"""
+    if mode is None:
+        return
+    ri, di = st.ri, st.di
+    sides = ("reference", "distorted") if side == "both" else ("distorted",)
+    orders = {}
+    for name, info in (("reference", ri), ("distorted", di)):
+        if name in sides:
+            orders[name] = order or _ORDER_TAGS.get(info.interlace)
+            if orders[name] is None:
+                raise ValueError(f"the {name} clip's header names no field order (I tag {info.interlace!r}): deinterlace_order must say tff or bff")
+    before = len(st.dis)
+    if side == "both":
+        st.ref = st.own(_DeinterlacedReader(st.ref, mode, DEINTERLACE_ORDERS[orders["reference"]], rate, st.device, st.make))
+    st.dis = st.own(_DeinterlacedReader(st.dis, mode, DEINTERLACE_ORDERS[orders["distorted"]], rate, st.device, st.make))
+    st.input = dict(st.input or {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": None, "packed_upload": False})
+    st.input["deinterlace"] = {"side": side, "mode": mode, "rate": rate, "order": orders["distorted"],
+                               "declared": {"reference": ri.interlace, "distorted": di.interlace},
+                               "frames": [before, len(st.dis)]}
+
+
 def _match_chroma(st: _Clips, mode: str, siting) -> None:
     """chroma_mismatch: "luma" scores both clips as luma-only clips, "convert" takes the distorted clip to the reference's
     layout, siting and depth"""
     ri, di = st.ri, st.di
+    kept = {k: v for k, v in (st.input or {}).items() if k == "deinterlace"}      # what the step before reported
     if (mode == "luma" and ri.bit_depth == di.bit_depth
             and (ri.hshift, ri.vshift, ri.mono) != (di.hshift, di.vshift, di.mono)):
-        st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "y", "packed_upload": False}
+        st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "y", "packed_upload": False, **kept}
         st.ref, st.dis = _LumaReader(st.ref), _LumaReader(st.dis)
     if (mode == "convert" and ri.mono == di.mono and not ri.mono
             and ri.bit_depth in N.CONVERT_BIT_DEPTHS and di.bit_depth in N.CONVERT_BIT_DEPTHS
@@ -459,7 +515,7 @@ def _match_chroma(st: _Clips, mode: str, siting) -> None:
         st.input = {"reference": ri.pix_fmt, "distorted": di.pix_fmt, "planes_scored": "yuv", "packed_upload": False,
                     "conversion": {"side": "distorted", "from": di.pix_fmt, "to": converter.info.pix_fmt,
                                    "bit_depth": [di.bit_depth, ri.bit_depth],
-                                   "siting": {"from": list(converter.src_siting), "to": list(converter.dst_siting)}}}
+                                   "siting": {"from": list(converter.src_siting), "to": list(converter.dst_siting)}}, **kept}
 
 
 def _match_size(st: _Clips, resize) -> None:
@@ -487,7 +543,9 @@ def _align_time(st: _Clips, align, align_frames, penalty_mse) -> None:
         st.ref, st.dis = _ShiftedReader(st.ref, max(0, -k)), _ShiftedReader(st.dis, max(0, k))
 
 
-def _align_fields(st: _Clips, mode, frames, penalty_mse) -> None:
+def _align_fields(st: _Clips, mode, frames, penalty_mse, repair=False) -> None:
+    if repair and mode != "apply":
+        raise ValueError('field_repair needs field_align="apply"')
     if mode is not None:
         if mode not in ("report", "apply"):
             raise ValueError('field_align must be None, "report" or "apply"')
@@ -501,6 +559,11 @@ def _align_fields(st: _Clips, mode, frames, penalty_mse) -> None:
         st.alignment = dict(st.alignment or {}, fields=fields)
         if fields["applied"]:
             st.ref, st.dis = _ShiftedReader(st.ref, plan["u_lo"]), _WovenReader(st.dis, plan)
+        elif repair and fields["segments"] and all(g["kind"] == "single_field" and g["state"][0] == fields["state"][0]
+                                                      and g["state"][1] == g["state"][3] == 0 for g in fields["segments"]):
+            # one field was dropped and the other line-doubled: keep the parity both captured parities show, interpolate the other
+            st.dis = st.own(_DeinterlacedReader(st.dis, "intra", fields["state"][0], "frame", st.device, st.make))
+            fields.update(applied=True, reason=None, repair="intra")
 
 
 def _crop_window(st: _Clips, crop, dis_rd=None) -> None:

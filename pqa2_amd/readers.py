@@ -1,6 +1,6 @@
 """The reader wrappers of pipeline.score_files: each wraps a reader (yuvio.open_video's, or another wrapper) once a step has
 changed a clip and offers `info`, len() and frame(i).  Five are plain host views (_LumaReader, _ShiftedReader, _CroppedReader,
-_WovenReader, _LevelledReader); seven put the frames through a GPU transform on a small context of their own, eight at a time (_RunReader)."""
+_WovenReader, _LevelledReader); eight put the frames through a GPU transform on a small context of their own, eight at a time (_RunReader)."""
 from __future__ import annotations
 
 import dataclasses
@@ -190,6 +190,39 @@ class _TableReader(_RunReader):
                 for f, mapped in zip(frames, self._eng.table_apply([f[p] for f in frames], table, p)):
                     f[p] = mapped
         return frames
+
+
+class _DeinterlacedReader(_RunReader):
+    """An interlaced clip as a progressive one: what score_files reads under deinterlace=.  Every plane of a frame goes through
+    the same FeatureEngine.deinterlace call (one call per plane kind and run): in interlaced 4:2:0 chroma row c belongs to
+    field c & 1, as _WovenReader assumes.  rate "field": two frames a source frame, `info` carries the doubled fps_num.  A run
+    fetches its source frames plus one neighbour each side where the clip has one and drops the neighbours' outputs, so a
+    frame is the same whatever run it is fetched in and equals the whole-clip call.  The source frames of the last run are
+    kept, so a clip read front to back asks the wrapped reader for every frame once and in order: a wrapped reader that converts
+    in runs of its own (_RgbReader) converts each of its runs once.  Every plane needs two rows."""
+
+    def __init__(self, reader, mode: str, first: int, rate: str, device, make):
+        src = reader.info
+        if min(h for h, _ in src.plane_shapes) < 2:
+            raise ValueError(f"deinterlace needs planes of at least two rows: a {src.pix_fmt} clip of height {src.height} has one of "
+                             f"{min(h for h, _ in src.plane_shapes)}")
+        self._mode, self._order, self._rate = mode, int(first), rate
+        self._per = 2 if rate == "field" else 1
+        self._kept = {}                                                # source frames of the last run, by number
+        info = dataclasses.replace(src, fps_num=src.fps_num * self._per, interlace="p", packed=None)
+        super().__init__(reader, info, _clip_context(make, device, src, 1 if src.mono else 3))
+
+    def __len__(self):
+        return len(self._rd) * self._per
+
+    def _fetch(self, span):
+        n, per = len(self._rd), self._per
+        s0, s1 = span[0] // per, span[-1] // per + 1                  # the source frames of the run
+        lo, hi = max(s0 - 1, 0), min(s1 + 1, n)                        # and a neighbour each side
+        frames = [self._kept[j] if j in self._kept else self._rd.frame(j) for j in range(lo, hi)]
+        self._kept = dict(zip(range(lo, hi), frames))
+        planes = [self._eng.deinterlace([f[p] for f in frames], self._mode, self._order, self._rate) for p in range(len(frames[0]))]
+        return [[pl[k - lo * per] for pl in planes] for k in span]
 
 
 class _ColourReader(_RunReader):

@@ -139,6 +139,20 @@ def main(argv=None) -> int:
     ap.add_argument("--field-penalty-mse", type=float, default=None, metavar="X",
                     help="with --field-align / --field-correct: what a change of field structure costs, as an MSE of one frame "
                          "(default: that of the temporal alignment)")
+    ap.add_argument("--field-repair", action="store_true",
+                    help="with --field-correct: when one field of the capture was dropped and the other line-doubled (single_field "
+                         "for the whole clip), interpolate the lost field from the kept one on the GPU before scoring")
+    ap.add_argument("--deinterlace", default=None, metavar="MODE", choices=["adaptive", "intra"],
+                    help="deinterlace the captured clip on the GPU before scoring, in exact integers: adaptive (the lost field from "
+                         "the fields before and after it where the picture is still) or intra (from the kept field alone); the "
+                         "JSON's input object gets a deinterlace entry")
+    ap.add_argument("--deinterlace-rate", default="frame", choices=["frame", "field"],
+                    help="with --deinterlace: a frame per frame, or a frame per field (twice the frames at twice the rate: a 50p "
+                         "master against a 25i capture; default frame)")
+    ap.add_argument("--field-order", default=None, choices=["tff", "bff"],
+                    help="with --deinterlace: the field that comes first in time (default: the Y4M header's I tag)")
+    ap.add_argument("--deinterlace-side", default="distorted", choices=["distorted", "both"],
+                    help="with --deinterlace: the captured clip only, or both clips (default distorted)")
     ap.add_argument("--distortion-map", type=int, default=0, metavar="T", choices=[0, 8, 16, 32, 64],
                     help="measure WHERE the clips differ: the second-order sums of every T x T tile (8, 16, 32 or 64) of every "
                          "scored frame pair, in a second pass over both clips; the JSON gets a top-level distortion object "
@@ -311,6 +325,9 @@ def main(argv=None) -> int:
                              if (a.active_picture or a.active_crop) else {}),
                           **({"field_align": "apply" if a.field_correct else "report", "field_frames": a.field_frames,
                               "field_penalty_mse": a.field_penalty_mse} if (a.field_align or a.field_correct) else {}),
+                          **({"field_repair": True} if a.field_repair else {}),
+                          **({"deinterlace": a.deinterlace, "deinterlace_rate": a.deinterlace_rate, "deinterlace_order": a.field_order,
+                              "deinterlace_side": a.deinterlace_side} if a.deinterlace else {}),
                           **({"distortion_map": a.distortion_map, "distortion_planes": a.distortion_planes,
                               "distortion_dir": a.distortion_dir, "distortion_factor": a.distortion_factor,
                               "distortion_min_mse": a.distortion_min_mse} if a.distortion_map else {}),

@@ -172,6 +172,9 @@ class VMAFAnalyzer(QObject):
         self.active_crop_enabled = False      # ... and crop both to the common rectangle (implies the measurement; score_files(active_picture=))
         self.field_align_enabled = False      # field alignment before scoring: measure the field structure of the capture
         self.field_correct_enabled = False    # ... and re-weave a field shift or swap (implies the measurement; score_files(field_align=))
+        self.deinterlace_mode = None          # deinterlace the captured clip before scoring: None, "adaptive" or "intra" (score_files(deinterlace=))
+        self.deinterlace_rate = None          # ... "frame" or "field"; None: frame
+        self.field_order = None               # ... "tff" or "bff"; None: the clip's own Y4M I tag
         self.distortion_map_enabled = False   # distortion map: where inside the frame the clips differ (a second pass over both
         self.distortion_tile = 32             # clips; score_files(distortion_map=)); its tile size: 8, 16, 32 or 64
         self.spectrum_enabled = False         # distortion spectrum: what kind of difference the clips have (the same second
@@ -262,6 +265,9 @@ class VMAFAnalyzer(QObject):
                 self.field_align_enabled = bool(s["field_align_enabled"])
             if "field_correct_enabled" in s:
                 self.field_correct_enabled = bool(s["field_correct_enabled"])
+            for key in ("deinterlace_mode", "deinterlace_rate", "field_order"):
+                if key in s:
+                    setattr(self, key, s[key] or None)
             if "distortion_map_enabled" in s:
                 self.distortion_map_enabled = bool(s["distortion_map_enabled"])
             if "distortion_tile" in s:
@@ -545,6 +551,8 @@ class VMAFAnalyzer(QObject):
                    if (self.active_picture_enabled or self.active_crop_enabled) else {}),
                 **({"field_align": "apply" if self.field_correct_enabled else "report"}
                    if (self.field_align_enabled or self.field_correct_enabled) else {}),
+                **({"deinterlace": self.deinterlace_mode, "deinterlace_rate": self.deinterlace_rate or "frame",
+                    "deinterlace_order": self.field_order} if self.deinterlace_mode else {}),
                 **({"distortion_map": int(self.distortion_tile)} if self.distortion_map_enabled else {}),
                 **({"spectrum": int(self.spectrum_levels)} if self.spectrum_enabled else {}),
                 **({"temporal": int(self.temporal_tile)} if self.temporal_enabled else {}),
@@ -611,6 +619,10 @@ class VMAFAnalyzer(QObject):
             cmd += ["--field-correct"]
         elif self.field_align_enabled:
             cmd += ["--field-align"]
+        if self.deinterlace_mode:
+            cmd += ["--deinterlace", self.deinterlace_mode, "--deinterlace-rate", self.deinterlace_rate or "frame"]
+            if self.field_order:
+                cmd += ["--field-order", self.field_order]
         if self.distortion_map_enabled:
             cmd += ["--distortion-map", str(int(self.distortion_tile))]
         if self.spectrum_enabled:
