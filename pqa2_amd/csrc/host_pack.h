@@ -13,8 +13,17 @@
 
 #include <unistd.h>
 
+#include "host_stage.h"
+
 namespace pqa {
 namespace host {
+
+// A run of n frames goes down in EQUAL launches of at most B frames (300 frames at batch 32: ten of 30, not nine of 32 and one
+// of 12 -- a short launch pays the same ramp and tail for fewer waves): the frames per launch; 0 for an empty run.
+inline int launch_size(int n, int B) {
+  const int launches = (n + B - 1) / B;
+  return launches ? (n + launches - 1) / launches : 0;
+}
 
 // pqa_submit packs the caller's planes into pinned staging.  One core's memcpy (~10 GB/s) is far below PCIe, so the
 // rows of a frame pair are split into ~1 MiB tasks that a few persistent helper threads and the caller drain together.
@@ -28,6 +37,37 @@ struct PackTask {
   int64_t file_off = 0;
   int frame = 0;           // which frame of a run the task belongs to (PackPool::run_frames)
 };
+
+// Plane p of the first frame of a caller's clip: rows `stride` bytes apart in memory from `ptr` on (fd < 0), or in a file from
+// byte `off` on.
+struct PlaneSrc {
+  const uint8_t* ptr;
+  int64_t stride;
+  int fd;
+  int64_t off;
+};
+
+// THE task builder: the copy of one frame of one side into its staging slot (layout L, at dst), appended to `tasks` in pieces of
+// about task_bytes.  The frame's planes lie src_frame * frame_step bytes behind src[p]; it is frame `run_frame` of the run the
+// tasks belong to.  Only the row_bytes of a row that hold samples are read.
+inline void pack_frame_tasks(std::vector<PackTask>& tasks, const ClipLayout& L, uint8_t* dst, const PlaneSrc src[3], int64_t frame_step,
+                             int64_t src_frame, int run_frame, size_t task_bytes) {
+  for (int p = 0; p < L.n_planes; ++p) {
+    const PlaneLayout& P = L.plane[p];
+    const PlaneSrc& s = src[p];
+    int rows_per = (int)(task_bytes / (P.row_bytes ? P.row_bytes : 1));
+    if (rows_per < 1) rows_per = 1;
+    for (int y = 0; y < P.h; y += rows_per) {
+      const int64_t at = src_frame * frame_step + (int64_t)y * s.stride;
+      PackTask t{dst + L.off[p] + (int64_t)y * P.pitch, s.fd < 0 ? s.ptr + at : nullptr, P.pitch, s.stride, P.row_bytes,
+                 P.h - y < rows_per ? P.h - y : rows_per};
+      t.fd = s.fd;
+      t.file_off = s.off + at;
+      t.frame = run_frame;
+      tasks.push_back(t);
+    }
+  }
+}
 
 // one task, by whoever takes it.  Returns false on a short read / I/O error of a file source.
 inline bool run_pack_task(const PackTask& t) {

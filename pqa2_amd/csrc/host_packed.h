@@ -70,23 +70,15 @@ inline ClipLayout converted_layout(int w, int h, int cw, int ch, int es, int n_p
   return clip_layout(n_planes, rb, rows, 16, 16);
 }
 
-// pack_clip's copy as tasks of about task_bytes for the pack pool (host_pack.h), appended to `tasks`: frame f0 + f of the clip is
-// task.frame = f of the run.  Large frames only: one core's memcpy, not PCIe, would bound the path otherwise.
+// pack_clip's copy as tasks of about task_bytes for the pack pool, appended to `tasks`: the builder of host_pack.h
+// (pack_frame_tasks) over a caller's frame list; frame f0 + f of the clip is task.frame = f of the run.
 inline void pack_clip_tasks(std::vector<PackTask>& tasks, uint8_t* pin, const ClipLayout& L, const void* const* frames,
                             const int64_t strides[3], int f0, int n, size_t task_bytes) {
-  for (int f = 0; f < n; ++f)
-    for (int p = 0; p < L.n_planes; ++p) {
-      const PlaneLayout& P = L.plane[p];
-      int rows_per = (int)(task_bytes / (P.row_bytes ? P.row_bytes : 1));
-      if (rows_per < 1) rows_per = 1;
-      const uint8_t* src = (const uint8_t*)frames[(size_t)(f0 + f) * L.n_planes + p];
-      for (int y = 0; y < P.h; y += rows_per) {
-        PackTask t{pin + (size_t)f * L.frame_bytes + L.off[p] + (size_t)y * P.pitch, src + (int64_t)y * strides[p], P.pitch, strides[p],
-                   P.row_bytes, P.h - y < rows_per ? P.h - y : rows_per};
-        t.frame = f;
-        tasks.push_back(t);
-      }
-    }
+  for (int f = 0; f < n; ++f) {
+    PlaneSrc src[3] = {};
+    for (int p = 0; p < L.n_planes; ++p) src[p] = PlaneSrc{(const uint8_t*)frames[(size_t)(f0 + f) * L.n_planes + p], strides[p], -1, 0};
+    pack_frame_tasks(tasks, L, pin + (size_t)f * L.frame_bytes, src, 0, 0, f, task_bytes);
+  }
 }
 
 }  // namespace host

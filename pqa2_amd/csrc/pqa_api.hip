@@ -15,6 +15,7 @@
 using namespace pqa;
 using pqa::host::PackPool;
 using pqa::host::PackTask;
+using pqa::host::PlaneSrc;
 using pqa::host::run_pack_task;
 
 static thread_local std::string g_create_error;   // pqa_last_error(NULL): what pqa_create and the pqa_debug_* entries report
@@ -876,23 +877,95 @@ int process_batch(pqa_ctx* c, int64_t first, int n, const pqa_device_clip* ref, 
   return keep_histories(c, b);
 }
 
-// One frame pair as the library lays it out itself (pinned staging, its device copy, unpacked decoder surfaces): ref
-// planes then dis planes, rows padded to 64 bytes, planes to 256.
-void slot_layout(pqa_ctx* c) {
-  size_t off = 0;
-  for (int side = 0; side < 2; ++side)
-    for (int p = 0; p < c->n_planes; ++p) {
-      c->slot_row_pitch[p] = round_up((int64_t)c->pw[p] * c->esize, 64);
-      c->plane_off[side][p] = off;
-      off += round_up(c->slot_row_pitch[p] * c->ph[p], 256);
+// One side of a frame pair as the library lays it out itself: pqa_ctx::slot.
+host::ClipLayout slot_layout(const pqa_ctx* c) {
+  size_t rb[3] = {0, 0, 0};
+  for (int p = 0; p < c->n_planes; ++p) rb[p] = (size_t)c->pw[p] * c->esize;
+  return host::clip_layout(c->n_planes, rb, c->ph, 64, 256);
+}
+
+// The frames of layout L that lie frame_pitch bytes apart from `base` on, as the kernels take a clip.
+pqa_device_clip clip_at(const void* base, const host::ClipLayout& L, int64_t frame_pitch) {
+  pqa_device_clip d{};
+  for (int p = 0; p < L.n_planes; ++p) {
+    d.plane[p] = (const uint8_t*)base + L.off[p];
+    d.row_pitch[p] = L.plane[p].pitch;
+    d.frame_pitch[p] = frame_pitch;
+  }
+  return d;
+}
+// side sd of the slots at `base` (a staging half's device copy, surf_dev)
+pqa_device_clip slot_clip(const pqa_ctx* c, const uint8_t* base, int sd) {
+  return clip_at(base + sd * c->slot.frame_bytes, c->slot, (int64_t)c->slot_bytes());
+}
+
+// ---- the staging halves (pqa::Half) ------------------------------------------------------------
+// The copy stream and a pair's events, made by whichever host path comes first.
+int ensure_copy_path(pqa_ctx* c, Half (&pair)[2]) {
+  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  for (Half& H : pair) {
+    if (!H.copied) HIPCHK(c, hipEventCreateWithFlags(&H.copied, hipEventDisableTiming));
+    if (!H.computed) HIPCHK(c, hipEventCreateWithFlags(&H.computed, hipEventDisableTiming));
+  }
+  return PQA_OK;
+}
+
+hipError_t half_alloc(Half& H, size_t bytes) {
+  hipError_t e = hipHostMalloc((void**)&H.pinned, bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&H.dev, bytes);
+  if (e == hipSuccess) H.cap = bytes;
+  return e;
+}
+
+void half_free(Half& H) {   // nothing reads it any more; the right device is current
+  if (H.pinned) hipHostFree(H.pinned);
+  if (H.dev) hipFree(H.dev);
+  H.pinned = H.dev = nullptr;
+  H.cap = 0;
+}
+
+// Before the host packs `bytes` into H: the upload that last read the pinned buffer has passed; a half too small is replaced
+// by a larger one once the kernels that last read its device copy are through; the next upload waits for those kernels.
+int half_claim(pqa_ctx* c, Half& H, size_t bytes) {
+  if (H.copied_pending) {
+    HIPCHK(c, hipEventSynchronize(H.copied));
+    H.copied_pending = false;
+  }
+  if (H.cap < bytes) {
+    if (H.computed_pending) {
+      HIPCHK(c, hipEventSynchronize(H.computed));
+      H.computed_pending = false;
     }
-  c->slot_bytes = off;
+    half_free(H);
+    HIPCHK(c, half_alloc(H, bytes));
+  }
+  if (H.computed_pending) {
+    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, H.computed, 0));
+    H.computed_pending = false;
+  }
+  return PQA_OK;
+}
+
+std::array<Half*, 4> all_halves(pqa_ctx* c) { return {{&c->half[0], &c->half[1], &c->chunk_half[0], &c->chunk_half[1]}}; }
+
+// H's uploads are queued: the kernels wait for them.
+int half_sent(pqa_ctx* c, Half& H) {
+  HIPCHK(c, hipEventRecord(H.copied, c->copy_stream));
+  H.copied_pending = true;
+  HIPCHK(c, hipStreamWaitEvent(c->stream, H.copied, 0));
+  return PQA_OK;
+}
+
+// The kernels that read H's device copy are queued.
+int half_launched(pqa_ctx* c, Half& H) {
+  HIPCHK(c, hipEventRecord(H.computed, c->stream));
+  H.computed_pending = true;
+  return PQA_OK;
 }
 
 int ensure_staging(pqa_ctx* c) {
   if (c->staging_ready) return PQA_OK;
-  slot_layout(c);
-  const size_t half_bytes = c->slot_bytes * c->HB;
+  const size_t half_bytes = c->slot_bytes() * c->HB;
   bool reused = false;
   if (staging_cache_enabled()) {
     std::lock_guard<std::mutex> g(g_staging_mu);
@@ -900,6 +973,7 @@ int ensure_staging(pqa_ctx* c) {
       for (int i = 0; i < 2; ++i) {
         c->half[i].pinned = g_staging.pinned[i];
         c->half[i].dev = g_staging.dev[i];
+        c->half[i].cap = half_bytes;
         g_staging.pinned[i] = g_staging.dev[i] = nullptr;
       }
       g_staging.bytes = 0;
@@ -907,22 +981,14 @@ int ensure_staging(pqa_ctx* c) {
       reused = true;
     }
   }
-  for (int i = 0; i < 2; ++i) {
-    Half& H = c->half[i];
-    HIPCHK(c, hipEventCreateWithFlags(&H.copied, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&H.computed, hipEventDisableTiming));
-  }
-  HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  PQACHK(ensure_copy_path(c, c->half));
   if (!reused) {
     // Pinning costs ~40 us per MiB (a 2160p 4:2:0 half of 8 frame pairs: 8 ms): only the first half is needed before
     // the first frame can be packed; the second is pinned by a helper thread while the first one fills.
-    HIPCHK(c, hipHostMalloc((void**)&c->half[0].pinned, half_bytes, hipHostMallocDefault));
-    HIPCHK(c, hipMalloc((void**)&c->half[0].dev, half_bytes));
+    HIPCHK(c, half_alloc(c->half[0], half_bytes));
     const auto pin_second = [c, half_bytes] {
-      hipError_t e = hipSetDevice(c->device);
-      if (e == hipSuccess) e = hipHostMalloc((void**)&c->half[1].pinned, half_bytes, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipMalloc((void**)&c->half[1].dev, half_bytes);
-      c->pin_err = e;
+      const hipError_t e = hipSetDevice(c->device);
+      c->pin_err = e == hipSuccess ? half_alloc(c->half[1], half_bytes) : e;
     };
     try {
       c->pin_thread = std::thread(pin_second);
@@ -948,35 +1014,16 @@ int staging_half_ready(pqa_ctx* c, int i) {
 int flush_pending(pqa_ctx* c) {
   if (c->pending == 0) return PQA_OK;
   Half& H = c->half[c->cur_half];
-  HIPCHK(c, hipEventRecord(H.copied, c->copy_stream));
-  H.copied_pending = true;
-  HIPCHK(c, hipStreamWaitEvent(c->stream, H.copied, 0));
-  pqa_device_clip r{}, d{};
-  for (int p = 0; p < c->n_planes; ++p) {
-    r.plane[p] = H.dev + c->plane_off[0][p];
-    d.plane[p] = H.dev + c->plane_off[1][p];
-    r.row_pitch[p] = d.row_pitch[p] = c->slot_row_pitch[p];
-    r.frame_pitch[p] = d.frame_pitch[p] = (int64_t)c->slot_bytes;
-  }
+  PQACHK(half_sent(c, H));
+  const pqa_device_clip r = slot_clip(c, H.dev, 0), d = slot_clip(c, H.dev, 1);
   const int n = c->pending;
-  int rc = check_slots_free(c, c->pending_first, n);
-  if (rc != PQA_OK) return rc;   // PQA_ESTATE: nothing launched, the packed frames stay pending (collect, then flush again)
+  PQACHK(check_slots_free(c, c->pending_first, n));   // PQA_ESTATE: nothing launched, the packed frames stay pending (collect, then flush again)
   c->pending = 0;
-  rc = process_batch(c, c->pending_first, n, &r, &d, nullptr, 0);
-  if (rc != PQA_OK) return rc;
-  HIPCHK(c, hipEventRecord(H.computed, c->stream));
-  H.computed_pending = true;
+  PQACHK(process_batch(c, c->pending_first, n, &r, &d, nullptr, 0));
+  PQACHK(half_launched(c, H));
   c->cur_half ^= 1;
   return PQA_OK;
 }
-
-// One frame pair from memory planes or from files into the pinned staging slot, its upload queued on the copy stream.
-struct PlaneSrc {
-  const uint8_t* ptr;   // memory source (fd < 0): rows `stride` bytes apart
-  int64_t stride;
-  int fd;               // file source: rows `stride` bytes apart from `off`
-  int64_t off;
-};
 
 // The helpers that pack large frames, made on first use (a context of small frames never starts a thread).
 void ensure_pack_pool(pqa_ctx* c) {
@@ -1001,6 +1048,7 @@ void ensure_pack_pool(pqa_ctx* c) {
 int submit_run(pqa_ctx* c, int64_t first_index, int n_frames, const PlaneSrc (&src)[2][3], const int64_t (&frame_step)[2]) {
   if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
   HIPCHK(c, hipSetDevice(c->device));
+  const size_t slot_bytes = c->slot_bytes();
   int rc = PQA_OK;
   int done = 0;
   while (done < n_frames) {
@@ -1024,16 +1072,9 @@ int submit_run(pqa_ctx* c, int64_t first_index, int n_frames, const PlaneSrc (&s
     rc = staging_half_ready(c, c->cur_half);   // the second half is pinned by a helper thread while the first one fills
     if (rc != PQA_OK) return rc;
     Half& H = c->half[c->cur_half];
-    if (c->pending == 0) {
+    if (c->pending == 0) {   // the first frames into this half
       c->pending_first = frame_index;
-      if (H.copied_pending) {  // pinned half still feeding an earlier upload?
-        HIPCHK(c, hipEventSynchronize(H.copied));
-        H.copied_pending = false;
-      }
-      if (H.computed_pending) {  // device half still read by an earlier batch?
-        HIPCHK(c, hipStreamWaitEvent(c->copy_stream, H.computed, 0));
-        H.computed_pending = false;
-      }
+      PQACHK(half_claim(c, H, H.cap));
     }
     const int slot0 = c->pending;
     // Pack into the pinned slots in ~1 MiB tasks (a 2160p 4:2:0 pair is 25 MB: one core's memcpy / pread, not PCIe, would
@@ -1041,35 +1082,19 @@ int submit_run(pqa_ctx* c, int64_t first_index, int n_frames, const PlaneSrc (&s
     bool ok = true;
     hipError_t copy_err = hipSuccess;
     const auto upload = [&](int k) {   // frame k of the chunk is complete in its pinned slot: queue its copy
-      const size_t off = (size_t)(slot0 + k) * c->slot_bytes;
-      copy_err = hipMemcpyAsync(H.dev + off, H.pinned + off, c->slot_bytes, hipMemcpyHostToDevice, c->copy_stream);
+      const size_t off = (size_t)(slot0 + k) * slot_bytes;
+      copy_err = hipMemcpyAsync(H.dev + off, H.pinned + off, slot_bytes, hipMemcpyHostToDevice, c->copy_stream);
       return copy_err == hipSuccess;
     };
     try {  // no exception may cross the C ABI: if the task list or the helpers cannot be made, that is PQA_ENOMEM below
       c->pack_tasks.clear();
       static const unsigned task_bytes = [] { const char* e = getenv("PQA_PACK_TASK_KB"); const int kb = e ? atoi(e) : 0; return (unsigned)(kb > 0 ? kb : 1024) << 10; }();
-      for (int k = 0; k < m; ++k) {
-        uint8_t* slot = H.pinned + (size_t)(slot0 + k) * c->slot_bytes;
+      for (int k = 0; k < m; ++k)
         for (int side = 0; side < 2; ++side)
-          for (int p = 0; p < c->n_planes; ++p) {
-            const PlaneSrc& ps = src[side][p];
-            const int64_t step = (int64_t)(done + k) * frame_step[side];
-            const size_t row_bytes = (size_t)c->pw[p] * c->esize;
-            int rows_per = (int)(task_bytes / (row_bytes ? row_bytes : 1));
-            if (rows_per < 1) rows_per = 1;
-            for (int y = 0; y < c->ph[p]; y += rows_per) {
-              const int rows = c->ph[p] - y < rows_per ? c->ph[p] - y : rows_per;
-              PackTask t{slot + c->plane_off[side][p] + (int64_t)y * c->slot_row_pitch[p],
-                         ps.fd < 0 ? ps.ptr + step + (int64_t)y * ps.stride : nullptr, c->slot_row_pitch[p], ps.stride, row_bytes, rows};
-              t.fd = ps.fd;
-              t.file_off = ps.off + step + (int64_t)y * ps.stride;
-              t.frame = k;
-              c->pack_tasks.push_back(t);
-            }
-          }
-      }
-      if (c->slot_bytes >= (4u << 20)) ensure_pack_pool(c);
-      if (c->pack_pool && c->slot_bytes >= (4u << 20)) {
+          host::pack_frame_tasks(c->pack_tasks, c->slot, H.pinned + (size_t)(slot0 + k) * slot_bytes + side * c->slot.frame_bytes,
+                                 src[side], frame_step[side], done + k, k, task_bytes);
+      if (slot_bytes >= (4u << 20)) ensure_pack_pool(c);
+      if (c->pack_pool && slot_bytes >= (4u << 20)) {
         ok = c->pack_pool->run_frames(c->pack_tasks.data(), (int)c->pack_tasks.size(), m, upload);
       } else {
         int k_done = 0;
@@ -1212,6 +1237,68 @@ int create_streams(pqa_ctx* c) {
   return PQA_OK;
 }
 
+// ---- what the submit and history entries share ------------------------------------------------
+// The rules of a run of n_frames that need no device call: a cancelled context takes none (pqa_submit_fd_run: submit_run says so
+// itself, after this), and the records of one call must not overwrite each other.
+int run_admit(pqa_ctx* c, int n_frames, bool check_cancel = true) {
+  if (check_cancel && c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+  if (n_frames > c->capacity)
+    return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)",
+                n_frames, c->capacity);
+  return PQA_OK;
+}
+
+// ... and what follows an entry's own argument rules: the pending host frames go first, and the slots of the WHOLE run must
+// be free before anything is copied, unpacked or launched.
+int run_begin(pqa_ctx* c, int64_t first_index, int n_frames) {
+  HIPCHK(c, hipSetDevice(c->device));
+  PQACHK(flush_pending(c));
+  return check_slots_free(c, first_index, n_frames);
+}
+
+// What a launch of a run scores: the two clips and the reference luma in front of them (null: none, or what the chains hold).
+struct LaunchInput {
+  pqa_device_clip ref{}, dis{};
+  const void* prev = nullptr;
+  int64_t prev_pitch = 0;   // bytes
+};
+
+// n_frames device-resident frames from first_index on in equal launches (host::launch_size; records do not depend on how a
+// run is cut): input(done, n, &in) fills in frames done ... done + n - 1 of the run, queueing whatever brings them there.
+template <class Input>
+int launch_run(pqa_ctx* c, int64_t first_index, int n_frames, Input input) {
+  const int per = host::launch_size(n_frames, c->B);
+  for (int done = 0; done < n_frames;) {
+    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
+    const int n = n_frames - done < per ? n_frames - done : per;
+    LaunchInput in;
+    PQACHK(input(done, n, &in));
+    PQACHK(process_batch(c, first_index + done, n, &in.ref, &in.dis, in.prev, in.prev_pitch));
+    done += n;
+  }
+  return PQA_OK;
+}
+
+pqa_device_clip clip_from(const pqa_device_clip& clip, int n_planes, int64_t f) {   // the clip from frame f on
+  pqa_device_clip d = clip;
+  for (int p = 0; p < n_planes; ++p) d.plane[p] = (const uint8_t*)clip.plane[p] + f * clip.frame_pitch[p];
+  return d;
+}
+
+// What the history-arming entries share: the pending host frames go first; then `restart` when there is nothing to arm (a chain
+// start), else `arm` on an idle stream.
+template <class Restart, class Arm>
+int arm_histories(pqa_ctx* c, bool have, Restart restart, Arm arm) {
+  HIPCHK(c, hipSetDevice(c->device));
+  PQACHK(flush_pending(c));
+  if (!have) {
+    restart();
+    return PQA_OK;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return arm();
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1279,6 +1366,7 @@ int pqa_create(const pqa_config* cfg, pqa_ctx** out) {
     c->pw[p] = (int)((cfg->width + (1u << cfg->chroma_hshift) - 1) >> cfg->chroma_hshift);
     c->ph[p] = (int)((cfg->height + (1u << cfg->chroma_vshift) - 1) >> cfg->chroma_vshift);
   }
+  c->slot = slot_layout(c);
   c->vif_fixed = (cfg->features & PQA_FEAT_VIF) && (cfg->fixed_point & PQA_FIXED_VIF);
   c->motion_fixed = (cfg->features & PQA_FEAT_MOTION) && (cfg->fixed_point & PQA_FIXED_MOTION);
   c->adm_fixed = (cfg->features & PQA_FEAT_ADM) && (cfg->fixed_point & PQA_FIXED_ADM);
@@ -1310,46 +1398,30 @@ void pqa_destroy(pqa_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
-  if (c->pk_stream) hipStreamSynchronize(c->pk_stream);
   for (int i = 0; i < 2; ++i) if (c->aux[i]) hipStreamSynchronize(c->aux[i]);
   prof_drain(c);
   for (void* p : c->allocs) hipFree(p);
-  {  // park the staging buffers for the next context (everything using them has been synchronised above)
-    StagingSet mine;
-    mine.device = c->device;
-    mine.bytes = c->slot_bytes * (size_t)c->HB;
-    bool complete = c->staging_ready;
+  // park the fixed halves for the next context (everything using them has been synchronised above) ...
+  if (c->staging_ready && staging_cache_enabled() && c->half[0].pinned && c->half[0].dev && c->half[1].pinned && c->half[1].dev) {
+    std::lock_guard<std::mutex> g(g_staging_mu);
+    if (g_staging.bytes) {           // one set per process: the older one goes
+      if (g_staging.device != c->device) hipSetDevice(g_staging.device);
+      staging_release(g_staging);
+      hipSetDevice(c->device);
+    }
+    g_staging.device = c->device;
+    g_staging.bytes = c->slot_bytes() * (size_t)c->HB;
     for (int i = 0; i < 2; ++i) {
-      mine.pinned[i] = c->half[i].pinned;
-      mine.dev[i] = c->half[i].dev;
-      complete = complete && mine.pinned[i] && mine.dev[i];
-    }
-    if (complete && staging_cache_enabled()) {
-      std::lock_guard<std::mutex> g(g_staging_mu);
-      if (g_staging.bytes) {           // one set per process: the older one goes
-        if (g_staging.device != c->device) hipSetDevice(g_staging.device);
-        staging_release(g_staging);
-        hipSetDevice(c->device);
-      }
-      g_staging = mine;
-    } else {
-      staging_release(mine);
+      g_staging.pinned[i] = c->half[i].pinned;
+      g_staging.dev[i] = c->half[i].dev;
+      c->half[i].pinned = c->half[i].dev = nullptr;
     }
   }
-  for (int i = 0; i < 2; ++i) {
-    Half& H = c->half[i];
-    if (H.copied) hipEventDestroy(H.copied);
-    if (H.computed) hipEventDestroy(H.computed);
+  for (Half* H : all_halves(c)) {   // ... and release what every half still holds
+    half_free(*H);
+    if (H->copied) hipEventDestroy(H->copied);
+    if (H->computed) hipEventDestroy(H->computed);
   }
-  for (int i = 0; i < 2; ++i) {
-    for (int sd = 0; sd < 2; ++sd) {
-      if (c->pk_pin[i][sd]) hipHostFree(c->pk_pin[i][sd]);
-      if (c->pk_dev[i][sd]) hipFree(c->pk_dev[i][sd]);
-    }
-    if (c->pk_copied[i]) hipEventDestroy(c->pk_copied[i]);
-    if (c->pk_computed[i]) hipEventDestroy(c->pk_computed[i]);
-  }
-  if (c->pk_stream) hipStreamDestroy(c->pk_stream);
   for (void* b : c->side_buf)
     if (b) hipFree(b);
   for (uint8_t* b : c->side_pin)
@@ -1380,40 +1452,16 @@ int pqa_submit_device(pqa_ctx* c, int64_t first_index, int32_t n_frames, const p
                       const pqa_device_clip* dis, const void* prev_ref_luma, int64_t prev_row_pitch) {
   if (!c) return PQA_EINVAL;
   if (!ref || !dis || n_frames < 0 || first_index < 0) return fail(c, PQA_EINVAL, "bad argument");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames > c->capacity)
-    return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)",
-                n_frames, c->capacity);
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = flush_pending(c);
-  if (rc != PQA_OK) return rc;
-  if ((rc = check_slots_free(c, first_index, n_frames)) != PQA_OK) return rc;   // the whole run, before any batch is launched
-  // a run longer than a batch goes down in EQUAL launches (300 frames at batch 32: ten of 30, not nine of 32 and one of 12 --
-  // a short launch pays the same ramp and tail for fewer waves); records do not depend on how a run is cut
-  const int n_launch = (n_frames + c->B - 1) / c->B;
-  const int per = n_launch ? (n_frames + n_launch - 1) / n_launch : 0;
-  for (int done = 0; done < n_frames;) {
-    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-    const int n = n_frames - done < per ? n_frames - done : per;
-    pqa_device_clip r = *ref, d = *dis;
-    for (int p = 0; p < c->n_planes; ++p) {
-      r.plane[p] = (const uint8_t*)ref->plane[p] + (int64_t)done * ref->frame_pitch[p];
-      d.plane[p] = (const uint8_t*)dis->plane[p] + (int64_t)done * dis->frame_pitch[p];
-    }
-    const void* prev = nullptr;
-    int64_t prev_pitch = 0;
-    if (done == 0) {
-      prev = prev_ref_luma;
-      prev_pitch = prev_row_pitch;
-    } else {
-      prev = (const uint8_t*)ref->plane[0] + (int64_t)(done - 1) * ref->frame_pitch[0];
-      prev_pitch = ref->row_pitch[0];
-    }
-    rc = process_batch(c, first_index + done, n, &r, &d, prev, prev_pitch);
-    if (rc != PQA_OK) return rc;
-    done += n;
-  }
-  return PQA_OK;
+  PQACHK(run_admit(c, n_frames));
+  PQACHK(run_begin(c, first_index, n_frames));
+  return launch_run(c, first_index, n_frames, [&](int done, int, LaunchInput* in) -> int {
+    in->ref = clip_from(*ref, c->n_planes, done);
+    in->dis = clip_from(*dis, c->n_planes, done);
+    // the halo: the caller's in front of the run, the reference frame before the launch inside it
+    in->prev = done == 0 ? prev_ref_luma : (const uint8_t*)ref->plane[0] + (int64_t)(done - 1) * ref->frame_pitch[0];
+    in->prev_pitch = done == 0 ? prev_row_pitch : ref->row_pitch[0];
+    return PQA_OK;
+  });
 }
 
 namespace {
@@ -1436,21 +1484,15 @@ int check_packed_rows(pqa_ctx* c, const char* who, uint32_t format, const void* 
 // n packed frames -> the planes of side sd of the surf_dev slots (luma only in a luma-only context)
 hipError_t unpack_to_slots(pqa_ctx* c, int sd, uint32_t format, const void* src, int64_t row_pitch, int64_t frame_pitch, int n,
                            pqa_device_clip* out) {
+  *out = slot_clip(c, c->surf_dev, sd);
   void* dst[3] = {nullptr, nullptr, nullptr};
-  int64_t rp[3] = {0, 0, 0}, fp[3] = {0, 0, 0};
-  for (int p = 0; p < c->n_planes; ++p) {
-    dst[p] = c->surf_dev + c->plane_off[sd][p];
-    rp[p] = c->slot_row_pitch[p];
-    fp[p] = (int64_t)c->slot_bytes;
-    out->plane[p] = dst[p]; out->row_pitch[p] = rp[p]; out->frame_pitch[p] = fp[p];
-  }
-  return launch_unpack(c->stream, (int)format, src, row_pitch, frame_pitch, dst, rp, fp, c->pw[0], c->ph[0], n);
+  for (int p = 0; p < c->n_planes; ++p) dst[p] = (void*)out->plane[p];
+  return launch_unpack(c->stream, (int)format, src, row_pitch, frame_pitch, dst, out->row_pitch, out->frame_pitch, c->pw[0], c->ph[0], n);
 }
 
 int ensure_surf_dev(pqa_ctx* c) {
   if (c->surf_dev) return PQA_OK;
-  slot_layout(c);
-  HIPCHK(c, hipMalloc((void**)&c->surf_dev, c->slot_bytes * (size_t)c->B));
+  HIPCHK(c, hipMalloc((void**)&c->surf_dev, c->slot_bytes() * (size_t)c->B));
   c->allocs.push_back(c->surf_dev);
   return PQA_OK;
 }
@@ -1460,10 +1502,7 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
                         const pqa_surface_clip* dis, const pqa_surface_clip* prev_ref) {
   if (!c) return PQA_EINVAL;
   if (!ref || !dis || n_frames < 0 || first_index < 0) return fail(c, PQA_EINVAL, "bad argument");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames > c->capacity)
-    return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)",
-                n_frames, c->capacity);
+  PQACHK(run_admit(c, n_frames));
   const int bpc = (int)c->cfg.bit_depth;
   const pqa_surface_clip* all[3] = {ref, dis, prev_ref};
   bool any_packed = false, any_decoder = false;
@@ -1500,32 +1539,28 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
     return fail(c, PQA_EINVAL, "decoder surfaces are 4:2:0: the context's chroma shifts must be 1, 1");
   if (c->n_planes == 3 && any_packed && (c->cfg.chroma_hshift != 1 || c->cfg.chroma_vshift != 0))
     return fail(c, PQA_EINVAL, "packed capture formats are 4:2:2: the context's chroma shifts must be 1, 0");
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = flush_pending(c);
-  if (rc != PQA_OK) return rc;
-  if ((rc = check_slots_free(c, first_index, n_frames)) != PQA_OK) return rc;   // before anything is unpacked
+  PQACHK(run_begin(c, first_index, n_frames));
   const bool shift_luma = bpc > 8;   // of a decoder surface
   const int shift = 16 - bpc;
   // Unpacked planes go to a device buffer of B slots.  One buffer is enough: unpack and scoring run on the same stream,
   // so the next batch's unpack starts when this batch's kernels are done.
   const bool stage = shift_luma || c->n_planes == 3 || any_packed;
-  if (stage && (rc = ensure_surf_dev(c)) != PQA_OK) return rc;
+  if (stage) PQACHK(ensure_surf_dev(c));
   const bool prev_packed = prev_ref && host::packed_format(prev_ref->format);
   const bool prev_staged = prev_ref && (prev_packed || shift_luma);   // not usable where it lies
-  if (prev_staged && (c->cfg.features & PQA_FEAT_MOTION)) {
-    // the halo frame goes where a previous batch would have left it, unpacked / shifted down
-    if (prev_packed) {
-      void* dst[3] = {c->mo_hist.base, nullptr, nullptr};
-      const int64_t rp[3] = {c->mo_hist.pitch, 0, 0}, fp[3] = {0, 0, 0};
-      HIPCHK(c, launch_unpack(c->stream, (int)prev_ref->format, prev_ref->luma, prev_ref->luma_row_pitch, 0, dst, rp, fp, c->pw[0],
-                              c->ph[0], 1));
-    } else {
-      HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->mo_hist.base, c->mo_hist.pitch,
-                                      0, c->pw[0], c->ph[0], shift, 1));
-    }
+  // prev_ref's luma, unpacked / shifted down, into a plane of the device
+  const auto stage_prev = [&](uint8_t* dst, int64_t pitch) -> hipError_t {
+    if (!prev_packed)
+      return launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, dst, pitch, 0, c->pw[0], c->ph[0], shift, 1);
+    void* planes[3] = {dst, nullptr, nullptr};
+    const int64_t rp[3] = {pitch, 0, 0}, fp[3] = {0, 0, 0};
+    return launch_unpack(c->stream, (int)prev_ref->format, prev_ref->luma, prev_ref->luma_row_pitch, 0, planes, rp, fp, c->pw[0], c->ph[0], 1);
+  };
+  if (prev_staged && (c->cfg.features & PQA_FEAT_MOTION)) {   // the halo frame goes where a previous batch would have left it
+    HIPCHK(c, stage_prev(c->mo_hist.base, c->mo_hist.pitch));
     c->mo_chain.arm(1);
   }
-  // xpsnr's and siti's reference frame first-1, unpacked / shifted down likewise
+  // xpsnr's and siti's reference frame first-1 likewise, into a plane of its own
   const bool shift_prev = prev_staged && (c->cfg.features & (PQA_FEAT_XPSNR | PQA_FEAT_SITI));
   const int64_t shift_prev_pitch = round_up((int64_t)c->pw[0] * c->esize, 64);
   if (shift_prev) {
@@ -1533,24 +1568,11 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
       HIPCHK(c, hipMalloc((void**)&c->xp_prev, (size_t)shift_prev_pitch * c->ph[0]));
       c->allocs.push_back(c->xp_prev);
     }
-    if (prev_packed) {
-      void* dst[3] = {c->xp_prev, nullptr, nullptr};
-      const int64_t rp[3] = {shift_prev_pitch, 0, 0}, fp[3] = {0, 0, 0};
-      HIPCHK(c, launch_unpack(c->stream, (int)prev_ref->format, prev_ref->luma, prev_ref->luma_row_pitch, 0, dst, rp, fp, c->pw[0],
-                              c->ph[0], 1));
-    } else {
-      HIPCHK(c, launch_ingest_shift16(c->stream, prev_ref->luma, prev_ref->luma_row_pitch, 0, c->xp_prev, shift_prev_pitch, 0,
-                                      c->pw[0], c->ph[0], shift, 1));
-    }
+    HIPCHK(c, stage_prev(c->xp_prev, shift_prev_pitch));
   }
-  const int n_launch = (n_frames + c->B - 1) / c->B;   // equal launches, as in pqa_submit_device
-  const int per = n_launch ? (n_frames + n_launch - 1) / n_launch : 0;
-  for (int done = 0; done < n_frames;) {
-    if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-    const int n = n_frames - done < per ? n_frames - done : per;
-    pqa_device_clip r{}, d{};
-    const pqa_surface_clip* side[2] = {ref, dis};
-    pqa_device_clip* out[2] = {&r, &d};
+  const pqa_surface_clip* side[2] = {ref, dis};
+  return launch_run(c, first_index, n_frames, [&](int done, int n, LaunchInput* in) -> int {
+    pqa_device_clip* out[2] = {&in->ref, &in->dis};
     for (int sd = 0; sd < 2; ++sd) {
       const pqa_surface_clip* s = side[sd];
       const uint8_t* luma = (const uint8_t*)s->luma + (int64_t)done * s->luma_frame_pitch;
@@ -1558,39 +1580,28 @@ int pqa_submit_surfaces(pqa_ctx* c, int64_t first_index, int32_t n_frames, const
         HIPCHK(c, unpack_to_slots(c, sd, s->format, luma, s->luma_row_pitch, s->luma_frame_pitch, n, out[sd]));
         continue;
       }
+      const pqa_device_clip slots = stage ? slot_clip(c, c->surf_dev, sd) : pqa_device_clip{};   // where this side's planes are staged
+      *out[sd] = slots;
       if (shift_luma) {
-        uint8_t* dst = c->surf_dev + c->plane_off[sd][0];
-        HIPCHK(c, launch_ingest_shift16(c->stream, luma, s->luma_row_pitch, s->luma_frame_pitch, dst, c->slot_row_pitch[0],
-                                        (int64_t)c->slot_bytes, c->pw[0], c->ph[0], shift, n));
-        out[sd]->plane[0] = dst; out[sd]->row_pitch[0] = c->slot_row_pitch[0]; out[sd]->frame_pitch[0] = (int64_t)c->slot_bytes;
+        HIPCHK(c, launch_ingest_shift16(c->stream, luma, s->luma_row_pitch, s->luma_frame_pitch, (void*)slots.plane[0], slots.row_pitch[0],
+                                        slots.frame_pitch[0], c->pw[0], c->ph[0], shift, n));
       } else {   // NV12 luma: scored in place
         out[sd]->plane[0] = luma; out[sd]->row_pitch[0] = s->luma_row_pitch; out[sd]->frame_pitch[0] = s->luma_frame_pitch;
       }
       if (c->n_planes == 3) {
         const uint8_t* uv = (const uint8_t*)s->chroma + (int64_t)done * s->chroma_frame_pitch;
-        uint8_t* du = c->surf_dev + c->plane_off[sd][1];
-        uint8_t* dv = c->surf_dev + c->plane_off[sd][2];
-        if (c->slot_row_pitch[1] != c->slot_row_pitch[2]) return fail(c, PQA_EINVAL, "internal: U and V staging pitches differ");
-        HIPCHK(c, launch_ingest_deinterleave(c->stream, c->esize, uv, s->chroma_row_pitch, s->chroma_frame_pitch, du, dv,
-                                             c->slot_row_pitch[1], (int64_t)c->slot_bytes, c->pw[1], c->ph[1],
+        if (slots.row_pitch[1] != slots.row_pitch[2]) return fail(c, PQA_EINVAL, "internal: U and V staging pitches differ");
+        HIPCHK(c, launch_ingest_deinterleave(c->stream, c->esize, uv, s->chroma_row_pitch, s->chroma_frame_pitch, (void*)slots.plane[1],
+                                             (void*)slots.plane[2], slots.row_pitch[1], slots.frame_pitch[1], c->pw[1], c->ph[1],
                                              shift_luma ? shift : 0, n));
-        out[sd]->plane[1] = du; out[sd]->plane[2] = dv;
-        out[sd]->row_pitch[1] = out[sd]->row_pitch[2] = c->slot_row_pitch[1];
-        out[sd]->frame_pitch[1] = out[sd]->frame_pitch[2] = (int64_t)c->slot_bytes;
       }
     }
-    // the halo of the first batch: an NV12 luma plane is usable as it is; an unpacked / shifted one was armed above
-    const void* prev = nullptr;
-    int64_t prev_pitch = 0;
-    if (done == 0 && prev_ref && !prev_staged) { prev = prev_ref->luma; prev_pitch = prev_ref->luma_row_pitch; }
-    if (done == 0 && shift_prev) {   // the same frame as the armed halo
-      prev = c->xp_prev; prev_pitch = shift_prev_pitch;
-    }
-    rc = process_batch(c, first_index + done, n, &r, &d, prev, prev_pitch);
-    if (rc != PQA_OK) return rc;
-    done += n;
-  }
-  return PQA_OK;
+    // the halo of the first launch: an NV12 luma plane is usable as it is; an unpacked / shifted one was armed above, and is
+    // the frame xpsnr and siti look back to
+    if (done == 0 && prev_ref && !prev_staged) { in->prev = prev_ref->luma; in->prev_pitch = prev_ref->luma_row_pitch; }
+    if (done == 0 && shift_prev) { in->prev = c->xp_prev; in->prev_pitch = shift_prev_pitch; }
+    return PQA_OK;
+  });
 }
 
 namespace {
@@ -1615,142 +1626,86 @@ int host_clip_check(pqa_ctx* c, const char* who, const pqa_host_clip* h, int n_f
     *L = host::packed_layout(h->format, c->pw[0], c->ph[0]);
     return PQA_OK;
   }
-  size_t rb[3] = {0, 0, 0};
-  for (int p = 0; p < c->n_planes; ++p) {
-    rb[p] = (size_t)c->pw[p] * c->esize;
-    if (n_frames > 0 && (h->strides[p] < 0 || (size_t)h->strides[p] < rb[p]))
+  for (int p = 0; p < c->n_planes; ++p)
+    if (n_frames > 0 && (h->strides[p] < 0 || (size_t)h->strides[p] < c->slot.plane[p].row_bytes))
       return fail(c, PQA_EINVAL, "submit_packed: %s clip: plane %d stride smaller than a row", who, p);
-  }
   for (int64_t i = 0; i < (int64_t)n_frames * c->n_planes; ++i)
     if (!h->frames[i]) return fail(c, PQA_EINVAL, "submit_packed: %s clip: plane pointer %lld is null", who, (long long)i);
-  *L = host::clip_layout(c->n_planes, rb, c->ph, 64, 256);   // the slot layout of the other host paths
+  *L = c->slot;   // planar frames are staged as the other host paths stage them
   return PQA_OK;
 }
 
-int packed_reserve(pqa_ctx* c, int set, int sd, size_t bytes) {
-  if (c->pk_pin_cap[set][sd] < bytes) {
-    if (c->pk_pin[set][sd]) {
-      HIPCHK(c, hipHostFree(c->pk_pin[set][sd]));
-      c->pk_pin[set][sd] = nullptr;
-      c->pk_pin_cap[set][sd] = 0;
-    }
-    HIPCHK(c, hipHostMalloc((void**)&c->pk_pin[set][sd], bytes, hipHostMallocDefault));
-    c->pk_pin_cap[set][sd] = bytes;
-  }
-  if (c->pk_dev_cap[set][sd] < bytes) {
-    if (c->pk_dev[set][sd]) {
-      HIPCHK(c, hipFree(c->pk_dev[set][sd]));
-      c->pk_dev[set][sd] = nullptr;
-      c->pk_dev_cap[set][sd] = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->pk_dev[set][sd], bytes));
-    c->pk_dev_cap[set][sd] = bytes;
-  }
-  return PQA_OK;
-}
 }  // namespace
 
 int pqa_submit_packed(pqa_ctx* c, int64_t first_index, int32_t n_frames, const pqa_host_clip* ref, const pqa_host_clip* dis) {
   if (!c) return PQA_EINVAL;
   if (!ref || !dis || n_frames < 0 || first_index < 0) return fail(c, PQA_EINVAL, "bad argument");
-  if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
-  if (n_frames > c->capacity)
-    return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)",
-                n_frames, c->capacity);
+  PQACHK(run_admit(c, n_frames));
   const pqa_host_clip* side[2] = {ref, dis};
   host::ClipLayout L[2];
   bool any_packed = false;
   for (int sd = 0; sd < 2; ++sd) {
-    const int rc = host_clip_check(c, sd ? "captured" : "reference", side[sd], n_frames, &L[sd]);
-    if (rc != PQA_OK) return rc;
+    PQACHK(host_clip_check(c, sd ? "captured" : "reference", side[sd], n_frames, &L[sd]));
     any_packed = any_packed || host::packed_format(side[sd]->format);
   }
   if (c->n_planes == 3 && any_packed && (c->cfg.chroma_hshift != 1 || c->cfg.chroma_vshift != 0))
     return fail(c, PQA_EINVAL, "packed capture formats are 4:2:2: the context's chroma shifts must be 1, 0");
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = flush_pending(c);
-  if (rc != PQA_OK) return rc;
-  if ((rc = check_slots_free(c, first_index, n_frames)) != PQA_OK) return rc;   // the whole run, before anything is copied
+  PQACHK(run_begin(c, first_index, n_frames));
   if (n_frames == 0) return PQA_OK;
   const int chunk = n_frames < c->HB ? n_frames : c->HB;
-  if (any_packed && (rc = ensure_surf_dev(c)) != PQA_OK) return rc;
-  if (!c->pk_stream) {
-    HIPCHK(c, hipStreamCreateWithFlags(&c->pk_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      HIPCHK(c, hipEventCreateWithFlags(&c->pk_copied[i], hipEventDisableTiming));
-      HIPCHK(c, hipEventCreateWithFlags(&c->pk_computed[i], hipEventDisableTiming));
-    }
-  }
-  // Chunks alternate between the two sets: chunk k + 1 is packed while chunk k is uploaded, and uploaded (on pk_stream) while
-  // the kernels of chunk k run (on the context's stream).
+  if (any_packed) PQACHK(ensure_surf_dev(c));
+  PQACHK(ensure_copy_path(c, c->chunk_half));
+  // Chunks alternate between the two halves: chunk k + 1 is packed while chunk k is uploaded, and uploaded (on the copy stream)
+  // while the kernels of chunk k run (on the context's stream).
   for (int f0 = 0; f0 < n_frames; f0 += chunk) {
     if (c->cancelled.load()) return fail(c, PQA_ECANCELLED, "cancelled");
     const int m = n_frames - f0 < chunk ? n_frames - f0 : chunk;
-    const int set = c->pk_set;
-    if (c->pk_copied_pending[set]) {   // the set's pinned chunks still feed an earlier upload (a larger chunk must not free them)
-      HIPCHK(c, hipEventSynchronize(c->pk_copied[set]));
-      c->pk_copied_pending[set] = false;
-    }
-    if (c->pk_computed_pending[set] &&
-        (c->pk_dev_cap[set][0] < L[0].frame_bytes * (size_t)m || c->pk_dev_cap[set][1] < L[1].frame_bytes * (size_t)m)) {
-      HIPCHK(c, hipEventSynchronize(c->pk_computed[set]));   // the device copies are about to be replaced by larger ones
-      c->pk_computed_pending[set] = false;
-    }
-    for (int sd = 0; sd < 2; ++sd)
-      if ((rc = packed_reserve(c, set, sd, L[sd].frame_bytes * (size_t)m)) != PQA_OK) return rc;
-    // large frames are packed in ~1 MiB tasks by the pack pool of the pqa_submit path, small ones here
+    Half& H = c->chunk_half[c->cur_chunk_half];
+    const size_t bytes[2] = {L[0].frame_bytes * (size_t)m, L[1].frame_bytes * (size_t)m};
+    const size_t at[2] = {0, (size_t)round_up((int64_t)bytes[0], 256)};   // the captured chunk lies behind the reference chunk
+    PQACHK(half_claim(c, H, at[1] + bytes[1]));
+    // large frames are packed in ~1 MiB tasks by the pack pool of the pqa_submit path, small ones here, the captured chunk
+    // under the upload of the reference chunk; memory sources cannot come up short
+    size_t side_tasks[3] = {0, 0, 0};   // side sd's tasks: [side_tasks[sd], side_tasks[sd + 1])
     bool pooled = false;
-    if (L[0].frame_bytes + L[1].frame_bytes >= (4u << 20)) {
-      try {   // no exception may cross the C ABI
-        ensure_pack_pool(c);
-        if (c->pack_pool) {
-          c->pack_tasks.clear();
-          for (int sd = 0; sd < 2; ++sd)
-            host::pack_clip_tasks(c->pack_tasks, c->pk_pin[set][sd], L[sd], side[sd]->frames, side[sd]->strides, f0, m, 1u << 20);
-          pooled = c->pack_pool->run(c->pack_tasks.data(), (int)c->pack_tasks.size());   // memory sources cannot come up short
-        }
-      } catch (...) {
-        return fail(c, PQA_ENOMEM, "out of host memory while staging frame %lld", (long long)(first_index + f0));
+    try {   // no exception may cross the C ABI
+      c->pack_tasks.clear();
+      for (int sd = 0; sd < 2; ++sd) {
+        host::pack_clip_tasks(c->pack_tasks, H.pinned + at[sd], L[sd], side[sd]->frames, side[sd]->strides, f0, m, 1u << 20);
+        side_tasks[sd + 1] = c->pack_tasks.size();
       }
-    }
-    if (c->pk_computed_pending[set]) {   // the set's device copies are still read by an earlier chunk's kernels
-      HIPCHK(c, hipStreamWaitEvent(c->pk_stream, c->pk_computed[set], 0));
-      c->pk_computed_pending[set] = false;
+      if (L[0].frame_bytes + L[1].frame_bytes >= (4u << 20)) {
+        ensure_pack_pool(c);
+        pooled = c->pack_pool && c->pack_pool->run(c->pack_tasks.data(), (int)c->pack_tasks.size());
+      }
+    } catch (...) {
+      return fail(c, PQA_ENOMEM, "out of host memory while staging frame %lld", (long long)(first_index + f0));
     }
     for (int sd = 0; sd < 2; ++sd) {
-      if (!pooled) host::pack_clip(c->pk_pin[set][sd], L[sd], side[sd]->frames, side[sd]->strides, f0, m);
-      HIPCHK(c, hipMemcpyAsync(c->pk_dev[set][sd], c->pk_pin[set][sd], L[sd].frame_bytes * (size_t)m, hipMemcpyHostToDevice, c->pk_stream));
+      for (size_t i = side_tasks[sd]; !pooled && i < side_tasks[sd + 1]; ++i) run_pack_task(c->pack_tasks[i]);
+      HIPCHK(c, hipMemcpyAsync(H.dev + at[sd], H.pinned + at[sd], bytes[sd], hipMemcpyHostToDevice, c->copy_stream));
     }
-    HIPCHK(c, hipEventRecord(c->pk_copied[set], c->pk_stream));
-    c->pk_copied_pending[set] = true;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->pk_copied[set], 0));
-    c->pk_set ^= 1;
-    const int n_launch = (m + c->B - 1) / c->B;   // equal launches, as in pqa_submit_device
-    const int per = (m + n_launch - 1) / n_launch;
-    for (int done = 0; done < m;) {
-      const int n = m - done < per ? m - done : per;
-      pqa_device_clip clip[2] = {};
+    PQACHK(half_sent(c, H));
+    c->cur_chunk_half ^= 1;
+    const int rc = launch_run(c, first_index + f0, m, [&](int done, int n, LaunchInput* in) -> int {
+      pqa_device_clip* out[2] = {&in->ref, &in->dis};
       for (int sd = 0; sd < 2; ++sd) {
-        const uint8_t* base = c->pk_dev[set][sd] + (size_t)done * L[sd].frame_bytes;
-        if (host::packed_format(side[sd]->format)) {
-          HIPCHK(c, unpack_to_slots(c, sd, side[sd]->format, base, L[sd].plane[0].pitch, (int64_t)L[sd].frame_bytes, n, &clip[sd]));
-        } else {   // planar planes are scored where they were uploaded
-          for (int p = 0; p < c->n_planes; ++p) {
-            clip[sd].plane[p] = base + L[sd].off[p];
-            clip[sd].row_pitch[p] = L[sd].plane[p].pitch;
-            clip[sd].frame_pitch[p] = (int64_t)L[sd].frame_bytes;
-          }
-        }
+        const uint8_t* base = H.dev + at[sd] + (size_t)done * L[sd].frame_bytes;
+        if (host::packed_format(side[sd]->format))
+          HIPCHK(c, unpack_to_slots(c, sd, side[sd]->format, base, L[sd].plane[0].pitch, (int64_t)L[sd].frame_bytes, n, out[sd]));
+        else   // planar planes are scored where they were uploaded
+          *out[sd] = clip_at(base, L[sd], (int64_t)L[sd].frame_bytes);
       }
-      rc = process_batch(c, first_index + f0 + done, n, &clip[0], &clip[1], nullptr, 0);
-      if (rc != PQA_OK) {   // whatever was queued still reads the set
-        c->pk_computed_pending[set] = hipEventRecord(c->pk_computed[set], c->stream) == hipSuccess;
-        return rc;
-      }
-      done += n;
+      return PQA_OK;   // no halo: the chains continue
+    });
+    if (rc != PQA_OK) {   // whatever was queued still reads the half
+      std::string why;
+      why.swap(c->err);
+      half_launched(c, H);
+      why.swap(c->err);
+      return rc;
     }
-    HIPCHK(c, hipEventRecord(c->pk_computed[set], c->stream));
-    c->pk_computed_pending[set] = true;
+    PQACHK(half_launched(c, H));
   }
   // the caller's buffers are free: everything was copied into the pinned chunks above
   return PQA_OK;
@@ -1794,8 +1749,7 @@ int pqa_submit_fd_run(pqa_ctx* c, int64_t first_index, int32_t n_frames, int ref
   if (ref_fd < 0 || dis_fd < 0 || !ref_plane_offsets || !dis_plane_offsets || first_index < 0 || n_frames < 0 ||
       ref_frame_stride < 0 || dis_frame_stride < 0)
     return fail(c, PQA_EINVAL, "bad argument");
-  if (n_frames > c->capacity)
-    return fail(c, PQA_ESTATE, "%d frames in one call exceed result_capacity %d (records would overwrite each other)", n_frames, c->capacity);
+  PQACHK(run_admit(c, n_frames, false));   // the length of the run first; submit_run refuses a cancelled context
   PlaneSrc src[2][3];
   for (int p = 0; p < c->n_planes; ++p) {
     if (ref_plane_offsets[p] < 0 || dis_plane_offsets[p] < 0) return fail(c, PQA_EINVAL, "plane %d file offset is negative", p);
@@ -1813,29 +1767,28 @@ int set_history(pqa_ctx* c, const void* const* prev, int n_prev, int64_t row_str
   const bool mot = c->cfg.features & PQA_FEAT_MOTION, xp = c->cfg.features & PQA_FEAT_XPSNR;
   const bool si = c->cfg.features & PQA_FEAT_SITI;
   if (!mot && !xp && !si) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = flush_pending(c);
-  if (rc != PQA_OK) return rc;
-  if (n_prev == 0) {   // a chain start
-    c->mo_chain.restart();
-    c->xp_chain.restart();
-    c->st_chain[1].restart();
-    return PQA_OK;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (mot) {
-    HIPCHK(c, hist_arm(c, c->mo_hist, prev[0], row_stride, 0));
-    c->mo_chain.arm(1);
-  }
-  if (xp) {
-    for (int j = 0; j < n_prev; ++j) HIPCHK(c, hist_arm(c, c->xp_hist[j], prev[j], row_stride, 0));
-    c->xp_chain.arm(n_prev);
-  }
-  if (si) {
-    HIPCHK(c, hist_arm(c, c->st_hist[1], prev[0], row_stride, 0));
-    c->st_chain[1].arm(1);
-  }
-  return PQA_OK;
+  return arm_histories(
+      c, n_prev > 0,
+      [&] {
+        c->mo_chain.restart();
+        c->xp_chain.restart();
+        c->st_chain[1].restart();
+      },
+      [&]() -> int {
+        if (mot) {
+          HIPCHK(c, hist_arm(c, c->mo_hist, prev[0], row_stride, 0));
+          c->mo_chain.arm(1);
+        }
+        if (xp) {
+          for (int j = 0; j < n_prev; ++j) HIPCHK(c, hist_arm(c, c->xp_hist[j], prev[j], row_stride, 0));
+          c->xp_chain.arm(n_prev);
+        }
+        if (si) {
+          HIPCHK(c, hist_arm(c, c->st_hist[1], prev[0], row_stride, 0));
+          c->st_chain[1].arm(1);
+        }
+        return PQA_OK;
+      });
 }
 }  // namespace
 
@@ -1860,17 +1813,13 @@ int pqa_set_dis_history(pqa_ctx* c, const void* prev_dis_luma_host, int64_t row_
   if (!(c->cfg.features & PQA_FEAT_SITI)) return PQA_OK;
   if (prev_dis_luma_host && row_stride < (int64_t)c->pw[0] * c->esize)
     return fail(c, PQA_EINVAL, "pqa_set_dis_history: row stride %lld smaller than a row", (long long)row_stride);
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = flush_pending(c);
-  if (rc != PQA_OK) return rc;
-  if (!prev_dis_luma_host) {   // a chain start of the distorted clip
-    c->st_chain[0].restart();
-    return PQA_OK;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hist_arm(c, c->st_hist[0], prev_dis_luma_host, row_stride, 0));
-  c->st_chain[0].arm(1);
-  return PQA_OK;
+  return arm_histories(
+      c, prev_dis_luma_host != nullptr, [&] { c->st_chain[0].restart(); },   // a chain start of the distorted clip
+      [&]() -> int {
+        HIPCHK(c, hist_arm(c, c->st_hist[0], prev_dis_luma_host, row_stride, 0));
+        c->st_chain[0].arm(1);
+        return PQA_OK;
+      });
 }
 
 int pqa_set_dis_history_planes(pqa_ctx* c, const void* const planes[3], const int64_t strides[3]) {
@@ -1885,22 +1834,15 @@ int pqa_set_dis_history_planes(pqa_ctx* c, const void* const planes[3], const in
         return fail(c, PQA_EINVAL, "pqa_set_dis_history_planes: plane %d stride %lld smaller than a row", p, (long long)strides[p]);
     }
   }
-  if (si) {   // what pqa_set_dis_history arms
-    const int rc = pqa_set_dis_history(c, planes ? planes[0] : nullptr, planes ? strides[0] : 0);
-    if (rc != PQA_OK) return rc;
-  }
+  if (si) PQACHK(pqa_set_dis_history(c, planes ? planes[0] : nullptr, planes ? strides[0] : 0));   // what it arms
   if (!ig) return PQA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = flush_pending(c);
-  if (rc != PQA_OK) return rc;
-  if (!planes) {   // a chain start
-    c->ig_chain.restart();
-    return PQA_OK;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int p = 0; p < c->n_planes; ++p) HIPCHK(c, hist_arm(c, c->ig_hist[p], planes[p], strides[p], p));
-  c->ig_chain.arm(1);
-  return PQA_OK;
+  return arm_histories(
+      c, planes != nullptr, [&] { c->ig_chain.restart(); },
+      [&]() -> int {
+        for (int p = 0; p < c->n_planes; ++p) HIPCHK(c, hist_arm(c, c->ig_hist[p], planes[p], strides[p], p));
+        c->ig_chain.arm(1);
+        return PQA_OK;
+      });
 }
 
 int pqa_set_black_threshold(pqa_ctx* c, uint32_t threshold) {
@@ -2030,8 +1972,7 @@ int pqa_reset(pqa_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-  if (c->pk_stream) HIPCHK(c, hipStreamSynchronize(c->pk_stream));
-  c->pk_copied_pending[0] = c->pk_copied_pending[1] = c->pk_computed_pending[0] = c->pk_computed_pending[1] = false;
+  for (Half* H : all_halves(c)) H->copied_pending = H->computed_pending = false;   // both streams are idle
   c->cancelled.store(0);
   c->done_seq = c->batch_seq;
   c->ring.reset();

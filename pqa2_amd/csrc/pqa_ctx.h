@@ -34,9 +34,14 @@ struct HistPlane {
   int64_t pitch = 0;  // bytes
 };
 
+// One half of a double-buffered host staging path: a pinned buffer and its device copy, of `cap` bytes each, filled in turn
+// with the other half.  Uploads run on pqa_ctx::copy_stream, kernels on pqa_ctx::stream; three steps keep the two apart
+// (half_claim, half_sent, half_launched in pqa_api.hip).  copied: the upload out of `pinned` is through -- the host may pack it
+// again and the kernels may read `dev`; computed: the kernels that read `dev` are through -- the next upload may overwrite it.
 struct Half {
   uint8_t* pinned = nullptr;
   uint8_t* dev = nullptr;
+  size_t cap = 0;
   hipEvent_t copied = nullptr, computed = nullptr;
   bool copied_pending = false, computed_pending = false;
 };
@@ -194,27 +199,20 @@ struct pqa_ctx {
   // motion continuity: the last reference luma of the chain; pqa_set_motion_halo / pqa_set_ref_history arm it
   pqa::HistPlane mo_hist;
   pqa::host::FrameChain mo_chain;
-  // host staging (pqa_submit path)
-  pqa::Half half[2];
-  int cur_half = 0, pending = 0;
+  // One side of a frame pair as the library lays it out itself (pinned staging, its device copy, unpacked decoder surfaces):
+  // rows padded to 64 bytes, planes to 256; the distorted side lies slot.frame_bytes behind the reference side.
+  pqa::host::ClipLayout slot;
+  size_t slot_bytes() const { return 2 * slot.frame_bytes; }
+  // host staging.  half: the fixed halves of HB slots of the pqa_submit path (frames stay pending until a half is full or
+  // flushed); chunk_half: the grow-only halves of pqa_submit_packed, a chunk of reference frames as the caller has them and the
+  // captured chunk behind it at a 256-byte boundary (a packed frame can be larger than a slot).  Both upload on copy_stream.
+  pqa::Half half[2], chunk_half[2];
+  int cur_half = 0, cur_chunk_half = 0, pending = 0;
   int64_t pending_first = 0;
-  size_t slot_bytes = 0;
-  size_t plane_off[2][3] = {};
-  int64_t slot_row_pitch[3] = {};
   bool staging_ready = false;
   std::thread pin_thread;            // pins the second staging half while the first one fills (ensure_staging)
   hipError_t pin_err = hipSuccess;   // its result; read after joining it (staging_half_ready)
-  uint8_t* surf_dev = nullptr;   // pqa_submit_surfaces: B slots of unpacked planes (device only, allocated on first use)
-  // pqa_submit_packed: two sets (chunks alternate) of a grow-only pinned chunk and its device copy per side, allocated on first
-  // use; uploads run on a stream of their own.  copied: the upload out of a set's pinned chunks is done (the host packs them
-  // again, the kernels may read the device copy); computed: the kernels that read a set's device copy are done
-  uint8_t* pk_pin[2][2] = {};   // [set][side]
-  uint8_t* pk_dev[2][2] = {};
-  size_t pk_pin_cap[2][2] = {}, pk_dev_cap[2][2] = {};
-  hipStream_t pk_stream = nullptr;
-  hipEvent_t pk_copied[2] = {nullptr, nullptr}, pk_computed[2] = {nullptr, nullptr};
-  bool pk_copied_pending[2] = {false, false}, pk_computed_pending[2] = {false, false};
-  int pk_set = 0;
+  uint8_t* surf_dev = nullptr;   // pqa_submit_surfaces, pqa_submit_packed: B slots of unpacked planes (device only, allocated on first use)
   std::unique_ptr<pqa::host::PackPool> pack_pool;
   bool pack_pool_tried = false;
   std::vector<pqa::host::PackTask> pack_tasks;

@@ -29,28 +29,14 @@ using namespace pqa::host;
 
 struct Geometry { int w, h, n_planes; };
 
-// the task list pqa_api.hip builds for m frames: rows of every plane of both clips in ~task_bytes pieces
-static std::vector<PackTask> make_tasks(const Geometry& g, int m, uint8_t* slots, size_t slot_bytes, const size_t (*plane_off)[3],
-                                        const int64_t* slot_pitch, const uint8_t* const mem[2], const int fds[2], int64_t frame_step,
-                                        const int64_t* file_plane_off, unsigned task_bytes) {
+// The task list of m frame pairs as submit_run (pqa_api.hip) cuts it: the library's builder per frame and side, the frames
+// frame_step bytes apart behind src, into slots of two sides each.
+static std::vector<PackTask> run_tasks(const ClipLayout& L, int m, uint8_t* slots, const PlaneSrc (&src)[2][3], int64_t frame_step,
+                                       unsigned task_bytes) {
   std::vector<PackTask> t;
   for (int k = 0; k < m; ++k)
     for (int side = 0; side < 2; ++side)
-      for (int p = 0; p < g.n_planes; ++p) {
-        const int pw = p ? (g.w + 1) / 2 : g.w, ph = p ? (g.h + 1) / 2 : g.h;
-        int rows_per = (int)(task_bytes / (unsigned)pw);
-        if (rows_per < 1) rows_per = 1;
-        for (int y = 0; y < ph; y += rows_per) {
-          const int rows = ph - y < rows_per ? ph - y : rows_per;
-          PackTask x{slots + (size_t)k * slot_bytes + plane_off[side][p] + (int64_t)y * slot_pitch[p],
-                     mem[side] ? mem[side] + (int64_t)k * frame_step + file_plane_off[p] + (int64_t)y * pw : nullptr, slot_pitch[p], pw,
-                     (size_t)pw, rows};
-          x.fd = mem[side] ? -1 : fds[side];
-          x.file_off = (int64_t)k * frame_step + file_plane_off[p] + (int64_t)y * pw;
-          x.frame = k;
-          t.push_back(x);
-        }
-      }
+      pack_frame_tasks(t, L, slots + (size_t)(2 * k + side) * L.frame_bytes, src[side], frame_step, k, k, task_bytes);
   return t;
 }
 
@@ -60,11 +46,23 @@ static void pack_scenarios(const char* dir) {
   const int cw = (g.w + 1) / 2, ch = (g.h + 1) / 2;
   const int64_t frame_bytes = (int64_t)g.w * g.h + 2ll * cw * ch;
   const int64_t file_plane_off[3] = {0, (int64_t)g.w * g.h, (int64_t)g.w * g.h + (int64_t)cw * ch};
-  const int64_t slot_pitch[3] = {(g.w + 63) / 64 * 64, (cw + 63) / 64 * 64, (cw + 63) / 64 * 64};
-  size_t plane_off[2][3], off = 0;
+  const size_t row_bytes[3] = {(size_t)g.w, (size_t)cw, (size_t)cw};
+  const int rows[3] = {g.h, ch, ch};
+  const ClipLayout L = clip_layout(g.n_planes, row_bytes, rows, 64, 256);   // one side of the context's slot
+  const int64_t slot_pitch[3] = {L.plane[0].pitch, L.plane[1].pitch, L.plane[2].pitch};
+  size_t plane_off[2][3];
   for (int side = 0; side < 2; ++side)
-    for (int p = 0; p < 3; ++p) { plane_off[side][p] = off; off += (size_t)slot_pitch[p] * (p ? ch : g.h); }
-  const size_t slot_bytes = off;
+    for (int p = 0; p < 3; ++p) plane_off[side][p] = side * L.frame_bytes + L.off[p];
+  const size_t slot_bytes = 2 * L.frame_bytes;
+  // both clips from memory (frame `first` in front) or from the files, plane p of the files' first frame at off[p]
+  struct Sources { PlaneSrc s[2][3]; };
+  const auto sources = [&](const uint8_t* const mem[2], const int fds[2], const int64_t off[3]) {
+    Sources r;
+    for (int side = 0; side < 2; ++side)
+      for (int p = 0; p < 3; ++p)
+        r.s[side][p] = mem[side] ? PlaneSrc{mem[side] + off[p], (int64_t)row_bytes[p], -1, 0} : PlaneSrc{nullptr, (int64_t)row_bytes[p], fds[side], off[p]};
+    return r;
+  };
   std::mt19937 rng(7);
   std::vector<uint8_t> clip[2];
   char path[2][512];
@@ -96,7 +94,7 @@ static void pack_scenarios(const char* dir) {
     // (1) memory sources, frame by frame (pqa_submit), plain run()
     for (int i = 0; i < n; ++i) {
       const uint8_t* mem[2] = {clip[0].data() + (size_t)i * frame_bytes, clip[1].data() + (size_t)i * frame_bytes};
-      auto t = make_tasks(g, 1, slots.data(), slot_bytes, plane_off, slot_pitch, mem, fds, 0, file_plane_off, 16 << 10);
+      auto t = run_tasks(L, 1, slots.data(), sources(mem, fds, file_plane_off).s, 0, 16 << 10);
       CHECK(pool.run(t.data(), (int)t.size()));
       verify(i, 1);
     }
@@ -107,7 +105,7 @@ static void pack_scenarios(const char* dir) {
       const int m = n - first < HB ? n - first : HB;
       std::fill(slots.begin(), slots.end(), 0);
       const int64_t base[3] = {file_plane_off[0] + first * frame_bytes, file_plane_off[1] + first * frame_bytes, file_plane_off[2] + first * frame_bytes};
-      auto t = make_tasks(g, m, slots.data(), slot_bytes, plane_off, slot_pitch, nomem, fds, frame_bytes, base, 24 << 10);
+      auto t = run_tasks(L, m, slots.data(), sources(nomem, fds, base).s, frame_bytes, 24 << 10);
       int next = 0;
       const bool ok = pool.run_frames(t.data(), (int)t.size(), m, [&](int k) {
         CHECK(k == next && std::this_thread::get_id() == caller);
@@ -127,12 +125,12 @@ static void pack_scenarios(const char* dir) {
       fclose(f);
       int sfd[2] = {open(sp, O_RDONLY), fds[1]};
       CHECK(sfd[0] >= 0);
-      auto t = make_tasks(g, 4, slots.data(), slot_bytes, plane_off, slot_pitch, nomem, sfd, frame_bytes, file_plane_off, 24 << 10);
+      auto t = run_tasks(L, 4, slots.data(), sources(nomem, sfd, file_plane_off).s, frame_bytes, 24 << 10);
       std::vector<int> seen;
       CHECK(!pool.run_frames(t.data(), (int)t.size(), 4, [&](int k) { seen.push_back(k); return true; }));
       for (size_t i = 0; i < seen.size(); ++i) CHECK(seen[i] == (int)i && seen[i] < 2);
       // a callback that fails (the upload could not be queued) ends the hand-over too
-      auto t2 = make_tasks(g, 3, slots.data(), slot_bytes, plane_off, slot_pitch, nomem, fds, frame_bytes, file_plane_off, 24 << 10);
+      auto t2 = run_tasks(L, 3, slots.data(), sources(nomem, fds, file_plane_off).s, frame_bytes, 24 << 10);
       int calls = 0;
       CHECK(!pool.run_frames(t2.data(), (int)t2.size(), 3, [&](int) { ++calls; return false; }) && calls == 1);
       close(sfd[0]);
@@ -144,7 +142,7 @@ static void pack_scenarios(const char* dir) {
       std::thread other([&] { std::this_thread::sleep_for(std::chrono::milliseconds(2)); cancelled.store(1); });
       int submitted = 0;
       for (int rep = 0; rep < 400 && !cancelled.load(); ++rep) {
-        auto t = make_tasks(g, HB, slots.data(), slot_bytes, plane_off, slot_pitch, nomem, fds, frame_bytes, file_plane_off, 24 << 10);
+        auto t = run_tasks(L, HB, slots.data(), sources(nomem, fds, file_plane_off).s, frame_bytes, 24 << 10);
         CHECK(pool.run_frames(t.data(), (int)t.size(), HB, [&](int) { return true; }));
         submitted += HB;
       }
@@ -153,6 +151,49 @@ static void pack_scenarios(const char* dir) {
     }
   }   // the pool is destroyed while idle here, three times
   for (int side = 0; side < 2; ++side) { close(fds[side]); remove(path[side]); }
+}
+
+// A packed clip as pqa_submit_packed stages it: one plane of minimum row bytes a frame, the caller's rows unpadded (one copy a
+// task) and padded (row by row), every caller frame a heap block that ends with its last sample; tasks of a few rows.
+static void packed_clip_scenarios() {
+  const int h = 18, n = 5, f0 = 1, m = 3;
+  for (size_t row : {(size_t)192, (size_t)100, (size_t)144}) {   // UYVY at 96 and 50 wide, v210 at 52
+    const ClipLayout L = plane_clip(row, h);
+    for (int64_t stride : {(int64_t)row, (int64_t)row + 12}) {
+      std::vector<std::unique_ptr<uint8_t[]>> frames;
+      for (int f = 0; f < n; ++f) {
+        const size_t bytes = (size_t)stride * (h - 1) + row;
+        frames.emplace_back(new uint8_t[bytes]);
+        for (size_t i = 0; i < bytes; ++i) frames.back()[i] = (uint8_t)(1 + (i * 131 + f * 17) % 255);
+      }
+      std::unique_ptr<uint8_t[]> pin(new uint8_t[L.frame_bytes * m]);   // exactly a chunk
+      memset(pin.get(), 0, L.frame_bytes * m);
+      std::vector<PackTask> t;
+      for (int f = 0; f < m; ++f) {
+        const PlaneSrc src[3] = {{frames[f0 + f].get(), stride, -1, 0}, {}, {}};
+        pack_frame_tasks(t, L, pin.get() + (size_t)f * L.frame_bytes, src, 0, 0, f, 5 * row + 1);
+      }
+      CHECK((int)t.size() == m * ((h + 4) / 5) && t.front().frame == 0 && t.back().frame == m - 1);
+      PackPool pool(2);
+      CHECK(pool.run(t.data(), (int)t.size()));
+      for (int f = 0; f < m; ++f)
+        for (int y = 0; y < h; ++y)
+          CHECK(!memcmp(pin.get() + (size_t)f * L.frame_bytes + (size_t)y * L.plane[0].pitch, frames[f0 + f].get() + (int64_t)y * stride, row));
+    }
+  }
+}
+
+// host::launch_size: equal launches of at most B frames, as few as launches of B would be
+static void launch_size_properties() {
+  CHECK(launch_size(300, 32) == 30);
+  for (int B = 1; B <= 40; ++B) {
+    CHECK(launch_size(0, B) == 0);
+    for (int n = 1; n <= 700; ++n) {
+      const int per = launch_size(n, B);
+      CHECK(per >= 1 && per <= B && (n + per - 1) / per == (n + B - 1) / B);
+    }
+  }
+  CHECK(launch_size(16384, 256) == 256 && launch_size(16385, 256) <= 256);
 }
 
 static void ring_scenarios() {
@@ -702,6 +743,8 @@ int main(int argc, char** argv) {
   stage_scenarios();
   transform_scenarios();
   pack_scenarios(dir);
+  packed_clip_scenarios();
+  launch_size_properties();
   printf("host harness ok\n");
   return 0;
 }

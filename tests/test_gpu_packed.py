@@ -379,3 +379,95 @@ def test_score_files_scores_the_luma_of_a_420_master_against_a_uyvy_capture(tmp_
     _same_result(got, want)
     assert "psnr_cb" not in got["metrics"] and "psnr_y" in got["metrics"] and "vmaf" in got["metrics"]
     assert got["input"] == {"reference": "yuv420p", "distorted": "uyvy422", "planes_scored": "y", "packed_upload": True}
+
+
+# ---- pqa_submit_packed's staging: halves that grow and alternate, a packed side larger than a slot, reset and mixing --------
+GROW = [("uyvy422", 96, 18), ("v210", 52, 20)]   # with max_batch=2 a staging half holds two frames
+
+
+def _grow_kw():
+    from pqa2_amd import _native as N
+    return dict(n_planes=3, chroma_shift=(1, 0), features=N.FEAT_ALL, max_batch=2)
+
+
+_grow_cache = {}
+
+
+def _grow_clip(fmt, w, h, t0=0):
+    """eight 4:2:2 frames and their records, submitted one by one through pqa_submit: computed once, never written"""
+    key = (fmt, w, h, t0)
+    if key not in _grow_cache:
+        refs, diss = _clip422(w, h, 8, PR.BIT_DEPTH[fmt], t0=t0)
+        _grow_cache[key] = (refs, diss, _planar_records(w, h, PR.BIT_DEPTH[fmt], refs, diss, **_grow_kw()))
+    return _grow_cache[key]
+
+
+def _packed_side(fmt, clip, stride, seed):
+    return [PR.pack(fmt, *f, stride=stride, seed=seed + i) for i, f in enumerate(clip)], fmt
+
+
+def _planar_side(clip):
+    return [[p.copy() for p in f] for f in clip], None
+
+
+def _scribble(*sides):
+    """the caller's arrays right after a call has returned: all of them overwritten"""
+    for frames, fmt in sides:
+        for f in frames:
+            for a in ([f] if fmt else f):
+                a[:] = 0x5A
+
+
+@pytest.mark.parametrize("fmt,w,h", GROW)
+@pytest.mark.parametrize("ref_packed", [False, True])
+def test_submit_packed_halves_grow_and_alternate(fmt, w, h, ref_packed):
+    """one frame reserves the smallest half; seven more run as chunks of 2, 2, 2, 1: both halves grow while the chunk before
+    may still be read, and they alternate four times"""
+    from pqa2_amd.engine import FeatureEngine
+    refs, diss, planar = _grow_clip(fmt, w, h)
+    row = PR.min_row_bytes(fmt, w)
+    rstride, dstride = PR.file_stride(fmt, w) + 8, row + 4   # two different caller strides (v210: multiples of 4)
+    side = lambda clip, f0, f1, stride, seed, packed: (_packed_side(fmt, clip[f0:f1], stride, seed) if packed
+                                                       else _planar_side(clip[f0:f1]))
+    with FeatureEngine(w, h, bit_depth=PR.BIT_DEPTH[fmt], **_grow_kw()) as eng:
+        for f0, f1 in ((0, 1), (1, 8)):
+            r, d = side(refs, f0, f1, rstride, 100, ref_packed), side(diss, f0, f1, dstride, 200, True)
+            eng.submit_packed(f0, r, d)
+            _scribble(r, d)
+        assert np.array_equal(eng.collect(0, 8).view(np.uint64), planar.view(np.uint64))
+
+
+def test_submit_packed_side_larger_than_a_planar_slot():
+    """a luma-only context: a UYVY frame is two bytes a pixel against a slot of one"""
+    from pqa2_amd.engine import FeatureEngine
+    fmt, w, h, n = "uyvy422", 96, 18, 5
+    refs, diss = _clip422(w, h, n, 8)
+    kw = dict(n_planes=1, max_batch=2)
+    planar = _planar_records(w, h, 8, [f[:1] for f in refs], [f[:1] for f in diss], **kw)
+    with FeatureEngine(w, h, **kw) as eng:
+        r, d = _planar_side([f[:1] for f in refs]), _packed_side(fmt, diss, PR.min_row_bytes(fmt, w) + 12, 7)
+        eng.submit_packed(0, r, d)
+        _scribble(r, d)
+        assert np.array_equal(eng.collect(0, n).view(np.uint64), planar.view(np.uint64))
+
+
+@pytest.mark.parametrize("fmt,w,h", GROW)
+def test_submit_packed_after_pending_frames_and_after_reset(fmt, w, h):
+    """pqa_submit leaves one frame pending when pqa_submit_packed enters; after pqa_reset the halves serve another clip"""
+    from pqa2_amd.engine import FeatureEngine
+    refs, diss, planar = _grow_clip(fmt, w, h)
+    refs2, diss2, planar2 = _grow_clip(fmt, w, h, t0=5)
+    row = PR.min_row_bytes(fmt, w)
+    with FeatureEngine(w, h, bit_depth=PR.BIT_DEPTH[fmt], **_grow_kw()) as eng:
+        for i in range(3):
+            eng.submit(i, refs[i], diss[i])
+        r, d = _planar_side(refs[3:6]), _packed_side(fmt, diss[3:6], row + 4, 300)
+        eng.submit_packed(3, r, d)
+        _scribble(r, d)
+        eng.submit(6, refs[6], diss[6])
+        assert np.array_equal(eng.collect(0, 7).view(np.uint64), planar[:7].view(np.uint64))
+        eng.reset()
+        r, d = _packed_side(fmt, refs2[:7], PR.file_stride(fmt, w) + 8, 400), _packed_side(fmt, diss2[:7], row + 4, 500)
+        eng.submit_packed(0, r, d)
+        _scribble(r, d)
+        assert np.array_equal(eng.collect(0, 7).view(np.uint64), planar2[:7].view(np.uint64))
