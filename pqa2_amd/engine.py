@@ -44,6 +44,32 @@ def _park(lib, key, ctx):
 _PARKED_HOOK = []
 
 
+def _tiles_out(n, sp, sums, dtype=np.uint64):
+    t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
+    return np.zeros((max(int(n), 0), -(-sp.height // t), -(-sp.width // t), sums), dtype)
+
+
+def _lines_out(n, sp, sums):
+    return np.zeros((max(int(n), 0), sp.height + sp.width, sums), np.uint64)
+
+
+def _bands_out(n, sp):
+    lv = sp.levels if 1 <= sp.levels <= 6 else 1      # a bad count is the library's to refuse
+    return np.zeros((max(int(n), 0), lv, 4, N.BAND_SUMS), np.uint64)
+
+
+# The spec-driven analyses, pqa_<name> and pqa_<name>_device: (spec class, its third field, the zeroed result of n frames)
+_ANALYSES = {
+    "flow_moments": (N.PqaFlowSpec, "tile", lambda n, sp: _tiles_out(n, sp, 6, np.int64)),
+    "tile_moments": (N.PqaTileSpec, "tile", lambda n, sp: _tiles_out(n, sp, N.TILE_SUMS)),
+    "band_moments": (N.PqaBandSpec, "levels", _bands_out),
+    "temporal_moments": (N.PqaTemporalSpec, "tile", lambda n, sp: _tiles_out(int(n) - 1, sp, N.TEMPORAL_SUMS)),
+    "line_profiles": (N.PqaProfileSpec, None, lambda n, sp: _lines_out(n, sp, 2)),
+    "field_moments": (N.PqaFieldSpec, None, lambda n, sp: np.zeros((max(int(n) - 1, 0), N.FIELD_SUMS), np.uint64)),
+    "edge_profiles": (N.PqaEdgeSpec, None, lambda n, sp: _lines_out(n, sp, N.EDGE_SUMS)),
+}
+
+
 class FeatureEngine:
     def __init__(self, width: int, height: int, bit_depth: int = 8, n_planes: int = 1,
                  chroma_shift=(1, 1), features: int = N.FEAT_VMAF, device: int = 0, max_batch: int = 0,
@@ -120,20 +146,57 @@ class FeatureEngine:
         msg = (self.lib.pqa_last_error(self._ctx) or b"").decode()
         raise (N.PqaCancelled if rc == N.PQA_ECANCELLED else N.PqaError)(rc, msg)
 
+    # -- marshalling: planes going in, planes coming out, clips in HBM -------------------------
+    @staticmethod
+    def _host_planes(frames, dtype, what, shapes=None, k=None, step=None):
+        """(arrays kept alive, pointer array, row stride of every plane kind as a c_int64 triple) of planes in host memory:
+        a list of planes (k None) or of frames of k planes, whose pointers lie `step` (default k) apart in the array.  The one
+        rule: the planes are handed over as they lie only if every one of them is 2-D, has `dtype`, a unit column stride and
+        a POSITIVE row stride equal to that of the same plane kind in the first frame; otherwise all become packed copies.
+        Then the sizes: shapes[p] is the (height, width) a plane of kind p must have, None for the first frame's (shapes
+        None: 2-D is all that is asked); `what` is the ValueError's text, formatted with i (frame), p (plane), got, want.
+        No frames: an array of one null pointer and the row bytes of shapes[p], 0 where there is none."""
+        dtype = np.dtype(dtype)
+        arrs = [[np.asarray(f)] if k is None else [np.asarray(f[p]) for p in range(k)] for f in frames]
+        k = k or 1
+        if not all(a.ndim == 2 and a.dtype == dtype and a.strides[1] == a.itemsize and 0 < a.strides[0] == arrs[0][p].strides[0]
+                   for f in arrs for p, a in enumerate(f)):
+            arrs = [[np.ascontiguousarray(a, dtype=dtype) for a in f] for f in arrs]
+        want = [None if shapes is None else arrs[0][p].shape if arrs and shapes[p] is None else shapes[p] for p in range(k)]
+        step = step or k
+        ptrs = (C.c_void_p * max(len(arrs) * step, 1))()
+        for i, f in enumerate(arrs):
+            for p, a in enumerate(f):
+                if a.ndim != 2 or (want[p] is not None and a.shape != tuple(want[p])):
+                    raise ValueError(what.format(i=i, p=p, got=a.shape, want=want[p]))
+                ptrs[i * step + p] = a.ctypes.data
+        strides = [arrs[0][p].strides[0] if arrs else (int(want[p][1]) * dtype.itemsize if want[p] is not None else 0) for p in range(k)]
+        return [a for f in arrs for a in f], ptrs, (C.c_int64 * 3)(*strides)
+
+    @staticmethod
+    def _outputs(n, shapes, dtype, planes=None):
+        """(new arrays, frame by frame; their pointer array; the row bytes of every plane kind as a c_int64 triple) of n output
+        frames that hold the first `planes` (default: all) of the plane kinds `shapes`; one kind: a pointer a frame, more: three"""
+        planes, step = planes or len(shapes), 1 if len(shapes) == 1 else 3
+        out = [np.empty(shapes[p], dtype) for _ in range(n) for p in range(planes)]
+        ptrs = (C.c_void_p * max(n * step, 1))()
+        for j, o in enumerate(out):
+            ptrs[j // planes * step + j % planes] = o.ctypes.data
+        return out, ptrs, (C.c_int64 * 3)(*[int(s[1]) * np.dtype(dtype).itemsize for s in shapes])
+
+    @staticmethod
+    def _device_clip(ptrs, row_pitch, frame_pitch, count=3):
+        """the pqa_device_clip of the first `count` planes of a clip in HBM (0 or None: a null plane)"""
+        d = N.PqaDeviceClip()
+        for p in range(count):
+            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptrs[p] or None, row_pitch[p], frame_pitch[p]
+        return d
+
     # -- host path ---------------------------------------------------------------------------
     def submit(self, index: int, ref_planes, dis_planes):
         """ref_planes / dis_planes: sequences of 2-D numpy arrays (Y[,U,V]) of this engine's dtype."""
-        P, S = C.c_void_p * 3, C.c_int64 * 3
-        rp, rs, dp, ds = P(), S(), P(), S()
-        keep = []
-        for p in range(self.n_planes):
-            for arr, pp, ss in ((ref_planes[p], rp, rs), (dis_planes[p], dp, ds)):
-                a = np.asarray(arr)
-                if a.dtype != self.dtype or a.strides[1] != a.itemsize:
-                    a = np.ascontiguousarray(a, dtype=self.dtype)
-                keep.append(a)
-                pp[p] = a.ctypes.data
-                ss[p] = a.strides[0]
+        keep_r, rp, rs = self._planes(ref_planes)
+        keep_d, dp, ds = self._planes(dis_planes)
         self._check(self.lib.pqa_submit(self._ctx, index, C.byref(rp), C.byref(rs), C.byref(dp), C.byref(ds)))
 
     def submit_file(self, index: int, ref_fd: int, ref_offsets, dis_fd: int, dis_offsets):
@@ -182,15 +245,7 @@ class FeatureEngine:
 
     def _planes(self, planes):
         """(keep-alive arrays, pointer triple, stride triple) of the first n_planes planes of a frame."""
-        P, S = C.c_void_p * 3, C.c_int64 * 3
-        pp, ss, keep = P(), S(), []
-        for p in range(self.n_planes):
-            a = np.asarray(planes[p])
-            if a.dtype != self.dtype or a.strides[1] != a.itemsize:
-                a = np.ascontiguousarray(a, dtype=self.dtype)
-            keep.append(a)
-            pp[p], ss[p] = a.ctypes.data, a.strides[0]
-        return keep, pp, ss
+        return self._host_planes([planes], self.dtype, "a frame needs 2-D planes", k=self.n_planes, step=3)
 
     def set_dis_history_planes(self, prev_dis_planes):
         """Every plane of the distorted frame in front of the next submitted frame (frame first-1): the integrity
@@ -214,14 +269,8 @@ class FeatureEngine:
         out = np.zeros((n, 3), np.uint64)
         if n == 0:
             return out
-        keep, ap, as_ = self._planes(anchor_planes)
-        ptrs = (C.c_void_p * (3 * n))()
-        strides = None
-        for f, planes in enumerate(frames):   # packed planes: one common row stride per plane
-            k, pp, strides = self._planes([np.ascontiguousarray(planes[p], dtype=self.dtype) for p in range(self.n_planes)])
-            keep += k
-            for p in range(self.n_planes):
-                ptrs[3 * f + p] = pp[p]
+        keep_a, ap, as_ = self._planes(anchor_planes)
+        keep, ptrs, strides = self._host_planes(frames, self.dtype, "a frame needs 2-D planes", k=self.n_planes, step=3)
         self._check(self.lib.pqa_frame_sad(self._ctx, C.byref(ap), C.byref(as_), ptrs, C.byref(strides), n, out.ctypes.data))
         return out
 
@@ -229,11 +278,8 @@ class FeatureEngine:
         """[n, 3] uint64 like frame_sad() for a clip in HBM (frame_ptrs: device addresses of frame 0's planes) against an
         anchor frame in HBM; pitches in bytes per plane (pqa_frame_sad_device)."""
         out = np.zeros((n_frames, 3), np.uint64)
-        P, S = C.c_void_p * 3, C.c_int64 * 3
-        ap, as_, d = P(), S(), N.PqaDeviceClip()
-        for p in range(self.n_planes):
-            ap[p], as_[p] = anchor_ptrs[p], anchor_row_pitch[p]
-            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = frame_ptrs[p], row_pitch[p], frame_pitch[p]
+        ap, as_ = (C.c_void_p * 3)(*anchor_ptrs[:self.n_planes]), (C.c_int64 * 3)(*anchor_row_pitch[:self.n_planes])
+        d = self._device_clip(frame_ptrs, row_pitch, frame_pitch, self.n_planes)
         self._check(self.lib.pqa_frame_sad_device(self._ctx, C.byref(ap), C.byref(as_), C.byref(d), n_frames, out.ctypes.data))
         return out
 
@@ -241,11 +287,8 @@ class FeatureEngine:
     def submit_resident(self, first_index: int, n_frames: int, ref_ptrs, dis_ptrs, row_pitch, frame_pitch,
                         prev_ref_luma_ptr: int = 0, prev_row_pitch: int = 0):
         """ref_ptrs/dis_ptrs: device addresses of frame 0's planes; pitches in bytes per plane."""
-        r, d = N.PqaDeviceClip(), N.PqaDeviceClip()
-        for p in range(self.n_planes):
-            r.plane[p], d.plane[p] = ref_ptrs[p], dis_ptrs[p]
-            r.row_pitch[p] = d.row_pitch[p] = row_pitch[p]
-            r.frame_pitch[p] = d.frame_pitch[p] = frame_pitch[p]
+        r = self._device_clip(ref_ptrs, row_pitch, frame_pitch, self.n_planes)
+        d = self._device_clip(dis_ptrs, row_pitch, frame_pitch, self.n_planes)
         self._check(self.lib.pqa_submit_device(self._ctx, first_index, n_frames, C.byref(r), C.byref(d),
                                                prev_ref_luma_ptr or None, prev_row_pitch))
 
@@ -290,25 +333,13 @@ class FeatureEngine:
         aligned); fmt: "uyvy422", "yuyv422" or "v210"; shape = (height, width) of the luma plane.  Y is height x width, U and
         V are height x ceil(width / 2); uint8, v210: uint16 values 0 ... 1023.  The size is the call's own."""
         f = self._packed_format(fmt)
-        arrs = [np.asarray(a) for a in frames]
-        if any(a.ndim != 2 or a.dtype != np.uint8 or a.strides[1] != 1 or a.strides[0] != arrs[0].strides[0] for a in arrs):
-            arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrs]
-        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
-            raise ValueError("unpack needs 2-D arrays of packed rows of one size")
+        keep, sptr, ss = self._host_planes(frames, np.uint8, "unpack needs 2-D arrays of packed rows of one size", [None])
         sp = self._unpack_spec(f, shape)
         h, w = int(shape[0]), int(shape[1])
-        dt = np.uint16 if N.PACKED_BIT_DEPTH[f] > 8 else np.uint8
-        n, cw = len(arrs), (w + 1) // 2
-        out = [tuple(np.empty((h, w if p == 0 else cw), dt) for p in range(1 if luma_only else 3)) for _ in arrs]
-        sptr, dptr = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(3 * n, 1))()
-        for i, (a, o) in enumerate(zip(arrs, out)):
-            sptr[i] = a.ctypes.data
-            for p, plane in enumerate(o):
-                dptr[3 * i + p] = plane.ctypes.data
-        item = np.dtype(dt).itemsize
-        ds = (C.c_int64 * 3)(w * item, cw * item, cw * item)
-        self._check(self.lib.pqa_unpack(self._ctx, C.byref(sp), sptr, arrs[0].strides[0] if arrs else 0, n, dptr, C.byref(ds)))
-        return out
+        n, cw, k = len(keep), (w + 1) // 2, 1 if luma_only else 3
+        out, dptr, ds = self._outputs(n, [(h, w), (h, cw), (h, cw)], np.uint16 if N.PACKED_BIT_DEPTH[f] > 8 else np.uint8, k)
+        self._check(self.lib.pqa_unpack(self._ctx, C.byref(sp), sptr, ss[0], n, dptr, C.byref(ds)))
+        return [tuple(out[i * k:(i + 1) * k]) for i in range(n)]
 
     def unpack_resident(self, fmt, shape, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, n_frames: int, dst_ptrs,
                         dst_row_pitch, dst_frame_pitch):
@@ -316,9 +347,7 @@ class FeatureEngine:
         src_ptr become the planes at dst_ptrs = (Y, U, V) or (Y,) for luma only.  Nothing crosses PCIe; the planes can go
         straight into submit_resident or any *_resident analysis."""
         sp = self._unpack_spec(self._packed_format(fmt), shape)
-        d = N.PqaDeviceClip()
-        for p, ptr in enumerate(dst_ptrs):
-            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptr or None, dst_row_pitch[p], dst_frame_pitch[p]
+        d = self._device_clip(dst_ptrs, dst_row_pitch, dst_frame_pitch, len(dst_ptrs))
         self._check(self.lib.pqa_unpack_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch, int(n_frames),
                                                C.byref(d)))
 
@@ -350,21 +379,10 @@ class FeatureEngine:
         sp = self._convert_spec(luma_shape, src, dst, generic)
         sdt = np.uint8 if int(src[4]) <= 8 else np.dtype("<u2")
         ddt = np.uint8 if int(dst[4]) <= 8 else np.dtype("<u2")
-        arrs = [np.asarray(f) for f in frames]
-        if any(a.ndim != 2 or a.dtype != sdt or a.strides[1] != a.itemsize or a.strides[0] < 0 or a.strides[0] != arrs[0].strides[0]
-               for a in arrs):
-            arrs = [np.ascontiguousarray(a, dtype=sdt) for a in arrs]
         src_shape = self.convert_plane_shape(luma_shape, int(src[0]) & 3, int(src[1]) & 3)
-        if any(a.ndim != 2 or a.shape != src_shape for a in arrs):
-            raise ValueError(f"format_convert needs 2-D planes of {src_shape[0]} x {src_shape[1]} samples")
-        dst_shape = self.convert_plane_shape(luma_shape, int(dst[0]) & 3, int(dst[1]) & 3)
-        out = [np.empty(dst_shape, ddt) for _ in arrs]
-        sptr, dptr = (C.c_void_p * max(len(arrs), 1))(), (C.c_void_p * max(len(arrs), 1))()
-        for i, (a, o) in enumerate(zip(arrs, out)):
-            sptr[i], dptr[i] = a.ctypes.data, o.ctypes.data
-        self._check(self.lib.pqa_format_convert(self._ctx, C.byref(sp), sptr,
-                                                arrs[0].strides[0] if arrs else src_shape[1] * np.dtype(sdt).itemsize, dptr,
-                                                dst_shape[1] * np.dtype(ddt).itemsize, len(arrs)))
+        keep, sptr, ss = self._host_planes(frames, sdt, f"format_convert needs 2-D planes of {src_shape[0]} x {src_shape[1]} samples", [src_shape])
+        out, dptr, ds = self._outputs(len(keep), [self.convert_plane_shape(luma_shape, int(dst[0]) & 3, int(dst[1]) & 3)], ddt)
+        self._check(self.lib.pqa_format_convert(self._ctx, C.byref(sp), sptr, ss[0], dptr, ds[0], len(keep)))
         return out
 
     def format_convert_resident(self, luma_shape, src, dst, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, dst_ptr: int,
@@ -402,25 +420,13 @@ class FeatureEngine:
         else uint16); m: the Q14 matrix (pqa2_amd.rgb.conversion_matrix).  generic: the general kernel whatever the layout
         (the same integers).  The size is the call's own, not this context's."""
         sp = self._rgb_spec(fmt, shape, dst, m, generic)
-        arrs = [np.asarray(a) for a in frames]
-        if any(a.ndim != 2 or a.dtype != np.uint8 or a.strides[1] != 1 or a.strides[0] != arrs[0].strides[0] for a in arrs):
-            arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrs]
-        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
-            raise ValueError("rgb_convert needs 2-D arrays of packed rows of one size")
+        keep, sptr, ss = self._host_planes(frames, np.uint8, "rgb_convert needs 2-D arrays of packed rows of one size", [None])
         h, w = int(shape[0]), int(shape[1])
-        ch, cw = self.convert_plane_shape((h, w), int(dst[0]) & 1, int(dst[1]) & 1)
-        dt = np.uint16 if int(dst[4]) > 8 else np.uint8
-        n = len(arrs)
-        out = [[np.empty((h, w) if p == 0 else (ch, cw), dt) for p in range(1 if luma_only else 3)] for _ in arrs]
-        sptr, dptr = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(3 * n, 1))()
-        for i, (a, o) in enumerate(zip(arrs, out)):
-            sptr[i] = a.ctypes.data
-            for p, plane in enumerate(o):
-                dptr[3 * i + p] = plane.ctypes.data
-        item = np.dtype(dt).itemsize
-        ds = (C.c_int64 * 3)(w * item, cw * item, cw * item)
-        self._check(self.lib.pqa_rgb_convert(self._ctx, C.byref(sp), sptr, arrs[0].strides[0] if arrs else 0, n, dptr, C.byref(ds)))
-        return out
+        chroma = self.convert_plane_shape((h, w), int(dst[0]) & 1, int(dst[1]) & 1)
+        n, k = len(keep), 1 if luma_only else 3
+        out, dptr, ds = self._outputs(n, [(h, w), chroma, chroma], np.uint16 if int(dst[4]) > 8 else np.uint8, k)
+        self._check(self.lib.pqa_rgb_convert(self._ctx, C.byref(sp), sptr, ss[0], n, dptr, C.byref(ds)))
+        return [out[i * k:(i + 1) * k] for i in range(n)]
 
     def rgb_convert_resident(self, fmt, shape, dst, m, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, n_frames: int, dst_ptrs,
                              dst_row_pitch, dst_frame_pitch, generic: bool = False):
@@ -428,9 +434,7 @@ class FeatureEngine:
         src_ptr become the planes at dst_ptrs = (Y, U, V) or (Y,) for luma only.  Nothing crosses PCIe; the planes can go
         straight into submit_resident or any *_resident analysis."""
         sp = self._rgb_spec(fmt, shape, dst, m, generic)
-        d = N.PqaDeviceClip()
-        for p, ptr in enumerate(dst_ptrs):
-            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptr or None, dst_row_pitch[p], dst_frame_pitch[p]
+        d = self._device_clip(dst_ptrs, dst_row_pitch, dst_frame_pitch, len(dst_ptrs))
         self._check(self.lib.pqa_rgb_convert_device(self._ctx, C.byref(sp), src_ptr or None, src_row_pitch, src_frame_pitch, int(n_frames),
                                                     C.byref(d)))
 
@@ -441,23 +445,11 @@ class FeatureEngine:
         h.struct_size = C.sizeof(N.PqaHostClip)
         if fmt is None or fmt == "planar":
             h.format = N.SURFACE_PLANAR
-            ptrs = (C.c_void_p * max(len(frames) * self.n_planes, 1))()
-            for f, planes in enumerate(frames):
-                k, pp, ss = self._planes([np.ascontiguousarray(planes[p], dtype=self.dtype) for p in range(self.n_planes)])
-                keep += k
-                for p in range(self.n_planes):
-                    ptrs[f * self.n_planes + p] = pp[p]
-                    h.strides[p] = ss[p]
+            arrs, ptrs, h.strides = self._host_planes(frames, self.dtype, "a frame needs 2-D planes", k=self.n_planes)
         else:
             h.format = self._packed_format(fmt)
-            arrs = [np.asarray(a) for a in frames]
-            if any(a.ndim != 2 or a.dtype != np.uint8 or a.strides[1] != 1 or a.strides[0] != arrs[0].strides[0] for a in arrs):
-                arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrs]
-            if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
-                raise ValueError("submit_packed needs 2-D arrays of packed rows of one size")
-            keep += arrs
-            ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
-            h.strides[0] = arrs[0].strides[0] if arrs else 0
+            arrs, ptrs, h.strides = self._host_planes(frames, np.uint8, "submit_packed needs 2-D arrays of packed rows of one size", [None])
+        keep += arrs
         keep.append(ptrs)
         h.frames = C.cast(ptrs, C.POINTER(C.c_void_p))
         return h
@@ -494,37 +486,16 @@ class FeatureEngine:
         out = np.zeros((n, 3), np.uint64)
         if n == 0:
             return out
-        keep, ptrs = [], (C.c_void_p * n)()
-        stride = None
-        for i, f in enumerate(luma_frames):
-            a = np.asarray(f)
-            if a.dtype != self.dtype or a.strides[1] != a.itemsize or (stride is not None and a.strides[0] != stride):
-                a = np.ascontiguousarray(a, dtype=self.dtype)
-            if stride is None:
-                stride = a.strides[0]
-            if a.strides[0] != stride:   # the first frame had an odd stride: normalise everything
-                return self.luma_stats([np.ascontiguousarray(x, dtype=self.dtype) for x in luma_frames], threshold)
-            if a.shape != (self.height, self.width):
-                raise ValueError(f"luma frame {i} is {a.shape}, engine is {(self.height, self.width)}")
-            keep.append(a)
-            ptrs[i] = a.ctypes.data
+        keep, ptrs, stride = self._luma_list(luma_frames, "luma")
         self._check(self.lib.pqa_luma_stats(self._ctx, ptrs, stride, n, int(threshold), out.ctypes.data))
         return out
 
     # -- temporal alignment ------------------------------------------------------------------
     def _luma_list(self, frames, what: str, shape=None):
         """(arrays kept alive, ctypes pointer array, common row stride) of luma planes (or planes of `shape`) in host memory"""
-        shape = shape or (self.height, self.width)
-        arrs = [np.asarray(f) for f in frames]
-        strides = {a.strides[0] for a in arrs if a.ndim == 2}
-        if any(a.ndim != 2 or a.dtype != self.dtype or a.strides[1] != a.itemsize for a in arrs) or len(strides) > 1:
-            arrs = [np.ascontiguousarray(a, dtype=self.dtype) for a in arrs]
-        ptrs = (C.c_void_p * max(len(arrs), 1))()
-        for i, a in enumerate(arrs):
-            if a.shape != shape:
-                raise ValueError(f"{what} frame {i} is {a.shape}, engine is {shape}")
-            ptrs[i] = a.ctypes.data
-        return arrs, ptrs, (arrs[0].strides[0] if arrs else shape[1] * np.dtype(self.dtype).itemsize)
+        arrs, ptrs, strides = self._host_planes(frames, self.dtype, what + " frame {i} is {got}, engine is {want}",
+                                                [shape or (self.height, self.width)])
+        return arrs, ptrs, strides[0]
 
     def cross_sse(self, ref_lumas, dis_lumas, k_lo: int, k_hi: int) -> np.ndarray:
         """[n_ref, k_hi - k_lo + 1] uint64: D[i][c] = sum (ref_i - dis_{i + k_lo + c})^2 over the luma plane, exact;
@@ -581,6 +552,14 @@ class FeatureEngine:
         hs, vs = self.chroma_shift
         return ((self.height + (1 << vs) - 1) >> vs, (self.width + (1 << hs) - 1) >> hs)
 
+    def _own_shape(self, name, frames, shape=None):
+        """(height, width) of the planes of a call that brings its own size: `shape`, else the first frame's, else this context's"""
+        if shape is None:
+            shape = np.shape(frames[0]) if len(frames) else (self.height, self.width)
+        if len(shape) != 2:
+            raise ValueError(f"{name} needs 2-D planes")
+        return tuple(int(v) for v in shape)
+
     def level_stats(self, ref_frames, dis_frames, plane: int = 0) -> np.ndarray:
         """[n, L, 3] uint64, L = 2^bit_depth: T[f][v] = (count, sum of dis, sum of dis^2) over the pixels of pair f whose
         reference sample is v, exact (pqa_level_stats).  Planes in HOST memory (two lists of 2-D arrays of equal length,
@@ -620,19 +599,12 @@ class FeatureEngine:
         L - 1)], L = 2^bit_depth (pqa_table_apply; definition: include/pqa_vmaf.h).  Any table of L entries none of which
         exceeds 2^bit_depth - 1, monotone or not; align.curve_lut makes the one that undoes a transfer curve.  The planes have
         the size of `plane` of this context, or with plane=None any one size of their own."""
-        arrs = [np.asarray(f) for f in frames]
-        shape = self.plane_shape(int(plane)) if plane is not None else (arrs[0].shape if arrs else (self.height, self.width))
-        if len(shape) != 2:
-            raise ValueError("table_apply needs 2-D planes")
+        shape = self._own_shape("table_apply", frames, None if plane is None else self.plane_shape(int(plane)))
         keep_t, tp = self._table(table)
         sp = self._plane_spec(N.PqaTableSpec, shape)
-        keep, sptr, sstride = self._luma_list(arrs, "source", tuple(int(v) for v in shape))
-        out = [np.empty(shape, self.dtype) for _ in keep]
-        dptr = (C.c_void_p * max(len(out), 1))()
-        for i, o in enumerate(out):
-            dptr[i] = o.ctypes.data
-        self._check(self.lib.pqa_table_apply(self._ctx, C.byref(sp), tp, sptr, sstride, dptr,
-                                             int(shape[1]) * np.dtype(self.dtype).itemsize, len(keep)))
+        keep, sptr, sstride = self._luma_list(frames, "source", shape)
+        out, dptr, ds = self._outputs(len(keep), [shape], self.dtype)
+        self._check(self.lib.pqa_table_apply(self._ctx, C.byref(sp), tp, sptr, sstride, dptr, ds[0], len(keep)))
         del keep, keep_t
         return out
 
@@ -665,18 +637,11 @@ class FeatureEngine:
         come first in time (0: top field first); rate "frame": one output a source frame, the field `first` kept; "field":
         two, `first` and then the other.  The planes have any one size of their own (`shape`, or the first frame's), at least
         two rows; every source frame is uploaded once."""
-        arrs = [np.asarray(f) for f in frames]
-        shape = tuple(int(v) for v in (shape if shape is not None else (arrs[0].shape if arrs else (self.height, self.width))))
-        if len(shape) != 2:
-            raise ValueError("deinterlace needs 2-D planes")
+        shape = self._own_shape("deinterlace", frames, shape)
         sp = self._deint_spec(shape, mode, first, rate)
-        keep, sptr, sstride = self._luma_list(arrs, "source", shape)
-        out = [np.empty(shape, self.dtype) for _ in range(len(keep) * (1 + sp.rate))]
-        dptr = (C.c_void_p * max(len(out), 1))()
-        for i, o in enumerate(out):
-            dptr[i] = o.ctypes.data
-        self._check(self.lib.pqa_deinterlace(self._ctx, C.byref(sp), sptr, sstride, dptr,
-                                             shape[1] * np.dtype(self.dtype).itemsize, len(keep)))
+        keep, sptr, sstride = self._luma_list(frames, "source", shape)
+        out, dptr, ds = self._outputs(len(keep) * (1 + sp.rate), [shape], self.dtype)
+        self._check(self.lib.pqa_deinterlace(self._ctx, C.byref(sp), sptr, sstride, dptr, ds[0], len(keep)))
         del keep
         return out
 
@@ -715,23 +680,15 @@ class FeatureEngine:
         an integer of at most 2^bit_depth - 1, or a list of as many planes as `frames` whose samples are the fill.
         distortion.overlay_mask makes the grid.  The planes have the size of `plane` of this context, or with plane=None any
         one size of their own."""
-        arrs = [np.asarray(f) for f in frames]
-        shape = self.plane_shape(int(plane)) if plane is not None else (arrs[0].shape if arrs else (self.height, self.width))
-        if len(shape) != 2:
-            raise ValueError("mask_blend needs 2-D planes")
-        shape = tuple(int(v) for v in shape)
+        shape = self._own_shape("mask_blend", frames, None if plane is None else self.plane_shape(int(plane)))
         const = isinstance(fill, (int, np.integer))
-        if not const and len(fill) != len(arrs):
+        if not const and len(fill) != len(frames):
             raise ValueError("mask_blend needs as many fill planes as frames")
         keep_g, gp, sp = self._mask(nodes, steps, fill if const else 0, shape)
-        keep, sptr, sstride = self._luma_list(arrs, "source", shape)
+        keep, sptr, sstride = self._luma_list(frames, "source", shape)
         keep_f, fptr, fstride = (None, None, 0) if const else self._luma_list(fill, "fill", shape)
-        out = [np.empty(shape, self.dtype) for _ in keep]
-        dptr = (C.c_void_p * max(len(out), 1))()
-        for i, o in enumerate(out):
-            dptr[i] = o.ctypes.data
-        self._check(self.lib.pqa_mask_blend(self._ctx, C.byref(sp), gp, sptr, sstride, fptr, fstride, dptr,
-                                            shape[1] * np.dtype(self.dtype).itemsize, len(keep)))
+        out, dptr, ds = self._outputs(len(keep), [shape], self.dtype)
+        self._check(self.lib.pqa_mask_blend(self._ctx, C.byref(sp), gp, sptr, sstride, fptr, fstride, dptr, ds[0], len(keep)))
         del keep, keep_f, keep_g
         return out
 
@@ -767,21 +724,11 @@ class FeatureEngine:
         (pqa_resample; definition: include/pqa_vmaf.h).  window = (x0, y0, w, h) in source samples is what the result
         shows (default: the whole plane); a fractional (x0, y0) with dst_shape = the source's is a sub-pixel shift.  Planes
         in HOST memory; samples of this context's bit depth."""
-        arrs = [np.asarray(f) for f in frames]
-        if any(a.ndim != 2 or a.dtype != self.dtype or a.strides[1] != a.itemsize or a.strides[0] < 0 or a.strides[0] != arrs[0].strides[0]
-               for a in arrs):
-            arrs = [np.ascontiguousarray(a, dtype=self.dtype) for a in arrs]
-        if any(a.ndim != 2 or a.shape != arrs[0].shape for a in arrs):
-            raise ValueError("resample needs 2-D planes of one size")
-        src_shape = arrs[0].shape if arrs else (int(dst_shape[0]), int(dst_shape[1]))
+        src_shape = np.shape(frames[0]) if len(frames) else (int(dst_shape[0]), int(dst_shape[1]))
+        keep, sptr, ss = self._host_planes(frames, self.dtype, "resample needs 2-D planes of one size", [src_shape])
         sp = self._resample_spec(src_shape, dst_shape, filter, window)
-        out = [np.empty((sp.dst_height, sp.dst_width), self.dtype) for _ in arrs]
-        sptr, dptr = (C.c_void_p * max(len(arrs), 1))(), (C.c_void_p * max(len(arrs), 1))()
-        for i, (a, o) in enumerate(zip(arrs, out)):
-            sptr[i], dptr[i] = a.ctypes.data, o.ctypes.data
-        itemsize = np.dtype(self.dtype).itemsize
-        self._check(self.lib.pqa_resample(self._ctx, C.byref(sp), sptr, arrs[0].strides[0] if arrs else src_shape[1] * itemsize,
-                                          dptr, sp.dst_width * itemsize, len(arrs)))
+        out, dptr, ds = self._outputs(len(keep), [(sp.dst_height, sp.dst_width)], self.dtype)
+        self._check(self.lib.pqa_resample(self._ctx, C.byref(sp), sptr, ss[0], dptr, ds[0], len(keep)))
         return out
 
     def resample_resident(self, src_ptr: int, src_row_pitch: int, src_frame_pitch: int, src_shape, dst_ptr: int,
@@ -803,20 +750,30 @@ class FeatureEngine:
             setattr(sp, name, max(0, int(v)))
         return sp
 
-    def _plane_call(self, name, lists, shape, spec_of, out_of):
+    @staticmethod
+    def _spec(name, shape, third=None):
+        """the spec of the analysis `name` (a row of _ANALYSES) over planes of `shape` = (height, width); third: its tile or levels"""
+        cls, field, _ = _ANALYSES[name]
+        return FeatureEngine._plane_spec(cls, shape, **({field: third} if field else {}))
+
+    # the names the argument tests of the raw entries build a spec by
+    _flow_spec = staticmethod(lambda shape, tile: FeatureEngine._spec("flow_moments", shape, tile))
+    _tile_spec = staticmethod(lambda shape, tile: FeatureEngine._spec("tile_moments", shape, tile))
+    _band_spec = staticmethod(lambda shape, levels: FeatureEngine._spec("band_moments", shape, levels))
+    _temporal_spec = staticmethod(lambda shape, tile: FeatureEngine._spec("temporal_moments", shape, tile))
+    _profile_spec = staticmethod(lambda shape: FeatureEngine._spec("line_profiles", shape))
+    _field_spec = staticmethod(lambda shape: FeatureEngine._spec("field_moments", shape))
+    _edge_spec = staticmethod(lambda shape: FeatureEngine._spec("edge_profiles", shape))
+
+    def _plane_call(self, name, lists, shape, third=None):
         """(out, spec) of pqa_<name> over planes in host memory.  lists: (reference frames, captured frames) or (frames,);
-        shape: (height, width) or None for the first frame's; spec_of(shape) and out_of(n, spec) build the spec and the
-        zeroed result array."""
+        shape: (height, width) or None for the first frame's; third: the tile or levels of the spec."""
         n = len(lists[0])
         if len(lists[-1]) != n:
             raise ValueError(f"{name} needs as many captured as reference frames")
-        if shape is None:
-            shape = np.shape(lists[0][0]) if n else (self.height, self.width)
-        if len(shape) != 2:
-            raise ValueError(f"{name} needs 2-D planes")
-        shape = tuple(int(v) for v in shape)
-        sp = spec_of(shape)
-        out = out_of(n, sp)
+        shape = self._own_shape(name, lists[0], shape)
+        sp = self._spec(name, shape, third)
+        out = _ANALYSES[name][2](n, sp)
         keep, args = [], []
         for frames, what in zip(lists, ("reference", "captured") if len(lists) == 2 else ("profile",)):
             arrs, ptrs, stride = self._luma_list(frames, what, shape)
@@ -826,105 +783,66 @@ class FeatureEngine:
         del keep
         return out, sp
 
-    def _plane_call_resident(self, name, clips, n_frames, sp, out):
-        """`out` of pqa_<name>_device; clips: (pointer, row pitch, frame pitch) of every clip, flat"""
+    def _plane_call_resident(self, name, clips, shape, n_frames, third=None):
+        """(out, spec) of pqa_<name>_device; clips: (pointer, row pitch, frame pitch) of every clip, flat"""
+        sp = self._spec(name, shape, third)
+        out = _ANALYSES[name][2](n_frames, sp)
         self._check(getattr(self.lib, f"pqa_{name}_device")(self._ctx, C.byref(sp), *clips, int(n_frames), out.ctypes.data))
-        return out
+        return out, sp
 
     @staticmethod
-    def _tiles_out(n, sp, sums, dtype=np.uint64):
-        t = sp.tile if sp.tile in N.FLOW_TILES else 64     # a bad tile is the library's to refuse
-        return np.zeros((max(int(n), 0), -(-sp.height // t), -(-sp.width // t), sums), dtype)
-
-    @staticmethod
-    def _lines_out(n, sp, sums):
-        return np.zeros((max(int(n), 0), sp.height + sp.width, sums), np.uint64)
+    def _profile_split(out, sp):
+        return out[:, :sp.height], out[:, sp.height:]
 
     # -- sub-pixel registration ----------------------------------------------------------------
-    @staticmethod
-    def _flow_spec(shape, tile):
-        return FeatureEngine._plane_spec(N.PqaFlowSpec, shape, tile=tile)
-
-    @staticmethod
-    def _flow_out(n, sp):
-        return FeatureEngine._tiles_out(n, sp, 6, np.int64)
-
     def flow_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
         """[n, ty, tx, 6] int64: per tile of `tile` x `tile` pixels (8, 16, 32 or 64) the sums of gx^2, gx gy, gy^2, gx dt,
         gy dt, dt^2 over the pixels 1 <= x <= W - 2, 1 <= y <= H - 2 (gx, gy: Sobel of ref + dis; dt: 3 x 3 binomial of
         dis - ref), exact (pqa_flow_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory: two lists of 2-D arrays
         of equal length and one size, which need not be this context's (3 ... 8192 each way); samples of this context's bit
         depth.  align.solve_geometry reads the sum over the frames."""
-        return self._plane_call("flow_moments", (ref_frames, dis_frames), None, lambda s: self._flow_spec(s, tile), self._flow_out)[0]
+        return self._plane_call("flow_moments", (ref_frames, dis_frames), None, tile)[0]
 
     def flow_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                               dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_flow_moments_device)."""
-        sp = self._flow_spec(shape, tile)
         return self._plane_call_resident("flow_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
-                                         n_frames, sp, self._flow_out(n_frames, sp))
+                                         shape, n_frames, tile)[0]
 
     # -- distortion map ------------------------------------------------------------------------
-    @staticmethod
-    def _tile_spec(shape, tile):
-        return FeatureEngine._plane_spec(N.PqaTileSpec, shape, tile=tile)
-
-    @staticmethod
-    def _tile_out(n, sp):
-        return FeatureEngine._tiles_out(n, sp, N.TILE_SUMS)
-
     def tile_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
         """[n, ty, tx, 6] uint64: per tile of `tile` x `tile` pixels (8, 16, 32 or 64; edge tiles hold the pixels that exist)
         the sums of r, d, r^2, d^2, r d and |d - r| (r: reference, d: captured), exact (pqa_tile_moments; definition:
         include/pqa_vmaf.h).  Planes in HOST memory: two lists of 2-D arrays of equal length and one size, which need not be
         this context's (1 ... 8192 each way); samples of this context's bit depth.  distortion.tile_metrics and
         distortion.find_defects read the result."""
-        return self._plane_call("tile_moments", (ref_frames, dis_frames), None, lambda s: self._tile_spec(s, tile), self._tile_out)[0]
+        return self._plane_call("tile_moments", (ref_frames, dis_frames), None, tile)[0]
 
     def tile_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                               dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_tile_moments_device)."""
-        sp = self._tile_spec(shape, tile)
         return self._plane_call_resident("tile_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
-                                         n_frames, sp, self._tile_out(n_frames, sp))
+                                         shape, n_frames, tile)[0]
 
     # -- distortion spectrum -------------------------------------------------------------------
-    @staticmethod
-    def _band_spec(shape, levels):
-        return FeatureEngine._plane_spec(N.PqaBandSpec, shape, levels=levels)
-
-    @staticmethod
-    def _band_out(n, sp):
-        lv = sp.levels if 1 <= sp.levels <= 6 else 1      # a bad count is the library's to refuse
-        return np.zeros((max(int(n), 0), lv, 4, N.BAND_SUMS), np.uint64)
-
     def band_moments(self, ref_frames, dis_frames, levels: int = 4) -> np.ndarray:
         """[n, L, 4, 3] uint64: per level l = 1 ... L = `levels` (1 ... 6) and orientation (0 H, 1 V, 2 D, 3 A) of the
         unnormalised Haar transform the sums of r^2, d^2 and r d over the level's coefficients (r: reference, d: captured; the
         last is an int64: .view(np.int64)), exact (pqa_band_moments; definition: include/pqa_vmaf.h).  Planes in HOST memory:
         two lists of 2-D arrays of equal length and one size, which need not be this context's (1 ... 8192 each way); samples
         of this context's bit depth.  spectrum.band_table and spectrum.summary read the result."""
-        return self._plane_call("band_moments", (ref_frames, dis_frames), None, lambda s: self._band_spec(s, levels), self._band_out)[0]
+        return self._plane_call("band_moments", (ref_frames, dis_frames), None, levels)[0]
 
     def band_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                               dis_frame_pitch: int, shape, n_frames: int, levels: int = 4) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_band_moments_device)."""
-        sp = self._band_spec(shape, levels)
         return self._plane_call_resident("band_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
-                                         n_frames, sp, self._band_out(n_frames, sp))
+                                         shape, n_frames, levels)[0]
 
     # -- temporal distortion -------------------------------------------------------------------
-    @staticmethod
-    def _temporal_spec(shape, tile):
-        return FeatureEngine._plane_spec(N.PqaTemporalSpec, shape, tile=tile)
-
-    @staticmethod
-    def _temporal_out(n, sp):
-        return FeatureEngine._tiles_out(int(n) - 1, sp, N.TEMPORAL_SUMS)
-
     def temporal_moments(self, ref_frames, dis_frames, tile: int = 32) -> np.ndarray:
         """[n - 1, ty, tx, 7] uint64: per transition k = 1 ... n - 1 and tile of `tile` x `tile` pixels (8, 16, 32 or 64; edge
         tiles hold the pixels that exist) the sums of a, b, a^2, b^2, a b, a e and e^2 with a = R_k - R_{k-1},
@@ -933,50 +851,29 @@ class FeatureEngine:
         HOST memory: two lists of 2-D arrays of equal length and one size, which need not be this context's (1 ... 8192 each
         way); samples of this context's bit depth.  Fewer than two frames give an empty result.  temporal.frame_table and
         temporal.summary read the result."""
-        return self._plane_call("temporal_moments", (ref_frames, dis_frames), None, lambda s: self._temporal_spec(s, tile),
-                                self._temporal_out)[0]
+        return self._plane_call("temporal_moments", (ref_frames, dis_frames), None, tile)[0]
 
     def temporal_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                                   dis_frame_pitch: int, shape, n_frames: int, tile: int = 32) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_temporal_moments_device)."""
-        sp = self._temporal_spec(shape, tile)
         return self._plane_call_resident("temporal_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
-                                         n_frames, sp, self._temporal_out(n_frames, sp))
+                                         shape, n_frames, tile)[0]
 
     # -- active-picture detection --------------------------------------------------------------
-    @staticmethod
-    def _profile_spec(shape):
-        return FeatureEngine._plane_spec(N.PqaProfileSpec, shape)
-
-    @staticmethod
-    def _profile_split(out, sp):
-        return out[:, :sp.height], out[:, sp.height:]
-
     def line_profiles(self, frames, shape=None):
         """(rows [n, H, 2], cols [n, W, 2]) uint64: per row and per column of every plane the sum of its samples and the sum
         of their squares, exact (pqa_line_profiles; definition: include/pqa_vmaf.h).  Planes in HOST memory: a list of 2-D
         arrays (views are fine) of `shape` = (height, width), default the first frame's, which need not be this context's
         (1 ... 8192 each way); samples of this context's bit depth.  align.active_picture reads the result."""
-        return self._profile_split(*self._plane_call("line_profiles", (frames,), shape, self._profile_spec,
-                                                     lambda n, sp: self._lines_out(n, sp, 2)))
+        return self._profile_split(*self._plane_call("line_profiles", (frames,), shape))
 
     def line_profiles_resident(self, ptr: int, row_pitch: int, frame_pitch: int, shape, n_frames: int):
         """The same for n_frames planes of `shape` = (height, width) in HBM (device pointer, pitches in bytes;
         pqa_line_profiles_device)."""
-        sp = self._profile_spec(shape)
-        return self._profile_split(self._plane_call_resident("line_profiles", (ptr, row_pitch, frame_pitch), n_frames, sp,
-                                                             self._lines_out(n_frames, sp, 2)), sp)
+        return self._profile_split(*self._plane_call_resident("line_profiles", (ptr, row_pitch, frame_pitch), shape, n_frames))
 
     # -- field alignment -------------------------------------------------------------------------
-    @staticmethod
-    def _field_spec(shape):
-        return FeatureEngine._plane_spec(N.PqaFieldSpec, shape)
-
-    @staticmethod
-    def _field_out(n, sp):
-        return np.zeros((max(int(n) - 1, 0), N.FIELD_SUMS), np.uint64)
-
     def field_moments(self, ref_frames, dis_frames, shape=None) -> np.ndarray:
         """[n - 1, 14] uint64: per transition k = 1 ... n - 1 the squared errors of field against field, E(A, p, B, q) summed
         over the row pairs: words 2 p + q: captured field p of frame k against reference field q of frame k; 4 + 2 p + q:
@@ -985,21 +882,16 @@ class FeatureEngine:
         lists of 2-D arrays (views are fine) of equal length and of `shape` = (height, width), default the first frame's,
         which need not be this context's (width 1 ... 8192, height 2 ... 8192); samples of this context's bit depth.  Fewer
         than two frames give an empty result.  fields.segments and fields.summary read the result."""
-        return self._plane_call("field_moments", (ref_frames, dis_frames), shape, self._field_spec, self._field_out)[0]
+        return self._plane_call("field_moments", (ref_frames, dis_frames), shape)[0]
 
     def field_moments_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                                dis_frame_pitch: int, shape, n_frames: int) -> np.ndarray:
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_field_moments_device)."""
-        sp = self._field_spec(shape)
         return self._plane_call_resident("field_moments", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch, dis_frame_pitch),
-                                         n_frames, sp, self._field_out(n_frames, sp))
+                                         shape, n_frames)[0]
 
     # -- coding-grid detection -----------------------------------------------------------------
-    @staticmethod
-    def _edge_spec(shape):
-        return FeatureEngine._plane_spec(N.PqaEdgeSpec, shape)
-
     def edge_profiles(self, ref_frames, dis_frames, shape=None):
         """(rows [n, H, 3], cols [n, W, 3]) uint64: per row line y (the boundary between the rows y - 1 and y) and per column
         line x (between the columns x - 1 and x) of every frame pair the sums of a^2, b^2 and a b, with a / b the difference
@@ -1007,49 +899,25 @@ class FeatureEngine:
         of each axis is zero; word 2 is int64: read it through .view(np.int64).  Planes in HOST memory: two lists of 2-D arrays
         (views are fine) of equal length and of `shape` = (height, width), default the first frame's, which need not be this
         context's (1 ... 8192 each way); samples of this context's bit depth.  grid.summary reads the result."""
-        return self._profile_split(*self._plane_call("edge_profiles", (ref_frames, dis_frames), shape, self._edge_spec,
-                                                     lambda n, sp: self._lines_out(n, sp, N.EDGE_SUMS)))
+        return self._profile_split(*self._plane_call("edge_profiles", (ref_frames, dis_frames), shape))
 
     def edge_profiles_resident(self, ref_ptr: int, ref_row_pitch: int, ref_frame_pitch: int, dis_ptr: int, dis_row_pitch: int,
                                dis_frame_pitch: int, shape, n_frames: int):
         """The same for two clips of planes of `shape` = (height, width) in HBM (device pointers, pitches in bytes;
         pqa_edge_profiles_device)."""
-        sp = self._edge_spec(shape)
-        return self._profile_split(self._plane_call_resident("edge_profiles", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch,
-                                                                               dis_frame_pitch), n_frames, sp,
-                                                             self._lines_out(n_frames, sp, N.EDGE_SUMS)), sp)
+        return self._profile_split(*self._plane_call_resident("edge_profiles", (ref_ptr, ref_row_pitch, ref_frame_pitch, dis_ptr, dis_row_pitch,
+                                                                                dis_frame_pitch), shape, n_frames))
 
     # -- colour-matrix alignment ---------------------------------------------------------------
     def _frame_list(self, frames, what: str):
         """(arrays kept alive, ctypes pointer array [n * 3], stride triple) of frames [Y, U, V] in host memory: packed copies
         unless every plane already has this engine's dtype, unit column stride and one row stride per plane kind"""
-        shapes = [self.plane_shape(p) for p in range(3)]
-        arrs = [[np.asarray(f[p]) for p in range(3)] for f in frames]
-        for i, f in enumerate(arrs):
-            for p in range(3):
-                if f[p].shape != shapes[p]:
-                    raise ValueError(f"{what} frame {i} plane {p} is {f[p].shape}, engine is {shapes[p]}")
-        plain = all(a.dtype == self.dtype and a.strides[1] == a.itemsize and a.strides[0] == arrs[0][p].strides[0] and a.strides[0] > 0
-                    for f in arrs for p, a in enumerate(f))
-        if not plain:
-            arrs = [[np.ascontiguousarray(a, dtype=self.dtype) for a in f] for f in arrs]
-        ptrs = (C.c_void_p * max(3 * len(arrs), 1))()
-        for i, f in enumerate(arrs):
-            for p in range(3):
-                ptrs[3 * i + p] = f[p].ctypes.data
-        itemsize = np.dtype(self.dtype).itemsize
-        strides = (C.c_int64 * 3)(*[arrs[0][p].strides[0] if arrs else shapes[p][1] * itemsize for p in range(3)])
-        return arrs, ptrs, strides
+        return self._host_planes(frames, self.dtype, what + " frame {i} plane {p} is {got}, engine is {want}",
+                                 [self.plane_shape(p) for p in range(3)], k=3)
 
     def _colour_mask(self, lo, hi):
         top = (1 << self.bit_depth) - 1
         return (1 if lo is None else int(lo)), (top - 1 if hi is None else int(hi))
-
-    def _device_clip(self, ptrs, row_pitch, frame_pitch):
-        d = N.PqaDeviceClip()
-        for p in range(3):
-            d.plane[p], d.row_pitch[p], d.frame_pitch[p] = ptrs[p], row_pitch[p], frame_pitch[p]
-        return d
 
     def colour_moments(self, ref_frames, dis_frames, lo=None, hi=None) -> np.ndarray:
         """[n, 28] uint64: per frame pair the upper triangle, row-major, of the sum of z z^T over the chroma grid, z = (1, SYr, Ur,
@@ -1087,11 +955,11 @@ class FeatureEngine:
             raise N.PqaError(N.PQA_EINVAL, "colour_apply needs the chroma planes: n_planes must be 3")
         mm = (C.c_int32 * 12)(*[int(v) for v in np.asarray(m).reshape(12)])
         keep, sp, ss = self._frame_list(frames, "source")
-        out = [[np.empty(self.plane_shape(p), self.dtype) for p in range(3)] for _ in keep]
-        _, dp, ds = self._frame_list(out, "destination")
-        self._check(self.lib.pqa_colour_apply(self._ctx, C.byref(mm), sp, C.byref(ss), dp, C.byref(ds), len(keep)))
+        n = len(frames)
+        out, dp, ds = self._outputs(n, [self.plane_shape(p) for p in range(3)], self.dtype)
+        self._check(self.lib.pqa_colour_apply(self._ctx, C.byref(mm), sp, C.byref(ss), dp, C.byref(ds), n))
         del keep
-        return out
+        return [out[3 * i:3 * i + 3] for i in range(n)]
 
     def colour_apply_resident(self, m, src_ptrs, dst_ptrs, row_pitch, frame_pitch, n_frames: int):
         """The same for a clip in HBM into planes in HBM (device addresses of frame 0's planes; pitches in bytes per plane,

@@ -23,6 +23,27 @@ def test_header_and_binding_agree():
         assert int(re.search(name + r"\s*=\s*(\d+)", src).group(1)) == val
 
 
+def _parameter_counts():
+    """{name: number of parameters} of every prototype _declared() finds"""
+    src = open(os.path.join(ROOT, "include", "pqa_vmaf.h")).read()
+    protos = re.findall(r"PQA_API\s+[\w\s\*]+?\b(pqa_\w+)\s*\(([^()]*)\)\s*;", src)
+    return {name: 0 if params.strip() == "void" else params.count(",") + 1 for name, params in protos}
+
+
+def test_declared_argtypes_have_the_prototypes_length():
+    """a binding with one argument too few or too many still loads and still calls: the count is checked here"""
+    from pqa2_amd import _native as N
+    if not os.path.exists(N.LIB_PATH):
+        N.build()
+    lib = N.load()
+    counts = _parameter_counts()
+    assert sorted(counts) == _declared()
+    wrong = {name: (len(getattr(lib, name).argtypes), n) for name, n in counts.items()
+             if getattr(lib, name).argtypes is not None and len(getattr(lib, name).argtypes) != n}
+    assert not wrong, wrong
+    assert sum(getattr(lib, name).argtypes is not None for name in counts) >= 90      # the check is not empty
+
+
 def test_library_exports_every_declared_symbol():
     from pqa2_amd import _native as N
     if not os.path.exists(N.LIB_PATH):
